@@ -60,6 +60,9 @@ FLOP_PER_KALMAN_STEP_3STATE = 60   # SURVEY.md 8d's model (one predict + update 
 FLOP_PER_KALMAN_STEP = 16
 BYTES_PER_ROW = 24      # key_id u64 + flow_end_s i64 + value u64, read once
 BYTES_PER_ANOMALY = 40  # key_id, flow_end_s, throughput, algo_calc, stddev
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: all files together, .npy headers included
+NPY_HEADER_BYTES = 128        # np.save of a 1-D float64 array
+DUMP_SAMPLE_SEED = 20240917   # --dump-outputs: the rows kept when a result is larger than that
 
 CONFIGS = {   # BASELINE.json configs[1..4]
     "c2": dict(algos=("EWMA",), rows=100_000_000, keys=100_000, buckets=250, agg="svc"),
@@ -322,6 +325,25 @@ def row_orders_leg(eng, dev):
     return out
 
 
+def dump_outputs(path, outputs, prefix, limit):
+    """--dump-outputs: every result column of every algo as <path>/<prefix><ALGO>_<column>.npy (float64), the row count as
+    <ALGO>_n_rows.npy.  When the columns exceed `limit` bytes, the same seeded sample of row indices (sorted, so the engine's
+    (key_id, flow_end_s) order is kept) is taken from every column of an algo and saved as <ALGO>_sample_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    ncols = sum(len(cols) + 1 for cols in outputs.values())       # (+1: the sample index)
+    nfiles = ncols + len(outputs)                                   # (+ the row counts)
+    per_algo_rows = max(1, (limit - NPY_HEADER_BYTES * nfiles - 8 * len(outputs)) // (8 * ncols))
+    for algo, cols in outputs.items():
+        n = len(next(iter(cols.values())))
+        np.save(os.path.join(path, "%s%s_n_rows.npy" % (prefix, algo)), np.array([n], dtype=np.float64))
+        idx = None
+        if n > per_algo_rows:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, per_algo_rows, replace=False))
+            np.save(os.path.join(path, "%s%s_sample_index.npy" % (prefix, algo)), idx.astype(np.float64))
+        for name, v in cols.items():
+            np.save(os.path.join(path, "%s%s_%s.npy" % (prefix, algo, name)), (v if idx is None else v[idx]).astype(np.float64))
+
+
 def launch_ranks(n):
     """Run this same command line as `n` ranks of one node (python -m torch.distributed.run, one process per GPU) and return
     the launcher's exit code."""
@@ -373,6 +395,12 @@ def main():
     ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the CPU sample (0 = chosen from the host's core count)")
     ap.add_argument("--dump-rows", default="", help="after the timed region run the step once more and save every rank's anomaly rows "
                                                      "(GLOBAL key ids) to <path>.rank<r>.npz — used by the N-rank == 1-rank parity test")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the LAST timed step of the headline config returned (every column of its "
+                         "result, per algo, in the engine's (key_id, flow_end_s) order) as DIR/<ALGO>_<column>.npy in float64, plus "
+                         "DIR/<ALGO>_n_rows.npy; above %d MB in all a fixed seeded sample of the rows (DIR/<ALGO>_sample_index.npy). "
+                         "The inputs are the same on every run with the same arguments: two builds compare output for output"
+                         % (DUMP_LIMIT_BYTES // 10**6))
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -445,7 +473,8 @@ def main():
         eng.synth(rank * n, n, K * (world if ingest == "rows" else 1), T, seed=SYNTH_SEED + 977 * index, into=(key, tend, val))
         return key, tend, val
 
-    def run_config(algos, n, K, T, agg, steps, warmup, ingest="keys", host_input=False, hint=False, tables=1, same_columns_steps=0):
+    def run_config(algos, n, K, T, agg, steps, warmup, ingest="keys", host_input=False, hint=False, tables=1, same_columns_steps=0,
+                   keep_outputs=False):
         """W warm-up steps, then exactly `steps` timed steps between synchronisation points; one step = one job per algo.  With
         tables > 1 step i runs on table i mod tables (different rows in different device buffers: no step meets the columns of the
         step before it); same_columns_steps > 0 adds a second timed loop on table 0 alone."""
@@ -457,6 +486,7 @@ def main():
         rccl = {"allgather_us": [], "alltoall_ms": [], "alltoall_bytes": 0, "exchanges": 0}
 
         dump = {}
+        kept = {}
 
         prepared = {}   # the device-resident job of a step, its two C structs built once (TadEngine.prepare): a step = the bare tad_run call
 
@@ -469,7 +499,7 @@ def main():
                 prepared[(algo, ti)] = eng.prepare(algo, k_, t_, v_, K, agg_flow=agg, lattice=lattice, out="device")
             return prepared[(algo, ti)].run()
 
-        def step(ti=0):
+        def step(ti=0, keep=False):
             stats, glob = [], None
             key, tend, val = tabs[ti]
             if ingest == "rows":
@@ -505,7 +535,10 @@ def main():
                     h = res.to_host()
                     dump[algo] = {f: (h[f] * np.uint64(world) + np.uint64(rank) if f == "key_id" else h[f]).copy()
                                   for f in ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")}
-                res.close()
+                if keep:        # --dump-outputs: copied to the host after the timed region
+                    kept[algo] = res
+                else:
+                    res.close()
                 stats.append(st)
             return stats, glob
 
@@ -518,7 +551,7 @@ def main():
             pending[0] = None
             return g
 
-        def timed_loop(count, table_of):
+        def timed_loop(count, table_of, keep_last=False):
             acc = [{"ms_meta": 0.0, "ms_stage0": 0.0, "ms_scatter": 0.0, "ms_detect": 0.0, "ms_total": 0.0} for _ in algos]
             glob, stats = None, None
             if grouped:
@@ -526,7 +559,7 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for i in range(count):
-                stats, g2 = step(table_of(i))
+                stats, g2 = step(table_of(i), keep=keep_last and i == count - 1)
                 glob = g2 or glob
                 for a, st in zip(acc, stats):
                     for f in a:
@@ -568,8 +601,15 @@ def main():
         rccl["allgather_us"].clear()
         rccl["alltoall_ms"].clear()
         # (the LAST timed step lands on table 0, the default-seed table the CPU baseline and the parity tests use: `result` is comparable)
-        dt, dt_min_rank, acc, stats, g2 = timed_loop(steps, lambda i: (i + 1 - steps) % tables)
+        dt, dt_min_rank, acc, stats, g2 = timed_loop(steps, lambda i: (i + 1 - steps) % tables, keep_last=keep_outputs)
         glob = g2 or glob
+        outputs = None
+        if keep_outputs:
+            outputs = {}
+            for a in algos:
+                res = kept.pop(a)
+                outputs[a] = {f: v.copy() for f, v in res.to_host().items()}
+                res.close()
         same = None
         if same_columns_steps:
             sdt, _, _, _, _ = timed_loop(same_columns_steps, lambda i: 0)
@@ -585,7 +625,7 @@ def main():
             np.savez(args.dump_rows + ".rank%d.npz" % rank, **{"%s_%s" % (a, f): v for a in algos for f, v in dump[a].items()})
         del tabs
         return dict(dt=dt, dt_min_rank=dt_min_rank, stats=stats, acc=acc, glob=glob, steps=steps, warmup=warmup, n=n, K=K, T=T, agg=agg, algos=algos, cold=cold,
-                    tables=tables, same=same, rccl=rccl)
+                    tables=tables, same=same, rccl=rccl, outputs=outputs)
 
     def describe(r, host_input=False, ingest="keys", hint=False):
         """the JSON fields of one measured config (rank 0)"""
@@ -672,7 +712,9 @@ def main():
     multi = args.tables > 1 and not strong and not args.host_input and args.ingest == "keys" and cfg["rows"] <= 100_000_000 and not args.dump_rows
     head = run_config(cfg["algos"], cfg["rows"], cfg["keys"], cfg["buckets"], cfg["agg"], args.steps, args.warmup,
                       ingest=args.ingest, host_input=args.host_input, hint=args.hint_lattice, tables=args.tables if multi else 1,
-                      same_columns_steps=max(1, args.steps // 2) if multi else 0)
+                      same_columns_steps=max(1, args.steps // 2) if multi else 0, keep_outputs=bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, head["outputs"], "rank%d_" % rank if world > 1 else "", DUMP_LIMIT_BYTES // world)
     out = None
     if rank == 0:
         d = describe(head, args.host_input, args.ingest, args.hint_lattice)

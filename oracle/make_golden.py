@@ -79,6 +79,16 @@ def drop_golden():
             next(d.process("initial", "det-1", "ns/pod", "ingress", "day-%04d" % i, x))
         rows = list(d.end_partition())
         out["series"][name] = {"x": xs, "rows": [[r[5], r[6], r[7], int(r[8])] for r in rows]}   # avg, std, date, number
+    # tests/test_oracle_drop.py::test_against_the_live_reference_udf: its seeded series through the UDF (date = day index)
+    rng = np.random.default_rng(9)
+    out["live_udf"] = []
+    for n in (3, 50, 200, 600):
+        x = rng.poisson(20.0, size=n).astype(np.int64)
+        x[rng.integers(0, n)] *= 40
+        d = udf.DropDetection()
+        for i, v in enumerate(x):
+            next(d.process("initial", "id", "e", "egress", i, int(v)))
+        out["live_udf"].append({"x": [int(v) for v in x], "rows": [[r[5], r[6], r[7]] for r in d.end_partition()]})   # avg, std, date
     with open(os.path.join(OUT_DIR, "drop_outputs.json"), "w") as f:
         json.dump(out, f, indent=1)
     print("wrote drop_outputs.json:", {k: len(v["rows"]) for k, v in out["series"].items()})

@@ -47,17 +47,17 @@ def test_pairwise_sum_is_numpy_sum():
         assert dro.pairwise_sum(a) == float(np.add.reduce(a))
 
 
-@pytest.mark.skipif(not dro.reference_available(), reason="needs /root/reference (build container)")
-def test_against_the_live_reference_udf():
-    udf = dro.load_reference_udf()
+def test_against_the_live_reference_udf(drop_golden):
+    """The reference UDF's rows on these seeded series, recorded by oracle/make_golden.py running it (tests/golden/drop_outputs.json,
+    `live_udf`): the oracle must give the same anomalous days and the same mean / std bits."""
     rng = np.random.default_rng(9)
-    for n in (3, 50, 200, 600):
+    recorded = drop_golden["live_udf"]
+    assert len(recorded) == 4
+    for n, e in zip((3, 50, 200, 600), recorded):
         x = rng.poisson(20.0, size=n).astype(np.int64)
         x[rng.integers(0, n)] *= 40
-        d = udf.DropDetection()
-        for i, v in enumerate(x):
-            next(d.process("initial", "id", "e", "egress", i, int(v)))
-        rows = list(d.end_partition())
+        assert x.tolist() == e["x"], n
+        rows = e["rows"]
         mean, std, verdict = dro.drop_detection_series(x)
-        assert [r[7] for r in rows] == np.flatnonzero(verdict).tolist()
-        assert all(r[5] == mean and r[6] == std for r in rows)
+        assert [r[2] for r in rows] == np.flatnonzero(verdict).tolist()
+        assert all(r[0] == mean and r[1] == std for r in rows)

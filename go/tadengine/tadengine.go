@@ -657,6 +657,36 @@ func (s *State) Export(numKeys uint64) (n []uint32, avg, m2, ewma []float64, las
 	return
 }
 
+// Resize grows the state's key space to numKeys (tad_state_resize, ABI 13): the added keys are unseen.  Fewer keys than the state
+// holds is an error and leaves the state as it was; so does a failed allocation.
+func (s *State) Resize(numKeys uint64) error {
+	if rc := C.tad_state_resize(s.e.h, s.h, C.uint64_t(numKeys)); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return IllegalArgument{msg}
+		}
+		return fmt.Errorf("tad_state_resize: %s (code %d)", msg, int(rc))
+	}
+	return nil
+}
+
+// Import restores what Export returned (tad_state_import, ABI 13): one entry per key of the state in every slice; a key with
+// n == 0 is stored as unseen.  A detector that restarts picks up every key's running sigma and EWMA where it left off.
+func (s *State) Import(n []uint32, avg, m2, ewma []float64, lastT []int64) error {
+	k := len(n)
+	if len(avg) != k || len(m2) != k || len(ewma) != k || len(lastT) != k {
+		return errors.New("tadengine: state slices differ in length")
+	}
+	if k == 0 {
+		return errors.New("tadengine: empty state")
+	}
+	if rc := C.tad_state_import(s.e.h, s.h, (*C.uint32_t)(unsafe.Pointer(&n[0])), (*C.double)(unsafe.Pointer(&avg[0])), (*C.double)(unsafe.Pointer(&m2[0])),
+		(*C.double)(unsafe.Pointer(&ewma[0])), (*C.int64_t)(unsafe.Pointer(&lastT[0]))); rc != C.TAD_OK {
+		return fmt.Errorf("tad_state_import: %s (code %d)", C.GoString(C.tad_last_error(s.e.h)), int(rc))
+	}
+	return nil
+}
+
 // Progress feeds Status.CompletedStages / TotalStages (controller.go:426-453): the sum over the jobs in flight.
 func (e *Engine) Progress() (done, total int) {
 	var d, t C.int32_t

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define TAD_ABI_VERSION 12
+#define TAD_ABI_VERSION 13
 #define TAD_KEY_SKIP UINT64_MAX /* row (or its second key) does not take part */
 
 /* ---- error codes (0 = ok, negative = failure; text via tad_last_error) ---- */
@@ -351,13 +351,24 @@ int tad_host_free(tad_engine *e, void *ptr);
  * what the batch job computes over the concatenated table bit for bit (same operations in the same order): n, avg, m2
  * give its stddev_samp, ewma its last EWMA value.  A row not newer than its key's last_t is rejected
  * (TAD_ERR_INVALID_ARGUMENT) and the state is left untouched.  job->algo must be TAD_ALGO_EWMA, and cols->num_keys must
- * EQUAL the num_keys the state was created with (a batch addresses the state's whole key space; keys without rows in
- * the batch keep their state) — anything else is TAD_ERR_INVALID_ARGUMENT. */
+ * EQUAL the num_keys the state holds (a batch addresses the state's whole key space; keys without rows in the batch keep
+ * their state) — anything else is TAD_ERR_INVALID_ARGUMENT.
+ * ABI 13: a batch takes the Stage 0 rule of tad_run (tad_plan.sparse / sparse_sort / stage0 included), so second-resolution
+ * flowEndSeconds and a big key space are fine: a sparse batch (tad_stats.stage0_path 4 or 8) sorts its rows by (key, time)
+ * and walks the sorted points per key — no K x span grid, no length classes.  Its cost follows the batch's rows plus about
+ * 82 B of device traffic per state key; one key's serial chain is at most the batch's span in seconds.
+ * tad_state_resize (ABI 13) grows the key space (a host that numbers keys in order of first appearance appends new ids):
+ * new_num_keys >= num_keys, the added keys are unseen; smaller is TAD_ERR_INVALID_ARGUMENT; if allocation fails the state
+ * is unchanged.  tad_state_import (ABI 13) is the inverse of tad_state_export: HOST arrays of num_keys entries each, none
+ * NULL; a key with n == 0 is stored as unseen (all zeros), any other as seen — a state survives a restart of the host. */
 typedef struct tad_state tad_state;
 int tad_state_create(tad_engine *e, uint64_t num_keys, tad_state **out);
 void tad_state_destroy(tad_engine *e, tad_state *s);
 /* copies the state to HOST arrays of num_keys entries each (any may be NULL) */
 int tad_state_export(tad_engine *e, const tad_state *s, uint32_t *n, double *avg, double *m2, double *ewma, int64_t *last_t);
+int tad_state_resize(tad_engine *e, tad_state *s, uint64_t new_num_keys);
+int tad_state_import(tad_engine *e, tad_state *s, const uint32_t *n, const double *avg, const double *m2, const double *ewma,
+                     const int64_t *last_t);
 int tad_run_stream(tad_engine *e, tad_state *s, const tad_job *job, const tad_columns *cols, tad_mem out_memory,
                    tad_result **out);
 

@@ -419,11 +419,13 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
     // out by rank (tad_sparse.hip).  Chosen when the rows could fill at most 1/8 of a large grid, or the grid does not fit.
     const uint64_t slots_all = n * (has2 ? 2 : 1);
     // (first[], len[] and the class offsets are 32-bit indices into the sorted point list: 2^32 slots and beyond stay dense or fail cleanly)
-    bool sparse = !empty && !stream && K <= 0xFFFFFFFFull && slots_all < (1ull << 32) &&
+    // (a streaming batch takes the same rule: its dense grid is state keys x batch span, whatever the batch's rows)
+    bool sparse = !empty && K <= 0xFFFFFFFFull && slots_all < (1ull << 32) &&
                   (plan.sparse == 2 ||
                    (plan.sparse != 1 && (cells_overflow || need > e->ws_limit || (cells >= (1ull << 24) && slots_all < cells / 8))));
     Grid sparse_grid{};
     bool sp_part = false;
+    const unsigned long long *stream_poff = nullptr;   // a sparse streaming batch: key k's points at [poff[k], poff[k + 1]) of the sorted list
     if (sparse && use_kh) {
       // the sparse sort plans LDS rounds of exactly known sizes from the histogram (k_ss_plan): only pass A's own count is trusted with that
       kh_rejected = true;
@@ -502,44 +504,64 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       }
       const uint64_t P = runs_tmax[0];    // the filtered-out slots sort last and the reduction drops them
       const unsigned int tmax = (unsigned int)runs_tmax[1];
-      cells = K * (uint64_t)tmax;
-      need = cells * 17 + (jp.algo == TAD_ALGO_ARIMA ? cells * 80 + (1ull << 22) : (jp.algo == TAD_ALGO_DROP ? cells * 8 : 0));
-      // Skewed series lengths (one key with a day of seconds next to many short-lived ones): K x Tmax does not fit although the
-      // points do.  The keys are split into length classes that run as jobs of their own (run_sparse_classes).
-      if (P && depth == 0 && (need > e->ws_limit || plan.sparse_classes == 1)) {
+      if (stream) {
+        // A streaming batch builds no rank grid and takes no length classes: k_stream_points walks the sorted unique list
+        // (e->sp_comp_a / e->sp_val_a) itself, from per-key point offsets.  Its cost follows the batch's points plus the state.
         if (sp_part) {
           launch_sparse_compact(s, spl, e->sp_temp.p, static_cast<const unsigned long long *>(e->sp_comp_b.p), static_cast<const unsigned long long *>(e->sp_val_b.p), ucomp, uval);
           launch_sparse_tmax(s, ucomp, slots_all, d_runs, static_cast<uint32_t *>(e->sp_first.p), reinterpret_cast<unsigned int *>(d_runs + 1));
         }
-        HIP_TRY(e, hipMemcpyAsync(e->ctr_host, ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, s));
-        HIP_TRY(e, hipStreamSynchronize(s));
-        const DevCounters c0 = *e->ctr_host;
-        if (c0.err & DEV_ERR_KEY_RANGE)
-          return fail(e, TAD_ERR_KEY_RANGE, "a key id is >= num_keys (%llu) and is not TAD_KEY_SKIP", (unsigned long long)K);
-        if (c0.err & DEV_ERR_OFF_LATTICE) {
-          if (lat_mode < 2) { lat_mode = (lat_mode == 0) ? 1 : 2; continue; }
-          return fail(e, TAD_ERR_HIP, "internal error: a row fell off the derived time lattice");
+        if ((rc = ensure_key_buffers(e, K)) != TAD_OK) return rc;
+        const size_t kpad = (size_t)((K + 3) & ~3ull);
+        if ((rc = ensure(e, e->sp_cls, kpad * 4 + (K + 1) * 8 + 64)) != TAD_OK) return rc;   // len u32[K] | poff u64[K + 1]
+        uint32_t *len = static_cast<uint32_t *>(e->sp_cls.p);
+        unsigned long long *poff = reinterpret_cast<unsigned long long *>(len + kpad);
+        HIP_TRY(e, hipMemsetAsync(len, 0, (size_t)K * 4, s));
+        launch_sparse_len(s, ucomp, P, static_cast<const uint32_t *>(e->sp_first.p), len);
+        launch_scan(s, len, poff, K, static_cast<unsigned long long *>(e->scan_scratch.p), nullptr);
+        stream_poff = poff;
+        sparse_grid = Grid{nullptr, nullptr, K, 0, nullptr};
+        HIP_TRY(e, hipEventRecord(e->ev[3], s));
+      } else {
+        cells = K * (uint64_t)tmax;
+        need = cells * 17 + (jp.algo == TAD_ALGO_ARIMA ? cells * 80 + (1ull << 22) : (jp.algo == TAD_ALGO_DROP ? cells * 8 : 0));
+        // Skewed series lengths (one key with a day of seconds next to many short-lived ones): K x Tmax does not fit although the
+        // points do.  The keys are split into length classes that run as jobs of their own (run_sparse_classes).
+        if (P && depth == 0 && (need > e->ws_limit || plan.sparse_classes == 1)) {
+          if (sp_part) {
+            launch_sparse_compact(s, spl, e->sp_temp.p, static_cast<const unsigned long long *>(e->sp_comp_b.p), static_cast<const unsigned long long *>(e->sp_val_b.p), ucomp, uval);
+            launch_sparse_tmax(s, ucomp, slots_all, d_runs, static_cast<uint32_t *>(e->sp_first.p), reinterpret_cast<unsigned int *>(d_runs + 1));
+          }
+          HIP_TRY(e, hipMemcpyAsync(e->ctr_host, ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, s));
+          HIP_TRY(e, hipStreamSynchronize(s));
+          const DevCounters c0 = *e->ctr_host;
+          if (c0.err & DEV_ERR_KEY_RANGE)
+            return fail(e, TAD_ERR_KEY_RANGE, "a key id is >= num_keys (%llu) and is not TAD_KEY_SKIP", (unsigned long long)K);
+          if (c0.err & DEV_ERR_OFF_LATTICE) {
+            if (lat_mode < 2) { lat_mode = (lat_mode == 0) ? 1 : 2; continue; }
+            return fail(e, TAD_ERR_HIP, "internal error: a row fell off the derived time lattice");
+          }
+          if (points_mode) return sparse_points_direct(e, n, c0.rows_used, L, P, ctr, out_memory, points_out);   // Stage 0 alone needs no grid
+          return run_sparse_classes(e, job, jp, op_max, n, c0.rows_used, K, L, P, tmax, out_memory, out);
         }
-        if (points_mode) return sparse_points_direct(e, n, c0.rows_used, L, P, ctr, out_memory, points_out);   // Stage 0 alone needs no grid
-        return run_sparse_classes(e, job, jp, op_max, n, c0.rows_used, K, L, P, tmax, out_memory, out);
+        if (need > e->ws_limit)
+          return fail(e, TAD_ERR_GRID_TOO_LARGE, "sparse point grid needs %llu bytes (%llu keys x longest series %u points) > workspace limit %llu",
+                      (unsigned long long)need, (unsigned long long)K, tmax, (unsigned long long)e->ws_limit);
+        if ((rc = ensure(e, e->grid_val, (cells ? cells : 1) * 8)) != TAD_OK) return rc;
+        if ((rc = ensure(e, e->grid_flag, cells ? cells : 1)) != TAD_OK) return rc;
+        if ((rc = ensure(e, e->sp_times, (cells ? cells : 1) * 8)) != TAD_OK) return rc;
+        sparse_grid = Grid{static_cast<unsigned long long *>(e->grid_val.p), static_cast<uint8_t *>(e->grid_flag.p), tmax ? K : 0, tmax,
+                           static_cast<const long long *>(e->sp_times.p)};
+        if (cells) {
+          HIP_TRY(e, hipMemsetAsync(sparse_grid.flag, 0, cells, s));
+          if (sp_part)
+            launch_sparse_place_staged(s, spl, e->sp_temp.p, static_cast<const unsigned long long *>(e->sp_comp_b.p), static_cast<const unsigned long long *>(e->sp_val_b.p),
+                                       reinterpret_cast<const uint32_t *>(uval), L.t0, sparse_grid, static_cast<long long *>(e->sp_times.p));
+          else
+            launch_sparse_place(s, ucomp, uval, P, static_cast<const uint32_t *>(e->sp_first.p), L.t0, sparse_grid, static_cast<long long *>(e->sp_times.p));
+        }
+        HIP_TRY(e, hipEventRecord(e->ev[3], s));
       }
-      if (need > e->ws_limit)
-        return fail(e, TAD_ERR_GRID_TOO_LARGE, "sparse point grid needs %llu bytes (%llu keys x longest series %u points) > workspace limit %llu",
-                    (unsigned long long)need, (unsigned long long)K, tmax, (unsigned long long)e->ws_limit);
-      if ((rc = ensure(e, e->grid_val, (cells ? cells : 1) * 8)) != TAD_OK) return rc;
-      if ((rc = ensure(e, e->grid_flag, cells ? cells : 1)) != TAD_OK) return rc;
-      if ((rc = ensure(e, e->sp_times, (cells ? cells : 1) * 8)) != TAD_OK) return rc;
-      sparse_grid = Grid{static_cast<unsigned long long *>(e->grid_val.p), static_cast<uint8_t *>(e->grid_flag.p), tmax ? K : 0, tmax,
-                         static_cast<const long long *>(e->sp_times.p)};
-      if (cells) {
-        HIP_TRY(e, hipMemsetAsync(sparse_grid.flag, 0, cells, s));
-        if (sp_part)
-          launch_sparse_place_staged(s, spl, e->sp_temp.p, static_cast<const unsigned long long *>(e->sp_comp_b.p), static_cast<const unsigned long long *>(e->sp_val_b.p),
-                                     reinterpret_cast<const uint32_t *>(uval), L.t0, sparse_grid, static_cast<long long *>(e->sp_times.p));
-        else
-          launch_sparse_place(s, ucomp, uval, P, static_cast<const uint32_t *>(e->sp_first.p), L.t0, sparse_grid, static_cast<long long *>(e->sp_times.p));
-      }
-      HIP_TRY(e, hipEventRecord(e->ev[3], s));
     }
     if (!sparse && cells_overflow) return fail(e, TAD_ERR_GRID_TOO_LARGE, "grid of %llu keys x %llu buckets overflows", (unsigned long long)K, (unsigned long long)L.nb);
     if (!sparse && need > e->ws_limit) {
@@ -653,8 +675,13 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       rows = *e->total_host;
     } else if (stream) {   // continue the per-key recurrences from the stored state; the next state stays a candidate
       if ((rc = ensure_key_buffers(e, g.K)) != TAD_OK) return rc;
-      launch_stream(s, g, L, jp.alpha, jp.all_points, false, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),
-                    static_cast<uint32_t *>(e->n_anom.p), nullptr, OutRows{}, ctr);
+      if (stream_poff)
+        launch_stream_points(s, static_cast<const unsigned long long *>(e->sp_comp_a.p), static_cast<const unsigned long long *>(e->sp_val_a.p), stream_poff,
+                             g.K, L.t0, jp.alpha, jp.all_points, false, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),
+                             static_cast<uint32_t *>(e->n_anom.p), nullptr, OutRows{}, ctr);
+      else
+        launch_stream(s, g, L, jp.alpha, jp.all_points, false, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),
+                      static_cast<uint32_t *>(e->n_anom.p), nullptr, OutRows{}, ctr);
       unsigned long long *off = static_cast<unsigned long long *>(e->off.p);
       launch_scan(s, static_cast<const uint32_t *>(e->n_anom.p), off, g.K, static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
       HIP_TRY(e, hipMemcpyAsync(e->tail_host, e->counters.p, kTailBytes, hipMemcpyDeviceToHost, s));
@@ -762,7 +789,11 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
 
     // ---- Stage 3: emit ----
     if ((rc = make_result(e, rows, jp.all_points, out_memory, &rp, &dev_rows, &dev_block)) != TAD_OK) return rc;
-    if (rows && stream)
+    if (rows && stream && stream_poff)
+      launch_stream_points(s, static_cast<const unsigned long long *>(e->sp_comp_a.p), static_cast<const unsigned long long *>(e->sp_val_a.p), stream_poff,
+                           g.K, L.t0, jp.alpha, jp.all_points, true, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),
+                           nullptr, static_cast<const unsigned long long *>(e->off.p), dev_rows, ctr);
+    else if (rows && stream)
       launch_stream(s, g, L, jp.alpha, jp.all_points, true, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),
                     nullptr, static_cast<const unsigned long long *>(e->off.p), dev_rows, ctr);
     else if (rows)
@@ -1127,6 +1158,69 @@ int tad_state_export(tad_engine *eng, const tad_state *st, uint32_t *n, double *
   if (m2) HIP_TRY(e, hipMemcpy(m2, v.m2, st->K * sizeof(double), hipMemcpyDeviceToHost));
   if (ewma) HIP_TRY(e, hipMemcpy(ewma, v.ewma, st->K * sizeof(double), hipMemcpyDeviceToHost));
   if (last_t) HIP_TRY(e, hipMemcpy(last_t, v.last_t, st->K * sizeof(long long), hipMemcpyDeviceToHost));
+  return TAD_OK;
+}
+
+int tad_state_resize(tad_engine *eng, tad_state *st, uint64_t new_num_keys) {
+  if (!eng || !st) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_resize: bad arguments");
+  std::lock_guard<std::mutex> state_lk(st->mu);   // (the order of tad_run_stream: the state, then a job context)
+  if (new_num_keys < st->K)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_resize: %llu keys < the %llu the state holds (a state only grows)",
+                (unsigned long long)new_num_keys, (unsigned long long)st->K);
+  if (new_num_keys == st->K) return TAD_OK;
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_resize: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  // both copies anew (the old ones stay the state's until everything succeeded); the added keys are unseen (all zeros)
+  tad_state grown;
+  grown.K = new_num_keys;
+  hipError_t r = hipSuccess;
+  for (int i = 0; i < 2 && r == hipSuccess; ++i) {
+    r = hipMalloc(&grown.block[i], state_bytes(new_num_keys));
+    if (r == hipSuccess) r = hipMemsetAsync(grown.block[i], 0, state_bytes(new_num_keys), e->stream);
+  }
+  if (r == hipSuccess) {
+    const StreamState a = state_view(st, st->cur), b = state_view(&grown, 0);
+    const size_t K = st->K;
+    r = hipMemcpyAsync(b.avg, a.avg, K * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(b.m2, a.m2, K * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(b.ewma, a.ewma, K * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(b.last_t, a.last_t, K * sizeof(long long), hipMemcpyDeviceToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(b.n, a.n, K * sizeof(uint32_t), hipMemcpyDeviceToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(b.seen, a.seen, K, hipMemcpyDeviceToDevice, e->stream);
+  }
+  if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+  if (r != hipSuccess) {
+    for (int i = 0; i < 2; ++i) if (grown.block[i]) hipFree(grown.block[i]);
+    return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_resize: %s (state unchanged)", hipGetErrorString(r));
+  }
+  for (int i = 0; i < 2; ++i) { hipFree(st->block[i]); st->block[i] = grown.block[i]; }
+  st->K = new_num_keys;
+  st->cur = 0;
+  return TAD_OK;
+}
+
+int tad_state_import(tad_engine *eng, tad_state *st, const uint32_t *n, const double *avg, const double *m2, const double *ewma, const int64_t *last_t) {
+  if (!eng || !st || !n || !avg || !m2 || !ewma || !last_t) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import: bad arguments");
+  std::lock_guard<std::mutex> state_lk(st->mu);
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_import: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  // the state's layout on the host (state_view), then one copy: a key with n == 0 is unseen and all zeros
+  const size_t K = st->K;
+  std::vector<unsigned char> h;
+  try { h.assign(state_bytes(K), 0); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
+  double *h_avg = reinterpret_cast<double *>(h.data()), *h_m2 = h_avg + K, *h_ewma = h_m2 + K;
+  long long *h_last = reinterpret_cast<long long *>(h_ewma + K);
+  uint32_t *h_n = reinterpret_cast<uint32_t *>(h_last + K);
+  unsigned char *h_seen = reinterpret_cast<unsigned char *>(h_n + K);
+  for (size_t k = 0; k < K; ++k) {
+    if (n[k] == 0) continue;
+    h_avg[k] = avg[k]; h_m2[k] = m2[k]; h_ewma[k] = ewma[k]; h_last[k] = last_t[k]; h_n[k] = n[k]; h_seen[k] = 1;
+  }
+  HIP_TRY(e, hipMemcpy(st->block[st->cur], h.data(), h.size(), hipMemcpyHostToDevice));
   return TAD_OK;
 }
 

@@ -241,6 +241,10 @@ struct StreamState {
 // emit == true: rows written from the OLD state `cur` at off[] (next is not touched)
 void launch_stream(hipStream_t s, Grid g, Lattice lat, double alpha, bool all_points, bool emit, StreamState cur, StreamState next,
                    uint32_t *n_anom, const unsigned long long *off, OutRows out, DevCounters *ctr);
+// the same over the sorted unique point list of a sparse batch (comp = key << 32 | (t - t0), val; key k's points at [poff[k], poff[k + 1]))
+void launch_stream_points(hipStream_t s, const unsigned long long *comp, const unsigned long long *val, const unsigned long long *poff, uint64_t K,
+                          int64_t t0, double alpha, bool all_points, bool emit, StreamState cur, StreamState next, uint32_t *n_anom,
+                          const unsigned long long *off, OutRows out, DevCounters *ctr);
 // EWMA value for every present point into calc[T][K] (series entry points)
 void launch_ewma_values(hipStream_t s, Grid g, double alpha, double *calc);
 

@@ -864,7 +864,63 @@ void launch_emit_points(hipStream_t s, Grid g, Lattice lat, const unsigned long 
 // EWMA recurrence from the key's stored state over its new points; verdict against the RUNNING stddev_samp.
 // EMIT = false counts (and produces the next state), EMIT = true replays from the old state and writes the rows.
 // The division stays a division here (n grows without bound, no reciprocal table); it rounds like div_by_count.
+// The per-point step is stream_step, shared with k_stream_points (the sparse batches): one source for the arithmetic.
 // ------------------------------------------------------------------------------------------------
+struct StreamAcc {
+  uint32_t n;
+  double cnt, avg, m2, e;
+  long long last_t;
+  bool seen;
+};
+
+__device__ __forceinline__ StreamAcc stream_load(const StreamState &cur, uint64_t k) {
+  const uint32_t n = cur.n[k];
+  return StreamAcc{n, (double)n, cur.avg[k], cur.m2[k], cur.ewma[k], cur.last_t[k], cur.seen[k] != 0};
+}
+
+__device__ __forceinline__ void stream_store(const StreamState &next, uint64_t k, const StreamAcc &a) {
+  next.n[k] = a.n; next.avg[k] = a.avg; next.m2[k] = a.m2; next.ewma[k] = a.e; next.last_t[k] = a.last_t; next.seen[k] = a.seen ? 1 : 0;
+}
+
+// one new point x at ts of one key (ts > last_t checked by the caller): returns the verdict, *sg = the running stddev_samp
+__device__ __forceinline__ bool stream_step(StreamAcc &a, double alpha, double one_minus, double x, long long ts, double *sg) {
+  a.cnt = a.cnt + 1.0;
+  a.n++;
+  const double d = x - a.avg;
+  const double dn = d / a.cnt;
+  a.avg = a.avg + dn;
+  a.m2 = a.m2 + d * (d - dn);
+  a.e = one_minus * a.e + alpha * x;
+  const bool has_sigma = a.n >= 2;
+  *sg = has_sigma ? sqrt(a.m2 / (a.cnt - 1.0)) : 0.0;
+  a.last_t = ts;
+  a.seen = true;
+  return has_sigma && fabs(x - a.e) > *sg;
+}
+
+__device__ __forceinline__ void stream_row(OutRows out, unsigned long long pos, uint64_t k, long long ts, double x, double e, double sg,
+                                           bool all, bool verdict) {
+  out.key_id[pos] = k;
+  out.flow_end_s[pos] = ts;
+  out.throughput[pos] = x;
+  out.algo_calc[pos] = e;
+  out.stddev[pos] = sg;
+  if (all) out.anomaly[pos] = verdict ? 1 : 0;
+}
+
+// count pass: the wavefront's points / keys / errors into the job counters
+__device__ __forceinline__ void stream_counters(unsigned long long my_pts, unsigned my_key, uint32_t err, DevCounters *ctr) {
+  for (int d = 32; d >= 1; d >>= 1) {
+    my_pts += __shfl_down(my_pts, d);
+    my_key += __shfl_down(my_key, d);
+    err |= __shfl_down(err, d);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (my_key) { atomicAdd(&ctr->n_points, my_pts); atomicAdd(&ctr->n_keys, (unsigned long long)my_key); }
+    if (err) atomicOr(&ctr->err, err);
+  }
+}
+
 template <bool EMIT, bool ALL>
 __global__ __launch_bounds__(kBlock) void k_stream(Grid g, Lattice L, double alpha, StreamState cur, StreamState next,
                                                    uint32_t *__restrict__ n_anom, const unsigned long long *__restrict__ off,
@@ -874,62 +930,31 @@ __global__ __launch_bounds__(kBlock) void k_stream(Grid g, Lattice L, double alp
   unsigned my_key = 0;
   uint32_t err = 0;
   if (k < g.K) {
-    uint32_t n = cur.n[k];
-    double cnt = (double)n, avg = cur.avg[k], m2 = cur.m2[k], e = cur.ewma[k];
-    long long last_t = cur.last_t[k];
-    bool seen = cur.seen[k] != 0;
+    StreamAcc st = stream_load(cur, k);
     const double one_minus = 1.0 - alpha;
     unsigned long long pos = EMIT ? off[k] : 0ull;
     uint32_t a = 0, fresh = 0;
     walk_series(g, k, [&](uint64_t t, uint8_t fl, unsigned long long raw) {
       if (!(fl & FLAG_PRESENT)) return;
       const long long ts = (long long)(L.t0 + (int64_t)t * L.step);
-      if (seen && ts <= last_t) { err |= DEV_ERR_LATE_ROW; return; }
+      if (st.seen && ts <= st.last_t) { err |= DEV_ERR_LATE_ROW; return; }
       const double x = (double)raw;
-      cnt = cnt + 1.0;
-      n++;
-      const double d = x - avg;
-      const double dn = d / cnt;
-      avg = avg + dn;
-      m2 = m2 + d * (d - dn);
-      e = one_minus * e + alpha * x;
-      const bool has_sigma = n >= 2;
-      const double sg = has_sigma ? sqrt(m2 / (cnt - 1.0)) : 0.0;
-      const bool verdict = has_sigma && fabs(x - e) > sg;
-      last_t = ts;
-      seen = true;
+      double sg;
+      const bool verdict = stream_step(st, alpha, one_minus, x, ts, &sg);
       fresh++;
       if (ALL || verdict) {
-        if (EMIT) {
-          out.key_id[pos] = k;
-          out.flow_end_s[pos] = ts;
-          out.throughput[pos] = x;
-          out.algo_calc[pos] = e;
-          out.stddev[pos] = sg;
-          if (ALL) out.anomaly[pos] = verdict ? 1 : 0;
-          pos++;
-        }
+        if (EMIT) stream_row(out, pos++, k, ts, x, st.e, sg, ALL, verdict);
         a++;
       }
     });
     if (!EMIT) {
-      next.n[k] = n; next.avg[k] = avg; next.m2[k] = m2; next.ewma[k] = e; next.last_t[k] = last_t; next.seen[k] = seen ? 1 : 0;
+      stream_store(next, k, st);
       n_anom[k] = a;
       my_pts = fresh;
       my_key = fresh > 0;
     }
   }
-  if (!EMIT) {
-    for (int d = 32; d >= 1; d >>= 1) {
-      my_pts += __shfl_down(my_pts, d);
-      my_key += __shfl_down(my_key, d);
-      err |= __shfl_down(err, d);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      if (my_key) { atomicAdd(&ctr->n_points, my_pts); atomicAdd(&ctr->n_keys, (unsigned long long)my_key); }
-      if (err) atomicOr(&ctr->err, err);
-    }
-  }
+  if (!EMIT) stream_counters(my_pts, my_key, err, ctr);
 }
 
 void launch_stream(hipStream_t s, Grid g, Lattice lat, double alpha, bool all_points, bool emit, StreamState cur, StreamState next,
@@ -937,6 +962,66 @@ void launch_stream(hipStream_t s, Grid g, Lattice lat, double alpha, bool all_po
   if (g.K == 0) return;
   const int blocks = (int)((g.K + kBlock - 1) / kBlock);
 #define TAD_STREAM(E, A) hipLaunchKernelGGL((k_stream<E, A>), dim3(blocks), dim3(kBlock), 0, s, g, lat, alpha, cur, next, n_anom, off, out, ctr)
+  if (emit) { if (all_points) TAD_STREAM(true, true); else TAD_STREAM(true, false); }
+  else { if (all_points) TAD_STREAM(false, true); else TAD_STREAM(false, false); }
+#undef TAD_STREAM
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_stream_points — the streaming EWMA of a SPARSE batch: k_stream over the sorted unique point list of the sparse Stage 0
+// (tad_sparse.hip) instead of a grid.  comp[i] = key << 32 | (t - t0), val[i] = the aggregated value, (key, t) ascending and
+// unique; key k owns points [poff[k], poff[k + 1]).  One lane = one key, stream_step for every point: the same operations in
+// the same order as k_stream and the batch job, so the state stays bit-identical to theirs.  Points are unique seconds, so a
+// key's serial chain in one batch is at most the batch's span in seconds (3600 steps for an hourly batch), and only a key's
+// FIRST point can be late (the rest are newer than it).  A batch costs its points plus one state read / write per key:
+// the state's 37 B (x2: cur and next), n_anom / poff / off and their scans — about 82 B per state key.
+// ------------------------------------------------------------------------------------------------
+template <bool EMIT, bool ALL>
+__global__ __launch_bounds__(kBlock) void k_stream_points(const unsigned long long *__restrict__ comp, const unsigned long long *__restrict__ val,
+                                                          const unsigned long long *__restrict__ poff, uint64_t K, int64_t t0, double alpha,
+                                                          StreamState cur, StreamState next, uint32_t *__restrict__ n_anom,
+                                                          const unsigned long long *__restrict__ off, OutRows out, DevCounters *ctr) {
+  const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  unsigned long long my_pts = 0;
+  unsigned my_key = 0;
+  uint32_t err = 0;
+  if (k < K) {
+    StreamAcc st = stream_load(cur, k);
+    const double one_minus = 1.0 - alpha;
+    const unsigned long long p0 = poff[k], p1 = poff[k + 1];
+    unsigned long long pos = EMIT ? off[k] : 0ull;
+    uint32_t a = 0;
+    if (p1 > p0 && st.seen && (long long)(t0 + (int64_t)(comp[p0] & 0xffffffffull)) <= st.last_t) {
+      err |= DEV_ERR_LATE_ROW;   // the state is not advanced: the batch fails as a whole
+    } else {
+      for (unsigned long long i = p0; i < p1; ++i) {
+        const long long ts = (long long)(t0 + (int64_t)(comp[i] & 0xffffffffull));
+        const double x = (double)val[i];
+        double sg;
+        const bool verdict = stream_step(st, alpha, one_minus, x, ts, &sg);
+        if (ALL || verdict) {
+          if (EMIT) stream_row(out, pos++, k, ts, x, st.e, sg, ALL, verdict);
+          a++;
+        }
+      }
+    }
+    if (!EMIT) {
+      stream_store(next, k, st);
+      n_anom[k] = a;
+      my_pts = p1 - p0;
+      my_key = p1 > p0;
+    }
+  }
+  if (!EMIT) stream_counters(my_pts, my_key, err, ctr);
+}
+
+void launch_stream_points(hipStream_t s, const unsigned long long *comp, const unsigned long long *val, const unsigned long long *poff, uint64_t K,
+                          int64_t t0, double alpha, bool all_points, bool emit, StreamState cur, StreamState next, uint32_t *n_anom,
+                          const unsigned long long *off, OutRows out, DevCounters *ctr) {
+  if (K == 0) return;
+  const int blocks = (int)((K + kBlock - 1) / kBlock);
+#define TAD_STREAM(E, A) hipLaunchKernelGGL((k_stream_points<E, A>), dim3(blocks), dim3(kBlock), 0, s, comp, val, poff, K, t0, alpha, cur, next, \
+                                            n_anom, off, out, ctr)
   if (emit) { if (all_points) TAD_STREAM(true, true); else TAD_STREAM(true, false); }
   else { if (all_points) TAD_STREAM(false, true); else TAD_STREAM(false, false); }
 #undef TAD_STREAM

@@ -272,6 +272,22 @@ class TadState:
                                                                                              ("n", "avg", "m2", "ewma", "last_t"))))
         return out
 
+    def resize(self, num_keys):
+        """Grow the key space to num_keys (tad_state_resize): the added keys are unseen; fewer keys than now is an error."""
+        self._engine._check(self._engine._lib.tad_state_resize(self._engine._h, self._h, int(num_keys)))
+        self.num_keys = int(num_keys)
+
+    def load(self, state):
+        """Restore what export() returned (tad_state_import): one entry per key of this state; keys with n == 0 are unseen."""
+        K = self.num_keys
+        cols = []
+        for f, dt in (("n", np.uint32), ("avg", np.float64), ("m2", np.float64), ("ewma", np.float64), ("last_t", np.int64)):
+            a = np.ascontiguousarray(state[f], dtype=dt)
+            if a.shape != (K,):
+                raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "load: %s has %d entries, the state holds %d keys" % (f, a.size, K))
+            cols.append(a)
+        self._engine._check(self._engine._lib.tad_state_import(self._engine._h, self._h, *(a.ctypes.data for a in cols)))
+
     def close(self):
         if self._h is not None and self._engine._h is not None:
             self._engine._lib.tad_state_destroy(self._engine._h, self._h)
@@ -412,22 +428,24 @@ class TadEngine:
         return TadState(self, num_keys)
 
     def run_stream(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, emit_all=False, out="host",
-                   alpha=0.0, job_id="", num_keys=None):
+                   alpha=0.0, job_id="", num_keys=None, key_id2=None):
+        """One batch of the streaming EWMA detector on `state` (tad_run_stream).  key_id2: the second key column of pod mode."""
         pk, n, dev, keep1 = _as_column(key_id, np.uint64)
         pt, nt, dev_t, keep2 = _as_column(flow_end_s, np.int64)
         pv, nv, dev_v, keep3 = _as_column(value, np.uint64)
-        if nt != n or nv != n or dev_t != dev or dev_v != dev:
+        pk2, nk2, dev_k2, keep4 = _as_column(key_id2, np.uint64)
+        if nt != n or nv != n or dev_t != dev or dev_v != dev or (key_id2 is not None and (nk2 != n or dev_k2 != dev)):
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "columns must have equal length and live in the same memory")
         job = capi.Job(algo=capi.TAD_ALGO["EWMA"], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
                        flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
-        cols = capi.Columns(n_rows=n, key_id=pk, flow_end_s=pt, value=pv, num_keys=state.num_keys if num_keys is None else int(num_keys),
+        cols = capi.Columns(n_rows=n, key_id=pk, key_id2=pk2, flow_end_s=pt, value=pv, num_keys=state.num_keys if num_keys is None else int(num_keys),
                             memory=capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST)
         if lattice is not None:
             cols.t0, cols.step, cols.n_buckets = int(lattice[0]), int(lattice[1]), int(lattice[2])
         res = C.POINTER(capi.Result)()
         rc = self._lib.tad_run_stream(self._h, state._h, C.byref(job), C.byref(cols),
                                       capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
-        del keep1, keep2, keep3
+        del keep1, keep2, keep3, keep4
         self._check(rc)
         return TadResult(self, res)
 

@@ -23,6 +23,7 @@ import (
 	"errors"
 	"fmt"
 	"runtime"
+	"sync"
 	"unsafe"
 )
 
@@ -126,14 +127,21 @@ type Job struct {
 }
 
 // Columns is one batch of flow rows after dictionary encoding; all slices have the same length.
+// The key and the time columns may instead come as 32-bit slices, read by the engine at that width (tad.h, TAD_FLAG_KEY_U32 /
+// TAD_FLAG_TIME_U32): KeyID32 / KeyID2_32 replace KeyID / KeyID2 (TAD_KEY_SKIP32 = the row does not take part; NumKeys < 2^32 - 1),
+// FlowEndS32 / FlowStartS32 replace FlowEndS / FlowStartS (ClickHouse DateTime: unsigned epoch seconds).  Set one form per column pair.
 type Columns struct {
-	KeyID       []uint64
-	KeyID2      []uint64 // pod mode only (inbound/outbound UNION ALL), else nil
-	FlowEndS    []int64
-	FlowStartS  []int64 // nil unless StartTime is set
-	Value       []uint64
-	NumKeys     uint64
-	KeyHist     *KeyHist // optional: FactorizeHist's by-product for THIS batch (Stage 0 then does not count the key column again)
+	KeyID        []uint64
+	KeyID2       []uint64 // pod mode only (inbound/outbound UNION ALL), else nil
+	FlowEndS     []int64
+	FlowStartS   []int64 // nil unless StartTime is set
+	Value        []uint64
+	NumKeys      uint64
+	KeyHist      *KeyHist // optional: FactorizeHist's by-product for THIS batch (Stage 0 then does not count the key column again)
+	KeyID32      []uint32 // optional 32-bit form of KeyID
+	KeyID2_32    []uint32 // optional 32-bit form of KeyID2
+	FlowEndS32   []uint32 // optional 32-bit form of FlowEndS
+	FlowStartS32 []uint32 // optional 32-bit form of FlowStartS
 }
 
 // KeyHist is tad_key_hist (tad.h, ABI 12): the key-bin histogram of a factorised batch per Stage-0 workgroup.  The bins live in device
@@ -172,26 +180,77 @@ type Stats struct {
 // cColumn copies a Go slice into C memory: cgo forbids handing Go pointers nested in a C struct, and the
 // library stages host columns to the GPU anyway.  A production binding would read ClickHouse blocks
 // straight into C/pinned buffers instead of Go slices.
-func cColumn[T uint64 | int64](s []T) unsafe.Pointer {
+func cColumn[T uint64 | int64 | uint32](s []T) unsafe.Pointer {
 	if len(s) == 0 {
 		return nil
 	}
-	n := C.size_t(len(s) * 8)
+	var z T
+	n := C.size_t(len(s) * int(unsafe.Sizeof(z)))
 	p := C.malloc(n)
 	C.memcpy(p, unsafe.Pointer(&s[0]), n)
 	return p
+}
+
+var narrowOnce sync.Once
+var narrowOK bool
+
+// columnBuffers copies the batch's columns into C memory: key, key2, flow end, flow start, value (nil where absent), the row count
+// and the narrow-column flags of tad_job.  32-bit slices are only handed over once the library has said it reads them
+// (tad_features): a library that predates the flags would ignore them and misread the columns.
+func columnBuffers(cols Columns) ([]unsafe.Pointer, int, C.uint32_t, error) {
+	if (cols.KeyID32 != nil && cols.KeyID != nil) || (cols.FlowEndS32 != nil && cols.FlowEndS != nil) ||
+		(cols.KeyID2_32 != nil && cols.KeyID2 != nil) || (cols.FlowStartS32 != nil && cols.FlowStartS != nil) ||
+		(cols.KeyID2_32 != nil && cols.KeyID32 == nil) || (cols.KeyID2 != nil && cols.KeyID32 != nil) ||
+		(cols.FlowStartS32 != nil && cols.FlowEndS32 == nil) || (cols.FlowStartS != nil && cols.FlowEndS32 != nil) {
+		return nil, 0, 0, errors.New("tadengine: set either the 64-bit or the 32-bit form of the key (time) columns")
+	}
+	var flags C.uint32_t
+	if cols.KeyID32 != nil || cols.FlowEndS32 != nil {
+		narrowOnce.Do(func() { narrowOK = C.tad_features()&C.TAD_FEATURE_NARROW_COLUMNS != 0 })
+		if !narrowOK {
+			return nil, 0, 0, errors.New("tadengine: libtad_mi355x.so does not read 32-bit columns (TAD_FEATURE_NARROW_COLUMNS)")
+		}
+	}
+	n := len(cols.KeyID)
+	bufs := []unsafe.Pointer{cColumn(cols.KeyID), cColumn(cols.KeyID2), cColumn(cols.FlowEndS), cColumn(cols.FlowStartS), cColumn(cols.Value)}
+	if cols.KeyID32 != nil {
+		n = len(cols.KeyID32)
+		bufs[0], bufs[1] = cColumn(cols.KeyID32), cColumn(cols.KeyID2_32)
+		flags |= C.TAD_FLAG_KEY_U32
+	}
+	if cols.FlowEndS32 != nil {
+		bufs[2], bufs[3] = cColumn(cols.FlowEndS32), cColumn(cols.FlowStartS32)
+		flags |= C.TAD_FLAG_TIME_U32
+	}
+	lens := []int{len(cols.KeyID2) + len(cols.KeyID2_32), len(cols.FlowEndS) + len(cols.FlowEndS32), len(cols.FlowStartS) + len(cols.FlowStartS32), len(cols.Value)}
+	for i, m := range lens {
+		if m != n && (i == 1 || i == 3 || m != 0) {
+			freeBuffers(bufs)
+			return nil, 0, 0, errors.New("tadengine: columns differ in length")
+		}
+	}
+	return bufs, n, flags, nil
+}
+
+func freeBuffers(bufs []unsafe.Pointer) {
+	for _, p := range bufs {
+		if p != nil {
+			C.free(p)
+		}
+	}
 }
 
 // Run replaces one SparkApplication run (anomaly_detection.py:647-710).  An empty result means the caller
 // writes the "NO ANOMALY DETECTED" sentinel row (anomaly_detection.py:395-420).
 func (e *Engine) Run(job Job, cols Columns) ([]Row, Stats, error) {
 	var st Stats
-	n := len(cols.KeyID)
-	if len(cols.FlowEndS) != n || len(cols.Value) != n || (cols.KeyID2 != nil && len(cols.KeyID2) != n) ||
-		(cols.FlowStartS != nil && len(cols.FlowStartS) != n) {
-		return nil, st, errors.New("tadengine: columns differ in length")
+	bufs, n, narrow, err := columnBuffers(cols)
+	if err != nil {
+		return nil, st, err
 	}
+	defer freeBuffers(bufs)
 	var cj C.tad_job
+	cj.flags = narrow
 	cj.algo = C.tad_algo(job.Algo)
 	cj.agg_flow = C.tad_agg_flow(job.AggFlow)
 	cj.value_op = C.TAD_OP_AUTO
@@ -208,14 +267,6 @@ func (e *Engine) Run(job Job, cols Columns) ([]Row, Stats, error) {
 	cc.n_rows = C.uint64_t(n)
 	cc.num_keys = C.uint64_t(cols.NumKeys)
 	cc.memory = C.TAD_MEM_HOST
-	bufs := []unsafe.Pointer{cColumn(cols.KeyID), cColumn(cols.KeyID2), cColumn(cols.FlowEndS), cColumn(cols.FlowStartS), cColumn(cols.Value)}
-	defer func() {
-		for _, p := range bufs {
-			if p != nil {
-				C.free(p)
-			}
-		}
-	}()
 	cc.key_id = (*C.uint64_t)(bufs[0])
 	cc.key_id2 = (*C.uint64_t)(bufs[1])
 	cc.flow_end_s = (*C.int64_t)(bufs[2])
@@ -263,24 +314,21 @@ type Point struct {
 }
 
 func (e *Engine) Aggregate(job Job, cols Columns) ([]Point, error) {
+	bufs, n, narrow, err := columnBuffers(cols)
+	if err != nil {
+		return nil, err
+	}
+	defer freeBuffers(bufs)
 	var cj C.tad_job
+	cj.flags = narrow
 	cj.agg_flow = C.tad_agg_flow(job.AggFlow)
 	cj.value_op = C.TAD_OP_AUTO
 	cj.start_time = C.int64_t(job.StartTime)
 	cj.end_time = C.int64_t(job.EndTime)
 	var cc C.tad_columns
-	n := len(cols.KeyID)
 	cc.n_rows = C.uint64_t(n)
 	cc.num_keys = C.uint64_t(cols.NumKeys)
 	cc.memory = C.TAD_MEM_HOST
-	bufs := []unsafe.Pointer{cColumn(cols.KeyID), cColumn(cols.KeyID2), cColumn(cols.FlowEndS), cColumn(cols.FlowStartS), cColumn(cols.Value)}
-	defer func() {
-		for _, p := range bufs {
-			if p != nil {
-				C.free(p)
-			}
-		}
-	}()
 	cc.key_id = (*C.uint64_t)(bufs[0])
 	cc.key_id2 = (*C.uint64_t)(bufs[1])
 	cc.flow_end_s = (*C.int64_t)(bufs[2])
@@ -597,11 +645,13 @@ func (s *State) Close() {
 // RunStream aggregates ONE new batch and continues every key's recurrences over its new points (tad_run_stream): the rows are the points
 // with |x - ewma| > the running stddev_samp.  cols.NumKeys must equal the state's key count; job.Algo must be EWMA.
 func (s *State) RunStream(job Job, cols Columns) ([]Row, error) {
-	n := len(cols.KeyID)
-	if len(cols.FlowEndS) != n || len(cols.Value) != n {
-		return nil, errors.New("tadengine: columns differ in length")
+	bufs, n, narrow, err := columnBuffers(cols)
+	if err != nil {
+		return nil, err
 	}
+	defer freeBuffers(bufs)
 	var cj C.tad_job
+	cj.flags = narrow
 	cj.algo = C.tad_algo(job.Algo)
 	cj.agg_flow = C.tad_agg_flow(job.AggFlow)
 	cj.value_op = C.TAD_OP_AUTO
@@ -609,17 +659,9 @@ func (s *State) RunStream(job Job, cols Columns) ([]Row, error) {
 	cc.n_rows = C.uint64_t(n)
 	cc.num_keys = C.uint64_t(cols.NumKeys)
 	cc.memory = C.TAD_MEM_HOST
-	bufs := []unsafe.Pointer{cColumn(cols.KeyID), cColumn(cols.FlowEndS), cColumn(cols.Value)}
-	defer func() {
-		for _, p := range bufs {
-			if p != nil {
-				C.free(p)
-			}
-		}
-	}()
 	cc.key_id = (*C.uint64_t)(bufs[0])
-	cc.flow_end_s = (*C.int64_t)(bufs[1])
-	cc.value = (*C.uint64_t)(bufs[2])
+	cc.flow_end_s = (*C.int64_t)(bufs[2])
+	cc.value = (*C.uint64_t)(bufs[4])
 	var res *C.tad_result
 	if rc := C.tad_run_stream(s.e.h, s.h, &cj, &cc, C.TAD_MEM_HOST, &res); rc != C.TAD_OK {
 		msg := C.GoString(C.tad_last_error(s.e.h))

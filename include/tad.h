@@ -66,6 +66,12 @@ typedef enum { TAD_MEM_HOST = 0, TAD_MEM_DEVICE = 1 } tad_mem;
 /* tad_job.flags */
 #define TAD_FLAG_EMIT_ALL_POINTS 1u /* result = every point (plotDF before the filter of :394),
                                        with its verdict in tad_result.anomaly; for inspection/tests */
+#define TAD_FLAG_KEY_U32  2u /* key_id / key_id2 point to uint32_t[n_rows]; TAD_KEY_SKIP32 = row does not take part (tad_columns) */
+#define TAD_FLAG_TIME_U32 4u /* flow_end_s / flow_start_s point to uint32_t[n_rows]: DateTime, unsigned epoch seconds (tad_columns) */
+#define TAD_KEY_SKIP32 UINT32_MAX
+
+/* tad_features(): what this build of the library understands beyond TAD_ABI_VERSION */
+#define TAD_FEATURE_NARROW_COLUMNS 1u /* TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 are honoured */
 
 typedef struct tad_engine tad_engine; /* opaque; one per GPU; runs up to max_jobs_in_flight jobs concurrently (ABI 12) */
 
@@ -142,7 +148,25 @@ typedef struct {
 } tad_key_hist;
 
 /* One columnar batch of flow rows (the columns the SQL of :507-614 touches, after the host's
- * dictionary encoding).  All arrays have n_rows entries; memory says where they live. */
+ * dictionary encoding).  All arrays have n_rows entries; memory says where they live.
+ *
+ * Narrow columns (tad_job.flags): every column below is 8 bytes wide by default.  The data a host holds is often narrower —
+ * flowEndSeconds / flowStartSeconds are ClickHouse DateTime (UInt32, create_table.sh:34), dictionary codes and dense key ids fit
+ * 32 bits — and Stage 0 is bound by the bytes it reads, so the engine reads such columns at their own width instead of asking the
+ * host to widen them first:
+ *   TAD_FLAG_KEY_U32:  key_id and key_id2 point to uint32_t[n_rows]; TAD_KEY_SKIP32 marks a row (side) that does not take part;
+ *                      num_keys must be < 2^32 - 1 (else TAD_ERR_INVALID_ARGUMENT).
+ *   TAD_FLAG_TIME_U32: flow_end_s and flow_start_s point to uint32_t[n_rows], unsigned epoch seconds, ZERO-extended
+ *                      (4000000000, year 2096, is a valid time, not a negative one).
+ * Either flag, both or neither; host or device memory; tad_run, tad_aggregate and tad_run_stream.  value stays UInt64, and
+ * start_time / end_time, the lattice fields (t0, step) and every output (tad_result, tad_points, the stream state) stay 64-bit.
+ * Host columns are staged at their own width.  Results are bit-identical to the same table passed in 8-byte columns.  The
+ * vector loads of Stage 0 need 16-byte aligned columns whatever their width; a narrow column that is only 4-byte aligned is read
+ * row by row, as an 8-byte column that is only 8-byte aligned is.  The struct below is unchanged (the pointers are typed for the
+ * default); cast a narrow column's pointer.
+ * A library older than these flags ignores them and would misread the columns: check tad_features() & TAD_FEATURE_NARROW_COLUMNS
+ * before setting either flag (an older library does not export tad_features at all, so a cgo link or dlsym fails instead).
+ * tad_shard_rows, tad_factorize and tad_widen_column do not take narrow columns: their outputs stay 8 bytes wide. */
 typedef struct {
   uint64_t n_rows;
   const uint64_t *key_id;       /* dense id of the row's key, < num_keys, or TAD_KEY_SKIP */
@@ -228,6 +252,8 @@ typedef struct {
 
 /* ---- engine life cycle ---- */
 int tad_abi_version(void);
+/* TAD_FEATURE_* bits this library understands; needs no device */
+int tad_features(void);
 int tad_engine_create(const tad_engine_opts *opts, tad_engine **out);
 void tad_engine_destroy(tad_engine *e);
 /* Replace the engine's plan overrides (NULL = all zero); serialised with the jobs, takes effect with the next one. */

@@ -16,6 +16,9 @@ TAD_AGG = {"": 0, None: 0, "None": 0, "pod": 1, "svc": 2, "external": 3}
 TAD_OP = {"auto": 0, "max": 1, "sum": 2}
 TAD_MEM_HOST, TAD_MEM_DEVICE = 0, 1
 TAD_FLAG_EMIT_ALL_POINTS = 1
+TAD_FLAG_KEY_U32, TAD_FLAG_TIME_U32 = 2, 4   # narrow input columns: uint32 key ids / uint32 DateTime seconds (tad.h, tad_columns)
+TAD_KEY_SKIP32 = (1 << 32) - 1
+TAD_FEATURE_NARROW_COLUMNS = 1               # tad_features() bit: the library honours the two flags above
 
 
 class Plan(C.Structure):
@@ -103,6 +106,7 @@ class Points(C.Structure):
 # every symbol include/tad.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "tad_abi_version": (C.c_int, []),
+    "tad_features": (C.c_int, []),
     "tad_engine_create": (C.c_int, [C.POINTER(EngineOpts), C.POINTER(C.c_void_p)]),
     "tad_engine_destroy": (None, [C.c_void_p]),
     "tad_engine_set_plan": (C.c_int, [C.c_void_p, C.POINTER(Plan)]),

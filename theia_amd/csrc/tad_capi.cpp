@@ -186,12 +186,13 @@ int finish_result(JobCtx *e, ResultPriv *rp, uint64_t rows, bool with_anomaly, R
   return TAD_OK;
 }
 
-int stage_column(JobCtx *e, DevBuf &buf, const void *src, uint64_t n, tad_mem mem, const void **dev) {
+// width: bytes per row of the column (8, or 4 for a narrow key / time column): a host column crosses PCIe at its own width
+int stage_column(JobCtx *e, DevBuf &buf, const void *src, uint64_t n, tad_mem mem, const void **dev, uint64_t width = 8) {
   if (!src) { *dev = nullptr; return TAD_OK; }
   if (mem == TAD_MEM_DEVICE) { *dev = src; return TAD_OK; }
-  int rc = ensure(e, buf, n * 8);
+  int rc = ensure(e, buf, n * width);
   if (rc != TAD_OK) return rc;
-  HIP_TRY(e, hipMemcpyAsync(buf.p, src, n * 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(buf.p, src, n * width, hipMemcpyHostToDevice, e->stream));
   *dev = buf.p;
   return TAD_OK;
 }
@@ -243,6 +244,8 @@ int run_job(tad_engine *eng, const tad_job *job, const tad_columns *cols, tad_me
     return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run: key_id, flow_end_s and value columns are required");
   if (cols->n_rows > 0 && cols->num_keys == 0)
     return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run: num_keys is 0 but there are rows");
+  if ((job->flags & TAD_FLAG_KEY_U32) && cols->num_keys >= 0xFFFFFFFFull)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run: TAD_FLAG_KEY_U32 needs num_keys < 2^32 - 1 (TAD_KEY_SKIP32 is the skip marker)");
   if (cols->n_buckets > 0 && cols->step < 1)
     return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run: lattice hint needs step >= 1");
   if (job->ewma_alpha < 0.0 || job->ewma_alpha > 1.0 || job->dbscan_eps < 0.0 || job->dbscan_min_samples < 0 || job->arima_maxiter < 0 ||
@@ -286,11 +289,14 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
   RowFilter rf{job->start_time, job->end_time};
 
   int rc;
+  // narrow input columns (tad.h, tad_columns): read at their own width by the Stage-0 kernels, nothing is widened first
+  const int cw = ((job->flags & TAD_FLAG_KEY_U32) ? kColKey32 : 0) | ((job->flags & TAD_FLAG_TIME_U32) ? kColTime32 : 0);
+  const uint64_t kw = (cw & kColKey32) ? 4 : 8, tw = (cw & kColTime32) ? 4 : 8;
   const void *d_key, *d_key2, *d_te, *d_ts, *d_val;
-  if ((rc = stage_column(e, e->in_key, cols->key_id, n, cols->memory, &d_key)) != TAD_OK) return rc;
-  if ((rc = stage_column(e, e->in_key2, cols->key_id2, n, cols->memory, &d_key2)) != TAD_OK) return rc;
-  if ((rc = stage_column(e, e->in_te, cols->flow_end_s, n, cols->memory, &d_te)) != TAD_OK) return rc;
-  if ((rc = stage_column(e, e->in_ts, cols->flow_start_s, n, cols->memory, &d_ts)) != TAD_OK) return rc;
+  if ((rc = stage_column(e, e->in_key, cols->key_id, n, cols->memory, &d_key, kw)) != TAD_OK) return rc;
+  if ((rc = stage_column(e, e->in_key2, cols->key_id2, n, cols->memory, &d_key2, kw)) != TAD_OK) return rc;
+  if ((rc = stage_column(e, e->in_te, cols->flow_end_s, n, cols->memory, &d_te, tw)) != TAD_OK) return rc;
+  if ((rc = stage_column(e, e->in_ts, cols->flow_start_s, n, cols->memory, &d_ts, tw)) != TAD_OK) return rc;
   if ((rc = stage_column(e, e->in_val, cols->value, n, cols->memory, &d_val)) != TAD_OK) return rc;
 
   if ((rc = ensure(e, e->counters, kTailBytes)) != TAD_OK) return rc;
@@ -354,7 +360,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       // pass A: lattice partials + per-workgroup key-bin histogram in one read of the key/time columns
       if ((rc = ensure(e, e->binhist, (size_t)pl.G * pl.nbins * 4)) != TAD_OK) return rc;
       hist_sampled = launch_meta_hist(s, (const uint64_t *)d_key, (const uint64_t *)d_key2, (const int64_t *)d_te, (const int64_t *)d_ts, n, K, rf,
-                                      pl, static_cast<MetaPartial *>(e->meta.p), static_cast<uint32_t *>(e->binhist.p), ctr,
+                                      pl, static_cast<MetaPartial *>(e->meta.p), static_cast<uint32_t *>(e->binhist.p), ctr, cw,
                                       // small regions (many keys: C4 has ~50 records per workgroup and 128-key block) make pass C's walk
                                       // over the regions cost more than the sampled pass A saves: sample only when a region of a
                                       // 128-key block is expected to hold a few hundred records
@@ -372,7 +378,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       meta_blocks = (int)((n + 255) / 256);
       if (meta_blocks > kMetaBlocks) meta_blocks = kMetaBlocks;
       launch_meta(s, (const uint64_t *)d_key, (const uint64_t *)d_key2, (const int64_t *)d_te, (const int64_t *)d_ts, n, rf,
-                  static_cast<MetaPartial *>(e->meta.p), meta_blocks);
+                  static_cast<MetaPartial *>(e->meta.p), meta_blocks, cw);
     }
     if (!hinted && !empty) {
       HIP_TRY(e, hipMemcpyAsync(e->meta_host, e->meta.p, sizeof(MetaPartial) * meta_blocks, hipMemcpyDeviceToHost, s));
@@ -476,13 +482,13 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
                             static_cast<const MetaPartial *>(e->meta.p), n, slots, e->slices.p, Grid{});
         // (no overflow list: a value that does not fit the record raises DEV_ERR_OVERFLOW_LIST and the LSD sort redoes the job)
         launch_partition(s, (const uint64_t *)d_key, (const uint64_t *)d_key2, (const int64_t *)d_te, (const int64_t *)d_ts, (const uint64_t *)d_val, n, K,
-                         rf, L, spl, offs32, part_start, e->recs.p, nullptr, dev_ovf_count(e), 0, ctr, nullptr, nullptr);
+                         rf, L, spl, offs32, part_start, e->recs.p, nullptr, dev_ovf_count(e), 0, ctr, nullptr, nullptr, cw);
         launch_sparse_sort(s, e->recs.p, part_start, binhist, spl, K, L.step, op_max,
                            ucomp, static_cast<unsigned long long *>(e->sp_comp_b.p), static_cast<unsigned long long *>(e->sp_val_b.p),
                            reinterpret_cast<uint32_t *>(uval), e->sp_temp.p, d_runs, ctr);
       } else if (launch_sparse_group(s, (const uint64_t *)d_key, (const uint64_t *)d_key2, (const int64_t *)d_te, (const int64_t *)d_ts, (const uint64_t *)d_val, n, K,
                                      rf, L.t0, span, op_max, ucomp, uval, static_cast<unsigned long long *>(e->sp_comp_b.p),
-                                     static_cast<unsigned long long *>(e->sp_val_b.p), e->sp_temp.p, tb, d_runs, ctr) != 0)
+                                     static_cast<unsigned long long *>(e->sp_val_b.p), e->sp_temp.p, tb, d_runs, ctr, cw) != 0)
         return fail(e, TAD_ERR_HIP, "sparse Stage 0: sort / reduce failed");
       if (depth == 0) e->sp_by_partition = sp_part;
       // first[] / the longest series from the device-resident point count; then ONE round trip for both numbers
@@ -636,7 +642,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       }
       HIP_TRY(e, hipEventRecord(e->ev[2], s));
       launch_partition(s, (const uint64_t *)d_key, (const uint64_t *)d_key2, (const int64_t *)d_te, (const int64_t *)d_ts,
-                       (const uint64_t *)d_val, n, K, rf, L, pl, offs32, part_start, e->recs.p, ovf, ovf_count, kOverflowCap, ctr, fin, ovf_keys);
+                       (const uint64_t *)d_val, n, K, rf, L, pl, offs32, part_start, e->recs.p, ovf, ovf_count, kOverflowCap, ctr, fin, ovf_keys, cw);
       HIP_TRY(e, hipEventRecord(e->ev[3], s));
       launch_tile_aggregate(s, e->recs.p, part_start, pl, slots, e->slices.p, g, op_max, ovf, ovf_count, kOverflowCap,
                             hist_sampled ? offs32 : nullptr, fin, settle);
@@ -648,7 +654,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       HIP_TRY(e, hipEventRecord(e->ev[2], s));
       if (!empty)
         launch_scatter(s, (const uint64_t *)d_key, (const uint64_t *)d_key2, (const int64_t *)d_te, (const int64_t *)d_ts,
-                       (const uint64_t *)d_val, n, rf, L, g, op_max, ctr);
+                       (const uint64_t *)d_val, n, rf, L, g, op_max, ctr, cw);
       HIP_TRY(e, hipEventRecord(e->ev[3], s));
     }
     HIP_TRY(e, hipEventRecord(e->ev[5], s));
@@ -1014,6 +1020,7 @@ int run_sparse_classes(JobCtx *e, const tad_job *job, const JobParams &jp, bool 
 
   // one job per class (filters are applied, every (key, time) is unique: the operator no longer matters)
   tad_job sub = *job;
+  sub.flags &= ~(TAD_FLAG_KEY_U32 | TAD_FLAG_TIME_U32);   // the class columns are the engine's own 8-byte ones
   sub.start_time = 0;
   sub.end_time = 0;
   sub.value_op = op_max ? TAD_OP_MAX : TAD_OP_SUM;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "tad.h"
 
@@ -56,6 +57,10 @@ struct DevCounters {
   uint32_t pad;
 };
 
+// Widths of the input columns a Stage-0 launcher reads (tad.h, TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32): 0 = every column 8 bytes.
+// The kernels take them as template parameters (K32, T32) and decode on load; everything after the loads is width-independent.
+enum : int { kColKey32 = 1, kColTime32 = 2 };
+
 struct RowFilter {
   int64_t start_time;  // 0 = unset
   int64_t end_time;    // 0 = unset
@@ -79,11 +84,11 @@ inline void allow_big_lds(const void *kernel, size_t bytes) {
 
 // ---- launchers (tad_kernels.hip / tad_dbscan.hip / tad_arima.hip / tad_synth.hip) ----
 int launch_meta(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
-                const int64_t *t_start, uint64_t n, RowFilter f, MetaPartial *partials, int n_blocks);
+                const int64_t *t_start, uint64_t n, RowFilter f, MetaPartial *partials, int n_blocks, int cw = 0);
 
 void launch_scatter(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
                     const int64_t *t_start, const uint64_t *value, uint64_t n, RowFilter f,
-                    Lattice lat, Grid g, bool op_max, DevCounters *ctr);
+                    Lattice lat, Grid g, bool op_max, DevCounters *ctr, int cw = 0);
 
 // a / b for an integer-valued b >= 1, given y = RN(1 / b): Markstein's correction steps on the FMA unit.
 // q0 = RN(a y); r = a - b q (exact in one FMA); q' = RN(q + r y) is the correctly rounded quotient once q is a
@@ -101,6 +106,36 @@ __device__ __forceinline__ double div_by_count(double a, double b, double y) {
 struct Moments { double n, mean, m2; };   // per-key / per-block (n, mean, M2) of the points
 
 #if defined(__HIPCC__)
+// ---- input columns at their own width (kColKey32 / kColTime32): the Stage-0 kernels keep their 8-byte pointer parameters (and their
+// argument layouts) and read a narrow column through these.  K32 / T32 = false is the plain 8-byte load, instruction for instruction.
+__device__ __forceinline__ uint64_t key_of32(uint32_t v) { return v == 0xFFFFFFFFu ? TAD_KEY_SKIP : (uint64_t)v; }   // TAD_KEY_SKIP32
+template <bool K32> __device__ __forceinline__ uint64_t ld_key(const uint64_t *p, uint64_t i) {
+  if constexpr (K32) return key_of32(reinterpret_cast<const uint32_t *>(p)[i]);
+  else return p[i];
+}
+template <bool T32> __device__ __forceinline__ int64_t ld_time(const int64_t *p, uint64_t i) {
+  if constexpr (T32) return (int64_t)(uint64_t)reinterpret_cast<const uint32_t *>(p)[i];   // DateTime: zero-extended
+  else return p[i];
+}
+// rows base + 2j and base + 2j + 1 with one load: 16 bytes of an 8-byte column, 8 bytes of a narrow one (base even, column 16-byte aligned)
+template <bool K32> __device__ __forceinline__ ulonglong2 ld_key2(const uint64_t *p, uint64_t base, uint64_t j) {
+  if constexpr (K32) { const uint2 v = reinterpret_cast<const uint2 *>(reinterpret_cast<const uint32_t *>(p) + base)[j]; return make_ulonglong2(key_of32(v.x), key_of32(v.y)); }
+  else return reinterpret_cast<const ulonglong2 *>(p + base)[j];
+}
+template <bool T32> __device__ __forceinline__ longlong2 ld_time2(const int64_t *p, uint64_t base, uint64_t j) {
+  if constexpr (T32) { const uint2 v = reinterpret_cast<const uint2 *>(reinterpret_cast<const uint32_t *>(p) + base)[j]; return make_longlong2((int64_t)v.x, (int64_t)v.y); }
+  else return reinterpret_cast<const longlong2 *>(p + base)[j];
+}
+// host: a launch with the column widths as template arguments: f(std::bool_constant<K32>, std::bool_constant<T32>)
+template <typename F> inline void with_widths(int cw, F &&f) {
+  switch (cw & (kColKey32 | kColTime32)) {
+    case 0: f(std::false_type{}, std::false_type{}); break;
+    case kColKey32: f(std::true_type{}, std::false_type{}); break;
+    case kColTime32: f(std::false_type{}, std::true_type{}); break;
+    default: f(std::true_type{}, std::true_type{}); break;
+  }
+}
+
 // (the per-key walks are HBM-latency bound: one lane = one key, 64 consecutive keys = one coalesced 512-byte access)
 // Walk one key's column of the time-major grid in time order, calling step(t, flag, raw_value) for every bucket.
 // The walk is a dependency chain per lane fed by HBM: it is software-pipelined — the loads of chunk c+1 are
@@ -354,7 +389,7 @@ bool part_plan_sparse(uint64_t K, uint64_t T, bool has2, PartPlan *pl);
 // Returns whether the histogram is sampled (only without a time-window filter and with 16-byte aligned columns).
 bool launch_meta_hist(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
                       const int64_t *t_start, uint64_t n, uint64_t K, RowFilter f, const PartPlan &pl,
-                      MetaPartial *partials, uint32_t *binhist, DevCounters *ctr, bool sample_hist);
+                      MetaPartial *partials, uint32_t *binhist, DevCounters *ctr, int cw, bool sample_hist);
 // offs32[G][nparts] (exclusive per-workgroup prefix inside each partition), total[nparts], part_start[nparts + 1]
 // sampled: the histogram is a sample -> region capacities (estimate + 6 sigma + margin); partials carry the sampling ratios
 // TWO launches (k_part_offsets, k_part_tail): also build the slice table of pass C in slice_mem (slice_table_bytes(slots, pl)) and zero
@@ -370,7 +405,7 @@ void launch_partition(hipStream_t s, const uint64_t *key, const uint64_t *key2, 
                       const int64_t *t_start, const uint64_t *value, uint64_t n, uint64_t K, RowFilter f,
                       Lattice L, const PartPlan &pl, const uint32_t *offs32, const unsigned long long *part_start,
                       void *recs, OverflowRec *ovf, unsigned long long *ovf_count, uint32_t ovf_cap, DevCounters *ctr,
-                      uint32_t *fin = nullptr, uint32_t *ovf_keys = nullptr);   // ovf_keys: bitmap (K bits, zeroed) of the keys with a value on the overflow list
+                      uint32_t *fin = nullptr, uint32_t *ovf_keys = nullptr, int cw = 0);   // ovf_keys: bitmap (K bits, zeroed) of the keys with a value on the overflow list
 // slots = record slots of the run (rows x keys per row); slice_mem = slice_table_bytes(slots, pl) bytes of device scratch
 size_t slice_table_bytes(uint64_t slots, const PartPlan &pl);
 void launch_tile_aggregate(hipStream_t s, const void *recs, const unsigned long long *part_start, const PartPlan &pl,
@@ -398,7 +433,7 @@ void launch_sparse_compact(hipStream_t s, const PartPlan &pl, void *temp, const 
 int launch_sparse_group(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end, const int64_t *t_start,
                         const uint64_t *value, uint64_t n, uint64_t K, RowFilter f, int64_t t0, uint64_t span, bool op_max, unsigned long long *comp_a,
                         unsigned long long *val_a, unsigned long long *comp_b, unsigned long long *val_b, void *temp, size_t temp_bytes,
-                        unsigned long long *num_runs, DevCounters *ctr);
+                        unsigned long long *num_runs, DevCounters *ctr, int cw = 0);
 // slots: upper bound of the points (grid size); the point count itself is read on the device (*P_dev)
 void launch_sparse_tmax(hipStream_t s, const unsigned long long *ucomp, uint64_t slots, const unsigned long long *P_dev, uint32_t *first, unsigned int *tmax);
 void launch_sparse_place(hipStream_t s, const unsigned long long *ucomp, const unsigned long long *uval, uint64_t P, const uint32_t *first,

@@ -60,16 +60,18 @@ __device__ __forceinline__ MetaAcc meta_shfl_down(const MetaAcc &a, int d) {
   return r;
 }
 
+template <bool T32 = false>
 __device__ __forceinline__ bool row_kept(int64_t te, const int64_t *t_start, uint64_t i, RowFilter f) {
   if (f.end_time != 0 && !(te < f.end_time)) return false;          // :584-586
-  if (f.start_time != 0 && t_start != nullptr && !(t_start[i] >= f.start_time)) return false;  // :581-583
+  if (f.start_time != 0 && t_start != nullptr && !(ld_time<T32>(t_start, i) >= f.start_time)) return false;  // :581-583
   return true;
 }
 
 // ------------------------------------------------------------------------------------------------
 // k_meta — derive the flowEndSeconds lattice (min, max, gcd of differences) of the rows that pass
-// the filters.  One read of the time column (+ key columns for TAD_KEY_SKIP).
+// the filters.  One read of the time column (+ key columns for TAD_KEY_SKIP).  K32 / T32: narrow key / time columns.
 // ------------------------------------------------------------------------------------------------
+template <bool K32 = false, bool T32 = false>
 __global__ __launch_bounds__(kBlock) void k_meta(const uint64_t *__restrict__ key,
                                                  const uint64_t *__restrict__ key2,
                                                  const int64_t *__restrict__ t_end,
@@ -78,10 +80,10 @@ __global__ __launch_bounds__(kBlock) void k_meta(const uint64_t *__restrict__ ke
   MetaAcc acc{0, 0, 0, 0, 0};
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    const int64_t te = t_end[i];
-    bool live = key[i] != TAD_KEY_SKIP;
-    if (key2 != nullptr) live = live || key2[i] != TAD_KEY_SKIP;
-    if (!live || !row_kept(te, t_start, i, f)) continue;
+    const int64_t te = ld_time<T32>(t_end, i);
+    bool live = ld_key<K32>(key, i) != TAD_KEY_SKIP;
+    if (key2 != nullptr) live = live || ld_key<K32>(key2, i) != TAD_KEY_SKIP;
+    if (!live || !row_kept<T32>(te, t_start, i, f)) continue;
     if (acc.used == 0) {
       acc.tmin = acc.tmax = acc.tref = te;
       acc.g = 0;
@@ -108,8 +110,10 @@ __global__ __launch_bounds__(kBlock) void k_meta(const uint64_t *__restrict__ ke
 }
 
 int launch_meta(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
-                const int64_t *t_start, uint64_t n, RowFilter f, MetaPartial *partials, int n_blocks) {
-  hipLaunchKernelGGL(k_meta, dim3(n_blocks), dim3(kBlock), 0, s, key, key2, t_end, t_start, n, f, partials);
+                const int64_t *t_start, uint64_t n, RowFilter f, MetaPartial *partials, int n_blocks, int cw) {
+  with_widths(cw, [&](auto k32, auto t32) {
+    hipLaunchKernelGGL((k_meta<k32(), t32()>), dim3(n_blocks), dim3(kBlock), 0, s, key, key2, t_end, t_start, n, f, partials);
+  });
   return 0;
 }
 
@@ -163,7 +167,7 @@ __device__ __forceinline__ void scatter_row(uint64_t k1, uint64_t k2, bool has2,
   }
 }
 
-template <bool OPMAX, bool VEC2>
+template <bool OPMAX, bool VEC2, bool K32 = false, bool T32 = false>
 __global__ __launch_bounds__(kBlock) void k_scatter(const uint64_t *__restrict__ key,
                                                     const uint64_t *__restrict__ key2,
                                                     const int64_t *__restrict__ t_end,
@@ -175,30 +179,27 @@ __global__ __launch_bounds__(kBlock) void k_scatter(const uint64_t *__restrict__
   const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const bool has2 = key2 != nullptr;
   if (VEC2) {
-    // 16-byte loads: two rows per lane per column, 1 KiB per wave-instruction.
+    // 16-byte loads: two rows per lane per column, 1 KiB per wave-instruction (8-byte loads of a narrow column).
     const uint64_t n2 = n >> 1;
-    const ulonglong2 *key_v = reinterpret_cast<const ulonglong2 *>(key);
-    const ulonglong2 *key2_v = reinterpret_cast<const ulonglong2 *>(key2);
-    const longlong2 *te_v = reinterpret_cast<const longlong2 *>(t_end);
     const ulonglong2 *val_v = reinterpret_cast<const ulonglong2 *>(value);
     for (uint64_t i = tid; i < n2; i += stride) {
-      const ulonglong2 k = key_v[i];
-      const longlong2 te = te_v[i];
+      const ulonglong2 k = ld_key2<K32>(key, 0, i);
+      const longlong2 te = ld_time2<T32>(t_end, 0, i);
       const ulonglong2 v = val_v[i];
       ulonglong2 k2 = make_ulonglong2(TAD_KEY_SKIP, TAD_KEY_SKIP);
-      if (has2) k2 = key2_v[i];
-      if (row_kept(te.x, t_start, 2 * i, f)) scatter_row<OPMAX>(k.x, k2.x, has2, te.x, v.x, L, g, err, used);
-      if (row_kept(te.y, t_start, 2 * i + 1, f)) scatter_row<OPMAX>(k.y, k2.y, has2, te.y, v.y, L, g, err, used);
+      if (has2) k2 = ld_key2<K32>(key2, 0, i);
+      if (row_kept<T32>(te.x, t_start, 2 * i, f)) scatter_row<OPMAX>(k.x, k2.x, has2, te.x, v.x, L, g, err, used);
+      if (row_kept<T32>(te.y, t_start, 2 * i + 1, f)) scatter_row<OPMAX>(k.y, k2.y, has2, te.y, v.y, L, g, err, used);
     }
     if ((n & 1) && tid == 0) {
       const uint64_t i = n - 1;
-      if (row_kept(t_end[i], t_start, i, f))
-        scatter_row<OPMAX>(key[i], has2 ? key2[i] : TAD_KEY_SKIP, has2, t_end[i], value[i], L, g, err, used);
+      if (row_kept<T32>(ld_time<T32>(t_end, i), t_start, i, f))
+        scatter_row<OPMAX>(ld_key<K32>(key, i), has2 ? ld_key<K32>(key2, i) : TAD_KEY_SKIP, has2, ld_time<T32>(t_end, i), value[i], L, g, err, used);
     }
   } else {
     for (uint64_t i = tid; i < n; i += stride) {
-      if (row_kept(t_end[i], t_start, i, f))
-        scatter_row<OPMAX>(key[i], has2 ? key2[i] : TAD_KEY_SKIP, has2, t_end[i], value[i], L, g, err, used);
+      if (row_kept<T32>(ld_time<T32>(t_end, i), t_start, i, f))
+        scatter_row<OPMAX>(ld_key<K32>(key, i), has2 ? ld_key<K32>(key2, i) : TAD_KEY_SKIP, has2, ld_time<T32>(t_end, i), value[i], L, g, err, used);
     }
   }
   // one counter update per wave
@@ -215,7 +216,7 @@ __global__ __launch_bounds__(kBlock) void k_scatter(const uint64_t *__restrict__
 
 void launch_scatter(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
                     const int64_t *t_start, const uint64_t *value, uint64_t n, RowFilter f,
-                    Lattice lat, Grid g, bool op_max, DevCounters *ctr) {
+                    Lattice lat, Grid g, bool op_max, DevCounters *ctr, int cw) {
   if (n == 0) return;
   auto aligned16 = [](const void *p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const bool vec = aligned16(key) && aligned16(key2) && aligned16(t_end) && aligned16(value) && n >= 2;
@@ -223,11 +224,13 @@ void launch_scatter(hipStream_t s, const uint64_t *key, const uint64_t *key2, co
   int blocks = (int)((work + kBlock - 1) / kBlock);
   if (blocks > 256 * 16) blocks = 256 * 16;  // grid-stride the rest (guide: ~8-16 blocks per CU)
   if (blocks < 1) blocks = 1;
+  with_widths(cw, [&](auto k32, auto t32) {
 #define TAD_LAUNCH_SCATTER(OPMAX, VEC) \
-  hipLaunchKernelGGL((k_scatter<OPMAX, VEC>), dim3(blocks), dim3(kBlock), 0, s, key, key2, t_end, t_start, value, n, f, lat, g, ctr)
-  if (op_max) { if (vec) TAD_LAUNCH_SCATTER(true, true); else TAD_LAUNCH_SCATTER(true, false); }
-  else        { if (vec) TAD_LAUNCH_SCATTER(false, true); else TAD_LAUNCH_SCATTER(false, false); }
+  hipLaunchKernelGGL((k_scatter<OPMAX, VEC, k32(), t32()>), dim3(blocks), dim3(kBlock), 0, s, key, key2, t_end, t_start, value, n, f, lat, g, ctr)
+    if (op_max) { if (vec) TAD_LAUNCH_SCATTER(true, true); else TAD_LAUNCH_SCATTER(true, false); }
+    else        { if (vec) TAD_LAUNCH_SCATTER(false, true); else TAD_LAUNCH_SCATTER(false, false); }
 #undef TAD_LAUNCH_SCATTER
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1049,6 +1052,6 @@ void launch_ewma_values(hipStream_t s, Grid g, double alpha, double *calc) {
 }
 
 // one kernel of this translation unit: tad_engine_create resolves it so that the unit's code object is loaded before the first job
-const void *code_anchor_kernels() { return reinterpret_cast<const void *>(&k_meta); }
+const void *code_anchor_kernels() { return reinterpret_cast<const void *>(&k_meta<>); }
 
 }  // namespace tad

@@ -18,7 +18,8 @@ namespace tad {
 static constexpr int kSpBlock = 256;
 
 // composite sort key of every (row, key) slot: key << 32 | (t - t0); slots that are filtered out get the key field K (one past the
-// last valid key: they sort behind every point and the reduction drops them)
+// last valid key: they sort behind every point and the reduction drops them).  K32 / T32: narrow key / time columns.
+template <bool K32 = false, bool T32 = false>
 __global__ __launch_bounds__(kSpBlock) void k_sparse_keys(const uint64_t *__restrict__ key, const uint64_t *__restrict__ key2,
                                                          const int64_t *__restrict__ t_end, const int64_t *__restrict__ t_start,
                                                          const uint64_t *__restrict__ value, uint64_t n, uint64_t K, RowFilter f, int64_t t0,
@@ -30,14 +31,14 @@ __global__ __launch_bounds__(kSpBlock) void k_sparse_keys(const uint64_t *__rest
   // grid-stride: the job counter gets ONE atomic per workgroup — one per wavefront of a 1e8-row table is 1.5e6 atomics on one address,
   // which serialise at ~12 ns each (the kernel took 18.8 ms for 4 GB of traffic, profiles/r4_v2_sparse_scale_kernel_stats.csv)
   for (uint64_t i = (uint64_t)blockIdx.x * kSpBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kSpBlock) {
-    const int64_t te = t_end[i];
+    const int64_t te = ld_time<T32>(t_end, i);
     bool kept = true;
     if (f.end_time != 0 && !(te < f.end_time)) kept = false;                                       // anomaly_detection.py:584-586
-    if (f.start_time != 0 && t_start != nullptr && !(t_start[i] >= f.start_time)) kept = false;    // :581-583
+    if (f.start_time != 0 && t_start != nullptr && !(ld_time<T32>(t_start, i) >= f.start_time)) kept = false;    // :581-583
     const uint64_t dt = (uint64_t)te - (uint64_t)t0;
     const uint64_t v = value[i];
     for (int h = 0; h < nk; ++h) {
-      const uint64_t k = h == 0 ? key[i] : key2[i];
+      const uint64_t k = h == 0 ? ld_key<K32>(key, i) : ld_key<K32>(key2, i);
       unsigned long long c = (unsigned long long)K << 32;
       if (kept && k != TAD_KEY_SKIP) {
         if (k >= K) err |= DEV_ERR_KEY_RANGE;
@@ -492,7 +493,7 @@ size_t sparse_sort_temp_bytes(uint64_t slots) { return rs_temp_layout(slots).tot
 int launch_sparse_group(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end, const int64_t *t_start,
                         const uint64_t *value, uint64_t n, uint64_t K, RowFilter f, int64_t t0, uint64_t span, bool op_max, unsigned long long *comp_a,
                         unsigned long long *val_a, unsigned long long *comp_b, unsigned long long *val_b, void *temp, size_t temp_bytes,
-                        unsigned long long *num_runs, DevCounters *ctr) {
+                        unsigned long long *num_runs, DevCounters *ctr, int cw) {
   const uint64_t slots = n * (key2 != nullptr ? 2 : 1);
   if (slots == 0 || slots >= (1ull << 32) || K > 0xFFFFFFFFull) return -1;
   if (span > 0xFFFFFFFFull) span = 0xFFFFFFFFull;
@@ -509,8 +510,10 @@ int launch_sparse_group(hipStream_t s, const uint64_t *key, const uint64_t *key2
   unsigned long long *ca = (pl.np & 1) ? comp_a : comp_b, *va = (pl.np & 1) ? val_a : val_b;
   unsigned long long *cb = (pl.np & 1) ? comp_b : comp_a, *vb = (pl.np & 1) ? val_b : val_a;
   const uint64_t kb = (n + kSpBlock - 1) / kSpBlock;
-  hipLaunchKernelGGL(k_sparse_keys, dim3((unsigned)(kb < 8192 ? kb : 8192)), dim3(kSpBlock), 0, s, key, key2, t_end, t_start, value, n, K,
-                     f, t0, span, ca, va, ctr);
+  with_widths(cw, [&](auto k32, auto t32) {
+    hipLaunchKernelGGL((k_sparse_keys<k32(), t32()>), dim3((unsigned)(kb < 8192 ? kb : 8192)), dim3(kSpBlock), 0, s, key, key2, t_end, t_start,
+                       value, n, K, f, t0, span, ca, va, ctr);
+  });
   const size_t lds = (size_t)kRsTile * 16 + kRsRadix * 8 + (size_t)kRsWaves * kRsRadix * 4 + kRsRadix * 4 + 64;
   allow_big_lds(reinterpret_cast<const void *>(k_rs_scatter), lds);
   for (int p = 0; p < pl.np; ++p) {

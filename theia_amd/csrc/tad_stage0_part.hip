@@ -204,7 +204,8 @@ __device__ __forceinline__ void hist_row(MetaAcc &a, uint32_t *hist, uint64_t k1
 #endif
 static constexpr uint32_t kSampleMask = TAD_SAMPLE_MASK;
 
-template <bool VEC, bool HAS2, bool SAMPLE_H>
+// K32 / T32: narrow key / time columns (8-byte loads of a row pair instead of 16-byte ones: the same rows are read, and sampled, as at 8 bytes)
+template <bool VEC, bool HAS2, bool SAMPLE_H, bool K32 = false, bool T32 = false>
 __global__ __launch_bounds__(kPartThreads) void k_meta_hist(const uint64_t *__restrict__ key,
                                                             const uint64_t *__restrict__ key2,
                                                             const int64_t *__restrict__ t_end,
@@ -228,6 +229,15 @@ __global__ __launch_bounds__(kPartThreads) void k_meta_hist(const uint64_t *__re
     const ulonglong2 *kv = reinterpret_cast<const ulonglong2 *>(key + lo);
     const ulonglong2 *k2v = reinterpret_cast<const ulonglong2 *>(key2 + (HAS2 ? lo : 0));
     const longlong2 *tv = reinterpret_cast<const longlong2 *>(t_end + lo);
+    // row pair j of the chunk (a narrow column: one 8-byte load)
+    auto kpair = [&](const ulonglong2 *wide, const uint64_t *col, uint64_t j) -> ulonglong2 {
+      if constexpr (K32) return ld_key2<true>(col, lo, j);
+      else return wide[j];
+    };
+    auto tpair = [&](uint64_t j) -> longlong2 {
+      if constexpr (T32) return ld_time2<true>(t_end, lo, j);
+      else return tv[j];
+    };
     constexpr int U = 4;
     // Without a time-window filter the time column is only needed for (min, max, sampled gcd): read it for one
     // iteration in sixteen plus both ends of the chunk (time-ordered tables have their extremes there) and let the
@@ -255,16 +265,16 @@ __global__ __launch_bounds__(kPartThreads) void k_meta_hist(const uint64_t *__re
       longlong2 t[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        k[u] = kv[i + u * kPartThreads];
-        k2[u] = HAS2 ? k2v[i + u * kPartThreads] : make_ulonglong2(TAD_KEY_SKIP, TAD_KEY_SKIP);
+        k[u] = kpair(kv, key, i + u * kPartThreads);
+        k2[u] = HAS2 ? kpair(k2v, key2, i + u * kPartThreads) : make_ulonglong2(TAD_KEY_SKIP, TAD_KEY_SKIP);
       }
       if (with_t) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) t[u] = tv[i + u * kPartThreads];
+        for (int u = 0; u < U; ++u) t[u] = tpair(i + u * kPartThreads);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const uint64_t r = lo + 2 * (i + u * kPartThreads);
-          const int64_t ts0 = has_ts ? t_start[r] : 0, ts1 = has_ts ? t_start[r + 1] : 0;
+          const int64_t ts0 = has_ts ? ld_time<T32>(t_start, r) : 0, ts1 = has_ts ? ld_time<T32>(t_start, r + 1) : 0;
           meta_row(acc, hist, k[u].x, k2[u].x, t[u].x, p_time_kept(t[u].x, ts0, has_ts, f), K, shift_bin, weight);
           meta_row(acc, hist, k[u].y, k2[u].y, t[u].y, p_time_kept(t[u].y, ts1, has_ts, f), K, shift_bin, weight);
         }
@@ -278,25 +288,25 @@ __global__ __launch_bounds__(kPartThreads) void k_meta_hist(const uint64_t *__re
     }
     for (; i < npair; i += kPartThreads) {
       seen += 2;
-      const ulonglong2 k = kv[i];
-      const longlong2 t = tv[i];
-      const ulonglong2 k2 = HAS2 ? k2v[i] : make_ulonglong2(TAD_KEY_SKIP, TAD_KEY_SKIP);
+      const ulonglong2 k = kpair(kv, key, i);
+      const longlong2 t = tpair(i);
+      const ulonglong2 k2 = HAS2 ? kpair(k2v, key2, i) : make_ulonglong2(TAD_KEY_SKIP, TAD_KEY_SKIP);
       const uint64_t r = lo + 2 * i;
-      const int64_t ts0 = has_ts ? t_start[r] : 0, ts1 = has_ts ? t_start[r + 1] : 0;
+      const int64_t ts0 = has_ts ? ld_time<T32>(t_start, r) : 0, ts1 = has_ts ? ld_time<T32>(t_start, r + 1) : 0;
       meta_row(acc, hist, k.x, k2.x, t.x, p_time_kept(t.x, ts0, has_ts, f), K, shift_bin);
       meta_row(acc, hist, k.y, k2.y, t.y, p_time_kept(t.y, ts1, has_ts, f), K, shift_bin);
     }
     if (((hi - lo) & 1) && threadIdx.x == 0 && hi > lo) {
       seen += 1;
       const uint64_t r = hi - 1;
-      const int64_t te = t_end[r];
-      meta_row(acc, hist, key[r], HAS2 ? key2[r] : TAD_KEY_SKIP, te, p_time_kept(te, has_ts ? t_start[r] : 0, has_ts, f), K, shift_bin);
+      const int64_t te = ld_time<T32>(t_end, r);
+      meta_row(acc, hist, ld_key<K32>(key, r), HAS2 ? ld_key<K32>(key2, r) : TAD_KEY_SKIP, te, p_time_kept(te, has_ts ? ld_time<T32>(t_start, r) : 0, has_ts, f), K, shift_bin);
     }
   } else {
     for (uint64_t r = lo + threadIdx.x; r < hi; r += kPartThreads) {
       seen += 1;
-      const int64_t te = t_end[r];
-      meta_row(acc, hist, key[r], HAS2 ? key2[r] : TAD_KEY_SKIP, te, p_time_kept(te, has_ts ? t_start[r] : 0, has_ts, f), K, shift_bin);
+      const int64_t te = ld_time<T32>(t_end, r);
+      meta_row(acc, hist, ld_key<K32>(key, r), HAS2 ? ld_key<K32>(key2, r) : TAD_KEY_SKIP, te, p_time_kept(te, has_ts ? ld_time<T32>(t_start, r) : 0, has_ts, f), K, shift_bin);
     }
   }
   PMeta m = acc.m;
@@ -590,7 +600,8 @@ __device__ __forceinline__ void lds_exclusive_scan(uint32_t *a, uint32_t n, uint
 // phase 1 has consumed the current ones; the value column is only needed in phase 3, so the next tile's values
 // are loaded after phase 3 into the registers phase 3 has just drained.  Every load therefore has two to four
 // LDS phases to land, and nothing is live twice.
-template <int RPT, bool HAS2, bool VEC, bool GENERIC>
+// K32 / T32: narrow key / time columns, read at their own width (8-byte loads of a row pair where VEC loads 16 bytes)
+template <int RPT, bool HAS2, bool VEC, bool GENERIC, bool K32 = false, bool T32 = false>
 __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NSLOT = RPT * (HAS2 ? 2 : 1);
@@ -643,13 +654,13 @@ __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs A) {
     for (int j = 0; j < RPT; j += (VEC ? 2 : 1)) {
       const uint64_t i = row_index(base, j);
       if (VEC) {
-        const ulonglong2 k = *reinterpret_cast<const ulonglong2 *>(A.key + i);
-        const longlong2 t = *reinterpret_cast<const longlong2 *>(A.t_end + i);
+        const ulonglong2 k = ld_key2<K32>(A.key, i, 0);
+        const longlong2 t = ld_time2<T32>(A.t_end, i, 0);
         pk[j] = k.x; pk[j + 1] = k.y; pt[j] = t.x; pt[j + 1] = t.y;
-        if (HAS2) { const ulonglong2 k2 = *reinterpret_cast<const ulonglong2 *>(A.key2 + i); pk2[j] = k2.x; pk2[j + 1] = k2.y; }
+        if (HAS2) { const ulonglong2 k2 = ld_key2<K32>(A.key2, i, 0); pk2[j] = k2.x; pk2[j + 1] = k2.y; }
       } else {
-        pk[j] = A.key[i]; pt[j] = A.t_end[i];
-        if (HAS2) pk2[j] = A.key2[i];
+        pk[j] = ld_key<K32>(A.key, i); pt[j] = ld_time<T32>(A.t_end, i);
+        if (HAS2) pk2[j] = ld_key<K32>(A.key2, i);
       }
     }
   };
@@ -670,9 +681,9 @@ __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs A) {
     for (int j = 0; j < RPT; ++j) {
       const uint64_t i = row_index(base, j);
       const bool in = i < hi;
-      pk[j] = in ? A.key[i] : TAD_KEY_SKIP;
-      pt[j] = in ? A.t_end[i] : 0;
-      if (HAS2) pk2[j] = in ? A.key2[i] : TAD_KEY_SKIP;
+      pk[j] = in ? ld_key<K32>(A.key, i) : TAD_KEY_SKIP;
+      pt[j] = in ? ld_time<T32>(A.t_end, i) : 0;
+      if (HAS2) pk2[j] = in ? ld_key<K32>(A.key2, i) : TAD_KEY_SKIP;
     }
   };
   auto load_values_tail = [&](uint64_t base) {
@@ -702,7 +713,7 @@ __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs A) {
       bool kept = true;
       if (GENERIC && (A.f.end_time != 0 || has_ts)) {
         const uint64_t i = row_index(base, j);
-        const int64_t ts = (has_ts && i < hi) ? A.t_start[i] : 0;
+        const int64_t ts = (has_ts && i < hi) ? ld_time<T32>(A.t_start, i) : 0;
         kept = p_time_kept(te, ts, has_ts, A.f);
       }
       uint32_t bucket = 0;
@@ -816,7 +827,8 @@ __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs A) {
 // column, the load sits between the LDS appends and is waited for together with the prefetched rows of the next tile: pass B 0.80 against
 // 0.66 ms.  A first form prefetched it behind a run-time test inside load_tile: the compiler then cannot count the loads in flight and waits
 // for all of them everywhere — slower even for jobs without a start_time, profiles/r6_s14_*.)
-template <int RPT, int SEC, bool HAS2, bool GENERIC, bool TS = false>
+// K32 / T32: narrow key / time columns (8-byte loads of a row pair)
+template <int RPT, int SEC, bool HAS2, bool GENERIC, bool TS = false, bool K32 = false, bool T32 = false>
 __global__ __launch_bounds__(kPartThreads) void k_partition_wc(PartArgs A, uint32_t cap, int G) {
   static_assert(!TS || GENERIC, "a start_time filter is a generic job");
   static_assert(RPT == 2 || RPT == 4, "rows per thread: one or two 16-byte loads per column");
@@ -933,23 +945,23 @@ __global__ __launch_bounds__(kPartThreads) void k_partition_wc(PartArgs A, uint3
 #pragma unroll
       for (int j = 0; j < RPT; j += 2) {
         const uint64_t i = row_index(base, j);
-        const ulonglong2 k = *reinterpret_cast<const ulonglong2 *>(A.key + i);
-        const longlong2 t = *reinterpret_cast<const longlong2 *>(A.t_end + i);
+        const ulonglong2 k = ld_key2<K32>(A.key, i, 0);
+        const longlong2 t = ld_time2<T32>(A.t_end, i, 0);
         const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(A.value + i);
         r.k[j] = k.x; r.k[j + 1] = k.y; r.t[j] = t.x; r.t[j + 1] = t.y; r.v[j] = v.x; r.v[j + 1] = v.y;
-        if (HAS2) { const ulonglong2 k2 = *reinterpret_cast<const ulonglong2 *>(A.key2 + i); r.k2[j] = k2.x; r.k2[j + 1] = k2.y; }
-        if (TS) { const longlong2 ts = *reinterpret_cast<const longlong2 *>(A.t_start + i); r.ts[TS ? j : 0] = ts.x; r.ts[TS ? j + 1 : 0] = ts.y; }
+        if (HAS2) { const ulonglong2 k2 = ld_key2<K32>(A.key2, i, 0); r.k2[j] = k2.x; r.k2[j + 1] = k2.y; }
+        if (TS) { const longlong2 ts = ld_time2<T32>(A.t_start, i, 0); r.ts[TS ? j : 0] = ts.x; r.ts[TS ? j + 1 : 0] = ts.y; }
       }
     } else if (tile < ntiles) {
 #pragma unroll
       for (int j = 0; j < RPT; ++j) {
         const uint64_t i = row_index(base, j);
         const bool in = i < hi;
-        r.k[j] = in ? A.key[i] : TAD_KEY_SKIP;
-        r.t[j] = in ? A.t_end[i] : 0;
+        r.k[j] = in ? ld_key<K32>(A.key, i) : TAD_KEY_SKIP;
+        r.t[j] = in ? ld_time<T32>(A.t_end, i) : 0;
         r.v[j] = in ? A.value[i] : 0;
-        if (HAS2) r.k2[j] = in ? A.key2[i] : TAD_KEY_SKIP;
-        if (TS) r.ts[TS ? j : 0] = in ? A.t_start[i] : 0;
+        if (HAS2) r.k2[j] = in ? ld_key<K32>(A.key2, i) : TAD_KEY_SKIP;
+        if (TS) r.ts[TS ? j : 0] = in ? ld_time<T32>(A.t_start, i) : 0;
       }
     }
   };
@@ -964,7 +976,7 @@ __global__ __launch_bounds__(kPartThreads) void k_partition_wc(PartArgs A, uint3
       bool kept = true;
       if (GENERIC && (A.f.end_time != 0 || has_ts)) {
         const uint64_t i = row_index(base, j);
-        const int64_t ts = TS ? r.ts[TS ? j : 0] : ((has_ts && i < hi) ? A.t_start[i] : 0);
+        const int64_t ts = TS ? r.ts[TS ? j : 0] : ((has_ts && i < hi) ? ld_time<T32>(A.t_start, i) : 0);
         kept = p_time_kept(te, ts, has_ts, A.f);
       }
       uint32_t bucket = 0;
@@ -1645,22 +1657,24 @@ void part_plan_wc(uint64_t slots, bool aligned, bool has2, int partition_pass, P
 
 bool launch_meta_hist(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
                       const int64_t *t_start, uint64_t n, uint64_t K, RowFilter f, const PartPlan &pl,
-                      MetaPartial *partials, uint32_t *binhist, DevCounters *ctr, bool sample_hist) {
+                      MetaPartial *partials, uint32_t *binhist, DevCounters *ctr, int cw, bool sample_hist) {
   const bool vec = aligned16(key) && aligned16(key2) && aligned16(t_end);
   const bool has2 = key2 != nullptr;
   // the histogram is sampled with 16-byte loads only; a time-window filter (anomaly_detection.py:581-586) is applied to the sampled rows
   const bool sh = sample_hist && vec && (t_start == nullptr || f.start_time == 0 || aligned16(t_start));
+  with_widths(cw, [&](auto k32, auto t32) {
 #define TAD_MH(V, H2, SH)                                                                                              \
   do {                                                                                                                 \
-    allow_big_lds(reinterpret_cast<const void *>(k_meta_hist<V, H2, SH>), kLdsBudget);                                 \
-    hipLaunchKernelGGL((k_meta_hist<V, H2, SH>), dim3(pl.G), dim3(kPartThreads), (size_t)pl.nbins * 4, s, key, key2, t_end, t_start, n, \
-                       pl.chunk, K, f, pl.shift_bin, pl.nbins, partials, binhist, ctr);                                \
+    allow_big_lds(reinterpret_cast<const void *>(k_meta_hist<V, H2, SH, k32(), t32()>), kLdsBudget);                   \
+    hipLaunchKernelGGL((k_meta_hist<V, H2, SH, k32(), t32()>), dim3(pl.G), dim3(kPartThreads), (size_t)pl.nbins * 4, s, key, key2, t_end, \
+                       t_start, n, pl.chunk, K, f, pl.shift_bin, pl.nbins, partials, binhist, ctr);                    \
   } while (0)
-  if (vec) {
-    if (sh) { if (has2) TAD_MH(true, true, true); else TAD_MH(true, false, true); }
-    else { if (has2) TAD_MH(true, true, false); else TAD_MH(true, false, false); }
-  } else { if (has2) TAD_MH(false, true, false); else TAD_MH(false, false, false); }
+    if (vec) {
+      if (sh) { if (has2) TAD_MH(true, true, true); else TAD_MH(true, false, true); }
+      else { if (has2) TAD_MH(true, true, false); else TAD_MH(true, false, false); }
+    } else { if (has2) TAD_MH(false, true, false); else TAD_MH(false, false, false); }
 #undef TAD_MH
+  });
   return sh;
 }
 
@@ -1714,7 +1728,7 @@ void launch_part_offsets(hipStream_t s, const uint32_t *binhist, const PartPlan 
 void launch_partition(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
                       const int64_t *t_start, const uint64_t *value, uint64_t n, uint64_t K, RowFilter f, Lattice L,
                       const PartPlan &pl, const uint32_t *offs32, const unsigned long long *part_start, void *recs,
-                      OverflowRec *ovf, unsigned long long *ovf_count, uint32_t ovf_cap, DevCounters *ctr, uint32_t *fin, uint32_t *ovf_keys) {
+                      OverflowRec *ovf, unsigned long long *ovf_count, uint32_t ovf_cap, DevCounters *ctr, uint32_t *fin, uint32_t *ovf_keys, int cw) {
   PartArgs A;
   A.fin = fin; A.G = pl.G;
   A.value_limit = 1ull << (64 - pl.cell_bits);
@@ -1730,48 +1744,52 @@ void launch_partition(hipStream_t s, const uint64_t *key, const uint64_t *key2, 
   const bool vec = aligned16(key) && aligned16(key2) && aligned16(t_end) && aligned16(value);
   // fast path: 16-byte loads, no time-window filter, bucket by one multiply-high
   const bool generic = !vec || L.mode == 2 || f.end_time != 0 || (f.start_time != 0 && t_start != nullptr);
-  if (pl.wc_cap) {  // write-combining variant (the plan checked the alignment)
-    const size_t wlds = ((size_t)pl.nparts * (8 * (size_t)pl.wc_cap + kWcFixedBytes) + 4 + 15) & ~(size_t)15;
-    const bool ts16 = generic && t_start != nullptr && f.start_time != 0 && aligned16(t_start);   // start times prefetched with the tile
+  with_widths(cw, [&](auto k32, auto t32) {
+    constexpr bool K32 = decltype(k32)::value, T32 = decltype(t32)::value;
+    if (pl.wc_cap) {  // write-combining variant (the plan checked the alignment)
+      const size_t wlds = ((size_t)pl.nparts * (8 * (size_t)pl.wc_cap + kWcFixedBytes) + 4 + 15) & ~(size_t)15;
+      const bool ts16 = generic && t_start != nullptr && f.start_time != 0 && aligned16(t_start);   // start times prefetched with the tile
 #define TAD_WC1(RPT, SEC, H2, GEN, TS)                                                                                  \
   do {                                                                                                                \
-    allow_big_lds(reinterpret_cast<const void *>(k_partition_wc<RPT, SEC, H2, GEN, TS>), kLdsBudget);                  \
-    hipLaunchKernelGGL((k_partition_wc<RPT, SEC, H2, GEN, TS>), dim3(pl.G), dim3(kPartThreads), wlds, s, A, pl.wc_cap, pl.G); \
+    allow_big_lds(reinterpret_cast<const void *>(k_partition_wc<RPT, SEC, H2, GEN, TS, K32, T32>), kLdsBudget);        \
+    hipLaunchKernelGGL((k_partition_wc<RPT, SEC, H2, GEN, TS, K32, T32>), dim3(pl.G), dim3(kPartThreads), wlds, s, A, pl.wc_cap, pl.G); \
   } while (0)
 #define TAD_WC(RPT, SEC, H2, GEN) do { if (GEN && ts16) TAD_WC1(RPT, SEC, H2, GEN, GEN); else TAD_WC1(RPT, SEC, H2, GEN, false); } while (0)
 #define TAD_WC_SEC(RPT, H2, GEN) do { if (pl.wc_sec == 16) TAD_WC(RPT, 16, H2, GEN); else TAD_WC(RPT, 8, H2, GEN); } while (0)
-    if (pl.wc_rpt == 4 && !has2) { if (generic) TAD_WC_SEC(4, false, true); else TAD_WC_SEC(4, false, false); }
-    else if (has2) { if (generic) TAD_WC_SEC(2, true, true); else TAD_WC_SEC(2, true, false); }
-    else { if (generic) TAD_WC_SEC(2, false, true); else TAD_WC_SEC(2, false, false); }
+      if (pl.wc_rpt == 4 && !has2) { if (generic) TAD_WC_SEC(4, false, true); else TAD_WC_SEC(4, false, false); }
+      else if (has2) { if (generic) TAD_WC_SEC(2, true, true); else TAD_WC_SEC(2, true, false); }
+      else { if (generic) TAD_WC_SEC(2, false, true); else TAD_WC_SEC(2, false, false); }
 #undef TAD_WC_SEC
 #undef TAD_WC
 #undef TAD_WC1
-    return;
-  }
-  int rpt = pl.rpt;
-  if (generic && rpt > 4) rpt = 4;
-  const size_t fixed = ((size_t)pl.nparts + 4) * 16 + 64;
-  const size_t lds = ((size_t)rpt * kPartThreads * (has2 ? 2 : 1) * 10 + fixed + 15) & ~(size_t)15;
+      return;
+    }
+    int rpt = pl.rpt;
+    if (generic && rpt > 4) rpt = 4;
+    if ((K32 || T32) && rpt > 4) rpt = 4;   // narrow columns: the sort-by-tile pass at 2 or 4 rows per thread (fewer instantiations)
+    const size_t fixed = ((size_t)pl.nparts + 4) * 16 + 64;
+    const size_t lds = ((size_t)rpt * kPartThreads * (has2 ? 2 : 1) * 10 + fixed + 15) & ~(size_t)15;
 #define TAD_PART(RPT, H2, V, GEN)                                                                                       \
   do {                                                                                                                \
-    allow_big_lds(reinterpret_cast<const void *>(k_partition<RPT, H2, V, GEN>), kLdsBudget);                           \
-    hipLaunchKernelGGL((k_partition<RPT, H2, V, GEN>), dim3(pl.G), dim3(kPartThreads), lds, s, A);                       \
+    allow_big_lds(reinterpret_cast<const void *>(k_partition<RPT, H2, V, GEN, K32, T32>), kLdsBudget);                 \
+    hipLaunchKernelGGL((k_partition<RPT, H2, V, GEN, K32, T32>), dim3(pl.G), dim3(kPartThreads), lds, s, A);            \
   } while (0)
-  if (!generic) {
-    switch (rpt) {
-      case 10: if (has2) TAD_PART(8, true, true, false); else TAD_PART(10, false, true, false); break;
-      case 8: if (has2) TAD_PART(8, true, true, false); else TAD_PART(8, false, true, false); break;
-      case 6: case 4: if (has2) TAD_PART(4, true, true, false); else TAD_PART(4, false, true, false); break;
-      default: if (has2) TAD_PART(2, true, true, false); else TAD_PART(2, false, true, false); break;
+    if (!generic) {
+      switch (rpt) {
+        case 10: if constexpr (!K32 && !T32) { if (has2) TAD_PART(8, true, true, false); else TAD_PART(10, false, true, false); } break;
+        case 8: if constexpr (!K32 && !T32) { if (has2) TAD_PART(8, true, true, false); else TAD_PART(8, false, true, false); } break;
+        case 6: case 4: if (has2) TAD_PART(4, true, true, false); else TAD_PART(4, false, true, false); break;
+        default: if (has2) TAD_PART(2, true, true, false); else TAD_PART(2, false, true, false); break;
+      }
+    } else if (vec) {
+      if (rpt >= 4) { if (has2) TAD_PART(4, true, true, true); else TAD_PART(4, false, true, true); }
+      else { if (has2) TAD_PART(2, true, true, true); else TAD_PART(2, false, true, true); }
+    } else {
+      if (rpt >= 4) { if (has2) TAD_PART(4, true, false, true); else TAD_PART(4, false, false, true); }
+      else { if (has2) TAD_PART(2, true, false, true); else TAD_PART(2, false, false, true); }
     }
-  } else if (vec) {
-    if (rpt >= 4) { if (has2) TAD_PART(4, true, true, true); else TAD_PART(4, false, true, true); }
-    else { if (has2) TAD_PART(2, true, true, true); else TAD_PART(2, false, true, true); }
-  } else {
-    if (rpt >= 4) { if (has2) TAD_PART(4, true, false, true); else TAD_PART(4, false, false, true); }
-    else { if (has2) TAD_PART(2, true, false, true); else TAD_PART(2, false, false, true); }
-  }
 #undef TAD_PART
+  });
 }
 
 size_t slice_table_bytes(uint64_t slots, const PartPlan &pl) {

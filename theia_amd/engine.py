@@ -83,10 +83,18 @@ class HostBuffer:
             pass
 
 
-def _as_column(x, dtype, n_expected=None):
-    """-> (pointer, n, is_device, keepalive)"""
+def _as_column(x, dtype, n_expected=None, narrow=None):
+    """-> (pointer, n, is_device, keepalive).  narrow = "key" / "time": a 4-byte column is passed at its own width (_narrow_of)."""
     if x is None:
         return None, 0, None, None
+    if narrow is not None and _narrow_of(x, narrow):
+        if hasattr(x, "data_ptr") and hasattr(x, "is_cuda"):
+            x = x.contiguous()
+            if x.is_cuda:
+                return x.data_ptr(), x.numel(), True, x
+            x = x.numpy()
+        a = np.ascontiguousarray(x).view(np.uint32)     # (a key id as its bits: -1 of an int32 column is TAD_KEY_SKIP32)
+        return a.ctypes.data, a.size, False, a
     if isinstance(x, DeviceArray):
         return x.ptr, x.n, True, x
     if hasattr(x, "data_ptr") and hasattr(x, "is_cuda"):  # torch tensor
@@ -104,6 +112,35 @@ def _as_column(x, dtype, n_expected=None):
         else:
             a = a.astype(dtype)
     return a.ctypes.data, a.size, False, a
+
+
+def _narrow_of(x, kind):
+    """Whether column x goes to the engine as a narrow (4-byte) column: 4-byte integer key columns (numpy or torch), uint32 numpy
+    time columns and 4-byte torch time tensors (an int32 tensor is read as UInt32 DateTime bits).  A numpy int32 time column keeps
+    the 8-byte path (sign-extended), as it always had."""
+    if x is None or isinstance(x, DeviceArray):
+        return False
+    if hasattr(x, "data_ptr") and hasattr(x, "is_cuda"):
+        return x.element_size() == 4 and not x.is_floating_point() and not x.is_complex()
+    dt = getattr(x, "dtype", None)
+    if dt is None or not isinstance(x, np.ndarray):
+        return False
+    if kind == "key":
+        return dt.kind in "iu" and dt.itemsize == 4
+    return dt == np.dtype(np.uint32)
+
+
+def _narrow_flags(lib, key_id, key_id2, flow_end_s, flow_start_s):
+    """TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 for these columns; the key (time) columns of a job must all be narrow or all be wide."""
+    nk = [_narrow_of(c, "key") for c in (key_id, key_id2) if c is not None]
+    nt = [_narrow_of(c, "time") for c in (flow_end_s, flow_start_s) if c is not None]
+    if len(set(nk)) > 1 or len(set(nt)) > 1:
+        raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "key_id / key_id2 (flow_end_s / flow_start_s) must have the same width")
+    flags = (capi.TAD_FLAG_KEY_U32 if nk and nk[0] else 0) | (capi.TAD_FLAG_TIME_U32 if nt and nt[0] else 0)
+    if flags and not (getattr(lib, "tad_features", None) and lib.tad_features() & capi.TAD_FEATURE_NARROW_COLUMNS):
+        raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of libtad_mi355x.so does not take 4-byte columns (no tad_features / "
+                       "TAD_FEATURE_NARROW_COLUMNS): pass 8-byte columns or rebuild the library")
+    return flags
 
 
 class KeyHistogram:
@@ -387,11 +424,12 @@ class TadEngine:
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "algo must be EWMA, ARIMA, DBSCAN or DROP")
         if agg_flow not in capi.TAD_AGG:
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "agg_flow must be '', pod, svc or external")
-        pk, n, dev, keep1 = _as_column(key_id, np.uint64)
-        pt, nt, dev_t, keep2 = _as_column(flow_end_s, np.int64)
+        narrow = _narrow_flags(self._lib, key_id, key_id2, flow_end_s, flow_start_s)
+        pk, n, dev, keep1 = _as_column(key_id, np.uint64, narrow="key")
+        pt, nt, dev_t, keep2 = _as_column(flow_end_s, np.int64, narrow="time")
         pv, nv, dev_v, keep3 = _as_column(value, np.uint64)
-        pk2, nk2, dev_k2, keep4 = _as_column(key_id2, np.uint64)
-        ps, ns, dev_s, keep5 = _as_column(flow_start_s, np.int64)
+        pk2, nk2, dev_k2, keep4 = _as_column(key_id2, np.uint64, narrow="key")
+        ps, ns, dev_s, keep5 = _as_column(flow_start_s, np.int64, narrow="time")
         for m, d in ((nt, dev_t), (nv, dev_v)) + (((nk2, dev_k2),) if key_id2 is not None else ()) + \
                 (((ns, dev_s),) if flow_start_s is not None else ()):
             if m != n or d != dev:
@@ -400,7 +438,7 @@ class TadEngine:
                        start_time=int(start_time), end_time=int(end_time), ewma_alpha=float(alpha),
                        dbscan_eps=float(eps), dbscan_min_samples=int(min_samples), arima_maxiter=int(maxiter),
                        drop_nsigma=float(drop_nsigma), drop_min_samples=int(drop_min_samples),
-                       flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
+                       flags=(capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0) | narrow, id=job_id.encode()[:63])
         cols = capi.Columns(n_rows=n, key_id=pk, key_id2=pk2, flow_end_s=pt, flow_start_s=ps, value=pv,
                             num_keys=int(num_keys), memory=capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST)
         if lattice is not None:
@@ -430,14 +468,15 @@ class TadEngine:
     def run_stream(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, emit_all=False, out="host",
                    alpha=0.0, job_id="", num_keys=None, key_id2=None):
         """One batch of the streaming EWMA detector on `state` (tad_run_stream).  key_id2: the second key column of pod mode."""
-        pk, n, dev, keep1 = _as_column(key_id, np.uint64)
-        pt, nt, dev_t, keep2 = _as_column(flow_end_s, np.int64)
+        narrow = _narrow_flags(self._lib, key_id, key_id2, flow_end_s, None)
+        pk, n, dev, keep1 = _as_column(key_id, np.uint64, narrow="key")
+        pt, nt, dev_t, keep2 = _as_column(flow_end_s, np.int64, narrow="time")
         pv, nv, dev_v, keep3 = _as_column(value, np.uint64)
-        pk2, nk2, dev_k2, keep4 = _as_column(key_id2, np.uint64)
+        pk2, nk2, dev_k2, keep4 = _as_column(key_id2, np.uint64, narrow="key")
         if nt != n or nv != n or dev_t != dev or dev_v != dev or (key_id2 is not None and (nk2 != n or dev_k2 != dev)):
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "columns must have equal length and live in the same memory")
         job = capi.Job(algo=capi.TAD_ALGO["EWMA"], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
-                       flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
+                       flags=(capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0) | narrow, id=job_id.encode()[:63])
         cols = capi.Columns(n_rows=n, key_id=pk, key_id2=pk2, flow_end_s=pt, value=pv, num_keys=state.num_keys if num_keys is None else int(num_keys),
                             memory=capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST)
         if lattice is not None:
@@ -656,17 +695,18 @@ class TadEngine:
                   start_time=0, end_time=0, lattice=None, out="host"):
         if agg_flow not in capi.TAD_AGG:
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "agg_flow must be '', pod, svc or external")
-        pk, n, dev, keep1 = _as_column(key_id, np.uint64)
-        pt, nt, dev_t, keep2 = _as_column(flow_end_s, np.int64)
+        narrow = _narrow_flags(self._lib, key_id, key_id2, flow_end_s, flow_start_s)
+        pk, n, dev, keep1 = _as_column(key_id, np.uint64, narrow="key")
+        pt, nt, dev_t, keep2 = _as_column(flow_end_s, np.int64, narrow="time")
         pv, nv, dev_v, keep3 = _as_column(value, np.uint64)
-        pk2, nk2, dev_k2, keep4 = _as_column(key_id2, np.uint64)
-        ps, ns, dev_s, keep5 = _as_column(flow_start_s, np.int64)
+        pk2, nk2, dev_k2, keep4 = _as_column(key_id2, np.uint64, narrow="key")
+        ps, ns, dev_s, keep5 = _as_column(flow_start_s, np.int64, narrow="time")
         for m, d in ((nt, dev_t), (nv, dev_v)) + (((nk2, dev_k2),) if key_id2 is not None else ()) + \
                 (((ns, dev_s),) if flow_start_s is not None else ()):
             if m != n or d != dev:
                 raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "columns must have equal length and live in the same memory")
         job = capi.Job(algo=0, agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op],
-                       start_time=int(start_time), end_time=int(end_time))
+                       start_time=int(start_time), end_time=int(end_time), flags=narrow)
         cols = capi.Columns(n_rows=n, key_id=pk, key_id2=pk2, flow_end_s=pt, flow_start_s=ps, value=pv,
                             num_keys=int(num_keys), memory=capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST)
         if lattice is not None:

@@ -77,8 +77,11 @@ def main():
                     cand = cand[:-1] + ", false>"
                 if short not in kb and cand in kb:
                     ka[cand] = ka.pop(short)
-                elif short not in kb and short + "<false>" in kb:
-                    ka[short + "<false>"] = ka.pop(short)
+                elif short not in kb:   # a non-template kernel that became a template with defaulted 'false' parameters
+                    for m in range(1, 4):
+                        if short + "<" + ", ".join(["false"] * m) + ">" in kb:
+                            ka[short + "<" + ", ".join(["false"] * m) + ">"] = ka.pop(short)
+                            break
             for short in sorted(set(ka) | set(kb)):
                 if short not in ka:
                     print("%-22s NEW      %-60s %s" % (f, short[:60], kb[short][1])); continue

@@ -124,6 +124,9 @@ type Job struct {
 	StartTime int64 // epoch seconds, 0 = unset (Spec.StartInterval)
 	EndTime   int64 // epoch seconds, 0 = unset (Spec.EndInterval)
 	ID        string
+	// DBSCAN parameters (tad_job.dbscan_eps / dbscan_min_samples): 0 = the reference's eps = 250000000, min_samples = 4
+	DBSCANEps        float64
+	DBSCANMinSamples int32
 }
 
 // Columns is one batch of flow rows after dictionary encoding; all slices have the same length.
@@ -254,6 +257,8 @@ func (e *Engine) Run(job Job, cols Columns) ([]Row, Stats, error) {
 	cj.algo = C.tad_algo(job.Algo)
 	cj.agg_flow = C.tad_agg_flow(job.AggFlow)
 	cj.value_op = C.TAD_OP_AUTO
+	cj.dbscan_eps = C.double(job.DBSCANEps)
+	cj.dbscan_min_samples = C.int32_t(job.DBSCANMinSamples)
 	cj.start_time = C.int64_t(job.StartTime)
 	cj.end_time = C.int64_t(job.EndTime)
 	id := []byte(job.ID)
@@ -621,10 +626,94 @@ func (e *Engine) CopyToHost(dst []byte, src unsafe.Pointer) error {
 }
 
 // State is the per-key running EWMA state of a long-running detector (tad.h: tad_state, SURVEY.md 8f rank 3): Spark's streaming moments
-// (n, avg, m2), the last EWMA value and the last flowEndSeconds of every key, kept in HBM between batches.
+// (n, avg, m2), the last EWMA value and the last flowEndSeconds of every key, kept in HBM between batches.  A state made by
+// NewStateWithHistory also keeps every key's aggregated point values, sorted, for the streaming DBSCAN detector.
 type State struct {
-	e *Engine
-	h *C.tad_state
+	e       *Engine
+	h       *C.tad_state
+	history bool
+}
+
+var streamDBSCANOnce sync.Once
+var streamDBSCANOK bool
+
+// hasStreamDBSCAN: the library knows history states and streaming DBSCAN (tad_features); an older one would not export the calls.
+func hasStreamDBSCAN() bool {
+	streamDBSCANOnce.Do(func() { streamDBSCANOK = C.tad_features()&C.TAD_FEATURE_STREAM_DBSCAN != 0 })
+	return streamDBSCANOK
+}
+
+// NewStateWithHistory makes a state that also keeps every key's aggregated point values (tad_state_create_ex with TAD_STATE_HISTORY):
+// RunStream then takes Job.Algo == DBSCAN, and each batch's rows are those the batch job emits for the batch's points over everything
+// seen so far.  The history grows with the points seen (HistoryPoints).
+func (e *Engine) NewStateWithHistory(numKeys uint64) (*State, error) {
+	if !hasStreamDBSCAN() {
+		return nil, errors.New("tadengine: libtad_mi355x.so has no streaming DBSCAN (TAD_FEATURE_STREAM_DBSCAN)")
+	}
+	var h *C.tad_state
+	if rc := C.tad_state_create_ex(e.h, C.uint64_t(numKeys), C.TAD_STATE_HISTORY, &h); rc != C.TAD_OK {
+		return nil, fmt.Errorf("tad_state_create_ex: %s (code %d)", C.GoString(C.tad_last_error(e.h)), int(rc))
+	}
+	return &State{e: e, h: h, history: true}, nil
+}
+
+// HistoryPoints is the number of values the state's history holds (tad_state_history_points); 0 for a state without history.
+func (s *State) HistoryPoints() (uint64, error) {
+	if !s.history {
+		return 0, nil
+	}
+	var n C.uint64_t
+	if rc := C.tad_state_history_points(s.e.h, s.h, &n); rc != C.TAD_OK {
+		return 0, fmt.Errorf("tad_state_history_points: %s (code %d)", C.GoString(C.tad_last_error(s.e.h)), int(rc))
+	}
+	return uint64(n), nil
+}
+
+// ExportHistory copies the history to the host (tad_state_export_history): per key its number of values, and every key's values
+// ascending, keys in order.
+func (s *State) ExportHistory(numKeys uint64) (length []uint64, values []uint64, err error) {
+	if !s.history {
+		return nil, nil, errors.New("tadengine: the state has no history")
+	}
+	total, err := s.HistoryPoints()
+	if err != nil {
+		return nil, nil, err
+	}
+	length, values = make([]uint64, numKeys), make([]uint64, total)
+	if numKeys == 0 {
+		return
+	}
+	var pv *C.uint64_t
+	if total > 0 {
+		pv = (*C.uint64_t)(unsafe.Pointer(&values[0]))
+	}
+	if rc := C.tad_state_export_history(s.e.h, s.h, (*C.uint64_t)(unsafe.Pointer(&length[0])), pv); rc != C.TAD_OK {
+		err = fmt.Errorf("tad_state_export_history: %s (code %d)", C.GoString(C.tad_last_error(s.e.h)), int(rc))
+	}
+	return
+}
+
+// ImportHistory restores what ExportHistory returned (tad_state_import_history), after Import of the moments: length[k] must equal
+// the key's n and every key's values must be ascending, else the state is left as it was.
+func (s *State) ImportHistory(length []uint64, values []uint64) error {
+	if !s.history {
+		return errors.New("tadengine: the state has no history")
+	}
+	if len(length) == 0 {
+		return errors.New("tadengine: empty state")
+	}
+	var pv *C.uint64_t
+	if len(values) > 0 {
+		pv = (*C.uint64_t)(unsafe.Pointer(&values[0]))
+	}
+	if rc := C.tad_state_import_history(s.e.h, s.h, (*C.uint64_t)(unsafe.Pointer(&length[0])), pv); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return IllegalArgument{msg}
+		}
+		return fmt.Errorf("tad_state_import_history: %s (code %d)", msg, int(rc))
+	}
+	return nil
 }
 
 func (e *Engine) NewState(numKeys uint64) (*State, error) {
@@ -643,18 +732,24 @@ func (s *State) Close() {
 }
 
 // RunStream aggregates ONE new batch and continues every key's recurrences over its new points (tad_run_stream): the rows are the points
-// with |x - ewma| > the running stddev_samp.  cols.NumKeys must equal the state's key count; job.Algo must be EWMA.
+// with |x - ewma| > the running stddev_samp.  cols.NumKeys must equal the state's key count; job.Algo must be EWMA, or DBSCAN on a state
+// made by NewStateWithHistory (the rows are then the batch's points the batch job over everything seen so far calls noise).
 func (s *State) RunStream(job Job, cols Columns) ([]Row, error) {
 	bufs, n, narrow, err := columnBuffers(cols)
 	if err != nil {
 		return nil, err
 	}
 	defer freeBuffers(bufs)
+	if job.Algo == DBSCAN && !s.history {
+		return nil, IllegalArgument{"tadengine: streaming DBSCAN needs a state made by NewStateWithHistory"}
+	}
 	var cj C.tad_job
 	cj.flags = narrow
 	cj.algo = C.tad_algo(job.Algo)
 	cj.agg_flow = C.tad_agg_flow(job.AggFlow)
 	cj.value_op = C.TAD_OP_AUTO
+	cj.dbscan_eps = C.double(job.DBSCANEps)
+	cj.dbscan_min_samples = C.int32_t(job.DBSCANMinSamples)
 	var cc C.tad_columns
 	cc.n_rows = C.uint64_t(n)
 	cc.num_keys = C.uint64_t(cols.NumKeys)

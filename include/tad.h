@@ -72,6 +72,7 @@ typedef enum { TAD_MEM_HOST = 0, TAD_MEM_DEVICE = 1 } tad_mem;
 
 /* tad_features(): what this build of the library understands beyond TAD_ABI_VERSION */
 #define TAD_FEATURE_NARROW_COLUMNS 1u /* TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 are honoured */
+#define TAD_FEATURE_STREAM_DBSCAN 2u  /* tad_state_create_ex(TAD_STATE_HISTORY) and tad_run_stream with TAD_ALGO_DBSCAN */
 
 typedef struct tad_engine tad_engine; /* opaque; one per GPU; runs up to max_jobs_in_flight jobs concurrently (ABI 12) */
 
@@ -376,7 +377,8 @@ int tad_host_free(tad_engine *e, void *ptr);
  * included) — the running sigma, the only one an append-only detector can know.  After the last batch the state equals
  * what the batch job computes over the concatenated table bit for bit (same operations in the same order): n, avg, m2
  * give its stddev_samp, ewma its last EWMA value.  A row not newer than its key's last_t is rejected
- * (TAD_ERR_INVALID_ARGUMENT) and the state is left untouched.  job->algo must be TAD_ALGO_EWMA, and cols->num_keys must
+ * (TAD_ERR_INVALID_ARGUMENT) and the state is left untouched.  job->algo must be TAD_ALGO_EWMA (or TAD_ALGO_DBSCAN on a state
+ * with history, below), and cols->num_keys must
  * EQUAL the num_keys the state holds (a batch addresses the state's whole key space; keys without rows in the batch keep
  * their state) — anything else is TAD_ERR_INVALID_ARGUMENT.
  * ABI 13: a batch takes the Stage 0 rule of tad_run (tad_plan.sparse / sparse_sort / stage0 included), so second-resolution
@@ -397,6 +399,39 @@ int tad_state_import(tad_engine *e, tad_state *s, const uint32_t *n, const doubl
                      const int64_t *last_t);
 int tad_run_stream(tad_engine *e, tad_state *s, const tad_job *job, const tad_columns *cols, tad_mem out_memory,
                    tad_result **out);
+
+/* ---- streaming DBSCAN: a state WITH HISTORY (TAD_FEATURE_STREAM_DBSCAN; check tad_features() before calling these) ----
+ * tad_state_create_ex(e, num_keys, TAD_STATE_HISTORY, &s) makes a state that keeps, on top of (n, avg, m2, ewma, last_t), every
+ * aggregated point value it has seen, sorted ascending per key, in HBM.  flags 0 is tad_state_create.
+ * tad_run_stream with job->algo == TAD_ALGO_DBSCAN on a history state, for one batch:
+ *   1. aggregates the batch with Stage 0 exactly as an EWMA batch does (dense grid or sparse sort, tad_run's rule and plan overrides);
+ *   2. advances the moments and last_t exactly as an EWMA batch does (a row not newer than its key's last_t fails the batch);
+ *   3. merges the batch's new point values into the history and judges ONLY the batch's new points.
+ * The rows of batch b are exactly the rows tad_run(DBSCAN), run with the same job parameters on the concatenation of batches 1..b,
+ * emits for the points of batch b: key_id, flow_end_s, throughput, algo_calc = 0.0 and stddev, in the same order, bit for bit.  stddev
+ * is the key's stddev_samp over everything seen through batch b (from the post-batch moments).  With TAD_FLAG_EMIT_ALL_POINTS the rows
+ * are all of batch b's points with their verdict in `anomaly`.  DBSCAN verdicts depend only on the multiset of a key's values, which is
+ * why this form is exact where the EWMA stream has to use a running sigma.  Consequences:
+ *   - every point of a key with fewer than min_samples points so far is noise, as in the batch job;
+ *   - dbscan_eps and dbscan_min_samples may differ from batch to batch: each batch is judged with its own, against the raw values;
+ *   - points judged in earlier batches are not judged again.  A point can stop being noise once later points arrive; the stream
+ *     reports each point once, when it arrives.
+ * An EWMA batch on a history state appends to the history too; its rows and moments are those of the same batch on a plain state.
+ * DBSCAN on a plain state is TAD_ERR_INVALID_ARGUMENT (state unchanged); ARIMA and DROP have no streaming form.
+ * Invariant: after every successful call the history of key k holds n[k] values; a failed batch (late row, key out of range, out of
+ * memory) leaves the history unchanged as well as the state.  The history is never evicted: it grows with the points seen (8 bytes
+ * each, twice over: a batch merges into a second copy), and tad_state_history_points is how a caller watches it.  A batch costs an
+ * EWMA stream batch, plus a rewrite of the history (about 16 B per history point), plus the sort and verdicts of its new points.
+ * tad_state_resize gives the added keys empty histories.  tad_state_export / tad_state_import / tad_state_destroy are unchanged. */
+#define TAD_STATE_HISTORY 1u           /* keep every key's aggregated point values (sorted) */
+int tad_state_create_ex(tad_engine *e, uint64_t num_keys, uint32_t flags, tad_state **out);   /* flags 0 == tad_state_create */
+/* total values in the history (0 for a plain state) */
+int tad_state_history_points(tad_engine *e, const tad_state *s, uint64_t *n_points);
+/* HOST arrays: len[num_keys] and values[n_points], ascending per key, keys in order */
+int tad_state_export_history(tad_engine *e, const tad_state *s, uint64_t *len, uint64_t *values);
+/* the inverse of tad_state_export_history, after tad_state_import of the moments: TAD_ERR_INVALID_ARGUMENT with the state unchanged
+ * unless the state has history, len[k] == n[k] of the state for every k, and every key's values are ascending */
+int tad_state_import_history(tad_engine *e, tad_state *s, const uint64_t *len, const uint64_t *values);
 
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).

@@ -19,6 +19,8 @@ TAD_FLAG_EMIT_ALL_POINTS = 1
 TAD_FLAG_KEY_U32, TAD_FLAG_TIME_U32 = 2, 4   # narrow input columns: uint32 key ids / uint32 DateTime seconds (tad.h, tad_columns)
 TAD_KEY_SKIP32 = (1 << 32) - 1
 TAD_FEATURE_NARROW_COLUMNS = 1               # tad_features() bit: the library honours the two flags above
+TAD_FEATURE_STREAM_DBSCAN = 2                # tad_features() bit: tad_state_create_ex(TAD_STATE_HISTORY), tad_run_stream with DBSCAN
+TAD_STATE_HISTORY = 1                        # tad_state_create_ex flag: keep every key's aggregated point values (sorted)
 
 
 class Plan(C.Structure):
@@ -118,6 +120,10 @@ SYMBOLS = {
     "tad_state_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_state_resize": (C.c_int, [C.c_void_p, C.c_void_p, u64]),
     "tad_state_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tad_state_create_ex": (C.c_int, [C.c_void_p, u64, u32, C.POINTER(C.c_void_p)]),
+    "tad_state_history_points": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(u64)]),
+    "tad_state_export_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tad_state_import_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_run_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_aggregate": (C.c_int, [C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Points))]),
     "tad_points_free": (None, [C.c_void_p, C.POINTER(Points)]),

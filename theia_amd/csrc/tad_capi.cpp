@@ -213,6 +213,99 @@ StreamState state_view(const tad_state *st, int which) {
 
 int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_mem out_memory, tad_result **out, tad_points **points_out,
                    tad_state *stream, int depth);
+
+// What a batch on a history state leaves for its emit: the new points in (key, time) order and, for DBSCAN, their verdicts and rows.
+struct HistBatch {
+  const unsigned long long *nk = nullptr, *nv = nullptr;
+  const long long *nt = nullptr;
+  const unsigned long long *P_dev = nullptr;   // the number of new points (device)
+  uint64_t P_cap = 0;                          // its bound on the host (exact for a sparse batch)
+  const uint8_t *noise = nullptr;
+  const uint32_t *cnt = nullptr;
+  const unsigned long long *row = nullptr;
+};
+
+// One batch on a history state (tad.h, TAD_STATE_HISTORY), after the stream count pass and before the job's tail is read: the batch's new
+// points in (key, time) order, sorted per key and merged with the current history into the candidate arena (tad_history.hip); a DBSCAN
+// batch also judges the new points against the merged history and scans their rows into the row total.  Writes only candidate memory:
+// the history becomes current with the moments, when the batch succeeds.  sparse_poff: a sparse batch's point offsets (P points in
+// e->sp_comp_a / e->sp_val_a); otherwise the dense grid g is compacted, at most P_bound points.
+int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound,
+                         const JobParams &jp, HistBatch *hb) {
+  hipStream_t s = e->stream;
+  const uint64_t K = g.K;
+  const int cur = st->cur, cand = cur ^ 1;
+  const bool dbscan = jp.algo == TAD_ALGO_DBSCAN;
+  const uint64_t P_cap = sparse_poff ? P : P_bound;
+  const size_t kpad = (size_t)((K + 3) & ~3ull);
+  int rc;
+  // the candidate arena first: an allocation failure leaves the state and its history as they are
+  const uint64_t need = st->hist_len[cur] + P_cap;
+  if (st->hist_cap[cand] < need) {
+    const uint64_t cap = need > 2 * st->hist_cap[cand] ? need : 2 * st->hist_cap[cand];
+    HIP_TRY(e, hipStreamSynchronize(s));
+    if (st->hist_val[cand]) hipFree(st->hist_val[cand]);
+    st->hist_val[cand] = nullptr;
+    st->hist_cap[cand] = 0;
+    void *p = nullptr;
+    const hipError_t r = hipMalloc(&p, cap * 8);
+    if (r != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_run_stream: %llu values of history do not fit (%s); state unchanged",
+                  (unsigned long long)need, hipGetErrorString(r));
+    }
+    st->hist_val[cand] = static_cast<unsigned long long *>(p);
+    st->hist_cap[cand] = cap;
+  }
+  const uint64_t pc = P_cap ? P_cap : 1;
+  if ((rc = ensure(e, e->hs_key, pc * 8)) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->hs_t, pc * 8)) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->hs_sorted, pc * 8)) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->hs_koff, (kpad + 4) * 16)) != TAD_OK) return rc;   // dense point offsets | chunk offsets, K + 1 each
+  if ((rc = ensure(e, e->hs_kcnt, kpad * 4 + 64)) != TAD_OK) return rc;     // per-key counts / long-sort list / chunks | long-list length
+  if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K > pc ? K : pc) * sizeof(unsigned long long))) != TAD_OK) return rc;
+  if (!sparse_poff && (rc = ensure(e, e->hs_val, pc * 8)) != TAD_OK) return rc;
+  if (dbscan) {
+    if ((rc = ensure(e, e->hs_noise, pc)) != TAD_OK) return rc;
+    if ((rc = ensure(e, e->hs_cnt, pc * 4)) != TAD_OK) return rc;
+    if ((rc = ensure(e, e->hs_row, (pc + 1) * 8)) != TAD_OK) return rc;
+  }
+  unsigned long long *nk = static_cast<unsigned long long *>(e->hs_key.p);
+  long long *nt = static_cast<long long *>(e->hs_t.p);
+  unsigned long long *ns = static_cast<unsigned long long *>(e->hs_sorted.p);
+  unsigned long long *koff = static_cast<unsigned long long *>(e->hs_koff.p), *coff = koff + kpad + 4;
+  uint32_t *kcnt = static_cast<uint32_t *>(e->hs_kcnt.p);
+  unsigned int *long_count = reinterpret_cast<unsigned int *>(kcnt + kpad);
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  const unsigned long long *poff, *nv;
+  if (sparse_poff) {   // 1. the sorted unique points of the sparse Stage 0
+    poff = sparse_poff;
+    nv = static_cast<const unsigned long long *>(e->sp_val_a.p);
+    launch_hist_decode(s, static_cast<const unsigned long long *>(e->sp_comp_a.p), P, L.t0, nk, nt);
+  } else {             // 1. the dense grid compacted as tad_aggregate does
+    launch_count_flags(s, g, true, kcnt);
+    launch_scan(s, kcnt, koff, K, scratch);
+    launch_emit_points(s, g, L, koff, nk, nt, static_cast<unsigned long long *>(e->hs_val.p));
+    poff = koff;
+    nv = static_cast<const unsigned long long *>(e->hs_val.p);
+  }
+  // 2. every key's new values sorted; 3. merged with its history into the candidate arena
+  launch_hist_sort(s, nv, poff, K, ns, kcnt, long_count);
+  launch_hist_merge(s, K, st->hist_off[cur], st->hist_val[cur], poff, ns, st->hist_off[cand], st->hist_val[cand], kcnt, coff, scratch,
+                    hist_merge_chunks_bound(K, need));
+  HIP_TRY(e, hipMemcpyAsync(static_cast<unsigned char *>(e->counters.p) + kTailHistLen, poff + K, 8, hipMemcpyDeviceToDevice, s));
+  hb->nk = nk; hb->nt = nt; hb->nv = nv; hb->P_dev = poff + K; hb->P_cap = P_cap;
+  if (dbscan && P_cap) {   // 4. verdicts of the new points; 5. their rows (the row total lands in the job's tail)
+    uint8_t *noise = static_cast<uint8_t *>(e->hs_noise.p);
+    uint32_t *cnt = static_cast<uint32_t *>(e->hs_cnt.p);
+    unsigned long long *row = static_cast<unsigned long long *>(e->hs_row.p);
+    launch_hist_verdict(s, nk, nv, poff + K, P_cap, st->hist_off[cand], st->hist_val[cand], jp.eps, jp.min_samples, jp.all_points, noise, cnt);
+    launch_scan(s, cnt, row, P_cap, scratch, dev_total(e));
+    hb->noise = noise; hb->cnt = cnt; hb->row = row;
+  }
+  return TAD_OK;
+}
+
 int run_sparse_classes(JobCtx *e, const tad_job *job, const JobParams &jp, bool op_max, uint64_t n_rows_in, uint64_t rows_used, uint64_t K, Lattice L,
                        uint64_t P, uint32_t tmax, tad_mem out_memory, tad_result **out);
 int sparse_points_direct(JobCtx *e, uint64_t n_rows_in, uint64_t rows_used, Lattice L, uint64_t P, DevCounters *ctr, tad_mem out_memory,
@@ -224,7 +317,11 @@ int run_job(tad_engine *eng, const tad_job *job, const tad_columns *cols, tad_me
   tad_engine *e = eng;
   const bool points_mode = points_out != nullptr;
   if (stream && e && job && cols) {
-    if (job->algo != TAD_ALGO_EWMA) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: only the EWMA detector has a streaming form");
+    if (job->algo == TAD_ALGO_DBSCAN && !stream->history)
+      return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: DBSCAN needs a state with history (tad_state_create_ex with TAD_STATE_HISTORY)");
+    if (job->algo != TAD_ALGO_EWMA && job->algo != TAD_ALGO_DBSCAN)
+      return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: only the EWMA detector has a streaming form, and DBSCAN on a state with history "
+                                               "(ARIMA and DROP depend on the whole series)");
     // k_stream writes the candidate state for keys < cols->num_keys and the double buffer flips as a whole: a batch
     // that declares fewer keys than the state holds would drop the others' state
     if (cols->num_keys != stream->K) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: batch declares %llu keys, the state holds %llu (they must be equal)",
@@ -432,6 +529,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
     Grid sparse_grid{};
     bool sp_part = false;
     const unsigned long long *stream_poff = nullptr;   // a sparse streaming batch: key k's points at [poff[k], poff[k + 1]) of the sorted list
+    uint64_t stream_P = 0;                             // ... and the number of its points
     if (sparse && use_kh) {
       // the sparse sort plans LDS rounds of exactly known sizes from the histogram (k_ss_plan): only pass A's own count is trusted with that
       kh_rejected = true;
@@ -526,6 +624,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
         launch_sparse_len(s, ucomp, P, static_cast<const uint32_t *>(e->sp_first.p), len);
         launch_scan(s, len, poff, K, static_cast<unsigned long long *>(e->scan_scratch.p), nullptr);
         stream_poff = poff;
+        stream_P = P;
         sparse_grid = Grid{nullptr, nullptr, K, 0, nullptr};
         HIP_TRY(e, hipEventRecord(e->ev[3], s));
       } else {
@@ -662,6 +761,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
 
     // ---- Stage 1+2: sigma, detector, count, scan ----
     uint64_t rows = 0;
+    HistBatch hist;
     ResultPriv *rp = nullptr;
     OutRows dev_rows{};
     ResultBlock dev_block;
@@ -689,7 +789,11 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
         launch_stream(s, g, L, jp.alpha, jp.all_points, false, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),
                       static_cast<uint32_t *>(e->n_anom.p), nullptr, OutRows{}, ctr);
       unsigned long long *off = static_cast<unsigned long long *>(e->off.p);
-      launch_scan(s, static_cast<const uint32_t *>(e->n_anom.p), off, g.K, static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
+      if (stream->history && g.K &&
+          (rc = stream_history_batch(e, stream, g, L, stream_poff, stream_P, (slots_all < cells ? slots_all : cells), jp, &hist)) != TAD_OK)
+        return rc;
+      if (jp.algo != TAD_ALGO_DBSCAN)   // (a DBSCAN batch counted its rows in stream_history_batch)
+        launch_scan(s, static_cast<const uint32_t *>(e->n_anom.p), off, g.K, static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
       HIP_TRY(e, hipMemcpyAsync(e->tail_host, e->counters.p, kTailBytes, hipMemcpyDeviceToHost, s));
       HIP_TRY(e, hipStreamSynchronize(s));
       HIP_TRY(e, hipGetLastError());
@@ -795,7 +899,10 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
 
     // ---- Stage 3: emit ----
     if ((rc = make_result(e, rows, jp.all_points, out_memory, &rp, &dev_rows, &dev_block)) != TAD_OK) return rc;
-    if (rows && stream && stream_poff)
+    if (rows && stream && jp.algo == TAD_ALGO_DBSCAN)
+      launch_hist_emit(s, hist.nk, hist.nt, hist.nv, hist.P_dev, hist.P_cap, hist.noise, hist.cnt, hist.row, state_view(stream, stream->cur ^ 1),
+                       jp.all_points, dev_rows);
+    else if (rows && stream && stream_poff)
       launch_stream_points(s, static_cast<const unsigned long long *>(e->sp_comp_a.p), static_cast<const unsigned long long *>(e->sp_val_a.p), stream_poff,
                            g.K, L.t0, jp.alpha, jp.all_points, true, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),
                            nullptr, static_cast<const unsigned long long *>(e->off.p), dev_rows, ctr);
@@ -880,7 +987,14 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       w.wide_tiles = force_wide_tiles && plan.tile_cells != 1;
     }
     strncpy(rp->pub.id, job->id, sizeof rp->pub.id - 1);
-    if (stream && g.K) stream->cur ^= 1;   // the batch succeeded: the candidate state becomes current (an empty batch wrote none)
+    if (stream && g.K) {   // the batch succeeded: the candidate state (and history) becomes current (an empty batch wrote none)
+      if (stream->history) {
+        unsigned long long added;
+        memcpy(&added, e->tail_host + kTailHistLen, 8);
+        stream->hist_len[stream->cur ^ 1] = stream->hist_len[stream->cur] + added;
+      }
+      stream->cur ^= 1;
+    }
     if (depth == 0) e->done.store(4);
     *out = &rp->pub;
     return TAD_OK;
@@ -1148,7 +1262,11 @@ void tad_state_destroy(tad_engine *e, tad_state *st) {
   if (!st) return;
   { std::lock_guard<std::mutex> lk(st->mu); }   // a batch on this state has returned (it synchronises its stream before it does)
   if (e) hipSetDevice(e->device);
-  for (int i = 0; i < 2; ++i) if (st->block[i]) hipFree(st->block[i]);
+  for (int i = 0; i < 2; ++i) {
+    if (st->block[i]) hipFree(st->block[i]);
+    if (st->hist_off[i]) hipFree(st->hist_off[i]);
+    if (st->hist_val[i]) hipFree(st->hist_val[i]);
+  }
   delete st;
 }
 
@@ -1197,12 +1315,35 @@ int tad_state_resize(tad_engine *eng, tad_state *st, uint64_t new_num_keys) {
     if (r == hipSuccess) r = hipMemcpyAsync(b.n, a.n, K * sizeof(uint32_t), hipMemcpyDeviceToDevice, e->stream);
     if (r == hipSuccess) r = hipMemcpyAsync(b.seen, a.seen, K, hipMemcpyDeviceToDevice, e->stream);
   }
+  // a history state: offsets of K' + 1 entries for both copies; the current one keeps its keys' offsets and gives the added keys empty
+  // segments at the end (offset = the history's length).  The value arenas stay; the current one moves to index 0 with the state.
+  std::vector<unsigned long long> tail_off;
+  if (r == hipSuccess && st->history) {
+    for (int i = 0; i < 2 && r == hipSuccess; ++i) r = hipMalloc(reinterpret_cast<void **>(&grown.hist_off[i]), (new_num_keys + 1) * 8);
+    if (r == hipSuccess) r = hipMemcpyAsync(grown.hist_off[0], st->hist_off[st->cur], (st->K + 1) * 8, hipMemcpyDeviceToDevice, e->stream);
+    if (r == hipSuccess) {
+      try { tail_off.assign(new_num_keys - st->K, st->hist_len[st->cur]); } catch (...) { r = hipErrorOutOfMemory; }
+    }
+    if (r == hipSuccess)
+      r = hipMemcpyAsync(grown.hist_off[0] + st->K + 1, tail_off.data(), tail_off.size() * 8, hipMemcpyHostToDevice, e->stream);
+  }
   if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
   if (r != hipSuccess) {
-    for (int i = 0; i < 2; ++i) if (grown.block[i]) hipFree(grown.block[i]);
+    for (int i = 0; i < 2; ++i) {
+      if (grown.block[i]) hipFree(grown.block[i]);
+      if (grown.hist_off[i]) hipFree(grown.hist_off[i]);
+    }
     return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_resize: %s (state unchanged)", hipGetErrorString(r));
   }
   for (int i = 0; i < 2; ++i) { hipFree(st->block[i]); st->block[i] = grown.block[i]; }
+  if (st->history) {
+    for (int i = 0; i < 2; ++i) { hipFree(st->hist_off[i]); st->hist_off[i] = grown.hist_off[i]; }
+    if (st->cur == 1) {
+      std::swap(st->hist_val[0], st->hist_val[1]);
+      std::swap(st->hist_cap[0], st->hist_cap[1]);
+      std::swap(st->hist_len[0], st->hist_len[1]);
+    }
+  }
   st->K = new_num_keys;
   st->cur = 0;
   return TAD_OK;
@@ -1228,6 +1369,96 @@ int tad_state_import(tad_engine *eng, tad_state *st, const uint32_t *n, const do
     h_avg[k] = avg[k]; h_m2[k] = m2[k]; h_ewma[k] = ewma[k]; h_last[k] = last_t[k]; h_n[k] = n[k]; h_seen[k] = 1;
   }
   HIP_TRY(e, hipMemcpy(st->block[st->cur], h.data(), h.size(), hipMemcpyHostToDevice));
+  return TAD_OK;
+}
+
+int tad_state_create_ex(tad_engine *eng, uint64_t num_keys, uint32_t flags, tad_state **out) {
+  if (flags & ~TAD_STATE_HISTORY) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_create_ex: unknown flags 0x%x", flags & ~TAD_STATE_HISTORY);
+  int rc = tad_state_create(eng, num_keys, out);
+  if (rc != TAD_OK || !(flags & TAD_STATE_HISTORY)) return rc;
+  tad_state *st = *out;
+  st->history = true;
+  hipError_t r = hipSetDevice(eng->device);
+  for (int i = 0; i < 2 && r == hipSuccess; ++i) {   // every key's segment empty: offsets all zero (the value arenas come with the first batch)
+    r = hipMalloc(reinterpret_cast<void **>(&st->hist_off[i]), (num_keys + 1) * 8);
+    if (r == hipSuccess) r = hipMemset(st->hist_off[i], 0, (num_keys + 1) * 8);
+  }
+  if (r != hipSuccess) {
+    tad_state_destroy(eng, st);
+    *out = nullptr;
+    return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_create_ex: %s", hipGetErrorString(r));
+  }
+  return TAD_OK;
+}
+
+int tad_state_history_points(tad_engine *eng, const tad_state *st, uint64_t *n_points) {
+  if (!eng || !st || !n_points) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_history_points: bad arguments");
+  std::lock_guard<std::mutex> state_lk(st->mu);
+  *n_points = st->history ? st->hist_len[st->cur] : 0;
+  return TAD_OK;
+}
+
+int tad_state_export_history(tad_engine *eng, const tad_state *st, uint64_t *len, uint64_t *values) {
+  if (!eng || !st || !len) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_history: bad arguments");
+  if (!st->history) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_history: the state has no history (TAD_STATE_HISTORY)");
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_export_history: no job context available");
+  std::lock_guard<std::mutex> state_lk(st->mu);
+  HIP_TRY(e, hipSetDevice(e->device));
+  std::vector<unsigned long long> off;
+  try { off.resize(st->K + 1); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
+  HIP_TRY(e, hipMemcpy(off.data(), st->hist_off[st->cur], (st->K + 1) * 8, hipMemcpyDeviceToHost));
+  for (uint64_t k = 0; k < st->K; ++k) len[k] = off[k + 1] - off[k];
+  const uint64_t total = st->hist_len[st->cur];
+  if (values && total) HIP_TRY(e, hipMemcpy(values, st->hist_val[st->cur], total * 8, hipMemcpyDeviceToHost));
+  return TAD_OK;
+}
+
+int tad_state_import_history(tad_engine *eng, tad_state *st, const uint64_t *len, const uint64_t *values) {
+  if (!eng || !st || !len) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_history: bad arguments");
+  if (!st->history) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_history: the state has no history (TAD_STATE_HISTORY)");
+  std::lock_guard<std::mutex> state_lk(st->mu);
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_import_history: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  const uint64_t K = st->K;
+  std::vector<uint32_t> n;
+  std::vector<unsigned long long> off;
+  try { n.resize(K); off.resize(K + 1); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
+  HIP_TRY(e, hipMemcpy(n.data(), state_view(st, st->cur).n, K * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  off[0] = 0;
+  for (uint64_t k = 0; k < K; ++k) {
+    if (len[k] != n[k])
+      return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_history: key %llu has %llu values, its state has n = %u (import the moments first); state unchanged",
+                  (unsigned long long)k, (unsigned long long)len[k], n[k]);
+    off[k + 1] = off[k] + len[k];
+  }
+  const uint64_t total = off[K];
+  if (total && !values) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_history: values is NULL");
+  for (uint64_t k = 0; k < K; ++k)
+    for (uint64_t i = off[k] + 1; i < off[k + 1]; ++i)
+      if (values[i] < values[i - 1])
+        return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_history: the values of key %llu are not ascending; state unchanged", (unsigned long long)k);
+  // into the candidate copy, which then trades places with the current one: any failure leaves the history as it was
+  const int cand = st->cur ^ 1;
+  unsigned long long *val = st->hist_val[cand];
+  uint64_t cap = st->hist_cap[cand];
+  if (cap < total) {
+    void *p = nullptr;
+    const hipError_t r = hipMalloc(&p, total * 8);
+    if (r != hipSuccess) { (void)hipGetLastError(); return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_import_history: %s; state unchanged", hipGetErrorString(r)); }
+    if (val) hipFree(val);
+    st->hist_val[cand] = val = static_cast<unsigned long long *>(p);
+    st->hist_cap[cand] = cap = total;
+  }
+  if (total) HIP_TRY(e, hipMemcpy(val, values, total * 8, hipMemcpyHostToDevice));
+  HIP_TRY(e, hipMemcpy(st->hist_off[cand], off.data(), (K + 1) * 8, hipMemcpyHostToDevice));
+  std::swap(st->hist_off[0], st->hist_off[1]);
+  std::swap(st->hist_val[0], st->hist_val[1]);
+  std::swap(st->hist_cap[0], st->hist_cap[1]);
+  st->hist_len[st->cur] = total;
   return TAD_OK;
 }
 

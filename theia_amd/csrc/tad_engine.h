@@ -93,6 +93,7 @@ struct JobCtx {
   DevBuf binhist, part_total, part_start, part_offs32, recs, ovf, slices;  // Stage 0 v2 (ovf: 8-byte count + overflow records)
   DevBuf sp_comp_a, sp_comp_b, sp_val_a, sp_val_b, sp_temp, sp_first, sp_times;  // Stage 0 sparse (sort + rank grid)
   DevBuf sp_cls;                                                                  // Stage 0 sparse, length classes: per-key class arrays
+  DevBuf hs_key, hs_t, hs_val, hs_sorted, hs_noise, hs_cnt, hs_row, hs_koff, hs_kcnt;   // a history batch: new points, sorted values, verdicts, rows, offsets
   int arima_relaunches = 0;       // times the running job's ARIMA fit was relaunched after it had yielded to whole-CU jobs (tad_stats.arima_relaunches)
   bool sp_by_partition = false;   // the running job's sparse Stage 0 went through the partition pass + LDS sort (stage0_path 8 / 9 / 10 instead of 4 / 6 / 7)
   DevBuf part_fin;                                                                // Stage 0 v2, sampled histogram: final cursors of the (workgroup, partition) regions
@@ -120,13 +121,19 @@ struct JobCtx {
 };
 
 // per-key running state of the streaming EWMA detector: two copies (the count pass writes the candidate next state,
-
-// per-key running state of the streaming EWMA detector: two copies (the count pass writes the candidate next state,
 // it becomes current only when the batch succeeds)
 struct tad_state {
   uint64_t K = 0;
   void *block[2] = {nullptr, nullptr};
   int cur = 0;
+  // TAD_STATE_HISTORY: every key's aggregated point values, ascending per key — hist_off[i] (K + 1 entries) and hist_val[i] (hist_cap
+  // entries, hist_len used).  Double-buffered with the same index as block[]: a batch merges into the candidate (cur ^ 1), which
+  // becomes current with the moments.  Arenas grow geometrically and are kept; a plain state allocates none of this.
+  bool history = false;
+  unsigned long long *hist_off[2] = {nullptr, nullptr};
+  unsigned long long *hist_val[2] = {nullptr, nullptr};
+  uint64_t hist_cap[2] = {0, 0};
+  uint64_t hist_len[2] = {0, 0};
   mutable std::mutex mu;     // batches of one state are serial (tad_run_stream from two threads on one state)
 };
 
@@ -159,7 +166,7 @@ using namespace tad;
 extern thread_local std::string g_static_err;   // tad_last_error(NULL): the message of a failed tad_engine_create
 
 // the job tail: what the host reads when a job's kernels are done, ONE block on the device and one pinned block on the host
-constexpr size_t kTailCtr = 0, kTailTotal = 64, kTailOvfCount = 72, kTailMoments = 128;
+constexpr size_t kTailCtr = 0, kTailTotal = 64, kTailOvfCount = 72, kTailHistLen = 80, kTailMoments = 128;   // kTailHistLen: a history batch's new points
 constexpr size_t kTailBytes = kTailMoments + sizeof(Moments) * kMomentBlocks;
 inline unsigned long long *dev_total(JobCtx *e) { return reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(e->counters.p) + kTailTotal); }
 inline unsigned long long *dev_ovf_count(JobCtx *e) { return reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(e->counters.p) + kTailOvfCount); }
@@ -190,7 +197,8 @@ template <typename F> void for_each_buf(JobCtx *c, F f) {
   DevBuf *bufs[] = {&c->grid_val, &c->grid_flag, &c->sigma, &c->n_pts, &c->n_anom, &c->off, &c->scan_scratch, &c->calc, &c->counters, &c->meta, &c->aux,
                     &c->key_mean, &c->key_m2, &c->rcp_table, &c->binhist, &c->part_total, &c->part_start, &c->part_offs32, &c->recs, &c->ovf, &c->slices,
                     &c->sp_comp_a, &c->sp_comp_b, &c->sp_val_a, &c->sp_val_b, &c->sp_temp, &c->sp_first, &c->sp_times, &c->sp_cls, &c->part_fin, &c->ovf_keys,
-                    &c->in_key, &c->in_key2, &c->in_te, &c->in_ts, &c->in_val};
+                    &c->in_key, &c->in_key2, &c->in_te, &c->in_ts, &c->in_val,
+                    &c->hs_key, &c->hs_t, &c->hs_val, &c->hs_sorted, &c->hs_noise, &c->hs_cnt, &c->hs_row, &c->hs_koff, &c->hs_kcnt};
   for (DevBuf *b : bufs) f(*b);
 }
 

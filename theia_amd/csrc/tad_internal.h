@@ -280,6 +280,28 @@ void launch_stream(hipStream_t s, Grid g, Lattice lat, double alpha, bool all_po
 void launch_stream_points(hipStream_t s, const unsigned long long *comp, const unsigned long long *val, const unsigned long long *poff, uint64_t K,
                           int64_t t0, double alpha, bool all_points, bool emit, StreamState cur, StreamState next, uint32_t *n_anom,
                           const unsigned long long *off, OutRows out, DevCounters *ctr);
+// ---- per-key value history of a streaming state, streaming DBSCAN (tad_history.hip) ----
+// the sparse batch's sorted unique points (comp = key << 32 | (t - t0)) as key / time columns
+void launch_hist_decode(hipStream_t s, const unsigned long long *comp, uint64_t P, int64_t t0, unsigned long long *nk, long long *nt);
+// ns = nv sorted ascending within every key's segment [poff[k], poff[k + 1]); long_list: K entries, long_count: one device word
+void launch_hist_sort(hipStream_t s, const unsigned long long *nv, const unsigned long long *poff, uint64_t K, unsigned long long *ns,
+                      uint32_t *long_list, unsigned int *long_count);
+// upper bound of k_hist_merge's wavefronts for K keys and total_len merged values
+uint64_t hist_merge_chunks_bound(uint64_t K, uint64_t total_len);
+// hoff_new = hoff_old + poff; hval_new = every key's old and new (ns) values merged; chunks u32[K], coff u64[K + 1] and scan_scratch
+// (scan_scratch_elems(K)) are scratch
+void launch_hist_merge(hipStream_t s, uint64_t K, const unsigned long long *hoff_old, const unsigned long long *hval_old, const unsigned long long *poff,
+                       const unsigned long long *ns, unsigned long long *hoff_new, unsigned long long *hval_new, uint32_t *chunks,
+                       unsigned long long *coff, unsigned long long *scan_scratch, uint64_t chunks_bound);
+// DBSCAN verdict of each of the *P_dev new points (key nk[i], value nv[i]) against its key's merged history h[hoff[k], hoff[k + 1]):
+// noise[i], cnt[i] = rows the point emits (1 with all_points, else the verdict; 0 for i in [*P_dev, P_cap))
+void launch_hist_verdict(hipStream_t s, const unsigned long long *nk, const unsigned long long *nv, const unsigned long long *P_dev, uint64_t P_cap,
+                         const unsigned long long *hoff, const unsigned long long *h, double eps, int min_samples, bool all_points, uint8_t *noise,
+                         uint32_t *cnt);
+// the rows of the points with cnt[i] != 0 at row[i]; stddev from the candidate state `next`
+void launch_hist_emit(hipStream_t s, const unsigned long long *nk, const long long *nt, const unsigned long long *nv, const unsigned long long *P_dev,
+                      uint64_t P_cap, const uint8_t *noise, const uint32_t *cnt, const unsigned long long *row, StreamState next, bool all_points,
+                      OutRows out);
 // EWMA value for every present point into calc[T][K] (series entry points)
 void launch_ewma_values(hipStream_t s, Grid g, double alpha, double *calc);
 
@@ -490,6 +512,7 @@ const void *code_anchor_arima();
 const void *code_anchor_dbscan();
 const void *code_anchor_drop();
 const void *code_anchor_factorize();
+const void *code_anchor_history();
 const void *code_anchor_ingest();
 const void *code_anchor_kernels();
 const void *code_anchor_shard();

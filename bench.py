@@ -6,10 +6,12 @@ resident in HBM: Stage-0 GROUP BY (key, flowEndSeconds) -> per-key stddev_samp -
 compaction of the anomalous points into device-resident result columns.
 
 Workload at N=1 (`--config c2`, the default) = BASELINE.json configs[1]: EWMA on 1e8 rows / 1e5 flow keys / 250 time
-buckets, sum(throughput) (mode svc), the deterministic synthetic table of SURVEY.md §8d.  The same JSON line carries
-`other_configs`: C4 (configs[3]: DBSCAN, 1e6 keys x 100 buckets, max(throughput) = mode None) and C3 (configs[2]: ARIMA
-on the C2 table), each timed the same way (W warm-up steps, K timed steps bracketed by synchronisation) with its own
-roofline — so that those rates are measured by whoever runs this file, not quoted.
+buckets, sum(throughput) (mode svc), the deterministic synthetic table of SURVEY.md §8d.  A plain run sets up, warms up, times
+the K steps, writes --dump-outputs if asked and prints the line: the headline, the roofline of its own steps, `cold`.  Everything
+else is measured only with `--full`, in the same process after the headline.  The --full line carries `other_configs`: C4
+(configs[3]: DBSCAN, 1e6 keys x 100 buckets, max(throughput) = mode None) and C3 (configs[2]: ARIMA on the C2 table), each
+timed the same way (W warm-up steps, K timed steps bracketed by synchronisation) with its own roofline — so that those rates are
+measured by whoever runs this file, not quoted.
 N>1 (`python bench.py --gpus N` starts the N ranks itself; under an external torchrun — WORLD_SIZE set — it is one of them;
 one rank per GPU): weak scaling — every rank owns the key shard `key mod N == rank`
 (1e8 rows / 1e5 keys per rank, pre-sharded by key as SURVEY.md §8e allows), no data-path collective;
@@ -27,14 +29,14 @@ separate --pmc runs of this same command).  `roofline.frac` prices the DOMINANT 
 per job over the WALL time of a step (`ms_per_step`, launch gaps and host round trips included) against the same peak.
 `value` is what a controller sees from a warm engine (controller.go:499-523: every CR is a new job on new data): the timed steps go
 ROUND ROBIN over `config.tables` (4) synthetic tables of the workload's shape with different seeds in different device buffers, so
-no step meets the columns of the step before it; `same_columns` is the old loop (one table, every step) beside it, `cold` the FIRST
-job of the engine in the process (allocations included).  `concurrency` (N = 1, default line): aggregate rows/s with 1 / 2 / 4 host
+no step meets the columns of the step before it; `same_columns` (--full) is the old loop (one table, every step) beside it, `cold` the FIRST
+job of the engine in the process (allocations included).  `concurrency` (N = 1, --full line): aggregate rows/s with 1 / 2 / 4 host
 threads submitting C2 jobs to the ONE engine (job contexts = stream pool, tad.h ABI 12), and the latency of C2 EWMA jobs submitted
-while a C3 ARIMA job runs.  `row_orders` (N = 1, default line): the C2 job on the SAME rows in the orders a caller can bring them in —
+while a C3 ARIMA job runs.  `row_orders` (N = 1, --full line): the C2 job on the SAME rows in the orders a caller can bring them in —
 ids handed out in order of first appearance (any dictionary encoder), rows by time (`flows` is ORDER BY (timeInserted, flowEndSeconds),
 create_table.sh:85), by key (a GROUP BY result), keys alive for a tenth of the table — and with an --end-time window; the synthetic
 table's rows are in arbitrary order with hashed ids.
-`cpu_baseline` = the oracle (numpy port of the reference
+`cpu_baseline` (--full) = the oracle (numpy port of the reference
 job) timed on this box's host cores on a bounded sample.  ARIMA lines add `arima`: fits/s and the
 FP64 flop rate from the engine's Kalman-step counter (16 flop per step of the recursion the kernel executes; the
 60-flop-equivalent of SURVEY.md 8d's three-state model beside it).
@@ -386,13 +388,16 @@ def main():
     ap.add_argument("--plan", default="", help="tad_plan overrides for A/B runs, e.g. histogram=exact,partition_pass=sort (default: the engine decides)")
     ap.add_argument("--tables", type=int, default=4, help="synthetic tables of the workload's shape the timed steps go round robin over "
                                                            "(different seeds, different device buffers); 1 = the same columns every step")
-    ap.add_argument("--c5-shape", default="", help="N > 1: run the other_configs.c5 leg (BASELINE configs[4], key- and row-sharded) on a table of "
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure what it does not need: same_columns, other_configs (N = 1: C4, C3, C5; N > 1: "
+                         "C5 key- and row-sharded), concurrency, row_orders and the CPU baselines (the --no-* options below trim it)")
+    ap.add_argument("--c5-shape", default="", help="N > 1, --full: run the other_configs.c5 leg (BASELINE configs[4], key- and row-sharded) on a table of "
                                                      "ROWS,KEYS,BUCKETS in total instead of 1e9,1e6,250, whatever the headline is (reduced-size tests)")
-    ap.add_argument("--no-row-orders", action="store_true", help="N = 1 default line: skip the row_orders leg")
-    ap.add_argument("--concurrency", default="1,2,4", help="N = 1 default line: host threads submitting C2 jobs to the one engine (job contexts); '' = skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
-    ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the CPU sample (0 = chosen from the host's core count)")
+    ap.add_argument("--no-row-orders", action="store_true", help="N = 1 --full line: skip the row_orders leg")
+    ap.add_argument("--concurrency", default="1,2,4", help="N = 1 --full line: host threads submitting C2 jobs to the one engine (job contexts); '' = skip")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip other_configs, concurrency and row_orders")
+    ap.add_argument("--cpu-rows", type=int, default=0, help="--full: rows of the CPU sample (0 = chosen from the host's core count)")
     ap.add_argument("--dump-rows", default="", help="after the timed region run the step once more and save every rank's anomaly rows "
                                                      "(GLOBAL key ids) to <path>.rank<r>.npz — used by the N-rank == 1-rank parity test")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -712,7 +717,7 @@ def main():
     multi = args.tables > 1 and not strong and not args.host_input and args.ingest == "keys" and cfg["rows"] <= 100_000_000 and not args.dump_rows
     head = run_config(cfg["algos"], cfg["rows"], cfg["keys"], cfg["buckets"], cfg["agg"], args.steps, args.warmup,
                       ingest=args.ingest, host_input=args.host_input, hint=args.hint_lattice, tables=args.tables if multi else 1,
-                      same_columns_steps=max(1, args.steps // 2) if multi else 0, keep_outputs=bool(args.dump_outputs))
+                      same_columns_steps=max(1, args.steps // 2) if multi and args.full else 0, keep_outputs=bool(args.dump_outputs))
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, head["outputs"], "rank%d_" % rank if world > 1 else "", DUMP_LIMIT_BYTES // world)
     out = None
@@ -731,7 +736,9 @@ def main():
         if headline_is_c2:   # the PMC passes were taken on this workload
             out["roofline"]["traffic"] = pmc_traffic({2: "k_partition", 3: "k_partition_wc"}.get(head["stats"][0]["stage0_path"], "k_scatter"))
     cores = os.cpu_count() or 1
-    if world == 1 and headline_is_c2 and not args.no_other_configs and not args.host_input and args.ingest == "keys":
+    # --full: what the headline does not need, measured after it in the same process
+    extras = args.full and not args.no_other_configs and not args.host_input and args.ingest == "keys"
+    if world == 1 and headline_is_c2 and extras:
         # BASELINE.json configs[3] and configs[2], measured in the same run (their tables replace the C2 table in HBM)
         others = {}
         # C5 at N = 1 is the strong-scaling base of BASELINE.json configs[4] (the whole 1e9-row / 1e6-key table on one GPU)
@@ -761,7 +768,7 @@ def main():
                     d["cpu_baseline"] = {"error": repr(exc)[:200]}
             others[name] = d
         out["other_configs"] = others
-    if world > 1 and (headline_is_c2 or args.c5_shape) and not args.no_other_configs and not args.host_input and args.ingest == "keys":
+    if world > 1 and (headline_is_c2 or args.c5_shape) and extras:
         # BASELINE.json configs[4], the only config it names for 8 GPUs: the 1e9-row / 1e6-key table split over the N ranks (strong
         # scaling), one step = EWMA then ARIMA on the rank's shard — key-sharded (no data-path collective) and row-sharded
         # (tad_aggregate + one all-to-all(v) of the partial points to the key owners: the shuffle of anomaly_detection.py:664-684)
@@ -782,12 +789,12 @@ def main():
                 torch.cuda.empty_cache()
         if rank == 0:
             out["other_configs"] = {"c5": c5}
-    if world == 1 and headline_is_c2 and args.concurrency and not args.no_other_configs and not args.host_input and args.ingest == "keys":
+    if world == 1 and headline_is_c2 and args.concurrency and extras:
         try:
             out["concurrency"] = concurrency_leg(eng, [int(x) for x in args.concurrency.split(",") if x], out["ms_per_step"])
         except Exception as exc:
             out["concurrency"] = {"error": repr(exc)[:300]}
-    if world == 1 and headline_is_c2 and not args.no_other_configs and not args.host_input and args.ingest == "keys" and not args.no_row_orders:
+    if world == 1 and headline_is_c2 and extras and not args.no_row_orders:
         try:
             eng_o = TadEngine(device=dev.index, plan=plan)     # (an engine of its own: its contexts learn from the sorted tables)
             out["row_orders"] = row_orders_leg(eng_o, dev)
@@ -796,7 +803,7 @@ def main():
             out["row_orders"] = {"error": repr(exc)[:300]}
             torch.cuda.empty_cache()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             algo = cfg["algos"][-1] if len(cfg["algos"]) > 1 else cfg["algos"][0]
             cr, ck, sr = cpu_sample(algo, cfg["rows"], cfg["keys"], cores)
             if args.cpu_rows:

@@ -125,10 +125,10 @@ def test_bench_gpus_2_starts_two_ranks_by_itself():
 
 
 def test_bench_gpus_2_default_line_carries_c5_and_rccl_evidence():
-    """What the driver's `bench.py --gpus N` must put on the line at N > 1 (reduced sizes here, two ranks on one GPU over gloo): the
+    """What `bench.py --gpus N --full` must put on the line at N > 1 (reduced sizes here, two ranks on one GPU over gloo): the
     weak-scaled headline, BASELINE configs[4] (C5: EWMA then ARIMA, strong scaling) key-sharded AND row-sharded in other_configs, and
     the evidence that the collectives crossed ranks: ranks seen, all-gather wait, all-to-all bytes / time, per-rank step times."""
-    d = _self_launched(["--rows", "2000000", "--keys", "2000", "--steps", "3", "--warmup", "1", "--c5-shape", "600000,600,60"])
+    d = _self_launched(["--full", "--rows", "2000000", "--keys", "2000", "--steps", "3", "--warmup", "1", "--c5-shape", "600000,600,60"])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["tables"] == 4
     rc = d["rccl"]
     assert rc["world"] == 2 and rc["ranks_seen"] == 2 and rc["allgather_us_p50"] > 0 and rc["alltoall_bytes"] == 0

@@ -8,7 +8,7 @@ O=$R/gpurun_out/$1
 mkdir -p $O
 cd $R
 if [ "$2" != notests ]; then ( timeout 1200 python -m pytest tests -m gpu -q 2>&1 | tail -6 ) > $O/pytest.log 2>&1; fi
-timeout 900 python bench.py > $O/bench_default_line.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default_line.json 2> $O/bench_default.err
 timeout 120 python bench.py --host-input --steps 5 --warmup 1 --no-cpu-baseline --no-other-configs > $O/bench_host_input.json 2>/dev/null
 timeout 300 python tools/cold_probe.py --config c2 > $O/cold_c2.log 2>&1
 timeout 300 python tools/cold_probe.py --config c4 > $O/cold_c4.log 2>&1

@@ -5,7 +5,7 @@ O=$R/gpurun_out/$1
 mkdir -p $O
 cd $R
 ( timeout 1200 python -m pytest tests/test_gpu_arima.py tests/test_gpu_parity.py tests/test_gpu_fullsize.py -m gpu -q -k "arima or yields or concurrent or job_contexts or c3" 2>&1 | tail -8 ) > $O/pytest.log 2>&1
-timeout 900 python bench.py > $O/bench_default_line.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default_line.json 2> $O/bench_default.err
 cat $O/pytest.log; tail -3 $O/bench_default.err
 python - <<PY
 import json

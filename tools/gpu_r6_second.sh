@@ -6,7 +6,7 @@ O=$R/gpurun_out/$1
 mkdir -p $O
 cd $R
 ( timeout 1500 python -m pytest tests -m gpu -q -x 2>&1 | tail -15 ) > $O/pytest.log 2>&1
-timeout 900 python bench.py > $O/bench_default_line.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default_line.json 2> $O/bench_default.err
 timeout 300 python tools/cold_probe.py --config c2 > $O/cold_c2.log 2>&1
 timeout 300 python tools/cold_probe.py --config c4 > $O/cold_c4.log 2>&1
 cat $O/pytest.log $O/cold_c2.log $O/cold_c4.log; tail -3 $O/bench_default.err

@@ -127,6 +127,8 @@ type Job struct {
 	// DBSCAN parameters (tad_job.dbscan_eps / dbscan_min_samples): 0 = the reference's eps = 250000000, min_samples = 4
 	DBSCANEps        float64
 	DBSCANMinSamples int32
+	// ARIMA parameter (tad_job.arima_maxiter): 0 = statsmodels' maxiter = 50
+	ARIMAMaxIter int32
 }
 
 // Columns is one batch of flow rows after dictionary encoding; all slices have the same length.
@@ -259,6 +261,7 @@ func (e *Engine) Run(job Job, cols Columns) ([]Row, Stats, error) {
 	cj.value_op = C.TAD_OP_AUTO
 	cj.dbscan_eps = C.double(job.DBSCANEps)
 	cj.dbscan_min_samples = C.int32_t(job.DBSCANMinSamples)
+	cj.arima_maxiter = C.int32_t(job.ARIMAMaxIter)
 	cj.start_time = C.int64_t(job.StartTime)
 	cj.end_time = C.int64_t(job.EndTime)
 	id := []byte(job.ID)
@@ -627,11 +630,13 @@ func (e *Engine) CopyToHost(dst []byte, src unsafe.Pointer) error {
 
 // State is the per-key running EWMA state of a long-running detector (tad.h: tad_state, SURVEY.md 8f rank 3): Spark's streaming moments
 // (n, avg, m2), the last EWMA value and the last flowEndSeconds of every key, kept in HBM between batches.  A state made by
-// NewStateWithHistory also keeps every key's aggregated point values, sorted, for the streaming DBSCAN detector.
+// NewStateWithHistory also keeps every key's aggregated point values, sorted, for the streaming DBSCAN detector; one made by
+// NewStateWithSeries keeps them in time order, for the streaming ARIMA detector.
 type State struct {
 	e       *Engine
 	h       *C.tad_state
 	history bool
+	series  bool
 }
 
 var streamDBSCANOnce sync.Once
@@ -716,6 +721,92 @@ func (s *State) ImportHistory(length []uint64, values []uint64) error {
 	return nil
 }
 
+var streamARIMAOnce sync.Once
+var streamARIMAOK bool
+
+// hasStreamARIMA: the library knows series states and streaming ARIMA (tad_features); an older one would not export the calls.
+func hasStreamARIMA() bool {
+	streamARIMAOnce.Do(func() { streamARIMAOK = C.tad_features()&C.TAD_FEATURE_STREAM_ARIMA != 0 })
+	return streamARIMAOK
+}
+
+// NewStateWithSeries makes a state that also keeps every key's aggregated point values in time order (tad_state_create_ex with
+// TAD_STATE_SERIES; withHistory adds TAD_STATE_HISTORY): RunStream then takes Job.Algo == ARIMA, and each batch's rows are those the
+// batch job emits for the batch's points over everything seen so far.  The series grows with the points seen (SeriesPoints).
+func (e *Engine) NewStateWithSeries(numKeys uint64, withHistory bool) (*State, error) {
+	if !hasStreamARIMA() {
+		return nil, errors.New("tadengine: libtad_mi355x.so has no streaming ARIMA (TAD_FEATURE_STREAM_ARIMA)")
+	}
+	flags := C.uint32_t(C.TAD_STATE_SERIES)
+	if withHistory {
+		flags |= C.TAD_STATE_HISTORY
+	}
+	var h *C.tad_state
+	if rc := C.tad_state_create_ex(e.h, C.uint64_t(numKeys), flags, &h); rc != C.TAD_OK {
+		return nil, fmt.Errorf("tad_state_create_ex: %s (code %d)", C.GoString(C.tad_last_error(e.h)), int(rc))
+	}
+	return &State{e: e, h: h, history: withHistory, series: true}, nil
+}
+
+// SeriesPoints is the number of values the state's series holds (tad_state_series_points); 0 for a state without a series.
+func (s *State) SeriesPoints() (uint64, error) {
+	if !s.series {
+		return 0, nil
+	}
+	var n C.uint64_t
+	if rc := C.tad_state_series_points(s.e.h, s.h, &n); rc != C.TAD_OK {
+		return 0, fmt.Errorf("tad_state_series_points: %s (code %d)", C.GoString(C.tad_last_error(s.e.h)), int(rc))
+	}
+	return uint64(n), nil
+}
+
+// ExportSeries copies the series to the host (tad_state_export_series): per key its number of values, and every key's values in
+// time order, keys in order.
+func (s *State) ExportSeries(numKeys uint64) (length []uint64, values []uint64, err error) {
+	if !s.series {
+		return nil, nil, errors.New("tadengine: the state has no series")
+	}
+	total, err := s.SeriesPoints()
+	if err != nil {
+		return nil, nil, err
+	}
+	length, values = make([]uint64, numKeys), make([]uint64, total)
+	if numKeys == 0 {
+		return
+	}
+	var pv *C.uint64_t
+	if total > 0 {
+		pv = (*C.uint64_t)(unsafe.Pointer(&values[0]))
+	}
+	if rc := C.tad_state_export_series(s.e.h, s.h, (*C.uint64_t)(unsafe.Pointer(&length[0])), pv); rc != C.TAD_OK {
+		err = fmt.Errorf("tad_state_export_series: %s (code %d)", C.GoString(C.tad_last_error(s.e.h)), int(rc))
+	}
+	return
+}
+
+// ImportSeries restores what ExportSeries returned (tad_state_import_series), after Import of the moments: length[k] must equal the
+// key's n, else the state is left as it was.
+func (s *State) ImportSeries(length []uint64, values []uint64) error {
+	if !s.series {
+		return errors.New("tadengine: the state has no series")
+	}
+	if len(length) == 0 {
+		return errors.New("tadengine: empty state")
+	}
+	var pv *C.uint64_t
+	if len(values) > 0 {
+		pv = (*C.uint64_t)(unsafe.Pointer(&values[0]))
+	}
+	if rc := C.tad_state_import_series(s.e.h, s.h, (*C.uint64_t)(unsafe.Pointer(&length[0])), pv); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return IllegalArgument{msg}
+		}
+		return fmt.Errorf("tad_state_import_series: %s (code %d)", msg, int(rc))
+	}
+	return nil
+}
+
 func (e *Engine) NewState(numKeys uint64) (*State, error) {
 	var h *C.tad_state
 	if rc := C.tad_state_create(e.h, C.uint64_t(numKeys), &h); rc != C.TAD_OK {
@@ -732,8 +823,9 @@ func (s *State) Close() {
 }
 
 // RunStream aggregates ONE new batch and continues every key's recurrences over its new points (tad_run_stream): the rows are the points
-// with |x - ewma| > the running stddev_samp.  cols.NumKeys must equal the state's key count; job.Algo must be EWMA, or DBSCAN on a state
-// made by NewStateWithHistory (the rows are then the batch's points the batch job over everything seen so far calls noise).
+// with |x - ewma| > the running stddev_samp.  cols.NumKeys must equal the state's key count; job.Algo must be EWMA, DBSCAN on a state
+// made by NewStateWithHistory (the rows are then the batch's points the batch job over everything seen so far calls noise), or ARIMA on
+// a state made by NewStateWithSeries (the batch's points the batch job over everything seen so far calls anomalous).
 func (s *State) RunStream(job Job, cols Columns) ([]Row, error) {
 	bufs, n, narrow, err := columnBuffers(cols)
 	if err != nil {
@@ -743,6 +835,9 @@ func (s *State) RunStream(job Job, cols Columns) ([]Row, error) {
 	if job.Algo == DBSCAN && !s.history {
 		return nil, IllegalArgument{"tadengine: streaming DBSCAN needs a state made by NewStateWithHistory"}
 	}
+	if job.Algo == ARIMA && !s.series {
+		return nil, IllegalArgument{"tadengine: streaming ARIMA needs a state made by NewStateWithSeries"}
+	}
 	var cj C.tad_job
 	cj.flags = narrow
 	cj.algo = C.tad_algo(job.Algo)
@@ -750,6 +845,7 @@ func (s *State) RunStream(job Job, cols Columns) ([]Row, error) {
 	cj.value_op = C.TAD_OP_AUTO
 	cj.dbscan_eps = C.double(job.DBSCANEps)
 	cj.dbscan_min_samples = C.int32_t(job.DBSCANMinSamples)
+	cj.arima_maxiter = C.int32_t(job.ARIMAMaxIter)
 	var cc C.tad_columns
 	cc.n_rows = C.uint64_t(n)
 	cc.num_keys = C.uint64_t(cols.NumKeys)

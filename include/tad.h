@@ -73,6 +73,7 @@ typedef enum { TAD_MEM_HOST = 0, TAD_MEM_DEVICE = 1 } tad_mem;
 /* tad_features(): what this build of the library understands beyond TAD_ABI_VERSION */
 #define TAD_FEATURE_NARROW_COLUMNS 1u /* TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 are honoured */
 #define TAD_FEATURE_STREAM_DBSCAN 2u  /* tad_state_create_ex(TAD_STATE_HISTORY) and tad_run_stream with TAD_ALGO_DBSCAN */
+#define TAD_FEATURE_STREAM_ARIMA 4u   /* tad_state_create_ex(TAD_STATE_SERIES) and tad_run_stream with TAD_ALGO_ARIMA */
 
 typedef struct tad_engine tad_engine; /* opaque; one per GPU; runs up to max_jobs_in_flight jobs concurrently (ABI 12) */
 
@@ -378,7 +379,7 @@ int tad_host_free(tad_engine *e, void *ptr);
  * what the batch job computes over the concatenated table bit for bit (same operations in the same order): n, avg, m2
  * give its stddev_samp, ewma its last EWMA value.  A row not newer than its key's last_t is rejected
  * (TAD_ERR_INVALID_ARGUMENT) and the state is left untouched.  job->algo must be TAD_ALGO_EWMA (or TAD_ALGO_DBSCAN on a state
- * with history, below), and cols->num_keys must
+ * with history, TAD_ALGO_ARIMA on a state with a series, below), and cols->num_keys must
  * EQUAL the num_keys the state holds (a batch addresses the state's whole key space; keys without rows in the batch keep
  * their state) — anything else is TAD_ERR_INVALID_ARGUMENT.
  * ABI 13: a batch takes the Stage 0 rule of tad_run (tad_plan.sparse / sparse_sort / stage0 included), so second-resolution
@@ -417,7 +418,8 @@ int tad_run_stream(tad_engine *e, tad_state *s, const tad_job *job, const tad_co
  *   - points judged in earlier batches are not judged again.  A point can stop being noise once later points arrive; the stream
  *     reports each point once, when it arrives.
  * An EWMA batch on a history state appends to the history too; its rows and moments are those of the same batch on a plain state.
- * DBSCAN on a plain state is TAD_ERR_INVALID_ARGUMENT (state unchanged); ARIMA and DROP have no streaming form.
+ * DBSCAN on a plain state is TAD_ERR_INVALID_ARGUMENT (state unchanged); ARIMA needs a state with a series (below); DROP has no
+ * streaming form.
  * Invariant: after every successful call the history of key k holds n[k] values; a failed batch (late row, key out of range, out of
  * memory) leaves the history unchanged as well as the state.  The history is never evicted: it grows with the points seen (8 bytes
  * each, twice over: a batch merges into a second copy), and tad_state_history_points is how a caller watches it.  A batch costs an
@@ -432,6 +434,41 @@ int tad_state_export_history(tad_engine *e, const tad_state *s, uint64_t *len, u
 /* the inverse of tad_state_export_history, after tad_state_import of the moments: TAD_ERR_INVALID_ARGUMENT with the state unchanged
  * unless the state has history, len[k] == n[k] of the state for every k, and every key's values are ascending */
 int tad_state_import_history(tad_engine *e, tad_state *s, const uint64_t *len, const uint64_t *values);
+
+/* ---- streaming ARIMA: a state WITH A SERIES (TAD_FEATURE_STREAM_ARIMA; check tad_features() before calling these) ----
+ * tad_state_create_ex(e, num_keys, TAD_STATE_SERIES, &s) makes a state that keeps every key's aggregated point values IN TIME ORDER,
+ * in HBM, double-buffered with the moments: the series becomes current only when a batch succeeds.  TAD_STATE_HISTORY | TAD_STATE_SERIES
+ * (flags 3) keeps both, and every batch appends to both.  Unknown flag bits are TAD_ERR_INVALID_ARGUMENT.
+ * tad_run_stream with job->algo == TAD_ALGO_ARIMA on a series state, for one batch:
+ *   1. aggregates the batch with Stage 0 exactly as an EWMA batch does (dense grid or sparse sort, tad_run's rule and plan overrides);
+ *   2. advances the moments and last_t exactly as an EWMA batch does (a late row fails the batch: state, history and series unchanged);
+ *   3. appends the batch's new points to each key's series;
+ *   4. for every key with new points and a result: lambda and the Box-Cox transform over the key's whole series, and the predictions of
+ *      the NEW points only.  A new point at position p < 3 gets inv_boxcox(y_p); one at p >= 3 the walk-forward fit on y[0..p).  The
+ *      verdict is |x - pred| > stddev, stddev the key's stddev_samp from the post-batch moments;
+ *   5. emits the batch's new points in (key, time) order: throughput, algo_calc = the prediction, stddev (with TAD_FLAG_EMIT_ALL_POINTS
+ *      every new point of a key that has a result, with its verdict in `anomaly`).
+ * The rows of batch b are exactly the rows tad_run(ARIMA), run with the same job parameters on the concatenation of batches 1..b,
+ * emits for the points of batch b, bit for bit and in the same order, whatever Stage-0 path either side takes.  Consequences:
+ *   - a key with <= 3 points so far has no result, so its points are never reported; the same holds for a key whose series is
+ *     constant, contains a value <= 0, or whose Box-Cox fit fails;
+ *   - points reported in earlier batches are not revised (their predictions and lambda are those of their own batch);
+ *   - arima_maxiter may differ from batch to batch.
+ * The batch's stats: arima_fits = the fits this batch ran (new points at p >= 3 of keys with a result), keys_no_result = keys with new
+ * points that have no result; kalman_steps, arima_nan_fits and arima_relaunches as in tad_run.  A batch costs an EWMA stream batch, a
+ * rewrite of the series (about 16 B per series point), the Box-Cox fit over the touched keys' series and one ARIMA fit per new point:
+ * the fits of earlier points are never run again.  Its workspace follows the touched series (packed), not keys x longest series.
+ * An EWMA or DBSCAN batch on a series state appends to the series too; its rows are those of the same batch without a series.
+ * ARIMA on a plain or history-only state and DROP on any state are TAD_ERR_INVALID_ARGUMENT (state unchanged).
+ * Invariant: after every successful call the series of key k holds n[k] values.  tad_state_resize gives the added keys empty series. */
+#define TAD_STATE_SERIES 2u            /* keep every key's aggregated point values (time order) */
+/* total values in the series (0 for a state without a series) */
+int tad_state_series_points(tad_engine *e, const tad_state *s, uint64_t *n_points);
+/* HOST arrays: len[num_keys] and values[n_points], each key's values in time order, keys in order */
+int tad_state_export_series(tad_engine *e, const tad_state *s, uint64_t *len, uint64_t *values);
+/* the inverse of tad_state_export_series, after tad_state_import of the moments: TAD_ERR_INVALID_ARGUMENT with the state unchanged
+ * unless the state has a series and len[k] == n[k] of the state for every k */
+int tad_state_import_series(tad_engine *e, tad_state *s, const uint64_t *len, const uint64_t *values);
 
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).

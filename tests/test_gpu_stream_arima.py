@@ -1,0 +1,455 @@
+"""GPU: streaming ARIMA (tad_run_stream with TAD_ALGO_ARIMA on a state with a series, include/tad.h).  The defining property: the rows
+of batch b are exactly the rows tad_run(ARIMA) emits, over batches 1..b concatenated with the same job parameters, for the points of
+batch b — key, time, throughput, algo_calc and stddev bit for bit, in the same order (emit_all: all of batch b's points of keys with a
+result, with their verdicts).  Float columns are compared as uint64 bit patterns.  The series holds n[k] values per key, in time order,
+after every batch, and a failed batch leaves state, history and series as they were."""
+import threading
+
+import numpy as np
+import pytest
+
+from oracle import arima_oracle as ao
+from oracle import tad_oracle as orc
+from theia_amd import TadEngine, TadError
+
+pytestmark = pytest.mark.gpu
+
+T_BASE = 1660202814
+ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
+STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
+SKIP = np.uint64((1 << 64) - 1)
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
+
+
+def rows_of(res):
+    d = {f: np.asarray(res[f]) for f in ROW_FIELDS}
+    if "anomaly" in res.to_host():
+        d["anomaly"] = np.asarray(res["anomaly"])
+    return d
+
+
+def point_codes(k, t, k2=None):
+    """(key, time) of the batch's points as one uint64 code (key << 32 | t - T_BASE + 2^31)"""
+    ks = [np.asarray(k, np.uint64)] + ([np.asarray(k2, np.uint64)] if k2 is not None else [])
+    tt = (np.asarray(t, np.int64) - T_BASE + (1 << 31)).astype(np.uint64)
+    out = [(kk[kk != SKIP] << np.uint64(32)) | tt[kk != SKIP] for kk in ks]
+    return np.unique(np.concatenate(out))
+
+
+def restrict(rows, codes):
+    c = (rows["key_id"].astype(np.uint64) << np.uint64(32)) | (rows["flow_end_s"].astype(np.int64) - T_BASE + (1 << 31)).astype(np.uint64)
+    sel = np.isin(c, codes)
+    return {f: a[sel] for f, a in rows.items()}
+
+
+def assert_rows(got, want, what=""):
+    assert set(got) == set(want), (what, sorted(got), sorted(want))
+    assert got["key_id"].size == want["key_id"].size, (what, got["key_id"].size, want["key_id"].size)
+    for f in want:
+        assert np.array_equal(bits(got[f]), bits(want[f])), (what, f)
+
+
+def concat(batches, upto):
+    return [np.concatenate([b[i] for b in batches[:upto + 1]]) for i in range(len(batches[0]))]
+
+
+def job_rows(engine, K, batches, upto, op="auto", emit_all=False, pod=False, maxiter=0, stats=False):
+    """tad_run(ARIMA) over batches[0..upto] concatenated, restricted to batch `upto`'s points"""
+    cat = concat(batches, upto)
+    kw = dict(key_id2=cat[3]) if pod else {}
+    res = engine.run("ARIMA", cat[0], cat[1], cat[2], K, agg_flow="pod" if pod else "svc", value_op=op, emit_all=emit_all, maxiter=maxiter, **kw)
+    b = batches[upto]
+    rows = restrict(rows_of(res), point_codes(b[0], b[1], b[3] if pod else None))
+    return (rows, res.stats) if stats else rows
+
+
+def minute_batches(n_rows, K, T, cuts, pod=False):
+    k, t, v = orc.synth_rows(0, n_rows, K, T)
+    bucket = (t - orc.SYNTH_T_BASE) // orc.SYNTH_T_STEP
+    edges = (0,) + tuple(cuts) + (T,)
+    k2 = ((k + np.uint64(7)) % np.uint64(K)).astype(np.uint64)
+    out = []
+    for lo, hi in zip(edges[:-1], edges[1:]):
+        sel = (bucket >= lo) & (bucket < hi)
+        out.append((k[sel], t[sel], v[sel]) + ((k2[sel],) if pod else ()))
+    return out
+
+
+def second_batches(K, pts_per_key, rows_per_point, seed, span, width):
+    rng = np.random.default_rng(seed)
+    pts = np.broadcast_to(np.asarray(pts_per_key, dtype=np.int64), (K,))
+    pk = np.repeat(np.arange(K, dtype=np.uint64), pts)
+    pt = T_BASE + rng.integers(0, span, size=pk.size).astype(np.int64)
+    base = 1_000_000_000 + (orc.mix64(pk + np.uint64(5)) % np.uint64(3_000_000_000)).astype(np.int64)
+    k, t = np.repeat(pk, rows_per_point), np.repeat(pt, rows_per_point)
+    v = (np.repeat(base, rows_per_point) + rng.integers(-300_000_000, 300_000_000, size=k.size)).astype(np.uint64)
+    order = rng.permutation(k.size)
+    k, t, v = k[order], t[order], v[order]
+    b = (t - T_BASE) // width
+    return [(k[b == h], t[b == h], v[b == h]) for h in range(int(b.max()) + 1)]
+
+
+def snapshot(st):
+    return st.export(), st.export_history() if st.history else None, st.export_series() if st.series else None
+
+
+def assert_unchanged(st, snap):
+    s, h, r = snapshot(st)
+    for f in STATE_FIELDS:
+        assert np.array_equal(bits(s[f]), bits(snap[0][f])), f
+    for a, b in ((h, snap[1]), (r, snap[2])):
+        if a is not None:
+            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+def assert_series(engine, st, K, batches, upto, op="auto", pod=False):
+    """series_points() == n.sum(); every key's series = its aggregated values of the concatenation in time order"""
+    n = st.export()["n"]
+    ln, vals = st.export_series()
+    assert st.series_points() == int(n.sum()) == vals.size
+    assert np.array_equal(ln, n.astype(np.uint64))
+    cat = concat(batches, upto)
+    kw = dict(key_id2=cat[3]) if pod else {}
+    pts = engine.aggregate(cat[0], cat[1], cat[2], K, agg_flow="pod" if pod else "svc", value_op=op, **kw)
+    pk, pt, pv = np.asarray(pts["key_id"]), np.asarray(pts["flow_end_s"]), np.asarray(pts["value"])
+    order = np.lexsort((pt, pk))
+    assert np.array_equal(vals, pv[order])
+
+
+# ---- 1. batches equal the batch job ----
+@pytest.mark.parametrize("emit_all", [False, True])
+@pytest.mark.parametrize("op", ["sum", "max"])
+def test_minute_batches_equal_the_batch_job(engine, emit_all, op):
+    K = 80
+    batches = minute_batches(30000, K, 48, (2, 5, 20, 33))
+    st = engine.state_create(K, series=True)
+    for b, (bk, bt, bv) in enumerate(batches):
+        got = engine.run_stream(st, bk, bt, bv, agg_flow="svc", value_op=op, algo="ARIMA", emit_all=emit_all)
+        assert_rows(rows_of(got), job_rows(engine, K, batches, b, op, emit_all=emit_all), b)
+        if emit_all:
+            assert got.n_rows > 0 or b == 0
+    assert_series(engine, st, K, batches, len(batches) - 1, op)
+    st.close()
+
+
+def test_second_resolution_connection_keys(engine):
+    K = 5000     # (5000 keys x an hour of seconds: the dense grid would be 18M cells for 30k points — the batches go sparse)
+    batches = second_batches(K, 12, 2, seed=5, span=4 * 3600, width=3600)
+    st = engine.state_create(K, series=True)
+    for b, (bk, bt, bv) in enumerate(batches):
+        got = engine.run_stream(st, bk, bt, bv, value_op="max", algo="ARIMA", emit_all=True)
+        assert got.stats["stage0_path"] in (4, 8), got.stats["stage0_path"]
+        assert_rows(rows_of(got), job_rows(engine, K, batches, b, "max", emit_all=True), b)
+    assert_series(engine, st, K, batches, len(batches) - 1, "max")
+    st.close()
+
+
+def test_pod_mode_and_narrow_columns(engine):
+    K = 60
+    batches = minute_batches(20000, K, 40, (10, 25), pod=True)
+    st = engine.state_create(K, series=True)
+    for b, (bk, bt, bv, bk2) in enumerate(batches):
+        got = engine.run_stream(st, bk, bt, bv, agg_flow="pod", key_id2=bk2, algo="ARIMA", emit_all=True)
+        assert_rows(rows_of(got), job_rows(engine, K, batches, b, emit_all=True, pod=True), b)
+    assert_series(engine, st, K, batches, len(batches) - 1, pod=True)
+    st.close()
+
+    batches = minute_batches(20000, K, 40, (10, 25))
+    st = engine.state_create(K, series=True)
+    for b, (bk, bt, bv) in enumerate(batches):
+        got = engine.run_stream(st, bk.astype(np.uint32), bt.astype(np.uint32), bv, agg_flow="svc", algo="ARIMA")
+        assert_rows(rows_of(got), job_rows(engine, K, batches, b), b)
+    st.close()
+
+
+@pytest.mark.parametrize("plan,paths", [({"sparse": "never"}, (1, 2, 3)), ({"sparse": "always", "sparse_sort": "lsd"}, (4,))])
+def test_forced_stage0_forms(engine, plan, paths):
+    K = 70
+    batches = minute_batches(20000, K, 36, (4, 18))
+    with engine.plan(**plan):
+        st = engine.state_create(K, series=True)
+        got = []
+        for bk, bt, bv in batches:
+            r = engine.run_stream(st, bk, bt, bv, agg_flow="svc", algo="ARIMA", emit_all=True)
+            assert r.stats["stage0_path"] in paths, r.stats["stage0_path"]
+            got.append(rows_of(r))
+        st.close()
+    for b in range(len(batches)):   # (the batch job in its own, automatic form: equal whatever path either side took)
+        assert_rows(got[b], job_rows(engine, K, batches, b, emit_all=True), b)
+
+
+# ---- 2. the oracle ----
+def test_oracle_leg(engine):
+    K = 40
+    batches = minute_batches(12000, K, 30, (8, 19))
+    st = engine.state_create(K, series=True)
+    for b, (bk, bt, bv) in enumerate(batches):
+        got = rows_of(engine.run_stream(st, bk, bt, bv, agg_flow="svc", algo="ARIMA", emit_all=True))
+        cat = concat(batches, b)
+        pk, pt, pv = orc.stage0(cat[0], cat[1], cat[2], "sum")
+        keys, ptr = orc.series_offsets(pk)
+        codes = point_codes(bk, bt)
+        for i in range(0, keys.size, 3):
+            x = orc.u64_to_f64(pv[ptr[i]:ptr[i + 1]])
+            want = ao.calculate_arima_exact(x)
+            mine = np.isin((pk[ptr[i]:ptr[i + 1]] << np.uint64(32)) | (pt[ptr[i]:ptr[i + 1]] - T_BASE + (1 << 31)).astype(np.uint64), codes)
+            sel = got["key_id"] == keys[i]
+            if want is None:
+                assert not sel.any(), (b, keys[i])
+                continue
+            sg = orc.stddev_samp_series(x)
+            pred = np.asarray(want)[mine]
+            assert np.array_equal(bits(got["algo_calc"][sel]), bits(pred)), (b, keys[i])
+            assert (got["stddev"][sel] == sg).all()
+            assert np.array_equal(got["anomaly"][sel].astype(bool), np.abs(x[mine] - pred) > sg), (b, keys[i])
+    st.close()
+
+
+# ---- 3. work: the history is not refitted ----
+def test_fits_follow_the_new_points(engine):
+    K = 100
+    batches = minute_batches(40000, K, 60, (40, 50))
+    st = engine.state_create(K, series=True)
+    for b, (bk, bt, bv) in enumerate(batches):
+        n0 = st.export()["n"].astype(np.int64)
+        got = engine.run_stream(st, bk, bt, bv, agg_flow="svc", algo="ARIMA", emit_all=True)
+        n1 = st.export()["n"].astype(np.int64)
+        want, jst = job_rows(engine, K, batches, b, emit_all=True, stats=True)
+        assert_rows(rows_of(got), want, b)
+        with_result = np.isin(np.arange(K), np.asarray(want["key_id"]).astype(np.int64))   # (emit_all: every touched key with a result has rows)
+        fits = int(np.clip(n1 - np.maximum(n0, 3), 0, None)[with_result].sum())
+        assert got.stats["arima_fits"] == fits, (b, got.stats["arima_fits"], fits)
+        touched = n1 > n0
+        assert got.stats["keys_no_result"] == int((touched & ~with_result).sum()), b
+        if b > 0:
+            assert got.stats["arima_fits"] * 3 < jst["arima_fits"], (b, got.stats["arima_fits"], jst["arima_fits"])
+    st.close()
+
+
+# ---- 4. edge keys ----
+def test_edge_keys_and_maxiter(engine):
+    rng = np.random.default_rng(3)
+    K = 6
+    t0 = T_BASE - T_BASE % 60
+
+    def batch(lo, hi, vals):
+        k, t, v = [], [], []
+        for key, f in vals.items():
+            for j in range(lo, hi):
+                x = f(j)
+                if x is None:
+                    continue
+                k.append(key); t.append(t0 + 60 * j); v.append(x)
+        return np.array(k, np.uint64), np.array(t, np.int64), np.array(v, np.uint64)
+
+    noise = lambda j: int(2_000_000_000 + rng.integers(0, 400_000_000))
+    series = {
+        0: lambda j: noise(j) if j in (0, 1, 4, 5, 6) else None,                       # 2 points, then crosses 3 inside batch 2
+        1: lambda j: 1_000_000 if j < 6 else noise(j),                                  # constant, then varies
+        2: lambda j: 0 if j == 9 else noise(j),                                         # a zero value in batch 2: no result from then on
+        3: noise,
+        4: lambda j: noise(j) if j < 3 else None,                                       # <= 3 points, never a result
+        5: lambda j: noise(j) if j % 2 else None,
+    }
+    edges = (0, 4, 12, 20, 28)
+    batches = [batch(lo, hi, series) for lo, hi in zip(edges[:-1], edges[1:])]
+    st = engine.state_create(K, series=True)
+    for b, ((bk, bt, bv), mi) in enumerate(zip(batches, (0, 7, 30, 3))):
+        got = engine.run_stream(st, bk, bt, bv, agg_flow="svc", algo="ARIMA", emit_all=True, maxiter=mi)
+        assert_rows(rows_of(got), job_rows(engine, K, batches, b, emit_all=True, maxiter=mi), b)
+        assert 4 not in set(np.asarray(got["key_id"]).tolist())
+    st.close()
+
+
+# ---- 5. skewed series lengths under a workspace limit ----
+def test_skew_under_a_workspace_limit():
+    K = 2000
+    rng = np.random.default_rng(11)
+    long_t = T_BASE + np.arange(3000, dtype=np.int64) * 7
+    long_v = (2_000_000_000 + rng.integers(0, 500_000_000, size=long_t.size)).astype(np.uint64)
+    short_k = np.repeat(np.arange(1, K, dtype=np.uint64), 6)
+    short_t = T_BASE + rng.integers(0, 3000 * 7, size=short_k.size).astype(np.int64)
+    short_v = (1_000_000_000 + rng.integers(0, 800_000_000, size=short_k.size)).astype(np.uint64)
+    k = np.concatenate([np.zeros(long_t.size, np.uint64), short_k])
+    t = np.concatenate([long_t, short_t])
+    v = np.concatenate([long_v, short_v])
+    cut = T_BASE + 3000 * 7 * 2 // 3
+    batches = [(k[t < cut], t[t < cut], v[t < cut]), (k[t >= cut], t[t >= cut], v[t >= cut])]
+    limit = 256 << 20     # touched keys x longest series x (tad_run's ~97 B per cell) would be 2000 x 3000 x 97 = 582 MB
+    eng = TadEngine(device=0, workspace_limit=limit)
+    try:
+        st = eng.state_create(K, series=True)
+        for b, (bk, bt, bv) in enumerate(batches):
+            got = eng.run_stream(st, bk, bt, bv, value_op="max", algo="ARIMA", emit_all=True)
+            assert_rows(rows_of(got), job_rows(eng, K, batches, b, "max", emit_all=True), b)
+        st.close()
+    finally:
+        eng.close()
+
+
+# ---- 6. the series: restart, bad length, growth ----
+def test_restart_and_growth(engine):
+    K = 90
+    batches = minute_batches(30000, K, 60, (20, 40, 50))
+    ref = engine.state_create(K, series=True)
+    for bk, bt, bv in batches[:2]:
+        engine.run_stream(ref, bk, bt, bv, agg_flow="svc", algo="ARIMA")
+    assert_series(engine, ref, K, batches, 1)
+    moments, (ln, vals) = ref.export(), ref.export_series()
+
+    fresh = engine.state_create(K, series=True)
+    fresh.load(moments)
+    snap = snapshot(fresh)
+    bad = ln.copy()
+    kk = int(np.flatnonzero(ln > 0)[0])
+    bad[kk] -= 1
+    with pytest.raises(TadError) as ei:
+        fresh.load_series(bad, vals[:-1])
+    assert ei.value.code == -1
+    assert_unchanged(fresh, snap)
+    hist_only = engine.state_create(K, history=True)
+    hist_only.load(moments)
+    with pytest.raises(TadError) as ei:
+        hist_only.load_series(ln, vals)
+    assert ei.value.code == -1 and hist_only.series_points() == 0
+    hist_only.close()
+
+    fresh.load_series(ln, vals)
+    assert fresh.series_points() == vals.size
+    bk, bt, bv = batches[2]
+    a = engine.run_stream(ref, bk, bt, bv, agg_flow="svc", algo="ARIMA", emit_all=True)
+    b = engine.run_stream(fresh, bk, bt, bv, agg_flow="svc", algo="ARIMA", emit_all=True)
+    assert_rows(rows_of(b), rows_of(a))
+    ref.close()
+
+    K2 = K + 40
+    ln1, vals1 = fresh.export_series()
+    fresh.resize(K2)
+    ln2, vals2 = fresh.export_series()
+    assert ln2.size == K2 and (ln2[K:] == 0).all() and np.array_equal(ln2[:K], ln1) and np.array_equal(vals2, vals1)
+    rng = np.random.default_rng(4)
+    t_next = int(batches[2][1].max()) + 60
+    nk = np.repeat(np.arange(K2, dtype=np.uint64), 8)
+    nt = t_next + 60 * np.tile(np.arange(8, dtype=np.int64), K2)
+    nv = (2_000_000_000 + rng.integers(0, 300_000_000, size=nk.size)).astype(np.uint64)
+    grown = batches[:3] + [(nk, nt, nv)]
+    got = engine.run_stream(fresh, nk, nt, nv, agg_flow="svc", algo="ARIMA", emit_all=True)
+    assert_rows(rows_of(got), job_rows(engine, K2, grown, 3, "sum", emit_all=True))
+    assert (np.asarray(got["key_id"]) >= K).any()
+    assert_series(engine, fresh, K2, grown, 3, "sum")
+    fresh.close()
+
+
+# ---- 7. the other detectors on a history + series state ----
+def test_ewma_and_dbscan_on_a_history_and_series_state(engine):
+    K = 80
+    batches = minute_batches(20000, K, 40, (15, 30))
+    both = engine.state_create(K, history=True, series=True)
+    hist = engine.state_create(K, history=True)
+    plain = engine.state_create(K)
+    for b, (bk, bt, bv) in enumerate(batches):
+        algo = "EWMA" if b != 1 else "DBSCAN"
+        r_both = rows_of(engine.run_stream(both, bk, bt, bv, agg_flow="svc", algo=algo, emit_all=True, eps=3e6))
+        r_hist = rows_of(engine.run_stream(hist, bk, bt, bv, agg_flow="svc", algo=algo, emit_all=True, eps=3e6))
+        assert_rows(r_both, r_hist, b)
+        if algo == "EWMA":
+            assert_rows(r_both, rows_of(engine.run_stream(plain, bk, bt, bv, agg_flow="svc", emit_all=True)), b)
+        else:
+            engine.run_stream(plain, bk, bt, bv, agg_flow="svc")
+        n = both.export()["n"]
+        assert both.series_points() == both.history_points() == int(n.sum())
+        assert_series(engine, both, K, batches, b)
+    for f in STATE_FIELDS:
+        assert np.array_equal(bits(both.export()[f]), bits(plain.export()[f])), f
+    # an ARIMA batch on the same state then equals the batch job
+    rng = np.random.default_rng(8)
+    t_next = int(batches[-1][1].max()) + 60
+    nk = rng.integers(0, K, size=3000).astype(np.uint64)
+    nt = t_next + 60 * rng.integers(0, 6, size=nk.size).astype(np.int64)
+    nv = (2_000_000_000 + rng.integers(0, 300_000_000, size=nk.size)).astype(np.uint64)
+    more = batches + [(nk, nt, nv)]
+    got = engine.run_stream(both, nk, nt, nv, agg_flow="svc", algo="ARIMA", emit_all=True)
+    assert_rows(rows_of(got), job_rows(engine, K, more, len(more) - 1, "sum", emit_all=True))
+    for s in (both, hist, plain):
+        s.close()
+
+
+# ---- 8. rejections ----
+def test_rejections(engine):
+    K = 60
+    batches = minute_batches(12000, K, 40, (20,))
+    for kind in ("plain", "history"):
+        st = engine.state_create(K, history=kind == "history")
+        engine.run_stream(st, *batches[0], agg_flow="svc")
+        snap = snapshot(st)
+        with pytest.raises(TadError) as ei:
+            engine.run_stream(st, *batches[1], agg_flow="svc", algo="ARIMA")
+        assert ei.value.code == -1
+        assert_unchanged(st, snap)
+        with pytest.raises(TadError):
+            st.export_series()
+        assert st.series_points() == 0
+        st.close()
+
+    st = engine.state_create(K, history=True, series=True)
+    engine.run_stream(st, *batches[0], agg_flow="svc", algo="ARIMA")
+    snap = snapshot(st)
+    with pytest.raises(TadError) as ei:
+        engine.run_stream(st, *batches[1], agg_flow="svc", algo="DROP")
+    assert ei.value.code == -1
+    assert_unchanged(st, snap)
+    with pytest.raises(TadError) as ei:                                      # a late row (batch 0 again)
+        engine.run_stream(st, *batches[0], agg_flow="svc", algo="ARIMA")
+    assert ei.value.code == -1
+    assert_unchanged(st, snap)
+    got = engine.run_stream(st, *batches[1], agg_flow="svc", algo="ARIMA", emit_all=True)   # the state goes on as if nothing had happened
+    assert_rows(rows_of(got), job_rows(engine, K, batches, 1, "sum", emit_all=True))
+    st.close()
+
+
+def test_state_flags(engine):
+    import ctypes as C
+    h = C.c_void_p()
+    assert engine._lib.tad_state_create_ex(engine._h, 10, 3, C.byref(h)) == 0 and h.value   # history and series together
+    engine._lib.tad_state_destroy(engine._h, h)
+    for flags in (4, 6, 0x80000002):                                                         # unknown bits stay rejected
+        h = C.c_void_p()
+        assert engine._lib.tad_state_create_ex(engine._h, 10, flags, C.byref(h)) == -1 and not h.value, flags
+
+
+# ---- 9. concurrency: the fit yields to partition-path jobs and still gives the serial rows ----
+def test_concurrent_partition_jobs(engine):
+    K = 300
+    batches = minute_batches(60000, K, 80, (60,))
+    serial = engine.state_create(K, series=True)
+    for bk, bt, bv in batches:
+        want = rows_of(engine.run_stream(serial, bk, bt, bv, agg_flow="svc", algo="ARIMA", emit_all=True))
+    serial.close()
+
+    k, t, v = orc.synth_rows(1, 1 << 22, 5000, 60)
+    stop = threading.Event()
+    errors = []
+
+    def ewma_jobs():
+        try:
+            while not stop.is_set():
+                engine.run("EWMA", k, t, v, 5000, agg_flow="svc")
+        except Exception as ex:   # noqa: BLE001 - reported below
+            errors.append(ex)
+
+    th = threading.Thread(target=ewma_jobs)
+    th.start()
+    try:
+        st = engine.state_create(K, series=True)
+        for bk, bt, bv in batches:
+            got = rows_of(engine.run_stream(st, bk, bt, bv, agg_flow="svc", algo="ARIMA", emit_all=True))
+        st.close()
+    finally:
+        stop.set()
+        th.join(timeout=120)
+    assert not errors, errors
+    assert_rows(got, want)

@@ -21,6 +21,8 @@ TAD_KEY_SKIP32 = (1 << 32) - 1
 TAD_FEATURE_NARROW_COLUMNS = 1               # tad_features() bit: the library honours the two flags above
 TAD_FEATURE_STREAM_DBSCAN = 2                # tad_features() bit: tad_state_create_ex(TAD_STATE_HISTORY), tad_run_stream with DBSCAN
 TAD_STATE_HISTORY = 1                        # tad_state_create_ex flag: keep every key's aggregated point values (sorted)
+TAD_FEATURE_STREAM_ARIMA = 4                 # tad_features() bit: tad_state_create_ex(TAD_STATE_SERIES), tad_run_stream with ARIMA
+TAD_STATE_SERIES = 2                         # tad_state_create_ex flag: keep every key's aggregated point values (time order)
 
 
 class Plan(C.Structure):
@@ -124,6 +126,9 @@ SYMBOLS = {
     "tad_state_history_points": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(u64)]),
     "tad_state_export_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_state_import_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tad_state_series_points": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(u64)]),
+    "tad_state_export_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tad_state_import_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_run_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_aggregate": (C.c_int, [C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Points))]),
     "tad_points_free": (None, [C.c_void_p, C.POINTER(Points)]),

@@ -964,11 +964,28 @@ __device__ unsigned long long g_arima_prof[8];
 #define TAD_PROF_ADD(slot, t0, t1)
 #endif
 
+// The fits of a streaming batch (k_arima_fit_list): per-position lists of the new points' fits instead of every key at every position.
+// Key indices of the body are then slots of the batch's touched keys; ws.ysk is packed (a slot's series at yoff[slot], a multiple of 8),
+// ws.u0 and ws.cursor are indexed by fit and by position, and the results go to the new points (index ibase[slot] + p).
+struct FitList {
+  const uint32_t *wave_pos;            // [wavefronts] the position of each wavefront (heaviest first)
+  const uint32_t *cnt;                 // [positions] fits at position p
+  const unsigned long long *loff;      // [positions] the first of them in list
+  const uint32_t *list;                // [fits] the slot of each fit, position by position
+  const unsigned long long *yoff;      // [slots] offset of the slot's series in ws.ysk
+  const unsigned long long *ibase;     // [slots] new-point index of position 0 (wraps: + p >= the key's old length brings it back)
+  const unsigned long long *nv;        // [new points] their values
+  double *pcalc;                       // [new points] the prediction
+  uint8_t *pflag;                      // [new points] the verdict
+};
+
+template <bool kList>
 __device__ __forceinline__ void arima_fit_body(Grid g, ArimaWs ws, const double *__restrict__ sigma,
                                                const uint32_t *__restrict__ n_pts, int maxiter, uint32_t pmax, uint32_t chunk,
-                                               double *__restrict__ calc, DevCounters *ctr, double *buf, double *park, const int *pause, uint32_t grace) {
+                                               double *__restrict__ calc, DevCounters *ctr, double *buf, double *park, const int *pause, uint32_t grace,
+                                               const FitList &fl) {
   const uint32_t nchunks = (uint32_t)((g.K + chunk - 1) / chunk);   // wavefronts per position
-  const uint32_t p = pmax - 1 - blockIdx.x / nchunks;           // heaviest (longest history) positions first
+  const uint32_t p = kList ? fl.wave_pos[blockIdx.x] : pmax - 1 - blockIdx.x / nchunks;           // heaviest (longest history) positions first
   const unsigned lane = threadIdx.x;
   bool dry = false;                                             // wave-uniform: position p has no key left to hand out
   bool yielded = false;                                         // wave-uniform: ... or the engine asked the fit to make room (cooperative yield)
@@ -1005,18 +1022,34 @@ __device__ __forceinline__ void arima_fit_body(Grid g, ArimaWs ws, const double 
       unsigned long long first = 0;
       if (lane == 0) first = atomicAdd(&ws.cursor[p], (unsigned long long)__popcll(m));
       first = __shfl(first, 0);
-      if (first >= g.K) { dry = true; break; }
+      // (if constexpr throughout the lambdas: the list form's names must not become captures of k_arima_fit's closures)
+      if constexpr (kList) {
+        if (first >= (uint64_t)fl.cnt[p]) { dry = true; break; }
+      } else if (first >= g.K) { dry = true; break; }
       const uint64_t cand = first + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
-      if (!busy && cand < g.K && ws.state[cand] == 0 && n_pts[cand] > p) {
+      if constexpr (kList) {
+        if (!busy && cand < (uint64_t)fl.cnt[p]) {
+          const size_t f = fl.loff[p] + cand;
+          k = fl.list[f];
+          busy = true;
+          lbfgs_reset(o, ws.u0[0][f], ws.u0[1][f], ws.u0[2][f]);
+        }
+      } else if (!busy && cand < g.K && ws.state[cand] == 0 && n_pts[cand] > p) {
         k = cand;
         busy = true;
         const size_t c = (size_t)p * g.K + k;
         lbfgs_reset(o, ws.u0[0][c], ws.u0[1][c], ws.u0[2][c]);
       }
     }
-    const unsigned long long mine = busy ? (unsigned long long)k : 0ull;   // idle lanes: row 0 (valid memory, values unused)
+    if constexpr (kList) {
+      const unsigned long long mine = busy ? fl.yoff[k] : 0ull;           // idle lanes: offset 0 (valid memory, values unused)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) row[j] = (size_t)__shfl(mine, j * 16 + (int)(lane >> 2)) * ws.Tpad + (lane & 3u) * 2u;
+      for (int j = 0; j < 4; ++j) row[j] = (size_t)__shfl(mine, j * 16 + (int)(lane >> 2)) + (lane & 3u) * 2u;
+    } else {
+      const unsigned long long mine = busy ? (unsigned long long)k : 0ull;   // idle lanes: row 0 (valid memory, values unused)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) row[j] = (size_t)__shfl(mine, j * 16 + (int)(lane >> 2)) * ws.Tpad + (lane & 3u) * 2u;
+    }
   };
 
   // one pass over the series: the four recursions of the contract (the difference y_t - y_t-1 is shared by them)
@@ -1024,7 +1057,9 @@ __device__ __forceinline__ void arima_fit_body(Grid g, ArimaWs ws, const double 
     KfStateC s4[4];
     double yprev;
     {   // t = 0 (burned) up front, from the lane's own first value: p11 and r0 are not carried through the loop
-      const double y0 = ws.ysk[(size_t)(busy ? k : 0ull) * ws.Tpad];
+      double y0;
+      if constexpr (kList) y0 = ws.ysk[busy ? fl.yoff[k] : 0ull];
+      else y0 = ws.ysk[(size_t)(busy ? k : 0ull) * ws.Tpad];
       yprev = y0;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -1128,11 +1163,19 @@ __device__ __forceinline__ void arima_fit_body(Grid g, ArimaWs ws, const double 
       for (int i = 0; i < 3; ++i) gr[i] = (nll[i + 1] - nll[0]) / dx[i];
       lbfgs_deliver(o, nll[0], gr, fc0, maxiter);
       if (o.done) {
-        const size_t st = g.K;
-        const uint64_t c = (uint64_t)ws.tpos[(size_t)p * st + k] * g.K + k;
-        const double pred = inv_boxcox(o.fc, ws.lam[k]);
-        calc[c] = pred;
-        if (fabs(ws.xs[(size_t)p * st + k] - pred) > sigma[k]) g.flag[c] = FLAG_PRESENT | FLAG_ANOMALY;
+        double pred;
+        if constexpr (kList) {
+          const uint64_t i = fl.ibase[k] + p;
+          pred = inv_boxcox(o.fc, ws.lam[k]);
+          fl.pcalc[i] = pred;
+          fl.pflag[i] = fabs((double)fl.nv[i] - pred) > sigma[k] ? 1 : 0;
+        } else {
+          const size_t st = g.K;
+          const uint64_t c = (uint64_t)ws.tpos[(size_t)p * st + k] * g.K + k;
+          pred = inv_boxcox(o.fc, ws.lam[k]);
+          calc[c] = pred;
+          if (fabs(ws.xs[(size_t)p * st + k] - pred) > sigma[k]) g.flag[c] = FLAG_PRESENT | FLAG_ANOMALY;
+        }
         if (!tad_finite(pred)) nanfits++;   // the optimiser walked into a non-finite likelihood: the point can never be an anomaly
         fits++;
         busy = false;
@@ -1181,7 +1224,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TAD_ARIMA_WA
     uint32_t chunk, double *__restrict__ calc, DevCounters *ctr, const int *pause, uint32_t grace) {
   __shared__ double buf[64 * (kStage + 1)];
   __shared__ double park[64 * kParkDoubles];
-  arima_fit_body(g, ws, sigma, n_pts, maxiter, pmax, chunk, calc, ctr, buf, park, pause, grace);
+  arima_fit_body<false>(g, ws, sigma, n_pts, maxiter, pmax, chunk, calc, ctr, buf, park, pause, grace, FitList{});
+}
+
+// The fits of a streaming batch (tad_run_stream, TAD_ALGO_ARIMA): the same body over per-position lists of the new points' fits —
+// wavefronts only for positions that have fits, so the work follows the new points, not touched keys x the position range.
+// sigma: per slot.  The cooperative yield is the same: wavefront b saves to and resumes from save block b.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TAD_ARIMA_WAVES, TAD_ARIMA_WAVES))) void k_arima_fit_list(
+    ArimaWs ws, FitList fl, const double *__restrict__ sigma, int maxiter, DevCounters *ctr, const int *pause, uint32_t grace) {
+  __shared__ double buf[64 * (kStage + 1)];
+  __shared__ double park[64 * kParkDoubles];
+  arima_fit_body<true>(Grid{nullptr, nullptr, 0, 0, nullptr}, ws, sigma, nullptr, maxiter, 0, 1, nullptr, ctr, buf, park, pause, grace, fl);
 }
 
 static uint32_t arima_tpad(uint64_t T) { return (uint32_t)((T + kStage - 1) / kStage * kStage); }
@@ -1261,6 +1314,226 @@ int launch_arima(hipStream_t s, Grid g, const double *sigma, const uint32_t *n_p
     }
 #endif
   }
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Streaming ARIMA (tad.h: TAD_STATE_SERIES; tad_capi.cpp: stream_arima_batch).  One batch, after the series append: the touched keys
+// (keys with new points) get slots; their whole series are Box-Cox'ed into a PACKED key-major layout (slot j's series at yoff[j], padded
+// to 8 doubles: the fit's 16-byte staged loads stay aligned); the fits of the new points at p >= 3 are counted and listed per position;
+// their start parameters and the fits themselves run per fit (k_arima_fit_list).  Arithmetic: that of k_arima_prep / k_arima_start /
+// k_arima_fit — the same functions over the same values in the same order (the stride does not enter the bits) — so every prediction
+// equals tad_run(ARIMA)'s over the concatenated series.
+// ------------------------------------------------------------------------------------------------
+static constexpr int kSBlock = 256;
+
+// touched[k] = the key has new points; len8[k] = its whole series padded to 8 doubles (0 if untouched); *tmax = the longest touched series
+__global__ __launch_bounds__(kSBlock) void k_as_touch(uint64_t K, const unsigned long long *__restrict__ soff, const unsigned long long *__restrict__ poff,
+                                                      uint32_t *__restrict__ touched, uint32_t *__restrict__ len8, unsigned int *__restrict__ tmax) {
+  const uint64_t k = (uint64_t)blockIdx.x * kSBlock + threadIdx.x;
+  if (k >= K) return;
+  const bool t = poff[k + 1] > poff[k];
+  const unsigned long long n = soff[k + 1] - soff[k];
+  touched[k] = t ? 1u : 0u;
+  len8[k] = t ? (uint32_t)((n + 7) & ~7ull) : 0u;
+  if (t) atomicMax(tmax, (unsigned int)n);
+}
+
+// One lane per touched key (slot j = tidx[k]): k_arima_prep's walk over the key's whole series (time order), lambda, the transform into
+// ysk, the predictions and verdicts of its new points at p < 3, and the positions of its fits [lo, hi).
+__global__ __launch_bounds__(kSBlock) void k_as_prep(uint64_t K, const unsigned long long *__restrict__ soff, const unsigned long long *__restrict__ sval,
+                                                     const unsigned long long *__restrict__ poff, StreamState next,
+                                                     const unsigned long long *__restrict__ tidx, const unsigned long long *__restrict__ yoffk,
+                                                     double *__restrict__ lx, double *__restrict__ ysk, ArimaSlots sl, double *__restrict__ pcalc,
+                                                     uint8_t *__restrict__ pflag, DevCounters *ctr) {
+  const uint64_t k = (uint64_t)blockIdx.x * kSBlock + threadIdx.x;
+  unsigned noresult = 0;
+  if (k < K && poff[k + 1] > poff[k]) {
+    const uint64_t j = tidx[k];
+    const unsigned long long s0 = soff[k], yo = yoffk[k], p0 = poff[k];
+    const uint32_t n = (uint32_t)(soff[k + 1] - s0);
+    const uint32_t old = n - (uint32_t)(poff[k + 1] - p0);
+    const unsigned long long *v = sval + s0;
+    double *l_k = lx + yo, *y_k = ysk + yo;
+    bool nonpos = false, allsame = true;
+    double x0 = 0.0, sumlog = 0.0;
+    for (uint32_t i = 0; i < n; ++i) {
+      const double x = (double)v[i];
+      if (i == 0) x0 = x;
+      if (x != x0) allsame = false;
+      if (!(x > 0.0)) nonpos = true;
+      const double l = tad_det_log(x);
+      l_k[i] = l;
+      sumlog += l;
+    }
+    bool ok = n > 3 && !nonpos && !allsame;
+    double lam = 0.0;
+    if (ok) ok = bc_mle_lambda(l_k, l_k, y_k, 1, n, sumlog, &lam);   // (y_k: scratch for the llf's terms until the transform fills it)
+    const uint32_t cnt = next.n[k];
+    const double sg = cnt >= 2 ? sqrt(next.m2[k] / ((double)cnt - 1.0)) : 0.0;   // k_key_sigma's expression on the post-batch moments
+    sl.key[j] = (uint32_t)k;
+    sl.yoff[j] = yo;
+    sl.lam[j] = lam;
+    sl.sigma[j] = sg;
+    sl.ibase[j] = p0 - (unsigned long long)old;
+    sl.lo[j] = ok ? (old > 3u ? old : 3u) : 0u;
+    sl.hi[j] = ok && n > 3u ? n : 0u;
+    sl.ok[j] = ok ? 1 : 0;
+    if (ok) {
+      stream_col8(l_k, 1, n, [&](uint32_t i, double l) {
+        const double y = lam == 0.0 ? l : tad_det_expm1(lam * l) / lam;  // scipy.special.boxcox
+        y_k[i] = y;
+        if (i < 3 && i >= old) {
+          const double pred = inv_boxcox(y, lam);
+          const uint64_t pi = p0 + (i - old);
+          pcalc[pi] = pred;
+          pflag[pi] = fabs((double)v[i] - pred) > sg ? 1 : 0;
+        }
+      });
+    } else {
+      noresult = 1;
+    }
+  }
+  for (int d = 32; d >= 1; d >>= 1) noresult += __shfl_down(noresult, d);
+  if ((threadIdx.x & 63) == 0 && noresult) atomicAdd(&ctr->keys_no_result, (unsigned long long)noresult);
+}
+
+// One lane per slot, the wavefront walking the union of its lanes' position ranges: at every position the lanes with a fit there take
+// consecutive places from ONE atomic of the wavefront.  fill == false: cnt[p] += the fits; fill == true: list / fpos of every fit.
+__global__ __launch_bounds__(kSBlock) void k_as_list(uint64_t Kt, ArimaSlots sl, bool fill, unsigned int *__restrict__ cnt,
+                                                     const unsigned long long *__restrict__ loff, uint32_t *__restrict__ list,
+                                                     uint32_t *__restrict__ fpos) {
+  const uint64_t j = (uint64_t)blockIdx.x * kSBlock + threadIdx.x;
+  const unsigned lane = threadIdx.x & 63u;
+  uint32_t lo = 0, hi = 0;
+  if (j < Kt) { lo = sl.lo[j]; hi = sl.hi[j]; }
+  uint32_t wlo = lo < hi ? lo : 0xFFFFFFFFu, whi = lo < hi ? hi : 0u;
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint32_t a = (uint32_t)__shfl_xor((int)wlo, d), b = (uint32_t)__shfl_xor((int)whi, d);
+    wlo = a < wlo ? a : wlo;
+    whi = b > whi ? b : whi;
+  }
+  for (uint32_t p = wlo; p < whi; ++p) {   // wave-uniform
+    const bool mine = lo <= p && p < hi;
+    const unsigned long long m = __ballot(mine);
+    unsigned int base = 0;
+    if (lane == (unsigned)__ffsll((long long)m) - 1u) base = atomicAdd(&cnt[p], (unsigned int)__popcll(m));
+    if (!fill) continue;
+    base = (unsigned int)__shfl((int)base, __ffsll((long long)m) - 1);
+    if (mine) {
+      const unsigned long long f = loff[p] + base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
+      list[f] = (uint32_t)j;
+      fpos[f] = p;
+    }
+  }
+}
+
+// start parameters of every fit (lane = fit): k_arima_start's arima_start_params on the slot's packed series
+__global__ __launch_bounds__(64) void k_as_start(uint64_t nfits, const uint32_t *__restrict__ list, const uint32_t *__restrict__ fpos,
+                                                 const unsigned long long *__restrict__ yoff, const double *__restrict__ ysk, double *u0a, double *u0b,
+                                                 double *u0c) {
+  const uint64_t f = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+  if (f >= nfits) return;
+  double u[3];
+  arima_start_params(ysk + yoff[list[f]], 1, fpos[f], u);
+  u0a[f] = u[0]; u0b[f] = u[1]; u0c[f] = u[2];
+}
+
+// rows of every new point (lane = point): its key has a result and (all_points or) the verdict says anomaly
+__global__ __launch_bounds__(kSBlock) void k_as_rows(uint64_t P, const unsigned long long *__restrict__ nk, const unsigned long long *__restrict__ tidx,
+                                                     const uint8_t *__restrict__ ok, const uint8_t *__restrict__ pflag, bool all_points,
+                                                     uint32_t *__restrict__ rows) {
+  const uint64_t i = (uint64_t)blockIdx.x * kSBlock + threadIdx.x;
+  if (i >= P) return;
+  rows[i] = ok[tidx[nk[i]]] ? (all_points ? 1u : (uint32_t)pflag[i]) : 0u;
+}
+
+__global__ __launch_bounds__(kSBlock) void k_as_emit(uint64_t P, const unsigned long long *__restrict__ nk, const long long *__restrict__ nt,
+                                                     const unsigned long long *__restrict__ nv, const unsigned long long *__restrict__ tidx,
+                                                     const double *__restrict__ sigma, const double *__restrict__ pcalc, const uint8_t *__restrict__ pflag,
+                                                     const uint32_t *__restrict__ rows, const unsigned long long *__restrict__ row_off, bool all_points,
+                                                     OutRows out) {
+  const uint64_t i = (uint64_t)blockIdx.x * kSBlock + threadIdx.x;
+  if (i >= P || rows[i] == 0) return;
+  const uint64_t k = nk[i];
+  const unsigned long long at = row_off[i];
+  out.key_id[at] = k;
+  out.flow_end_s[at] = nt[i];
+  out.throughput[at] = (double)nv[i];
+  out.algo_calc[at] = pcalc[i];
+  out.stddev[at] = sigma[tidx[k]];
+  if (all_points) out.anomaly[at] = pflag[i];
+}
+
+static inline unsigned s_blocks(uint64_t lanes) { return (unsigned)((lanes + kSBlock - 1) / kSBlock); }
+
+void launch_as_touch(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *poff, uint32_t *touched, uint32_t *len8,
+                     unsigned int *tmax) {
+  hipMemsetAsync(tmax, 0, 4, s);
+  if (K) hipLaunchKernelGGL(k_as_touch, dim3(s_blocks(K)), dim3(kSBlock), 0, s, K, soff, poff, touched, len8, tmax);
+}
+
+void launch_as_prep(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *sval, const unsigned long long *poff,
+                    StreamState next, const unsigned long long *tidx, const unsigned long long *yoffk, double *lx, double *ysk, ArimaSlots sl,
+                    double *pcalc, uint8_t *pflag, DevCounters *ctr) {
+  if (K) hipLaunchKernelGGL(k_as_prep, dim3(s_blocks(K)), dim3(kSBlock), 0, s, K, soff, sval, poff, next, tidx, yoffk, lx, ysk, sl, pcalc, pflag, ctr);
+}
+
+void launch_as_list(hipStream_t s, uint64_t Kt, ArimaSlots sl, bool fill, unsigned int *cnt, const unsigned long long *loff, uint32_t *list, uint32_t *fpos) {
+  if (Kt) hipLaunchKernelGGL(k_as_list, dim3(s_blocks(Kt)), dim3(kSBlock), 0, s, Kt, sl, fill, cnt, loff, list, fpos);
+}
+
+void launch_as_rows(hipStream_t s, uint64_t P, const unsigned long long *nk, const unsigned long long *tidx, const uint8_t *ok, const uint8_t *pflag,
+                    bool all_points, uint32_t *rows) {
+  if (P) hipLaunchKernelGGL(k_as_rows, dim3(s_blocks(P)), dim3(kSBlock), 0, s, P, nk, tidx, ok, pflag, all_points, rows);
+}
+
+void launch_as_emit(hipStream_t s, uint64_t P, const unsigned long long *nk, const long long *nt, const unsigned long long *nv,
+                    const unsigned long long *tidx, const double *sigma, const double *pcalc, const uint8_t *pflag, const uint32_t *rows,
+                    const unsigned long long *row_off, bool all_points, OutRows out) {
+  if (P) hipLaunchKernelGGL(k_as_emit, dim3(s_blocks(P)), dim3(kSBlock), 0, s, P, nk, nt, nv, tidx, sigma, pcalc, pflag, rows, row_off, all_points, out);
+}
+
+// the fit workspace of a streaming batch: u0[3][fits] | cursor[positions] | yielded | saved[waves] | hist[waves] | save[waves]
+size_t arima_stream_ws_bytes(uint64_t nfits, uint64_t npos, uint64_t waves) {
+  return (size_t)nfits * 24 + 512 + (size_t)npos * 8 + 512 + 64 + 512 + (size_t)waves * 4 + 512 + (size_t)waves * (kHistDoubles * 64 * 8) + 512 +
+         (size_t)waves * (kSaveDoubles * 64 * 8) + 1024;
+}
+
+static ArimaWs arima_stream_carve(void *workspace, double *ysk, const double *lam, uint64_t nfits, uint64_t npos, uint64_t waves) {
+  auto align512 = [](unsigned char *q) { return reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(q) + 511) & ~(uintptr_t)511); };
+  unsigned char *w = align512(static_cast<unsigned char *>(workspace));
+  ArimaWs ws{};
+  for (int i = 0; i < 3; ++i) { ws.u0[i] = reinterpret_cast<double *>(w); w += (size_t)nfits * 8; }
+  w = align512(w);
+  ws.cursor = reinterpret_cast<unsigned long long *>(w); w = align512(w + (size_t)npos * 8);
+  ws.yielded = reinterpret_cast<unsigned int *>(w); w = align512(w + 64);
+  ws.saved = reinterpret_cast<unsigned int *>(w); w = align512(w + (size_t)waves * 4);
+  ws.hist = reinterpret_cast<double *>(w); w = align512(w + (size_t)waves * (kHistDoubles * 64 * 8));
+  ws.save = reinterpret_cast<double *>(w);
+  ws.ysk = ysk;
+  ws.lam = const_cast<double *>(lam);
+  return ws;
+}
+
+// start parameters of the nfits listed fits, then the fits (first == true: cursors and suspend flags reset); a relaunch after a yield
+// passes first == false and the grace of the relaunch loop
+int launch_arima_stream_fit(hipStream_t s, bool first, uint64_t nfits, uint64_t npos, uint64_t waves, const uint32_t *fpos, double *ysk,
+                            ArimaSlots sl, FitListArgs fa, int maxiter, DevCounters *ctr, void *workspace, const int *pause,
+                            const unsigned int **yielded, uint32_t grace) {
+  if (yielded) *yielded = nullptr;
+  if (nfits == 0 || waves == 0) return 0;
+  if (waves > 0x7FFFFFFFull || nfits / 64 + 1 > 0x7FFFFFFFull) return -1;
+  const ArimaWs ws = arima_stream_carve(workspace, ysk, sl.lam, nfits, npos, waves);
+  if (first) {
+    hipLaunchKernelGGL(k_as_start, dim3((unsigned)((nfits + 63) / 64)), dim3(64), 0, s, nfits, fa.list, fpos, sl.yoff, ysk, ws.u0[0], ws.u0[1], ws.u0[2]);
+    hipMemsetAsync(ws.cursor, 0, (size_t)npos * 8, s);
+    hipMemsetAsync(ws.saved, 0, (size_t)waves * 4, s);
+  }
+  hipMemsetAsync(ws.yielded, 0, 4, s);
+  const FitList fl{fa.wave_pos, fa.cnt, fa.loff, fa.list, sl.yoff, sl.ibase, fa.nv, fa.pcalc, fa.pflag};
+  hipLaunchKernelGGL(k_arima_fit_list, dim3((unsigned)waves), dim3(64), 0, s, ws, fl, (const double *)sl.sigma, maxiter, ctr, pause, grace);
+  if (yielded) *yielded = ws.yielded;
   return 0;
 }
 

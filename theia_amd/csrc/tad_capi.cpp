@@ -44,6 +44,28 @@ int ensure_key_buffers(JobCtx *e, uint64_t K) {
 
 namespace {
 
+// The fit yields to whole-CU jobs of other contexts (PauseHold): its wavefronts suspend their fits while the engine's pause word is raised
+// and the kernel is relaunched here — after the word has cleared, or after 2 ms at the latest, so that a steady stream of short jobs
+// time-slices with the fit instead of starving it.  relaunch(grace, &yielded_dev) launches the fit again over what it left (0 on success).
+template <typename Relaunch>
+int arima_yield_loop(JobCtx *e, const unsigned int *yielded_dev, Relaunch relaunch) {
+  hipStream_t s = e->stream;
+  while (yielded_dev != nullptr && e->eng->pause_dev != nullptr) {
+    unsigned int y = 0;
+    HIP_TRY(e, hipMemcpyAsync(&y, yielded_dev, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    if (y == 0) break;
+    const auto t0 = std::chrono::steady_clock::now();
+    while (__atomic_load_n(&e->eng->pause_count, __ATOMIC_ACQUIRE) != 0 && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(2))
+      std::this_thread::sleep_for(std::chrono::microseconds(50));
+    // still raised after 2 ms (short jobs arrive back to back): this launch runs 24 optimiser cycles (~1 ms) before it looks at the word
+    const uint32_t grace = __atomic_load_n(&e->eng->pause_count, __ATOMIC_ACQUIRE) != 0 ? 24u : 0u;
+    if (relaunch(grace, &yielded_dev) != 0) return fail(e, TAD_ERR_HIP, "ARIMA launch failed");
+    e->arima_relaunches++;
+  }
+  return TAD_OK;
+}
+
 int detect_and_count(JobCtx *e, Grid g, JobParams &jp, DevCounters *ctr, uint64_t *rows, bool stats_done = false) {
   hipStream_t s = e->stream;
   int rc;
@@ -82,28 +104,17 @@ int detect_and_count(JobCtx *e, Grid g, JobParams &jp, DevCounters *ctr, uint64_
     if ((rc = ensure(e, e->calc, g.K * g.T * sizeof(double))) != TAD_OK) return rc;
     const size_t wsb = arima_workspace_bytes(g);
     if ((rc = ensure(e, e->aux, wsb)) != TAD_OK) return rc;
-    // The fit yields to whole-CU jobs of other contexts (PauseHold): its wavefronts suspend their fits while the engine's pause word is raised
-    // and the kernel is relaunched here — after the word has cleared, or after 2 ms at the latest, so that a steady stream of short jobs
-    // time-slices with the fit instead of starving it.  This job's own claim is dropped for the duration (it would pause itself) and taken back for the emit.
+    // The fit yields to whole-CU jobs of other contexts (arima_yield_loop).  This job's own claim is dropped for the duration (it would pause
+    // itself) and taken back for the emit.
     const bool held = e->hold && e->hold->held;
     if (held) e->hold->release();
     const unsigned int *yielded_dev = nullptr;
     if (launch_arima(s, g, sigma, n_pts, jp.maxiter, static_cast<double *>(e->calc.p), ctr, e->aux.p, wsb, e->eng->pause_dev, &yielded_dev) != 0)
       return fail(e, TAD_ERR_HIP, "ARIMA launch failed");
-    while (yielded_dev != nullptr && e->eng->pause_dev != nullptr) {
-      unsigned int y = 0;
-      HIP_TRY(e, hipMemcpyAsync(&y, yielded_dev, 4, hipMemcpyDeviceToHost, s));
-      HIP_TRY(e, hipStreamSynchronize(s));
-      if (y == 0) break;
-      const auto t0 = std::chrono::steady_clock::now();
-      while (__atomic_load_n(&e->eng->pause_count, __ATOMIC_ACQUIRE) != 0 && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(2))
-        std::this_thread::sleep_for(std::chrono::microseconds(50));
-      // still raised after 2 ms (short jobs arrive back to back): this launch runs 24 optimiser cycles (~1 ms) before it looks at the word
-      const uint32_t grace = __atomic_load_n(&e->eng->pause_count, __ATOMIC_ACQUIRE) != 0 ? 24u : 0u;
-      if (launch_arima_fit(s, g, sigma, n_pts, jp.maxiter, static_cast<double *>(e->calc.p), ctr, e->aux.p, e->eng->pause_dev, &yielded_dev, grace) != 0)
-        return fail(e, TAD_ERR_HIP, "ARIMA launch failed");
-      e->arima_relaunches++;
-    }
+    if ((rc = arima_yield_loop(e, yielded_dev, [&](uint32_t grace, const unsigned int **yd) {
+           return launch_arima_fit(s, g, sigma, n_pts, jp.maxiter, static_cast<double *>(e->calc.p), ctr, e->aux.p, e->eng->pause_dev, yd, grace);
+         })) != TAD_OK)
+      return rc;
     if (held) e->hold->acquire();
   }
   const uint32_t *cnt = n_anom;
@@ -214,10 +225,11 @@ StreamState state_view(const tad_state *st, int which) {
 int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_mem out_memory, tad_result **out, tad_points **points_out,
                    tad_state *stream, int depth);
 
-// What a batch on a history state leaves for its emit: the new points in (key, time) order and, for DBSCAN, their verdicts and rows.
+// What a batch on a history or series state leaves for its emit: the new points in (key, time) order and, for DBSCAN, their verdicts and rows.
 struct HistBatch {
   const unsigned long long *nk = nullptr, *nv = nullptr;
   const long long *nt = nullptr;
+  const unsigned long long *poff = nullptr;    // key k's new points at [poff[k], poff[k + 1])
   const unsigned long long *P_dev = nullptr;   // the number of new points (device)
   uint64_t P_cap = 0;                          // its bound on the host (exact for a sparse batch)
   const uint8_t *noise = nullptr;
@@ -225,10 +237,32 @@ struct HistBatch {
   const unsigned long long *row = nullptr;
 };
 
-// One batch on a history state (tad.h, TAD_STATE_HISTORY), after the stream count pass and before the job's tail is read: the batch's new
-// points in (key, time) order, sorted per key and merged with the current history into the candidate arena (tad_history.hip); a DBSCAN
+// grows a candidate value arena of a state (history or series) to hold `need` values, geometrically; the current arena is not touched, so a
+// failure leaves the state as it is
+int grow_arena(JobCtx *e, unsigned long long *&val, uint64_t &cap, uint64_t need, const char *what) {
+  if (cap >= need) return TAD_OK;
+  const uint64_t want = need > 2 * cap ? need : 2 * cap;
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  if (val) hipFree(val);
+  val = nullptr;
+  cap = 0;
+  void *p = nullptr;
+  const hipError_t r = hipMalloc(&p, want * 8);
+  if (r != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_run_stream: %llu values of %s do not fit (%s); state unchanged", (unsigned long long)need, what,
+                hipGetErrorString(r));
+  }
+  val = static_cast<unsigned long long *>(p);
+  cap = want;
+  return TAD_OK;
+}
+
+// One batch on a history and / or series state (tad.h, TAD_STATE_HISTORY / TAD_STATE_SERIES), after the stream count pass and before the
+// job's tail is read: the batch's new points in (key, time) order; a history state sorts them per key and merges them with the current
+// history into the candidate arena (tad_history.hip); a series state appends them to every key's series in the candidate arena; a DBSCAN
 // batch also judges the new points against the merged history and scans their rows into the row total.  Writes only candidate memory:
-// the history becomes current with the moments, when the batch succeeds.  sparse_poff: a sparse batch's point offsets (P points in
+// history and series become current with the moments, when the batch succeeds.  sparse_poff: a sparse batch's point offsets (P points in
 // e->sp_comp_a / e->sp_val_a); otherwise the dense grid g is compacted, at most P_bound points.
 int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound,
                          const JobParams &jp, HistBatch *hb) {
@@ -239,24 +273,10 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
   const uint64_t P_cap = sparse_poff ? P : P_bound;
   const size_t kpad = (size_t)((K + 3) & ~3ull);
   int rc;
-  // the candidate arena first: an allocation failure leaves the state and its history as they are
+  // the candidate arenas first: an allocation failure leaves the state, its history and its series as they are
   const uint64_t need = st->hist_len[cur] + P_cap;
-  if (st->hist_cap[cand] < need) {
-    const uint64_t cap = need > 2 * st->hist_cap[cand] ? need : 2 * st->hist_cap[cand];
-    HIP_TRY(e, hipStreamSynchronize(s));
-    if (st->hist_val[cand]) hipFree(st->hist_val[cand]);
-    st->hist_val[cand] = nullptr;
-    st->hist_cap[cand] = 0;
-    void *p = nullptr;
-    const hipError_t r = hipMalloc(&p, cap * 8);
-    if (r != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_run_stream: %llu values of history do not fit (%s); state unchanged",
-                  (unsigned long long)need, hipGetErrorString(r));
-    }
-    st->hist_val[cand] = static_cast<unsigned long long *>(p);
-    st->hist_cap[cand] = cap;
-  }
+  if (st->history && (rc = grow_arena(e, st->hist_val[cand], st->hist_cap[cand], need, "history")) != TAD_OK) return rc;
+  if (st->series && (rc = grow_arena(e, st->ser_val[cand], st->ser_cap[cand], st->ser_len[cur] + P_cap, "series")) != TAD_OK) return rc;
   const uint64_t pc = P_cap ? P_cap : 1;
   if ((rc = ensure(e, e->hs_key, pc * 8)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->hs_t, pc * 8)) != TAD_OK) return rc;
@@ -289,12 +309,15 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
     poff = koff;
     nv = static_cast<const unsigned long long *>(e->hs_val.p);
   }
-  // 2. every key's new values sorted; 3. merged with its history into the candidate arena
-  launch_hist_sort(s, nv, poff, K, ns, kcnt, long_count);
-  launch_hist_merge(s, K, st->hist_off[cur], st->hist_val[cur], poff, ns, st->hist_off[cand], st->hist_val[cand], kcnt, coff, scratch,
-                    hist_merge_chunks_bound(K, need));
+  if (st->history) {   // 2. every key's new values sorted; 3. merged with its history into the candidate arena
+    launch_hist_sort(s, nv, poff, K, ns, kcnt, long_count);
+    launch_hist_merge(s, K, st->hist_off[cur], st->hist_val[cur], poff, ns, st->hist_off[cand], st->hist_val[cand], kcnt, coff, scratch,
+                      hist_merge_chunks_bound(K, need));
+  }
+  if (st->series)      // 3'. appended to its series in the candidate arena
+    launch_series_append(s, K, st->ser_off[cur], st->ser_val[cur], poff, nv, st->ser_off[cand], st->ser_val[cand]);
   HIP_TRY(e, hipMemcpyAsync(static_cast<unsigned char *>(e->counters.p) + kTailHistLen, poff + K, 8, hipMemcpyDeviceToDevice, s));
-  hb->nk = nk; hb->nt = nt; hb->nv = nv; hb->P_dev = poff + K; hb->P_cap = P_cap;
+  hb->nk = nk; hb->nt = nt; hb->nv = nv; hb->poff = poff; hb->P_dev = poff + K; hb->P_cap = P_cap;
   if (dbscan && P_cap) {   // 4. verdicts of the new points; 5. their rows (the row total lands in the job's tail)
     uint8_t *noise = static_cast<uint8_t *>(e->hs_noise.p);
     uint32_t *cnt = static_cast<uint32_t *>(e->hs_cnt.p);
@@ -303,6 +326,125 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
     launch_scan(s, cnt, row, P_cap, scratch, dev_total(e));
     hb->noise = noise; hb->cnt = cnt; hb->row = row;
   }
+  return TAD_OK;
+}
+
+// What a stream ARIMA batch leaves for its emit (stream_arima_batch)
+struct ArimaBatch {
+  uint64_t P = 0;
+  const unsigned long long *tidx = nullptr;    // slot of key k
+  const double *sigma = nullptr;               // per slot
+  const double *pcalc = nullptr;               // per new point
+  const uint8_t *pflag = nullptr;
+  const uint32_t *rows = nullptr;
+  const unsigned long long *row_off = nullptr;
+};
+
+constexpr uint64_t kStreamFitWaves = 4096;   // k_arima_fit_list: wavefronts a batch aims for (two per SIMD twice over)
+
+// One ARIMA batch on a series state (tad.h, TAD_STATE_SERIES), after stream_history_batch appended the new points to the candidate series:
+// the touched keys' Box-Cox fits over their whole series, the fits of the new points only, verdicts and the row count (tad_arima.hip).
+// Writes only workspace memory.  A batch whose Stage 0 or stream pass raised an error (a late row) runs no fit: the caller fails it.
+int stream_arima_batch(JobCtx *e, tad_state *st, uint64_t K, const HistBatch &hb, const JobParams &jp, DevCounters *ctr, ArimaBatch *ab) {
+  hipStream_t s = e->stream;
+  const int cand = st->cur ^ 1;
+  const unsigned long long *soff = st->ser_off[cand], *sval = st->ser_val[cand];
+  const size_t kpad = (size_t)((K + 3) & ~3ull);
+  int rc;
+  // per key: touched u32 | len8 u32 | tidx u64[K + 1] | yoffk u64[K + 1] | tmax; per slot: key u32 | lo u32 | hi u32 | ok u8 | yoff u64 | lam | sigma | ibase
+  if ((rc = ensure(e, e->as_key, kpad * 8 + (kpad + 4) * 16 + 64 + kpad * (4 * 3 + 1 + 8 * 4) + 256)) != TAD_OK) return rc;
+  unsigned char *kb = static_cast<unsigned char *>(e->as_key.p);
+  uint32_t *touched = reinterpret_cast<uint32_t *>(kb), *len8 = touched + kpad;
+  unsigned long long *tidx = reinterpret_cast<unsigned long long *>(len8 + kpad), *yoffk = tidx + kpad + 4;
+  unsigned int *tmax_dev = reinterpret_cast<unsigned int *>(yoffk + kpad + 4);
+  unsigned char *sb = reinterpret_cast<unsigned char *>(tmax_dev) + 64;
+  ArimaSlots sl;
+  sl.yoff = reinterpret_cast<unsigned long long *>(sb);
+  sl.lam = reinterpret_cast<double *>(sl.yoff + kpad);
+  sl.sigma = sl.lam + kpad;
+  sl.ibase = reinterpret_cast<unsigned long long *>(sl.sigma + kpad);
+  sl.key = reinterpret_cast<uint32_t *>(sl.ibase + kpad);
+  sl.lo = sl.key + kpad;
+  sl.hi = sl.lo + kpad;
+  sl.ok = reinterpret_cast<uint8_t *>(sl.hi + kpad);
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  launch_as_touch(s, K, soff, hb.poff, touched, len8, tmax_dev);
+  launch_scan(s, touched, tidx, K, scratch);
+  launch_scan(s, len8, yoffk, K, scratch);
+  unsigned long long hv[3] = {0, 0, 0};   // new points, slots, packed doubles
+  unsigned int tmax = 0;
+  HIP_TRY(e, hipMemcpyAsync(&hv[0], hb.P_dev, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(&hv[1], tidx + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(&hv[2], yoffk + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(&tmax, tmax_dev, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(e->ctr_host, ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  const uint64_t P = hv[0], Kt = hv[1], S8 = hv[2];
+  ab->P = 0;
+  if (e->ctr_host->err != 0 || P == 0) return TAD_OK;   // (the caller reads the error from the tail)
+  // per new point: pcalc f64 | rows u32 | row_off u64[P + 1] | pflag u8; the packed series: lx | ysk, each with the slack an idle lane's
+  // staged loads (k_arima_fit_list reads slot 0's offset up to the wavefront's position + 16) may touch
+  const size_t ppad = (size_t)((P + 3) & ~3ull);
+  if ((rc = ensure(e, e->as_pt, ppad * (8 + 4 + 8 + 1) + 64)) != TAD_OK) return rc;
+  double *pcalc = static_cast<double *>(e->as_pt.p);
+  uint32_t *rows = reinterpret_cast<uint32_t *>(pcalc + ppad);
+  unsigned long long *row_off = reinterpret_cast<unsigned long long *>(rows + ppad);
+  uint8_t *pflag = reinterpret_cast<uint8_t *>(row_off + ppad + 4);
+  const size_t ser = (size_t)S8 + tmax + 32;
+  if ((rc = ensure(e, e->as_ser, ser * 16)) != TAD_OK) return rc;
+  double *lx = static_cast<double *>(e->as_ser.p), *ysk = lx + ser;
+  HIP_TRY(e, hipMemsetAsync(pflag, 0, P, s));
+  HIP_TRY(e, hipMemsetAsync(ysk, 0, ser * 8, s));   // (the slack: finite values for idle lanes)
+  launch_as_prep(s, K, soff, sval, hb.poff, state_view(st, cand), tidx, yoffk, lx, ysk, sl, pcalc, pflag, ctr);
+  // the fits: counted per position, listed, their wavefronts laid out on the host (heaviest position first)
+  const uint64_t npos = (uint64_t)tmax + 1;
+  if ((rc = ensure(e, e->as_pos, npos * (4 + 8) + 128)) != TAD_OK) return rc;   // cnt u32[npos] | (64-byte aligned) loff u64[npos + 1]
+  unsigned int *pcnt = static_cast<unsigned int *>(e->as_pos.p);
+  unsigned long long *loff = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(e->as_pos.p) + ((npos * 4 + 63) & ~63ull));
+  HIP_TRY(e, hipMemsetAsync(pcnt, 0, npos * 4, s));
+  launch_as_list(s, Kt, sl, false, pcnt, nullptr, nullptr, nullptr);
+  std::vector<uint32_t> hcnt;
+  std::vector<unsigned long long> hoff;
+  std::vector<uint32_t> wave_pos;
+  try { hcnt.resize(npos); hoff.resize(npos + 1); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
+  HIP_TRY(e, hipMemcpyAsync(hcnt.data(), pcnt, npos * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  uint64_t nfits = 0;
+  for (uint64_t p = 0; p < npos; ++p) { hoff[p] = nfits; nfits += hcnt[p]; }
+  hoff[npos] = nfits;
+  const uint64_t chunk = nfits / kStreamFitWaves < 64 ? 64 : (nfits / kStreamFitWaves + 63) / 64 * 64;   // fits per wavefront and position
+  try {
+    for (uint64_t p = npos; p-- > 0;)
+      for (uint64_t w = 0; w < (hcnt[p] + chunk - 1) / chunk; ++w) wave_pos.push_back((uint32_t)p);
+  } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
+  const uint64_t waves = wave_pos.size();
+  const size_t fpad = (size_t)((nfits + 3) & ~3ull);
+  if ((rc = ensure(e, e->as_fit, fpad * 8 + (size_t)(waves + 4) * 4 + 64)) != TAD_OK) return rc;
+  uint32_t *list = static_cast<uint32_t *>(e->as_fit.p), *fpos = list + fpad, *wpos = fpos + fpad;
+  if (nfits) {
+    HIP_TRY(e, hipMemcpyAsync(loff, hoff.data(), (npos + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, hipMemcpyAsync(wpos, wave_pos.data(), waves * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, hipMemsetAsync(pcnt, 0, npos * 4, s));
+    launch_as_list(s, Kt, sl, true, pcnt, loff, list, fpos);
+    const size_t wsb = arima_stream_ws_bytes(nfits, npos, waves);
+    if ((rc = ensure(e, e->as_ws, wsb)) != TAD_OK) return rc;
+    const FitListArgs fa{wpos, pcnt, loff, list, hb.nv, pcalc, pflag};
+    // the fit yields to whole-CU jobs of other contexts like tad_run's (arima_yield_loop); this job's own claim is dropped meanwhile
+    const bool held = e->hold && e->hold->held;
+    if (held) e->hold->release();
+    const unsigned int *yielded_dev = nullptr;
+    if (launch_arima_stream_fit(s, true, nfits, npos, waves, fpos, ysk, sl, fa, jp.maxiter, ctr, e->as_ws.p, e->eng->pause_dev, &yielded_dev, 0) != 0)
+      return fail(e, TAD_ERR_HIP, "ARIMA launch failed");
+    if ((rc = arima_yield_loop(e, yielded_dev, [&](uint32_t grace, const unsigned int **yd) {
+           return launch_arima_stream_fit(s, false, nfits, npos, waves, fpos, ysk, sl, fa, jp.maxiter, ctr, e->as_ws.p, e->eng->pause_dev, yd, grace);
+         })) != TAD_OK)
+      return rc;
+    if (held) e->hold->acquire();
+  }
+  // rows of the new points (the row total lands in the job's tail)
+  launch_as_rows(s, P, hb.nk, tidx, sl.ok, pflag, jp.all_points, rows);
+  launch_scan(s, rows, row_off, P, scratch, dev_total(e));
+  ab->P = P; ab->tidx = tidx; ab->sigma = sl.sigma; ab->pcalc = pcalc; ab->pflag = pflag; ab->rows = rows; ab->row_off = row_off;
   return TAD_OK;
 }
 
@@ -319,9 +461,11 @@ int run_job(tad_engine *eng, const tad_job *job, const tad_columns *cols, tad_me
   if (stream && e && job && cols) {
     if (job->algo == TAD_ALGO_DBSCAN && !stream->history)
       return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: DBSCAN needs a state with history (tad_state_create_ex with TAD_STATE_HISTORY)");
-    if (job->algo != TAD_ALGO_EWMA && job->algo != TAD_ALGO_DBSCAN)
-      return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: only the EWMA detector has a streaming form, and DBSCAN on a state with history "
-                                               "(ARIMA and DROP depend on the whole series)");
+    if (job->algo == TAD_ALGO_ARIMA && !stream->series)
+      return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: ARIMA needs a state with a series (tad_state_create_ex with TAD_STATE_SERIES)");
+    if (job->algo != TAD_ALGO_EWMA && job->algo != TAD_ALGO_DBSCAN && job->algo != TAD_ALGO_ARIMA)
+      return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: only the EWMA detector has a streaming form, DBSCAN on a state with history and "
+                                               "ARIMA on a state with a series (DROP has none)");
     // k_stream writes the candidate state for keys < cols->num_keys and the double buffer flips as a whole: a batch
     // that declares fewer keys than the state holds would drop the others' state
     if (cols->num_keys != stream->K) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: batch declares %llu keys, the state holds %llu (they must be equal)",
@@ -762,6 +906,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
     // ---- Stage 1+2: sigma, detector, count, scan ----
     uint64_t rows = 0;
     HistBatch hist;
+    ArimaBatch ab;
     ResultPriv *rp = nullptr;
     OutRows dev_rows{};
     ResultBlock dev_block;
@@ -789,10 +934,11 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
         launch_stream(s, g, L, jp.alpha, jp.all_points, false, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),
                       static_cast<uint32_t *>(e->n_anom.p), nullptr, OutRows{}, ctr);
       unsigned long long *off = static_cast<unsigned long long *>(e->off.p);
-      if (stream->history && g.K &&
+      if ((stream->history || stream->series) && g.K &&
           (rc = stream_history_batch(e, stream, g, L, stream_poff, stream_P, (slots_all < cells ? slots_all : cells), jp, &hist)) != TAD_OK)
         return rc;
-      if (jp.algo != TAD_ALGO_DBSCAN)   // (a DBSCAN batch counted its rows in stream_history_batch)
+      if (jp.algo == TAD_ALGO_ARIMA && g.K && (rc = stream_arima_batch(e, stream, g.K, hist, jp, ctr, &ab)) != TAD_OK) return rc;
+      if (jp.algo == TAD_ALGO_EWMA)   // (a DBSCAN / ARIMA batch counted its rows in stream_history_batch / stream_arima_batch)
         launch_scan(s, static_cast<const uint32_t *>(e->n_anom.p), off, g.K, static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
       HIP_TRY(e, hipMemcpyAsync(e->tail_host, e->counters.p, kTailBytes, hipMemcpyDeviceToHost, s));
       HIP_TRY(e, hipStreamSynchronize(s));
@@ -899,7 +1045,9 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
 
     // ---- Stage 3: emit ----
     if ((rc = make_result(e, rows, jp.all_points, out_memory, &rp, &dev_rows, &dev_block)) != TAD_OK) return rc;
-    if (rows && stream && jp.algo == TAD_ALGO_DBSCAN)
+    if (rows && stream && jp.algo == TAD_ALGO_ARIMA)
+      launch_as_emit(s, ab.P, hist.nk, hist.nt, hist.nv, ab.tidx, ab.sigma, ab.pcalc, ab.pflag, ab.rows, ab.row_off, jp.all_points, dev_rows);
+    else if (rows && stream && jp.algo == TAD_ALGO_DBSCAN)
       launch_hist_emit(s, hist.nk, hist.nt, hist.nv, hist.P_dev, hist.P_cap, hist.noise, hist.cnt, hist.row, state_view(stream, stream->cur ^ 1),
                        jp.all_points, dev_rows);
     else if (rows && stream && stream_poff)
@@ -987,12 +1135,11 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       w.wide_tiles = force_wide_tiles && plan.tile_cells != 1;
     }
     strncpy(rp->pub.id, job->id, sizeof rp->pub.id - 1);
-    if (stream && g.K) {   // the batch succeeded: the candidate state (and history) becomes current (an empty batch wrote none)
-      if (stream->history) {
-        unsigned long long added;
-        memcpy(&added, e->tail_host + kTailHistLen, 8);
-        stream->hist_len[stream->cur ^ 1] = stream->hist_len[stream->cur] + added;
-      }
+    if (stream && g.K) {   // the batch succeeded: the candidate state (and history, series) becomes current (an empty batch wrote none)
+      unsigned long long added = 0;
+      memcpy(&added, e->tail_host + kTailHistLen, 8);
+      if (stream->history) stream->hist_len[stream->cur ^ 1] = stream->hist_len[stream->cur] + added;
+      if (stream->series) stream->ser_len[stream->cur ^ 1] = stream->ser_len[stream->cur] + added;
       stream->cur ^= 1;
     }
     if (depth == 0) e->done.store(4);
@@ -1266,6 +1413,8 @@ void tad_state_destroy(tad_engine *e, tad_state *st) {
     if (st->block[i]) hipFree(st->block[i]);
     if (st->hist_off[i]) hipFree(st->hist_off[i]);
     if (st->hist_val[i]) hipFree(st->hist_val[i]);
+    if (st->ser_off[i]) hipFree(st->ser_off[i]);
+    if (st->ser_val[i]) hipFree(st->ser_val[i]);
   }
   delete st;
 }
@@ -1317,7 +1466,7 @@ int tad_state_resize(tad_engine *eng, tad_state *st, uint64_t new_num_keys) {
   }
   // a history state: offsets of K' + 1 entries for both copies; the current one keeps its keys' offsets and gives the added keys empty
   // segments at the end (offset = the history's length).  The value arenas stay; the current one moves to index 0 with the state.
-  std::vector<unsigned long long> tail_off;
+  std::vector<unsigned long long> tail_off, ser_tail_off;
   if (r == hipSuccess && st->history) {
     for (int i = 0; i < 2 && r == hipSuccess; ++i) r = hipMalloc(reinterpret_cast<void **>(&grown.hist_off[i]), (new_num_keys + 1) * 8);
     if (r == hipSuccess) r = hipMemcpyAsync(grown.hist_off[0], st->hist_off[st->cur], (st->K + 1) * 8, hipMemcpyDeviceToDevice, e->stream);
@@ -1327,11 +1476,21 @@ int tad_state_resize(tad_engine *eng, tad_state *st, uint64_t new_num_keys) {
     if (r == hipSuccess)
       r = hipMemcpyAsync(grown.hist_off[0] + st->K + 1, tail_off.data(), tail_off.size() * 8, hipMemcpyHostToDevice, e->stream);
   }
+  if (r == hipSuccess && st->series) {   // the series the same way: the added keys' segments are empty, at the end
+    for (int i = 0; i < 2 && r == hipSuccess; ++i) r = hipMalloc(reinterpret_cast<void **>(&grown.ser_off[i]), (new_num_keys + 1) * 8);
+    if (r == hipSuccess) r = hipMemcpyAsync(grown.ser_off[0], st->ser_off[st->cur], (st->K + 1) * 8, hipMemcpyDeviceToDevice, e->stream);
+    if (r == hipSuccess) {
+      try { ser_tail_off.assign(new_num_keys - st->K, st->ser_len[st->cur]); } catch (...) { r = hipErrorOutOfMemory; }
+    }
+    if (r == hipSuccess)
+      r = hipMemcpyAsync(grown.ser_off[0] + st->K + 1, ser_tail_off.data(), ser_tail_off.size() * 8, hipMemcpyHostToDevice, e->stream);
+  }
   if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
   if (r != hipSuccess) {
     for (int i = 0; i < 2; ++i) {
       if (grown.block[i]) hipFree(grown.block[i]);
       if (grown.hist_off[i]) hipFree(grown.hist_off[i]);
+      if (grown.ser_off[i]) hipFree(grown.ser_off[i]);
     }
     return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_resize: %s (state unchanged)", hipGetErrorString(r));
   }
@@ -1342,6 +1501,14 @@ int tad_state_resize(tad_engine *eng, tad_state *st, uint64_t new_num_keys) {
       std::swap(st->hist_val[0], st->hist_val[1]);
       std::swap(st->hist_cap[0], st->hist_cap[1]);
       std::swap(st->hist_len[0], st->hist_len[1]);
+    }
+  }
+  if (st->series) {
+    for (int i = 0; i < 2; ++i) { hipFree(st->ser_off[i]); st->ser_off[i] = grown.ser_off[i]; }
+    if (st->cur == 1) {
+      std::swap(st->ser_val[0], st->ser_val[1]);
+      std::swap(st->ser_cap[0], st->ser_cap[1]);
+      std::swap(st->ser_len[0], st->ser_len[1]);
     }
   }
   st->K = new_num_keys;
@@ -1373,15 +1540,23 @@ int tad_state_import(tad_engine *eng, tad_state *st, const uint32_t *n, const do
 }
 
 int tad_state_create_ex(tad_engine *eng, uint64_t num_keys, uint32_t flags, tad_state **out) {
-  if (flags & ~TAD_STATE_HISTORY) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_create_ex: unknown flags 0x%x", flags & ~TAD_STATE_HISTORY);
+  const uint32_t known = TAD_STATE_HISTORY | TAD_STATE_SERIES;
+  if (flags & ~known) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_create_ex: unknown flags 0x%x", flags & ~known);
   int rc = tad_state_create(eng, num_keys, out);
-  if (rc != TAD_OK || !(flags & TAD_STATE_HISTORY)) return rc;
+  if (rc != TAD_OK || !(flags & known)) return rc;
   tad_state *st = *out;
-  st->history = true;
+  st->history = (flags & TAD_STATE_HISTORY) != 0;
+  st->series = (flags & TAD_STATE_SERIES) != 0;
   hipError_t r = hipSetDevice(eng->device);
   for (int i = 0; i < 2 && r == hipSuccess; ++i) {   // every key's segment empty: offsets all zero (the value arenas come with the first batch)
-    r = hipMalloc(reinterpret_cast<void **>(&st->hist_off[i]), (num_keys + 1) * 8);
-    if (r == hipSuccess) r = hipMemset(st->hist_off[i], 0, (num_keys + 1) * 8);
+    if (st->history) {
+      r = hipMalloc(reinterpret_cast<void **>(&st->hist_off[i]), (num_keys + 1) * 8);
+      if (r == hipSuccess) r = hipMemset(st->hist_off[i], 0, (num_keys + 1) * 8);
+    }
+    if (st->series && r == hipSuccess) {
+      r = hipMalloc(reinterpret_cast<void **>(&st->ser_off[i]), (num_keys + 1) * 8);
+      if (r == hipSuccess) r = hipMemset(st->ser_off[i], 0, (num_keys + 1) * 8);
+    }
   }
   if (r != hipSuccess) {
     tad_state_destroy(eng, st);
@@ -1459,6 +1634,72 @@ int tad_state_import_history(tad_engine *eng, tad_state *st, const uint64_t *len
   std::swap(st->hist_val[0], st->hist_val[1]);
   std::swap(st->hist_cap[0], st->hist_cap[1]);
   st->hist_len[st->cur] = total;
+  return TAD_OK;
+}
+
+int tad_state_series_points(tad_engine *eng, const tad_state *st, uint64_t *n_points) {
+  if (!eng || !st || !n_points) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_series_points: bad arguments");
+  std::lock_guard<std::mutex> state_lk(st->mu);
+  *n_points = st->series ? st->ser_len[st->cur] : 0;
+  return TAD_OK;
+}
+
+int tad_state_export_series(tad_engine *eng, const tad_state *st, uint64_t *len, uint64_t *values) {
+  if (!eng || !st || !len) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_series: bad arguments");
+  if (!st->series) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_series: the state has no series (TAD_STATE_SERIES)");
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_export_series: no job context available");
+  std::lock_guard<std::mutex> state_lk(st->mu);
+  HIP_TRY(e, hipSetDevice(e->device));
+  std::vector<unsigned long long> off;
+  try { off.resize(st->K + 1); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
+  HIP_TRY(e, hipMemcpy(off.data(), st->ser_off[st->cur], (st->K + 1) * 8, hipMemcpyDeviceToHost));
+  for (uint64_t k = 0; k < st->K; ++k) len[k] = off[k + 1] - off[k];
+  const uint64_t total = st->ser_len[st->cur];
+  if (values && total) HIP_TRY(e, hipMemcpy(values, st->ser_val[st->cur], total * 8, hipMemcpyDeviceToHost));
+  return TAD_OK;
+}
+
+int tad_state_import_series(tad_engine *eng, tad_state *st, const uint64_t *len, const uint64_t *values) {
+  if (!eng || !st || !len) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_series: bad arguments");
+  if (!st->series) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_series: the state has no series (TAD_STATE_SERIES)");
+  std::lock_guard<std::mutex> state_lk(st->mu);
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_import_series: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  const uint64_t K = st->K;
+  std::vector<uint32_t> n;
+  std::vector<unsigned long long> off;
+  try { n.resize(K); off.resize(K + 1); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
+  HIP_TRY(e, hipMemcpy(n.data(), state_view(st, st->cur).n, K * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  off[0] = 0;
+  for (uint64_t k = 0; k < K; ++k) {
+    if (len[k] != n[k])
+      return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_series: key %llu has %llu values, its state has n = %u (import the moments first); state unchanged",
+                  (unsigned long long)k, (unsigned long long)len[k], n[k]);
+    off[k + 1] = off[k] + len[k];
+  }
+  const uint64_t total = off[K];
+  if (total && !values) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_series: values is NULL");
+  // into the candidate copy, which then trades places with the current one: any failure leaves the series as it was
+  const int cand = st->cur ^ 1;
+  unsigned long long *val = st->ser_val[cand];
+  if (st->ser_cap[cand] < total) {
+    void *p = nullptr;
+    const hipError_t r = hipMalloc(&p, total * 8);
+    if (r != hipSuccess) { (void)hipGetLastError(); return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_import_series: %s; state unchanged", hipGetErrorString(r)); }
+    if (val) hipFree(val);
+    st->ser_val[cand] = val = static_cast<unsigned long long *>(p);
+    st->ser_cap[cand] = total;
+  }
+  if (total) HIP_TRY(e, hipMemcpy(val, values, total * 8, hipMemcpyHostToDevice));
+  HIP_TRY(e, hipMemcpy(st->ser_off[cand], off.data(), (K + 1) * 8, hipMemcpyHostToDevice));
+  std::swap(st->ser_off[0], st->ser_off[1]);
+  std::swap(st->ser_val[0], st->ser_val[1]);
+  std::swap(st->ser_cap[0], st->ser_cap[1]);
+  st->ser_len[st->cur] = total;
   return TAD_OK;
 }
 

@@ -94,6 +94,7 @@ struct JobCtx {
   DevBuf sp_comp_a, sp_comp_b, sp_val_a, sp_val_b, sp_temp, sp_first, sp_times;  // Stage 0 sparse (sort + rank grid)
   DevBuf sp_cls;                                                                  // Stage 0 sparse, length classes: per-key class arrays
   DevBuf hs_key, hs_t, hs_val, hs_sorted, hs_noise, hs_cnt, hs_row, hs_koff, hs_kcnt;   // a history batch: new points, sorted values, verdicts, rows, offsets
+  DevBuf as_key, as_pt, as_ser, as_fit, as_pos, as_ws;   // a stream ARIMA batch: per key | per new point | packed series | per fit | per position | fit workspace
   int arima_relaunches = 0;       // times the running job's ARIMA fit was relaunched after it had yielded to whole-CU jobs (tad_stats.arima_relaunches)
   bool sp_by_partition = false;   // the running job's sparse Stage 0 went through the partition pass + LDS sort (stage0_path 8 / 9 / 10 instead of 4 / 6 / 7)
   DevBuf part_fin;                                                                // Stage 0 v2, sampled histogram: final cursors of the (workgroup, partition) regions
@@ -134,6 +135,13 @@ struct tad_state {
   unsigned long long *hist_val[2] = {nullptr, nullptr};
   uint64_t hist_cap[2] = {0, 0};
   uint64_t hist_len[2] = {0, 0};
+  // TAD_STATE_SERIES: every key's aggregated point values in time order — ser_off[i] (K + 1 entries) and ser_val[i]; the same double
+  // buffering and growth as the history (a batch writes old segment ++ new points into the candidate)
+  bool series = false;
+  unsigned long long *ser_off[2] = {nullptr, nullptr};
+  unsigned long long *ser_val[2] = {nullptr, nullptr};
+  uint64_t ser_cap[2] = {0, 0};
+  uint64_t ser_len[2] = {0, 0};
   mutable std::mutex mu;     // batches of one state are serial (tad_run_stream from two threads on one state)
 };
 
@@ -198,7 +206,8 @@ template <typename F> void for_each_buf(JobCtx *c, F f) {
                     &c->key_mean, &c->key_m2, &c->rcp_table, &c->binhist, &c->part_total, &c->part_start, &c->part_offs32, &c->recs, &c->ovf, &c->slices,
                     &c->sp_comp_a, &c->sp_comp_b, &c->sp_val_a, &c->sp_val_b, &c->sp_temp, &c->sp_first, &c->sp_times, &c->sp_cls, &c->part_fin, &c->ovf_keys,
                     &c->in_key, &c->in_key2, &c->in_te, &c->in_ts, &c->in_val,
-                    &c->hs_key, &c->hs_t, &c->hs_val, &c->hs_sorted, &c->hs_noise, &c->hs_cnt, &c->hs_row, &c->hs_koff, &c->hs_kcnt};
+                    &c->hs_key, &c->hs_t, &c->hs_val, &c->hs_sorted, &c->hs_noise, &c->hs_cnt, &c->hs_row, &c->hs_koff, &c->hs_kcnt,
+                    &c->as_key, &c->as_pt, &c->as_ser, &c->as_fit, &c->as_pos, &c->as_ws};
   for (DevBuf *b : bufs) f(*b);
 }
 

@@ -279,6 +279,36 @@ void launch_hist_emit(hipStream_t s, const unsigned long long *nk, const long lo
   hipLaunchKernelGGL(k_hist_emit, dim3(hist_blocks(P_cap)), dim3(kHBlock), 0, s, nk, nt, nv, P_dev, noise, cnt, row, next, all_points, out);
 }
 
+// ---- the series of a streaming state (TAD_STATE_SERIES): every key's values in time order ----
+// A batch's new points are later than everything its key has seen (a late row fails the batch), so the candidate series of key k is
+// its old segment followed by its new points: soff_new[k] = soff_old[k] + poff[k], then one wavefront per key copies both.
+__global__ __launch_bounds__(kHBlock) void k_series_off(const unsigned long long *__restrict__ soff_old, const unsigned long long *__restrict__ poff,
+                                                       uint64_t K, unsigned long long *__restrict__ soff_new) {
+  const uint64_t k = (uint64_t)blockIdx.x * kHBlock + threadIdx.x;
+  if (k <= K) soff_new[k] = soff_old[k] + poff[k];
+}
+
+__global__ __launch_bounds__(kHBlock) void k_series_append(uint64_t K, const unsigned long long *__restrict__ soff_old,
+                                                          const unsigned long long *__restrict__ sval_old, const unsigned long long *__restrict__ poff,
+                                                          const unsigned long long *__restrict__ nv, const unsigned long long *__restrict__ soff_new,
+                                                          unsigned long long *__restrict__ sval_new) {
+  const uint64_t k = ((uint64_t)blockIdx.x * kHBlock + threadIdx.x) >> 6;   // wavefront-uniform
+  if (k >= K) return;
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned long long o0 = soff_old[k], a = soff_old[k + 1] - o0;
+  const unsigned long long p0 = poff[k], b = poff[k + 1] - p0;
+  unsigned long long *dst = sval_new + soff_new[k];
+  for (unsigned long long u = lane; u < a; u += 64) dst[u] = sval_old[o0 + u];
+  for (unsigned long long u = lane; u < b; u += 64) dst[a + u] = nv[p0 + u];
+}
+
+void launch_series_append(hipStream_t s, uint64_t K, const unsigned long long *soff_old, const unsigned long long *sval_old, const unsigned long long *poff,
+                          const unsigned long long *nv, unsigned long long *soff_new, unsigned long long *sval_new) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_series_off, dim3(hist_blocks(K + 1)), dim3(kHBlock), 0, s, soff_old, poff, K, soff_new);
+  hipLaunchKernelGGL(k_series_append, dim3(hist_blocks(K * 64)), dim3(kHBlock), 0, s, K, soff_old, sval_old, poff, nv, soff_new, sval_new);
+}
+
 const void *code_anchor_history() { return reinterpret_cast<const void *>(&k_hist_verdict); }
 
 }  // namespace tad

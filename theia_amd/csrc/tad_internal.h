@@ -357,6 +357,46 @@ int launch_dbscan(hipStream_t s, Grid g, double eps, int min_samples, void *scra
 bool launch_emit_dbscan_list(hipStream_t s, Grid g, Lattice lat, const void *scratch, const uint32_t *n_anom, const unsigned long long *off,
                              OutRows out);
 
+// the series of a streaming state (TAD_STATE_SERIES): soff_new = soff_old + poff; every key's old segment, then its new points nv[poff[k],
+// poff[k + 1]), into sval_new
+void launch_series_append(hipStream_t s, uint64_t K, const unsigned long long *soff_old, const unsigned long long *sval_old, const unsigned long long *poff,
+                          const unsigned long long *nv, unsigned long long *soff_new, unsigned long long *sval_new);
+// ---- streaming ARIMA (tad_arima.hip): a batch on a series state, per touched key (slot) and per new point ----
+struct ArimaSlots {
+  uint32_t *key;                 // the slot's key
+  unsigned long long *yoff;      // its series in the packed Box-Cox arrays (a multiple of 8)
+  double *lam, *sigma;           // lambda; stddev_samp from the post-batch moments
+  unsigned long long *ibase;     // new-point index of position 0 (wrapping)
+  uint32_t *lo, *hi;             // the positions of its fits [lo, hi) (empty without a result)
+  uint8_t *ok;                   // 1: the key has a result
+};
+struct FitListArgs {
+  const uint32_t *wave_pos;          // [waves] position of each wavefront of k_arima_fit_list
+  const uint32_t *cnt;               // [positions] fits per position
+  const unsigned long long *loff;    // [positions] first fit of each position in list
+  const uint32_t *list;              // [fits] slot of each fit
+  const unsigned long long *nv;      // [new points] values
+  double *pcalc;                     // [new points] predictions
+  uint8_t *pflag;                    // [new points] verdicts
+};
+// touched[k] = key k has new points, len8[k] = its whole series rounded up to 8 (0 if untouched), *tmax = the longest touched series
+void launch_as_touch(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *poff, uint32_t *touched, uint32_t *len8,
+                     unsigned int *tmax);
+// per touched key (slot tidx[k]): the Box-Cox fit over the whole series (lx, ysk at yoffk[k]), slots, predictions / verdicts of new points at p < 3
+void launch_as_prep(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *sval, const unsigned long long *poff,
+                    StreamState next, const unsigned long long *tidx, const unsigned long long *yoffk, double *lx, double *ysk, ArimaSlots sl,
+                    double *pcalc, uint8_t *pflag, DevCounters *ctr);
+// fill == false: cnt[p] += fits of the Kt slots at position p; fill == true: list / fpos of every fit from loff (cnt zeroed again first)
+void launch_as_list(hipStream_t s, uint64_t Kt, ArimaSlots sl, bool fill, unsigned int *cnt, const unsigned long long *loff, uint32_t *list, uint32_t *fpos);
+size_t arima_stream_ws_bytes(uint64_t nfits, uint64_t npos, uint64_t waves);
+int launch_arima_stream_fit(hipStream_t s, bool first, uint64_t nfits, uint64_t npos, uint64_t waves, const uint32_t *fpos, double *ysk,
+                            ArimaSlots sl, FitListArgs fa, int maxiter, DevCounters *ctr, void *workspace, const int *pause,
+                            const unsigned int **yielded, uint32_t grace);
+void launch_as_rows(hipStream_t s, uint64_t P, const unsigned long long *nk, const unsigned long long *tidx, const uint8_t *ok, const uint8_t *pflag,
+                    bool all_points, uint32_t *rows);
+void launch_as_emit(hipStream_t s, uint64_t P, const unsigned long long *nk, const long long *nt, const unsigned long long *nv,
+                    const unsigned long long *tidx, const double *sigma, const double *pcalc, const uint8_t *pflag, const uint32_t *rows,
+                    const unsigned long long *row_off, bool all_points, OutRows out);
 // drop detector (tad_drop.hip): sigma / n_pts / key_mean / key_m2 / counters + FLAG_ANOMALY; ws = K * T doubles
 void launch_drop(hipStream_t s, Grid g, double n_sigma, int min_samples, double *ws, double *sigma, uint32_t *n_pts,
                  double *key_mean, double *key_m2, DevCounters *ctr);

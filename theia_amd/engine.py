@@ -293,17 +293,22 @@ class TadPoints:
 
 class TadState:
     """Per-key running state of the streaming detectors (tad_state), resident in HBM.  history=True: the state also keeps every
-    aggregated point value it has seen, sorted per key (TAD_STATE_HISTORY), which the streaming DBSCAN detector needs."""
+    aggregated point value it has seen, sorted per key (TAD_STATE_HISTORY), which the streaming DBSCAN detector needs.  series=True:
+    it keeps them in time order (TAD_STATE_SERIES), which the streaming ARIMA detector needs."""
 
-    def __init__(self, engine, num_keys, history=False):
+    def __init__(self, engine, num_keys, history=False, series=False):
         self._engine = engine
         self.num_keys = int(num_keys)
         self.history = bool(history)
+        self.series = bool(series)
         h = C.c_void_p()
-        if self.history:
-            if not engine._lib.tad_features() & capi.TAD_FEATURE_STREAM_DBSCAN:
+        if self.history or self.series:
+            if self.history and not engine._lib.tad_features() & capi.TAD_FEATURE_STREAM_DBSCAN:
                 raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no streaming DBSCAN (TAD_FEATURE_STREAM_DBSCAN)")
-            engine._check(engine._lib.tad_state_create_ex(engine._h, self.num_keys, capi.TAD_STATE_HISTORY, C.byref(h)))
+            if self.series and not engine._lib.tad_features() & capi.TAD_FEATURE_STREAM_ARIMA:
+                raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no streaming ARIMA (TAD_FEATURE_STREAM_ARIMA)")
+            flags = (capi.TAD_STATE_HISTORY if self.history else 0) | (capi.TAD_STATE_SERIES if self.series else 0)
+            engine._check(engine._lib.tad_state_create_ex(engine._h, self.num_keys, flags, C.byref(h)))
         else:
             engine._check(engine._lib.tad_state_create(engine._h, self.num_keys, C.byref(h)))
         self._h = h
@@ -330,6 +335,29 @@ class TadState:
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "load_history: len has %d entries, the state holds %d keys" % (ln.size, self.num_keys))
         self._engine._check(self._engine._lib.tad_state_import_history(self._engine._h, self._h, ln.ctypes.data,
                                                                        vals.ctypes.data if vals.size else None))
+
+    def series_points(self):
+        """values held in the series (tad_state_series_points; 0 for a state without a series)"""
+        n = capi.u64()
+        self._engine._check(self._engine._lib.tad_state_series_points(self._engine._h, self._h, C.byref(n)))
+        return int(n.value)
+
+    def export_series(self):
+        """(len uint64[num_keys], values uint64[series_points()]): every key's values in time order, keys in order"""
+        ln = np.zeros(self.num_keys, np.uint64)
+        vals = np.zeros(self.series_points(), np.uint64)
+        self._engine._check(self._engine._lib.tad_state_export_series(self._engine._h, self._h, ln.ctypes.data,
+                                                                      vals.ctypes.data if vals.size else None))
+        return ln, vals
+
+    def load_series(self, len, values):
+        """Restore what export_series() returned (tad_state_import_series), after load() of the moments: len[k] must equal n[k]."""
+        ln = np.ascontiguousarray(len, dtype=np.uint64)
+        vals = np.ascontiguousarray(values, dtype=np.uint64)
+        if ln.shape != (self.num_keys,):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "load_series: len has %d entries, the state holds %d keys" % (ln.size, self.num_keys))
+        self._engine._check(self._engine._lib.tad_state_import_series(self._engine._h, self._h, ln.ctypes.data,
+                                                                      vals.ctypes.data if vals.size else None))
 
     def export(self):
         """dict of numpy arrays: n, avg, m2, ewma, last_t (one entry per key)."""
@@ -492,14 +520,16 @@ class TadEngine:
         return self.run(*args, _prepare_only=True, **kw)
 
     # ---- streaming EWMA / DBSCAN: one new batch against the per-key running state ----
-    def state_create(self, num_keys, history=False):
-        """history=True: a state for streaming DBSCAN too (tad_state_create_ex with TAD_STATE_HISTORY)"""
-        return TadState(self, num_keys, history=history)
+    def state_create(self, num_keys, history=False, series=False):
+        """history=True: a state for streaming DBSCAN too (tad_state_create_ex with TAD_STATE_HISTORY); series=True: for streaming
+        ARIMA too (TAD_STATE_SERIES)"""
+        return TadState(self, num_keys, history=history, series=series)
 
     def run_stream(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, emit_all=False, out="host",
-                   alpha=0.0, job_id="", num_keys=None, key_id2=None, algo="EWMA", eps=0.0, min_samples=0):
+                   alpha=0.0, job_id="", num_keys=None, key_id2=None, algo="EWMA", eps=0.0, min_samples=0, maxiter=0):
         """One batch of a streaming detector on `state` (tad_run_stream).  key_id2: the second key column of pod mode.  algo="DBSCAN"
-        needs a state with history: the rows are those tad_run(DBSCAN) emits for this batch's points over everything seen so far."""
+        needs a state with history, algo="ARIMA" (maxiter: arima_maxiter) a state with a series: the rows are those tad_run emits for
+        this batch's points over everything seen so far."""
         if algo not in capi.TAD_ALGO:
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "algo must be EWMA, ARIMA, DBSCAN or DROP")
         narrow = _narrow_flags(self._lib, key_id, key_id2, flow_end_s, None)
@@ -510,7 +540,8 @@ class TadEngine:
         if nt != n or nv != n or dev_t != dev or dev_v != dev or (key_id2 is not None and (nk2 != n or dev_k2 != dev)):
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "columns must have equal length and live in the same memory")
         job = capi.Job(algo=capi.TAD_ALGO[algo], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
-                       dbscan_eps=float(eps), dbscan_min_samples=int(min_samples), flags=(capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0) | narrow, id=job_id.encode()[:63])
+                       dbscan_eps=float(eps), dbscan_min_samples=int(min_samples), arima_maxiter=int(maxiter),
+                       flags=(capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0) | narrow, id=job_id.encode()[:63])
         cols = capi.Columns(n_rows=n, key_id=pk, key_id2=pk2, flow_end_s=pt, value=pv, num_keys=state.num_keys if num_keys is None else int(num_keys),
                             memory=capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST)
         if lattice is not None:

@@ -637,6 +637,7 @@ type State struct {
 	h       *C.tad_state
 	history bool
 	series  bool
+	times   bool
 }
 
 var streamDBSCANOnce sync.Once
@@ -803,6 +804,114 @@ func (s *State) ImportSeries(length []uint64, values []uint64) error {
 			return IllegalArgument{msg}
 		}
 		return fmt.Errorf("tad_state_import_series: %s (code %d)", msg, int(rc))
+	}
+	return nil
+}
+
+var streamTrimOnce sync.Once
+var streamTrimOK bool
+
+// hasStreamTrim: the library knows states with times and tad_state_trim (tad_features); an older one would not export the calls.
+func hasStreamTrim() bool {
+	streamTrimOnce.Do(func() { streamTrimOK = C.tad_features()&C.TAD_FEATURE_STREAM_TRIM != 0 })
+	return streamTrimOK
+}
+
+// NewStateWithTimes makes a series state that also keeps every series point's flowEndSeconds (tad_state_create_ex with
+// TAD_STATE_SERIES | TAD_STATE_TIMES; withHistory adds TAD_STATE_HISTORY), so that Trim can keep a window of time.
+func (e *Engine) NewStateWithTimes(numKeys uint64, withHistory bool) (*State, error) {
+	if !hasStreamTrim() {
+		return nil, errors.New("tadengine: libtad_mi355x.so has no state trim (TAD_FEATURE_STREAM_TRIM)")
+	}
+	flags := C.uint32_t(C.TAD_STATE_SERIES | C.TAD_STATE_TIMES)
+	if withHistory {
+		flags |= C.TAD_STATE_HISTORY
+	}
+	var h *C.tad_state
+	if rc := C.tad_state_create_ex(e.h, C.uint64_t(numKeys), flags, &h); rc != C.TAD_OK {
+		return nil, fmt.Errorf("tad_state_create_ex: %s (code %d)", C.GoString(C.tad_last_error(e.h)), int(rc))
+	}
+	return &State{e: e, h: h, history: withHistory, series: true, times: true}, nil
+}
+
+// Trim drops every key's oldest points (tad_state_trim): it keeps the points with flowEndSeconds >= keepFrom (0: no time rule; needs a
+// state made by NewStateWithTimes), then at most the newest keepPoints (0: no count rule).  The state becomes that of a fresh state
+// streamed only the retained points with EWMA parameter alpha (0 -> 0.5).  Returns the number of points dropped.
+func (s *State) Trim(keepPoints uint64, keepFrom int64, alpha float64) (uint64, error) {
+	if !hasStreamTrim() {
+		return 0, errors.New("tadengine: libtad_mi355x.so has no state trim (TAD_FEATURE_STREAM_TRIM)")
+	}
+	if !s.series {
+		return 0, IllegalArgument{"tadengine: a trim needs a state with a series (NewStateWithSeries or NewStateWithTimes)"}
+	}
+	if keepFrom != 0 && !s.times {
+		return 0, IllegalArgument{"tadengine: a trim by time needs a state made by NewStateWithTimes"}
+	}
+	var dropped C.uint64_t
+	if rc := C.tad_state_trim(s.e.h, s.h, C.uint64_t(keepPoints), C.int64_t(keepFrom), C.double(alpha), &dropped); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return 0, IllegalArgument{msg}
+		}
+		return 0, fmt.Errorf("tad_state_trim: %s (code %d)", msg, int(rc))
+	}
+	return uint64(dropped), nil
+}
+
+// Bytes is the device memory the state holds (tad_state_bytes): both moment blocks, the offsets and every arena at its capacity.
+func (s *State) Bytes() (uint64, error) {
+	if !hasStreamTrim() {
+		return 0, errors.New("tadengine: libtad_mi355x.so has no tad_state_bytes (TAD_FEATURE_STREAM_TRIM)")
+	}
+	var n C.uint64_t
+	if rc := C.tad_state_bytes(s.e.h, s.h, &n); rc != C.TAD_OK {
+		return 0, fmt.Errorf("tad_state_bytes: %s (code %d)", C.GoString(C.tad_last_error(s.e.h)), int(rc))
+	}
+	return uint64(n), nil
+}
+
+// ExportTimes copies every series point's flowEndSeconds to the host (tad_state_export_times), in the order of ExportSeries.
+func (s *State) ExportTimes() ([]int64, error) {
+	if !s.times || !hasStreamTrim() {
+		return nil, errors.New("tadengine: the state has no times")
+	}
+	total, err := s.SeriesPoints()
+	if err != nil {
+		return nil, err
+	}
+	t := make([]int64, total)
+	if total == 0 {
+		return t, nil
+	}
+	if rc := C.tad_state_export_times(s.e.h, s.h, (*C.int64_t)(unsafe.Pointer(&t[0]))); rc != C.TAD_OK {
+		return nil, fmt.Errorf("tad_state_export_times: %s (code %d)", C.GoString(C.tad_last_error(s.e.h)), int(rc))
+	}
+	return t, nil
+}
+
+// ImportTimes restores what ExportTimes returned (tad_state_import_times), after Import and ImportSeries: one time per series point,
+// every key's times strictly ascending and ending at its last_t, else the state is left as it was.
+func (s *State) ImportTimes(t []int64) error {
+	if !s.times || !hasStreamTrim() {
+		return errors.New("tadengine: the state has no times")
+	}
+	total, err := s.SeriesPoints()
+	if err != nil {
+		return err
+	}
+	if uint64(len(t)) != total {
+		return IllegalArgument{fmt.Sprintf("tadengine: %d times, the series holds %d points", len(t), total)}
+	}
+	var pt *C.int64_t
+	if len(t) > 0 {
+		pt = (*C.int64_t)(unsafe.Pointer(&t[0]))
+	}
+	if rc := C.tad_state_import_times(s.e.h, s.h, pt); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return IllegalArgument{msg}
+		}
+		return fmt.Errorf("tad_state_import_times: %s (code %d)", msg, int(rc))
 	}
 	return nil
 }

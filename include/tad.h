@@ -74,6 +74,7 @@ typedef enum { TAD_MEM_HOST = 0, TAD_MEM_DEVICE = 1 } tad_mem;
 #define TAD_FEATURE_NARROW_COLUMNS 1u /* TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 are honoured */
 #define TAD_FEATURE_STREAM_DBSCAN 2u  /* tad_state_create_ex(TAD_STATE_HISTORY) and tad_run_stream with TAD_ALGO_DBSCAN */
 #define TAD_FEATURE_STREAM_ARIMA 4u   /* tad_state_create_ex(TAD_STATE_SERIES) and tad_run_stream with TAD_ALGO_ARIMA */
+#define TAD_FEATURE_STREAM_TRIM 8u    /* TAD_STATE_TIMES, tad_state_trim, tad_state_bytes, tad_state_export_times / import_times */
 
 typedef struct tad_engine tad_engine; /* opaque; one per GPU; runs up to max_jobs_in_flight jobs concurrently (ABI 12) */
 
@@ -421,8 +422,9 @@ int tad_run_stream(tad_engine *e, tad_state *s, const tad_job *job, const tad_co
  * DBSCAN on a plain state is TAD_ERR_INVALID_ARGUMENT (state unchanged); ARIMA needs a state with a series (below); DROP has no
  * streaming form.
  * Invariant: after every successful call the history of key k holds n[k] values; a failed batch (late row, key out of range, out of
- * memory) leaves the history unchanged as well as the state.  The history is never evicted: it grows with the points seen (8 bytes
- * each, twice over: a batch merges into a second copy), and tad_state_history_points is how a caller watches it.  A batch costs an
+ * memory) leaves the history unchanged as well as the state.  A batch never evicts: the history grows with the points seen (8 bytes
+ * each, twice over: a batch merges into a second copy), and tad_state_history_points is how a caller watches it; a state that also has
+ * a series is bounded by tad_state_trim (below).  A batch costs an
  * EWMA stream batch, plus a rewrite of the history (about 16 B per history point), plus the sort and verdicts of its new points.
  * tad_state_resize gives the added keys empty histories.  tad_state_export / tad_state_import / tad_state_destroy are unchanged. */
 #define TAD_STATE_HISTORY 1u           /* keep every key's aggregated point values (sorted) */
@@ -462,6 +464,7 @@ int tad_state_import_history(tad_engine *e, tad_state *s, const uint64_t *len, c
  * ARIMA on a plain or history-only state and DROP on any state are TAD_ERR_INVALID_ARGUMENT (state unchanged).
  * Invariant: after every successful call the series of key k holds n[k] values.  tad_state_resize gives the added keys empty series. */
 #define TAD_STATE_SERIES 2u            /* keep every key's aggregated point values (time order) */
+#define TAD_STATE_TIMES 8u             /* with TAD_STATE_SERIES only: keep every series point's flowEndSeconds too (tad_state_trim, below) */
 /* total values in the series (0 for a state without a series) */
 int tad_state_series_points(tad_engine *e, const tad_state *s, uint64_t *n_points);
 /* HOST arrays: len[num_keys] and values[n_points], each key's values in time order, keys in order */
@@ -469,6 +472,40 @@ int tad_state_export_series(tad_engine *e, const tad_state *s, uint64_t *len, ui
 /* the inverse of tad_state_export_series, after tad_state_import of the moments: TAD_ERR_INVALID_ARGUMENT with the state unchanged
  * unless the state has a series and len[k] == n[k] of the state for every k */
 int tad_state_import_series(tad_engine *e, tad_state *s, const uint64_t *len, const uint64_t *values);
+
+/* ---- trimming a streaming state (TAD_FEATURE_STREAM_TRIM; check tad_features() before calling these) ----
+ * A long-running detector judges against a window, as the batch job does with start_time / end_time: "the last 24 h" or "the last N
+ * points of each key".  TAD_STATE_TIMES (valid only with TAD_STATE_SERIES; without it TAD_ERR_INVALID_ARGUMENT, as is bit 4u, which
+ * stays unknown) makes the state keep
+ * every series point's flowEndSeconds beside its value (int64, same offsets, double-buffered and grown like the series: 8 more bytes
+ * per point, twice over).  States without it are unchanged.
+ * tad_state_trim keeps, of every key's series in time order:
+ *   - with keep_from_t != 0, only the points with flow_end_s >= keep_from_t (needs TAD_STATE_TIMES, else TAD_ERR_INVALID_ARGUMENT);
+ *   - with keep_points != 0, only the newest keep_points of those;
+ *   - both 0: a no-op (TAD_OK).  *dropped (may be NULL) = the points removed.
+ * Contract: afterwards the state is bit for bit the state a fresh state with the same flags and num_keys holds after tad_run_stream of
+ * only the retained points, with EWMA parameter ewma_alpha (0 -> 0.5, as in tad_job):
+ *   - a key that lost points has n, avg, m2 and ewma replayed over its retained values in time order from the zero state, with the very
+ *     step of the stream batches; last_t = its newest retained point's time; a key that lost all of them is unseen (all zeros);
+ *   - a key that lost nothing keeps its state as it is, so the contract holds when its batches used ewma_alpha too;
+ *   - the series (and its times) is every key's retained suffix; the history, if the state has one, the sorted multiset of the retained
+ *     values (the history must be the series' values sorted, which every batch keeps; an import that breaks this voids the contract).
+ * Consequences: a DBSCAN or ARIMA batch after a trim emits exactly what tad_run emits over the retained points and the later batches for the
+ * batch's new points; an EWMA batch emits exactly what the fresh state would.  A trim needs a series (a history alone does not know
+ * which values are oldest): on a plain or history-only state it is TAD_ERR_INVALID_ARGUMENT.  It writes only the candidate copies and
+ * swaps them in when everything succeeded: any failure, allocation included, leaves state, history, series and times as they were.
+ * An arena left below a quarter of its capacity is allocated anew at twice its length, so the memory shrinks.  A trim costs about 16 B
+ * of traffic per series point (values and times), 16 B per history point plus the sort of the evicted values, and a serial replay per
+ * key that lost points, as long as the key's retained series.  Lock order: the state, then a job context, as a batch.
+ * tad_state_export_times / tad_state_import_times: HOST arrays of tad_state_series_points entries, in the order of
+ * tad_state_export_series.  Import after tad_state_import and tad_state_import_series (which leaves a times state refusing batches,
+ * trims and exports of the times until its times are imported): TAD_ERR_INVALID_ARGUMENT with the state unchanged unless the state has
+ * times, every key's times ascend strictly and every non-empty key's last time equals its last_t.
+ * tad_state_bytes: the device bytes the state holds — both moment blocks, the offsets and every arena at its capacity. */
+int tad_state_trim(tad_engine *e, tad_state *s, uint64_t keep_points, int64_t keep_from_t, double ewma_alpha, uint64_t *dropped);
+int tad_state_bytes(tad_engine *e, const tad_state *s, uint64_t *bytes);
+int tad_state_export_times(tad_engine *e, const tad_state *s, int64_t *t);
+int tad_state_import_times(tad_engine *e, tad_state *s, const int64_t *t);
 
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).

@@ -1,0 +1,369 @@
+"""GPU: trimming a streaming state (tad_state_trim, include/tad.h).  The defining property: after a trim the state is bit for bit the
+state a fresh state with the same flags holds after being streamed only the retained points — moments, last_t, history, series and
+times — so a DBSCAN or ARIMA batch after the trim emits exactly what tad_run emits over (retained points + the batch) for the batch's
+points, and an EWMA batch exactly what the fresh state emits.  The references are the engine's own fresh-state stream and tad_run (both
+pinned to the oracle by the stream tests); the retained table is one row per retained point (key, time, aggregated value).  Float
+columns are compared as uint64 bit patterns.  A refused call leaves the state as it was."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle import tad_oracle as orc
+from theia_amd import TadError, _capi
+
+pytestmark = pytest.mark.gpu
+
+T_BASE = 1660202814
+ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
+STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
+SKIP = np.uint64((1 << 64) - 1)
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
+
+
+def rows_of(res):
+    d = {f: np.asarray(res[f]) for f in ROW_FIELDS}
+    if "anomaly" in res.to_host():
+        d["anomaly"] = np.asarray(res["anomaly"])
+    return d
+
+
+def point_codes(k, t, k2=None):
+    ks = [np.asarray(k, np.uint64)] + ([np.asarray(k2, np.uint64)] if k2 is not None else [])
+    tt = (np.asarray(t, np.int64) - T_BASE + (1 << 31)).astype(np.uint64)
+    return np.unique(np.concatenate([(kk[kk != SKIP] << np.uint64(32)) | tt[kk != SKIP] for kk in ks]))
+
+
+def restrict(rows, codes):
+    c = (rows["key_id"].astype(np.uint64) << np.uint64(32)) | (rows["flow_end_s"].astype(np.int64) - T_BASE + (1 << 31)).astype(np.uint64)
+    sel = np.isin(c, codes)
+    return {f: a[sel] for f, a in rows.items()}
+
+
+def assert_rows(got, want, what=""):
+    assert set(got) == set(want), (what, sorted(got), sorted(want))
+    assert got["key_id"].size == want["key_id"].size, (what, got["key_id"].size, want["key_id"].size)
+    for f in want:
+        assert np.array_equal(bits(got[f]), bits(want[f])), (what, f)
+
+
+HIST, SER, TIMES = 1, 2, 8     # TAD_STATE_HISTORY, TAD_STATE_SERIES, TAD_STATE_TIMES
+ALL = HIST | SER | TIMES
+
+
+def new_state(engine, K, flags=ALL):
+    return engine.state_create(K, history=bool(flags & HIST), series=bool(flags & SER), times=bool(flags & TIMES))
+
+
+def snapshot(st):
+    return {"state": st.export(), "history": st.export_history() if st.history else None,
+            "series": st.export_series() if st.series else None, "times": st.export_times() if st.times else None}
+
+
+def assert_same(a, b, what=""):
+    for f in STATE_FIELDS:
+        assert np.array_equal(bits(a["state"][f]), bits(b["state"][f])), (what, f)
+    for part in ("history", "series"):
+        if a[part] is not None or b[part] is not None:
+            assert np.array_equal(a[part][0], b[part][0]) and np.array_equal(a[part][1], b[part][1]), (what, part)
+    if a["times"] is not None or b["times"] is not None:
+        assert np.array_equal(a["times"], b["times"]), (what, "times")
+
+
+def retained(st, keep_points=0, keep_from=0):
+    """the points a trim keeps, from the state's own series and times: (key, time, value) in (key, time) order"""
+    ln, vals = st.export_series()
+    t = st.export_times()
+    keys = np.repeat(np.arange(st.num_keys, dtype=np.uint64), ln.astype(np.int64))
+    off = np.concatenate([[0], np.cumsum(ln.astype(np.int64))])
+    keep = np.zeros(vals.size, bool)
+    for k in np.nonzero(ln)[0]:
+        seg = t[off[k]:off[k + 1]]
+        lo = int(np.searchsorted(seg, keep_from, "left")) if keep_from else 0
+        r = seg.size - lo
+        if keep_points:
+            r = min(r, keep_points)
+        keep[off[k + 1] - r:off[k + 1]] = True
+    return keys[keep], t[keep], vals[keep]
+
+
+def fresh(engine, K, pts, op, flags=ALL, alpha=0.0):
+    """a fresh state streamed only the retained points (one row per point)"""
+    st = new_state(engine, K, flags)
+    if pts[0].size:
+        engine.run_stream(st, pts[0], pts[1], pts[2], agg_flow="svc", value_op=op, alpha=alpha)
+    return st
+
+
+def minute_batches(n_rows, K, T, cuts, pod=False):
+    k, t, v = orc.synth_rows(0, n_rows, K, T)
+    bucket = (t - orc.SYNTH_T_BASE) // orc.SYNTH_T_STEP
+    edges = (0,) + tuple(cuts) + (T,)
+    k2 = ((k + np.uint64(7)) % np.uint64(K)).astype(np.uint64)
+    out = []
+    for lo, hi in zip(edges[:-1], edges[1:]):
+        sel = (bucket >= lo) & (bucket < hi)
+        out.append((k[sel], t[sel], v[sel]) + ((k2[sel],) if pod else ()))
+    return out
+
+
+def second_batches(K, n_batches, width, pts_per_batch, seed, lifetimes=False):
+    """second-resolution rows (two per point) in batches of `width` seconds; every key has exactly pts_per_batch points in every batch
+    it is alive in.  lifetimes: a third of the keys only in the first half, a third only in the last batches, the rest throughout."""
+    rng = np.random.default_rng(seed)
+    out = []
+    base = 1_000_000_000 + (orc.mix64(np.arange(K, dtype=np.uint64) + np.uint64(5)) % np.uint64(3_000_000_000)).astype(np.int64)
+    for b in range(n_batches):
+        alive = np.ones(K, bool)
+        if lifetimes:
+            g = np.arange(K) % 3
+            alive = (g == 2) | ((g == 0) & (b < n_batches // 2)) | ((g == 1) & (b >= n_batches - 2))
+        ks = np.nonzero(alive)[0].astype(np.uint64)
+        pk = np.repeat(ks, pts_per_batch)
+        pt = np.concatenate([np.sort(rng.choice(width, pts_per_batch, replace=False)) for _ in ks]).astype(np.int64) + T_BASE + b * width
+        k, t = np.repeat(pk, 2), np.repeat(pt, 2)
+        v = (np.repeat(base[pk.astype(np.int64)], 2) + rng.integers(-300_000_000, 300_000_000, size=k.size)).astype(np.uint64)
+        order = rng.permutation(k.size)
+        out.append((k[order], t[order], v[order]))
+    return out
+
+
+def check_trim(engine, st, K, op, keep_points=0, keep_from=0, alpha=0.0):
+    """trim st and compare it with a fresh state streamed the retained points"""
+    pts = retained(st, keep_points, keep_from)
+    before = st.series_points()
+    dropped = st.trim(keep_points=keep_points, keep_from=keep_from, alpha=alpha)
+    assert dropped == before - pts[0].size
+    assert st.series_points() == pts[0].size
+    if st.history:
+        assert st.history_points() == pts[0].size
+    ref = fresh(engine, K, pts, op, alpha=alpha)
+    assert_same(snapshot(st), snapshot(ref), (keep_points, keep_from))
+    ref.close()
+    return pts
+
+
+# ---- 1. a count trim equals a fresh state streamed the retained points ----
+@pytest.mark.parametrize("form", ["minute", "second"])
+def test_count_trim_equals_a_fresh_state(engine, form):
+    if form == "minute":
+        K, op = 90, "sum"
+        batches = minute_batches(30000, K, 48, (6, 20, 31))
+    else:
+        K, op = 5000, "max"     # (5000 keys x an hour of seconds: the batches go sparse)
+        batches = second_batches(K, 4, 3600, 3, seed=3)
+    st = new_state(engine, K)
+    for b, (bk, bt, bv) in enumerate(batches):
+        r = engine.run_stream(st, bk, bt, bv, agg_flow="svc", value_op=op, algo=("EWMA", "DBSCAN", "ARIMA")[b % 3])
+        if form == "second":
+            assert r.stats["stage0_path"] in (4, 8), r.stats["stage0_path"]
+    n = st.export()["n"]
+    assert np.array_equal(st.export_series()[0], n.astype(np.uint64))
+    for keep in (int(n.max()) + 5, 9, 4, 1):      # (the first keeps everything: a no-op)
+        check_trim(engine, st, K, op, keep_points=keep)
+    st.close()
+
+
+# ---- 2. a time trim: keys that lose all, keys that lose none, both rules at once ----
+def test_time_trim_and_both_rules(engine):
+    K, width, alpha = 600, 900, 0.3
+    batches = second_batches(K, 8, width, 5, seed=11, lifetimes=True)
+    states = []
+    for _ in range(3):
+        st = new_state(engine, K)
+        for bk, bt, bv in batches:
+            engine.run_stream(st, bk, bt, bv, agg_flow="svc", value_op="sum", alpha=alpha)
+        states.append(st)
+    cut = T_BASE + 5 * width + 300
+    st = states[0]
+    pts = check_trim(engine, st, K, "sum", keep_from=cut, alpha=alpha)
+    n = st.export()["n"]
+    g = np.arange(K) % 3
+    assert (n[g == 0] == 0).all() and (st.export()["last_t"][g == 0] == 0).all()    # lost everything: unseen
+    assert (n[g == 1] == 10).all()                                                     # lost nothing
+    assert pts[1].min() >= cut
+    check_trim(engine, st, K, "sum", keep_from=cut + 900, alpha=alpha)                  # again, later
+    check_trim(engine, states[1], K, "sum", keep_points=4, keep_from=cut, alpha=alpha)  # both rules
+    check_trim(engine, states[2], K, "sum", keep_from=T_BASE + 100 * width, alpha=alpha)  # everything goes
+    assert states[2].series_points() == 0 and (states[2].export()["n"] == 0).all()
+    for s in states:
+        s.close()
+
+
+# ---- 3. rows after a trim ----
+def window_rows(engine, algo, K, pts, batch, op, emit_all=False, pod=False):
+    """tad_run over (the retained table, one row per point) + the batch, restricted to the batch's points"""
+    k = np.concatenate([pts[0], batch[0]])
+    t = np.concatenate([pts[1], batch[1]])
+    v = np.concatenate([pts[2], batch[2]])
+    kw = dict(key_id2=np.concatenate([np.full(pts[0].size, SKIP, np.uint64), batch[3]])) if pod else {}
+    res = engine.run(algo, k, t, v, K, agg_flow="pod" if pod else "svc", value_op=op, emit_all=emit_all, **kw)
+    return restrict(rows_of(res), point_codes(batch[0], batch[1], batch[3] if pod else None))
+
+
+@pytest.mark.parametrize("emit_all", [False, True])
+def test_rows_after_a_trim(engine, emit_all):
+    K, op = 80, "sum"
+    batches = minute_batches(40000, K, 60, (10, 25, 40, 50))
+    sts = {a: new_state(engine, K) for a in ("EWMA", "DBSCAN", "ARIMA")}
+    for bk, bt, bv in batches[:3]:
+        for st in sts.values():
+            engine.run_stream(st, bk, bt, bv, agg_flow="svc", value_op=op)
+    for b, keep in ((3, 12), (4, 7)):
+        bk, bt, bv = batches[b]
+        pts = None
+        for algo, st in sts.items():
+            pts = retained(st, keep_points=keep)
+            st.trim(keep_points=keep)
+            got = rows_of(engine.run_stream(st, bk, bt, bv, agg_flow="svc", value_op=op, algo=algo, emit_all=emit_all))
+            if algo == "EWMA":
+                ref = fresh(engine, K, pts, op)
+                want = rows_of(engine.run_stream(ref, bk, bt, bv, agg_flow="svc", value_op=op, emit_all=emit_all))
+                assert_same(snapshot(st), snapshot(ref), b)
+                ref.close()
+            else:
+                want = window_rows(engine, algo, K, pts, (bk, bt, bv), op, emit_all)
+            assert_rows(got, want, (algo, b))
+            assert got["key_id"].size > 0 or not emit_all
+    for st in sts.values():
+        st.close()
+
+
+def test_rows_after_a_trim_pod_mode(engine):
+    K = 60
+    batches = minute_batches(30000, K, 40, (12, 26), pod=True)
+    for algo in ("DBSCAN", "ARIMA"):
+        st = new_state(engine, K)
+        for bk, bt, bv, bk2 in batches[:2]:
+            engine.run_stream(st, bk, bt, bv, agg_flow="pod", key_id2=bk2, value_op="max")
+        pts = retained(st, keep_points=9)
+        st.trim(keep_points=9)
+        bk, bt, bv, bk2 = batches[2]
+        got = rows_of(engine.run_stream(st, bk, bt, bv, agg_flow="pod", key_id2=bk2, value_op="max", algo=algo, emit_all=True))
+        assert_rows(got, window_rows(engine, algo, K, pts, batches[2], "max", emit_all=True, pod=True), algo)
+        st.close()
+
+
+# ---- 4. a sliding window: trim to the last W seconds before every batch ----
+def test_sliding_window(engine):
+    K, width, n_batches, W = 150, 600, 22, 3000
+    batches = second_batches(K, n_batches, width, 4, seed=21)
+    with engine.plan(sparse="always", sparse_sort="lsd"):   # (sparse batches: an arena grows by the batch's points, not a grid bound)
+        sliding_window(engine, K, width, W, batches)
+
+
+def sliding_window(engine, K, width, W, batches):
+    st_d, st_a, twin = new_state(engine, K), new_state(engine, K, SER | TIMES), new_state(engine, K)
+    sizes, twin_sizes = [], []
+    for b, (bk, bt, bv) in enumerate(batches):
+        keep_from = T_BASE + b * width - W
+        if b:
+            assert st_d.trim(keep_from=keep_from) > (0 if b * width > W else -1)
+            st_a.trim(keep_from=keep_from)
+        wk = np.concatenate([x[0] for x in batches[:b + 1]])
+        wt = np.concatenate([x[1] for x in batches[:b + 1]])
+        wv = np.concatenate([x[2] for x in batches[:b + 1]])
+        sel = wt >= keep_from
+        for algo, st in (("DBSCAN", st_d), ("ARIMA", st_a)):
+            got = rows_of(engine.run_stream(st, bk, bt, bv, agg_flow="svc", value_op="sum", algo=algo, emit_all=True))
+            res = engine.run(algo, wk[sel], wt[sel], wv[sel], K, agg_flow="svc", value_op="sum", emit_all=True)
+            assert_rows(got, restrict(rows_of(res), point_codes(bk, bt)), (algo, b))
+        assert engine.run_stream(twin, bk, bt, bv, agg_flow="svc", value_op="sum").stats["stage0_path"] == 4
+        sizes.append(st_d.nbytes())
+        twin_sizes.append(twin.nbytes())
+    full = W // width + 2
+    assert len(set(sizes[full + 2:])) == 1, sizes             # the window is full: the state stops growing
+    assert twin_sizes[-1] > twin_sizes[full + 2] and twin_sizes[-1] > 2 * sizes[-1], (twin_sizes, sizes)
+    for s in (st_d, st_a, twin):
+        s.close()
+
+
+# ---- 5. refused calls leave the state unchanged ----
+def test_failures_leave_the_state_unchanged(engine):
+    K = 50
+    batches = minute_batches(12000, K, 30, (15,))
+    for flags in (0, HIST, SER, ALL):
+        st = new_state(engine, K, flags)
+        for bk, bt, bv in batches:
+            engine.run_stream(st, bk, bt, bv, agg_flow="svc", value_op="sum")
+        snap = snapshot(st)
+        if flags in (0, HIST):    # no series: no trim at all
+            with pytest.raises(TadError):
+                st.trim(keep_points=3)
+        if flags == SER:          # no times: no trim by time
+            with pytest.raises(TadError):
+                st.trim(keep_from=T_BASE)
+            with pytest.raises(TadError):
+                st.export_times()
+        if flags == ALL:          # times imports that do not fit
+            t = snap["times"]
+            ln = snap["series"][0].astype(np.int64)
+            k = int(np.nonzero(ln > 2)[0][0])
+            o = int(ln[:k].sum())
+            bad = t.copy(); bad[o], bad[o + 1] = bad[o + 1], bad[o]
+            with pytest.raises(TadError):
+                st.load_times(bad)                      # not ascending
+            bad = t.copy(); bad[o + 1] = bad[o]
+            with pytest.raises(TadError):
+                st.load_times(bad)                      # not strictly ascending
+            with pytest.raises(TadError):
+                st.load_times(t[:-1])                   # wrong length
+            bad = t.copy(); bad[o + ln[k] - 1] += 1
+            with pytest.raises(TadError):
+                st.load_times(bad)                      # last time != last_t
+            st.load_times(t)                            # (the right ones are taken)
+        assert_same(snapshot(st), snap, flags)
+        st.close()
+    with pytest.raises(TadError):
+        engine.state_create(K, times=True)              # times without a series
+    h = C.c_void_p()
+    for flags in (TIMES, TIMES | HIST, 4, 4 | SER, 16, 16 | SER):   # times without a series; unknown bits (4u stays unknown)
+        assert engine._lib.tad_state_create_ex(engine._h, K, flags, C.byref(h)) == _capi.TAD_ERR_INVALID_ARGUMENT, flags
+    assert not h.value
+    st = new_state(engine, K, SER | TIMES)
+    assert st.trim() == 0 and st.series_points() == 0   # both rules 0: a no-op
+    st.close()
+
+
+# ---- 6. restart, resize ----
+def test_restart_after_a_trim(engine):
+    K = 70
+    batches = minute_batches(30000, K, 50, (10, 20, 35))
+    st = new_state(engine, K)
+    for bk, bt, bv in batches[:2]:
+        engine.run_stream(st, bk, bt, bv, agg_flow="svc", value_op="sum")
+    st.trim(keep_points=6)
+    snap = snapshot(st)
+    st2 = new_state(engine, K)
+    st2.load(snap["state"])
+    st2.load_history(*snap["history"])
+    st2.load_series(*snap["series"])
+    with pytest.raises(TadError):       # the series without its times: no batch
+        engine.run_stream(st2, *batches[2], agg_flow="svc", value_op="sum")
+    st2.load_times(snap["times"])
+    assert_same(snapshot(st2), snap)
+    for b, algo in ((2, "DBSCAN"), (3, "ARIMA")):
+        got = [rows_of(engine.run_stream(s, *batches[b], agg_flow="svc", value_op="sum", algo=algo, emit_all=True)) for s in (st, st2)]
+        assert_rows(got[1], got[0], algo)
+    assert_same(snapshot(st2), snapshot(st))
+    st.close()
+    st2.close()
+
+
+def test_resize_and_trim(engine):
+    K, K2 = 60, 75
+    batches = minute_batches(30000, K2, 40, (12, 26))
+    first = [(bk[bk < K], bt[bk < K], bv[bk < K]) for bk, bt, bv in batches[:2]]
+    st = new_state(engine, K)
+    for bk, bt, bv in first:
+        engine.run_stream(st, bk, bt, bv, agg_flow="svc", value_op="sum")
+    st.trim(keep_points=8)              # a resize after a trim ...
+    st.resize(K2)
+    engine.run_stream(st, *batches[2], agg_flow="svc", value_op="sum")
+    check_trim(engine, st, K2, "sum", keep_points=5)     # ... and a trim after a resize
+    check_trim(engine, st, K2, "sum", keep_from=int(batches[2][1].min()) + 60)
+    st.close()

@@ -23,6 +23,8 @@ TAD_FEATURE_STREAM_DBSCAN = 2                # tad_features() bit: tad_state_cre
 TAD_STATE_HISTORY = 1                        # tad_state_create_ex flag: keep every key's aggregated point values (sorted)
 TAD_FEATURE_STREAM_ARIMA = 4                 # tad_features() bit: tad_state_create_ex(TAD_STATE_SERIES), tad_run_stream with ARIMA
 TAD_STATE_SERIES = 2                         # tad_state_create_ex flag: keep every key's aggregated point values (time order)
+TAD_FEATURE_STREAM_TRIM = 8                  # tad_features() bit: TAD_STATE_TIMES, tad_state_trim, tad_state_bytes, export / import of times
+TAD_STATE_TIMES = 8                          # tad_state_create_ex flag (with TAD_STATE_SERIES): keep every series point's flowEndSeconds
 
 
 class Plan(C.Structure):
@@ -129,6 +131,10 @@ SYMBOLS = {
     "tad_state_series_points": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(u64)]),
     "tad_state_export_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_state_import_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tad_state_trim": (C.c_int, [C.c_void_p, C.c_void_p, u64, i64, f64, C.POINTER(u64)]),
+    "tad_state_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(u64)]),
+    "tad_state_export_times": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tad_state_import_times": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_run_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_aggregate": (C.c_int, [C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Points))]),
     "tad_points_free": (None, [C.c_void_p, C.POINTER(Points)]),

@@ -237,9 +237,10 @@ struct HistBatch {
   const unsigned long long *row = nullptr;
 };
 
-// grows a candidate value arena of a state (history or series) to hold `need` values, geometrically; the current arena is not touched, so a
-// failure leaves the state as it is
-int grow_arena(JobCtx *e, unsigned long long *&val, uint64_t &cap, uint64_t need, const char *what) {
+// grows a candidate value arena of a state (history, series or times) to hold `need` values, geometrically; the current arena is not
+// touched, so a failure leaves the state as it is
+template <typename T>
+int grow_arena(JobCtx *e, T *&val, uint64_t &cap, uint64_t need, const char *what) {
   if (cap >= need) return TAD_OK;
   const uint64_t want = need > 2 * cap ? need : 2 * cap;
   HIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -253,8 +254,31 @@ int grow_arena(JobCtx *e, unsigned long long *&val, uint64_t &cap, uint64_t need
     return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_run_stream: %llu values of %s do not fit (%s); state unchanged", (unsigned long long)need, what,
                 hipGetErrorString(r));
   }
-  val = static_cast<unsigned long long *>(p);
+  val = static_cast<T *>(p);
   cap = want;
+  return TAD_OK;
+}
+
+// a trim leaves `len` values in an arena: below a quarter of its capacity the arena is given back and, for a candidate that is about to be
+// written, allocated anew at twice the length (how a trimmed state's memory actually shrinks); a candidate too small grows to twice the
+// length too.  Only candidate arenas come here, so a failure leaves the state as it is.
+template <typename T>
+int size_trim_arena(JobCtx *e, T *&val, uint64_t &cap, uint64_t len, bool allocate) {
+  if (cap >= len && !(len * 4 < cap)) return TAD_OK;
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  if (val) hipFree(val);
+  val = nullptr;
+  cap = 0;
+  if (!allocate || len == 0) return TAD_OK;
+  void *p = nullptr;
+  const hipError_t r = hipMalloc(&p, 2 * len * sizeof(T));
+  if (r != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_trim: %llu retained values do not fit (%s); state unchanged", (unsigned long long)len,
+                hipGetErrorString(r));
+  }
+  val = static_cast<T *>(p);
+  cap = 2 * len;
   return TAD_OK;
 }
 
@@ -277,6 +301,7 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
   const uint64_t need = st->hist_len[cur] + P_cap;
   if (st->history && (rc = grow_arena(e, st->hist_val[cand], st->hist_cap[cand], need, "history")) != TAD_OK) return rc;
   if (st->series && (rc = grow_arena(e, st->ser_val[cand], st->ser_cap[cand], st->ser_len[cur] + P_cap, "series")) != TAD_OK) return rc;
+  if (st->times && (rc = grow_arena(e, st->ser_t[cand], st->ser_tcap[cand], st->ser_len[cur] + P_cap, "times")) != TAD_OK) return rc;
   const uint64_t pc = P_cap ? P_cap : 1;
   if ((rc = ensure(e, e->hs_key, pc * 8)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->hs_t, pc * 8)) != TAD_OK) return rc;
@@ -316,6 +341,9 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
   }
   if (st->series)      // 3'. appended to its series in the candidate arena
     launch_series_append(s, K, st->ser_off[cur], st->ser_val[cur], poff, nv, st->ser_off[cand], st->ser_val[cand]);
+  if (st->times)       // 3''. and their times beside them (the same offsets, written again)
+    launch_series_append(s, K, st->ser_off[cur], reinterpret_cast<const unsigned long long *>(st->ser_t[cur]), poff,
+                         reinterpret_cast<const unsigned long long *>(nt), st->ser_off[cand], reinterpret_cast<unsigned long long *>(st->ser_t[cand]));
   HIP_TRY(e, hipMemcpyAsync(static_cast<unsigned char *>(e->counters.p) + kTailHistLen, poff + K, 8, hipMemcpyDeviceToDevice, s));
   hb->nk = nk; hb->nt = nt; hb->nv = nv; hb->poff = poff; hb->P_dev = poff + K; hb->P_cap = P_cap;
   if (dbscan && P_cap) {   // 4. verdicts of the new points; 5. their rows (the row total lands in the job's tail)
@@ -496,6 +524,8 @@ int run_job(tad_engine *eng, const tad_job *job, const tad_columns *cols, tad_me
   // one job context = one job in flight; a streaming state is advanced by one batch at a time
   std::unique_lock<std::mutex> state_lk;
   if (stream) state_lk = std::unique_lock<std::mutex>(stream->mu);
+  if (stream && stream->times_stale)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: the series was imported without its times (tad_state_import_times); state unchanged");
   Lease lease(eng, job->id, !points_mode && job->algo == TAD_ALGO_ARIMA);
   if (!lease.c) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_run: no job context available");
   PauseHold hold(eng);     // (declared after the lease: dropped before the context goes back to the pool)
@@ -1415,6 +1445,7 @@ void tad_state_destroy(tad_engine *e, tad_state *st) {
     if (st->hist_val[i]) hipFree(st->hist_val[i]);
     if (st->ser_off[i]) hipFree(st->ser_off[i]);
     if (st->ser_val[i]) hipFree(st->ser_val[i]);
+    if (st->ser_t[i]) hipFree(st->ser_t[i]);
   }
   delete st;
 }
@@ -1509,6 +1540,8 @@ int tad_state_resize(tad_engine *eng, tad_state *st, uint64_t new_num_keys) {
       std::swap(st->ser_val[0], st->ser_val[1]);
       std::swap(st->ser_cap[0], st->ser_cap[1]);
       std::swap(st->ser_len[0], st->ser_len[1]);
+      std::swap(st->ser_t[0], st->ser_t[1]);   // (the times share the series' offsets)
+      std::swap(st->ser_tcap[0], st->ser_tcap[1]);
     }
   }
   st->K = new_num_keys;
@@ -1540,13 +1573,17 @@ int tad_state_import(tad_engine *eng, tad_state *st, const uint32_t *n, const do
 }
 
 int tad_state_create_ex(tad_engine *eng, uint64_t num_keys, uint32_t flags, tad_state **out) {
-  const uint32_t known = TAD_STATE_HISTORY | TAD_STATE_SERIES;
+  const uint32_t known = TAD_STATE_HISTORY | TAD_STATE_SERIES | TAD_STATE_TIMES;
+  if (out) *out = nullptr;
   if (flags & ~known) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_create_ex: unknown flags 0x%x", flags & ~known);
+  if ((flags & TAD_STATE_TIMES) && !(flags & TAD_STATE_SERIES))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_create_ex: TAD_STATE_TIMES needs TAD_STATE_SERIES");
   int rc = tad_state_create(eng, num_keys, out);
   if (rc != TAD_OK || !(flags & known)) return rc;
   tad_state *st = *out;
   st->history = (flags & TAD_STATE_HISTORY) != 0;
   st->series = (flags & TAD_STATE_SERIES) != 0;
+  st->times = (flags & TAD_STATE_TIMES) != 0;   // (the times arenas come with the first batch, like the values)
   hipError_t r = hipSetDevice(eng->device);
   for (int i = 0; i < 2 && r == hipSuccess; ++i) {   // every key's segment empty: offsets all zero (the value arenas come with the first batch)
     if (st->history) {
@@ -1700,6 +1737,158 @@ int tad_state_import_series(tad_engine *eng, tad_state *st, const uint64_t *len,
   std::swap(st->ser_val[0], st->ser_val[1]);
   std::swap(st->ser_cap[0], st->ser_cap[1]);
   st->ser_len[st->cur] = total;
+  st->times_stale = st->times;   // the times of a times state come next (tad_state_import_times)
+  return TAD_OK;
+}
+
+int tad_state_export_times(tad_engine *eng, const tad_state *st, int64_t *t) {
+  if (!eng || !st) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_times: bad arguments");
+  if (!st->times) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_times: the state has no times (TAD_STATE_TIMES)");
+  std::lock_guard<std::mutex> state_lk(st->mu);
+  if (st->times_stale)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_times: the series was imported without its times (tad_state_import_times)");
+  const uint64_t total = st->ser_len[st->cur];
+  if (!total) return TAD_OK;
+  if (!t) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_times: t is NULL");
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_export_times: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  HIP_TRY(e, hipMemcpy(t, st->ser_t[st->cur], total * 8, hipMemcpyDeviceToHost));
+  return TAD_OK;
+}
+
+int tad_state_import_times(tad_engine *eng, tad_state *st, const int64_t *t) {
+  if (!eng || !st) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_times: bad arguments");
+  if (!st->times) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_times: the state has no times (TAD_STATE_TIMES)");
+  std::lock_guard<std::mutex> state_lk(st->mu);
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_import_times: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  const uint64_t K = st->K, total = st->ser_len[st->cur];
+  if (total && !t) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_times: t is NULL");
+  std::vector<long long> last;
+  std::vector<unsigned long long> off;
+  try { last.resize(K); off.resize(K + 1); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
+  HIP_TRY(e, hipMemcpy(off.data(), st->ser_off[st->cur], (K + 1) * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(e, hipMemcpy(last.data(), state_view(st, st->cur).last_t, K * sizeof(long long), hipMemcpyDeviceToHost));
+  for (uint64_t k = 0; k < K; ++k) {
+    if (off[k + 1] == off[k]) continue;
+    for (uint64_t i = off[k] + 1; i < off[k + 1]; ++i)
+      if (t[i] <= t[i - 1])
+        return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_times: the times of key %llu are not strictly ascending; state unchanged",
+                    (unsigned long long)k);
+    if (t[off[k + 1] - 1] != last[k])
+      return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_times: the last time of key %llu is %lld, its state has last_t = %lld; state unchanged",
+                  (unsigned long long)k, (long long)t[off[k + 1] - 1], last[k]);
+  }
+  // into the candidate copy, which then trades places with the current one: any failure leaves the times as they were
+  const int cand = st->cur ^ 1;
+  if (st->ser_tcap[cand] < total) {
+    void *p = nullptr;
+    const hipError_t r = hipMalloc(&p, total * 8);
+    if (r != hipSuccess) { (void)hipGetLastError(); return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_import_times: %s; state unchanged", hipGetErrorString(r)); }
+    if (st->ser_t[cand]) hipFree(st->ser_t[cand]);
+    st->ser_t[cand] = static_cast<long long *>(p);
+    st->ser_tcap[cand] = total;
+  }
+  if (total) HIP_TRY(e, hipMemcpy(st->ser_t[cand], t, total * 8, hipMemcpyHostToDevice));
+  std::swap(st->ser_t[0], st->ser_t[1]);
+  std::swap(st->ser_tcap[0], st->ser_tcap[1]);
+  st->times_stale = false;
+  return TAD_OK;
+}
+
+int tad_state_bytes(tad_engine *eng, const tad_state *st, uint64_t *bytes) {
+  if (!eng || !st || !bytes) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_bytes: bad arguments");
+  std::lock_guard<std::mutex> state_lk(st->mu);
+  const uint64_t off = 2 * (st->K + 1) * 8;   // both copies of a key-offset array
+  uint64_t b = 2 * (uint64_t)state_bytes(st->K);
+  if (st->history) b += off + (st->hist_cap[0] + st->hist_cap[1]) * 8;
+  if (st->series) b += off + (st->ser_cap[0] + st->ser_cap[1]) * 8;
+  if (st->times) b += (st->ser_tcap[0] + st->ser_tcap[1]) * 8;
+  *bytes = b;
+  return TAD_OK;
+}
+
+// tad.h: every key keeps a suffix of its series (kernels in tad_history.hip).  Writes only the candidate copies of the moments, offsets
+// and arenas; they become current together once every launch has succeeded.
+int tad_state_trim(tad_engine *eng, tad_state *st, uint64_t keep_points, int64_t keep_from_t, double ewma_alpha, uint64_t *dropped) {
+  if (dropped) *dropped = 0;
+  if (!eng || !st) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_trim: bad arguments");
+  if (!st->series)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_trim: the state has no series (TAD_STATE_SERIES): a history alone does not know "
+                                               "which values are oldest; state unchanged");
+  if (keep_from_t != 0 && !st->times)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_trim: keep_from_t needs a state with times (TAD_STATE_TIMES); state unchanged");
+  if (!(ewma_alpha >= 0.0 && ewma_alpha <= 1.0)) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_trim: ewma_alpha out of range");
+  std::lock_guard<std::mutex> state_lk(st->mu);   // (the order of tad_run_stream: the state, then a job context)
+  if (st->times_stale)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_trim: the series was imported without its times (tad_state_import_times)");
+  const uint64_t K = st->K;
+  const int cur = st->cur, cand = cur ^ 1;
+  const uint64_t S = st->ser_len[cur];
+  if ((keep_points == 0 && keep_from_t == 0) || S == 0) return TAD_OK;
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_trim: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  const double alpha = ewma_alpha == 0.0 ? 0.5 : ewma_alpha;
+  const size_t kpad = (size_t)((K + 3) & ~3ull);
+  int rc;
+  if ((rc = ensure(e, e->hs_kcnt, kpad * 12 + 64)) != TAD_OK) return rc;        // retained | evicted | chunks (later the long-sort list) | count
+  if ((rc = ensure(e, e->hs_koff, (kpad + 4) * 16)) != TAD_OK) return rc;       // evicted offsets | chunk offsets, K + 1 each
+  if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K) * sizeof(unsigned long long))) != TAD_OK) return rc;
+  uint32_t *rcnt = static_cast<uint32_t *>(e->hs_kcnt.p), *ecnt = rcnt + kpad, *chunks = ecnt + kpad;
+  unsigned int *long_count = reinterpret_cast<unsigned int *>(chunks + kpad);
+  unsigned long long *eoff = static_cast<unsigned long long *>(e->hs_koff.p), *coff = eoff + kpad + 4;
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  // 1. what every key keeps; the candidate series offsets, the packed evicted offsets and the chunk offsets
+  launch_trim_keep(s, K, st->ser_off[cur], keep_from_t != 0 ? st->ser_t[cur] : nullptr, keep_points, (long long)keep_from_t, rcnt, ecnt, chunks);
+  launch_scan(s, rcnt, st->ser_off[cand], K, scratch);
+  launch_scan(s, ecnt, eoff, K, scratch);
+  launch_scan(s, chunks, coff, K, scratch);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipMemcpyAsync(e->tail_host, st->ser_off[cand] + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(e->tail_host + 8, eoff + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  unsigned long long kept = 0, evicted = 0;
+  memcpy(&kept, e->tail_host, 8);
+  memcpy(&evicted, e->tail_host + 8, 8);
+  if (evicted == 0) return TAD_OK;   // nothing to drop: the state stays as it is (the candidate offsets are scratch)
+  // 2. the candidate arenas at their new size, the evicted values' scratch: an allocation failure leaves the state as it is
+  if ((rc = size_trim_arena(e, st->ser_val[cand], st->ser_cap[cand], kept, true)) != TAD_OK) return rc;
+  if (st->times && (rc = size_trim_arena(e, st->ser_t[cand], st->ser_tcap[cand], kept, true)) != TAD_OK) return rc;
+  unsigned long long *ev = nullptr, *es = nullptr;
+  if (st->history) {
+    if ((rc = size_trim_arena(e, st->hist_val[cand], st->hist_cap[cand], kept, true)) != TAD_OK) return rc;
+    if ((rc = ensure(e, e->hs_val, evicted * 8)) != TAD_OK) return rc;
+    if ((rc = ensure(e, e->hs_sorted, evicted * 8)) != TAD_OK) return rc;
+    ev = static_cast<unsigned long long *>(e->hs_val.p);
+    es = static_cast<unsigned long long *>(e->hs_sorted.p);
+  }
+  // 3. the retained suffixes (and the evicted prefixes); 4. the history without the evicted values; 5. the moments
+  const uint64_t bound = trim_chunks_bound(K, S);
+  launch_trim_copy(s, bound, coff, K, st->ser_off[cur], st->ser_val[cur], st->times ? st->ser_t[cur] : nullptr, st->ser_off[cand], st->ser_val[cand],
+                   st->times ? st->ser_t[cand] : nullptr, eoff, ev);
+  if (st->history) {
+    HIP_TRY(e, hipMemcpyAsync(st->hist_off[cand], st->ser_off[cand], (K + 1) * 8, hipMemcpyDeviceToDevice, s));
+    launch_hist_sort(s, ev, eoff, K, es, chunks, long_count);
+    launch_hist_subtract(s, bound, coff, K, st->hist_off[cur], st->hist_val[cur], eoff, es, st->hist_off[cand], st->hist_val[cand]);
+  }
+  launch_trim_moments(s, K, rcnt, ecnt, st->ser_off[cand], st->ser_val[cand], alpha, state_view(st, cur), state_view(st, cand));
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipStreamSynchronize(s));
+  // everything succeeded: the candidate becomes current; the old arenas, now the candidates, are given back when far too big for it
+  st->ser_len[cand] = kept;
+  if (st->history) st->hist_len[cand] = kept;
+  st->cur = cand;
+  (void)size_trim_arena(e, st->ser_val[cur], st->ser_cap[cur], kept, false);
+  if (st->times) (void)size_trim_arena(e, st->ser_t[cur], st->ser_tcap[cur], kept, false);
+  if (st->history) (void)size_trim_arena(e, st->hist_val[cur], st->hist_cap[cur], kept, false);
+  if (dropped) *dropped = evicted;
   return TAD_OK;
 }
 

@@ -142,6 +142,12 @@ struct tad_state {
   unsigned long long *ser_val[2] = {nullptr, nullptr};
   uint64_t ser_cap[2] = {0, 0};
   uint64_t ser_len[2] = {0, 0};
+  // TAD_STATE_TIMES (with a series): every series point's flowEndSeconds, parallel to ser_val (same offsets ser_off[i], same double
+  // buffering; its own capacity).  times_stale: tad_state_import_series replaced the series and tad_state_import_times has not yet
+  // brought the times that go with it — batches, trims and exports of the times are refused until it has.
+  bool times = false, times_stale = false;
+  long long *ser_t[2] = {nullptr, nullptr};
+  uint64_t ser_tcap[2] = {0, 0};
   mutable std::mutex mu;     // batches of one state are serial (tad_run_stream from two threads on one state)
 };
 

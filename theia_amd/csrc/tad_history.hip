@@ -309,6 +309,151 @@ void launch_series_append(hipStream_t s, uint64_t K, const unsigned long long *s
   hipLaunchKernelGGL(k_series_append, dim3(hist_blocks(K * 64)), dim3(kHBlock), 0, s, K, soff_old, sval_old, poff, nv, soff_new, sval_new);
 }
 
+// ---- tad_state_trim: drop every key's oldest points (include/tad.h) ----
+// A series state keeps key k's points in time order at soff[k], times (TAD_STATE_TIMES) alongside, and its history holds the same
+// values sorted; a trim keeps a suffix of every key's series:
+//   1. k_trim_keep, one lane per key: the time cut (lower_bound of keep_from in the key's times), then at most keep_points of the rest.
+//      rcnt[k] = retained, ecnt[k] = evicted, chunks[k] = the key's wavefronts in 2 / 4 (old segment length / kHistChunk).
+//   2. the retained suffix of every key's values (and times) into the candidate arena, the evicted prefix packed for the history
+//      (k_trim_copy, a wavefront per chunk as k_hist_merge: coalesced, and a key of a day of seconds is 43 wavefronts, not one).
+//   3. a history state: the evicted prefixes sorted per key (launch_hist_sort), then
+//   4. k_hist_subtract removes them from the history: one lane per history element, chunked like 2 (a key's history is as long as its
+//      series).  Element h[i] = v with rank r inside its run of equal values and c copies of v among the key's evicted values: kept iff
+//      r >= c, at i - #{evicted < v} - min(r, c).  The cost follows the history plus the evicted points; the retained series is not
+//      re-sorted.
+//   5. k_trim_moments, one lane per key: a key that lost points replays stream_step over its retained values from the zero state (the
+//      fresh state's moments bit for bit: the same inline step, the same order); a key that lost all is unseen; the others are copied.
+__global__ __launch_bounds__(kHBlock) void k_trim_keep(uint64_t K, const unsigned long long *__restrict__ soff, const long long *__restrict__ st,
+                                                      uint64_t keep_points, long long keep_from, uint32_t *__restrict__ rcnt,
+                                                      uint32_t *__restrict__ ecnt, uint32_t *__restrict__ chunks) {
+  const uint64_t k = (uint64_t)blockIdx.x * kHBlock + threadIdx.x;
+  if (k >= K) return;
+  const unsigned long long o0 = soff[k], len = soff[k + 1] - o0;
+  unsigned long long lo = 0;
+  if (st) {   // the first point at or after keep_from (times ascend)
+    unsigned long long hi = len;
+    while (lo < hi) { const unsigned long long mid = lo + ((hi - lo) >> 1); if (st[o0 + mid] < keep_from) lo = mid + 1; else hi = mid; }
+  }
+  unsigned long long r = len - lo;
+  if (keep_points && r > keep_points) r = keep_points;
+  rcnt[k] = (uint32_t)r;
+  ecnt[k] = (uint32_t)(len - r);
+  chunks[k] = (uint32_t)((len + kHistChunk - 1) / kHistChunk);
+}
+
+// the key of wavefront w from the chunk offsets (wavefront-uniform): the last k with coff[k] <= w
+__device__ __forceinline__ uint64_t chunk_key(const unsigned long long *coff, uint64_t K, unsigned long long w) {
+  uint64_t lo = 0, hi = K;
+  while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (coff[mid] <= w) lo = mid; else hi = mid; }
+  return lo;
+}
+
+// One wavefront per chunk of a key's OLD segment: element u < e goes to the packed evicted values (ev at eoff[k], history states only),
+// element u >= e to the candidate series at soff_new[k] + u - e (values, and times when st_old is given).
+__global__ __launch_bounds__(kHBlock) void k_trim_copy(const unsigned long long *__restrict__ coff, uint64_t K,
+                                                      const unsigned long long *__restrict__ soff_old, const unsigned long long *__restrict__ sval_old,
+                                                      const long long *__restrict__ st_old, const unsigned long long *__restrict__ soff_new,
+                                                      unsigned long long *__restrict__ sval_new, long long *__restrict__ st_new,
+                                                      const unsigned long long *__restrict__ eoff, unsigned long long *__restrict__ ev) {
+  const unsigned long long w = ((uint64_t)blockIdx.x * kHBlock + threadIdx.x) >> 6;
+  if (w >= coff[K]) return;
+  const unsigned lane = threadIdx.x & 63u;
+  const uint64_t k = chunk_key(coff, K, w);
+  const unsigned long long o0 = soff_old[k], len = soff_old[k + 1] - o0;
+  const unsigned long long d0 = soff_new[k], e = len - (soff_new[k + 1] - d0);
+  const unsigned long long c0 = (w - coff[k]) * kHistChunk;
+  unsigned long long c1 = c0 + kHistChunk;
+  if (c1 > len) c1 = len;
+  for (unsigned long long u = c0 + lane; u < c1; u += 64) {
+    const unsigned long long x = sval_old[o0 + u];
+    if (u >= e) {
+      sval_new[d0 + u - e] = x;
+      if (st_old) st_new[d0 + u - e] = st_old[o0 + u];
+    } else if (ev) {
+      ev[eoff[k] + u] = x;
+    }
+  }
+}
+
+// One wavefront per chunk of a key's old history (the chunks of its series: the same length); es = the key's evicted values sorted at
+// [eoff[k], eoff[k + 1]); hoff_new = the candidate series offsets (retained history = retained series, key by key).
+__global__ __launch_bounds__(kHBlock) void k_hist_subtract(const unsigned long long *__restrict__ coff, uint64_t K,
+                                                          const unsigned long long *__restrict__ hoff_old, const unsigned long long *__restrict__ hval_old,
+                                                          const unsigned long long *__restrict__ eoff, const unsigned long long *__restrict__ es,
+                                                          const unsigned long long *__restrict__ hoff_new, unsigned long long *__restrict__ hval_new) {
+  const unsigned long long w = ((uint64_t)blockIdx.x * kHBlock + threadIdx.x) >> 6;
+  if (w >= coff[K]) return;
+  const unsigned lane = threadIdx.x & 63u;
+  const uint64_t k = chunk_key(coff, K, w);
+  const unsigned long long o0 = hoff_old[k], len = hoff_old[k + 1] - o0;
+  const unsigned long long e0 = eoff[k], e1 = eoff[k + 1];
+  unsigned long long *dst = hval_new + hoff_new[k];
+  const unsigned long long rlen = hoff_new[k + 1] - hoff_new[k];
+  const unsigned long long c0 = (w - coff[k]) * kHistChunk;
+  unsigned long long c1 = c0 + kHistChunk;
+  if (c1 > len) c1 = len;
+  for (unsigned long long i = c0 + lane; i < c1; i += 64) {
+    const unsigned long long v = hval_old[o0 + i];
+    if (e0 == e1) { dst[i] = v; continue; }   // the key lost nothing: a coalesced copy
+    const unsigned long long r = i - (lower_u64(hval_old, o0, o0 + len, v) - o0);
+    const unsigned long long lt = lower_u64(es, e0, e1, v), c = upper_u64(es, lt, e1, v) - lt;
+    const unsigned long long drop = (lt - e0) + c;   // (min(r, c) = c for a kept element)
+    if (r >= c && i >= drop && i - drop < rlen) dst[i - drop] = v;   // (the bounds hold whenever the evicted values are in the history)
+  }
+}
+
+// One lane per key: the candidate moments.  The retained values are read from the candidate series (written by k_trim_copy);
+// last_t stays: a key that keeps a point keeps its newest one.
+__global__ __launch_bounds__(kHBlock) void k_trim_moments(uint64_t K, const uint32_t *__restrict__ rcnt, const uint32_t *__restrict__ ecnt,
+                                                         const unsigned long long *__restrict__ soff_new, const unsigned long long *__restrict__ sval_new,
+                                                         double alpha, StreamState cur, StreamState next) {
+  const uint64_t k = (uint64_t)blockIdx.x * kHBlock + threadIdx.x;
+  if (k >= K) return;
+  StreamAcc a = stream_load(cur, k);
+  const uint32_t r = rcnt[k];
+  if (ecnt[k] != 0) {
+    const long long last_t = a.last_t;
+    a = StreamAcc{0u, 0.0, 0.0, 0.0, 0.0, 0ll, false};
+    const double one_minus = 1.0 - alpha;
+    const unsigned long long p0 = soff_new[k];
+    for (uint32_t i = 0; i < r; ++i) {
+      double sg;
+      (void)stream_step(a, alpha, one_minus, (double)sval_new[p0 + i], last_t, &sg);
+    }
+  }
+  stream_store(next, k, a);
+}
+
+uint64_t trim_chunks_bound(uint64_t K, uint64_t total_len) { return K + total_len / kHistChunk + 1; }
+
+void launch_trim_keep(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, uint64_t keep_points, long long keep_from,
+                      uint32_t *rcnt, uint32_t *ecnt, uint32_t *chunks) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_trim_keep, dim3(hist_blocks(K)), dim3(kHBlock), 0, s, K, soff, st, keep_points, keep_from, rcnt, ecnt, chunks);
+}
+
+void launch_trim_copy(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *soff_old,
+                      const unsigned long long *sval_old, const long long *st_old, const unsigned long long *soff_new, unsigned long long *sval_new,
+                      long long *st_new, const unsigned long long *eoff, unsigned long long *ev) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_trim_copy, dim3(hist_blocks(chunks_bound * 64)), dim3(kHBlock), 0, s, coff, K, soff_old, sval_old, st_old, soff_new, sval_new,
+                     st_new, eoff, ev);
+}
+
+void launch_hist_subtract(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *hoff_old,
+                          const unsigned long long *hval_old, const unsigned long long *eoff, const unsigned long long *es,
+                          const unsigned long long *hoff_new, unsigned long long *hval_new) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_hist_subtract, dim3(hist_blocks(chunks_bound * 64)), dim3(kHBlock), 0, s, coff, K, hoff_old, hval_old, eoff, es, hoff_new,
+                     hval_new);
+}
+
+void launch_trim_moments(hipStream_t s, uint64_t K, const uint32_t *rcnt, const uint32_t *ecnt, const unsigned long long *soff_new,
+                         const unsigned long long *sval_new, double alpha, StreamState cur, StreamState next) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_trim_moments, dim3(hist_blocks(K)), dim3(kHBlock), 0, s, K, rcnt, ecnt, soff_new, sval_new, alpha, cur, next);
+}
+
 const void *code_anchor_history() { return reinterpret_cast<const void *>(&k_hist_verdict); }
 
 }  // namespace tad

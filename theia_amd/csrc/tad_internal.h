@@ -272,6 +272,40 @@ struct StreamState {
   long long *last_t;
   unsigned char *seen;  // 0 until the key has seen a point
 };
+// one key's running state in registers and the per-point step of the streaming detectors: k_stream, k_stream_points and the moments
+// replay of tad_state_trim (k_trim_moments) share this one source for the arithmetic
+struct StreamAcc {
+  uint32_t n;
+  double cnt, avg, m2, e;
+  long long last_t;
+  bool seen;
+};
+
+__device__ __forceinline__ StreamAcc stream_load(const StreamState &cur, uint64_t k) {
+  const uint32_t n = cur.n[k];
+  return StreamAcc{n, (double)n, cur.avg[k], cur.m2[k], cur.ewma[k], cur.last_t[k], cur.seen[k] != 0};
+}
+
+__device__ __forceinline__ void stream_store(const StreamState &next, uint64_t k, const StreamAcc &a) {
+  next.n[k] = a.n; next.avg[k] = a.avg; next.m2[k] = a.m2; next.ewma[k] = a.e; next.last_t[k] = a.last_t; next.seen[k] = a.seen ? 1 : 0;
+}
+
+// one new point x at ts of one key (ts > last_t checked by the caller): returns the verdict, *sg = the running stddev_samp
+__device__ __forceinline__ bool stream_step(StreamAcc &a, double alpha, double one_minus, double x, long long ts, double *sg) {
+  a.cnt = a.cnt + 1.0;
+  a.n++;
+  const double d = x - a.avg;
+  const double dn = d / a.cnt;
+  a.avg = a.avg + dn;
+  a.m2 = a.m2 + d * (d - dn);
+  a.e = one_minus * a.e + alpha * x;
+  const bool has_sigma = a.n >= 2;
+  *sg = has_sigma ? sqrt(a.m2 / (a.cnt - 1.0)) : 0.0;
+  a.last_t = ts;
+  a.seen = true;
+  return has_sigma && fabs(x - a.e) > *sg;
+}
+
 // emit == false: next = updated state, n_anom[k] = anomalies among the new points (or all new points), late rows flagged;
 // emit == true: rows written from the OLD state `cur` at off[] (next is not touched)
 void launch_stream(hipStream_t s, Grid g, Lattice lat, double alpha, bool all_points, bool emit, StreamState cur, StreamState next,
@@ -361,6 +395,23 @@ bool launch_emit_dbscan_list(hipStream_t s, Grid g, Lattice lat, const void *scr
 // poff[k + 1]), into sval_new
 void launch_series_append(hipStream_t s, uint64_t K, const unsigned long long *soff_old, const unsigned long long *sval_old, const unsigned long long *poff,
                           const unsigned long long *nv, unsigned long long *soff_new, unsigned long long *sval_new);
+// tad_state_trim (tad_history.hip): rcnt / ecnt[k] = the points key k keeps / loses (times st: NULL = no time rule; keep_points 0 = no
+// count rule), chunks[k] = its old segment's wavefronts in the chunked kernels below
+void launch_trim_keep(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, uint64_t keep_points, long long keep_from,
+                      uint32_t *rcnt, uint32_t *ecnt, uint32_t *chunks);
+// upper bound of the chunked kernels' wavefronts for K keys and total_len values
+uint64_t trim_chunks_bound(uint64_t K, uint64_t total_len);
+// the retained suffix of every key's values (and times, st_old != NULL) to soff_new; the evicted prefix packed at eoff (ev != NULL)
+void launch_trim_copy(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *soff_old,
+                      const unsigned long long *sval_old, const long long *st_old, const unsigned long long *soff_new, unsigned long long *sval_new,
+                      long long *st_new, const unsigned long long *eoff, unsigned long long *ev);
+// the history without every key's evicted values (es, sorted per key at eoff)
+void launch_hist_subtract(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *hoff_old,
+                          const unsigned long long *hval_old, const unsigned long long *eoff, const unsigned long long *es,
+                          const unsigned long long *hoff_new, unsigned long long *hval_new);
+// next = cur for the keys that lost nothing; the others replayed with stream_step over their retained values (unseen if none)
+void launch_trim_moments(hipStream_t s, uint64_t K, const uint32_t *rcnt, const uint32_t *ecnt, const unsigned long long *soff_new,
+                         const unsigned long long *sval_new, double alpha, StreamState cur, StreamState next);
 // ---- streaming ARIMA (tad_arima.hip): a batch on a series state, per touched key (slot) and per new point ----
 struct ArimaSlots {
   uint32_t *key;                 // the slot's key

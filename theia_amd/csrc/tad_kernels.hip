@@ -869,37 +869,7 @@ void launch_emit_points(hipStream_t s, Grid g, Lattice lat, const unsigned long 
 // The division stays a division here (n grows without bound, no reciprocal table); it rounds like div_by_count.
 // The per-point step is stream_step, shared with k_stream_points (the sparse batches): one source for the arithmetic.
 // ------------------------------------------------------------------------------------------------
-struct StreamAcc {
-  uint32_t n;
-  double cnt, avg, m2, e;
-  long long last_t;
-  bool seen;
-};
-
-__device__ __forceinline__ StreamAcc stream_load(const StreamState &cur, uint64_t k) {
-  const uint32_t n = cur.n[k];
-  return StreamAcc{n, (double)n, cur.avg[k], cur.m2[k], cur.ewma[k], cur.last_t[k], cur.seen[k] != 0};
-}
-
-__device__ __forceinline__ void stream_store(const StreamState &next, uint64_t k, const StreamAcc &a) {
-  next.n[k] = a.n; next.avg[k] = a.avg; next.m2[k] = a.m2; next.ewma[k] = a.e; next.last_t[k] = a.last_t; next.seen[k] = a.seen ? 1 : 0;
-}
-
-// one new point x at ts of one key (ts > last_t checked by the caller): returns the verdict, *sg = the running stddev_samp
-__device__ __forceinline__ bool stream_step(StreamAcc &a, double alpha, double one_minus, double x, long long ts, double *sg) {
-  a.cnt = a.cnt + 1.0;
-  a.n++;
-  const double d = x - a.avg;
-  const double dn = d / a.cnt;
-  a.avg = a.avg + dn;
-  a.m2 = a.m2 + d * (d - dn);
-  a.e = one_minus * a.e + alpha * x;
-  const bool has_sigma = a.n >= 2;
-  *sg = has_sigma ? sqrt(a.m2 / (a.cnt - 1.0)) : 0.0;
-  a.last_t = ts;
-  a.seen = true;
-  return has_sigma && fabs(x - a.e) > *sg;
-}
+// StreamAcc, stream_load, stream_store and stream_step live in tad_internal.h (tad_state_trim replays the moments with stream_step).
 
 __device__ __forceinline__ void stream_row(OutRows out, unsigned long long pos, uint64_t k, long long ts, double x, double e, double sg,
                                            bool all, bool verdict) {

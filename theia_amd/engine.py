@@ -294,15 +294,22 @@ class TadPoints:
 class TadState:
     """Per-key running state of the streaming detectors (tad_state), resident in HBM.  history=True: the state also keeps every
     aggregated point value it has seen, sorted per key (TAD_STATE_HISTORY), which the streaming DBSCAN detector needs.  series=True:
-    it keeps them in time order (TAD_STATE_SERIES), which the streaming ARIMA detector needs."""
+    it keeps them in time order (TAD_STATE_SERIES), which the streaming ARIMA detector needs.  times=True (with series=True): it keeps
+    every series point's flowEndSeconds too (TAD_STATE_TIMES), so that trim() can cut by time."""
 
-    def __init__(self, engine, num_keys, history=False, series=False):
+    def __init__(self, engine, num_keys, history=False, series=False, times=False):
         self._engine = engine
         self.num_keys = int(num_keys)
         self.history = bool(history)
         self.series = bool(series)
+        self.times = bool(times)
         h = C.c_void_p()
-        if self.history or self.series:
+        if self.times:
+            if not engine._lib.tad_features() & capi.TAD_FEATURE_STREAM_TRIM:
+                raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no state trim (TAD_FEATURE_STREAM_TRIM)")
+            flags = (capi.TAD_STATE_HISTORY if self.history else 0) | (capi.TAD_STATE_SERIES if self.series else 0) | capi.TAD_STATE_TIMES
+            engine._check(engine._lib.tad_state_create_ex(engine._h, self.num_keys, flags, C.byref(h)))
+        elif self.history or self.series:
             if self.history and not engine._lib.tad_features() & capi.TAD_FEATURE_STREAM_DBSCAN:
                 raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no streaming DBSCAN (TAD_FEATURE_STREAM_DBSCAN)")
             if self.series and not engine._lib.tad_features() & capi.TAD_FEATURE_STREAM_ARIMA:
@@ -358,6 +365,35 @@ class TadState:
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "load_series: len has %d entries, the state holds %d keys" % (ln.size, self.num_keys))
         self._engine._check(self._engine._lib.tad_state_import_series(self._engine._h, self._h, ln.ctypes.data,
                                                                       vals.ctypes.data if vals.size else None))
+
+    def export_times(self):
+        """int64[series_points()]: every series point's flowEndSeconds, in the order of export_series() (tad_state_export_times)"""
+        t = np.zeros(self.series_points(), np.int64)
+        self._engine._check(self._engine._lib.tad_state_export_times(self._engine._h, self._h, t.ctypes.data if t.size else None))
+        return t
+
+    def load_times(self, t):
+        """Restore what export_times() returned (tad_state_import_times), after load() and load_series(): every key's times must
+        ascend strictly and end at its last_t."""
+        tt = np.ascontiguousarray(t, dtype=np.int64)
+        if tt.shape != (self.series_points(),):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "load_times: %d times, the series holds %d points" % (tt.size, self.series_points()))
+        self._engine._check(self._engine._lib.tad_state_import_times(self._engine._h, self._h, tt.ctypes.data if tt.size else None))
+
+    def trim(self, keep_points=0, keep_from=0, alpha=0.0):
+        """Drop every key's oldest points (tad_state_trim): keep those with flow_end_s >= keep_from (needs times=True; 0 = no time
+        rule), then at most the newest keep_points (0 = no count rule).  The state becomes that of a fresh state streamed only the
+        retained points with EWMA parameter alpha (0 -> 0.5).  Returns the number of points dropped."""
+        dropped = capi.u64()
+        self._engine._check(self._engine._lib.tad_state_trim(self._engine._h, self._h, int(keep_points), int(keep_from), float(alpha),
+                                                             C.byref(dropped)))
+        return int(dropped.value)
+
+    def nbytes(self):
+        """device bytes the state holds: both moment blocks, the offsets and every arena at its capacity (tad_state_bytes)"""
+        n = capi.u64()
+        self._engine._check(self._engine._lib.tad_state_bytes(self._engine._h, self._h, C.byref(n)))
+        return int(n.value)
 
     def export(self):
         """dict of numpy arrays: n, avg, m2, ewma, last_t (one entry per key)."""
@@ -520,10 +556,11 @@ class TadEngine:
         return self.run(*args, _prepare_only=True, **kw)
 
     # ---- streaming EWMA / DBSCAN: one new batch against the per-key running state ----
-    def state_create(self, num_keys, history=False, series=False):
+    def state_create(self, num_keys, history=False, series=False, times=False):
         """history=True: a state for streaming DBSCAN too (tad_state_create_ex with TAD_STATE_HISTORY); series=True: for streaming
-        ARIMA too (TAD_STATE_SERIES)"""
-        return TadState(self, num_keys, history=history, series=series)
+        ARIMA too (TAD_STATE_SERIES); times=True (with series=True): the series keeps its points' times, for TadState.trim by time
+        (TAD_STATE_TIMES)"""
+        return TadState(self, num_keys, history=history, series=series, times=times)
 
     def run_stream(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, emit_all=False, out="host",
                    alpha=0.0, job_id="", num_keys=None, key_id2=None, algo="EWMA", eps=0.0, min_samples=0, maxiter=0):

@@ -916,6 +916,67 @@ func (s *State) ImportTimes(t []int64) error {
 	return nil
 }
 
+var stateRunOnce sync.Once
+var stateRunOK bool
+
+// hasStateRun: the library knows tad_run_state (tad_features); an older one would not export the call.
+func hasStateRun() bool {
+	stateRunOnce.Do(func() { stateRunOK = C.tad_features()&C.TAD_FEATURE_STATE_RUN != 0 })
+	return stateRunOK
+}
+
+// Run judges every point the state holds against the window as a whole (tad_run_state): the rows are exactly those the batch job
+// returns over the state's points with job.Algo and its detector parameters, computed from the state alone — no flow row is read again.
+// The state must be made by NewStateWithTimes (with history for DBSCAN); it is left unchanged.  job.StartTime / EndTime must be 0: the
+// window is what the state holds, and Trim narrows it.  job.AggFlow is ignored (the points are already aggregated).
+func (s *State) Run(job Job) ([]Row, error) {
+	if !hasStateRun() {
+		return nil, errors.New("tadengine: libtad_mi355x.so has no tad_run_state (TAD_FEATURE_STATE_RUN)")
+	}
+	if !s.series || !s.times {
+		return nil, IllegalArgument{"tadengine: Run needs a state made by NewStateWithTimes"}
+	}
+	if job.Algo == DBSCAN && !s.history {
+		return nil, IllegalArgument{"tadengine: Run with DBSCAN needs a state made by NewStateWithTimes with history"}
+	}
+	var cj C.tad_job
+	cj.algo = C.tad_algo(job.Algo)
+	cj.start_time = C.int64_t(job.StartTime)
+	cj.end_time = C.int64_t(job.EndTime)
+	// the detector parameters (0 = the reference's defaults, as in Run and RunStream)
+	cj.dbscan_eps = C.double(job.DBSCANEps)
+	cj.dbscan_min_samples, cj.arima_maxiter = C.int32_t(job.DBSCANMinSamples), C.int32_t(job.ARIMAMaxIter)
+	id := []byte(job.ID)
+	if len(id) > 63 {
+		id = id[:63]
+	}
+	for i, b := range id {
+		cj.id[i] = C.char(b)
+	}
+	var res *C.tad_result
+	if rc := C.tad_run_state(s.e.h, s.h, &cj, C.TAD_MEM_HOST, &res); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, IllegalArgument{msg}
+		}
+		return nil, fmt.Errorf("tad_run_state: %s (code %d)", msg, int(rc))
+	}
+	defer C.tad_result_free(s.e.h, res)
+	a := int(res.n_rows)
+	rows := make([]Row, a)
+	if a > 0 {
+		k := unsafe.Slice((*uint64)(unsafe.Pointer(res.key_id)), a)
+		t := unsafe.Slice((*int64)(unsafe.Pointer(res.flow_end_s)), a)
+		x := unsafe.Slice((*float64)(unsafe.Pointer(res.throughput)), a)
+		c := unsafe.Slice((*float64)(unsafe.Pointer(res.algo_calc)), a)
+		sd := unsafe.Slice((*float64)(unsafe.Pointer(res.stddev)), a)
+		for i := range rows {
+			rows[i] = Row{k[i], t[i], x[i], c[i], sd[i]}
+		}
+	}
+	return rows, nil
+}
+
 func (e *Engine) NewState(numKeys uint64) (*State, error) {
 	var h *C.tad_state
 	if rc := C.tad_state_create(e.h, C.uint64_t(numKeys), &h); rc != C.TAD_OK {

@@ -75,6 +75,7 @@ typedef enum { TAD_MEM_HOST = 0, TAD_MEM_DEVICE = 1 } tad_mem;
 #define TAD_FEATURE_STREAM_DBSCAN 2u  /* tad_state_create_ex(TAD_STATE_HISTORY) and tad_run_stream with TAD_ALGO_DBSCAN */
 #define TAD_FEATURE_STREAM_ARIMA 4u   /* tad_state_create_ex(TAD_STATE_SERIES) and tad_run_stream with TAD_ALGO_ARIMA */
 #define TAD_FEATURE_STREAM_TRIM 8u    /* TAD_STATE_TIMES, tad_state_trim, tad_state_bytes, tad_state_export_times / import_times */
+#define TAD_FEATURE_STATE_RUN 16u     /* tad_run_state: the batch job's rows over everything a series + times state holds */
 
 typedef struct tad_engine tad_engine; /* opaque; one per GPU; runs up to max_jobs_in_flight jobs concurrently (ABI 12) */
 
@@ -506,6 +507,39 @@ int tad_state_trim(tad_engine *e, tad_state *s, uint64_t keep_points, int64_t ke
 int tad_state_bytes(tad_engine *e, const tad_state *s, uint64_t *bytes);
 int tad_state_export_times(tad_engine *e, const tad_state *s, int64_t *t);
 int tad_state_import_times(tad_engine *e, tad_state *s, const int64_t *t);
+
+/* ---- the window's batch verdicts from the state alone (TAD_FEATURE_STATE_RUN; check tad_features() before calling this) ----
+ * The batch job judges every point of the window against the window as a whole (anomaly_detection.py:647-710).  The stream cannot give
+ * that answer: its EWMA verdicts use the running sigma, and its DBSCAN and ARIMA batches report each point once, when it arrives.  A
+ * state created with TAD_STATE_SERIES | TAD_STATE_TIMES already holds what Stage 0 would produce for the window — every key's aggregated
+ * points in time order with their flowEndSeconds, and moments (n, avg, m2) that are the batch job's bit for bit; with TAD_STATE_HISTORY
+ * each key's values sorted as well — so "stream the batches, trim, ask for the window's verdicts" needs no raw row read twice.
+ * Contract: let W be the table with one row per series point the state holds, (key, flow_end_s, value).  tad_run_state returns exactly
+ * the rows tad_run returns for W with the same algo, detector parameters and TAD_FLAG_EMIT_ALL_POINTS (any value op: a single-row group
+ * aggregates to itself): key_id, flow_end_s, throughput, algo_calc, stddev (and anomaly with the flag), in the same (key, time) order,
+ * bit for bit, whatever Stage-0 path tad_run takes for W.  The state is read only: after the call, successful or not, moments, history,
+ * series and times are unchanged.
+ * What the state must hold (anything else is TAD_ERR_INVALID_ARGUMENT): EWMA and ARIMA need TAD_STATE_SERIES | TAD_STATE_TIMES, DBSCAN
+ * needs TAD_STATE_HISTORY as well; a state whose times are stale (series imported, times not yet) is refused, as a batch is.
+ * Fields of tad_job that are honoured: algo, ewma_alpha, dbscan_eps, dbscan_min_samples, arima_maxiter, flags & TAD_FLAG_EMIT_ALL_POINTS
+ * and id; zero means the default, as in tad_run.  agg_flow and value_op are ignored: the points are already aggregated.  Refused with
+ * TAD_ERR_INVALID_ARGUMENT: start_time or end_time non-zero (the window is what the state holds; narrow it with tad_state_trim),
+ * TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 (there are no input columns), and TAD_ALGO_DROP, which has no streaming form.
+ * The contract rests on the state's invariants — the moments are those of the series, the history is the series' values sorted — which
+ * every batch and every trim keep; an import that breaks them voids the contract.
+ *   - EWMA: stddev = n >= 2 ? sqrt(m2 / (n - 1.0)) : 0.0 from the state's moments; the EWMA value is replayed from 0 over the key's series
+ *     with the job's alpha (the state's stored ewma is not used: it may come from another alpha); verdict n >= 2 && |x - e| > stddev.
+ *   - DBSCAN: every series point is judged against its key's history; algo_calc = 0.0, stddev as above.
+ *   - ARIMA: lambda and Box-Cox over the whole series, every position predicted; keys with no result emit nothing.
+ * tad_stats of the result: rows_in = rows_used = n_points = the series points; n_keys = keys with at least one point; n_anomalies; for
+ * ARIMA keys_no_result, arima_fits, kalman_steps, arima_nan_fits and arima_relaunches as tad_run over W reports them; pts_mean / pts_m2
+ * merged from the per-key moments as tad_run merges them; t0 = the smallest retained time, step = n_buckets = 0; stage0_path =
+ * stage0_attempts = 0 and ms_meta = ms_stage0 = ms_scatter = 0 (no Stage 0 ran); ms_detect, ms_total, job_context.  An empty state gives
+ * TAD_OK with zero rows.  A call costs one walk of the series (two without TAD_FLAG_EMIT_ALL_POINTS for EWMA: count, then emit) plus
+ * the rows; DBSCAN adds the verdicts' binary searches in the history, ARIMA runs the job's fits.
+ * tad_plan.ewma_emit / ewma_emit_rows choose and size its staged EWMA emit as they do tad_run's (tests, A/B measurements).
+ * Lock order: the state, then a job context, as a batch and a trim; calls on one state are serial, tad_job_progress finds the job by id. */
+int tad_run_state(tad_engine *e, tad_state *s, const tad_job *job, tad_mem out_memory, tad_result **out);
 
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).

@@ -25,6 +25,7 @@ TAD_FEATURE_STREAM_ARIMA = 4                 # tad_features() bit: tad_state_cre
 TAD_STATE_SERIES = 2                         # tad_state_create_ex flag: keep every key's aggregated point values (time order)
 TAD_FEATURE_STREAM_TRIM = 8                  # tad_features() bit: TAD_STATE_TIMES, tad_state_trim, tad_state_bytes, export / import of times
 TAD_STATE_TIMES = 8                          # tad_state_create_ex flag (with TAD_STATE_SERIES): keep every series point's flowEndSeconds
+TAD_FEATURE_STATE_RUN = 16                   # tad_features() bit: tad_run_state, the batch job's rows over everything a state holds
 
 
 class Plan(C.Structure):
@@ -136,6 +137,7 @@ SYMBOLS = {
     "tad_state_export_times": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_state_import_times": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_run_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),
+    "tad_run_state": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_aggregate": (C.c_int, [C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Points))]),
     "tad_points_free": (None, [C.c_void_p, C.POINTER(Points)]),
     "tad_shard_rows": (C.c_int, [C.c_void_p, C.POINTER(Columns), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -373,10 +373,11 @@ constexpr uint64_t kStreamFitWaves = 4096;   // k_arima_fit_list: wavefronts a b
 // One ARIMA batch on a series state (tad.h, TAD_STATE_SERIES), after stream_history_batch appended the new points to the candidate series:
 // the touched keys' Box-Cox fits over their whole series, the fits of the new points only, verdicts and the row count (tad_arima.hip).
 // Writes only workspace memory.  A batch whose Stage 0 or stream pass raised an error (a late row) runs no fit: the caller fails it.
-int stream_arima_batch(JobCtx *e, tad_state *st, uint64_t K, const HistBatch &hb, const JobParams &jp, DevCounters *ctr, ArimaBatch *ab) {
+// which: the copy of the series and moments to read — the candidate for a batch; the current one for tad_run_state, whose HistBatch names
+// every series point as new (poff = the series offsets).
+int stream_arima_batch(JobCtx *e, const tad_state *st, int which, uint64_t K, const HistBatch &hb, const JobParams &jp, DevCounters *ctr, ArimaBatch *ab) {
   hipStream_t s = e->stream;
-  const int cand = st->cur ^ 1;
-  const unsigned long long *soff = st->ser_off[cand], *sval = st->ser_val[cand];
+  const unsigned long long *soff = st->ser_off[which], *sval = st->ser_val[which];
   const size_t kpad = (size_t)((K + 3) & ~3ull);
   int rc;
   // per key: touched u32 | len8 u32 | tidx u64[K + 1] | yoffk u64[K + 1] | tmax; per slot: key u32 | lo u32 | hi u32 | ok u8 | yoff u64 | lam | sigma | ibase
@@ -423,7 +424,7 @@ int stream_arima_batch(JobCtx *e, tad_state *st, uint64_t K, const HistBatch &hb
   double *lx = static_cast<double *>(e->as_ser.p), *ysk = lx + ser;
   HIP_TRY(e, hipMemsetAsync(pflag, 0, P, s));
   HIP_TRY(e, hipMemsetAsync(ysk, 0, ser * 8, s));   // (the slack: finite values for idle lanes)
-  launch_as_prep(s, K, soff, sval, hb.poff, state_view(st, cand), tidx, yoffk, lx, ysk, sl, pcalc, pflag, ctr);
+  launch_as_prep(s, K, soff, sval, hb.poff, state_view(st, which), tidx, yoffk, lx, ysk, sl, pcalc, pflag, ctr);
   // the fits: counted per position, listed, their wavefronts laid out on the host (heaviest position first)
   const uint64_t npos = (uint64_t)tmax + 1;
   if ((rc = ensure(e, e->as_pos, npos * (4 + 8) + 128)) != TAD_OK) return rc;   // cnt u32[npos] | (64-byte aligned) loff u64[npos + 1]
@@ -473,6 +474,164 @@ int stream_arima_batch(JobCtx *e, tad_state *st, uint64_t K, const HistBatch &hb
   launch_as_rows(s, P, hb.nk, tidx, sl.ok, pflag, jp.all_points, rows);
   launch_scan(s, rows, row_off, P, scratch, dev_total(e));
   ab->P = P; ab->tidx = tidx; ab->sigma = sl.sigma; ab->pcalc = pcalc; ab->pflag = pflag; ab->rows = rows; ab->row_off = row_off;
+  return TAD_OK;
+}
+
+// tad_run_state on the context the caller holds (tad.h; kernels: tad_window.hip).  Reads the CURRENT copies of the state only.  EWMA walks
+// the CSR series; DBSCAN and ARIMA run the stream's kernels with every series point named as new (poff = the series offsets).
+int run_state_locked(JobCtx *e, const tad_state *st, const tad_job *job, tad_mem out_memory, tad_result **out) {
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  e->done.store(0);
+  e->total.store(4);
+  e->arima_relaunches = 0;
+  JobParams jp;
+  jp.algo = job->algo;
+  jp.alpha = job->ewma_alpha == 0.0 ? 0.5 : job->ewma_alpha;
+  jp.eps = job->dbscan_eps == 0.0 ? 250000000.0 : job->dbscan_eps;
+  jp.min_samples = job->dbscan_min_samples == 0 ? 4 : job->dbscan_min_samples;
+  jp.maxiter = job->arima_maxiter == 0 ? 50 : job->arima_maxiter;
+  jp.drop_nsigma = 3.0;
+  jp.drop_min_samples = 3;
+  jp.all_points = (job->flags & TAD_FLAG_EMIT_ALL_POINTS) != 0;
+  const uint64_t K = st->K;
+  const int cur = st->cur;
+  const uint64_t P = st->ser_len[cur];
+  const unsigned long long *soff = st->ser_off[cur], *sval = st->ser_val[cur];
+  const long long *stt = st->ser_t[cur];
+  const StreamState view = state_view(st, cur);
+  int rc;
+  if ((rc = ensure_key_buffers(e, K)) != TAD_OK) return rc;
+  DevCounters *ctr = static_cast<DevCounters *>(e->counters.p);
+  unsigned long long *tmin_dev = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(e->counters.p) + kTailHistLen);
+  HIP_TRY(e, hipEventRecord(e->ev[0], s));
+  HIP_TRY(e, hipMemsetAsync(e->counters.p, 0, kTailBytes, s));
+  uint64_t rows = 0;
+  HistBatch hist;
+  ArimaBatch ab;
+  const bool ewma = jp.algo == TAD_ALGO_EWMA;
+  unsigned long long coop_min = 0;
+  uint32_t *list = nullptr;
+  unsigned int *lcount = nullptr;
+  const unsigned long long *off = soff;   // EWMA with every point: the row offsets are the series offsets
+  if (P) {
+    const size_t kpad = (size_t)((K + 3) & ~3ull);
+    if ((rc = ensure(e, e->hs_kcnt, kpad * 4 + 64)) != TAD_OK) return rc;   // the long keys' list | its length
+    if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K > P ? K : P) * sizeof(unsigned long long))) != TAD_OK) return rc;
+    list = static_cast<uint32_t *>(e->hs_kcnt.p);
+    lcount = reinterpret_cast<unsigned int *>(list + kpad);
+    unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+    coop_min = win_coop_min(K, P);
+    launch_win_route(s, K, soff, stt, coop_min, list, lcount, tmin_dev);
+    launch_moments(s, K, view.n, view.avg, view.m2, dev_moments(e), ctr);   // (and n_keys / n_points)
+    if (ewma) {
+      if (!jp.all_points) {
+        launch_win_ewma(s, K, soff, sval, stt, view, jp.alpha, coop_min, list, lcount, false, false, static_cast<uint32_t *>(e->n_anom.p), nullptr, OutRows{});
+        launch_scan(s, static_cast<const uint32_t *>(e->n_anom.p), static_cast<unsigned long long *>(e->off.p), K, scratch, dev_total(e));
+        off = static_cast<const unsigned long long *>(e->off.p);
+      }
+    } else {
+      if ((rc = ensure(e, e->hs_key, P * 8)) != TAD_OK) return rc;
+      unsigned long long *nk = static_cast<unsigned long long *>(e->hs_key.p);
+      launch_win_keys(s, K, soff, nk);
+      hist.nk = nk; hist.nv = sval; hist.nt = stt; hist.poff = soff; hist.P_dev = soff + K; hist.P_cap = P;
+      if (jp.algo == TAD_ALGO_DBSCAN) {
+        if ((rc = ensure(e, e->hs_noise, P)) != TAD_OK) return rc;
+        if ((rc = ensure(e, e->hs_cnt, P * 4)) != TAD_OK) return rc;
+        if ((rc = ensure(e, e->hs_row, (P + 1) * 8)) != TAD_OK) return rc;
+        uint8_t *noise = static_cast<uint8_t *>(e->hs_noise.p);
+        uint32_t *cnt = static_cast<uint32_t *>(e->hs_cnt.p);
+        unsigned long long *row = static_cast<unsigned long long *>(e->hs_row.p);
+        launch_hist_verdict(s, nk, sval, hist.P_dev, P, st->hist_off[cur], st->hist_val[cur], jp.eps, jp.min_samples, jp.all_points, noise, cnt);
+        launch_scan(s, cnt, row, P, scratch, dev_total(e));
+        hist.noise = noise; hist.cnt = cnt; hist.row = row;
+      } else if ((rc = stream_arima_batch(e, st, cur, K, hist, jp, ctr, &ab)) != TAD_OK) {
+        return rc;
+      }
+    }
+  }
+  e->done.store(2);
+  HIP_TRY(e, hipMemcpyAsync(e->tail_host, e->counters.p, kTailBytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  rows = (ewma && jp.all_points) ? P : (P ? *e->total_host : 0);
+  const DevCounters c = *e->ctr_host;
+  e->done.store(3);
+
+  ResultPriv *rp = nullptr;
+  OutRows dev_rows{};
+  ResultBlock dev_block;
+  if ((rc = make_result(e, rows, jp.all_points, out_memory, &rp, &dev_rows, &dev_block)) != TAD_OK) return rc;
+  if (rows && ewma)
+    launch_win_ewma(s, K, soff, sval, stt, view, jp.alpha, coop_min, list, lcount, true, jp.all_points, nullptr, off, dev_rows, rows, e->plan.ewma_emit,
+                    e->plan.ewma_emit_rows);
+  else if (rows && jp.algo == TAD_ALGO_DBSCAN)
+    launch_hist_emit(s, hist.nk, hist.nt, hist.nv, hist.P_dev, hist.P_cap, hist.noise, hist.cnt, hist.row, view, jp.all_points, dev_rows);
+  else if (rows)
+    launch_as_emit(s, ab.P, hist.nk, hist.nt, hist.nv, ab.tidx, ab.sigma, ab.pcalc, ab.pflag, ab.rows, ab.row_off, jp.all_points, dev_rows);
+  {
+    const hipError_t er = hipEventRecord(e->ev[4], s);
+    if (er != hipSuccess) {
+      release_block(e, dev_block.base, dev_block.cap);
+      delete rp;
+      return fail(e, TAD_ERR_HIP, "hipEventRecord failed: %s", hipGetErrorString(er));
+    }
+  }
+  if ((rc = finish_result(e, rp, rows, jp.all_points, dev_block, dev_rows)) != TAD_OK) { delete rp; return rc; }
+  hipError_t le = hipStreamSynchronize(s);
+  if (le == hipSuccess) le = hipGetLastError();
+  if (le != hipSuccess) { tad_result_free(e->eng, &rp->pub); return fail(e, TAD_ERR_HIP, "kernel failure: %s", hipGetErrorString(le)); }
+
+  tad_stats &rs = rp->pub.stats;
+  rs.rows_in = rs.rows_used = rs.n_points = P;
+  rs.n_keys = c.n_keys;
+  rs.keys_no_result = c.keys_no_result;
+  rs.kalman_steps = c.kalman_steps;
+  rs.arima_fits = c.arima_fits;
+  rs.arima_nan_fits = c.arima_nan_fits;
+  {
+    unsigned long long tmin = ~0ull;
+    memcpy(&tmin, e->tail_host + kTailHistLen, 8);
+    rs.t0 = (P && tmin != ~0ull) ? (int64_t)(tmin ^ (1ull << 63)) : 0;
+  }
+  {
+    double mn = 0.0, mean = 0.0, m2 = 0.0;   // Chan merge of the block partials, fixed order (as tad_run)
+    if (P)
+      for (int b = 0; b < kMomentBlocks; ++b) {
+        const Moments &p = e->moments_host[b];
+        if (p.n == 0.0) continue;
+        if (mn == 0.0) { mn = p.n; mean = p.mean; m2 = p.m2; continue; }
+        const double nn = mn + p.n, d = p.mean - mean;
+        mean = mean + d * (p.n / nn);
+        m2 = m2 + p.m2 + d * d * (mn * p.n / nn);
+        mn = nn;
+      }
+    rs.pts_mean = mean;
+    rs.pts_m2 = m2;
+  }
+  rs.n_anomalies = rows;
+  if (jp.all_points) {   // the emit kernel wrote the verdicts: counted on the host copy
+    rs.n_anomalies = 0;
+    if (rows) {
+      std::vector<uint8_t> tmp;
+      const uint8_t *a = rp->pub.anomaly;
+      if (out_memory == TAD_MEM_DEVICE) {
+        tmp.resize(rows);
+        const hipError_t cr = hipMemcpy(tmp.data(), rp->pub.anomaly, rows, hipMemcpyDeviceToHost);
+        if (cr != hipSuccess) { tad_result_free(e->eng, &rp->pub); return fail(e, TAD_ERR_HIP, "verdict copy failed: %s", hipGetErrorString(cr)); }
+        a = tmp.data();
+      }
+      for (uint64_t i = 0; i < rows; ++i) rs.n_anomalies += a[i];
+    }
+  }
+  hipEventElapsedTime(&rs.ms_total, e->ev[0], e->ev[4]);
+  rs.ms_detect = rs.ms_total;   // no Stage 0 ran: the whole call is the detector and its emit
+  rs.host_syncs = 2;
+  rs.job_context = e->index;
+  rs.arima_relaunches = e->arima_relaunches;
+  strncpy(rp->pub.id, job->id, sizeof rp->pub.id - 1);
+  e->done.store(4);
+  *out = &rp->pub;
   return TAD_OK;
 }
 
@@ -967,7 +1126,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       if ((stream->history || stream->series) && g.K &&
           (rc = stream_history_batch(e, stream, g, L, stream_poff, stream_P, (slots_all < cells ? slots_all : cells), jp, &hist)) != TAD_OK)
         return rc;
-      if (jp.algo == TAD_ALGO_ARIMA && g.K && (rc = stream_arima_batch(e, stream, g.K, hist, jp, ctr, &ab)) != TAD_OK) return rc;
+      if (jp.algo == TAD_ALGO_ARIMA && g.K && (rc = stream_arima_batch(e, stream, stream->cur ^ 1, g.K, hist, jp, ctr, &ab)) != TAD_OK) return rc;
       if (jp.algo == TAD_ALGO_EWMA)   // (a DBSCAN / ARIMA batch counted its rows in stream_history_batch / stream_arima_batch)
         launch_scan(s, static_cast<const uint32_t *>(e->n_anom.p), off, g.K, static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
       HIP_TRY(e, hipMemcpyAsync(e->tail_host, e->counters.p, kTailBytes, hipMemcpyDeviceToHost, s));
@@ -1890,6 +2049,30 @@ int tad_state_trim(tad_engine *eng, tad_state *st, uint64_t keep_points, int64_t
   if (st->history) (void)size_trim_arena(e, st->hist_val[cur], st->hist_cap[cur], kept, false);
   if (dropped) *dropped = evicted;
   return TAD_OK;
+}
+
+int tad_run_state(tad_engine *eng, tad_state *st, const tad_job *job, tad_mem out_memory, tad_result **out) {
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: engine is NULL");
+  if (!st || !job || !out) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: state, job and out must not be NULL");
+  *out = nullptr;
+  if (job->algo != TAD_ALGO_EWMA && job->algo != TAD_ALGO_DBSCAN && job->algo != TAD_ALGO_ARIMA)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: the algorithm must be EWMA, DBSCAN or ARIMA (DROP has no streaming form)");
+  if (job->start_time != 0 || job->end_time != 0)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: start_time / end_time must be 0: the window is what the state holds (tad_state_trim narrows it)");
+  if (job->flags & (TAD_FLAG_KEY_U32 | TAD_FLAG_TIME_U32))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 describe input columns; there are none");
+  if (job->ewma_alpha < 0.0 || job->ewma_alpha > 1.0 || job->dbscan_eps < 0.0 || job->dbscan_min_samples < 0 || job->arima_maxiter < 0)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: detector parameter out of range");
+  if (!st->series || !st->times)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES)");
+  if (job->algo == TAD_ALGO_DBSCAN && !st->history)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: DBSCAN needs a state with history too (TAD_STATE_HISTORY)");
+  std::lock_guard<std::mutex> state_lk(st->mu);   // (the order of tad_run_stream: the state, then a job context)
+  if (st->times_stale)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: the series was imported without its times (tad_state_import_times)");
+  Lease lease(eng, job->id, job->algo == TAD_ALGO_ARIMA);
+  if (!lease.c) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_run_state: no job context available");
+  return run_state_locked(lease.c, st, job, out_memory, out);
 }
 
 int tad_aggregate(tad_engine *e, const tad_job *job, const tad_columns *cols, tad_mem out_memory, tad_points **out) {

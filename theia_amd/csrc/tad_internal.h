@@ -412,6 +412,20 @@ void launch_hist_subtract(hipStream_t s, uint64_t chunks_bound, const unsigned l
 // next = cur for the keys that lost nothing; the others replayed with stream_step over their retained values (unseen if none)
 void launch_trim_moments(hipStream_t s, uint64_t K, const uint32_t *rcnt, const uint32_t *ecnt, const unsigned long long *soff_new,
                          const unsigned long long *sval_new, double alpha, StreamState cur, StreamState next);
+// ---- tad_run_state (tad_window.hip): the batch verdicts of a state's whole window from its CSR series soff / sval / st ----
+// the shortest series that takes a wavefront of its own, for K keys holding `points` points
+unsigned long long win_coop_min(uint64_t K, uint64_t points);
+// list / *count = the keys with >= coop_min points (list: K entries); *tmin = the smallest time ^ 2^63 (~0: no point)
+void launch_win_route(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, unsigned long long coop_min, uint32_t *list,
+                      unsigned int *count, unsigned long long *tmin);
+// EWMA replayed from 0 over every key's series against the stddev_samp of the state's moments `cur`.  emit == false: n_anom[k] = the key's
+// anomalies; emit == true: the rows (all points, or the anomalies — those staged through LDS and stored coalesced) at off[k]
+void launch_win_ewma(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *sval, const long long *st, StreamState cur,
+                     double alpha, unsigned long long coop_min, const uint32_t *list, const unsigned int *count, bool emit, bool all_points,
+                     uint32_t *n_anom, const unsigned long long *off, OutRows out, uint64_t rows = 0,   // rows: off[K], for the emit
+                     int ewma_emit = 0, uint32_t ewma_emit_rows = 0);   // tad_plan: 1 = the lanes store their rows themselves; LDS rows per wavefront of the staged emit
+// nk[i] = the key of series point i
+void launch_win_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, unsigned long long *nk);
 // ---- streaming ARIMA (tad_arima.hip): a batch on a series state, per touched key (slot) and per new point ----
 struct ArimaSlots {
   uint32_t *key;                 // the slot's key
@@ -610,5 +624,6 @@ const void *code_anchor_shard();
 const void *code_anchor_sparse();
 const void *code_anchor_stage0_part();
 const void *code_anchor_synth();
+const void *code_anchor_window();
 
 }  // namespace tad

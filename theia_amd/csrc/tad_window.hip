@@ -1,0 +1,342 @@
+// tad_window.hip — the batch verdicts of a streaming state's whole window, computed from the state alone (include/tad.h: tad_run_state).
+//
+// A state with a series and times holds what Stage 0 would produce for the window: ser_off[K + 1], ser_val[] and ser_t[] are every
+// key's aggregated points in time order (CSR, key-major), the moments (n, avg, m2) are the batch job's bit for bit.  The grid kernels
+// of tad_kernels.hip walk a time-major grid and do not apply; these walk the CSR arrays:
+//   k_win_route      the keys long enough for a wavefront of their own, listed (ballot-compacted: one atomic per wavefront), and the
+//                    smallest retained time (tad_stats.t0);
+//   k_win_ewma       one lane per key: the EWMA recurrence replayed from 0 over the key's segment, verdict against the stddev_samp of
+//                    the WHOLE series (from the state's moments, k_key_sigma's final expression).  Every lane prefetches its next two
+//                    chunks of kWinChunk points into registers before it consumes one, so a wavefront keeps 64 x 2 x 64 B of its own
+//                    segments in flight instead of one point per lane (k_stream_points: one exposed round trip per point);
+//   k_win_emit_staged  the emit pass of k_win_ewma for anomalous rows only, with COALESCED row stores (k_emit_staged's scheme on the CSR
+//                    series): one wavefront = 64 consecutive keys, whose rows are ONE contiguous range [off[k0], off[k0 + 64]) of every
+//                    output column.  During the walk a lane parks (e_t, point, lane) of each anomalous point in LDS at its row's place
+//                    inside that range (13 B a row); afterwards the wavefront writes the range row by row, five coalesced stores per 64
+//                    rows, value and time re-read from the series (an L2 / MALL hit: the wavefront has just walked it).  Rows past the
+//                    LDS capacity are stored directly, as k_win_ewma does, so any capacity is correct;
+//   k_win_ewma_coop  one wavefront per listed key (walk_series_coop's scheme on a contiguous segment): lane l loads point 64 c + l,
+//                    three blocks in flight, all lanes step on readlane broadcasts; lane u keeps the EWMA value and verdict of point
+//                    u, so the rows of a block are written by their own lanes, coalesced;
+//   k_win_keys       the key of every series point (what launch_hist_verdict / launch_hist_emit / launch_as_emit index by).
+// The count pass (EMIT = false) leaves n_anom[k]; the emit pass replays and writes rows at off[k].  With TAD_FLAG_EMIT_ALL_POINTS the
+// row offsets are ser_off itself and the count pass is skipped.  The recurrence is the sequential one of k_key_sigma / k_emit —
+// e = one_minus * e + alpha * x, x = (double)value, in time order — so the bits are theirs.
+#include <stdint.h>
+
+#include "tad_internal.h"
+
+namespace tad {
+
+static constexpr int kWBlock = 256;
+static constexpr int kWinChunk = 8;   // points per lane and prefetch (64 B of values)
+
+__device__ __forceinline__ double win_sigma(const StreamState &cur, uint64_t k, bool *has_sigma) {
+  const uint32_t n = cur.n[k];
+  *has_sigma = n >= 2;
+  return n >= 2 ? sqrt(cur.m2[k] / ((double)n - 1.0)) : 0.0;   // k_key_sigma: sqrt(m2 / (cnt - 1.0))
+}
+
+__device__ __forceinline__ void win_row(OutRows out, unsigned long long at, uint64_t k, long long ts, double x, double e, double sg, bool all,
+                                        bool verdict) {
+  out.key_id[at] = k;
+  out.flow_end_s[at] = ts;
+  out.throughput[at] = x;
+  out.algo_calc[at] = e;
+  out.stddev[at] = sg;
+  if (all) out.anomaly[at] = verdict ? 1 : 0;
+}
+
+// tmin: the smallest first time of a non-empty key, biased by 2^63 so that the unsigned minimum is the signed one (~0 = no point)
+__global__ __launch_bounds__(kWBlock) void k_win_route(uint64_t K, const unsigned long long *__restrict__ soff, const long long *__restrict__ st,
+                                                      unsigned long long coop_min, uint32_t *__restrict__ list, unsigned int *__restrict__ count,
+                                                      unsigned long long *__restrict__ tmin) {
+  const uint64_t k = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
+  const unsigned lane = threadIdx.x & 63u;
+  unsigned long long p0 = 0, len = 0;
+  if (k < K) { p0 = soff[k]; len = soff[k + 1] - p0; }
+  const bool is_long = len >= coop_min;
+  const unsigned long long m = __ballot(is_long);
+  if (m) {
+    const int first = __ffsll((long long)m) - 1;
+    unsigned int base = 0;
+    if ((int)lane == first) base = atomicAdd(count, (unsigned int)__popcll(m));
+    base = (unsigned int)__shfl((int)base, first);
+    if (is_long) list[base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)k;
+  }
+  unsigned long long t = len ? ((unsigned long long)st[p0] ^ (1ull << 63)) : ~0ull;
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long o = __shfl_xor(t, d);
+    t = o < t ? o : t;
+  }
+  if (lane == 0 && t != ~0ull) atomicMin(tmin, t);
+}
+
+template <bool EMIT, bool ALL>
+__global__ __launch_bounds__(kWBlock) void k_win_ewma(uint64_t K, const unsigned long long *__restrict__ soff, const unsigned long long *__restrict__ sval,
+                                                     const long long *__restrict__ st, StreamState cur, double alpha, unsigned long long coop_min,
+                                                     uint32_t *__restrict__ n_anom, const unsigned long long *__restrict__ off, OutRows out) {
+  const uint64_t k = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
+  if (k >= K) return;
+  const unsigned long long p0 = soff[k], len = soff[k + 1] - p0;
+  if (len >= coop_min) return;   // k_win_ewma_coop's
+  if (len == 0) {
+    if (!EMIT) n_anom[k] = 0;
+    return;
+  }
+  bool has_sigma;
+  const double sg = win_sigma(cur, k, &has_sigma);
+  const double one_minus = 1.0 - alpha;
+  double e = 0.0;
+  uint32_t a = 0;
+  unsigned long long pos = EMIT ? off[k] : 0ull;
+  const unsigned long long nch = (len + kWinChunk - 1) / kWinChunk;
+  unsigned long long va[kWinChunk], vb[kWinChunk];
+  long long ta[kWinChunk], tb[kWinChunk];
+  // chunk c of the lane's segment; an index past the end re-reads the last point (in bounds, the load count stays fixed)
+  auto load = [&](unsigned long long c, unsigned long long *v, long long *t) {
+#pragma unroll
+    for (int u = 0; u < kWinChunk; ++u) {
+      const unsigned long long i = c * kWinChunk + u;
+      const unsigned long long at = p0 + (i < len ? i : len - 1);
+      v[u] = sval[at];
+      if (EMIT) t[u] = st[at];
+    }
+  };
+  auto consume = [&](unsigned long long c, const unsigned long long *v, const long long *t) {
+#pragma unroll
+    for (int u = 0; u < kWinChunk; ++u) {
+      if (c * kWinChunk + u >= len) break;
+      const double x = (double)v[u];
+      e = one_minus * e + alpha * x;
+      const bool verdict = has_sigma && fabs(x - e) > sg;
+      if (ALL || verdict) {
+        if (EMIT) win_row(out, pos++, k, t[u], x, e, sg, ALL, verdict);
+        a++;
+      }
+    }
+  };
+  load(0, va, ta);
+  for (unsigned long long c = 0; c < nch; c += 2) {
+    load(c + 1 < nch ? c + 1 : c, vb, tb);
+    consume(c, va, ta);
+    load(c + 2 < nch ? c + 2 : nch - 1, va, ta);
+    if (c + 1 < nch) consume(c + 1, vb, tb);
+  }
+  if (!EMIT) n_anom[k] = a;
+}
+
+// The emit pass for anomalous rows, staged through LDS (see the head of this file).  One workgroup = one wavefront = 64 consecutive keys.
+// Rows of keys that k_win_ewma_coop owns lie inside the wavefront's range too: their places keep the "nobody parked here" mark and are
+// skipped by the flush.
+static constexpr uint32_t kWinNoLane = 0xFFu;
+__global__ __launch_bounds__(64) void k_win_emit_staged(uint64_t K, const unsigned long long *__restrict__ soff, const unsigned long long *__restrict__ sval,
+                                                        const long long *__restrict__ st, StreamState cur, double alpha, unsigned long long coop_min,
+                                                        const unsigned long long *__restrict__ off, OutRows out, uint32_t cap) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_win[];
+  double *s_e = reinterpret_cast<double *>(smem_win);                  // [cap]
+  double *s_sg = s_e + cap;                                            // [64]
+  uint32_t *s_p = reinterpret_cast<uint32_t *>(s_sg + 64);             // [cap] the point, relative to the wavefront's first
+  uint8_t *s_l = reinterpret_cast<uint8_t *>(s_p + cap);               // [cap] the lane that parked the row
+  const uint32_t lane = threadIdx.x;
+  const uint64_t k0 = (uint64_t)blockIdx.x * 64;
+  const uint64_t k = k0 + lane;
+  const uint64_t kend = k0 + 64 < K ? k0 + 64 : K;
+  const unsigned long long base = off[k0];
+  const unsigned long long total = off[kend] - base;
+  if (total == 0) return;   // uniform over the wavefront
+  const bool live = k < K;
+  const unsigned long long pbase = soff[k0];
+  const unsigned long long p0 = live ? soff[k] : 0ull;
+  unsigned long long len = live ? soff[k + 1] - p0 : 0ull;
+  if (len >= coop_min) len = 0;   // k_win_ewma_coop's
+  unsigned long long pos = live ? off[k] - base : 0ull;
+  const unsigned long long end = live ? off[k + 1] - base : 0ull;
+  bool has_sigma = false;
+  const double sg = len ? win_sigma(cur, k, &has_sigma) : 0.0;
+  s_sg[lane] = sg;
+  const uint32_t mycap = soff[kend] - pbase < (1ull << 32) ? cap : 0u;   // (the relative point index is 32 bits wide)
+  const unsigned long long staged = total < mycap ? total : mycap;
+  for (unsigned long long r = lane; r < staged; r += 64) s_l[r] = (uint8_t)kWinNoLane;
+  __syncthreads();
+  if (len != 0 && pos != end) {   // (rows imply a defined sigma: the count pass counts nothing otherwise)
+    const double one_minus = 1.0 - alpha;
+    double e = 0.0;
+    const unsigned long long nch = (len + kWinChunk - 1) / kWinChunk;
+    unsigned long long va[kWinChunk], vb[kWinChunk];
+    auto load = [&](unsigned long long c, unsigned long long *v) {
+#pragma unroll
+      for (int u = 0; u < kWinChunk; ++u) {
+        const unsigned long long i = c * kWinChunk + u;
+        v[u] = sval[p0 + (i < len ? i : len - 1)];
+      }
+    };
+    auto consume = [&](unsigned long long c, const unsigned long long *v) {
+#pragma unroll
+      for (int u = 0; u < kWinChunk; ++u) {
+        const unsigned long long i = c * kWinChunk + u;
+        if (i >= len) break;
+        const double x = (double)v[u];
+        e = one_minus * e + alpha * x;
+        if (has_sigma && fabs(x - e) > sg && pos < end) {
+          if (pos < staged) {
+            s_e[pos] = e;
+            s_p[pos] = (uint32_t)(p0 + i - pbase);
+            s_l[pos] = (uint8_t)lane;
+          } else {
+            win_row(out, base + pos, k, st[p0 + i], x, e, sg, false, true);
+          }
+          pos++;
+        }
+      }
+    };
+    load(0, va);
+    for (unsigned long long c = 0; c < nch; c += 2) {
+      load(c + 1 < nch ? c + 1 : c, vb);
+      consume(c, va);
+      load(c + 2 < nch ? c + 2 : nch - 1, va);
+      if (c + 1 < nch) consume(c + 1, vb);
+    }
+  }
+  __syncthreads();
+  for (unsigned long long r = lane; r < staged; r += 64) {
+    const uint32_t ln = s_l[r];
+    if (ln == kWinNoLane) continue;
+    const unsigned long long p = pbase + s_p[r];
+    const unsigned long long at = base + r;
+    out.key_id[at] = k0 + ln;
+    out.flow_end_s[at] = st[p];
+    out.throughput[at] = (double)sval[p];
+    out.algo_calc[at] = s_e[r];
+    out.stddev[at] = s_sg[ln];
+  }
+}
+
+// One wavefront per listed key, grid-stride over the list.
+template <bool EMIT, bool ALL>
+__global__ __launch_bounds__(kWBlock) void k_win_ewma_coop(const uint32_t *__restrict__ list, const unsigned int *__restrict__ count,
+                                                          const unsigned long long *__restrict__ soff, const unsigned long long *__restrict__ sval,
+                                                          const long long *__restrict__ st, StreamState cur, double alpha,
+                                                          uint32_t *__restrict__ n_anom, const unsigned long long *__restrict__ off, OutRows out) {
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned wave = (blockIdx.x * kWBlock + threadIdx.x) >> 6, nwaves = gridDim.x * (kWBlock / 64);
+  const unsigned total = *count;
+  for (unsigned ent = wave; ent < total; ent += nwaves) {   // wavefront-uniform
+    const uint64_t k = list[ent];
+    const unsigned long long p0 = soff[k], len = soff[k + 1] - p0;
+    const unsigned long long nblk = (len + 63) / 64;
+    bool has_sigma;
+    const double sg = win_sigma(cur, k, &has_sigma);
+    const double one_minus = 1.0 - alpha;
+    double e = 0.0;
+    uint32_t a = 0;
+    unsigned long long pos = EMIT ? off[k] : 0ull;
+    auto load = [&](unsigned long long c, unsigned long long &v, long long &t) {
+      const unsigned long long i = c * 64 + lane;
+      const bool in = c < nblk && i < len;
+      v = in ? sval[p0 + i] : 0ull;
+      t = (EMIT && in) ? st[p0 + i] : 0ll;
+    };
+    unsigned long long v0, v1, v2;
+    long long t0, t1, t2;
+    load(0, v0, t0);
+    load(1, v1, t1);
+    for (unsigned long long c = 0; c < nblk; ++c) {
+      load(c + 2, v2, t2);
+      const unsigned long long left = len - c * 64;
+      const int cnt = __builtin_amdgcn_readfirstlane((int)(left < 64 ? left : 64));   // points of this block (scalar)
+      const double x0 = (double)v0;   // every lane converts its own point
+      double my_e = 0.0;
+      bool my_verdict = false;
+      for (int u = 0; u < cnt; ++u) {
+        const double x = readlane_f64(x0, u);
+        e = one_minus * e + alpha * x;
+        const bool verdict = has_sigma && fabs(x - e) > sg;
+        if ((int)lane == u) { my_e = e; my_verdict = verdict; }
+      }
+      const unsigned long long m = __ballot(ALL ? (int)lane < cnt : my_verdict);
+      if (EMIT && ((m >> lane) & 1ull))
+        win_row(out, pos + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull)), k, t0, x0, my_e, sg, ALL, my_verdict);
+      pos += (unsigned long long)__popcll(m);
+      a += (uint32_t)__popcll(m);
+      v0 = v1; t0 = t1;
+      v1 = v2; t1 = t2;
+    }
+    if (!EMIT && lane == 0) n_anom[k] = a;
+  }
+}
+
+// One wavefront per key: nk[i] = k for the key's points, coalesced.
+__global__ __launch_bounds__(kWBlock) void k_win_keys(uint64_t K, const unsigned long long *__restrict__ soff, unsigned long long *__restrict__ nk) {
+  const uint64_t k = ((uint64_t)blockIdx.x * kWBlock + threadIdx.x) >> 6;   // wavefront-uniform
+  if (k >= K) return;
+  const unsigned long long p1 = soff[k + 1];
+  for (unsigned long long i = soff[k] + (threadIdx.x & 63u); i < p1; i += 64) nk[i] = k;
+}
+
+// ---- launchers ----
+static inline unsigned win_blocks(uint64_t lanes) { return (unsigned)((lanes + kWBlock - 1) / kWBlock); }
+
+// A key takes a wavefront of its own when it is long (>= kCoopMinT points, the grid's rule) and a lane would be the tail of the launch:
+// either there are few keys anyway (<= kCoopMaxK: the chip is not full of lanes) or the key is eight times the average length.  A
+// wavefront per key costs 64 lanes of arithmetic for one key's recurrence, so a window of many equally long keys stays on lanes.
+unsigned long long win_coop_min(uint64_t K, uint64_t points) {
+  if (K <= kCoopMaxK) return kCoopMinT;
+  const unsigned long long outlier = 8 * (points / K + 1);
+  return outlier > kCoopMinT ? outlier : kCoopMinT;
+}
+
+void launch_win_route(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, unsigned long long coop_min, uint32_t *list,
+                      unsigned int *count, unsigned long long *tmin) {
+  hipMemsetAsync(count, 0, sizeof(unsigned int), s);
+  hipMemsetAsync(tmin, 0xFF, sizeof(unsigned long long), s);
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_win_route, dim3(win_blocks(K)), dim3(kWBlock), 0, s, K, soff, st, coop_min, list, count, tmin);
+}
+
+// LDS rows per wavefront of the staged emit (emit_stage_rows' rule in tad_kernels.hip): the mean row count of a 64-key range plus 1/8
+// plus 128 rows, at most 4096 (52 KB: three wavefronts a CU).  tad_plan: ewma_emit = 1 -> k_win_ewma writes the rows itself;
+// ewma_emit_rows pins the capacity (tests).
+static uint32_t win_stage_rows(uint64_t K, uint64_t rows, int ewma_emit, uint32_t ewma_emit_rows) {
+  if (ewma_emit == 1) return 0;
+  const uint64_t mean = (rows * 64 + K - 1) / K;
+  uint64_t cap = mean + mean / 8 + 128;
+  if (ewma_emit_rows != 0) cap = ewma_emit_rows;
+  cap = (cap + 63) & ~63ull;
+  if (cap < 64) cap = 64;
+  if (cap > 4096) cap = 4096;
+  return (uint32_t)cap;
+}
+
+void launch_win_ewma(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *sval, const long long *st, StreamState cur,
+                     double alpha, unsigned long long coop_min, const uint32_t *list, const unsigned int *count, bool emit, bool all_points,
+                     uint32_t *n_anom, const unsigned long long *off, OutRows out, uint64_t rows, int ewma_emit, uint32_t ewma_emit_rows) {
+  if (K == 0) return;
+  const unsigned cwaves = (unsigned)(K < 8192 ? K : 8192);   // wavefronts that stride over the list of long keys
+#define TAD_WIN_COOP(E, A)                                                                                                                     \
+  hipLaunchKernelGGL((k_win_ewma_coop<E, A>), dim3(win_blocks((uint64_t)cwaves * 64)), dim3(kWBlock), 0, s, list, count, soff, sval, st, cur, \
+                     alpha, n_anom, off, out)
+#define TAD_WIN(E, A)                                                                                                                              \
+  do {                                                                                                                                             \
+    hipLaunchKernelGGL((k_win_ewma<E, A>), dim3(win_blocks(K)), dim3(kWBlock), 0, s, K, soff, sval, st, cur, alpha, coop_min, n_anom, off, out);   \
+    TAD_WIN_COOP(E, A);                                                                                                                            \
+  } while (0)
+  if (!emit) TAD_WIN(false, false);
+  else if (all_points) TAD_WIN(true, true);
+  else if (const uint32_t cap = win_stage_rows(K, rows, ewma_emit, ewma_emit_rows)) {
+    hipLaunchKernelGGL(k_win_emit_staged, dim3((unsigned)((K + 63) / 64)), dim3(64), (size_t)cap * 13 + 64 * 8, s, K, soff, sval, st, cur, alpha, coop_min,
+                       off, out, cap);
+    TAD_WIN_COOP(true, false);
+  } else TAD_WIN(true, false);
+#undef TAD_WIN
+#undef TAD_WIN_COOP
+}
+
+void launch_win_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, unsigned long long *nk) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_win_keys, dim3(win_blocks(K * 64)), dim3(kWBlock), 0, s, K, soff, nk);
+}
+
+const void *code_anchor_window() { return reinterpret_cast<const void *>(&k_win_route); }
+
+}  // namespace tad

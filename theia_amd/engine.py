@@ -590,6 +590,22 @@ class TadEngine:
         self._check(rc)
         return TadResult(self, res)
 
+    def run_state(self, state, algo="EWMA", alpha=0.0, eps=0.0, min_samples=0, maxiter=0, emit_all=False, out="host", job_id=""):
+        """The batch job's verdicts over everything `state` holds, from the state alone (tad_run_state): exactly the rows run() returns
+        for the table of the state's series points with the same algo and parameters.  Needs a state with series=True and times=True
+        (and history=True for DBSCAN); the state is left unchanged.  Narrow the window with TadState.trim first."""
+        if algo not in capi.TAD_ALGO:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "algo must be EWMA, ARIMA, DBSCAN or DROP")
+        if not self._lib.tad_features() & capi.TAD_FEATURE_STATE_RUN:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_run_state (TAD_FEATURE_STATE_RUN)")
+        job = capi.Job(algo=capi.TAD_ALGO[algo], ewma_alpha=float(alpha), dbscan_eps=float(eps), dbscan_min_samples=int(min_samples),
+                       arima_maxiter=int(maxiter), flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
+        res = C.POINTER(capi.Result)()
+        rc = self._lib.tad_run_state(self._h, state._h, C.byref(job), capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST,
+                                     C.byref(res))
+        self._check(rc)
+        return TadResult(self, res)
+
     # ---- row-sharded ingest: bucket device rows by owner = key mod world (tad_shard_rows) ----
     def shard_rows(self, key_id, flow_end_s, value, world):
         """Device columns (torch CUDA tensors or DeviceArray) -> ((key_local, flow_end_s, value) DeviceArrays grouped by

@@ -977,6 +977,82 @@ func (s *State) Run(job Job) ([]Row, error) {
 	return rows, nil
 }
 
+var stateMergeOnce sync.Once
+var stateMergeOK bool
+
+// hasStateMerge: the library knows tad_state_merge (tad_features); an older one would not export the call.
+func hasStateMerge() bool {
+	stateMergeOnce.Do(func() { stateMergeOK = C.tad_features()&C.TAD_FEATURE_STATE_MERGE != 0 })
+	return stateMergeOK
+}
+
+// MergeStats is what one Merge did with the batch's points (tad_merge_stats).
+type MergeStats struct {
+	RowsIn, RowsUsed uint64
+	BatchPoints      uint64 // distinct (key, flowEndSeconds) points of the batch
+	PointsTooOld     uint64 // older than keepFrom: dropped
+	PointsAppended   uint64 // newer than everything their key held
+	PointsInserted   uint64 // a new time before the key's last one
+	PointsCombined   uint64 // a time the key already held: value = op(old, new)
+	KeysTouched      uint64
+	KeysReplayed     uint64 // keys whose moments were replayed from the zero state
+	MsTotal          float32
+}
+
+// Merge places ONE batch by time into the state (tad_state_merge): late rows, re-sent rows and rows of a (key, flowEndSeconds) group split
+// over batches, which RunStream refuses.  Afterwards the state is the one a fresh state holds after one RunStream EWMA batch over its
+// window's points plus this batch (without the points older than keepFrom, when that is not 0).  The state must be made by
+// NewStateWithTimes; a poller streams its in-order batches with RunStream, merges whatever trails in, trims, and asks Run for the window's
+// verdicts.  No rows are returned.  The value op follows job.AggFlow as in RunStream: keep it the same for every batch of a state.
+func (s *State) Merge(job Job, cols Columns, keepFrom int64) (MergeStats, error) {
+	if !hasStateMerge() {
+		return MergeStats{}, errors.New("tadengine: libtad_mi355x.so has no tad_state_merge (TAD_FEATURE_STATE_MERGE)")
+	}
+	if !s.series || !s.times {
+		return MergeStats{}, IllegalArgument{"tadengine: Merge needs a state made by NewStateWithTimes"}
+	}
+	bufs, n, narrow, err := columnBuffers(cols)
+	if err != nil {
+		return MergeStats{}, err
+	}
+	defer freeBuffers(bufs)
+	var cj C.tad_job
+	cj.flags = narrow
+	cj.algo = C.TAD_ALGO_EWMA
+	cj.agg_flow = C.tad_agg_flow(job.AggFlow)
+	cj.value_op = C.TAD_OP_AUTO
+	cj.start_time = C.int64_t(job.StartTime)
+	cj.end_time = C.int64_t(job.EndTime)
+	id := []byte(job.ID)
+	if len(id) > 63 {
+		id = id[:63]
+	}
+	for i, b := range id {
+		cj.id[i] = C.char(b)
+	}
+	var cc C.tad_columns
+	cc.n_rows = C.uint64_t(n)
+	cc.num_keys = C.uint64_t(cols.NumKeys)
+	cc.memory = C.TAD_MEM_HOST
+	cc.key_id = (*C.uint64_t)(bufs[0])
+	cc.key_id2 = (*C.uint64_t)(bufs[1])
+	cc.flow_end_s = (*C.int64_t)(bufs[2])
+	cc.flow_start_s = (*C.int64_t)(bufs[3])
+	cc.value = (*C.uint64_t)(bufs[4])
+	var ms C.tad_merge_stats
+	if rc := C.tad_state_merge(s.e.h, s.h, &cj, &cc, C.int64_t(keepFrom), &ms); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return MergeStats{}, IllegalArgument{msg}
+		}
+		return MergeStats{}, fmt.Errorf("tad_state_merge: %s (code %d)", msg, int(rc))
+	}
+	return MergeStats{RowsIn: uint64(ms.rows_in), RowsUsed: uint64(ms.rows_used), BatchPoints: uint64(ms.batch_points),
+		PointsTooOld: uint64(ms.points_too_old), PointsAppended: uint64(ms.points_appended), PointsInserted: uint64(ms.points_inserted),
+		PointsCombined: uint64(ms.points_combined), KeysTouched: uint64(ms.keys_touched), KeysReplayed: uint64(ms.keys_replayed),
+		MsTotal: float32(ms.ms_total)}, nil
+}
+
 func (e *Engine) NewState(numKeys uint64) (*State, error) {
 	var h *C.tad_state
 	if rc := C.tad_state_create(e.h, C.uint64_t(numKeys), &h); rc != C.TAD_OK {

@@ -502,7 +502,8 @@ int tad_state_import_series(tad_engine *e, tad_state *s, const uint64_t *len, co
  * tad_state_export_series.  Import after tad_state_import and tad_state_import_series (which leaves a times state refusing batches,
  * trims and exports of the times until its times are imported): TAD_ERR_INVALID_ARGUMENT with the state unchanged unless the state has
  * times, every key's times ascend strictly and every non-empty key's last time equals its last_t.
- * tad_state_bytes: the device bytes the state holds — both moment blocks, the offsets and every arena at its capacity. */
+ * tad_state_bytes: the device bytes the state holds — both moment blocks, the offsets and every arena at its capacity (the state's own
+ * memory only: the job contexts' workspace, such as the history scratch arena of tad_state_merge below, is not in it). */
 int tad_state_trim(tad_engine *e, tad_state *s, uint64_t keep_points, int64_t keep_from_t, double ewma_alpha, uint64_t *dropped);
 int tad_state_bytes(tad_engine *e, const tad_state *s, uint64_t *bytes);
 int tad_state_export_times(tad_engine *e, const tad_state *s, int64_t *t);
@@ -540,6 +541,72 @@ int tad_state_import_times(tad_engine *e, tad_state *s, const int64_t *t);
  * tad_plan.ewma_emit / ewma_emit_rows choose and size its staged EWMA emit as they do tad_run's (tests, A/B measurements).
  * Lock order: the state, then a job context, as a batch and a trim; calls on one state are serial, tad_job_progress finds the job by id. */
 int tad_run_state(tad_engine *e, tad_state *s, const tad_job *job, tad_mem out_memory, tad_result **out);
+
+/* ---- a batch placed by time: late rows, re-sent rows, rows of a group split over batches (TAD_FEATURE_STATE_MERGE; check tad_features()
+ * before calling this) ----
+ * tad_run_stream appends: one row not newer than its key's last flowEndSeconds fails the whole batch.  Flow records do not arrive in that
+ * order (the flows table is ordered and expired by timeInserted, the exporters lag by node), and the only remedy was to rebuild the state
+ * from the window's raw rows.  A state created with TAD_STATE_SERIES | TAD_STATE_TIMES holds what it needs to repair itself: every key's
+ * aggregated points in time order with their flowEndSeconds; Stage 0's operators (sum mod 2^64, unsigned max) are associative and
+ * commutative.  tad_state_merge aggregates the batch with Stage 0 exactly as a stream batch does and places its points BY TIME.
+ * Contract: let W be the table with one row per series point the state holds, (key, flow_end_s, value) — tad_run_state's W — and B the
+ * batch's rows after the job's filters, without the points whose flow_end_s < keep_from_t when keep_from_t != 0.  After a successful call
+ * the state — n, avg, m2, ewma, last_t, series, times, and the history if it has one — is bit for bit the state a fresh state of the same
+ * flags and num_keys holds after ONE tad_run_stream EWMA batch over the rows W ++ B with the job's value op and ewma_alpha (0 -> 0.5).
+ * Consequences:
+ *   - cut a table into batches anyhow, in any row order, and feed every batch through tad_state_merge with the same value op: the state
+ *     is the one a single batch over the whole table leaves, so tad_run_state afterwards returns exactly tad_run over the whole table
+ *     (rows, order, bits) for EWMA, DBSCAN (history states) and ARIMA;
+ *   - a point at a time the key already holds is combined with Stage 0's own operator, sum wrapping mod 2^64 or unsigned max.  The state
+ *     does not remember which op built it: use the same value op for every batch of a state (there is nothing to check it against);
+ *   - re-sending a batch is idempotent under max and doubles the values under sum: it is a merge, not a de-duplication;
+ *   - tad_run_stream batches and merges mix freely on one state: the invariants (the moments are the series', the history is the series'
+ *     values sorted, times ascend strictly, last_t is the newest time) hold after every merge, so a later DBSCAN / ARIMA stream batch
+ *     emits what tad_run over the merged window plus the batch emits for the batch's points.  tad_run_stream itself still refuses late rows;
+ *   - the call emits no rows: the verdicts of a merged window come from tad_run_state.  job->algo and the detector parameters other than
+ *     ewma_alpha are ignored;
+ *   - moments: a key with at least one inserted or combined point is replayed from the zero state over its merged series in time order
+ *     with the very step of the stream batches; a key that only had points appended continues from its stored state exactly as a stream
+ *     batch does (so, as for tad_state_trim, the contract holds for it when its earlier batches used the same ewma_alpha); an untouched
+ *     key is copied.
+ * Fields of tad_job that are honoured: agg_flow / value_op, start_time / end_time (Stage 0's row filter), ewma_alpha, TAD_FLAG_KEY_U32 /
+ * TAD_FLAG_TIME_U32 and id (tad_job_progress).  TAD_FLAG_EMIT_ALL_POINTS is TAD_ERR_INVALID_ARGUMENT (there are no rows).  The batch takes
+ * Stage 0 as a stream batch does: dense grid or sparse sort, tad_plan overrides included, host or device columns; cols->num_keys must
+ * equal the state's.  The state needs TAD_STATE_SERIES | TAD_STATE_TIMES: a plain, history-only or series-without-times state, a state
+ * whose times are stale and ewma_alpha outside [0, 1] are TAD_ERR_INVALID_ARGUMENT.
+ * Atomic: only the candidate copies (moments, offsets, arenas) and job-context workspace are written, and they become current together;
+ * any failure — a key out of range (TAD_ERR_KEY_RANGE), allocation, a HIP error — leaves moments, history, series and times as they were.
+ * An empty batch, or one whose points are all too old, is TAD_OK with the state untouched.  A batch without an inserted, combined or
+ * too-old point takes the append path of a stream batch (keys_replayed == 0).  Otherwise a merge costs a rewrite of the series and times
+ * (about 32 B per series point), for a history state the history rewritten once (twice when a point combined: the old values leave,
+ * then the new ones enter), and a serial replay per key with an inserted or combined point, as long as its merged series.
+ * The append path needs a batch without a too-old point as well: with keep_from_t set, ONE point under the cut sends an otherwise in-order
+ * batch through the full rewrite.  Memory outside the state: a merge that combines a point on a history state passes the history through
+ * a scratch arena of the job context that runs it — 8 B per history point, grow-only like all context workspace, kept by every context
+ * that ever ran such a merge (at most max_jobs_in_flight of them) and NOT counted by tad_state_bytes.
+ * Lock order: the state, then a job context, as a batch, a trim and tad_run_state. */
+#define TAD_FEATURE_STATE_MERGE 32u   /* tad_state_merge: a batch placed by time — late rows, re-sent rows, rows of a group split over batches */
+typedef struct {
+  uint64_t rows_in;                  /* as tad_stats */
+  uint64_t rows_used;
+  uint64_t batch_points;             /* distinct (key, flowEndSeconds) points Stage 0 made of the batch, before keep_from_t */
+  uint64_t points_too_old;           /* of those: flow_end_s < keep_from_t, dropped */
+  uint64_t points_appended;          /* newer than everything their key held (what tad_run_stream would have taken) */
+  uint64_t points_inserted;          /* a new time before the key's last_t */
+  uint64_t points_combined;          /* a time the key already held: value = op(old, new) */
+  uint64_t keys_touched;             /* keys with >= 1 appended / inserted / combined point */
+  uint64_t keys_replayed;            /* of those: keys whose moments were replayed from the zero state (>= 1 inserted or combined point) */
+  int32_t stage0_path;               /* as tad_stats */
+  int32_t stage0_attempts;
+  int32_t job_context;
+  int32_t reserved;
+  float ms_stage0;                   /* HIP events, as tad_stats */
+  float ms_merge;                    /* everything after Stage 0 */
+  float ms_total;
+  float reserved1;
+} tad_merge_stats;
+int tad_state_merge(tad_engine *e, tad_state *s, const tad_job *job, const tad_columns *cols, int64_t keep_from_t,
+                    tad_merge_stats *stats /* may be NULL */);
 
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).

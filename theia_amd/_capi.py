@@ -26,6 +26,7 @@ TAD_STATE_SERIES = 2                         # tad_state_create_ex flag: keep ev
 TAD_FEATURE_STREAM_TRIM = 8                  # tad_features() bit: TAD_STATE_TIMES, tad_state_trim, tad_state_bytes, export / import of times
 TAD_STATE_TIMES = 8                          # tad_state_create_ex flag (with TAD_STATE_SERIES): keep every series point's flowEndSeconds
 TAD_FEATURE_STATE_RUN = 16                   # tad_features() bit: tad_run_state, the batch job's rows over everything a state holds
+TAD_FEATURE_STATE_MERGE = 32                 # tad_features() bit: tad_state_merge, a batch placed by time (late, re-sent and split rows)
 
 
 class Plan(C.Structure):
@@ -105,6 +106,14 @@ class Result(C.Structure):
                 ("anomaly", C.c_void_p), ("memory", C.c_int), ("stats", Stats), ("id", C.c_char * 64)]
 
 
+class MergeStats(C.Structure):
+    """tad_merge_stats: what one tad_state_merge call did with the batch's points."""
+    _fields_ = [("rows_in", u64), ("rows_used", u64), ("batch_points", u64), ("points_too_old", u64), ("points_appended", u64),
+                ("points_inserted", u64), ("points_combined", u64), ("keys_touched", u64), ("keys_replayed", u64),
+                ("stage0_path", i32), ("stage0_attempts", i32), ("job_context", i32), ("reserved", i32),
+                ("ms_stage0", f32), ("ms_merge", f32), ("ms_total", f32), ("reserved1", f32)]
+
+
 class Points(C.Structure):
     _fields_ = [("n_points", u64), ("key_id", C.c_void_p), ("flow_end_s", C.c_void_p), ("value", C.c_void_p),
                 ("memory", C.c_int), ("stats", Stats)]
@@ -138,6 +147,7 @@ SYMBOLS = {
     "tad_state_import_times": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_run_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_run_state": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(C.POINTER(Result))]),
+    "tad_state_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), i64, C.POINTER(MergeStats)]),
     "tad_aggregate": (C.c_int, [C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Points))]),
     "tad_points_free": (None, [C.c_void_p, C.POINTER(Points)]),
     "tad_shard_rows": (C.c_int, [C.c_void_p, C.POINTER(Columns), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -282,6 +282,43 @@ int size_trim_arena(JobCtx *e, T *&val, uint64_t &cap, uint64_t len, bool alloca
   return TAD_OK;
 }
 
+// The batch's new points in (key, time) order for stream_history_batch and state_merge_batch: keys in e->hs_key, times in e->hs_t, values
+// and per-key offsets in *nv / *poff.  ensure_batch_points sizes the buffers both share (hs_key, hs_t, hs_sorted, hs_koff: dense point
+// offsets | chunk offsets, K + 1 each; hs_kcnt: per-key counts / long-sort list / chunks | long-list length; the scan scratch).
+int ensure_batch_points(JobCtx *e, uint64_t K, uint64_t P_cap, bool sparse) {
+  const size_t kpad = (size_t)((K + 3) & ~3ull);
+  const uint64_t pc = P_cap ? P_cap : 1;
+  int rc;
+  if ((rc = ensure(e, e->hs_key, pc * 8)) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->hs_t, pc * 8)) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->hs_sorted, pc * 8)) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->hs_koff, (kpad + 4) * 16)) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->hs_kcnt, kpad * 4 + 64)) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K > pc ? K : pc) * sizeof(unsigned long long))) != TAD_OK) return rc;
+  if (!sparse && (rc = ensure(e, e->hs_val, pc * 8)) != TAD_OK) return rc;
+  return TAD_OK;
+}
+
+void batch_points(JobCtx *e, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, const unsigned long long **poff,
+                  const unsigned long long **nv) {
+  hipStream_t s = e->stream;
+  unsigned long long *nk = static_cast<unsigned long long *>(e->hs_key.p);
+  long long *nt = static_cast<long long *>(e->hs_t.p);
+  if (sparse_poff) {   // the sorted unique points of the sparse Stage 0
+    *poff = sparse_poff;
+    *nv = static_cast<const unsigned long long *>(e->sp_val_a.p);
+    launch_hist_decode(s, static_cast<const unsigned long long *>(e->sp_comp_a.p), P, L.t0, nk, nt);
+  } else {             // the dense grid compacted as tad_aggregate does
+    unsigned long long *koff = static_cast<unsigned long long *>(e->hs_koff.p);
+    uint32_t *kcnt = static_cast<uint32_t *>(e->hs_kcnt.p);
+    launch_count_flags(s, g, true, kcnt);
+    launch_scan(s, kcnt, koff, g.K, static_cast<unsigned long long *>(e->scan_scratch.p));
+    launch_emit_points(s, g, L, koff, nk, nt, static_cast<unsigned long long *>(e->hs_val.p));
+    *poff = koff;
+    *nv = static_cast<const unsigned long long *>(e->hs_val.p);
+  }
+}
+
 // One batch on a history and / or series state (tad.h, TAD_STATE_HISTORY / TAD_STATE_SERIES), after the stream count pass and before the
 // job's tail is read: the batch's new points in (key, time) order; a history state sorts them per key and merges them with the current
 // history into the candidate arena (tad_history.hip); a series state appends them to every key's series in the candidate arena; a DBSCAN
@@ -303,13 +340,7 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
   if (st->series && (rc = grow_arena(e, st->ser_val[cand], st->ser_cap[cand], st->ser_len[cur] + P_cap, "series")) != TAD_OK) return rc;
   if (st->times && (rc = grow_arena(e, st->ser_t[cand], st->ser_tcap[cand], st->ser_len[cur] + P_cap, "times")) != TAD_OK) return rc;
   const uint64_t pc = P_cap ? P_cap : 1;
-  if ((rc = ensure(e, e->hs_key, pc * 8)) != TAD_OK) return rc;
-  if ((rc = ensure(e, e->hs_t, pc * 8)) != TAD_OK) return rc;
-  if ((rc = ensure(e, e->hs_sorted, pc * 8)) != TAD_OK) return rc;
-  if ((rc = ensure(e, e->hs_koff, (kpad + 4) * 16)) != TAD_OK) return rc;   // dense point offsets | chunk offsets, K + 1 each
-  if ((rc = ensure(e, e->hs_kcnt, kpad * 4 + 64)) != TAD_OK) return rc;     // per-key counts / long-sort list / chunks | long-list length
-  if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K > pc ? K : pc) * sizeof(unsigned long long))) != TAD_OK) return rc;
-  if (!sparse_poff && (rc = ensure(e, e->hs_val, pc * 8)) != TAD_OK) return rc;
+  if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr)) != TAD_OK) return rc;
   if (dbscan) {
     if ((rc = ensure(e, e->hs_noise, pc)) != TAD_OK) return rc;
     if ((rc = ensure(e, e->hs_cnt, pc * 4)) != TAD_OK) return rc;
@@ -323,17 +354,7 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
   unsigned int *long_count = reinterpret_cast<unsigned int *>(kcnt + kpad);
   unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
   const unsigned long long *poff, *nv;
-  if (sparse_poff) {   // 1. the sorted unique points of the sparse Stage 0
-    poff = sparse_poff;
-    nv = static_cast<const unsigned long long *>(e->sp_val_a.p);
-    launch_hist_decode(s, static_cast<const unsigned long long *>(e->sp_comp_a.p), P, L.t0, nk, nt);
-  } else {             // 1. the dense grid compacted as tad_aggregate does
-    launch_count_flags(s, g, true, kcnt);
-    launch_scan(s, kcnt, koff, K, scratch);
-    launch_emit_points(s, g, L, koff, nk, nt, static_cast<unsigned long long *>(e->hs_val.p));
-    poff = koff;
-    nv = static_cast<const unsigned long long *>(e->hs_val.p);
-  }
+  batch_points(e, g, L, sparse_poff, P, &poff, &nv);   // 1.
   if (st->history) {   // 2. every key's new values sorted; 3. merged with its history into the candidate arena
     launch_hist_sort(s, nv, poff, K, ns, kcnt, long_count);
     launch_hist_merge(s, K, st->hist_off[cur], st->hist_val[cur], poff, ns, st->hist_off[cand], st->hist_val[cand], kcnt, coff, scratch,
@@ -354,6 +375,122 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
     launch_scan(s, cnt, row, P_cap, scratch, dev_total(e));
     hb->noise = noise; hb->cnt = cnt; hb->row = row;
   }
+  return TAD_OK;
+}
+
+// One tad_state_merge batch (tad.h; kernels in tad_merge.hip), in the place of a stream batch's count pass: the batch's points in (key, time)
+// order are classified against the current series, then either appended as a stream batch appends them (nothing inserted, combined or
+// too old) or merged by time into the candidate series, times, history and moments.  Writes candidate memory and context workspace only;
+// mc->changed tells run_job_locked whether the candidates are to become current.  One host round trip: the Stage-0 error word and the
+// classification's counters; a Stage-0 error leaves the rest undone (run_job_locked retries or reports it).
+int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound, bool op_max,
+                      double alpha, MergeCall *mc) {
+  hipStream_t s = e->stream;
+  const uint64_t K = g.K;
+  const int cur = st->cur, cand = cur ^ 1;
+  const uint64_t P_cap = sparse_poff ? P : P_bound;
+  const uint64_t pc = P_cap ? P_cap : 1;
+  const size_t kpad = (size_t)((K + 3) & ~3ull), ko = kpad + 4;
+  const uint64_t S = st->ser_len[cur], H = st->hist_len[cur];
+  int rc;
+  mc->changed = false;
+  mc->added = 0;
+  // the candidate arenas first: an allocation failure leaves the state as it is
+  if ((rc = grow_arena(e, st->ser_val[cand], st->ser_cap[cand], S + P_cap, "series")) != TAD_OK) return rc;
+  if ((rc = grow_arena(e, st->ser_t[cand], st->ser_tcap[cand], S + P_cap, "times")) != TAD_OK) return rc;
+  if (st->history && (rc = grow_arena(e, st->hist_val[cand], st->hist_cap[cand], H + P_cap, "history")) != TAD_OK) return rc;
+  if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr)) != TAD_OK) return rc;
+  // per point: three scans (pc + 1 each) | history gains, sorted | losses, sorted | rank, three flag arrays | class
+  if ((rc = ensure(e, e->mg_pts, (7 * pc + 8) * 8 + pc * 16 + pc + 64)) != TAD_OK) return rc;
+  // per key: counters | long-list length | five offset arrays (K + 1 each) | four u32 arrays
+  if ((rc = ensure(e, e->mg_keys, 128 + ko * 40 + kpad * 16)) != TAD_OK) return rc;
+  unsigned long long *nhoff = static_cast<unsigned long long *>(e->mg_pts.p), *aoff = nhoff + pc + 2, *roff = aoff + pc + 2;
+  unsigned long long *hadd = roff + pc + 2, *hadd_s = hadd + pc, *hrem = hadd_s + pc, *hrem_s = hrem + pc;
+  uint32_t *rank = reinterpret_cast<uint32_t *>(hrem_s + pc), *f_nh = rank + pc, *f_kept = f_nh + pc, *f_hit = f_kept + pc;
+  uint8_t *cls = reinterpret_cast<uint8_t *>(f_hit + pc);
+  MergeCounters *mcnt = static_cast<MergeCounters *>(e->mg_keys.p);
+  unsigned int *long_count = reinterpret_cast<unsigned int *>(mcnt + 1);
+  unsigned long long *akoff = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(e->mg_keys.p) + 128), *rkoff = akoff + ko;
+  unsigned long long *hoff_mid = rkoff + ko, *coff_s = hoff_mid + ko, *coff_h = coff_s + ko;
+  uint32_t *chunks_s = reinterpret_cast<uint32_t *>(coff_h + ko), *chunks_h = chunks_s + kpad, *replay = chunks_h + kpad, *long_list = replay + kpad;
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  const unsigned long long *nk = static_cast<const unsigned long long *>(e->hs_key.p);
+  const long long *nt = static_cast<const long long *>(e->hs_t.p);
+  const unsigned long long *poff, *nv;
+  batch_points(e, g, L, sparse_poff, P, &poff, &nv);
+  // 1. classify; the one round trip: Stage 0's error word, the point count, the classification's counters
+  HIP_TRY(e, hipMemsetAsync(mcnt, 0, sizeof(MergeCounters), s));
+  launch_merge_classify(s, nk, nt, poff + K, P_cap, K, st->ser_off[cur], st->ser_t[cur], (long long)mc->keep_from, cls, rank, f_nh, f_kept, f_hit, mcnt);
+  unsigned char *hm = e->tail_host + kTailMoments;   // (the moment partials' place in the pinned tail: a merge has none)
+  HIP_TRY(e, hipMemcpyAsync(e->ctr_host, e->counters.p, sizeof(DevCounters), hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(hm + sizeof(MergeCounters), poff + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  if (e->ctr_host->err != 0) return TAD_OK;
+  MergeCounters c;
+  unsigned long long points = 0;
+  memcpy(&c, hm, sizeof c);
+  memcpy(&points, hm + sizeof c, 8);
+  tad_merge_stats &ms = mc->stats;
+  ms.batch_points = points;
+  ms.points_too_old = c.too_old;
+  ms.points_appended = c.appended;
+  ms.points_inserted = c.inserted;
+  ms.points_combined = c.combined;
+  ms.keys_touched = ms.keys_replayed = 0;
+  if (c.appended + c.inserted + c.combined == 0) return TAD_OK;   // nothing to merge: the state stays as it is
+  if (c.inserted == 0 && c.combined == 0 && c.too_old == 0) {
+    // 6. every point is newer than what its key held: the append path of a stream batch (stream_history_batch's steps 2, 3, 3', 3'')
+    if (st->history) {
+      unsigned long long *ns = static_cast<unsigned long long *>(e->hs_sorted.p);
+      launch_hist_sort(s, nv, poff, K, ns, long_list, long_count);
+      launch_hist_merge(s, K, st->hist_off[cur], st->hist_val[cur], poff, ns, st->hist_off[cand], st->hist_val[cand], chunks_h, coff_h, scratch,
+                        hist_merge_chunks_bound(K, H + P_cap));
+    }
+    launch_series_append(s, K, st->ser_off[cur], st->ser_val[cur], poff, nv, st->ser_off[cand], st->ser_val[cand]);
+    launch_series_append(s, K, st->ser_off[cur], reinterpret_cast<const unsigned long long *>(st->ser_t[cur]), poff,
+                         reinterpret_cast<const unsigned long long *>(nt), st->ser_off[cand], reinterpret_cast<unsigned long long *>(st->ser_t[cand]));
+    launch_merge_moments(s, K, nullptr, st->ser_off[cur], st->ser_off[cand], st->ser_val[cand], st->ser_t[cand], alpha, state_view(st, cur),
+                         state_view(st, cand), mcnt);
+  } else {
+    if (st->history && c.combined && (rc = ensure(e, e->mg_hist, (H ? H : 1) * 8)) != TAD_OK) return rc;
+    // 2. the scans; per key: candidate offsets, the history's packed gains / losses, chunk counts, who replays
+    launch_scan(s, f_nh, nhoff, P_cap, scratch);
+    launch_scan(s, f_kept, aoff, P_cap, scratch);
+    launch_scan(s, f_hit, roff, P_cap, scratch);
+    launch_merge_keys(s, K, poff, nhoff, aoff, roff, cls, st->ser_off[cur], st->history ? st->hist_off[cur] : nullptr, st->ser_off[cand], akoff, rkoff,
+                      hoff_mid, chunks_s, chunks_h, replay);
+    launch_scan(s, chunks_s, coff_s, K, scratch);
+    // 3. series and times merged by time (and the history's gains and losses packed)
+    launch_merge_series(s, merge_chunks_bound(K, S + P_cap), coff_s, K, op_max, st->ser_off[cur], st->ser_val[cur], st->ser_t[cur], poff, nt, nv, cls, rank,
+                        nhoff, aoff, roff, st->ser_off[cand], st->ser_val[cand], st->ser_t[cand], st->history ? hadd : nullptr, st->history ? hrem : nullptr);
+    if (st->history) {   // 4. the combined points' old values leave the history (through the scratch arena), then the batch's values enter
+      const unsigned long long *hoff_from = st->hist_off[cur], *hval_from = st->hist_val[cur];
+      if (c.combined) {
+        unsigned long long *hmid = static_cast<unsigned long long *>(e->mg_hist.p);
+        launch_hist_sort(s, hrem, rkoff, K, hrem_s, long_list, long_count);
+        launch_scan(s, chunks_h, coff_h, K, scratch);
+        launch_hist_subtract(s, trim_chunks_bound(K, H), coff_h, K, st->hist_off[cur], st->hist_val[cur], rkoff, hrem_s, hoff_mid, hmid);
+        hoff_from = hoff_mid;
+        hval_from = hmid;
+      }
+      launch_hist_sort(s, hadd, akoff, K, hadd_s, long_list, long_count);
+      launch_hist_merge(s, K, hoff_from, hval_from, akoff, hadd_s, st->hist_off[cand], st->hist_val[cand], chunks_h, coff_h, scratch,
+                        hist_merge_chunks_bound(K, H + P_cap));
+    }
+    // 5. the moments
+    launch_merge_moments(s, K, replay, st->ser_off[cur], st->ser_off[cand], st->ser_val[cand], st->ser_t[cand], alpha, state_view(st, cur),
+                         state_view(st, cand), mcnt);
+  }
+  HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  memcpy(&c, hm, sizeof c);
+  ms.keys_touched = c.keys_touched;
+  ms.keys_replayed = c.keys_replayed;
+  mc->changed = true;
+  mc->added = c.inserted + c.appended;
   return TAD_OK;
 }
 
@@ -640,6 +777,24 @@ int run_sparse_classes(JobCtx *e, const tad_job *job, const JobParams &jp, bool 
 int sparse_points_direct(JobCtx *e, uint64_t n_rows_in, uint64_t rows_used, Lattice L, uint64_t P, DevCounters *ctr, tad_mem out_memory,
                          tad_points **points_out);
 
+// what every entry point that feeds a batch through run_job_locked checks about the job's Stage-0 fields and the columns (who: the call's
+// name in its own messages; the request messages are the reference's wording)
+int validate_job_columns(tad_engine *e, const tad_job *job, const tad_columns *cols, const char *who) {
+  if (job->agg_flow < TAD_AGG_NONE || job->agg_flow > TAD_AGG_EXTERNAL)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "invalid request: Throughput Anomaly Detector aggregated flow type should be 'pod' or 'external' or 'svc'");
+  if (job->start_time != 0 && job->end_time != 0 && job->end_time <= job->start_time)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "invalid request: EndInterval should be after StartInterval");
+  if (cols->n_rows > 0 && (!cols->key_id || !cols->flow_end_s || !cols->value))
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: key_id, flow_end_s and value columns are required", who);
+  if (cols->n_rows > 0 && cols->num_keys == 0)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: num_keys is 0 but there are rows", who);
+  if ((job->flags & TAD_FLAG_KEY_U32) && cols->num_keys >= 0xFFFFFFFFull)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: TAD_FLAG_KEY_U32 needs num_keys < 2^32 - 1 (TAD_KEY_SKIP32 is the skip marker)", who);
+  if (cols->n_buckets > 0 && cols->step < 1)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: lattice hint needs step >= 1", who);
+  return TAD_OK;
+}
+
 // The job (points_out == nullptr), Stage 0 alone (points_out != nullptr), or one streaming batch (stream != nullptr).
 int run_job(tad_engine *eng, const tad_job *job, const tad_columns *cols, tad_mem out_memory, tad_result **out, tad_points **points_out,
             tad_state *stream = nullptr) {
@@ -664,18 +819,10 @@ int run_job(tad_engine *eng, const tad_job *job, const tad_columns *cols, tad_me
   if (points_out) *points_out = nullptr;
   if (!points_mode && job->algo != TAD_ALGO_EWMA && job->algo != TAD_ALGO_ARIMA && job->algo != TAD_ALGO_DBSCAN && job->algo != TAD_ALGO_DROP)
     return fail(e, TAD_ERR_INVALID_ARGUMENT, "invalid request: Throughput Anomaly Detector algorithm type should be 'EWMA' or 'ARIMA' or 'DBSCAN'");
-  if (job->agg_flow < TAD_AGG_NONE || job->agg_flow > TAD_AGG_EXTERNAL)
-    return fail(e, TAD_ERR_INVALID_ARGUMENT, "invalid request: Throughput Anomaly Detector aggregated flow type should be 'pod' or 'external' or 'svc'");
-  if (job->start_time != 0 && job->end_time != 0 && job->end_time <= job->start_time)
-    return fail(e, TAD_ERR_INVALID_ARGUMENT, "invalid request: EndInterval should be after StartInterval");
-  if (cols->n_rows > 0 && (!cols->key_id || !cols->flow_end_s || !cols->value))
-    return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run: key_id, flow_end_s and value columns are required");
-  if (cols->n_rows > 0 && cols->num_keys == 0)
-    return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run: num_keys is 0 but there are rows");
-  if ((job->flags & TAD_FLAG_KEY_U32) && cols->num_keys >= 0xFFFFFFFFull)
-    return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run: TAD_FLAG_KEY_U32 needs num_keys < 2^32 - 1 (TAD_KEY_SKIP32 is the skip marker)");
-  if (cols->n_buckets > 0 && cols->step < 1)
-    return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run: lattice hint needs step >= 1");
+  {
+    const int vrc = validate_job_columns(e, job, cols, "tad_run");
+    if (vrc != TAD_OK) return vrc;
+  }
   if (job->ewma_alpha < 0.0 || job->ewma_alpha > 1.0 || job->dbscan_eps < 0.0 || job->dbscan_min_samples < 0 || job->arima_maxiter < 0 ||
       job->drop_nsigma < 0.0 || job->drop_min_samples < 0)
     return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run: detector parameter out of range");
@@ -1115,7 +1262,11 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       rows = *e->total_host;
     } else if (stream) {   // continue the per-key recurrences from the stored state; the next state stays a candidate
       if ((rc = ensure_key_buffers(e, g.K)) != TAD_OK) return rc;
-      if (stream_poff)
+      if (e->merge) {   // tad_state_merge: the points are placed by time, no count pass (it would refuse a late row), no rows
+        e->merge->changed = false;
+        if (g.K && (rc = state_merge_batch(e, stream, g, L, stream_poff, stream_P, (slots_all < cells ? slots_all : cells), op_max, jp.alpha, e->merge)) != TAD_OK)
+          return rc;
+      } else if (stream_poff)
         launch_stream_points(s, static_cast<const unsigned long long *>(e->sp_comp_a.p), static_cast<const unsigned long long *>(e->sp_val_a.p), stream_poff,
                              g.K, L.t0, jp.alpha, jp.all_points, false, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),
                              static_cast<uint32_t *>(e->n_anom.p), nullptr, OutRows{}, ctr);
@@ -1123,11 +1274,11 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
         launch_stream(s, g, L, jp.alpha, jp.all_points, false, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),
                       static_cast<uint32_t *>(e->n_anom.p), nullptr, OutRows{}, ctr);
       unsigned long long *off = static_cast<unsigned long long *>(e->off.p);
-      if ((stream->history || stream->series) && g.K &&
+      if (!e->merge && (stream->history || stream->series) && g.K &&
           (rc = stream_history_batch(e, stream, g, L, stream_poff, stream_P, (slots_all < cells ? slots_all : cells), jp, &hist)) != TAD_OK)
         return rc;
       if (jp.algo == TAD_ALGO_ARIMA && g.K && (rc = stream_arima_batch(e, stream, stream->cur ^ 1, g.K, hist, jp, ctr, &ab)) != TAD_OK) return rc;
-      if (jp.algo == TAD_ALGO_EWMA)   // (a DBSCAN / ARIMA batch counted its rows in stream_history_batch / stream_arima_batch)
+      if (jp.algo == TAD_ALGO_EWMA && !e->merge)   // (a DBSCAN / ARIMA batch counted its rows in stream_history_batch / stream_arima_batch)
         launch_scan(s, static_cast<const uint32_t *>(e->n_anom.p), off, g.K, static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
       HIP_TRY(e, hipMemcpyAsync(e->tail_host, e->counters.p, kTailBytes, hipMemcpyDeviceToHost, s));
       HIP_TRY(e, hipStreamSynchronize(s));
@@ -1229,6 +1380,28 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       st.hist_sampled = (v2 && hist_sampled) ? 1 : (use_kh ? 2 : 0);
       e->done.store(4);
       *points_out = &pp->pub;
+      return TAD_OK;
+    }
+
+    if (e->merge) {   // tad_state_merge: no rows; the candidate copies become current together
+      MergeCall *mc = e->merge;
+      HIP_TRY(e, hipEventRecord(e->ev[4], s));
+      HIP_TRY(e, hipStreamSynchronize(s));
+      tad_merge_stats &ms = mc->stats;
+      ms.rows_in = n;
+      ms.rows_used = c.rows_used;
+      ms.stage0_path = sparse ? (sp_part ? 8 : 4) : (v2 ? (pl.wc_cap ? 3 : 2) : 1);
+      ms.stage0_attempts = attempt + 1;
+      ms.job_context = e->index;
+      hipEventElapsedTime(&ms.ms_stage0, e->ev[1], e->ev[5]);
+      hipEventElapsedTime(&ms.ms_merge, e->ev[5], e->ev[4]);
+      hipEventElapsedTime(&ms.ms_total, e->ev[0], e->ev[4]);
+      if (mc->changed) {
+        stream->ser_len[stream->cur ^ 1] = stream->ser_len[stream->cur] + mc->added;
+        if (stream->history) stream->hist_len[stream->cur ^ 1] = stream->hist_len[stream->cur] + mc->added;
+        stream->cur ^= 1;
+      }
+      if (depth == 0) e->done.store(4);
       return TAD_OK;
     }
 
@@ -2073,6 +2246,44 @@ int tad_run_state(tad_engine *eng, tad_state *st, const tad_job *job, tad_mem ou
   Lease lease(eng, job->id, job->algo == TAD_ALGO_ARIMA);
   if (!lease.c) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_run_state: no job context available");
   return run_state_locked(lease.c, st, job, out_memory, out);
+}
+
+// tad.h: a batch placed by time.  The batch runs as a stream batch does up to the end of Stage 0 (run_job_locked with the context's merge
+// mode set), then state_merge_batch.
+int tad_state_merge(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, int64_t keep_from_t, tad_merge_stats *stats) {
+  if (stats) memset(stats, 0, sizeof *stats);
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: engine is NULL");
+  if (!st || !job || !cols) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: state, job and cols must not be NULL");
+  if (!st->series || !st->times)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES): "
+                                               "without them it does not know where a late point belongs; state unchanged");
+  if (job->flags & TAD_FLAG_EMIT_ALL_POINTS)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: TAD_FLAG_EMIT_ALL_POINTS asks for rows; a merge emits none (tad_run_state judges the window)");
+  if (!(job->ewma_alpha >= 0.0 && job->ewma_alpha <= 1.0)) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: ewma_alpha out of range");
+  if (cols->num_keys != st->K)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: batch declares %llu keys, the state holds %llu (they must be equal)",
+                (unsigned long long)cols->num_keys, (unsigned long long)st->K);
+  {
+    const int vrc = validate_job_columns(eng, job, cols, "tad_state_merge");
+    if (vrc != TAD_OK) return vrc;
+  }
+  tad_job j = *job;   // the detector is not run: a stream batch of the EWMA kind up to the end of Stage 0
+  j.algo = TAD_ALGO_EWMA;
+  std::unique_lock<std::mutex> state_lk(st->mu);   // (the order of tad_run_stream: the state, then a job context)
+  if (st->times_stale)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: the series was imported without its times (tad_state_import_times); state unchanged");
+  Lease lease(eng, j.id, false);
+  if (!lease.c) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_merge: no job context available");
+  PauseHold hold(eng);
+  lease.c->hold = &hold;
+  MergeCall mc;
+  mc.keep_from = keep_from_t;
+  lease.c->merge = &mc;
+  tad_result *none = nullptr;
+  const int rc = run_job_locked(lease.c, &j, cols, TAD_MEM_DEVICE, &none, nullptr, st, 0);
+  lease.c->merge = nullptr;
+  if (rc == TAD_OK && stats) *stats = mc.stats;
+  return rc;
 }
 
 int tad_aggregate(tad_engine *e, const tad_job *job, const tad_columns *cols, tad_mem out_memory, tad_points **out) {

@@ -94,6 +94,8 @@ struct JobCtx {
   DevBuf sp_comp_a, sp_comp_b, sp_val_a, sp_val_b, sp_temp, sp_first, sp_times;  // Stage 0 sparse (sort + rank grid)
   DevBuf sp_cls;                                                                  // Stage 0 sparse, length classes: per-key class arrays
   DevBuf hs_key, hs_t, hs_val, hs_sorted, hs_noise, hs_cnt, hs_row, hs_koff, hs_kcnt;   // a history batch: new points, sorted values, verdicts, rows, offsets
+  DevBuf mg_pts, mg_keys, mg_hist;   // tad_state_merge: per batch point | per key | the history between its subtract and its merge
+  struct MergeCall *merge = nullptr;   // set while the context runs a tad_state_merge batch (run_job_locked's merge mode)
   DevBuf as_key, as_pt, as_ser, as_fit, as_pos, as_ws;   // a stream ARIMA batch: per key | per new point | packed series | per fit | per position | fit workspace
   int arima_relaunches = 0;       // times the running job's ARIMA fit was relaunched after it had yielded to whole-CU jobs (tad_stats.arima_relaunches)
   bool sp_by_partition = false;   // the running job's sparse Stage 0 went through the partition pass + LDS sort (stage0_path 8 / 9 / 10 instead of 4 / 6 / 7)
@@ -119,6 +121,14 @@ struct JobCtx {
                                                   // hashed ones of the same shape); a probe that fails doubles the interval, up to 64
     bool wide_tiles = false;   // 32-bit tile cells overflowed the list for this table: go straight to 8-byte cells
   } learnt;
+};
+
+// one tad_state_merge call: what run_job_locked's merge mode needs beyond the job, and what it reports
+struct MergeCall {
+  int64_t keep_from = 0;
+  tad_merge_stats stats{};
+  bool changed = false;    // the candidate copies hold the merged state (false: nothing to merge, the state stays as it is)
+  uint64_t added = 0;      // series points gained (inserted + appended)
 };
 
 // per-key running state of the streaming EWMA detector: two copies (the count pass writes the candidate next state,
@@ -213,6 +223,7 @@ template <typename F> void for_each_buf(JobCtx *c, F f) {
                     &c->sp_comp_a, &c->sp_comp_b, &c->sp_val_a, &c->sp_val_b, &c->sp_temp, &c->sp_first, &c->sp_times, &c->sp_cls, &c->part_fin, &c->ovf_keys,
                     &c->in_key, &c->in_key2, &c->in_te, &c->in_ts, &c->in_val,
                     &c->hs_key, &c->hs_t, &c->hs_val, &c->hs_sorted, &c->hs_noise, &c->hs_cnt, &c->hs_row, &c->hs_koff, &c->hs_kcnt,
+                    &c->mg_pts, &c->mg_keys, &c->mg_hist,
                     &c->as_key, &c->as_pt, &c->as_ser, &c->as_fit, &c->as_pos, &c->as_ws};
   for (DevBuf *b : bufs) f(*b);
 }

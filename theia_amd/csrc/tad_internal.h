@@ -426,6 +426,35 @@ void launch_win_ewma(hipStream_t s, uint64_t K, const unsigned long long *soff, 
                      int ewma_emit = 0, uint32_t ewma_emit_rows = 0);   // tad_plan: 1 = the lanes store their rows themselves; LDS rows per wavefront of the staged emit
 // nk[i] = the key of series point i
 void launch_win_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, unsigned long long *nk);
+// ---- tad_state_merge (tad_merge.hip): a batch's points nk / nt / nv (key k's at [poff[k], poff[k + 1])) placed by time ----
+struct MergeCounters {   // one 64-byte block on the device, zeroed per attempt
+  unsigned long long too_old, appended, inserted, combined, keys_touched, keys_replayed, pad[2];
+};
+// per point: cls (too old / appended / inserted / combined), rank = the key's old points before it, and the flags of the three scans:
+// f_nh = adds an element (inserted or appended), f_kept = not too old, f_hit = combined; lanes in [*P_dev, P_cap) write zeros
+void launch_merge_classify(hipStream_t s, const unsigned long long *nk, const long long *nt, const unsigned long long *P_dev, uint64_t P_cap, uint64_t K,
+                           const unsigned long long *soff, const long long *st, long long keep_from, uint8_t *cls, uint32_t *rank, uint32_t *f_nh,
+                           uint32_t *f_kept, uint32_t *f_hit, MergeCounters *mc);
+// nhoff / aoff / roff = the scans of f_nh / f_kept / f_hit.  soff_new (K + 1) = the candidate series offsets; chunks_s[k] = the key's
+// wavefronts in launch_merge_series; replay[k] = the key has an inserted or combined point.  hoff_old != NULL (history states): akoff /
+// rkoff (K + 1) = the packed per-key offsets of the values the history gains / loses, hoff_mid = hoff_old - rkoff, chunks_h[k] = the
+// wavefronts of the key's old history
+void launch_merge_keys(hipStream_t s, uint64_t K, const unsigned long long *poff, const unsigned long long *nhoff, const unsigned long long *aoff,
+                       const unsigned long long *roff, const uint8_t *cls, const unsigned long long *soff_old, const unsigned long long *hoff_old,
+                       unsigned long long *soff_new, unsigned long long *akoff, unsigned long long *rkoff, unsigned long long *hoff_mid, uint32_t *chunks_s,
+                       uint32_t *chunks_h, uint32_t *replay);
+uint64_t merge_chunks_bound(uint64_t K, uint64_t total_len);   // total_len = old series points + batch points
+// every key's old points and batch points merged by time into sval_new / st_new; a combined point's value is op(old, new).  hadd / hrem
+// (NULL without a history): the values the history gains at aoff[i] / loses at roff[i]
+void launch_merge_series(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, bool op_max, const unsigned long long *soff_old,
+                         const unsigned long long *sval_old, const long long *st_old, const unsigned long long *poff, const long long *nt,
+                         const unsigned long long *nv, const uint8_t *cls, const uint32_t *rank, const unsigned long long *nhoff,
+                         const unsigned long long *aoff, const unsigned long long *roff, const unsigned long long *soff_new, unsigned long long *sval_new,
+                         long long *st_new, unsigned long long *hadd, unsigned long long *hrem);
+// next = cur for the untouched keys; a key with replay[k] replayed with stream_step over its merged series from the zero state; a key that
+// only gained newer points continued over them.  replay == NULL: no key replays.  Counts keys_touched / keys_replayed
+void launch_merge_moments(hipStream_t s, uint64_t K, const uint32_t *replay, const unsigned long long *soff_old, const unsigned long long *soff_new,
+                          const unsigned long long *sval_new, const long long *st_new, double alpha, StreamState cur, StreamState next, MergeCounters *mc);
 // ---- streaming ARIMA (tad_arima.hip): a batch on a series state, per touched key (slot) and per new point ----
 struct ArimaSlots {
   uint32_t *key;                 // the slot's key
@@ -620,6 +649,7 @@ const void *code_anchor_factorize();
 const void *code_anchor_history();
 const void *code_anchor_ingest();
 const void *code_anchor_kernels();
+const void *code_anchor_merge();
 const void *code_anchor_shard();
 const void *code_anchor_sparse();
 const void *code_anchor_stage0_part();

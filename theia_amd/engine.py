@@ -562,13 +562,9 @@ class TadEngine:
         (TAD_STATE_TIMES)"""
         return TadState(self, num_keys, history=history, series=series, times=times)
 
-    def run_stream(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, emit_all=False, out="host",
-                   alpha=0.0, job_id="", num_keys=None, key_id2=None, algo="EWMA", eps=0.0, min_samples=0, maxiter=0):
-        """One batch of a streaming detector on `state` (tad_run_stream).  key_id2: the second key column of pod mode.  algo="DBSCAN"
-        needs a state with history, algo="ARIMA" (maxiter: arima_maxiter) a state with a series: the rows are those tad_run emits for
-        this batch's points over everything seen so far."""
-        if algo not in capi.TAD_ALGO:
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "algo must be EWMA, ARIMA, DBSCAN or DROP")
+    def _stream_columns(self, state, key_id, flow_end_s, value, key_id2, num_keys, lattice):
+        """The tad_columns of one batch on `state` (run_stream, merge_stream): narrow columns, device arrays, the second key column of pod
+        mode.  Returns (cols, narrow flags, what must stay alive until the call returns)."""
         narrow = _narrow_flags(self._lib, key_id, key_id2, flow_end_s, None)
         pk, n, dev, keep1 = _as_column(key_id, np.uint64, narrow="key")
         pt, nt, dev_t, keep2 = _as_column(flow_end_s, np.int64, narrow="time")
@@ -576,19 +572,47 @@ class TadEngine:
         pk2, nk2, dev_k2, keep4 = _as_column(key_id2, np.uint64, narrow="key")
         if nt != n or nv != n or dev_t != dev or dev_v != dev or (key_id2 is not None and (nk2 != n or dev_k2 != dev)):
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "columns must have equal length and live in the same memory")
-        job = capi.Job(algo=capi.TAD_ALGO[algo], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
-                       dbscan_eps=float(eps), dbscan_min_samples=int(min_samples), arima_maxiter=int(maxiter),
-                       flags=(capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0) | narrow, id=job_id.encode()[:63])
         cols = capi.Columns(n_rows=n, key_id=pk, key_id2=pk2, flow_end_s=pt, value=pv, num_keys=state.num_keys if num_keys is None else int(num_keys),
                             memory=capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST)
         if lattice is not None:
             cols.t0, cols.step, cols.n_buckets = int(lattice[0]), int(lattice[1]), int(lattice[2])
+        return cols, narrow, (keep1, keep2, keep3, keep4)
+
+    def run_stream(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, emit_all=False, out="host",
+                   alpha=0.0, job_id="", num_keys=None, key_id2=None, algo="EWMA", eps=0.0, min_samples=0, maxiter=0):
+        """One batch of a streaming detector on `state` (tad_run_stream).  key_id2: the second key column of pod mode.  algo="DBSCAN"
+        needs a state with history, algo="ARIMA" (maxiter: arima_maxiter) a state with a series: the rows are those tad_run emits for
+        this batch's points over everything seen so far."""
+        if algo not in capi.TAD_ALGO:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "algo must be EWMA, ARIMA, DBSCAN or DROP")
+        cols, narrow, keep = self._stream_columns(state, key_id, flow_end_s, value, key_id2, num_keys, lattice)
+        job = capi.Job(algo=capi.TAD_ALGO[algo], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
+                       dbscan_eps=float(eps), dbscan_min_samples=int(min_samples), arima_maxiter=int(maxiter),
+                       flags=(capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0) | narrow, id=job_id.encode()[:63])
         res = C.POINTER(capi.Result)()
         rc = self._lib.tad_run_stream(self._h, state._h, C.byref(job), C.byref(cols),
                                       capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
-        del keep1, keep2, keep3, keep4
+        del keep
         self._check(rc)
         return TadResult(self, res)
+
+    def merge_stream(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, alpha=0.0, keep_from=0, job_id="",
+                     num_keys=None, key_id2=None):
+        """One batch placed BY TIME into `state` (tad_state_merge): late rows, re-sent rows, rows of a (key, flowEndSeconds) group split
+        over batches.  Afterwards the state is the one a fresh state holds after one run_stream EWMA batch over its window's points plus
+        this batch (without the points older than keep_from, when that is not 0).  Needs a state with series=True and times=True; use
+        the same value_op for every batch of a state.  No rows: ask run_state for the window's verdicts.  Returns the call's
+        tad_merge_stats as a dict."""
+        if not self._lib.tad_features() & capi.TAD_FEATURE_STATE_MERGE:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_state_merge (TAD_FEATURE_STATE_MERGE)")
+        cols, narrow, keep = self._stream_columns(state, key_id, flow_end_s, value, key_id2, num_keys, lattice)
+        job = capi.Job(algo=capi.TAD_ALGO["EWMA"], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
+                       flags=narrow, id=job_id.encode()[:63])
+        stats = capi.MergeStats()
+        rc = self._lib.tad_state_merge(self._h, state._h, C.byref(job), C.byref(cols), int(keep_from), C.byref(stats))
+        del keep
+        self._check(rc)
+        return {name: getattr(stats, name) for name, _ in capi.MergeStats._fields_ if not name.startswith("reserved")}
 
     def run_state(self, state, algo="EWMA", alpha=0.0, eps=0.0, min_samples=0, maxiter=0, emit_all=False, out="host", job_id=""):
         """The batch job's verdicts over everything `state` holds, from the state alone (tad_run_state): exactly the rows run() returns

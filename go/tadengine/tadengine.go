@@ -977,6 +977,66 @@ func (s *State) Run(job Job) ([]Row, error) {
 	return rows, nil
 }
 
+var stateWindowOnce sync.Once
+var stateWindowOK bool
+
+// hasStateWindow: the library knows tad_run_state_window (tad_features); an older one would not export the call.
+func hasStateWindow() bool {
+	stateWindowOnce.Do(func() { stateWindowOK = C.tad_features()&C.TAD_FEATURE_STATE_WINDOW != 0 })
+	return stateWindowOK
+}
+
+// RunWindow is Run over a window of what the state holds, read-only (tad_run_state_window): of every key's series the points with
+// flowEndSeconds >= fromT and < toT (0 = no bound on that side), then the newest keepPoints of those (0 = all).  The rows are exactly
+// those the batch job returns over these points.  Both bounds act on flowEndSeconds: fromT is not the reference's start_time filter,
+// which tests flowStartSeconds.  job.StartTime / EndTime must be 0, as for Run; the state is left unchanged.
+func (s *State) RunWindow(job Job, fromT, toT int64, keepPoints uint64) ([]Row, error) {
+	if !hasStateWindow() {
+		return nil, errors.New("tadengine: libtad_mi355x.so has no tad_run_state_window (TAD_FEATURE_STATE_WINDOW)")
+	}
+	if !s.series || !s.times {
+		return nil, IllegalArgument{"tadengine: RunWindow needs a state made by NewStateWithTimes"}
+	}
+	if job.Algo == DBSCAN && !s.history {
+		return nil, IllegalArgument{"tadengine: RunWindow with DBSCAN needs a state made by NewStateWithTimes with history"}
+	}
+	var cj C.tad_job
+	cj.algo = C.tad_algo(job.Algo)
+	cj.start_time = C.int64_t(job.StartTime)
+	cj.end_time = C.int64_t(job.EndTime)
+	cj.dbscan_eps = C.double(job.DBSCANEps)
+	cj.dbscan_min_samples, cj.arima_maxiter = C.int32_t(job.DBSCANMinSamples), C.int32_t(job.ARIMAMaxIter)
+	id := []byte(job.ID)
+	if len(id) > 63 {
+		id = id[:63]
+	}
+	for i, b := range id {
+		cj.id[i] = C.char(b)
+	}
+	var res *C.tad_result
+	if rc := C.tad_run_state_window(s.e.h, s.h, &cj, C.int64_t(fromT), C.int64_t(toT), C.uint64_t(keepPoints), C.TAD_MEM_HOST, &res); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, IllegalArgument{msg}
+		}
+		return nil, fmt.Errorf("tad_run_state_window: %s (code %d)", msg, int(rc))
+	}
+	defer C.tad_result_free(s.e.h, res)
+	a := int(res.n_rows)
+	rows := make([]Row, a)
+	if a > 0 {
+		k := unsafe.Slice((*uint64)(unsafe.Pointer(res.key_id)), a)
+		t := unsafe.Slice((*int64)(unsafe.Pointer(res.flow_end_s)), a)
+		x := unsafe.Slice((*float64)(unsafe.Pointer(res.throughput)), a)
+		c := unsafe.Slice((*float64)(unsafe.Pointer(res.algo_calc)), a)
+		sd := unsafe.Slice((*float64)(unsafe.Pointer(res.stddev)), a)
+		for i := range rows {
+			rows[i] = Row{k[i], t[i], x[i], c[i], sd[i]}
+		}
+	}
+	return rows, nil
+}
+
 var stateMergeOnce sync.Once
 var stateMergeOK bool
 

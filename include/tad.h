@@ -608,6 +608,51 @@ typedef struct {
 int tad_state_merge(tad_engine *e, tad_state *s, const tad_job *job, const tad_columns *cols, int64_t keep_from_t,
                     tad_merge_stats *stats /* may be NULL */);
 
+/* ---- the batch verdicts over a time range of a state (TAD_FEATURE_STATE_WINDOW; check tad_features() before calling this) ----
+ * tad_run_state judges everything the state holds, and tad_state_trim narrows a state for good and at its old end only.  A state that
+ * keeps seven days can answer "the last 24 h" or "everything up to the last complete hour" with this call: read-only, any window the
+ * state covers.  Cost: tad_run_state's over the window plus the view (below).  Measured on 24 h states of 1e5 and 1e6 keys it is below
+ * tad_run over the same points in device columns for EWMA on every window tried and for DBSCAN except in one corner: a state of very many
+ * short keys (1e6 keys, about 100 points each) and a window that keeps nearly all of it, where the call took 1.14x tad_run's time — the
+ * view copies almost the whole state and rewrites its history.
+ * The window.  Of every key's series, in time order: (1) the points with flow_end_s >= from_t, when from_t != 0; (2) and flow_end_s <
+ * to_t, when to_t != 0 — the half-open rule of tad_job.end_time (anomaly_detection.py:584-586); (3) then only the newest keep_points of
+ * those, when keep_points != 0.  (1) and (3) are tad_state_trim's rules.  All three zero is the whole state.  BOTH bounds act on
+ * flowEndSeconds: the state holds no flowStartSeconds, so from_t is NOT the reference's start_time filter, which tests flowStartSeconds
+ * (anomaly_detection.py:581-583); a caller that needs that filter applies it to the rows before they reach the state.
+ * Contract: let W be tad_run_state's W and W' its rows inside the window.  The call returns exactly the rows tad_run returns for W' with
+ * the same algo, detector parameters and TAD_FLAG_EMIT_ALL_POINTS: key_id, flow_end_s, throughput, algo_calc, stddev (and anomaly with the
+ * flag), in the same (key, time) order, bit for bit, whatever Stage-0 path tad_run takes for W'.  Equivalently, with to_t == 0: the rows
+ * of tad_run_state on a copy of the state after tad_state_trim(keep_points, from_t).  The state is read only: after the call,
+ * successful or not, moments, history, series and times are unchanged.
+ * Arguments: the honoured tad_job fields, the refusals and what the state must hold are tad_run_state's — start_time / end_time in the
+ * job stay refused (the window is this call's arguments), as do TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 and TAD_ALGO_DROP; EWMA and ARIMA
+ * need TAD_STATE_SERIES | TAD_STATE_TIMES, DBSCAN needs TAD_STATE_HISTORY as well; stale times are refused.  from_t > to_t with both
+ * non-zero is TAD_ERR_INVALID_ARGUMENT; from_t == to_t is an empty window; an empty window or an empty state is TAD_OK with zero rows.
+ * tad_stats: as tad_run_state, over W' — rows_in = rows_used = n_points = the window's points, n_keys = keys with a point in the window,
+ * t0 = the smallest time in the window, pts_mean / pts_m2 merged from the window's per-key moments, the ARIMA counters as tad_run over
+ * W' reports them, the Stage-0 fields zero; host_syncs is 3 when bounds are set on a non-empty state (one more than tad_run_state: the
+ * window's size is read before the view is allocated) and 2 for the all-zero window or an empty state.
+ * How: a key cut by the window has its (n, avg, m2) replayed from the zero state over its window values with the very step of the
+ * stream and of tad_state_trim — one lane's serial chain as long as the cut key's window, as for a trim; a key wholly inside takes the
+ * state's moments (bit-identical by the state's invariants).  DBSCAN judges against the window's values sorted per key, not the state's
+ * history: when 2 * (window points) <= (state points) the window's values are sorted, otherwise the excluded values are sorted and
+ * removed from the state's history — the same bits either way, so "everything but the newest hour" does not sort 99 % of the state to
+ * remove 1 %.  ARIMA's lambda, Box-Cox and fits run over the window's subseries.  When the window leaves every key whole the state's own
+ * arrays are judged and the call costs tad_run_state plus the bounds.
+ * Memory outside the state: the window's view lives in the workspace of the job context that runs the call — about 16 B per window point
+ * (values and times), 8 B more per window point for DBSCAN's sorted values, 16 B per excluded point on the subtract path (packed and
+ * sorted), about 80 B per key, and the sort's scratch; sized from the window, not the state; grow-only like all context workspace, kept
+ * by every context that ever ran such a call (at most max_jobs_in_flight of them) and NOT counted by tad_state_bytes.  Any failure,
+ * allocation included, returns an error with no result and the state untouched.
+ * Lock order: the state, then a job context, as tad_run_state; calls on one state are serial, tad_job_progress finds the job by id. */
+#define TAD_FEATURE_STATE_WINDOW 64u  /* tad_run_state_window: tad_run_state over a time range / newest points of the state, read-only */
+int tad_run_state_window(tad_engine *e, tad_state *s, const tad_job *job, int64_t from_t, int64_t to_t,
+                         uint64_t keep_points, tad_mem out_memory, tad_result **out);
+/* the rule of DBSCAN's window history, the very function the call uses: 1 = the window's values are sorted, 0 = the excluded values are
+ * sorted and subtracted from the state's history.  Needs no device. */
+int tad_window_history_by_sort(uint64_t window_points, uint64_t state_points);
+
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).
  * tad_job_progress (ABI 12): the job whose tad_job.id equals `id`; *total = 0 when no such job is in flight (finished or not yet

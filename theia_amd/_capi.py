@@ -27,6 +27,7 @@ TAD_FEATURE_STREAM_TRIM = 8                  # tad_features() bit: TAD_STATE_TIM
 TAD_STATE_TIMES = 8                          # tad_state_create_ex flag (with TAD_STATE_SERIES): keep every series point's flowEndSeconds
 TAD_FEATURE_STATE_RUN = 16                   # tad_features() bit: tad_run_state, the batch job's rows over everything a state holds
 TAD_FEATURE_STATE_MERGE = 32                 # tad_features() bit: tad_state_merge, a batch placed by time (late, re-sent and split rows)
+TAD_FEATURE_STATE_WINDOW = 64                # tad_features() bit: tad_run_state_window, tad_run_state over a time range of the state, read-only
 
 
 class Plan(C.Structure):
@@ -148,6 +149,8 @@ SYMBOLS = {
     "tad_run_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_run_state": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_state_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), i64, C.POINTER(MergeStats)]),
+    "tad_run_state_window": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_int, C.POINTER(C.POINTER(Result))]),
+    "tad_window_history_by_sort": (C.c_int, [u64, u64]),
     "tad_aggregate": (C.c_int, [C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Points))]),
     "tad_points_free": (None, [C.c_void_p, C.POINTER(Points)]),
     "tad_shard_rows": (C.c_int, [C.c_void_p, C.POINTER(Columns), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -210,15 +210,31 @@ int stage_column(JobCtx *e, DevBuf &buf, const void *src, uint64_t n, tad_mem me
 
 size_t state_bytes(uint64_t K) { return (size_t)K * (4 + 8 * 4 + 1) + 64; }
 
-StreamState state_view(const tad_state *st, int which) {
-  unsigned char *b = static_cast<unsigned char *>(st->block[which]);
+// the arrays of K keys' running state inside one block of state_bytes(K) bytes
+StreamState stream_view(void *block, uint64_t K) {
+  unsigned char *b = static_cast<unsigned char *>(block);
   StreamState v;
   v.avg = reinterpret_cast<double *>(b);
-  v.m2 = v.avg + st->K;
-  v.ewma = v.m2 + st->K;
-  v.last_t = reinterpret_cast<long long *>(v.ewma + st->K);
-  v.n = reinterpret_cast<uint32_t *>(v.last_t + st->K);
-  v.seen = reinterpret_cast<unsigned char *>(v.n + st->K);
+  v.m2 = v.avg + K;
+  v.ewma = v.m2 + K;
+  v.last_t = reinterpret_cast<long long *>(v.ewma + K);
+  v.n = reinterpret_cast<uint32_t *>(v.last_t + K);
+  v.seen = reinterpret_cast<unsigned char *>(v.n + K);
+  return v;
+}
+
+StreamState state_view(const tad_state *st, int which) { return stream_view(st->block[which], st->K); }
+
+// copy `which` of a series state as the detectors of tad_run_state read it (the times and the history where the state has them)
+StateView series_view(const tad_state *st, int which) {
+  StateView v;
+  v.K = st->K;
+  v.P = st->ser_len[which];
+  v.soff = st->ser_off[which];
+  v.sval = st->ser_val[which];
+  v.st = st->times ? st->ser_t[which] : nullptr;
+  v.mom = state_view(st, which);
+  if (st->history) { v.hist_off = st->hist_off[which]; v.hist_val = st->hist_val[which]; }
   return v;
 }
 
@@ -471,7 +487,8 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
         unsigned long long *hmid = static_cast<unsigned long long *>(e->mg_hist.p);
         launch_hist_sort(s, hrem, rkoff, K, hrem_s, long_list, long_count);
         launch_scan(s, chunks_h, coff_h, K, scratch);
-        launch_hist_subtract(s, trim_chunks_bound(K, H), coff_h, K, st->hist_off[cur], st->hist_val[cur], rkoff, hrem_s, hoff_mid, hmid);
+        // (chunks_h gives an empty key no chunk: not the one-chunk-at-least counts of a trim)
+        launch_hist_subtract(s, trim_chunks_bound(K, H), coff_h, K, st->hist_off[cur], st->hist_val[cur], rkoff, hrem_s, hoff_mid, hmid, false);
         hoff_from = hoff_mid;
         hval_from = hmid;
       }
@@ -510,11 +527,12 @@ constexpr uint64_t kStreamFitWaves = 4096;   // k_arima_fit_list: wavefronts a b
 // One ARIMA batch on a series state (tad.h, TAD_STATE_SERIES), after stream_history_batch appended the new points to the candidate series:
 // the touched keys' Box-Cox fits over their whole series, the fits of the new points only, verdicts and the row count (tad_arima.hip).
 // Writes only workspace memory.  A batch whose Stage 0 or stream pass raised an error (a late row) runs no fit: the caller fails it.
-// which: the copy of the series and moments to read — the candidate for a batch; the current one for tad_run_state, whose HistBatch names
-// every series point as new (poff = the series offsets).
-int stream_arima_batch(JobCtx *e, const tad_state *st, int which, uint64_t K, const HistBatch &hb, const JobParams &jp, DevCounters *ctr, ArimaBatch *ab) {
+// v: the series and moments to read — the state's candidate copy for a batch; the current one, or a window's view, for tad_run_state /
+// tad_run_state_window, whose HistBatch names every series point as new (poff = the series offsets).
+int stream_arima_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const JobParams &jp, DevCounters *ctr, ArimaBatch *ab) {
   hipStream_t s = e->stream;
-  const unsigned long long *soff = st->ser_off[which], *sval = st->ser_val[which];
+  const uint64_t K = v.K;
+  const unsigned long long *soff = v.soff, *sval = v.sval;
   const size_t kpad = (size_t)((K + 3) & ~3ull);
   int rc;
   // per key: touched u32 | len8 u32 | tidx u64[K + 1] | yoffk u64[K + 1] | tmax; per slot: key u32 | lo u32 | hi u32 | ok u8 | yoff u64 | lam | sigma | ibase
@@ -561,7 +579,7 @@ int stream_arima_batch(JobCtx *e, const tad_state *st, int which, uint64_t K, co
   double *lx = static_cast<double *>(e->as_ser.p), *ysk = lx + ser;
   HIP_TRY(e, hipMemsetAsync(pflag, 0, P, s));
   HIP_TRY(e, hipMemsetAsync(ysk, 0, ser * 8, s));   // (the slack: finite values for idle lanes)
-  launch_as_prep(s, K, soff, sval, hb.poff, state_view(st, which), tidx, yoffk, lx, ysk, sl, pcalc, pflag, ctr);
+  launch_as_prep(s, K, soff, sval, hb.poff, v.mom, tidx, yoffk, lx, ysk, sl, pcalc, pflag, ctr);
   // the fits: counted per position, listed, their wavefronts laid out on the host (heaviest position first)
   const uint64_t npos = (uint64_t)tmax + 1;
   if ((rc = ensure(e, e->as_pos, npos * (4 + 8) + 128)) != TAD_OK) return rc;   // cnt u32[npos] | (64-byte aligned) loff u64[npos + 1]
@@ -614,14 +632,25 @@ int stream_arima_batch(JobCtx *e, const tad_state *st, int which, uint64_t K, co
   return TAD_OK;
 }
 
-// tad_run_state on the context the caller holds (tad.h; kernels: tad_window.hip).  Reads the CURRENT copies of the state only.  EWMA walks
-// the CSR series; DBSCAN and ARIMA run the stream's kernels with every series point named as new (poff = the series offsets).
-int run_state_locked(JobCtx *e, const tad_state *st, const tad_job *job, tad_mem out_memory, tad_result **out) {
+// the start of a tad_run_state / tad_run_state_window job on the context the caller holds: progress, the first event, the job tail zeroed
+int run_view_begin(JobCtx *e, uint64_t K) {
   HIP_TRY(e, hipSetDevice(e->device));
-  hipStream_t s = e->stream;
   e->done.store(0);
   e->total.store(4);
   e->arima_relaunches = 0;
+  int rc;
+  if ((rc = ensure_key_buffers(e, K)) != TAD_OK) return rc;
+  HIP_TRY(e, hipEventRecord(e->ev[0], e->stream));
+  HIP_TRY(e, hipMemsetAsync(e->counters.p, 0, kTailBytes, e->stream));
+  return TAD_OK;
+}
+
+// tad_run_state / tad_run_state_window after run_view_begin (tad.h; kernels: tad_window.hip).  Reads the view only: the state's CURRENT
+// copies, or a window's view in this context's workspace (wv_key / wv_pts, which nothing below resizes).  EWMA walks the CSR series;
+// DBSCAN and ARIMA run the stream's kernels with every series point named as new (poff = the series offsets).  view_syncs: the host
+// synchronisations the caller spent on building the view (tad_stats.host_syncs).
+int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem out_memory, tad_result **out, int view_syncs) {
+  hipStream_t s = e->stream;
   JobParams jp;
   jp.algo = job->algo;
   jp.alpha = job->ewma_alpha == 0.0 ? 0.5 : job->ewma_alpha;
@@ -631,18 +660,14 @@ int run_state_locked(JobCtx *e, const tad_state *st, const tad_job *job, tad_mem
   jp.drop_nsigma = 3.0;
   jp.drop_min_samples = 3;
   jp.all_points = (job->flags & TAD_FLAG_EMIT_ALL_POINTS) != 0;
-  const uint64_t K = st->K;
-  const int cur = st->cur;
-  const uint64_t P = st->ser_len[cur];
-  const unsigned long long *soff = st->ser_off[cur], *sval = st->ser_val[cur];
-  const long long *stt = st->ser_t[cur];
-  const StreamState view = state_view(st, cur);
+  const uint64_t K = v.K;
+  const uint64_t P = v.P;
+  const unsigned long long *soff = v.soff, *sval = v.sval;
+  const long long *stt = v.st;
+  const StreamState view = v.mom;
   int rc;
-  if ((rc = ensure_key_buffers(e, K)) != TAD_OK) return rc;
   DevCounters *ctr = static_cast<DevCounters *>(e->counters.p);
   unsigned long long *tmin_dev = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(e->counters.p) + kTailHistLen);
-  HIP_TRY(e, hipEventRecord(e->ev[0], s));
-  HIP_TRY(e, hipMemsetAsync(e->counters.p, 0, kTailBytes, s));
   uint64_t rows = 0;
   HistBatch hist;
   ArimaBatch ab;
@@ -679,10 +704,10 @@ int run_state_locked(JobCtx *e, const tad_state *st, const tad_job *job, tad_mem
         uint8_t *noise = static_cast<uint8_t *>(e->hs_noise.p);
         uint32_t *cnt = static_cast<uint32_t *>(e->hs_cnt.p);
         unsigned long long *row = static_cast<unsigned long long *>(e->hs_row.p);
-        launch_hist_verdict(s, nk, sval, hist.P_dev, P, st->hist_off[cur], st->hist_val[cur], jp.eps, jp.min_samples, jp.all_points, noise, cnt);
+        launch_hist_verdict(s, nk, sval, hist.P_dev, P, v.hist_off, v.hist_val, jp.eps, jp.min_samples, jp.all_points, noise, cnt);
         launch_scan(s, cnt, row, P, scratch, dev_total(e));
         hist.noise = noise; hist.cnt = cnt; hist.row = row;
-      } else if ((rc = stream_arima_batch(e, st, cur, K, hist, jp, ctr, &ab)) != TAD_OK) {
+      } else if ((rc = stream_arima_batch(e, v, hist, jp, ctr, &ab)) != TAD_OK) {
         return rc;
       }
     }
@@ -763,7 +788,7 @@ int run_state_locked(JobCtx *e, const tad_state *st, const tad_job *job, tad_mem
   }
   hipEventElapsedTime(&rs.ms_total, e->ev[0], e->ev[4]);
   rs.ms_detect = rs.ms_total;   // no Stage 0 ran: the whole call is the detector and its emit
-  rs.host_syncs = 2;
+  rs.host_syncs = 2 + view_syncs;
   rs.job_context = e->index;
   rs.arima_relaunches = e->arima_relaunches;
   strncpy(rp->pub.id, job->id, sizeof rp->pub.id - 1);
@@ -1277,7 +1302,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       if (!e->merge && (stream->history || stream->series) && g.K &&
           (rc = stream_history_batch(e, stream, g, L, stream_poff, stream_P, (slots_all < cells ? slots_all : cells), jp, &hist)) != TAD_OK)
         return rc;
-      if (jp.algo == TAD_ALGO_ARIMA && g.K && (rc = stream_arima_batch(e, stream, stream->cur ^ 1, g.K, hist, jp, ctr, &ab)) != TAD_OK) return rc;
+      if (jp.algo == TAD_ALGO_ARIMA && g.K && (rc = stream_arima_batch(e, series_view(stream, stream->cur ^ 1), hist, jp, ctr, &ab)) != TAD_OK) return rc;
       if (jp.algo == TAD_ALGO_EWMA && !e->merge)   // (a DBSCAN / ARIMA batch counted its rows in stream_history_batch / stream_arima_batch)
         launch_scan(s, static_cast<const uint32_t *>(e->n_anom.p), off, g.K, static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
       HIP_TRY(e, hipMemcpyAsync(e->tail_host, e->counters.p, kTailBytes, hipMemcpyDeviceToHost, s));
@@ -2208,7 +2233,7 @@ int tad_state_trim(tad_engine *eng, tad_state *st, uint64_t keep_points, int64_t
   if (st->history) {
     HIP_TRY(e, hipMemcpyAsync(st->hist_off[cand], st->ser_off[cand], (K + 1) * 8, hipMemcpyDeviceToDevice, s));
     launch_hist_sort(s, ev, eoff, K, es, chunks, long_count);
-    launch_hist_subtract(s, bound, coff, K, st->hist_off[cur], st->hist_val[cur], eoff, es, st->hist_off[cand], st->hist_val[cand]);
+    launch_hist_subtract(s, bound, coff, K, st->hist_off[cur], st->hist_val[cur], eoff, es, st->hist_off[cand], st->hist_val[cand], true);
   }
   launch_trim_moments(s, K, rcnt, ecnt, st->ser_off[cand], st->ser_val[cand], alpha, state_view(st, cur), state_view(st, cand));
   HIP_TRY(e, hipGetLastError());
@@ -2224,28 +2249,114 @@ int tad_state_trim(tad_engine *eng, tad_state *st, uint64_t keep_points, int64_t
   return TAD_OK;
 }
 
-int tad_run_state(tad_engine *eng, tad_state *st, const tad_job *job, tad_mem out_memory, tad_result **out) {
-  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: engine is NULL");
-  if (!st || !job || !out) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: state, job and out must not be NULL");
+// what tad_run_state and tad_run_state_window refuse before they take the state's lock (who: the call's name for the message)
+static int check_state_job(tad_engine *eng, const tad_state *st, const tad_job *job, tad_result **out, const char *who, const char *narrow) {
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!st || !job || !out) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: state, job and out must not be NULL", who);
   *out = nullptr;
   if (job->algo != TAD_ALGO_EWMA && job->algo != TAD_ALGO_DBSCAN && job->algo != TAD_ALGO_ARIMA)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: the algorithm must be EWMA, DBSCAN or ARIMA (DROP has no streaming form)");
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the algorithm must be EWMA, DBSCAN or ARIMA (DROP has no streaming form)", who);
   if (job->start_time != 0 || job->end_time != 0)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: start_time / end_time must be 0: the window is what the state holds (tad_state_trim narrows it)");
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: start_time / end_time must be 0: %s", who, narrow);
   if (job->flags & (TAD_FLAG_KEY_U32 | TAD_FLAG_TIME_U32))
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 describe input columns; there are none");
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 describe input columns; there are none", who);
   if (job->ewma_alpha < 0.0 || job->ewma_alpha > 1.0 || job->dbscan_eps < 0.0 || job->dbscan_min_samples < 0 || job->arima_maxiter < 0)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: detector parameter out of range");
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: detector parameter out of range", who);
   if (!st->series || !st->times)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES)");
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES)", who);
   if (job->algo == TAD_ALGO_DBSCAN && !st->history)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: DBSCAN needs a state with history too (TAD_STATE_HISTORY)");
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: DBSCAN needs a state with history too (TAD_STATE_HISTORY)", who);
+  return TAD_OK;
+}
+
+int tad_run_state(tad_engine *eng, tad_state *st, const tad_job *job, tad_mem out_memory, tad_result **out) {
+  int rc = check_state_job(eng, st, job, out, "tad_run_state", "the window is what the state holds (tad_state_trim narrows it)");
+  if (rc != TAD_OK) return rc;
   std::lock_guard<std::mutex> state_lk(st->mu);   // (the order of tad_run_stream: the state, then a job context)
   if (st->times_stale)
     return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: the series was imported without its times (tad_state_import_times)");
   Lease lease(eng, job->id, job->algo == TAD_ALGO_ARIMA);
   if (!lease.c) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_run_state: no job context available");
-  return run_state_locked(lease.c, st, job, out_memory, out);
+  if ((rc = run_view_begin(lease.c, st->K)) != TAD_OK) return rc;
+  return run_view_locked(lease.c, series_view(st, st->cur), job, out_memory, out, 0);
+}
+
+int tad_window_history_by_sort(uint64_t window_points, uint64_t state_points) { return win_hist_by_sort(window_points, state_points) ? 1 : 0; }
+
+// tad.h: the view of the window in the context's workspace (kernels: tad_window.hip), then tad_run_state's path on it.  Reads the state's
+// CURRENT copies and writes workspace only.  wv_key and wv_pts hold the view; run_view_locked resizes neither.
+int tad_run_state_window(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, tad_mem out_memory,
+                         tad_result **out) {
+  int rc = check_state_job(eng, st, job, out, "tad_run_state_window", "the window is from_t / to_t / keep_points");
+  if (rc != TAD_OK) return rc;
+  if (from_t != 0 && to_t != 0 && from_t > to_t)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state_window: from_t is later than to_t");
+  std::lock_guard<std::mutex> state_lk(st->mu);   // (the order of tad_run_state: the state, then a job context)
+  if (st->times_stale)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state_window: the series was imported without its times (tad_state_import_times)");
+  Lease lease(eng, job->id, job->algo == TAD_ALGO_ARIMA);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_run_state_window: no job context available");
+  const uint64_t K = st->K;
+  if ((rc = run_view_begin(e, K)) != TAD_OK) return rc;
+  const StateView whole = series_view(st, st->cur);
+  const uint64_t S = whole.P;
+  if (S == 0 || (from_t == 0 && to_t == 0 && keep_points == 0)) return run_view_locked(e, whole, job, out_memory, out, 0);
+  hipStream_t s = e->stream;
+  // per key: wbeg | wlen | ecnt | chunks (later the long-sort list) u32 each | the list's length | woff | coff | eoff u64[K + 1] each | moments
+  const size_t kpad = (size_t)((K + 3) & ~3ull);
+  const size_t key_bytes = kpad * 16 + 64 + (kpad + 4) * 24;
+  if ((rc = ensure(e, e->wv_key, key_bytes + state_bytes(K))) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K) * sizeof(unsigned long long))) != TAD_OK) return rc;
+  uint32_t *wbeg = static_cast<uint32_t *>(e->wv_key.p), *wlen = wbeg + kpad, *ecnt = wlen + kpad, *chunks = ecnt + kpad;
+  unsigned int *long_count = reinterpret_cast<unsigned int *>(chunks + kpad);
+  unsigned long long *woff = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(long_count) + 64);
+  unsigned long long *coff = woff + kpad + 4, *eoff = coff + kpad + 4;
+  const StreamState wmom = stream_view(static_cast<unsigned char *>(e->wv_key.p) + key_bytes, K);
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  // 1. every key's bounds; the view's offsets and the chunk offsets; the window's point total
+  launch_win_bounds(s, K, whole.soff, whole.st, (long long)from_t, (long long)to_t, keep_points, wbeg, wlen, ecnt, chunks);
+  launch_scan(s, wlen, woff, K, scratch);
+  launch_scan(s, chunks, coff, K, scratch);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipMemcpyAsync(e->tail_host + kTailTotal, woff + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  const uint64_t P = *e->total_host;
+  if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1);   // every key is whole: the state's own arrays, no view
+  StateView v;
+  v.K = K;
+  v.P = P;
+  if (P != 0) {
+    // 2. the window's values and times (DBSCAN on the subtract side: the excluded values too); 3. the moments; 4. DBSCAN's history
+    const bool dbscan = job->algo == TAD_ALGO_DBSCAN;
+    const bool subtract = dbscan && !win_hist_by_sort(P, S);
+    if ((rc = ensure(e, e->wv_pts, P * (dbscan ? 24 : 16))) != TAD_OK) return rc;
+    unsigned long long *wval = static_cast<unsigned long long *>(e->wv_pts.p);
+    long long *wt = reinterpret_cast<long long *>(wval + P);
+    unsigned long long *wh = wval + 2 * P, *ev = nullptr, *es = nullptr;
+    if (subtract) {
+      if ((rc = ensure(e, e->hs_val, (S - P) * 8)) != TAD_OK) return rc;
+      if ((rc = ensure(e, e->hs_sorted, (S - P) * 8)) != TAD_OK) return rc;
+      ev = static_cast<unsigned long long *>(e->hs_val.p);
+      es = static_cast<unsigned long long *>(e->hs_sorted.p);
+      launch_scan(s, ecnt, eoff, K, scratch);
+    }
+    const uint64_t bound = trim_chunks_bound(K, S);
+    launch_win_gather(s, bound, coff, K, whole.soff, whole.sval, whole.st, wbeg, woff, wval, wt, eoff, ev);
+    const double alpha = job->ewma_alpha == 0.0 ? 0.5 : job->ewma_alpha;   // (for the view's ewma only, which no detector reads)
+    launch_trim_moments(s, K, wlen, ecnt, woff, wval, alpha, whole.mom, wmom);
+    if (subtract) {
+      launch_hist_sort(s, ev, eoff, K, es, chunks, long_count);
+      launch_hist_subtract(s, bound, coff, K, whole.hist_off, whole.hist_val, eoff, es, woff, wh, true);
+    } else if (dbscan) {
+      launch_hist_sort(s, wval, woff, K, wh, chunks, long_count);
+    }
+    HIP_TRY(e, hipGetLastError());
+    v.soff = woff; v.sval = wval; v.st = wt; v.mom = wmom;
+    if (dbscan) { v.hist_off = woff; v.hist_val = wh; }
+  }
+  e->done.store(1);
+  return run_view_locked(e, v, job, out_memory, out, 1);
 }
 
 // tad.h: a batch placed by time.  The batch runs as a stream batch does up to the end of Stage 0 (run_job_locked with the context's merge

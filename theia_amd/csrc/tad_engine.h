@@ -94,6 +94,7 @@ struct JobCtx {
   DevBuf sp_comp_a, sp_comp_b, sp_val_a, sp_val_b, sp_temp, sp_first, sp_times;  // Stage 0 sparse (sort + rank grid)
   DevBuf sp_cls;                                                                  // Stage 0 sparse, length classes: per-key class arrays
   DevBuf hs_key, hs_t, hs_val, hs_sorted, hs_noise, hs_cnt, hs_row, hs_koff, hs_kcnt;   // a history batch: new points, sorted values, verdicts, rows, offsets
+  DevBuf wv_key, wv_pts;   // tad_run_state_window's view: per key (bounds, offsets, moments) | per window point (values, times, sorted values)
   DevBuf mg_pts, mg_keys, mg_hist;   // tad_state_merge: per batch point | per key | the history between its subtract and its merge
   struct MergeCall *merge = nullptr;   // set while the context runs a tad_state_merge batch (run_job_locked's merge mode)
   DevBuf as_key, as_pt, as_ser, as_fit, as_pos, as_ws;   // a stream ARIMA batch: per key | per new point | packed series | per fit | per position | fit workspace
@@ -224,6 +225,7 @@ template <typename F> void for_each_buf(JobCtx *c, F f) {
                     &c->in_key, &c->in_key2, &c->in_te, &c->in_ts, &c->in_val,
                     &c->hs_key, &c->hs_t, &c->hs_val, &c->hs_sorted, &c->hs_noise, &c->hs_cnt, &c->hs_row, &c->hs_koff, &c->hs_kcnt,
                     &c->mg_pts, &c->mg_keys, &c->mg_hist,
+                    &c->wv_key, &c->wv_pts,
                     &c->as_key, &c->as_pt, &c->as_ser, &c->as_fit, &c->as_pos, &c->as_ws};
   for (DevBuf *b : bufs) f(*b);
 }

@@ -23,7 +23,6 @@ namespace tad {
 static constexpr int kHBlock = 256;
 static constexpr int kHWaves = kHBlock / 64;
 static constexpr uint32_t kHistLdsPoints = 4096;   // k_hist_sort_long: segments up to this many points sort in LDS (32 KB)
-static constexpr uint32_t kHistChunk = 2048;       // k_hist_merge: elements per wavefront (32 per lane)
 
 // ---- 1. the sparse batch's sorted unique points (comp = key << 32 | (t - t0)) as key / time columns ----
 __global__ __launch_bounds__(kHBlock) void k_hist_decode(const unsigned long long *__restrict__ comp, uint64_t P, int64_t t0,
@@ -338,14 +337,7 @@ __global__ __launch_bounds__(kHBlock) void k_trim_keep(uint64_t K, const unsigne
   if (keep_points && r > keep_points) r = keep_points;
   rcnt[k] = (uint32_t)r;
   ecnt[k] = (uint32_t)(len - r);
-  chunks[k] = (uint32_t)((len + kHistChunk - 1) / kHistChunk);
-}
-
-// the key of wavefront w from the chunk offsets (wavefront-uniform): the last k with coff[k] <= w
-__device__ __forceinline__ uint64_t chunk_key(const unsigned long long *coff, uint64_t K, unsigned long long w) {
-  uint64_t lo = 0, hi = K;
-  while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (coff[mid] <= w) lo = mid; else hi = mid; }
-  return lo;
+  chunks[k] = len > kHistChunk ? (uint32_t)((len + kHistChunk - 1) / kHistChunk) : 1u;   // (an empty key too: see chunk_key_min1)
 }
 
 // One wavefront per chunk of a key's OLD segment: element u < e goes to the packed evicted values (ev at eoff[k], history states only),
@@ -358,7 +350,7 @@ __global__ __launch_bounds__(kHBlock) void k_trim_copy(const unsigned long long 
   const unsigned long long w = ((uint64_t)blockIdx.x * kHBlock + threadIdx.x) >> 6;
   if (w >= coff[K]) return;
   const unsigned lane = threadIdx.x & 63u;
-  const uint64_t k = chunk_key(coff, K, w);
+  const uint64_t k = chunk_key_min1(coff, K, w);   // (coff: the scan of k_trim_keep's chunks)
   const unsigned long long o0 = soff_old[k], len = soff_old[k + 1] - o0;
   const unsigned long long d0 = soff_new[k], e = len - (soff_new[k + 1] - d0);
   const unsigned long long c0 = (w - coff[k]) * kHistChunk;
@@ -376,7 +368,9 @@ __global__ __launch_bounds__(kHBlock) void k_trim_copy(const unsigned long long 
 }
 
 // One wavefront per chunk of a key's old history (the chunks of its series: the same length); es = the key's evicted values sorted at
-// [eoff[k], eoff[k + 1]); hoff_new = the candidate series offsets (retained history = retained series, key by key).
+// [eoff[k], eoff[k + 1]); hoff_new = the candidate series offsets (retained history = retained series, key by key).  kMin1: the chunk
+// counts give every key at least one chunk (a trim's, a window's; not a merge's, whose empty keys have none): see chunk_key_min1.
+template <bool kMin1>
 __global__ __launch_bounds__(kHBlock) void k_hist_subtract(const unsigned long long *__restrict__ coff, uint64_t K,
                                                           const unsigned long long *__restrict__ hoff_old, const unsigned long long *__restrict__ hval_old,
                                                           const unsigned long long *__restrict__ eoff, const unsigned long long *__restrict__ es,
@@ -384,7 +378,7 @@ __global__ __launch_bounds__(kHBlock) void k_hist_subtract(const unsigned long l
   const unsigned long long w = ((uint64_t)blockIdx.x * kHBlock + threadIdx.x) >> 6;
   if (w >= coff[K]) return;
   const unsigned lane = threadIdx.x & 63u;
-  const uint64_t k = chunk_key(coff, K, w);
+  const uint64_t k = kMin1 ? chunk_key_min1(coff, K, w) : chunk_key(coff, K, w);
   const unsigned long long o0 = hoff_old[k], len = hoff_old[k + 1] - o0;
   const unsigned long long e0 = eoff[k], e1 = eoff[k + 1];
   unsigned long long *dst = hval_new + hoff_new[k];
@@ -395,13 +389,15 @@ __global__ __launch_bounds__(kHBlock) void k_hist_subtract(const unsigned long l
   for (unsigned long long i = c0 + lane; i < c1; i += 64) {
     const unsigned long long v = hval_old[o0 + i];
     if (e0 == e1) { dst[i] = v; continue; }   // the key lost nothing: a coalesced copy
-    const unsigned long long r = i - (lower_u64(hval_old, o0, o0 + len, v) - o0);
+    // the evicted list first: most elements have no evicted copy (c == 0: kept, whatever the rank) and skip the search for their rank
     const unsigned long long lt = lower_u64(es, e0, e1, v), c = upper_u64(es, lt, e1, v) - lt;
+    const unsigned long long r = c == 0 ? 0ull : i - (lower_u64(hval_old, o0, o0 + len, v) - o0);
     const unsigned long long drop = (lt - e0) + c;   // (min(r, c) = c for a kept element)
     if (r >= c && i >= drop && i - drop < rlen) dst[i - drop] = v;   // (the bounds hold whenever the evicted values are in the history)
   }
 }
 
+static constexpr int kTrimChunk = 8;   // points per prefetched register chunk of k_trim_moments (64 B of values)
 // One lane per key: the candidate moments.  The retained values are read from the candidate series (written by k_trim_copy);
 // last_t stays: a key that keeps a point keeps its newest one.
 __global__ __launch_bounds__(kHBlock) void k_trim_moments(uint64_t K, const uint32_t *__restrict__ rcnt, const uint32_t *__restrict__ ecnt,
@@ -414,11 +410,34 @@ __global__ __launch_bounds__(kHBlock) void k_trim_moments(uint64_t K, const uint
   if (ecnt[k] != 0) {
     const long long last_t = a.last_t;
     a = StreamAcc{0u, 0.0, 0.0, 0.0, 0.0, 0ll, false};
-    const double one_minus = 1.0 - alpha;
-    const unsigned long long p0 = soff_new[k];
-    for (uint32_t i = 0; i < r; ++i) {
-      double sg;
-      (void)stream_step(a, alpha, one_minus, (double)sval_new[p0 + i], last_t, &sg);
+    if (r != 0) {
+      // the values in chunks of kTrimChunk, prefetched two ahead (k_win_ewma's scheme): the loads do not wait for the FP64 chain
+      const double one_minus = 1.0 - alpha;
+      const unsigned long long p0 = soff_new[k], len = r;
+      const unsigned long long nch = (len + kTrimChunk - 1) / kTrimChunk;
+      unsigned long long va[kTrimChunk], vb[kTrimChunk];
+      auto load = [&](unsigned long long c, unsigned long long *v) {   // (an index past the end re-reads the last point: in bounds)
+#pragma unroll
+        for (int u = 0; u < kTrimChunk; ++u) {
+          const unsigned long long i = c * kTrimChunk + u;
+          v[u] = sval_new[p0 + (i < len ? i : len - 1)];
+        }
+      };
+      auto consume = [&](unsigned long long c, const unsigned long long *v) {
+#pragma unroll
+        for (int u = 0; u < kTrimChunk; ++u) {
+          if (c * kTrimChunk + u >= len) break;
+          double sg;
+          (void)stream_step(a, alpha, one_minus, (double)v[u], last_t, &sg);
+        }
+      };
+      load(0, va);
+      for (unsigned long long c = 0; c < nch; c += 2) {
+        load(c + 1 < nch ? c + 1 : c, vb);
+        consume(c, va);
+        load(c + 2 < nch ? c + 2 : nch - 1, va);
+        if (c + 1 < nch) consume(c + 1, vb);
+      }
     }
   }
   stream_store(next, k, a);
@@ -442,10 +461,11 @@ void launch_trim_copy(hipStream_t s, uint64_t chunks_bound, const unsigned long 
 
 void launch_hist_subtract(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *hoff_old,
                           const unsigned long long *hval_old, const unsigned long long *eoff, const unsigned long long *es,
-                          const unsigned long long *hoff_new, unsigned long long *hval_new) {
+                          const unsigned long long *hoff_new, unsigned long long *hval_new, bool chunks_min1) {
   if (K == 0) return;
-  hipLaunchKernelGGL(k_hist_subtract, dim3(hist_blocks(chunks_bound * 64)), dim3(kHBlock), 0, s, coff, K, hoff_old, hval_old, eoff, es, hoff_new,
-                     hval_new);
+  const dim3 grid(hist_blocks(chunks_bound * 64)), block(kHBlock);
+  if (chunks_min1) hipLaunchKernelGGL(k_hist_subtract<true>, grid, block, 0, s, coff, K, hoff_old, hval_old, eoff, es, hoff_new, hval_new);
+  else hipLaunchKernelGGL(k_hist_subtract<false>, grid, block, 0, s, coff, K, hoff_old, hval_old, eoff, es, hoff_new, hval_new);
 }
 
 void launch_trim_moments(hipStream_t s, uint64_t K, const uint32_t *rcnt, const uint32_t *ecnt, const unsigned long long *soff_new,

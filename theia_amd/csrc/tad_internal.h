@@ -320,6 +320,24 @@ void launch_hist_decode(hipStream_t s, const unsigned long long *comp, uint64_t 
 // ns = nv sorted ascending within every key's segment [poff[k], poff[k + 1]); long_list: K entries, long_count: one device word
 void launch_hist_sort(hipStream_t s, const unsigned long long *nv, const unsigned long long *poff, uint64_t K, unsigned long long *ns,
                       uint32_t *long_list, unsigned int *long_count);
+// elements per wavefront of the chunked kernels (k_hist_merge, k_trim_copy, k_hist_subtract, k_win_gather): 32 per lane
+static constexpr uint32_t kHistChunk = 2048;
+#if defined(__HIPCC__)
+// the key of wavefront w from the chunk offsets coff = the scan of the keys' chunk counts (wavefront-uniform): the last k with coff[k] <= w.
+// Counts of 0 are allowed: a key without chunks has coff[k] == coff[k + 1] and is never the last one
+__device__ __forceinline__ uint64_t chunk_key(const unsigned long long *coff, uint64_t K, unsigned long long w) {
+  uint64_t lo = 0, hi = K;
+  while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (coff[mid] <= w) lo = mid; else hi = mid; }
+  return lo;
+}
+// The same, ONLY for chunk counts that give every key at least one chunk, an empty key included (k_trim_keep's and k_win_bounds').  Then
+// coff[K] == K means one chunk each, wavefront w IS key w, and the search (20 dependent loads at 1e6 keys) is skipped: the common case of
+// keys shorter than a chunk.  With a count of 0 anywhere (k_merge_keys' history chunks, k_hist_merge's) coff[K] == K can hold with a key
+// of several chunks, and the shortcut would hand wavefronts the wrong key: those callers take chunk_key
+__device__ __forceinline__ uint64_t chunk_key_min1(const unsigned long long *coff, uint64_t K, unsigned long long w) {
+  return coff[K] == K ? w : chunk_key(coff, K, w);
+}
+#endif
 // upper bound of k_hist_merge's wavefronts for K keys and total_len merged values
 uint64_t hist_merge_chunks_bound(uint64_t K, uint64_t total_len);
 // hoff_new = hoff_old + poff; hval_new = every key's old and new (ns) values merged; chunks u32[K], coff u64[K + 1] and scan_scratch
@@ -405,10 +423,12 @@ uint64_t trim_chunks_bound(uint64_t K, uint64_t total_len);
 void launch_trim_copy(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *soff_old,
                       const unsigned long long *sval_old, const long long *st_old, const unsigned long long *soff_new, unsigned long long *sval_new,
                       long long *st_new, const unsigned long long *eoff, unsigned long long *ev);
-// the history without every key's evicted values (es, sorted per key at eoff)
+// the history without every key's evicted values (es, sorted per key at eoff).  coff = the scan of the keys' chunk counts, ceil(history
+// length / kHistChunk) for every key longer than a chunk.  chunks_min1: every other key has exactly one chunk, an empty key too
+// (launch_trim_keep's and launch_win_bounds' counts); false: an empty key may have none (launch_merge_keys' chunks_h)
 void launch_hist_subtract(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *hoff_old,
                           const unsigned long long *hval_old, const unsigned long long *eoff, const unsigned long long *es,
-                          const unsigned long long *hoff_new, unsigned long long *hval_new);
+                          const unsigned long long *hoff_new, unsigned long long *hval_new, bool chunks_min1);
 // next = cur for the keys that lost nothing; the others replayed with stream_step over their retained values (unseen if none)
 void launch_trim_moments(hipStream_t s, uint64_t K, const uint32_t *rcnt, const uint32_t *ecnt, const unsigned long long *soff_new,
                          const unsigned long long *sval_new, double alpha, StreamState cur, StreamState next);
@@ -426,6 +446,31 @@ void launch_win_ewma(hipStream_t s, uint64_t K, const unsigned long long *soff, 
                      int ewma_emit = 0, uint32_t ewma_emit_rows = 0);   // tad_plan: 1 = the lanes store their rows themselves; LDS rows per wavefront of the staged emit
 // nk[i] = the key of series point i
 void launch_win_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, unsigned long long *nk);
+// What tad_run_state's kernels read: K keys holding P points, key k's values and times in time order at [soff[k], soff[k + 1]), the
+// moments of those points and, for DBSCAN, the same values sorted per key at hist_off / hist_val.  tad_run_state passes the state's
+// current copies; tad_run_state_window passes the view it built in context workspace.
+struct StateView {
+  uint64_t K = 0, P = 0;
+  const unsigned long long *soff = nullptr, *sval = nullptr;
+  const long long *st = nullptr;
+  StreamState mom{};   // n, avg, m2 of the view's points.  In a WINDOW's view ewma is replayed with the job's alpha and last_t is the
+                       // state's, not the window's newest time: the detectors of run_view_locked read neither, a stream-style kernel must not
+  const unsigned long long *hist_off = nullptr, *hist_val = nullptr;
+};
+// ---- tad_run_state_window (tad_window.hip): the view of every key's points inside a window ----
+// per key: wbeg = the window's first point inside the key's segment, wlen = its points, ecnt = the key's points outside it (prefix +
+// suffix), chunks = the wavefronts of the key's old segment in launch_win_gather / launch_hist_subtract (at least 1).  from_t / to_t 0 = no bound on
+// that side (flow_end_s >= from_t, < to_t); keep_points 0 = no count rule, else the newest keep_points of the rest
+void launch_win_bounds(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, long long from_t, long long to_t,
+                       uint64_t keep_points, uint32_t *wbeg, uint32_t *wlen, uint32_t *ecnt, uint32_t *chunks);
+// every key's window values and times to woff (the scan of wlen); ev != NULL: the excluded values, prefix then suffix, packed at eoff
+// (the scan of ecnt).  chunks_bound: trim_chunks_bound(K, the state's points)
+void launch_win_gather(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *soff,
+                       const unsigned long long *sval, const long long *st, const uint32_t *wbeg, const unsigned long long *woff,
+                       unsigned long long *wval, long long *wt, const unsigned long long *eoff, unsigned long long *ev);
+// DBSCAN's window history: true = sort the window's values per key, false = sort the excluded values and subtract them from the state's
+// history.  A pure function of the two totals: 2 * window_points <= state_points
+bool win_hist_by_sort(uint64_t window_points, uint64_t state_points);
 // ---- tad_state_merge (tad_merge.hip): a batch's points nk / nt / nv (key k's at [poff[k], poff[k + 1])) placed by time ----
 struct MergeCounters {   // one 64-byte block on the device, zeroed per attempt
   unsigned long long too_old, appended, inserted, combined, keys_touched, keys_replayed, pad[2];

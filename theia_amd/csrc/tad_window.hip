@@ -274,6 +274,77 @@ __global__ __launch_bounds__(kWBlock) void k_win_keys(uint64_t K, const unsigned
   for (unsigned long long i = soff[k] + (threadIdx.x & 63u); i < p1; i += 64) nk[i] = k;
 }
 
+// ---- tad_run_state_window: a transient view of every key's points inside a window (include/tad.h) ----
+// The window keeps an INTERIOR range of every key's series — the points with from_t <= t < to_t, then the newest keep_points of those —
+// where tad_state_trim keeps a suffix.  The view is what a state trimmed to the window would hold, built in context workspace and never
+// in the state: CSR offsets woff[K + 1], values wval[] and times wt[], window moments, and for DBSCAN the window's values sorted per key.
+// The kernels above and the stream's DBSCAN / ARIMA kernels then run on the view unchanged.
+//   1. k_win_bounds, one lane per key: two lower-bound searches in the key's times [soff[k], soff[k + 1]) for from_t and to_t, then the
+//      count rule.  Per key: the window's first point (relative to the segment), its length, the excluded count (prefix + suffix) and
+//      the wavefronts of the copy (the key's OLD segment in chunks of kHistChunk: k_hist_subtract walks the history by the same chunks).
+//      The scan of the lengths is woff, and woff[K] the window's point total; the excluded total is the state's points minus that.
+//      Traffic: 16 B of offsets and 16 B of results per key, plus 2 x log2(len) dependent 8-byte loads.
+//   2. k_win_gather, one wavefront per chunk, lanes on consecutive points (coalesced 8-byte loads and stores): the interior range of
+//      values and times to woff[k]; with `ev` the excluded values, prefix then suffix, packed at eoff[k].  Without `ev` a wavefront
+//      touches only its part of the interior range.  Model: 32 B per window point (value and time, read and written) plus 16 B per
+//      packed excluded value (read and written; the issue's model counts the write alone).
+//   3. the moments: launch_trim_moments with rcnt = the window lengths, ecnt = the excluded counts, the view's series as the "new" one:
+//      a cut key is replayed from the zero state with stream_step, a whole key takes the state's moments, a key left empty is unseen.
+//      The replay is one lane's serial chain as long as the cut key's window, as for a trim (k_trim_moments prefetches the values).
+//   4. DBSCAN's window history, one rule per call (win_hist_by_sort): sort the window's values per key (launch_hist_sort over wval /
+//      woff), or sort the packed excluded values and remove them from the state's history (launch_hist_subtract).  Same bits either way:
+//      both are the sorted multiset of the key's window values.
+// No kernel here reads a series slot outside [soff[k], soff[k + 1]) or writes anything but the workspace arrays it is handed.
+__device__ __forceinline__ unsigned long long win_lower_t(const long long *__restrict__ st, unsigned long long lo, unsigned long long hi, long long t) {
+  while (lo < hi) { const unsigned long long mid = lo + ((hi - lo) >> 1); if (st[mid] < t) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+
+__global__ __launch_bounds__(kWBlock) void k_win_bounds(uint64_t K, const unsigned long long *__restrict__ soff, const long long *__restrict__ st,
+                                                       long long from_t, long long to_t, uint64_t keep_points, uint32_t *__restrict__ wbeg,
+                                                       uint32_t *__restrict__ wlen, uint32_t *__restrict__ ecnt, uint32_t *__restrict__ chunks) {
+  const uint64_t k = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
+  if (k >= K) return;
+  const unsigned long long o0 = soff[k], o1 = soff[k + 1], len = o1 - o0;
+  unsigned long long lo = from_t != 0 ? win_lower_t(st, o0, o1, from_t) - o0 : 0ull;          // the first point at or after from_t
+  const unsigned long long hi = to_t != 0 ? win_lower_t(st, o0 + lo, o1, to_t) - o0 : len;     // the first point at or after to_t (>= lo)
+  if (keep_points != 0 && hi - lo > keep_points) lo = hi - keep_points;
+  wbeg[k] = (uint32_t)lo;
+  wlen[k] = (uint32_t)(hi - lo);
+  ecnt[k] = (uint32_t)(len - (hi - lo));
+  chunks[k] = len > kHistChunk ? (uint32_t)((len + kHistChunk - 1) / kHistChunk) : 1u;   // (an empty key too: see chunk_key_min1)
+}
+
+__global__ __launch_bounds__(kWBlock) void k_win_gather(const unsigned long long *__restrict__ coff, uint64_t K, const unsigned long long *__restrict__ soff,
+                                                       const unsigned long long *__restrict__ sval, const long long *__restrict__ st,
+                                                       const uint32_t *__restrict__ wbeg, const unsigned long long *__restrict__ woff,
+                                                       unsigned long long *__restrict__ wval, long long *__restrict__ wt,
+                                                       const unsigned long long *__restrict__ eoff, unsigned long long *__restrict__ ev) {
+  const unsigned long long w = ((uint64_t)blockIdx.x * kWBlock + threadIdx.x) >> 6;
+  if (w >= coff[K]) return;
+  const unsigned lane = threadIdx.x & 63u;
+  const uint64_t k = chunk_key_min1(coff, K, w);   // (coff: the scan of k_win_bounds' chunks, at least one for every key)
+  const unsigned long long o0 = soff[k], len = soff[k + 1] - o0;
+  const unsigned long long d0 = woff[k], n = woff[k + 1] - d0;
+  const unsigned long long b = wbeg[k], be = b + n;   // the interior range [b, be) of the segment
+  unsigned long long c0 = (w - coff[k]) * kHistChunk, c1 = c0 + kHistChunk;
+  if (c1 > len) c1 = len;
+  if (!ev) {   // only the interior part of this chunk
+    if (c0 < b) c0 = b;
+    if (c1 > be) c1 = be;
+  }
+  const unsigned long long e0 = ev ? eoff[k] : 0ull;
+  for (unsigned long long u = c0 + lane; u < c1; u += 64) {
+    const unsigned long long x = sval[o0 + u];
+    if (u >= b && u < be) {
+      wval[d0 + u - b] = x;
+      wt[d0 + u - b] = st[o0 + u];
+    } else {
+      ev[e0 + (u < b ? u : u - n)] = x;   // (reached with ev only: without it the loop stays inside [b, be))
+    }
+  }
+}
+
 // ---- launchers ----
 static inline unsigned win_blocks(uint64_t lanes) { return (unsigned)((lanes + kWBlock - 1) / kWBlock); }
 
@@ -335,6 +406,29 @@ void launch_win_ewma(hipStream_t s, uint64_t K, const unsigned long long *soff, 
 void launch_win_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, unsigned long long *nk) {
   if (K == 0) return;
   hipLaunchKernelGGL(k_win_keys, dim3(win_blocks(K * 64)), dim3(kWBlock), 0, s, K, soff, nk);
+}
+
+// TAD_WIN_HIST_FORCE (measurement builds of tools/build_variants.py only; the product's build() never defines it): 1 = always sort the
+// window, 2 = always subtract
+bool win_hist_by_sort(uint64_t window_points, uint64_t state_points) {
+#if defined(TAD_WIN_HIST_FORCE)
+  return TAD_WIN_HIST_FORCE == 1;
+#else
+  return 2 * window_points <= state_points;
+#endif
+}
+
+void launch_win_bounds(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, long long from_t, long long to_t,
+                       uint64_t keep_points, uint32_t *wbeg, uint32_t *wlen, uint32_t *ecnt, uint32_t *chunks) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_win_bounds, dim3(win_blocks(K)), dim3(kWBlock), 0, s, K, soff, st, from_t, to_t, keep_points, wbeg, wlen, ecnt, chunks);
+}
+
+void launch_win_gather(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *soff,
+                       const unsigned long long *sval, const long long *st, const uint32_t *wbeg, const unsigned long long *woff,
+                       unsigned long long *wval, long long *wt, const unsigned long long *eoff, unsigned long long *ev) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_win_gather, dim3(win_blocks(chunks_bound * 64)), dim3(kWBlock), 0, s, coff, K, soff, sval, st, wbeg, woff, wval, wt, eoff, ev);
 }
 
 const void *code_anchor_window() { return reinterpret_cast<const void *>(&k_win_route); }

@@ -630,6 +630,23 @@ class TadEngine:
         self._check(rc)
         return TadResult(self, res)
 
+    def run_state_window(self, state, from_t=0, to_t=0, keep_points=0, algo="EWMA", alpha=0.0, eps=0.0, min_samples=0, maxiter=0, emit_all=False,
+                         out="host", job_id=""):
+        """run_state over a window of what `state` holds, read-only (tad_run_state_window): of every key's series the points with
+        flow_end_s >= from_t and < to_t (0 = no bound on that side), then the newest keep_points of those (0 = all).  Exactly the rows
+        run() returns for the table of those points; the state is left unchanged.  Both bounds act on flowEndSeconds."""
+        if algo not in capi.TAD_ALGO:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "algo must be EWMA, ARIMA, DBSCAN or DROP")
+        if not self._lib.tad_features() & capi.TAD_FEATURE_STATE_WINDOW:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_run_state_window (TAD_FEATURE_STATE_WINDOW)")
+        job = capi.Job(algo=capi.TAD_ALGO[algo], ewma_alpha=float(alpha), dbscan_eps=float(eps), dbscan_min_samples=int(min_samples),
+                       arima_maxiter=int(maxiter), flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
+        res = C.POINTER(capi.Result)()
+        rc = self._lib.tad_run_state_window(self._h, state._h, C.byref(job), int(from_t), int(to_t), int(keep_points),
+                                            capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
+        self._check(rc)
+        return TadResult(self, res)
+
     # ---- row-sharded ingest: bucket device rows by owner = key mod world (tad_shard_rows) ----
     def shard_rows(self, key_id, flow_end_s, value, world):
         """Device columns (torch CUDA tensors or DeviceArray) -> ((key_local, flow_end_s, value) DeviceArrays grouped by

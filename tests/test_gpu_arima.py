@@ -110,9 +110,11 @@ def test_series_arima_every_length(engine):
         assert_same(got, want, "length %d" % n)
 
 
-def check_job(engine, k, t, v, K):
-    want = orc.run_job("ARIMA", k, t, v, agg_flow="svc")
-    allp = engine.run("ARIMA", k, t, v, K, agg_flow="svc", emit_all=True)
+def check_job(engine, k, t, v, K, maxiter=0):
+    """maxiter: tad_job.arima_maxiter, the optimiser's iteration limit on both sides (0 = the default, 50)"""
+    arima_fn = None if not maxiter else lambda x, counters=None: ao.calculate_arima_exact(x, maxiter=maxiter, counters=counters)
+    want = orc.run_job("ARIMA", k, t, v, agg_flow="svc", arima_fn=arima_fn)
+    allp = engine.run("ARIMA", k, t, v, K, agg_flow="svc", emit_all=True, maxiter=maxiter)
     pk, pt, pv = want["points"]
     keep = np.repeat(np.array([r is not None for r in want_results(want)]), np.diff(want["ptr"]))
     assert allp.n_rows == int(keep.sum()) and (allp["key_id"] == pk[keep]).all() and (allp["flow_end_s"] == pt[keep]).all()
@@ -120,7 +122,7 @@ def check_job(engine, k, t, v, K):
     assert (allp["stddev"] == np.repeat(want["sigma"], np.diff(want["ptr"]))[keep]).all()
     assert_same(allp["algo_calc"], want["calc_all"][keep], "job predictions")
     assert (allp["anomaly"].astype(bool) == want["anomaly_all"][keep]).all()       # zero verdict flips
-    res = engine.run("ARIMA", k, t, v, K, agg_flow="svc")
+    res = engine.run("ARIMA", k, t, v, K, agg_flow="svc", maxiter=maxiter)
     assert res.n_rows == want["n_anomalies"] and (res["key_id"] == want["key_id"]).all() and (res["flow_end_s"] == want["flow_end_s"]).all()
     assert_same(res["algo_calc"], want["algo_calc"], "job anomaly rows")
     assert res.stats["keys_no_result"] == want["keys_no_result"]
@@ -138,6 +140,19 @@ def test_job_arima_matches_oracle(engine):
     want, res = check_job(engine, k, t, v, 24)
     assert res.stats["arima_fits"] == want["n_points"] - 3 * want["n_keys"]
     assert res.stats["kalman_steps"] == want["kalman_steps"]          # the flop figure's counter, cross-checked
+
+
+@pytest.mark.parametrize("maxiter", [1, 5])
+def test_job_arima_maxiter(engine, maxiter):
+    """arima_maxiter away from its default on the 24-key table: an optimiser stopped after 1 or 5 iterations predicts other values
+    than one that runs to convergence, and fewer Kalman steps are spent"""
+    k, t, v = orc.synth_rows(0, 4000, 24, 40)
+    want, res = check_job(engine, k, t, v, 24, maxiter=maxiter)
+    usual = orc.run_job("ARIMA", k, t, v, agg_flow="svc")
+    fin = np.isfinite(want["calc_all"]) & np.isfinite(usual["calc_all"])
+    assert (want["calc_all"][fin] != usual["calc_all"][fin]).mean() > 0.5
+    assert res.stats["arima_fits"] == want["n_points"] - 3 * want["n_keys"]
+    assert res.stats["kalman_steps"] == want["kalman_steps"] < usual["kalman_steps"]
 
 
 def test_job_arima_c3_table_sample(engine):

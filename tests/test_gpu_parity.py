@@ -111,6 +111,7 @@ def test_series_dbscan_sorted_windows_adversarial(engine):
 # ------------------------------------------------------------------ (c) whole job vs oracle
 def check_job(engine, algo, key, t, v, num_keys, agg_flow="svc", **kw):
     okw = {k: kw[k] for k in ("key_id2", "flow_start_s", "start_time", "end_time") if k in kw}
+    okw.update({k: kw[k] for k in ("alpha", "eps", "min_samples") if kw.get(k)})      # 0 = the detector's default on both sides
     want = orc.run_job(algo, key, t, v, agg_flow=agg_flow, **okw)
     # every point, with verdicts (plotDF before the filter)
     allp = engine.run(algo, key, t, v, num_keys, agg_flow=agg_flow, emit_all=True, **kw)

@@ -181,18 +181,23 @@ def test_skewed_series_lengths_run_as_length_classes(algo, agg):
         eng.close()
 
 
+def class_boundary_table():
+    """18 keys with a series at every class boundary (16 / 64 / 256 points), keys without points among them -> (key, t, value, K)"""
+    rng = np.random.default_rng(3)
+    n_k = np.array([0, 1, 2, 3, 4, 15, 16, 17, 63, 64, 65, 255, 256, 257, 300, 0, 5, 40], dtype=np.int64)
+    K = n_k.size
+    pk = np.repeat(np.arange(K, dtype=np.uint64), n_k)
+    pt = np.concatenate([np.sort(rng.choice(5000, size=n, replace=False)) for n in n_k]).astype(np.int64) + 1660202814
+    v = (2_000_000_000 + rng.integers(-3_000_000, 3_000_000, size=pk.size)).astype(np.uint64)
+    v = np.where(rng.random(pk.size) < 0.02, v * np.uint64(5), v)
+    order = rng.permutation(pk.size)
+    return pk[order], pt[order], v[order], K
+
+
 def test_length_classes_forced_small_tables(engine):
     # every class boundary (16 / 64 / 256 points), keys without points, ARIMA's no-result keys, a single class
     with engine.plan(sparse="always", sparse_classes="always"):
-        rng = np.random.default_rng(3)
-        n_k = np.array([0, 1, 2, 3, 4, 15, 16, 17, 63, 64, 65, 255, 256, 257, 300, 0, 5, 40], dtype=np.int64)
-        K = n_k.size
-        pk = np.repeat(np.arange(K, dtype=np.uint64), n_k)
-        pt = np.concatenate([np.sort(rng.choice(5000, size=n, replace=False)) for n in n_k]).astype(np.int64) + 1660202814
-        v = (2_000_000_000 + rng.integers(-3_000_000, 3_000_000, size=pk.size)).astype(np.uint64)
-        v = np.where(rng.random(pk.size) < 0.02, v * np.uint64(5), v)
-        order = rng.permutation(pk.size)
-        k, t, v = pk[order], pt[order], v[order]
+        k, t, v, K = class_boundary_table()
         for algo, agg in (("EWMA", "svc"), ("DBSCAN", ""), ("ARIMA", "svc")):
             check_classes(engine, algo, k, t, v, K, agg)
         k1, t1, v1 = day_table(40, 10, 2, seed=9, span=3000)      # all keys in one class

@@ -1113,6 +1113,243 @@ func (s *State) Merge(job Job, cols Columns, keepFrom int64) (MergeStats, error)
 		MsTotal: float32(ms.ms_total)}, nil
 }
 
+var keyDictOnce sync.Once
+var keyDictOK bool
+
+// hasKeyDict: the library knows the persistent key dictionary (tad_features); an older one would not export the calls.
+func hasKeyDict() bool {
+	keyDictOnce.Do(func() { keyDictOK = C.tad_features()&C.TAD_FEATURE_KEY_DICT != 0 })
+	return keyDictOK
+}
+
+// KeyDict is a key dictionary kept in HBM that outlives the call (tad_keydict): key tuples -> dense ids that stay the same from batch
+// to batch, new ids in order of first appearance.  It is what gives a poller the key ids of RunStream / Merge: Encode every batch,
+// State.Resize when NumKeys grew, then RunStream or Merge with Columns.NumKeys = the dictionary's.
+type KeyDict struct {
+	e     *Engine
+	h     *C.tad_keydict
+	nCols int
+}
+
+// NewKeyDict makes a dictionary for tuples of nCols (1..8) int64 columns.  expectedKeys sizes the first table (0 = the default).
+func (e *Engine) NewKeyDict(nCols int, expectedKeys uint64) (*KeyDict, error) {
+	if !hasKeyDict() {
+		return nil, errors.New("tadengine: libtad_mi355x.so has no key dictionary (TAD_FEATURE_KEY_DICT)")
+	}
+	var h *C.tad_keydict
+	if rc := C.tad_keydict_create(e.h, C.int32_t(nCols), C.uint64_t(expectedKeys), &h); rc != C.TAD_OK {
+		return nil, fmt.Errorf("tad_keydict_create: %s (code %d)", C.GoString(C.tad_last_error(e.h)), int(rc))
+	}
+	return &KeyDict{e: e, h: h, nCols: nCols}, nil
+}
+
+func (d *KeyDict) Close() {
+	if d.h != nil {
+		C.tad_keydict_destroy(d.e.h, d.h)
+		d.h = nil
+	}
+}
+
+// keyBatch copies the key tuples of one batch into C memory (no Go pointer is stored in the struct) and fills the tad_key_columns.
+// release frees the copies.
+func keyBatch(nCols int, colsA [][]int64, keepA []byte, colsB [][]int64, keepB []byte) (kb *C.tad_key_columns, n int, release func(), err error) {
+	if len(colsA) != nCols || (colsB != nil && len(colsB) != nCols) {
+		return nil, 0, nil, IllegalArgument{fmt.Sprintf("tadengine: %d key columns on every side", nCols)}
+	}
+	n = len(colsA[0])
+	var bufs []unsafe.Pointer
+	release = func() {
+		for _, p := range bufs {
+			if p != nil {
+				C.free(p)
+			}
+		}
+	}
+	ptrs := func(cols [][]int64) *unsafe.Pointer {
+		arr := (*[8]unsafe.Pointer)(C.malloc(C.size_t(8 * unsafe.Sizeof(unsafe.Pointer(nil)))))
+		bufs = append(bufs, unsafe.Pointer(arr))
+		for c, col := range cols {
+			if len(col) != n {
+				return nil
+			}
+			arr[c] = cColumn(col)
+			bufs = append(bufs, arr[c])
+		}
+		return &arr[0]
+	}
+	mask := func(m []byte) unsafe.Pointer {
+		if m == nil {
+			return nil
+		}
+		p := C.CBytes(m)
+		bufs = append(bufs, p)
+		return p
+	}
+	kb = (*C.tad_key_columns)(C.calloc(1, C.size_t(unsafe.Sizeof(C.tad_key_columns{}))))
+	bufs = append(bufs, unsafe.Pointer(kb))
+	kb.n_rows = C.uint64_t(n)
+	kb.n_cols = C.int32_t(nCols)
+	kb.memory = C.TAD_MEM_HOST
+	pa := ptrs(colsA)
+	if pa == nil || (keepA != nil && len(keepA) != n) || (keepB != nil && len(keepB) != n) {
+		release()
+		return nil, 0, nil, IllegalArgument{"tadengine: key columns and masks differ in length"}
+	}
+	kb.cols_a = (**C.int64_t)(unsafe.Pointer(pa))
+	kb.keep_a = (*C.uint8_t)(mask(keepA))
+	if colsB != nil {
+		pb := ptrs(colsB)
+		if pb == nil {
+			release()
+			return nil, 0, nil, IllegalArgument{"tadengine: key columns differ in length"}
+		}
+		kb.cols_b = (**C.int64_t)(unsafe.Pointer(pb))
+		kb.keep_b = (*C.uint8_t)(mask(keepB))
+	}
+	return kb, n, release, nil
+}
+
+// Encode maps one batch's key tuples to ids (tad_keydict_encode).  colsA / keepA / colsB / keepB as in Factorize.  Tuples the
+// dictionary holds keep their ids; new ones get numKeysBefore, numKeysBefore + 1, ... in order of first appearance over the virtual
+// rows [side a ++ side b]; rows the masks reject get KeySkip.  newFirstRow[j] = the virtual row of THIS batch where key
+// numKeysBefore + j first appears: the caller reads the new key's strings there.
+func (d *KeyDict) Encode(colsA [][]int64, keepA []byte, colsB [][]int64, keepB []byte) (keyID, keyID2, newFirstRow []uint64, numKeysBefore uint64, err error) {
+	if !hasKeyDict() {
+		return nil, nil, nil, 0, errors.New("tadengine: libtad_mi355x.so has no key dictionary (TAD_FEATURE_KEY_DICT)")
+	}
+	kb, n, release, err := keyBatch(d.nCols, colsA, keepA, colsB, keepB)
+	if err != nil {
+		return nil, nil, nil, 0, err
+	}
+	defer release()
+	sides := 1
+	if colsB != nil {
+		sides = 2
+	}
+	keyID = make([]uint64, n)
+	newFirstRow = make([]uint64, n*sides)
+	var k1, k2, fr *C.uint64_t
+	if colsB != nil {
+		keyID2 = make([]uint64, n)
+	}
+	if n > 0 {
+		k1 = (*C.uint64_t)(unsafe.Pointer(&keyID[0]))
+		fr = (*C.uint64_t)(unsafe.Pointer(&newFirstRow[0]))
+		if colsB != nil {
+			k2 = (*C.uint64_t)(unsafe.Pointer(&keyID2[0]))
+		}
+	}
+	var before, after C.uint64_t
+	if rc := C.tad_keydict_encode(d.e.h, d.h, kb, k1, k2, fr, C.uint64_t(len(newFirstRow)), &before, &after); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(d.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, nil, nil, 0, IllegalArgument{msg}
+		}
+		return nil, nil, nil, 0, fmt.Errorf("tad_keydict_encode: %s (code %d)", msg, int(rc))
+	}
+	return keyID, keyID2, newFirstRow[:int(after-before)], uint64(before), nil
+}
+
+// Lookup is Encode read-only (tad_keydict_lookup): an unknown tuple gets KeySkip and the dictionary is unchanged.
+func (d *KeyDict) Lookup(colsA [][]int64, keepA []byte, colsB [][]int64, keepB []byte) (keyID, keyID2 []uint64, err error) {
+	if !hasKeyDict() {
+		return nil, nil, errors.New("tadengine: libtad_mi355x.so has no key dictionary (TAD_FEATURE_KEY_DICT)")
+	}
+	kb, n, release, err := keyBatch(d.nCols, colsA, keepA, colsB, keepB)
+	if err != nil {
+		return nil, nil, err
+	}
+	defer release()
+	keyID = make([]uint64, n)
+	var k1, k2 *C.uint64_t
+	if colsB != nil {
+		keyID2 = make([]uint64, n)
+	}
+	if n > 0 {
+		k1 = (*C.uint64_t)(unsafe.Pointer(&keyID[0]))
+		if colsB != nil {
+			k2 = (*C.uint64_t)(unsafe.Pointer(&keyID2[0]))
+		}
+	}
+	if rc := C.tad_keydict_lookup(d.e.h, d.h, kb, k1, k2); rc != C.TAD_OK {
+		return nil, nil, fmt.Errorf("tad_keydict_lookup: %s (code %d)", C.GoString(C.tad_last_error(d.e.h)), int(rc))
+	}
+	return keyID, keyID2, nil
+}
+
+// NumKeys is the number of keys the dictionary holds (tad_keydict_num_keys): Columns.NumKeys of the next RunStream / Merge.
+func (d *KeyDict) NumKeys() (uint64, error) {
+	if !hasKeyDict() {
+		return 0, errors.New("tadengine: libtad_mi355x.so has no key dictionary (TAD_FEATURE_KEY_DICT)")
+	}
+	var n C.uint64_t
+	if rc := C.tad_keydict_num_keys(d.e.h, d.h, &n); rc != C.TAD_OK {
+		return 0, fmt.Errorf("tad_keydict_num_keys: %s (code %d)", C.GoString(C.tad_last_error(d.e.h)), int(rc))
+	}
+	return uint64(n), nil
+}
+
+// Bytes is the device memory the dictionary holds: the table and the key records at their capacity (tad_keydict_bytes).
+func (d *KeyDict) Bytes() (uint64, error) {
+	if !hasKeyDict() {
+		return 0, errors.New("tadengine: libtad_mi355x.so has no key dictionary (TAD_FEATURE_KEY_DICT)")
+	}
+	var n C.uint64_t
+	if rc := C.tad_keydict_bytes(d.e.h, d.h, &n); rc != C.TAD_OK {
+		return 0, fmt.Errorf("tad_keydict_bytes: %s (code %d)", C.GoString(C.tad_last_error(d.e.h)), int(rc))
+	}
+	return uint64(n), nil
+}
+
+// Export returns the tuples of the keys [firstKey, firstKey + nKeys) column by column, and their sides (tad_keydict_export).
+func (d *KeyDict) Export(firstKey, nKeys uint64) (cols [][]int64, side []byte, err error) {
+	if !hasKeyDict() {
+		return nil, nil, errors.New("tadengine: libtad_mi355x.so has no key dictionary (TAD_FEATURE_KEY_DICT)")
+	}
+	cols = make([][]int64, d.nCols)
+	side = make([]byte, nKeys)
+	// the pointer array and the columns it names live in C memory for the call (no Go pointer inside C memory)
+	arr := (*[8]*C.int64_t)(C.calloc(8, C.size_t(unsafe.Sizeof(unsafe.Pointer(nil)))))
+	defer C.free(unsafe.Pointer(arr))
+	for c := range cols {
+		cols[c] = make([]int64, nKeys)
+		arr[c] = (*C.int64_t)(C.calloc(C.size_t(nKeys)+1, 8))
+		defer C.free(unsafe.Pointer(arr[c]))
+	}
+	var sp *C.uint8_t
+	if nKeys > 0 {
+		sp = (*C.uint8_t)(unsafe.Pointer(&side[0]))
+	}
+	if rc := C.tad_keydict_export(d.e.h, d.h, C.uint64_t(firstKey), C.uint64_t(nKeys), &arr[0], sp); rc != C.TAD_OK {
+		return nil, nil, fmt.Errorf("tad_keydict_export: %s (code %d)", C.GoString(C.tad_last_error(d.e.h)), int(rc))
+	}
+	for c := range cols {
+		copy(cols[c], unsafe.Slice((*int64)(unsafe.Pointer(arr[c])), nKeys))
+	}
+	return cols, side, nil
+}
+
+// Import fills an EMPTY dictionary so that key i is tuple i (tad_keydict_import): what Export returned, after a restart of the host.
+// side nil = every key on side a.  A duplicate tuple, a dictionary that holds keys or a side > 1 is an IllegalArgument.
+func (d *KeyDict) Import(cols [][]int64, side []byte) error {
+	if !hasKeyDict() {
+		return errors.New("tadengine: libtad_mi355x.so has no key dictionary (TAD_FEATURE_KEY_DICT)")
+	}
+	kb, n, release, err := keyBatch(d.nCols, cols, side, nil, nil)
+	if err != nil {
+		return err
+	}
+	defer release()
+	if rc := C.tad_keydict_import(d.e.h, d.h, C.uint64_t(n), kb.cols_a, kb.keep_a); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(d.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return IllegalArgument{msg}
+		}
+		return fmt.Errorf("tad_keydict_import: %s (code %d)", msg, int(rc))
+	}
+	return nil
+}
+
 func (e *Engine) NewState(numKeys uint64) (*State, error) {
 	var h *C.tad_state
 	if rc := C.tad_state_create(e.h, C.uint64_t(numKeys), &h); rc != C.TAD_OK {

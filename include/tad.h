@@ -653,6 +653,61 @@ int tad_run_state_window(tad_engine *e, tad_state *s, const tad_job *job, int64_
  * sorted and subtracted from the state's history.  Needs no device. */
 int tad_window_history_by_sort(uint64_t window_points, uint64_t state_points);
 
+/* ---- key ids that stay the same from batch to batch: a key dictionary kept in HBM (TAD_FEATURE_KEY_DICT; check tad_features() before
+ * calling these) ----
+ * Every streaming call above takes dense key ids: cols->num_keys must equal the state's, and key k must be the same flow key in every
+ * batch for as long as the state lives.  tad_factorize numbers the keys of ONE call (its table is scratch, a match is confirmed against
+ * that call's input rows), so a streaming host had to keep its own tuple -> id map in front of the engine.  tad_keydict is that map on
+ * the device: it maps key tuples to dense ids, hands out new ids in order of first appearance, and outlives the call.
+ * tad_keydict_create: n_cols (1..8) is the tuple width for the dictionary's life.  expected_keys sizes the first table (0 = a default
+ * that stays in the caches, 2^20 slots); 1 gives the smallest table the implementation allows (64 slots, 32 key records).  The dictionary
+ * grows by itself whatever was given here.
+ * tad_keydict_encode, one batch: kc is tad_factorize's argument — host or device memory (all arrays, inputs and outputs, live in
+ * kc->memory), keep masks, an optional second tuple per row — and kc->n_cols must equal the dictionary's.  The side (0 = a, 1 = b) is
+ * part of the tuple, as in tad_factorize; a batch without cols_b is side 0, and one dictionary takes one-sided and two-sided batches alike.
+ *   - a tuple the dictionary holds gets the id it holds for it;
+ *   - new tuples get the ids *num_keys_before, *num_keys_before + 1, ... in order of first appearance over the batch's kept virtual rows
+ *     [side a: 0 .. n) ++ [side b: n .. 2n);
+ *   - rows that are not kept get TAD_KEY_SKIP;
+ *   - new_first_row[j] (j < new_first_row_cap) = the virtual row of THIS batch where key *num_keys_before + j first appears — the host
+ *     reads the new key's strings there, as with tad_factorize's first_row.  A cap below the number of new keys caps the list, never the ids;
+ *   - *num_keys_before and *num_keys (either may be NULL) = the keys held before and after the call.
+ * One-sided batches: after batches 1..b the ids of batch b's rows equal what tad_factorize returns for those rows when called once on the
+ * concatenation of batches 1..b.  Two-sided batches are numbered in the sequential order b1.a, b1.b, b2.a, b2.b, ...  Ids are never
+ * reused or moved.  Limits: n_rows * sides < 2^32 - 1 per batch, fewer than 2^32 - 1 keys per dictionary.  An empty batch is TAD_OK.
+ * tad_keydict_lookup is tad_keydict_encode read-only: an unknown tuple gets TAD_KEY_SKIP and the dictionary is unchanged.
+ * tad_keydict_export writes the tuples of the keys [first_key, first_key + n_keys) into n_cols HOST arrays of n_keys entries (cols[c][i] =
+ * column c of key first_key + i) and their sides into side[n_keys] (HOST, may be NULL).  tad_keydict_import fills an EMPTY dictionary so
+ * that key i is tuple i (side NULL = every key on side 0): a restart, as tad_state_import is.  A duplicate tuple, a dictionary that holds
+ * keys, or a side > 1 is TAD_ERR_INVALID_ARGUMENT and leaves the dictionary unchanged.
+ * Strings: the dictionary holds integers.  A host with string key columns passes codes that are stable across batches — one vocabulary
+ * per column, kept for the life of the dictionary.
+ * Atomic: everything that can fail happens before the dictionary is touched — argument checks, the workspace limit, every allocation,
+ * growth of the table into a fresh table, growth of the key records — so any failure leaves num_keys, the ids and the exported tuples
+ * as they were.  (Growth may have taken place: it changes the capacity, never the contents.)
+ * How: an open-addressing table of 8-byte slots, fingerprint << 32 | id, and one record per key with its tuple (side + n_cols words,
+ * padded to a multiple of 16 bytes), against which a fingerprint match is confirmed (theia_amd/csrc/tad_keydict.hip).  A batch probes
+ * the table once; a batch of known tuples ends there with one synchronisation.  Rows with unknown tuples are factorised among
+ * themselves by tad_factorize's kernels, one lane per new key appends its record and claims a slot, and the new ids are written.  The
+ * table is kept at a load of at most 1/2: when new keys would pass that, a table of the next power of two is filled from the records
+ * and swapped in.
+ * Memory: tad_keydict_bytes = the device bytes the dictionary holds (table and key records at their capacity).  Scratch is job-context
+ * workspace and is checked against tad_engine_opts.workspace_limit (TAD_ERR_GRID_TOO_LARGE): V bytes of miss flags for the V = n_rows *
+ * sides virtual rows, plus the staged columns, masks and ids of a host batch; a batch with unknown tuples adds 8 V bytes of local ids,
+ * 8 bytes per miss row and tad_factorize's scratch for V virtual rows.
+ * Lock order: the dictionary, then a job context; calls on one dictionary are serial. */
+#define TAD_FEATURE_KEY_DICT 128u     /* tad_keydict: a persistent tuple -> key id dictionary on the device */
+typedef struct tad_keydict tad_keydict;
+int tad_keydict_create(tad_engine *e, int32_t n_cols, uint64_t expected_keys, tad_keydict **out);
+void tad_keydict_destroy(tad_engine *e, tad_keydict *d);
+int tad_keydict_encode(tad_engine *e, tad_keydict *d, const tad_key_columns *kc, uint64_t *key_id, uint64_t *key_id2,
+                       uint64_t *new_first_row, uint64_t new_first_row_cap, uint64_t *num_keys_before, uint64_t *num_keys);
+int tad_keydict_lookup(tad_engine *e, const tad_keydict *d, const tad_key_columns *kc, uint64_t *key_id, uint64_t *key_id2);
+int tad_keydict_num_keys(tad_engine *e, const tad_keydict *d, uint64_t *num_keys);
+int tad_keydict_bytes(tad_engine *e, const tad_keydict *d, uint64_t *bytes);
+int tad_keydict_export(tad_engine *e, const tad_keydict *d, uint64_t first_key, uint64_t n_keys, int64_t *const *cols, uint8_t *side);
+int tad_keydict_import(tad_engine *e, tad_keydict *d, uint64_t n_keys, const int64_t *const *cols, const uint8_t *side);
+
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).
  * tad_job_progress (ABI 12): the job whose tad_job.id equals `id`; *total = 0 when no such job is in flight (finished or not yet

@@ -28,6 +28,7 @@ TAD_STATE_TIMES = 8                          # tad_state_create_ex flag (with TA
 TAD_FEATURE_STATE_RUN = 16                   # tad_features() bit: tad_run_state, the batch job's rows over everything a state holds
 TAD_FEATURE_STATE_MERGE = 32                 # tad_features() bit: tad_state_merge, a batch placed by time (late, re-sent and split rows)
 TAD_FEATURE_STATE_WINDOW = 64                # tad_features() bit: tad_run_state_window, tad_run_state over a time range of the state, read-only
+TAD_FEATURE_KEY_DICT = 128                   # tad_features() bit: tad_keydict, a persistent tuple -> key id dictionary on the device
 
 
 class Plan(C.Structure):
@@ -156,6 +157,14 @@ SYMBOLS = {
     "tad_shard_rows": (C.c_int, [C.c_void_p, C.POINTER(Columns), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_factorize": (C.c_int, [C.c_void_p, C.POINTER(KeyColumns), C.c_void_p, C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]),
     "tad_factorize_hist": (C.c_int, [C.c_void_p, C.POINTER(KeyColumns), C.c_void_p, C.c_void_p, C.c_void_p, u64, C.POINTER(u64), C.POINTER(KeyHist)]),
+    "tad_keydict_create": (C.c_int, [C.c_void_p, i32, u64, C.POINTER(C.c_void_p)]),
+    "tad_keydict_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "tad_keydict_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(KeyColumns), C.c_void_p, C.c_void_p, C.c_void_p, u64, C.POINTER(u64), C.POINTER(u64)]),
+    "tad_keydict_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(KeyColumns), C.c_void_p, C.c_void_p]),
+    "tad_keydict_num_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(u64)]),
+    "tad_keydict_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(u64)]),
+    "tad_keydict_export": (C.c_int, [C.c_void_p, C.c_void_p, u64, u64, C.POINTER(C.c_void_p), C.c_void_p]),
+    "tad_keydict_import": (C.c_int, [C.c_void_p, C.c_void_p, u64, C.POINTER(C.c_void_p), C.c_void_p]),
     "tad_encode_strings": (C.c_int, [C.c_void_p, C.POINTER(StringColumn), C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]),
     "tad_widen_column": (C.c_int, [C.c_void_p, C.c_void_p, i32, i32, C.c_int, u64, C.c_void_p, u64, C.c_void_p]),
     "tad_mask_rows": (C.c_int, [C.c_void_p, u64, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(u64), i32, C.c_void_p]),

@@ -1,0 +1,361 @@
+// tad_capi_keydict.cpp — the persistent key dictionary of include/tad.h (tad_keydict_*): the host side of tad_keydict.hip.
+// Order of every call that changes the dictionary: check, size, allocate, grow (capacity only) — and only then touch the contents.
+#include "tad_engine.h"
+
+using namespace tad;
+using namespace tadh;
+
+struct tad_keydict {
+  int n_cols = 0;
+  uint64_t K = 0;                        // keys held
+  unsigned long long *table = nullptr;   // slots words: fingerprint << 32 | id, all ones = empty
+  uint64_t slots = 0;                    // a power of two, >= 2 K
+  unsigned long long *keys = nullptr;    // key_cap records of kd_stride(n_cols) words
+  uint64_t key_cap = 0;
+  mutable std::mutex mu;                 // calls on one dictionary are serial (lock order: the dictionary, then a job context)
+};
+
+namespace {
+
+constexpr uint64_t kKdMinSlots = 64, kKdMinKeys = 32, kKdDefaultSlots = 1ull << 20, kKdDefaultKeys = 1ull << 16;
+constexpr uint64_t kKdMaxKeys = 0xFFFFFFFFull - 1;     // ids < 2^32 - 1
+
+size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+uint64_t pow2_at_least(uint64_t x) { uint64_t s = kKdMinSlots; while (s < x) s <<= 1; return s; }
+
+// hipMalloc that gives the idle contexts' buffers back to the device before it fails (as ensure does)
+hipError_t kd_alloc(JobCtx *e, void **p, size_t bytes) {
+  hipError_t r = hipMalloc(p, bytes);
+  if (r != hipSuccess) {
+    (void)hipGetLastError();
+    trim_idle(e->eng, e);
+    r = hipMalloc(p, bytes);
+  }
+  if (r != hipSuccess) { *p = nullptr; (void)hipGetLastError(); }
+  return r;
+}
+
+// Room for `total` keys: key records and a table at load <= 1/2.  Capacity only — K, the ids and the tuples are what they were, whether
+// this succeeds or not; the old arrays stay the dictionary's until the new ones are complete.
+int kd_reserve(JobCtx *e, tad_keydict *d, uint64_t total, uint64_t min_slots = 0) {
+  hipStream_t s = e->stream;
+  const size_t rec = (size_t)kd_stride(d->n_cols) * 8;
+  unsigned long long *nkeys = nullptr, *ntable = nullptr;
+  uint64_t ncap = d->key_cap, nslots = d->slots;
+  if (total > d->key_cap) {
+    ncap = d->key_cap * 2 > total ? d->key_cap * 2 : total;
+    if (ncap > kKdMaxKeys) ncap = kKdMaxKeys;
+  }
+  if (2 * total > d->slots) nslots = pow2_at_least(2 * total);
+  if (min_slots > nslots) nslots = min_slots;
+  if (ncap == d->key_cap && nslots == d->slots) return TAD_OK;
+  hipError_t r = hipSuccess;
+  if (ncap != d->key_cap) r = kd_alloc(e, reinterpret_cast<void **>(&nkeys), ncap * rec);
+  if (r == hipSuccess && nslots != d->slots) r = kd_alloc(e, reinterpret_cast<void **>(&ntable), nslots * 8);
+  if (r == hipSuccess && nkeys && d->K) r = hipMemcpyAsync(nkeys, d->keys, d->K * rec, hipMemcpyDeviceToDevice, s);
+  if (r == hipSuccess && ntable) {
+    r = hipMemsetAsync(ntable, 0xFF, nslots * 8, s);
+    if (r == hipSuccess && d->K) launch_kd_rehash(s, d->keys, d->n_cols, d->K, ntable, nslots, nullptr, false);
+  }
+  if (r == hipSuccess) r = hipStreamSynchronize(s);
+  if (r == hipSuccess) r = hipGetLastError();
+  if (r != hipSuccess) {
+    if (nkeys) hipFree(nkeys);
+    if (ntable) hipFree(ntable);
+    return fail(e, r == hipErrorOutOfMemory ? TAD_ERR_OUT_OF_MEMORY : TAD_ERR_HIP, "tad_keydict: no room for %llu keys: %s (dictionary unchanged)",
+                (unsigned long long)total, hipGetErrorString(r));
+  }
+  if (nkeys) { hipFree(d->keys); d->keys = nkeys; d->key_cap = ncap; }
+  if (ntable) { hipFree(d->table); d->table = ntable; d->slots = nslots; }
+  return TAD_OK;
+}
+
+// tad_keydict_encode (insert) / tad_keydict_lookup
+int kd_run(tad_engine *eng, tad_keydict *d, const tad_key_columns *kc, uint64_t *key_id, uint64_t *key_id2, uint64_t *new_first_row, uint64_t new_first_row_cap,
+           uint64_t *num_keys_before, uint64_t *num_keys, bool insert) {
+  const char *who = insert ? "tad_keydict_encode" : "tad_keydict_lookup";
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!d || !kc || !kc->cols_a || (kc->n_rows && !key_id) || (kc->cols_b && kc->n_rows && !key_id2) || (new_first_row_cap && !new_first_row))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bad arguments (dictionary, key columns, key_id / key_id2 / new_first_row buffers)", who);
+  if (kc->n_cols != d->n_cols)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: %d key columns, the dictionary holds tuples of %d", who, (int)kc->n_cols, d->n_cols);
+  const uint64_t n = kc->n_rows;
+  const uint32_t sides = kc->cols_b ? 2 : 1;
+  const uint64_t V = n * sides;
+  if (V >= 0xFFFFFFFFull) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: %llu virtual rows do not fit 32-bit row indices", who, (unsigned long long)V);
+  for (int c = 0; c < kc->n_cols; ++c)
+    if (!kc->cols_a[c] || (kc->cols_b && !kc->cols_b[c])) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key column %d is NULL", who, c);
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  if (num_keys_before) *num_keys_before = d->K;
+  if (num_keys) *num_keys = d->K;
+  if (n == 0) return TAD_OK;
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "%s: no job context available", who);
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  const bool host = kc->memory == TAD_MEM_HOST;
+  const int nc = kc->n_cols;
+  // scratch of the probe: in_key = a host batch's columns and masks, in_key2 = its ids, sp_comp_a = miss flags | miss count, flags, new-key count
+  const size_t col_bytes = up256(n * 8), mask_bytes = up256(n), miss_bytes = up256(V);
+  const size_t stage_in = host ? (size_t)nc * sides * col_bytes + 2 * mask_bytes : 0, stage_out = host ? sides * col_bytes : 0;
+  const size_t need0 = stage_in + stage_out + miss_bytes + 256;
+  if (need0 > e->ws_limit)
+    return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu", who, (unsigned long long)need0, (unsigned long long)e->ws_limit);
+  int rc;
+  if ((rc = ensure(e, e->sp_comp_a, miss_bytes + 256)) != TAD_OK) return rc;
+  if (host && ((rc = ensure(e, e->in_key, stage_in)) != TAD_OK || (rc = ensure(e, e->in_key2, stage_out)) != TAD_OK)) return rc;
+  uint8_t *miss = static_cast<uint8_t *>(e->sp_comp_a.p);
+  unsigned char *tail = miss + miss_bytes;
+  unsigned long long *n_miss_dev = reinterpret_cast<unsigned long long *>(tail);
+  uint32_t *kd_flags_dev = reinterpret_cast<uint32_t *>(tail + 8);
+  unsigned long long *nk_dev = reinterpret_cast<unsigned long long *>(tail + 16);
+  KdBatch A{};
+  A.keep_a = kc->keep_a; A.keep_b = kc->keep_b; A.n = n; A.n_cols = nc; A.sides = sides;
+  uint64_t *d_key = key_id, *d_key2 = key_id2;
+  if (host) {
+    unsigned char *p = static_cast<unsigned char *>(e->in_key.p);
+    for (int c = 0; c < nc; ++c) {
+      HIP_TRY(e, hipMemcpyAsync(p, kc->cols_a[c], n * 8, hipMemcpyHostToDevice, s)); A.a[c] = reinterpret_cast<const long long *>(p); p += col_bytes;
+      if (sides == 2) { HIP_TRY(e, hipMemcpyAsync(p, kc->cols_b[c], n * 8, hipMemcpyHostToDevice, s)); A.b[c] = reinterpret_cast<const long long *>(p); p += col_bytes; }
+    }
+    if (A.keep_a) { HIP_TRY(e, hipMemcpyAsync(p, A.keep_a, n, hipMemcpyHostToDevice, s)); A.keep_a = p; }
+    p += mask_bytes;
+    if (A.keep_b) { HIP_TRY(e, hipMemcpyAsync(p, A.keep_b, n, hipMemcpyHostToDevice, s)); A.keep_b = p; }
+    d_key = reinterpret_cast<uint64_t *>(e->in_key2.p);
+    if (sides == 2) d_key2 = d_key + col_bytes / 8;
+  } else {
+    for (int c = 0; c < nc; ++c) { A.a[c] = reinterpret_cast<const long long *>(kc->cols_a[c]); if (sides == 2) A.b[c] = reinterpret_cast<const long long *>(kc->cols_b[c]); }
+  }
+  if (sides == 1) A.keep_b = nullptr;
+  auto ids_to_host = [&]() -> int {
+    HIP_TRY(e, hipMemcpyAsync(key_id, d_key, n * 8, hipMemcpyDeviceToHost, s));
+    if (sides == 2) HIP_TRY(e, hipMemcpyAsync(key_id2, d_key2, n * 8, hipMemcpyDeviceToHost, s));
+    return TAD_OK;
+  };
+  // 1. the probe: the dictionary is only read
+  HIP_TRY(e, hipMemsetAsync(tail, 0, 32, s));
+  launch_kd_probe(s, A, d->table, d->slots, d->keys, d->K, d_key, d_key2, insert ? miss : nullptr, n_miss_dev);
+  unsigned long long M = 0;
+  if (insert) HIP_TRY(e, hipMemcpyAsync(&M, n_miss_dev, 8, hipMemcpyDeviceToHost, s));
+  if (host && !insert && (rc = ids_to_host()) != TAD_OK) return rc;
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  if (!insert) return TAD_OK;
+  if (M == 0) {      // every tuple known
+    if (host) {
+      if ((rc = ids_to_host()) != TAD_OK) return rc;
+      HIP_TRY(e, hipStreamSynchronize(s));
+    }
+    return TAD_OK;
+  }
+  // 2. the miss rows factorised among themselves (keep masks = miss flags): local ids in order of first appearance, the first row of each.
+  //    sp_val_a = local ids of both sides, sp_first = first rows (at most one new key per miss row), sp_temp = tad_factorize's scratch
+  const size_t loc_bytes = sides * col_bytes, fr_bytes = up256((size_t)M * 8);
+  unsigned long long m = 0;
+  uint64_t *loc_a = nullptr, *loc_b = nullptr, *fr = nullptr;
+  for (uint64_t slots = factorize_first_slots(V);;) {
+    const size_t tb = factorize_temp_bytes(V, slots);
+    const size_t need = need0 + loc_bytes + fr_bytes + tb;
+    if (need > e->ws_limit)
+      return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu", who, (unsigned long long)need, (unsigned long long)e->ws_limit);
+    if ((rc = ensure(e, e->sp_val_a, loc_bytes)) != TAD_OK || (rc = ensure(e, e->sp_first, fr_bytes)) != TAD_OK || (rc = ensure(e, e->sp_temp, tb)) != TAD_OK) return rc;
+    loc_a = static_cast<uint64_t *>(e->sp_val_a.p);
+    loc_b = sides == 2 ? loc_a + col_bytes / 8 : nullptr;
+    fr = static_cast<uint64_t *>(e->sp_first.p);
+    uint32_t *fz_flags_dev = nullptr;
+    launch_factorize(s, A.a, miss, sides == 2 ? A.b : nullptr, sides == 2 ? miss + n : nullptr, n, nc, slots, e->sp_temp.p, loc_a, loc_b, fr, M, nk_dev, &fz_flags_dev);
+    uint32_t fz_flags = 0;
+    HIP_TRY(e, hipMemcpyAsync(&m, nk_dev, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipMemcpyAsync(&fz_flags, fz_flags_dev, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    HIP_TRY(e, hipGetLastError());
+    if (fz_flags == 0) break;
+    const uint64_t next = factorize_next_slots(V, slots);      // more new keys than this scratch table takes: once more with the next size
+    if (next == slots) return fail(e, TAD_ERR_HIP, "%s: the full-size scratch table filled up", who);
+    slots = next;
+  }
+  if (m == 0 || m > M) return fail(e, TAD_ERR_HIP, "%s: %llu new keys from %llu miss rows", who, (unsigned long long)m, (unsigned long long)M);
+  if (d->K + m > kKdMaxKeys)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: %llu keys do not fit 32-bit key ids (dictionary unchanged)", who, (unsigned long long)(d->K + m));
+  // room for the new keys: the last step that can fail
+  if ((rc = kd_reserve(e, d, d->K + m)) != TAD_OK) return rc;
+  // 3. + 4. the new keys' records and slots, the miss rows' ids
+  launch_kd_append(s, A, fr, m, d->K, d->table, d->slots, d->keys, kd_flags_dev);
+  launch_kd_fix(s, miss, loc_a, loc_b, n, sides, d->K, d_key, d_key2);
+  const uint64_t listed = m < new_first_row_cap ? m : new_first_row_cap;
+  hipError_t r = hipSuccess;
+  if (listed) r = hipMemcpyAsync(new_first_row, fr, listed * 8, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s);
+  if (r == hipSuccess && host) {
+    r = hipMemcpyAsync(key_id, d_key, n * 8, hipMemcpyDeviceToHost, s);
+    if (r == hipSuccess && sides == 2) r = hipMemcpyAsync(key_id2, d_key2, n * 8, hipMemcpyDeviceToHost, s);
+  }
+  uint32_t kd_flags = 0;
+  if (r == hipSuccess) r = hipMemcpyAsync(&kd_flags, kd_flags_dev, 4, hipMemcpyDeviceToHost, s);
+  const hipError_t rs = hipStreamSynchronize(s);      // (always: the append is in flight)
+  if (r == hipSuccess) r = rs;
+  if (r == hipSuccess) r = hipGetLastError();
+  if (r != hipSuccess || (kd_flags & KD_FLAG_BAD_ROW))
+    return fail(e, TAD_ERR_HIP, "%s: appending %llu keys failed: %s", who, (unsigned long long)m, hipGetErrorString(r));
+  d->K += m;
+  if (num_keys) *num_keys = d->K;
+  if ((kd_flags & KD_FLAG_CLUSTER) && d->slots < (1ull << 34)) {      // long probe sequences: a table of twice the size, if there is room for one
+    if (kd_reserve(e, d, d->K, d->slots * 2) != TAD_OK) (void)hipGetLastError();
+  }
+  return TAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tad_keydict_create(tad_engine *eng, int32_t n_cols, uint64_t expected_keys, tad_keydict **out) {
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_create: engine is NULL");
+  if (!out || n_cols < 1 || n_cols > kFzMaxCols || expected_keys > kKdMaxKeys)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_create: bad arguments (1..%d key columns, fewer than 2^32 - 1 keys)", kFzMaxCols);
+  *out = nullptr;
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_keydict_create: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  tad_keydict *d = new (std::nothrow) tad_keydict();
+  if (!d) return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory");
+  d->n_cols = n_cols;
+  d->slots = expected_keys ? pow2_at_least(2 * expected_keys) : kKdDefaultSlots;
+  d->key_cap = expected_keys ? (expected_keys > kKdMinKeys ? expected_keys : kKdMinKeys) : kKdDefaultKeys;
+  hipError_t r = kd_alloc(e, reinterpret_cast<void **>(&d->table), d->slots * 8);
+  if (r == hipSuccess) r = kd_alloc(e, reinterpret_cast<void **>(&d->keys), d->key_cap * (size_t)kd_stride(n_cols) * 8);
+  if (r == hipSuccess) r = hipMemsetAsync(d->table, 0xFF, d->slots * 8, e->stream);
+  if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+  if (r != hipSuccess) {
+    if (d->table) hipFree(d->table);
+    if (d->keys) hipFree(d->keys);
+    delete d;
+    return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_keydict_create: %s", hipGetErrorString(r));
+  }
+  *out = d;
+  return TAD_OK;
+}
+
+void tad_keydict_destroy(tad_engine *e, tad_keydict *d) {
+  if (!d) return;
+  { std::lock_guard<std::mutex> lk(d->mu); }   // a call on this dictionary has returned (it synchronises its stream before it does)
+  if (e) hipSetDevice(e->device);
+  if (d->table) hipFree(d->table);
+  if (d->keys) hipFree(d->keys);
+  delete d;
+}
+
+int tad_keydict_encode(tad_engine *eng, tad_keydict *d, const tad_key_columns *kc, uint64_t *key_id, uint64_t *key_id2, uint64_t *new_first_row,
+                       uint64_t new_first_row_cap, uint64_t *num_keys_before, uint64_t *num_keys) {
+  return kd_run(eng, d, kc, key_id, key_id2, new_first_row, new_first_row_cap, num_keys_before, num_keys, true);
+}
+
+int tad_keydict_lookup(tad_engine *eng, const tad_keydict *d, const tad_key_columns *kc, uint64_t *key_id, uint64_t *key_id2) {
+  return kd_run(eng, const_cast<tad_keydict *>(d), kc, key_id, key_id2, nullptr, 0, nullptr, nullptr, false);
+}
+
+int tad_keydict_num_keys(tad_engine *eng, const tad_keydict *d, uint64_t *num_keys) {
+  if (!eng || !d || !num_keys) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_num_keys: bad arguments");
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  *num_keys = d->K;
+  return TAD_OK;
+}
+
+int tad_keydict_bytes(tad_engine *eng, const tad_keydict *d, uint64_t *bytes) {
+  if (!eng || !d || !bytes) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_bytes: bad arguments");
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  *bytes = d->slots * 8 + d->key_cap * (uint64_t)kd_stride(d->n_cols) * 8;
+  return TAD_OK;
+}
+
+int tad_keydict_export(tad_engine *eng, const tad_keydict *d, uint64_t first_key, uint64_t n_keys, int64_t *const *cols, uint8_t *side) {
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_export: engine is NULL");
+  if (!d || (n_keys && !cols)) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_export: bad arguments");
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  if (first_key > d->K || n_keys > d->K - first_key)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_export: keys %llu .. %llu of %llu", (unsigned long long)first_key, (unsigned long long)(first_key + n_keys),
+                (unsigned long long)d->K);
+  if (n_keys == 0) return TAD_OK;
+  for (int c = 0; c < d->n_cols; ++c)
+    if (!cols[c]) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_export: column %d is NULL", c);
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_keydict_export: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  const size_t stride = (size_t)kd_stride(d->n_cols);
+  const uint64_t chunk = n_keys < (1ull << 20) ? n_keys : (1ull << 20);      // records cross the link a chunk at a time
+  std::vector<unsigned long long> rows;
+  try { rows.resize(chunk * stride); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
+  for (uint64_t k0 = 0; k0 < n_keys; k0 += chunk) {
+    const uint64_t cnt = n_keys - k0 < chunk ? n_keys - k0 : chunk;
+    HIP_TRY(e, hipMemcpyAsync(rows.data(), d->keys + (first_key + k0) * stride, cnt * stride * 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    for (uint64_t i = 0; i < cnt; ++i) {
+      const unsigned long long *rec = rows.data() + i * stride;
+      if (side) side[k0 + i] = (uint8_t)rec[0];
+      for (int c = 0; c < d->n_cols; ++c) cols[c][k0 + i] = (int64_t)rec[c + 1];
+    }
+  }
+  return TAD_OK;
+}
+
+int tad_keydict_import(tad_engine *eng, tad_keydict *d, uint64_t n_keys, const int64_t *const *cols, const uint8_t *side) {
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_import: engine is NULL");
+  if (!d || (n_keys && !cols) || n_keys > kKdMaxKeys) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_import: bad arguments (fewer than 2^32 - 1 keys)");
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  if (d->K != 0) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_import: the dictionary holds %llu keys (import fills an empty one)", (unsigned long long)d->K);
+  if (n_keys == 0) return TAD_OK;
+  for (int c = 0; c < d->n_cols; ++c)
+    if (!cols[c]) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_import: column %d is NULL", c);
+  if (side)
+    for (uint64_t i = 0; i < n_keys; ++i)
+      if (side[i] > 1) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_import: side[%llu] = %u (0 = a, 1 = b)", (unsigned long long)i, (unsigned)side[i]);
+  const size_t stride = (size_t)kd_stride(d->n_cols);
+  std::vector<unsigned long long> rows;
+  try { rows.assign(n_keys * stride, 0ull); } catch (...) { return fail(eng, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
+  for (uint64_t i = 0; i < n_keys; ++i) {
+    unsigned long long *rec = rows.data() + i * stride;
+    rec[0] = side ? side[i] : 0;
+    for (int c = 0; c < d->n_cols; ++c) rec[c + 1] = (unsigned long long)cols[c][i];
+  }
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_keydict_import: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  int rc;
+  if ((rc = ensure(e, e->sp_comp_a, 256)) != TAD_OK) return rc;
+  uint32_t *flags_dev = static_cast<uint32_t *>(e->sp_comp_a.p);
+  // candidates: they become the dictionary's only when no two tuples are the same
+  const uint64_t ncap = n_keys > d->key_cap ? n_keys : d->key_cap;
+  uint64_t nslots = pow2_at_least(2 * n_keys);
+  if (nslots < d->slots) nslots = d->slots;
+  unsigned long long *nkeys = nullptr, *ntable = nullptr;
+  hipError_t r = kd_alloc(e, reinterpret_cast<void **>(&nkeys), ncap * stride * 8);
+  if (r == hipSuccess) r = kd_alloc(e, reinterpret_cast<void **>(&ntable), nslots * 8);
+  if (r == hipSuccess) r = hipMemcpyAsync(nkeys, rows.data(), n_keys * stride * 8, hipMemcpyHostToDevice, s);
+  if (r == hipSuccess) r = hipMemsetAsync(ntable, 0xFF, nslots * 8, s);
+  if (r == hipSuccess) r = hipMemsetAsync(flags_dev, 0, 4, s);
+  uint32_t flags = 0;
+  if (r == hipSuccess) {
+    launch_kd_rehash(s, nkeys, d->n_cols, n_keys, ntable, nslots, flags_dev, true);
+    r = hipMemcpyAsync(&flags, flags_dev, 4, hipMemcpyDeviceToHost, s);
+  }
+  const hipError_t rs = hipStreamSynchronize(s);
+  if (r == hipSuccess) r = rs;
+  if (r == hipSuccess) r = hipGetLastError();
+  if (r != hipSuccess || flags != 0) {
+    if (nkeys) hipFree(nkeys);
+    if (ntable) hipFree(ntable);
+    if (r != hipSuccess)
+      return fail(e, r == hipErrorOutOfMemory ? TAD_ERR_OUT_OF_MEMORY : TAD_ERR_HIP, "tad_keydict_import: %s (dictionary unchanged)", hipGetErrorString(r));
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_import: two keys hold the same tuple (dictionary unchanged)");
+  }
+  hipFree(d->keys); d->keys = nkeys; d->key_cap = ncap;
+  hipFree(d->table); d->table = ntable; d->slots = nslots;
+  d->K = n_keys;
+  return TAD_OK;
+}
+
+}  // extern "C"

@@ -675,6 +675,32 @@ void launch_encode_strings(hipStream_t s, const void *offsets, int off64, const 
                            uint64_t n, uint64_t slots, void *temp, long long *codes, uint64_t *first_row, uint64_t first_row_cap,
                            unsigned long long *num_values_dev, uint32_t **flags_dev_out);
 
+// ---- ingest: a key dictionary that outlives the call — tuples -> ids that stay the same from batch to batch (tad_keydict.hip) ----
+struct KdBatch {                    // the key tuples of one batch (device pointers)
+  const long long *a[kFzMaxCols];
+  const long long *b[kFzMaxCols];   // all NULL: one tuple per row
+  const uint8_t *keep_a, *keep_b;   // NULL = every row
+  uint64_t n;
+  int n_cols;
+  uint32_t sides;                   // 1 or 2
+};
+static constexpr uint32_t kKdMaxProbe = 32;     // a claim that probed further asks the host for a larger table
+enum : uint32_t { KD_FLAG_CLUSTER = 1u, KD_FLAG_DUPLICATE = 2u, KD_FLAG_BAD_ROW = 4u };
+int kd_stride(int n_cols);          // 8-byte words of one key record: side + columns, padded to an even count
+// every kept virtual row looks its tuple up in table[slots] / keys (K records).  miss != NULL: hits write their id, misses raise miss[v] and
+// are counted in *n_miss (zeroed by the caller), rows that are not kept get TAD_KEY_SKIP; miss == NULL: a miss is TAD_KEY_SKIP too
+void launch_kd_probe(hipStream_t s, const KdBatch &A, const unsigned long long *table, uint64_t slots, const unsigned long long *keys, uint64_t K, uint64_t *key_a,
+                     uint64_t *key_b, uint8_t *miss, unsigned long long *n_miss);
+// new key j (< m) = the tuple at virtual row first_row[j]: record K0 + j and a slot (the table must have room: load <= 1/2 afterwards)
+void launch_kd_append(hipStream_t s, const KdBatch &A, const uint64_t *first_row, uint64_t m, uint64_t K0, unsigned long long *table, uint64_t slots,
+                      unsigned long long *keys, uint32_t *flags);
+// key = K0 + batch-local id on the rows whose miss flag is raised
+void launch_kd_fix(hipStream_t s, const uint8_t *miss, const uint64_t *loc_a, const uint64_t *loc_b, uint64_t n, uint32_t sides, uint64_t K0, uint64_t *key_a,
+                   uint64_t *key_b);
+// records 0 .. K into an empty table; check_duplicates: KD_FLAG_DUPLICATE when two records hold the same tuple
+void launch_kd_rehash(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, unsigned long long *table, uint64_t slots, uint32_t *flags,
+                      bool check_duplicates);
+
 void launch_synth(hipStream_t s, uint64_t seed, uint64_t first_row, uint64_t n_rows,
                   uint64_t num_keys, uint64_t n_buckets, uint64_t *key_id, int64_t *flow_end_s,
                   uint64_t *value);
@@ -694,6 +720,7 @@ const void *code_anchor_factorize();
 const void *code_anchor_history();
 const void *code_anchor_ingest();
 const void *code_anchor_kernels();
+const void *code_anchor_keydict();
 const void *code_anchor_merge();
 const void *code_anchor_shard();
 const void *code_anchor_sparse();

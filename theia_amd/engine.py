@@ -431,6 +431,157 @@ class TadState:
             pass
 
 
+def _key_columns(engine, what, n_cols, cols_a, keep_a, cols_b, keep_b):
+    """The tad_key_columns of one batch of key tuples (KeyDict): -> (kc, n, sides, is_device, what must stay alive until the call returns)."""
+    if len(cols_a) != n_cols or (cols_b is not None and len(cols_b) != n_cols):
+        raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "%s: %d key columns on every side" % (what, n_cols))
+    keepalive = []
+
+    def col(x):
+        p, n, dev, keep = _as_column(x, np.int64)
+        keepalive.append(keep)
+        return p, n, dev
+
+    pa = [col(c) for c in cols_a]
+    n, dev = pa[0][1], pa[0][2]
+    pb = [col(c) for c in cols_b] if cols_b is not None else None
+    if any(q[1] != n or q[2] != dev for q in pa + (pb or [])):
+        raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "%s: columns must have equal length and live in the same memory" % what)
+
+    def mask(m):
+        if m is None:
+            return None
+        if isinstance(m, DeviceArray):
+            return m.ptr
+        a = np.ascontiguousarray(np.asarray(m).astype(np.uint8, copy=False))
+        if a.size != n:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "%s: mask length" % what)
+        if dev:
+            d = DeviceArray.from_host(engine, np.frombuffer(a.tobytes() + b"\0" * (-a.size % 8), dtype=np.uint64))
+            keepalive.append(d)
+            return d.ptr
+        keepalive.append(a)
+        return a.ctypes.data
+
+    ka, kb = mask(keep_a), mask(keep_b)
+    arr_a = (C.c_void_p * n_cols)(*[q[0] for q in pa])
+    arr_b = (C.c_void_p * n_cols)(*[q[0] for q in pb]) if pb is not None else None
+    kc = capi.KeyColumns(n_rows=n, n_cols=n_cols, cols_a=arr_a, keep_a=ka, cols_b=arr_b, keep_b=kb,
+                         memory=capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST)
+    keepalive += [arr_a, arr_b]
+    return kc, n, 2 if pb is not None else 1, dev, keepalive
+
+
+class KeyDict:
+    """A key dictionary that lives in HBM and outlives the call (tad_keydict): key tuples -> dense ids that stay the same from batch to
+    batch, new ids in order of first appearance — what the streaming states want for their key ids.  n_cols: the tuple width;
+    expected_keys sizes the first table (0 = the default, 1 = the smallest)."""
+
+    def __init__(self, engine, n_cols, expected_keys=0):
+        self._engine = engine
+        self._h = None
+        self.n_cols = int(n_cols)
+        if not (getattr(engine._lib, "tad_features", None) and engine._lib.tad_features() & capi.TAD_FEATURE_KEY_DICT):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no key dictionary (TAD_FEATURE_KEY_DICT)")
+        h = C.c_void_p()
+        engine._check(engine._lib.tad_keydict_create(engine._h, self.n_cols, int(expected_keys), C.byref(h)))
+        self._h = h
+
+    def encode(self, cols_a, keep_a=None, cols_b=None, keep_b=None, max_new=None):
+        """One batch.  cols_a / keep_a / cols_b / keep_b: as TadEngine.factorize (numpy arrays on the host, or DeviceArrays all on the
+        device).  Returns (key_id u64[n], key_id2 u64[n] or None, new_first_row, num_keys_before), in the memory the inputs live in:
+        known tuples keep their ids, new ones get num_keys_before, num_keys_before + 1, ... in order of first appearance over the
+        virtual rows [side a ++ side b], TAD_KEY_SKIP where the mask is 0; new_first_row[j] = the virtual row of this batch where key
+        num_keys_before + j first appears (at most max_new entries; None = all of them)."""
+        eng = self._engine
+        kc, n, sides, dev, keepalive = _key_columns(eng, "KeyDict.encode", self.n_cols, cols_a, keep_a, cols_b, keep_b)
+        cap = int(max_new) if max_new is not None else n * sides
+        before, after = capi.u64(), capi.u64()
+        if dev:
+            key1 = DeviceArray(eng, n, np.uint64)
+            key2 = DeviceArray(eng, n, np.uint64) if sides == 2 else None
+            first = DeviceArray(eng, max(cap, 1), np.uint64)
+            ptrs = (key1.ptr, key2.ptr if key2 is not None else None, first.ptr)
+        else:
+            key1 = np.empty(n, dtype=np.uint64)
+            key2 = np.empty(n, dtype=np.uint64) if sides == 2 else None
+            first = np.empty(max(cap, 1), dtype=np.uint64)
+            ptrs = (key1.ctypes.data, key2.ctypes.data if key2 is not None else None, first.ctypes.data)
+        rc = eng._lib.tad_keydict_encode(eng._h, self._h, C.byref(kc), ptrs[0], ptrs[1], ptrs[2], cap, C.byref(before), C.byref(after))
+        del keepalive
+        eng._check(rc)
+        listed = min(int(after.value - before.value), cap)
+        if dev:
+            first.n = listed
+        else:
+            first = first[:listed]
+        return key1, key2, first, int(before.value)
+
+    def lookup(self, cols_a, keep_a=None, cols_b=None, keep_b=None):
+        """encode() read-only (tad_keydict_lookup): (key_id, key_id2 or None); an unknown tuple gets TAD_KEY_SKIP, the dictionary is unchanged"""
+        eng = self._engine
+        kc, n, sides, dev, keepalive = _key_columns(eng, "KeyDict.lookup", self.n_cols, cols_a, keep_a, cols_b, keep_b)
+        if dev:
+            key1 = DeviceArray(eng, n, np.uint64)
+            key2 = DeviceArray(eng, n, np.uint64) if sides == 2 else None
+            ptrs = (key1.ptr, key2.ptr if key2 is not None else None)
+        else:
+            key1 = np.empty(n, dtype=np.uint64)
+            key2 = np.empty(n, dtype=np.uint64) if sides == 2 else None
+            ptrs = (key1.ctypes.data, key2.ctypes.data if key2 is not None else None)
+        rc = eng._lib.tad_keydict_lookup(eng._h, self._h, C.byref(kc), ptrs[0], ptrs[1])
+        del keepalive
+        eng._check(rc)
+        return key1, key2
+
+    def num_keys(self):
+        """keys held (tad_keydict_num_keys)"""
+        n = capi.u64()
+        self._engine._check(self._engine._lib.tad_keydict_num_keys(self._engine._h, self._h, C.byref(n)))
+        return int(n.value)
+
+    def nbytes(self):
+        """device bytes the dictionary holds: the table and the key records at their capacity (tad_keydict_bytes)"""
+        n = capi.u64()
+        self._engine._check(self._engine._lib.tad_keydict_bytes(self._engine._h, self._h, C.byref(n)))
+        return int(n.value)
+
+    def export(self, first_key=0, n_keys=None):
+        """(cols: list of n_cols int64 arrays, side uint8 array) of the keys [first_key, first_key + n_keys) (tad_keydict_export);
+        n_keys None = up to the last key"""
+        if n_keys is None:
+            n_keys = max(self.num_keys() - int(first_key), 0)
+        cols = [np.zeros(int(n_keys), np.int64) for _ in range(self.n_cols)]
+        side = np.zeros(int(n_keys), np.uint8)
+        ptrs = (C.c_void_p * self.n_cols)(*[c.ctypes.data for c in cols])
+        self._engine._check(self._engine._lib.tad_keydict_export(self._engine._h, self._h, int(first_key), int(n_keys), ptrs, side.ctypes.data))
+        return cols, side
+
+    def load(self, cols, side=None):
+        """Fill this EMPTY dictionary so that key i is tuple i (tad_keydict_import): what export() returned, after a restart.
+        side None = every key on side 0."""
+        if len(cols) != self.n_cols:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "KeyDict.load: %d key columns" % self.n_cols)
+        arrs = [np.ascontiguousarray(c, dtype=np.int64) for c in cols]
+        n = arrs[0].size
+        sd = np.ascontiguousarray(side, dtype=np.uint8) if side is not None else None
+        if any(a.shape != (n,) for a in arrs) or (sd is not None and sd.shape != (n,)):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "KeyDict.load: columns and side must have equal length")
+        ptrs = (C.c_void_p * self.n_cols)(*[a.ctypes.data for a in arrs])
+        self._engine._check(self._engine._lib.tad_keydict_import(self._engine._h, self._h, n, ptrs, sd.ctypes.data if sd is not None else None))
+
+    def close(self):
+        if self._h is not None and self._engine._h is not None:
+            self._engine._lib.tad_keydict_destroy(self._engine._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class TadEngine:
     """One engine per GPU.  Thread-safe: up to max_jobs_in_flight jobs (0 = the library's default, 4) run concurrently, each on its own
     job context (HIP stream + workspace) inside the library; further callers wait."""
@@ -778,6 +929,12 @@ class TadEngine:
         self._check(rc)
         first = first[:min(int(nk.value), cap)]
         return (key1, key2, first, hist) if with_hist else (key1, key2, first)
+
+    # ---- ingest for the streaming states: key ids that stay the same from batch to batch (tad_keydict) ----
+    def key_dict(self, n_cols, expected_keys=0):
+        """A persistent key dictionary for tuples of n_cols int64 columns (KeyDict): encode every batch through it, resize the state
+        when num_keys grew, then run_stream / merge_stream with num_keys = the dictionary's."""
+        return KeyDict(self, n_cols, expected_keys)
 
     # ---- ingest, one step earlier: an Arrow string column -> dictionary codes (tad_encode_strings) ----
     def encode_strings(self, column, max_values=None):

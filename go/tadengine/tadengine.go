@@ -1350,6 +1350,87 @@ func (d *KeyDict) Import(cols [][]int64, side []byte) error {
 	return nil
 }
 
+var keyRetireOnce sync.Once
+var keyRetireOK bool
+
+// hasKeyRetire: the library knows tad_state_compact / tad_keydict_compact (tad_features); an older one would not export the calls.
+func hasKeyRetire() bool {
+	keyRetireOnce.Do(func() { keyRetireOK = C.tad_features()&C.TAD_FEATURE_KEY_RETIRE != 0 })
+	return keyRetireOK
+}
+
+// KeySkip is remap's entry for a retired key (TAD_KEY_SKIP).
+const KeySkip = ^uint64(0)
+
+// CompactStats is what one State.Compact retired and moved (tad_compact_stats).
+type CompactStats struct {
+	KeysBefore, KeysAfter uint64 // keys held at entry; survivors
+	NumKeys               uint64 // keys held at exit: max(survivors, 1)
+	KeysUnseen, KeysIdle  uint64 // retired without a point; retired because the newest point is older than retireBefore
+	PointsDropped         uint64 // the points of the idle keys
+	SeriesPointsMoved     uint64
+	HistoryPointsMoved    uint64
+	BytesBefore           uint64
+	BytesAfter            uint64
+	MsTotal               float32
+}
+
+// Compact drops the dead keys of the state and renumbers the survivors densely, order kept (tad_state_compact).  A key survives iff it
+// holds points and, with retireBefore != 0, its newest point is at or after retireBefore.  numKeys = the keys the state holds now.
+// remap[k] = the new id of old key k, or KeySkip: pass it to KeyDict.Compact and apply it to the host's key table.  The state then holds
+// CompactStats.NumKeys keys.  On a tick after Trim, not per batch.
+func (s *State) Compact(numKeys uint64, retireBefore int64) (remap []uint64, st CompactStats, err error) {
+	if !hasKeyRetire() {
+		return nil, CompactStats{}, errors.New("tadengine: libtad_mi355x.so has no tad_state_compact (TAD_FEATURE_KEY_RETIRE)")
+	}
+	if numKeys == 0 {
+		return nil, CompactStats{}, IllegalArgument{"tadengine: Compact needs the state's key count"}
+	}
+	// the remap lives in C memory for the call (the library writes it from its own stream)
+	buf := (*C.uint64_t)(C.calloc(C.size_t(numKeys), 8))
+	if buf == nil {
+		return nil, CompactStats{}, errors.New("tadengine: out of memory")
+	}
+	defer C.free(unsafe.Pointer(buf))
+	var cs C.tad_compact_stats
+	if rc := C.tad_state_compact(s.e.h, s.h, C.int64_t(retireBefore), buf, C.TAD_MEM_HOST, &cs); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, CompactStats{}, IllegalArgument{msg}
+		}
+		return nil, CompactStats{}, fmt.Errorf("tad_state_compact: %s (code %d)", msg, int(rc))
+	}
+	if uint64(cs.keys_before) != numKeys {
+		return nil, CompactStats{}, IllegalArgument{fmt.Sprintf("tadengine: Compact was told %d keys, the state held %d", numKeys, uint64(cs.keys_before))}
+	}
+	remap = make([]uint64, numKeys)
+	copy(remap, unsafe.Slice((*uint64)(unsafe.Pointer(buf)), numKeys))
+	return remap, CompactStats{KeysBefore: uint64(cs.keys_before), KeysAfter: uint64(cs.keys_after), NumKeys: uint64(cs.num_keys),
+		KeysUnseen: uint64(cs.keys_unseen), KeysIdle: uint64(cs.keys_idle), PointsDropped: uint64(cs.points_dropped),
+		SeriesPointsMoved: uint64(cs.series_points_moved), HistoryPointsMoved: uint64(cs.history_points_moved),
+		BytesBefore: uint64(cs.bytes_before), BytesAfter: uint64(cs.bytes_after), MsTotal: float32(cs.ms_total)}, nil
+}
+
+// Compact applies the remap of State.Compact to the dictionary (tad_keydict_compact): a survivor's tuple now encodes to remap[old id], a
+// retired tuple is forgotten and gets a new id at the end when it returns.  len(remap) must be the dictionary's NumKeys; a remap that is
+// not the one State.Compact writes is an IllegalArgument and leaves the dictionary unchanged.  Returns the keys held afterwards.
+func (d *KeyDict) Compact(remap []uint64) (uint64, error) {
+	if !hasKeyRetire() {
+		return 0, errors.New("tadengine: libtad_mi355x.so has no tad_keydict_compact (TAD_FEATURE_KEY_RETIRE)")
+	}
+	buf := (*C.uint64_t)(cColumn(remap))
+	defer C.free(unsafe.Pointer(buf))
+	var n C.uint64_t
+	if rc := C.tad_keydict_compact(d.e.h, d.h, buf, C.uint64_t(len(remap)), C.TAD_MEM_HOST, &n); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(d.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return 0, IllegalArgument{msg}
+		}
+		return 0, fmt.Errorf("tad_keydict_compact: %s (code %d)", msg, int(rc))
+	}
+	return uint64(n), nil
+}
+
 func (e *Engine) NewState(numKeys uint64) (*State, error) {
 	var h *C.tad_state
 	if rc := C.tad_state_create(e.h, C.uint64_t(numKeys), &h); rc != C.TAD_OK {

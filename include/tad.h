@@ -674,7 +674,7 @@ int tad_window_history_by_sort(uint64_t window_points, uint64_t state_points);
  *   - *num_keys_before and *num_keys (either may be NULL) = the keys held before and after the call.
  * One-sided batches: after batches 1..b the ids of batch b's rows equal what tad_factorize returns for those rows when called once on the
  * concatenation of batches 1..b.  Two-sided batches are numbered in the sequential order b1.a, b1.b, b2.a, b2.b, ...  Ids are never
- * reused or moved.  Limits: n_rows * sides < 2^32 - 1 per batch, fewer than 2^32 - 1 keys per dictionary.  An empty batch is TAD_OK.
+ * reused or moved, except by tad_keydict_compact (below), which the caller asks for.  Limits: n_rows * sides < 2^32 - 1 per batch, fewer than 2^32 - 1 keys per dictionary.  An empty batch is TAD_OK.
  * tad_keydict_lookup is tad_keydict_encode read-only: an unknown tuple gets TAD_KEY_SKIP and the dictionary is unchanged.
  * tad_keydict_export writes the tuples of the keys [first_key, first_key + n_keys) into n_cols HOST arrays of n_keys entries (cols[c][i] =
  * column c of key first_key + i) and their sides into side[n_keys] (HOST, may be NULL).  tad_keydict_import fills an EMPTY dictionary so
@@ -707,6 +707,62 @@ int tad_keydict_num_keys(tad_engine *e, const tad_keydict *d, uint64_t *num_keys
 int tad_keydict_bytes(tad_engine *e, const tad_keydict *d, uint64_t *bytes);
 int tad_keydict_export(tad_engine *e, const tad_keydict *d, uint64_t first_key, uint64_t n_keys, int64_t *const *cols, uint8_t *side);
 int tad_keydict_import(tad_engine *e, tad_keydict *d, uint64_t n_keys, const int64_t *const *cols, const uint8_t *side);
+
+/* ---- retiring dead keys: a state and its dictionary compacted (TAD_FEATURE_KEY_RETIRE; check tad_features() before calling these) ----
+ * Key ids are handed out in order of first appearance, and with per-connection keys (TAD_AGG_NONE: the tuple carries ports and
+ * flowStartSeconds) every new connection is a new key.  A state trimmed to "the last 24 h" still kept moments, offsets, a key record and
+ * table slots for every connection it ever saw, and every stream batch walked all of them.  These two calls take the dead keys out: one
+ * drops them from a state and renumbers the survivors densely, the other applies the same renumbering to the dictionary.  Nothing is
+ * recomputed: what a survivor holds is moved, bit for bit.
+ * tad_state_compact, on every kind of state (plain, history, series, series + times, all of them):
+ *   - key k survives iff n[k] > 0 and (retire_before_t == 0 or last_t[k] >= retire_before_t); 0 means "no time rule", as keep_from_t
+ *     does in tad_state_trim.  So an unseen key (never fed, or emptied by a trim) always goes, an idle key goes by its newest time;
+ *   - a survivor's new id is the number of survivors below it: the relative order — order of first appearance — is kept;
+ *   - remap (required; keys_before = the state's num_keys entries, in remap_memory): remap[k] = the new id of old key k, or
+ *     TAD_KEY_SKIP for a retired key.  The host maps its own key table and any key ids it still holds through it;
+ *   - afterwards the state is bit for bit a fresh state with the same flags and max(m, 1) keys (m survivors; a state never holds fewer
+ *     than one key) into which the survivors' exports were imported — moments, history, series and times: survivor j holds old key k's
+ *     entries unchanged.  With m == 0 the one remaining key is unseen;
+ *   - so any later tad_run_stream, tad_state_merge, tad_state_trim or tad_run_state(_window) on the compacted state, with key ids passed
+ *     through remap, gives what the same call gives on the uncompacted state, minus the retired keys' rows.
+ * Atomic, like a trim: only candidate copies and job-context workspace are written, and they are swapped in together; any failure —
+ * allocation, workspace over workspace_limit (TAD_ERR_GRID_TOO_LARGE), a HIP error — leaves the state exactly as it was.  A state whose
+ * times are stale is refused, as a trim refuses it.  When nothing is retired the call is TAD_OK, remap is the identity, the state is
+ * untouched and nothing is reallocated.  When only unseen keys go (points_dropped == 0) every arena already holds exactly the survivors'
+ * segments in order: no arena element is moved, only the moment blocks and the offsets are rebuilt at the new key count.  Otherwise the
+ * arenas are gathered into the candidates and the trim's shrink rule applies: below a quarter of its capacity an arena is allocated anew
+ * at twice its length.  Workspace: about 68 B per key of the state before the call, plus 8 B per key for a remap in host memory.
+ * Lock order: the state, then a job context.
+ * tad_keydict_compact applies a remap to the dictionary: remap_len must equal the dictionary's num_keys (resize the state to the
+ * dictionary's keys first, as the ingest recipe does), and the entries that are not TAD_KEY_SKIP must be exactly 0, 1, ..., m - 1,
+ * strictly increasing with k (checked on the device).  Any other remap — a wrong length, a swapped pair, a duplicate, a gap — is
+ * TAD_ERR_INVALID_ARGUMENT and the dictionary stays unchanged.  Afterwards the dictionary is what a fresh one holds after
+ * tad_keydict_import of the surviving tuples (sides included) in new-id order: a survivor encodes and looks up to remap[old id], a
+ * retired tuple looks up to TAD_KEY_SKIP, and tad_keydict_encode gives a retired tuple that returns a new id at the end (m, m + 1, ...).
+ * The table and the key records are rebuilt at the size tad_keydict_create(expected_keys = 2 m) would pick (the minimum for m == 0) and
+ * never larger than before, so tad_keydict_bytes does not grow.  Fresh allocations are filled first and swapped in last: any failure
+ * leaves the dictionary as it was.  *num_keys (may be NULL) = the keys held afterwards.  Lock order: the dictionary, then a job context. */
+#define TAD_FEATURE_KEY_RETIRE 256u   /* tad_state_compact / tad_keydict_compact: dead keys dropped, the survivors renumbered densely */
+typedef struct {
+  uint64_t keys_before;              /* the state's num_keys at entry */
+  uint64_t keys_after;               /* surviving keys m */
+  uint64_t num_keys;                 /* the state's num_keys at exit: max(m, 1) — a state never holds fewer than one key */
+  uint64_t keys_unseen;              /* retired because n == 0 */
+  uint64_t keys_idle;                /* retired because last_t < retire_before_t (n > 0) */
+  uint64_t points_dropped;           /* sum of n over the idle-retired keys */
+  uint64_t series_points_moved;      /* arena elements copied; 0 when points_dropped == 0 */
+  uint64_t history_points_moved;
+  uint64_t bytes_before;             /* tad_state_bytes at entry ... */
+  uint64_t bytes_after;              /* ... and at exit */
+  int32_t job_context;
+  int32_t reserved;
+  float ms_total;                    /* HIP events */
+  float reserved1;
+} tad_compact_stats;
+int tad_state_compact(tad_engine *e, tad_state *s, int64_t retire_before_t, uint64_t *remap, tad_mem remap_memory,
+                      tad_compact_stats *stats /* may be NULL */);
+int tad_keydict_compact(tad_engine *e, tad_keydict *d, const uint64_t *remap, uint64_t remap_len, tad_mem remap_memory,
+                        uint64_t *num_keys /* may be NULL */);
 
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).

@@ -29,6 +29,7 @@ TAD_FEATURE_STATE_RUN = 16                   # tad_features() bit: tad_run_state
 TAD_FEATURE_STATE_MERGE = 32                 # tad_features() bit: tad_state_merge, a batch placed by time (late, re-sent and split rows)
 TAD_FEATURE_STATE_WINDOW = 64                # tad_features() bit: tad_run_state_window, tad_run_state over a time range of the state, read-only
 TAD_FEATURE_KEY_DICT = 128                   # tad_features() bit: tad_keydict, a persistent tuple -> key id dictionary on the device
+TAD_FEATURE_KEY_RETIRE = 256                 # tad_features() bit: tad_state_compact / tad_keydict_compact, dead keys dropped and the rest renumbered
 
 
 class Plan(C.Structure):
@@ -116,6 +117,13 @@ class MergeStats(C.Structure):
                 ("ms_stage0", f32), ("ms_merge", f32), ("ms_total", f32), ("reserved1", f32)]
 
 
+class CompactStats(C.Structure):
+    """tad_compact_stats: what one tad_state_compact call retired and moved."""
+    _fields_ = [("keys_before", u64), ("keys_after", u64), ("num_keys", u64), ("keys_unseen", u64), ("keys_idle", u64), ("points_dropped", u64),
+                ("series_points_moved", u64), ("history_points_moved", u64), ("bytes_before", u64), ("bytes_after", u64),
+                ("job_context", i32), ("reserved", i32), ("ms_total", f32), ("reserved1", f32)]
+
+
 class Points(C.Structure):
     _fields_ = [("n_points", u64), ("key_id", C.c_void_p), ("flow_end_s", C.c_void_p), ("value", C.c_void_p),
                 ("memory", C.c_int), ("stats", Stats)]
@@ -165,6 +173,8 @@ SYMBOLS = {
     "tad_keydict_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(u64)]),
     "tad_keydict_export": (C.c_int, [C.c_void_p, C.c_void_p, u64, u64, C.POINTER(C.c_void_p), C.c_void_p]),
     "tad_keydict_import": (C.c_int, [C.c_void_p, C.c_void_p, u64, C.POINTER(C.c_void_p), C.c_void_p]),
+    "tad_state_compact": (C.c_int, [C.c_void_p, C.c_void_p, i64, C.c_void_p, C.c_int, C.POINTER(CompactStats)]),
+    "tad_keydict_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
     "tad_encode_strings": (C.c_int, [C.c_void_p, C.POINTER(StringColumn), C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]),
     "tad_widen_column": (C.c_int, [C.c_void_p, C.c_void_p, i32, i32, C.c_int, u64, C.c_void_p, u64, C.c_void_p]),
     "tad_mask_rows": (C.c_int, [C.c_void_p, u64, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(u64), i32, C.c_void_p]),

@@ -279,7 +279,7 @@ int grow_arena(JobCtx *e, T *&val, uint64_t &cap, uint64_t need, const char *wha
 // written, allocated anew at twice the length (how a trimmed state's memory actually shrinks); a candidate too small grows to twice the
 // length too.  Only candidate arenas come here, so a failure leaves the state as it is.
 template <typename T>
-int size_trim_arena(JobCtx *e, T *&val, uint64_t &cap, uint64_t len, bool allocate) {
+int size_trim_arena(JobCtx *e, T *&val, uint64_t &cap, uint64_t len, bool allocate, const char *who = "tad_state_trim") {
   if (cap >= len && !(len * 4 < cap)) return TAD_OK;
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   if (val) hipFree(val);
@@ -290,7 +290,7 @@ int size_trim_arena(JobCtx *e, T *&val, uint64_t &cap, uint64_t len, bool alloca
   const hipError_t r = hipMalloc(&p, 2 * len * sizeof(T));
   if (r != hipSuccess) {
     (void)hipGetLastError();
-    return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_trim: %llu retained values do not fit (%s); state unchanged", (unsigned long long)len,
+    return fail(e, TAD_ERR_OUT_OF_MEMORY, "%s: %llu retained values do not fit (%s); state unchanged", who, (unsigned long long)len,
                 hipGetErrorString(r));
   }
   val = static_cast<T *>(p);
@@ -2157,15 +2157,20 @@ int tad_state_import_times(tad_engine *eng, tad_state *st, const int64_t *t) {
   return TAD_OK;
 }
 
-int tad_state_bytes(tad_engine *eng, const tad_state *st, uint64_t *bytes) {
-  if (!eng || !st || !bytes) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_bytes: bad arguments");
-  std::lock_guard<std::mutex> state_lk(st->mu);
+// tad_state_bytes with the state's lock held
+static uint64_t state_device_bytes(const tad_state *st) {
   const uint64_t off = 2 * (st->K + 1) * 8;   // both copies of a key-offset array
   uint64_t b = 2 * (uint64_t)state_bytes(st->K);
   if (st->history) b += off + (st->hist_cap[0] + st->hist_cap[1]) * 8;
   if (st->series) b += off + (st->ser_cap[0] + st->ser_cap[1]) * 8;
   if (st->times) b += (st->ser_tcap[0] + st->ser_tcap[1]) * 8;
-  *bytes = b;
+  return b;
+}
+
+int tad_state_bytes(tad_engine *eng, const tad_state *st, uint64_t *bytes) {
+  if (!eng || !st || !bytes) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_bytes: bad arguments");
+  std::lock_guard<std::mutex> state_lk(st->mu);
+  *bytes = state_device_bytes(st);
   return TAD_OK;
 }
 
@@ -2246,6 +2251,154 @@ int tad_state_trim(tad_engine *eng, tad_state *st, uint64_t keep_points, int64_t
   if (st->times) (void)size_trim_arena(e, st->ser_t[cur], st->ser_tcap[cur], kept, false);
   if (st->history) (void)size_trim_arena(e, st->hist_val[cur], st->hist_cap[cur], kept, false);
   if (dropped) *dropped = evicted;
+  return TAD_OK;
+}
+
+// tad.h: the unseen and the idle keys leave, the survivors are renumbered densely (kernels in tad_compact.hip).  Fresh moment blocks and
+// offsets at the new key count and, when points leave, the candidate arenas are written; they become the state's together once every
+// launch has succeeded.
+int tad_state_compact(tad_engine *eng, tad_state *st, int64_t retire_before_t, uint64_t *remap, tad_mem remap_memory, tad_compact_stats *stats) {
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_state_compact: engine is NULL");
+  if (!st || !remap || (remap_memory != TAD_MEM_HOST && remap_memory != TAD_MEM_DEVICE))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_compact: bad arguments (state, remap of num_keys entries in host or device memory); state unchanged");
+  std::lock_guard<std::mutex> state_lk(st->mu);   // (the order of tad_run_stream: the state, then a job context)
+  if (st->times_stale)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_compact: the series was imported without its times (tad_state_import_times)");
+  const uint64_t K = st->K;
+  const int cur = st->cur, cand = cur ^ 1;
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_compact: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  const bool host_remap = remap_memory == TAD_MEM_HOST;
+  // workspace: hs_kcnt = live | series lengths | history lengths | series chunks | history chunks | counters; hs_koff = new ids | candidate
+  // series offsets | candidate history offsets | series chunk offsets | history chunk offsets, K + 1 each; in_key = a host remap's staging
+  const size_t kpad = (size_t)((K + 3) & ~3ull);
+  const size_t cnt_bytes = kpad * 20 + 64, off_bytes = (kpad + 4) * 40, scan_bytes = scan_scratch_elems(K) * sizeof(unsigned long long);
+  const size_t need = cnt_bytes + off_bytes + scan_bytes + (host_remap ? (size_t)K * 8 : 0);
+  if (need > e->ws_limit)
+    return fail(e, TAD_ERR_GRID_TOO_LARGE, "tad_state_compact needs %llu bytes of scratch > workspace limit %llu; state unchanged", (unsigned long long)need,
+                (unsigned long long)e->ws_limit);
+  int rc;
+  if ((rc = ensure(e, e->hs_kcnt, cnt_bytes)) != TAD_OK || (rc = ensure(e, e->hs_koff, off_bytes)) != TAD_OK ||
+      (rc = ensure(e, e->scan_scratch, scan_bytes)) != TAD_OK || (host_remap && (rc = ensure(e, e->in_key, (size_t)K * 8)) != TAD_OK))
+    return rc;
+  uint32_t *live = static_cast<uint32_t *>(e->hs_kcnt.p), *slen = live + kpad, *hlen = slen + kpad, *schunks = hlen + kpad, *hchunks = schunks + kpad;
+  CompactCounters *cc = reinterpret_cast<CompactCounters *>(hchunks + kpad);
+  unsigned long long *newid = static_cast<unsigned long long *>(e->hs_koff.p), *sscan = newid + kpad + 4, *hscan = sscan + kpad + 4,
+                     *scoff = hscan + kpad + 4, *hcoff = scoff + kpad + 4;
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  unsigned long long *d_remap = host_remap ? static_cast<unsigned long long *>(e->in_key.p) : reinterpret_cast<unsigned long long *>(remap);
+  const StreamState cur_view = state_view(st, cur);
+  // 1. who survives, what it keeps; 2. the new ids, the candidate offsets and the chunk offsets; one round trip for the totals
+  HIP_TRY(e, hipEventRecord(e->ev[0], s));
+  HIP_TRY(e, hipMemsetAsync(cc, 0, sizeof(CompactCounters), s));
+  launch_compact_mark(s, K, cur_view, st->series ? st->ser_off[cur] : nullptr, st->history ? st->hist_off[cur] : nullptr, (long long)retire_before_t, live,
+                      slen, hlen, schunks, hchunks, cc);
+  launch_scan(s, live, newid, K, scratch);
+  launch_scan(s, slen, sscan, K, scratch);
+  launch_scan(s, hlen, hscan, K, scratch);
+  launch_scan(s, schunks, scoff, K, scratch);
+  launch_scan(s, hchunks, hcoff, K, scratch);
+  HIP_TRY(e, hipGetLastError());
+  unsigned long long *tot = reinterpret_cast<unsigned long long *>(e->tail_host);
+  const unsigned long long *tails[5] = {newid + K, sscan + K, hscan + K, scoff + K, hcoff + K};
+  for (int i = 0; i < 5; ++i) HIP_TRY(e, hipMemcpyAsync(tot + i, tails[i], 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(tot + 5, cc, 24, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  const uint64_t m = tot[0], skept = tot[1], hkept = tot[2], s_chunks = tot[3], h_chunks = tot[4];
+  const uint64_t n_unseen = tot[5], n_idle = tot[6], dropped = tot[7];
+  if (m > K || m + n_unseen + n_idle != K) return fail(e, TAD_ERR_HIP, "tad_state_compact: %llu survivors of %llu keys; state unchanged", (unsigned long long)m, (unsigned long long)K);
+  tad_compact_stats cs{};
+  cs.keys_before = K;
+  cs.keys_after = m;
+  cs.keys_unseen = n_unseen;
+  cs.keys_idle = n_idle;
+  cs.points_dropped = dropped;
+  cs.bytes_before = state_device_bytes(st);
+  cs.job_context = e->index;
+  auto remap_out = [&]() -> int {
+    if (host_remap) HIP_TRY(e, hipMemcpyAsync(remap, d_remap, K * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipEventRecord(e->ev[1], s));
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipStreamSynchronize(s));
+    HIP_TRY(e, hipEventElapsedTime(&cs.ms_total, e->ev[0], e->ev[1]));
+    return TAD_OK;
+  };
+  if (m == K) {   // nothing retired: the identity, the state as it is
+    launch_compact_keys(s, K, live, newid, sscan, hscan, false, cur_view, cur_view, nullptr, nullptr, d_remap);
+    if ((rc = remap_out()) != TAD_OK) return rc;
+    cs.num_keys = K;
+    cs.bytes_after = cs.bytes_before;
+    if (stats) *stats = cs;
+    return TAD_OK;
+  }
+  // 3. fresh moment blocks and offsets for max(m, 1) keys, all zero: with no survivor the one key left is unseen and its segments empty
+  const uint64_t Km = m ? m : 1;
+  const bool gather = dropped != 0;        // only unseen keys went: the arenas already are the survivors' segments in order
+  const int to = gather ? cand : cur;      // the copy that is current afterwards
+  tad_state fresh;
+  fresh.K = Km;
+  hipError_t r = hipSuccess;
+  for (int i = 0; i < 2 && r == hipSuccess; ++i) {
+    r = hipMalloc(&fresh.block[i], state_bytes(Km));
+    if (r == hipSuccess) r = hipMemsetAsync(fresh.block[i], 0, state_bytes(Km), s);
+    if (r == hipSuccess && st->history) r = hipMalloc(reinterpret_cast<void **>(&fresh.hist_off[i]), (Km + 1) * 8);
+    if (r == hipSuccess && st->history) r = hipMemsetAsync(fresh.hist_off[i], 0, (Km + 1) * 8, s);
+    if (r == hipSuccess && st->series) r = hipMalloc(reinterpret_cast<void **>(&fresh.ser_off[i]), (Km + 1) * 8);
+    if (r == hipSuccess && st->series) r = hipMemsetAsync(fresh.ser_off[i], 0, (Km + 1) * 8, s);
+  }
+  auto drop_fresh = [&]() {
+    (void)hipStreamSynchronize(s);
+    for (int i = 0; i < 2; ++i) {
+      if (fresh.block[i]) hipFree(fresh.block[i]);
+      if (fresh.hist_off[i]) hipFree(fresh.hist_off[i]);
+      if (fresh.ser_off[i]) hipFree(fresh.ser_off[i]);
+    }
+  };
+  if (r != hipSuccess) {
+    (void)hipGetLastError();
+    drop_fresh();
+    return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_compact: %s (state unchanged)", hipGetErrorString(r));
+  }
+  rc = TAD_OK;
+  if (gather) {   // the candidate arenas at their new size (the trim's rule): an allocation failure leaves the state as it is
+    const char *who = "tad_state_compact";
+    if (st->series) rc = size_trim_arena(e, st->ser_val[cand], st->ser_cap[cand], skept, true, who);
+    if (rc == TAD_OK && st->times) rc = size_trim_arena(e, st->ser_t[cand], st->ser_tcap[cand], skept, true, who);
+    if (rc == TAD_OK && st->history) rc = size_trim_arena(e, st->hist_val[cand], st->hist_cap[cand], hkept, true, who);
+  }
+  if (rc != TAD_OK) { drop_fresh(); return rc; }
+  // 4. the survivors' moments and offsets, remap; 5. their segments
+  launch_compact_keys(s, K, live, newid, sscan, hscan, true, cur_view, stream_view(fresh.block[to], Km), st->series ? fresh.ser_off[to] : nullptr,
+                      st->history ? fresh.hist_off[to] : nullptr, d_remap);
+  if (gather && st->series)
+    launch_compact_copy(s, s_chunks, scoff, K, st->ser_off[cur], st->ser_val[cur], st->times ? st->ser_t[cur] : nullptr, sscan, st->ser_val[cand],
+                        st->times ? st->ser_t[cand] : nullptr);
+  if (gather && st->history) launch_compact_copy(s, h_chunks, hcoff, K, st->hist_off[cur], st->hist_val[cur], nullptr, hscan, st->hist_val[cand], nullptr);
+  if ((rc = remap_out()) != TAD_OK) { drop_fresh(); return rc; }
+  // everything succeeded: the fresh blocks and offsets replace the old ones; after a gather the candidate arenas become current and the
+  // old ones, now the candidates, are given back when far too big
+  for (int i = 0; i < 2; ++i) {
+    hipFree(st->block[i]); st->block[i] = fresh.block[i];
+    if (st->history) { hipFree(st->hist_off[i]); st->hist_off[i] = fresh.hist_off[i]; }
+    if (st->series) { hipFree(st->ser_off[i]); st->ser_off[i] = fresh.ser_off[i]; }
+  }
+  st->K = Km;
+  if (gather) {
+    if (st->series) st->ser_len[cand] = skept;
+    if (st->history) st->hist_len[cand] = hkept;
+    st->cur = cand;
+    if (st->series) (void)size_trim_arena(e, st->ser_val[cur], st->ser_cap[cur], skept, false);
+    if (st->times) (void)size_trim_arena(e, st->ser_t[cur], st->ser_tcap[cur], skept, false);
+    if (st->history) (void)size_trim_arena(e, st->hist_val[cur], st->hist_cap[cur], hkept, false);
+    cs.series_points_moved = st->series ? skept : 0;
+    cs.history_points_moved = st->history ? hkept : 0;
+  }
+  cs.num_keys = Km;
+  cs.bytes_after = state_device_bytes(st);
+  if (stats) *stats = cs;
   return TAD_OK;
 }
 

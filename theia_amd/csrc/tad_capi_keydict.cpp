@@ -358,4 +358,83 @@ int tad_keydict_import(tad_engine *eng, tad_keydict *d, uint64_t n_keys, const i
   return TAD_OK;
 }
 
+// tad.h: the renumbering of tad_state_compact applied to the dictionary (kernels in tad_compact.hip).  The check runs first and alone;
+// then fresh records and a fresh table are filled and swapped in.
+int tad_keydict_compact(tad_engine *eng, tad_keydict *d, const uint64_t *remap, uint64_t remap_len, tad_mem remap_memory, uint64_t *num_keys) {
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_compact: engine is NULL");
+  if (!d || (remap_len && !remap) || (remap_memory != TAD_MEM_HOST && remap_memory != TAD_MEM_DEVICE))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_compact: bad arguments (dictionary, remap in host or device memory); dictionary unchanged");
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  const uint64_t K = d->K;
+  if (remap_len != K)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_compact: remap has %llu entries, the dictionary holds %llu keys (dictionary unchanged)",
+                (unsigned long long)remap_len, (unsigned long long)K);
+  if (num_keys) *num_keys = K;
+  if (K == 0) return TAD_OK;
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_keydict_compact: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  const bool host = remap_memory == TAD_MEM_HOST;
+  // scratch: in_key = a host remap; sp_comp_a = live flags | error word; sp_val_a = survivors below, K + 1
+  const size_t live_bytes = up256(K * 4), below_bytes = up256((K + 1) * 8), scan_bytes = scan_scratch_elems(K) * sizeof(unsigned long long);
+  const size_t need = (host ? up256(K * 8) : 0) + live_bytes + 256 + below_bytes + scan_bytes;
+  if (need > e->ws_limit)
+    return fail(e, TAD_ERR_GRID_TOO_LARGE, "tad_keydict_compact needs %llu bytes of scratch > workspace limit %llu (dictionary unchanged)",
+                (unsigned long long)need, (unsigned long long)e->ws_limit);
+  int rc;
+  if ((rc = ensure(e, e->sp_comp_a, live_bytes + 256)) != TAD_OK || (rc = ensure(e, e->sp_val_a, below_bytes)) != TAD_OK ||
+      (rc = ensure(e, e->scan_scratch, scan_bytes)) != TAD_OK || (host && (rc = ensure(e, e->in_key, up256(K * 8))) != TAD_OK))
+    return rc;
+  uint32_t *live = static_cast<uint32_t *>(e->sp_comp_a.p);
+  uint32_t *err_dev = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(e->sp_comp_a.p) + live_bytes);
+  unsigned long long *below = static_cast<unsigned long long *>(e->sp_val_a.p);
+  const unsigned long long *d_remap = reinterpret_cast<const unsigned long long *>(remap);
+  if (host) {
+    HIP_TRY(e, hipMemcpyAsync(e->in_key.p, remap, K * 8, hipMemcpyHostToDevice, s));
+    d_remap = static_cast<const unsigned long long *>(e->in_key.p);
+  }
+  // 1. the check: the kept entries are 0, 1, ..., m - 1 in order.  The dictionary is only read
+  HIP_TRY(e, hipMemsetAsync(err_dev, 0, 4, s));
+  launch_kd_live(s, d_remap, K, live);
+  launch_scan(s, live, below, K, static_cast<unsigned long long *>(e->scan_scratch.p));
+  launch_kd_compact(s, d_remap, below, K, d->keys, d->n_cols, nullptr, err_dev);
+  unsigned long long m = 0;
+  uint32_t err = 0;
+  HIP_TRY(e, hipMemcpyAsync(&m, below + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(&err, err_dev, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  if (err != 0 || m > K)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_compact: the entries of remap that are not TAD_KEY_SKIP must be 0, 1, ..., m - 1 in order "
+                                             "(what tad_state_compact writes); dictionary unchanged");
+  if (m == K) return TAD_OK;      // the identity: nothing leaves
+  // 2. fresh records and a fresh table, at the size tad_keydict_create(expected_keys = 2 m) picks and never above the current one
+  const size_t rec = (size_t)kd_stride(d->n_cols) * 8;
+  uint64_t ncap = 2 * m > kKdMinKeys ? 2 * m : kKdMinKeys, nslots = pow2_at_least(4 * m);
+  if (ncap > d->key_cap) ncap = d->key_cap;
+  if (nslots > d->slots) nslots = d->slots;
+  unsigned long long *nkeys = nullptr, *ntable = nullptr;
+  hipError_t r = kd_alloc(e, reinterpret_cast<void **>(&nkeys), ncap * rec);
+  if (r == hipSuccess) r = kd_alloc(e, reinterpret_cast<void **>(&ntable), nslots * 8);
+  if (r == hipSuccess) r = hipMemsetAsync(ntable, 0xFF, nslots * 8, s);
+  if (r == hipSuccess) {
+    launch_kd_compact(s, d_remap, below, K, d->keys, d->n_cols, nkeys, err_dev);
+    if (m) launch_kd_rehash(s, nkeys, d->n_cols, m, ntable, nslots, nullptr, false);
+    r = hipStreamSynchronize(s);
+  }
+  if (r == hipSuccess) r = hipGetLastError();
+  if (r != hipSuccess) {
+    if (nkeys) hipFree(nkeys);
+    if (ntable) hipFree(ntable);
+    return fail(e, r == hipErrorOutOfMemory ? TAD_ERR_OUT_OF_MEMORY : TAD_ERR_HIP, "tad_keydict_compact: %s (dictionary unchanged)", hipGetErrorString(r));
+  }
+  hipFree(d->keys); d->keys = nkeys; d->key_cap = ncap;
+  hipFree(d->table); d->table = ntable; d->slots = nslots;
+  d->K = m;
+  if (num_keys) *num_keys = m;
+  return TAD_OK;
+}
+
 }  // extern "C"

@@ -701,6 +701,30 @@ void launch_kd_fix(hipStream_t s, const uint8_t *miss, const uint64_t *loc_a, co
 void launch_kd_rehash(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, unsigned long long *table, uint64_t slots, uint32_t *flags,
                       bool check_duplicates);
 
+// ---- retiring dead keys: tad_state_compact / tad_keydict_compact (tad_compact.hip) ----
+struct CompactCounters {   // one 64-byte block on the device, zeroed per call
+  unsigned long long unseen, idle, dropped, pad[5];   // keys with n == 0 | keys with last_t < retire_before | the points of those
+};
+// per key: live = it survives (n > 0 and, with retire_before != 0, last_t >= retire_before), slen / hlen = the series / history elements
+// it keeps (0 when retired or when soff / hoff is NULL), schunks / hchunks = ceil(len / kHistChunk) — 0 for an empty segment: chunk_key
+void launch_compact_mark(hipStream_t s, uint64_t K, StreamState cur, const unsigned long long *soff, const unsigned long long *hoff, long long retire_before,
+                         uint32_t *live, uint32_t *slen, uint32_t *hlen, uint32_t *schunks, uint32_t *hchunks, CompactCounters *cc);
+// newid / sscan / hscan (K + 1 each) = the scans of live / slen / hlen.  remap[k] = newid[k] or TAD_KEY_SKIP; move: survivor k's moments to
+// slot newid[k] of `next`, its offsets to soff_out / hoff_out (NULL: no such arena; entry newid[K] = the total)
+void launch_compact_keys(hipStream_t s, uint64_t K, const uint32_t *live, const unsigned long long *newid, const unsigned long long *sscan,
+                         const unsigned long long *hscan, bool move, StreamState cur, StreamState next, unsigned long long *soff_out,
+                         unsigned long long *hoff_out, unsigned long long *remap);
+// the survivors' segments [off_old[k], + len) to off_new[k] (off_new = the scan of the retained lengths, by old key); t_old NULL = no times.
+// chunks = coff[K], the scan of the chunk counts
+void launch_compact_copy(hipStream_t s, uint64_t chunks, const unsigned long long *coff, uint64_t K, const unsigned long long *off_old,
+                         const unsigned long long *val_old, const long long *t_old, const unsigned long long *off_new, unsigned long long *val_new,
+                         long long *t_new);
+// live[k] = remap[k] != TAD_KEY_SKIP
+void launch_kd_live(hipStream_t s, const unsigned long long *remap, uint64_t K, uint32_t *live);
+// below = the scan of live.  *err |= 1 unless every kept remap[k] == below[k]; keys_new != NULL: record k to record remap[k] of keys_new
+void launch_kd_compact(hipStream_t s, const unsigned long long *remap, const unsigned long long *below, uint64_t K, const unsigned long long *keys_old,
+                       int n_cols, unsigned long long *keys_new, uint32_t *err);
+
 void launch_synth(hipStream_t s, uint64_t seed, uint64_t first_row, uint64_t n_rows,
                   uint64_t num_keys, uint64_t n_buckets, uint64_t *key_id, int64_t *flow_end_s,
                   uint64_t *value);
@@ -714,6 +738,7 @@ void launch_mask_rows(hipStream_t s, uint64_t n, int n_terms, const long long *c
 // ---- code-object preload (tad_engine.cpp:preload_code_objects) ----
 // HIP loads a translation unit's code object on the first use of one of its kernels (~0.4 ms each, inside the first job otherwise).
 const void *code_anchor_arima();
+const void *code_anchor_compact();
 const void *code_anchor_dbscan();
 const void *code_anchor_drop();
 const void *code_anchor_factorize();

@@ -389,6 +389,27 @@ class TadState:
                                                              C.byref(dropped)))
         return int(dropped.value)
 
+    def compact(self, retire_before=0, out="host"):
+        """Drop the dead keys and renumber the survivors densely, order kept (tad_state_compact): a key survives iff it has points and,
+        with retire_before != 0, its newest point is at or after retire_before.  What a survivor holds is unchanged.  Returns (remap,
+        stats): remap[k] = the new id of old key k or TAD_KEY_SKIP — a numpy array, or a DeviceArray with out="device" — and the
+        fields of tad_compact_stats as a dict.  num_keys becomes max(survivors, 1)."""
+        eng = self._engine
+        if not (getattr(eng._lib, "tad_features", None) and eng._lib.tad_features() & capi.TAD_FEATURE_KEY_RETIRE):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_state_compact (TAD_FEATURE_KEY_RETIRE)")
+        if out not in ("host", "device"):
+            raise ValueError("out must be 'host' or 'device'")
+        if out == "device":
+            remap = DeviceArray(eng, self.num_keys, np.uint64)
+            ptr, mem = remap.ptr, capi.TAD_MEM_DEVICE
+        else:
+            remap = np.empty(self.num_keys, dtype=np.uint64)
+            ptr, mem = remap.ctypes.data, capi.TAD_MEM_HOST
+        cs = capi.CompactStats()
+        eng._check(eng._lib.tad_state_compact(eng._h, self._h, int(retire_before), ptr, mem, C.byref(cs)))
+        self.num_keys = int(cs.num_keys)
+        return remap, {name: getattr(cs, name) for name, _ in capi.CompactStats._fields_ if not name.startswith("reserved")}
+
     def nbytes(self):
         """device bytes the state holds: both moment blocks, the offsets and every arena at its capacity (tad_state_bytes)"""
         n = capi.u64()
@@ -544,6 +565,22 @@ class KeyDict:
         """device bytes the dictionary holds: the table and the key records at their capacity (tad_keydict_bytes)"""
         n = capi.u64()
         self._engine._check(self._engine._lib.tad_keydict_bytes(self._engine._h, self._h, C.byref(n)))
+        return int(n.value)
+
+    def compact(self, remap):
+        """Apply the remap of TadState.compact() (tad_keydict_compact): a survivor's tuple now encodes to remap[old id], a retired tuple
+        is forgotten (a lookup gives TAD_KEY_SKIP, an encode a new id at the end).  remap: a numpy array or a DeviceArray with one entry
+        per key held.  Returns the keys held afterwards."""
+        eng = self._engine
+        if not (getattr(eng._lib, "tad_features", None) and eng._lib.tad_features() & capi.TAD_FEATURE_KEY_RETIRE):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_keydict_compact (TAD_FEATURE_KEY_RETIRE)")
+        n = capi.u64()
+        if isinstance(remap, DeviceArray):
+            rc = eng._lib.tad_keydict_compact(eng._h, self._h, remap.ptr, remap.n, capi.TAD_MEM_DEVICE, C.byref(n))
+        else:
+            a = np.ascontiguousarray(remap, dtype=np.uint64)
+            rc = eng._lib.tad_keydict_compact(eng._h, self._h, a.ctypes.data if a.size else None, a.size, capi.TAD_MEM_HOST, C.byref(n))
+        eng._check(rc)
         return int(n.value)
 
     def export(self, first_key=0, n_keys=None):

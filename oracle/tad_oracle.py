@@ -224,6 +224,40 @@ def dbscan_noise_1d(x, eps=250000000.0, min_samples=4):
     return ~(core | reach)
 
 
+def dbscan_noise_sorted(x, eps=250000000.0, min_samples=4):
+    """dbscan_noise_1d by a DIFFERENT, faster route (n log n instead of n^2), for series of thousands of points.  On the sorted
+    values fl|x_i - x_j| <= eps is monotone in j on either side of i (a correctly rounded difference is monotone), so the
+    neighbours of i are one index range [lo_i, hi_i], found by binary search with that very predicate; i is core iff the range
+    holds min_samples points and reachable iff a core point lies inside it.  tests/test_oracle.py holds it to dbscan_noise_1d."""
+    x = np.asarray(x, dtype=np.float64)
+    n = x.size
+    if n == 0:
+        return np.zeros(0, dtype=bool)
+    order = np.argsort(x, kind="stable")
+    xs = x[order]
+    idx = np.arange(n)
+    a, b = np.zeros(n, dtype=np.int64), idx.copy()          # the first j in [0, i] within eps
+    while (a < b).any():
+        mid = (a + b) // 2
+        near = np.abs(xs - xs[mid]) <= eps
+        b = np.where((a < b) & near, mid, b)
+        a = np.where((a < b) & ~near, mid + 1, a)
+    lo = a
+    a, b = idx.copy(), np.full(n, n - 1, dtype=np.int64)    # the last j in [i, n - 1] within eps
+    while (a < b).any():
+        mid = (a + b + 1) // 2
+        near = np.abs(xs - xs[mid]) <= eps
+        a = np.where((a < b) & near, mid, a)
+        b = np.where((a < b) & ~near, mid - 1, b)
+    hi = a
+    core = hi - lo + 1 >= min_samples
+    cc = np.concatenate([[0], np.cumsum(core)])
+    noise = ~core & (cc[hi + 1] - cc[lo] == 0)
+    out = np.zeros(n, dtype=bool)
+    out[order] = noise
+    return out
+
+
 def calculate_dbscan_anomaly(throughput_row, stddev=None, eps=250000000.0, min_samples=4):
     return dbscan_noise_1d(np.array([float(v) for v in throughput_row]), eps, min_samples).tolist()
 
@@ -242,10 +276,11 @@ def u64_to_f64(v):
 
 
 def run_job(algo, key_id, flow_end_s, value, op=None, agg_flow="", key_id2=None, flow_start_s=None,
-            start_time=0, end_time=0, alpha=0.5, eps=250000000.0, min_samples=4, arima_fn=None):
+            start_time=0, end_time=0, alpha=0.5, eps=250000000.0, min_samples=4, arima_fn=None, dbscan_fn=None):
     """Returns dict with the anomalous points ordered by (key, t) and the counters tad_stats carries.
 
     algo in {"EWMA", "ARIMA", "DBSCAN"}.  op defaults to max for agg_flow "" / None and sum otherwise.
+    dbscan_fn: dbscan_noise_1d (the default) or dbscan_noise_sorted, the same verdicts faster on long series.
     """
     if op is None:
         op = "sum" if agg_flow else "max"
@@ -266,7 +301,7 @@ def run_job(algo, key_id, flow_end_s, value, op=None, agg_flow="", key_id2=None,
         calc = np.zeros(pk.size)
         anomaly = np.zeros(pk.size, dtype=bool)
         for a, b in zip(ptr[:-1], ptr[1:]):
-            anomaly[a:b] = dbscan_noise_1d(pvf[a:b], eps, min_samples)
+            anomaly[a:b] = (dbscan_fn or dbscan_noise_1d)(pvf[a:b], eps, min_samples)
     elif algo == "ARIMA":
         if arima_fn is None:
             from oracle.arima_oracle import calculate_arima_exact as arima_fn   # the fixed-arithmetic restatement

@@ -34,6 +34,8 @@ def test_ctypes_binds_them_with_argtypes():
 
 
 def test_library_exports_them():
+    from theia_amd import build
+    assert "tad_capi_state.cpp" in build.SOURCES     # the unit that implements them
     lib = _capi.load_library()
     for name in NEW:
         fn = getattr(lib, name)

@@ -1,4 +1,5 @@
-// tad_capi.cpp — the job of include/tad.h: tad_run / tad_aggregate / tad_run_stream on a job context (tad_engine.h).  Replaces one run of
+// tad_capi.cpp — the job of include/tad.h: tad_run / tad_aggregate / tad_run_stream on a job context (tad_engine.h), and the state calls that
+// run through it (tad_run_state, tad_run_state_window, tad_state_merge; the life of a tad_state itself is tad_capi_state.cpp).  Replaces one run of
 // anomaly_detection() (plugins/anomaly-detection/anomaly_detection.py:647-710): Stage 0 GROUP BY -> per-key sigma -> detector -> compaction.
 #include "tad_engine.h"
 
@@ -208,36 +209,6 @@ int stage_column(JobCtx *e, DevBuf &buf, const void *src, uint64_t n, tad_mem me
   return TAD_OK;
 }
 
-size_t state_bytes(uint64_t K) { return (size_t)K * (4 + 8 * 4 + 1) + 64; }
-
-// the arrays of K keys' running state inside one block of state_bytes(K) bytes
-StreamState stream_view(void *block, uint64_t K) {
-  unsigned char *b = static_cast<unsigned char *>(block);
-  StreamState v;
-  v.avg = reinterpret_cast<double *>(b);
-  v.m2 = v.avg + K;
-  v.ewma = v.m2 + K;
-  v.last_t = reinterpret_cast<long long *>(v.ewma + K);
-  v.n = reinterpret_cast<uint32_t *>(v.last_t + K);
-  v.seen = reinterpret_cast<unsigned char *>(v.n + K);
-  return v;
-}
-
-StreamState state_view(const tad_state *st, int which) { return stream_view(st->block[which], st->K); }
-
-// copy `which` of a series state as the detectors of tad_run_state read it (the times and the history where the state has them)
-StateView series_view(const tad_state *st, int which) {
-  StateView v;
-  v.K = st->K;
-  v.P = st->ser_len[which];
-  v.soff = st->ser_off[which];
-  v.sval = st->ser_val[which];
-  v.st = st->times ? st->ser_t[which] : nullptr;
-  v.mom = state_view(st, which);
-  if (st->history) { v.hist_off = st->hist_off[which]; v.hist_val = st->hist_val[which]; }
-  return v;
-}
-
 int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_mem out_memory, tad_result **out, tad_points **points_out,
                    tad_state *stream, int depth);
 
@@ -252,51 +223,6 @@ struct HistBatch {
   const uint32_t *cnt = nullptr;
   const unsigned long long *row = nullptr;
 };
-
-// grows a candidate value arena of a state (history, series or times) to hold `need` values, geometrically; the current arena is not
-// touched, so a failure leaves the state as it is
-template <typename T>
-int grow_arena(JobCtx *e, T *&val, uint64_t &cap, uint64_t need, const char *what) {
-  if (cap >= need) return TAD_OK;
-  const uint64_t want = need > 2 * cap ? need : 2 * cap;
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  if (val) hipFree(val);
-  val = nullptr;
-  cap = 0;
-  void *p = nullptr;
-  const hipError_t r = hipMalloc(&p, want * 8);
-  if (r != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_run_stream: %llu values of %s do not fit (%s); state unchanged", (unsigned long long)need, what,
-                hipGetErrorString(r));
-  }
-  val = static_cast<T *>(p);
-  cap = want;
-  return TAD_OK;
-}
-
-// a trim leaves `len` values in an arena: below a quarter of its capacity the arena is given back and, for a candidate that is about to be
-// written, allocated anew at twice the length (how a trimmed state's memory actually shrinks); a candidate too small grows to twice the
-// length too.  Only candidate arenas come here, so a failure leaves the state as it is.
-template <typename T>
-int size_trim_arena(JobCtx *e, T *&val, uint64_t &cap, uint64_t len, bool allocate, const char *who = "tad_state_trim") {
-  if (cap >= len && !(len * 4 < cap)) return TAD_OK;
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  if (val) hipFree(val);
-  val = nullptr;
-  cap = 0;
-  if (!allocate || len == 0) return TAD_OK;
-  void *p = nullptr;
-  const hipError_t r = hipMalloc(&p, 2 * len * sizeof(T));
-  if (r != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(e, TAD_ERR_OUT_OF_MEMORY, "%s: %llu retained values do not fit (%s); state unchanged", who, (unsigned long long)len,
-                hipGetErrorString(r));
-  }
-  val = static_cast<T *>(p);
-  cap = 2 * len;
-  return TAD_OK;
-}
 
 // The batch's new points in (key, time) order for stream_history_batch and state_merge_batch: keys in e->hs_key, times in e->hs_t, values
 // and per-key offsets in *nv / *poff.  ensure_batch_points sizes the buffers both share (hs_key, hs_t, hs_sorted, hs_koff: dense point
@@ -351,10 +277,8 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
   const size_t kpad = (size_t)((K + 3) & ~3ull);
   int rc;
   // the candidate arenas first: an allocation failure leaves the state, its history and its series as they are
-  const uint64_t need = st->hist_len[cur] + P_cap;
-  if (st->history && (rc = grow_arena(e, st->hist_val[cand], st->hist_cap[cand], need, "history")) != TAD_OK) return rc;
-  if (st->series && (rc = grow_arena(e, st->ser_val[cand], st->ser_cap[cand], st->ser_len[cur] + P_cap, "series")) != TAD_OK) return rc;
-  if (st->times && (rc = grow_arena(e, st->ser_t[cand], st->ser_tcap[cand], st->ser_len[cur] + P_cap, "times")) != TAD_OK) return rc;
+  const uint64_t need = st->hist.len[cur] + P_cap;
+  if ((rc = state_grow_candidates(e, st, P_cap)) != TAD_OK) return rc;
   const uint64_t pc = P_cap ? P_cap : 1;
   if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr)) != TAD_OK) return rc;
   if (dbscan) {
@@ -373,21 +297,21 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
   batch_points(e, g, L, sparse_poff, P, &poff, &nv);   // 1.
   if (st->history) {   // 2. every key's new values sorted; 3. merged with its history into the candidate arena
     launch_hist_sort(s, nv, poff, K, ns, kcnt, long_count);
-    launch_hist_merge(s, K, st->hist_off[cur], st->hist_val[cur], poff, ns, st->hist_off[cand], st->hist_val[cand], kcnt, coff, scratch,
+    launch_hist_merge(s, K, st->hist.off[cur], st->hist.val.p[cur], poff, ns, st->hist.off[cand], st->hist.val.p[cand], kcnt, coff, scratch,
                       hist_merge_chunks_bound(K, need));
   }
   if (st->series)      // 3'. appended to its series in the candidate arena
-    launch_series_append(s, K, st->ser_off[cur], st->ser_val[cur], poff, nv, st->ser_off[cand], st->ser_val[cand]);
+    launch_series_append(s, K, st->ser.off[cur], st->ser.val.p[cur], poff, nv, st->ser.off[cand], st->ser.val.p[cand]);
   if (st->times)       // 3''. and their times beside them (the same offsets, written again)
-    launch_series_append(s, K, st->ser_off[cur], reinterpret_cast<const unsigned long long *>(st->ser_t[cur]), poff,
-                         reinterpret_cast<const unsigned long long *>(nt), st->ser_off[cand], reinterpret_cast<unsigned long long *>(st->ser_t[cand]));
+    launch_series_append(s, K, st->ser.off[cur], reinterpret_cast<const unsigned long long *>(st->ser_times.p[cur]), poff,
+                         reinterpret_cast<const unsigned long long *>(nt), st->ser.off[cand], reinterpret_cast<unsigned long long *>(st->ser_times.p[cand]));
   HIP_TRY(e, hipMemcpyAsync(static_cast<unsigned char *>(e->counters.p) + kTailHistLen, poff + K, 8, hipMemcpyDeviceToDevice, s));
   hb->nk = nk; hb->nt = nt; hb->nv = nv; hb->poff = poff; hb->P_dev = poff + K; hb->P_cap = P_cap;
   if (dbscan && P_cap) {   // 4. verdicts of the new points; 5. their rows (the row total lands in the job's tail)
     uint8_t *noise = static_cast<uint8_t *>(e->hs_noise.p);
     uint32_t *cnt = static_cast<uint32_t *>(e->hs_cnt.p);
     unsigned long long *row = static_cast<unsigned long long *>(e->hs_row.p);
-    launch_hist_verdict(s, nk, nv, poff + K, P_cap, st->hist_off[cand], st->hist_val[cand], jp.eps, jp.min_samples, jp.all_points, noise, cnt);
+    launch_hist_verdict(s, nk, nv, poff + K, P_cap, st->hist.off[cand], st->hist.val.p[cand], jp.eps, jp.min_samples, jp.all_points, noise, cnt);
     launch_scan(s, cnt, row, P_cap, scratch, dev_total(e));
     hb->noise = noise; hb->cnt = cnt; hb->row = row;
   }
@@ -407,14 +331,12 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
   const uint64_t P_cap = sparse_poff ? P : P_bound;
   const uint64_t pc = P_cap ? P_cap : 1;
   const size_t kpad = (size_t)((K + 3) & ~3ull), ko = kpad + 4;
-  const uint64_t S = st->ser_len[cur], H = st->hist_len[cur];
+  const uint64_t S = st->ser.len[cur], H = st->hist.len[cur];
   int rc;
   mc->changed = false;
   mc->added = 0;
   // the candidate arenas first: an allocation failure leaves the state as it is
-  if ((rc = grow_arena(e, st->ser_val[cand], st->ser_cap[cand], S + P_cap, "series")) != TAD_OK) return rc;
-  if ((rc = grow_arena(e, st->ser_t[cand], st->ser_tcap[cand], S + P_cap, "times")) != TAD_OK) return rc;
-  if (st->history && (rc = grow_arena(e, st->hist_val[cand], st->hist_cap[cand], H + P_cap, "history")) != TAD_OK) return rc;
+  if ((rc = state_grow_candidates(e, st, P_cap)) != TAD_OK) return rc;
   if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr)) != TAD_OK) return rc;
   // per point: three scans (pc + 1 each) | history gains, sorted | losses, sorted | rank, three flag arrays | class
   if ((rc = ensure(e, e->mg_pts, (7 * pc + 8) * 8 + pc * 16 + pc + 64)) != TAD_OK) return rc;
@@ -436,7 +358,7 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
   batch_points(e, g, L, sparse_poff, P, &poff, &nv);
   // 1. classify; the one round trip: Stage 0's error word, the point count, the classification's counters
   HIP_TRY(e, hipMemsetAsync(mcnt, 0, sizeof(MergeCounters), s));
-  launch_merge_classify(s, nk, nt, poff + K, P_cap, K, st->ser_off[cur], st->ser_t[cur], (long long)mc->keep_from, cls, rank, f_nh, f_kept, f_hit, mcnt);
+  launch_merge_classify(s, nk, nt, poff + K, P_cap, K, st->ser.off[cur], st->ser_times.p[cur], (long long)mc->keep_from, cls, rank, f_nh, f_kept, f_hit, mcnt);
   unsigned char *hm = e->tail_host + kTailMoments;   // (the moment partials' place in the pinned tail: a merge has none)
   HIP_TRY(e, hipMemcpyAsync(e->ctr_host, e->counters.p, sizeof(DevCounters), hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
@@ -461,13 +383,13 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
     if (st->history) {
       unsigned long long *ns = static_cast<unsigned long long *>(e->hs_sorted.p);
       launch_hist_sort(s, nv, poff, K, ns, long_list, long_count);
-      launch_hist_merge(s, K, st->hist_off[cur], st->hist_val[cur], poff, ns, st->hist_off[cand], st->hist_val[cand], chunks_h, coff_h, scratch,
+      launch_hist_merge(s, K, st->hist.off[cur], st->hist.val.p[cur], poff, ns, st->hist.off[cand], st->hist.val.p[cand], chunks_h, coff_h, scratch,
                         hist_merge_chunks_bound(K, H + P_cap));
     }
-    launch_series_append(s, K, st->ser_off[cur], st->ser_val[cur], poff, nv, st->ser_off[cand], st->ser_val[cand]);
-    launch_series_append(s, K, st->ser_off[cur], reinterpret_cast<const unsigned long long *>(st->ser_t[cur]), poff,
-                         reinterpret_cast<const unsigned long long *>(nt), st->ser_off[cand], reinterpret_cast<unsigned long long *>(st->ser_t[cand]));
-    launch_merge_moments(s, K, nullptr, st->ser_off[cur], st->ser_off[cand], st->ser_val[cand], st->ser_t[cand], alpha, state_view(st, cur),
+    launch_series_append(s, K, st->ser.off[cur], st->ser.val.p[cur], poff, nv, st->ser.off[cand], st->ser.val.p[cand]);
+    launch_series_append(s, K, st->ser.off[cur], reinterpret_cast<const unsigned long long *>(st->ser_times.p[cur]), poff,
+                         reinterpret_cast<const unsigned long long *>(nt), st->ser.off[cand], reinterpret_cast<unsigned long long *>(st->ser_times.p[cand]));
+    launch_merge_moments(s, K, nullptr, st->ser.off[cur], st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], alpha, state_view(st, cur),
                          state_view(st, cand), mcnt);
   } else {
     if (st->history && c.combined && (rc = ensure(e, e->mg_hist, (H ? H : 1) * 8)) != TAD_OK) return rc;
@@ -475,29 +397,29 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
     launch_scan(s, f_nh, nhoff, P_cap, scratch);
     launch_scan(s, f_kept, aoff, P_cap, scratch);
     launch_scan(s, f_hit, roff, P_cap, scratch);
-    launch_merge_keys(s, K, poff, nhoff, aoff, roff, cls, st->ser_off[cur], st->history ? st->hist_off[cur] : nullptr, st->ser_off[cand], akoff, rkoff,
+    launch_merge_keys(s, K, poff, nhoff, aoff, roff, cls, st->ser.off[cur], st->history ? st->hist.off[cur] : nullptr, st->ser.off[cand], akoff, rkoff,
                       hoff_mid, chunks_s, chunks_h, replay);
     launch_scan(s, chunks_s, coff_s, K, scratch);
     // 3. series and times merged by time (and the history's gains and losses packed)
-    launch_merge_series(s, merge_chunks_bound(K, S + P_cap), coff_s, K, op_max, st->ser_off[cur], st->ser_val[cur], st->ser_t[cur], poff, nt, nv, cls, rank,
-                        nhoff, aoff, roff, st->ser_off[cand], st->ser_val[cand], st->ser_t[cand], st->history ? hadd : nullptr, st->history ? hrem : nullptr);
+    launch_merge_series(s, merge_chunks_bound(K, S + P_cap), coff_s, K, op_max, st->ser.off[cur], st->ser.val.p[cur], st->ser_times.p[cur], poff, nt, nv, cls, rank,
+                        nhoff, aoff, roff, st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], st->history ? hadd : nullptr, st->history ? hrem : nullptr);
     if (st->history) {   // 4. the combined points' old values leave the history (through the scratch arena), then the batch's values enter
-      const unsigned long long *hoff_from = st->hist_off[cur], *hval_from = st->hist_val[cur];
+      const unsigned long long *hoff_from = st->hist.off[cur], *hval_from = st->hist.val.p[cur];
       if (c.combined) {
         unsigned long long *hmid = static_cast<unsigned long long *>(e->mg_hist.p);
         launch_hist_sort(s, hrem, rkoff, K, hrem_s, long_list, long_count);
         launch_scan(s, chunks_h, coff_h, K, scratch);
         // (chunks_h gives an empty key no chunk: not the one-chunk-at-least counts of a trim)
-        launch_hist_subtract(s, trim_chunks_bound(K, H), coff_h, K, st->hist_off[cur], st->hist_val[cur], rkoff, hrem_s, hoff_mid, hmid, false);
+        launch_hist_subtract(s, trim_chunks_bound(K, H), coff_h, K, st->hist.off[cur], st->hist.val.p[cur], rkoff, hrem_s, hoff_mid, hmid, false);
         hoff_from = hoff_mid;
         hval_from = hmid;
       }
       launch_hist_sort(s, hadd, akoff, K, hadd_s, long_list, long_count);
-      launch_hist_merge(s, K, hoff_from, hval_from, akoff, hadd_s, st->hist_off[cand], st->hist_val[cand], chunks_h, coff_h, scratch,
+      launch_hist_merge(s, K, hoff_from, hval_from, akoff, hadd_s, st->hist.off[cand], st->hist.val.p[cand], chunks_h, coff_h, scratch,
                         hist_merge_chunks_bound(K, H + P_cap));
     }
     // 5. the moments
-    launch_merge_moments(s, K, replay, st->ser_off[cur], st->ser_off[cand], st->ser_val[cand], st->ser_t[cand], alpha, state_view(st, cur),
+    launch_merge_moments(s, K, replay, st->ser.off[cur], st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], alpha, state_view(st, cur),
                          state_view(st, cand), mcnt);
   }
   HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
@@ -634,7 +556,6 @@ int stream_arima_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const
 
 // the start of a tad_run_state / tad_run_state_window job on the context the caller holds: progress, the first event, the job tail zeroed
 int run_view_begin(JobCtx *e, uint64_t K) {
-  HIP_TRY(e, hipSetDevice(e->device));
   e->done.store(0);
   e->total.store(4);
   e->arima_relaunches = 0;
@@ -704,7 +625,7 @@ int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem o
         uint8_t *noise = static_cast<uint8_t *>(e->hs_noise.p);
         uint32_t *cnt = static_cast<uint32_t *>(e->hs_cnt.p);
         unsigned long long *row = static_cast<unsigned long long *>(e->hs_row.p);
-        launch_hist_verdict(s, nk, sval, hist.P_dev, P, v.hist_off, v.hist_val, jp.eps, jp.min_samples, jp.all_points, noise, cnt);
+        launch_hist_verdict(s, nk, sval, hist.P_dev, P, v.hoff, v.hval, jp.eps, jp.min_samples, jp.all_points, noise, cnt);
         launch_scan(s, cnt, row, P, scratch, dev_total(e));
         hist.noise = noise; hist.cnt = cnt; hist.row = row;
       } else if ((rc = stream_arima_batch(e, v, hist, jp, ctr, &ab)) != TAD_OK) {
@@ -1421,11 +1342,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
       hipEventElapsedTime(&ms.ms_stage0, e->ev[1], e->ev[5]);
       hipEventElapsedTime(&ms.ms_merge, e->ev[5], e->ev[4]);
       hipEventElapsedTime(&ms.ms_total, e->ev[0], e->ev[4]);
-      if (mc->changed) {
-        stream->ser_len[stream->cur ^ 1] = stream->ser_len[stream->cur] + mc->added;
-        if (stream->history) stream->hist_len[stream->cur ^ 1] = stream->hist_len[stream->cur] + mc->added;
-        stream->cur ^= 1;
-      }
+      if (mc->changed) state_commit(stream, stream->ser.len[stream->cur] + mc->added, stream->hist.len[stream->cur] + mc->added);
       if (depth == 0) e->done.store(4);
       return TAD_OK;
     }
@@ -1525,9 +1442,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
     if (stream && g.K) {   // the batch succeeded: the candidate state (and history, series) becomes current (an empty batch wrote none)
       unsigned long long added = 0;
       memcpy(&added, e->tail_host + kTailHistLen, 8);
-      if (stream->history) stream->hist_len[stream->cur ^ 1] = stream->hist_len[stream->cur] + added;
-      if (stream->series) stream->ser_len[stream->cur ^ 1] = stream->ser_len[stream->cur] + added;
-      stream->cur ^= 1;
+      state_commit(stream, stream->ser.len[stream->cur] + added, stream->hist.len[stream->cur] + added);
     }
     if (depth == 0) e->done.store(4);
     *out = &rp->pub;
@@ -1768,640 +1683,6 @@ int tad_run_stream(tad_engine *e, tad_state *st, const tad_job *job, const tad_c
   return run_job(e, job, cols, out_memory, out, nullptr, st);
 }
 
-int tad_state_create(tad_engine *eng, uint64_t num_keys, tad_state **out) {
-  if (!eng || !out || num_keys == 0) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_create: bad arguments");
-  *out = nullptr;
-  Lease lease(eng);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_create: no job context available");
-  HIP_TRY(e, hipSetDevice(e->device));
-  tad_state *st = new (std::nothrow) tad_state();
-  if (!st) return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory");
-  st->K = num_keys;
-  for (int i = 0; i < 2; ++i) {
-    hipError_t r = hipMalloc(&st->block[i], state_bytes(num_keys));
-    if (r == hipSuccess) r = hipMemsetAsync(st->block[i], 0, state_bytes(num_keys), e->stream);   // n = 0, avg = m2 = ewma = 0, unseen
-    if (r != hipSuccess) {
-      for (int j = 0; j <= i; ++j) if (st->block[j]) hipFree(st->block[j]);
-      delete st;
-      return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_create: %s", hipGetErrorString(r));
-    }
-  }
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  *out = st;
-  return TAD_OK;
-}
-
-void tad_state_destroy(tad_engine *e, tad_state *st) {
-  if (!st) return;
-  { std::lock_guard<std::mutex> lk(st->mu); }   // a batch on this state has returned (it synchronises its stream before it does)
-  if (e) hipSetDevice(e->device);
-  for (int i = 0; i < 2; ++i) {
-    if (st->block[i]) hipFree(st->block[i]);
-    if (st->hist_off[i]) hipFree(st->hist_off[i]);
-    if (st->hist_val[i]) hipFree(st->hist_val[i]);
-    if (st->ser_off[i]) hipFree(st->ser_off[i]);
-    if (st->ser_val[i]) hipFree(st->ser_val[i]);
-    if (st->ser_t[i]) hipFree(st->ser_t[i]);
-  }
-  delete st;
-}
-
-int tad_state_export(tad_engine *eng, const tad_state *st, uint32_t *n, double *avg, double *m2, double *ewma, int64_t *last_t) {
-  if (!eng || !st) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export: bad arguments");
-  Lease lease(eng);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_export: no job context available");
-  std::lock_guard<std::mutex> state_lk(st->mu);
-  HIP_TRY(e, hipSetDevice(e->device));
-  const StreamState v = state_view(st, st->cur);
-  if (n) HIP_TRY(e, hipMemcpy(n, v.n, st->K * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (avg) HIP_TRY(e, hipMemcpy(avg, v.avg, st->K * sizeof(double), hipMemcpyDeviceToHost));
-  if (m2) HIP_TRY(e, hipMemcpy(m2, v.m2, st->K * sizeof(double), hipMemcpyDeviceToHost));
-  if (ewma) HIP_TRY(e, hipMemcpy(ewma, v.ewma, st->K * sizeof(double), hipMemcpyDeviceToHost));
-  if (last_t) HIP_TRY(e, hipMemcpy(last_t, v.last_t, st->K * sizeof(long long), hipMemcpyDeviceToHost));
-  return TAD_OK;
-}
-
-int tad_state_resize(tad_engine *eng, tad_state *st, uint64_t new_num_keys) {
-  if (!eng || !st) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_resize: bad arguments");
-  std::lock_guard<std::mutex> state_lk(st->mu);   // (the order of tad_run_stream: the state, then a job context)
-  if (new_num_keys < st->K)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_resize: %llu keys < the %llu the state holds (a state only grows)",
-                (unsigned long long)new_num_keys, (unsigned long long)st->K);
-  if (new_num_keys == st->K) return TAD_OK;
-  Lease lease(eng);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_resize: no job context available");
-  HIP_TRY(e, hipSetDevice(e->device));
-  // both copies anew (the old ones stay the state's until everything succeeded); the added keys are unseen (all zeros)
-  tad_state grown;
-  grown.K = new_num_keys;
-  hipError_t r = hipSuccess;
-  for (int i = 0; i < 2 && r == hipSuccess; ++i) {
-    r = hipMalloc(&grown.block[i], state_bytes(new_num_keys));
-    if (r == hipSuccess) r = hipMemsetAsync(grown.block[i], 0, state_bytes(new_num_keys), e->stream);
-  }
-  if (r == hipSuccess) {
-    const StreamState a = state_view(st, st->cur), b = state_view(&grown, 0);
-    const size_t K = st->K;
-    r = hipMemcpyAsync(b.avg, a.avg, K * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(b.m2, a.m2, K * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(b.ewma, a.ewma, K * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(b.last_t, a.last_t, K * sizeof(long long), hipMemcpyDeviceToDevice, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(b.n, a.n, K * sizeof(uint32_t), hipMemcpyDeviceToDevice, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(b.seen, a.seen, K, hipMemcpyDeviceToDevice, e->stream);
-  }
-  // a history state: offsets of K' + 1 entries for both copies; the current one keeps its keys' offsets and gives the added keys empty
-  // segments at the end (offset = the history's length).  The value arenas stay; the current one moves to index 0 with the state.
-  std::vector<unsigned long long> tail_off, ser_tail_off;
-  if (r == hipSuccess && st->history) {
-    for (int i = 0; i < 2 && r == hipSuccess; ++i) r = hipMalloc(reinterpret_cast<void **>(&grown.hist_off[i]), (new_num_keys + 1) * 8);
-    if (r == hipSuccess) r = hipMemcpyAsync(grown.hist_off[0], st->hist_off[st->cur], (st->K + 1) * 8, hipMemcpyDeviceToDevice, e->stream);
-    if (r == hipSuccess) {
-      try { tail_off.assign(new_num_keys - st->K, st->hist_len[st->cur]); } catch (...) { r = hipErrorOutOfMemory; }
-    }
-    if (r == hipSuccess)
-      r = hipMemcpyAsync(grown.hist_off[0] + st->K + 1, tail_off.data(), tail_off.size() * 8, hipMemcpyHostToDevice, e->stream);
-  }
-  if (r == hipSuccess && st->series) {   // the series the same way: the added keys' segments are empty, at the end
-    for (int i = 0; i < 2 && r == hipSuccess; ++i) r = hipMalloc(reinterpret_cast<void **>(&grown.ser_off[i]), (new_num_keys + 1) * 8);
-    if (r == hipSuccess) r = hipMemcpyAsync(grown.ser_off[0], st->ser_off[st->cur], (st->K + 1) * 8, hipMemcpyDeviceToDevice, e->stream);
-    if (r == hipSuccess) {
-      try { ser_tail_off.assign(new_num_keys - st->K, st->ser_len[st->cur]); } catch (...) { r = hipErrorOutOfMemory; }
-    }
-    if (r == hipSuccess)
-      r = hipMemcpyAsync(grown.ser_off[0] + st->K + 1, ser_tail_off.data(), ser_tail_off.size() * 8, hipMemcpyHostToDevice, e->stream);
-  }
-  if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-  if (r != hipSuccess) {
-    for (int i = 0; i < 2; ++i) {
-      if (grown.block[i]) hipFree(grown.block[i]);
-      if (grown.hist_off[i]) hipFree(grown.hist_off[i]);
-      if (grown.ser_off[i]) hipFree(grown.ser_off[i]);
-    }
-    return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_resize: %s (state unchanged)", hipGetErrorString(r));
-  }
-  for (int i = 0; i < 2; ++i) { hipFree(st->block[i]); st->block[i] = grown.block[i]; }
-  if (st->history) {
-    for (int i = 0; i < 2; ++i) { hipFree(st->hist_off[i]); st->hist_off[i] = grown.hist_off[i]; }
-    if (st->cur == 1) {
-      std::swap(st->hist_val[0], st->hist_val[1]);
-      std::swap(st->hist_cap[0], st->hist_cap[1]);
-      std::swap(st->hist_len[0], st->hist_len[1]);
-    }
-  }
-  if (st->series) {
-    for (int i = 0; i < 2; ++i) { hipFree(st->ser_off[i]); st->ser_off[i] = grown.ser_off[i]; }
-    if (st->cur == 1) {
-      std::swap(st->ser_val[0], st->ser_val[1]);
-      std::swap(st->ser_cap[0], st->ser_cap[1]);
-      std::swap(st->ser_len[0], st->ser_len[1]);
-      std::swap(st->ser_t[0], st->ser_t[1]);   // (the times share the series' offsets)
-      std::swap(st->ser_tcap[0], st->ser_tcap[1]);
-    }
-  }
-  st->K = new_num_keys;
-  st->cur = 0;
-  return TAD_OK;
-}
-
-int tad_state_import(tad_engine *eng, tad_state *st, const uint32_t *n, const double *avg, const double *m2, const double *ewma, const int64_t *last_t) {
-  if (!eng || !st || !n || !avg || !m2 || !ewma || !last_t) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import: bad arguments");
-  std::lock_guard<std::mutex> state_lk(st->mu);
-  Lease lease(eng);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_import: no job context available");
-  HIP_TRY(e, hipSetDevice(e->device));
-  // the state's layout on the host (state_view), then one copy: a key with n == 0 is unseen and all zeros
-  const size_t K = st->K;
-  std::vector<unsigned char> h;
-  try { h.assign(state_bytes(K), 0); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
-  double *h_avg = reinterpret_cast<double *>(h.data()), *h_m2 = h_avg + K, *h_ewma = h_m2 + K;
-  long long *h_last = reinterpret_cast<long long *>(h_ewma + K);
-  uint32_t *h_n = reinterpret_cast<uint32_t *>(h_last + K);
-  unsigned char *h_seen = reinterpret_cast<unsigned char *>(h_n + K);
-  for (size_t k = 0; k < K; ++k) {
-    if (n[k] == 0) continue;
-    h_avg[k] = avg[k]; h_m2[k] = m2[k]; h_ewma[k] = ewma[k]; h_last[k] = last_t[k]; h_n[k] = n[k]; h_seen[k] = 1;
-  }
-  HIP_TRY(e, hipMemcpy(st->block[st->cur], h.data(), h.size(), hipMemcpyHostToDevice));
-  return TAD_OK;
-}
-
-int tad_state_create_ex(tad_engine *eng, uint64_t num_keys, uint32_t flags, tad_state **out) {
-  const uint32_t known = TAD_STATE_HISTORY | TAD_STATE_SERIES | TAD_STATE_TIMES;
-  if (out) *out = nullptr;
-  if (flags & ~known) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_create_ex: unknown flags 0x%x", flags & ~known);
-  if ((flags & TAD_STATE_TIMES) && !(flags & TAD_STATE_SERIES))
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_create_ex: TAD_STATE_TIMES needs TAD_STATE_SERIES");
-  int rc = tad_state_create(eng, num_keys, out);
-  if (rc != TAD_OK || !(flags & known)) return rc;
-  tad_state *st = *out;
-  st->history = (flags & TAD_STATE_HISTORY) != 0;
-  st->series = (flags & TAD_STATE_SERIES) != 0;
-  st->times = (flags & TAD_STATE_TIMES) != 0;   // (the times arenas come with the first batch, like the values)
-  hipError_t r = hipSetDevice(eng->device);
-  for (int i = 0; i < 2 && r == hipSuccess; ++i) {   // every key's segment empty: offsets all zero (the value arenas come with the first batch)
-    if (st->history) {
-      r = hipMalloc(reinterpret_cast<void **>(&st->hist_off[i]), (num_keys + 1) * 8);
-      if (r == hipSuccess) r = hipMemset(st->hist_off[i], 0, (num_keys + 1) * 8);
-    }
-    if (st->series && r == hipSuccess) {
-      r = hipMalloc(reinterpret_cast<void **>(&st->ser_off[i]), (num_keys + 1) * 8);
-      if (r == hipSuccess) r = hipMemset(st->ser_off[i], 0, (num_keys + 1) * 8);
-    }
-  }
-  if (r != hipSuccess) {
-    tad_state_destroy(eng, st);
-    *out = nullptr;
-    return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_create_ex: %s", hipGetErrorString(r));
-  }
-  return TAD_OK;
-}
-
-int tad_state_history_points(tad_engine *eng, const tad_state *st, uint64_t *n_points) {
-  if (!eng || !st || !n_points) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_history_points: bad arguments");
-  std::lock_guard<std::mutex> state_lk(st->mu);
-  *n_points = st->history ? st->hist_len[st->cur] : 0;
-  return TAD_OK;
-}
-
-int tad_state_export_history(tad_engine *eng, const tad_state *st, uint64_t *len, uint64_t *values) {
-  if (!eng || !st || !len) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_history: bad arguments");
-  if (!st->history) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_history: the state has no history (TAD_STATE_HISTORY)");
-  Lease lease(eng);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_export_history: no job context available");
-  std::lock_guard<std::mutex> state_lk(st->mu);
-  HIP_TRY(e, hipSetDevice(e->device));
-  std::vector<unsigned long long> off;
-  try { off.resize(st->K + 1); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
-  HIP_TRY(e, hipMemcpy(off.data(), st->hist_off[st->cur], (st->K + 1) * 8, hipMemcpyDeviceToHost));
-  for (uint64_t k = 0; k < st->K; ++k) len[k] = off[k + 1] - off[k];
-  const uint64_t total = st->hist_len[st->cur];
-  if (values && total) HIP_TRY(e, hipMemcpy(values, st->hist_val[st->cur], total * 8, hipMemcpyDeviceToHost));
-  return TAD_OK;
-}
-
-int tad_state_import_history(tad_engine *eng, tad_state *st, const uint64_t *len, const uint64_t *values) {
-  if (!eng || !st || !len) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_history: bad arguments");
-  if (!st->history) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_history: the state has no history (TAD_STATE_HISTORY)");
-  std::lock_guard<std::mutex> state_lk(st->mu);
-  Lease lease(eng);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_import_history: no job context available");
-  HIP_TRY(e, hipSetDevice(e->device));
-  const uint64_t K = st->K;
-  std::vector<uint32_t> n;
-  std::vector<unsigned long long> off;
-  try { n.resize(K); off.resize(K + 1); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
-  HIP_TRY(e, hipMemcpy(n.data(), state_view(st, st->cur).n, K * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  off[0] = 0;
-  for (uint64_t k = 0; k < K; ++k) {
-    if (len[k] != n[k])
-      return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_history: key %llu has %llu values, its state has n = %u (import the moments first); state unchanged",
-                  (unsigned long long)k, (unsigned long long)len[k], n[k]);
-    off[k + 1] = off[k] + len[k];
-  }
-  const uint64_t total = off[K];
-  if (total && !values) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_history: values is NULL");
-  for (uint64_t k = 0; k < K; ++k)
-    for (uint64_t i = off[k] + 1; i < off[k + 1]; ++i)
-      if (values[i] < values[i - 1])
-        return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_history: the values of key %llu are not ascending; state unchanged", (unsigned long long)k);
-  // into the candidate copy, which then trades places with the current one: any failure leaves the history as it was
-  const int cand = st->cur ^ 1;
-  unsigned long long *val = st->hist_val[cand];
-  uint64_t cap = st->hist_cap[cand];
-  if (cap < total) {
-    void *p = nullptr;
-    const hipError_t r = hipMalloc(&p, total * 8);
-    if (r != hipSuccess) { (void)hipGetLastError(); return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_import_history: %s; state unchanged", hipGetErrorString(r)); }
-    if (val) hipFree(val);
-    st->hist_val[cand] = val = static_cast<unsigned long long *>(p);
-    st->hist_cap[cand] = cap = total;
-  }
-  if (total) HIP_TRY(e, hipMemcpy(val, values, total * 8, hipMemcpyHostToDevice));
-  HIP_TRY(e, hipMemcpy(st->hist_off[cand], off.data(), (K + 1) * 8, hipMemcpyHostToDevice));
-  std::swap(st->hist_off[0], st->hist_off[1]);
-  std::swap(st->hist_val[0], st->hist_val[1]);
-  std::swap(st->hist_cap[0], st->hist_cap[1]);
-  st->hist_len[st->cur] = total;
-  return TAD_OK;
-}
-
-int tad_state_series_points(tad_engine *eng, const tad_state *st, uint64_t *n_points) {
-  if (!eng || !st || !n_points) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_series_points: bad arguments");
-  std::lock_guard<std::mutex> state_lk(st->mu);
-  *n_points = st->series ? st->ser_len[st->cur] : 0;
-  return TAD_OK;
-}
-
-int tad_state_export_series(tad_engine *eng, const tad_state *st, uint64_t *len, uint64_t *values) {
-  if (!eng || !st || !len) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_series: bad arguments");
-  if (!st->series) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_series: the state has no series (TAD_STATE_SERIES)");
-  Lease lease(eng);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_export_series: no job context available");
-  std::lock_guard<std::mutex> state_lk(st->mu);
-  HIP_TRY(e, hipSetDevice(e->device));
-  std::vector<unsigned long long> off;
-  try { off.resize(st->K + 1); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
-  HIP_TRY(e, hipMemcpy(off.data(), st->ser_off[st->cur], (st->K + 1) * 8, hipMemcpyDeviceToHost));
-  for (uint64_t k = 0; k < st->K; ++k) len[k] = off[k + 1] - off[k];
-  const uint64_t total = st->ser_len[st->cur];
-  if (values && total) HIP_TRY(e, hipMemcpy(values, st->ser_val[st->cur], total * 8, hipMemcpyDeviceToHost));
-  return TAD_OK;
-}
-
-int tad_state_import_series(tad_engine *eng, tad_state *st, const uint64_t *len, const uint64_t *values) {
-  if (!eng || !st || !len) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_series: bad arguments");
-  if (!st->series) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_series: the state has no series (TAD_STATE_SERIES)");
-  std::lock_guard<std::mutex> state_lk(st->mu);
-  Lease lease(eng);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_import_series: no job context available");
-  HIP_TRY(e, hipSetDevice(e->device));
-  const uint64_t K = st->K;
-  std::vector<uint32_t> n;
-  std::vector<unsigned long long> off;
-  try { n.resize(K); off.resize(K + 1); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
-  HIP_TRY(e, hipMemcpy(n.data(), state_view(st, st->cur).n, K * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  off[0] = 0;
-  for (uint64_t k = 0; k < K; ++k) {
-    if (len[k] != n[k])
-      return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_series: key %llu has %llu values, its state has n = %u (import the moments first); state unchanged",
-                  (unsigned long long)k, (unsigned long long)len[k], n[k]);
-    off[k + 1] = off[k] + len[k];
-  }
-  const uint64_t total = off[K];
-  if (total && !values) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_series: values is NULL");
-  // into the candidate copy, which then trades places with the current one: any failure leaves the series as it was
-  const int cand = st->cur ^ 1;
-  unsigned long long *val = st->ser_val[cand];
-  if (st->ser_cap[cand] < total) {
-    void *p = nullptr;
-    const hipError_t r = hipMalloc(&p, total * 8);
-    if (r != hipSuccess) { (void)hipGetLastError(); return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_import_series: %s; state unchanged", hipGetErrorString(r)); }
-    if (val) hipFree(val);
-    st->ser_val[cand] = val = static_cast<unsigned long long *>(p);
-    st->ser_cap[cand] = total;
-  }
-  if (total) HIP_TRY(e, hipMemcpy(val, values, total * 8, hipMemcpyHostToDevice));
-  HIP_TRY(e, hipMemcpy(st->ser_off[cand], off.data(), (K + 1) * 8, hipMemcpyHostToDevice));
-  std::swap(st->ser_off[0], st->ser_off[1]);
-  std::swap(st->ser_val[0], st->ser_val[1]);
-  std::swap(st->ser_cap[0], st->ser_cap[1]);
-  st->ser_len[st->cur] = total;
-  st->times_stale = st->times;   // the times of a times state come next (tad_state_import_times)
-  return TAD_OK;
-}
-
-int tad_state_export_times(tad_engine *eng, const tad_state *st, int64_t *t) {
-  if (!eng || !st) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_times: bad arguments");
-  if (!st->times) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_times: the state has no times (TAD_STATE_TIMES)");
-  std::lock_guard<std::mutex> state_lk(st->mu);
-  if (st->times_stale)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_times: the series was imported without its times (tad_state_import_times)");
-  const uint64_t total = st->ser_len[st->cur];
-  if (!total) return TAD_OK;
-  if (!t) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_export_times: t is NULL");
-  Lease lease(eng);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_export_times: no job context available");
-  HIP_TRY(e, hipSetDevice(e->device));
-  HIP_TRY(e, hipMemcpy(t, st->ser_t[st->cur], total * 8, hipMemcpyDeviceToHost));
-  return TAD_OK;
-}
-
-int tad_state_import_times(tad_engine *eng, tad_state *st, const int64_t *t) {
-  if (!eng || !st) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_times: bad arguments");
-  if (!st->times) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_times: the state has no times (TAD_STATE_TIMES)");
-  std::lock_guard<std::mutex> state_lk(st->mu);
-  Lease lease(eng);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_import_times: no job context available");
-  HIP_TRY(e, hipSetDevice(e->device));
-  const uint64_t K = st->K, total = st->ser_len[st->cur];
-  if (total && !t) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_times: t is NULL");
-  std::vector<long long> last;
-  std::vector<unsigned long long> off;
-  try { last.resize(K); off.resize(K + 1); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
-  HIP_TRY(e, hipMemcpy(off.data(), st->ser_off[st->cur], (K + 1) * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(e, hipMemcpy(last.data(), state_view(st, st->cur).last_t, K * sizeof(long long), hipMemcpyDeviceToHost));
-  for (uint64_t k = 0; k < K; ++k) {
-    if (off[k + 1] == off[k]) continue;
-    for (uint64_t i = off[k] + 1; i < off[k + 1]; ++i)
-      if (t[i] <= t[i - 1])
-        return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_times: the times of key %llu are not strictly ascending; state unchanged",
-                    (unsigned long long)k);
-    if (t[off[k + 1] - 1] != last[k])
-      return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_state_import_times: the last time of key %llu is %lld, its state has last_t = %lld; state unchanged",
-                  (unsigned long long)k, (long long)t[off[k + 1] - 1], last[k]);
-  }
-  // into the candidate copy, which then trades places with the current one: any failure leaves the times as they were
-  const int cand = st->cur ^ 1;
-  if (st->ser_tcap[cand] < total) {
-    void *p = nullptr;
-    const hipError_t r = hipMalloc(&p, total * 8);
-    if (r != hipSuccess) { (void)hipGetLastError(); return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_import_times: %s; state unchanged", hipGetErrorString(r)); }
-    if (st->ser_t[cand]) hipFree(st->ser_t[cand]);
-    st->ser_t[cand] = static_cast<long long *>(p);
-    st->ser_tcap[cand] = total;
-  }
-  if (total) HIP_TRY(e, hipMemcpy(st->ser_t[cand], t, total * 8, hipMemcpyHostToDevice));
-  std::swap(st->ser_t[0], st->ser_t[1]);
-  std::swap(st->ser_tcap[0], st->ser_tcap[1]);
-  st->times_stale = false;
-  return TAD_OK;
-}
-
-// tad_state_bytes with the state's lock held
-static uint64_t state_device_bytes(const tad_state *st) {
-  const uint64_t off = 2 * (st->K + 1) * 8;   // both copies of a key-offset array
-  uint64_t b = 2 * (uint64_t)state_bytes(st->K);
-  if (st->history) b += off + (st->hist_cap[0] + st->hist_cap[1]) * 8;
-  if (st->series) b += off + (st->ser_cap[0] + st->ser_cap[1]) * 8;
-  if (st->times) b += (st->ser_tcap[0] + st->ser_tcap[1]) * 8;
-  return b;
-}
-
-int tad_state_bytes(tad_engine *eng, const tad_state *st, uint64_t *bytes) {
-  if (!eng || !st || !bytes) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_bytes: bad arguments");
-  std::lock_guard<std::mutex> state_lk(st->mu);
-  *bytes = state_device_bytes(st);
-  return TAD_OK;
-}
-
-// tad.h: every key keeps a suffix of its series (kernels in tad_history.hip).  Writes only the candidate copies of the moments, offsets
-// and arenas; they become current together once every launch has succeeded.
-int tad_state_trim(tad_engine *eng, tad_state *st, uint64_t keep_points, int64_t keep_from_t, double ewma_alpha, uint64_t *dropped) {
-  if (dropped) *dropped = 0;
-  if (!eng || !st) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_trim: bad arguments");
-  if (!st->series)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_trim: the state has no series (TAD_STATE_SERIES): a history alone does not know "
-                                               "which values are oldest; state unchanged");
-  if (keep_from_t != 0 && !st->times)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_trim: keep_from_t needs a state with times (TAD_STATE_TIMES); state unchanged");
-  if (!(ewma_alpha >= 0.0 && ewma_alpha <= 1.0)) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_trim: ewma_alpha out of range");
-  std::lock_guard<std::mutex> state_lk(st->mu);   // (the order of tad_run_stream: the state, then a job context)
-  if (st->times_stale)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_trim: the series was imported without its times (tad_state_import_times)");
-  const uint64_t K = st->K;
-  const int cur = st->cur, cand = cur ^ 1;
-  const uint64_t S = st->ser_len[cur];
-  if ((keep_points == 0 && keep_from_t == 0) || S == 0) return TAD_OK;
-  Lease lease(eng);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_trim: no job context available");
-  HIP_TRY(e, hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  const double alpha = ewma_alpha == 0.0 ? 0.5 : ewma_alpha;
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
-  int rc;
-  if ((rc = ensure(e, e->hs_kcnt, kpad * 12 + 64)) != TAD_OK) return rc;        // retained | evicted | chunks (later the long-sort list) | count
-  if ((rc = ensure(e, e->hs_koff, (kpad + 4) * 16)) != TAD_OK) return rc;       // evicted offsets | chunk offsets, K + 1 each
-  if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K) * sizeof(unsigned long long))) != TAD_OK) return rc;
-  uint32_t *rcnt = static_cast<uint32_t *>(e->hs_kcnt.p), *ecnt = rcnt + kpad, *chunks = ecnt + kpad;
-  unsigned int *long_count = reinterpret_cast<unsigned int *>(chunks + kpad);
-  unsigned long long *eoff = static_cast<unsigned long long *>(e->hs_koff.p), *coff = eoff + kpad + 4;
-  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
-  // 1. what every key keeps; the candidate series offsets, the packed evicted offsets and the chunk offsets
-  launch_trim_keep(s, K, st->ser_off[cur], keep_from_t != 0 ? st->ser_t[cur] : nullptr, keep_points, (long long)keep_from_t, rcnt, ecnt, chunks);
-  launch_scan(s, rcnt, st->ser_off[cand], K, scratch);
-  launch_scan(s, ecnt, eoff, K, scratch);
-  launch_scan(s, chunks, coff, K, scratch);
-  HIP_TRY(e, hipGetLastError());
-  HIP_TRY(e, hipMemcpyAsync(e->tail_host, st->ser_off[cand] + K, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipMemcpyAsync(e->tail_host + 8, eoff + K, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipStreamSynchronize(s));
-  unsigned long long kept = 0, evicted = 0;
-  memcpy(&kept, e->tail_host, 8);
-  memcpy(&evicted, e->tail_host + 8, 8);
-  if (evicted == 0) return TAD_OK;   // nothing to drop: the state stays as it is (the candidate offsets are scratch)
-  // 2. the candidate arenas at their new size, the evicted values' scratch: an allocation failure leaves the state as it is
-  if ((rc = size_trim_arena(e, st->ser_val[cand], st->ser_cap[cand], kept, true)) != TAD_OK) return rc;
-  if (st->times && (rc = size_trim_arena(e, st->ser_t[cand], st->ser_tcap[cand], kept, true)) != TAD_OK) return rc;
-  unsigned long long *ev = nullptr, *es = nullptr;
-  if (st->history) {
-    if ((rc = size_trim_arena(e, st->hist_val[cand], st->hist_cap[cand], kept, true)) != TAD_OK) return rc;
-    if ((rc = ensure(e, e->hs_val, evicted * 8)) != TAD_OK) return rc;
-    if ((rc = ensure(e, e->hs_sorted, evicted * 8)) != TAD_OK) return rc;
-    ev = static_cast<unsigned long long *>(e->hs_val.p);
-    es = static_cast<unsigned long long *>(e->hs_sorted.p);
-  }
-  // 3. the retained suffixes (and the evicted prefixes); 4. the history without the evicted values; 5. the moments
-  const uint64_t bound = trim_chunks_bound(K, S);
-  launch_trim_copy(s, bound, coff, K, st->ser_off[cur], st->ser_val[cur], st->times ? st->ser_t[cur] : nullptr, st->ser_off[cand], st->ser_val[cand],
-                   st->times ? st->ser_t[cand] : nullptr, eoff, ev);
-  if (st->history) {
-    HIP_TRY(e, hipMemcpyAsync(st->hist_off[cand], st->ser_off[cand], (K + 1) * 8, hipMemcpyDeviceToDevice, s));
-    launch_hist_sort(s, ev, eoff, K, es, chunks, long_count);
-    launch_hist_subtract(s, bound, coff, K, st->hist_off[cur], st->hist_val[cur], eoff, es, st->hist_off[cand], st->hist_val[cand], true);
-  }
-  launch_trim_moments(s, K, rcnt, ecnt, st->ser_off[cand], st->ser_val[cand], alpha, state_view(st, cur), state_view(st, cand));
-  HIP_TRY(e, hipGetLastError());
-  HIP_TRY(e, hipStreamSynchronize(s));
-  // everything succeeded: the candidate becomes current; the old arenas, now the candidates, are given back when far too big for it
-  st->ser_len[cand] = kept;
-  if (st->history) st->hist_len[cand] = kept;
-  st->cur = cand;
-  (void)size_trim_arena(e, st->ser_val[cur], st->ser_cap[cur], kept, false);
-  if (st->times) (void)size_trim_arena(e, st->ser_t[cur], st->ser_tcap[cur], kept, false);
-  if (st->history) (void)size_trim_arena(e, st->hist_val[cur], st->hist_cap[cur], kept, false);
-  if (dropped) *dropped = evicted;
-  return TAD_OK;
-}
-
-// tad.h: the unseen and the idle keys leave, the survivors are renumbered densely (kernels in tad_compact.hip).  Fresh moment blocks and
-// offsets at the new key count and, when points leave, the candidate arenas are written; they become the state's together once every
-// launch has succeeded.
-int tad_state_compact(tad_engine *eng, tad_state *st, int64_t retire_before_t, uint64_t *remap, tad_mem remap_memory, tad_compact_stats *stats) {
-  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_state_compact: engine is NULL");
-  if (!st || !remap || (remap_memory != TAD_MEM_HOST && remap_memory != TAD_MEM_DEVICE))
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_compact: bad arguments (state, remap of num_keys entries in host or device memory); state unchanged");
-  std::lock_guard<std::mutex> state_lk(st->mu);   // (the order of tad_run_stream: the state, then a job context)
-  if (st->times_stale)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_compact: the series was imported without its times (tad_state_import_times)");
-  const uint64_t K = st->K;
-  const int cur = st->cur, cand = cur ^ 1;
-  Lease lease(eng);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_compact: no job context available");
-  HIP_TRY(e, hipSetDevice(e->device));
-  hipStream_t s = e->stream;
-  const bool host_remap = remap_memory == TAD_MEM_HOST;
-  // workspace: hs_kcnt = live | series lengths | history lengths | series chunks | history chunks | counters; hs_koff = new ids | candidate
-  // series offsets | candidate history offsets | series chunk offsets | history chunk offsets, K + 1 each; in_key = a host remap's staging
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
-  const size_t cnt_bytes = kpad * 20 + 64, off_bytes = (kpad + 4) * 40, scan_bytes = scan_scratch_elems(K) * sizeof(unsigned long long);
-  const size_t need = cnt_bytes + off_bytes + scan_bytes + (host_remap ? (size_t)K * 8 : 0);
-  if (need > e->ws_limit)
-    return fail(e, TAD_ERR_GRID_TOO_LARGE, "tad_state_compact needs %llu bytes of scratch > workspace limit %llu; state unchanged", (unsigned long long)need,
-                (unsigned long long)e->ws_limit);
-  int rc;
-  if ((rc = ensure(e, e->hs_kcnt, cnt_bytes)) != TAD_OK || (rc = ensure(e, e->hs_koff, off_bytes)) != TAD_OK ||
-      (rc = ensure(e, e->scan_scratch, scan_bytes)) != TAD_OK || (host_remap && (rc = ensure(e, e->in_key, (size_t)K * 8)) != TAD_OK))
-    return rc;
-  uint32_t *live = static_cast<uint32_t *>(e->hs_kcnt.p), *slen = live + kpad, *hlen = slen + kpad, *schunks = hlen + kpad, *hchunks = schunks + kpad;
-  CompactCounters *cc = reinterpret_cast<CompactCounters *>(hchunks + kpad);
-  unsigned long long *newid = static_cast<unsigned long long *>(e->hs_koff.p), *sscan = newid + kpad + 4, *hscan = sscan + kpad + 4,
-                     *scoff = hscan + kpad + 4, *hcoff = scoff + kpad + 4;
-  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
-  unsigned long long *d_remap = host_remap ? static_cast<unsigned long long *>(e->in_key.p) : reinterpret_cast<unsigned long long *>(remap);
-  const StreamState cur_view = state_view(st, cur);
-  // 1. who survives, what it keeps; 2. the new ids, the candidate offsets and the chunk offsets; one round trip for the totals
-  HIP_TRY(e, hipEventRecord(e->ev[0], s));
-  HIP_TRY(e, hipMemsetAsync(cc, 0, sizeof(CompactCounters), s));
-  launch_compact_mark(s, K, cur_view, st->series ? st->ser_off[cur] : nullptr, st->history ? st->hist_off[cur] : nullptr, (long long)retire_before_t, live,
-                      slen, hlen, schunks, hchunks, cc);
-  launch_scan(s, live, newid, K, scratch);
-  launch_scan(s, slen, sscan, K, scratch);
-  launch_scan(s, hlen, hscan, K, scratch);
-  launch_scan(s, schunks, scoff, K, scratch);
-  launch_scan(s, hchunks, hcoff, K, scratch);
-  HIP_TRY(e, hipGetLastError());
-  unsigned long long *tot = reinterpret_cast<unsigned long long *>(e->tail_host);
-  const unsigned long long *tails[5] = {newid + K, sscan + K, hscan + K, scoff + K, hcoff + K};
-  for (int i = 0; i < 5; ++i) HIP_TRY(e, hipMemcpyAsync(tot + i, tails[i], 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipMemcpyAsync(tot + 5, cc, 24, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipStreamSynchronize(s));
-  const uint64_t m = tot[0], skept = tot[1], hkept = tot[2], s_chunks = tot[3], h_chunks = tot[4];
-  const uint64_t n_unseen = tot[5], n_idle = tot[6], dropped = tot[7];
-  if (m > K || m + n_unseen + n_idle != K) return fail(e, TAD_ERR_HIP, "tad_state_compact: %llu survivors of %llu keys; state unchanged", (unsigned long long)m, (unsigned long long)K);
-  tad_compact_stats cs{};
-  cs.keys_before = K;
-  cs.keys_after = m;
-  cs.keys_unseen = n_unseen;
-  cs.keys_idle = n_idle;
-  cs.points_dropped = dropped;
-  cs.bytes_before = state_device_bytes(st);
-  cs.job_context = e->index;
-  auto remap_out = [&]() -> int {
-    if (host_remap) HIP_TRY(e, hipMemcpyAsync(remap, d_remap, K * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(e, hipEventRecord(e->ev[1], s));
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipStreamSynchronize(s));
-    HIP_TRY(e, hipEventElapsedTime(&cs.ms_total, e->ev[0], e->ev[1]));
-    return TAD_OK;
-  };
-  if (m == K) {   // nothing retired: the identity, the state as it is
-    launch_compact_keys(s, K, live, newid, sscan, hscan, false, cur_view, cur_view, nullptr, nullptr, d_remap);
-    if ((rc = remap_out()) != TAD_OK) return rc;
-    cs.num_keys = K;
-    cs.bytes_after = cs.bytes_before;
-    if (stats) *stats = cs;
-    return TAD_OK;
-  }
-  // 3. fresh moment blocks and offsets for max(m, 1) keys, all zero: with no survivor the one key left is unseen and its segments empty
-  const uint64_t Km = m ? m : 1;
-  const bool gather = dropped != 0;        // only unseen keys went: the arenas already are the survivors' segments in order
-  const int to = gather ? cand : cur;      // the copy that is current afterwards
-  tad_state fresh;
-  fresh.K = Km;
-  hipError_t r = hipSuccess;
-  for (int i = 0; i < 2 && r == hipSuccess; ++i) {
-    r = hipMalloc(&fresh.block[i], state_bytes(Km));
-    if (r == hipSuccess) r = hipMemsetAsync(fresh.block[i], 0, state_bytes(Km), s);
-    if (r == hipSuccess && st->history) r = hipMalloc(reinterpret_cast<void **>(&fresh.hist_off[i]), (Km + 1) * 8);
-    if (r == hipSuccess && st->history) r = hipMemsetAsync(fresh.hist_off[i], 0, (Km + 1) * 8, s);
-    if (r == hipSuccess && st->series) r = hipMalloc(reinterpret_cast<void **>(&fresh.ser_off[i]), (Km + 1) * 8);
-    if (r == hipSuccess && st->series) r = hipMemsetAsync(fresh.ser_off[i], 0, (Km + 1) * 8, s);
-  }
-  auto drop_fresh = [&]() {
-    (void)hipStreamSynchronize(s);
-    for (int i = 0; i < 2; ++i) {
-      if (fresh.block[i]) hipFree(fresh.block[i]);
-      if (fresh.hist_off[i]) hipFree(fresh.hist_off[i]);
-      if (fresh.ser_off[i]) hipFree(fresh.ser_off[i]);
-    }
-  };
-  if (r != hipSuccess) {
-    (void)hipGetLastError();
-    drop_fresh();
-    return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_state_compact: %s (state unchanged)", hipGetErrorString(r));
-  }
-  rc = TAD_OK;
-  if (gather) {   // the candidate arenas at their new size (the trim's rule): an allocation failure leaves the state as it is
-    const char *who = "tad_state_compact";
-    if (st->series) rc = size_trim_arena(e, st->ser_val[cand], st->ser_cap[cand], skept, true, who);
-    if (rc == TAD_OK && st->times) rc = size_trim_arena(e, st->ser_t[cand], st->ser_tcap[cand], skept, true, who);
-    if (rc == TAD_OK && st->history) rc = size_trim_arena(e, st->hist_val[cand], st->hist_cap[cand], hkept, true, who);
-  }
-  if (rc != TAD_OK) { drop_fresh(); return rc; }
-  // 4. the survivors' moments and offsets, remap; 5. their segments
-  launch_compact_keys(s, K, live, newid, sscan, hscan, true, cur_view, stream_view(fresh.block[to], Km), st->series ? fresh.ser_off[to] : nullptr,
-                      st->history ? fresh.hist_off[to] : nullptr, d_remap);
-  if (gather && st->series)
-    launch_compact_copy(s, s_chunks, scoff, K, st->ser_off[cur], st->ser_val[cur], st->times ? st->ser_t[cur] : nullptr, sscan, st->ser_val[cand],
-                        st->times ? st->ser_t[cand] : nullptr);
-  if (gather && st->history) launch_compact_copy(s, h_chunks, hcoff, K, st->hist_off[cur], st->hist_val[cur], nullptr, hscan, st->hist_val[cand], nullptr);
-  if ((rc = remap_out()) != TAD_OK) { drop_fresh(); return rc; }
-  // everything succeeded: the fresh blocks and offsets replace the old ones; after a gather the candidate arenas become current and the
-  // old ones, now the candidates, are given back when far too big
-  for (int i = 0; i < 2; ++i) {
-    hipFree(st->block[i]); st->block[i] = fresh.block[i];
-    if (st->history) { hipFree(st->hist_off[i]); st->hist_off[i] = fresh.hist_off[i]; }
-    if (st->series) { hipFree(st->ser_off[i]); st->ser_off[i] = fresh.ser_off[i]; }
-  }
-  st->K = Km;
-  if (gather) {
-    if (st->series) st->ser_len[cand] = skept;
-    if (st->history) st->hist_len[cand] = hkept;
-    st->cur = cand;
-    if (st->series) (void)size_trim_arena(e, st->ser_val[cur], st->ser_cap[cur], skept, false);
-    if (st->times) (void)size_trim_arena(e, st->ser_t[cur], st->ser_tcap[cur], skept, false);
-    if (st->history) (void)size_trim_arena(e, st->hist_val[cur], st->hist_cap[cur], hkept, false);
-    cs.series_points_moved = st->series ? skept : 0;
-    cs.history_points_moved = st->history ? hkept : 0;
-  }
-  cs.num_keys = Km;
-  cs.bytes_after = state_device_bytes(st);
-  if (stats) *stats = cs;
-  return TAD_OK;
-}
-
 // what tad_run_state and tad_run_state_window refuse before they take the state's lock (who: the call's name for the message)
 static int check_state_job(tad_engine *eng, const tad_state *st, const tad_job *job, tad_result **out, const char *who, const char *narrow) {
   if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
@@ -2425,13 +1706,12 @@ static int check_state_job(tad_engine *eng, const tad_state *st, const tad_job *
 int tad_run_state(tad_engine *eng, tad_state *st, const tad_job *job, tad_mem out_memory, tad_result **out) {
   int rc = check_state_job(eng, st, job, out, "tad_run_state", "the window is what the state holds (tad_state_trim narrows it)");
   if (rc != TAD_OK) return rc;
-  std::lock_guard<std::mutex> state_lk(st->mu);   // (the order of tad_run_stream: the state, then a job context)
+  StateCall call(eng, st);
   if (st->times_stale)
     return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: the series was imported without its times (tad_state_import_times)");
-  Lease lease(eng, job->id, job->algo == TAD_ALGO_ARIMA);
-  if (!lease.c) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_run_state: no job context available");
-  if ((rc = run_view_begin(lease.c, st->K)) != TAD_OK) return rc;
-  return run_view_locked(lease.c, series_view(st, st->cur), job, out_memory, out, 0);
+  if ((rc = call.enter("tad_run_state", job->id, job->algo == TAD_ALGO_ARIMA)) != TAD_OK) return rc;
+  if ((rc = run_view_begin(call.e, st->K)) != TAD_OK) return rc;
+  return run_view_locked(call.e, series_view(st, st->cur), job, out_memory, out, 0);
 }
 
 int tad_window_history_by_sort(uint64_t window_points, uint64_t state_points) { return win_hist_by_sort(window_points, state_points) ? 1 : 0; }
@@ -2444,12 +1724,11 @@ int tad_run_state_window(tad_engine *eng, tad_state *st, const tad_job *job, int
   if (rc != TAD_OK) return rc;
   if (from_t != 0 && to_t != 0 && from_t > to_t)
     return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state_window: from_t is later than to_t");
-  std::lock_guard<std::mutex> state_lk(st->mu);   // (the order of tad_run_state: the state, then a job context)
+  StateCall call(eng, st);
   if (st->times_stale)
     return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state_window: the series was imported without its times (tad_state_import_times)");
-  Lease lease(eng, job->id, job->algo == TAD_ALGO_ARIMA);
-  JobCtx *e = lease.c;
-  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_run_state_window: no job context available");
+  if ((rc = call.enter("tad_run_state_window", job->id, job->algo == TAD_ALGO_ARIMA)) != TAD_OK) return rc;
+  JobCtx *e = call.e;
   const uint64_t K = st->K;
   if ((rc = run_view_begin(e, K)) != TAD_OK) return rc;
   const StateView whole = series_view(st, st->cur);
@@ -2500,13 +1779,13 @@ int tad_run_state_window(tad_engine *eng, tad_state *st, const tad_job *job, int
     launch_trim_moments(s, K, wlen, ecnt, woff, wval, alpha, whole.mom, wmom);
     if (subtract) {
       launch_hist_sort(s, ev, eoff, K, es, chunks, long_count);
-      launch_hist_subtract(s, bound, coff, K, whole.hist_off, whole.hist_val, eoff, es, woff, wh, true);
+      launch_hist_subtract(s, bound, coff, K, whole.hoff, whole.hval, eoff, es, woff, wh, true);
     } else if (dbscan) {
       launch_hist_sort(s, wval, woff, K, wh, chunks, long_count);
     }
     HIP_TRY(e, hipGetLastError());
     v.soff = woff; v.sval = wval; v.st = wt; v.mom = wmom;
-    if (dbscan) { v.hist_off = woff; v.hist_val = wh; }
+    if (dbscan) { v.hoff = woff; v.hval = wh; }
   }
   e->done.store(1);
   return run_view_locked(e, v, job, out_memory, out, 1);
@@ -2533,19 +1812,19 @@ int tad_state_merge(tad_engine *eng, tad_state *st, const tad_job *job, const ta
   }
   tad_job j = *job;   // the detector is not run: a stream batch of the EWMA kind up to the end of Stage 0
   j.algo = TAD_ALGO_EWMA;
-  std::unique_lock<std::mutex> state_lk(st->mu);   // (the order of tad_run_stream: the state, then a job context)
+  StateCall call(eng, st);
   if (st->times_stale)
     return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: the series was imported without its times (tad_state_import_times); state unchanged");
-  Lease lease(eng, j.id, false);
-  if (!lease.c) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_state_merge: no job context available");
-  PauseHold hold(eng);
-  lease.c->hold = &hold;
+  int rc = call.enter("tad_state_merge", j.id);
+  if (rc != TAD_OK) return rc;
+  PauseHold hold(eng);     // (declared after the call's context: dropped before the context goes back to the pool)
+  call.e->hold = &hold;
   MergeCall mc;
   mc.keep_from = keep_from_t;
-  lease.c->merge = &mc;
+  call.e->merge = &mc;
   tad_result *none = nullptr;
-  const int rc = run_job_locked(lease.c, &j, cols, TAD_MEM_DEVICE, &none, nullptr, st, 0);
-  lease.c->merge = nullptr;
+  rc = run_job_locked(call.e, &j, cols, TAD_MEM_DEVICE, &none, nullptr, st, 0);
+  call.e->merge = nullptr;
   if (rc == TAD_OK && stats) *stats = mc.stats;
   return rc;
 }

@@ -1,6 +1,7 @@
-// tad_engine.h — PRIVATE header of libtad_mi355x.so's host side: the engine, its pool of job contexts, and what the four translation
-// units of the C ABI share (tad_engine.cpp: life cycle, pool, memory; tad_capi.cpp: the job; tad_capi_ingest.cpp: the ingest entry
-// points; tad_capi_series.cpp: the per-series entry points).  HIP only: there is no CPU fallback in this library (the CPU oracle under
+// tad_engine.h — PRIVATE header of libtad_mi355x.so's host side: the engine, its pool of job contexts, and what the translation
+// units of the C ABI share (tad_engine.cpp: life cycle, pool, memory; tad_capi.cpp: the job, and the state calls that run through it;
+// tad_capi_state.cpp: the life of a streaming state; tad_capi_ingest.cpp: the ingest entry points; tad_capi_series.cpp: the per-series
+// entry points; tad_capi_keydict.cpp: the key dictionary).  HIP only: there is no CPU fallback in this library (the CPU oracle under
 // oracle/ is test infrastructure and is never linked or called from here).
 //
 // Threading (controller.go:199-201 runs four workers, Spark ran one pod per job): an engine owns a small POOL of job
@@ -21,8 +22,10 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "tad_internal.h"
@@ -132,33 +135,41 @@ struct MergeCall {
   uint64_t added = 0;      // series points gained (inserted + appended)
 };
 
+// A double-buffered value arena of a streaming state: two device arrays of T and their capacities in values, indexed like
+// tad_state::block[] by cur / cur ^ 1.  Arenas grow geometrically and are kept; a plain state allocates none.
+template <typename T> struct Arena {
+  T *p[2] = {nullptr, nullptr};
+  uint64_t cap[2] = {0, 0};
+  void swap() { std::swap(p[0], p[1]); std::swap(cap[0], cap[1]); }
+};
+
+// every key's values as one segment each: off[i] (K + 1 entries) into val.p[i] (val.cap[i] entries, len[i] used)
+struct Segments {
+  unsigned long long *off[2] = {nullptr, nullptr};
+  uint64_t len[2] = {0, 0};
+  Arena<unsigned long long> val;
+};
+
 // per-key running state of the streaming EWMA detector: two copies (the count pass writes the candidate next state,
 // it becomes current only when the batch succeeds)
 struct tad_state {
   uint64_t K = 0;
   void *block[2] = {nullptr, nullptr};
   int cur = 0;
-  // TAD_STATE_HISTORY: every key's aggregated point values, ascending per key — hist_off[i] (K + 1 entries) and hist_val[i] (hist_cap
-  // entries, hist_len used).  Double-buffered with the same index as block[]: a batch merges into the candidate (cur ^ 1), which
+  // TAD_STATE_HISTORY: every key's aggregated point values, ascending per key — hist.off[i] (K + 1 entries) and hist.val.p[i] (hist.val.cap[i]
+  // entries, hist.len[i] used).  Double-buffered with the same index as block[]: a batch merges into the candidate (cur ^ 1), which
   // becomes current with the moments.  Arenas grow geometrically and are kept; a plain state allocates none of this.
   bool history = false;
-  unsigned long long *hist_off[2] = {nullptr, nullptr};
-  unsigned long long *hist_val[2] = {nullptr, nullptr};
-  uint64_t hist_cap[2] = {0, 0};
-  uint64_t hist_len[2] = {0, 0};
-  // TAD_STATE_SERIES: every key's aggregated point values in time order — ser_off[i] (K + 1 entries) and ser_val[i]; the same double
+  Segments hist;
+  // TAD_STATE_SERIES: every key's aggregated point values in time order — ser.off[i] (K + 1 entries) and ser.val.p[i]; the same double
   // buffering and growth as the history (a batch writes old segment ++ new points into the candidate)
   bool series = false;
-  unsigned long long *ser_off[2] = {nullptr, nullptr};
-  unsigned long long *ser_val[2] = {nullptr, nullptr};
-  uint64_t ser_cap[2] = {0, 0};
-  uint64_t ser_len[2] = {0, 0};
-  // TAD_STATE_TIMES (with a series): every series point's flowEndSeconds, parallel to ser_val (same offsets ser_off[i], same double
-  // buffering; its own capacity).  times_stale: tad_state_import_series replaced the series and tad_state_import_times has not yet
+  Segments ser;
+  // TAD_STATE_TIMES (with a series): every series point's flowEndSeconds, parallel to ser.val (same offsets ser.off[i], same lengths, same
+  // double buffering; its own capacity).  times_stale: tad_state_import_series replaced the series and tad_state_import_times has not yet
   // brought the times that go with it — batches, trims and exports of the times are refused until it has.
   bool times = false, times_stale = false;
-  long long *ser_t[2] = {nullptr, nullptr};
-  uint64_t ser_tcap[2] = {0, 0};
+  Arena<long long> ser_times;
   mutable std::mutex mu;     // batches of one state are serial (tad_run_stream from two threads on one state)
 };
 
@@ -285,6 +296,25 @@ struct Lease {
 };
 
 
+// How every call on a state that needs a job context starts: the state's mutex FIRST (the constructor), then — after whatever the call
+// refuses or answers from the host alone — a context (enter).  One order for all: a thread that waits for a context never holds one, so
+// a call on a busy state cannot keep the pool's last context from the batch that holds the state.  The context goes back before the
+// state is unlocked.  who: the call's name in its messages.
+struct StateCall {
+  tad_engine *eng;
+  std::unique_lock<std::mutex> state_lk;
+  std::optional<Lease> lease;
+  JobCtx *e = nullptr;
+  StateCall(tad_engine *eng_, const tad_state *st) : eng(eng_), state_lk(st->mu) {}
+  int enter(const char *who, const char *id = nullptr, bool low_priority = false) {
+    lease.emplace(eng, id, low_priority);
+    e = lease->c;
+    if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "%s: no job context available", who);
+    HIP_TRY(e, hipSetDevice(e->device));
+    return TAD_OK;
+  }
+};
+
 // recycled device result blocks (engine-wide: a result is freed by whoever holds it)
 void release_block(tad_engine *eng, void *p, size_t cap);
 inline void release_block(JobCtx *e, void *p, size_t cap) { release_block(e->eng, p, cap); }
@@ -329,6 +359,15 @@ struct JobParams {
 int ensure_rcp_table(JobCtx *e, uint64_t T);
 int ensure_key_buffers(JobCtx *e, uint64_t K);
 void emit_rows(JobCtx *e, Grid g, Lattice L, const JobParams &jp, OutRows out, uint64_t rows = 0);
+
+// (tad_capi_state.cpp) shared with the batches on a state (tad_capi.cpp)
+size_t state_bytes(uint64_t K);                              // one block of K keys' running state
+StreamState stream_view(void *block, uint64_t K);            // the arrays inside such a block
+StreamState state_view(const tad_state *st, int which);
+StateView series_view(const tad_state *st, int which);       // copy `which` as the detectors of tad_run_state read it
+int state_grow_candidates(JobCtx *e, tad_state *st, uint64_t P_cap);   // room for a batch of at most P_cap new points
+void state_commit(tad_state *st, uint64_t n_ser, uint64_t n_hist); // the candidate copies become current
+uint64_t state_device_bytes(const tad_state *st);            // tad_state_bytes with the state's lock held
 
 }  // namespace tadh
 

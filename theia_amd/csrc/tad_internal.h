@@ -447,7 +447,7 @@ void launch_win_ewma(hipStream_t s, uint64_t K, const unsigned long long *soff, 
 // nk[i] = the key of series point i
 void launch_win_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, unsigned long long *nk);
 // What tad_run_state's kernels read: K keys holding P points, key k's values and times in time order at [soff[k], soff[k + 1]), the
-// moments of those points and, for DBSCAN, the same values sorted per key at hist_off / hist_val.  tad_run_state passes the state's
+// moments of those points and, for DBSCAN, the same values sorted per key at hoff / hval.  tad_run_state passes the state's
 // current copies; tad_run_state_window passes the view it built in context workspace.
 struct StateView {
   uint64_t K = 0, P = 0;
@@ -455,7 +455,7 @@ struct StateView {
   const long long *st = nullptr;
   StreamState mom{};   // n, avg, m2 of the view's points.  In a WINDOW's view ewma is replayed with the job's alpha and last_t is the
                        // state's, not the window's newest time: the detectors of run_view_locked read neither, a stream-style kernel must not
-  const unsigned long long *hist_off = nullptr, *hist_val = nullptr;
+  const unsigned long long *hoff = nullptr, *hval = nullptr;
 };
 // ---- tad_run_state_window (tad_window.hip): the view of every key's points inside a window ----
 // per key: wbeg = the window's first point inside the key's segment, wlen = its points, ecnt = the key's points outside it (prefix +

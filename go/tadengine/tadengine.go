@@ -1431,6 +1431,111 @@ func (d *KeyDict) Compact(remap []uint64) (uint64, error) {
 	return uint64(n), nil
 }
 
+var stateDropOnce sync.Once
+var stateDropOK bool
+
+// hasStateDrop: the library knows tad_drop_state / tad_drop_stream (tad_features); an older one would not export the calls.
+func hasStateDrop() bool {
+	stateDropOnce.Do(func() { stateDropOK = C.tad_features()&C.TAD_FEATURE_STATE_DROP != 0 })
+	return stateDropOK
+}
+
+// dropJob: the tad_job of the two drop calls.  nSigma / minSamples 0 = the reference's 3 and 3.
+func dropJob(job Job, nSigma float64, minSamples int32) C.tad_job {
+	var cj C.tad_job
+	cj.algo = C.TAD_ALGO_DROP
+	cj.agg_flow = C.tad_agg_flow(job.AggFlow)
+	cj.start_time = C.int64_t(job.StartTime)
+	cj.end_time = C.int64_t(job.EndTime)
+	cj.drop_nsigma = C.double(nSigma)
+	cj.drop_min_samples = C.int32_t(minSamples)
+	id := []byte(job.ID)
+	if len(id) > 63 {
+		id = id[:63]
+	}
+	for i, b := range id {
+		cj.id[i] = C.char(b)
+	}
+	return cj
+}
+
+// resultRows copies a host result's rows and frees it.
+func (s *State) resultRows(res *C.tad_result) []Row {
+	defer C.tad_result_free(s.e.h, res)
+	a := int(res.n_rows)
+	rows := make([]Row, a)
+	if a > 0 {
+		k := unsafe.Slice((*uint64)(unsafe.Pointer(res.key_id)), a)
+		t := unsafe.Slice((*int64)(unsafe.Pointer(res.flow_end_s)), a)
+		x := unsafe.Slice((*float64)(unsafe.Pointer(res.throughput)), a)
+		c := unsafe.Slice((*float64)(unsafe.Pointer(res.algo_calc)), a)
+		sd := unsafe.Slice((*float64)(unsafe.Pointer(res.stddev)), a)
+		for i := range rows {
+			rows[i] = Row{k[i], t[i], x[i], c[i], sd[i]}
+		}
+	}
+	return rows
+}
+
+// DropWindow is the drop detector's batch job over a window of what the state holds, read-only (tad_drop_state): the window is
+// RunWindow's; the rows are exactly those Run with Algo Drop returns over the window's points — AlgoCalc is the key's mean, Stddev
+// pandas' sample std.  job.Algo is ignored (the call is the drop detector's), job.StartTime / EndTime must be 0.  Needs a state made
+// by NewStateWithTimes.
+func (s *State) DropWindow(job Job, nSigma float64, minSamples int32, fromT, toT int64, keepPoints uint64) ([]Row, error) {
+	if !hasStateDrop() {
+		return nil, errors.New("tadengine: libtad_mi355x.so has no tad_drop_state (TAD_FEATURE_STATE_DROP)")
+	}
+	if !s.series || !s.times {
+		return nil, IllegalArgument{"tadengine: DropWindow needs a state made by NewStateWithTimes"}
+	}
+	cj := dropJob(job, nSigma, minSamples)
+	var res *C.tad_result
+	if rc := C.tad_drop_state(s.e.h, s.h, &cj, C.int64_t(fromT), C.int64_t(toT), C.uint64_t(keepPoints), C.TAD_MEM_HOST, &res); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, IllegalArgument{msg}
+		}
+		return nil, fmt.Errorf("tad_drop_state: %s (code %d)", msg, int(rc))
+	}
+	return s.resultRows(res), nil
+}
+
+// DropStream is one batch of the periodical drop job (tad_drop_stream): the state advances exactly as under RunStream with EWMA; the
+// rows are those Run with Algo Drop over everything the state now holds returns for this batch's points.  cols.NumKeys must equal
+// the state's key count.  Needs a state made by NewStateWithSeries or NewStateWithTimes.
+func (s *State) DropStream(job Job, nSigma float64, minSamples int32, cols Columns) ([]Row, error) {
+	if !hasStateDrop() {
+		return nil, errors.New("tadengine: libtad_mi355x.so has no tad_drop_stream (TAD_FEATURE_STATE_DROP)")
+	}
+	if !s.series {
+		return nil, IllegalArgument{"tadengine: DropStream needs a state made by NewStateWithSeries"}
+	}
+	bufs, n, narrow, err := columnBuffers(cols)
+	if err != nil {
+		return nil, err
+	}
+	defer freeBuffers(bufs)
+	cj := dropJob(job, nSigma, minSamples)
+	cj.flags = narrow
+	cj.value_op = C.TAD_OP_AUTO
+	var cc C.tad_columns
+	cc.n_rows = C.uint64_t(n)
+	cc.num_keys = C.uint64_t(cols.NumKeys)
+	cc.memory = C.TAD_MEM_HOST
+	cc.key_id = (*C.uint64_t)(bufs[0])
+	cc.flow_end_s = (*C.int64_t)(bufs[2])
+	cc.value = (*C.uint64_t)(bufs[4])
+	var res *C.tad_result
+	if rc := C.tad_drop_stream(s.e.h, s.h, &cj, &cc, C.TAD_MEM_HOST, &res); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, IllegalArgument{msg}
+		}
+		return nil, fmt.Errorf("tad_drop_stream: %s (code %d)", msg, int(rc))
+	}
+	return s.resultRows(res), nil
+}
+
 func (e *Engine) NewState(numKeys uint64) (*State, error) {
 	var h *C.tad_state
 	if rc := C.tad_state_create(e.h, C.uint64_t(numKeys), &h); rc != C.TAD_OK {

@@ -420,8 +420,8 @@ int tad_run_stream(tad_engine *e, tad_state *s, const tad_job *job, const tad_co
  *   - points judged in earlier batches are not judged again.  A point can stop being noise once later points arrive; the stream
  *     reports each point once, when it arrives.
  * An EWMA batch on a history state appends to the history too; its rows and moments are those of the same batch on a plain state.
- * DBSCAN on a plain state is TAD_ERR_INVALID_ARGUMENT (state unchanged); ARIMA needs a state with a series (below); DROP has no
- * streaming form.
+ * DBSCAN on a plain state is TAD_ERR_INVALID_ARGUMENT (state unchanged); ARIMA needs a state with a series (below); DROP is
+ * refused here and streams through tad_drop_stream (further below).
  * Invariant: after every successful call the history of key k holds n[k] values; a failed batch (late row, key out of range, out of
  * memory) leaves the history unchanged as well as the state.  A batch never evicts: the history grows with the points seen (8 bytes
  * each, twice over: a batch merges into a second copy), and tad_state_history_points is how a caller watches it; a state that also has
@@ -462,7 +462,7 @@ int tad_state_import_history(tad_engine *e, tad_state *s, const uint64_t *len, c
  * rewrite of the series (about 16 B per series point), the Box-Cox fit over the touched keys' series and one ARIMA fit per new point:
  * the fits of earlier points are never run again.  Its workspace follows the touched series (packed), not keys x longest series.
  * An EWMA or DBSCAN batch on a series state appends to the series too; its rows are those of the same batch without a series.
- * ARIMA on a plain or history-only state and DROP on any state are TAD_ERR_INVALID_ARGUMENT (state unchanged).
+ * ARIMA on a plain or history-only state and DROP on any state are TAD_ERR_INVALID_ARGUMENT (state unchanged; DROP: tad_drop_stream).
  * Invariant: after every successful call the series of key k holds n[k] values.  tad_state_resize gives the added keys empty series. */
 #define TAD_STATE_SERIES 2u            /* keep every key's aggregated point values (time order) */
 #define TAD_STATE_TIMES 8u             /* with TAD_STATE_SERIES only: keep every series point's flowEndSeconds too (tad_state_trim, below) */
@@ -525,7 +525,7 @@ int tad_state_import_times(tad_engine *e, tad_state *s, const int64_t *t);
  * Fields of tad_job that are honoured: algo, ewma_alpha, dbscan_eps, dbscan_min_samples, arima_maxiter, flags & TAD_FLAG_EMIT_ALL_POINTS
  * and id; zero means the default, as in tad_run.  agg_flow and value_op are ignored: the points are already aggregated.  Refused with
  * TAD_ERR_INVALID_ARGUMENT: start_time or end_time non-zero (the window is what the state holds; narrow it with tad_state_trim),
- * TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 (there are no input columns), and TAD_ALGO_DROP, which has no streaming form.
+ * TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 (there are no input columns), and TAD_ALGO_DROP, whose window call is tad_drop_state.
  * The contract rests on the state's invariants — the moments are those of the series, the history is the series' values sorted — which
  * every batch and every trim keep; an import that breaks them voids the contract.
  *   - EWMA: stddev = n >= 2 ? sqrt(m2 / (n - 1.0)) : 0.0 from the state's moments; the EWMA value is replayed from 0 over the key's series
@@ -763,6 +763,47 @@ int tad_state_compact(tad_engine *e, tad_state *s, int64_t retire_before_t, uint
                       tad_compact_stats *stats /* may be NULL */);
 int tad_keydict_compact(tad_engine *e, tad_keydict *d, const uint64_t *remap, uint64_t remap_len, tad_mem remap_memory,
                         uint64_t *num_keys /* may be NULL */);
+
+/* ---- the drop detector on a state (TAD_FEATURE_STATE_DROP; check tad_features() before calling these) ----
+ * TAD_ALGO_DROP is the abnormal-traffic-drop detector of the reference's Snowflake backend (drop_detection_udf.py): per key, mean and
+ * pandas' sample std over the key's daily counts, a day is anomalous when it lies more than drop_nsigma std from the mean.  The reference
+ * runs it as an "initial" job over the whole table and names a "periodical" job it does not have (dropDetection.go:282).  These two calls
+ * are that job on a streaming state: tad_drop_stream adds a batch and judges the batch's points against everything the state then holds,
+ * tad_drop_state returns the batch verdicts of a window of the state.  tad_run_stream, tad_run_state and tad_run_state_window keep
+ * refusing TAD_ALGO_DROP; for both calls here job->algo must be TAD_ALGO_DROP (anything else is TAD_ERR_INVALID_ARGUMENT).
+ * pandas sums pairwise (numpy's pairwise_sum_DOUBLE), which running moments cannot reproduce bit for bit; a state created with
+ * TAD_STATE_SERIES holds every key's aggregated values in time order, and both sums are taken over that series in numpy's order.
+ * tad_drop_state, read-only.  The window is tad_run_state_window's: from_t, to_t and keep_points with the same three rules; all zero is
+ * the whole state; from_t > to_t with both non-zero is TAD_ERR_INVALID_ARGUMENT; an empty window or an empty state is TAD_OK with zero
+ * rows.  Contract: with W' the table of one row per series point inside the window, the call returns exactly the rows of
+ * tad_run(TAD_ALGO_DROP) over W' with the same drop_nsigma, drop_min_samples (0 = the defaults 3 and 3) and TAD_FLAG_EMIT_ALL_POINTS:
+ * key_id, flow_end_s, throughput, algo_calc (the key's mean), stddev (pandas' sample std) and anomaly (with the flag), bit for bit, in
+ * (key, time) order, whatever Stage-0 path tad_run takes for W'.  A key has a result iff n >= drop_min_samples && n >= 2, n its points
+ * inside the window; the other keys with points emit nothing and count in keys_no_result.  The state needs TAD_STATE_SERIES |
+ * TAD_STATE_TIMES; no history is needed.  Refused as tad_run_state refuses them: stale times, start_time / end_time non-zero, the
+ * narrow-column flags, a negative drop_nsigma or drop_min_samples.  tad_stats: rows_in = rows_used = n_points = the window's points;
+ * n_keys, n_anomalies, keys_no_result, t0 and host_syncs as tad_run_state_window; the Stage-0 fields zero; pts_mean / pts_m2 merged from
+ * the per-key pairwise mean and sum of squared deviations (equal to tad_run's up to rounding).  After the call, successful or not, the
+ * state is bit for bit what it was.  A window that cuts keys builds tad_run_state_window's view, values and times only — DROP reads no
+ * moments, so none are replayed; a window that leaves every key whole judges the state's own arrays.
+ * tad_drop_stream, the periodical job: one batch.  Its effect on the state is exactly that of tad_run_stream with TAD_ALGO_EWMA and the
+ * same job fields on the same state: the same Stage-0 rule and plan overrides, agg_flow, value_op, start_time / end_time, ewma_alpha and
+ * the narrow flags; moments, ewma, last_t, series, times and history are bit for bit those of the EWMA batch; a late row, a key out of
+ * range or a failed allocation fails the batch and leaves everything as it was; cols->num_keys must equal the state's.  The state needs
+ * TAD_STATE_SERIES; times and history are optional and are appended to when present.  Rows: for the batch's new points only, in (key,
+ * time) order — the rows tad_drop_state with the all-zero window would return after the batch, restricted to the batch's points;
+ * equivalently what tad_run(TAD_ALGO_DROP) over everything the state now holds emits for these points.  Mean and std are taken over the
+ * key's whole post-batch series.  A touched key without a result emits nothing and counts in keys_no_result; untouched keys are not read
+ * at all.  Points of earlier batches are not judged again: each point once, when it arrives, as the DBSCAN and ARIMA streams do.
+ * drop_nsigma / drop_min_samples may differ from batch to batch.  The remaining stats are a DBSCAN stream batch's.
+ * Cost and memory: two passes over the judged keys' series (a lane per key, a wavefront per key of at least 512 points, or of 8 times
+ * the mean length above 8192 keys), no K x T grid and no K x T workspace; about 29 B per key and 13 B per judged point of job-context
+ * workspace, grow-only.  Not yet measured on an MI355X.
+ * Lock order: the state, then a job context, as the calls above; calls on one state are serial, tad_job_progress finds the job by id. */
+#define TAD_FEATURE_STATE_DROP 512u   /* tad_drop_state / tad_drop_stream: the drop detector on a series state */
+int tad_drop_state(tad_engine *e, tad_state *s, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points,
+                   tad_mem out_memory, tad_result **out);
+int tad_drop_stream(tad_engine *e, tad_state *s, const tad_job *job, const tad_columns *cols, tad_mem out_memory, tad_result **out);
 
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).

@@ -30,6 +30,7 @@ TAD_FEATURE_STATE_MERGE = 32                 # tad_features() bit: tad_state_mer
 TAD_FEATURE_STATE_WINDOW = 64                # tad_features() bit: tad_run_state_window, tad_run_state over a time range of the state, read-only
 TAD_FEATURE_KEY_DICT = 128                   # tad_features() bit: tad_keydict, a persistent tuple -> key id dictionary on the device
 TAD_FEATURE_KEY_RETIRE = 256                 # tad_features() bit: tad_state_compact / tad_keydict_compact, dead keys dropped and the rest renumbered
+TAD_FEATURE_STATE_DROP = 512                 # tad_features() bit: tad_drop_state / tad_drop_stream, the drop detector on a series state
 
 
 class Plan(C.Structure):
@@ -175,6 +176,8 @@ SYMBOLS = {
     "tad_keydict_import": (C.c_int, [C.c_void_p, C.c_void_p, u64, C.POINTER(C.c_void_p), C.c_void_p]),
     "tad_state_compact": (C.c_int, [C.c_void_p, C.c_void_p, i64, C.c_void_p, C.c_int, C.POINTER(CompactStats)]),
     "tad_keydict_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
+    "tad_drop_state": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_int, C.POINTER(C.POINTER(Result))]),
+    "tad_drop_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_encode_strings": (C.c_int, [C.c_void_p, C.POINTER(StringColumn), C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]),
     "tad_widen_column": (C.c_int, [C.c_void_p, C.c_void_p, i32, i32, C.c_int, u64, C.c_void_p, u64, C.c_void_p]),
     "tad_mask_rows": (C.c_int, [C.c_void_p, u64, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(u64), i32, C.c_void_p]),

@@ -554,6 +554,43 @@ int stream_arima_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const
   return TAD_OK;
 }
 
+// What the drop detector on a state leaves for its emit (state_drop_batch)
+struct DropBatch {
+  DropStateKeys keys{};
+  const uint8_t *flag = nullptr;
+  const uint32_t *cnt = nullptr;
+  const unsigned long long *row = nullptr;
+};
+
+// The drop detector over a state's series (tad.h: tad_drop_state / tad_drop_stream; kernels: tad_drop_state.hip): per-key mean / std over
+// the WHOLE series of v, the verdicts of the points hb names and their rows (the row total lands in the job's tail).  touched_only (a
+// stream batch: v is the candidate series, hb the batch's new points): only keys with new points are routed, read and judged.  Otherwise
+// (tad_drop_state: hb names every series point, poff = the series offsets) list / lcount are the routing launch_win_route left, and the
+// job's moments partials are merged from the per-key pairwise mean and m2.  Writes context workspace only, per key and per judged point.
+int state_drop_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const JobParams &jp, bool touched_only, unsigned long long coop_min,
+                     uint32_t *list, unsigned int *lcount, DevCounters *ctr, DropBatch *db) {
+  hipStream_t s = e->stream;
+  const uint64_t K = v.K, pc = hb.P_cap ? hb.P_cap : 1;
+  int rc;
+  if ((rc = ensure(e, e->ds_key, drop_state_key_bytes(K))) != TAD_OK) return rc;
+  // per judged point: row u64[pc + 1] | cnt u32 | flag u8
+  if ((rc = ensure(e, e->ds_pt, (pc + 1) * 8 + pc * 4 + pc + 64)) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K > pc ? K : pc) * sizeof(unsigned long long))) != TAD_OK) return rc;
+  const DropStateKeys dk = drop_state_keys(e->ds_key.p, K);
+  unsigned long long *row = static_cast<unsigned long long *>(e->ds_pt.p);
+  uint32_t *cnt = reinterpret_cast<uint32_t *>(row + pc + 1);
+  uint8_t *flag = reinterpret_cast<uint8_t *>(cnt + pc);
+  if (touched_only) launch_ds_route(s, K, v.soff, hb.poff, coop_min, list, lcount);
+  launch_ds_stats(s, K, v.soff, v.sval, touched_only ? hb.poff : nullptr, coop_min, list, lcount, jp.drop_min_samples, dk, ctr);
+  if (!touched_only) launch_moments(s, K, dk.n, dk.mean, dk.m2, dev_moments(e), ctr);   // (and n_keys / n_points)
+  if (hb.P_cap) {
+    launch_ds_verdict(s, hb.nk, hb.nv, hb.P_dev, hb.P_cap, dk, jp.drop_nsigma, jp.all_points, flag, cnt);
+    launch_scan(s, cnt, row, hb.P_cap, static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
+  }
+  db->keys = dk; db->flag = flag; db->cnt = cnt; db->row = row;
+  return TAD_OK;
+}
+
 // the start of a tad_run_state / tad_run_state_window job on the context the caller holds: progress, the first event, the job tail zeroed
 int run_view_begin(JobCtx *e, uint64_t K) {
   e->done.store(0);
@@ -568,8 +605,8 @@ int run_view_begin(JobCtx *e, uint64_t K) {
 
 // tad_run_state / tad_run_state_window after run_view_begin (tad.h; kernels: tad_window.hip).  Reads the view only: the state's CURRENT
 // copies, or a window's view in this context's workspace (wv_key / wv_pts, which nothing below resizes).  EWMA walks the CSR series;
-// DBSCAN and ARIMA run the stream's kernels with every series point named as new (poff = the series offsets).  view_syncs: the host
-// synchronisations the caller spent on building the view (tad_stats.host_syncs).
+// DBSCAN, ARIMA and DROP (tad_drop_state: its view carries no moments) run the stream's kernels with every series point named as new
+// (poff = the series offsets).  view_syncs: the host synchronisations the caller spent on building the view (tad_stats.host_syncs).
 int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem out_memory, tad_result **out, int view_syncs) {
   hipStream_t s = e->stream;
   JobParams jp;
@@ -578,8 +615,8 @@ int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem o
   jp.eps = job->dbscan_eps == 0.0 ? 250000000.0 : job->dbscan_eps;
   jp.min_samples = job->dbscan_min_samples == 0 ? 4 : job->dbscan_min_samples;
   jp.maxiter = job->arima_maxiter == 0 ? 50 : job->arima_maxiter;
-  jp.drop_nsigma = 3.0;
-  jp.drop_min_samples = 3;
+  jp.drop_nsigma = job->drop_nsigma == 0.0 ? 3.0 : job->drop_nsigma;
+  jp.drop_min_samples = job->drop_min_samples == 0 ? 3 : job->drop_min_samples;
   jp.all_points = (job->flags & TAD_FLAG_EMIT_ALL_POINTS) != 0;
   const uint64_t K = v.K;
   const uint64_t P = v.P;
@@ -592,6 +629,7 @@ int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem o
   uint64_t rows = 0;
   HistBatch hist;
   ArimaBatch ab;
+  DropBatch db;
   const bool ewma = jp.algo == TAD_ALGO_EWMA;
   unsigned long long coop_min = 0;
   uint32_t *list = nullptr;
@@ -606,7 +644,7 @@ int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem o
     unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
     coop_min = win_coop_min(K, P);
     launch_win_route(s, K, soff, stt, coop_min, list, lcount, tmin_dev);
-    launch_moments(s, K, view.n, view.avg, view.m2, dev_moments(e), ctr);   // (and n_keys / n_points)
+    if (jp.algo != TAD_ALGO_DROP) launch_moments(s, K, view.n, view.avg, view.m2, dev_moments(e), ctr);   // (and n_keys / n_points)
     if (ewma) {
       if (!jp.all_points) {
         launch_win_ewma(s, K, soff, sval, stt, view, jp.alpha, coop_min, list, lcount, false, false, static_cast<uint32_t *>(e->n_anom.p), nullptr, OutRows{});
@@ -628,6 +666,8 @@ int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem o
         launch_hist_verdict(s, nk, sval, hist.P_dev, P, v.hoff, v.hval, jp.eps, jp.min_samples, jp.all_points, noise, cnt);
         launch_scan(s, cnt, row, P, scratch, dev_total(e));
         hist.noise = noise; hist.cnt = cnt; hist.row = row;
+      } else if (jp.algo == TAD_ALGO_DROP) {
+        if ((rc = state_drop_batch(e, v, hist, jp, false, coop_min, list, lcount, ctr, &db)) != TAD_OK) return rc;
       } else if ((rc = stream_arima_batch(e, v, hist, jp, ctr, &ab)) != TAD_OK) {
         return rc;
       }
@@ -650,6 +690,8 @@ int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem o
                     e->plan.ewma_emit_rows);
   else if (rows && jp.algo == TAD_ALGO_DBSCAN)
     launch_hist_emit(s, hist.nk, hist.nt, hist.nv, hist.P_dev, hist.P_cap, hist.noise, hist.cnt, hist.row, view, jp.all_points, dev_rows);
+  else if (rows && jp.algo == TAD_ALGO_DROP)
+    launch_ds_emit(s, hist.nk, hist.nt, hist.nv, hist.P_dev, hist.P_cap, db.flag, db.cnt, db.row, db.keys, jp.all_points, dev_rows);
   else if (rows)
     launch_as_emit(s, ab.P, hist.nk, hist.nt, hist.nv, ab.tidx, ab.sigma, ab.pcalc, ab.pflag, ab.rows, ab.row_off, jp.all_points, dev_rows);
   {
@@ -753,7 +795,7 @@ int run_job(tad_engine *eng, const tad_job *job, const tad_columns *cols, tad_me
       return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: ARIMA needs a state with a series (tad_state_create_ex with TAD_STATE_SERIES)");
     if (job->algo != TAD_ALGO_EWMA && job->algo != TAD_ALGO_DBSCAN && job->algo != TAD_ALGO_ARIMA)
       return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: only the EWMA detector has a streaming form, DBSCAN on a state with history and "
-                                               "ARIMA on a state with a series (DROP has none)");
+                                               "ARIMA on a state with a series (DROP: tad_drop_stream)");
     // k_stream writes the candidate state for keys < cols->num_keys and the double buffer flips as a whole: a batch
     // that declares fewer keys than the state holds would drop the others' state
     if (cols->num_keys != stream->K) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_run_stream: batch declares %llu keys, the state holds %llu (they must be equal)",
@@ -942,7 +984,8 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
     uint64_t cells = empty ? 0 : K * L.nb;
     const bool cells_overflow = !empty && L.nb != 0 && cells / L.nb != K;
     // (ARIMA: predictions + 60 B per cell of workspace, arima_workspace_bytes; DROP: one double per cell)
-    uint64_t need = cells * 9 + (jp.algo == TAD_ALGO_ARIMA ? cells * 80 + (1ull << 22) : (jp.algo == TAD_ALGO_DROP ? cells * 8 : 0));
+    // (a tad_drop_stream batch judges the state's packed series, tad_drop_state.hip: no workspace per cell, the EWMA batch's rule)
+    uint64_t need = cells * 9 + (jp.algo == TAD_ALGO_ARIMA ? cells * 80 + (1ull << 22) : (jp.algo == TAD_ALGO_DROP && !stream ? cells * 8 : 0));
     // Sparse tables (few points per key on a fine lattice: second-resolution timestamps, per-connection keys): the dense
     // K x T grid would be mostly empty or not fit at all — sort the rows by (key, time) instead and lay each key's points
     // out by rank (tad_sparse.hip).  Chosen when the rows could fill at most 1/8 of a large grid, or the grid does not fit.
@@ -1189,6 +1232,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
     uint64_t rows = 0;
     HistBatch hist;
     ArimaBatch ab;
+    DropBatch db;
     ResultPriv *rp = nullptr;
     OutRows dev_rows{};
     ResultBlock dev_block;
@@ -1224,7 +1268,14 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
           (rc = stream_history_batch(e, stream, g, L, stream_poff, stream_P, (slots_all < cells ? slots_all : cells), jp, &hist)) != TAD_OK)
         return rc;
       if (jp.algo == TAD_ALGO_ARIMA && g.K && (rc = stream_arima_batch(e, series_view(stream, stream->cur ^ 1), hist, jp, ctr, &ab)) != TAD_OK) return rc;
-      if (jp.algo == TAD_ALGO_EWMA && !e->merge)   // (a DBSCAN / ARIMA batch counted its rows in stream_history_batch / stream_arima_batch)
+      if (jp.algo == TAD_ALGO_DROP && g.K) {   // tad_drop_stream: the touched keys' statistics over the candidate series, the new points' verdicts and rows
+        const StateView cv = series_view(stream, stream->cur ^ 1);
+        if ((rc = state_drop_batch(e, cv, hist, jp, true, win_coop_min(g.K, stream->ser.len[stream->cur] + hist.P_cap),
+                                   static_cast<uint32_t *>(e->hs_kcnt.p), reinterpret_cast<unsigned int *>(static_cast<uint32_t *>(e->hs_kcnt.p) + ((g.K + 3) & ~3ull)),
+                                   ctr, &db)) != TAD_OK)
+          return rc;
+      }
+      if (jp.algo == TAD_ALGO_EWMA && !e->merge)   // (a DBSCAN / ARIMA / DROP batch counted its rows in stream_history_batch / stream_arima_batch)
         launch_scan(s, static_cast<const uint32_t *>(e->n_anom.p), off, g.K, static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
       HIP_TRY(e, hipMemcpyAsync(e->tail_host, e->counters.p, kTailBytes, hipMemcpyDeviceToHost, s));
       HIP_TRY(e, hipStreamSynchronize(s));
@@ -1354,6 +1405,8 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
     else if (rows && stream && jp.algo == TAD_ALGO_DBSCAN)
       launch_hist_emit(s, hist.nk, hist.nt, hist.nv, hist.P_dev, hist.P_cap, hist.noise, hist.cnt, hist.row, state_view(stream, stream->cur ^ 1),
                        jp.all_points, dev_rows);
+    else if (rows && stream && jp.algo == TAD_ALGO_DROP)
+      launch_ds_emit(s, hist.nk, hist.nt, hist.nv, hist.P_dev, hist.P_cap, db.flag, db.cnt, db.row, db.keys, jp.all_points, dev_rows);
     else if (rows && stream && stream_poff)
       launch_stream_points(s, static_cast<const unsigned long long *>(e->sp_comp_a.p), static_cast<const unsigned long long *>(e->sp_val_a.p), stream_poff,
                            g.K, L.t0, jp.alpha, jp.all_points, true, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),
@@ -1689,7 +1742,7 @@ static int check_state_job(tad_engine *eng, const tad_state *st, const tad_job *
   if (!st || !job || !out) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: state, job and out must not be NULL", who);
   *out = nullptr;
   if (job->algo != TAD_ALGO_EWMA && job->algo != TAD_ALGO_DBSCAN && job->algo != TAD_ALGO_ARIMA)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the algorithm must be EWMA, DBSCAN or ARIMA (DROP has no streaming form)", who);
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the algorithm must be EWMA, DBSCAN or ARIMA (DROP: tad_drop_state)", who);
   if (job->start_time != 0 || job->end_time != 0)
     return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: start_time / end_time must be 0: %s", who, narrow);
   if (job->flags & (TAD_FLAG_KEY_U32 | TAD_FLAG_TIME_U32))
@@ -1716,8 +1769,100 @@ int tad_run_state(tad_engine *eng, tad_state *st, const tad_job *job, tad_mem ou
 
 int tad_window_history_by_sort(uint64_t window_points, uint64_t state_points) { return win_hist_by_sort(window_points, state_points) ? 1 : 0; }
 
-// tad.h: the view of the window in the context's workspace (kernels: tad_window.hip), then tad_run_state's path on it.  Reads the state's
-// CURRENT copies and writes workspace only.  wv_key and wv_pts hold the view; run_view_locked resizes neither.
+// The view of a window of the state in the context's workspace (kernels: tad_window.hip), after run_view_begin, in two steps that
+// tad_run_state_window and tad_drop_state share: window_bounds (every key's bounds, the view's offsets, the window's point total — one
+// host round trip) and window_gather (the view itself, which run_view_locked then judges).  Both read the state's CURRENT copies and
+// write workspace only: wv_key and wv_pts hold the view; run_view_locked resizes neither.
+struct WinKeys {   // wv_key: per key wbeg | wlen | ecnt | chunks (later the long-sort list) u32 each | the list's length | woff | coff | eoff u64[K + 1] each | moments
+  uint32_t *wbeg, *wlen, *ecnt, *chunks;
+  unsigned int *long_count;
+  unsigned long long *woff, *coff, *eoff;
+  StreamState wmom;
+};
+
+static size_t win_key_bytes(uint64_t K) {
+  const size_t kpad = (size_t)((K + 3) & ~3ull);
+  return kpad * 16 + 64 + (kpad + 4) * 24;
+}
+
+static WinKeys win_keys(JobCtx *e, uint64_t K) {
+  const size_t kpad = (size_t)((K + 3) & ~3ull);
+  WinKeys w;
+  w.wbeg = static_cast<uint32_t *>(e->wv_key.p); w.wlen = w.wbeg + kpad; w.ecnt = w.wlen + kpad; w.chunks = w.ecnt + kpad;
+  w.long_count = reinterpret_cast<unsigned int *>(w.chunks + kpad);
+  w.woff = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(w.long_count) + 64);
+  w.coff = w.woff + kpad + 4; w.eoff = w.coff + kpad + 4;
+  w.wmom = stream_view(static_cast<unsigned char *>(e->wv_key.p) + win_key_bytes(K), K);
+  return w;
+}
+
+// 1. every key's bounds; the view's offsets and the chunk offsets; *P = the window's point total
+static int window_bounds(JobCtx *e, const tad_state *st, int64_t from_t, int64_t to_t, uint64_t keep_points, uint64_t *P) {
+  hipStream_t s = e->stream;
+  const uint64_t K = st->K;
+  const StateView whole = series_view(st, st->cur);
+  int rc;
+  if ((rc = ensure(e, e->wv_key, win_key_bytes(K) + state_bytes(K))) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K) * sizeof(unsigned long long))) != TAD_OK) return rc;
+  const WinKeys w = win_keys(e, K);
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  launch_win_bounds(s, K, whole.soff, whole.st, (long long)from_t, (long long)to_t, keep_points, w.wbeg, w.wlen, w.ecnt, w.chunks);
+  launch_scan(s, w.wlen, w.woff, K, scratch);
+  launch_scan(s, w.chunks, w.coff, K, scratch);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipMemcpyAsync(e->tail_host + kTailTotal, w.woff + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  *P = *e->total_host;
+  return TAD_OK;
+}
+
+// 2. the window's values and times (DBSCAN on the subtract side: the excluded values too); 3. the moments — not for TAD_ALGO_DROP, which
+// reads none; 4. DBSCAN's history, by sorting the window's values or (subtract) by removing the sorted excluded values from the state's
+static int window_gather(JobCtx *e, const tad_state *st, const tad_job *job, uint64_t P, bool subtract, StateView *v) {
+  hipStream_t s = e->stream;
+  const uint64_t K = st->K;
+  const StateView whole = series_view(st, st->cur);
+  const uint64_t S = whole.P;
+  const WinKeys w = win_keys(e, K);
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  int rc;
+  *v = StateView{};
+  v->K = K;
+  v->P = P;
+  if (P != 0) {
+    const bool dbscan = job->algo == TAD_ALGO_DBSCAN;
+    if ((rc = ensure(e, e->wv_pts, P * (dbscan ? 24 : 16))) != TAD_OK) return rc;
+    unsigned long long *wval = static_cast<unsigned long long *>(e->wv_pts.p);
+    long long *wt = reinterpret_cast<long long *>(wval + P);
+    unsigned long long *wh = wval + 2 * P, *ev = nullptr, *es = nullptr;
+    if (subtract) {
+      if ((rc = ensure(e, e->hs_val, (S - P) * 8)) != TAD_OK) return rc;
+      if ((rc = ensure(e, e->hs_sorted, (S - P) * 8)) != TAD_OK) return rc;
+      ev = static_cast<unsigned long long *>(e->hs_val.p);
+      es = static_cast<unsigned long long *>(e->hs_sorted.p);
+      launch_scan(s, w.ecnt, w.eoff, K, scratch);
+    }
+    const uint64_t bound = trim_chunks_bound(K, S);
+    launch_win_gather(s, bound, w.coff, K, whole.soff, whole.sval, whole.st, w.wbeg, w.woff, wval, wt, w.eoff, ev);
+    if (job->algo != TAD_ALGO_DROP) {
+      const double alpha = job->ewma_alpha == 0.0 ? 0.5 : job->ewma_alpha;   // (for the view's ewma only, which no detector reads)
+      launch_trim_moments(s, K, w.wlen, w.ecnt, w.woff, wval, alpha, whole.mom, w.wmom);
+    }
+    if (subtract) {
+      launch_hist_sort(s, ev, w.eoff, K, es, w.chunks, w.long_count);
+      launch_hist_subtract(s, bound, w.coff, K, whole.hoff, whole.hval, w.eoff, es, w.woff, wh, true);
+    } else if (dbscan) {
+      launch_hist_sort(s, wval, w.woff, K, wh, w.chunks, w.long_count);
+    }
+    HIP_TRY(e, hipGetLastError());
+    v->soff = w.woff; v->sval = wval; v->st = wt; v->mom = w.wmom;
+    if (dbscan) { v->hoff = w.woff; v->hval = wh; }
+  }
+  e->done.store(1);
+  return TAD_OK;
+}
+
+// tad.h: the window's view (window_bounds, window_gather), then tad_run_state's path on it.
 int tad_run_state_window(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, tad_mem out_memory,
                          tad_result **out) {
   int rc = check_state_job(eng, st, job, out, "tad_run_state_window", "the window is from_t / to_t / keep_points");
@@ -1729,66 +1874,85 @@ int tad_run_state_window(tad_engine *eng, tad_state *st, const tad_job *job, int
     return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state_window: the series was imported without its times (tad_state_import_times)");
   if ((rc = call.enter("tad_run_state_window", job->id, job->algo == TAD_ALGO_ARIMA)) != TAD_OK) return rc;
   JobCtx *e = call.e;
-  const uint64_t K = st->K;
-  if ((rc = run_view_begin(e, K)) != TAD_OK) return rc;
+  if ((rc = run_view_begin(e, st->K)) != TAD_OK) return rc;
   const StateView whole = series_view(st, st->cur);
   const uint64_t S = whole.P;
   if (S == 0 || (from_t == 0 && to_t == 0 && keep_points == 0)) return run_view_locked(e, whole, job, out_memory, out, 0);
-  hipStream_t s = e->stream;
-  // per key: wbeg | wlen | ecnt | chunks (later the long-sort list) u32 each | the list's length | woff | coff | eoff u64[K + 1] each | moments
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
-  const size_t key_bytes = kpad * 16 + 64 + (kpad + 4) * 24;
-  if ((rc = ensure(e, e->wv_key, key_bytes + state_bytes(K))) != TAD_OK) return rc;
-  if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K) * sizeof(unsigned long long))) != TAD_OK) return rc;
-  uint32_t *wbeg = static_cast<uint32_t *>(e->wv_key.p), *wlen = wbeg + kpad, *ecnt = wlen + kpad, *chunks = ecnt + kpad;
-  unsigned int *long_count = reinterpret_cast<unsigned int *>(chunks + kpad);
-  unsigned long long *woff = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(long_count) + 64);
-  unsigned long long *coff = woff + kpad + 4, *eoff = coff + kpad + 4;
-  const StreamState wmom = stream_view(static_cast<unsigned char *>(e->wv_key.p) + key_bytes, K);
-  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
-  // 1. every key's bounds; the view's offsets and the chunk offsets; the window's point total
-  launch_win_bounds(s, K, whole.soff, whole.st, (long long)from_t, (long long)to_t, keep_points, wbeg, wlen, ecnt, chunks);
-  launch_scan(s, wlen, woff, K, scratch);
-  launch_scan(s, chunks, coff, K, scratch);
-  HIP_TRY(e, hipGetLastError());
-  HIP_TRY(e, hipMemcpyAsync(e->tail_host + kTailTotal, woff + K, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipStreamSynchronize(s));
-  const uint64_t P = *e->total_host;
+  uint64_t P = 0;
+  if ((rc = window_bounds(e, st, from_t, to_t, keep_points, &P)) != TAD_OK) return rc;
+  if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1);   // every key is whole: the state's own arrays, no view
+  const bool subtract = job->algo == TAD_ALGO_DBSCAN && P != 0 && !win_hist_by_sort(P, S);
+  StateView v;
+  if ((rc = window_gather(e, st, job, P, subtract, &v)) != TAD_OK) return rc;
+  return run_view_locked(e, v, job, out_memory, out, 1);
+}
+
+// tad.h: the drop detector's batch verdicts over a window of the state — tad_run_state_window's window and view (window_bounds, window_gather:
+// values and times only), then run_view_locked's DROP path (state_drop_batch).  Read-only.
+int tad_drop_state(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, tad_mem out_memory,
+                   tad_result **out) {
+  const char *who = "tad_drop_state";
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!st || !job || !out) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: state, job and out must not be NULL", who);
+  *out = nullptr;
+  if (job->algo != TAD_ALGO_DROP)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the algorithm must be DROP (tad_run_state_window judges EWMA, DBSCAN and ARIMA)", who);
+  if (job->start_time != 0 || job->end_time != 0)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: start_time / end_time must be 0: the window is from_t / to_t / keep_points", who);
+  if (job->flags & (TAD_FLAG_KEY_U32 | TAD_FLAG_TIME_U32))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 describe input columns; there are none", who);
+  if (!(job->drop_nsigma >= 0.0) || job->drop_min_samples < 0)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: detector parameter out of range", who);
+  if (!st->series || !st->times)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES)", who);
+  if (from_t != 0 && to_t != 0 && from_t > to_t) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: from_t is later than to_t", who);
+  StateCall call(eng, st);
+  if (st->times_stale)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the series was imported without its times (tad_state_import_times)", who);
+  int rc;
+  if ((rc = call.enter(who, job->id)) != TAD_OK) return rc;
+  JobCtx *e = call.e;
+  if ((rc = run_view_begin(e, st->K)) != TAD_OK) return rc;
+  const StateView whole = series_view(st, st->cur);
+  const uint64_t S = whole.P;
+  if (S == 0 || (from_t == 0 && to_t == 0 && keep_points == 0)) return run_view_locked(e, whole, job, out_memory, out, 0);
+  uint64_t P = 0;
+  if ((rc = window_bounds(e, st, from_t, to_t, keep_points, &P)) != TAD_OK) return rc;
   if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1);   // every key is whole: the state's own arrays, no view
   StateView v;
-  v.K = K;
-  v.P = P;
-  if (P != 0) {
-    // 2. the window's values and times (DBSCAN on the subtract side: the excluded values too); 3. the moments; 4. DBSCAN's history
-    const bool dbscan = job->algo == TAD_ALGO_DBSCAN;
-    const bool subtract = dbscan && !win_hist_by_sort(P, S);
-    if ((rc = ensure(e, e->wv_pts, P * (dbscan ? 24 : 16))) != TAD_OK) return rc;
-    unsigned long long *wval = static_cast<unsigned long long *>(e->wv_pts.p);
-    long long *wt = reinterpret_cast<long long *>(wval + P);
-    unsigned long long *wh = wval + 2 * P, *ev = nullptr, *es = nullptr;
-    if (subtract) {
-      if ((rc = ensure(e, e->hs_val, (S - P) * 8)) != TAD_OK) return rc;
-      if ((rc = ensure(e, e->hs_sorted, (S - P) * 8)) != TAD_OK) return rc;
-      ev = static_cast<unsigned long long *>(e->hs_val.p);
-      es = static_cast<unsigned long long *>(e->hs_sorted.p);
-      launch_scan(s, ecnt, eoff, K, scratch);
-    }
-    const uint64_t bound = trim_chunks_bound(K, S);
-    launch_win_gather(s, bound, coff, K, whole.soff, whole.sval, whole.st, wbeg, woff, wval, wt, eoff, ev);
-    const double alpha = job->ewma_alpha == 0.0 ? 0.5 : job->ewma_alpha;   // (for the view's ewma only, which no detector reads)
-    launch_trim_moments(s, K, wlen, ecnt, woff, wval, alpha, whole.mom, wmom);
-    if (subtract) {
-      launch_hist_sort(s, ev, eoff, K, es, chunks, long_count);
-      launch_hist_subtract(s, bound, coff, K, whole.hoff, whole.hval, eoff, es, woff, wh, true);
-    } else if (dbscan) {
-      launch_hist_sort(s, wval, woff, K, wh, chunks, long_count);
-    }
-    HIP_TRY(e, hipGetLastError());
-    v.soff = woff; v.sval = wval; v.st = wt; v.mom = wmom;
-    if (dbscan) { v.hoff = woff; v.hval = wh; }
-  }
-  e->done.store(1);
+  if ((rc = window_gather(e, st, job, P, false, &v)) != TAD_OK) return rc;   // values and times only: DROP reads no moments, no history
   return run_view_locked(e, v, job, out_memory, out, 1);
+}
+
+// tad.h: the periodical drop job, one batch.  The batch runs as a stream batch of the EWMA kind does (run_job_locked: Stage 0, the count
+// pass into the candidate state, stream_history_batch), then state_drop_batch judges the new points; tad_run_stream itself keeps
+// refusing TAD_ALGO_DROP.
+int tad_drop_stream(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, tad_mem out_memory, tad_result **out) {
+  const char *who = "tad_drop_stream";
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!st || !job || !cols || !out) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: state, job, cols and out must not be NULL", who);
+  *out = nullptr;
+  if (job->algo != TAD_ALGO_DROP)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the algorithm must be DROP (tad_run_stream streams EWMA, DBSCAN and ARIMA)", who);
+  if (!st->series)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the state must keep its series (tad_state_create_ex with TAD_STATE_SERIES); state unchanged", who);
+  if (cols->num_keys != st->K)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: batch declares %llu keys, the state holds %llu (they must be equal)", who,
+                (unsigned long long)cols->num_keys, (unsigned long long)st->K);
+  {
+    const int vrc = validate_job_columns(eng, job, cols, who);
+    if (vrc != TAD_OK) return vrc;
+  }
+  if (!(job->ewma_alpha >= 0.0 && job->ewma_alpha <= 1.0) || !(job->drop_nsigma >= 0.0) || job->drop_min_samples < 0)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: detector parameter out of range", who);
+  StateCall call(eng, st);
+  if (st->times_stale)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the series was imported without its times (tad_state_import_times); state unchanged", who);
+  int rc = call.enter(who, job->id);
+  if (rc != TAD_OK) return rc;
+  PauseHold hold(eng);     // (declared after the call's context: dropped before the context goes back to the pool)
+  call.e->hold = &hold;
+  return run_job_locked(call.e, job, cols, out_memory, out, nullptr, st, 0);
 }
 
 // tad.h: a batch placed by time.  The batch runs as a stream batch does up to the end of Stage 0 (run_job_locked with the context's merge

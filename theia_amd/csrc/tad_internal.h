@@ -540,6 +540,30 @@ void launch_as_emit(hipStream_t s, uint64_t P, const unsigned long long *nk, con
 void launch_drop(hipStream_t s, Grid g, double n_sigma, int min_samples, double *ws, double *sigma, uint32_t *n_pts,
                  double *key_mean, double *key_m2, DevCounters *ctr);
 
+// ---- the drop detector on a state's series (tad_drop_state.hip): tad_drop_state / tad_drop_stream ----
+struct DropStateKeys {   // per key, in one block of drop_state_key_bytes(K)
+  double *mean, *std, *m2;   // pairwise mean, pandas' sample std, the pairwise sum of (mean - x)^2
+  uint32_t *n;               // the key's points
+  uint8_t *ok;               // 1: the key has a result (n >= min_samples && n >= 2)
+};
+size_t drop_state_key_bytes(uint64_t K);
+DropStateKeys drop_state_keys(void *mem, uint64_t K);
+// list / *count = the keys with new points (poff[k + 1] > poff[k]) and >= coop_min series points (list: K entries)
+void launch_ds_route(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *poff, unsigned long long coop_min, uint32_t *list,
+                     unsigned int *count);
+// mean / std / m2 / n / ok of every key (poff == NULL) or of the keys with new points, over the key's WHOLE series soff / sval in numpy's
+// pairwise order: a lane per key shorter than coop_min, a wavefront per listed key.  ctr->keys_no_result += the judged keys with points
+// and no result
+void launch_ds_stats(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *sval, const unsigned long long *poff,
+                     unsigned long long coop_min, const uint32_t *list, const unsigned int *count, int min_samples, DropStateKeys d, DevCounters *ctr);
+// per judged point i < *P_dev (key nk[i], value nv[i]): flag[i] = x > mean + n_sigma std || x < mean - n_sigma std, cnt[i] = its rows
+// (0 for a key without a result and for i in [*P_dev, P_cap))
+void launch_ds_verdict(hipStream_t s, const unsigned long long *nk, const unsigned long long *nv, const unsigned long long *P_dev, uint64_t P_cap,
+                       DropStateKeys d, double n_sigma, bool all_points, uint8_t *flag, uint32_t *cnt);
+// the rows of the points with cnt[i] != 0 at row[i]: algo_calc = the key's mean, stddev = its std
+void launch_ds_emit(hipStream_t s, const unsigned long long *nk, const long long *nt, const unsigned long long *nv, const unsigned long long *P_dev,
+                    uint64_t P_cap, const uint8_t *flag, const uint32_t *cnt, const unsigned long long *row, DropStateKeys d, bool all_points, OutRows out);
+
 // ARIMA(1,1,1) walk-forward on Box-Cox data: calc[T][K] + FLAG_ANOMALY.
 // pause (NULL = never yield): a word in device memory; while it is non-zero the wavefronts of k_arima_fit SUSPEND their fits at the end
 // of the running optimiser cycle (state saved per wavefront in the workspace) and retire — other jobs' whole-CU workgroups cannot be placed
@@ -741,6 +765,7 @@ const void *code_anchor_arima();
 const void *code_anchor_compact();
 const void *code_anchor_dbscan();
 const void *code_anchor_drop();
+const void *code_anchor_drop_state();
 const void *code_anchor_factorize();
 const void *code_anchor_history();
 const void *code_anchor_ingest();

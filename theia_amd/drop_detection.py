@@ -4,6 +4,8 @@ Reference: /root/reference/snowflake/udfs/udfs/drop_detection/drop_detection_udf
 partitioned by (endpoint, direction): `process` collects (date, drop_number) pairs (ref:25-40), `end_partition` yields one
 row per anomalous day (ref:42-56).  Same class and method names here; `end_partition` calls tad_series_drop through the C
 ABI, `drop_detection_table` runs every partition of an aggregated table in ONE tad_run (algo DROP).  No CPU fallback.
+`PeriodicalDropDetection` is the "periodical" job the reference names and does not have (snowflake/cmd/dropDetection.go:282): the
+partitions' daily counts live in a streaming state on the device, a feed judges the new days against everything kept.
 Only the UDTF's call protocol is mirrored (a thin adaptor); the reference's Result helper class is not reproduced.
 """
 import datetime
@@ -73,3 +75,75 @@ def drop_detection_table(endpoint, direction, date, drop_number, detection_id=No
         dd = str(np.datetime64(int(t), "D")) if d.dtype.kind in "USO" else int(t)
         rows.append((job_type, detection_id or str(uuid.uuid4()), now, ep, di, mean, std, dd, int(x)))   # (ref:8-11: id per row)
     return rows
+
+
+def _days(date):
+    """dates (YYYY-MM-DD strings, datetime64 or day numbers) -> (int64 day numbers, whether they were dates)"""
+    import pandas as pd
+    d = np.asarray(date)
+    if d.dtype.kind in "USOM":
+        return np.asarray(pd.to_datetime(d).values.astype("datetime64[D]").astype(np.int64)), True
+    return d.astype(np.int64), False
+
+
+class PeriodicalDropDetection:
+    """The periodical drop job: `feed` adds a batch of (endpoint, direction, date, drop_number) rows — the new days — and returns the
+    anomalous ones among them, judged against every day fed so far (mean and std over the partition's whole series, as an "initial"
+    job over the concatenation would compute them); `window` returns the verdicts of a range of days of what is kept.  Owns a series +
+    times state on the engine (TadEngine.drop_stream / drop_state) and the (endpoint, direction) -> key id table, ids in order of first
+    appearance; the state is resized as partitions appear.  A partition's days must arrive in order: a feed with a day that is not
+    newer than the partition's newest fails as a whole and changes nothing.  Nothing is computed on the host."""
+
+    def __init__(self, engine=None):
+        self._engine = engine or _ad.get_engine()
+        self._ids = {}                    # (endpoint, direction) -> key id
+        self._keys = []                   # key id -> (endpoint, direction)
+        self._state = None
+        self._dates = False               # the feeds carried dates (rows report dates) or day numbers
+
+    @property
+    def state(self):
+        return self._state
+
+    def _key_ids(self, endpoint, direction):
+        out = np.empty(len(endpoint), dtype=np.uint64)
+        for i, key in enumerate(zip(endpoint.tolist(), direction.tolist())):
+            k = self._ids.get(key)
+            if k is None:
+                k = self._ids[key] = len(self._keys)
+                self._keys.append(key)
+            out[i] = k
+        return out
+
+    def _rows(self, res, job_type, detection_id):
+        now = datetime.datetime.now()
+        host = res.to_host()
+        rows = []
+        for k, t, x, mean, std in zip(host["key_id"].tolist(), host["flow_end_s"].tolist(), host["throughput"].tolist(),
+                                      host["algo_calc"].tolist(), host["stddev"].tolist()):
+            ep, di = self._keys[int(k)]
+            dd = str(np.datetime64(int(t), "D")) if self._dates else int(t)
+            rows.append((job_type, detection_id or str(uuid.uuid4()), now, ep, di, mean, std, dd, int(x)))
+        return rows
+
+    def feed(self, endpoint, direction, date, drop_number, detection_id=None):
+        """One batch -> its anomalous days as RESULT_COLUMNS tuples with job_type "periodical", in (partition, date) order."""
+        endpoint, direction = np.asarray(endpoint).astype(str), np.asarray(direction).astype(str)
+        day, self._dates = _days(date)
+        key = self._key_ids(endpoint, direction)
+        n_keys = max(len(self._keys), 1)
+        if self._state is None:
+            self._state = self._engine.state_create(n_keys, series=True, times=True)
+        elif n_keys > self._state.num_keys:
+            self._state.resize(n_keys)
+        res = self._engine.drop_stream(self._state, key, day, np.asarray(drop_number, dtype=np.uint64), agg_flow="svc", value_op="sum")
+        return self._rows(res, "periodical", detection_id)
+
+    def window(self, from_date=None, to_date=None, detection_id=None):
+        """The anomalous days with from_date <= date < to_date (None = no bound) of everything kept, each partition judged over its days
+        inside the range: the rows of an "initial" job over those days."""
+        if self._state is None:
+            return []
+        bound = lambda d: 0 if d is None else int(_days([d])[0][0])
+        res = self._engine.drop_state(self._state, bound(from_date), bound(to_date))
+        return self._rows(res, "periodical", detection_id)

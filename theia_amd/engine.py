@@ -835,6 +835,43 @@ class TadEngine:
         self._check(rc)
         return TadResult(self, res)
 
+    # ---- the drop detector on a state (tad_drop_state / tad_drop_stream) ----
+    def _need_state_drop(self, what):
+        if not (getattr(self._lib, "tad_features", None) and self._lib.tad_features() & capi.TAD_FEATURE_STATE_DROP):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no %s (TAD_FEATURE_STATE_DROP)" % what)
+
+    def drop_state(self, state, from_t=0, to_t=0, keep_points=0, nsigma=0.0, min_samples=0, emit_all=False, out="host", job_id=""):
+        """The drop detector's batch verdicts over a window of what `state` holds, read-only (tad_drop_state): exactly the rows
+        run("DROP") returns for the table of the window's series points with the same nsigma / min_samples (0 = the defaults 3 and 3).
+        The window is run_state_window's; all zero is the whole state.  Needs a state with series=True and times=True."""
+        self._need_state_drop("tad_drop_state")
+        job = capi.Job(algo=capi.TAD_ALGO["DROP"], drop_nsigma=float(nsigma), drop_min_samples=int(min_samples),
+                       flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
+        res = C.POINTER(capi.Result)()
+        rc = self._lib.tad_drop_state(self._h, state._h, C.byref(job), int(from_t), int(to_t), int(keep_points),
+                                      capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
+        self._check(rc)
+        return TadResult(self, res)
+
+    def drop_stream(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, nsigma=0.0, min_samples=0, alpha=0.0,
+                    emit_all=False, out="host", job_id="", num_keys=None, key_id2=None):
+        """One batch of the periodical drop job on `state` (tad_drop_stream): the state advances exactly as under run_stream with EWMA;
+        the rows are those run("DROP") over everything the state now holds emits for this batch's points.  Needs a state with
+        series=True (times and history are kept up when present)."""
+        self._need_state_drop("tad_drop_stream")
+        if agg_flow not in capi.TAD_AGG:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "agg_flow must be '', pod, svc or external")
+        cols, narrow, keep = self._stream_columns(state, key_id, flow_end_s, value, key_id2, num_keys, lattice)
+        job = capi.Job(algo=capi.TAD_ALGO["DROP"], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
+                       drop_nsigma=float(nsigma), drop_min_samples=int(min_samples),
+                       flags=(capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0) | narrow, id=job_id.encode()[:63])
+        res = C.POINTER(capi.Result)()
+        rc = self._lib.tad_drop_stream(self._h, state._h, C.byref(job), C.byref(cols),
+                                       capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
+        del keep
+        self._check(rc)
+        return TadResult(self, res)
+
     # ---- row-sharded ingest: bucket device rows by owner = key mod world (tad_shard_rows) ----
     def shard_rows(self, key_id, flow_end_s, value, world):
         """Device columns (torch CUDA tensors or DeviceArray) -> ((key_local, flow_end_s, value) DeviceArrays grouped by

@@ -598,6 +598,78 @@ func (e *Engine) MaskRows(n uint64, codes, masks []unsafe.Pointer, maskLen []uin
 	return nil
 }
 
+var dropRowsOnce sync.Once
+var dropRowsOK bool
+
+// hasDropRows: the library knows tad_drop_select (tad_features); an older one would not export the call.
+func hasDropRows() bool {
+	dropRowsOnce.Do(func() { dropRowsOK = C.tad_features()&C.TAD_FEATURE_DROP_ROWS != 0 })
+	return dropRowsOK
+}
+
+// DropFlowColumns are the flow-table columns of the drop job's query, all DEVICE pointers to N elements (AllocDevice, the ingest
+// calls): UInt8 rule actions and keep, int64 epoch seconds (uint32 with TimeU32), int64 dictionary codes.  FlowEnd and Keep may be nil.
+type DropFlowColumns struct {
+	N                                                   uint64
+	IngressAction, EgressAction                         unsafe.Pointer
+	FlowStart, FlowEnd                                  unsafe.Pointer
+	SrcIP, SrcPodNs, SrcPodName, DstIP, DstPodNs, DstPodName unsafe.Pointer
+	SrcPodNull, DstPodNull                              int64 // the pod-name code that means "no pod" on that side; -1 = none
+	Keep                                                unsafe.Pointer
+	TimeU32                                             bool
+}
+
+// DropRows is DropSelect's result: seven DEVICE columns of N rows, one per selected flow row in input order.  The first four are the key
+// tuple for Factorize-style calls on device columns; DayS and Count go to the job with the key ids.  The library owns the memory: Close.
+type DropRows struct {
+	e                                                *Engine
+	h                                                *C.tad_drop_rows
+	N                                                uint64
+	EndpointKind, EndpointNs, EndpointName, Direction unsafe.Pointer
+	DayS, Count, Row                                 unsafe.Pointer
+}
+
+func (r *DropRows) Close() {
+	if r.h != nil {
+		C.tad_drop_rows_free(r.e.h, r.h)
+		r.h = nil
+	}
+}
+
+// DropSelect is the flow-row query of the drop job on the device (tad_drop_select; snowflake/cmd/dropDetection.go:36-190 up to the
+// sums): the rows whose ingress or egress rule action is 2 or 3 and that pass startTime <= flowStart, flowEnd < endTime (0 = no bound)
+// and Keep, each as (endpoint kind, namespace code, name or IP code, direction, day, count 1, input row).
+func (e *Engine) DropSelect(cols DropFlowColumns, startTime, endTime int64) (*DropRows, error) {
+	if !hasDropRows() {
+		return nil, errors.New("tadengine: libtad_mi355x.so has no tad_drop_select (TAD_FEATURE_DROP_ROWS)")
+	}
+	var fc C.tad_drop_flow_columns
+	fc.n_rows = C.uint64_t(cols.N)
+	fc.ingress_action = (*C.uint8_t)(cols.IngressAction)
+	fc.egress_action = (*C.uint8_t)(cols.EgressAction)
+	fc.flow_start_s = (*C.int64_t)(cols.FlowStart)
+	fc.flow_end_s = (*C.int64_t)(cols.FlowEnd)
+	fc.src_ip, fc.src_pod_ns, fc.src_pod_name = (*C.int64_t)(cols.SrcIP), (*C.int64_t)(cols.SrcPodNs), (*C.int64_t)(cols.SrcPodName)
+	fc.dst_ip, fc.dst_pod_ns, fc.dst_pod_name = (*C.int64_t)(cols.DstIP), (*C.int64_t)(cols.DstPodNs), (*C.int64_t)(cols.DstPodName)
+	fc.src_pod_null, fc.dst_pod_null = C.int64_t(cols.SrcPodNull), C.int64_t(cols.DstPodNull)
+	fc.keep = (*C.uint8_t)(cols.Keep)
+	if cols.TimeU32 {
+		fc.flags = C.TAD_FLAG_TIME_U32
+	}
+	fc.memory = C.TAD_MEM_DEVICE
+	var dr *C.tad_drop_rows
+	if rc := C.tad_drop_select(e.h, &fc, C.int64_t(startTime), C.int64_t(endTime), C.TAD_MEM_DEVICE, &dr); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, IllegalArgument{msg}
+		}
+		return nil, fmt.Errorf("tad_drop_select: %s (code %d)", msg, int(rc))
+	}
+	return &DropRows{e: e, h: dr, N: uint64(dr.n_rows), EndpointKind: unsafe.Pointer(dr.endpoint_kind), EndpointNs: unsafe.Pointer(dr.endpoint_ns),
+		EndpointName: unsafe.Pointer(dr.endpoint_name), Direction: unsafe.Pointer(dr.direction), DayS: unsafe.Pointer(dr.day_s),
+		Count: unsafe.Pointer(dr.count), Row: unsafe.Pointer(dr.row)}, nil
+}
+
 func (e *Engine) AllocDevice(bytes uint64) (unsafe.Pointer, error) {
 	var p unsafe.Pointer
 	if rc := C.tad_device_alloc(e.h, C.uint64_t(bytes), &p); rc != C.TAD_OK {

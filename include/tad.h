@@ -805,6 +805,79 @@ int tad_drop_state(tad_engine *e, tad_state *s, const tad_job *job, int64_t from
                    tad_mem out_memory, tad_result **out);
 int tad_drop_stream(tad_engine *e, tad_state *s, const tad_job *job, const tad_columns *cols, tad_mem out_memory, tad_result **out);
 
+/* ---- the drop job's flow-row query (TAD_FEATURE_DROP_ROWS; check tad_features() before calling these) ----
+ * The three forms of the drop detector start from per-endpoint daily drop counts.  The reference gets those from the query that
+ * snowflake/cmd/dropDetection.go:36-190 builds over the flow table: it filters on the two network-policy rule actions (:65-72, the time bounds :85-105), picks
+ * endpoint and direction per row (the CASE at :131-148), takes to_date(flowStartSeconds) and count(*) per nine-column group (:59-62, :119-128), then SUM per
+ * (endpoint, direction, date) (:155-165).  tad_drop_select is that query up to the sums, on columns held in HBM (fetch_flows_device,
+ * tad_encode_strings, tad_widen_column, tad_mask_rows): it selects the dropped rows, chooses a side per row, buckets by day and hands over
+ * compact columns; tad_factorize / tad_keydict_encode over the four tuple columns and Stage 0 (tad_run / tad_drop_stream with TAD_OP_SUM
+ * over key id, day_s, count) do the rest.
+ * Row rule.  Row i is selected iff (ia in {2,3} || ea in {2,3}) && (start_time == 0 || flow_start_s >= start_time) &&
+ * (end_time == 0 || flow_end_s < end_time) && (keep == NULL || keep[i] != 0); ia / ea are ingress_action / egress_action, the
+ * ingressNetworkPolicyRuleAction / egressNetworkPolicyRuleAction UInt8 columns (create_table.sh:63,68; 2 = Drop, 3 = Reject).  The row
+ * is on the INGRESS side iff ia in {2,3} — ingress wins when both actions drop, as the CASE has it — else on the egress side.  Ingress
+ * rows describe the destination, egress rows the source.  On the chosen side the endpoint is a pod when pod_name != <side>_pod_null and
+ * an IP otherwise.  Output, one row per selected row, in INPUT ORDER (so the ids tad_factorize and tad_keydict_encode then hand out are
+ * the ids a host path over the same rows gives):
+ *   pod endpoint: endpoint_kind = 1, endpoint_ns = pod_ns, endpoint_name = pod_name;   IP endpoint: endpoint_kind = 0, endpoint_ns = 0,
+ *   endpoint_name = ip;   direction: 0 ingress, 1 egress;   day_s = floor(flow_start_s / 86400) * 86400 (floor, not truncation: -1 is day
+ *   -86400);   count = 1;   row = i.
+ * Comparing the (kind, ns, name) tuples equals comparing the reference's endpoint strings — CONCAT(ns, '/', name) for a pod, the IP string
+ * otherwise — as long as no namespace or pod name contains '/', which Kubernetes forbids (both are DNS labels / subdomains), and an IP string
+ * contains none either: the kind column keeps a pod from colliding with an IP whose code happens to be equal.  Summing count by
+ * (tuple, day_s) equals the query's two GROUP BYs composed: the first groups by (endpoint, direction, date) AND further columns, so its
+ * extra columns only split groups that the second, which sums the first's counts by (endpoint, direction, date) alone, merges again —
+ * the sum of the parts' count(*) is the count(*) of the whole.
+ * Columns.  All of one memory space (cols->memory); the code columns are int64 dictionary codes of any one dictionary per column pair
+ * (src_ip / dst_ip share one, as do the namespaces and the pod names, if the tuples are to compare across sides).  flags: 0 or
+ * TAD_FLAG_TIME_U32 — flow_start_s / flow_end_s point to uint32_t[n_rows], zero-extended; start_time, end_time and day_s stay 64-bit.
+ * Columns need only their natural alignment (1, 8 or 4 bytes): a device slice at any offset is accepted; 16-byte aligned action columns
+ * are read with 16-byte loads.  The call reads its inputs only; two calls on the same inputs give the same result.  It leases a job
+ * context as the other ingest calls do, so it runs beside jobs.  The result belongs to the library, as tad_points does: free it with
+ * tad_drop_rows_free.  n_rows == 0 returns an empty result (n_rows = 0, NULL columns).
+ * TAD_ERR_INVALID_ARGUMENT, a message in tad_last_error and no result: a NULL engine, cols or out; a mandatory column NULL with
+ * n_rows > 0; end_time != 0 with flow_end_s == NULL; a flag other than TAD_FLAG_TIME_U32.
+ * Cost: two launches with a scan between them and two host synchronisations (the host reads the total to size the result).  About
+ * 2.25 B a row for the action columns and the row bitmask, plus the sectors the selected rows touch and 56 B written per selected row;
+ * n_rows / 8 B + 12 B per 4096 rows of job-context workspace, grow-only; a host table is staged whole.  Not yet measured on an MI355X
+ * (DESIGN.md §5). */
+#define TAD_FEATURE_DROP_ROWS 1024u   /* tad_drop_select: flow rows -> the drop job's (endpoint, direction, day, count) rows */
+typedef struct {
+  uint64_t n_rows;
+  const uint8_t *ingress_action;                    /* UInt8, create_table.sh:63 */
+  const uint8_t *egress_action;                     /* UInt8, create_table.sh:68 */
+  const int64_t *flow_start_s;                      /* mandatory: the date and the start filter */
+  const int64_t *flow_end_s;                        /* optional (NULL) */
+  const int64_t *src_ip;                            /* dictionary codes, these six */
+  const int64_t *src_pod_ns;
+  const int64_t *src_pod_name;
+  const int64_t *dst_ip;
+  const int64_t *dst_pod_ns;
+  const int64_t *dst_pod_name;
+  int64_t src_pod_null;                             /* the pod-name code that means NULL / '' on that side; -1 = none */
+  int64_t dst_pod_null;
+  const uint8_t *keep;                              /* optional (NULL): tad_mask_rows' output, e.g. the clusterUUID predicate */
+  uint32_t flags;                                   /* TAD_FLAG_TIME_U32 only */
+  tad_mem memory;
+} tad_drop_flow_columns;
+
+typedef struct {
+  uint64_t n_rows;                                  /* m */
+  int64_t *endpoint_kind;                           /* the key tuple, these four: ready for tad_key_columns.cols_a */
+  int64_t *endpoint_ns;
+  int64_t *endpoint_name;
+  int64_t *direction;
+  int64_t *day_s;
+  uint64_t *count;
+  uint64_t *row;
+  tad_mem memory;
+} tad_drop_rows;
+
+int tad_drop_select(tad_engine *e, const tad_drop_flow_columns *cols, int64_t start_time, int64_t end_time,
+                    tad_mem out_memory, tad_drop_rows **out);
+void tad_drop_rows_free(tad_engine *e, tad_drop_rows *r);
+
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).
  * tad_job_progress (ABI 12): the job whose tad_job.id equals `id`; *total = 0 when no such job is in flight (finished or not yet

@@ -31,6 +31,7 @@ TAD_FEATURE_STATE_WINDOW = 64                # tad_features() bit: tad_run_state
 TAD_FEATURE_KEY_DICT = 128                   # tad_features() bit: tad_keydict, a persistent tuple -> key id dictionary on the device
 TAD_FEATURE_KEY_RETIRE = 256                 # tad_features() bit: tad_state_compact / tad_keydict_compact, dead keys dropped and the rest renumbered
 TAD_FEATURE_STATE_DROP = 512                 # tad_features() bit: tad_drop_state / tad_drop_stream, the drop detector on a series state
+TAD_FEATURE_DROP_ROWS = 1024                 # tad_features() bit: tad_drop_select, flow rows -> the drop job's (endpoint, direction, day, count) rows
 
 
 class Plan(C.Structure):
@@ -130,6 +131,20 @@ class Points(C.Structure):
                 ("memory", C.c_int), ("stats", Stats)]
 
 
+class DropFlowColumns(C.Structure):
+    """tad_drop_flow_columns: the ten flow-table columns tad_drop_select reads (two UInt8 actions, the times, six dictionary-code columns, keep)."""
+    _fields_ = [("n_rows", u64), ("ingress_action", C.c_void_p), ("egress_action", C.c_void_p), ("flow_start_s", C.c_void_p), ("flow_end_s", C.c_void_p),
+                ("src_ip", C.c_void_p), ("src_pod_ns", C.c_void_p), ("src_pod_name", C.c_void_p),
+                ("dst_ip", C.c_void_p), ("dst_pod_ns", C.c_void_p), ("dst_pod_name", C.c_void_p),
+                ("src_pod_null", i64), ("dst_pod_null", i64), ("keep", C.c_void_p), ("flags", u32), ("memory", C.c_int)]
+
+
+class DropRows(C.Structure):
+    """tad_drop_rows: tad_drop_select's result, one row per selected flow row in input order; owned by the library."""
+    _fields_ = [("n_rows", u64), ("endpoint_kind", C.c_void_p), ("endpoint_ns", C.c_void_p), ("endpoint_name", C.c_void_p), ("direction", C.c_void_p),
+                ("day_s", C.c_void_p), ("count", C.c_void_p), ("row", C.c_void_p), ("memory", C.c_int)]
+
+
 # every symbol include/tad.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "tad_abi_version": (C.c_int, []),
@@ -178,6 +193,8 @@ SYMBOLS = {
     "tad_keydict_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
     "tad_drop_state": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_drop_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),
+    "tad_drop_select": (C.c_int, [C.c_void_p, C.POINTER(DropFlowColumns), i64, i64, C.c_int, C.POINTER(C.POINTER(DropRows))]),
+    "tad_drop_rows_free": (None, [C.c_void_p, C.POINTER(DropRows)]),
     "tad_encode_strings": (C.c_int, [C.c_void_p, C.POINTER(StringColumn), C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]),
     "tad_widen_column": (C.c_int, [C.c_void_p, C.c_void_p, i32, i32, C.c_int, u64, C.c_void_p, u64, C.c_void_p]),
     "tad_mask_rows": (C.c_int, [C.c_void_p, u64, i32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(u64), i32, C.c_void_p]),

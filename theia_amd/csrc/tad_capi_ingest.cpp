@@ -1,5 +1,6 @@
 // tad_capi_ingest.cpp — the ingest entry points of include/tad.h: rows bucketed by owner for the all-to-all(v),
-// key tuples -> dense ids, Arrow string columns -> dictionary codes, Arrow buffers -> 8-byte device columns, row masks, the synthetic table.
+// key tuples -> dense ids, Arrow string columns -> dictionary codes, Arrow buffers -> 8-byte device columns, row masks, the synthetic table,
+// flow rows -> the drop job's rows.
 #include "tad_engine.h"
 
 using namespace tad;
@@ -288,6 +289,139 @@ int tad_mask_rows(tad_engine *eng, uint64_t n, int32_t n_terms, const int64_t *c
   HIP_TRY(e, hipGetLastError());
   if (herr) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_mask_rows: a code lies outside its mask");
   return TAD_OK;
+}
+
+// ---- the drop job's flow-row query: tad_drop_select (tad_drop_select.hip) ----
+int tad_drop_select(tad_engine *eng, const tad_drop_flow_columns *cols, int64_t start_time, int64_t end_time, tad_mem out_memory, tad_drop_rows **out) {
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_drop_select: engine is NULL");
+  if (!cols || !out) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_drop_select: cols / out is NULL");
+  *out = nullptr;
+  if ((cols->memory != TAD_MEM_HOST && cols->memory != TAD_MEM_DEVICE) || (out_memory != TAD_MEM_HOST && out_memory != TAD_MEM_DEVICE))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_drop_select: memory must be TAD_MEM_HOST or TAD_MEM_DEVICE");
+  if (cols->flags & ~TAD_FLAG_TIME_U32) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_drop_select: flags 0x%x: only TAD_FLAG_TIME_U32 is understood", cols->flags);
+  if (end_time != 0 && !cols->flow_end_s) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_drop_select: end_time is set and flow_end_s is NULL");
+  const uint64_t n = cols->n_rows;
+  if (n && (!cols->ingress_action || !cols->egress_action || !cols->flow_start_s || !cols->src_ip || !cols->src_pod_ns || !cols->src_pod_name || !cols->dst_ip ||
+            !cols->dst_pod_ns || !cols->dst_pod_name))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_drop_select: the two action columns, flow_start_s and the six code columns are required");
+  DropRowsPriv *rp = new (std::nothrow) DropRowsPriv();
+  if (!rp) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "out of host memory");
+  memset(rp, 0, sizeof *rp);
+  rp->pub.memory = out_memory;
+  if (n == 0) { *out = &rp->pub; return TAD_OK; }
+  struct Guard { DropRowsPriv *p; ~Guard() { delete p; } } guard{rp};   // (until the result is handed over)
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "tad_drop_select: no job context available");
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  const bool host = cols->memory == TAD_MEM_HOST;
+  const int t32 = (cols->flags & TAD_FLAG_TIME_U32) ? 1 : 0;
+  const uint64_t tiles = dsel_tiles(n);
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  // workspace: row bitmask | tile counts | tile offsets (64-bit) | scan scratch | total | a host table's columns
+  const size_t bits_b = up((size_t)((n + kDselLaneRows - 1) / kDselLaneRows) * 2), cnt_b = up((size_t)tiles * 4), off_b = up((size_t)(tiles + 1) * 8);
+  const size_t scr_b = up(scan_scratch_elems(tiles) * 8), t_b = up((size_t)n * (t32 ? 4 : 8)), c_b = up((size_t)n * 8), a_b = up((size_t)n);
+  const size_t stage = host ? 2 * a_b + t_b + (cols->flow_end_s ? t_b : 0) + 6 * c_b + (cols->keep ? a_b : 0) : 0;
+  const size_t need = bits_b + cnt_b + off_b + scr_b + 256 + stage;
+  if (need > e->ws_limit)
+    return fail(e, TAD_ERR_GRID_TOO_LARGE, "tad_drop_select needs %llu bytes of scratch > workspace limit %llu", (unsigned long long)need, (unsigned long long)e->ws_limit);
+  int rc;
+  if ((rc = ensure(e, e->dsel, need)) != TAD_OK) return rc;
+  unsigned char *p = static_cast<unsigned char *>(e->dsel.p);
+  uint16_t *bits = reinterpret_cast<uint16_t *>(p); p += bits_b;
+  uint32_t *cnt = reinterpret_cast<uint32_t *>(p); p += cnt_b;
+  unsigned long long *off = reinterpret_cast<unsigned long long *>(p); p += off_b;
+  unsigned long long *scratch = reinterpret_cast<unsigned long long *>(p); p += scr_b;
+  unsigned long long *total_dev = reinterpret_cast<unsigned long long *>(p); p += 256;
+  DselIn A{};
+  A.ia = cols->ingress_action; A.ea = cols->egress_action; A.keep = cols->keep;
+  A.ts = cols->flow_start_s; A.te = cols->flow_end_s;
+  const int64_t *codes[6] = {cols->src_ip, cols->src_pod_ns, cols->src_pod_name, cols->dst_ip, cols->dst_pod_ns, cols->dst_pod_name};
+  if (host) {
+    auto put = [&](const void *src, size_t bytes, size_t room) -> const void * {
+      const void *d = p;
+      if (hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return nullptr;
+      p += room;
+      return d;
+    };
+    bool ok = true;
+    ok = ok && (A.ia = static_cast<const uint8_t *>(put(cols->ingress_action, n, a_b))) != nullptr;
+    ok = ok && (A.ea = static_cast<const uint8_t *>(put(cols->egress_action, n, a_b))) != nullptr;
+    ok = ok && (A.ts = put(cols->flow_start_s, (size_t)n * (t32 ? 4 : 8), t_b)) != nullptr;
+    if (cols->flow_end_s) ok = ok && (A.te = put(cols->flow_end_s, (size_t)n * (t32 ? 4 : 8), t_b)) != nullptr;
+    for (int c = 0; c < 6; ++c) ok = ok && (codes[c] = static_cast<const int64_t *>(put(codes[c], (size_t)n * 8, c_b))) != nullptr;
+    if (cols->keep) ok = ok && (A.keep = static_cast<const uint8_t *>(put(cols->keep, n, a_b))) != nullptr;
+    if (!ok) { (void)hipGetLastError(); return fail(e, TAD_ERR_HIP, "tad_drop_select: staging the host columns failed"); }
+  }
+  A.src_ip = reinterpret_cast<const long long *>(codes[0]); A.src_ns = reinterpret_cast<const long long *>(codes[1]); A.src_pod = reinterpret_cast<const long long *>(codes[2]);
+  A.dst_ip = reinterpret_cast<const long long *>(codes[3]); A.dst_ns = reinterpret_cast<const long long *>(codes[4]); A.dst_pod = reinterpret_cast<const long long *>(codes[5]);
+  A.src_null = cols->src_pod_null; A.dst_null = cols->dst_pod_null;
+  A.start_time = start_time; A.end_time = end_time;
+  A.n = n; A.t32 = t32;
+  launch_dsel_flags(s, A, bits, cnt);
+  launch_scan(s, cnt, off, tiles, scratch, total_dev);
+  unsigned long long m = 0;
+  HIP_TRY(e, hipMemcpyAsync(&m, total_dev, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));     // the host sizes the result
+  HIP_TRY(e, hipGetLastError());
+  if (m > n) return fail(e, TAD_ERR_HIP, "tad_drop_select: internal error: %llu rows selected out of %llu", m, (unsigned long long)n);
+  if (m == 0) { guard.p = nullptr; *out = &rp->pub; return TAD_OK; }
+  // seven columns of m values, each starting on a 32-byte boundary
+  const uint64_t stride = (m + 3) & ~3ull;
+  const size_t bytes = (size_t)stride * 8 * 7;
+  ResultBlock blk;
+  if ((rc = alloc_device_block(e, bytes, &blk)) != TAD_OK) return rc;
+  unsigned char *d = static_cast<unsigned char *>(blk.base);
+  DselOut O{reinterpret_cast<long long *>(d), reinterpret_cast<long long *>(d + stride * 8), reinterpret_cast<long long *>(d + stride * 16),
+            reinterpret_cast<long long *>(d + stride * 24), reinterpret_cast<long long *>(d + stride * 32),
+            reinterpret_cast<unsigned long long *>(d + stride * 40), reinterpret_cast<unsigned long long *>(d + stride * 48)};
+  launch_dsel_emit(s, A, bits, off, O);
+  void *h = nullptr;
+  hipError_t hr = hipSuccess;
+  if (out_memory == TAD_MEM_HOST) {
+    h = malloc(bytes);
+    if (!h) { (void)hipStreamSynchronize(s); release_block(e, blk.base, blk.cap); return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory for %zu bytes of drop rows", bytes); }
+    hr = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s);
+  }
+  const hipError_t hs = hipStreamSynchronize(s);
+  if (hr == hipSuccess) hr = hs;
+  if (hr == hipSuccess) hr = hipGetLastError();
+  if (hr != hipSuccess) {
+    release_block(e, blk.base, blk.cap);
+    free(h);
+    return fail(e, TAD_ERR_HIP, "tad_drop_select: %s", hipGetErrorString(hr));
+  }
+  unsigned char *base = d;
+  if (out_memory == TAD_MEM_HOST) {
+    release_block(e, blk.base, blk.cap);
+    base = static_cast<unsigned char *>(h);
+    rp->block = h; rp->block_cap = bytes;
+  } else {
+    rp->block = blk.base; rp->block_cap = blk.cap;
+  }
+  rp->pub.n_rows = m;
+  rp->pub.endpoint_kind = reinterpret_cast<int64_t *>(base);
+  rp->pub.endpoint_ns = reinterpret_cast<int64_t *>(base + stride * 8);
+  rp->pub.endpoint_name = reinterpret_cast<int64_t *>(base + stride * 16);
+  rp->pub.direction = reinterpret_cast<int64_t *>(base + stride * 24);
+  rp->pub.day_s = reinterpret_cast<int64_t *>(base + stride * 32);
+  rp->pub.count = reinterpret_cast<uint64_t *>(base + stride * 40);
+  rp->pub.row = reinterpret_cast<uint64_t *>(base + stride * 48);
+  guard.p = nullptr;
+  *out = &rp->pub;
+  return TAD_OK;
+}
+
+void tad_drop_rows_free(tad_engine *e, tad_drop_rows *r) {
+  if (!r) return;
+  DropRowsPriv *rp = reinterpret_cast<DropRowsPriv *>(r);
+  if (rp->block) {
+    if (r->memory == TAD_MEM_DEVICE && e) release_block(e, rp->block, rp->block_cap);
+    else if (r->memory == TAD_MEM_DEVICE) hipFree(rp->block);
+    else free(rp->block);
+  }
+  delete rp;
 }
 
 }  // extern "C"

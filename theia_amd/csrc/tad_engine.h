@@ -102,6 +102,7 @@ struct JobCtx {
   struct MergeCall *merge = nullptr;   // set while the context runs a tad_state_merge batch (run_job_locked's merge mode)
   DevBuf as_key, as_pt, as_ser, as_fit, as_pos, as_ws;   // a stream ARIMA batch: per key | per new point | packed series | per fit | per position | fit workspace
   DevBuf ds_key, ds_pt;   // tad_drop_state / tad_drop_stream: per key (mean, std, m2, n, ok) | per judged point (verdict, rows, row offset)
+  DevBuf dsel;            // tad_drop_select: row bitmask | tile counts | tile offsets | scan scratch | total | a host table's staged columns
   int arima_relaunches = 0;       // times the running job's ARIMA fit was relaunched after it had yielded to whole-CU jobs (tad_stats.arima_relaunches)
   bool sp_by_partition = false;   // the running job's sparse Stage 0 went through the partition pass + LDS sort (stage0_path 8 / 9 / 10 instead of 4 / 6 / 7)
   DevBuf part_fin;                                                                // Stage 0 v2, sampled histogram: final cursors of the (workgroup, partition) regions
@@ -239,7 +240,7 @@ template <typename F> void for_each_buf(JobCtx *c, F f) {
                     &c->mg_pts, &c->mg_keys, &c->mg_hist,
                     &c->wv_key, &c->wv_pts,
                     &c->as_key, &c->as_pt, &c->as_ser, &c->as_fit, &c->as_pos, &c->as_ws,
-                    &c->ds_key, &c->ds_pt};
+                    &c->ds_key, &c->ds_pt, &c->dsel};
   for (DevBuf *b : bufs) f(*b);
 }
 
@@ -342,6 +343,12 @@ struct ResultPriv {  // lives right behind the public struct
 
 struct PointsPriv {  // tad_points + its storage
   tad_points pub;
+  void *block;
+  size_t block_cap;
+};
+
+struct DropRowsPriv {  // tad_drop_rows + its storage
+  tad_drop_rows pub;
   void *block;
   size_t block_cap;
 };

@@ -759,12 +759,29 @@ void launch_widen(hipStream_t s, const void *src, int bits, bool is_signed, uint
 void launch_mask_rows(hipStream_t s, uint64_t n, int n_terms, const long long *const *codes, const uint8_t *const *masks, const uint64_t *mask_len, bool combine,
                       uint8_t *keep, unsigned int *err);
 
+// ---- the drop job's flow-row select (tad_drop_select.hip; tad.h, tad_drop_select) ----
+constexpr int kDselLaneRows = 16;      // rows a lane owns: one 16-byte load of an action column, one 16-bit word of the row bitmask
+constexpr int kDselTileRows = 4096;    // rows a workgroup of 256 lanes owns
+struct DselIn {          // every pointer DEVICE; ts / te: long long[n], or uint32_t[n] when t32 (te may be NULL when end_time == 0)
+  const uint8_t *ia, *ea, *keep;
+  const void *ts, *te;
+  const long long *src_ip, *src_ns, *src_pod, *dst_ip, *dst_ns, *dst_pod;
+  long long src_null, dst_null, start_time, end_time;
+  uint64_t n;
+  int t32;
+};
+struct DselOut { long long *kind, *ns, *name, *dir, *day; unsigned long long *count, *row; };
+uint64_t dsel_tiles(uint64_t n);
+void launch_dsel_flags(hipStream_t s, const DselIn &A, uint16_t *bits, uint32_t *cnt);
+void launch_dsel_emit(hipStream_t s, const DselIn &A, const uint16_t *bits, const unsigned long long *off, const DselOut &O);
+
 // ---- code-object preload (tad_engine.cpp:preload_code_objects) ----
 // HIP loads a translation unit's code object on the first use of one of its kernels (~0.4 ms each, inside the first job otherwise).
 const void *code_anchor_arima();
 const void *code_anchor_compact();
 const void *code_anchor_dbscan();
 const void *code_anchor_drop();
+const void *code_anchor_drop_select();
 const void *code_anchor_drop_state();
 const void *code_anchor_factorize();
 const void *code_anchor_history();

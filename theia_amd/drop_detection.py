@@ -6,6 +6,8 @@ row per anomalous day (ref:42-56).  Same class and method names here; `end_parti
 ABI, `drop_detection_table` runs every partition of an aggregated table in ONE tad_run (algo DROP).  No CPU fallback.
 `PeriodicalDropDetection` is the "periodical" job the reference names and does not have (snowflake/cmd/dropDetection.go:282): the
 partitions' daily counts live in a streaming state on the device, a feed judges the new days against everything kept.
+`drop_detection_from_flows` and `PeriodicalDropDetection.feed_flows` start one step earlier, from the flow rows themselves: the query
+that dropDetection.go:36-190 builds runs on the device (TadEngine.drop_select, then factorize / the key dictionary and Stage 0's sum).
 Only the UDTF's call protocol is mirrored (a thin adaptor); the reference's Result helper class is not reproduced.
 """
 import datetime
@@ -77,6 +79,51 @@ def drop_detection_table(endpoint, direction, date, drop_number, detection_id=No
     return rows
 
 
+FLOW_COLUMNS = ("ingress_action", "egress_action", "flow_start_s", "src_ip", "src_pod_ns", "src_pod_name", "dst_ip", "dst_pod_ns", "dst_pod_name")
+DIRECTIONS = ("ingress", "egress")
+
+
+def _select_flows(engine, columns, dictionaries, start_time, end_time, keep):
+    """TadEngine.drop_select over a dict of flow columns; the pod-name code that means "no pod" is the dictionary's '' unless the
+    columns name one (src_pod_null / dst_pod_null)"""
+    names = list(dictionaries["pod_name"])
+    null = names.index("") if "" in names else -1
+    return engine.drop_select(*[columns[c] for c in FLOW_COLUMNS], flow_end_s=columns.get("flow_end_s"),
+                              src_pod_null=columns.get("src_pod_null", null), dst_pod_null=columns.get("dst_pod_null", null),
+                              start_time=start_time, end_time=end_time, keep=keep, out="device")
+
+
+def _decode_keys(engine, rows, first, dictionaries):
+    """the (endpoint, direction) strings of the keys whose first rows (into `rows`) are `first`: ns/name for a pod, the IP otherwise"""
+    kind, ns, name, direction = (engine.gather(c, first).tolist() for c in rows.tuple_columns())
+    ips, nss, pods = dictionaries["ip"], dictionaries["pod_ns"], dictionaries["pod_name"]
+    return [("%s/%s" % (nss[n], pods[m]) if k else str(ips[m]), DIRECTIONS[d]) for k, n, m, d in zip(kind, ns, name, direction)]
+
+
+def drop_detection_from_flows(engine, columns, dictionaries, start_time=0, end_time=0, keep=None, detection_id=None, job_type="initial"):
+    """The drop job from flow rows to result rows on the device.  columns: dict of the flow table's columns (FLOW_COLUMNS, optionally
+    flow_end_s, src_pod_null, dst_pod_null) — uint8 rule actions, epoch-second times and int64 dictionary codes, numpy arrays or
+    DeviceArrays; dictionaries: {"ip": [...], "pod_ns": [...], "pod_name": [...]}, code -> string.  start_time / end_time / keep: the
+    query's flowStartSeconds >=, flowEndSeconds < and clusterUUID predicates (keep: one byte per row, e.g. TadEngine.mask_rows').
+    drop_select -> factorize over (kind, ns, name, direction) -> run("DROP", value_op="sum") over (key id, day, 1): the rows
+    drop_detection_table returns for the query's aggregated counts, in (key by first appearance among the dropped rows, date) order."""
+    eng = engine or _ad.get_engine()
+    rows = _select_flows(eng, columns, dictionaries, start_time, end_time, keep)
+    if rows.n_rows == 0:
+        return []
+    key, _, first = eng.factorize(rows.tuple_columns())
+    keys = _decode_keys(eng, rows, first, dictionaries)
+    res = eng.run("DROP", key, rows["day_s"], rows["count"], max(len(keys), 1), agg_flow="svc", value_op="sum")
+    now = datetime.datetime.now()
+    host = res.to_host()
+    out = []
+    for k, t, x, mean, std in zip(host["key_id"].tolist(), host["flow_end_s"].tolist(), host["throughput"].tolist(),
+                                  host["algo_calc"].tolist(), host["stddev"].tolist()):
+        ep, di = keys[int(k)]
+        out.append((job_type, detection_id or str(uuid.uuid4()), now, ep, di, mean, std, str(np.datetime64(int(t), "s").astype("datetime64[D]")), int(x)))
+    return out
+
+
 def _days(date):
     """dates (YYYY-MM-DD strings, datetime64 or day numbers) -> (int64 day numbers, whether they were dates)"""
     import pandas as pd
@@ -100,6 +147,8 @@ class PeriodicalDropDetection:
         self._keys = []                   # key id -> (endpoint, direction)
         self._state = None
         self._dates = False               # the feeds carried dates (rows report dates) or day numbers
+        self._seconds = False             # the state's times are epoch seconds (feed_flows) rather than day numbers (feed)
+        self._dict = None                 # feed_flows: the (kind, ns, name, direction) -> key id dictionary on the device
 
     @property
     def state(self):
@@ -122,12 +171,17 @@ class PeriodicalDropDetection:
         for k, t, x, mean, std in zip(host["key_id"].tolist(), host["flow_end_s"].tolist(), host["throughput"].tolist(),
                                       host["algo_calc"].tolist(), host["stddev"].tolist()):
             ep, di = self._keys[int(k)]
-            dd = str(np.datetime64(int(t), "D")) if self._dates else int(t)
+            if self._seconds:
+                dd = str(np.datetime64(int(t), "s").astype("datetime64[D]"))
+            else:
+                dd = str(np.datetime64(int(t), "D")) if self._dates else int(t)
             rows.append((job_type, detection_id or str(uuid.uuid4()), now, ep, di, mean, std, dd, int(x)))
         return rows
 
     def feed(self, endpoint, direction, date, drop_number, detection_id=None):
         """One batch -> its anomalous days as RESULT_COLUMNS tuples with job_type "periodical", in (partition, date) order."""
+        if self._dict is not None:
+            raise ValueError("this instance is fed flow rows (feed_flows): its key ids come from the device dictionary")
         endpoint, direction = np.asarray(endpoint).astype(str), np.asarray(direction).astype(str)
         day, self._dates = _days(date)
         key = self._key_ids(endpoint, direction)
@@ -139,11 +193,37 @@ class PeriodicalDropDetection:
         res = self._engine.drop_stream(self._state, key, day, np.asarray(drop_number, dtype=np.uint64), agg_flow="svc", value_op="sum")
         return self._rows(res, "periodical", detection_id)
 
+    def feed_flows(self, columns, dictionaries, start_time=0, end_time=0, keep=None, detection_id=None):
+        """One batch of FLOW ROWS -> its anomalous days, as `feed` returns them for the batch's aggregated counts: drop_select -> this
+        instance's key dictionary (KeyDict over kind, ns, name, direction: ids stay the same from feed to feed) -> drop_stream with
+        value_op="sum" over (key id, day, 1).  columns / dictionaries / start_time / end_time / keep: as drop_detection_from_flows; the
+        dictionaries must keep their codes from feed to feed (they may grow).  A feed must hold WHOLE DAYS: the stream judges a day when
+        it arrives, so a day split over two feeds is a late row in the second and that feed is refused as a whole, as `feed` refuses
+        it.  An instance is fed either counts (`feed`) or flow rows, not both; dates come back as YYYY-MM-DD."""
+        if self._keys and self._dict is None:
+            raise ValueError("this instance is fed daily counts (feed): its key ids come from the host table")
+        eng = self._engine
+        rows = _select_flows(eng, columns, dictionaries, start_time, end_time, keep)
+        if rows.n_rows == 0:
+            return []
+        if self._dict is None:
+            self._dict = eng.key_dict(4)
+        self._dates = self._seconds = True
+        key, _, first, _ = self._dict.encode(rows.tuple_columns())
+        self._keys += _decode_keys(eng, rows, first, dictionaries)
+        n_keys = max(len(self._keys), 1)
+        if self._state is None:
+            self._state = eng.state_create(n_keys, series=True, times=True)
+        elif n_keys > self._state.num_keys:
+            self._state.resize(n_keys)
+        res = eng.drop_stream(self._state, key, rows["day_s"], rows["count"], agg_flow="svc", value_op="sum")
+        return self._rows(res, "periodical", detection_id)
+
     def window(self, from_date=None, to_date=None, detection_id=None):
         """The anomalous days with from_date <= date < to_date (None = no bound) of everything kept, each partition judged over its days
         inside the range: the rows of an "initial" job over those days."""
         if self._state is None:
             return []
-        bound = lambda d: 0 if d is None else int(_days([d])[0][0])
+        bound = lambda d: 0 if d is None else int(_days([d])[0][0]) * (86400 if self._seconds else 1)
         res = self._engine.drop_state(self._state, bound(from_date), bound(to_date))
         return self._rows(res, "periodical", detection_id)

@@ -40,6 +40,22 @@ class DeviceArray:
             engine._check(engine._lib.tad_copy_to_device(engine._h, d.ptr, a.ctypes.data, a.nbytes))
         return d
 
+    _base = None     # a view's owner: the memory is the owner's, which stays alive with the view
+
+    @classmethod
+    def view_of(cls, engine, ptr, n, dtype, base):
+        """n elements of dtype at device address ptr, inside memory `base` owns (a DeviceArray, a result): nothing is allocated or freed"""
+        d = object.__new__(cls)
+        d.engine, d.n, d.dtype, d.ptr, d._base = engine, int(n), np.dtype(dtype), ptr, base
+        return d
+
+    def view(self, byte_offset, n, dtype):
+        """n elements of dtype starting byte_offset bytes into this array (a device slice; shares the memory)"""
+        dt = np.dtype(dtype)
+        if byte_offset < 0 or byte_offset + int(n) * dt.itemsize > self.n * self.dtype.itemsize:
+            raise ValueError("view of %d x %d bytes at %d does not fit %d bytes" % (n, dt.itemsize, byte_offset, self.n * self.dtype.itemsize))
+        return DeviceArray.view_of(self.engine, self.ptr + int(byte_offset), n, dt, self)
+
     def to_host(self):
         out = np.empty(self.n, dtype=self.dtype)
         if self.n:
@@ -47,9 +63,10 @@ class DeviceArray:
         return out
 
     def free(self):
-        if self.ptr is not None and self.engine._h is not None:
+        if self._base is None and self.ptr is not None and self.engine._h is not None:
             self.engine._lib.tad_device_free(self.engine._h, self.ptr)
         self.ptr = None
+        self._base = None
 
     def __del__(self):
         try:
@@ -282,6 +299,60 @@ class TadPoints:
     def close(self):
         if self._ptr is not None and self._engine._h is not None:
             self._engine._lib.tad_points_free(self._engine._h, self._ptr)
+        self._ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TadDropRows:
+    """tad_drop_select's result: seven columns, one row per selected flow row in input order.  Iterates as (endpoint_kind, endpoint_ns,
+    endpoint_name, direction, day_s, count, row); each is a numpy array (out="host") or a DeviceArray view into the library's block
+    (out="device"), which lives as long as this object or any of the views."""
+
+    FIELDS = (("endpoint_kind", np.int64), ("endpoint_ns", np.int64), ("endpoint_name", np.int64), ("direction", np.int64),
+              ("day_s", np.int64), ("count", np.uint64), ("row", np.uint64))
+
+    def __init__(self, engine, ptr):
+        self._engine = engine
+        self._ptr = ptr
+        p = ptr.contents
+        self.n_rows = int(p.n_rows)
+        self.memory = "device" if p.memory == capi.TAD_MEM_DEVICE else "host"
+        self._cols = {}
+        for name, dt in self.FIELDS:
+            if self.memory == "device":
+                self._cols[name] = DeviceArray.view_of(engine, getattr(p, name), self.n_rows, dt, self)
+            else:
+                arr = np.empty(self.n_rows, dtype=dt)
+                if self.n_rows:
+                    C.memmove(arr.ctypes.data, getattr(p, name), arr.nbytes)
+                self._cols[name] = arr
+        if self.memory == "host":
+            self.close()
+
+    def __getitem__(self, name):
+        return self._cols[name]
+
+    def __iter__(self):
+        return iter(self._cols[name] for name, _ in self.FIELDS)
+
+    def __len__(self):
+        return len(self.FIELDS)
+
+    def tuple_columns(self):
+        """the four key-tuple columns, as factorize / KeyDict.encode take them"""
+        return [self._cols[name] for name, _ in self.FIELDS[:4]]
+
+    def to_host(self):
+        return {name: (c.to_host() if isinstance(c, DeviceArray) else c) for name, c in self._cols.items()}
+
+    def close(self):
+        if self._ptr is not None and self._engine._h is not None:
+            self._engine._lib.tad_drop_rows_free(self._engine._h, self._ptr)
         self._ptr = None
 
     def __del__(self):
@@ -871,6 +942,76 @@ class TadEngine:
         del keep
         self._check(rc)
         return TadResult(self, res)
+
+    # ---- the drop job's flow-row query (tad_drop_select) ----
+    def drop_select(self, ingress_action, egress_action, flow_start_s, src_ip, src_pod_ns, src_pod_name, dst_ip, dst_pod_ns, dst_pod_name,
+                    flow_end_s=None, src_pod_null=-1, dst_pod_null=-1, start_time=0, end_time=0, keep=None, out="device"):
+        """Flow rows -> the drop job's rows (tad_drop_select): the rows whose ingress or egress rule action is 2 or 3 (and that pass
+        start_time <= flow_start_s, flow_end_s < end_time and keep), each with its endpoint tuple (kind, ns, name), direction, day,
+        count 1 and input row, in input order.  Columns: numpy arrays on the host, or DeviceArrays / CUDA tensors all on the device —
+        uint8 actions and keep, int64 (or uint32: DateTime) times, int64 dictionary codes; *_pod_null: the pod-name code that means "no
+        pod" on that side.  Returns a TadDropRows: the seven columns as DeviceArrays (out="device") or numpy arrays (out="host")."""
+        if not (getattr(self._lib, "tad_features", None) and self._lib.tad_features() & capi.TAD_FEATURE_DROP_ROWS):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_drop_select (TAD_FEATURE_DROP_ROWS)")
+        keepalive = []
+
+        def col(x, dtype, what):
+            """-> (pointer, n, on the device, element size)"""
+            if x is None:
+                return None, None, None, 0
+            if isinstance(x, DeviceArray):
+                p, n, dev, size = x.ptr, x.n, True, x.dtype.itemsize
+                keepalive.append(x)
+            elif hasattr(x, "data_ptr") and hasattr(x, "is_cuda") and x.is_cuda:
+                x = x.contiguous()
+                p, n, dev, size = x.data_ptr(), x.numel(), True, x.element_size()
+                keepalive.append(x)
+            else:
+                a = np.asarray(x.numpy() if hasattr(x, "data_ptr") else x)
+                if not (dtype == np.int64 and what.startswith("flow_") and a.dtype == np.dtype(np.uint32)) and a.dtype != np.dtype(dtype):
+                    a = a.astype(dtype)
+                a = np.ascontiguousarray(a)
+                p, n, dev, size = a.ctypes.data, a.size, False, a.dtype.itemsize
+                keepalive.append(a)
+            ok = (1,) if dtype == np.uint8 else ((4, 8) if what.startswith("flow_") else (8,))
+            if size not in ok:
+                raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "drop_select: %s has %d-byte elements" % (what, size))
+            return p, n, dev, size
+
+        named = [("ingress_action", ingress_action, np.uint8), ("egress_action", egress_action, np.uint8), ("flow_start_s", flow_start_s, np.int64),
+                 ("flow_end_s", flow_end_s, np.int64), ("src_ip", src_ip, np.int64), ("src_pod_ns", src_pod_ns, np.int64),
+                 ("src_pod_name", src_pod_name, np.int64), ("dst_ip", dst_ip, np.int64), ("dst_pod_ns", dst_pod_ns, np.int64),
+                 ("dst_pod_name", dst_pod_name, np.int64)]
+        got = {name: col(x, dt, name) for name, x, dt in named}
+        n, dev = got["ingress_action"][1], got["ingress_action"][2]
+        present = [v for v in got.values() if v[1] is not None]
+        if n is None or any(v[1] != n or v[2] != dev for v in present):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "drop_select: columns must have equal length and live in the same memory")
+        widths = set(got[name][3] for name in ("flow_start_s", "flow_end_s") if got[name][1] is not None)
+        if len(widths) > 1:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "drop_select: flow_start_s / flow_end_s must have the same width")
+        pkeep = None
+        if keep is not None:
+            if not isinstance(keep, DeviceArray) and not (hasattr(keep, "is_cuda") and keep.is_cuda):
+                a = np.ascontiguousarray(np.asarray(keep).astype(np.uint8, copy=False))
+                if dev:       # a host mask over device columns is uploaded
+                    padded = np.frombuffer(a.tobytes() + b"\0" * (-a.size % 8 or 8), dtype=np.uint64)
+                    keep = DeviceArray.from_host(self, padded).view(0, a.size, np.uint8)
+                else:
+                    keep = a
+            pkeep, nk, devk, _ = col(keep, np.uint8, "keep")
+            if nk != n or devk != dev:
+                raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "drop_select: keep must have one byte per row and live where the columns live")
+        fc = capi.DropFlowColumns(n_rows=n, src_pod_null=int(src_pod_null), dst_pod_null=int(dst_pod_null), keep=pkeep,
+                                  flags=capi.TAD_FLAG_TIME_U32 if widths == {4} else 0, memory=capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST)
+        for name, _, _ in named:
+            setattr(fc, name, got[name][0])
+        res = C.POINTER(capi.DropRows)()
+        rc = self._lib.tad_drop_select(self._h, C.byref(fc), int(start_time), int(end_time),
+                                       capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
+        del keepalive
+        self._check(rc)
+        return TadDropRows(self, res)
 
     # ---- row-sharded ingest: bucket device rows by owner = key mod world (tad_shard_rows) ----
     def shard_rows(self, key_id, flow_end_s, value, world):

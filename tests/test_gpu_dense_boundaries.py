@@ -530,7 +530,7 @@ def test_record_cell_and_value_fields(engine, T, cb, variant):
 
 @pytest.mark.parametrize("T,dense", [(65535, True), (65536, False)])
 def test_tile_plan_ends_at_65536_buckets(engine, T, dense):
-    """part_plan_tiles / tad_capi.cpp:1110: T >= 2^16 has no tile plan, the direct scatter runs (path 1, in one attempt)"""
+    """part_plan_tiles / tad_capi_job.cpp (stage0_dense): T >= 2^16 has no tile plan, the direct scatter runs (path 1, in one attempt)"""
     K = 2
     pl = plan_tiles(K, T)
     assert (pl is not None) == dense

@@ -6,7 +6,7 @@
   B  the partition pass + LDS sort: rounds of <= 14336 records (k_ss_plan), split sets of 8192 (k_ss_split), the MSD bucket rule
      and mshift (k_ss_sort), the fold across threads of 14 slots, the one-pass / three-pass output, the rank-grid transposition in
      chunks of 4096 staged points (k_ss_place), the record's cell and value bits (part_plan_sparse, pass B)
-  C  the rule that sends a table to the sparse path at all (tad_capi.cpp)
+  C  the rule that sends a table to the sparse path at all (tad_capi_job.cpp: choose_stage0)
 
 References: orc.stage0 (a numpy group-by) for engine.aggregate, orc.run_job for the rows of engine.run with and without emit_all,
 through the check helpers of tests/test_gpu_sparse.py and tests/test_gpu_sparse_partition.py.  No tolerances anywhere.
@@ -41,8 +41,8 @@ RS_TILE = 4096                # tad_sparse.hip:220   kRsTile = kRsThreads * kRsI
 RS_WAVE_SLOTS = 512           # tad_sparse.hip:286   64 * kRsItems: consecutive slots a wavefront of k_rs_scatter ranks
 RS_DIGIT = 8                  # tad_sparse.hip:459   np = ceil(bits / 8) balanced digits
 RS_MAX_TB = 32                # tad_sparse.hip:457   time bits capped at 32
-SPARSE_MIN_CELLS = 1 << 24    # tad_capi.cpp:954     sparse iff cells >= 2^24 && slots < cells / 8 (or the grid does not fit)
-SPARSE_FILL = 8               # tad_capi.cpp:954
+SPARSE_MIN_CELLS = 1 << 24    # choose_stage0        sparse iff cells >= 2^24 && slots < cells / 8 (or the grid does not fit)
+SPARSE_FILL = 8               # choose_stage0
 SS_ITEMS = 14                 # tad_sparse.hip:566   kSsItems: sorted slots a thread of k_ss_sort folds
 SS_CAP = 14336                # tad_sparse.hip:567   kSsCap = 1024 * 14 records per LDS round
 SPLIT_SET = 8192              # tad_sparse.hip:671   kSet = kSplitThreads * 2 * kL records per set of k_ss_split
@@ -744,7 +744,7 @@ def rule_table(T, n):
 
 @pytest.mark.parametrize("T,n,sparse", [(4096, 30000, True), (4095, 30000, False), (4096, (1 << 21) - 1, True), (4096, 1 << 21, False)])
 def test_sparse_rule(engine, T, n, sparse):
-    """tad_capi.cpp: sparse iff cells >= 2^24 && slots < cells / 8 — no plan override, the engine decides"""
+    """tad_capi_job.cpp (choose_stage0): sparse iff cells >= 2^24 && slots < cells / 8 — no plan override, the engine decides"""
     k, t, v, K = rule_table(T, n)
     cells = K * T
     assert lattice(t)[1:] == (1, T)

@@ -1,5 +1,5 @@
 // tad_engine.h — PRIVATE header of libtad_mi355x.so's host side: the engine, its pool of job contexts, and what the translation
-// units of the C ABI share (tad_engine.cpp: life cycle, pool, memory; tad_capi.cpp: the job, and the state calls that run through it;
+// units of the C ABI share (tad_engine.cpp: life cycle, pool, memory; tad_capi_job.cpp: the batch job; tad_capi.cpp: the batches on a state and the state calls;
 // tad_capi_state.cpp: the life of a streaming state; tad_capi_ingest.cpp: the ingest entry points; tad_capi_series.cpp: the per-series
 // entry points; tad_capi_keydict.cpp: the key dictionary).  HIP only: there is no CPU fallback in this library (the CPU oracle under
 // oracle/ is test infrastructure and is never linked or called from here).
@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "tad_internal.h"
+#include "tad_stage0_retry.h"
 
 struct DevBuf {
   void *p = nullptr;
@@ -62,7 +63,7 @@ struct tad_engine {
   // whatever the stream priorities.  pause_count = jobs in flight that are in a whole-CU phase; *pause_dev (DEVICE memory) is 0 / non-zero
   // accordingly, written on the 0 <-> 1 transitions by a 4-byte fill on signal_stream (one stream, under pause_mu: the writes cannot
   // pass each other).  The fit polls it every optimiser cycle and suspends while it is raised (tad_arima.hip); its host loop relaunches it
-  // (detect_and_count).  The word lives in device memory because 2048 wavefronts polling a page-locked HOST word once per cycle (1.6e7
+  // (arima_yield_loop).  The word lives in device memory because 2048 wavefronts polling a page-locked HOST word once per cycle (1.6e7
   // reads/s over the host link) doubled the fit's time (C3 266 -> 492 ms, profiles/r6_a4_*); an agent-scope load from HBM costs nothing
   // measurable.
   std::mutex pause_mu;
@@ -115,18 +116,7 @@ struct JobCtx {
   tad::DevCounters *ctr_host = nullptr;           // = tail_host
   unsigned long long *total_host = nullptr;  // = tail_host + 64
   tad::Moments *moments_host = nullptr;           // = tail_host + 128
-  // what the last job of this context learnt about its table, reused when the next job has the same shape (nothing speculative: both only
-  // skip an attempt that is known to fail)
-  struct Learnt {
-    bool valid = false;
-    uint64_t n = 0, K = 0;
-    bool has2 = false;
-    int algo = 0, op = 0;
-    bool exact_hist = false;   // the sampled histogram proved too optimistic for this table: go straight to the exact one ...
-    uint32_t exact_uses = 0, exact_backoff = 8;   // ... for `exact_backoff` jobs, then the sample is tried again (a sorted table may be followed by
-                                                  // hashed ones of the same shape); a probe that fails doubles the interval, up to 64
-    bool wide_tiles = false;   // 32-bit tile cells overflowed the list for this table: go straight to 8-byte cells
-  } learnt;
+  tadh::Stage0Learnt learnt;   // what the last job of this context learnt about its table (tad_stage0_retry.h)
 };
 
 // one tad_state_merge call: what run_job_locked's merge mode needs beyond the job, and what it reports
@@ -368,6 +358,85 @@ struct JobParams {
 int ensure_rcp_table(JobCtx *e, uint64_t T);
 int ensure_key_buffers(JobCtx *e, uint64_t K);
 void emit_rows(JobCtx *e, Grid g, Lattice L, const JobParams &jp, OutRows out, uint64_t rows = 0);
+
+// (tad_capi.cpp) shared with the batch job (tad_capi_job.cpp)
+JobParams job_params(const tad_job *job);   // the job's detector parameters, 0 = the reference's default
+// the fixed-order Chan merge of the job tail's kMomentBlocks moment partials (any == false: no point, both 0)
+void merge_moments(const Moments *blocks, bool any, double *pts_mean, double *pts_m2);
+struct RowsOut {   // a rows result in the making: the device block the emit kernels write
+  ResultPriv *rp = nullptr;
+  OutRows dev_rows{};
+  ResultBlock dev_block;
+};
+int make_result(JobCtx *e, uint64_t rows, bool with_anomaly, tad_mem out_memory, ResultPriv **out, OutRows *dev_rows, ResultBlock *dev_block);
+int finish_result(JobCtx *e, ResultPriv *rp, uint64_t rows, bool with_anomaly, ResultBlock dev_block, OutRows dev_rows);
+// After the emit kernels are on the stream: ev[4], the block handed over or copied to the host (finish_result), the call's last
+// synchronisation — on failure the block and the result are gone — then what every rows result reports: the counters of c, the moments
+// (any_points), n_anomalies (TAD_FLAG_EMIT_ALL_POINTS: the verdicts counted), the context, the id.
+int finish_rows(JobCtx *e, const tad_job *job, RowsOut *ro, uint64_t rows, bool with_anomaly, const DevCounters &c, bool any_points);
+
+// What a batch on a history or series state leaves for its emit: the new points in (key, time) order and, for DBSCAN, their verdicts and rows.
+struct HistBatch {
+  const unsigned long long *nk = nullptr, *nv = nullptr;
+  const long long *nt = nullptr;
+  const unsigned long long *poff = nullptr;    // key k's new points at [poff[k], poff[k + 1])
+  const unsigned long long *P_dev = nullptr;   // the number of new points (device)
+  uint64_t P_cap = 0;                          // its bound on the host (exact for a sparse batch)
+  const uint8_t *noise = nullptr;
+  const uint32_t *cnt = nullptr;
+  const unsigned long long *row = nullptr;
+};
+// What a stream ARIMA batch leaves for its emit (stream_arima_batch)
+struct ArimaBatch {
+  uint64_t P = 0;
+  const unsigned long long *tidx = nullptr;    // slot of key k
+  const double *sigma = nullptr;               // per slot
+  const double *pcalc = nullptr;               // per new point
+  const uint8_t *pflag = nullptr;
+  const uint32_t *rows = nullptr;
+  const unsigned long long *row_off = nullptr;
+};
+// What the drop detector on a state leaves for its emit (state_drop_batch)
+struct DropBatch {
+  DropStateKeys keys{};
+  const uint8_t *flag = nullptr;
+  const uint32_t *cnt = nullptr;
+  const unsigned long long *row = nullptr;
+};
+int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound,
+                         const JobParams &jp, HistBatch *hb);
+int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound, bool op_max,
+                      double alpha, MergeCall *mc);
+int stream_arima_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const JobParams &jp, DevCounters *ctr, ArimaBatch *ab);
+int state_drop_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const JobParams &jp, bool touched_only, unsigned long long coop_min,
+                     uint32_t *list, unsigned int *lcount, DevCounters *ctr, DropBatch *db);
+
+// (tad_capi_job.cpp) the batch job on the context the caller holds, and what every entry point that feeds it a batch checks first
+int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_mem out_memory, tad_result **out, tad_points **points_out,
+                   tad_state *stream, int depth);
+int validate_job_columns(tad_engine *e, const tad_job *job, const tad_columns *cols, const char *who);
+
+// The ARIMA fit yields to whole-CU jobs of other contexts (PauseHold): its wavefronts suspend their fits while the engine's pause word is raised
+// and the kernel is relaunched here — after the word has cleared, or after 2 ms at the latest, so that a steady stream of short jobs
+// time-slices with the fit instead of starving it.  relaunch(grace, &yielded_dev) launches the fit again over what it left (0 on success).
+template <typename Relaunch>
+int arima_yield_loop(JobCtx *e, const unsigned int *yielded_dev, Relaunch relaunch) {
+  hipStream_t s = e->stream;
+  while (yielded_dev != nullptr && e->eng->pause_dev != nullptr) {
+    unsigned int y = 0;
+    HIP_TRY(e, hipMemcpyAsync(&y, yielded_dev, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    if (y == 0) break;
+    const auto t0 = std::chrono::steady_clock::now();
+    while (__atomic_load_n(&e->eng->pause_count, __ATOMIC_ACQUIRE) != 0 && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(2))
+      std::this_thread::sleep_for(std::chrono::microseconds(50));
+    // still raised after 2 ms (short jobs arrive back to back): this launch runs 24 optimiser cycles (~1 ms) before it looks at the word
+    const uint32_t grace = __atomic_load_n(&e->eng->pause_count, __ATOMIC_ACQUIRE) != 0 ? 24u : 0u;
+    if (relaunch(grace, &yielded_dev) != 0) return fail(e, TAD_ERR_HIP, "ARIMA launch failed");
+    e->arima_relaunches++;
+  }
+  return TAD_OK;
+}
 
 // (tad_capi_state.cpp) shared with the batches on a state (tad_capi.cpp)
 size_t state_bytes(uint64_t K);                              // one block of K keys' running state

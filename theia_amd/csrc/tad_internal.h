@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "tad.h"
+#include "tad_dev_err.h"   // DEV_ERR_*: what a kernel raises in DevCounters::err
 
 namespace tad {
 
@@ -30,10 +31,6 @@ struct Grid {
                             // row b holds every key's b-th point in time order and times[b * K + k] its flowEndSeconds
 };
 
-enum : uint32_t { DEV_ERR_KEY_RANGE = 1u, DEV_ERR_OFF_LATTICE = 2u, DEV_ERR_OVERFLOW_LIST = 4u, DEV_ERR_LATE_ROW = 8u,
-                  DEV_ERR_REGION_FULL = 16u,   // Stage 0 v2 with a SAMPLED histogram: a (workgroup, partition) region was sized too small
-                  // (32u was DEV_ERR_SPEC of the one-synchronisation job, ABI 8-11: removed in round 6, see docs/HISTORY.md)
-                  DEV_ERR_SPARSE_ROUND = 64u };  // sparse Stage 0 through the partition pass: one key bin holds more records than a workgroup sorts in LDS (the LSD sort takes over)
 enum : uint8_t { FLAG_PRESENT = 1, FLAG_ANOMALY = 2 };
 
 // Per-block partial of the lattice-derivation pass.
@@ -663,7 +660,7 @@ int launch_sparse_group(hipStream_t s, const uint64_t *key, const uint64_t *key2
 void launch_sparse_tmax(hipStream_t s, const unsigned long long *ucomp, uint64_t slots, const unsigned long long *P_dev, uint32_t *first, unsigned int *tmax);
 void launch_sparse_place(hipStream_t s, const unsigned long long *ucomp, const unsigned long long *uval, uint64_t P, const uint32_t *first,
                          int64_t t0, Grid g, long long *times);
-// length classes for skewed sparse tables (tad_sparse.hip; orchestration: tad_capi.cpp:run_sparse_classes)
+// length classes for skewed sparse tables (tad_sparse.hip; orchestration: tad_capi_job.cpp:run_sparse_classes)
 uint32_t sparse_class_count(uint32_t tmax);   // classes 0 .. count-1: series of <= 16, <= 64, <= 256, ... points
 void launch_sparse_len(hipStream_t s, const unsigned long long *ucomp, uint64_t P, const uint32_t *first, uint32_t *len);
 void launch_sparse_class_counts(hipStream_t s, const uint32_t *len, uint64_t K, uint32_t c, uint32_t *member, uint32_t *pts);

@@ -1740,3 +1740,130 @@ func (e *Engine) JobProgress(id string) (done, total int) {
 
 // JobsInFlight: job contexts busy right now.
 func (e *Engine) JobsInFlight() int { return int(C.tad_jobs_in_flight(e.h)) }
+
+var keySelectOnce sync.Once
+var keySelectOK bool
+
+// hasKeySelect: the library knows tad_keydict_select / tad_run_state_keys / tad_drop_state_keys (tad_features); an older one would not
+// export the calls.
+func hasKeySelect() bool {
+	keySelectOnce.Do(func() { keySelectOK = C.tad_features()&C.TAD_FEATURE_KEY_SELECT != 0 })
+	return keySelectOK
+}
+
+// SelectTerm is one term of KeyDict.Select: the key is kept iff Mask[tuple[Col]] != 0.
+type SelectTerm struct {
+	Col  int32
+	Mask []byte
+}
+
+// Select computes a key mask from the dictionary's tuples (tad_keydict_select): keep[k] = 1 iff key k's side is `side` (-1 = either) and
+// every term's mask byte at the key's code is not 0.  numKeys must be the dictionary's NumKeys.  Up to 8 terms; a code outside a term's
+// mask is an IllegalArgument.  The dictionary is only read.  The result is what State.RunKeys / State.DropKeys take.
+func (d *KeyDict) Select(terms []SelectTerm, side int32, numKeys uint64) (keep []byte, selected uint64, err error) {
+	if !hasKeySelect() {
+		return nil, 0, errors.New("tadengine: libtad_mi355x.so has no tad_keydict_select (TAD_FEATURE_KEY_SELECT)")
+	}
+	if len(terms) > 8 {
+		return nil, 0, IllegalArgument{"tadengine: Select takes at most 8 terms"}
+	}
+	// the three term arrays live in C memory for the call; the masks they name are pinned Go slices
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	ptrs := (*[8]*C.uint8_t)(C.calloc(8, C.size_t(unsafe.Sizeof(unsafe.Pointer(nil)))))
+	defer C.free(unsafe.Pointer(ptrs))
+	lens := (*[8]C.uint64_t)(C.calloc(8, 8))
+	defer C.free(unsafe.Pointer(lens))
+	colv := (*[8]C.int32_t)(C.calloc(8, 4))
+	defer C.free(unsafe.Pointer(colv))
+	for i, t := range terms {
+		colv[i] = C.int32_t(t.Col)
+		lens[i] = C.uint64_t(len(t.Mask))
+		if len(t.Mask) > 0 {
+			pin.Pin(&t.Mask[0])
+			ptrs[i] = (*C.uint8_t)(unsafe.Pointer(&t.Mask[0]))
+		}
+	}
+	keep = make([]byte, numKeys)
+	var kp *C.uint8_t
+	if numKeys > 0 {
+		kp = (*C.uint8_t)(unsafe.Pointer(&keep[0]))
+	}
+	var n C.uint64_t
+	if rc := C.tad_keydict_select(d.e.h, d.h, C.int32_t(len(terms)), &colv[0], &ptrs[0], &lens[0], C.int32_t(side), kp, C.uint64_t(numKeys),
+		C.TAD_MEM_HOST, &n); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(d.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, 0, IllegalArgument{msg}
+		}
+		return nil, 0, fmt.Errorf("tad_keydict_select: %s (code %d)", msg, int(rc))
+	}
+	return keep, uint64(n), nil
+}
+
+// RunKeys is RunWindow over the keys keyKeep selects, read-only (tad_run_state_keys): one byte per key of the state, any non-zero byte
+// selects; nil is RunWindow itself.  The rows are exactly those of RunWindow whose key is selected, with the state's own key ids; a key
+// that is not selected costs no fit.
+func (s *State) RunKeys(job Job, fromT, toT int64, keepPoints uint64, keyKeep []byte) ([]Row, error) {
+	if !hasKeySelect() {
+		return nil, errors.New("tadengine: libtad_mi355x.so has no tad_run_state_keys (TAD_FEATURE_KEY_SELECT)")
+	}
+	if !s.series || !s.times {
+		return nil, IllegalArgument{"tadengine: RunKeys needs a state made by NewStateWithTimes"}
+	}
+	if job.Algo == DBSCAN && !s.history {
+		return nil, IllegalArgument{"tadengine: RunKeys with DBSCAN needs a state made by NewStateWithTimes with history"}
+	}
+	var cj C.tad_job
+	cj.algo = C.tad_algo(job.Algo)
+	cj.start_time = C.int64_t(job.StartTime)
+	cj.end_time = C.int64_t(job.EndTime)
+	cj.dbscan_eps = C.double(job.DBSCANEps)
+	cj.dbscan_min_samples, cj.arima_maxiter = C.int32_t(job.DBSCANMinSamples), C.int32_t(job.ARIMAMaxIter)
+	id := []byte(job.ID)
+	if len(id) > 63 {
+		id = id[:63]
+	}
+	for i, b := range id {
+		cj.id[i] = C.char(b)
+	}
+	var kp *C.uint8_t
+	if len(keyKeep) > 0 {
+		kp = (*C.uint8_t)(unsafe.Pointer(&keyKeep[0]))
+	}
+	var res *C.tad_result
+	if rc := C.tad_run_state_keys(s.e.h, s.h, &cj, C.int64_t(fromT), C.int64_t(toT), C.uint64_t(keepPoints), kp, C.uint64_t(len(keyKeep)),
+		C.TAD_MEM_HOST, C.TAD_MEM_HOST, &res); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, IllegalArgument{msg}
+		}
+		return nil, fmt.Errorf("tad_run_state_keys: %s (code %d)", msg, int(rc))
+	}
+	return s.resultRows(res), nil
+}
+
+// DropKeys is DropWindow over the keys keyKeep selects, read-only (tad_drop_state_keys); keyKeep as for RunKeys.
+func (s *State) DropKeys(job Job, nSigma float64, minSamples int32, fromT, toT int64, keepPoints uint64, keyKeep []byte) ([]Row, error) {
+	if !hasKeySelect() {
+		return nil, errors.New("tadengine: libtad_mi355x.so has no tad_drop_state_keys (TAD_FEATURE_KEY_SELECT)")
+	}
+	if !s.series || !s.times {
+		return nil, IllegalArgument{"tadengine: DropKeys needs a state made by NewStateWithTimes"}
+	}
+	cj := dropJob(job, nSigma, minSamples)
+	var kp *C.uint8_t
+	if len(keyKeep) > 0 {
+		kp = (*C.uint8_t)(unsafe.Pointer(&keyKeep[0]))
+	}
+	var res *C.tad_result
+	if rc := C.tad_drop_state_keys(s.e.h, s.h, &cj, C.int64_t(fromT), C.int64_t(toT), C.uint64_t(keepPoints), kp, C.uint64_t(len(keyKeep)),
+		C.TAD_MEM_HOST, C.TAD_MEM_HOST, &res); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, IllegalArgument{msg}
+		}
+		return nil, fmt.Errorf("tad_drop_state_keys: %s (code %d)", msg, int(rc))
+	}
+	return s.resultRows(res), nil
+}

@@ -878,6 +878,56 @@ int tad_drop_select(tad_engine *e, const tad_drop_flow_columns *cols, int64_t st
                     tad_mem out_memory, tad_drop_rows **out);
 void tad_drop_rows_free(tad_engine *e, tad_drop_rows *r);
 
+/* ---- key-filtered jobs on a streaming state (TAD_FEATURE_KEY_SELECT; check tad_features() before calling these) ----
+ * The job's argument vector carries --pod-name, --pod-namespace, --pod-label, --external-ip and --svc-port-name.  On the batch path they
+ * are row predicates ahead of Stage 0 (tad_mask_rows).  Every one of them tests key columns of the mode (destinationIP in external mode,
+ * destinationServicePortName in svc mode, namespace / name / labels per side in pod mode), so on a state they are KEY selections, and the
+ * detectors are per key: the tuples are in the dictionary, the selection is computed where they live, and the window calls leave the
+ * keys that are not selected empty.  Filters that test other columns (the namespace ignore list over both sides, flowStartSeconds) are
+ * applied to the rows before they reach the state.
+ * tad_keydict_select, read-only.  key_keep[k] = 1 iff (side < 0 || key k's side == side) and, for every term t < n_terms,
+ * masks[t][tuple_k[term_col[t]]] != 0; otherwise 0 — tad_mask_rows' rule on the dictionary's records instead of on rows.  n_terms is
+ * 0 .. 8 (0: the side test alone); a column may appear in several terms; side is -1 (either), 0 (a) or 1 (b); term_col[t] is in
+ * [0, n_cols); any non-zero mask byte selects.  key_keep_len must equal the dictionary's num_keys — a stale length is refused, never a
+ * short write.  `memory` says where masks[t] and key_keep live; term_col, mask_len and the pointer array masks are host memory; host
+ * masks and a host key_keep are staged by the call; device pointers need no alignment.  *n_selected (may be NULL) = the keys selected.
+ * An empty dictionary is TAD_OK with *n_selected = 0.  TAD_ERR_INVALID_ARGUMENT, a message in tad_last_error: a NULL engine or
+ * dictionary; n_terms outside 0 .. 8 or its arrays NULL; side outside -1 .. 1; term_col out of range; a NULL mask of non-zero length;
+ * key_keep NULL with a non-zero length; key_keep_len != num_keys; and a key whose value in a term's column lies outside
+ * [0, mask_len[t]) — raised from a device flag after the kernel ran, as tad_widen_column raises an index outside its table; key_keep is
+ * then unspecified.  The dictionary is never changed.  Lock order: the dictionary, then a job context.
+ * Cost: one launch, one host synchronisation; per key one record (16 .. 80 B), one mask byte per term and one byte written; a host call
+ * stages the masks and num_keys bytes of job-context workspace, grow-only.
+ * tad_run_state_keys / tad_drop_state_keys, read-only: tad_run_state_window / tad_drop_state over the selected keys.  With W' the
+ * window's rows of those calls (same from_t, to_t, keep_points) and W'' the rows of W' whose key has key_keep[key] != 0, the call returns
+ * exactly the rows tad_run returns for W'' — equivalently the rows of the window call whose key_id is selected, in the same order, bit
+ * for bit.  Key ids are the state's own; nothing is renumbered.  key_keep == NULL with key_keep_len == 0 is the window call itself;
+ * otherwise key_keep_len must equal the state's num_keys.  The mask may be host memory (staged into job-context workspace) or device
+ * memory at any alignment (key_memory); any non-zero byte selects.  An empty selection is TAD_OK with zero rows.  Every refusal of the
+ * window call holds (tad_run_state_keys refuses TAD_ALGO_DROP, tad_drop_state_keys anything else; stale times; from_t > to_t;
+ * start_time / end_time; the narrow-column flags; parameters out of range; a state without series and times, or without history for
+ * DBSCAN), plus: key_keep NULL with a non-zero length, a length that is not num_keys, key_memory neither host nor device.  After the
+ * call, successful or not, the state is bit for bit what it was.
+ * tad_stats are over W'': rows_in = rows_used = n_points = the selected points inside the window; n_keys = the selected keys with a
+ * point there; t0 = the smallest selected time; n_anomalies, keys_no_result and the ARIMA counters (arima_fits, kalman_steps,
+ * arima_nan_fits) are what tad_run over W'' reports — a key that is not selected costs no fit; pts_mean / pts_m2 are merged from the
+ * selected keys' moments, equal to tad_run's up to rounding (as tad_run_state's are).  host_syncs is 3 whenever a
+ * mask is given and the state holds a point (the mask is a window of its own: the all-zero-window shortcut is not taken).
+ * How: the bounds kernel reads one mask byte per key; a key that is not selected gets an empty window with all its points excluded and
+ * skips both searches; the view, the moments and DBSCAN's history rule (tad_window_history_by_sort with the SELECTED window points) are
+ * the window call's.  When the selection and the window keep every point the state holds, the state's own arrays are judged.  Cost: an
+ * O(num_keys) pass of 33 B a key, then the window call's cost over the selected points; on DBSCAN's subtract side (more than half the
+ * state's points selected) the excluded points are packed and sorted as for any window.  Not yet measured on an MI355X.
+ * Lock order: the state, then a job context; calls on one state are serial; tad_job_progress finds the job by id. */
+#define TAD_FEATURE_KEY_SELECT 2048u  /* tad_keydict_select, tad_run_state_keys, tad_drop_state_keys: jobs over selected keys of a state */
+int tad_keydict_select(tad_engine *e, const tad_keydict *d, int32_t n_terms, const int32_t *term_col, const uint8_t *const *masks,
+                       const uint64_t *mask_len, int32_t side, uint8_t *key_keep, uint64_t key_keep_len, tad_mem memory,
+                       uint64_t *n_selected /* may be NULL */);
+int tad_run_state_keys(tad_engine *e, tad_state *s, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points,
+                       const uint8_t *key_keep, uint64_t key_keep_len, tad_mem key_memory, tad_mem out_memory, tad_result **out);
+int tad_drop_state_keys(tad_engine *e, tad_state *s, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points,
+                        const uint8_t *key_keep, uint64_t key_keep_len, tad_mem key_memory, tad_mem out_memory, tad_result **out);
+
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).
  * tad_job_progress (ABI 12): the job whose tad_job.id equals `id`; *total = 0 when no such job is in flight (finished or not yet

@@ -7,6 +7,7 @@ Product layout:
   engine.py             TadEngine: columnar batches in, anomalous points out
   anomaly_detection.py  host-side mirror of the reference job's interface
                         (plugins/anomaly-detection/anomaly_detection.py)
+  stream_detection.py   the same jobs, name filters included, answered from a streaming state fed as rows arrive
 There is no CPU fallback: every compute entry point goes through the HIP library and fails
 loudly if it (or a GPU) is missing.
 """

@@ -32,6 +32,7 @@ TAD_FEATURE_KEY_DICT = 128                   # tad_features() bit: tad_keydict, 
 TAD_FEATURE_KEY_RETIRE = 256                 # tad_features() bit: tad_state_compact / tad_keydict_compact, dead keys dropped and the rest renumbered
 TAD_FEATURE_STATE_DROP = 512                 # tad_features() bit: tad_drop_state / tad_drop_stream, the drop detector on a series state
 TAD_FEATURE_DROP_ROWS = 1024                 # tad_features() bit: tad_drop_select, flow rows -> the drop job's (endpoint, direction, day, count) rows
+TAD_FEATURE_KEY_SELECT = 2048                # tad_features() bit: tad_keydict_select, tad_run_state_keys, tad_drop_state_keys: jobs over selected keys of a state
 
 
 class Plan(C.Structure):
@@ -192,6 +193,9 @@ SYMBOLS = {
     "tad_state_compact": (C.c_int, [C.c_void_p, C.c_void_p, i64, C.c_void_p, C.c_int, C.POINTER(CompactStats)]),
     "tad_keydict_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
     "tad_drop_state": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_int, C.POINTER(C.POINTER(Result))]),
+    "tad_keydict_select": (C.c_int, [C.c_void_p, C.c_void_p, i32, C.POINTER(i32), C.POINTER(C.c_void_p), C.POINTER(u64), i32, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
+    "tad_run_state_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_void_p, u64, C.c_int, C.c_int, C.POINTER(C.POINTER(Result))]),
+    "tad_drop_state_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_void_p, u64, C.c_int, C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_drop_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_drop_select": (C.c_int, [C.c_void_p, C.POINTER(DropFlowColumns), i64, i64, C.c_int, C.POINTER(C.POINTER(DropRows))]),
     "tad_drop_rows_free": (None, [C.c_void_p, C.POINTER(DropRows)]),

@@ -1,6 +1,6 @@
 // tad_capi.cpp — what the entry points of include/tad.h share (key buffers, the rows result and its epilogue, the moments' merge), the batches
 // on a streaming state that the job's count pass runs (history, series, merge, ARIMA, DROP), and the state calls: tad_run_state,
-// tad_run_state_window, tad_drop_state, tad_drop_stream, tad_state_merge.  The batch job itself (run_job_locked: lattice, Stage 0, count,
+// tad_run_state_window, tad_drop_state, their *_keys forms, tad_drop_stream, tad_state_merge.  The batch job itself (run_job_locked: lattice, Stage 0, count,
 // retries) is tad_capi_job.cpp; the life of a tad_state is tad_capi_state.cpp.
 #include "tad_engine.h"
 
@@ -695,8 +695,9 @@ static WinKeys win_keys(JobCtx *e, uint64_t K) {
   return w;
 }
 
-// 1. every key's bounds; the view's offsets and the chunk offsets; *P = the window's point total
-static int window_bounds(JobCtx *e, const tad_state *st, int64_t from_t, int64_t to_t, uint64_t keep_points, uint64_t *P) {
+// 1. every key's bounds; the view's offsets and the chunk offsets; *P = the window's point total.  keep (device, K bytes, or NULL): the
+// key selection of tad_run_state_keys / tad_drop_state_keys — a key that is not selected gets an empty window
+static int window_bounds(JobCtx *e, const tad_state *st, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *keep, uint64_t *P) {
   hipStream_t s = e->stream;
   const uint64_t K = st->K;
   const StateView whole = series_view(st, st->cur);
@@ -705,7 +706,7 @@ static int window_bounds(JobCtx *e, const tad_state *st, int64_t from_t, int64_t
   if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K) * sizeof(unsigned long long))) != TAD_OK) return rc;
   const WinKeys w = win_keys(e, K);
   unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
-  launch_win_bounds(s, K, whole.soff, whole.st, (long long)from_t, (long long)to_t, keep_points, w.wbeg, w.wlen, w.ecnt, w.chunks);
+  launch_win_bounds(s, K, whole.soff, whole.st, (long long)from_t, (long long)to_t, keep_points, keep, w.wbeg, w.wlen, w.ecnt, w.chunks);
   launch_scan(s, w.wlen, w.woff, K, scratch);
   launch_scan(s, w.chunks, w.coff, K, scratch);
   HIP_TRY(e, hipGetLastError());
@@ -778,7 +779,7 @@ int tad_run_state_window(tad_engine *eng, tad_state *st, const tad_job *job, int
   const uint64_t S = whole.P;
   if (S == 0 || (from_t == 0 && to_t == 0 && keep_points == 0)) return run_view_locked(e, whole, job, out_memory, out, 0);
   uint64_t P = 0;
-  if ((rc = window_bounds(e, st, from_t, to_t, keep_points, &P)) != TAD_OK) return rc;
+  if ((rc = window_bounds(e, st, from_t, to_t, keep_points, nullptr, &P)) != TAD_OK) return rc;
   if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1);   // every key is whole: the state's own arrays, no view
   const bool subtract = job->algo == TAD_ALGO_DBSCAN && P != 0 && !win_hist_by_sort(P, S);
   StateView v;
@@ -816,11 +817,76 @@ int tad_drop_state(tad_engine *eng, tad_state *st, const tad_job *job, int64_t f
   const uint64_t S = whole.P;
   if (S == 0 || (from_t == 0 && to_t == 0 && keep_points == 0)) return run_view_locked(e, whole, job, out_memory, out, 0);
   uint64_t P = 0;
-  if ((rc = window_bounds(e, st, from_t, to_t, keep_points, &P)) != TAD_OK) return rc;
+  if ((rc = window_bounds(e, st, from_t, to_t, keep_points, nullptr, &P)) != TAD_OK) return rc;
   if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1);   // every key is whole: the state's own arrays, no view
   StateView v;
   if ((rc = window_gather(e, st, job, P, false, &v)) != TAD_OK) return rc;   // values and times only: DROP reads no moments, no history
   return run_view_locked(e, v, job, out_memory, out, 1);
+}
+
+// tad.h: tad_run_state_window / tad_drop_state over the keys key_keep selects, once the job is checked (the window calls' own checks, under
+// the *_keys name).  A key whose byte is 0 is left empty by window_bounds, and the rest of the call treats it as any key the window left
+// empty.  The mask is a window of its own, so with one the "no window at all" shortcut is not taken; P == S still is, since then every
+// point the state holds is selected.  Without a mask (NULL, length 0) this is the window call, step for step.  DROP: values and times only, no moments, no history.
+static int window_keys_call(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *key_keep,
+                            uint64_t key_keep_len, tad_mem key_memory, tad_mem out_memory, tad_result **out, const char *who) {
+  if (from_t != 0 && to_t != 0 && from_t > to_t) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: from_t is later than to_t", who);
+  if (!key_keep && key_keep_len != 0)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep is NULL with a length of %llu", who, (unsigned long long)key_keep_len);
+  if (key_keep && key_memory != TAD_MEM_HOST && key_memory != TAD_MEM_DEVICE)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep must be in host or device memory", who);
+  StateCall call(eng, st);
+  if (st->times_stale)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the series was imported without its times (tad_state_import_times)", who);
+  if (key_keep && key_keep_len != st->K)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep has %llu entries, the state holds %llu keys", who, (unsigned long long)key_keep_len,
+                (unsigned long long)st->K);
+  int rc;
+  if ((rc = call.enter(who, job->id, job->algo == TAD_ALGO_ARIMA)) != TAD_OK) return rc;
+  JobCtx *e = call.e;
+  if ((rc = run_view_begin(e, st->K)) != TAD_OK) return rc;
+  const StateView whole = series_view(st, st->cur);
+  const uint64_t S = whole.P;
+  if (S == 0 || (!key_keep && from_t == 0 && to_t == 0 && keep_points == 0)) return run_view_locked(e, whole, job, out_memory, out, 0);
+  const uint8_t *d_keep = key_keep;
+  if (key_keep && key_memory == TAD_MEM_HOST) {   // staged: only window_bounds reads it
+    if ((rc = ensure(e, e->in_key, (size_t)st->K)) != TAD_OK) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->in_key.p, key_keep, st->K, hipMemcpyHostToDevice, e->stream));
+    d_keep = static_cast<const uint8_t *>(e->in_key.p);
+  }
+  uint64_t P = 0;
+  if ((rc = window_bounds(e, st, from_t, to_t, keep_points, d_keep, &P)) != TAD_OK) return rc;
+  if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1);   // every key is selected and whole: the state's own arrays, no view
+  const bool subtract = job->algo == TAD_ALGO_DBSCAN && P != 0 && !win_hist_by_sort(P, S);   // (P: the SELECTED window points)
+  StateView v;
+  if ((rc = window_gather(e, st, job, P, subtract, &v)) != TAD_OK) return rc;
+  return run_view_locked(e, v, job, out_memory, out, 1);
+}
+
+int tad_run_state_keys(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *key_keep,
+                       uint64_t key_keep_len, tad_mem key_memory, tad_mem out_memory, tad_result **out) {
+  const int rc = check_state_job(eng, st, job, out, "tad_run_state_keys", "the window is from_t / to_t / keep_points");
+  if (rc != TAD_OK) return rc;
+  return window_keys_call(eng, st, job, from_t, to_t, keep_points, key_keep, key_keep_len, key_memory, out_memory, out, "tad_run_state_keys");
+}
+
+int tad_drop_state_keys(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *key_keep,
+                        uint64_t key_keep_len, tad_mem key_memory, tad_mem out_memory, tad_result **out) {
+  const char *who = "tad_drop_state_keys";
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!st || !job || !out) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: state, job and out must not be NULL", who);
+  *out = nullptr;
+  if (job->algo != TAD_ALGO_DROP)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the algorithm must be DROP (tad_run_state_keys judges EWMA, DBSCAN and ARIMA)", who);
+  if (job->start_time != 0 || job->end_time != 0)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: start_time / end_time must be 0: the window is from_t / to_t / keep_points", who);
+  if (job->flags & (TAD_FLAG_KEY_U32 | TAD_FLAG_TIME_U32))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 describe input columns; there are none", who);
+  if (!(job->drop_nsigma >= 0.0) || job->drop_min_samples < 0)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: detector parameter out of range", who);
+  if (!st->series || !st->times)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES)", who);
+  return window_keys_call(eng, st, job, from_t, to_t, keep_points, key_keep, key_keep_len, key_memory, out_memory, out, who);
 }
 
 // tad.h: the periodical drop job, one batch.  The batch runs as a stream batch of the EWMA kind does (run_job_locked: Stage 0, the count

@@ -358,6 +358,74 @@ int tad_keydict_import(tad_engine *eng, tad_keydict *d, uint64_t n_keys, const i
   return TAD_OK;
 }
 
+// tad.h: a key mask from the dictionary's tuples (kernel: k_kd_select).  The dictionary is only read.
+int tad_keydict_select(tad_engine *eng, const tad_keydict *d, int32_t n_terms, const int32_t *term_col, const uint8_t *const *masks, const uint64_t *mask_len,
+                       int32_t side, uint8_t *key_keep, uint64_t key_keep_len, tad_mem memory, uint64_t *n_selected) {
+  const char *who = "tad_keydict_select";
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!d || n_terms < 0 || n_terms > kKdMaxTerms || (n_terms && (!term_col || !masks || !mask_len)) || side < -1 || side > 1 || (key_keep_len && !key_keep) ||
+      (memory != TAD_MEM_HOST && memory != TAD_MEM_DEVICE))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bad arguments (dictionary, 0..%d terms, side -1 / 0 / 1, key_keep buffer in host or device memory)", who,
+                kKdMaxTerms);
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  const uint64_t K = d->K;
+  for (int t = 0; t < n_terms; ++t) {
+    if (term_col[t] < 0 || term_col[t] >= d->n_cols)
+      return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: term %d names column %d, the dictionary holds tuples of %d", who, t, (int)term_col[t], d->n_cols);
+    if (mask_len[t] && !masks[t]) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the mask of term %d is NULL", who, t);
+  }
+  if (key_keep_len != K)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep has %llu entries, the dictionary holds %llu keys", who, (unsigned long long)key_keep_len,
+                (unsigned long long)K);
+  if (n_selected) *n_selected = 0;
+  if (K == 0) return TAD_OK;
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "%s: no job context available", who);
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  const bool host = memory == TAD_MEM_HOST;
+  // scratch: sp_comp_a = the selected count | flags; a host call's masks in in_key and its key_keep in in_key2
+  size_t stage_in = 0;
+  if (host)
+    for (int t = 0; t < n_terms; ++t) stage_in += up256(mask_len[t]);
+  const size_t need = 256 + (host ? stage_in + up256(K) : 0);
+  if (need > e->ws_limit)
+    return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu", who, (unsigned long long)need, (unsigned long long)e->ws_limit);
+  int rc;
+  if ((rc = ensure(e, e->sp_comp_a, 256)) != TAD_OK) return rc;
+  if (host && ((stage_in && (rc = ensure(e, e->in_key, stage_in)) != TAD_OK) || (rc = ensure(e, e->in_key2, up256(K))) != TAD_OK)) return rc;
+  unsigned long long *n_sel_dev = static_cast<unsigned long long *>(e->sp_comp_a.p);
+  uint32_t *flags_dev = reinterpret_cast<uint32_t *>(n_sel_dev + 1);
+  KdSelect q{};
+  q.n_terms = n_terms;
+  q.side = side;
+  unsigned char *p = host && stage_in ? static_cast<unsigned char *>(e->in_key.p) : nullptr;
+  for (int t = 0; t < n_terms; ++t) {
+    q.col[t] = term_col[t];
+    q.mask_len[t] = mask_len[t];
+    q.mask[t] = masks[t];
+    if (host && mask_len[t]) {
+      HIP_TRY(e, hipMemcpyAsync(p, masks[t], mask_len[t], hipMemcpyHostToDevice, s));
+      q.mask[t] = p;
+      p += up256(mask_len[t]);
+    }
+  }
+  uint8_t *d_keep = host ? static_cast<uint8_t *>(e->in_key2.p) : key_keep;
+  HIP_TRY(e, hipMemsetAsync(n_sel_dev, 0, 16, s));
+  launch_kd_select(s, d->keys, d->n_cols, K, q, d_keep, n_sel_dev, flags_dev);
+  unsigned long long n_sel = 0;
+  uint32_t flags = 0;
+  HIP_TRY(e, hipMemcpyAsync(&n_sel, n_sel_dev, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(&flags, flags_dev, 4, hipMemcpyDeviceToHost, s));
+  if (host) HIP_TRY(e, hipMemcpyAsync(key_keep, d_keep, K, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  if (flags & KD_FLAG_BAD_CODE) return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: a key's value lies outside the mask of its term (key_keep unspecified)", who);
+  if (n_selected) *n_selected = n_sel;
+  return TAD_OK;
+}
+
 // tad.h: the renumbering of tad_state_compact applied to the dictionary (kernels in tad_compact.hip).  The check runs first and alone;
 // then fresh records and a fresh table are filled and swapped in.
 int tad_keydict_compact(tad_engine *eng, tad_keydict *d, const uint64_t *remap, uint64_t remap_len, tad_mem remap_memory, uint64_t *num_keys) {

@@ -457,9 +457,10 @@ struct StateView {
 // ---- tad_run_state_window (tad_window.hip): the view of every key's points inside a window ----
 // per key: wbeg = the window's first point inside the key's segment, wlen = its points, ecnt = the key's points outside it (prefix +
 // suffix), chunks = the wavefronts of the key's old segment in launch_win_gather / launch_hist_subtract (at least 1).  from_t / to_t 0 = no bound on
-// that side (flow_end_s >= from_t, < to_t); keep_points 0 = no count rule, else the newest keep_points of the rest
+// that side (flow_end_s >= from_t, < to_t); keep_points 0 = no count rule, else the newest keep_points of the rest.  keep != NULL (K bytes):
+// a key with keep[k] == 0 gets wlen = 0 and ecnt = its length
 void launch_win_bounds(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, long long from_t, long long to_t,
-                       uint64_t keep_points, uint32_t *wbeg, uint32_t *wlen, uint32_t *ecnt, uint32_t *chunks);
+                       uint64_t keep_points, const uint8_t *keep, uint32_t *wbeg, uint32_t *wlen, uint32_t *ecnt, uint32_t *chunks);
 // every key's window values and times to woff (the scan of wlen); ev != NULL: the excluded values, prefix then suffix, packed at eoff
 // (the scan of ecnt).  chunks_bound: trim_chunks_bound(K, the state's points)
 void launch_win_gather(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *soff,
@@ -706,7 +707,7 @@ struct KdBatch {                    // the key tuples of one batch (device point
   uint32_t sides;                   // 1 or 2
 };
 static constexpr uint32_t kKdMaxProbe = 32;     // a claim that probed further asks the host for a larger table
-enum : uint32_t { KD_FLAG_CLUSTER = 1u, KD_FLAG_DUPLICATE = 2u, KD_FLAG_BAD_ROW = 4u };
+enum : uint32_t { KD_FLAG_CLUSTER = 1u, KD_FLAG_DUPLICATE = 2u, KD_FLAG_BAD_ROW = 4u, KD_FLAG_BAD_CODE = 8u };
 int kd_stride(int n_cols);          // 8-byte words of one key record: side + columns, padded to an even count
 // every kept virtual row looks its tuple up in table[slots] / keys (K records).  miss != NULL: hits write their id, misses raise miss[v] and
 // are counted in *n_miss (zeroed by the caller), rows that are not kept get TAD_KEY_SKIP; miss == NULL: a miss is TAD_KEY_SKIP too
@@ -721,6 +722,18 @@ void launch_kd_fix(hipStream_t s, const uint8_t *miss, const uint64_t *loc_a, co
 // records 0 .. K into an empty table; check_duplicates: KD_FLAG_DUPLICATE when two records hold the same tuple
 void launch_kd_rehash(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, unsigned long long *table, uint64_t slots, uint32_t *flags,
                       bool check_duplicates);
+// tad_keydict_select: the terms of a key selection (mask: device pointers; a term past n_terms is all zero)
+static constexpr int kKdMaxTerms = 8;
+struct KdSelect {
+  const uint8_t *mask[kKdMaxTerms];
+  unsigned long long mask_len[kKdMaxTerms];
+  int32_t col[kKdMaxTerms];
+  int32_t n_terms, side;            // side < 0: either side
+};
+// keep[k] = 1 iff record k's side is q.side (or q.side < 0) and every term's mask byte at the record's value is not 0, else 0;
+// *n_sel += the selected keys, *flags |= KD_FLAG_BAD_CODE for a value outside its mask (both zeroed by the caller)
+void launch_kd_select(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, const KdSelect &q, uint8_t *keep, unsigned long long *n_sel,
+                      uint32_t *flags);
 
 // ---- retiring dead keys: tad_state_compact / tad_keydict_compact (tad_compact.hip) ----
 struct CompactCounters {   // one 64-byte block on the device, zeroed per call

@@ -186,6 +186,48 @@ __global__ __launch_bounds__(kKdBlock) void k_kd_rehash(const unsigned long long
   }
 }
 
+// tad_keydict_select: one lane per key.  keep[k] = 1 iff the key's side is the wanted one (q.side < 0: either) and, for every term t, the
+// byte of mask[t] at the key's value in column col[t] is not 0 — tad_mask_rows' rule on the records instead of on rows.  The record is
+// loaded whole (kd_load_record) before any mask byte is read; the term's column is picked by compares, so the record stays in registers;
+// the loop over the terms stays rolled (unrolled, eight pointers, lengths and columns at once spill scalar registers).
+// A value outside [0, mask_len[t]) raises KD_FLAG_BAD_CODE and reads nothing.  The selected keys are counted per wavefront, summed per
+// workgroup in LDS, one atomic per workgroup.
+__global__ __launch_bounds__(kKdBlock) void k_kd_select(const unsigned long long *__restrict__ keys, int pairs, uint64_t K, KdSelect q, uint8_t *__restrict__ keep,
+                                                        unsigned long long *__restrict__ n_sel, uint32_t *__restrict__ flags) {
+  __shared__ uint32_t s_cnt[kKdBlock / 64];
+  uint32_t mine = 0;
+  for (uint64_t k = (uint64_t)blockIdx.x * kKdBlock + threadIdx.x; k < K; k += (uint64_t)gridDim.x * kKdBlock) {
+    ulonglong2 w[kKdMaxPairs];
+    kd_load_record(keys, k, pairs, w);
+    bool ok = q.side < 0 || w[0].x == (uint64_t)q.side;
+    bool bad = false;
+#pragma unroll 1
+    for (int t = 0; t < q.n_terms; ++t) {      // (uniform: the terms are kernel arguments)
+      const int col = q.col[t];
+      uint64_t v = 0;
+#pragma unroll
+      for (int c = 0; c < kFzMaxCols; ++c)
+        if (col == c) v = kd_word(w, c + 1);
+      const bool in = v < q.mask_len[t];       // (a negative value is a huge unsigned one)
+      bad |= !in;
+      const uint8_t b = in ? q.mask[t][v] : (uint8_t)0;
+      ok = ok & (b != 0);
+    }
+    if (bad) atomicOr(flags, KD_FLAG_BAD_CODE);
+    keep[k] = ok ? 1 : 0;
+    mine += ok ? 1u : 0u;
+  }
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
+  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t total = 0;
+#pragma unroll
+    for (int i = 0; i < kKdBlock / 64; ++i) total += s_cnt[i];
+    if (total) atomicAdd(n_sel, (unsigned long long)total);
+  }
+}
+
 int kd_stride(int n_cols) { return (n_cols + 2) & ~1; }      // side + columns, padded to an even number of 8-byte words
 
 static dim3 kd_grid(uint64_t items) { const uint64_t b = (items + kKdBlock - 1) / kKdBlock; return dim3((unsigned)(b < 16384 ? (b ? b : 1) : 16384)); }
@@ -213,6 +255,12 @@ void launch_kd_rehash(hipStream_t s, const unsigned long long *keys, int n_cols,
   const int pairs = kd_stride(n_cols) / 2;
   if (check_duplicates) hipLaunchKernelGGL(k_kd_rehash<true>, kd_grid(K), dim3(kKdBlock), 0, s, keys, pairs, n_cols, K, table, slots - 1, flags);
   else hipLaunchKernelGGL(k_kd_rehash<false>, kd_grid(K), dim3(kKdBlock), 0, s, keys, pairs, n_cols, K, table, slots - 1, flags);
+}
+
+void launch_kd_select(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, const KdSelect &q, uint8_t *keep, unsigned long long *n_sel,
+                      uint32_t *flags) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_kd_select, kd_grid(K), dim3(kKdBlock), 0, s, keys, kd_stride(n_cols) / 2, K, q, keep, n_sel, flags);
 }
 
 // one kernel of this translation unit: tad_engine_create resolves it so that the unit's code object is loaded before the first batch

@@ -283,7 +283,9 @@ __global__ __launch_bounds__(kWBlock) void k_win_keys(uint64_t K, const unsigned
 //      count rule.  Per key: the window's first point (relative to the segment), its length, the excluded count (prefix + suffix) and
 //      the wavefronts of the copy (the key's OLD segment in chunks of kHistChunk: k_hist_subtract walks the history by the same chunks).
 //      The scan of the lengths is woff, and woff[K] the window's point total; the excluded total is the state's points minus that.
-//      Traffic: 16 B of offsets and 16 B of results per key, plus 2 x log2(len) dependent 8-byte loads.
+//      Traffic: 16 B of offsets and 16 B of results per key, plus 2 x log2(len) dependent 8-byte loads.  With a key mask
+//      (tad_run_state_keys / tad_drop_state_keys: keep[k], one byte per key) a key that is not selected gets an empty window with all
+//      its points excluded and searches nothing; everything after this kernel treats it as a key the window left empty.
 //   2. k_win_gather, one wavefront per chunk, lanes on consecutive points (coalesced 8-byte loads and stores): the interior range of
 //      values and times to woff[k]; with `ev` the excluded values, prefix then suffix, packed at eoff[k].  Without `ev` a wavefront
 //      touches only its part of the interior range.  Model: 32 B per window point (value and time, read and written) plus 16 B per
@@ -301,11 +303,19 @@ __device__ __forceinline__ unsigned long long win_lower_t(const long long *__res
 }
 
 __global__ __launch_bounds__(kWBlock) void k_win_bounds(uint64_t K, const unsigned long long *__restrict__ soff, const long long *__restrict__ st,
-                                                       long long from_t, long long to_t, uint64_t keep_points, uint32_t *__restrict__ wbeg,
-                                                       uint32_t *__restrict__ wlen, uint32_t *__restrict__ ecnt, uint32_t *__restrict__ chunks) {
+                                                       long long from_t, long long to_t, uint64_t keep_points, const uint8_t *__restrict__ keep,
+                                                       uint32_t *__restrict__ wbeg, uint32_t *__restrict__ wlen, uint32_t *__restrict__ ecnt,
+                                                       uint32_t *__restrict__ chunks) {
   const uint64_t k = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
   if (k >= K) return;
   const unsigned long long o0 = soff[k], o1 = soff[k + 1], len = o1 - o0;
+  if (keep != nullptr && keep[k] == 0) {   // a key that is not selected (tad_run_state_keys): no window point, every point excluded, no search
+    wbeg[k] = 0;
+    wlen[k] = 0;
+    ecnt[k] = (uint32_t)len;
+    chunks[k] = len > kHistChunk ? (uint32_t)((len + kHistChunk - 1) / kHistChunk) : 1u;   // (k_hist_subtract walks the history by these)
+    return;
+  }
   unsigned long long lo = from_t != 0 ? win_lower_t(st, o0, o1, from_t) - o0 : 0ull;          // the first point at or after from_t
   const unsigned long long hi = to_t != 0 ? win_lower_t(st, o0 + lo, o1, to_t) - o0 : len;     // the first point at or after to_t (>= lo)
   if (keep_points != 0 && hi - lo > keep_points) lo = hi - keep_points;
@@ -419,9 +429,9 @@ bool win_hist_by_sort(uint64_t window_points, uint64_t state_points) {
 }
 
 void launch_win_bounds(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, long long from_t, long long to_t,
-                       uint64_t keep_points, uint32_t *wbeg, uint32_t *wlen, uint32_t *ecnt, uint32_t *chunks) {
+                       uint64_t keep_points, const uint8_t *keep, uint32_t *wbeg, uint32_t *wlen, uint32_t *ecnt, uint32_t *chunks) {
   if (K == 0) return;
-  hipLaunchKernelGGL(k_win_bounds, dim3(win_blocks(K)), dim3(kWBlock), 0, s, K, soff, st, from_t, to_t, keep_points, wbeg, wlen, ecnt, chunks);
+  hipLaunchKernelGGL(k_win_bounds, dim3(win_blocks(K)), dim3(kWBlock), 0, s, K, soff, st, from_t, to_t, keep_points, keep, wbeg, wlen, ecnt, chunks);
 }
 
 void launch_win_gather(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *soff,

@@ -149,6 +149,7 @@ class PeriodicalDropDetection:
         self._dates = False               # the feeds carried dates (rows report dates) or day numbers
         self._seconds = False             # the state's times are epoch seconds (feed_flows) rather than day numbers (feed)
         self._dict = None                 # feed_flows: the (kind, ns, name, direction) -> key id dictionary on the device
+        self._namespaces = []             # feed_flows: the namespace dictionary of the newest feed (code -> string)
 
     @property
     def state(self):
@@ -209,6 +210,7 @@ class PeriodicalDropDetection:
         if self._dict is None:
             self._dict = eng.key_dict(4)
         self._dates = self._seconds = True
+        self._namespaces = [str(x) for x in dictionaries["pod_ns"]]
         key, _, first, _ = self._dict.encode(rows.tuple_columns())
         self._keys += _decode_keys(eng, rows, first, dictionaries)
         n_keys = max(len(self._keys), 1)
@@ -219,11 +221,28 @@ class PeriodicalDropDetection:
         res = eng.drop_stream(self._state, key, rows["day_s"], rows["count"], agg_flow="svc", value_op="sum")
         return self._rows(res, "periodical", detection_id)
 
-    def window(self, from_date=None, to_date=None, detection_id=None):
+    def window(self, from_date=None, to_date=None, detection_id=None, direction=None, namespace=None):
         """The anomalous days with from_date <= date < to_date (None = no bound) of everything kept, each partition judged over its days
-        inside the range: the rows of an "initial" job over those days."""
+        inside the range: the rows of an "initial" job over those days.  direction ("ingress" / "egress") and namespace (the pod
+        endpoints of that namespace) narrow the job to the partitions they name — an instance fed flow rows only: the partitions are
+        selected on its (kind, ns, name, direction) dictionary (KeyDict.select) and only they are judged (TadEngine.drop_state_keys);
+        the rows are those of the unfiltered call for these partitions."""
+        if (direction is not None or namespace is not None) and self._dict is None and (self._keys or self._state is not None):
+            raise ValueError("direction / namespace select partitions on the device dictionary of an instance fed flow rows (feed_flows); "
+                             "this one is fed daily counts (feed)")
+        if direction is not None and direction not in DIRECTIONS:
+            raise ValueError("direction should be 'ingress' or 'egress'")
         if self._state is None:
             return []
         bound = lambda d: 0 if d is None else int(_days([d])[0][0]) * (86400 if self._seconds else 1)
-        res = self._engine.drop_state(self._state, bound(from_date), bound(to_date))
+        if direction is None and namespace is None:
+            res = self._engine.drop_state(self._state, bound(from_date), bound(to_date))
+            return self._rows(res, "periodical", detection_id)
+        terms = []
+        if direction is not None:
+            terms.append((3, np.arange(2) == DIRECTIONS.index(direction)))
+        if namespace is not None:          # a pod endpoint (kind 1) whose namespace code names this string
+            terms += [(0, np.array([0, 1], np.uint8)), (1, np.asarray([s == namespace for s in self._namespaces], dtype=np.uint8))]
+        keep, _ = self._dict.select(terms, out="device")
+        res = self._engine.drop_state_keys(self._state, keep, bound(from_date), bound(to_date))
         return self._rows(res, "periodical", detection_id)

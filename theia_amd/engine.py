@@ -626,6 +626,55 @@ class KeyDict:
         eng._check(rc)
         return key1, key2
 
+    def select(self, terms=(), side=None, out="device"):
+        """A key mask from the dictionary's tuples (tad_keydict_select): keep[k] = 1 iff key k's side is `side` (None = either) and, for
+        every term (col, mask), mask[tuple_k[col]] != 0 — TadEngine.mask_rows' rule on the keys instead of on rows.  Up to 8 terms; a
+        column may appear in several; each mask is a uint8 array indexed by the column's codes (numpy arrays, or DeviceArrays of bytes
+        when out == "device").  Returns (keep, n_selected): keep a DeviceArray of num_keys bytes (out="device": what run_state_keys
+        takes without a copy) or a numpy uint8 array (out="host").  A key whose code lies outside a term's mask is refused; the
+        dictionary is only read."""
+        eng = self._engine
+        if not (getattr(eng._lib, "tad_features", None) and eng._lib.tad_features() & capi.TAD_FEATURE_KEY_SELECT):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_keydict_select (TAD_FEATURE_KEY_SELECT)")
+        if out not in ("device", "host"):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "KeyDict.select: out must be device or host")
+        terms = list(terms)
+        dev = out == "device"
+        keepalive, ptrs, lens = [], [], []
+        for _, m in terms:
+            if isinstance(m, DeviceArray):
+                if not dev:
+                    raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "KeyDict.select: device masks need out=\"device\"")
+                ptrs.append(m.ptr)
+                lens.append(m.n * np.dtype(m.dtype).itemsize)
+                continue
+            a = np.ascontiguousarray(np.asarray(m).astype(np.uint8, copy=False)).reshape(-1)
+            if dev and a.size:
+                d = DeviceArray.from_host(eng, np.frombuffer(a.tobytes() + b"\0" * (-a.size % 8), dtype=np.uint64))
+                keepalive.append(d)
+                ptrs.append(d.ptr)
+            else:
+                keepalive.append(a)
+                ptrs.append(a.ctypes.data if a.size else None)
+            lens.append(a.size)
+        nt = len(terms)
+        K = self.num_keys()
+        if dev:
+            keep = DeviceArray(eng, (K + 7) // 8 if K else 1, np.uint64)
+            keep_ptr = keep.ptr
+        else:
+            keep = np.zeros(K, np.uint8)
+            keep_ptr = keep.ctypes.data if K else None
+        n_sel = capi.u64()
+        rc = eng._lib.tad_keydict_select(eng._h, self._h, nt, (capi.i32 * max(nt, 1))(*[int(c) for c, _ in terms]),
+                                         (C.c_void_p * max(nt, 1))(*ptrs), (capi.u64 * max(nt, 1))(*lens), -1 if side is None else int(side),
+                                         keep_ptr if K else None, K, capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST, C.byref(n_sel))
+        del keepalive
+        eng._check(rc)
+        if dev:
+            keep = keep.view(0, K, np.uint8)
+        return keep, int(n_sel.value)
+
     def num_keys(self):
         """keys held (tad_keydict_num_keys)"""
         n = capi.u64()
@@ -940,6 +989,53 @@ class TadEngine:
         rc = self._lib.tad_drop_stream(self._h, state._h, C.byref(job), C.byref(cols),
                                        capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
         del keep
+        self._check(rc)
+        return TadResult(self, res)
+
+    # ---- the window calls over selected keys (tad_run_state_keys / tad_drop_state_keys) ----
+    def _need_key_select(self, what):
+        if not (getattr(self._lib, "tad_features", None) and self._lib.tad_features() & capi.TAD_FEATURE_KEY_SELECT):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no %s (TAD_FEATURE_KEY_SELECT)" % what)
+
+    @staticmethod
+    def _key_mask(key_keep):
+        """-> (pointer, length, tad_mem, what must stay alive) of a key mask: None, a DeviceArray of bytes, or anything numpy reads"""
+        if key_keep is None:
+            return None, 0, capi.TAD_MEM_HOST, None
+        if isinstance(key_keep, DeviceArray):
+            return key_keep.ptr, key_keep.n * np.dtype(key_keep.dtype).itemsize, capi.TAD_MEM_DEVICE, key_keep
+        a = np.ascontiguousarray(np.asarray(key_keep).astype(np.uint8, copy=False)).reshape(-1)
+        return (a.ctypes.data if a.size else None), a.size, capi.TAD_MEM_HOST, a
+
+    def run_state_keys(self, state, key_keep, from_t=0, to_t=0, keep_points=0, algo="EWMA", alpha=0.0, eps=0.0, min_samples=0, maxiter=0,
+                       emit_all=False, out="host", job_id=""):
+        """run_state_window over the keys `key_keep` selects, read-only (tad_run_state_keys): key_keep has one byte per key of the state
+        (a numpy array, or a DeviceArray such as KeyDict.select returns; any non-zero byte selects; None = every key).  Exactly the rows
+        of run_state_window whose key is selected, with the state's own key ids; the stats and the ARIMA counters are those of a job
+        over the selected points alone."""
+        if algo not in capi.TAD_ALGO:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "algo must be EWMA, ARIMA, DBSCAN or DROP")
+        self._need_key_select("tad_run_state_keys")
+        ptr, n, mem, alive = self._key_mask(key_keep)
+        job = capi.Job(algo=capi.TAD_ALGO[algo], ewma_alpha=float(alpha), dbscan_eps=float(eps), dbscan_min_samples=int(min_samples),
+                       arima_maxiter=int(maxiter), flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
+        res = C.POINTER(capi.Result)()
+        rc = self._lib.tad_run_state_keys(self._h, state._h, C.byref(job), int(from_t), int(to_t), int(keep_points), ptr, n, mem,
+                                          capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
+        del alive
+        self._check(rc)
+        return TadResult(self, res)
+
+    def drop_state_keys(self, state, key_keep, from_t=0, to_t=0, keep_points=0, nsigma=0.0, min_samples=0, emit_all=False, out="host", job_id=""):
+        """drop_state over the keys `key_keep` selects, read-only (tad_drop_state_keys); key_keep as for run_state_keys"""
+        self._need_key_select("tad_drop_state_keys")
+        ptr, n, mem, alive = self._key_mask(key_keep)
+        job = capi.Job(algo=capi.TAD_ALGO["DROP"], drop_nsigma=float(nsigma), drop_min_samples=int(min_samples),
+                       flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
+        res = C.POINTER(capi.Result)()
+        rc = self._lib.tad_drop_state_keys(self._h, state._h, C.byref(job), int(from_t), int(to_t), int(keep_points), ptr, n, mem,
+                                           capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
+        del alive
         self._check(rc)
         return TadResult(self, res)
 

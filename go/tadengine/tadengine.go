@@ -1867,3 +1867,228 @@ func (s *State) DropKeys(job Job, nSigma float64, minSamples int32, fromT, toT i
 	}
 	return s.resultRows(res), nil
 }
+
+var stringDictOnce sync.Once
+var stringDictOK bool
+
+// hasStringDict: the library knows the persistent string dictionary (tad_features); an older one would not export the calls.
+func hasStringDict() bool {
+	stringDictOnce.Do(func() { stringDictOK = C.tad_features()&C.TAD_FEATURE_STRING_DICT != 0 })
+	return stringDictOK
+}
+
+var errNoStringDict = errors.New("tadengine: libtad_mi355x.so has no string dictionary (TAD_FEATURE_STRING_DICT)")
+
+// Match operations of StringDict.Match (TAD_STR_*).
+const (
+	StrEqual          int32 = 0 // the value's bytes are the pattern's bytes
+	StrContainsNoCase int32 = 1 // the pattern occurs in the value; 'A'..'Z' fold to 'a'..'z', every other byte matches only itself
+)
+
+// CodeNone is what Lookup gives a string the dictionary does not hold (TAD_CODE_NONE).
+const CodeNone int64 = -1
+
+// StringDict is a string dictionary kept in HBM that outlives the call (tad_strdict): the strings of a key column -> codes that stay the
+// same from batch to batch, new codes in order of first appearance.  One per string key column, in front of the KeyDict: Encode every
+// batch's column, hand the codes to KeyDict.Encode, and build the job filters' masks with Match.
+type StringDict struct {
+	e *Engine
+	h *C.tad_strdict
+}
+
+// NewStringDict makes an empty dictionary.  expectedValues sizes the first table and records, expectedBytes the first arena (0 = the defaults).
+func (e *Engine) NewStringDict(expectedValues, expectedBytes uint64) (*StringDict, error) {
+	if !hasStringDict() {
+		return nil, errNoStringDict
+	}
+	var h *C.tad_strdict
+	if rc := C.tad_strdict_create(e.h, C.uint64_t(expectedValues), C.uint64_t(expectedBytes), &h); rc != C.TAD_OK {
+		return nil, fmt.Errorf("tad_strdict_create: %s (code %d)", C.GoString(C.tad_last_error(e.h)), int(rc))
+	}
+	return &StringDict{e: e, h: h}, nil
+}
+
+func (d *StringDict) Close() {
+	if d.h != nil {
+		C.tad_strdict_destroy(d.e.h, d.h)
+		d.h = nil
+	}
+}
+
+func (d *StringDict) fail(call string, rc C.int) error {
+	msg := C.GoString(C.tad_last_error(d.e.h))
+	if rc == C.TAD_ERR_INVALID_ARGUMENT {
+		return IllegalArgument{msg}
+	}
+	return fmt.Errorf("%s: %s (code %d)", call, msg, int(rc))
+}
+
+// stringBatch copies one Arrow string column — offsets (n + 1, starting anywhere) and the bytes they address — into C memory (no Go
+// pointer is stored in the struct) and fills the tad_string_column.  release frees the copies.
+func stringBatch(offsets []int64, data []byte) (sb *C.tad_string_column, n int, release func(), err error) {
+	if len(offsets) == 0 {
+		return nil, 0, nil, IllegalArgument{"tadengine: a string column has n + 1 offsets"}
+	}
+	n = len(offsets) - 1
+	var bufs []unsafe.Pointer
+	release = func() {
+		for _, p := range bufs {
+			if p != nil {
+				C.free(p)
+			}
+		}
+	}
+	sb = (*C.tad_string_column)(C.calloc(1, C.size_t(unsafe.Sizeof(C.tad_string_column{}))))
+	bufs = append(bufs, unsafe.Pointer(sb))
+	off := cColumn(offsets)
+	bufs = append(bufs, off)
+	sb.n_rows = C.uint64_t(n)
+	sb.offsets = off
+	sb.offset_bits = 64
+	if len(data) > 0 {
+		p := C.CBytes(data)
+		bufs = append(bufs, p)
+		sb.data = (*C.uint8_t)(p)
+	}
+	sb.data_bytes = C.uint64_t(len(data))
+	sb.memory = C.TAD_MEM_HOST
+	return sb, n, release, nil
+}
+
+// Encode maps one batch's strings to codes (tad_strdict_encode): row i is data[offsets[i]:offsets[i+1]].  Strings the dictionary holds
+// keep their codes; new ones get numBefore, numBefore + 1, ... in order of first appearance; newFirstRow[j] = the row of THIS batch
+// where value numBefore + j first appears: the caller reads the new string there.
+func (d *StringDict) Encode(offsets []int64, data []byte) (codes []int64, newFirstRow []uint64, numBefore uint64, err error) {
+	if !hasStringDict() {
+		return nil, nil, 0, errNoStringDict
+	}
+	sb, n, release, err := stringBatch(offsets, data)
+	if err != nil {
+		return nil, nil, 0, err
+	}
+	defer release()
+	codes = make([]int64, n)
+	newFirstRow = make([]uint64, n)
+	var cp *C.int64_t
+	var fr *C.uint64_t
+	if n > 0 {
+		cp = (*C.int64_t)(unsafe.Pointer(&codes[0]))
+		fr = (*C.uint64_t)(unsafe.Pointer(&newFirstRow[0]))
+	}
+	var before, after C.uint64_t
+	if rc := C.tad_strdict_encode(d.e.h, d.h, sb, cp, fr, C.uint64_t(n), &before, &after); rc != C.TAD_OK {
+		return nil, nil, 0, d.fail("tad_strdict_encode", rc)
+	}
+	return codes, newFirstRow[:int(after-before)], uint64(before), nil
+}
+
+// Lookup is Encode read-only (tad_strdict_lookup): an unknown string gets CodeNone and the dictionary is unchanged.
+func (d *StringDict) Lookup(offsets []int64, data []byte) (codes []int64, err error) {
+	if !hasStringDict() {
+		return nil, errNoStringDict
+	}
+	sb, n, release, err := stringBatch(offsets, data)
+	if err != nil {
+		return nil, err
+	}
+	defer release()
+	codes = make([]int64, n)
+	var cp *C.int64_t
+	if n > 0 {
+		cp = (*C.int64_t)(unsafe.Pointer(&codes[0]))
+	}
+	if rc := C.tad_strdict_lookup(d.e.h, d.h, sb, cp); rc != C.TAD_OK {
+		return nil, d.fail("tad_strdict_lookup", rc)
+	}
+	return codes, nil
+}
+
+// NumValues is the number of values the dictionary holds (tad_strdict_num_values): the length of a Match mask.
+func (d *StringDict) NumValues() (uint64, error) {
+	if !hasStringDict() {
+		return 0, errNoStringDict
+	}
+	var n C.uint64_t
+	if rc := C.tad_strdict_num_values(d.e.h, d.h, &n); rc != C.TAD_OK {
+		return 0, d.fail("tad_strdict_num_values", rc)
+	}
+	return uint64(n), nil
+}
+
+// Bytes is the device memory the dictionary holds: table, records and arena at their capacity (tad_strdict_bytes).
+func (d *StringDict) Bytes() (uint64, error) {
+	if !hasStringDict() {
+		return 0, errNoStringDict
+	}
+	var n C.uint64_t
+	if rc := C.tad_strdict_bytes(d.e.h, d.h, &n); rc != C.TAD_OK {
+		return 0, d.fail("tad_strdict_bytes", rc)
+	}
+	return uint64(n), nil
+}
+
+// Export returns the values [firstCode, firstCode + nValues) in Arrow's layout (tad_strdict_export): nValues + 1 offsets starting at 0
+// and the packed bytes — what Import takes after a restart, and where the host reads the strings of result rows.
+func (d *StringDict) Export(firstCode, nValues uint64) (offsets []int64, data []byte, err error) {
+	if !hasStringDict() {
+		return nil, nil, errNoStringDict
+	}
+	var need C.uint64_t
+	if rc := C.tad_strdict_export(d.e.h, d.h, C.uint64_t(firstCode), C.uint64_t(nValues), nil, nil, 0, &need); rc != C.TAD_OK {
+		return nil, nil, d.fail("tad_strdict_export", rc)
+	}
+	offsets = make([]int64, nValues+1)
+	data = make([]byte, uint64(need))
+	var dp *C.uint8_t
+	if len(data) > 0 {
+		dp = (*C.uint8_t)(unsafe.Pointer(&data[0]))
+	}
+	if rc := C.tad_strdict_export(d.e.h, d.h, C.uint64_t(firstCode), C.uint64_t(nValues), (*C.int64_t)(unsafe.Pointer(&offsets[0])), dp, need, &need); rc != C.TAD_OK {
+		return nil, nil, d.fail("tad_strdict_export", rc)
+	}
+	return offsets, data, nil
+}
+
+// Import fills this EMPTY dictionary so that value i is data[offsets[i]:offsets[i+1]] (tad_strdict_import): what Export returned.
+// Two equal strings, offsets that do not start at 0 or decrease, or a dictionary that holds values are refused; nothing changes then.
+func (d *StringDict) Import(offsets []int64, data []byte) error {
+	if !hasStringDict() {
+		return errNoStringDict
+	}
+	if len(offsets) == 0 {
+		return IllegalArgument{"tadengine: a string column has n + 1 offsets"}
+	}
+	var dp *C.uint8_t
+	if len(data) > 0 {
+		dp = (*C.uint8_t)(unsafe.Pointer(&data[0]))
+	}
+	if rc := C.tad_strdict_import(d.e.h, d.h, C.uint64_t(len(offsets)-1), (*C.int64_t)(unsafe.Pointer(&offsets[0])), dp); rc != C.TAD_OK {
+		return d.fail("tad_strdict_import", rc)
+	}
+	return nil
+}
+
+// Match evaluates one string predicate on every value (tad_strdict_match): mask[c] = 1 iff value c satisfies op (StrEqual,
+// StrContainsNoCase) with the pattern (at most 1024 bytes).  The mask is a term of KeyDict.Select.
+func (d *StringDict) Match(op int32, pattern []byte) (mask []byte, matched uint64, err error) {
+	if !hasStringDict() {
+		return nil, 0, errNoStringDict
+	}
+	n, err := d.NumValues()
+	if err != nil {
+		return nil, 0, err
+	}
+	mask = make([]byte, n)
+	var mp, pp *C.uint8_t
+	if n > 0 {
+		mp = (*C.uint8_t)(unsafe.Pointer(&mask[0]))
+	}
+	if len(pattern) > 0 {
+		pp = (*C.uint8_t)(unsafe.Pointer(&pattern[0]))
+	}
+	var hit C.uint64_t
+	if rc := C.tad_strdict_match(d.e.h, d.h, C.int32_t(op), pp, C.uint64_t(len(pattern)), mp, C.uint64_t(n), C.TAD_MEM_HOST, &hit); rc != C.TAD_OK {
+		return nil, 0, d.fail("tad_strdict_match", rc)
+	}
+	return mask, uint64(hit), nil
+}

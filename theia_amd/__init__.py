@@ -11,6 +11,6 @@ Product layout:
 There is no CPU fallback: every compute entry point goes through the HIP library and fails
 loudly if it (or a GPU) is missing.
 """
-from .engine import KeyDict, TadDropRows, TadEngine, TadError, TadPoints, TadResult, TadState  # noqa: F401
+from .engine import KeyDict, StringDict, TadDropRows, TadEngine, TadError, TadPoints, TadResult, TadState  # noqa: F401
 
-__all__ = ["KeyDict", "TadDropRows", "TadEngine", "TadError", "TadPoints", "TadResult", "TadState"]
+__all__ = ["KeyDict", "StringDict", "TadDropRows", "TadEngine", "TadError", "TadPoints", "TadResult", "TadState"]

@@ -17,17 +17,12 @@
 // Pod mode (the UNION ALL of the inbound and the outbound view, :556-565) passes two tuples per row: the table runs over the
 // virtual rows [side a: 0 .. n) ++ [side b: n .. 2n), the side is part of the tuple.
 #include "tad_internal.h"
+#include "tad_strbytes.h"      // fz_mix, StrArgs, se_span, se_load, se_load_lds, se_hash, se_same_as, kSeStage
 
 namespace tad {
 
 static constexpr int kFzBlock = 256;
 static constexpr unsigned long long kFzEmpty = ~0ull;
-
-__device__ __forceinline__ uint64_t fz_mix(uint64_t x) {   // splitmix64 finaliser
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 
 // A probe LOOKS at a slot with a plain cached load.  On this multi-XCD chip an agent-scope load is a transaction with the memory side for every
 // row (the L2s of the eight XCDs are not coherent with each other, so device-scope accesses bypass them): 1e8 of them were the insert pass
@@ -317,116 +312,15 @@ void launch_factorize(hipStream_t s, const long long *const *cols_a, const uint8
 // scan of its popcounts — the kernels above.  A null row (Arrow validity bitmap) encodes like the empty string, which is what the
 // host path did (`fill_null("")`, theia_amd/clickhouse.py).
 // ------------------------------------------------------------------------------------------------
-struct StrArgs {
-  const void *off;        // n + 1 offsets into data
-  const uint8_t *data;
-  const uint8_t *valid;   // Arrow validity bitmap (bit valid_off + i), NULL = no nulls
-  uint64_t valid_off;
-  uint64_t n;
-  uint64_t data_bytes;
-  int off64;              // offsets are int64 (large_string) instead of int32
-};
-
 static constexpr uint32_t kSeMaxProbe = 32;
 enum : uint32_t { SE_FLAG_GROW = FZ_FLAG_GROW, SE_FLAG_BAD_OFFSETS = FZ_FLAG_BAD_INPUT };
 
-// [b, b + len) of row v; false if the offsets are not usable
-__device__ __forceinline__ bool se_span(const StrArgs &A, uint64_t v, uint64_t &b, uint32_t &len) {
-  uint64_t e;
-  if (A.off64) {
-    const long long *o = static_cast<const long long *>(A.off);
-    b = (uint64_t)o[v]; e = (uint64_t)o[v + 1];
-  } else {
-    const int *o = static_cast<const int *>(A.off);
-    b = (uint64_t)(uint32_t)o[v]; e = (uint64_t)(uint32_t)o[v + 1];
-  }
-  if (e < b || e > A.data_bytes || e - b > 0xFFFFFFFFull) return false;
-  len = (uint32_t)(e - b);
-  if (A.valid != nullptr) {
-    const uint64_t bit = A.valid_off + v;
-    if (((A.valid[bit >> 3] >> (bit & 7)) & 1u) == 0) len = 0;   // null = ""
-  }
-  return true;
-}
-
-// m (1..8) bytes at p as a little-endian word, bytes beyond m zero.  Two aligned loads without a branch between them (a conditional second load
-// made every chunk of a compare its own memory round trip): when the chunk does not reach into the next word, the first word is loaded twice.
-__device__ __forceinline__ uint64_t se_load(const uint8_t *p, uint32_t m) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-  const uint64_t *w = reinterpret_cast<const uint64_t *>(a & ~(uintptr_t)7);
-  const uint32_t skip = (uint32_t)(a & 7);           // bytes of w[0] in front of p
-  const bool two = skip + m > 8;                      // (skip >= 1 then: the left shift below is < 64)
-  const uint64_t lo = w[0], hi = w[two ? 1 : 0];
-  uint64_t x = lo >> (skip * 8);
-  if (two) x |= hi << ((8 - skip) * 8);
-  if (m < 8) x &= (1ull << (m * 8)) - 1ull;
-  return x;
-}
-
-__device__ __forceinline__ uint64_t se_hash(const uint8_t *p, uint32_t len) {
-  uint64_t h = 0x9E3779B97F4A7C15ull ^ len;
-  for (uint32_t i = 0; i < len; i += 8) h = fz_mix(h ^ se_load(p + i, len - i < 8 ? len - i : 8)) + 0x632BE59BD9B4E019ull;
-  return fz_mix(h);
-}
-
-// own(at, m): m bytes of the lane's own string at offset `at`; q: the representative row's bytes in global memory.  What the compare costs is
-// the number of load instructions — 64 lanes, 64 different representatives, 64 different cache lines per instruction, all from L2 — not their
-// latency (3.4 of the insert pass's 5.1 ms, profiles/r4_v33_*; loading the chunks four at a time changed nothing).  So the representative's bytes
-// are fetched as ALIGNED 16-byte words, each exactly once (a 29-byte name is 2-3 loads; chunk by chunk through se_load it was 8: every aligned word
-// twice), and each 8-byte half is compared with the bytes of the own string it covers.
-template <class Own>
-__device__ __forceinline__ bool se_same_as(Own own, const uint8_t *q, uint32_t len) {
-  if (len == 0) return true;                               // (nothing to read: the lengths are equal)
-  const uintptr_t a = reinterpret_cast<uintptr_t>(q);
-  const ulonglong2 *w = reinterpret_cast<const ulonglong2 *>(a & ~(uintptr_t)15);
-  const int skip = (int)(a & 15);                          // bytes of w[0] in front of the string
-  const uint32_t nw = ((uint32_t)skip + len + 15u) >> 4;   // aligned 16-byte words that hold a byte of the string (each inside the buffer's pages)
-  bool same = true;
-  for (uint32_t k0 = 0; k0 < nw && same; k0 += 2) {
-    ulonglong2 v[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) v[u] = w[k0 + u < nw ? k0 + u : k0];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (k0 + u >= nw) break;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int start = (int)(16u * (k0 + u)) + 8 * h - skip;        // offset in the string of this 8-byte half's first byte (may be < 0)
-        const int s0 = start < 0 ? 0 : start;
-        const int e0 = start + 8 < (int)len ? start + 8 : (int)len;
-        if (e0 <= s0) continue;                                         // the half lies before or behind the string
-        const uint32_t m = (uint32_t)(e0 - s0);
-        uint64_t x = (h == 0 ? v[u].x : v[u].y) >> (8 * (s0 - start));
-        if (m < 8) x &= (1ull << (m * 8)) - 1ull;
-        same = same && x == own((uint32_t)s0, m);
-      }
-    }
-  }
-  return same;
-}
-__device__ __forceinline__ bool se_same(const uint8_t *p, const uint8_t *q, uint32_t len) {
-  return se_same_as([&](uint32_t at, uint32_t m) { return se_load(p + at, m); }, q, len);
-}
-
-// A block's rows are CONSECUTIVE rows of the column, so their bytes are one contiguous range [off[r0], off[r0 + 256)) of `data`: it is copied
-// into LDS with 16-byte loads (consecutive lanes on consecutive 16 bytes: the column's bytes cross the memory system once, in whole lines),
-// and every lane then hashes and compares its own string from LDS.  Per-lane 8-byte global loads at a ~29-byte stride — the first version —
-// made every wave-level load touch ~15 cache lines, five times over per row, and ran at 0.07 of the HBM peak (profiles/r4_v28_*).
-// A block whose 256 rows hold more than kSeStage bytes (long labels) reads its strings from global memory lane by lane instead.
-static constexpr uint32_t kSeStage = 24 * 1024;
-
-// m (1..8) bytes at byte offset `at` of an 8-byte aligned LDS buffer, bytes beyond m zero
-__device__ __forceinline__ uint64_t se_load_lds(const uint64_t *buf, uint32_t at, uint32_t m) {
-  const uint32_t skip = at & 7u;
-  uint64_t x = buf[at >> 3] >> (skip * 8);
-  if (skip + m > 8) x |= buf[(at >> 3) + 1] << ((8 - skip) * 8);
-  if (m < 8) x &= (1ull << (m * 8)) - 1ull;
-  return x;
-}
-
 // every row into the table; slot_of[v] = the slot of v's string.  flags: SE_FLAG_GROW / SE_FLAG_BAD_OFFSETS; claims: slots claimed
+// keep (tad_strdict: the miss flags of its probe; NULL = every row): a row whose byte is 0 is staged and validated with its block but neither
+// hashed nor inserted, and its slot_of entry is not written
 __global__ __launch_bounds__(kFzBlock) void k_se_insert(StrArgs A, unsigned long long *__restrict__ table, uint64_t mask, uint32_t *__restrict__ slot_of,
-                                                        uint32_t *__restrict__ flags, unsigned long long *__restrict__ claims, uint32_t max_probe) {
+                                                        uint32_t *__restrict__ flags, unsigned long long *__restrict__ claims, uint32_t max_probe,
+                                                        const uint8_t *__restrict__ keep) {
   __shared__ __attribute__((aligned(16))) uint64_t s_bytes[kSeStage / 8 + 4];
   __shared__ uint64_t s_lo, s_hi;
   __shared__ uint32_t s_stop;
@@ -464,7 +358,7 @@ __global__ __launch_bounds__(kFzBlock) void k_se_insert(StrArgs A, unsigned long
     __syncthreads();
     // a lane reads its string from the stage when it lies inside the staged range (always, for monotone offsets), else from global memory
     const bool staged = block_staged && b >= lo && b + len <= hi;
-    if (ok && tid < rows) {
+    if (ok && tid < rows && (keep == nullptr || keep[v] != 0)) {
       const uint8_t *p = A.data + b;
       const uint32_t at = staged ? (uint32_t)((reinterpret_cast<uintptr_t>(A.data) + b) - abs_a) : 0u;      // own string's offset in the stage
       uint64_t h = 0x9E3779B97F4A7C15ull ^ len;
@@ -518,22 +412,26 @@ __global__ __launch_bounds__(kFzBlock) void k_se_insert(StrArgs A, unsigned long
   }
 }
 
-// code of every row: slot -> id (k_fz_ids has turned the table's words into ids and written the first rows)
+// code of every row: slot -> id (k_fz_ids has turned the table's words into ids and written the first rows).  keep != NULL: the rows whose
+// byte is 0 have no slot; their codes are left as they are
 __global__ __launch_bounds__(kFzBlock) void k_se_codes(uint64_t n, const unsigned long long *__restrict__ table, const uint32_t *__restrict__ slot_of,
-                                                       long long *__restrict__ codes, const uint32_t *__restrict__ flags) {
+                                                       long long *__restrict__ codes, const uint32_t *__restrict__ flags, const uint8_t *__restrict__ keep) {
   if (*flags != 0u) return;     // the insert pass gave up (table too small / bad offsets): slot_of is not complete, the host repeats or fails
   constexpr int U = 4;
   const uint64_t stride = (uint64_t)gridDim.x * kFzBlock;
   for (uint64_t v0 = (uint64_t)blockIdx.x * kFzBlock + threadIdx.x; v0 < n; v0 += U * stride) {
+    bool in[U];
     uint32_t sl[U];
     unsigned long long id[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) sl[u] = v0 + u * stride < n ? slot_of[v0 + u * stride] : 0u;
+    for (int u = 0; u < U; ++u) in[u] = v0 + u * stride < n && (keep == nullptr || keep[v0 + u * stride] != 0);
 #pragma unroll
-    for (int u = 0; u < U; ++u) id[u] = v0 + u * stride < n ? table[sl[u]] : 0ull;
+    for (int u = 0; u < U; ++u) sl[u] = in[u] ? slot_of[v0 + u * stride] : 0u;
+#pragma unroll
+    for (int u = 0; u < U; ++u) id[u] = in[u] ? table[sl[u]] : 0ull;
 #pragma unroll
     for (int u = 0; u < U; ++u)
-      if (v0 + u * stride < n) codes[v0 + u * stride] = (long long)id[u];
+      if (in[u]) codes[v0 + u * stride] = (long long)id[u];
   }
 }
 
@@ -542,7 +440,7 @@ __global__ __launch_bounds__(kFzBlock) void k_se_codes(uint64_t n, const unsigne
 // written then), bit 1 -> the offsets are malformed.
 void launch_encode_strings(hipStream_t s, const void *offsets, int off64, const uint8_t *data, uint64_t data_bytes, const uint8_t *valid, uint64_t valid_off,
                            uint64_t n, uint64_t slots, void *temp, long long *codes, uint64_t *first_row, uint64_t first_row_cap,
-                           unsigned long long *num_values_dev, uint32_t **flags_dev_out) {
+                           unsigned long long *num_values_dev, uint32_t **flags_dev_out, const uint8_t *keep) {
   StrArgs A{};
   A.off = offsets; A.data = data; A.valid = valid; A.valid_off = valid_off; A.n = n; A.data_bytes = data_bytes; A.off64 = off64;
   const uint64_t words = (n + 31) / 32;
@@ -552,14 +450,14 @@ void launch_encode_strings(hipStream_t s, const void *offsets, int off64, const 
   hipMemsetAsync(t.bits, 0, words * 4, s);
   hipMemsetAsync(t.claims, 0, 16, s);
   hipLaunchKernelGGL(k_se_insert, fz_grid(n), dim3(kFzBlock), 0, s, A, t.table, slots - 1, t.slot_of, t.flags, t.claims,
-                     slots >= factorize_table_slots(n) ? 0xFFFFFFFFu : kSeMaxProbe);
+                     slots >= factorize_table_slots(n) ? 0xFFFFFFFFu : kSeMaxProbe, keep);
   // (after a raised flag the table is incomplete: the passes below still run — over a bitmap of n bits, harmless — and k_se_codes returns
   // at once; the host reads flags and the count in ONE synchronisation and repeats the attempt with the next table size if asked to)
   hipLaunchKernelGGL(k_fz_mark, fz_grid(slots), dim3(kFzBlock), 0, s, t.table, slots, t.bits);
   hipLaunchKernelGGL(k_fz_popc, fz_grid(words), dim3(kFzBlock), 0, s, t.bits, words, t.cnt);
   launch_scan(s, t.cnt, t.off, words, t.scratch, num_values_dev);
   hipLaunchKernelGGL(k_fz_ids, fz_grid(slots), dim3(kFzBlock), 0, s, t.table, slots, t.bits, t.off, first_row, first_row_cap, t.flags);
-  hipLaunchKernelGGL(k_se_codes, fz_grid(n), dim3(kFzBlock), 0, s, n, t.table, t.slot_of, codes, t.flags);
+  hipLaunchKernelGGL(k_se_codes, fz_grid(n), dim3(kFzBlock), 0, s, n, t.table, t.slot_of, codes, t.flags, keep);
 }
 
 // one kernel of this translation unit: tad_engine_create resolves it so that the unit's code object is loaded before the first job

@@ -695,7 +695,7 @@ void launch_factorize(hipStream_t s, const long long *const *cols_a, const uint8
 // Arrow string column -> dictionary codes in order of first appearance (tad_factorize.hip, ABI 10); same table sizes and temp layout
 void launch_encode_strings(hipStream_t s, const void *offsets, int off64, const uint8_t *data, uint64_t data_bytes, const uint8_t *valid, uint64_t valid_off,
                            uint64_t n, uint64_t slots, void *temp, long long *codes, uint64_t *first_row, uint64_t first_row_cap,
-                           unsigned long long *num_values_dev, uint32_t **flags_dev_out);
+                           unsigned long long *num_values_dev, uint32_t **flags_dev_out, const uint8_t *keep = nullptr);
 
 // ---- ingest: a key dictionary that outlives the call — tuples -> ids that stay the same from batch to batch (tad_keydict.hip) ----
 struct KdBatch {                    // the key tuples of one batch (device pointers)
@@ -734,6 +734,38 @@ struct KdSelect {
 // *n_sel += the selected keys, *flags |= KD_FLAG_BAD_CODE for a value outside its mask (both zeroed by the caller)
 void launch_kd_select(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, const KdSelect &q, uint8_t *keep, unsigned long long *n_sel,
                       uint32_t *flags);
+
+// ---- ingest: a string dictionary that outlives the call — strings -> codes that stay the same from batch to batch (tad_strdict.hip) ----
+struct SdBatch {                    // one Arrow string column (device pointers): tad_string_column
+  const void *offsets;              // n + 1
+  const uint8_t *data;
+  const uint8_t *valid;             // NULL = no nulls
+  uint64_t valid_off, n, data_bytes;
+  int off64;
+};
+static constexpr uint32_t kSdMaxProbe = 32;       // a claim that probed further asks the host for a larger table
+static constexpr uint32_t kSdMaxPattern = 1024;   // tad_strdict_match: bytes of the longest pattern
+enum : uint32_t { SD_FLAG_CLUSTER = 1u, SD_FLAG_BAD_OFFSETS = 2u, SD_FLAG_BAD_ROW = 4u };
+// recs: one 16-byte record per code (arena offset | hash's low half << 32 | length); arena: the strings, each 16-byte aligned and zero-padded.
+// every row looks its string up in table[slots] / recs (K records) / arena.  miss != NULL: hits write their code, misses raise miss[v] and
+// are counted in *n_miss; miss == NULL: a miss is TAD_CODE_NONE.  *flags |= SD_FLAG_BAD_OFFSETS for unusable offsets (both zeroed by the caller)
+void launch_sd_probe(hipStream_t s, const SdBatch &B, const unsigned long long *table, uint64_t slots, const void *recs, const uint8_t *arena, uint64_t K,
+                     long long *codes, uint8_t *miss, unsigned long long *n_miss, uint32_t *flags);
+// cnt[j] (j < M) = the 16-byte units of the string at row first_row[j] for j < *num_new, else 0; all 0 when *se_flags != 0
+void launch_sd_lens(hipStream_t s, const SdBatch &B, const uint64_t *first_row, const unsigned long long *num_new, uint64_t M, const uint32_t *se_flags, uint32_t *cnt);
+// new value j (< m) = the string at row first_row[j]: its bytes at arena_used + 16 off16[j], record K0 + j and a slot (load <= 1/2 afterwards)
+void launch_sd_append(hipStream_t s, const SdBatch &B, const uint64_t *first_row, const unsigned long long *off16, uint64_t m, uint64_t K0, uint64_t arena_used,
+                      unsigned long long *table, uint64_t slots, void *recs, uint8_t *arena, uint32_t *flags);
+// codes[v] += K0 on the rows whose miss flag is raised
+void launch_sd_fix(hipStream_t s, const uint8_t *miss, uint64_t n, uint64_t K0, long long *codes);
+// the claimed slots of old_table into an empty table of `slots` slots
+void launch_sd_rehash(hipStream_t s, const unsigned long long *old_table, uint64_t old_slots, const void *recs, uint64_t K, unsigned long long *table, uint64_t slots);
+// out[c] = 1 iff value c satisfies op (TAD_STR_*) with the pattern (device memory, folded for TAD_STR_CONTAINS_NOCASE), else 0; *n_hit += the matches
+void launch_sd_match(hipStream_t s, const void *recs, const uint8_t *arena, uint64_t K, int op, const uint8_t *pattern, uint32_t pattern_len, uint8_t *out,
+                     unsigned long long *n_hit);
+// cnt[i] = the length of value first + i; the values' bytes packed at out + off[i] (out 8-byte aligned)
+void launch_sd_export_lens(hipStream_t s, const void *recs, uint64_t first, uint64_t n, uint32_t *cnt);
+void launch_sd_export(hipStream_t s, const void *recs, const uint8_t *arena, uint64_t first, uint64_t n, const unsigned long long *off, uint8_t *out);
 
 // ---- retiring dead keys: tad_state_compact / tad_keydict_compact (tad_compact.hip) ----
 struct CompactCounters {   // one 64-byte block on the device, zeroed per call
@@ -802,6 +834,7 @@ const void *code_anchor_merge();
 const void *code_anchor_shard();
 const void *code_anchor_sparse();
 const void *code_anchor_stage0_part();
+const void *code_anchor_strdict();
 const void *code_anchor_synth();
 const void *code_anchor_window();
 

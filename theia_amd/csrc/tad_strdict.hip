@@ -1,0 +1,351 @@
+// tad_strdict.hip — a string dictionary that OUTLIVES the call: the strings of an Arrow column -> codes that stay the same from batch to batch.
+//
+// tad_encode_strings (tad_factorize.hip) numbers the strings of ONE call: its table is scratch, and a fingerprint match is confirmed against
+// the representative row in that call's own bytes.  A streaming host wants string s to be the same code in every batch for as long as the
+// key dictionary behind it lives (tad.h, tad_keydict: "one vocabulary per column, kept for the life of the dictionary"), so it kept its own
+// string -> code map (numpy's unique + a Python dict per batch and column) in front of an encode that runs at 2.3e10 rows/s.  Here the map
+// lives in HBM — to tad_encode_strings what tad_keydict.hip is to tad_factorize:
+//   table    open addressing, linear probing, one 8-byte word per slot — word = fingerprint (high 32 bits of the string's hash) << 32 | code,
+//            all ones = empty.  A slot is claimed with ONE compare-and-swap and its word never changes afterwards, so probes LOOK with plain
+//            cached loads (kd_peek's reasoning: a stale view can only show "empty" where a slot has just been claimed, and an empty slot is
+//            only ever taken with the compare-and-swap, which returns the truth);
+//   records  one 16-byte record per code, read with one 16-byte load: the string's offset in the arena (8 bytes), its length (4) and the LOW
+//            32 bits of its hash (4).  Slot and record together hold the whole hash, so growing the table (k_sd_rehash) walks the old slots
+//            and reads the records only, never the arena;
+//   arena    the strings' bytes, because the rows of earlier batches are gone.  Every string starts on a 16-byte boundary and is padded with
+//            zero bytes to a multiple of 16: the compare (se_same_as) fetches the held string as aligned 16-byte words, ceil(len / 16) of
+//            them when the string is aligned and ceil((skip + len) / 16) when it starts `skip` bytes into a word — for a 29-byte pod name 2
+//            load instructions against 2.75 on average over the 16 starts.  What the compare costs is the number of load
+//            instructions (the se_same_as comment), so the arena pays 7.5 bytes a value on average for the shorter compare.  The allocation's
+//            length is a multiple of 16: every aligned 16-byte load of a compare stays inside it.
+// One batch (tad_strdict_encode):
+//   1. k_sd_probe: a workgroup takes 256 consecutive rows, stages their contiguous byte range in LDS with 16-byte loads (k_se_insert's rule:
+//      kSeStage, per-lane global reads for a block over it or a lane outside the staged range), validates every span, hashes from LDS and
+//      looks the string up.  Hit -> the code goes to the output; miss -> a flag byte, counted per wavefront.  The dictionary is only read.
+//      A batch of known strings ends here: one pass, one synchronisation.
+//   2. the misses are de-duplicated among themselves by launch_encode_strings with the miss flags as its keep mask: batch-local ids in
+//      order of first appearance and the first row of each — deterministic, whatever order the wavefronts run in.  The local ids are
+//      written to the miss rows of the output itself.
+//   3. k_sd_lens + launch_scan: the new values' padded lengths become arena offsets (in 16-byte units, so that a count fits 32 bits).
+//      The host reads the new-value count, the new bytes and the flags in one synchronisation and grows table, records or arena
+//      into fresh allocations where needed (capacity only; the old arrays stay the dictionary's until the new ones are complete).
+//   4. k_sd_append: one lane per NEW value copies the string from its first row into the arena in whole 8-byte words (se_load assembles
+//      each word from aligned loads, whatever the source's alignment; the destination is 16-byte aligned), writes the record and claims a
+//      slot.  New values are distinct from each other and from every value held, so nothing is compared here.
+//   5. k_sd_fix: code = num_before + local id on the miss rows.
+// The table never passes load 1/2 (grown BEFORE step 4), so every probe sequence ends at an empty slot and step 4 cannot fail.
+#include "tad_internal.h"
+#include "tad_strbytes.h"
+
+namespace tad {
+
+static constexpr int kSdBlock = 256;
+static constexpr unsigned long long kSdEmpty = ~0ull;
+
+// a plain cached load (see the top of the file and tad_keydict.hip: an agent-scope load would be a memory-side transaction per row)
+__device__ __forceinline__ unsigned long long sd_peek(const unsigned long long *slot) {
+  return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// record c: x = the string's byte offset in the arena, y = hash's low 32 bits << 32 | length
+__device__ __forceinline__ uint32_t sd_rec_len(const ulonglong2 &r) { return (uint32_t)(r.y & 0xffffffffull); }
+__device__ __forceinline__ uint32_t sd_rec_hash_lo(const ulonglong2 &r) { return (uint32_t)(r.y >> 32); }
+
+// Step 1.  kInsert: a miss raises miss[v] (0 is written otherwise: the flags are the keep mask of step 2) and is counted; the code of a
+// miss row is left to steps 2 and 5.  !kInsert (tad_strdict_lookup): a miss is TAD_CODE_NONE.  A word whose code is >= K is never a match
+// (no such word exists in a dictionary that every call left normally).  A row whose offsets are unusable raises SD_FLAG_BAD_OFFSETS,
+// reads no byte and is neither a hit nor a miss: the host fails the call.
+template <bool kInsert>
+__global__ __launch_bounds__(kSdBlock) void k_sd_probe(StrArgs A, const unsigned long long *__restrict__ table, uint64_t mask, const ulonglong2 *__restrict__ recs,
+                                                       const uint8_t *__restrict__ arena, uint64_t K, long long *__restrict__ codes, uint8_t *__restrict__ miss,
+                                                       unsigned long long *__restrict__ n_miss, uint32_t *__restrict__ flags) {
+  __shared__ __attribute__((aligned(16))) uint64_t s_bytes[kSeStage / 8 + 4];
+  __shared__ uint64_t s_lo, s_hi;
+  uint32_t missed = 0;
+  const uint32_t tid = threadIdx.x;
+  for (uint64_t base = (uint64_t)blockIdx.x * kSdBlock; base < A.n; base += (uint64_t)gridDim.x * kSdBlock) {
+    const uint64_t v = base + tid;
+    const uint32_t rows = A.n - base < kSdBlock ? (uint32_t)(A.n - base) : kSdBlock;
+    uint64_t b = 0; uint32_t len = 0;
+    bool ok = true;
+    if (tid < rows) ok = se_span(A, v, b, len);
+    if (tid == 0) {
+      // the block's byte range from its first and last row's RAW offsets (a null row reads as "" but its bytes may still be there)
+      uint64_t lo, hi;
+      if (A.off64) { const long long *o = static_cast<const long long *>(A.off); lo = (uint64_t)o[base]; hi = (uint64_t)o[base + rows]; }
+      else { const int *o = static_cast<const int *>(A.off); lo = (uint64_t)(uint32_t)o[base]; hi = (uint64_t)(uint32_t)o[base + rows]; }
+      s_lo = lo; s_hi = hi;
+    }
+    if (!ok) atomicOr(flags, SD_FLAG_BAD_OFFSETS);      // (the host fails the call; this lane skips its row)
+    __syncthreads();                                    // (also: the previous round's strings are no longer read)
+    const uint64_t lo = s_lo, hi = s_hi;
+    const bool bad_range = hi < lo || hi > A.data_bytes;
+    if (bad_range && tid == 0) atomicOr(flags, SD_FLAG_BAD_OFFSETS);
+    const uintptr_t abs_lo = reinterpret_cast<uintptr_t>(A.data) + lo;
+    const uintptr_t abs_a = abs_lo & ~(uintptr_t)15;    // the aligned 16-byte word that holds the range's first byte
+    const uint64_t span = !bad_range && hi > lo ? (reinterpret_cast<uintptr_t>(A.data) + hi) - abs_a : 0;
+    const bool block_staged = !bad_range && span <= kSeStage;     // block-uniform (from the shared bounds)
+    if (block_staged && span) {
+      const uint4 *src = reinterpret_cast<const uint4 *>(abs_a);
+      uint4 *dst = reinterpret_cast<uint4 *>(s_bytes);
+      for (uint32_t i = tid; (uint64_t)i * 16 < span; i += kSdBlock) dst[i] = src[i];   // (the last word may reach past `hi`: same aligned 16 bytes, same page)
+    }
+    __syncthreads();
+    // a lane reads its string from the stage when it lies inside the staged range (always, for monotone offsets), else from global memory
+    const bool staged = block_staged && b >= lo && b + len <= hi;
+    if (tid < rows) {
+      long long code = TAD_CODE_NONE;
+      bool m = false;
+      if (ok) {
+        const uint8_t *p = A.data + b;
+        const uint32_t at = staged ? (uint32_t)((reinterpret_cast<uintptr_t>(A.data) + b) - abs_a) : 0u;      // own string's offset in the stage
+        uint64_t h = 0x9E3779B97F4A7C15ull ^ len;
+        if (staged) {
+          for (uint32_t i = 0; i < len; i += 8) h = fz_mix(h ^ se_load_lds(s_bytes, at + i, len - i < 8 ? len - i : 8)) + 0x632BE59BD9B4E019ull;
+          h = fz_mix(h);
+        } else {
+          h = se_hash(p, len);
+        }
+        for (uint64_t s = h & mask;; s = (s + 1) & mask) {
+          const unsigned long long w = sd_peek(table + s);
+          if (w == kSdEmpty) { m = true; break; }                   // (load <= 1/2: every probe sequence reaches an empty slot)
+          const uint64_t cand = w & 0xffffffffull;
+          if ((w >> 32) != (h >> 32) || cand >= K) continue;
+          const ulonglong2 r = recs[cand];
+          if (sd_rec_len(r) != len) continue;                       // lengths first
+          const uint8_t *q = arena + r.x;
+          const bool same = staged ? se_same_as([&](uint32_t o, uint32_t mm) { return se_load_lds(s_bytes, at + o, mm); }, q, len) : se_same(p, q, len);
+          if (same) { code = (long long)cand; break; }
+        }
+      }
+      if (kInsert) {
+        miss[v] = m ? 1 : 0;
+        missed += m ? 1u : 0u;
+        if (!m) codes[v] = code;
+      } else {
+        codes[v] = code;
+      }
+    }
+  }
+  if (kInsert) {
+    for (int o = 32; o > 0; o >>= 1) missed += __shfl_down(missed, o);     // one atomic per wavefront
+    if ((threadIdx.x & 63) == 0 && missed) atomicAdd(n_miss, (unsigned long long)missed);
+  }
+}
+
+// Step 3: cnt[j] = the 16-byte units new value j takes in the arena, for j < *num_new (step 2's count, on the device); 0 for the rest of
+// the M entries the scan runs over, and for all of them when step 2 gave up (its flags: the host repeats it with a larger scratch table).
+__global__ __launch_bounds__(kSdBlock) void k_sd_lens(StrArgs A, const uint64_t *__restrict__ first_row, const unsigned long long *__restrict__ num_new, uint64_t M,
+                                                      const uint32_t *__restrict__ se_flags, uint32_t *__restrict__ cnt) {
+  const uint64_t m = *se_flags != 0u ? 0ull : *num_new;
+  for (uint64_t j = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; j < M; j += (uint64_t)gridDim.x * kSdBlock) {
+    uint32_t units = 0;
+    if (j < m) {
+      const uint64_t v = first_row[j];
+      uint64_t b; uint32_t len;
+      if (v < A.n && se_span(A, v, b, len)) units = (uint32_t)(((uint64_t)len + 15) >> 4);
+    }
+    cnt[j] = units;
+  }
+}
+
+// Step 4: one lane per new value.  first_row[j] = the row where new value j first appears (step 2), off16[j] = its place in the arena in
+// 16-byte units behind arena_used (step 3).  The string is hashed while it is copied.  flags |= SD_FLAG_CLUSTER when a claim needed a long
+// probe sequence: the host then grows the table after the call (a hint for speed; the claim itself always succeeds).
+__global__ __launch_bounds__(kSdBlock) void k_sd_append(StrArgs A, const uint64_t *__restrict__ first_row, const unsigned long long *__restrict__ off16, uint64_t m,
+                                                        uint64_t K0, uint64_t arena_used, unsigned long long *__restrict__ table, uint64_t mask,
+                                                        ulonglong2 *__restrict__ recs, uint8_t *__restrict__ arena, uint32_t *__restrict__ flags) {
+  for (uint64_t j = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; j < m; j += (uint64_t)gridDim.x * kSdBlock) {
+    const uint64_t v = first_row[j];
+    uint64_t b; uint32_t len;
+    if (v >= A.n || !se_span(A, v, b, len)) { atomicOr(flags, SD_FLAG_BAD_ROW); continue; }      // (cannot happen: steps 1 and 2 validated it)
+    const uint64_t at = arena_used + off16[j] * 16ull;
+    const uint8_t *p = A.data + b;
+    uint64_t *dst = reinterpret_cast<uint64_t *>(arena + at);      // 16-byte aligned
+    uint64_t h = 0x9E3779B97F4A7C15ull ^ len;
+    for (uint32_t i = 0; i < len; i += 8) {
+      const uint64_t x = se_load(p + i, len - i < 8 ? len - i : 8);     // bytes beyond the string are zero: the pad
+      h = fz_mix(h ^ x) + 0x632BE59BD9B4E019ull;
+      dst[i >> 3] = x;
+    }
+    if (((len + 7u) >> 3) & 1u) dst[(len + 7u) >> 3] = 0ull;            // the second half of the last 16 bytes
+    h = fz_mix(h);
+    recs[K0 + j] = ulonglong2{at, ((h & 0xffffffffull) << 32) | len};
+    const unsigned long long mine = ((h >> 32) << 32) | (K0 + j);       // (K0 + j < 2^32 - 1: never the empty word)
+    uint32_t probes = 0;
+    for (uint64_t s = h & mask;; s = (s + 1) & mask, ++probes) {
+      unsigned long long w = sd_peek(table + s);
+      if (w == kSdEmpty) {
+        w = atomicCAS(table + s, kSdEmpty, mine);
+        if (w == kSdEmpty) break;                                       // claimed
+      }
+    }
+    if (probes > kSdMaxProbe) atomicOr(flags, SD_FLAG_CLUSTER);
+  }
+}
+
+// Step 5 (the miss rows hold step 2's local ids)
+__global__ __launch_bounds__(kSdBlock) void k_sd_fix(const uint8_t *__restrict__ miss, uint64_t n, uint64_t K0, long long *__restrict__ codes) {
+  for (uint64_t v = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; v < n; v += (uint64_t)gridDim.x * kSdBlock)
+    if (miss[v] != 0) codes[v] += (long long)K0;
+}
+
+// The claimed slots of the old table into an EMPTY larger one (growth).  The slot gives the high half of the hash and the code, the code's
+// record the low half: no string is read.
+__global__ __launch_bounds__(kSdBlock) void k_sd_rehash(const unsigned long long *__restrict__ old_table, uint64_t old_slots, const ulonglong2 *__restrict__ recs, uint64_t K,
+                                                        unsigned long long *__restrict__ table, uint64_t mask) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; i < old_slots; i += (uint64_t)gridDim.x * kSdBlock) {
+    const unsigned long long w = old_table[i];
+    if (w == kSdEmpty || (w & 0xffffffffull) >= K) continue;
+    const uint64_t h = ((w >> 32) << 32) | sd_rec_hash_lo(recs[w & 0xffffffffull]);
+    for (uint64_t s = h & mask;; s = (s + 1) & mask) {
+      unsigned long long x = sd_peek(table + s);
+      if (x == kSdEmpty) {
+        x = atomicCAS(table + s, kSdEmpty, w);
+        if (x == kSdEmpty) break;
+      }
+    }
+  }
+}
+
+// 'A'..'Z' -> 'a'..'z' in each of the eight bytes of x, every other byte — a byte >= 0x80 included — as it is
+__device__ __forceinline__ uint64_t sd_fold(uint64_t x) {
+  const uint64_t lo7 = x & 0x7f7f7f7f7f7f7f7full;
+  const uint64_t ge_A = lo7 + 0x3f3f3f3f3f3f3f3full;      // bit 7 of a byte: its low seven bits are >= 0x41
+  const uint64_t gt_Z = lo7 + 0x2525252525252525ull;      // ... are >= 0x5b
+  return x | ((ge_A & ~gt_Z & ~x & 0x8080808080808080ull) >> 2);
+}
+
+// tad_strdict_match: one lane per value.  The pattern (already folded by the host for TAD_STR_CONTAINS_NOCASE) lies in LDS.  TAD_STR_EQUAL: the
+// length, then the aligned 16-byte compare.  TAD_STR_CONTAINS_NOCASE: a plain search — for every start the value's bytes are taken as 8-byte
+// words from ALIGNED 8-byte loads (the two words under the start stay in registers while the start moves through them), folded and compared with
+// the pattern's words.  The matches are counted per wavefront, summed per workgroup in LDS, one atomic per workgroup.
+__global__ __launch_bounds__(kSdBlock) void k_sd_match(const ulonglong2 *__restrict__ recs, const uint8_t *__restrict__ arena, uint64_t K, int op,
+                                                       const uint8_t *__restrict__ pattern, uint32_t plen, uint8_t *__restrict__ out, unsigned long long *__restrict__ n_hit) {
+  __shared__ __attribute__((aligned(16))) uint64_t s_pat[kSdMaxPattern / 8 + 2];
+  __shared__ uint32_t s_cnt[kSdBlock / 64];
+  for (uint32_t i = threadIdx.x; i < kSdMaxPattern / 8 + 2; i += kSdBlock) s_pat[i] = 0ull;
+  __syncthreads();
+  uint8_t *pb = reinterpret_cast<uint8_t *>(s_pat);
+  for (uint32_t i = threadIdx.x; i < plen; i += kSdBlock) pb[i] = pattern[i];
+  __syncthreads();
+  uint32_t mine = 0;
+  const uint64_t first = plen ? se_load_lds(s_pat, 0, plen < 8 ? plen : 8) : 0ull;
+  for (uint64_t c = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; c < K; c += (uint64_t)gridDim.x * kSdBlock) {
+    const ulonglong2 r = recs[c];
+    const uint32_t len = sd_rec_len(r);
+    const uint8_t *q = arena + r.x;
+    bool hit;
+    if (op == TAD_STR_EQUAL) {
+      hit = len == plen && se_same_as([&](uint32_t o, uint32_t m) { return se_load_lds(s_pat, o, m); }, q, len);
+    } else if (plen == 0) {
+      hit = true;
+    } else if (len < plen) {
+      hit = false;
+    } else {
+      hit = false;
+      const uint64_t *w = reinterpret_cast<const uint64_t *>(q);      // 16-byte aligned, zero-padded to a multiple of 16
+      const uint32_t m0 = plen < 8 ? plen : 8;
+      const uint64_t keep0 = m0 < 8 ? (1ull << (m0 * 8)) - 1ull : ~0ull;
+      uint64_t cur = w[0], nxt = len > 8 ? w[1] : 0ull;
+      for (uint32_t i = 0; i + plen <= len && !hit; ++i) {
+        const uint32_t sk = i & 7u;
+        if (sk == 0 && i) { cur = nxt; nxt = i + 8 < len ? w[(i >> 3) + 1] : 0ull; }
+        uint64_t x = cur >> (sk * 8);
+        if (sk) x |= nxt << ((8 - sk) * 8);
+        if (sd_fold(x & keep0) != first) continue;
+        bool same = true;
+        for (uint32_t k = 8; k < plen && same; k += 8) {
+          const uint32_t m = plen - k < 8 ? plen - k : 8;
+          same = sd_fold(se_load(q + i + k, m)) == se_load_lds(s_pat, k, m);
+        }
+        hit = same;
+      }
+    }
+    out[c] = hit ? 1 : 0;
+    mine += hit ? 1u : 0u;
+  }
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
+  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t total = 0;
+#pragma unroll
+    for (int i = 0; i < kSdBlock / 64; ++i) total += s_cnt[i];
+    if (total) atomicAdd(n_hit, (unsigned long long)total);
+  }
+}
+
+// tad_strdict_export: cnt[i] = the length of value first + i (the scan of it gives Arrow's offsets) ...
+__global__ __launch_bounds__(kSdBlock) void k_sd_export_lens(const ulonglong2 *__restrict__ recs, uint64_t first, uint64_t n, uint32_t *__restrict__ cnt) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kSdBlock) cnt[i] = sd_rec_len(recs[first + i]);
+}
+
+// ... and the bytes packed behind each other: one lane per value; single bytes up to the destination's next 8-byte boundary, whole words from
+// there (se_load: the source is then misaligned by whatever the head took), single bytes for the tail.  `out` is 8-byte aligned.
+__global__ __launch_bounds__(kSdBlock) void k_sd_export(const ulonglong2 *__restrict__ recs, const uint8_t *__restrict__ arena, uint64_t first, uint64_t n,
+                                                        const unsigned long long *__restrict__ off, uint8_t *__restrict__ out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kSdBlock) {
+    const ulonglong2 r = recs[first + i];
+    const uint32_t len = sd_rec_len(r);
+    const uint8_t *q = arena + r.x;
+    uint8_t *d = out + off[i];
+    uint32_t k = 0;
+    const uint32_t head = (uint32_t)((8u - (uint32_t)(off[i] & 7ull)) & 7u);
+    for (; k < len && k < head; ++k) d[k] = q[k];
+    for (; k + 8 <= len; k += 8) *reinterpret_cast<uint64_t *>(d + k) = se_load(q + k, 8);
+    for (; k < len; ++k) d[k] = q[k];
+  }
+}
+
+static dim3 sd_grid(uint64_t items) { const uint64_t b = (items + kSdBlock - 1) / kSdBlock; return dim3((unsigned)(b < 16384 ? (b ? b : 1) : 16384)); }
+
+static StrArgs sd_args(const SdBatch &B) {
+  StrArgs A{};
+  A.off = B.offsets; A.data = B.data; A.valid = B.valid; A.valid_off = B.valid_off; A.n = B.n; A.data_bytes = B.data_bytes; A.off64 = B.off64;
+  return A;
+}
+
+void launch_sd_probe(hipStream_t s, const SdBatch &B, const unsigned long long *table, uint64_t slots, const void *recs, const uint8_t *arena, uint64_t K,
+                     long long *codes, uint8_t *miss, unsigned long long *n_miss, uint32_t *flags) {
+  const ulonglong2 *r = static_cast<const ulonglong2 *>(recs);
+  if (miss != nullptr) hipLaunchKernelGGL(k_sd_probe<true>, sd_grid(B.n), dim3(kSdBlock), 0, s, sd_args(B), table, slots - 1, r, arena, K, codes, miss, n_miss, flags);
+  else hipLaunchKernelGGL(k_sd_probe<false>, sd_grid(B.n), dim3(kSdBlock), 0, s, sd_args(B), table, slots - 1, r, arena, K, codes, miss, n_miss, flags);
+}
+
+void launch_sd_lens(hipStream_t s, const SdBatch &B, const uint64_t *first_row, const unsigned long long *num_new, uint64_t M, const uint32_t *se_flags, uint32_t *cnt) {
+  hipLaunchKernelGGL(k_sd_lens, sd_grid(M), dim3(kSdBlock), 0, s, sd_args(B), first_row, num_new, M, se_flags, cnt);
+}
+
+void launch_sd_append(hipStream_t s, const SdBatch &B, const uint64_t *first_row, const unsigned long long *off16, uint64_t m, uint64_t K0, uint64_t arena_used,
+                      unsigned long long *table, uint64_t slots, void *recs, uint8_t *arena, uint32_t *flags) {
+  hipLaunchKernelGGL(k_sd_append, sd_grid(m), dim3(kSdBlock), 0, s, sd_args(B), first_row, off16, m, K0, arena_used, table, slots - 1, static_cast<ulonglong2 *>(recs), arena,
+                     flags);
+}
+
+void launch_sd_fix(hipStream_t s, const uint8_t *miss, uint64_t n, uint64_t K0, long long *codes) {
+  hipLaunchKernelGGL(k_sd_fix, sd_grid(n), dim3(kSdBlock), 0, s, miss, n, K0, codes);
+}
+
+void launch_sd_rehash(hipStream_t s, const unsigned long long *old_table, uint64_t old_slots, const void *recs, uint64_t K, unsigned long long *table, uint64_t slots) {
+  hipLaunchKernelGGL(k_sd_rehash, sd_grid(old_slots), dim3(kSdBlock), 0, s, old_table, old_slots, static_cast<const ulonglong2 *>(recs), K, table, slots - 1);
+}
+
+void launch_sd_match(hipStream_t s, const void *recs, const uint8_t *arena, uint64_t K, int op, const uint8_t *pattern, uint32_t pattern_len, uint8_t *out,
+                     unsigned long long *n_hit) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_sd_match, sd_grid(K), dim3(kSdBlock), 0, s, static_cast<const ulonglong2 *>(recs), arena, K, op, pattern, pattern_len, out, n_hit);
+}
+
+void launch_sd_export_lens(hipStream_t s, const void *recs, uint64_t first, uint64_t n, uint32_t *cnt) {
+  hipLaunchKernelGGL(k_sd_export_lens, sd_grid(n), dim3(kSdBlock), 0, s, static_cast<const ulonglong2 *>(recs), first, n, cnt);
+}
+
+void launch_sd_export(hipStream_t s, const void *recs, const uint8_t *arena, uint64_t first, uint64_t n, const unsigned long long *off, uint8_t *out) {
+  hipLaunchKernelGGL(k_sd_export, sd_grid(n), dim3(kSdBlock), 0, s, static_cast<const ulonglong2 *>(recs), arena, first, n, off, out);
+}
+
+// one kernel of this translation unit: tad_engine_create resolves it so that the unit's code object is loaded before the first batch
+const void *code_anchor_strdict() { return reinterpret_cast<const void *>(&k_sd_fix); }
+
+}  // namespace tad

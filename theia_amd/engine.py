@@ -564,6 +564,57 @@ def _key_columns(engine, what, n_cols, cols_a, keep_a, cols_b, keep_b):
     return kc, n, 2 if pb is not None else 1, dev, keepalive
 
 
+def _string_column(column, what):
+    """An Arrow string column in any of the forms TadEngine.encode_strings takes -> (tad_string_column, n_rows, is_device, keepalive)"""
+    keepalive = []
+    validity, voff = None, 0
+    if hasattr(column, "combine_chunks") and hasattr(column, "chunks"):     # a pyarrow ChunkedArray: one contiguous column first
+        column = column.combine_chunks() if column.num_chunks != 1 else column.chunk(0)
+    if hasattr(column, "buffers") and hasattr(column, "type"):        # a pyarrow Array
+        import pyarrow as pa
+        t = column.type
+        if pa.types.is_string(t) or pa.types.is_binary(t):
+            bits = 32
+        elif pa.types.is_large_string(t) or pa.types.is_large_binary(t):
+            bits = 64
+        else:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, what + ": not a string / binary column: %s" % t)
+        vbuf, obuf, dbuf = column.buffers()
+        n, dev = len(column), False
+        off_ptr = obuf.address + column.offset * (bits // 8) if obuf is not None else None
+        data_ptr, data_bytes = (dbuf.address, dbuf.size) if dbuf is not None else (None, 0)
+        if vbuf is not None and column.null_count:
+            validity, voff = vbuf.address, column.offset
+        keepalive.append(column)
+        if n and off_ptr is None:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, what + ": the column has no offsets buffer")
+    else:
+        offsets, data = column[0], column[1]
+        if isinstance(offsets, DeviceArray):
+            dev, bits, n = True, offsets.dtype.itemsize * 8, offsets.n - 1
+            off_ptr, data_ptr, data_bytes = offsets.ptr, data.ptr, data.n * data.dtype.itemsize
+            if len(column) > 2 and column[2] is not None:
+                validity, voff = column[2].ptr, int(column[3]) if len(column) > 3 else 0
+        else:
+            dev = False
+            offsets = np.ascontiguousarray(offsets)
+            if offsets.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+                raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, what + ": offsets must be int32 or int64")
+            data = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data)
+            bits, n = offsets.dtype.itemsize * 8, offsets.size - 1
+            off_ptr, data_ptr, data_bytes = offsets.ctypes.data, (data.ctypes.data if data.size else None), data.size
+            if len(column) > 2 and column[2] is not None:
+                v = np.ascontiguousarray(column[2], dtype=np.uint8)
+                keepalive.append(v)
+                validity, voff = v.ctypes.data, int(column[3]) if len(column) > 3 else 0
+        keepalive += [offsets, data]
+    if n < 0:
+        raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, what + ": the offsets hold n + 1 entries")
+    sc = capi.StringColumn(n_rows=n, offsets=off_ptr, offset_bits=bits, data=data_ptr, data_bytes=data_bytes, validity=validity,
+                           validity_offset=voff, memory=capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST)
+    return sc, n, dev, keepalive
+
+
 class KeyDict:
     """A key dictionary that lives in HBM and outlives the call (tad_keydict): key tuples -> dense ids that stay the same from batch to
     batch, new ids in order of first appearance — what the streaming states want for their key ids.  n_cols: the tuple width;
@@ -730,6 +781,158 @@ class KeyDict:
     def close(self):
         if self._h is not None and self._engine._h is not None:
             self._engine._lib.tad_keydict_destroy(self._engine._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class StringDict:
+    """A string dictionary that lives in HBM and outlives the call (tad_strdict): the strings of an Arrow column -> codes that stay the
+    same from batch to batch, new codes in order of first appearance — the stable vocabulary a KeyDict wants for a string key column.
+    expected_values sizes the first table, expected_bytes the first arena (0 = the defaults, 1 = the smallest)."""
+
+    def __init__(self, engine, expected_values=0, expected_bytes=0):
+        self._engine = engine
+        self._h = None
+        if not (getattr(engine._lib, "tad_features", None) and engine._lib.tad_features() & capi.TAD_FEATURE_STRING_DICT):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no string dictionary (TAD_FEATURE_STRING_DICT)")
+        h = C.c_void_p()
+        engine._check(engine._lib.tad_strdict_create(engine._h, int(expected_values), int(expected_bytes), C.byref(h)))
+        self._h = h
+
+    def _out(self, out, x):
+        """x (a numpy array or a DeviceArray: the call's result, in the memory the column lives in) in the memory `out` names"""
+        if out == "device":
+            return x if isinstance(x, DeviceArray) else DeviceArray.from_host(self._engine, x)
+        return x.to_host() if isinstance(x, DeviceArray) else x
+
+    def encode(self, column, out="host", max_new=None):
+        """One batch.  column: every form TadEngine.encode_strings takes (a pyarrow string / binary array, or (offsets, data[, validity,
+        validity_offset]) as numpy arrays or DeviceArrays; a null encodes like "").  The call runs in the memory the column lives in; the
+        results are handed over in the memory `out` names ("host": numpy arrays, "device": DeviceArrays).  Returns (codes int64[n], new_first_row, num_before): a string the dictionary holds keeps its code, new
+        strings get num_before, num_before + 1, ... in order of first appearance; new_first_row[j] = the row of this batch where value
+        num_before + j first appears (at most max_new entries; None = all of them)."""
+        eng = self._engine
+        if out not in ("host", "device"):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "StringDict.encode: out must be host or device")
+        sc, n, dev, keepalive = _string_column(column, "StringDict.encode")
+        cap = int(max_new) if max_new is not None else n
+        before, after = capi.u64(), capi.u64()
+        if dev:
+            codes = DeviceArray(eng, max(n, 1), np.int64)
+            first = DeviceArray(eng, max(cap, 1), np.uint64)
+            ptrs = (codes.ptr, first.ptr)
+        else:
+            codes = np.empty(n, dtype=np.int64)
+            first = np.empty(max(cap, 1), dtype=np.uint64)
+            ptrs = (codes.ctypes.data, first.ctypes.data)
+        rc = eng._lib.tad_strdict_encode(eng._h, self._h, C.byref(sc), ptrs[0], ptrs[1], cap, C.byref(before), C.byref(after))
+        del keepalive
+        eng._check(rc)
+        listed = min(int(after.value - before.value), cap)
+        if dev:
+            codes.n, first.n = n, listed
+        else:
+            first = first[:listed]
+        return self._out(out, codes), self._out(out, first), int(before.value)
+
+    def lookup(self, column, out="host"):
+        """encode() read-only (tad_strdict_lookup): codes; an unknown string gets TAD_CODE_NONE (-1), the dictionary is unchanged"""
+        eng = self._engine
+        if out not in ("host", "device"):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "StringDict.lookup: out must be host or device")
+        sc, n, dev, keepalive = _string_column(column, "StringDict.lookup")
+        codes = DeviceArray(eng, max(n, 1), np.int64) if dev else np.empty(n, dtype=np.int64)
+        rc = eng._lib.tad_strdict_lookup(eng._h, self._h, C.byref(sc), codes.ptr if dev else codes.ctypes.data)
+        del keepalive
+        eng._check(rc)
+        if dev:
+            codes.n = n
+        return self._out(out, codes)
+
+    def num_values(self):
+        """values held (tad_strdict_num_values)"""
+        n = capi.u64()
+        self._engine._check(self._engine._lib.tad_strdict_num_values(self._engine._h, self._h, C.byref(n)))
+        return int(n.value)
+
+    def nbytes(self):
+        """device bytes the dictionary holds: table, records and arena at their capacity (tad_strdict_bytes)"""
+        n = capi.u64()
+        self._engine._check(self._engine._lib.tad_strdict_bytes(self._engine._h, self._h, C.byref(n)))
+        return int(n.value)
+
+    def export(self, first=0, n=None):
+        """(offsets int64[n + 1], data uint8[...]) of the values [first, first + n) in Arrow's layout (tad_strdict_export); n None = up
+        to the last value"""
+        eng = self._engine
+        if n is None:
+            n = max(self.num_values() - int(first), 0)
+        need = capi.u64()
+        eng._check(eng._lib.tad_strdict_export(eng._h, self._h, int(first), int(n), None, None, 0, C.byref(need)))
+        offsets = np.zeros(int(n) + 1, dtype=np.int64)
+        data = np.zeros(int(need.value), dtype=np.uint8)
+        eng._check(eng._lib.tad_strdict_export(eng._h, self._h, int(first), int(n), offsets.ctypes.data, data.ctypes.data if data.size else None, data.size,
+                                               C.byref(need)))
+        return offsets, data
+
+    def values(self, first=0, n=None):
+        """the values [first, first + n) as a pyarrow large_string array (n None = up to the last value): the strings the host needs for
+        decoding result rows"""
+        import pyarrow as pa
+        offsets, data = self.export(first, n)
+        return pa.Array.from_buffers(pa.large_string(), offsets.size - 1, [None, pa.py_buffer(offsets), pa.py_buffer(data)])
+
+    def load(self, values):
+        """Fill this EMPTY dictionary so that value i is string i (tad_strdict_import): what values() / export() returned, after a
+        restart.  values: a pyarrow string array, a sequence of str / bytes, or (offsets, data) as export() returns them.  Two equal
+        strings, or a dictionary that already holds values, are refused and nothing changes."""
+        eng = self._engine
+        if isinstance(values, tuple) and len(values) == 2 and hasattr(values[0], "dtype"):
+            offsets, data = np.ascontiguousarray(values[0], dtype=np.int64), np.ascontiguousarray(values[1], dtype=np.uint8)
+        else:
+            if hasattr(values, "to_pylist"):
+                values = values.to_pylist()
+            raw = [v if isinstance(v, (bytes, bytearray)) else ("" if v is None else str(v)).encode("utf-8") for v in values]
+            offsets = np.zeros(len(raw) + 1, dtype=np.int64)
+            np.cumsum([len(r) for r in raw], out=offsets[1:])
+            data = np.frombuffer(b"".join(raw), dtype=np.uint8)
+        n = offsets.size - 1
+        eng._check(eng._lib.tad_strdict_import(eng._h, self._h, n, offsets.ctypes.data if n else None, data.ctypes.data if data.size else None))
+
+    def match(self, op, pattern, out="host"):
+        """One byte per value (tad_strdict_match): mask[c] = 1 iff value c satisfies op with the pattern — capi.TAD_STR_EQUAL (the same
+        bytes) or capi.TAD_STR_CONTAINS_NOCASE (the pattern occurs in the value; 'A'..'Z' fold to 'a'..'z', every other byte matches
+        only itself).  pattern: str (UTF-8) or bytes, at most 1024 bytes.  Returns (mask, n_matched): mask a numpy uint8 array
+        (out="host") or a DeviceArray of num_values bytes (out="device": what KeyDict.select and TadEngine.mask_rows take)."""
+        eng = self._engine
+        if out not in ("host", "device"):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "StringDict.match: out must be host or device")
+        pat = pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern)
+        buf = (C.c_ubyte * max(len(pat), 1)).from_buffer_copy(pat or b"\0")
+        K = self.num_values()
+        dev = out == "device"
+        if dev:
+            mask = DeviceArray(eng, (K + 7) // 8 if K else 1, np.uint64)
+            ptr = mask.ptr
+        else:
+            mask = np.zeros(K, np.uint8)
+            ptr = mask.ctypes.data if K else None
+        hit = capi.u64()
+        rc = eng._lib.tad_strdict_match(eng._h, self._h, int(op), C.cast(buf, C.c_void_p) if pat else None, len(pat), ptr if K else None, K,
+                                        capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST, C.byref(hit))
+        eng._check(rc)
+        if dev:
+            mask = mask.view(0, K, np.uint8)
+        return mask, int(hit.value)
+
+    def close(self):
+        if self._h is not None and self._engine._h is not None:
+            self._engine._lib.tad_strdict_destroy(self._engine._h, self._h)
         self._h = None
 
     def __del__(self):
@@ -1247,6 +1450,11 @@ class TadEngine:
         when num_keys grew, then run_stream / merge_stream with num_keys = the dictionary's."""
         return KeyDict(self, n_cols, expected_keys)
 
+    def string_dict(self, expected_values=0, expected_bytes=0):
+        """A persistent string dictionary (StringDict): encode every batch's string key column through it and hand the codes to the
+        KeyDict; its match() masks are KeyDict.select's terms."""
+        return StringDict(self, expected_values, expected_bytes)
+
     # ---- ingest, one step earlier: an Arrow string column -> dictionary codes (tad_encode_strings) ----
     def encode_strings(self, column, max_values=None):
         """column: a pyarrow string / large_string / binary / large_binary Array (host memory; slices and nulls are fine: a null encodes like
@@ -1254,53 +1462,8 @@ class TadEngine:
         uint8), or DeviceArrays on the device (offsets as int32 / int64 elements).  Returns (codes int64[n], first_row u64[num_values]): codes
         in order of first appearance (pyarrow.compute.dictionary_encode's, pandas.factorize's), first_row[k] = the row where value k
         first appears — in the memory the input lives in."""
-        keepalive = []
-        validity, voff = None, 0
-        if hasattr(column, "combine_chunks") and hasattr(column, "chunks"):     # a pyarrow ChunkedArray: one contiguous column first
-            column = column.combine_chunks() if column.num_chunks != 1 else column.chunk(0)
-        if hasattr(column, "buffers") and hasattr(column, "type"):        # a pyarrow Array
-            import pyarrow as pa
-            t = column.type
-            if pa.types.is_string(t) or pa.types.is_binary(t):
-                bits = 32
-            elif pa.types.is_large_string(t) or pa.types.is_large_binary(t):
-                bits = 64
-            else:
-                raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "encode_strings: not a string / binary column: %s" % t)
-            vbuf, obuf, dbuf = column.buffers()
-            n, dev = len(column), False
-            off_ptr = obuf.address + column.offset * (bits // 8) if obuf is not None else None
-            data_ptr, data_bytes = (dbuf.address, dbuf.size) if dbuf is not None else (None, 0)
-            if vbuf is not None and column.null_count:
-                validity, voff = vbuf.address, column.offset
-            keepalive.append(column)
-            if n and off_ptr is None:
-                raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "encode_strings: the column has no offsets buffer")
-        else:
-            offsets, data = column[0], column[1]
-            if isinstance(offsets, DeviceArray):
-                dev, bits, n = True, offsets.dtype.itemsize * 8, offsets.n - 1
-                off_ptr, data_ptr, data_bytes = offsets.ptr, data.ptr, data.n * data.dtype.itemsize
-                if len(column) > 2 and column[2] is not None:
-                    validity, voff = column[2].ptr, int(column[3]) if len(column) > 3 else 0
-            else:
-                dev = False
-                offsets = np.ascontiguousarray(offsets)
-                if offsets.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
-                    raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "encode_strings: offsets must be int32 or int64")
-                data = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data)
-                bits, n = offsets.dtype.itemsize * 8, offsets.size - 1
-                off_ptr, data_ptr, data_bytes = offsets.ctypes.data, (data.ctypes.data if data.size else None), data.size
-                if len(column) > 2 and column[2] is not None:
-                    v = np.ascontiguousarray(column[2], dtype=np.uint8)
-                    keepalive.append(v)
-                    validity, voff = v.ctypes.data, int(column[3]) if len(column) > 3 else 0
-            keepalive += [offsets, data]
-        if n < 0:
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "encode_strings: the offsets hold n + 1 entries")
+        sc, n, dev, keepalive = _string_column(column, "encode_strings")
         cap = int(max_values) if max_values is not None else n
-        sc = capi.StringColumn(n_rows=n, offsets=off_ptr, offset_bits=bits, data=data_ptr, data_bytes=data_bytes, validity=validity,
-                               validity_offset=voff, memory=capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST)
         nv = capi.u64()
         if dev:
             codes = DeviceArray(self, max(n, 1), np.int64)

@@ -3,48 +3,56 @@
 `anomaly_detection` (anomaly_detection.py) answers one job from the flow table: it reads the rows, applies the job's filters and runs
 the batch job.  A `StreamingAnomalyDetection` is fed the flow rows as they arrive — in any order — and answers the same jobs from what it
 keeps on the device: a key dictionary (KeyDict: the mode's key tuples -> stable ids), a series state (TadState with history and times,
-fed through TadEngine.merge_stream) and, on the host, one vocabulary per string column and the key table.
+fed through TadEngine.merge_stream), one string dictionary per string key column (StringDict: strings -> stable codes, in HBM as well) and,
+on the host, the key table.
 
 The job's name filters (--pod-name, --pod-namespace, --pod-label, --external-ip, --svc-port-name) are predicates on KEY columns of the
-mode, so a job is a key selection: the filter is evaluated once per distinct string of the vocabulary (equality is one code, ilike
-goes over the distinct label strings), KeyDict.select turns the vocabulary masks into a key mask on the device, and
+mode, so a job is a key selection: the filter is evaluated once per distinct string of the vocabulary, on the device (StringDict.match:
+equality, and ilike '%label%' as a case-folded substring search), KeyDict.select turns the vocabulary masks into a key mask there, and
 TadEngine.run_state_keys judges the selected keys only.  The predicates that are NOT key predicates — the namespace ignore list (it tests
 both namespaces of a row), flowType = 3 in external mode, the `<> ''` rules — are applied to the rows in `feed`, before they reach the
 state.  Mode None (no aggregation) has no key filter to serve and is not offered.
 """
 import numpy as np
 
+from . import _capi
 from . import anomaly_detection as _ad
 
 MODES = ("svc", "external", "pod")
 
 
-class _Vocabulary:
-    """string -> code; a string keeps the code it was first given (new strings of a batch get the next codes in their sorted order)"""
-
-    def __init__(self):
-        self.code = {}
-        self.values = []
-
-    def encode(self, strings):
-        uniq, inv = np.unique(np.asarray(strings).astype(str), return_inverse=True)
-        codes = np.empty(uniq.size, dtype=np.int64)
-        for i, s in enumerate(uniq.tolist()):
-            c = self.code.get(s)
-            if c is None:
-                c = self.code[s] = len(self.values)
-                self.values.append(s)
-            codes[i] = c
-        return codes[inv]
-
-    def mask(self, predicate):
-        """one byte per code: predicate(string)"""
-        return np.fromiter((1 if predicate(s) else 0 for s in self.values), dtype=np.uint8, count=len(self.values))
+def _arrow(strings):
+    """a numpy array of str -> (offsets int64[n + 1], data uint8[...]): the column in Arrow's layout, UTF-8"""
+    raw = np.char.encode(np.asarray(strings).astype(str), "utf-8")
+    offsets = np.zeros(raw.size + 1, dtype=np.int64)
+    np.cumsum(np.char.str_len(raw), out=offsets[1:])
+    return offsets, np.frombuffer(b"".join(raw.tolist()), dtype=np.uint8)
 
 
 def _strings(flows, name):
     c = _ad._str_col(flows, name)
     return c.materialise() if isinstance(c, _ad.DictColumn) else c
+
+
+def _encode(vocab, flows, name):
+    """the rows' codes (int64[n], host) of a string column through its StringDict: a DictColumn is encoded through its distinct values
+    and mapped, a plain column goes to the device as it is.  No string is hashed or compared on the host."""
+    c = _ad._str_col(flows, name)
+    if isinstance(c, _ad.DictColumn):
+        if not c.values.size:
+            return np.zeros(c.codes.size, dtype=np.int64)
+        return vocab.encode(_arrow(c.values))[0][c.codes]
+    return vocab.encode(_arrow(c))[0]
+
+
+def _string_at(flows, name, row):
+    c = flows[name]
+    return str(c.values[c.codes[row]]) if isinstance(c, _ad.DictColumn) else str(np.asarray(c)[row])
+
+
+def _code_of(vocab, s):
+    """the code the dictionary holds for s, or -1"""
+    return int(vocab.lookup(_arrow([s]))[0])
 
 
 class StreamingAnomalyDetection:
@@ -54,7 +62,10 @@ class StreamingAnomalyDetection:
     rows as they are fed.  `job` returns what anomaly_detection returns for the same arguments over all rows fed so far.  One
     difference at the edge: in pod mode the feed drops the rows of a side whose labels / name are '' (the query's `<> ''` rule for a
     job without a pod filter), while the batch query with a pod_label or pod_name filter applies only that filter — so a pattern that
-    matches the empty string, such as pod_label='%', finds the '' keys in the batch job and not here."""
+    matches the empty string, such as pod_label='%', finds the '' keys in the batch job and not here.  The label filter runs on the
+    device when pod_label is ASCII and free of %, _ and \\ (StringDict.match folds the bytes 'A'..'Z' to 'a'..'z' and nothing else: on
+    ASCII strings, which is what Kubernetes allows in labels, exactly ilike '%label%'); any other pattern is evaluated on the host over
+    the exported label strings, with the regex the batch job uses."""
 
     def __init__(self, engine=None, agg_flow="svc", pod_ident="labels", ns_ignore_list=()):
         if agg_flow not in MODES:
@@ -66,7 +77,7 @@ class StreamingAnomalyDetection:
         self.pod_ident = pod_ident
         self.ns_ignore_list = tuple(ns_ignore_list or ())
         self.mode = ("podname" if pod_ident == "name" else "pod") if agg_flow == "pod" else agg_flow
-        self._vocab = [_Vocabulary() for _ in range(2 if agg_flow == "pod" else 1)]     # pod: namespaces, labels / names
+        self._vocab = [self._engine.string_dict() for _ in range(2 if agg_flow == "pod" else 1)]     # pod: namespaces, labels / names
         self._dict = self._engine.key_dict(len(self._vocab))
         self._state = None
         self._keys = [[] for _ in _ad.KEY_COLUMNS[self.mode]]      # the host key table: key id -> the mode's key columns
@@ -94,55 +105,61 @@ class StreamingAnomalyDetection:
             ident = "PodName" if self.pod_ident == "name" else "PodLabels"
             sides = []
             for side in ("destination", "source"):                 # side a = inbound, side b = outbound
-                col = _strings(flows, side + ident)
-                sides.append(([self._vocab[0].encode(_strings(flows, side + "PodNamespace")), self._vocab[1].encode(col)], keep & (col != "")))
+                codes = [_encode(self._vocab[0], flows, side + "PodNamespace"), _encode(self._vocab[1], flows, side + ident)]
+                sides.append((codes, keep & (codes[1] != _code_of(self._vocab[1], ""))))
             if not (sides[0][1].any() or sides[1][1].any()):
                 return None
             key, key2, first, _ = self._dict.encode(sides[0][0], sides[0][1], sides[1][0], sides[1][1])
-            for v in np.asarray(first).tolist():
+            for v in np.asarray(first).tolist():                   # the host key table: the new keys' strings, read at their first rows
                 b = v >= n
-                cols = sides[1 if b else 0][0]
+                side = "source" if b else "destination"
                 row = v - n if b else v
-                self._keys[0].append(self._vocab[0].values[cols[0][row]])
-                self._keys[1].append(self._vocab[1].values[cols[1][row]])
+                self._keys[0].append(_string_at(flows, side + "PodNamespace", row))
+                self._keys[1].append(_string_at(flows, side + ident, row))
                 self._keys[2].append("outbound" if b else "inbound")
         else:
             name = "destinationIP" if self.agg_flow == "external" else "destinationServicePortName"
-            col = _strings(flows, name)
+            codes = _encode(self._vocab[0], flows, name)
             if self.agg_flow == "external":
                 keep &= np.asarray(flows["flowType"]).astype(np.int64) == 3
             else:
-                keep &= col != ""
+                keep &= codes != _code_of(self._vocab[0], "")
             if not keep.any():
                 return None
-            codes = self._vocab[0].encode(col)
             key, key2, first, _ = self._dict.encode([codes], keep)
-            self._keys[0] += [self._vocab[0].values[codes[v]] for v in np.asarray(first).tolist()]
+            self._keys[0] += [_string_at(flows, name, v) for v in np.asarray(first).tolist()]
         if self._state is None:
             self._state = eng.state_create(self.num_keys, history=True, series=True, times=True)
         elif self.num_keys > self._state.num_keys:
             self._state.resize(self.num_keys)
         return eng.merge_stream(self._state, key, flow_end, value, agg_flow=self.agg_flow, key_id2=key2)
 
+    def _equal(self, col, s):
+        return col, self._vocab[col].match(_capi.TAD_STR_EQUAL, s, out="device")[0]
+
     def _terms(self, pod_label, pod_name, pod_namespace, external_ip, svc_port_name):
-        """the job's name filters as (key column, vocabulary mask) terms of KeyDict.select"""
+        """the job's name filters as (key column, vocabulary mask) terms of KeyDict.select; the masks are computed on the device"""
         if self.agg_flow == "external":
-            return [(0, self._vocab[0].mask(lambda s: s == external_ip))] if external_ip else []
+            return [self._equal(0, external_ip)] if external_ip else []
         if self.agg_flow == "svc":
-            return [(0, self._vocab[0].mask(lambda s: s == svc_port_name))] if svc_port_name else []
+            return [self._equal(0, svc_port_name)] if svc_port_name else []
         by_name = bool(pod_name) and not pod_label
         if by_name != (self.pod_ident == "name"):
             raise ValueError("this instance keys the pods by their %s: it serves jobs %s" %
                              (self.pod_ident, "with pod_name" if self.pod_ident == "name" else "with pod_label or without a pod filter"))
         if pod_label:
-            rx = _ad._like_regex("%" + pod_label + "%")
-            terms = [(1, self._vocab[1].mask(lambda s: rx.match(s) is not None))]
+            if pod_label.isascii() and not any(c in pod_label for c in "%_\\") and len(pod_label) <= 1024:
+                terms = [(1, self._vocab[1].match(_capi.TAD_STR_CONTAINS_NOCASE, pod_label, out="device")[0])]
+            else:                                                  # wildcards or non-ASCII case folding: the batch job's regex over the exported labels
+                rx = _ad._like_regex("%" + pod_label + "%")
+                labels = self._vocab[1].values().to_pylist()
+                terms = [(1, np.fromiter((1 if rx.match(s) is not None else 0 for s in labels), dtype=np.uint8, count=len(labels)))]
         elif pod_name:
-            terms = [(1, self._vocab[1].mask(lambda s: s == pod_name))]
+            terms = [self._equal(1, pod_name)]
         else:
             return []
         if pod_namespace:
-            terms.append((0, self._vocab[0].mask(lambda s: s == pod_namespace)))
+            terms.append(self._equal(0, pod_namespace))
         return terms
 
     def job(self, algo_type, tad_id, end_time="", pod_label="", pod_name="", pod_namespace="", external_ip="", svc_port_name=""):
@@ -166,3 +183,5 @@ class StreamingAnomalyDetection:
             self._state.close()
             self._state = None
         self._dict.close()
+        for v in self._vocab:
+            v.close()

@@ -115,7 +115,7 @@ def test_the_unit_is_hip_in_its_own_source():
         assert name in src, name
     assert "asm" not in src and "rocprim" not in src.lower() and "hipcub" not in src.lower()
     assert re.findall(r"#include\s+[<\"]([^>\"]+)[>\"]", src) == ["tad_internal.h"]
-    host = "".join(open(os.path.join(ROOT, "theia_amd", "csrc", f)).read() for f in ("tad_capi.cpp", "tad_capi_state.cpp", "tad_capi_keydict.cpp"))
+    host = "".join(open(os.path.join(ROOT, "theia_amd", "csrc", f)).read() for f in ("tad_capi.cpp", "tad_capi_view.cpp", "tad_capi_state.cpp", "tad_capi_keydict.cpp"))
     assert "int tad_state_compact(" in host and "int tad_keydict_compact(" in host and "launch_scan(" in host and "launch_kd_rehash(" in host
 
 

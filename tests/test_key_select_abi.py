@@ -115,7 +115,7 @@ def test_the_kernels_are_hip_in_the_units_the_design_names():
     kd = open(os.path.join(csrc, "tad_keydict.hip")).read()
     assert "k_kd_select" in kd and "launch_kd_select" in kd and "asm" not in kd and "rocprim" not in kd.lower()
     assert "launch_kd_select" in open(os.path.join(csrc, "tad_capi_keydict.cpp")).read()
-    host = open(os.path.join(csrc, "tad_capi.cpp")).read()
+    host = open(os.path.join(csrc, "tad_capi_view.cpp")).read()
     assert "int tad_run_state_keys(" in host and "int tad_drop_state_keys(" in host
     assert "TAD_FEATURE_KEY_SELECT" in open(os.path.join(csrc, "tad_engine.cpp")).read()
 

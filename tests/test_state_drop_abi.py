@@ -99,7 +99,7 @@ def test_the_unit_is_hip_in_its_own_source():
     assert "fma(" not in src                                                                # d * d and the add stay two operations
     assert re.findall(r"#include\s+[<\"]([^>\"]+)[>\"]", src) == ["stdint.h", "tad_internal.h"]
     csrc = os.path.join(ROOT, "theia_amd", "csrc")
-    host = open(os.path.join(csrc, "tad_capi.cpp")).read()
+    host = "".join(open(os.path.join(csrc, f)).read() for f in ("tad_capi.cpp", "tad_capi_view.cpp"))
     assert "int tad_drop_state(" in host and "int tad_drop_stream(" in host and "launch_ds_stats(" in host and "launch_win_route(" in host
     assert "code_anchor_drop_state()" in open(os.path.join(csrc, "tad_engine.cpp")).read()
     # the old entry points still refuse DROP

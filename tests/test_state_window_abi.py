@@ -97,7 +97,12 @@ def test_history_rule_is_the_documented_function_of_the_two_totals():
     for P, S, by_sort in ((0, 0, 1), (0, 10, 1), (1, 2, 1), (5, 10, 1), (6, 11, 0), (5, 9, 0), (10, 10, 0), (1 << 40, 1 << 41, 1),
                           ((1 << 40) + 1, 1 << 41, 0), (1, 1, 0)):
         assert lib.tad_window_history_by_sort(P, S) == by_sort, (P, S)
-    src = open(os.path.join(ROOT, "theia_amd", "csrc", "tad_capi.cpp")).read()
-    body = src[src.index("int tad_run_state_window("):]
-    assert "win_hist_by_sort(P, S)" in body[:body.index("\n}\n")]            # the call decides with the same function
-    assert "return win_hist_by_sort(window_points, state_points)" in src
+    src = open(os.path.join(ROOT, "theia_amd", "csrc", "tad_capi_view.cpp")).read()
+
+    def body_of(head):
+        body = src[src.index(head):]
+        return body[:body.index("\n}\n")]
+    assert "win_hist_by_sort(P, S)" in body_of("int view_call(")             # the one call path decides with the same function,
+    for name in ("tad_run_state_window", "tad_run_state_keys"):               # both window calls go through it,
+        assert "view_call(eng, st, job, \"%s\"" % name in body_of("int %s(" % name), name
+    assert "return win_hist_by_sort(window_points, state_points)" in src      # and the exported function returns its result

@@ -1,7 +1,8 @@
 // tad_capi.cpp — what the entry points of include/tad.h share (key buffers, the rows result and its epilogue, the moments' merge), the batches
-// on a streaming state that the job's count pass runs (history, series, merge, ARIMA, DROP), and the state calls: tad_run_state,
-// tad_run_state_window, tad_drop_state, their *_keys forms, tad_drop_stream, tad_state_merge.  The batch job itself (run_job_locked: lattice, Stage 0, count,
-// retries) is tad_capi_job.cpp; the life of a tad_state is tad_capi_state.cpp.
+// on a streaming state that the job's count pass runs (history, series, merge, ARIMA, DROP), and the two calls that feed the job such a
+// batch: tad_drop_stream, tad_state_merge.  The batch job itself (run_job_locked: lattice, Stage 0, count, retries) is tad_capi_job.cpp;
+// the read-only jobs on a state (tad_run_state, tad_run_state_window, tad_drop_state, their *_keys forms) are tad_capi_view.cpp; the life
+// of a tad_state is tad_capi_state.cpp.
 #include "tad_engine.h"
 
 using namespace tad;
@@ -210,6 +211,41 @@ static void batch_points(JobCtx *e, Grid g, Lattice L, const unsigned long long 
   }
 }
 
+static int ensure_hist_verdicts(JobCtx *e, uint64_t P_cap) {   // per point: noise u8 | cnt u32 | row u64 (+ 1)
+  const uint64_t pc = P_cap ? P_cap : 1;
+  int rc;
+  if ((rc = ensure(e, e->hs_noise, pc)) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->hs_cnt, pc * 4)) != TAD_OK) return rc;
+  return ensure(e, e->hs_row, (pc + 1) * 8);
+}
+
+// DBSCAN's verdicts of the points hb names (nk, nv, P_dev, P_cap) against the history (hoff, hval), and their rows: the row total lands in
+// the job's tail.  The scan's scratch is the caller's (e->scan_scratch, sized for P_cap).  No point, no launch: hb keeps no verdicts.
+int hist_verdicts(JobCtx *e, const unsigned long long *hoff, const unsigned long long *hval, const JobParams &jp, HistBatch *hb) {
+  int rc;
+  if ((rc = ensure_hist_verdicts(e, hb->P_cap)) != TAD_OK) return rc;
+  if (hb->P_cap == 0) return TAD_OK;
+  uint8_t *noise = static_cast<uint8_t *>(e->hs_noise.p);
+  uint32_t *cnt = static_cast<uint32_t *>(e->hs_cnt.p);
+  unsigned long long *row = static_cast<unsigned long long *>(e->hs_row.p);
+  launch_hist_verdict(e->stream, hb->nk, hb->nv, hb->P_dev, hb->P_cap, hoff, hval, jp.eps, jp.min_samples, jp.all_points, noise, cnt);
+  launch_scan(e->stream, cnt, row, hb->P_cap, static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
+  hb->noise = noise; hb->cnt = cnt; hb->row = row;
+  return TAD_OK;
+}
+
+// The rows of a batch of points that DBSCAN, ARIMA or DROP judged (hist_verdicts, stream_arima_batch, state_drop_batch); mom: the moments
+// DBSCAN's stddev column comes from.  EWMA's emits are its callers' own.
+void emit_point_rows(hipStream_t s, const JobParams &jp, const HistBatch &hb, const ArimaBatch &ab, const DropBatch &db, const StreamState &mom,
+                     OutRows out) {
+  if (jp.algo == TAD_ALGO_ARIMA)
+    launch_as_emit(s, ab.P, hb.nk, hb.nt, hb.nv, ab.tidx, ab.sigma, ab.pcalc, ab.pflag, ab.rows, ab.row_off, jp.all_points, out);
+  else if (jp.algo == TAD_ALGO_DBSCAN)
+    launch_hist_emit(s, hb.nk, hb.nt, hb.nv, hb.P_dev, hb.P_cap, hb.noise, hb.cnt, hb.row, mom, jp.all_points, out);
+  else if (jp.algo == TAD_ALGO_DROP)
+    launch_ds_emit(s, hb.nk, hb.nt, hb.nv, hb.P_dev, hb.P_cap, db.flag, db.cnt, db.row, db.keys, jp.all_points, out);
+}
+
 // One batch on a history and / or series state (tad.h, TAD_STATE_HISTORY / TAD_STATE_SERIES), after the stream count pass and before the
 // job's tail is read: the batch's new points in (key, time) order; a history state sorts them per key and merges them with the current
 // history into the candidate arena (tad_history.hip); a series state appends them to every key's series in the candidate arena; a DBSCAN
@@ -228,13 +264,8 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
   // the candidate arenas first: an allocation failure leaves the state, its history and its series as they are
   const uint64_t need = st->hist.len[cur] + P_cap;
   if ((rc = state_grow_candidates(e, st, P_cap)) != TAD_OK) return rc;
-  const uint64_t pc = P_cap ? P_cap : 1;
   if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr)) != TAD_OK) return rc;
-  if (dbscan) {
-    if ((rc = ensure(e, e->hs_noise, pc)) != TAD_OK) return rc;
-    if ((rc = ensure(e, e->hs_cnt, pc * 4)) != TAD_OK) return rc;
-    if ((rc = ensure(e, e->hs_row, (pc + 1) * 8)) != TAD_OK) return rc;
-  }
+  if (dbscan && (rc = ensure_hist_verdicts(e, P_cap)) != TAD_OK) return rc;   // (before the first launch: hist_verdicts then allocates nothing)
   unsigned long long *nk = static_cast<unsigned long long *>(e->hs_key.p);
   long long *nt = static_cast<long long *>(e->hs_t.p);
   unsigned long long *ns = static_cast<unsigned long long *>(e->hs_sorted.p);
@@ -256,15 +287,8 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
                          reinterpret_cast<const unsigned long long *>(nt), st->ser.off[cand], reinterpret_cast<unsigned long long *>(st->ser_times.p[cand]));
   HIP_TRY(e, hipMemcpyAsync(static_cast<unsigned char *>(e->counters.p) + kTailHistLen, poff + K, 8, hipMemcpyDeviceToDevice, s));
   hb->nk = nk; hb->nt = nt; hb->nv = nv; hb->poff = poff; hb->P_dev = poff + K; hb->P_cap = P_cap;
-  if (dbscan && P_cap) {   // 4. verdicts of the new points; 5. their rows (the row total lands in the job's tail)
-    uint8_t *noise = static_cast<uint8_t *>(e->hs_noise.p);
-    uint32_t *cnt = static_cast<uint32_t *>(e->hs_cnt.p);
-    unsigned long long *row = static_cast<unsigned long long *>(e->hs_row.p);
-    launch_hist_verdict(s, nk, nv, poff + K, P_cap, st->hist.off[cand], st->hist.val.p[cand], jp.eps, jp.min_samples, jp.all_points, noise, cnt);
-    launch_scan(s, cnt, row, P_cap, scratch, dev_total(e));
-    hb->noise = noise; hb->cnt = cnt; hb->row = row;
-  }
-  return TAD_OK;
+  // 4. verdicts of the new points against the merged history; 5. their rows
+  return dbscan ? hist_verdicts(e, st->hist.off[cand], st->hist.val.p[cand], jp, hb) : TAD_OK;
 }
 
 // One tad_state_merge batch (tad.h; kernels in tad_merge.hip), in the place of a stream batch's count pass: the batch's points in (key, time)
@@ -521,373 +545,9 @@ int state_drop_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const J
   return TAD_OK;
 }
 
-// the start of a tad_run_state / tad_run_state_window job on the context the caller holds: progress, the first event, the job tail zeroed
-static int run_view_begin(JobCtx *e, uint64_t K) {
-  e->done.store(0);
-  e->total.store(4);
-  e->arima_relaunches = 0;
-  int rc;
-  if ((rc = ensure_key_buffers(e, K)) != TAD_OK) return rc;
-  HIP_TRY(e, hipEventRecord(e->ev[0], e->stream));
-  HIP_TRY(e, hipMemsetAsync(e->counters.p, 0, kTailBytes, e->stream));
-  return TAD_OK;
-}
-
-// tad_run_state / tad_run_state_window after run_view_begin (tad.h; kernels: tad_window.hip).  Reads the view only: the state's CURRENT
-// copies, or a window's view in this context's workspace (wv_key / wv_pts, which nothing below resizes).  EWMA walks the CSR series;
-// DBSCAN, ARIMA and DROP (tad_drop_state: its view carries no moments) run the stream's kernels with every series point named as new
-// (poff = the series offsets).  view_syncs: the host synchronisations the caller spent on building the view (tad_stats.host_syncs).
-static int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem out_memory, tad_result **out, int view_syncs) {
-  hipStream_t s = e->stream;
-  JobParams jp = job_params(job);
-  const uint64_t K = v.K;
-  const uint64_t P = v.P;
-  const unsigned long long *soff = v.soff, *sval = v.sval;
-  const long long *stt = v.st;
-  const StreamState view = v.mom;
-  int rc;
-  DevCounters *ctr = static_cast<DevCounters *>(e->counters.p);
-  unsigned long long *tmin_dev = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(e->counters.p) + kTailHistLen);
-  uint64_t rows = 0;
-  HistBatch hist;
-  ArimaBatch ab;
-  DropBatch db;
-  const bool ewma = jp.algo == TAD_ALGO_EWMA;
-  unsigned long long coop_min = 0;
-  uint32_t *list = nullptr;
-  unsigned int *lcount = nullptr;
-  const unsigned long long *off = soff;   // EWMA with every point: the row offsets are the series offsets
-  if (P) {
-    const size_t kpad = (size_t)((K + 3) & ~3ull);
-    if ((rc = ensure(e, e->hs_kcnt, kpad * 4 + 64)) != TAD_OK) return rc;   // the long keys' list | its length
-    if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K > P ? K : P) * sizeof(unsigned long long))) != TAD_OK) return rc;
-    list = static_cast<uint32_t *>(e->hs_kcnt.p);
-    lcount = reinterpret_cast<unsigned int *>(list + kpad);
-    unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
-    coop_min = win_coop_min(K, P);
-    launch_win_route(s, K, soff, stt, coop_min, list, lcount, tmin_dev);
-    if (jp.algo != TAD_ALGO_DROP) launch_moments(s, K, view.n, view.avg, view.m2, dev_moments(e), ctr);   // (and n_keys / n_points)
-    if (ewma) {
-      if (!jp.all_points) {
-        launch_win_ewma(s, K, soff, sval, stt, view, jp.alpha, coop_min, list, lcount, false, false, static_cast<uint32_t *>(e->n_anom.p), nullptr, OutRows{});
-        launch_scan(s, static_cast<const uint32_t *>(e->n_anom.p), static_cast<unsigned long long *>(e->off.p), K, scratch, dev_total(e));
-        off = static_cast<const unsigned long long *>(e->off.p);
-      }
-    } else {
-      if ((rc = ensure(e, e->hs_key, P * 8)) != TAD_OK) return rc;
-      unsigned long long *nk = static_cast<unsigned long long *>(e->hs_key.p);
-      launch_win_keys(s, K, soff, nk);
-      hist.nk = nk; hist.nv = sval; hist.nt = stt; hist.poff = soff; hist.P_dev = soff + K; hist.P_cap = P;
-      if (jp.algo == TAD_ALGO_DBSCAN) {
-        if ((rc = ensure(e, e->hs_noise, P)) != TAD_OK) return rc;
-        if ((rc = ensure(e, e->hs_cnt, P * 4)) != TAD_OK) return rc;
-        if ((rc = ensure(e, e->hs_row, (P + 1) * 8)) != TAD_OK) return rc;
-        uint8_t *noise = static_cast<uint8_t *>(e->hs_noise.p);
-        uint32_t *cnt = static_cast<uint32_t *>(e->hs_cnt.p);
-        unsigned long long *row = static_cast<unsigned long long *>(e->hs_row.p);
-        launch_hist_verdict(s, nk, sval, hist.P_dev, P, v.hoff, v.hval, jp.eps, jp.min_samples, jp.all_points, noise, cnt);
-        launch_scan(s, cnt, row, P, scratch, dev_total(e));
-        hist.noise = noise; hist.cnt = cnt; hist.row = row;
-      } else if (jp.algo == TAD_ALGO_DROP) {
-        if ((rc = state_drop_batch(e, v, hist, jp, false, coop_min, list, lcount, ctr, &db)) != TAD_OK) return rc;
-      } else if ((rc = stream_arima_batch(e, v, hist, jp, ctr, &ab)) != TAD_OK) {
-        return rc;
-      }
-    }
-  }
-  e->done.store(2);
-  HIP_TRY(e, hipMemcpyAsync(e->tail_host, e->counters.p, kTailBytes, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipStreamSynchronize(s));
-  HIP_TRY(e, hipGetLastError());
-  rows = (ewma && jp.all_points) ? P : (P ? *e->total_host : 0);
-  const DevCounters c = *e->ctr_host;
-  e->done.store(3);
-
-  RowsOut ro;
-  if ((rc = make_result(e, rows, jp.all_points, out_memory, &ro.rp, &ro.dev_rows, &ro.dev_block)) != TAD_OK) return rc;
-  const OutRows dev_rows = ro.dev_rows;
-  if (rows && ewma)
-    launch_win_ewma(s, K, soff, sval, stt, view, jp.alpha, coop_min, list, lcount, true, jp.all_points, nullptr, off, dev_rows, rows, e->plan.ewma_emit,
-                    e->plan.ewma_emit_rows);
-  else if (rows && jp.algo == TAD_ALGO_DBSCAN)
-    launch_hist_emit(s, hist.nk, hist.nt, hist.nv, hist.P_dev, hist.P_cap, hist.noise, hist.cnt, hist.row, view, jp.all_points, dev_rows);
-  else if (rows && jp.algo == TAD_ALGO_DROP)
-    launch_ds_emit(s, hist.nk, hist.nt, hist.nv, hist.P_dev, hist.P_cap, db.flag, db.cnt, db.row, db.keys, jp.all_points, dev_rows);
-  else if (rows)
-    launch_as_emit(s, ab.P, hist.nk, hist.nt, hist.nv, ab.tidx, ab.sigma, ab.pcalc, ab.pflag, ab.rows, ab.row_off, jp.all_points, dev_rows);
-  if ((rc = finish_rows(e, job, &ro, rows, jp.all_points, c, P != 0)) != TAD_OK) return rc;
-  tad_stats &rs = ro.rp->pub.stats;
-  rs.rows_in = rs.rows_used = rs.n_points = P;
-  {
-    unsigned long long tmin = ~0ull;
-    memcpy(&tmin, e->tail_host + kTailHistLen, 8);
-    rs.t0 = (P && tmin != ~0ull) ? (int64_t)(tmin ^ (1ull << 63)) : 0;
-  }
-  hipEventElapsedTime(&rs.ms_total, e->ev[0], e->ev[4]);
-  rs.ms_detect = rs.ms_total;   // no Stage 0 ran: the whole call is the detector and its emit
-  rs.host_syncs = 2 + view_syncs;
-  e->done.store(4);
-  *out = &ro.rp->pub;
-  return TAD_OK;
-}
-
 }  // namespace tadh
 
 extern "C" {
-
-// what tad_run_state and tad_run_state_window refuse before they take the state's lock (who: the call's name for the message)
-static int check_state_job(tad_engine *eng, const tad_state *st, const tad_job *job, tad_result **out, const char *who, const char *narrow) {
-  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
-  if (!st || !job || !out) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: state, job and out must not be NULL", who);
-  *out = nullptr;
-  if (job->algo != TAD_ALGO_EWMA && job->algo != TAD_ALGO_DBSCAN && job->algo != TAD_ALGO_ARIMA)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the algorithm must be EWMA, DBSCAN or ARIMA (DROP: tad_drop_state)", who);
-  if (job->start_time != 0 || job->end_time != 0)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: start_time / end_time must be 0: %s", who, narrow);
-  if (job->flags & (TAD_FLAG_KEY_U32 | TAD_FLAG_TIME_U32))
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 describe input columns; there are none", who);
-  if (job->ewma_alpha < 0.0 || job->ewma_alpha > 1.0 || job->dbscan_eps < 0.0 || job->dbscan_min_samples < 0 || job->arima_maxiter < 0)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: detector parameter out of range", who);
-  if (!st->series || !st->times)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES)", who);
-  if (job->algo == TAD_ALGO_DBSCAN && !st->history)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: DBSCAN needs a state with history too (TAD_STATE_HISTORY)", who);
-  return TAD_OK;
-}
-
-int tad_run_state(tad_engine *eng, tad_state *st, const tad_job *job, tad_mem out_memory, tad_result **out) {
-  int rc = check_state_job(eng, st, job, out, "tad_run_state", "the window is what the state holds (tad_state_trim narrows it)");
-  if (rc != TAD_OK) return rc;
-  StateCall call(eng, st);
-  if (st->times_stale)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state: the series was imported without its times (tad_state_import_times)");
-  if ((rc = call.enter("tad_run_state", job->id, job->algo == TAD_ALGO_ARIMA)) != TAD_OK) return rc;
-  if ((rc = run_view_begin(call.e, st->K)) != TAD_OK) return rc;
-  return run_view_locked(call.e, series_view(st, st->cur), job, out_memory, out, 0);
-}
-
-int tad_window_history_by_sort(uint64_t window_points, uint64_t state_points) { return win_hist_by_sort(window_points, state_points) ? 1 : 0; }
-
-// The view of a window of the state in the context's workspace (kernels: tad_window.hip), after run_view_begin, in two steps that
-// tad_run_state_window and tad_drop_state share: window_bounds (every key's bounds, the view's offsets, the window's point total — one
-// host round trip) and window_gather (the view itself, which run_view_locked then judges).  Both read the state's CURRENT copies and
-// write workspace only: wv_key and wv_pts hold the view; run_view_locked resizes neither.
-struct WinKeys {   // wv_key: per key wbeg | wlen | ecnt | chunks (later the long-sort list) u32 each | the list's length | woff | coff | eoff u64[K + 1] each | moments
-  uint32_t *wbeg, *wlen, *ecnt, *chunks;
-  unsigned int *long_count;
-  unsigned long long *woff, *coff, *eoff;
-  StreamState wmom;
-};
-
-static size_t win_key_bytes(uint64_t K) {
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
-  return kpad * 16 + 64 + (kpad + 4) * 24;
-}
-
-static WinKeys win_keys(JobCtx *e, uint64_t K) {
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
-  WinKeys w;
-  w.wbeg = static_cast<uint32_t *>(e->wv_key.p); w.wlen = w.wbeg + kpad; w.ecnt = w.wlen + kpad; w.chunks = w.ecnt + kpad;
-  w.long_count = reinterpret_cast<unsigned int *>(w.chunks + kpad);
-  w.woff = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(w.long_count) + 64);
-  w.coff = w.woff + kpad + 4; w.eoff = w.coff + kpad + 4;
-  w.wmom = stream_view(static_cast<unsigned char *>(e->wv_key.p) + win_key_bytes(K), K);
-  return w;
-}
-
-// 1. every key's bounds; the view's offsets and the chunk offsets; *P = the window's point total.  keep (device, K bytes, or NULL): the
-// key selection of tad_run_state_keys / tad_drop_state_keys — a key that is not selected gets an empty window
-static int window_bounds(JobCtx *e, const tad_state *st, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *keep, uint64_t *P) {
-  hipStream_t s = e->stream;
-  const uint64_t K = st->K;
-  const StateView whole = series_view(st, st->cur);
-  int rc;
-  if ((rc = ensure(e, e->wv_key, win_key_bytes(K) + state_bytes(K))) != TAD_OK) return rc;
-  if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K) * sizeof(unsigned long long))) != TAD_OK) return rc;
-  const WinKeys w = win_keys(e, K);
-  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
-  launch_win_bounds(s, K, whole.soff, whole.st, (long long)from_t, (long long)to_t, keep_points, keep, w.wbeg, w.wlen, w.ecnt, w.chunks);
-  launch_scan(s, w.wlen, w.woff, K, scratch);
-  launch_scan(s, w.chunks, w.coff, K, scratch);
-  HIP_TRY(e, hipGetLastError());
-  HIP_TRY(e, hipMemcpyAsync(e->tail_host + kTailTotal, w.woff + K, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipStreamSynchronize(s));
-  *P = *e->total_host;
-  return TAD_OK;
-}
-
-// 2. the window's values and times (DBSCAN on the subtract side: the excluded values too); 3. the moments — not for TAD_ALGO_DROP, which
-// reads none; 4. DBSCAN's history, by sorting the window's values or (subtract) by removing the sorted excluded values from the state's
-static int window_gather(JobCtx *e, const tad_state *st, const tad_job *job, uint64_t P, bool subtract, StateView *v) {
-  hipStream_t s = e->stream;
-  const uint64_t K = st->K;
-  const StateView whole = series_view(st, st->cur);
-  const uint64_t S = whole.P;
-  const WinKeys w = win_keys(e, K);
-  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
-  int rc;
-  *v = StateView{};
-  v->K = K;
-  v->P = P;
-  if (P != 0) {
-    const bool dbscan = job->algo == TAD_ALGO_DBSCAN;
-    if ((rc = ensure(e, e->wv_pts, P * (dbscan ? 24 : 16))) != TAD_OK) return rc;
-    unsigned long long *wval = static_cast<unsigned long long *>(e->wv_pts.p);
-    long long *wt = reinterpret_cast<long long *>(wval + P);
-    unsigned long long *wh = wval + 2 * P, *ev = nullptr, *es = nullptr;
-    if (subtract) {
-      if ((rc = ensure(e, e->hs_val, (S - P) * 8)) != TAD_OK) return rc;
-      if ((rc = ensure(e, e->hs_sorted, (S - P) * 8)) != TAD_OK) return rc;
-      ev = static_cast<unsigned long long *>(e->hs_val.p);
-      es = static_cast<unsigned long long *>(e->hs_sorted.p);
-      launch_scan(s, w.ecnt, w.eoff, K, scratch);
-    }
-    const uint64_t bound = trim_chunks_bound(K, S);
-    launch_win_gather(s, bound, w.coff, K, whole.soff, whole.sval, whole.st, w.wbeg, w.woff, wval, wt, w.eoff, ev);
-    if (job->algo != TAD_ALGO_DROP) {
-      const double alpha = job->ewma_alpha == 0.0 ? 0.5 : job->ewma_alpha;   // (for the view's ewma only, which no detector reads)
-      launch_trim_moments(s, K, w.wlen, w.ecnt, w.woff, wval, alpha, whole.mom, w.wmom);
-    }
-    if (subtract) {
-      launch_hist_sort(s, ev, w.eoff, K, es, w.chunks, w.long_count);
-      launch_hist_subtract(s, bound, w.coff, K, whole.hoff, whole.hval, w.eoff, es, w.woff, wh, true);
-    } else if (dbscan) {
-      launch_hist_sort(s, wval, w.woff, K, wh, w.chunks, w.long_count);
-    }
-    HIP_TRY(e, hipGetLastError());
-    v->soff = w.woff; v->sval = wval; v->st = wt; v->mom = w.wmom;
-    if (dbscan) { v->hoff = w.woff; v->hval = wh; }
-  }
-  e->done.store(1);
-  return TAD_OK;
-}
-
-// tad.h: the window's view (window_bounds, window_gather), then tad_run_state's path on it.
-int tad_run_state_window(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, tad_mem out_memory,
-                         tad_result **out) {
-  int rc = check_state_job(eng, st, job, out, "tad_run_state_window", "the window is from_t / to_t / keep_points");
-  if (rc != TAD_OK) return rc;
-  if (from_t != 0 && to_t != 0 && from_t > to_t)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state_window: from_t is later than to_t");
-  StateCall call(eng, st);
-  if (st->times_stale)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_run_state_window: the series was imported without its times (tad_state_import_times)");
-  if ((rc = call.enter("tad_run_state_window", job->id, job->algo == TAD_ALGO_ARIMA)) != TAD_OK) return rc;
-  JobCtx *e = call.e;
-  if ((rc = run_view_begin(e, st->K)) != TAD_OK) return rc;
-  const StateView whole = series_view(st, st->cur);
-  const uint64_t S = whole.P;
-  if (S == 0 || (from_t == 0 && to_t == 0 && keep_points == 0)) return run_view_locked(e, whole, job, out_memory, out, 0);
-  uint64_t P = 0;
-  if ((rc = window_bounds(e, st, from_t, to_t, keep_points, nullptr, &P)) != TAD_OK) return rc;
-  if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1);   // every key is whole: the state's own arrays, no view
-  const bool subtract = job->algo == TAD_ALGO_DBSCAN && P != 0 && !win_hist_by_sort(P, S);
-  StateView v;
-  if ((rc = window_gather(e, st, job, P, subtract, &v)) != TAD_OK) return rc;
-  return run_view_locked(e, v, job, out_memory, out, 1);
-}
-
-// tad.h: the drop detector's batch verdicts over a window of the state — tad_run_state_window's window and view (window_bounds, window_gather:
-// values and times only), then run_view_locked's DROP path (state_drop_batch).  Read-only.
-int tad_drop_state(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, tad_mem out_memory,
-                   tad_result **out) {
-  const char *who = "tad_drop_state";
-  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
-  if (!st || !job || !out) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: state, job and out must not be NULL", who);
-  *out = nullptr;
-  if (job->algo != TAD_ALGO_DROP)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the algorithm must be DROP (tad_run_state_window judges EWMA, DBSCAN and ARIMA)", who);
-  if (job->start_time != 0 || job->end_time != 0)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: start_time / end_time must be 0: the window is from_t / to_t / keep_points", who);
-  if (job->flags & (TAD_FLAG_KEY_U32 | TAD_FLAG_TIME_U32))
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 describe input columns; there are none", who);
-  if (!(job->drop_nsigma >= 0.0) || job->drop_min_samples < 0)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: detector parameter out of range", who);
-  if (!st->series || !st->times)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES)", who);
-  if (from_t != 0 && to_t != 0 && from_t > to_t) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: from_t is later than to_t", who);
-  StateCall call(eng, st);
-  if (st->times_stale)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the series was imported without its times (tad_state_import_times)", who);
-  int rc;
-  if ((rc = call.enter(who, job->id)) != TAD_OK) return rc;
-  JobCtx *e = call.e;
-  if ((rc = run_view_begin(e, st->K)) != TAD_OK) return rc;
-  const StateView whole = series_view(st, st->cur);
-  const uint64_t S = whole.P;
-  if (S == 0 || (from_t == 0 && to_t == 0 && keep_points == 0)) return run_view_locked(e, whole, job, out_memory, out, 0);
-  uint64_t P = 0;
-  if ((rc = window_bounds(e, st, from_t, to_t, keep_points, nullptr, &P)) != TAD_OK) return rc;
-  if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1);   // every key is whole: the state's own arrays, no view
-  StateView v;
-  if ((rc = window_gather(e, st, job, P, false, &v)) != TAD_OK) return rc;   // values and times only: DROP reads no moments, no history
-  return run_view_locked(e, v, job, out_memory, out, 1);
-}
-
-// tad.h: tad_run_state_window / tad_drop_state over the keys key_keep selects, once the job is checked (the window calls' own checks, under
-// the *_keys name).  A key whose byte is 0 is left empty by window_bounds, and the rest of the call treats it as any key the window left
-// empty.  The mask is a window of its own, so with one the "no window at all" shortcut is not taken; P == S still is, since then every
-// point the state holds is selected.  Without a mask (NULL, length 0) this is the window call, step for step.  DROP: values and times only, no moments, no history.
-static int window_keys_call(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *key_keep,
-                            uint64_t key_keep_len, tad_mem key_memory, tad_mem out_memory, tad_result **out, const char *who) {
-  if (from_t != 0 && to_t != 0 && from_t > to_t) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: from_t is later than to_t", who);
-  if (!key_keep && key_keep_len != 0)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep is NULL with a length of %llu", who, (unsigned long long)key_keep_len);
-  if (key_keep && key_memory != TAD_MEM_HOST && key_memory != TAD_MEM_DEVICE)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep must be in host or device memory", who);
-  StateCall call(eng, st);
-  if (st->times_stale)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the series was imported without its times (tad_state_import_times)", who);
-  if (key_keep && key_keep_len != st->K)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep has %llu entries, the state holds %llu keys", who, (unsigned long long)key_keep_len,
-                (unsigned long long)st->K);
-  int rc;
-  if ((rc = call.enter(who, job->id, job->algo == TAD_ALGO_ARIMA)) != TAD_OK) return rc;
-  JobCtx *e = call.e;
-  if ((rc = run_view_begin(e, st->K)) != TAD_OK) return rc;
-  const StateView whole = series_view(st, st->cur);
-  const uint64_t S = whole.P;
-  if (S == 0 || (!key_keep && from_t == 0 && to_t == 0 && keep_points == 0)) return run_view_locked(e, whole, job, out_memory, out, 0);
-  const uint8_t *d_keep = key_keep;
-  if (key_keep && key_memory == TAD_MEM_HOST) {   // staged: only window_bounds reads it
-    if ((rc = ensure(e, e->in_key, (size_t)st->K)) != TAD_OK) return rc;
-    HIP_TRY(e, hipMemcpyAsync(e->in_key.p, key_keep, st->K, hipMemcpyHostToDevice, e->stream));
-    d_keep = static_cast<const uint8_t *>(e->in_key.p);
-  }
-  uint64_t P = 0;
-  if ((rc = window_bounds(e, st, from_t, to_t, keep_points, d_keep, &P)) != TAD_OK) return rc;
-  if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1);   // every key is selected and whole: the state's own arrays, no view
-  const bool subtract = job->algo == TAD_ALGO_DBSCAN && P != 0 && !win_hist_by_sort(P, S);   // (P: the SELECTED window points)
-  StateView v;
-  if ((rc = window_gather(e, st, job, P, subtract, &v)) != TAD_OK) return rc;
-  return run_view_locked(e, v, job, out_memory, out, 1);
-}
-
-int tad_run_state_keys(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *key_keep,
-                       uint64_t key_keep_len, tad_mem key_memory, tad_mem out_memory, tad_result **out) {
-  const int rc = check_state_job(eng, st, job, out, "tad_run_state_keys", "the window is from_t / to_t / keep_points");
-  if (rc != TAD_OK) return rc;
-  return window_keys_call(eng, st, job, from_t, to_t, keep_points, key_keep, key_keep_len, key_memory, out_memory, out, "tad_run_state_keys");
-}
-
-int tad_drop_state_keys(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *key_keep,
-                        uint64_t key_keep_len, tad_mem key_memory, tad_mem out_memory, tad_result **out) {
-  const char *who = "tad_drop_state_keys";
-  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
-  if (!st || !job || !out) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: state, job and out must not be NULL", who);
-  *out = nullptr;
-  if (job->algo != TAD_ALGO_DROP)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the algorithm must be DROP (tad_run_state_keys judges EWMA, DBSCAN and ARIMA)", who);
-  if (job->start_time != 0 || job->end_time != 0)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: start_time / end_time must be 0: the window is from_t / to_t / keep_points", who);
-  if (job->flags & (TAD_FLAG_KEY_U32 | TAD_FLAG_TIME_U32))
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 describe input columns; there are none", who);
-  if (!(job->drop_nsigma >= 0.0) || job->drop_min_samples < 0)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: detector parameter out of range", who);
-  if (!st->series || !st->times)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES)", who);
-  return window_keys_call(eng, st, job, from_t, to_t, keep_points, key_keep, key_keep_len, key_memory, out_memory, out, who);
-}
 
 // tad.h: the periodical drop job, one batch.  The batch runs as a stream batch of the EWMA kind does (run_job_locked: Stage 0, the count
 // pass into the candidate state, stream_history_batch), then state_drop_batch judges the new points; tad_run_stream itself keeps
@@ -957,7 +617,5 @@ int tad_state_merge(tad_engine *eng, tad_state *st, const tad_job *job, const ta
   if (rc == TAD_OK && stats) *stats = mc.stats;
   return rc;
 }
-
-
 
 }  // extern "C"

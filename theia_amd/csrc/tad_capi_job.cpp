@@ -1,5 +1,5 @@
 // tad_capi_job.cpp — the batch job of include/tad.h: tad_run / tad_aggregate / tad_run_stream, and the Stage 0 that tad_drop_stream and
-// tad_state_merge run through (tad_capi.cpp).  Replaces one run of anomaly_detection() (plugins/anomaly-detection/anomaly_detection.py:647-710):
+// tad_state_merge run through (tad_capi.cpp; the read-only jobs on a state, which run no Stage 0, are tad_capi_view.cpp).  Replaces one run of anomaly_detection() (plugins/anomaly-detection/anomaly_detection.py:647-710):
 // Stage 0 GROUP BY -> per-key sigma -> detector -> compaction.  run_job_locked reads as the sequence of its stages: the lattice, Stage 0
 // (sparse, tiles or scatter), the count pass, the retry rules' word (tad_stage0_retry.h), the result.
 #include "tad_engine.h"
@@ -745,18 +745,12 @@ int job_rows(JobCtx *e, const Job &j, const Attempt &a, const StreamBatches &sb,
   hipStream_t s = e->stream;
   tad_state *stream = j.stream;
   const JobParams &jp = j.jp;
-  const HistBatch &hist = sb.hist;
   const Grid g = a.g;
   RowsOut ro;
   int rc;
   if ((rc = make_result(e, rows, jp.all_points, j.out_memory, &ro.rp, &ro.dev_rows, &ro.dev_block)) != TAD_OK) return rc;
-  if (rows && stream && jp.algo == TAD_ALGO_ARIMA)
-    launch_as_emit(s, sb.ab.P, hist.nk, hist.nt, hist.nv, sb.ab.tidx, sb.ab.sigma, sb.ab.pcalc, sb.ab.pflag, sb.ab.rows, sb.ab.row_off, jp.all_points, ro.dev_rows);
-  else if (rows && stream && jp.algo == TAD_ALGO_DBSCAN)
-    launch_hist_emit(s, hist.nk, hist.nt, hist.nv, hist.P_dev, hist.P_cap, hist.noise, hist.cnt, hist.row, state_view(stream, stream->cur ^ 1),
-                     jp.all_points, ro.dev_rows);
-  else if (rows && stream && jp.algo == TAD_ALGO_DROP)
-    launch_ds_emit(s, hist.nk, hist.nt, hist.nv, hist.P_dev, hist.P_cap, sb.db.flag, sb.db.cnt, sb.db.row, sb.db.keys, jp.all_points, ro.dev_rows);
+  if (rows && stream && jp.algo != TAD_ALGO_EWMA)   // the batch's points as DBSCAN, ARIMA or DROP judged them (stddev: the candidate state's)
+    emit_point_rows(s, jp, sb.hist, sb.ab, sb.db, state_view(stream, stream->cur ^ 1), ro.dev_rows);
   else if (rows && stream && a.stream_poff)
     launch_stream_points(s, static_cast<const unsigned long long *>(e->sp_comp_a.p), static_cast<const unsigned long long *>(e->sp_val_a.p), a.stream_poff,
                          g.K, a.L.t0, jp.alpha, jp.all_points, true, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),

@@ -1,0 +1,331 @@
+// tad_capi_view.cpp — the read-only jobs on a streaming state of include/tad.h: tad_run_state, tad_run_state_window, tad_drop_state and
+// their *_keys forms.  All five are one call (view_call): one checker for what they refuse, one window — time bounds, a point count, a key
+// mask, any of them absent — whose view is built in the context's workspace (window_bounds, window_gather; kernels: tad_window.hip), and
+// one job on that view (run_view_locked), which runs the stream batches' detectors (tad_capi.cpp) with every point of the view named as
+// new.  Nothing here writes the state.
+#include "tad_engine.h"
+
+using namespace tad;
+using namespace tadh;
+
+namespace {
+
+// the start of a job on a view, on the context the caller holds: progress, the first event, the job tail zeroed
+int run_view_begin(JobCtx *e, uint64_t K) {
+  e->done.store(0);
+  e->total.store(4);
+  e->arima_relaunches = 0;
+  int rc;
+  if ((rc = ensure_key_buffers(e, K)) != TAD_OK) return rc;
+  HIP_TRY(e, hipEventRecord(e->ev[0], e->stream));
+  HIP_TRY(e, hipMemsetAsync(e->counters.p, 0, kTailBytes, e->stream));
+  return TAD_OK;
+}
+
+// what run_view_locked's detectors leave for its emit, across the host round trip
+struct ViewJob {
+  HistBatch hist;
+  ArimaBatch ab;
+  DropBatch db;
+  unsigned long long coop_min = 0;   // the routing launch_win_route left: keys from coop_min points on are on the list
+  uint32_t *list = nullptr;
+  unsigned int *lcount = nullptr;
+  const unsigned long long *off = nullptr;   // EWMA: the row offsets
+};
+
+// Before the round trip: the routing, the moments, the detector and its row total.  EWMA walks the CSR series; DBSCAN, ARIMA and DROP
+// (its view carries no moments) run the stream's kernels with every series point named as new (poff = the series offsets).
+int view_detect(JobCtx *e, const StateView &v, const JobParams &jp, ViewJob *vj) {
+  hipStream_t s = e->stream;
+  const uint64_t K = v.K, P = v.P;
+  DevCounters *ctr = static_cast<DevCounters *>(e->counters.p);
+  unsigned long long *tmin_dev = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(e->counters.p) + kTailHistLen);
+  HistBatch &hist = vj->hist;
+  int rc;
+  vj->off = v.soff;   // EWMA with every point: the row offsets are the series offsets
+  if (P == 0) return TAD_OK;
+  const size_t kpad = (size_t)((K + 3) & ~3ull);
+  if ((rc = ensure(e, e->hs_kcnt, kpad * 4 + 64)) != TAD_OK) return rc;   // the long keys' list | its length
+  if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K > P ? K : P) * sizeof(unsigned long long))) != TAD_OK) return rc;
+  vj->list = static_cast<uint32_t *>(e->hs_kcnt.p);
+  vj->lcount = reinterpret_cast<unsigned int *>(vj->list + kpad);
+  vj->coop_min = win_coop_min(K, P);
+  launch_win_route(s, K, v.soff, v.st, vj->coop_min, vj->list, vj->lcount, tmin_dev);
+  if (jp.algo != TAD_ALGO_DROP) launch_moments(s, K, v.mom.n, v.mom.avg, v.mom.m2, dev_moments(e), ctr);   // (and n_keys / n_points)
+  if (jp.algo == TAD_ALGO_EWMA) {
+    if (jp.all_points) return TAD_OK;
+    launch_win_ewma(s, K, v.soff, v.sval, v.st, v.mom, jp.alpha, vj->coop_min, vj->list, vj->lcount, false, false, static_cast<uint32_t *>(e->n_anom.p), nullptr,
+                    OutRows{});
+    launch_scan(s, static_cast<const uint32_t *>(e->n_anom.p), static_cast<unsigned long long *>(e->off.p), K,
+                static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
+    vj->off = static_cast<const unsigned long long *>(e->off.p);
+    return TAD_OK;
+  }
+  if ((rc = ensure(e, e->hs_key, P * 8)) != TAD_OK) return rc;
+  unsigned long long *nk = static_cast<unsigned long long *>(e->hs_key.p);
+  launch_win_keys(s, K, v.soff, nk);
+  hist.nk = nk; hist.nv = v.sval; hist.nt = v.st; hist.poff = v.soff; hist.P_dev = v.soff + K; hist.P_cap = P;
+  if (jp.algo == TAD_ALGO_DBSCAN) return hist_verdicts(e, v.hoff, v.hval, jp, &hist);
+  if (jp.algo == TAD_ALGO_DROP) return state_drop_batch(e, v, hist, jp, false, vj->coop_min, vj->list, vj->lcount, ctr, &vj->db);
+  return stream_arima_batch(e, v, hist, jp, ctr, &vj->ab);
+}
+
+// After the round trip (c: the job's counters as the host read them): the result, the emit, the stats.  view_syncs: the host
+// synchronisations the caller spent on building the view (tad_stats.host_syncs).
+int view_rows(JobCtx *e, const StateView &v, const tad_job *job, const JobParams &jp, const ViewJob &vj, const DevCounters &c, uint64_t rows,
+              tad_mem out_memory, tad_result **out, int view_syncs) {
+  hipStream_t s = e->stream;
+  const uint64_t P = v.P;
+  RowsOut ro;
+  int rc;
+  if ((rc = make_result(e, rows, jp.all_points, out_memory, &ro.rp, &ro.dev_rows, &ro.dev_block)) != TAD_OK) return rc;
+  if (rows && jp.algo == TAD_ALGO_EWMA)
+    launch_win_ewma(s, v.K, v.soff, v.sval, v.st, v.mom, jp.alpha, vj.coop_min, vj.list, vj.lcount, true, jp.all_points, nullptr, vj.off, ro.dev_rows, rows,
+                    e->plan.ewma_emit, e->plan.ewma_emit_rows);
+  else if (rows)
+    emit_point_rows(s, jp, vj.hist, vj.ab, vj.db, v.mom, ro.dev_rows);
+  if ((rc = finish_rows(e, job, &ro, rows, jp.all_points, c, P != 0)) != TAD_OK) return rc;
+  tad_stats &rs = ro.rp->pub.stats;
+  rs.rows_in = rs.rows_used = rs.n_points = P;
+  {
+    unsigned long long tmin = ~0ull;
+    memcpy(&tmin, e->tail_host + kTailHistLen, 8);
+    rs.t0 = (P && tmin != ~0ull) ? (int64_t)(tmin ^ (1ull << 63)) : 0;
+  }
+  hipEventElapsedTime(&rs.ms_total, e->ev[0], e->ev[4]);
+  rs.ms_detect = rs.ms_total;   // no Stage 0 ran: the whole call is the detector and its emit
+  rs.host_syncs = 2 + view_syncs;
+  e->done.store(4);
+  *out = &ro.rp->pub;
+  return TAD_OK;
+}
+
+// The job on a view after run_view_begin (tad.h; kernels: tad_window.hip): the detector, the one host round trip of the job's tail, the
+// rows.  Reads the view only: the state's CURRENT copies, or a window's view in this context's workspace (wv_key / wv_pts, which nothing
+// below resizes).
+int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem out_memory, tad_result **out, int view_syncs) {
+  const JobParams jp = job_params(job);
+  ViewJob vj;
+  int rc;
+  if ((rc = view_detect(e, v, jp, &vj)) != TAD_OK) return rc;
+  e->done.store(2);
+  HIP_TRY(e, hipMemcpyAsync(e->tail_host, e->counters.p, kTailBytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  HIP_TRY(e, hipGetLastError());
+  const uint64_t rows = (jp.algo == TAD_ALGO_EWMA && jp.all_points) ? v.P : (v.P ? *e->total_host : 0);
+  const DevCounters c = *e->ctr_host;
+  e->done.store(3);
+  return view_rows(e, v, job, jp, vj, c, rows, out_memory, out, view_syncs);
+}
+
+// The view of a window of the state in the context's workspace (kernels: tad_window.hip), after run_view_begin, in two steps:
+// window_bounds (every key's bounds, the view's offsets, the window's point total — one host round trip) and window_gather (the view
+// itself, which run_view_locked then judges).  Both read the state's CURRENT copies and write workspace only: wv_key and wv_pts hold the
+// view; run_view_locked resizes neither.
+struct WinKeys {   // wv_key: per key wbeg | wlen | ecnt | chunks (later the long-sort list) u32 each | the list's length | woff | coff | eoff u64[K + 1] each | moments
+  uint32_t *wbeg, *wlen, *ecnt, *chunks;
+  unsigned int *long_count;
+  unsigned long long *woff, *coff, *eoff;
+  StreamState wmom;
+};
+
+size_t win_key_bytes(uint64_t K) {
+  const size_t kpad = (size_t)((K + 3) & ~3ull);
+  return kpad * 16 + 64 + (kpad + 4) * 24;
+}
+
+WinKeys win_keys(JobCtx *e, uint64_t K) {
+  const size_t kpad = (size_t)((K + 3) & ~3ull);
+  WinKeys w;
+  w.wbeg = static_cast<uint32_t *>(e->wv_key.p); w.wlen = w.wbeg + kpad; w.ecnt = w.wlen + kpad; w.chunks = w.ecnt + kpad;
+  w.long_count = reinterpret_cast<unsigned int *>(w.chunks + kpad);
+  w.woff = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(w.long_count) + 64);
+  w.coff = w.woff + kpad + 4; w.eoff = w.coff + kpad + 4;
+  w.wmom = stream_view(static_cast<unsigned char *>(e->wv_key.p) + win_key_bytes(K), K);
+  return w;
+}
+
+// 1. every key's bounds; the view's offsets and the chunk offsets; *P = the window's point total.  keep (device, K bytes, or NULL): the
+// key selection of tad_run_state_keys / tad_drop_state_keys — a key that is not selected gets an empty window
+int window_bounds(JobCtx *e, const tad_state *st, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *keep, uint64_t *P) {
+  hipStream_t s = e->stream;
+  const uint64_t K = st->K;
+  const StateView whole = series_view(st, st->cur);
+  int rc;
+  if ((rc = ensure(e, e->wv_key, win_key_bytes(K) + state_bytes(K))) != TAD_OK) return rc;
+  if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K) * sizeof(unsigned long long))) != TAD_OK) return rc;
+  const WinKeys w = win_keys(e, K);
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  launch_win_bounds(s, K, whole.soff, whole.st, (long long)from_t, (long long)to_t, keep_points, keep, w.wbeg, w.wlen, w.ecnt, w.chunks);
+  launch_scan(s, w.wlen, w.woff, K, scratch);
+  launch_scan(s, w.chunks, w.coff, K, scratch);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipMemcpyAsync(e->tail_host + kTailTotal, w.woff + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  *P = *e->total_host;
+  return TAD_OK;
+}
+
+// 2. the window's values and times (DBSCAN on the subtract side: the excluded values too); 3. the moments — not for TAD_ALGO_DROP, which
+// reads none; 4. DBSCAN's history, by sorting the window's values or (subtract) by removing the sorted excluded values from the state's
+int window_gather(JobCtx *e, const tad_state *st, const tad_job *job, uint64_t P, bool subtract, StateView *v) {
+  hipStream_t s = e->stream;
+  const uint64_t K = st->K;
+  const StateView whole = series_view(st, st->cur);
+  const uint64_t S = whole.P;
+  const WinKeys w = win_keys(e, K);
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  int rc;
+  *v = StateView{};
+  v->K = K;
+  v->P = P;
+  if (P != 0) {
+    const bool dbscan = job->algo == TAD_ALGO_DBSCAN;
+    if ((rc = ensure(e, e->wv_pts, P * (dbscan ? 24 : 16))) != TAD_OK) return rc;
+    unsigned long long *wval = static_cast<unsigned long long *>(e->wv_pts.p);
+    long long *wt = reinterpret_cast<long long *>(wval + P);
+    unsigned long long *wh = wval + 2 * P, *ev = nullptr, *es = nullptr;
+    if (subtract) {
+      if ((rc = ensure(e, e->hs_val, (S - P) * 8)) != TAD_OK) return rc;
+      if ((rc = ensure(e, e->hs_sorted, (S - P) * 8)) != TAD_OK) return rc;
+      ev = static_cast<unsigned long long *>(e->hs_val.p);
+      es = static_cast<unsigned long long *>(e->hs_sorted.p);
+      launch_scan(s, w.ecnt, w.eoff, K, scratch);
+    }
+    const uint64_t bound = trim_chunks_bound(K, S);
+    launch_win_gather(s, bound, w.coff, K, whole.soff, whole.sval, whole.st, w.wbeg, w.woff, wval, wt, w.eoff, ev);
+    if (job->algo != TAD_ALGO_DROP) {
+      const double alpha = job->ewma_alpha == 0.0 ? 0.5 : job->ewma_alpha;   // (for the view's ewma only, which no detector reads)
+      launch_trim_moments(s, K, w.wlen, w.ecnt, w.woff, wval, alpha, whole.mom, w.wmom);
+    }
+    if (subtract) {
+      launch_hist_sort(s, ev, w.eoff, K, es, w.chunks, w.long_count);
+      launch_hist_subtract(s, bound, w.coff, K, whole.hoff, whole.hval, w.eoff, es, w.woff, wh, true);
+    } else if (dbscan) {
+      launch_hist_sort(s, wval, w.woff, K, wh, w.chunks, w.long_count);
+    }
+    HIP_TRY(e, hipGetLastError());
+    v->soff = w.woff; v->sval = wval; v->st = wt; v->mom = w.wmom;
+    if (dbscan) { v->hoff = w.woff; v->hval = wh; }
+  }
+  e->done.store(1);
+  return TAD_OK;
+}
+
+// What the five calls refuse before they take the state's lock.  Both families check the same things in the same order; the family
+// supplies the algorithm test with its message, the parameter ranges and DBSCAN's history.  who: the call's name in the messages; narrow:
+// where the caller narrows the window instead of start_time / end_time.
+enum class Family { Run, Drop };   // Run: EWMA, DBSCAN, ARIMA; Drop: DROP
+
+int check_view_job(tad_engine *eng, const tad_state *st, const tad_job *job, tad_result **out, const char *who, Family family, const char *narrow) {
+  const bool drop = family == Family::Drop;
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!st || !job || !out) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: state, job and out must not be NULL", who);
+  *out = nullptr;
+  if (drop && job->algo != TAD_ALGO_DROP)   // (the message names the Run call with the same arguments)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the algorithm must be DROP (%s judges EWMA, DBSCAN and ARIMA)", who,
+                strstr(who, "_keys") ? "tad_run_state_keys" : "tad_run_state_window");
+  if (!drop && job->algo != TAD_ALGO_EWMA && job->algo != TAD_ALGO_DBSCAN && job->algo != TAD_ALGO_ARIMA)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the algorithm must be EWMA, DBSCAN or ARIMA (DROP: tad_drop_state)", who);
+  if (job->start_time != 0 || job->end_time != 0)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: start_time / end_time must be 0: %s", who, narrow);
+  if (job->flags & (TAD_FLAG_KEY_U32 | TAD_FLAG_TIME_U32))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32 describe input columns; there are none", who);
+  if (drop ? (!(job->drop_nsigma >= 0.0) || job->drop_min_samples < 0)
+           : (job->ewma_alpha < 0.0 || job->ewma_alpha > 1.0 || job->dbscan_eps < 0.0 || job->dbscan_min_samples < 0 || job->arima_maxiter < 0))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: detector parameter out of range", who);
+  if (!st->series || !st->times)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES)", who);
+  if (job->algo == TAD_ALGO_DBSCAN && !st->history)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: DBSCAN needs a state with history too (TAD_STATE_HISTORY)", who);
+  return TAD_OK;
+}
+
+// Which of the state's points a call judges: of every key's series the points with from_t <= flow_end_s < to_t (0 = no bound on that
+// side), of those the newest keep_points (0 = all), and only of the keys whose byte in key_keep is not 0 (NULL, length 0 = every key).
+// All zero is the whole state.
+struct Window {
+  int64_t from_t = 0, to_t = 0;
+  uint64_t keep_points = 0;
+  const uint8_t *key_keep = nullptr;
+  uint64_t key_keep_len = 0;
+  tad_mem key_memory = TAD_MEM_HOST;
+};
+
+const char *const kNarrowWindow = "the window is from_t / to_t / keep_points";
+
+// The checked job (check_view_job) over the window w of the state, under the name who.  A key whose byte is 0 is left empty by
+// window_bounds, and the rest of the call treats it as any key the window left empty.  The mask is a window of its own, so with one the
+// "no window at all" shortcut is not taken; P == S still is, since then every point the state holds is selected.  DROP: values and times
+// only, no moments, no history.
+int view_call(tad_engine *eng, tad_state *st, const tad_job *job, const char *who, const Window &w, tad_mem out_memory, tad_result **out) {
+  if (w.from_t != 0 && w.to_t != 0 && w.from_t > w.to_t) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: from_t is later than to_t", who);
+  if (!w.key_keep && w.key_keep_len != 0)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep is NULL with a length of %llu", who, (unsigned long long)w.key_keep_len);
+  if (w.key_keep && w.key_memory != TAD_MEM_HOST && w.key_memory != TAD_MEM_DEVICE)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep must be in host or device memory", who);
+  StateCall call(eng, st);
+  if (st->times_stale)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the series was imported without its times (tad_state_import_times)", who);
+  if (w.key_keep && w.key_keep_len != st->K)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep has %llu entries, the state holds %llu keys", who, (unsigned long long)w.key_keep_len,
+                (unsigned long long)st->K);
+  int rc;
+  if ((rc = call.enter(who, job->id, job->algo == TAD_ALGO_ARIMA)) != TAD_OK) return rc;
+  JobCtx *e = call.e;
+  if ((rc = run_view_begin(e, st->K)) != TAD_OK) return rc;
+  const StateView whole = series_view(st, st->cur);
+  const uint64_t S = whole.P;
+  if (S == 0 || (!w.key_keep && w.from_t == 0 && w.to_t == 0 && w.keep_points == 0)) return run_view_locked(e, whole, job, out_memory, out, 0);
+  const uint8_t *d_keep = w.key_keep;
+  if (w.key_keep && w.key_memory == TAD_MEM_HOST) {   // staged: only window_bounds reads it
+    if ((rc = ensure(e, e->in_key, (size_t)st->K)) != TAD_OK) return rc;
+    HIP_TRY(e, hipMemcpyAsync(e->in_key.p, w.key_keep, st->K, hipMemcpyHostToDevice, e->stream));
+    d_keep = static_cast<const uint8_t *>(e->in_key.p);
+  }
+  uint64_t P = 0;
+  if ((rc = window_bounds(e, st, w.from_t, w.to_t, w.keep_points, d_keep, &P)) != TAD_OK) return rc;
+  if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1);   // every key is selected and whole: the state's own arrays, no view
+  const bool subtract = job->algo == TAD_ALGO_DBSCAN && P != 0 && !win_hist_by_sort(P, S);   // (P: the SELECTED window points)
+  StateView v;
+  if ((rc = window_gather(e, st, job, P, subtract, &v)) != TAD_OK) return rc;
+  return run_view_locked(e, v, job, out_memory, out, 1);
+}
+
+}  // namespace
+
+extern "C" {
+
+// the rule view_call decides DBSCAN's history with
+int tad_window_history_by_sort(uint64_t window_points, uint64_t state_points) { return win_hist_by_sort(window_points, state_points) ? 1 : 0; }
+
+int tad_run_state(tad_engine *eng, tad_state *st, const tad_job *job, tad_mem out_memory, tad_result **out) {
+  const int rc = check_view_job(eng, st, job, out, "tad_run_state", Family::Run, "the window is what the state holds (tad_state_trim narrows it)");
+  return rc != TAD_OK ? rc : view_call(eng, st, job, "tad_run_state", Window{}, out_memory, out);
+}
+
+int tad_run_state_window(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, tad_mem out_memory,
+                         tad_result **out) {
+  const int rc = check_view_job(eng, st, job, out, "tad_run_state_window", Family::Run, kNarrowWindow);
+  return rc != TAD_OK ? rc : view_call(eng, st, job, "tad_run_state_window", Window{from_t, to_t, keep_points}, out_memory, out);
+}
+
+int tad_drop_state(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, tad_mem out_memory,
+                   tad_result **out) {
+  const int rc = check_view_job(eng, st, job, out, "tad_drop_state", Family::Drop, kNarrowWindow);
+  return rc != TAD_OK ? rc : view_call(eng, st, job, "tad_drop_state", Window{from_t, to_t, keep_points}, out_memory, out);
+}
+
+int tad_run_state_keys(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *key_keep,
+                       uint64_t key_keep_len, tad_mem key_memory, tad_mem out_memory, tad_result **out) {
+  const int rc = check_view_job(eng, st, job, out, "tad_run_state_keys", Family::Run, kNarrowWindow);
+  return rc != TAD_OK ? rc : view_call(eng, st, job, "tad_run_state_keys", Window{from_t, to_t, keep_points, key_keep, key_keep_len, key_memory}, out_memory, out);
+}
+
+int tad_drop_state_keys(tad_engine *eng, tad_state *st, const tad_job *job, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *key_keep,
+                        uint64_t key_keep_len, tad_mem key_memory, tad_mem out_memory, tad_result **out) {
+  const int rc = check_view_job(eng, st, job, out, "tad_drop_state_keys", Family::Drop, kNarrowWindow);
+  return rc != TAD_OK ? rc : view_call(eng, st, job, "tad_drop_state_keys", Window{from_t, to_t, keep_points, key_keep, key_keep_len, key_memory}, out_memory, out);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // tad_engine.h — PRIVATE header of libtad_mi355x.so's host side: the engine, its pool of job contexts, and what the translation
-// units of the C ABI share (tad_engine.cpp: life cycle, pool, memory; tad_capi_job.cpp: the batch job; tad_capi.cpp: the batches on a state and the state calls;
-// tad_capi_state.cpp: the life of a streaming state; tad_capi_ingest.cpp: the ingest entry points; tad_capi_series.cpp: the per-series
+// units of the C ABI share (tad_engine.cpp: life cycle, pool, memory; tad_capi_job.cpp: the batch job; tad_capi.cpp: what the entry points share and the batches
+// on a state; tad_capi_view.cpp: the read-only jobs on a state; tad_capi_state.cpp: the life of a streaming state; tad_capi_ingest.cpp: the ingest entry points; tad_capi_series.cpp: the per-series
 // entry points; tad_capi_keydict.cpp: the key dictionary).  HIP only: there is no CPU fallback in this library (the CPU oracle under
 // oracle/ is test infrastructure and is never linked or called from here).
 //
@@ -403,6 +403,11 @@ struct DropBatch {
   const uint32_t *cnt = nullptr;
   const unsigned long long *row = nullptr;
 };
+// (tad_capi.cpp) shared by the stream batch and the read-only jobs on a state (tad_capi_view.cpp): DBSCAN's verdicts and rows of the points hb
+// names against a history, filling hb->noise / cnt / row; the emit of the rows of points that DBSCAN, ARIMA or DROP judged
+int hist_verdicts(JobCtx *e, const unsigned long long *hoff, const unsigned long long *hval, const JobParams &jp, HistBatch *hb);
+void emit_point_rows(hipStream_t s, const JobParams &jp, const HistBatch &hb, const ArimaBatch &ab, const DropBatch &db, const StreamState &mom,
+                     OutRows out);
 int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound,
                          const JobParams &jp, HistBatch *hb);
 int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound, bool op_max,
@@ -438,7 +443,7 @@ int arima_yield_loop(JobCtx *e, const unsigned int *yielded_dev, Relaunch relaun
   return TAD_OK;
 }
 
-// (tad_capi_state.cpp) shared with the batches on a state (tad_capi.cpp)
+// (tad_capi_state.cpp) shared with the batches on a state (tad_capi.cpp) and the read-only jobs on it (tad_capi_view.cpp)
 size_t state_bytes(uint64_t K);                              // one block of K keys' running state
 StreamState stream_view(void *block, uint64_t K);            // the arrays inside such a block
 StreamState state_view(const tad_state *st, int which);

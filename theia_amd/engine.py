@@ -1089,23 +1089,42 @@ class TadEngine:
             cols.t0, cols.step, cols.n_buckets = int(lattice[0]), int(lattice[1]), int(lattice[2])
         return cols, narrow, (keep1, keep2, keep3, keep4)
 
+    # ---- what the jobs on a state share: the feature gate, the detector's tad_job, the out memory, the call itself ----
+    def _need(self, feature, what):
+        """a library of before `feature` (or of before tad_features) has no `what`: refused before it is touched"""
+        if not (getattr(self._lib, "tad_features", None) and self._lib.tad_features() & getattr(capi, "TAD_FEATURE_" + feature)):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no %s (TAD_FEATURE_%s)" % (what, feature))
+
+    @staticmethod
+    def _detector_job(algo, alpha=0.0, eps=0.0, min_samples=0, maxiter=0, nsigma=0.0, emit_all=False, job_id="", agg_flow="", value_op="auto"):
+        """the tad_job of a detector on a state; min_samples is DROP's drop_min_samples, else dbscan_min_samples"""
+        if algo not in capi.TAD_ALGO:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "algo must be EWMA, ARIMA, DBSCAN or DROP")
+        drop = algo == "DROP"
+        return capi.Job(algo=capi.TAD_ALGO[algo], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
+                        dbscan_eps=float(eps), dbscan_min_samples=0 if drop else int(min_samples), arima_maxiter=int(maxiter),
+                        drop_nsigma=float(nsigma), drop_min_samples=int(min_samples) if drop else 0,
+                        flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
+
+    @staticmethod
+    def _out_mem(out):
+        return capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST
+
+    def _state_rows(self, call, state, job, out, *args):
+        """lib.<call>(engine, state, job, *args, out memory, &result) -> TadResult; the caller keeps alive what args point to"""
+        res = C.POINTER(capi.Result)()
+        self._check(getattr(self._lib, call)(self._h, state._h, C.byref(job), *args, self._out_mem(out), C.byref(res)))
+        return TadResult(self, res)
+
     def run_stream(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, emit_all=False, out="host",
                    alpha=0.0, job_id="", num_keys=None, key_id2=None, algo="EWMA", eps=0.0, min_samples=0, maxiter=0):
         """One batch of a streaming detector on `state` (tad_run_stream).  key_id2: the second key column of pod mode.  algo="DBSCAN"
         needs a state with history, algo="ARIMA" (maxiter: arima_maxiter) a state with a series: the rows are those tad_run emits for
         this batch's points over everything seen so far."""
-        if algo not in capi.TAD_ALGO:
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "algo must be EWMA, ARIMA, DBSCAN or DROP")
+        job = self._detector_job(algo, alpha, eps, min_samples, maxiter, emit_all=emit_all, job_id=job_id, agg_flow=agg_flow, value_op=value_op)
         cols, narrow, keep = self._stream_columns(state, key_id, flow_end_s, value, key_id2, num_keys, lattice)
-        job = capi.Job(algo=capi.TAD_ALGO[algo], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
-                       dbscan_eps=float(eps), dbscan_min_samples=int(min_samples), arima_maxiter=int(maxiter),
-                       flags=(capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0) | narrow, id=job_id.encode()[:63])
-        res = C.POINTER(capi.Result)()
-        rc = self._lib.tad_run_stream(self._h, state._h, C.byref(job), C.byref(cols),
-                                      capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
-        del keep
-        self._check(rc)
-        return TadResult(self, res)
+        job.flags |= narrow
+        return self._state_rows("tad_run_stream", state, job, out, C.byref(cols))
 
     def merge_stream(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, alpha=0.0, keep_from=0, job_id="",
                      num_keys=None, key_id2=None):
@@ -1129,77 +1148,43 @@ class TadEngine:
         """The batch job's verdicts over everything `state` holds, from the state alone (tad_run_state): exactly the rows run() returns
         for the table of the state's series points with the same algo and parameters.  Needs a state with series=True and times=True
         (and history=True for DBSCAN); the state is left unchanged.  Narrow the window with TadState.trim first."""
-        if algo not in capi.TAD_ALGO:
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "algo must be EWMA, ARIMA, DBSCAN or DROP")
-        if not self._lib.tad_features() & capi.TAD_FEATURE_STATE_RUN:
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_run_state (TAD_FEATURE_STATE_RUN)")
-        job = capi.Job(algo=capi.TAD_ALGO[algo], ewma_alpha=float(alpha), dbscan_eps=float(eps), dbscan_min_samples=int(min_samples),
-                       arima_maxiter=int(maxiter), flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
-        res = C.POINTER(capi.Result)()
-        rc = self._lib.tad_run_state(self._h, state._h, C.byref(job), capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST,
-                                     C.byref(res))
-        self._check(rc)
-        return TadResult(self, res)
+        job = self._detector_job(algo, alpha, eps, min_samples, maxiter, emit_all=emit_all, job_id=job_id)
+        self._need("STATE_RUN", "tad_run_state")
+        return self._state_rows("tad_run_state", state, job, out)
 
     def run_state_window(self, state, from_t=0, to_t=0, keep_points=0, algo="EWMA", alpha=0.0, eps=0.0, min_samples=0, maxiter=0, emit_all=False,
                          out="host", job_id=""):
         """run_state over a window of what `state` holds, read-only (tad_run_state_window): of every key's series the points with
         flow_end_s >= from_t and < to_t (0 = no bound on that side), then the newest keep_points of those (0 = all).  Exactly the rows
         run() returns for the table of those points; the state is left unchanged.  Both bounds act on flowEndSeconds."""
-        if algo not in capi.TAD_ALGO:
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "algo must be EWMA, ARIMA, DBSCAN or DROP")
-        if not self._lib.tad_features() & capi.TAD_FEATURE_STATE_WINDOW:
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_run_state_window (TAD_FEATURE_STATE_WINDOW)")
-        job = capi.Job(algo=capi.TAD_ALGO[algo], ewma_alpha=float(alpha), dbscan_eps=float(eps), dbscan_min_samples=int(min_samples),
-                       arima_maxiter=int(maxiter), flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
-        res = C.POINTER(capi.Result)()
-        rc = self._lib.tad_run_state_window(self._h, state._h, C.byref(job), int(from_t), int(to_t), int(keep_points),
-                                            capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
-        self._check(rc)
-        return TadResult(self, res)
+        job = self._detector_job(algo, alpha, eps, min_samples, maxiter, emit_all=emit_all, job_id=job_id)
+        self._need("STATE_WINDOW", "tad_run_state_window")
+        return self._state_rows("tad_run_state_window", state, job, out, int(from_t), int(to_t), int(keep_points))
 
     # ---- the drop detector on a state (tad_drop_state / tad_drop_stream) ----
-    def _need_state_drop(self, what):
-        if not (getattr(self._lib, "tad_features", None) and self._lib.tad_features() & capi.TAD_FEATURE_STATE_DROP):
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no %s (TAD_FEATURE_STATE_DROP)" % what)
-
     def drop_state(self, state, from_t=0, to_t=0, keep_points=0, nsigma=0.0, min_samples=0, emit_all=False, out="host", job_id=""):
         """The drop detector's batch verdicts over a window of what `state` holds, read-only (tad_drop_state): exactly the rows
         run("DROP") returns for the table of the window's series points with the same nsigma / min_samples (0 = the defaults 3 and 3).
         The window is run_state_window's; all zero is the whole state.  Needs a state with series=True and times=True."""
-        self._need_state_drop("tad_drop_state")
-        job = capi.Job(algo=capi.TAD_ALGO["DROP"], drop_nsigma=float(nsigma), drop_min_samples=int(min_samples),
-                       flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
-        res = C.POINTER(capi.Result)()
-        rc = self._lib.tad_drop_state(self._h, state._h, C.byref(job), int(from_t), int(to_t), int(keep_points),
-                                      capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
-        self._check(rc)
-        return TadResult(self, res)
+        self._need("STATE_DROP", "tad_drop_state")
+        job = self._detector_job("DROP", nsigma=nsigma, min_samples=min_samples, emit_all=emit_all, job_id=job_id)
+        return self._state_rows("tad_drop_state", state, job, out, int(from_t), int(to_t), int(keep_points))
 
     def drop_stream(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, nsigma=0.0, min_samples=0, alpha=0.0,
                     emit_all=False, out="host", job_id="", num_keys=None, key_id2=None):
         """One batch of the periodical drop job on `state` (tad_drop_stream): the state advances exactly as under run_stream with EWMA;
         the rows are those run("DROP") over everything the state now holds emits for this batch's points.  Needs a state with
         series=True (times and history are kept up when present)."""
-        self._need_state_drop("tad_drop_stream")
+        self._need("STATE_DROP", "tad_drop_stream")
         if agg_flow not in capi.TAD_AGG:
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "agg_flow must be '', pod, svc or external")
+        job = self._detector_job("DROP", alpha=alpha, nsigma=nsigma, min_samples=min_samples, emit_all=emit_all, job_id=job_id, agg_flow=agg_flow,
+                                 value_op=value_op)
         cols, narrow, keep = self._stream_columns(state, key_id, flow_end_s, value, key_id2, num_keys, lattice)
-        job = capi.Job(algo=capi.TAD_ALGO["DROP"], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
-                       drop_nsigma=float(nsigma), drop_min_samples=int(min_samples),
-                       flags=(capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0) | narrow, id=job_id.encode()[:63])
-        res = C.POINTER(capi.Result)()
-        rc = self._lib.tad_drop_stream(self._h, state._h, C.byref(job), C.byref(cols),
-                                       capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
-        del keep
-        self._check(rc)
-        return TadResult(self, res)
+        job.flags |= narrow
+        return self._state_rows("tad_drop_stream", state, job, out, C.byref(cols))
 
     # ---- the window calls over selected keys (tad_run_state_keys / tad_drop_state_keys) ----
-    def _need_key_select(self, what):
-        if not (getattr(self._lib, "tad_features", None) and self._lib.tad_features() & capi.TAD_FEATURE_KEY_SELECT):
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no %s (TAD_FEATURE_KEY_SELECT)" % what)
-
     @staticmethod
     def _key_mask(key_keep):
         """-> (pointer, length, tad_mem, what must stay alive) of a key mask: None, a DeviceArray of bytes, or anything numpy reads"""
@@ -1216,31 +1201,17 @@ class TadEngine:
         (a numpy array, or a DeviceArray such as KeyDict.select returns; any non-zero byte selects; None = every key).  Exactly the rows
         of run_state_window whose key is selected, with the state's own key ids; the stats and the ARIMA counters are those of a job
         over the selected points alone."""
-        if algo not in capi.TAD_ALGO:
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "algo must be EWMA, ARIMA, DBSCAN or DROP")
-        self._need_key_select("tad_run_state_keys")
+        job = self._detector_job(algo, alpha, eps, min_samples, maxiter, emit_all=emit_all, job_id=job_id)
+        self._need("KEY_SELECT", "tad_run_state_keys")
         ptr, n, mem, alive = self._key_mask(key_keep)
-        job = capi.Job(algo=capi.TAD_ALGO[algo], ewma_alpha=float(alpha), dbscan_eps=float(eps), dbscan_min_samples=int(min_samples),
-                       arima_maxiter=int(maxiter), flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
-        res = C.POINTER(capi.Result)()
-        rc = self._lib.tad_run_state_keys(self._h, state._h, C.byref(job), int(from_t), int(to_t), int(keep_points), ptr, n, mem,
-                                          capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
-        del alive
-        self._check(rc)
-        return TadResult(self, res)
+        return self._state_rows("tad_run_state_keys", state, job, out, int(from_t), int(to_t), int(keep_points), ptr, n, mem)
 
     def drop_state_keys(self, state, key_keep, from_t=0, to_t=0, keep_points=0, nsigma=0.0, min_samples=0, emit_all=False, out="host", job_id=""):
         """drop_state over the keys `key_keep` selects, read-only (tad_drop_state_keys); key_keep as for run_state_keys"""
-        self._need_key_select("tad_drop_state_keys")
+        self._need("KEY_SELECT", "tad_drop_state_keys")
         ptr, n, mem, alive = self._key_mask(key_keep)
-        job = capi.Job(algo=capi.TAD_ALGO["DROP"], drop_nsigma=float(nsigma), drop_min_samples=int(min_samples),
-                       flags=capi.TAD_FLAG_EMIT_ALL_POINTS if emit_all else 0, id=job_id.encode()[:63])
-        res = C.POINTER(capi.Result)()
-        rc = self._lib.tad_drop_state_keys(self._h, state._h, C.byref(job), int(from_t), int(to_t), int(keep_points), ptr, n, mem,
-                                           capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(res))
-        del alive
-        self._check(rc)
-        return TadResult(self, res)
+        job = self._detector_job("DROP", nsigma=nsigma, min_samples=min_samples, emit_all=emit_all, job_id=job_id)
+        return self._state_rows("tad_drop_state_keys", state, job, out, int(from_t), int(to_t), int(keep_points), ptr, n, mem)
 
     # ---- the drop job's flow-row query (tad_drop_select) ----
     def drop_select(self, ingress_action, egress_action, flow_start_s, src_ip, src_pod_ns, src_pod_name, dst_ip, dst_pod_ns, dst_pod_name,

@@ -96,7 +96,7 @@ def test_the_unit_is_hip_in_its_own_source():
     for name in ("k_kd_probe", "k_kd_append", "k_kd_fix", "k_kd_rehash", "launch_kd_probe", "launch_kd_append", "launch_kd_rehash", "atomicCAS"):
         assert name in src, name
     assert "asm" not in src and "rocprim" not in src.lower() and "hipcub" not in src.lower()
-    assert re.findall(r"#include\s+[<\"]([^>\"]+)[>\"]", src) == ["tad_internal.h"]
+    assert re.findall(r"#include\s+[<\"]([^>\"]+)[>\"]", src) == ["tad_internal.h", "tad_slots.h"]
 
 
 class _FakeLib:

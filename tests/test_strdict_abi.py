@@ -112,10 +112,12 @@ def test_the_unit_is_hip_in_its_own_source():
     includes = re.findall(r"#include\s+[<\"]([^>\"]+)[>\"]", src)
     assert includes == ["tad_internal.h", "tad_strbytes.h"]                                 # project-internal headers only
     assert all(os.path.exists(os.path.join(csrc, h)) for h in includes)
-    # the byte helpers live in the shared header, and tad_encode_strings' file uses them from there
+    # the byte helpers live in the shared header, and tad_encode_strings' file uses them from there; the column they read (StrBatch: what StrArgs and
+    # SdBatch were) lives in tad_internal.h, where the host side fills it
     shared = open(os.path.join(csrc, "tad_strbytes.h")).read()
     fz = open(os.path.join(csrc, "tad_factorize.hip")).read()
-    for name in ("struct StrArgs", "bool se_span(", "uint64_t se_load(", "uint64_t se_load_lds(", "uint64_t se_hash(", "bool se_same_as("):
+    assert "struct StrBatch" in open(os.path.join(csrc, "tad_internal.h")).read() and "struct StrBatch" not in fz and "struct StrArgs" not in fz
+    for name in ("bool se_span(", "uint64_t se_load(", "uint64_t se_load_lds(", "uint64_t se_hash(", "bool se_same_as("):
         assert name in shared and name not in fz, name
     assert '#include "tad_strbytes.h"' in fz
 

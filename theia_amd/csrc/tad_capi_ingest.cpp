@@ -1,7 +1,7 @@
 // tad_capi_ingest.cpp — the ingest entry points of include/tad.h: rows bucketed by owner for the all-to-all(v),
 // key tuples -> dense ids, Arrow string columns -> dictionary codes, Arrow buffers -> 8-byte device columns, row masks, the synthetic table,
 // flow rows -> the drop job's rows.
-#include "tad_engine.h"
+#include "tad_capi_dict.h"
 
 using namespace tad;
 using namespace tadh;
@@ -72,65 +72,49 @@ static int factorize_impl(tad_engine *eng, const tad_key_columns *kc, uint64_t *
   hipStream_t s = e->stream;
   const bool host = kc->memory == TAD_MEM_HOST;
   // host inputs are staged behind the table block in the same scratch: columns, masks, outputs
-  const size_t col_bytes = (n * 8 + 255) & ~(size_t)255, mask_bytes = (n + 255) & ~(size_t)255, fr_bytes = (first_row_cap * 8 + 255) & ~(size_t)255;
-  const size_t stage = host ? (size_t)kc->n_cols * sides * col_bytes + 2 * mask_bytes + sides * col_bytes + fr_bytes : 0;
+  const size_t col_bytes = up256(n * 8), fr_bytes = up256(first_row_cap * 8);
+  const size_t stage = host ? key_stage_bytes(kc) + sides * col_bytes + fr_bytes : 0;
+  unsigned long long nk = 0;
+  uint64_t *d_key = key_id, *d_key2 = key_id2, *d_fr = first_row;
   // the table starts small and grows when the device says so (tad_factorize.hip): 2^20 -> 2^24 -> 2 n slots
-  for (uint64_t slots = factorize_first_slots(n * sides);;) {
-    const size_t tb = factorize_temp_bytes(n * sides, slots);
-    if (tb + stage + 64 > e->ws_limit)
-      return fail(e, TAD_ERR_GRID_TOO_LARGE, "tad_factorize needs %llu bytes of scratch > workspace limit %llu", (unsigned long long)(tb + stage), (unsigned long long)e->ws_limit);
+  int rc = with_factorize_ladder(e, n * sides, "tad_factorize", "", "table", 64, [&](size_t tb) { return tb + stage; }, [&](uint64_t slots, size_t tb, bool *grow) -> int {
     int rc;
     if ((rc = ensure(e, e->sp_temp, tb + stage + 64)) != TAD_OK) return rc;
     unsigned char *base = static_cast<unsigned char *>(e->sp_temp.p);
     unsigned long long *nk_dev = reinterpret_cast<unsigned long long *>(base + tb);
-    const long long *ca[kFzMaxCols] = {}, *cb[kFzMaxCols] = {};
-    const uint8_t *ka = kc->keep_a, *kb = kc->keep_b;
-    uint64_t *d_key = key_id, *d_key2 = key_id2, *d_fr = first_row;
+    TupleBatch A;      // (a host batch is staged again on every rung: the block may have moved)
+    if ((rc = stage_key_columns(e, kc, host ? base + tb + 64 : nullptr, &A)) != TAD_OK) return rc;
     if (host) {
-      unsigned char *p = base + tb + 64;
-      for (int c = 0; c < kc->n_cols; ++c) {
-        HIP_TRY(e, hipMemcpyAsync(p, kc->cols_a[c], n * 8, hipMemcpyHostToDevice, s)); ca[c] = reinterpret_cast<const long long *>(p); p += col_bytes;
-        if (sides == 2) { HIP_TRY(e, hipMemcpyAsync(p, kc->cols_b[c], n * 8, hipMemcpyHostToDevice, s)); cb[c] = reinterpret_cast<const long long *>(p); p += col_bytes; }
-      }
-      if (ka) { HIP_TRY(e, hipMemcpyAsync(p, ka, n, hipMemcpyHostToDevice, s)); ka = p; }
-      p += mask_bytes;
-      if (kb) { HIP_TRY(e, hipMemcpyAsync(p, kb, n, hipMemcpyHostToDevice, s)); kb = p; }
-      p += mask_bytes;
+      unsigned char *p = base + tb + 64 + key_stage_bytes(kc);
       d_key = reinterpret_cast<uint64_t *>(p); p += col_bytes;
       if (sides == 2) { d_key2 = reinterpret_cast<uint64_t *>(p); p += col_bytes; }
       d_fr = reinterpret_cast<uint64_t *>(p);
-    } else {
-      for (int c = 0; c < kc->n_cols; ++c) { ca[c] = reinterpret_cast<const long long *>(kc->cols_a[c]); if (sides == 2) cb[c] = reinterpret_cast<const long long *>(kc->cols_b[c]); }
     }
     uint32_t *flags_dev = nullptr;
-    launch_factorize(s, ca, ka, sides == 2 ? cb : nullptr, kb, n, kc->n_cols, slots, base, d_key, d_key2, d_fr, first_row_cap, nk_dev, &flags_dev,
+    launch_factorize(s, A.a, A.keep_a, sides == 2 ? A.b : nullptr, A.keep_b, n, kc->n_cols, slots, base, d_key, d_key2, d_fr, first_row_cap, nk_dev, &flags_dev,
                      hist_bins, hpl.G, hpl.chunk);
-    unsigned long long nk = 0;
     uint32_t flags = 0;
     HIP_TRY(e, hipMemcpyAsync(&nk, nk_dev, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipMemcpyAsync(&flags, flags_dev, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
     HIP_TRY(e, hipGetLastError());
-    if (flags != 0) {      // more keys than this table takes: once more with the next size (a host batch is staged again: the block may have moved)
-      const uint64_t next = factorize_next_slots(n * sides, slots);
-      if (next == slots) return fail(e, TAD_ERR_HIP, "tad_factorize: the full-size table filled up");
-      slots = next;
-      continue;
-    }
-    if (host) {
-      HIP_TRY(e, hipMemcpyAsync(key_id, d_key, n * 8, hipMemcpyDeviceToHost, s));
-      if (sides == 2) HIP_TRY(e, hipMemcpyAsync(key_id2, d_key2, n * 8, hipMemcpyDeviceToHost, s));
-      const uint64_t m = nk < first_row_cap ? nk : first_row_cap;
-      if (m) HIP_TRY(e, hipMemcpyAsync(first_row, d_fr, m * 8, hipMemcpyDeviceToHost, s));
-      HIP_TRY(e, hipStreamSynchronize(s));
-    }
-    *num_keys = nk;
-    if (hist_bins != nullptr && nk != 0 && part_plan_bins(n, nk, sides == 2, &hpl)) {   // what the kernel derived from the device-side count
-      hist->n_rows = n; hist->num_keys = nk; hist->chunk_rows = hpl.chunk;
-      hist->workgroups = (uint32_t)hpl.G; hist->nbins = hpl.nbins; hist->shift = (uint32_t)hpl.shift_bin; hist->sides = sides;
-    }
+    *grow = flags != 0;      // more keys than this table takes
     return TAD_OK;
+  });
+  if (rc != TAD_OK) return rc;
+  if (host) {
+    HIP_TRY(e, hipMemcpyAsync(key_id, d_key, n * 8, hipMemcpyDeviceToHost, s));
+    if (sides == 2) HIP_TRY(e, hipMemcpyAsync(key_id2, d_key2, n * 8, hipMemcpyDeviceToHost, s));
+    const uint64_t m = nk < first_row_cap ? nk : first_row_cap;
+    if (m) HIP_TRY(e, hipMemcpyAsync(first_row, d_fr, m * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
   }
+  *num_keys = nk;
+  if (hist_bins != nullptr && nk != 0 && part_plan_bins(n, nk, sides == 2, &hpl)) {   // what the kernel derived from the device-side count
+    hist->n_rows = n; hist->num_keys = nk; hist->chunk_rows = hpl.chunk;
+    hist->workgroups = (uint32_t)hpl.G; hist->nbins = hpl.nbins; hist->shift = (uint32_t)hpl.shift_bin; hist->sides = sides;
+  }
+  return TAD_OK;
 }
 
 extern "C" {
@@ -161,57 +145,45 @@ int tad_encode_strings(tad_engine *eng, const tad_string_column *col, int64_t *c
   HIP_TRY(e, hipSetDevice(e->device));
   hipStream_t s = e->stream;
   const bool host = col->memory == TAD_MEM_HOST;
-  const int off64 = col->offset_bits == 64;
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   // host inputs are staged behind the table block: offsets, bytes (+ 8 of slack: the last aligned word), validity, codes, first rows
-  const size_t off_bytes = up((n + 1) * (off64 ? 8 : 4)), data_bytes = up(col->data_bytes + 8);
-  const size_t val_bytes = col->validity ? up((col->validity_offset + n + 7) / 8) : 0, code_bytes = up(n * 8), fr_bytes = up(first_row_cap * 8);
-  const size_t stage = host ? off_bytes + data_bytes + val_bytes + code_bytes + fr_bytes : 0;
-  for (uint64_t slots = factorize_first_slots(n);;) {
-    const size_t tb = factorize_temp_bytes(n, slots);
-    if (tb + stage + 64 > e->ws_limit)
-      return fail(e, TAD_ERR_GRID_TOO_LARGE, "tad_encode_strings needs %llu bytes of scratch > workspace limit %llu", (unsigned long long)(tb + stage), (unsigned long long)e->ws_limit);
+  const size_t code_bytes = up256(n * 8), fr_bytes = up256(first_row_cap * 8);
+  const size_t stage = host ? string_stage_bytes(col, 8) + code_bytes + fr_bytes : 0;
+  unsigned long long nv = 0;
+  long long *d_codes = reinterpret_cast<long long *>(codes);
+  uint64_t *d_fr = first_row;
+  // more distinct values than a table takes: once more with the next size (2^20 -> 2^24 -> 2 n slots)
+  int rc = with_factorize_ladder(e, n, "tad_encode_strings", "", "table", 64, [&](size_t tb) { return tb + stage; }, [&](uint64_t slots, size_t tb, bool *grow) -> int {
     int rc;
     if ((rc = ensure(e, e->sp_temp, tb + stage + 64)) != TAD_OK) return rc;
     unsigned char *base = static_cast<unsigned char *>(e->sp_temp.p);
     unsigned long long *nv_dev = reinterpret_cast<unsigned long long *>(base + tb);
-    const void *d_off = col->offsets;
-    const uint8_t *d_data = col->data, *d_valid = col->validity;
-    long long *d_codes = reinterpret_cast<long long *>(codes);
-    uint64_t *d_fr = first_row;
+    StrBatch B;
+    if ((rc = stage_string_column(e, col, host ? base + tb + 64 : nullptr, 8, &B)) != TAD_OK) return rc;
     if (host) {
-      unsigned char *p = base + tb + 64;
-      HIP_TRY(e, hipMemcpyAsync(p, col->offsets, (n + 1) * (off64 ? 8 : 4), hipMemcpyHostToDevice, s)); d_off = p; p += off_bytes;
-      if (col->data_bytes) HIP_TRY(e, hipMemcpyAsync(p, col->data, col->data_bytes, hipMemcpyHostToDevice, s));
-      d_data = p; p += data_bytes;
-      if (col->validity) { HIP_TRY(e, hipMemcpyAsync(p, col->validity, (col->validity_offset + n + 7) / 8, hipMemcpyHostToDevice, s)); d_valid = p; p += val_bytes; }
+      unsigned char *p = base + tb + 64 + string_stage_bytes(col, 8);
       d_codes = reinterpret_cast<long long *>(p); p += code_bytes;
       d_fr = reinterpret_cast<uint64_t *>(p);
     }
     uint32_t *flags_dev = nullptr;
-    launch_encode_strings(s, d_off, off64, d_data, col->data_bytes, d_valid, col->validity_offset, n, slots, base, d_codes, d_fr, first_row_cap, nv_dev, &flags_dev);
-    unsigned long long nv = 0;
+    launch_encode_strings(s, B.off, B.off64, B.data, B.data_bytes, B.valid, B.valid_off, n, slots, base, d_codes, d_fr, first_row_cap, nv_dev, &flags_dev);
     uint32_t flags = 0;
     HIP_TRY(e, hipMemcpyAsync(&nv, nv_dev, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipMemcpyAsync(&flags, flags_dev, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
     HIP_TRY(e, hipGetLastError());
     if (flags & 2u) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_encode_strings: offsets decrease or point beyond data_bytes");
-    if (flags & 1u) {      // more distinct values than this table takes: once more with the next size (2^20 -> 2^24 -> 2 n slots)
-      const uint64_t next = factorize_next_slots(n, slots);
-      if (next == slots) return fail(e, TAD_ERR_HIP, "tad_encode_strings: the full-size table filled up");
-      slots = next;
-      continue;
-    }
-    if (host) {
-      HIP_TRY(e, hipMemcpyAsync(codes, d_codes, n * 8, hipMemcpyDeviceToHost, s));
-      const uint64_t m = nv < first_row_cap ? nv : first_row_cap;
-      if (m) HIP_TRY(e, hipMemcpyAsync(first_row, d_fr, m * 8, hipMemcpyDeviceToHost, s));
-      HIP_TRY(e, hipStreamSynchronize(s));
-    }
-    *num_values = nv;
+    *grow = (flags & 1u) != 0;
     return TAD_OK;
+  });
+  if (rc != TAD_OK) return rc;
+  if (host) {
+    HIP_TRY(e, hipMemcpyAsync(codes, d_codes, n * 8, hipMemcpyDeviceToHost, s));
+    const uint64_t m = nv < first_row_cap ? nv : first_row_cap;
+    if (m) HIP_TRY(e, hipMemcpyAsync(first_row, d_fr, m * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
   }
+  *num_values = nv;
+  return TAD_OK;
 }
 
 int tad_synth_generate(tad_engine *eng, uint64_t seed, uint64_t first_row, uint64_t n_rows, uint64_t num_keys,
@@ -324,8 +296,7 @@ int tad_drop_select(tad_engine *eng, const tad_drop_flow_columns *cols, int64_t 
   const size_t scr_b = up(scan_scratch_elems(tiles) * 8), t_b = up((size_t)n * (t32 ? 4 : 8)), c_b = up((size_t)n * 8), a_b = up((size_t)n);
   const size_t stage = host ? 2 * a_b + t_b + (cols->flow_end_s ? t_b : 0) + 6 * c_b + (cols->keep ? a_b : 0) : 0;
   const size_t need = bits_b + cnt_b + off_b + scr_b + 256 + stage;
-  if (need > e->ws_limit)
-    return fail(e, TAD_ERR_GRID_TOO_LARGE, "tad_drop_select needs %llu bytes of scratch > workspace limit %llu", (unsigned long long)need, (unsigned long long)e->ws_limit);
+  if (need > e->ws_limit) return over_limit(e, "tad_drop_select", need);
   int rc;
   if ((rc = ensure(e, e->dsel, need)) != TAD_OK) return rc;
   unsigned char *p = static_cast<unsigned char *>(e->dsel.p);

@@ -1,6 +1,6 @@
 // tad_capi_keydict.cpp — the persistent key dictionary of include/tad.h (tad_keydict_*): the host side of tad_keydict.hip.
 // Order of every call that changes the dictionary: check, size, allocate, grow (capacity only) — and only then touch the contents.
-#include "tad_engine.h"
+#include "tad_capi_dict.h"
 
 using namespace tad;
 using namespace tadh;
@@ -17,56 +17,34 @@ struct tad_keydict {
 
 namespace {
 
-constexpr uint64_t kKdMinSlots = 64, kKdMinKeys = 32, kKdDefaultSlots = 1ull << 20, kKdDefaultKeys = 1ull << 16;
+constexpr uint64_t kKdMinKeys = 32, kKdDefaultSlots = 1ull << 20, kKdDefaultKeys = 1ull << 16;
 constexpr uint64_t kKdMaxKeys = 0xFFFFFFFFull - 1;     // ids < 2^32 - 1
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-uint64_t pow2_at_least(uint64_t x) { uint64_t s = kKdMinSlots; while (s < x) s <<= 1; return s; }
-
-// hipMalloc that gives the idle contexts' buffers back to the device before it fails (as ensure does)
-hipError_t kd_alloc(JobCtx *e, void **p, size_t bytes) {
-  hipError_t r = hipMalloc(p, bytes);
-  if (r != hipSuccess) {
-    (void)hipGetLastError();
-    trim_idle(e->eng, e);
-    r = hipMalloc(p, bytes);
-  }
-  if (r != hipSuccess) { *p = nullptr; (void)hipGetLastError(); }
-  return r;
-}
 
 // Room for `total` keys: key records and a table at load <= 1/2.  Capacity only — K, the ids and the tuples are what they were, whether
 // this succeeds or not; the old arrays stay the dictionary's until the new ones are complete.
 int kd_reserve(JobCtx *e, tad_keydict *d, uint64_t total, uint64_t min_slots = 0) {
   hipStream_t s = e->stream;
   const size_t rec = (size_t)kd_stride(d->n_cols) * 8;
-  unsigned long long *nkeys = nullptr, *ntable = nullptr;
-  uint64_t ncap = d->key_cap, nslots = d->slots;
-  if (total > d->key_cap) {
-    ncap = d->key_cap * 2 > total ? d->key_cap * 2 : total;
-    if (ncap > kKdMaxKeys) ncap = kKdMaxKeys;
-  }
-  if (2 * total > d->slots) nslots = pow2_at_least(2 * total);
-  if (min_slots > nslots) nslots = min_slots;
-  if (ncap == d->key_cap && nslots == d->slots) return TAD_OK;
+  Candidate<unsigned long long> nkeys, ntable;
   hipError_t r = hipSuccess;
-  if (ncap != d->key_cap) r = kd_alloc(e, reinterpret_cast<void **>(&nkeys), ncap * rec);
-  if (r == hipSuccess && nslots != d->slots) r = kd_alloc(e, reinterpret_cast<void **>(&ntable), nslots * 8);
-  if (r == hipSuccess && nkeys && d->K) r = hipMemcpyAsync(nkeys, d->keys, d->K * rec, hipMemcpyDeviceToDevice, s);
-  if (r == hipSuccess && ntable) {
-    r = hipMemsetAsync(ntable, 0xFF, nslots * 8, s);
-    if (r == hipSuccess && d->K) launch_kd_rehash(s, d->keys, d->n_cols, d->K, ntable, nslots, nullptr, false);
+  if (total > d->key_cap) {
+    uint64_t ncap = d->key_cap * 2 > total ? d->key_cap * 2 : total;
+    if (ncap > kKdMaxKeys) ncap = kKdMaxKeys;
+    r = nkeys.alloc(e, ncap, ncap * rec);
+    if (r == hipSuccess && d->K) r = hipMemcpyAsync(nkeys.p, d->keys, d->K * rec, hipMemcpyDeviceToDevice, s);
   }
+  if (r == hipSuccess)
+    r = grow_table(e, d->slots, total, min_slots, &ntable, [&](unsigned long long *t, uint64_t nslots) {
+      if (d->K) launch_kd_rehash(s, d->keys, d->n_cols, d->K, t, nslots, nullptr, false);
+    });
+  if (r == hipSuccess && !nkeys.p && !ntable.p) return TAD_OK;      // room enough
   if (r == hipSuccess) r = hipStreamSynchronize(s);
   if (r == hipSuccess) r = hipGetLastError();
-  if (r != hipSuccess) {
-    if (nkeys) hipFree(nkeys);
-    if (ntable) hipFree(ntable);
+  if (r != hipSuccess)
     return fail(e, r == hipErrorOutOfMemory ? TAD_ERR_OUT_OF_MEMORY : TAD_ERR_HIP, "tad_keydict: no room for %llu keys: %s (dictionary unchanged)",
                 (unsigned long long)total, hipGetErrorString(r));
-  }
-  if (nkeys) { hipFree(d->keys); d->keys = nkeys; d->key_cap = ncap; }
-  if (ntable) { hipFree(d->table); d->table = ntable; d->slots = nslots; }
+  nkeys.commit_into(d->keys, d->key_cap);
+  ntable.commit_into(d->table, d->slots);
   return TAD_OK;
 }
 
@@ -97,11 +75,10 @@ int kd_run(tad_engine *eng, tad_keydict *d, const tad_key_columns *kc, uint64_t 
   const bool host = kc->memory == TAD_MEM_HOST;
   const int nc = kc->n_cols;
   // scratch of the probe: in_key = a host batch's columns and masks, in_key2 = its ids, sp_comp_a = miss flags | miss count, flags, new-key count
-  const size_t col_bytes = up256(n * 8), mask_bytes = up256(n), miss_bytes = up256(V);
-  const size_t stage_in = host ? (size_t)nc * sides * col_bytes + 2 * mask_bytes : 0, stage_out = host ? sides * col_bytes : 0;
+  const size_t col_bytes = up256(n * 8), miss_bytes = up256(V);
+  const size_t stage_in = host ? key_stage_bytes(kc) : 0, stage_out = host ? sides * col_bytes : 0;
   const size_t need0 = stage_in + stage_out + miss_bytes + 256;
-  if (need0 > e->ws_limit)
-    return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu", who, (unsigned long long)need0, (unsigned long long)e->ws_limit);
+  if (need0 > e->ws_limit) return over_limit(e, who, need0);
   int rc;
   if ((rc = ensure(e, e->sp_comp_a, miss_bytes + 256)) != TAD_OK) return rc;
   if (host && ((rc = ensure(e, e->in_key, stage_in)) != TAD_OK || (rc = ensure(e, e->in_key2, stage_out)) != TAD_OK)) return rc;
@@ -110,24 +87,10 @@ int kd_run(tad_engine *eng, tad_keydict *d, const tad_key_columns *kc, uint64_t 
   unsigned long long *n_miss_dev = reinterpret_cast<unsigned long long *>(tail);
   uint32_t *kd_flags_dev = reinterpret_cast<uint32_t *>(tail + 8);
   unsigned long long *nk_dev = reinterpret_cast<unsigned long long *>(tail + 16);
-  KdBatch A{};
-  A.keep_a = kc->keep_a; A.keep_b = kc->keep_b; A.n = n; A.n_cols = nc; A.sides = sides;
-  uint64_t *d_key = key_id, *d_key2 = key_id2;
-  if (host) {
-    unsigned char *p = static_cast<unsigned char *>(e->in_key.p);
-    for (int c = 0; c < nc; ++c) {
-      HIP_TRY(e, hipMemcpyAsync(p, kc->cols_a[c], n * 8, hipMemcpyHostToDevice, s)); A.a[c] = reinterpret_cast<const long long *>(p); p += col_bytes;
-      if (sides == 2) { HIP_TRY(e, hipMemcpyAsync(p, kc->cols_b[c], n * 8, hipMemcpyHostToDevice, s)); A.b[c] = reinterpret_cast<const long long *>(p); p += col_bytes; }
-    }
-    if (A.keep_a) { HIP_TRY(e, hipMemcpyAsync(p, A.keep_a, n, hipMemcpyHostToDevice, s)); A.keep_a = p; }
-    p += mask_bytes;
-    if (A.keep_b) { HIP_TRY(e, hipMemcpyAsync(p, A.keep_b, n, hipMemcpyHostToDevice, s)); A.keep_b = p; }
-    d_key = reinterpret_cast<uint64_t *>(e->in_key2.p);
-    if (sides == 2) d_key2 = d_key + col_bytes / 8;
-  } else {
-    for (int c = 0; c < nc; ++c) { A.a[c] = reinterpret_cast<const long long *>(kc->cols_a[c]); if (sides == 2) A.b[c] = reinterpret_cast<const long long *>(kc->cols_b[c]); }
-  }
-  if (sides == 1) A.keep_b = nullptr;
+  TupleBatch A;
+  if ((rc = stage_key_columns(e, kc, host ? static_cast<unsigned char *>(e->in_key.p) : nullptr, &A)) != TAD_OK) return rc;
+  uint64_t *d_key = host ? reinterpret_cast<uint64_t *>(e->in_key2.p) : key_id;
+  uint64_t *d_key2 = host && sides == 2 ? d_key + col_bytes / 8 : key_id2;
   auto ids_to_host = [&]() -> int {
     HIP_TRY(e, hipMemcpyAsync(key_id, d_key, n * 8, hipMemcpyDeviceToHost, s));
     if (sides == 2) HIP_TRY(e, hipMemcpyAsync(key_id2, d_key2, n * 8, hipMemcpyDeviceToHost, s));
@@ -154,11 +117,8 @@ int kd_run(tad_engine *eng, tad_keydict *d, const tad_key_columns *kc, uint64_t 
   const size_t loc_bytes = sides * col_bytes, fr_bytes = up256((size_t)M * 8);
   unsigned long long m = 0;
   uint64_t *loc_a = nullptr, *loc_b = nullptr, *fr = nullptr;
-  for (uint64_t slots = factorize_first_slots(V);;) {
-    const size_t tb = factorize_temp_bytes(V, slots);
-    const size_t need = need0 + loc_bytes + fr_bytes + tb;
-    if (need > e->ws_limit)
-      return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu", who, (unsigned long long)need, (unsigned long long)e->ws_limit);
+  rc = with_factorize_ladder(e, V, who, "", "scratch table", 0, [&](size_t tb) { return need0 + loc_bytes + fr_bytes + tb; }, [&](uint64_t slots, size_t tb, bool *grow) -> int {
+    int rc;
     if ((rc = ensure(e, e->sp_val_a, loc_bytes)) != TAD_OK || (rc = ensure(e, e->sp_first, fr_bytes)) != TAD_OK || (rc = ensure(e, e->sp_temp, tb)) != TAD_OK) return rc;
     loc_a = static_cast<uint64_t *>(e->sp_val_a.p);
     loc_b = sides == 2 ? loc_a + col_bytes / 8 : nullptr;
@@ -170,11 +130,10 @@ int kd_run(tad_engine *eng, tad_keydict *d, const tad_key_columns *kc, uint64_t 
     HIP_TRY(e, hipMemcpyAsync(&fz_flags, fz_flags_dev, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
     HIP_TRY(e, hipGetLastError());
-    if (fz_flags == 0) break;
-    const uint64_t next = factorize_next_slots(V, slots);      // more new keys than this scratch table takes: once more with the next size
-    if (next == slots) return fail(e, TAD_ERR_HIP, "%s: the full-size scratch table filled up", who);
-    slots = next;
-  }
+    *grow = fz_flags != 0;      // more new keys than this scratch table takes
+    return TAD_OK;
+  });
+  if (rc != TAD_OK) return rc;
   if (m == 0 || m > M) return fail(e, TAD_ERR_HIP, "%s: %llu new keys from %llu miss rows", who, (unsigned long long)m, (unsigned long long)M);
   if (d->K + m > kKdMaxKeys)
     return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: %llu keys do not fit 32-bit key ids (dictionary unchanged)", who, (unsigned long long)(d->K + m));
@@ -192,9 +151,7 @@ int kd_run(tad_engine *eng, tad_keydict *d, const tad_key_columns *kc, uint64_t 
   }
   uint32_t kd_flags = 0;
   if (r == hipSuccess) r = hipMemcpyAsync(&kd_flags, kd_flags_dev, 4, hipMemcpyDeviceToHost, s);
-  const hipError_t rs = hipStreamSynchronize(s);      // (always: the append is in flight)
-  if (r == hipSuccess) r = rs;
-  if (r == hipSuccess) r = hipGetLastError();
+  r = finish_stream(e, r);      // (always synchronises: the append is in flight)
   if (r != hipSuccess || (kd_flags & KD_FLAG_BAD_ROW))
     return fail(e, TAD_ERR_HIP, "%s: appending %llu keys failed: %s", who, (unsigned long long)m, hipGetErrorString(r));
   d->K += m;
@@ -221,18 +178,19 @@ int tad_keydict_create(tad_engine *eng, int32_t n_cols, uint64_t expected_keys, 
   tad_keydict *d = new (std::nothrow) tad_keydict();
   if (!d) return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory");
   d->n_cols = n_cols;
-  d->slots = expected_keys ? pow2_at_least(2 * expected_keys) : kKdDefaultSlots;
-  d->key_cap = expected_keys ? (expected_keys > kKdMinKeys ? expected_keys : kKdMinKeys) : kKdDefaultKeys;
-  hipError_t r = kd_alloc(e, reinterpret_cast<void **>(&d->table), d->slots * 8);
-  if (r == hipSuccess) r = kd_alloc(e, reinterpret_cast<void **>(&d->keys), d->key_cap * (size_t)kd_stride(n_cols) * 8);
-  if (r == hipSuccess) r = hipMemsetAsync(d->table, 0xFF, d->slots * 8, e->stream);
+  const uint64_t slots = expected_keys ? pow2_at_least(2 * expected_keys) : kKdDefaultSlots;
+  const uint64_t key_cap = expected_keys ? (expected_keys > kKdMinKeys ? expected_keys : kKdMinKeys) : kKdDefaultKeys;
+  Candidate<unsigned long long> table, keys;
+  hipError_t r = table.alloc(e, slots, slots * 8);
+  if (r == hipSuccess) r = keys.alloc(e, key_cap, key_cap * (size_t)kd_stride(n_cols) * 8);
+  if (r == hipSuccess) r = hipMemsetAsync(table.p, 0xFF, slots * 8, e->stream);
   if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
   if (r != hipSuccess) {
-    if (d->table) hipFree(d->table);
-    if (d->keys) hipFree(d->keys);
     delete d;
     return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_keydict_create: %s", hipGetErrorString(r));
   }
+  table.commit_into(d->table, d->slots);
+  keys.commit_into(d->keys, d->key_cap);
   *out = d;
   return TAD_OK;
 }
@@ -331,29 +289,23 @@ int tad_keydict_import(tad_engine *eng, tad_keydict *d, uint64_t n_keys, const i
   const uint64_t ncap = n_keys > d->key_cap ? n_keys : d->key_cap;
   uint64_t nslots = pow2_at_least(2 * n_keys);
   if (nslots < d->slots) nslots = d->slots;
-  unsigned long long *nkeys = nullptr, *ntable = nullptr;
-  hipError_t r = kd_alloc(e, reinterpret_cast<void **>(&nkeys), ncap * stride * 8);
-  if (r == hipSuccess) r = kd_alloc(e, reinterpret_cast<void **>(&ntable), nslots * 8);
-  if (r == hipSuccess) r = hipMemcpyAsync(nkeys, rows.data(), n_keys * stride * 8, hipMemcpyHostToDevice, s);
-  if (r == hipSuccess) r = hipMemsetAsync(ntable, 0xFF, nslots * 8, s);
+  Candidate<unsigned long long> nkeys, ntable;
+  hipError_t r = nkeys.alloc(e, ncap, ncap * stride * 8);
+  if (r == hipSuccess) r = ntable.alloc(e, nslots, nslots * 8);
+  if (r == hipSuccess) r = hipMemcpyAsync(nkeys.p, rows.data(), n_keys * stride * 8, hipMemcpyHostToDevice, s);
+  if (r == hipSuccess) r = hipMemsetAsync(ntable.p, 0xFF, nslots * 8, s);
   if (r == hipSuccess) r = hipMemsetAsync(flags_dev, 0, 4, s);
   uint32_t flags = 0;
   if (r == hipSuccess) {
-    launch_kd_rehash(s, nkeys, d->n_cols, n_keys, ntable, nslots, flags_dev, true);
+    launch_kd_rehash(s, nkeys.p, d->n_cols, n_keys, ntable.p, nslots, flags_dev, true);
     r = hipMemcpyAsync(&flags, flags_dev, 4, hipMemcpyDeviceToHost, s);
   }
-  const hipError_t rs = hipStreamSynchronize(s);
-  if (r == hipSuccess) r = rs;
-  if (r == hipSuccess) r = hipGetLastError();
-  if (r != hipSuccess || flags != 0) {
-    if (nkeys) hipFree(nkeys);
-    if (ntable) hipFree(ntable);
-    if (r != hipSuccess)
-      return fail(e, r == hipErrorOutOfMemory ? TAD_ERR_OUT_OF_MEMORY : TAD_ERR_HIP, "tad_keydict_import: %s (dictionary unchanged)", hipGetErrorString(r));
-    return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_import: two keys hold the same tuple (dictionary unchanged)");
-  }
-  hipFree(d->keys); d->keys = nkeys; d->key_cap = ncap;
-  hipFree(d->table); d->table = ntable; d->slots = nslots;
+  r = finish_stream(e, r);
+  if (r != hipSuccess)
+    return fail(e, r == hipErrorOutOfMemory ? TAD_ERR_OUT_OF_MEMORY : TAD_ERR_HIP, "tad_keydict_import: %s (dictionary unchanged)", hipGetErrorString(r));
+  if (flags != 0) return fail(e, TAD_ERR_INVALID_ARGUMENT, "tad_keydict_import: two keys hold the same tuple (dictionary unchanged)");
+  nkeys.commit_into(d->keys, d->key_cap);
+  ntable.commit_into(d->table, d->slots);
   d->K = n_keys;
   return TAD_OK;
 }
@@ -390,8 +342,7 @@ int tad_keydict_select(tad_engine *eng, const tad_keydict *d, int32_t n_terms, c
   if (host)
     for (int t = 0; t < n_terms; ++t) stage_in += up256(mask_len[t]);
   const size_t need = 256 + (host ? stage_in + up256(K) : 0);
-  if (need > e->ws_limit)
-    return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu", who, (unsigned long long)need, (unsigned long long)e->ws_limit);
+  if (need > e->ws_limit) return over_limit(e, who, need);
   int rc;
   if ((rc = ensure(e, e->sp_comp_a, 256)) != TAD_OK) return rc;
   if (host && ((stage_in && (rc = ensure(e, e->in_key, stage_in)) != TAD_OK) || (rc = ensure(e, e->in_key2, up256(K))) != TAD_OK)) return rc;
@@ -448,9 +399,7 @@ int tad_keydict_compact(tad_engine *eng, tad_keydict *d, const uint64_t *remap, 
   // scratch: in_key = a host remap; sp_comp_a = live flags | error word; sp_val_a = survivors below, K + 1
   const size_t live_bytes = up256(K * 4), below_bytes = up256((K + 1) * 8), scan_bytes = scan_scratch_elems(K) * sizeof(unsigned long long);
   const size_t need = (host ? up256(K * 8) : 0) + live_bytes + 256 + below_bytes + scan_bytes;
-  if (need > e->ws_limit)
-    return fail(e, TAD_ERR_GRID_TOO_LARGE, "tad_keydict_compact needs %llu bytes of scratch > workspace limit %llu (dictionary unchanged)",
-                (unsigned long long)need, (unsigned long long)e->ws_limit);
+  if (need > e->ws_limit) return over_limit(e, "tad_keydict_compact", need, " (dictionary unchanged)");
   int rc;
   if ((rc = ensure(e, e->sp_comp_a, live_bytes + 256)) != TAD_OK || (rc = ensure(e, e->sp_val_a, below_bytes)) != TAD_OK ||
       (rc = ensure(e, e->scan_scratch, scan_bytes)) != TAD_OK || (host && (rc = ensure(e, e->in_key, up256(K * 8))) != TAD_OK))
@@ -483,23 +432,20 @@ int tad_keydict_compact(tad_engine *eng, tad_keydict *d, const uint64_t *remap, 
   uint64_t ncap = 2 * m > kKdMinKeys ? 2 * m : kKdMinKeys, nslots = pow2_at_least(4 * m);
   if (ncap > d->key_cap) ncap = d->key_cap;
   if (nslots > d->slots) nslots = d->slots;
-  unsigned long long *nkeys = nullptr, *ntable = nullptr;
-  hipError_t r = kd_alloc(e, reinterpret_cast<void **>(&nkeys), ncap * rec);
-  if (r == hipSuccess) r = kd_alloc(e, reinterpret_cast<void **>(&ntable), nslots * 8);
-  if (r == hipSuccess) r = hipMemsetAsync(ntable, 0xFF, nslots * 8, s);
+  Candidate<unsigned long long> nkeys, ntable;
+  hipError_t r = nkeys.alloc(e, ncap, ncap * rec);
+  if (r == hipSuccess) r = ntable.alloc(e, nslots, nslots * 8);
+  if (r == hipSuccess) r = hipMemsetAsync(ntable.p, 0xFF, nslots * 8, s);
   if (r == hipSuccess) {
-    launch_kd_compact(s, d_remap, below, K, d->keys, d->n_cols, nkeys, err_dev);
-    if (m) launch_kd_rehash(s, nkeys, d->n_cols, m, ntable, nslots, nullptr, false);
+    launch_kd_compact(s, d_remap, below, K, d->keys, d->n_cols, nkeys.p, err_dev);
+    if (m) launch_kd_rehash(s, nkeys.p, d->n_cols, m, ntable.p, nslots, nullptr, false);
     r = hipStreamSynchronize(s);
   }
   if (r == hipSuccess) r = hipGetLastError();
-  if (r != hipSuccess) {
-    if (nkeys) hipFree(nkeys);
-    if (ntable) hipFree(ntable);
+  if (r != hipSuccess)
     return fail(e, r == hipErrorOutOfMemory ? TAD_ERR_OUT_OF_MEMORY : TAD_ERR_HIP, "tad_keydict_compact: %s (dictionary unchanged)", hipGetErrorString(r));
-  }
-  hipFree(d->keys); d->keys = nkeys; d->key_cap = ncap;
-  hipFree(d->table); d->table = ntable; d->slots = nslots;
+  nkeys.commit_into(d->keys, d->key_cap);
+  ntable.commit_into(d->table, d->slots);
   d->K = m;
   if (num_keys) *num_keys = m;
   return TAD_OK;

@@ -1,7 +1,7 @@
 // tad_capi_strdict.cpp — the persistent string dictionary of include/tad.h (tad_strdict_*): the host side of tad_strdict.hip.
 // Order of every call that changes the dictionary: check, probe (the offsets are validated there), size, allocate, grow (capacity only) —
 // and only then touch the contents.
-#include "tad_engine.h"
+#include "tad_capi_dict.h"
 
 using namespace tad;
 using namespace tadh;
@@ -19,62 +19,44 @@ struct tad_strdict {
 
 namespace {
 
-constexpr uint64_t kSdMinSlots = 64, kSdMinValues = 32, kSdDefaultSlots = 1ull << 20, kSdDefaultValues = 1ull << 16, kSdDefaultArena = 4ull << 20;
+constexpr uint64_t kSdMinValues = 32, kSdDefaultSlots = 1ull << 20, kSdDefaultValues = 1ull << 16, kSdDefaultArena = 4ull << 20;
 constexpr uint64_t kSdMaxValues = 0xFFFFFFFFull - 1;     // codes < 2^32 - 1
 constexpr uint64_t kNoCount = ~0ull;
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 uint64_t up16(uint64_t x) { return (x + 15) & ~15ull; }
-uint64_t pow2_at_least(uint64_t x) { uint64_t s = kSdMinSlots; while (s < x) s <<= 1; return s; }
-
-// hipMalloc that gives the idle contexts' buffers back to the device before it fails (as ensure does)
-hipError_t sd_alloc(JobCtx *e, void **p, size_t bytes) {
-  hipError_t r = hipMalloc(p, bytes);
-  if (r != hipSuccess) {
-    (void)hipGetLastError();
-    trim_idle(e->eng, e);
-    r = hipMalloc(p, bytes);
-  }
-  if (r != hipSuccess) { *p = nullptr; (void)hipGetLastError(); }
-  return r;
-}
 
 // Room for `total` values and `bytes` arena bytes: records, arena and a table at load <= 1/2.  Capacity only — K, the codes and the strings
 // are what they were, whether this succeeds or not; the old arrays stay the dictionary's until the new ones are complete.
 int sd_reserve(JobCtx *e, tad_strdict *d, uint64_t total, uint64_t bytes, uint64_t min_slots = 0) {
   hipStream_t s = e->stream;
-  uint64_t ncap = d->rec_cap, nslots = d->slots, narena = d->arena_cap;
-  if (total > d->rec_cap) {
-    ncap = d->rec_cap * 2 > total ? d->rec_cap * 2 : total;
-    if (ncap > kSdMaxValues) ncap = kSdMaxValues;
-  }
-  if (2 * total > d->slots) nslots = pow2_at_least(2 * total);
-  if (min_slots > nslots) nslots = min_slots;
-  if (bytes > d->arena_cap) narena = up16(d->arena_cap * 2 > bytes ? d->arena_cap * 2 : bytes);
-  if (ncap == d->rec_cap && nslots == d->slots && narena == d->arena_cap) return TAD_OK;
-  void *nrecs = nullptr, *ntable = nullptr, *nbytes = nullptr;
+  Candidate<void> nrecs;
+  Candidate<uint8_t> narena;
+  Candidate<unsigned long long> ntable;
   hipError_t r = hipSuccess;
-  if (ncap != d->rec_cap) r = sd_alloc(e, &nrecs, ncap * 16);
-  if (r == hipSuccess && narena != d->arena_cap) r = sd_alloc(e, &nbytes, narena);
-  if (r == hipSuccess && nslots != d->slots) r = sd_alloc(e, &ntable, nslots * 8);
-  if (r == hipSuccess && nrecs && d->K) r = hipMemcpyAsync(nrecs, d->recs, d->K * 16, hipMemcpyDeviceToDevice, s);
-  if (r == hipSuccess && nbytes && d->arena_used) r = hipMemcpyAsync(nbytes, d->arena, d->arena_used, hipMemcpyDeviceToDevice, s);
-  if (r == hipSuccess && ntable) {
-    r = hipMemsetAsync(ntable, 0xFF, nslots * 8, s);
-    if (r == hipSuccess && d->K) launch_sd_rehash(s, d->table, d->slots, d->recs, d->K, static_cast<unsigned long long *>(ntable), nslots);
+  if (total > d->rec_cap) {
+    uint64_t ncap = d->rec_cap * 2 > total ? d->rec_cap * 2 : total;
+    if (ncap > kSdMaxValues) ncap = kSdMaxValues;
+    r = nrecs.alloc(e, ncap, ncap * 16);
   }
+  if (r == hipSuccess && bytes > d->arena_cap) {
+    const uint64_t ncap = up16(d->arena_cap * 2 > bytes ? d->arena_cap * 2 : bytes);
+    r = narena.alloc(e, ncap, ncap);
+  }
+  if (r == hipSuccess && nrecs.p && d->K) r = hipMemcpyAsync(nrecs.p, d->recs, d->K * 16, hipMemcpyDeviceToDevice, s);
+  if (r == hipSuccess && narena.p && d->arena_used) r = hipMemcpyAsync(narena.p, d->arena, d->arena_used, hipMemcpyDeviceToDevice, s);
+  if (r == hipSuccess)
+    r = grow_table(e, d->slots, total, min_slots, &ntable, [&](unsigned long long *t, uint64_t nslots) {
+      if (d->K) launch_sd_rehash(s, d->table, d->slots, d->recs, d->K, t, nslots);
+    });
+  if (r == hipSuccess && !nrecs.p && !narena.p && !ntable.p) return TAD_OK;      // room enough
   if (r == hipSuccess) r = hipStreamSynchronize(s);
   if (r == hipSuccess) r = hipGetLastError();
-  if (r != hipSuccess) {
-    if (nrecs) hipFree(nrecs);
-    if (nbytes) hipFree(nbytes);
-    if (ntable) hipFree(ntable);
+  if (r != hipSuccess)
     return fail(e, r == hipErrorOutOfMemory ? TAD_ERR_OUT_OF_MEMORY : TAD_ERR_HIP, "tad_strdict: no room for %llu values, %llu bytes: %s (dictionary unchanged)",
                 (unsigned long long)total, (unsigned long long)bytes, hipGetErrorString(r));
-  }
-  if (nrecs) { hipFree(d->recs); d->recs = nrecs; d->rec_cap = ncap; }
-  if (nbytes) { hipFree(d->arena); d->arena = static_cast<uint8_t *>(nbytes); d->arena_cap = narena; }
-  if (ntable) { hipFree(d->table); d->table = static_cast<unsigned long long *>(ntable); d->slots = nslots; }
+  nrecs.commit_into(d->recs, d->rec_cap);
+  narena.commit_into(d->arena, d->arena_cap);
+  ntable.commit_into(d->table, d->slots);
   return TAD_OK;
 }
 
@@ -92,15 +74,11 @@ int sd_run(tad_engine *eng, tad_strdict *d, const tad_string_column *col, int64_
   HIP_TRY(e, hipSetDevice(e->device));
   hipStream_t s = e->stream;
   const bool host = col->memory == TAD_MEM_HOST;
-  const int off64 = col->offset_bits == 64;
   // scratch of the probe: in_key = a host batch's offsets | bytes (+ 16 of slack: the last aligned word) | validity, in_key2 = its codes,
   // sp_comp_a = miss flags | miss count, probe flags, new-value count, append flags
-  const size_t off_in = up256((n + 1) * (off64 ? 8 : 4)), data_in = up256(col->data_bytes + 16);
-  const size_t val_in = col->validity ? up256((col->validity_offset + n + 7) / 8) : 0;
-  const size_t stage_in = host ? off_in + data_in + val_in : 0, stage_out = host ? up256(n * 8) : 0, miss_bytes = up256(n);
+  const size_t stage_in = host ? string_stage_bytes(col, 16) : 0, stage_out = host ? up256(n * 8) : 0, miss_bytes = up256(n);
   const size_t need0 = stage_in + stage_out + miss_bytes + 256;
-  if (need0 > e->ws_limit)
-    return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu", who, (unsigned long long)need0, (unsigned long long)e->ws_limit);
+  if (need0 > e->ws_limit) return over_limit(e, who, need0);
   int rc;
   if ((rc = ensure(e, e->sp_comp_a, miss_bytes + 256)) != TAD_OK) return rc;
   if (host && ((rc = ensure(e, e->in_key, stage_in)) != TAD_OK || (rc = ensure(e, e->in_key2, stage_out)) != TAD_OK)) return rc;
@@ -110,17 +88,9 @@ int sd_run(tad_engine *eng, tad_strdict *d, const tad_string_column *col, int64_
   uint32_t *probe_flags_dev = reinterpret_cast<uint32_t *>(tail + 8);
   unsigned long long *nv_dev = reinterpret_cast<unsigned long long *>(tail + 16);
   uint32_t *append_flags_dev = reinterpret_cast<uint32_t *>(tail + 24);
-  SdBatch B{};
-  B.offsets = col->offsets; B.data = col->data; B.valid = col->validity; B.valid_off = col->validity_offset; B.n = n; B.data_bytes = col->data_bytes; B.off64 = off64;
-  long long *d_codes = reinterpret_cast<long long *>(codes);
-  if (host) {
-    unsigned char *p = static_cast<unsigned char *>(e->in_key.p);
-    HIP_TRY(e, hipMemcpyAsync(p, col->offsets, (n + 1) * (off64 ? 8 : 4), hipMemcpyHostToDevice, s)); B.offsets = p; p += off_in;
-    if (col->data_bytes) HIP_TRY(e, hipMemcpyAsync(p, col->data, col->data_bytes, hipMemcpyHostToDevice, s));
-    B.data = p; p += data_in;
-    if (col->validity) { HIP_TRY(e, hipMemcpyAsync(p, col->validity, (col->validity_offset + n + 7) / 8, hipMemcpyHostToDevice, s)); B.valid = p; }
-    d_codes = reinterpret_cast<long long *>(e->in_key2.p);
-  }
+  StrBatch B;
+  if ((rc = stage_string_column(e, col, host ? static_cast<unsigned char *>(e->in_key.p) : nullptr, 16, &B)) != TAD_OK) return rc;
+  long long *d_codes = reinterpret_cast<long long *>(host ? e->in_key2.p : codes);
   // 1. the probe: the dictionary is only read; every row's offsets are validated
   HIP_TRY(e, hipMemsetAsync(tail, 0, 32, s));
   launch_sd_probe(s, B, d->table, d->slots, d->recs, d->arena, d->K, d_codes, insert ? miss : nullptr, n_miss_dev, probe_flags_dev);
@@ -151,12 +121,9 @@ int sd_run(tad_engine *eng, tad_strdict *d, const tad_string_column *col, int64_
   unsigned long long m = 0, units = 0;
   uint64_t *fr = nullptr;
   unsigned long long *off16 = nullptr;
-  for (uint64_t slots = factorize_first_slots(n);;) {
-    const size_t tb = factorize_temp_bytes(n, slots);
-    const size_t need = need0 + tb + fr_bytes + cnt_bytes + offs_bytes + scan_bytes;
-    if (need > e->ws_limit)
-      return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu (dictionary unchanged)", who, (unsigned long long)need,
-                  (unsigned long long)e->ws_limit);
+  rc = with_factorize_ladder(e, n, who, " (dictionary unchanged)", "scratch table", 0, [&](size_t tb) { return need0 + tb + fr_bytes + cnt_bytes + offs_bytes + scan_bytes; },
+                             [&](uint64_t slots, size_t tb, bool *grow) -> int {
+    int rc;
     if ((rc = ensure(e, e->sp_temp, tb)) != TAD_OK || (rc = ensure(e, e->sp_first, fr_bytes)) != TAD_OK || (rc = ensure(e, e->sp_val_a, cnt_bytes + offs_bytes)) != TAD_OK ||
         (rc = ensure(e, e->scan_scratch, scan_bytes)) != TAD_OK)
       return rc;
@@ -164,7 +131,7 @@ int sd_run(tad_engine *eng, tad_strdict *d, const tad_string_column *col, int64_
     uint32_t *cnt = static_cast<uint32_t *>(e->sp_val_a.p);
     off16 = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(e->sp_val_a.p) + cnt_bytes);
     uint32_t *se_flags_dev = nullptr;
-    launch_encode_strings(s, B.offsets, off64, B.data, B.data_bytes, B.valid, B.valid_off, n, slots, e->sp_temp.p, d_codes, fr, M, nv_dev, &se_flags_dev, miss);
+    launch_encode_strings(s, B.off, B.off64, B.data, B.data_bytes, B.valid, B.valid_off, n, slots, e->sp_temp.p, d_codes, fr, M, nv_dev, &se_flags_dev, miss);
     launch_sd_lens(s, B, fr, nv_dev, M, se_flags_dev, cnt);
     launch_scan(s, cnt, off16, M, static_cast<unsigned long long *>(e->scan_scratch.p));
     uint32_t se_flags = 0;
@@ -174,11 +141,10 @@ int sd_run(tad_engine *eng, tad_strdict *d, const tad_string_column *col, int64_
     HIP_TRY(e, hipStreamSynchronize(s));
     HIP_TRY(e, hipGetLastError());
     if (se_flags & 2u) return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: offsets decrease or point beyond data_bytes (dictionary unchanged)", who);
-    if (se_flags == 0) break;
-    const uint64_t next = factorize_next_slots(n, slots);      // more new values than this scratch table takes: once more with the next size
-    if (next == slots) return fail(e, TAD_ERR_HIP, "%s: the full-size scratch table filled up", who);
-    slots = next;
-  }
+    *grow = se_flags != 0;      // more new values than this scratch table takes
+    return TAD_OK;
+  });
+  if (rc != TAD_OK) return rc;
   if (m == 0 || m > M) return fail(e, TAD_ERR_HIP, "%s: %llu new values from %llu miss rows", who, (unsigned long long)m, (unsigned long long)M);
   if (must_be_new != kNoCount && m != must_be_new)
     return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: two strings are equal (%llu distinct of %llu; dictionary unchanged)", who, (unsigned long long)m,
@@ -197,9 +163,7 @@ int sd_run(tad_engine *eng, tad_strdict *d, const tad_string_column *col, int64_
   if (r == hipSuccess && host) r = hipMemcpyAsync(codes, d_codes, n * 8, hipMemcpyDeviceToHost, s);
   uint32_t append_flags = 0;
   if (r == hipSuccess) r = hipMemcpyAsync(&append_flags, append_flags_dev, 4, hipMemcpyDeviceToHost, s);
-  const hipError_t rs = hipStreamSynchronize(s);      // (always: the append is in flight)
-  if (r == hipSuccess) r = rs;
-  if (r == hipSuccess) r = hipGetLastError();
+  r = finish_stream(e, r);      // (always synchronises: the append is in flight)
   if (r != hipSuccess || (append_flags & SD_FLAG_BAD_ROW))
     return fail(e, TAD_ERR_HIP, "%s: appending %llu values failed: %s", who, (unsigned long long)m, hipGetErrorString(r));
   d->K += m;
@@ -234,24 +198,24 @@ int tad_strdict_create(tad_engine *eng, uint64_t expected_values, uint64_t expec
   HIP_TRY(e, hipSetDevice(e->device));
   tad_strdict *d = new (std::nothrow) tad_strdict();
   if (!d) return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory");
-  d->slots = expected_values ? pow2_at_least(2 * expected_values) : kSdDefaultSlots;
-  d->rec_cap = expected_values ? (expected_values > kSdMinValues ? expected_values : kSdMinValues) : kSdDefaultValues;
-  d->arena_cap = expected_bytes ? up16(expected_bytes) : kSdDefaultArena;
-  void *table = nullptr, *arena = nullptr;
-  hipError_t r = sd_alloc(e, &table, d->slots * 8);
-  if (r == hipSuccess) r = sd_alloc(e, &d->recs, d->rec_cap * 16);
-  if (r == hipSuccess) r = sd_alloc(e, &arena, d->arena_cap);
-  if (r == hipSuccess) r = hipMemsetAsync(table, 0xFF, d->slots * 8, e->stream);
+  const uint64_t slots = expected_values ? pow2_at_least(2 * expected_values) : kSdDefaultSlots;
+  const uint64_t rec_cap = expected_values ? (expected_values > kSdMinValues ? expected_values : kSdMinValues) : kSdDefaultValues;
+  const uint64_t arena_cap = expected_bytes ? up16(expected_bytes) : kSdDefaultArena;
+  Candidate<unsigned long long> table;
+  Candidate<void> recs;
+  Candidate<uint8_t> arena;
+  hipError_t r = table.alloc(e, slots, slots * 8);
+  if (r == hipSuccess) r = recs.alloc(e, rec_cap, rec_cap * 16);
+  if (r == hipSuccess) r = arena.alloc(e, arena_cap, arena_cap);
+  if (r == hipSuccess) r = hipMemsetAsync(table.p, 0xFF, slots * 8, e->stream);
   if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
   if (r != hipSuccess) {
-    if (table) hipFree(table);
-    if (d->recs) hipFree(d->recs);
-    if (arena) hipFree(arena);
     delete d;
     return fail(e, TAD_ERR_OUT_OF_MEMORY, "tad_strdict_create: %s", hipGetErrorString(r));
   }
-  d->table = static_cast<unsigned long long *>(table);
-  d->arena = static_cast<uint8_t *>(arena);
+  table.commit_into(d->table, d->slots);
+  recs.commit_into(d->recs, d->rec_cap);
+  arena.commit_into(d->arena, d->arena_cap);
   *out = d;
   return TAD_OK;
 }
@@ -322,9 +286,7 @@ int tad_strdict_export(tad_engine *eng, const tad_strdict *d, uint64_t first_cod
   // scratch: sp_val_a = lengths | offsets, sp_temp = the packed bytes
   const size_t cnt_bytes = up256((size_t)n_values * 4), offs_bytes = up256(((size_t)n_values + 1) * 8);
   const size_t scan_bytes = scan_scratch_elems(n_values) * sizeof(unsigned long long);
-  if (cnt_bytes + offs_bytes + scan_bytes > e->ws_limit)
-    return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu", who, (unsigned long long)(cnt_bytes + offs_bytes + scan_bytes),
-                (unsigned long long)e->ws_limit);
+  if (cnt_bytes + offs_bytes + scan_bytes > e->ws_limit) return over_limit(e, who, cnt_bytes + offs_bytes + scan_bytes);
   int rc;
   if ((rc = ensure(e, e->sp_val_a, cnt_bytes + offs_bytes)) != TAD_OK || (rc = ensure(e, e->scan_scratch, scan_bytes)) != TAD_OK) return rc;
   uint32_t *cnt = static_cast<uint32_t *>(e->sp_val_a.p);
@@ -340,9 +302,7 @@ int tad_strdict_export(tad_engine *eng, const tad_strdict *d, uint64_t first_cod
   if (total > data_cap)
     return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: the values hold %llu bytes, data has room for %llu", who, (unsigned long long)total, (unsigned long long)data_cap);
   const size_t out_bytes = up256((size_t)total + 8);
-  if (cnt_bytes + offs_bytes + scan_bytes + out_bytes > e->ws_limit)
-    return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu", who,
-                (unsigned long long)(cnt_bytes + offs_bytes + scan_bytes + out_bytes), (unsigned long long)e->ws_limit);
+  if (cnt_bytes + offs_bytes + scan_bytes + out_bytes > e->ws_limit) return over_limit(e, who, cnt_bytes + offs_bytes + scan_bytes + out_bytes);
   if ((rc = ensure(e, e->sp_temp, out_bytes)) != TAD_OK) return rc;
   uint8_t *packed = static_cast<uint8_t *>(e->sp_temp.p);
   launch_sd_export(s, d->recs, d->arena, first_code, n_values, off, packed);
@@ -395,8 +355,7 @@ int tad_strdict_match(tad_engine *eng, const tad_strdict *d, int32_t op, const u
   const bool host = memory == TAD_MEM_HOST;
   // scratch: sp_comp_a = the match count | the pattern; a host mask in in_key2
   const size_t need = 256 + up256(kSdMaxPattern) + (host ? up256(K) : 0);
-  if (need > e->ws_limit)
-    return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu", who, (unsigned long long)need, (unsigned long long)e->ws_limit);
+  if (need > e->ws_limit) return over_limit(e, who, need);
   int rc;
   if ((rc = ensure(e, e->sp_comp_a, 256 + up256(kSdMaxPattern))) != TAD_OK || (host && (rc = ensure(e, e->in_key2, up256(K))) != TAD_OK)) return rc;
   unsigned long long *n_hit_dev = static_cast<unsigned long long *>(e->sp_comp_a.p);

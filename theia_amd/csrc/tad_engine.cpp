@@ -79,6 +79,21 @@ void trim_idle(tad_engine *eng, JobCtx *self) {
   eng->cv.notify_all();
 }
 
+hipError_t dev_alloc(JobCtx *e, void **p, size_t bytes) {
+  hipError_t r = hipMalloc(p, bytes);
+  if (r != hipSuccess) {
+    (void)hipGetLastError();
+    trim_idle(e->eng, e);
+    r = hipMalloc(p, bytes);
+  }
+  if (r != hipSuccess) { *p = nullptr; (void)hipGetLastError(); }
+  return r;
+}
+
+int over_limit(JobCtx *e, const char *who, size_t need, const char *suffix) {
+  return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu%s", who, (unsigned long long)need, (unsigned long long)e->ws_limit, suffix);
+}
+
 int ensure(JobCtx *e, DevBuf &b, size_t bytes) {
   if (bytes <= b.cap) return TAD_OK;
   if (b.p) {
@@ -88,20 +103,11 @@ int ensure(JobCtx *e, DevBuf &b, size_t bytes) {
   }
   size_t want = bytes + bytes / 8 + 256;
   hipError_t r = hipMalloc(&b.p, want);
-  if (r != hipSuccess) {
+  if (r != hipSuccess) {      // without the head room
     want = bytes;
-    r = hipMalloc(&b.p, want);
+    r = dev_alloc(e, &b.p, want);
   }
-  if (r != hipSuccess) {
-    (void)hipGetLastError();
-    trim_idle(e->eng, e);
-    r = hipMalloc(&b.p, want);
-  }
-  if (r != hipSuccess) {
-    b.p = nullptr;
-    (void)hipGetLastError();
-    return fail(e, TAD_ERR_OUT_OF_MEMORY, "hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(r));
-  }
+  if (r != hipSuccess) return fail(e, TAD_ERR_OUT_OF_MEMORY, "hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(r));
   b.cap = want;
   return TAD_OK;
 }
@@ -238,13 +244,8 @@ int alloc_device_block(JobCtx *e, size_t bytes, ResultBlock *rb) {
     }
   }
   void *p = nullptr;
-  hipError_t r = hipMalloc(&p, bytes);
-  if (r != hipSuccess) {
-    (void)hipGetLastError();
-    trim_idle(e->eng, e);
-    r = hipMalloc(&p, bytes);
-  }
-  if (r != hipSuccess) { (void)hipGetLastError(); return fail(e, TAD_ERR_OUT_OF_MEMORY, "hipMalloc(result, %zu) failed: %s", bytes, hipGetErrorString(r)); }
+  const hipError_t r = dev_alloc(e, &p, bytes);
+  if (r != hipSuccess) return fail(e, TAD_ERR_OUT_OF_MEMORY, "hipMalloc(result, %zu) failed: %s", bytes, hipGetErrorString(r));
   rb->base = p;
   rb->cap = bytes;
   return TAD_OK;

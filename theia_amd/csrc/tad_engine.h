@@ -1,7 +1,7 @@
 // tad_engine.h — PRIVATE header of libtad_mi355x.so's host side: the engine, its pool of job contexts, and what the translation
 // units of the C ABI share (tad_engine.cpp: life cycle, pool, memory; tad_capi_job.cpp: the batch job; tad_capi.cpp: what the entry points share and the batches
 // on a state; tad_capi_view.cpp: the read-only jobs on a state; tad_capi_state.cpp: the life of a streaming state; tad_capi_ingest.cpp: the ingest entry points; tad_capi_series.cpp: the per-series
-// entry points; tad_capi_keydict.cpp: the key dictionary).  HIP only: there is no CPU fallback in this library (the CPU oracle under
+// entry points; tad_capi_keydict.cpp: the key dictionary; tad_capi_strdict.cpp: the string dictionary; tad_capi_dict.h: what the ingest encoders share).  HIP only: there is no CPU fallback in this library (the CPU oracle under
 // oracle/ is test infrastructure and is never linked or called from here).
 //
 // Threading (controller.go:199-201 runs four workers, Spark ran one pod per job): an engine owns a small POOL of job
@@ -237,6 +237,10 @@ template <typename F> void for_each_buf(JobCtx *c, F f) {
 void drop_buffers(JobCtx *c);
 void trim_idle(tad_engine *eng, JobCtx *self);
 int ensure(JobCtx *e, DevBuf &b, size_t bytes);          // grow-only device scratch
+// hipMalloc that gives the idle contexts' buffers and the recycled result blocks back to the device (trim_idle) before it fails; *p = NULL then
+hipError_t dev_alloc(JobCtx *e, void **p, size_t bytes);
+// the refusal of a call whose scratch would pass the workspace limit: "<who> needs <need> bytes of scratch > workspace limit <limit><suffix>"
+int over_limit(JobCtx *e, const char *who, size_t need, const char *suffix = "");
 void preload_code_objects();
 JobCtx *ctx_create(tad_engine *eng, bool first);
 void ctx_destroy(JobCtx *c);

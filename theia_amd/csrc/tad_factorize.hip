@@ -6,8 +6,8 @@
 // flowStartSeconds: up to eight 8-byte integers per row — into ids.  pandas does that at 3e6-1.5e7 rows/s on one core in front of an
 // engine that aggregates 7e10 rows/s.  Here: an open-addressing hash table in HBM, one 8-byte word per slot
 //     word = fingerprint (32 bits of the tuple's hash) << 32 | virtual row of a row that holds the tuple     (all ones = empty)
-// A row claims an empty slot with ONE compare-and-swap (fingerprint and representative row appear together: no reader ever sees a
-// half-written slot, nobody spins); a row that finds its fingerprint compares its tuple with the representative row's tuple in the
+// (the slot of tad_slots.h, which has the protocol: a look with a plain cached load, a claim with ONE compare-and-swap).  A row claims an
+// empty slot; a row that finds its fingerprint compares its tuple with the representative row's tuple in the
 // input columns (exact: a fingerprint match alone is not equality) and, if it comes EARLIER in the table, lowers the slot's row
 // with an atomic min — the fingerprint sits in the high half, so the minimum is taken among rows of this very tuple.  After the
 // pass every slot names the first row of its tuple.  Ids in order of first appearance (what pandas.factorize gives, so that the
@@ -17,56 +17,20 @@
 // Pod mode (the UNION ALL of the inbound and the outbound view, :556-565) passes two tuples per row: the table runs over the
 // virtual rows [side a: 0 .. n) ++ [side b: n .. 2n), the side is part of the tuple.
 #include "tad_internal.h"
-#include "tad_strbytes.h"      // fz_mix, StrArgs, se_span, se_load, se_load_lds, se_hash, se_same_as, kSeStage
+#include "tad_strbytes.h"      // se_span, se_load, se_load_lds, se_hash, se_same_as, kSeStage; through it tad_slots.h: the slot table, fz_mix, tb_*
 
 namespace tad {
 
 static constexpr int kFzBlock = 256;
-static constexpr unsigned long long kFzEmpty = ~0ull;
 
-// A probe LOOKS at a slot with a plain cached load.  On this multi-XCD chip an agent-scope load is a transaction with the memory side for every
-// row (the L2s of the eight XCDs are not coherent with each other, so device-scope accesses bypass them): 1e8 of them were the insert pass
-// (3 of its 4 ms for one key column, profiles/r4_v29_*).  A stale view is harmless here: a slot's fingerprint never changes once claimed, so a
-// non-empty word is trusted for WHICH slot it is (its row half may be stale-high: the atomic min below is then merely redundant), and a word
-// that looks empty is only ever claimed with a compare-and-swap, which is performed at the memory side and returns the truth.
-__device__ __forceinline__ unsigned long long fz_peek(const unsigned long long *slot) {
-  return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-struct FzArgs {
-  const long long *a[kFzMaxCols];
-  const long long *b[kFzMaxCols];   // all NULL: one tuple per row
-  const uint8_t *keep_a, *keep_b;   // NULL = every row
-  uint64_t n;
-  int n_cols;
-  uint32_t sides;                   // 1 or 2
-};
-
-__device__ __forceinline__ bool fz_kept(const FzArgs &A, uint64_t v) {
-  const bool sb = v >= A.n;
-  const uint8_t *keep = sb ? A.keep_b : A.keep_a;
-  return keep == nullptr || keep[sb ? v - A.n : v] != 0;
-}
-__device__ __forceinline__ long long fz_value(const FzArgs &A, uint64_t v, int c) {
-  const bool sb = v >= A.n;
-  return (sb ? A.b[c] : A.a[c])[sb ? v - A.n : v];
-}
-__device__ __forceinline__ uint64_t fz_hash(const FzArgs &A, uint64_t v, long long (&t)[kFzMaxCols]) {
-  uint64_t h = v >= A.n ? 0x9E3779B97F4A7C15ull : 0ull;   // the side is part of the tuple
-  for (int c = 0; c < A.n_cols; ++c) {
-    t[c] = fz_value(A, v, c);
-    h = fz_mix(h ^ (uint64_t)t[c]) + 0x632BE59BD9B4E019ull * (uint64_t)(c + 1);
-  }
-  return fz_mix(h);
-}
-__device__ __forceinline__ bool fz_same(const FzArgs &A, uint64_t v, const long long (&t)[kFzMaxCols], uint64_t rep) {
+__device__ __forceinline__ bool fz_same(const TupleBatch &A, uint64_t v, const long long (&t)[kFzMaxCols], uint64_t rep) {
   if ((v >= A.n) != (rep >= A.n)) return false;
   // every column of the representative row is loaded before any is compared: with an early exit per column the compare was one memory round
   // trip per key column (rows that match — all but the first of a key — never take the exit anyway)
   bool same = true;
 #pragma unroll
   for (int c = 0; c < kFzMaxCols; ++c)
-    if (c < A.n_cols) same = same & (fz_value(A, rep, c) == t[c]);
+    if (c < A.n_cols) same = same & (tb_value(A, rep, c) == t[c]);
   return same;
 }
 
@@ -81,7 +45,7 @@ enum : uint32_t { FZ_FLAG_GROW = 1u, FZ_FLAG_BAD_INPUT = 2u };
 // every kept virtual row into the table; on return a slot's low half = the smallest virtual row holding its tuple, slot_of[v] = v's slot
 // max_probe: kFzMaxProbe on the small tables; unlimited on the full-size one (2 n slots: it cannot fill up, and with tens of millions of distinct
 // keys a linear-probing cluster longer than 32 DOES occur — 5e7 keys at load 0.37: ~400 expected — which round 6's 5e7-connection ingest met)
-__global__ __launch_bounds__(kFzBlock) void k_fz_insert(FzArgs A, unsigned long long *__restrict__ table, uint64_t mask, uint32_t *__restrict__ slot_of,
+__global__ __launch_bounds__(kFzBlock) void k_fz_insert(TupleBatch A, unsigned long long *__restrict__ table, uint64_t mask, uint32_t *__restrict__ slot_of,
                                                         uint32_t *__restrict__ flags, unsigned long long *__restrict__ claims, uint32_t max_probe) {
   const uint64_t V = A.n * A.sides;
   uint32_t claimed = 0;
@@ -89,16 +53,21 @@ __global__ __launch_bounds__(kFzBlock) void k_fz_insert(FzArgs A, unsigned long 
   for (uint64_t v = (uint64_t)blockIdx.x * kFzBlock + threadIdx.x; v < V; v += (uint64_t)gridDim.x * kFzBlock, ++round) {
     // the table is too small: the pass is being abandoned (asked at the memory side, so only every eighth row of a thread)
     if ((round & 7u) == 0u && __hip_atomic_load(flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
-    if (!fz_kept(A, v)) continue;
+    if (!tb_kept(A, v)) continue;
     long long t[kFzMaxCols];
-    const uint64_t h = fz_hash(A, v, t);
-    const unsigned long long mine = ((h >> 32) << 32) | v;     // (v < 2^32 - 1: never the empty word)
+    uint64_t h = v >= A.n ? kTupleSideB : 0ull;
+    for (int c = 0; c < A.n_cols; ++c) {
+      t[c] = tb_value(A, v, c);
+      h = tb_hash_col(h, t[c], c);
+    }
+    h = fz_mix(h);
+    const unsigned long long mine = slot_word(h, v);           // (v < 2^32 - 1: never the empty word)
     uint32_t probes = 0;
     for (uint64_t s = h & mask;; s = (s + 1) & mask) {
-      unsigned long long w = fz_peek(table + s);
-      if (w == kFzEmpty) {
-        w = atomicCAS(table + s, kFzEmpty, mine);
-        if (w == kFzEmpty) { ++claimed; slot_of[v] = (uint32_t)s; break; }      // claimed
+      unsigned long long w = slot_peek(table + s);
+      if (w == kSlotEmpty) {
+        w = atomicCAS(table + s, kSlotEmpty, mine);
+        if (w == kSlotEmpty) { ++claimed; slot_of[v] = (uint32_t)s; break; }      // claimed
       }
       if ((w >> 32) == (mine >> 32) && fz_same(A, v, t, w & 0xffffffffull)) {
         if (mine < w) atomicMin(table + s, mine);                // an earlier row of the same tuple (same high half: the min stays in the class)
@@ -119,7 +88,7 @@ __global__ __launch_bounds__(kFzBlock) void k_fz_insert(FzArgs A, unsigned long 
 __global__ __launch_bounds__(kFzBlock) void k_fz_mark(const unsigned long long *__restrict__ table, uint64_t slots, uint32_t *__restrict__ bits) {
   for (uint64_t s = (uint64_t)blockIdx.x * kFzBlock + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * kFzBlock) {
     const unsigned long long w = table[s];
-    if (w != kFzEmpty) atomicOr(bits + ((w & 0xffffffffull) >> 5), 1u << (w & 31ull));
+    if (w != kSlotEmpty) atomicOr(bits + ((w & 0xffffffffull) >> 5), 1u << (w & 31ull));
   }
 }
 
@@ -136,7 +105,7 @@ __global__ __launch_bounds__(kFzBlock) void k_fz_ids(unsigned long long *__restr
   if (*flags != 0u) return;     // the insert pass gave up: the host repeats with a larger table
   for (uint64_t s = (uint64_t)blockIdx.x * kFzBlock + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * kFzBlock) {
     const unsigned long long w = table[s];
-    if (w == kFzEmpty) continue;
+    if (w == kSlotEmpty) continue;
     const uint64_t rep = w & 0xffffffffull;
     const uint64_t id = off[rep >> 5] + (uint64_t)__popc(bits[rep >> 5] & ((1u << (rep & 31ull)) - 1u));
     table[s] = id;
@@ -145,7 +114,7 @@ __global__ __launch_bounds__(kFzBlock) void k_fz_ids(unsigned long long *__restr
 }
 
 // id of every row (TAD_KEY_SKIP for rows that are not kept): slot -> id
-__global__ __launch_bounds__(kFzBlock) void k_fz_lookup(FzArgs A, const unsigned long long *__restrict__ table, const uint32_t *__restrict__ slot_of,
+__global__ __launch_bounds__(kFzBlock) void k_fz_lookup(TupleBatch A, const unsigned long long *__restrict__ table, const uint32_t *__restrict__ slot_of,
                                                          uint64_t *__restrict__ key_a, uint64_t *__restrict__ key_b, const uint32_t *__restrict__ flags) {
   if (*flags != 0u) return;     // the insert pass gave up: slot_of is incomplete, the host repeats with a larger table
   constexpr int U = 4;          // four rows per thread in flight (slot, then the table word)
@@ -157,7 +126,7 @@ __global__ __launch_bounds__(kFzBlock) void k_fz_lookup(FzArgs A, const unsigned
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint64_t v = v0 + u * stride;
-      kept[u] = v < V && fz_kept(A, v);
+      kept[u] = v < V && tb_kept(A, v);
       sl[u] = kept[u] ? slot_of[v] : 0u;
     }
 #pragma unroll
@@ -177,7 +146,7 @@ __global__ __launch_bounds__(kFzBlock) void k_fz_lookup(FzArgs A, const unsigned
 // (part_plan_bins) — and counts bin = id >> shift in LDS; shift and nbins follow from the key count, which only exists on the device at this
 // point (the same rule as part_plan_bins: the smallest shift with at most kMaxBins bins).
 static constexpr int kFzHistThreads = 1024;
-__global__ __launch_bounds__(kFzHistThreads) void k_fz_lookup_hist(FzArgs A, const unsigned long long *__restrict__ table, const uint32_t *__restrict__ slot_of,
+__global__ __launch_bounds__(kFzHistThreads) void k_fz_lookup_hist(TupleBatch A, const unsigned long long *__restrict__ table, const uint32_t *__restrict__ slot_of,
                                                                   uint64_t *__restrict__ key_a, uint64_t *__restrict__ key_b, const uint32_t *__restrict__ flags,
                                                                   const unsigned long long *__restrict__ num_keys, uint64_t chunk, uint32_t *__restrict__ bins) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_fz_hist[];
@@ -200,7 +169,7 @@ __global__ __launch_bounds__(kFzHistThreads) void k_fz_lookup_hist(FzArgs A, con
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const uint64_t i = i0 + (uint64_t)u * kFzHistThreads;
-        kept[u] = i < hi && fz_kept(A, i + side * A.n);
+        kept[u] = i < hi && tb_kept(A, i + side * A.n);
         sl[u] = kept[u] ? slot_of[i + side * A.n] : 0u;
       }
 #pragma unroll
@@ -267,7 +236,7 @@ static dim3 fz_grid(uint64_t items) { const uint64_t b = (items + kFzBlock - 1) 
 void launch_factorize(hipStream_t s, const long long *const *cols_a, const uint8_t *keep_a, const long long *const *cols_b, const uint8_t *keep_b, uint64_t n,
                       int n_cols, uint64_t slots, void *temp, uint64_t *key_a, uint64_t *key_b, uint64_t *first_row, uint64_t first_row_cap,
                       unsigned long long *num_keys_dev, uint32_t **flags_dev_out, uint32_t *hist_bins, int hist_workgroups, uint64_t hist_chunk) {
-  FzArgs A{};
+  TupleBatch A{};
   for (int c = 0; c < n_cols; ++c) { A.a[c] = cols_a[c]; A.b[c] = cols_b != nullptr ? cols_b[c] : nullptr; }
   A.keep_a = keep_a; A.keep_b = keep_b; A.n = n; A.n_cols = n_cols; A.sides = cols_b != nullptr ? 2u : 1u;
   const uint64_t V = n * A.sides, words = (V + 31) / 32;
@@ -318,7 +287,7 @@ enum : uint32_t { SE_FLAG_GROW = FZ_FLAG_GROW, SE_FLAG_BAD_OFFSETS = FZ_FLAG_BAD
 // every row into the table; slot_of[v] = the slot of v's string.  flags: SE_FLAG_GROW / SE_FLAG_BAD_OFFSETS; claims: slots claimed
 // keep (tad_strdict: the miss flags of its probe; NULL = every row): a row whose byte is 0 is staged and validated with its block but neither
 // hashed nor inserted, and its slot_of entry is not written
-__global__ __launch_bounds__(kFzBlock) void k_se_insert(StrArgs A, unsigned long long *__restrict__ table, uint64_t mask, uint32_t *__restrict__ slot_of,
+__global__ __launch_bounds__(kFzBlock) void k_se_insert(StrBatch A, unsigned long long *__restrict__ table, uint64_t mask, uint32_t *__restrict__ slot_of,
                                                         uint32_t *__restrict__ flags, unsigned long long *__restrict__ claims, uint32_t max_probe,
                                                         const uint8_t *__restrict__ keep) {
   __shared__ __attribute__((aligned(16))) uint64_t s_bytes[kSeStage / 8 + 4];
@@ -368,17 +337,17 @@ __global__ __launch_bounds__(kFzBlock) void k_se_insert(StrArgs A, unsigned long
       } else {
         h = se_hash(p, len);
       }
-      const unsigned long long mine = ((h >> 32) << 32) | v;
+      const unsigned long long mine = slot_word(h, v);
       uint32_t probes = 0;
 #if defined(TAD_SE_PROF_NOTABLE)      // measurement builds (tools/build_variants.py): stage + hash only
       slot_of[v] = (uint32_t)(h & mask);
       continue;
 #endif
       for (uint64_t s = h & mask;; s = (s + 1) & mask) {
-        unsigned long long w = fz_peek(table + s);
-        if (w == kFzEmpty) {
-          w = atomicCAS(table + s, kFzEmpty, mine);
-          if (w == kFzEmpty) { ++claimed; slot_of[v] = (uint32_t)s; break; }
+        unsigned long long w = slot_peek(table + s);
+        if (w == kSlotEmpty) {
+          w = atomicCAS(table + s, kSlotEmpty, mine);
+          if (w == kSlotEmpty) { ++claimed; slot_of[v] = (uint32_t)s; break; }
         }
         if ((w >> 32) == (mine >> 32)) {
           uint64_t rb; uint32_t rlen;
@@ -441,7 +410,7 @@ __global__ __launch_bounds__(kFzBlock) void k_se_codes(uint64_t n, const unsigne
 void launch_encode_strings(hipStream_t s, const void *offsets, int off64, const uint8_t *data, uint64_t data_bytes, const uint8_t *valid, uint64_t valid_off,
                            uint64_t n, uint64_t slots, void *temp, long long *codes, uint64_t *first_row, uint64_t first_row_cap,
                            unsigned long long *num_values_dev, uint32_t **flags_dev_out, const uint8_t *keep) {
-  StrArgs A{};
+  StrBatch A{};
   A.off = offsets; A.data = data; A.valid = valid; A.valid_off = valid_off; A.n = n; A.data_bytes = data_bytes; A.off64 = off64;
   const uint64_t words = (n + 31) / 32;
   const FzTemp t = fz_temp(temp, n, slots);

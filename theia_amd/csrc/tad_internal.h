@@ -698,7 +698,7 @@ void launch_encode_strings(hipStream_t s, const void *offsets, int off64, const 
                            unsigned long long *num_values_dev, uint32_t **flags_dev_out, const uint8_t *keep = nullptr);
 
 // ---- ingest: a key dictionary that outlives the call — tuples -> ids that stay the same from batch to batch (tad_keydict.hip) ----
-struct KdBatch {                    // the key tuples of one batch (device pointers)
+struct TupleBatch {                 // the key tuples of one batch (device pointers): what tad_factorize's and the dictionary's kernels read
   const long long *a[kFzMaxCols];
   const long long *b[kFzMaxCols];   // all NULL: one tuple per row
   const uint8_t *keep_a, *keep_b;   // NULL = every row
@@ -711,10 +711,10 @@ enum : uint32_t { KD_FLAG_CLUSTER = 1u, KD_FLAG_DUPLICATE = 2u, KD_FLAG_BAD_ROW 
 int kd_stride(int n_cols);          // 8-byte words of one key record: side + columns, padded to an even count
 // every kept virtual row looks its tuple up in table[slots] / keys (K records).  miss != NULL: hits write their id, misses raise miss[v] and
 // are counted in *n_miss (zeroed by the caller), rows that are not kept get TAD_KEY_SKIP; miss == NULL: a miss is TAD_KEY_SKIP too
-void launch_kd_probe(hipStream_t s, const KdBatch &A, const unsigned long long *table, uint64_t slots, const unsigned long long *keys, uint64_t K, uint64_t *key_a,
+void launch_kd_probe(hipStream_t s, const TupleBatch &A, const unsigned long long *table, uint64_t slots, const unsigned long long *keys, uint64_t K, uint64_t *key_a,
                      uint64_t *key_b, uint8_t *miss, unsigned long long *n_miss);
 // new key j (< m) = the tuple at virtual row first_row[j]: record K0 + j and a slot (the table must have room: load <= 1/2 afterwards)
-void launch_kd_append(hipStream_t s, const KdBatch &A, const uint64_t *first_row, uint64_t m, uint64_t K0, unsigned long long *table, uint64_t slots,
+void launch_kd_append(hipStream_t s, const TupleBatch &A, const uint64_t *first_row, uint64_t m, uint64_t K0, unsigned long long *table, uint64_t slots,
                       unsigned long long *keys, uint32_t *flags);
 // key = K0 + batch-local id on the rows whose miss flag is raised
 void launch_kd_fix(hipStream_t s, const uint8_t *miss, const uint64_t *loc_a, const uint64_t *loc_b, uint64_t n, uint32_t sides, uint64_t K0, uint64_t *key_a,
@@ -736,12 +736,14 @@ void launch_kd_select(hipStream_t s, const unsigned long long *keys, int n_cols,
                       uint32_t *flags);
 
 // ---- ingest: a string dictionary that outlives the call — strings -> codes that stay the same from batch to batch (tad_strdict.hip) ----
-struct SdBatch {                    // one Arrow string column (device pointers): tad_string_column
-  const void *offsets;              // n + 1
+struct StrBatch {                   // one Arrow string column (device pointers): what tad_encode_strings' and the dictionary's kernels read
+  const void *off;                  // n + 1 offsets into data
   const uint8_t *data;
-  const uint8_t *valid;             // NULL = no nulls
-  uint64_t valid_off, n, data_bytes;
-  int off64;
+  const uint8_t *valid;             // Arrow validity bitmap (bit valid_off + i), NULL = no nulls
+  uint64_t valid_off;
+  uint64_t n;
+  uint64_t data_bytes;
+  int off64;                        // offsets are int64 (large_string) instead of int32
 };
 static constexpr uint32_t kSdMaxProbe = 32;       // a claim that probed further asks the host for a larger table
 static constexpr uint32_t kSdMaxPattern = 1024;   // tad_strdict_match: bytes of the longest pattern
@@ -749,12 +751,12 @@ enum : uint32_t { SD_FLAG_CLUSTER = 1u, SD_FLAG_BAD_OFFSETS = 2u, SD_FLAG_BAD_RO
 // recs: one 16-byte record per code (arena offset | hash's low half << 32 | length); arena: the strings, each 16-byte aligned and zero-padded.
 // every row looks its string up in table[slots] / recs (K records) / arena.  miss != NULL: hits write their code, misses raise miss[v] and
 // are counted in *n_miss; miss == NULL: a miss is TAD_CODE_NONE.  *flags |= SD_FLAG_BAD_OFFSETS for unusable offsets (both zeroed by the caller)
-void launch_sd_probe(hipStream_t s, const SdBatch &B, const unsigned long long *table, uint64_t slots, const void *recs, const uint8_t *arena, uint64_t K,
+void launch_sd_probe(hipStream_t s, const StrBatch &B, const unsigned long long *table, uint64_t slots, const void *recs, const uint8_t *arena, uint64_t K,
                      long long *codes, uint8_t *miss, unsigned long long *n_miss, uint32_t *flags);
 // cnt[j] (j < M) = the 16-byte units of the string at row first_row[j] for j < *num_new, else 0; all 0 when *se_flags != 0
-void launch_sd_lens(hipStream_t s, const SdBatch &B, const uint64_t *first_row, const unsigned long long *num_new, uint64_t M, const uint32_t *se_flags, uint32_t *cnt);
+void launch_sd_lens(hipStream_t s, const StrBatch &B, const uint64_t *first_row, const unsigned long long *num_new, uint64_t M, const uint32_t *se_flags, uint32_t *cnt);
 // new value j (< m) = the string at row first_row[j]: its bytes at arena_used + 16 off16[j], record K0 + j and a slot (load <= 1/2 afterwards)
-void launch_sd_append(hipStream_t s, const SdBatch &B, const uint64_t *first_row, const unsigned long long *off16, uint64_t m, uint64_t K0, uint64_t arena_used,
+void launch_sd_append(hipStream_t s, const StrBatch &B, const uint64_t *first_row, const unsigned long long *off16, uint64_t m, uint64_t K0, uint64_t arena_used,
                       unsigned long long *table, uint64_t slots, void *recs, uint8_t *arena, uint32_t *flags);
 // codes[v] += K0 on the rows whose miss flag is raised
 void launch_sd_fix(hipStream_t s, const uint8_t *miss, uint64_t n, uint64_t K0, long long *codes);

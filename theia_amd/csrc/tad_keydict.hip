@@ -4,10 +4,9 @@
 // representative row in that call's input columns.  The streaming states (tad_run_stream, tad_state_merge, tad_run_state ...) want key k to be
 // the same flow key in every batch for as long as the state lives, so a streaming host kept its own tuple -> id map (a Go map, pandas:
 // 1e6-1.5e7 rows/s) in front of an engine that aggregates 7e10 rows/s.  Here the map lives in HBM:
-//   table   open addressing, linear probing, one 8-byte word per slot — word = fingerprint (high 32 bits of the tuple's hash) << 32 | key id,
-//           all ones = empty — exactly tad_factorize's slot, with the id where that one keeps a row.  A slot is claimed with ONE
-//           compare-and-swap and its word never changes afterwards, so probes LOOK with plain cached loads (a stale view can only show
-//           "empty" where a slot has just been claimed, and an empty slot is only ever taken with the compare-and-swap, which returns the truth);
+//   table   the slot table of tad_slots.h (which has the protocol: a look with a plain cached load, a claim with ONE compare-and-swap —
+//           slot_claim's atomicCAS) — word = fingerprint (high 32 bits of the tuple's hash) << 32 | key id, all ones = empty: exactly
+//           tad_factorize's slot, with the id where that one keeps a row, and a word that never changes once claimed;
 //   keys    the tuples themselves, because the rows of earlier batches are gone: one RECORD per key id, kd_stride(n_cols) 8-byte words —
 //           word 0 the side (0 = a, 1 = b), words 1 .. n_cols the columns, padded to an even count so that a record starts on a 16-byte
 //           boundary and is read with 16-byte loads.  A record is at most 80 bytes: a compare touches one 128-byte line, two when the
@@ -23,41 +22,13 @@
 // The table never passes load 1/2 (the host grows it BEFORE step 3: k_kd_rehash fills a table of twice the size from the records, and
 // the new one is swapped in when that succeeded), so every probe sequence ends at an empty slot and step 3 cannot fail.
 #include "tad_internal.h"
+#include "tad_slots.h"
 
 namespace tad {
 
 static constexpr int kKdBlock = 256;
-static constexpr unsigned long long kKdEmpty = ~0ull;
 static constexpr int kKdMaxPairs = (kFzMaxCols + 2) / 2;     // 16-byte words of the longest record
 
-__device__ __forceinline__ uint64_t kd_mix(uint64_t x) {   // splitmix64 finaliser
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-// a plain cached load (see the top of the file and tad_factorize.hip: an agent-scope load would be a memory-side transaction per row)
-__device__ __forceinline__ unsigned long long kd_peek(const unsigned long long *slot) {
-  return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-__device__ __forceinline__ bool kd_kept(const KdBatch &A, uint64_t v) {
-  const bool sb = v >= A.n;
-  const uint8_t *keep = sb ? A.keep_b : A.keep_a;
-  return keep == nullptr || keep[sb ? v - A.n : v] != 0;
-}
-__device__ __forceinline__ long long kd_value(const KdBatch &A, uint64_t v, int c) {
-  const bool sb = v >= A.n;
-  return (sb ? A.b[c] : A.a[c])[sb ? v - A.n : v];
-}
-// the side is part of the tuple
-__device__ __forceinline__ uint64_t kd_hash(uint64_t side, const long long (&t)[kFzMaxCols], int n_cols) {
-  uint64_t h = side ? 0x9E3779B97F4A7C15ull : 0ull;
-#pragma unroll
-  for (int c = 0; c < kFzMaxCols; ++c)
-    if (c < n_cols) h = kd_mix(h ^ (uint64_t)t[c]) + 0x632BE59BD9B4E019ull * (uint64_t)(c + 1);
-  return kd_mix(h);
-}
 // every 16-byte word of the record is loaded before any is compared (one memory round trip, not one per column)
 __device__ __forceinline__ void kd_load_record(const unsigned long long *keys, uint64_t id, int pairs, ulonglong2 (&w)[kKdMaxPairs]) {
   const ulonglong2 *r = reinterpret_cast<const ulonglong2 *>(keys + id * (uint64_t)(2 * pairs));
@@ -79,7 +50,7 @@ __device__ __forceinline__ bool kd_same(const unsigned long long *keys, uint64_t
 // row is left to step 4.  !kInsert (tad_keydict_lookup): a miss is TAD_KEY_SKIP.  A word whose id is >= K is never a match (no such word
 // exists in a dictionary that every call left normally).
 template <bool kInsert>
-__global__ __launch_bounds__(kKdBlock) void k_kd_probe(KdBatch A, const unsigned long long *__restrict__ table, uint64_t mask, const unsigned long long *__restrict__ keys,
+__global__ __launch_bounds__(kKdBlock) void k_kd_probe(TupleBatch A, const unsigned long long *__restrict__ table, uint64_t mask, const unsigned long long *__restrict__ keys,
                                                        int pairs, uint64_t K, uint64_t *__restrict__ key_a, uint64_t *__restrict__ key_b, uint8_t *__restrict__ miss,
                                                        unsigned long long *__restrict__ n_miss) {
   const uint64_t V = A.n * A.sides;
@@ -87,18 +58,12 @@ __global__ __launch_bounds__(kKdBlock) void k_kd_probe(KdBatch A, const unsigned
   for (uint64_t v = (uint64_t)blockIdx.x * kKdBlock + threadIdx.x; v < V; v += (uint64_t)gridDim.x * kKdBlock) {
     uint64_t id = TAD_KEY_SKIP;
     bool m = false;
-    if (kd_kept(A, v)) {
+    if (tb_kept(A, v)) {
       const uint64_t side = v >= A.n ? 1ull : 0ull;
       long long t[kFzMaxCols];
 #pragma unroll
-      for (int c = 0; c < kFzMaxCols; ++c) t[c] = c < A.n_cols ? kd_value(A, v, c) : 0ll;
-      const uint64_t h = kd_hash(side, t, A.n_cols);
-      for (uint64_t s = h & mask;; s = (s + 1) & mask) {
-        const unsigned long long w = kd_peek(table + s);
-        if (w == kKdEmpty) { m = true; break; }                 // (load <= 1/2: every probe sequence reaches an empty slot)
-        const uint64_t cand = w & 0xffffffffull;
-        if ((w >> 32) == (h >> 32) && cand < K && kd_same(keys, cand, pairs, side, t, A.n_cols)) { id = cand; break; }
-      }
+      for (int c = 0; c < kFzMaxCols; ++c) t[c] = c < A.n_cols ? tb_value(A, v, c) : 0ll;
+      m = !slot_find(table, mask, tb_hash(side, t, A.n_cols), K, id, [&](uint64_t cand) { return kd_same(keys, cand, pairs, side, t, A.n_cols); });
     }
     if (kInsert) {
       miss[v] = m ? 1 : 0;
@@ -108,15 +73,12 @@ __global__ __launch_bounds__(kKdBlock) void k_kd_probe(KdBatch A, const unsigned
       *(v >= A.n ? key_b + (v - A.n) : key_a + v) = id;
     }
   }
-  if (kInsert) {
-    for (int o = 32; o > 0; o >>= 1) missed += __shfl_down(missed, o);     // one atomic per wavefront
-    if ((threadIdx.x & 63) == 0 && missed) atomicAdd(n_miss, (unsigned long long)missed);
-  }
+  if (kInsert) wave_count_add(n_miss, missed);
 }
 
 // Step 3: one lane per new key.  first_row[j] = the virtual row where new key j first appears (step 2).  flags |= KD_FLAG_CLUSTER when a
 // claim needed a long probe sequence: the host then grows the table after the call (a hint for speed; the claim itself always succeeds).
-__global__ __launch_bounds__(kKdBlock) void k_kd_append(KdBatch A, const uint64_t *__restrict__ first_row, uint64_t m, uint64_t K0, unsigned long long *__restrict__ table,
+__global__ __launch_bounds__(kKdBlock) void k_kd_append(TupleBatch A, const uint64_t *__restrict__ first_row, uint64_t m, uint64_t K0, unsigned long long *__restrict__ table,
                                                         uint64_t mask, unsigned long long *__restrict__ keys, int pairs, uint32_t *__restrict__ flags) {
   const uint64_t V = A.n * A.sides;
   for (uint64_t j = (uint64_t)blockIdx.x * kKdBlock + threadIdx.x; j < m; j += (uint64_t)gridDim.x * kKdBlock) {
@@ -125,24 +87,15 @@ __global__ __launch_bounds__(kKdBlock) void k_kd_append(KdBatch A, const uint64_
     const uint64_t side = v >= A.n ? 1ull : 0ull;
     long long t[kFzMaxCols];
 #pragma unroll
-    for (int c = 0; c < kFzMaxCols; ++c) t[c] = c < A.n_cols ? kd_value(A, v, c) : 0ll;
+    for (int c = 0; c < kFzMaxCols; ++c) t[c] = c < A.n_cols ? tb_value(A, v, c) : 0ll;
     unsigned long long *rec = keys + (K0 + j) * (uint64_t)(2 * pairs);
     rec[0] = side;
 #pragma unroll
     for (int c = 0; c < kFzMaxCols; ++c)
       if (c < A.n_cols) rec[c + 1] = (unsigned long long)t[c];
     if (((A.n_cols + 1) & 1) != 0) rec[A.n_cols + 1] = 0ull;          // the pad word
-    const uint64_t h = kd_hash(side, t, A.n_cols);
-    const unsigned long long mine = ((h >> 32) << 32) | (K0 + j);      // (K0 + j < 2^32 - 1: never the empty word)
-    uint32_t probes = 0;
-    for (uint64_t s = h & mask;; s = (s + 1) & mask, ++probes) {
-      unsigned long long w = kd_peek(table + s);
-      if (w == kKdEmpty) {
-        w = atomicCAS(table + s, kKdEmpty, mine);
-        if (w == kKdEmpty) break;                                      // claimed
-      }
-    }
-    if (probes > kKdMaxProbe) atomicOr(flags, KD_FLAG_CLUSTER);
+    const uint64_t h = tb_hash(side, t, A.n_cols);
+    if (slot_claim(table, mask, h, slot_word(h, K0 + j)) > kKdMaxProbe) atomicOr(flags, KD_FLAG_CLUSTER);      // (K0 + j < 2^32 - 1: never the empty word)
   }
 }
 
@@ -169,20 +122,14 @@ __global__ __launch_bounds__(kKdBlock) void k_kd_rehash(const unsigned long long
     long long t[kFzMaxCols];
 #pragma unroll
     for (int c = 0; c < kFzMaxCols; ++c) t[c] = c < n_cols ? (long long)kd_word(rw, c + 1) : 0ll;
-    const uint64_t h = kd_hash(side, t, n_cols);
-    const unsigned long long mine = ((h >> 32) << 32) | j;
-    for (uint64_t s = h & mask;; s = (s + 1) & mask) {
-      unsigned long long w = kd_peek(table + s);
-      if (w == kKdEmpty) {
-        w = atomicCAS(table + s, kKdEmpty, mine);
-        if (w == kKdEmpty) break;
-      }
-      if (kCheck && (w >> 32) == (mine >> 32) && (w & 0xffffffffull) != j && (w & 0xffffffffull) < K &&
-          kd_same(keys, w & 0xffffffffull, pairs, side, t, n_cols)) {
+    const uint64_t h = tb_hash(side, t, n_cols);
+    slot_claim(table, mask, h, slot_word(h, j), [&](unsigned long long w) {
+      if (kCheck && (w >> 32) == (h >> 32) && (w & 0xffffffffull) != j && (w & 0xffffffffull) < K && kd_same(keys, w & 0xffffffffull, pairs, side, t, n_cols)) {
         atomicOr(flags, KD_FLAG_DUPLICATE);
-        break;
+        return true;
       }
-    }
+      return false;
+    });
   }
 }
 
@@ -190,8 +137,7 @@ __global__ __launch_bounds__(kKdBlock) void k_kd_rehash(const unsigned long long
 // byte of mask[t] at the key's value in column col[t] is not 0 — tad_mask_rows' rule on the records instead of on rows.  The record is
 // loaded whole (kd_load_record) before any mask byte is read; the term's column is picked by compares, so the record stays in registers;
 // the loop over the terms stays rolled (unrolled, eight pointers, lengths and columns at once spill scalar registers).
-// A value outside [0, mask_len[t]) raises KD_FLAG_BAD_CODE and reads nothing.  The selected keys are counted per wavefront, summed per
-// workgroup in LDS, one atomic per workgroup.
+// A value outside [0, mask_len[t]) raises KD_FLAG_BAD_CODE and reads nothing.  The selected keys are counted with one atomic per workgroup.
 __global__ __launch_bounds__(kKdBlock) void k_kd_select(const unsigned long long *__restrict__ keys, int pairs, uint64_t K, KdSelect q, uint8_t *__restrict__ keep,
                                                         unsigned long long *__restrict__ n_sel, uint32_t *__restrict__ flags) {
   __shared__ uint32_t s_cnt[kKdBlock / 64];
@@ -217,22 +163,14 @@ __global__ __launch_bounds__(kKdBlock) void k_kd_select(const unsigned long long
     keep[k] = ok ? 1 : 0;
     mine += ok ? 1u : 0u;
   }
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
-  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t total = 0;
-#pragma unroll
-    for (int i = 0; i < kKdBlock / 64; ++i) total += s_cnt[i];
-    if (total) atomicAdd(n_sel, (unsigned long long)total);
-  }
+  block_count_add(s_cnt, n_sel, mine);
 }
 
 int kd_stride(int n_cols) { return (n_cols + 2) & ~1; }      // side + columns, padded to an even number of 8-byte words
 
 static dim3 kd_grid(uint64_t items) { const uint64_t b = (items + kKdBlock - 1) / kKdBlock; return dim3((unsigned)(b < 16384 ? (b ? b : 1) : 16384)); }
 
-void launch_kd_probe(hipStream_t s, const KdBatch &A, const unsigned long long *table, uint64_t slots, const unsigned long long *keys, uint64_t K, uint64_t *key_a,
+void launch_kd_probe(hipStream_t s, const TupleBatch &A, const unsigned long long *table, uint64_t slots, const unsigned long long *keys, uint64_t K, uint64_t *key_a,
                      uint64_t *key_b, uint8_t *miss, unsigned long long *n_miss) {
   const uint64_t V = A.n * A.sides;
   const int pairs = kd_stride(A.n_cols) / 2;
@@ -240,7 +178,7 @@ void launch_kd_probe(hipStream_t s, const KdBatch &A, const unsigned long long *
   else hipLaunchKernelGGL(k_kd_probe<false>, kd_grid(V), dim3(kKdBlock), 0, s, A, table, slots - 1, keys, pairs, K, key_a, key_b, miss, n_miss);
 }
 
-void launch_kd_append(hipStream_t s, const KdBatch &A, const uint64_t *first_row, uint64_t m, uint64_t K0, unsigned long long *table, uint64_t slots,
+void launch_kd_append(hipStream_t s, const TupleBatch &A, const uint64_t *first_row, uint64_t m, uint64_t K0, unsigned long long *table, uint64_t slots,
                       unsigned long long *keys, uint32_t *flags) {
   hipLaunchKernelGGL(k_kd_append, kd_grid(m), dim3(kKdBlock), 0, s, A, first_row, m, K0, table, slots - 1, keys, kd_stride(A.n_cols) / 2, flags);
 }

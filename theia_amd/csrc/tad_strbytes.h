@@ -1,29 +1,15 @@
-// tad_strbytes.h — the byte helpers of the string kernels: a row's span in an Arrow string column, its bytes as little-endian words
-// from global memory and from an LDS stage, the hash and the aligned 16-byte compare.  Shared by tad_factorize.hip (tad_encode_strings: the
-// strings of one call) and tad_strdict.hip (tad_strdict: the strings of every call); device code only, included by those two files.
+// tad_strbytes.h — the byte helpers of the string kernels: a row's span in an Arrow string column (StrBatch, tad_internal.h), its bytes as
+// little-endian words from global memory and from an LDS stage, the hash and the aligned 16-byte compare.  Shared by tad_factorize.hip
+// (tad_encode_strings: the strings of one call) and tad_strdict.hip (tad_strdict: the strings of every call); device code only, included by
+// those two files.
 #pragma once
 #include "tad_internal.h"
+#include "tad_slots.h"      // fz_mix, and the slot table for both includers
 
 namespace tad {
 
-__device__ __forceinline__ uint64_t fz_mix(uint64_t x) {   // splitmix64 finaliser
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-struct StrArgs {
-  const void *off;        // n + 1 offsets into data
-  const uint8_t *data;
-  const uint8_t *valid;   // Arrow validity bitmap (bit valid_off + i), NULL = no nulls
-  uint64_t valid_off;
-  uint64_t n;
-  uint64_t data_bytes;
-  int off64;              // offsets are int64 (large_string) instead of int32
-};
-
 // [b, b + len) of row v; false if the offsets are not usable
-__device__ __forceinline__ bool se_span(const StrArgs &A, uint64_t v, uint64_t &b, uint32_t &len) {
+__device__ __forceinline__ bool se_span(const StrBatch &A, uint64_t v, uint64_t &b, uint32_t &len) {
   uint64_t e;
   if (A.off64) {
     const long long *o = static_cast<const long long *>(A.off);

@@ -5,10 +5,9 @@
 // key dictionary behind it lives (tad.h, tad_keydict: "one vocabulary per column, kept for the life of the dictionary"), so it kept its own
 // string -> code map (numpy's unique + a Python dict per batch and column) in front of an encode that runs at 2.3e10 rows/s.  Here the map
 // lives in HBM — to tad_encode_strings what tad_keydict.hip is to tad_factorize:
-//   table    open addressing, linear probing, one 8-byte word per slot — word = fingerprint (high 32 bits of the string's hash) << 32 | code,
-//            all ones = empty.  A slot is claimed with ONE compare-and-swap and its word never changes afterwards, so probes LOOK with plain
-//            cached loads (kd_peek's reasoning: a stale view can only show "empty" where a slot has just been claimed, and an empty slot is
-//            only ever taken with the compare-and-swap, which returns the truth);
+//   table    the slot table of tad_slots.h (which has the protocol: a look with a plain cached load, a claim with ONE compare-and-swap —
+//            slot_claim's atomicCAS) — word = fingerprint (high 32 bits of the string's hash) << 32 | code, all ones = empty, and a word
+//            that never changes once claimed;
 //   records  one 16-byte record per code, read with one 16-byte load: the string's offset in the arena (8 bytes), its length (4) and the LOW
 //            32 bits of its hash (4).  Slot and record together hold the whole hash, so growing the table (k_sd_rehash) walks the old slots
 //            and reads the records only, never the arena;
@@ -40,12 +39,6 @@
 namespace tad {
 
 static constexpr int kSdBlock = 256;
-static constexpr unsigned long long kSdEmpty = ~0ull;
-
-// a plain cached load (see the top of the file and tad_keydict.hip: an agent-scope load would be a memory-side transaction per row)
-__device__ __forceinline__ unsigned long long sd_peek(const unsigned long long *slot) {
-  return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 // record c: x = the string's byte offset in the arena, y = hash's low 32 bits << 32 | length
 __device__ __forceinline__ uint32_t sd_rec_len(const ulonglong2 &r) { return (uint32_t)(r.y & 0xffffffffull); }
@@ -56,7 +49,7 @@ __device__ __forceinline__ uint32_t sd_rec_hash_lo(const ulonglong2 &r) { return
 // (no such word exists in a dictionary that every call left normally).  A row whose offsets are unusable raises SD_FLAG_BAD_OFFSETS,
 // reads no byte and is neither a hit nor a miss: the host fails the call.
 template <bool kInsert>
-__global__ __launch_bounds__(kSdBlock) void k_sd_probe(StrArgs A, const unsigned long long *__restrict__ table, uint64_t mask, const ulonglong2 *__restrict__ recs,
+__global__ __launch_bounds__(kSdBlock) void k_sd_probe(StrBatch A, const unsigned long long *__restrict__ table, uint64_t mask, const ulonglong2 *__restrict__ recs,
                                                        const uint8_t *__restrict__ arena, uint64_t K, long long *__restrict__ codes, uint8_t *__restrict__ miss,
                                                        unsigned long long *__restrict__ n_miss, uint32_t *__restrict__ flags) {
   __shared__ __attribute__((aligned(16))) uint64_t s_bytes[kSeStage / 8 + 4];
@@ -106,17 +99,14 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_probe(StrArgs A, const unsigned
         } else {
           h = se_hash(p, len);
         }
-        for (uint64_t s = h & mask;; s = (s + 1) & mask) {
-          const unsigned long long w = sd_peek(table + s);
-          if (w == kSdEmpty) { m = true; break; }                   // (load <= 1/2: every probe sequence reaches an empty slot)
-          const uint64_t cand = w & 0xffffffffull;
-          if ((w >> 32) != (h >> 32) || cand >= K) continue;
+        uint64_t held;
+        m = !slot_find(table, mask, h, K, held, [&](uint64_t cand) {
           const ulonglong2 r = recs[cand];
-          if (sd_rec_len(r) != len) continue;                       // lengths first
+          if (sd_rec_len(r) != len) return false;                   // lengths first
           const uint8_t *q = arena + r.x;
-          const bool same = staged ? se_same_as([&](uint32_t o, uint32_t mm) { return se_load_lds(s_bytes, at + o, mm); }, q, len) : se_same(p, q, len);
-          if (same) { code = (long long)cand; break; }
-        }
+          return staged ? se_same_as([&](uint32_t o, uint32_t mm) { return se_load_lds(s_bytes, at + o, mm); }, q, len) : se_same(p, q, len);
+        });
+        if (!m) code = (long long)held;
       }
       if (kInsert) {
         miss[v] = m ? 1 : 0;
@@ -127,15 +117,12 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_probe(StrArgs A, const unsigned
       }
     }
   }
-  if (kInsert) {
-    for (int o = 32; o > 0; o >>= 1) missed += __shfl_down(missed, o);     // one atomic per wavefront
-    if ((threadIdx.x & 63) == 0 && missed) atomicAdd(n_miss, (unsigned long long)missed);
-  }
+  if (kInsert) wave_count_add(n_miss, missed);
 }
 
 // Step 3: cnt[j] = the 16-byte units new value j takes in the arena, for j < *num_new (step 2's count, on the device); 0 for the rest of
 // the M entries the scan runs over, and for all of them when step 2 gave up (its flags: the host repeats it with a larger scratch table).
-__global__ __launch_bounds__(kSdBlock) void k_sd_lens(StrArgs A, const uint64_t *__restrict__ first_row, const unsigned long long *__restrict__ num_new, uint64_t M,
+__global__ __launch_bounds__(kSdBlock) void k_sd_lens(StrBatch A, const uint64_t *__restrict__ first_row, const unsigned long long *__restrict__ num_new, uint64_t M,
                                                       const uint32_t *__restrict__ se_flags, uint32_t *__restrict__ cnt) {
   const uint64_t m = *se_flags != 0u ? 0ull : *num_new;
   for (uint64_t j = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; j < M; j += (uint64_t)gridDim.x * kSdBlock) {
@@ -152,7 +139,7 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_lens(StrArgs A, const uint64_t 
 // Step 4: one lane per new value.  first_row[j] = the row where new value j first appears (step 2), off16[j] = its place in the arena in
 // 16-byte units behind arena_used (step 3).  The string is hashed while it is copied.  flags |= SD_FLAG_CLUSTER when a claim needed a long
 // probe sequence: the host then grows the table after the call (a hint for speed; the claim itself always succeeds).
-__global__ __launch_bounds__(kSdBlock) void k_sd_append(StrArgs A, const uint64_t *__restrict__ first_row, const unsigned long long *__restrict__ off16, uint64_t m,
+__global__ __launch_bounds__(kSdBlock) void k_sd_append(StrBatch A, const uint64_t *__restrict__ first_row, const unsigned long long *__restrict__ off16, uint64_t m,
                                                         uint64_t K0, uint64_t arena_used, unsigned long long *__restrict__ table, uint64_t mask,
                                                         ulonglong2 *__restrict__ recs, uint8_t *__restrict__ arena, uint32_t *__restrict__ flags) {
   for (uint64_t j = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; j < m; j += (uint64_t)gridDim.x * kSdBlock) {
@@ -171,16 +158,7 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_append(StrArgs A, const uint64_
     if (((len + 7u) >> 3) & 1u) dst[(len + 7u) >> 3] = 0ull;            // the second half of the last 16 bytes
     h = fz_mix(h);
     recs[K0 + j] = ulonglong2{at, ((h & 0xffffffffull) << 32) | len};
-    const unsigned long long mine = ((h >> 32) << 32) | (K0 + j);       // (K0 + j < 2^32 - 1: never the empty word)
-    uint32_t probes = 0;
-    for (uint64_t s = h & mask;; s = (s + 1) & mask, ++probes) {
-      unsigned long long w = sd_peek(table + s);
-      if (w == kSdEmpty) {
-        w = atomicCAS(table + s, kSdEmpty, mine);
-        if (w == kSdEmpty) break;                                       // claimed
-      }
-    }
-    if (probes > kSdMaxProbe) atomicOr(flags, SD_FLAG_CLUSTER);
+    if (slot_claim(table, mask, h, slot_word(h, K0 + j)) > kSdMaxProbe) atomicOr(flags, SD_FLAG_CLUSTER);       // (K0 + j < 2^32 - 1: never the empty word)
   }
 }
 
@@ -196,15 +174,8 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_rehash(const unsigned long long
                                                         unsigned long long *__restrict__ table, uint64_t mask) {
   for (uint64_t i = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; i < old_slots; i += (uint64_t)gridDim.x * kSdBlock) {
     const unsigned long long w = old_table[i];
-    if (w == kSdEmpty || (w & 0xffffffffull) >= K) continue;
-    const uint64_t h = ((w >> 32) << 32) | sd_rec_hash_lo(recs[w & 0xffffffffull]);
-    for (uint64_t s = h & mask;; s = (s + 1) & mask) {
-      unsigned long long x = sd_peek(table + s);
-      if (x == kSdEmpty) {
-        x = atomicCAS(table + s, kSdEmpty, w);
-        if (x == kSdEmpty) break;
-      }
-    }
+    if (w == kSlotEmpty || (w & 0xffffffffull) >= K) continue;
+    slot_claim(table, mask, ((w >> 32) << 32) | sd_rec_hash_lo(recs[w & 0xffffffffull]), w);
   }
 }
 
@@ -219,7 +190,7 @@ __device__ __forceinline__ uint64_t sd_fold(uint64_t x) {
 // tad_strdict_match: one lane per value.  The pattern (already folded by the host for TAD_STR_CONTAINS_NOCASE) lies in LDS.  TAD_STR_EQUAL: the
 // length, then the aligned 16-byte compare.  TAD_STR_CONTAINS_NOCASE: a plain search — for every start the value's bytes are taken as 8-byte
 // words from ALIGNED 8-byte loads (the two words under the start stay in registers while the start moves through them), folded and compared with
-// the pattern's words.  The matches are counted per wavefront, summed per workgroup in LDS, one atomic per workgroup.
+// the pattern's words.  The matches are counted with one atomic per workgroup.
 __global__ __launch_bounds__(kSdBlock) void k_sd_match(const ulonglong2 *__restrict__ recs, const uint8_t *__restrict__ arena, uint64_t K, int op,
                                                        const uint8_t *__restrict__ pattern, uint32_t plen, uint8_t *__restrict__ out, unsigned long long *__restrict__ n_hit) {
   __shared__ __attribute__((aligned(16))) uint64_t s_pat[kSdMaxPattern / 8 + 2];
@@ -265,15 +236,7 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_match(const ulonglong2 *__restr
     out[c] = hit ? 1 : 0;
     mine += hit ? 1u : 0u;
   }
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
-  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t total = 0;
-#pragma unroll
-    for (int i = 0; i < kSdBlock / 64; ++i) total += s_cnt[i];
-    if (total) atomicAdd(n_hit, (unsigned long long)total);
-  }
+  block_count_add(s_cnt, n_hit, mine);
 }
 
 // tad_strdict_export: cnt[i] = the length of value first + i (the scan of it gives Arrow's offsets) ...
@@ -300,26 +263,20 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_export(const ulonglong2 *__rest
 
 static dim3 sd_grid(uint64_t items) { const uint64_t b = (items + kSdBlock - 1) / kSdBlock; return dim3((unsigned)(b < 16384 ? (b ? b : 1) : 16384)); }
 
-static StrArgs sd_args(const SdBatch &B) {
-  StrArgs A{};
-  A.off = B.offsets; A.data = B.data; A.valid = B.valid; A.valid_off = B.valid_off; A.n = B.n; A.data_bytes = B.data_bytes; A.off64 = B.off64;
-  return A;
-}
-
-void launch_sd_probe(hipStream_t s, const SdBatch &B, const unsigned long long *table, uint64_t slots, const void *recs, const uint8_t *arena, uint64_t K,
+void launch_sd_probe(hipStream_t s, const StrBatch &B, const unsigned long long *table, uint64_t slots, const void *recs, const uint8_t *arena, uint64_t K,
                      long long *codes, uint8_t *miss, unsigned long long *n_miss, uint32_t *flags) {
   const ulonglong2 *r = static_cast<const ulonglong2 *>(recs);
-  if (miss != nullptr) hipLaunchKernelGGL(k_sd_probe<true>, sd_grid(B.n), dim3(kSdBlock), 0, s, sd_args(B), table, slots - 1, r, arena, K, codes, miss, n_miss, flags);
-  else hipLaunchKernelGGL(k_sd_probe<false>, sd_grid(B.n), dim3(kSdBlock), 0, s, sd_args(B), table, slots - 1, r, arena, K, codes, miss, n_miss, flags);
+  if (miss != nullptr) hipLaunchKernelGGL(k_sd_probe<true>, sd_grid(B.n), dim3(kSdBlock), 0, s, B, table, slots - 1, r, arena, K, codes, miss, n_miss, flags);
+  else hipLaunchKernelGGL(k_sd_probe<false>, sd_grid(B.n), dim3(kSdBlock), 0, s, B, table, slots - 1, r, arena, K, codes, miss, n_miss, flags);
 }
 
-void launch_sd_lens(hipStream_t s, const SdBatch &B, const uint64_t *first_row, const unsigned long long *num_new, uint64_t M, const uint32_t *se_flags, uint32_t *cnt) {
-  hipLaunchKernelGGL(k_sd_lens, sd_grid(M), dim3(kSdBlock), 0, s, sd_args(B), first_row, num_new, M, se_flags, cnt);
+void launch_sd_lens(hipStream_t s, const StrBatch &B, const uint64_t *first_row, const unsigned long long *num_new, uint64_t M, const uint32_t *se_flags, uint32_t *cnt) {
+  hipLaunchKernelGGL(k_sd_lens, sd_grid(M), dim3(kSdBlock), 0, s, B, first_row, num_new, M, se_flags, cnt);
 }
 
-void launch_sd_append(hipStream_t s, const SdBatch &B, const uint64_t *first_row, const unsigned long long *off16, uint64_t m, uint64_t K0, uint64_t arena_used,
+void launch_sd_append(hipStream_t s, const StrBatch &B, const uint64_t *first_row, const unsigned long long *off16, uint64_t m, uint64_t K0, uint64_t arena_used,
                       unsigned long long *table, uint64_t slots, void *recs, uint8_t *arena, uint32_t *flags) {
-  hipLaunchKernelGGL(k_sd_append, sd_grid(m), dim3(kSdBlock), 0, s, sd_args(B), first_row, off16, m, K0, arena_used, table, slots - 1, static_cast<ulonglong2 *>(recs), arena,
+  hipLaunchKernelGGL(k_sd_append, sd_grid(m), dim3(kSdBlock), 0, s, B, first_row, off16, m, K0, arena_used, table, slots - 1, static_cast<ulonglong2 *>(recs), arena,
                      flags);
 }
 

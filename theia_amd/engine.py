@@ -615,6 +615,33 @@ def _string_column(column, what):
     return sc, n, dev, keepalive
 
 
+def _need_feature(lib, feature, what):
+    """a library of before `feature` (or of before tad_features) has no `what`: refused before it is touched"""
+    if not (getattr(lib, "tad_features", None) and lib.tad_features() & getattr(capi, "TAD_FEATURE_" + feature)):
+        raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no %s (TAD_FEATURE_%s)" % (what, feature))
+
+
+def _out_array(eng, dev, n, dtype, room=None):
+    """-> (array, pointer): a call's output of n values — a DeviceArray (dev) or a numpy array — allocated with room for `room` values"""
+    room = n if room is None else room
+    if dev:
+        a = DeviceArray(eng, room, dtype)
+        a.n = n
+        return a, a.ptr
+    a = np.empty(room, dtype=dtype)
+    return a[:n], a.ctypes.data
+
+
+def _out_mask(eng, dev, K):
+    """-> (mask, pointer): K bytes, one per key or value, zeroed on the host or allocated on the device (in 8-byte elements); the pointer
+    is None for K == 0"""
+    if dev:
+        m = DeviceArray(eng, (K + 7) // 8 if K else 1, np.uint64)
+        return m, (m.ptr if K else None)
+    m = np.zeros(K, np.uint8)
+    return m, (m.ctypes.data if K else None)
+
+
 class KeyDict:
     """A key dictionary that lives in HBM and outlives the call (tad_keydict): key tuples -> dense ids that stay the same from batch to
     batch, new ids in order of first appearance — what the streaming states want for their key ids.  n_cols: the tuple width;
@@ -624,8 +651,7 @@ class KeyDict:
         self._engine = engine
         self._h = None
         self.n_cols = int(n_cols)
-        if not (getattr(engine._lib, "tad_features", None) and engine._lib.tad_features() & capi.TAD_FEATURE_KEY_DICT):
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no key dictionary (TAD_FEATURE_KEY_DICT)")
+        _need_feature(engine._lib, "KEY_DICT", "key dictionary")
         h = C.c_void_p()
         engine._check(engine._lib.tad_keydict_create(engine._h, self.n_cols, int(expected_keys), C.byref(h)))
         self._h = h
@@ -640,17 +666,10 @@ class KeyDict:
         kc, n, sides, dev, keepalive = _key_columns(eng, "KeyDict.encode", self.n_cols, cols_a, keep_a, cols_b, keep_b)
         cap = int(max_new) if max_new is not None else n * sides
         before, after = capi.u64(), capi.u64()
-        if dev:
-            key1 = DeviceArray(eng, n, np.uint64)
-            key2 = DeviceArray(eng, n, np.uint64) if sides == 2 else None
-            first = DeviceArray(eng, max(cap, 1), np.uint64)
-            ptrs = (key1.ptr, key2.ptr if key2 is not None else None, first.ptr)
-        else:
-            key1 = np.empty(n, dtype=np.uint64)
-            key2 = np.empty(n, dtype=np.uint64) if sides == 2 else None
-            first = np.empty(max(cap, 1), dtype=np.uint64)
-            ptrs = (key1.ctypes.data, key2.ctypes.data if key2 is not None else None, first.ctypes.data)
-        rc = eng._lib.tad_keydict_encode(eng._h, self._h, C.byref(kc), ptrs[0], ptrs[1], ptrs[2], cap, C.byref(before), C.byref(after))
+        key1, p1 = _out_array(eng, dev, n, np.uint64)
+        key2, p2 = _out_array(eng, dev, n, np.uint64) if sides == 2 else (None, None)
+        first, pf = _out_array(eng, dev, max(cap, 1), np.uint64)
+        rc = eng._lib.tad_keydict_encode(eng._h, self._h, C.byref(kc), p1, p2, pf, cap, C.byref(before), C.byref(after))
         del keepalive
         eng._check(rc)
         listed = min(int(after.value - before.value), cap)
@@ -664,15 +683,9 @@ class KeyDict:
         """encode() read-only (tad_keydict_lookup): (key_id, key_id2 or None); an unknown tuple gets TAD_KEY_SKIP, the dictionary is unchanged"""
         eng = self._engine
         kc, n, sides, dev, keepalive = _key_columns(eng, "KeyDict.lookup", self.n_cols, cols_a, keep_a, cols_b, keep_b)
-        if dev:
-            key1 = DeviceArray(eng, n, np.uint64)
-            key2 = DeviceArray(eng, n, np.uint64) if sides == 2 else None
-            ptrs = (key1.ptr, key2.ptr if key2 is not None else None)
-        else:
-            key1 = np.empty(n, dtype=np.uint64)
-            key2 = np.empty(n, dtype=np.uint64) if sides == 2 else None
-            ptrs = (key1.ctypes.data, key2.ctypes.data if key2 is not None else None)
-        rc = eng._lib.tad_keydict_lookup(eng._h, self._h, C.byref(kc), ptrs[0], ptrs[1])
+        key1, p1 = _out_array(eng, dev, n, np.uint64)
+        key2, p2 = _out_array(eng, dev, n, np.uint64) if sides == 2 else (None, None)
+        rc = eng._lib.tad_keydict_lookup(eng._h, self._h, C.byref(kc), p1, p2)
         del keepalive
         eng._check(rc)
         return key1, key2
@@ -685,8 +698,7 @@ class KeyDict:
         takes without a copy) or a numpy uint8 array (out="host").  A key whose code lies outside a term's mask is refused; the
         dictionary is only read."""
         eng = self._engine
-        if not (getattr(eng._lib, "tad_features", None) and eng._lib.tad_features() & capi.TAD_FEATURE_KEY_SELECT):
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_keydict_select (TAD_FEATURE_KEY_SELECT)")
+        _need_feature(eng._lib, "KEY_SELECT", "tad_keydict_select")
         if out not in ("device", "host"):
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "KeyDict.select: out must be device or host")
         terms = list(terms)
@@ -710,16 +722,11 @@ class KeyDict:
             lens.append(a.size)
         nt = len(terms)
         K = self.num_keys()
-        if dev:
-            keep = DeviceArray(eng, (K + 7) // 8 if K else 1, np.uint64)
-            keep_ptr = keep.ptr
-        else:
-            keep = np.zeros(K, np.uint8)
-            keep_ptr = keep.ctypes.data if K else None
+        keep, keep_ptr = _out_mask(eng, dev, K)
         n_sel = capi.u64()
         rc = eng._lib.tad_keydict_select(eng._h, self._h, nt, (capi.i32 * max(nt, 1))(*[int(c) for c, _ in terms]),
                                          (C.c_void_p * max(nt, 1))(*ptrs), (capi.u64 * max(nt, 1))(*lens), -1 if side is None else int(side),
-                                         keep_ptr if K else None, K, capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST, C.byref(n_sel))
+                                         keep_ptr, K, capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST, C.byref(n_sel))
         del keepalive
         eng._check(rc)
         if dev:
@@ -743,8 +750,7 @@ class KeyDict:
         is forgotten (a lookup gives TAD_KEY_SKIP, an encode a new id at the end).  remap: a numpy array or a DeviceArray with one entry
         per key held.  Returns the keys held afterwards."""
         eng = self._engine
-        if not (getattr(eng._lib, "tad_features", None) and eng._lib.tad_features() & capi.TAD_FEATURE_KEY_RETIRE):
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_keydict_compact (TAD_FEATURE_KEY_RETIRE)")
+        _need_feature(eng._lib, "KEY_RETIRE", "tad_keydict_compact")
         n = capi.u64()
         if isinstance(remap, DeviceArray):
             rc = eng._lib.tad_keydict_compact(eng._h, self._h, remap.ptr, remap.n, capi.TAD_MEM_DEVICE, C.byref(n))
@@ -798,8 +804,7 @@ class StringDict:
     def __init__(self, engine, expected_values=0, expected_bytes=0):
         self._engine = engine
         self._h = None
-        if not (getattr(engine._lib, "tad_features", None) and engine._lib.tad_features() & capi.TAD_FEATURE_STRING_DICT):
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no string dictionary (TAD_FEATURE_STRING_DICT)")
+        _need_feature(engine._lib, "STRING_DICT", "string dictionary")
         h = C.c_void_p()
         engine._check(engine._lib.tad_strdict_create(engine._h, int(expected_values), int(expected_bytes), C.byref(h)))
         self._h = h
@@ -822,20 +827,14 @@ class StringDict:
         sc, n, dev, keepalive = _string_column(column, "StringDict.encode")
         cap = int(max_new) if max_new is not None else n
         before, after = capi.u64(), capi.u64()
-        if dev:
-            codes = DeviceArray(eng, max(n, 1), np.int64)
-            first = DeviceArray(eng, max(cap, 1), np.uint64)
-            ptrs = (codes.ptr, first.ptr)
-        else:
-            codes = np.empty(n, dtype=np.int64)
-            first = np.empty(max(cap, 1), dtype=np.uint64)
-            ptrs = (codes.ctypes.data, first.ctypes.data)
-        rc = eng._lib.tad_strdict_encode(eng._h, self._h, C.byref(sc), ptrs[0], ptrs[1], cap, C.byref(before), C.byref(after))
+        codes, pc = _out_array(eng, dev, n, np.int64, room=max(n, 1))
+        first, pf = _out_array(eng, dev, max(cap, 1), np.uint64)
+        rc = eng._lib.tad_strdict_encode(eng._h, self._h, C.byref(sc), pc, pf, cap, C.byref(before), C.byref(after))
         del keepalive
         eng._check(rc)
         listed = min(int(after.value - before.value), cap)
         if dev:
-            codes.n, first.n = n, listed
+            first.n = listed
         else:
             first = first[:listed]
         return self._out(out, codes), self._out(out, first), int(before.value)
@@ -846,12 +845,10 @@ class StringDict:
         if out not in ("host", "device"):
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "StringDict.lookup: out must be host or device")
         sc, n, dev, keepalive = _string_column(column, "StringDict.lookup")
-        codes = DeviceArray(eng, max(n, 1), np.int64) if dev else np.empty(n, dtype=np.int64)
-        rc = eng._lib.tad_strdict_lookup(eng._h, self._h, C.byref(sc), codes.ptr if dev else codes.ctypes.data)
+        codes, pc = _out_array(eng, dev, n, np.int64, room=max(n, 1))
+        rc = eng._lib.tad_strdict_lookup(eng._h, self._h, C.byref(sc), pc)
         del keepalive
         eng._check(rc)
-        if dev:
-            codes.n = n
         return self._out(out, codes)
 
     def num_values(self):
@@ -916,14 +913,9 @@ class StringDict:
         buf = (C.c_ubyte * max(len(pat), 1)).from_buffer_copy(pat or b"\0")
         K = self.num_values()
         dev = out == "device"
-        if dev:
-            mask = DeviceArray(eng, (K + 7) // 8 if K else 1, np.uint64)
-            ptr = mask.ptr
-        else:
-            mask = np.zeros(K, np.uint8)
-            ptr = mask.ctypes.data if K else None
+        mask, ptr = _out_mask(eng, dev, K)
         hit = capi.u64()
-        rc = eng._lib.tad_strdict_match(eng._h, self._h, int(op), C.cast(buf, C.c_void_p) if pat else None, len(pat), ptr if K else None, K,
+        rc = eng._lib.tad_strdict_match(eng._h, self._h, int(op), C.cast(buf, C.c_void_p) if pat else None, len(pat), ptr, K,
                                         capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST, C.byref(hit))
         eng._check(rc)
         if dev:
@@ -1091,9 +1083,7 @@ class TadEngine:
 
     # ---- what the jobs on a state share: the feature gate, the detector's tad_job, the out memory, the call itself ----
     def _need(self, feature, what):
-        """a library of before `feature` (or of before tad_features) has no `what`: refused before it is touched"""
-        if not (getattr(self._lib, "tad_features", None) and self._lib.tad_features() & getattr(capi, "TAD_FEATURE_" + feature)):
-            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no %s (TAD_FEATURE_%s)" % (what, feature))
+        _need_feature(self._lib, feature, what)
 
     @staticmethod
     def _detector_job(algo, alpha=0.0, eps=0.0, min_samples=0, maxiter=0, nsigma=0.0, emit_all=False, job_id="", agg_flow="", value_op="auto"):

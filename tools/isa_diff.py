@@ -42,7 +42,7 @@ def kernels(asm_path, remarks):
         if m:
             cur = m.group(1); res[cur] = {}
             continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
+        m = re.search(r"remark:.*?\s(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
         if m and cur:
             res[cur][m.group(1).split(" ")[0]] = m.group(2)
     return body, res

@@ -57,10 +57,8 @@ int make_result(JobCtx *e, uint64_t rows, bool with_anomaly, tad_mem out_memory,
   ResultPriv *rp = new (std::nothrow) ResultPriv();
   if (!rp) return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory");
   memset(rp, 0, sizeof *rp);
-  const size_t bytes = result_bytes(rows, with_anomaly);
-  int rc = alloc_device_block(e, bytes, dev_block);
+  const int rc = carve_block(e, dev_block, dev_rows, result_layout, rows, with_anomaly);
   if (rc != TAD_OK) { delete rp; return rc; }
-  carve(dev_block->base, rows, with_anomaly, dev_rows);
   rp->pub.n_rows = rows;
   rp->pub.memory = out_memory;
   *out = rp;
@@ -80,15 +78,14 @@ int finish_result(JobCtx *e, ResultPriv *rp, uint64_t rows, bool with_anomaly, R
     rp->pub.anomaly = dev_rows.anomaly;
     return TAD_OK;
   }
-  const size_t bytes = result_bytes(rows, with_anomaly);
+  const size_t bytes = carved_bytes(result_layout, rows, with_anomaly);
   void *h = malloc(bytes);
   if (!h) { release_block(e, dev_block.base, dev_block.cap); return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory for %zu result bytes", bytes); }
   hipError_t r = hipMemcpyAsync(h, dev_block.base, bytes, hipMemcpyDeviceToHost, e->stream);
   if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
   release_block(e, dev_block.base, dev_block.cap);
   if (r != hipSuccess) { free(h); return fail(e, TAD_ERR_HIP, "result copy failed: %s", hipGetErrorString(r)); }
-  OutRows ho;
-  carve(h, rows, with_anomaly, &ho);
+  const OutRows ho = carve_at(h, result_layout, rows, with_anomaly);
   rp->block = h;
   rp->block_cap = bytes;
   rp->pub.key_id = reinterpret_cast<uint64_t *>(ho.key_id);
@@ -175,24 +172,22 @@ int finish_rows(JobCtx *e, const tad_job *job, RowsOut *ro, uint64_t rows, bool 
 }
 
 // The batch's new points in (key, time) order for stream_history_batch and state_merge_batch: keys in e->hs_key, times in e->hs_t, values
-// and per-key offsets in *nv / *poff.  ensure_batch_points sizes the buffers both share (hs_key, hs_t, hs_sorted, hs_koff: dense point
-// offsets | chunk offsets, K + 1 each; hs_kcnt: per-key counts / long-sort list / chunks | long-list length; the scan scratch).
-static int ensure_batch_points(JobCtx *e, uint64_t K, uint64_t P_cap, bool sparse) {
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
+// and per-key offsets in *nv / *poff.  ensure_batch_points sizes the buffers both share (hs_key, hs_t, hs_sorted, the per-key counts and
+// offsets of BatchKeys in hs_kcnt / hs_koff, the scan scratch).
+static int ensure_batch_points(JobCtx *e, uint64_t K, uint64_t P_cap, bool sparse, BatchKeys *bk) {
   const uint64_t pc = P_cap ? P_cap : 1;
   int rc;
   if ((rc = ensure(e, e->hs_key, pc * 8)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->hs_t, pc * 8)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->hs_sorted, pc * 8)) != TAD_OK) return rc;
-  if ((rc = ensure(e, e->hs_koff, (kpad + 4) * 16)) != TAD_OK) return rc;
-  if ((rc = ensure(e, e->hs_kcnt, kpad * 4 + 64)) != TAD_OK) return rc;
+  if ((rc = carve_bufs(e, e->hs_koff, e->hs_kcnt, bk, batch_keys_layout, K)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K > pc ? K : pc) * sizeof(unsigned long long))) != TAD_OK) return rc;
   if (!sparse && (rc = ensure(e, e->hs_val, pc * 8)) != TAD_OK) return rc;
   return TAD_OK;
 }
 
-static void batch_points(JobCtx *e, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, const unsigned long long **poff,
-                  const unsigned long long **nv) {
+static void batch_points(JobCtx *e, const BatchKeys &bk, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P,
+                         const unsigned long long **poff, const unsigned long long **nv) {
   hipStream_t s = e->stream;
   unsigned long long *nk = static_cast<unsigned long long *>(e->hs_key.p);
   long long *nt = static_cast<long long *>(e->hs_t.p);
@@ -201,12 +196,10 @@ static void batch_points(JobCtx *e, Grid g, Lattice L, const unsigned long long 
     *nv = static_cast<const unsigned long long *>(e->sp_val_a.p);
     launch_hist_decode(s, static_cast<const unsigned long long *>(e->sp_comp_a.p), P, L.t0, nk, nt);
   } else {             // the dense grid compacted as tad_aggregate does
-    unsigned long long *koff = static_cast<unsigned long long *>(e->hs_koff.p);
-    uint32_t *kcnt = static_cast<uint32_t *>(e->hs_kcnt.p);
-    launch_count_flags(s, g, true, kcnt);
-    launch_scan(s, kcnt, koff, g.K, static_cast<unsigned long long *>(e->scan_scratch.p));
-    launch_emit_points(s, g, L, koff, nk, nt, static_cast<unsigned long long *>(e->hs_val.p));
-    *poff = koff;
+    launch_count_flags(s, g, true, bk.kcnt);
+    launch_scan(s, bk.kcnt, bk.koff, g.K, static_cast<unsigned long long *>(e->scan_scratch.p));
+    launch_emit_points(s, g, L, bk.koff, nk, nt, static_cast<unsigned long long *>(e->hs_val.p));
+    *poff = bk.koff;
     *nv = static_cast<const unsigned long long *>(e->hs_val.p);
   }
 }
@@ -259,25 +252,22 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
   const int cur = st->cur, cand = cur ^ 1;
   const bool dbscan = jp.algo == TAD_ALGO_DBSCAN;
   const uint64_t P_cap = sparse_poff ? P : P_bound;
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
+  BatchKeys bk;
   int rc;
   // the candidate arenas first: an allocation failure leaves the state, its history and its series as they are
   const uint64_t need = st->hist.len[cur] + P_cap;
   if ((rc = state_grow_candidates(e, st, P_cap)) != TAD_OK) return rc;
-  if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr)) != TAD_OK) return rc;
+  if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr, &bk)) != TAD_OK) return rc;
   if (dbscan && (rc = ensure_hist_verdicts(e, P_cap)) != TAD_OK) return rc;   // (before the first launch: hist_verdicts then allocates nothing)
   unsigned long long *nk = static_cast<unsigned long long *>(e->hs_key.p);
   long long *nt = static_cast<long long *>(e->hs_t.p);
   unsigned long long *ns = static_cast<unsigned long long *>(e->hs_sorted.p);
-  unsigned long long *koff = static_cast<unsigned long long *>(e->hs_koff.p), *coff = koff + kpad + 4;
-  uint32_t *kcnt = static_cast<uint32_t *>(e->hs_kcnt.p);
-  unsigned int *long_count = reinterpret_cast<unsigned int *>(kcnt + kpad);
   unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
   const unsigned long long *poff, *nv;
-  batch_points(e, g, L, sparse_poff, P, &poff, &nv);   // 1.
+  batch_points(e, bk, g, L, sparse_poff, P, &poff, &nv);   // 1.
   if (st->history) {   // 2. every key's new values sorted; 3. merged with its history into the candidate arena
-    launch_hist_sort(s, nv, poff, K, ns, kcnt, long_count);
-    launch_hist_merge(s, K, st->hist.off[cur], st->hist.val.p[cur], poff, ns, st->hist.off[cand], st->hist.val.p[cand], kcnt, coff, scratch,
+    launch_hist_sort(s, nv, poff, K, ns, bk.kcnt, bk.long_count);
+    launch_hist_merge(s, K, st->hist.off[cur], st->hist.val.p[cur], poff, ns, st->hist.off[cand], st->hist.val.p[cand], bk.kcnt, bk.coff, scratch,
                       hist_merge_chunks_bound(K, need));
   }
   if (st->series)      // 3'. appended to its series in the candidate arena
@@ -303,35 +293,27 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
   const int cur = st->cur, cand = cur ^ 1;
   const uint64_t P_cap = sparse_poff ? P : P_bound;
   const uint64_t pc = P_cap ? P_cap : 1;
-  const size_t kpad = (size_t)((K + 3) & ~3ull), ko = kpad + 4;
   const uint64_t S = st->ser.len[cur], H = st->hist.len[cur];
+  BatchKeys bk;
+  MergePts mp;
+  MergeKeys mk;
   int rc;
   mc->changed = false;
   mc->added = 0;
   // the candidate arenas first: an allocation failure leaves the state as it is
   if ((rc = state_grow_candidates(e, st, P_cap)) != TAD_OK) return rc;
-  if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr)) != TAD_OK) return rc;
-  // per point: three scans (pc + 1 each) | history gains, sorted | losses, sorted | rank, three flag arrays | class
-  if ((rc = ensure(e, e->mg_pts, (7 * pc + 8) * 8 + pc * 16 + pc + 64)) != TAD_OK) return rc;
-  // per key: counters | long-list length | five offset arrays (K + 1 each) | four u32 arrays
-  if ((rc = ensure(e, e->mg_keys, 128 + ko * 40 + kpad * 16)) != TAD_OK) return rc;
-  unsigned long long *nhoff = static_cast<unsigned long long *>(e->mg_pts.p), *aoff = nhoff + pc + 2, *roff = aoff + pc + 2;
-  unsigned long long *hadd = roff + pc + 2, *hadd_s = hadd + pc, *hrem = hadd_s + pc, *hrem_s = hrem + pc;
-  uint32_t *rank = reinterpret_cast<uint32_t *>(hrem_s + pc), *f_nh = rank + pc, *f_kept = f_nh + pc, *f_hit = f_kept + pc;
-  uint8_t *cls = reinterpret_cast<uint8_t *>(f_hit + pc);
-  MergeCounters *mcnt = static_cast<MergeCounters *>(e->mg_keys.p);
-  unsigned int *long_count = reinterpret_cast<unsigned int *>(mcnt + 1);
-  unsigned long long *akoff = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(e->mg_keys.p) + 128), *rkoff = akoff + ko;
-  unsigned long long *hoff_mid = rkoff + ko, *coff_s = hoff_mid + ko, *coff_h = coff_s + ko;
-  uint32_t *chunks_s = reinterpret_cast<uint32_t *>(coff_h + ko), *chunks_h = chunks_s + kpad, *replay = chunks_h + kpad, *long_list = replay + kpad;
+  if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr, &bk)) != TAD_OK) return rc;
+  if ((rc = carve_buf(e, e->mg_pts, &mp, merge_pts_layout, pc)) != TAD_OK) return rc;
+  if ((rc = carve_buf(e, e->mg_keys, &mk, merge_keys_layout, K)) != TAD_OK) return rc;
+  MergeCounters *mcnt = mk.mcnt;
   unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
   const unsigned long long *nk = static_cast<const unsigned long long *>(e->hs_key.p);
   const long long *nt = static_cast<const long long *>(e->hs_t.p);
   const unsigned long long *poff, *nv;
-  batch_points(e, g, L, sparse_poff, P, &poff, &nv);
+  batch_points(e, bk, g, L, sparse_poff, P, &poff, &nv);
   // 1. classify; the one round trip: Stage 0's error word, the point count, the classification's counters
   HIP_TRY(e, hipMemsetAsync(mcnt, 0, sizeof(MergeCounters), s));
-  launch_merge_classify(s, nk, nt, poff + K, P_cap, K, st->ser.off[cur], st->ser_times.p[cur], (long long)mc->keep_from, cls, rank, f_nh, f_kept, f_hit, mcnt);
+  launch_merge_classify(s, nk, nt, poff + K, P_cap, K, st->ser.off[cur], st->ser_times.p[cur], (long long)mc->keep_from, mp.cls, mp.rank, mp.f_nh, mp.f_kept, mp.f_hit, mcnt);
   unsigned char *hm = e->tail_host + kTailMoments;   // (the moment partials' place in the pinned tail: a merge has none)
   HIP_TRY(e, hipMemcpyAsync(e->ctr_host, e->counters.p, sizeof(DevCounters), hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
@@ -355,8 +337,8 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
     // 6. every point is newer than what its key held: the append path of a stream batch (stream_history_batch's steps 2, 3, 3', 3'')
     if (st->history) {
       unsigned long long *ns = static_cast<unsigned long long *>(e->hs_sorted.p);
-      launch_hist_sort(s, nv, poff, K, ns, long_list, long_count);
-      launch_hist_merge(s, K, st->hist.off[cur], st->hist.val.p[cur], poff, ns, st->hist.off[cand], st->hist.val.p[cand], chunks_h, coff_h, scratch,
+      launch_hist_sort(s, nv, poff, K, ns, mk.long_list, mk.long_count);
+      launch_hist_merge(s, K, st->hist.off[cur], st->hist.val.p[cur], poff, ns, st->hist.off[cand], st->hist.val.p[cand], mk.chunks_h, mk.coff_h, scratch,
                         hist_merge_chunks_bound(K, H + P_cap));
     }
     launch_series_append(s, K, st->ser.off[cur], st->ser.val.p[cur], poff, nv, st->ser.off[cand], st->ser.val.p[cand]);
@@ -367,32 +349,32 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
   } else {
     if (st->history && c.combined && (rc = ensure(e, e->mg_hist, (H ? H : 1) * 8)) != TAD_OK) return rc;
     // 2. the scans; per key: candidate offsets, the history's packed gains / losses, chunk counts, who replays
-    launch_scan(s, f_nh, nhoff, P_cap, scratch);
-    launch_scan(s, f_kept, aoff, P_cap, scratch);
-    launch_scan(s, f_hit, roff, P_cap, scratch);
-    launch_merge_keys(s, K, poff, nhoff, aoff, roff, cls, st->ser.off[cur], st->history ? st->hist.off[cur] : nullptr, st->ser.off[cand], akoff, rkoff,
-                      hoff_mid, chunks_s, chunks_h, replay);
-    launch_scan(s, chunks_s, coff_s, K, scratch);
+    launch_scan(s, mp.f_nh, mp.nhoff, P_cap, scratch);
+    launch_scan(s, mp.f_kept, mp.aoff, P_cap, scratch);
+    launch_scan(s, mp.f_hit, mp.roff, P_cap, scratch);
+    launch_merge_keys(s, K, poff, mp.nhoff, mp.aoff, mp.roff, mp.cls, st->ser.off[cur], st->history ? st->hist.off[cur] : nullptr, st->ser.off[cand], mk.akoff, mk.rkoff,
+                      mk.hoff_mid, mk.chunks_s, mk.chunks_h, mk.replay);
+    launch_scan(s, mk.chunks_s, mk.coff_s, K, scratch);
     // 3. series and times merged by time (and the history's gains and losses packed)
-    launch_merge_series(s, merge_chunks_bound(K, S + P_cap), coff_s, K, op_max, st->ser.off[cur], st->ser.val.p[cur], st->ser_times.p[cur], poff, nt, nv, cls, rank,
-                        nhoff, aoff, roff, st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], st->history ? hadd : nullptr, st->history ? hrem : nullptr);
+    launch_merge_series(s, merge_chunks_bound(K, S + P_cap), mk.coff_s, K, op_max, st->ser.off[cur], st->ser.val.p[cur], st->ser_times.p[cur], poff, nt, nv, mp.cls, mp.rank,
+                        mp.nhoff, mp.aoff, mp.roff, st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], st->history ? mp.hadd : nullptr, st->history ? mp.hrem : nullptr);
     if (st->history) {   // 4. the combined points' old values leave the history (through the scratch arena), then the batch's values enter
       const unsigned long long *hoff_from = st->hist.off[cur], *hval_from = st->hist.val.p[cur];
       if (c.combined) {
         unsigned long long *hmid = static_cast<unsigned long long *>(e->mg_hist.p);
-        launch_hist_sort(s, hrem, rkoff, K, hrem_s, long_list, long_count);
-        launch_scan(s, chunks_h, coff_h, K, scratch);
-        // (chunks_h gives an empty key no chunk: not the one-chunk-at-least counts of a trim)
-        launch_hist_subtract(s, trim_chunks_bound(K, H), coff_h, K, st->hist.off[cur], st->hist.val.p[cur], rkoff, hrem_s, hoff_mid, hmid, false);
-        hoff_from = hoff_mid;
+        launch_hist_sort(s, mp.hrem, mk.rkoff, K, mp.hrem_s, mk.long_list, mk.long_count);
+        launch_scan(s, mk.chunks_h, mk.coff_h, K, scratch);
+        // (mk.chunks_h gives an empty key no chunk: not the one-chunk-at-least counts of a trim)
+        launch_hist_subtract(s, trim_chunks_bound(K, H), mk.coff_h, K, st->hist.off[cur], st->hist.val.p[cur], mk.rkoff, mp.hrem_s, mk.hoff_mid, hmid, false);
+        hoff_from = mk.hoff_mid;
         hval_from = hmid;
       }
-      launch_hist_sort(s, hadd, akoff, K, hadd_s, long_list, long_count);
-      launch_hist_merge(s, K, hoff_from, hval_from, akoff, hadd_s, st->hist.off[cand], st->hist.val.p[cand], chunks_h, coff_h, scratch,
+      launch_hist_sort(s, mp.hadd, mk.akoff, K, mp.hadd_s, mk.long_list, mk.long_count);
+      launch_hist_merge(s, K, hoff_from, hval_from, mk.akoff, mp.hadd_s, st->hist.off[cand], st->hist.val.p[cand], mk.chunks_h, mk.coff_h, scratch,
                         hist_merge_chunks_bound(K, H + P_cap));
     }
     // 5. the moments
-    launch_merge_moments(s, K, replay, st->ser.off[cur], st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], alpha, state_view(st, cur),
+    launch_merge_moments(s, K, mk.replay, st->ser.off[cur], st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], alpha, state_view(st, cur),
                          state_view(st, cand), mcnt);
   }
   HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
@@ -417,65 +399,43 @@ int stream_arima_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const
   hipStream_t s = e->stream;
   const uint64_t K = v.K;
   const unsigned long long *soff = v.soff, *sval = v.sval;
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
   int rc;
-  // per key: touched u32 | len8 u32 | tidx u64[K + 1] | yoffk u64[K + 1] | tmax; per slot: key u32 | lo u32 | hi u32 | ok u8 | yoff u64 | lam | sigma | ibase
-  if ((rc = ensure(e, e->as_key, kpad * 8 + (kpad + 4) * 16 + 64 + kpad * (4 * 3 + 1 + 8 * 4) + 256)) != TAD_OK) return rc;
-  unsigned char *kb = static_cast<unsigned char *>(e->as_key.p);
-  uint32_t *touched = reinterpret_cast<uint32_t *>(kb), *len8 = touched + kpad;
-  unsigned long long *tidx = reinterpret_cast<unsigned long long *>(len8 + kpad), *yoffk = tidx + kpad + 4;
-  unsigned int *tmax_dev = reinterpret_cast<unsigned int *>(yoffk + kpad + 4);
-  unsigned char *sb = reinterpret_cast<unsigned char *>(tmax_dev) + 64;
-  ArimaSlots sl;
-  sl.yoff = reinterpret_cast<unsigned long long *>(sb);
-  sl.lam = reinterpret_cast<double *>(sl.yoff + kpad);
-  sl.sigma = sl.lam + kpad;
-  sl.ibase = reinterpret_cast<unsigned long long *>(sl.sigma + kpad);
-  sl.key = reinterpret_cast<uint32_t *>(sl.ibase + kpad);
-  sl.lo = sl.key + kpad;
-  sl.hi = sl.lo + kpad;
-  sl.ok = reinterpret_cast<uint8_t *>(sl.hi + kpad);
+  ArimaKeys ak;
+  if ((rc = carve_buf(e, e->as_key, &ak, arima_keys_layout, K)) != TAD_OK) return rc;
   unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
-  launch_as_touch(s, K, soff, hb.poff, touched, len8, tmax_dev);
-  launch_scan(s, touched, tidx, K, scratch);
-  launch_scan(s, len8, yoffk, K, scratch);
+  launch_as_touch(s, K, soff, hb.poff, ak.touched, ak.len8, ak.tmax);
+  launch_scan(s, ak.touched, ak.tidx, K, scratch);
+  launch_scan(s, ak.len8, ak.yoffk, K, scratch);
   unsigned long long hv[3] = {0, 0, 0};   // new points, slots, packed doubles
   unsigned int tmax = 0;
   HIP_TRY(e, hipMemcpyAsync(&hv[0], hb.P_dev, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipMemcpyAsync(&hv[1], tidx + K, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipMemcpyAsync(&hv[2], yoffk + K, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipMemcpyAsync(&tmax, tmax_dev, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(&hv[1], ak.tidx + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(&hv[2], ak.yoffk + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(&tmax, ak.tmax, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipMemcpyAsync(e->ctr_host, ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipStreamSynchronize(s));
   const uint64_t P = hv[0], Kt = hv[1], S8 = hv[2];
   ab->P = 0;
   if (e->ctr_host->err != 0 || P == 0) return TAD_OK;   // (the caller reads the error from the tail)
-  // per new point: pcalc f64 | rows u32 | row_off u64[P + 1] | pflag u8; the packed series: lx | ysk, each with the slack an idle lane's
-  // staged loads (k_arima_fit_list reads slot 0's offset up to the wavefront's position + 16) may touch
-  const size_t ppad = (size_t)((P + 3) & ~3ull);
-  if ((rc = ensure(e, e->as_pt, ppad * (8 + 4 + 8 + 1) + 64)) != TAD_OK) return rc;
-  double *pcalc = static_cast<double *>(e->as_pt.p);
-  uint32_t *rows = reinterpret_cast<uint32_t *>(pcalc + ppad);
-  unsigned long long *row_off = reinterpret_cast<unsigned long long *>(rows + ppad);
-  uint8_t *pflag = reinterpret_cast<uint8_t *>(row_off + ppad + 4);
-  const size_t ser = (size_t)S8 + tmax + 32;
-  if ((rc = ensure(e, e->as_ser, ser * 16)) != TAD_OK) return rc;
-  double *lx = static_cast<double *>(e->as_ser.p), *ysk = lx + ser;
-  HIP_TRY(e, hipMemsetAsync(pflag, 0, P, s));
-  HIP_TRY(e, hipMemsetAsync(ysk, 0, ser * 8, s));   // (the slack: finite values for idle lanes)
-  launch_as_prep(s, K, soff, sval, hb.poff, v.mom, tidx, yoffk, lx, ysk, sl, pcalc, pflag, ctr);
+  // per new point, and the packed series with its slack
+  ArimaPts ap;
+  ArimaSeries as;
+  if ((rc = carve_buf(e, e->as_pt, &ap, arima_pts_layout, P)) != TAD_OK) return rc;
+  if ((rc = carve_buf(e, e->as_ser, &as, arima_series_layout, S8, tmax)) != TAD_OK) return rc;
+  HIP_TRY(e, hipMemsetAsync(ap.pflag, 0, P, s));
+  HIP_TRY(e, hipMemsetAsync(as.ysk, 0, as.ser * 8, s));   // (the slack: finite values for idle lanes)
+  launch_as_prep(s, K, soff, sval, hb.poff, v.mom, ak.tidx, ak.yoffk, as.lx, as.ysk, ak.sl, ap.pcalc, ap.pflag, ctr);
   // the fits: counted per position, listed, their wavefronts laid out on the host (heaviest position first)
   const uint64_t npos = (uint64_t)tmax + 1;
-  if ((rc = ensure(e, e->as_pos, npos * (4 + 8) + 128)) != TAD_OK) return rc;   // cnt u32[npos] | (64-byte aligned) loff u64[npos + 1]
-  unsigned int *pcnt = static_cast<unsigned int *>(e->as_pos.p);
-  unsigned long long *loff = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(e->as_pos.p) + ((npos * 4 + 63) & ~63ull));
-  HIP_TRY(e, hipMemsetAsync(pcnt, 0, npos * 4, s));
-  launch_as_list(s, Kt, sl, false, pcnt, nullptr, nullptr, nullptr);
+  ArimaPos pos;
+  if ((rc = carve_buf(e, e->as_pos, &pos, arima_pos_layout, npos)) != TAD_OK) return rc;
+  HIP_TRY(e, hipMemsetAsync(pos.pcnt, 0, npos * 4, s));
+  launch_as_list(s, Kt, ak.sl, false, pos.pcnt, nullptr, nullptr, nullptr);
   std::vector<uint32_t> hcnt;
   std::vector<unsigned long long> hoff;
   std::vector<uint32_t> wave_pos;
   try { hcnt.resize(npos); hoff.resize(npos + 1); } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
-  HIP_TRY(e, hipMemcpyAsync(hcnt.data(), pcnt, npos * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(hcnt.data(), pos.pcnt, npos * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipStreamSynchronize(s));
   uint64_t nfits = 0;
   for (uint64_t p = 0; p < npos; ++p) { hoff[p] = nfits; nfits += hcnt[p]; }
@@ -486,33 +446,32 @@ int stream_arima_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const
       for (uint64_t w = 0; w < (hcnt[p] + chunk - 1) / chunk; ++w) wave_pos.push_back((uint32_t)p);
   } catch (...) { return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory"); }
   const uint64_t waves = wave_pos.size();
-  const size_t fpad = (size_t)((nfits + 3) & ~3ull);
-  if ((rc = ensure(e, e->as_fit, fpad * 8 + (size_t)(waves + 4) * 4 + 64)) != TAD_OK) return rc;
-  uint32_t *list = static_cast<uint32_t *>(e->as_fit.p), *fpos = list + fpad, *wpos = fpos + fpad;
+  ArimaFits fits;
+  if ((rc = carve_buf(e, e->as_fit, &fits, arima_fits_layout, nfits, waves)) != TAD_OK) return rc;
   if (nfits) {
-    HIP_TRY(e, hipMemcpyAsync(loff, hoff.data(), (npos + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(e, hipMemcpyAsync(wpos, wave_pos.data(), waves * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(e, hipMemsetAsync(pcnt, 0, npos * 4, s));
-    launch_as_list(s, Kt, sl, true, pcnt, loff, list, fpos);
+    HIP_TRY(e, hipMemcpyAsync(pos.loff, hoff.data(), (npos + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, hipMemcpyAsync(fits.wpos, wave_pos.data(), waves * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(e, hipMemsetAsync(pos.pcnt, 0, npos * 4, s));
+    launch_as_list(s, Kt, ak.sl, true, pos.pcnt, pos.loff, fits.list, fits.fpos);
     const size_t wsb = arima_stream_ws_bytes(nfits, npos, waves);
     if ((rc = ensure(e, e->as_ws, wsb)) != TAD_OK) return rc;
-    const FitListArgs fa{wpos, pcnt, loff, list, hb.nv, pcalc, pflag};
+    const FitListArgs fa{fits.wpos, pos.pcnt, pos.loff, fits.list, hb.nv, ap.pcalc, ap.pflag};
     // the fit yields to whole-CU jobs of other contexts like tad_run's (arima_yield_loop); this job's own claim is dropped meanwhile
     const bool held = e->hold && e->hold->held;
     if (held) e->hold->release();
     const unsigned int *yielded_dev = nullptr;
-    if (launch_arima_stream_fit(s, true, nfits, npos, waves, fpos, ysk, sl, fa, jp.maxiter, ctr, e->as_ws.p, e->eng->pause_dev, &yielded_dev, 0) != 0)
+    if (launch_arima_stream_fit(s, true, nfits, npos, waves, fits.fpos, as.ysk, ak.sl, fa, jp.maxiter, ctr, e->as_ws.p, e->eng->pause_dev, &yielded_dev, 0) != 0)
       return fail(e, TAD_ERR_HIP, "ARIMA launch failed");
     if ((rc = arima_yield_loop(e, yielded_dev, [&](uint32_t grace, const unsigned int **yd) {
-           return launch_arima_stream_fit(s, false, nfits, npos, waves, fpos, ysk, sl, fa, jp.maxiter, ctr, e->as_ws.p, e->eng->pause_dev, yd, grace);
+           return launch_arima_stream_fit(s, false, nfits, npos, waves, fits.fpos, as.ysk, ak.sl, fa, jp.maxiter, ctr, e->as_ws.p, e->eng->pause_dev, yd, grace);
          })) != TAD_OK)
       return rc;
     if (held) e->hold->acquire();
   }
   // rows of the new points (the row total lands in the job's tail)
-  launch_as_rows(s, P, hb.nk, tidx, sl.ok, pflag, jp.all_points, rows);
-  launch_scan(s, rows, row_off, P, scratch, dev_total(e));
-  ab->P = P; ab->tidx = tidx; ab->sigma = sl.sigma; ab->pcalc = pcalc; ab->pflag = pflag; ab->rows = rows; ab->row_off = row_off;
+  launch_as_rows(s, P, hb.nk, ak.tidx, ak.sl.ok, ap.pflag, jp.all_points, ap.rows);
+  launch_scan(s, ap.rows, ap.row_off, P, scratch, dev_total(e));
+  ab->P = P; ab->tidx = ak.tidx; ab->sigma = ak.sl.sigma; ab->pcalc = ap.pcalc; ab->pflag = ap.pflag; ab->rows = ap.rows; ab->row_off = ap.row_off;
   return TAD_OK;
 }
 
@@ -526,22 +485,19 @@ int state_drop_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const J
   hipStream_t s = e->stream;
   const uint64_t K = v.K, pc = hb.P_cap ? hb.P_cap : 1;
   int rc;
-  if ((rc = ensure(e, e->ds_key, drop_state_key_bytes(K))) != TAD_OK) return rc;
-  // per judged point: row u64[pc + 1] | cnt u32 | flag u8
-  if ((rc = ensure(e, e->ds_pt, (pc + 1) * 8 + pc * 4 + pc + 64)) != TAD_OK) return rc;
+  DropStateKeys dk;
+  DropPts dp;
+  if ((rc = carve_buf(e, e->ds_key, &dk, drop_state_keys_layout, K)) != TAD_OK) return rc;
+  if ((rc = carve_buf(e, e->ds_pt, &dp, drop_pts_layout, pc)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K > pc ? K : pc) * sizeof(unsigned long long))) != TAD_OK) return rc;
-  const DropStateKeys dk = drop_state_keys(e->ds_key.p, K);
-  unsigned long long *row = static_cast<unsigned long long *>(e->ds_pt.p);
-  uint32_t *cnt = reinterpret_cast<uint32_t *>(row + pc + 1);
-  uint8_t *flag = reinterpret_cast<uint8_t *>(cnt + pc);
   if (touched_only) launch_ds_route(s, K, v.soff, hb.poff, coop_min, list, lcount);
   launch_ds_stats(s, K, v.soff, v.sval, touched_only ? hb.poff : nullptr, coop_min, list, lcount, jp.drop_min_samples, dk, ctr);
   if (!touched_only) launch_moments(s, K, dk.n, dk.mean, dk.m2, dev_moments(e), ctr);   // (and n_keys / n_points)
   if (hb.P_cap) {
-    launch_ds_verdict(s, hb.nk, hb.nv, hb.P_dev, hb.P_cap, dk, jp.drop_nsigma, jp.all_points, flag, cnt);
-    launch_scan(s, cnt, row, hb.P_cap, static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
+    launch_ds_verdict(s, hb.nk, hb.nv, hb.P_dev, hb.P_cap, dk, jp.drop_nsigma, jp.all_points, dp.flag, dp.cnt);
+    launch_scan(s, dp.cnt, dp.row, hb.P_cap, static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
   }
-  db->keys = dk; db->flag = flag; db->cnt = cnt; db->row = row;
+  db->keys = dk; db->flag = dp.flag; db->cnt = dp.cnt; db->row = dp.row;
   return TAD_OK;
 }
 

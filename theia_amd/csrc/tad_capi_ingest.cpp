@@ -290,39 +290,31 @@ int tad_drop_select(tad_engine *eng, const tad_drop_flow_columns *cols, int64_t 
   const bool host = cols->memory == TAD_MEM_HOST;
   const int t32 = (cols->flags & TAD_FLAG_TIME_U32) ? 1 : 0;
   const uint64_t tiles = dsel_tiles(n);
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   // workspace: row bitmask | tile counts | tile offsets (64-bit) | scan scratch | total | a host table's columns
-  const size_t bits_b = up((size_t)((n + kDselLaneRows - 1) / kDselLaneRows) * 2), cnt_b = up((size_t)tiles * 4), off_b = up((size_t)(tiles + 1) * 8);
-  const size_t scr_b = up(scan_scratch_elems(tiles) * 8), t_b = up((size_t)n * (t32 ? 4 : 8)), c_b = up((size_t)n * 8), a_b = up((size_t)n);
-  const size_t stage = host ? 2 * a_b + t_b + (cols->flow_end_s ? t_b : 0) + 6 * c_b + (cols->keep ? a_b : 0) : 0;
-  const size_t need = bits_b + cnt_b + off_b + scr_b + 256 + stage;
+  const DselDims dims{n, (n + kDselLaneRows - 1) / kDselLaneRows, tiles, scan_scratch_elems(tiles), t32 != 0, host, cols->flow_end_s != nullptr, cols->keep != nullptr};
+  const size_t need = carved_bytes(dsel_layout, dims);
   if (need > e->ws_limit) return over_limit(e, "tad_drop_select", need);
   int rc;
-  if ((rc = ensure(e, e->dsel, need)) != TAD_OK) return rc;
-  unsigned char *p = static_cast<unsigned char *>(e->dsel.p);
-  uint16_t *bits = reinterpret_cast<uint16_t *>(p); p += bits_b;
-  uint32_t *cnt = reinterpret_cast<uint32_t *>(p); p += cnt_b;
-  unsigned long long *off = reinterpret_cast<unsigned long long *>(p); p += off_b;
-  unsigned long long *scratch = reinterpret_cast<unsigned long long *>(p); p += scr_b;
-  unsigned long long *total_dev = reinterpret_cast<unsigned long long *>(p); p += 256;
+  DselWs ws;
+  if ((rc = carve_buf(e, e->dsel, &ws, dsel_layout, dims)) != TAD_OK) return rc;
+  uint16_t *bits = ws.bits;
+  uint32_t *cnt = ws.cnt;
+  unsigned long long *off = ws.off, *scratch = ws.scratch, *total_dev = ws.total;
   DselIn A{};
   A.ia = cols->ingress_action; A.ea = cols->egress_action; A.keep = cols->keep;
   A.ts = cols->flow_start_s; A.te = cols->flow_end_s;
   const int64_t *codes[6] = {cols->src_ip, cols->src_pod_ns, cols->src_pod_name, cols->dst_ip, cols->dst_pod_ns, cols->dst_pod_name};
   if (host) {
-    auto put = [&](const void *src, size_t bytes, size_t room) -> const void * {
-      const void *d = p;
-      if (hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return nullptr;
-      p += room;
-      return d;
+    auto put = [&](void *dst, const void *src, size_t bytes) -> const void * {
+      return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) == hipSuccess ? dst : nullptr;
     };
     bool ok = true;
-    ok = ok && (A.ia = static_cast<const uint8_t *>(put(cols->ingress_action, n, a_b))) != nullptr;
-    ok = ok && (A.ea = static_cast<const uint8_t *>(put(cols->egress_action, n, a_b))) != nullptr;
-    ok = ok && (A.ts = put(cols->flow_start_s, (size_t)n * (t32 ? 4 : 8), t_b)) != nullptr;
-    if (cols->flow_end_s) ok = ok && (A.te = put(cols->flow_end_s, (size_t)n * (t32 ? 4 : 8), t_b)) != nullptr;
-    for (int c = 0; c < 6; ++c) ok = ok && (codes[c] = static_cast<const int64_t *>(put(codes[c], (size_t)n * 8, c_b))) != nullptr;
-    if (cols->keep) ok = ok && (A.keep = static_cast<const uint8_t *>(put(cols->keep, n, a_b))) != nullptr;
+    ok = ok && (A.ia = static_cast<const uint8_t *>(put(ws.ia, cols->ingress_action, n))) != nullptr;
+    ok = ok && (A.ea = static_cast<const uint8_t *>(put(ws.ea, cols->egress_action, n))) != nullptr;
+    ok = ok && (A.ts = put(ws.ts, cols->flow_start_s, (size_t)n * (t32 ? 4 : 8))) != nullptr;
+    if (cols->flow_end_s) ok = ok && (A.te = put(ws.te, cols->flow_end_s, (size_t)n * (t32 ? 4 : 8))) != nullptr;
+    for (int c = 0; c < 6; ++c) ok = ok && (codes[c] = static_cast<const int64_t *>(put(ws.codes[c], codes[c], (size_t)n * 8))) != nullptr;
+    if (cols->keep) ok = ok && (A.keep = static_cast<const uint8_t *>(put(ws.keep, cols->keep, n))) != nullptr;
     if (!ok) { (void)hipGetLastError(); return fail(e, TAD_ERR_HIP, "tad_drop_select: staging the host columns failed"); }
   }
   A.src_ip = reinterpret_cast<const long long *>(codes[0]); A.src_ns = reinterpret_cast<const long long *>(codes[1]); A.src_pod = reinterpret_cast<const long long *>(codes[2]);
@@ -338,22 +330,17 @@ int tad_drop_select(tad_engine *eng, const tad_drop_flow_columns *cols, int64_t 
   HIP_TRY(e, hipGetLastError());
   if (m > n) return fail(e, TAD_ERR_HIP, "tad_drop_select: internal error: %llu rows selected out of %llu", m, (unsigned long long)n);
   if (m == 0) { guard.p = nullptr; *out = &rp->pub; return TAD_OK; }
-  // seven columns of m values, each starting on a 32-byte boundary
-  const uint64_t stride = (m + 3) & ~3ull;
-  const size_t bytes = (size_t)stride * 8 * 7;
+  const size_t bytes = carved_bytes(drop_rows_layout, m);
   ResultBlock blk;
-  if ((rc = alloc_device_block(e, bytes, &blk)) != TAD_OK) return rc;
-  unsigned char *d = static_cast<unsigned char *>(blk.base);
-  DselOut O{reinterpret_cast<long long *>(d), reinterpret_cast<long long *>(d + stride * 8), reinterpret_cast<long long *>(d + stride * 16),
-            reinterpret_cast<long long *>(d + stride * 24), reinterpret_cast<long long *>(d + stride * 32),
-            reinterpret_cast<unsigned long long *>(d + stride * 40), reinterpret_cast<unsigned long long *>(d + stride * 48)};
+  DselOut O;
+  if ((rc = carve_block(e, &blk, &O, drop_rows_layout, m)) != TAD_OK) return rc;
   launch_dsel_emit(s, A, bits, off, O);
   void *h = nullptr;
   hipError_t hr = hipSuccess;
   if (out_memory == TAD_MEM_HOST) {
     h = malloc(bytes);
     if (!h) { (void)hipStreamSynchronize(s); release_block(e, blk.base, blk.cap); return fail(e, TAD_ERR_OUT_OF_MEMORY, "out of host memory for %zu bytes of drop rows", bytes); }
-    hr = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s);
+    hr = hipMemcpyAsync(h, blk.base, bytes, hipMemcpyDeviceToHost, s);
   }
   const hipError_t hs = hipStreamSynchronize(s);
   if (hr == hipSuccess) hr = hs;
@@ -363,22 +350,21 @@ int tad_drop_select(tad_engine *eng, const tad_drop_flow_columns *cols, int64_t 
     free(h);
     return fail(e, TAD_ERR_HIP, "tad_drop_select: %s", hipGetErrorString(hr));
   }
-  unsigned char *base = d;
   if (out_memory == TAD_MEM_HOST) {
     release_block(e, blk.base, blk.cap);
-    base = static_cast<unsigned char *>(h);
+    O = carve_at(h, drop_rows_layout, m);
     rp->block = h; rp->block_cap = bytes;
   } else {
     rp->block = blk.base; rp->block_cap = blk.cap;
   }
   rp->pub.n_rows = m;
-  rp->pub.endpoint_kind = reinterpret_cast<int64_t *>(base);
-  rp->pub.endpoint_ns = reinterpret_cast<int64_t *>(base + stride * 8);
-  rp->pub.endpoint_name = reinterpret_cast<int64_t *>(base + stride * 16);
-  rp->pub.direction = reinterpret_cast<int64_t *>(base + stride * 24);
-  rp->pub.day_s = reinterpret_cast<int64_t *>(base + stride * 32);
-  rp->pub.count = reinterpret_cast<uint64_t *>(base + stride * 40);
-  rp->pub.row = reinterpret_cast<uint64_t *>(base + stride * 48);
+  rp->pub.endpoint_kind = reinterpret_cast<int64_t *>(O.kind);
+  rp->pub.endpoint_ns = reinterpret_cast<int64_t *>(O.ns);
+  rp->pub.endpoint_name = reinterpret_cast<int64_t *>(O.name);
+  rp->pub.direction = reinterpret_cast<int64_t *>(O.dir);
+  rp->pub.day_s = reinterpret_cast<int64_t *>(O.day);
+  rp->pub.count = reinterpret_cast<uint64_t *>(O.count);
+  rp->pub.row = reinterpret_cast<uint64_t *>(O.row);
   guard.p = nullptr;
   *out = &rp->pub;
   return TAD_OK;

@@ -316,10 +316,11 @@ int sparse_sort(JobCtx *e, const Job &j, Stage0Retry &rs, Attempt &a, SparseSort
   if ((uint64_t)slots_all * 32 + tb > e->ws_limit)   // the four sort buffers count against the workspace too: fail cleanly, not in hipMalloc
     return fail(e, TAD_ERR_GRID_TOO_LARGE, "sparse Stage 0 needs %llu bytes of sort buffers for %llu row slots > workspace limit %llu",
                 (unsigned long long)(slots_all * 32 + tb), (unsigned long long)slots_all, (unsigned long long)e->ws_limit);
-  if ((rc = ensure(e, e->sp_temp, tb + 64)) != TAD_OK) return rc;
+  SparseTemp temp;
+  if ((rc = carve_buf(e, e->sp_temp, &temp, sparse_temp_layout, tb)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->sp_first, K * 4 + 64)) != TAD_OK) return rc;
   ss.tb = tb;
-  ss.d_runs = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(e->sp_temp.p) + tb);
+  ss.d_runs = temp.runs;
   HIP_TRY(e, hipMemsetAsync(ss.d_runs, 0, 16, s));
   HIP_TRY(e, hipEventRecord(e->ev[2], s));
   unsigned long long *ucomp = ss.ucomp = static_cast<unsigned long long *>(e->sp_comp_a.p), *uval = ss.uval = static_cast<unsigned long long *>(e->sp_val_a.p);
@@ -366,14 +367,12 @@ int sparse_stream_offsets(JobCtx *e, const Job &j, Attempt &a, const SparseSort 
   int rc;
   sparse_sorted_list(e, j, a, ss);
   if ((rc = ensure_key_buffers(e, K)) != TAD_OK) return rc;
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
-  if ((rc = ensure(e, e->sp_cls, kpad * 4 + (K + 1) * 8 + 64)) != TAD_OK) return rc;   // len u32[K] | poff u64[K + 1]
-  uint32_t *len = static_cast<uint32_t *>(e->sp_cls.p);
-  unsigned long long *poff = reinterpret_cast<unsigned long long *>(len + kpad);
-  HIP_TRY(e, hipMemsetAsync(len, 0, (size_t)K * 4, s));
-  launch_sparse_len(s, ss.ucomp, ss.P, static_cast<const uint32_t *>(e->sp_first.p), len);
-  launch_scan(s, len, poff, K, static_cast<unsigned long long *>(e->scan_scratch.p), nullptr);
-  a.stream_poff = poff;
+  StreamPoints sp;
+  if ((rc = carve_buf(e, e->sp_cls, &sp, stream_points_layout, K)) != TAD_OK) return rc;
+  HIP_TRY(e, hipMemsetAsync(sp.len, 0, (size_t)K * 4, s));
+  launch_sparse_len(s, ss.ucomp, ss.P, static_cast<const uint32_t *>(e->sp_first.p), sp.len);
+  launch_scan(s, sp.len, sp.poff, K, static_cast<unsigned long long *>(e->scan_scratch.p), nullptr);
+  a.stream_poff = sp.poff;
   a.stream_P = ss.P;
   a.g = Grid{nullptr, nullptr, K, 0, nullptr};
   HIP_TRY(e, hipEventRecord(e->ev[3], s));
@@ -605,8 +604,9 @@ int count_stream(JobCtx *e, const Job &j, const Attempt &a, StreamBatches *sb, u
   if (jp.algo == TAD_ALGO_ARIMA && g.K && (rc = stream_arima_batch(e, series_view(stream, stream->cur ^ 1), sb->hist, jp, j.ctr, &sb->ab)) != TAD_OK) return rc;
   if (jp.algo == TAD_ALGO_DROP && g.K) {   // tad_drop_stream: the touched keys' statistics over the candidate series, the new points' verdicts and rows
     const StateView cv = series_view(stream, stream->cur ^ 1);
-    if ((rc = state_drop_batch(e, cv, sb->hist, jp, true, win_coop_min(g.K, stream->ser.len[stream->cur] + sb->hist.P_cap),
-                               static_cast<uint32_t *>(e->hs_kcnt.p), reinterpret_cast<unsigned int *>(static_cast<uint32_t *>(e->hs_kcnt.p) + ((g.K + 3) & ~3ull)),
+    ViewRoute route;   // (hs_kcnt once more, at the size stream_history_batch gave it: nothing grows here)
+    if ((rc = carve_buf(e, e->hs_kcnt, &route, view_route_layout, g.K)) != TAD_OK) return rc;
+    if ((rc = state_drop_batch(e, cv, sb->hist, jp, true, win_coop_min(g.K, stream->ser.len[stream->cur] + sb->hist.P_cap), route.list, route.lcount,
                                j.ctr, &sb->db)) != TAD_OK)
       return rc;
   }
@@ -951,26 +951,25 @@ int run_sparse_classes(JobCtx *e, const tad_job *job, const JobParams &jp, bool 
   hipStream_t s = e->stream;
   int rc;
   const uint32_t nclass = sparse_class_count(tmax);
-  // per-key arrays: len u32 | member u32 | pts u32 | key_off u64[K + 1] | pt_off u64[K + 1]
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
-  if ((rc = ensure(e, e->sp_cls, kpad * 12 + (kpad + 4) * 16 + 64)) != TAD_OK) return rc;
+  ClassKeys ck;
+  if ((rc = carve_buf(e, e->sp_cls, &ck, class_keys_layout, K)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K ? K : 1) * sizeof(unsigned long long))) != TAD_OK) return rc;
-  uint32_t *len = static_cast<uint32_t *>(e->sp_cls.p), *member = len + kpad, *pts = member + kpad;
-  unsigned long long *key_off = reinterpret_cast<unsigned long long *>(pts + kpad), *pt_off = key_off + kpad + 4;
+  uint32_t *len = ck.len, *member = ck.member, *pts = ck.pts;
+  unsigned long long *key_off = ck.key_off, *pt_off = ck.pt_off;
   unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
   const unsigned long long *ucomp = static_cast<const unsigned long long *>(e->sp_comp_a.p), *uval = static_cast<const unsigned long long *>(e->sp_val_a.p);
   const uint32_t *first = static_cast<const uint32_t *>(e->sp_first.p);
   HIP_TRY(e, hipMemsetAsync(len, 0, (size_t)K * 4, s));
   launch_sparse_len(s, ucomp, P, first, len);
 
-  // the class tables: three 8-byte columns per point, class after class, then the key maps (class key -> original key)
+  // the class tables, class after class
   const uint64_t kmax = K < P ? K : P;   // keys with points
   ResultBlock blk;
-  if ((rc = alloc_device_block(e, (size_t)P * 24 + (size_t)kmax * 4 + 256, &blk)) != TAD_OK) return rc;
-  unsigned long long *c_key = static_cast<unsigned long long *>(blk.base);
-  long long *c_t = reinterpret_cast<long long *>(c_key + P);
-  unsigned long long *c_val = reinterpret_cast<unsigned long long *>(c_t + P);
-  uint32_t *c_map = reinterpret_cast<uint32_t *>(c_val + P);
+  ClassTables ct;
+  if ((rc = carve_block(e, &blk, &ct, class_tables_layout, P, kmax)) != TAD_OK) return rc;
+  unsigned long long *c_key = ct.key, *c_val = ct.val;
+  long long *c_t = ct.t;
+  uint32_t *c_map = ct.map;
   struct Cls { uint64_t keys, points, key0, pt0; tad_result *res; };
   std::vector<Cls> cls;
   auto release = [&]() {

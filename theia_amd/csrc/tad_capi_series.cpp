@@ -39,9 +39,8 @@ int series_emit_all(JobCtx *e, Grid g, const JobParams &jp, bool has_sigma, doub
   HIP_TRY(e, hipMemcpyAsync(e->n_pts.p, &npts, sizeof npts, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(e, hipMemcpyAsync(e->off.p, off, sizeof off, hipMemcpyHostToDevice, e->stream));
   ResultBlock blk;
-  if ((rc = alloc_device_block(e, result_bytes(n, true), &blk)) != TAD_OK) return rc;
   OutRows o;
-  carve(blk.base, n, true, &o);
+  if ((rc = carve_block(e, &blk, &o, result_layout, n, true)) != TAD_OK) return rc;
   JobParams all = jp;
   all.all_points = true;
   emit_rows(e, g, make_lattice(0, 1, n), all, o);

@@ -210,21 +210,6 @@ int import_segments(tad_engine *eng, tad_state *st, const Kind &kd, const char *
 
 namespace tadh {
 
-size_t state_bytes(uint64_t K) { return (size_t)K * (4 + 8 * 4 + 1) + 64; }
-
-// the arrays of K keys' running state inside one block of state_bytes(K) bytes
-StreamState stream_view(void *block, uint64_t K) {
-  unsigned char *b = static_cast<unsigned char *>(block);
-  StreamState v;
-  v.avg = reinterpret_cast<double *>(b);
-  v.m2 = v.avg + K;
-  v.ewma = v.m2 + K;
-  v.last_t = reinterpret_cast<long long *>(v.ewma + K);
-  v.n = reinterpret_cast<uint32_t *>(v.last_t + K);
-  v.seen = reinterpret_cast<unsigned char *>(v.n + K);
-  return v;
-}
-
 StreamState state_view(const tad_state *st, int which) { return stream_view(st->block[which], st->K); }
 
 // copy `which` of a series state as the detectors of tad_run_state read it (the times and the history where the state has them)
@@ -500,24 +485,20 @@ int tad_state_trim(tad_engine *eng, tad_state *st, uint64_t keep_points, int64_t
   JobCtx *e = call.e;
   hipStream_t s = e->stream;
   const double alpha = ewma_alpha == 0.0 ? 0.5 : ewma_alpha;
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
-  if ((rc = ensure(e, e->hs_kcnt, kpad * 12 + 64)) != TAD_OK) return rc;        // retained | evicted | chunks (later the long-sort list) | count
-  if ((rc = ensure(e, e->hs_koff, (kpad + 4) * 16)) != TAD_OK) return rc;       // evicted offsets | chunk offsets, K + 1 each
+  TrimKeys tk;
+  if ((rc = carve_bufs(e, e->hs_kcnt, e->hs_koff, &tk, trim_keys_layout, K)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K) * sizeof(unsigned long long))) != TAD_OK) return rc;
-  uint32_t *rcnt = static_cast<uint32_t *>(e->hs_kcnt.p), *ecnt = rcnt + kpad, *chunks = ecnt + kpad;
-  unsigned int *long_count = reinterpret_cast<unsigned int *>(chunks + kpad);
-  unsigned long long *eoff = static_cast<unsigned long long *>(e->hs_koff.p), *coff = eoff + kpad + 4;
   unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
   const Segments &ser = st->ser, &hist = st->hist;
   const long long *t_cur = st->times ? st->ser_times.p[cur] : nullptr;
   // 1. what every key keeps; the candidate series offsets, the packed evicted offsets and the chunk offsets
-  launch_trim_keep(s, K, ser.off[cur], keep_from_t != 0 ? t_cur : nullptr, keep_points, (long long)keep_from_t, rcnt, ecnt, chunks);
-  launch_scan(s, rcnt, ser.off[cand], K, scratch);
-  launch_scan(s, ecnt, eoff, K, scratch);
-  launch_scan(s, chunks, coff, K, scratch);
+  launch_trim_keep(s, K, ser.off[cur], keep_from_t != 0 ? t_cur : nullptr, keep_points, (long long)keep_from_t, tk.rcnt, tk.ecnt, tk.chunks);
+  launch_scan(s, tk.rcnt, ser.off[cand], K, scratch);
+  launch_scan(s, tk.ecnt, tk.eoff, K, scratch);
+  launch_scan(s, tk.chunks, tk.coff, K, scratch);
   HIP_TRY(e, hipGetLastError());
   HIP_TRY(e, hipMemcpyAsync(e->tail_host, ser.off[cand] + K, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipMemcpyAsync(e->tail_host + 8, eoff + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(e->tail_host + 8, tk.eoff + K, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipStreamSynchronize(s));
   unsigned long long kept = 0, evicted = 0;
   memcpy(&kept, e->tail_host, 8);
@@ -534,14 +515,14 @@ int tad_state_trim(tad_engine *eng, tad_state *st, uint64_t keep_points, int64_t
   }
   // 3. the retained suffixes (and the evicted prefixes); 4. the history without the evicted values; 5. the moments
   const uint64_t bound = trim_chunks_bound(K, S);
-  launch_trim_copy(s, bound, coff, K, ser.off[cur], ser.val.p[cur], t_cur, ser.off[cand], ser.val.p[cand], st->times ? st->ser_times.p[cand] : nullptr,
-                   eoff, ev);
+  launch_trim_copy(s, bound, tk.coff, K, ser.off[cur], ser.val.p[cur], t_cur, ser.off[cand], ser.val.p[cand], st->times ? st->ser_times.p[cand] : nullptr,
+                   tk.eoff, ev);
   if (st->history) {
     HIP_TRY(e, hipMemcpyAsync(hist.off[cand], ser.off[cand], (K + 1) * 8, hipMemcpyDeviceToDevice, s));
-    launch_hist_sort(s, ev, eoff, K, es, chunks, long_count);
-    launch_hist_subtract(s, bound, coff, K, hist.off[cur], hist.val.p[cur], eoff, es, hist.off[cand], hist.val.p[cand], true);
+    launch_hist_sort(s, ev, tk.eoff, K, es, tk.chunks, tk.long_count);
+    launch_hist_subtract(s, bound, tk.coff, K, hist.off[cur], hist.val.p[cur], tk.eoff, es, hist.off[cand], hist.val.p[cand], true);
   }
-  launch_trim_moments(s, K, rcnt, ecnt, ser.off[cand], ser.val.p[cand], alpha, state_view(st, cur), state_view(st, cand));
+  launch_trim_moments(s, K, tk.rcnt, tk.ecnt, ser.off[cand], ser.val.p[cand], alpha, state_view(st, cur), state_view(st, cand));
   HIP_TRY(e, hipGetLastError());
   HIP_TRY(e, hipStreamSynchronize(s));
   // everything succeeded: the candidate becomes current; the old arenas, now the candidates, are given back when far too big for it
@@ -568,40 +549,35 @@ int tad_state_compact(tad_engine *eng, tad_state *st, int64_t retire_before_t, u
   JobCtx *e = call.e;
   hipStream_t s = e->stream;
   const bool host_remap = remap_memory == TAD_MEM_HOST;
-  // workspace: hs_kcnt = live | series lengths | history lengths | series chunks | history chunks | counters; hs_koff = new ids | candidate
-  // series offsets | candidate history offsets | series chunk offsets | history chunk offsets, K + 1 each; in_key = a host remap's staging
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
-  const size_t cnt_bytes = kpad * 20 + 64, off_bytes = (kpad + 4) * 40, scan_bytes = scan_scratch_elems(K) * sizeof(unsigned long long);
-  const size_t need = cnt_bytes + off_bytes + scan_bytes + (host_remap ? (size_t)K * 8 : 0);
+  // workspace: the per-key counts and offsets of CompactKeys (hs_kcnt / hs_koff), the scan scratch; in_key = a host remap's staging
+  const size_t scan_bytes = scan_scratch_elems(K) * sizeof(unsigned long long);
+  const size_t need = compact_workspace_bytes(K, scan_bytes, host_remap);
   if (need > e->ws_limit)
     return fail(e, TAD_ERR_GRID_TOO_LARGE, "tad_state_compact needs %llu bytes of scratch > workspace limit %llu; state unchanged", (unsigned long long)need,
                 (unsigned long long)e->ws_limit);
-  if ((rc = ensure(e, e->hs_kcnt, cnt_bytes)) != TAD_OK || (rc = ensure(e, e->hs_koff, off_bytes)) != TAD_OK ||
-      (rc = ensure(e, e->scan_scratch, scan_bytes)) != TAD_OK || (host_remap && (rc = ensure(e, e->in_key, (size_t)K * 8)) != TAD_OK))
+  CompactKeys ck;
+  if ((rc = carve_bufs(e, e->hs_kcnt, e->hs_koff, &ck, compact_keys_layout, K)) != TAD_OK || (rc = ensure(e, e->scan_scratch, scan_bytes)) != TAD_OK ||
+      (host_remap && (rc = ensure(e, e->in_key, (size_t)K * 8)) != TAD_OK))
     return rc;
-  uint32_t *live = static_cast<uint32_t *>(e->hs_kcnt.p), *slen = live + kpad, *hlen = slen + kpad, *schunks = hlen + kpad, *hchunks = schunks + kpad;
-  CompactCounters *cc = reinterpret_cast<CompactCounters *>(hchunks + kpad);
-  unsigned long long *newid = static_cast<unsigned long long *>(e->hs_koff.p), *sscan = newid + kpad + 4, *hscan = sscan + kpad + 4,
-                     *scoff = hscan + kpad + 4, *hcoff = scoff + kpad + 4;
   unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
   unsigned long long *d_remap = host_remap ? static_cast<unsigned long long *>(e->in_key.p) : reinterpret_cast<unsigned long long *>(remap);
   const StreamState cur_view = state_view(st, cur);
   const Segments &ser = st->ser, &hist = st->hist;
   // 1. who survives, what it keeps; 2. the new ids, the candidate offsets and the chunk offsets; one round trip for the totals
   HIP_TRY(e, hipEventRecord(e->ev[0], s));
-  HIP_TRY(e, hipMemsetAsync(cc, 0, sizeof(CompactCounters), s));
-  launch_compact_mark(s, K, cur_view, st->series ? ser.off[cur] : nullptr, st->history ? hist.off[cur] : nullptr, (long long)retire_before_t, live,
-                      slen, hlen, schunks, hchunks, cc);
-  launch_scan(s, live, newid, K, scratch);
-  launch_scan(s, slen, sscan, K, scratch);
-  launch_scan(s, hlen, hscan, K, scratch);
-  launch_scan(s, schunks, scoff, K, scratch);
-  launch_scan(s, hchunks, hcoff, K, scratch);
+  HIP_TRY(e, hipMemsetAsync(ck.cc, 0, sizeof(CompactCounters), s));
+  launch_compact_mark(s, K, cur_view, st->series ? ser.off[cur] : nullptr, st->history ? hist.off[cur] : nullptr, (long long)retire_before_t, ck.live,
+                      ck.slen, ck.hlen, ck.schunks, ck.hchunks, ck.cc);
+  launch_scan(s, ck.live, ck.newid, K, scratch);
+  launch_scan(s, ck.slen, ck.sscan, K, scratch);
+  launch_scan(s, ck.hlen, ck.hscan, K, scratch);
+  launch_scan(s, ck.schunks, ck.scoff, K, scratch);
+  launch_scan(s, ck.hchunks, ck.hcoff, K, scratch);
   HIP_TRY(e, hipGetLastError());
   unsigned long long *tot = reinterpret_cast<unsigned long long *>(e->tail_host);
-  const unsigned long long *tails[5] = {newid + K, sscan + K, hscan + K, scoff + K, hcoff + K};
+  const unsigned long long *tails[5] = {ck.newid + K, ck.sscan + K, ck.hscan + K, ck.scoff + K, ck.hcoff + K};
   for (int i = 0; i < 5; ++i) HIP_TRY(e, hipMemcpyAsync(tot + i, tails[i], 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipMemcpyAsync(tot + 5, cc, 24, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(tot + 5, ck.cc, 24, hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipStreamSynchronize(s));
   const uint64_t m = tot[0], skept = tot[1], hkept = tot[2], s_chunks = tot[3], h_chunks = tot[4];
   const uint64_t n_unseen = tot[5], n_idle = tot[6], dropped = tot[7];
@@ -623,7 +599,7 @@ int tad_state_compact(tad_engine *eng, tad_state *st, int64_t retire_before_t, u
     return TAD_OK;
   };
   if (m == K) {   // nothing retired: the identity, the state as it is
-    launch_compact_keys(s, K, live, newid, sscan, hscan, false, cur_view, cur_view, nullptr, nullptr, d_remap);
+    launch_compact_keys(s, K, ck.live, ck.newid, ck.sscan, ck.hscan, false, cur_view, cur_view, nullptr, nullptr, d_remap);
     if ((rc = remap_out()) != TAD_OK) return rc;
     cs.num_keys = K;
     cs.bytes_after = cs.bytes_before;
@@ -652,12 +628,12 @@ int tad_state_compact(tad_engine *eng, tad_state *st, int64_t retire_before_t, u
   // the candidate arenas at their new size (the trim's rule): an allocation failure leaves the state as it is
   if (gather && (rc = size_arenas(e, st, cand, skept, hkept, true, "tad_state_compact")) != TAD_OK) { drop_fresh(); return rc; }
   // 4. the survivors' moments and offsets, remap; 5. their segments
-  launch_compact_keys(s, K, live, newid, sscan, hscan, true, cur_view, stream_view(fresh.block[to], Km), st->series ? fresh.ser.off[to] : nullptr,
+  launch_compact_keys(s, K, ck.live, ck.newid, ck.sscan, ck.hscan, true, cur_view, stream_view(fresh.block[to], Km), st->series ? fresh.ser.off[to] : nullptr,
                       st->history ? fresh.hist.off[to] : nullptr, d_remap);
   if (gather && st->series)
-    launch_compact_copy(s, s_chunks, scoff, K, ser.off[cur], ser.val.p[cur], st->times ? st->ser_times.p[cur] : nullptr, sscan, ser.val.p[cand],
+    launch_compact_copy(s, s_chunks, ck.scoff, K, ser.off[cur], ser.val.p[cur], st->times ? st->ser_times.p[cur] : nullptr, ck.sscan, ser.val.p[cand],
                         st->times ? st->ser_times.p[cand] : nullptr);
-  if (gather && st->history) launch_compact_copy(s, h_chunks, hcoff, K, hist.off[cur], hist.val.p[cur], nullptr, hscan, hist.val.p[cand], nullptr);
+  if (gather && st->history) launch_compact_copy(s, h_chunks, ck.hcoff, K, hist.off[cur], hist.val.p[cur], nullptr, ck.hscan, hist.val.p[cand], nullptr);
   if ((rc = remap_out()) != TAD_OK) { drop_fresh(); return rc; }
   // everything succeeded: the fresh blocks and offsets replace the old ones; after a gather the candidate arenas become current and the
   // old ones, now the candidates, are given back when far too big

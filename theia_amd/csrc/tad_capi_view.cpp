@@ -44,11 +44,11 @@ int view_detect(JobCtx *e, const StateView &v, const JobParams &jp, ViewJob *vj)
   int rc;
   vj->off = v.soff;   // EWMA with every point: the row offsets are the series offsets
   if (P == 0) return TAD_OK;
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
-  if ((rc = ensure(e, e->hs_kcnt, kpad * 4 + 64)) != TAD_OK) return rc;   // the long keys' list | its length
+  ViewRoute route;
+  if ((rc = carve_buf(e, e->hs_kcnt, &route, view_route_layout, K)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K > P ? K : P) * sizeof(unsigned long long))) != TAD_OK) return rc;
-  vj->list = static_cast<uint32_t *>(e->hs_kcnt.p);
-  vj->lcount = reinterpret_cast<unsigned int *>(vj->list + kpad);
+  vj->list = route.list;
+  vj->lcount = route.lcount;
   vj->coop_min = win_coop_min(K, P);
   launch_win_route(s, K, v.soff, v.st, vj->coop_min, vj->list, vj->lcount, tmin_dev);
   if (jp.algo != TAD_ALGO_DROP) launch_moments(s, K, v.mom.n, v.mom.avg, v.mom.m2, dev_moments(e), ctr);   // (and n_keys / n_points)
@@ -122,29 +122,6 @@ int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem o
 // window_bounds (every key's bounds, the view's offsets, the window's point total — one host round trip) and window_gather (the view
 // itself, which run_view_locked then judges).  Both read the state's CURRENT copies and write workspace only: wv_key and wv_pts hold the
 // view; run_view_locked resizes neither.
-struct WinKeys {   // wv_key: per key wbeg | wlen | ecnt | chunks (later the long-sort list) u32 each | the list's length | woff | coff | eoff u64[K + 1] each | moments
-  uint32_t *wbeg, *wlen, *ecnt, *chunks;
-  unsigned int *long_count;
-  unsigned long long *woff, *coff, *eoff;
-  StreamState wmom;
-};
-
-size_t win_key_bytes(uint64_t K) {
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
-  return kpad * 16 + 64 + (kpad + 4) * 24;
-}
-
-WinKeys win_keys(JobCtx *e, uint64_t K) {
-  const size_t kpad = (size_t)((K + 3) & ~3ull);
-  WinKeys w;
-  w.wbeg = static_cast<uint32_t *>(e->wv_key.p); w.wlen = w.wbeg + kpad; w.ecnt = w.wlen + kpad; w.chunks = w.ecnt + kpad;
-  w.long_count = reinterpret_cast<unsigned int *>(w.chunks + kpad);
-  w.woff = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(w.long_count) + 64);
-  w.coff = w.woff + kpad + 4; w.eoff = w.coff + kpad + 4;
-  w.wmom = stream_view(static_cast<unsigned char *>(e->wv_key.p) + win_key_bytes(K), K);
-  return w;
-}
-
 // 1. every key's bounds; the view's offsets and the chunk offsets; *P = the window's point total.  keep (device, K bytes, or NULL): the
 // key selection of tad_run_state_keys / tad_drop_state_keys — a key that is not selected gets an empty window
 int window_bounds(JobCtx *e, const tad_state *st, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *keep, uint64_t *P) {
@@ -152,9 +129,9 @@ int window_bounds(JobCtx *e, const tad_state *st, int64_t from_t, int64_t to_t, 
   const uint64_t K = st->K;
   const StateView whole = series_view(st, st->cur);
   int rc;
-  if ((rc = ensure(e, e->wv_key, win_key_bytes(K) + state_bytes(K))) != TAD_OK) return rc;
+  WinKeys w;
+  if ((rc = carve_buf(e, e->wv_key, &w, win_keys_layout, K)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K) * sizeof(unsigned long long))) != TAD_OK) return rc;
-  const WinKeys w = win_keys(e, K);
   unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
   launch_win_bounds(s, K, whole.soff, whole.st, (long long)from_t, (long long)to_t, keep_points, keep, w.wbeg, w.wlen, w.ecnt, w.chunks);
   launch_scan(s, w.wlen, w.woff, K, scratch);
@@ -173,7 +150,7 @@ int window_gather(JobCtx *e, const tad_state *st, const tad_job *job, uint64_t P
   const uint64_t K = st->K;
   const StateView whole = series_view(st, st->cur);
   const uint64_t S = whole.P;
-  const WinKeys w = win_keys(e, K);
+  const WinKeys w = carve_at(e->wv_key.p, win_keys_layout, K);   // (as window_bounds placed it)
   unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
   int rc;
   *v = StateView{};
@@ -181,10 +158,10 @@ int window_gather(JobCtx *e, const tad_state *st, const tad_job *job, uint64_t P
   v->P = P;
   if (P != 0) {
     const bool dbscan = job->algo == TAD_ALGO_DBSCAN;
-    if ((rc = ensure(e, e->wv_pts, P * (dbscan ? 24 : 16))) != TAD_OK) return rc;
-    unsigned long long *wval = static_cast<unsigned long long *>(e->wv_pts.p);
-    long long *wt = reinterpret_cast<long long *>(wval + P);
-    unsigned long long *wh = wval + 2 * P, *ev = nullptr, *es = nullptr;
+    WinPts wp;
+    if ((rc = carve_buf(e, e->wv_pts, &wp, win_pts_layout, P, dbscan)) != TAD_OK) return rc;
+    unsigned long long *wval = wp.wval, *wh = wp.wh, *ev = nullptr, *es = nullptr;
+    long long *wt = wp.wt;
     if (subtract) {
       if ((rc = ensure(e, e->hs_val, (S - P) * 8)) != TAD_OK) return rc;
       if ((rc = ensure(e, e->hs_sorted, (S - P) * 8)) != TAD_OK) return rc;

@@ -253,22 +253,6 @@ __global__ __launch_bounds__(kDsBlock) void k_ds_emit(const unsigned long long *
 // ---- launchers ----
 static inline unsigned ds_blocks(uint64_t lanes) { return (unsigned)((lanes + kDsBlock - 1) / kDsBlock); }
 
-size_t drop_state_key_bytes(uint64_t K) {
-  const size_t kpad = (size_t)((K + 7) & ~7ull);
-  return kpad * (3 * sizeof(double) + sizeof(uint32_t) + 1) + 64;
-}
-
-DropStateKeys drop_state_keys(void *mem, uint64_t K) {
-  const size_t kpad = (size_t)((K + 7) & ~7ull);
-  DropStateKeys d;
-  d.mean = static_cast<double *>(mem);
-  d.std = d.mean + kpad;
-  d.m2 = d.std + kpad;
-  d.n = reinterpret_cast<uint32_t *>(d.m2 + kpad);
-  d.ok = reinterpret_cast<uint8_t *>(d.n + kpad);
-  return d;
-}
-
 void launch_ds_route(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *poff, unsigned long long coop_min, uint32_t *list,
                      unsigned int *count) {
   hipMemsetAsync(count, 0, sizeof(unsigned int), s);

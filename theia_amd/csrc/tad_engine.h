@@ -25,6 +25,7 @@
 #include <optional>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -74,9 +75,30 @@ struct tad_engine {
   std::vector<FreeBlock> free_blocks;  // recycled device result blocks (a result may be freed from any thread)
 };
 
+// The grow-only device scratch of a context: DevBuf members and NOTHING ELSE, so that for_each_buf walks the struct as an array and a new
+// buffer is trimmed and freed without being listed anywhere.  The static_assert below only catches a member whose size breaks the
+// multiple: a pointer pair or any other 16-byte member would pass it and be walked (and hipFree'd) as a DevBuf.  This comment is the guard.
+struct JobBufs {
+  DevBuf grid_val, grid_flag, sigma, n_pts, n_anom, off, scan_scratch, calc, counters, meta, aux, key_mean, key_m2;   // counters: the job tail (kTailBytes)
+  DevBuf in_key, in_key2, in_te, in_ts, in_val;
+  DevBuf rcp_table;           // rcp_table[n] = RN(1/n), n = 0..rcp_n-1
+  DevBuf binhist, part_total, part_start, part_offs32, recs, ovf, slices;  // Stage 0 v2 (ovf: 8-byte count + overflow records)
+  DevBuf sp_comp_a, sp_comp_b, sp_val_a, sp_val_b, sp_temp, sp_first, sp_times;  // Stage 0 sparse (sort + rank grid)
+  DevBuf sp_cls;                                                                  // Stage 0 sparse, length classes: per-key class arrays
+  DevBuf hs_key, hs_t, hs_val, hs_sorted, hs_noise, hs_cnt, hs_row, hs_koff, hs_kcnt;   // a history batch: new points, sorted values, verdicts, rows, offsets
+  DevBuf wv_key, wv_pts;   // tad_run_state_window's view: per key (bounds, offsets, moments) | per window point (values, times, sorted values)
+  DevBuf mg_pts, mg_keys, mg_hist;   // tad_state_merge: per batch point | per key | the history between its subtract and its merge
+  DevBuf as_key, as_pt, as_ser, as_fit, as_pos, as_ws;   // a stream ARIMA batch: per key | per new point | packed series | per fit | per position | fit workspace
+  DevBuf ds_key, ds_pt;   // tad_drop_state / tad_drop_stream: per key (mean, std, m2, n, ok) | per judged point (verdict, rows, row offset)
+  DevBuf dsel;            // tad_drop_select: row bitmask | tile counts | tile offsets | scan scratch | total | a host table's staged columns
+  DevBuf part_fin;                                                                // Stage 0 v2, sampled histogram: final cursors of the (workgroup, partition) regions
+  DevBuf ovf_keys;                                                                // Stage 0 v2, settle mode: bitmap of the keys with a value on the overflow list
+};
+static_assert(std::is_standard_layout<JobBufs>::value && sizeof(JobBufs) % sizeof(DevBuf) == 0, "JobBufs holds DevBuf members only");
+
 // One job in flight.  Everything below is touched by the thread that holds the context only (busy == true), except done / total / id.
 struct PauseHold;
-struct JobCtx {
+struct JobCtx : JobBufs {
   tad_engine *eng = nullptr;
   PauseHold *hold = nullptr;   // the running job's claim on whole CUs (run_job); NULL for the small entry points
   int index = 0;               // position in eng->ctxs (tad_stats.job_context)
@@ -89,25 +111,10 @@ struct JobCtx {
   tad_plan plan{};             // the engine's plan when the job was admitted
   std::atomic<int32_t> done{0}, total{0};
   char id[64] = {};            // tad_job.id of the running job (tad_job_progress); under eng->mu
-  // grow-only device scratch
-  DevBuf grid_val, grid_flag, sigma, n_pts, n_anom, off, scan_scratch, calc, counters, meta, aux, key_mean, key_m2;   // counters: the job tail (kTailBytes)
-  DevBuf in_key, in_key2, in_te, in_ts, in_val;
-  DevBuf rcp_table;           // rcp_table[n] = RN(1/n), n = 0..rcp_n-1
-  uint64_t rcp_n = 0;
-  DevBuf binhist, part_total, part_start, part_offs32, recs, ovf, slices;  // Stage 0 v2 (ovf: 8-byte count + overflow records)
-  DevBuf sp_comp_a, sp_comp_b, sp_val_a, sp_val_b, sp_temp, sp_first, sp_times;  // Stage 0 sparse (sort + rank grid)
-  DevBuf sp_cls;                                                                  // Stage 0 sparse, length classes: per-key class arrays
-  DevBuf hs_key, hs_t, hs_val, hs_sorted, hs_noise, hs_cnt, hs_row, hs_koff, hs_kcnt;   // a history batch: new points, sorted values, verdicts, rows, offsets
-  DevBuf wv_key, wv_pts;   // tad_run_state_window's view: per key (bounds, offsets, moments) | per window point (values, times, sorted values)
-  DevBuf mg_pts, mg_keys, mg_hist;   // tad_state_merge: per batch point | per key | the history between its subtract and its merge
+  uint64_t rcp_n = 0;             // entries of rcp_table
   struct MergeCall *merge = nullptr;   // set while the context runs a tad_state_merge batch (run_job_locked's merge mode)
-  DevBuf as_key, as_pt, as_ser, as_fit, as_pos, as_ws;   // a stream ARIMA batch: per key | per new point | packed series | per fit | per position | fit workspace
-  DevBuf ds_key, ds_pt;   // tad_drop_state / tad_drop_stream: per key (mean, std, m2, n, ok) | per judged point (verdict, rows, row offset)
-  DevBuf dsel;            // tad_drop_select: row bitmask | tile counts | tile offsets | scan scratch | total | a host table's staged columns
   int arima_relaunches = 0;       // times the running job's ARIMA fit was relaunched after it had yielded to whole-CU jobs (tad_stats.arima_relaunches)
   bool sp_by_partition = false;   // the running job's sparse Stage 0 went through the partition pass + LDS sort (stage0_path 8 / 9 / 10 instead of 4 / 6 / 7)
-  DevBuf part_fin;                                                                // Stage 0 v2, sampled histogram: final cursors of the (workgroup, partition) regions
-  DevBuf ovf_keys;                                                                // Stage 0 v2, settle mode: bitmap of the keys with a value on the overflow list
   hipEvent_t ev[8] = {};
   tad::MetaPartial *meta_host = nullptr;    // pinned
   // The job's tail — what the host reads when a job's kernels are done — is ONE block on the device (e->counters: DevCounters |
@@ -222,21 +229,39 @@ int fail(std::nullptr_t, int code, const char *fmt, ...);
 
 // every grow-only buffer of a context, for trimming and teardown
 template <typename F> void for_each_buf(JobCtx *c, F f) {
-  DevBuf *bufs[] = {&c->grid_val, &c->grid_flag, &c->sigma, &c->n_pts, &c->n_anom, &c->off, &c->scan_scratch, &c->calc, &c->counters, &c->meta, &c->aux,
-                    &c->key_mean, &c->key_m2, &c->rcp_table, &c->binhist, &c->part_total, &c->part_start, &c->part_offs32, &c->recs, &c->ovf, &c->slices,
-                    &c->sp_comp_a, &c->sp_comp_b, &c->sp_val_a, &c->sp_val_b, &c->sp_temp, &c->sp_first, &c->sp_times, &c->sp_cls, &c->part_fin, &c->ovf_keys,
-                    &c->in_key, &c->in_key2, &c->in_te, &c->in_ts, &c->in_val,
-                    &c->hs_key, &c->hs_t, &c->hs_val, &c->hs_sorted, &c->hs_noise, &c->hs_cnt, &c->hs_row, &c->hs_koff, &c->hs_kcnt,
-                    &c->mg_pts, &c->mg_keys, &c->mg_hist,
-                    &c->wv_key, &c->wv_pts,
-                    &c->as_key, &c->as_pt, &c->as_ser, &c->as_fit, &c->as_pos, &c->as_ws,
-                    &c->ds_key, &c->ds_pt, &c->dsel};
-  for (DevBuf *b : bufs) f(*b);
+  DevBuf *bufs = reinterpret_cast<DevBuf *>(static_cast<JobBufs *>(c));
+  for (size_t i = 0; i < sizeof(JobBufs) / sizeof(DevBuf); ++i) f(bufs[i]);
 }
 
 void drop_buffers(JobCtx *c);
 void trim_idle(tad_engine *eng, JobCtx *self);
 int ensure(JobCtx *e, DevBuf &b, size_t bytes);          // grow-only device scratch
+// A workspace block with more than one array (tad_carve.h): its layout function measures it with a walker that has no base, the buffer
+// grows, the same function places the arrays.  carve_bufs: a layout over two buffers (per-key counts, per-key offsets).
+template <typename L, typename... A, typename... D> size_t carved_bytes(L (*layout)(Carve &, A...), D... dims) {
+  Carve m(nullptr);
+  layout(m, dims...);
+  return m.bytes();
+}
+template <typename L, typename... A, typename... D> L carve_at(void *base, L (*layout)(Carve &, A...), D... dims) {
+  Carve c(base);
+  return layout(c, dims...);
+}
+template <typename L, typename... A, typename... D> int carve_buf(JobCtx *e, DevBuf &b, L *out, L (*layout)(Carve &, A...), D... dims) {
+  const int rc = ensure(e, b, carved_bytes(layout, dims...));
+  if (rc == TAD_OK) *out = carve_at(b.p, layout, dims...);
+  return rc;
+}
+template <typename L, typename... A, typename... D>
+int carve_bufs(JobCtx *e, DevBuf &b0, DevBuf &b1, L *out, L (*layout)(Carve &, Carve &, A...), D... dims) {
+  Carve m0(nullptr), m1(nullptr);
+  layout(m0, m1, dims...);
+  int rc;
+  if ((rc = ensure(e, b0, m0.bytes())) != TAD_OK || (rc = ensure(e, b1, m1.bytes())) != TAD_OK) return rc;
+  Carve c0(b0.p), c1(b1.p);
+  *out = layout(c0, c1, dims...);
+  return TAD_OK;
+}
 // hipMalloc that gives the idle contexts' buffers and the recycled result blocks back to the device (trim_idle) before it fails; *p = NULL then
 hipError_t dev_alloc(JobCtx *e, void **p, size_t bytes);
 // the refusal of a call whose scratch would pass the workspace limit: "<who> needs <need> bytes of scratch > workspace limit <limit><suffix>"
@@ -324,10 +349,13 @@ struct ResultBlock {
   size_t cap = 0;
 };
 
-// every column of a result block starts on a 32-byte boundary (stride = rows rounded up to 4): k_emit stores four rows at a time
-size_t result_bytes(uint64_t rows, bool with_anomaly);
-void carve(void *base, uint64_t rows, bool with_anomaly, OutRows *o);
 int alloc_device_block(JobCtx *e, size_t bytes, ResultBlock *rb);
+// a recycled or new device block of the layout's size, and its arrays
+template <typename L, typename... A, typename... D> int carve_block(JobCtx *e, ResultBlock *rb, L *out, L (*layout)(Carve &, A...), D... dims) {
+  const int rc = alloc_device_block(e, carved_bytes(layout, dims...), rb);
+  if (rc == TAD_OK) *out = carve_at(rb->base, layout, dims...);
+  return rc;
+}
 
 struct ResultPriv {  // lives right behind the public struct
   tad_result pub;
@@ -448,8 +476,8 @@ int arima_yield_loop(JobCtx *e, const unsigned int *yielded_dev, Relaunch relaun
 }
 
 // (tad_capi_state.cpp) shared with the batches on a state (tad_capi.cpp) and the read-only jobs on it (tad_capi_view.cpp)
-size_t state_bytes(uint64_t K);                              // one block of K keys' running state
-StreamState stream_view(void *block, uint64_t K);            // the arrays inside such a block
+inline size_t state_bytes(uint64_t K) { return carved_bytes(stream_state_layout, K); }                          // one block of K keys' running state
+inline StreamState stream_view(void *block, uint64_t K) { return carve_at(block, stream_state_layout, K); }     // the arrays inside such a block
 StreamState state_view(const tad_state *st, int which);
 StateView series_view(const tad_state *st, int which);       // copy `which` as the detectors of tad_run_state read it
 int state_grow_candidates(JobCtx *e, tad_state *st, uint64_t P_cap);   // room for a batch of at most P_cap new points

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "tad.h"
+#include "tad_carve.h"     // the workspace blocks: their pointer structs (OutRows, StreamState, ArimaSlots, ...) and layouts
 #include "tad_dev_err.h"   // DEV_ERR_*: what a kernel raises in DevCounters::err
 
 namespace tad {
@@ -61,15 +62,6 @@ enum : int { kColKey32 = 1, kColTime32 = 2 };
 struct RowFilter {
   int64_t start_time;  // 0 = unset
   int64_t end_time;    // 0 = unset
-};
-
-struct OutRows {
-  unsigned long long *key_id;
-  long long *flow_end_s;
-  double *throughput;
-  double *algo_calc;
-  double *stddev;
-  uint8_t *anomaly;  // only with TAD_FLAG_EMIT_ALL_POINTS
 };
 
 // Opt a kernel into more than 64 KB of dynamic LDS.  The attribute is per (function, device) in the HIP runtime and a
@@ -262,13 +254,7 @@ void launch_emit(hipStream_t s, Grid g, Lattice lat, int kind, bool all_points, 
                  int ewma_emit = 0, uint32_t ewma_emit_rows = 0);  // tad_plan: 1 = lane-per-key k_emit for the EWMA job; LDS rows per wavefront of the staged emit
 void launch_emit_points(hipStream_t s, Grid g, Lattice lat, const unsigned long long *off, unsigned long long *out_key,
                         long long *out_t, unsigned long long *out_val);
-// streaming EWMA: per-key running state (tad_state); k_stream continues the recurrences over the new grid
-struct StreamState {
-  uint32_t *n;
-  double *avg, *m2, *ewma;
-  long long *last_t;
-  unsigned char *seen;  // 0 until the key has seen a point
-};
+// streaming EWMA: per-key running state (tad_state, StreamState in tad_carve.h); k_stream continues the recurrences over the new grid
 // one key's running state in registers and the per-point step of the streaming detectors: k_stream, k_stream_points and the moments
 // replay of tad_state_trim (k_trim_moments) share this one source for the arithmetic
 struct StreamAcc {
@@ -470,9 +456,6 @@ void launch_win_gather(hipStream_t s, uint64_t chunks_bound, const unsigned long
 // history.  A pure function of the two totals: 2 * window_points <= state_points
 bool win_hist_by_sort(uint64_t window_points, uint64_t state_points);
 // ---- tad_state_merge (tad_merge.hip): a batch's points nk / nt / nv (key k's at [poff[k], poff[k + 1])) placed by time ----
-struct MergeCounters {   // one 64-byte block on the device, zeroed per attempt
-  unsigned long long too_old, appended, inserted, combined, keys_touched, keys_replayed, pad[2];
-};
 // per point: cls (too old / appended / inserted / combined), rank = the key's old points before it, and the flags of the three scans:
 // f_nh = adds an element (inserted or appended), f_kept = not too old, f_hit = combined; lanes in [*P_dev, P_cap) write zeros
 void launch_merge_classify(hipStream_t s, const unsigned long long *nk, const long long *nt, const unsigned long long *P_dev, uint64_t P_cap, uint64_t K,
@@ -499,14 +482,6 @@ void launch_merge_series(hipStream_t s, uint64_t chunks_bound, const unsigned lo
 void launch_merge_moments(hipStream_t s, uint64_t K, const uint32_t *replay, const unsigned long long *soff_old, const unsigned long long *soff_new,
                           const unsigned long long *sval_new, const long long *st_new, double alpha, StreamState cur, StreamState next, MergeCounters *mc);
 // ---- streaming ARIMA (tad_arima.hip): a batch on a series state, per touched key (slot) and per new point ----
-struct ArimaSlots {
-  uint32_t *key;                 // the slot's key
-  unsigned long long *yoff;      // its series in the packed Box-Cox arrays (a multiple of 8)
-  double *lam, *sigma;           // lambda; stddev_samp from the post-batch moments
-  unsigned long long *ibase;     // new-point index of position 0 (wrapping)
-  uint32_t *lo, *hi;             // the positions of its fits [lo, hi) (empty without a result)
-  uint8_t *ok;                   // 1: the key has a result
-};
 struct FitListArgs {
   const uint32_t *wave_pos;          // [waves] position of each wavefront of k_arima_fit_list
   const uint32_t *cnt;               // [positions] fits per position
@@ -539,13 +514,6 @@ void launch_drop(hipStream_t s, Grid g, double n_sigma, int min_samples, double 
                  double *key_mean, double *key_m2, DevCounters *ctr);
 
 // ---- the drop detector on a state's series (tad_drop_state.hip): tad_drop_state / tad_drop_stream ----
-struct DropStateKeys {   // per key, in one block of drop_state_key_bytes(K)
-  double *mean, *std, *m2;   // pairwise mean, pandas' sample std, the pairwise sum of (mean - x)^2
-  uint32_t *n;               // the key's points
-  uint8_t *ok;               // 1: the key has a result (n >= min_samples && n >= 2)
-};
-size_t drop_state_key_bytes(uint64_t K);
-DropStateKeys drop_state_keys(void *mem, uint64_t K);
 // list / *count = the keys with new points (poff[k + 1] > poff[k]) and >= coop_min series points (list: K entries)
 void launch_ds_route(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *poff, unsigned long long coop_min, uint32_t *list,
                      unsigned int *count);
@@ -770,9 +738,6 @@ void launch_sd_export_lens(hipStream_t s, const void *recs, uint64_t first, uint
 void launch_sd_export(hipStream_t s, const void *recs, const uint8_t *arena, uint64_t first, uint64_t n, const unsigned long long *off, uint8_t *out);
 
 // ---- retiring dead keys: tad_state_compact / tad_keydict_compact (tad_compact.hip) ----
-struct CompactCounters {   // one 64-byte block on the device, zeroed per call
-  unsigned long long unseen, idle, dropped, pad[5];   // keys with n == 0 | keys with last_t < retire_before | the points of those
-};
 // per key: live = it survives (n > 0 and, with retire_before != 0, last_t >= retire_before), slen / hlen = the series / history elements
 // it keeps (0 when retired or when soff / hoff is NULL), schunks / hchunks = ceil(len / kHistChunk) — 0 for an empty segment: chunk_key
 void launch_compact_mark(hipStream_t s, uint64_t K, StreamState cur, const unsigned long long *soff, const unsigned long long *hoff, long long retire_before,
@@ -814,7 +779,6 @@ struct DselIn {          // every pointer DEVICE; ts / te: long long[n], or uint
   uint64_t n;
   int t32;
 };
-struct DselOut { long long *kind, *ns, *name, *dir, *day; unsigned long long *count, *row; };
 uint64_t dsel_tiles(uint64_t n);
 void launch_dsel_flags(hipStream_t s, const DselIn &A, uint16_t *bits, uint32_t *cnt);
 void launch_dsel_emit(hipStream_t s, const DselIn &A, const uint16_t *bits, const unsigned long long *off, const DselOut &O);

@@ -2092,3 +2092,77 @@ func (d *StringDict) Match(op int32, pattern []byte) (mask []byte, matched uint6
 	}
 	return mask, uint64(hit), nil
 }
+
+var dictDecodeOnce sync.Once
+var dictDecodeOK bool
+
+// hasDictDecode: the library decodes on the device (tad_features); an older one would not export the two calls.
+func hasDictDecode() bool {
+	dictDecodeOnce.Do(func() { dictDecodeOK = C.tad_features()&C.TAD_FEATURE_DICT_DECODE != 0 })
+	return dictDecodeOK
+}
+
+var errNoDictDecode = errors.New("tadengine: libtad_mi355x.so has no device decode (TAD_FEATURE_DICT_DECODE)")
+
+// Gather returns the tuples of arbitrary keys column by column, and their sides (tad_keydict_gather): cols[c][i] is column c of key
+// keyID[i].  Ids may repeat and come in any order; an id that is not below NumKeys is an IllegalArgument.
+func (d *KeyDict) Gather(keyID []uint64) (cols [][]int64, side []byte, err error) {
+	if !hasDictDecode() {
+		return nil, nil, errNoDictDecode
+	}
+	n := len(keyID)
+	cols = make([][]int64, d.nCols)
+	side = make([]byte, n)
+	// the pointer array and the columns it names live in C memory for the call (no Go pointer inside C memory)
+	arr := (*[8]*C.int64_t)(C.calloc(8, C.size_t(unsafe.Sizeof(unsafe.Pointer(nil)))))
+	defer C.free(unsafe.Pointer(arr))
+	for c := range cols {
+		cols[c] = make([]int64, n)
+		arr[c] = (*C.int64_t)(C.calloc(C.size_t(n)+1, 8))
+		defer C.free(unsafe.Pointer(arr[c]))
+	}
+	var kp *C.uint64_t
+	var sp *C.uint8_t
+	if n > 0 {
+		kp = (*C.uint64_t)(unsafe.Pointer(&keyID[0]))
+		sp = (*C.uint8_t)(unsafe.Pointer(&side[0]))
+	}
+	if rc := C.tad_keydict_gather(d.e.h, d.h, kp, C.uint64_t(n), C.TAD_MEM_HOST, &arr[0], sp); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(d.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, nil, IllegalArgument{msg}
+		}
+		return nil, nil, fmt.Errorf("tad_keydict_gather: %s (code %d)", msg, int(rc))
+	}
+	for c := range cols {
+		copy(cols[c], unsafe.Slice((*int64)(unsafe.Pointer(arr[c])), n))
+	}
+	return cols, side, nil
+}
+
+// Decode returns the values of arbitrary codes in Arrow's layout (tad_strdict_decode): len(codes) + 1 offsets starting at 0 and the
+// packed bytes — value codes[i] is data[offsets[i]:offsets[i+1]].  A code that is not in [0, NumValues) is an IllegalArgument.
+func (d *StringDict) Decode(codes []int64) (offsets []int64, data []byte, err error) {
+	if !hasDictDecode() {
+		return nil, nil, errNoDictDecode
+	}
+	n := len(codes)
+	var cp *C.int64_t
+	if n > 0 {
+		cp = (*C.int64_t)(unsafe.Pointer(&codes[0]))
+	}
+	var need C.uint64_t
+	if rc := C.tad_strdict_decode(d.e.h, d.h, cp, C.uint64_t(n), C.TAD_MEM_HOST, nil, nil, 0, C.TAD_MEM_HOST, &need); rc != C.TAD_OK {
+		return nil, nil, d.fail("tad_strdict_decode", rc)
+	}
+	offsets = make([]int64, n+1)
+	data = make([]byte, uint64(need))
+	var dp *C.uint8_t
+	if len(data) > 0 {
+		dp = (*C.uint8_t)(unsafe.Pointer(&data[0]))
+	}
+	if rc := C.tad_strdict_decode(d.e.h, d.h, cp, C.uint64_t(n), C.TAD_MEM_HOST, (*C.int64_t)(unsafe.Pointer(&offsets[0])), dp, need, C.TAD_MEM_HOST, &need); rc != C.TAD_OK {
+		return nil, nil, d.fail("tad_strdict_decode", rc)
+	}
+	return offsets, data, nil
+}

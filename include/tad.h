@@ -994,6 +994,43 @@ int tad_strdict_import(tad_engine *e, tad_strdict *d, uint64_t n_values, const i
 int tad_strdict_match(tad_engine *e, const tad_strdict *d, int32_t op, const uint8_t *pattern, uint64_t pattern_len, uint8_t *mask,
                       uint64_t mask_len, tad_mem memory, uint64_t *n_matched);
 
+/* ---- decoding on the device: key ids -> tuples, string codes -> strings (TAD_FEATURE_DICT_DECODE; check tad_features() before calling these) ----
+ * The two dictionaries above turn strings into codes and code tuples into key ids; the state calls return result rows that carry key
+ * ids.  These two calls go the other way, for ARBITRARY ids and codes — the export calls read a contiguous range only — so a host keeps
+ * no table of its keys: it gathers the tuples of the keys its result rows name and decodes their codes, and nothing else crosses the link.
+ * Both calls only read the dictionary.
+ * tad_keydict_gather: cols[c][i] = column c of key key_id[i] and side[i] = its side (0 = a, 1 = b), for i < n: for every i what the
+ * dictionary's export gives for first_key = key_id[i], n_keys = 1.  `memory` says where key_id, every cols[c] and side live; the pointer
+ * array cols itself is host memory with n_cols entries, and a NULL entry skips that column; side may be NULL.  Ids may repeat and come in
+ * any order.  n == 0 is TAD_OK.  An id >= num_keys — TAD_KEY_SKIP is one — is TAD_ERR_INVALID_ARGUMENT, raised from a device flag after
+ * the kernel ran, as the select call raises a code outside its mask; the outputs are unspecified then.  One launch (one lane per id: the
+ * record in 16-byte loads, the stores column by column) and one synchronisation; it reads 8 B of id and one record (8 (n_cols + 1) B,
+ * rounded up to 16) and writes 8 B per asked column and 1 B of side, per id.  A host call stages the ids and the outputs in job-context
+ * workspace (8 B an id, 8 B an id and asked column, 1 B a side), checked against workspace_limit (TAD_ERR_GRID_TOO_LARGE) before anything
+ * runs.  Limit: n < 2^32 - 1.
+ * tad_strdict_decode: Arrow's layout, as the dictionary's export writes it, for arbitrary codes: offsets[n + 1] starting at 0, and in
+ * data the bytes of value codes[0], codes[1], ... packed behind each other.  codes_memory says where codes live, out_memory where offsets
+ * and data live, independently: the useful chain is device codes from a gather into host strings.  *data_bytes (may be NULL) is always the
+ * bytes needed; offsets == NULL && data == NULL is the size query; a data_cap that is too small is TAD_ERR_INVALID_ARGUMENT with nothing
+ * written but *data_bytes.  A code outside [0, num_values) — TAD_CODE_NONE is one — is TAD_ERR_INVALID_ARGUMENT with nothing written to
+ * offsets or data: the lengths pass finds it before any byte is copied.  Device codes and offsets are 8-byte aligned; a device data
+ * pointer may have any byte alignment, and no byte outside [data, data + *data_bytes) is written.  No validity is produced: a code is a
+ * value.  Limits: n < 2^32 - 1; the total bytes are addressed with 64 bits.
+ * Cost of a decode.  Three launches and two synchronisations (the total is read between the lengths and the copy): the lengths pass reads
+ * 8 B of code and one 16-byte record a row, the scan turns 4 B a row into 8 B a row, the copy reads the record again and the value's
+ * ceil(len / 16) aligned 16-byte words of the arena and writes the bytes once, in whole lines: a workgroup assembles the bytes of 256
+ * consecutive rows in 16 KiB of LDS, laid out as the destination's 16-byte words, and stores them with aligned 16-byte stores; a tile over
+ * 16 KiB is copied string by string, a wavefront each.  Job-context workspace, grow-only and bounded by workspace_limit: 12 B a row
+ * (lengths, offsets), the scan's scratch, 8 B a row for host codes, the packed bytes for a host output.  Measured once on an MI355X
+ * (DESIGN.md §5): 1e7 codes of 30-byte values, device to device, in 0.36 - 0.87 ms, 0.15 - 0.34 of a copy of the same bytes.
+ * Every call on a NULL engine or dictionary is TAD_ERR_INVALID_ARGUMENT without a device and writes nothing.  The ABI stays 13 and no
+ * struct grows.  Lock order: the dictionary, then a job context. */
+#define TAD_FEATURE_DICT_DECODE 8192u /* tad_keydict_gather, tad_strdict_decode: ids -> tuples and codes -> strings on the device */
+int tad_keydict_gather(tad_engine *e, const tad_keydict *d, const uint64_t *key_id, uint64_t n, tad_mem memory, int64_t *const *cols,
+                       uint8_t *side /* may be NULL */);
+int tad_strdict_decode(tad_engine *e, const tad_strdict *d, const int64_t *codes, uint64_t n, tad_mem codes_memory, int64_t *offsets,
+                       uint8_t *data, uint64_t data_cap, tad_mem out_memory, uint64_t *data_bytes /* may be NULL */);
+
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).
  * tad_job_progress (ABI 12): the job whose tad_job.id equals `id`; *total = 0 when no such job is in flight (finished or not yet

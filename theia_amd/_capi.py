@@ -34,6 +34,7 @@ TAD_FEATURE_STATE_DROP = 512                 # tad_features() bit: tad_drop_stat
 TAD_FEATURE_DROP_ROWS = 1024                 # tad_features() bit: tad_drop_select, flow rows -> the drop job's (endpoint, direction, day, count) rows
 TAD_FEATURE_KEY_SELECT = 2048                # tad_features() bit: tad_keydict_select, tad_run_state_keys, tad_drop_state_keys: jobs over selected keys of a state
 TAD_FEATURE_STRING_DICT = 4096               # tad_features() bit: tad_strdict, a persistent string -> code dictionary on the device, with match masks
+TAD_FEATURE_DICT_DECODE = 8192               # tad_features() bit: tad_keydict_gather, tad_strdict_decode: ids -> tuples and codes -> strings on the device
 TAD_CODE_NONE = -1                           # tad_strdict_lookup: the string is not in the dictionary
 TAD_STR_EQUAL, TAD_STR_CONTAINS_NOCASE = 0, 1   # tad_strdict_match: the value is the pattern / the pattern occurs in it, ASCII letters without case
 
@@ -202,6 +203,8 @@ SYMBOLS = {
     "tad_strdict_export": (C.c_int, [C.c_void_p, C.c_void_p, u64, u64, C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]),
     "tad_strdict_import": (C.c_int, [C.c_void_p, C.c_void_p, u64, C.c_void_p, C.c_void_p]),
     "tad_strdict_match": (C.c_int, [C.c_void_p, C.c_void_p, i32, C.c_void_p, u64, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
+    "tad_keydict_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    "tad_strdict_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.c_void_p, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
     "tad_state_compact": (C.c_int, [C.c_void_p, C.c_void_p, i64, C.c_void_p, C.c_int, C.POINTER(CompactStats)]),
     "tad_keydict_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
     "tad_drop_state": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_int, C.POINTER(C.POINTER(Result))]),

@@ -377,6 +377,53 @@ int tad_keydict_select(tad_engine *eng, const tad_keydict *d, int32_t n_terms, c
   return TAD_OK;
 }
 
+// tad.h: ids -> tuples (kernel: k_kd_gather).  The dictionary is only read.
+int tad_keydict_gather(tad_engine *eng, const tad_keydict *d, const uint64_t *key_id, uint64_t n, tad_mem memory, int64_t *const *cols, uint8_t *side) {
+  const char *who = "tad_keydict_gather";
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!d || (n && (!key_id || !cols)) || (memory != TAD_MEM_HOST && memory != TAD_MEM_DEVICE))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bad arguments (dictionary, key_id, the array of column pointers, host or device memory)", who);
+  if (n >= 0xFFFFFFFFull) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: %llu ids do not fit 32-bit row indices", who, (unsigned long long)n);
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  if (n == 0) return TAD_OK;
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "%s: no job context available", who);
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  const bool host = memory == TAD_MEM_HOST;
+  unsigned col_mask = 0;
+  for (int c = 0; c < d->n_cols; ++c)
+    if (cols[c]) col_mask |= 1u << c;
+  // scratch: in_key = the flag word; a host call's ids, asked columns and sides behind it (kd_gather_layout)
+  Carve measure(nullptr);
+  kd_gather_layout(measure, n, d->n_cols, col_mask, side != nullptr, host);
+  if (measure.bytes() > e->ws_limit) return over_limit(e, who, measure.bytes());
+  int rc;
+  if ((rc = ensure(e, e->in_key, measure.bytes())) != TAD_OK) return rc;
+  Carve place(e->in_key.p);
+  const KdGatherWs w = kd_gather_layout(place, n, d->n_cols, col_mask, side != nullptr, host);
+  KdGatherOut o{};
+  for (int c = 0; c < d->n_cols; ++c) o.col[c] = host ? w.col[c] : reinterpret_cast<long long *>(cols[c]);
+  o.side = host ? w.side : side;
+  HIP_TRY(e, hipMemsetAsync(w.flags, 0, 4, s));
+  if (host) HIP_TRY(e, hipMemcpyAsync(w.ids, key_id, n * 8, hipMemcpyHostToDevice, s));
+  launch_kd_gather(s, d->keys, d->n_cols, d->K, host ? reinterpret_cast<const uint64_t *>(w.ids) : key_id, n, o, w.flags);
+  uint32_t flags = 0;
+  HIP_TRY(e, hipMemcpyAsync(&flags, w.flags, 4, hipMemcpyDeviceToHost, s));
+  if (host) {
+    for (int c = 0; c < d->n_cols; ++c)
+      if (cols[c]) HIP_TRY(e, hipMemcpyAsync(cols[c], w.col[c], n * 8, hipMemcpyDeviceToHost, s));
+    if (side) HIP_TRY(e, hipMemcpyAsync(side, w.side, n, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  if (flags & KD_FLAG_BAD_ID)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: an id is not below the %llu keys held (TAD_KEY_SKIP is no key; the outputs are unspecified)", who,
+                (unsigned long long)d->K);
+  return TAD_OK;
+}
+
 // tad.h: the renumbering of tad_state_compact applied to the dictionary (kernels in tad_compact.hip).  The check runs first and alone;
 // then fresh records and a fresh table are filled and swapped in.
 int tad_keydict_compact(tad_engine *eng, tad_keydict *d, const uint64_t *remap, uint64_t remap_len, tad_mem remap_memory, uint64_t *num_keys) {

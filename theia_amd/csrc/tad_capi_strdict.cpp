@@ -378,4 +378,77 @@ int tad_strdict_match(tad_engine *eng, const tad_strdict *d, int32_t op, const u
   return TAD_OK;
 }
 
+// tad.h: codes -> strings in Arrow's layout (kernels: k_sd_decode_lens, the scan, k_sd_decode).  The dictionary is only read.
+int tad_strdict_decode(tad_engine *eng, const tad_strdict *d, const int64_t *codes, uint64_t n, tad_mem codes_memory, int64_t *offsets, uint8_t *data,
+                       uint64_t data_cap, tad_mem out_memory, uint64_t *data_bytes) {
+  const char *who = "tad_strdict_decode";
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!d || (n && !codes) || (!offsets && data) || (data_cap && !data) || (codes_memory != TAD_MEM_HOST && codes_memory != TAD_MEM_DEVICE) ||
+      (out_memory != TAD_MEM_HOST && out_memory != TAD_MEM_DEVICE))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bad arguments (dictionary, codes, offsets with data, host or device memory)", who);
+  if (n >= 0xFFFFFFFFull) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: %llu codes do not fit 32-bit row indices", who, (unsigned long long)n);
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  const bool query = !offsets && !data, host_codes = codes_memory == TAD_MEM_HOST, host_out = out_memory == TAD_MEM_HOST;
+  if (n == 0 && (query || host_out)) {
+    if (data_bytes) *data_bytes = 0;
+    if (offsets) offsets[0] = 0;
+    return TAD_OK;
+  }
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "%s: no job context available", who);
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  if (n == 0) {      // offsets[0] = 0 in device memory
+    if (data_bytes) *data_bytes = 0;
+    HIP_TRY(e, hipMemsetAsync(offsets, 0, 8, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    return TAD_OK;
+  }
+  // scratch: sp_val_a = flag word | a host call's codes | lengths | offsets (sd_decode_layout), scan_scratch; sp_temp = a host call's packed bytes
+  Carve measure(nullptr);
+  sd_decode_layout(measure, n, host_codes);
+  const size_t scan_bytes = scan_scratch_elems(n) * sizeof(unsigned long long);
+  if (measure.bytes() + scan_bytes > e->ws_limit) return over_limit(e, who, measure.bytes() + scan_bytes);
+  int rc;
+  if ((rc = ensure(e, e->sp_val_a, measure.bytes())) != TAD_OK || (rc = ensure(e, e->scan_scratch, scan_bytes)) != TAD_OK) return rc;
+  Carve place(e->sp_val_a.p);
+  const SdDecodeWs w = sd_decode_layout(place, n, host_codes);
+  const long long *d_codes = reinterpret_cast<const long long *>(codes);
+  HIP_TRY(e, hipMemsetAsync(w.flags, 0, 4, s));
+  if (host_codes) {
+    HIP_TRY(e, hipMemcpyAsync(w.codes, codes, n * 8, hipMemcpyHostToDevice, s));
+    d_codes = w.codes;
+  }
+  // 1. the lengths (every code is checked here) and their scan: the offsets, and the bytes needed behind them
+  launch_sd_decode_lens(s, d->recs, d->K, d_codes, n, w.cnt, w.flags);
+  launch_scan(s, w.cnt, w.off, n, static_cast<unsigned long long *>(e->scan_scratch.p));
+  unsigned long long total = 0;
+  uint32_t flags = 0;
+  HIP_TRY(e, hipMemcpyAsync(&total, w.off + n, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(&flags, w.flags, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  if (flags & SD_FLAG_BAD_CODE)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: a code lies outside the %llu values held (TAD_CODE_NONE is no value; nothing written)", who, (unsigned long long)d->K);
+  if (data_bytes) *data_bytes = total;
+  if (query) return TAD_OK;
+  if (total > data_cap)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: the values hold %llu bytes, data has room for %llu", who, (unsigned long long)total, (unsigned long long)data_cap);
+  // 2. the bytes, straight into device `data` (any alignment) or into sp_temp on their way to the host
+  uint8_t *d_data = data;
+  if (host_out && total) {
+    const size_t out_bytes = up256((size_t)total);
+    if (measure.bytes() + scan_bytes + out_bytes > e->ws_limit) return over_limit(e, who, measure.bytes() + scan_bytes + out_bytes);
+    if ((rc = ensure(e, e->sp_temp, out_bytes)) != TAD_OK) return rc;
+    d_data = static_cast<uint8_t *>(e->sp_temp.p);
+  }
+  if (total) launch_sd_decode(s, d->recs, d->arena, d_codes, n, w.off, d_data);
+  HIP_TRY(e, hipMemcpyAsync(offsets, w.off, (n + 1) * 8, host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+  if (host_out && total) HIP_TRY(e, hipMemcpyAsync(data, d_data, total, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  return TAD_OK;
+}
+
 }  // extern "C"

@@ -473,6 +473,38 @@ inline DselWs dsel_layout(Carve &c, const DselDims &d) {
   return w;
 }
 
+// ---- the dictionaries' decode side (tad_keydict_gather, tad_strdict_decode): every part rounded up to 256 bytes ----
+struct KdGatherWs {   // the flag word; a host call's staging behind it: the ids | the asked columns | the sides
+  uint32_t *flags;
+  unsigned long long *ids;   // NULL for a device call, as are the columns and the sides
+  long long *col[8];         // (kFzMaxCols) NULL where the caller's entry is
+  uint8_t *side;
+};
+inline KdGatherWs kd_gather_layout(Carve &c, uint64_t n, int n_cols, unsigned col_mask, bool with_side, bool host) {
+  KdGatherWs w{};
+  w.flags = c.take<uint32_t>(1, 256); c.pad_to(256);
+  if (!host) return w;
+  w.ids = c.take<unsigned long long>((size_t)n, 256); c.pad_to(256);
+  for (int i = 0; i < n_cols && i < 8; ++i)
+    if (col_mask & (1u << i)) { w.col[i] = c.take<long long>((size_t)n, 256); c.pad_to(256); }
+  if (with_side) { w.side = c.take<uint8_t>((size_t)n, 256); c.pad_to(256); }
+  return w;
+}
+struct SdDecodeWs {   // the flag word | a host call's codes | lengths | offsets (n + 1: the scan's total is the last)
+  uint32_t *flags;
+  long long *codes;   // NULL when the codes are device memory
+  uint32_t *cnt;
+  unsigned long long *off;
+};
+inline SdDecodeWs sd_decode_layout(Carve &c, uint64_t n, bool host_codes) {
+  SdDecodeWs w{};
+  w.flags = c.take<uint32_t>(1, 256); c.pad_to(256);
+  if (host_codes) { w.codes = c.take<long long>((size_t)n, 256); c.pad_to(256); }
+  w.cnt = c.take<uint32_t>((size_t)n, 256); c.pad_to(256);
+  w.off = c.take<unsigned long long>((size_t)n + 1, 256); c.pad_to(256);
+  return w;
+}
+
 }  // namespace tad
 
 #endif  // THEIA_TAD_CARVE_H

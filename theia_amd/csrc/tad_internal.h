@@ -675,7 +675,7 @@ struct TupleBatch {                 // the key tuples of one batch (device point
   uint32_t sides;                   // 1 or 2
 };
 static constexpr uint32_t kKdMaxProbe = 32;     // a claim that probed further asks the host for a larger table
-enum : uint32_t { KD_FLAG_CLUSTER = 1u, KD_FLAG_DUPLICATE = 2u, KD_FLAG_BAD_ROW = 4u, KD_FLAG_BAD_CODE = 8u };
+enum : uint32_t { KD_FLAG_CLUSTER = 1u, KD_FLAG_DUPLICATE = 2u, KD_FLAG_BAD_ROW = 4u, KD_FLAG_BAD_CODE = 8u, KD_FLAG_BAD_ID = 16u };
 int kd_stride(int n_cols);          // 8-byte words of one key record: side + columns, padded to an even count
 // every kept virtual row looks its tuple up in table[slots] / keys (K records).  miss != NULL: hits write their id, misses raise miss[v] and
 // are counted in *n_miss (zeroed by the caller), rows that are not kept get TAD_KEY_SKIP; miss == NULL: a miss is TAD_KEY_SKIP too
@@ -702,6 +702,14 @@ struct KdSelect {
 // *n_sel += the selected keys, *flags |= KD_FLAG_BAD_CODE for a value outside its mask (both zeroed by the caller)
 void launch_kd_select(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, const KdSelect &q, uint8_t *keep, unsigned long long *n_sel,
                       uint32_t *flags);
+// tad_keydict_gather: where the tuples of the asked ids go (device pointers; a NULL column or side is not written)
+struct KdGatherOut {
+  long long *col[kFzMaxCols];
+  uint8_t *side;
+};
+// col[c][i] = column c of key key_id[i], side[i] = its side, for i < n; *flags |= KD_FLAG_BAD_ID for an id >= K (zeroed by the caller),
+// that row is not written
+void launch_kd_gather(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, const uint64_t *key_id, uint64_t n, const KdGatherOut &o, uint32_t *flags);
 
 // ---- ingest: a string dictionary that outlives the call — strings -> codes that stay the same from batch to batch (tad_strdict.hip) ----
 struct StrBatch {                   // one Arrow string column (device pointers): what tad_encode_strings' and the dictionary's kernels read
@@ -715,7 +723,7 @@ struct StrBatch {                   // one Arrow string column (device pointers)
 };
 static constexpr uint32_t kSdMaxProbe = 32;       // a claim that probed further asks the host for a larger table
 static constexpr uint32_t kSdMaxPattern = 1024;   // tad_strdict_match: bytes of the longest pattern
-enum : uint32_t { SD_FLAG_CLUSTER = 1u, SD_FLAG_BAD_OFFSETS = 2u, SD_FLAG_BAD_ROW = 4u };
+enum : uint32_t { SD_FLAG_CLUSTER = 1u, SD_FLAG_BAD_OFFSETS = 2u, SD_FLAG_BAD_ROW = 4u, SD_FLAG_BAD_CODE = 8u };
 // recs: one 16-byte record per code (arena offset | hash's low half << 32 | length); arena: the strings, each 16-byte aligned and zero-padded.
 // every row looks its string up in table[slots] / recs (K records) / arena.  miss != NULL: hits write their code, misses raise miss[v] and
 // are counted in *n_miss; miss == NULL: a miss is TAD_CODE_NONE.  *flags |= SD_FLAG_BAD_OFFSETS for unusable offsets (both zeroed by the caller)
@@ -736,6 +744,12 @@ void launch_sd_match(hipStream_t s, const void *recs, const uint8_t *arena, uint
 // cnt[i] = the length of value first + i; the values' bytes packed at out + off[i] (out 8-byte aligned)
 void launch_sd_export_lens(hipStream_t s, const void *recs, uint64_t first, uint64_t n, uint32_t *cnt);
 void launch_sd_export(hipStream_t s, const void *recs, const uint8_t *arena, uint64_t first, uint64_t n, const unsigned long long *off, uint8_t *out);
+// tad_strdict_decode.  Lengths: cnt[i] = the length of value codes[i]; a code outside [0, K) counts 0 and raises SD_FLAG_BAD_CODE in *flags
+// (zeroed by the caller).  Copy: the bytes of value codes[i] at out + off[i] (off: the scan of cnt; out at any byte alignment), a workgroup
+// per kSdDecodeRows consecutive rows, staged in kSdDecodeStage bytes of LDS
+static constexpr uint32_t kSdDecodeRows = 256, kSdDecodeStage = 16 * 1024, kSdDecodeMaxBlocks = 2048;
+void launch_sd_decode_lens(hipStream_t s, const void *recs, uint64_t K, const long long *codes, uint64_t n, uint32_t *cnt, uint32_t *flags);
+void launch_sd_decode(hipStream_t s, const void *recs, const uint8_t *arena, const long long *codes, uint64_t n, const unsigned long long *off, uint8_t *out);
 
 // ---- retiring dead keys: tad_state_compact / tad_keydict_compact (tad_compact.hip) ----
 // per key: live = it survives (n > 0 and, with retire_before != 0, last_t >= retire_before), slen / hlen = the series / history elements

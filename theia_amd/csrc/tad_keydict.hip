@@ -21,6 +21,7 @@
 //   4. k_kd_fix: id = num_keys_before + local id on the miss rows.
 // The table never passes load 1/2 (the host grows it BEFORE step 3: k_kd_rehash fills a table of twice the size from the records, and
 // the new one is swapped in when that succeeded), so every probe sequence ends at an empty slot and step 3 cannot fail.
+// The other direction (tad_keydict_gather: arbitrary ids -> tuples) reads the records only: k_kd_gather.
 #include "tad_internal.h"
 #include "tad_slots.h"
 
@@ -166,7 +167,24 @@ __global__ __launch_bounds__(kKdBlock) void k_kd_select(const unsigned long long
   block_count_add(s_cnt, n_sel, mine);
 }
 
-int kd_stride(int n_cols) { return (n_cols + 2) & ~1; }      // side + columns, padded to an even number of 8-byte words
+// tad_keydict_gather: one lane per asked id.  The record is loaded whole (kd_load_record: 16-byte loads, 64 lanes on up to 64 lines — a
+// gather, whatever the kernel does) and stored column by column: consecutive lanes write consecutive 8-byte words of each column, one byte
+// each of the sides.  An id >= K (TAD_KEY_SKIP is one) raises KD_FLAG_BAD_ID, reads no record and writes nothing.
+__global__ __launch_bounds__(kKdBlock) void k_kd_gather(const unsigned long long *__restrict__ keys, int pairs, int n_cols, uint64_t K, const uint64_t *__restrict__ key_id,
+                                                        uint64_t n, KdGatherOut o, uint32_t *__restrict__ flags) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kKdBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kKdBlock) {
+    const uint64_t id = key_id[i];
+    if (id >= K) { atomicOr(flags, KD_FLAG_BAD_ID); continue; }
+    ulonglong2 w[kKdMaxPairs];
+    kd_load_record(keys, id, pairs, w);
+#pragma unroll
+    for (int c = 0; c < kFzMaxCols; ++c)
+      if (c < n_cols && o.col[c] != nullptr) o.col[c][i] = (long long)kd_word(w, c + 1);
+    if (o.side != nullptr) o.side[i] = (uint8_t)w[0].x;
+  }
+}
+
+int kd_stride(int n_cols) { return (n_cols + 2) & ~1; }     // side + columns, padded to an even number of 8-byte words
 
 static dim3 kd_grid(uint64_t items) { const uint64_t b = (items + kKdBlock - 1) / kKdBlock; return dim3((unsigned)(b < 16384 ? (b ? b : 1) : 16384)); }
 
@@ -199,6 +217,11 @@ void launch_kd_select(hipStream_t s, const unsigned long long *keys, int n_cols,
                       uint32_t *flags) {
   if (K == 0) return;
   hipLaunchKernelGGL(k_kd_select, kd_grid(K), dim3(kKdBlock), 0, s, keys, kd_stride(n_cols) / 2, K, q, keep, n_sel, flags);
+}
+
+void launch_kd_gather(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, const uint64_t *key_id, uint64_t n, const KdGatherOut &o, uint32_t *flags) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_kd_gather, kd_grid(n), dim3(kKdBlock), 0, s, keys, kd_stride(n_cols) / 2, n_cols, K, key_id, n, o, flags);
 }
 
 // one kernel of this translation unit: tad_engine_create resolves it so that the unit's code object is loaded before the first batch

@@ -33,6 +33,9 @@
 //      slot.  New values are distinct from each other and from every value held, so nothing is compared here.
 //   5. k_sd_fix: code = num_before + local id on the miss rows.
 // The table never passes load 1/2 (grown BEFORE step 4), so every probe sequence ends at an empty slot and step 4 cannot fail.
+// The other direction (tad_strdict_decode: arbitrary codes -> strings in Arrow's layout) reads records and arena only: k_sd_decode_lens,
+// launch_scan, k_sd_decode — the staging of step 1 run backwards, the arena's alignment and padding doing for the reads what they do for
+// the compare.
 #include "tad_internal.h"
 #include "tad_strbytes.h"
 
@@ -261,6 +264,143 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_export(const ulonglong2 *__rest
   }
 }
 
+// ---- tad_strdict_decode: codes -> strings ----
+// Lengths: cnt[i] = the length of value codes[i], read from its record (one 16-byte load a row).  A code outside [0, K) — TAD_CODE_NONE is
+// one — counts 0 and raises SD_FLAG_BAD_CODE: the host refuses the call before a byte is copied.
+__global__ __launch_bounds__(kSdBlock) void k_sd_decode_lens(const ulonglong2 *__restrict__ recs, uint64_t K, const long long *__restrict__ codes, uint64_t n,
+                                                             uint32_t *__restrict__ cnt, uint32_t *__restrict__ flags) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kSdBlock) {
+    const uint64_t c = (uint64_t)codes[i];      // (a negative code is a huge unsigned one)
+    const bool in = c < K;
+    if (!in) atomicOr(flags, SD_FLAG_BAD_CODE);
+    cnt[i] = in ? sd_rec_len(recs[c]) : 0u;
+  }
+}
+
+// 8-byte word k of a held string of len bytes with the bytes at and beyond len zeroed (they are the arena's pad: zero as k_sd_append left
+// them, but nothing of a pad may reach the output whatever it holds)
+__device__ __forceinline__ uint64_t sd_keep(uint64_t x, uint64_t k, uint64_t len) {
+  const uint64_t b = k * 8;
+  if (b + 8 <= len) return x;
+  return b >= len ? 0ull : x & ((1ull << ((len - b) * 8)) - 1ull);
+}
+
+// A held string q (16-byte aligned in the arena, padded to a multiple of 16) as the ALIGNED 8-byte words of a destination in which it
+// begins s (0..7) bytes into word 0: put(k, x) for the words k = 2 j, 2 j + 1 of j = j0, j0 + step, ... — x holds the string's bytes
+// [8 k - s, 8 k - s + 8) in place and zeros elsewhere.  Every source read is an aligned 16-byte load inside the allocation, but for the
+// 8 bytes in front of a pair when another lane loaded them (step > 1): one more aligned 8-byte load of the line just read.
+template <class Put>
+__device__ __forceinline__ void sd_shifted_words(const uint8_t *q, uint64_t len, uint32_t s, uint64_t j0, uint64_t step, Put put) {
+  const ulonglong2 *q16 = reinterpret_cast<const ulonglong2 *>(q);
+  const uint64_t *q64 = reinterpret_cast<const uint64_t *>(q);
+  const uint64_t nw16 = (len + 15) >> 4, ndw = (s + len + 7) >> 3;
+  const uint32_t sh = s * 8u;
+  uint64_t carried = 0;
+  for (uint64_t j = j0; 2 * j < ndw; j += step) {
+    const ulonglong2 v = j < nw16 ? q16[j] : ulonglong2{0ull, 0ull};      // (j == nw16: the word that takes the last bytes shifted out)
+    const uint64_t a = sd_keep(v.x, 2 * j, len), b = sd_keep(v.y, 2 * j + 1, len);
+    uint64_t prev = 0;
+    if (sh != 0u && j != 0) prev = (step == 1 && j != j0) ? carried : sd_keep(q64[2 * j - 1], 2 * j - 1, len);
+    put(2 * j, sh ? (a << sh) | (prev >> (64u - sh)) : a);
+    if (2 * j + 1 < ndw) put(2 * j + 1, sh ? (b << sh) | (a >> (64u - sh)) : b);
+    carried = b;
+  }
+}
+
+static constexpr uint32_t kSdDecodeLaneMax = 128;      // a longer string of a staged tile is assembled by a wavefront, not by its row's lane
+
+#ifndef TAD_SD_DECODE_ROWS
+// Copy, the shipped form: k_sd_probe's staging run backwards.  A workgroup takes kSdDecodeRows consecutive rows; their output bytes
+// [off[r0], off[r1]) are contiguous.  A tile of at most kSdDecodeStage bytes is assembled in LDS, laid out as the 16-byte words of the
+// DESTINATION (the tile begins `head` = its address mod 16 bytes into word 0): the stage is zeroed, every lane ORs its row's shifted words
+// into it (rows share the words at their ends, and never a byte), a row over kSdDecodeLaneMax bytes is left to a wavefront.  The stage then
+// goes out in aligned 16-byte stores, consecutive lanes on consecutive words: the output crosses the memory system once, in whole lines.
+// Only the bytes of the partial words at the tile's two ends are stored singly — the neighbouring tiles own the rest of those words.
+// A tile over the stage (long labels, one long string) is not staged: its rows are taken in turn by the wavefronts, 64 lanes on
+// consecutive 8-byte words of the destination, single bytes where a word is shared with the next row.
+__global__ __launch_bounds__(kSdBlock) void k_sd_decode(const ulonglong2 *__restrict__ recs, const uint8_t *__restrict__ arena, const long long *__restrict__ codes,
+                                                        uint64_t n, const unsigned long long *__restrict__ off, uint8_t *__restrict__ out) {
+  __shared__ __attribute__((aligned(16))) unsigned long long s_stage[kSdDecodeStage / 8 + 4];      // (+ 16: head, + 16: the last word's other half)
+  __shared__ uint16_t s_long[kSdDecodeRows];
+  __shared__ uint32_t s_nlong;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  for (uint64_t base = (uint64_t)blockIdx.x * kSdDecodeRows; base < n; base += (uint64_t)gridDim.x * kSdDecodeRows) {
+    const uint32_t rows = n - base < kSdDecodeRows ? (uint32_t)(n - base) : kSdDecodeRows;
+    const uint64_t lo = off[base], total = off[base + rows] - lo;      // block-uniform
+    if (total == 0) continue;
+    if (total <= kSdDecodeStage) {
+      const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(out + lo) & 15u), end = head + (uint32_t)total;
+      uint4 *stage16 = reinterpret_cast<uint4 *>(s_stage);
+      if (tid == 0) s_nlong = 0;
+      for (uint32_t i = tid; i < (end + 15u) >> 4; i += kSdBlock) stage16[i] = uint4{0u, 0u, 0u, 0u};
+      __syncthreads();
+      if (tid < rows) {
+        const ulonglong2 r = recs[codes[base + tid]];
+        const uint32_t len = sd_rec_len(r);
+        if (len > kSdDecodeLaneMax) {
+          s_long[atomicAdd(&s_nlong, 1u)] = (uint16_t)tid;
+        } else if (len != 0u) {
+          const uint32_t at = head + (uint32_t)(off[base + tid] - lo);
+          sd_shifted_words(arena + r.x, len, at & 7u, 0, 1, [&](uint64_t k, uint64_t x) { atomicOr(&s_stage[(at >> 3) + k], (unsigned long long)x); });
+        }
+      }
+      __syncthreads();
+      const uint32_t nlong = s_nlong;
+      for (uint32_t i = wave; i < nlong; i += kSdBlock / 64) {
+        const uint32_t t = s_long[i];
+        const ulonglong2 r = recs[codes[base + t]];
+        const uint32_t at = head + (uint32_t)(off[base + t] - lo);
+        sd_shifted_words(arena + r.x, sd_rec_len(r), at & 7u, lane, 64, [&](uint64_t k, uint64_t x) { atomicOr(&s_stage[(at >> 3) + k], (unsigned long long)x); });
+      }
+      if (nlong != 0u) __syncthreads();
+      uint8_t *dst = out + lo - head;                           // 16-byte aligned; the stage's byte p belongs at dst + p, for head <= p < end
+      const uint32_t first = head != 0u ? 1u : 0u, last = end >> 4;      // [first, last): the words that are the tile's alone
+      for (uint32_t i = first + tid; i < last; i += kSdBlock) reinterpret_cast<uint4 *>(dst)[i] = stage16[i];
+      const uint8_t *stage8 = reinterpret_cast<const uint8_t *>(s_stage);
+      if (tid < 16u) {
+        if (head != 0u && tid >= head && tid < end) dst[tid] = stage8[tid];
+      } else if (tid < 32u) {
+        const uint32_t p = last * 16u + (tid - 16u);
+        if ((last != 0u || head == 0u) && p < end) dst[p] = stage8[p];
+      }
+      __syncthreads();                                          // (the next round zeroes the stage)
+    } else {
+      for (uint32_t t = wave; t < rows; t += kSdBlock / 64) {
+        const ulonglong2 r = recs[codes[base + t]];
+        const uint64_t len = sd_rec_len(r);
+        if (len == 0) continue;
+        uint8_t *d = out + off[base + t];
+        const uint32_t s = (uint32_t)(reinterpret_cast<uintptr_t>(d) & 7u);
+        uint8_t *d0 = d - s;                                    // 8-byte aligned
+        sd_shifted_words(arena + r.x, len, s, lane, 64, [&](uint64_t k, uint64_t x) {
+          const long long b0 = (long long)(k * 8) - (long long)s;      // the string's byte at the word's byte 0
+          const uint32_t t0 = b0 < 0 ? (uint32_t)(-b0) : 0u, t1 = (long long)len - b0 < 8 ? (uint32_t)((long long)len - b0) : 8u;
+          if (t0 == 0u && t1 == 8u) *reinterpret_cast<uint64_t *>(d0 + k * 8) = x;
+          else for (uint32_t b = t0; b < t1; ++b) d0[k * 8 + b] = (uint8_t)(x >> (b * 8u));
+        });
+      }
+    }
+  }
+}
+#else
+// Copy, the plain form (measured against the tiled one: DESIGN.md §5): k_sd_export's loop on gathered records — one lane per row, single
+// bytes up to the destination's next 8-byte boundary, whole words from there, single bytes for the tail.
+__global__ __launch_bounds__(kSdBlock) void k_sd_decode(const ulonglong2 *__restrict__ recs, const uint8_t *__restrict__ arena, const long long *__restrict__ codes,
+                                                        uint64_t n, const unsigned long long *__restrict__ off, uint8_t *__restrict__ out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kSdBlock) {
+    const ulonglong2 r = recs[codes[i]];
+    const uint32_t len = sd_rec_len(r);
+    const uint8_t *q = arena + r.x;
+    uint8_t *d = out + off[i];
+    uint32_t k = 0;
+    const uint32_t head = (uint32_t)((8u - (uint32_t)(reinterpret_cast<uintptr_t>(d) & 7u)) & 7u);
+    for (; k < len && k < head; ++k) d[k] = q[k];
+    for (; k + 8 <= len; k += 8) *reinterpret_cast<uint64_t *>(d + k) = se_load(q + k, 8);
+    for (; k < len; ++k) d[k] = q[k];
+  }
+}
+#endif
+
 static dim3 sd_grid(uint64_t items) { const uint64_t b = (items + kSdBlock - 1) / kSdBlock; return dim3((unsigned)(b < 16384 ? (b ? b : 1) : 16384)); }
 
 void launch_sd_probe(hipStream_t s, const StrBatch &B, const unsigned long long *table, uint64_t slots, const void *recs, const uint8_t *arena, uint64_t K,
@@ -300,6 +440,17 @@ void launch_sd_export_lens(hipStream_t s, const void *recs, uint64_t first, uint
 
 void launch_sd_export(hipStream_t s, const void *recs, const uint8_t *arena, uint64_t first, uint64_t n, const unsigned long long *off, uint8_t *out) {
   hipLaunchKernelGGL(k_sd_export, sd_grid(n), dim3(kSdBlock), 0, s, static_cast<const ulonglong2 *>(recs), arena, first, n, off, out);
+}
+
+void launch_sd_decode_lens(hipStream_t s, const void *recs, uint64_t K, const long long *codes, uint64_t n, uint32_t *cnt, uint32_t *flags) {
+  hipLaunchKernelGGL(k_sd_decode_lens, sd_grid(n), dim3(kSdBlock), 0, s, static_cast<const ulonglong2 *>(recs), K, codes, n, cnt, flags);
+}
+
+void launch_sd_decode(hipStream_t s, const void *recs, const uint8_t *arena, const long long *codes, uint64_t n, const unsigned long long *off, uint8_t *out) {
+  static_assert(kSdDecodeRows == kSdBlock, "a lane per row of the tile");
+  const uint64_t tiles = (n + kSdDecodeRows - 1) / kSdDecodeRows;      // past kSdDecodeMaxBlocks workgroups the tiles are taken in a grid stride
+  hipLaunchKernelGGL(k_sd_decode, dim3((unsigned)(tiles < kSdDecodeMaxBlocks ? (tiles ? tiles : 1) : kSdDecodeMaxBlocks)), dim3(kSdBlock), 0, s,
+                     static_cast<const ulonglong2 *>(recs), arena, codes, n, off, out);
 }
 
 // one kernel of this translation unit: tad_engine_create resolves it so that the unit's code object is loaded before the first batch

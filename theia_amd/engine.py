@@ -771,6 +771,47 @@ class KeyDict:
         self._engine._check(self._engine._lib.tad_keydict_export(self._engine._h, self._h, int(first_key), int(n_keys), ptrs, side.ctypes.data))
         return cols, side
 
+    def gather(self, key_id, cols=None, out="host"):
+        """The tuples of arbitrary keys (tad_keydict_gather): key_id a numpy array or a DeviceArray of uint64 ids, in any order and with
+        repeats; cols the tuple columns wanted (None = all of them).  Returns (columns, side): columns a list of int64 arrays, one per
+        entry of cols, with column c of key key_id[i] at i, and side a uint8 array (0 = side a, 1 = side b) — numpy arrays
+        (out="host") or DeviceArrays (out="device": what StringDict.decode takes without a copy).  The call runs on the device arrays
+        when key_id or the outputs live there.  An id that is not below num_keys() is refused."""
+        eng = self._engine
+        _need_feature(eng._lib, "DICT_DECODE", "tad_keydict_gather")
+        if out not in ("host", "device"):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "KeyDict.gather: out must be host or device")
+        want = list(range(self.n_cols)) if cols is None else [int(c) for c in cols]
+        if any(c < 0 or c >= self.n_cols for c in want) or len(set(want)) != len(want):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "KeyDict.gather: cols names each of the %d key columns at most once" % self.n_cols)
+        ids = key_id
+        if not isinstance(ids, DeviceArray):
+            ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+            if out == "device":
+                n_ids = ids.size
+                ids = DeviceArray.from_host(eng, ids if n_ids else np.zeros(1, np.uint64))
+                ids.n = n_ids
+        dev = isinstance(ids, DeviceArray)
+        n = ids.n if dev else ids.size
+        outs = {c: _out_array(eng, dev, n, np.int64, room=max(n, 1)) for c in want}
+        if dev:
+            side = DeviceArray(eng, (n + 7) // 8 if n else 1, np.uint64)
+            side_ptr = side.ptr
+        else:
+            side = np.zeros(n, np.uint8)
+            side_ptr = side.ctypes.data if n else None
+        ptrs = (C.c_void_p * self.n_cols)(*[outs[c][1] if c in outs else None for c in range(self.n_cols)])
+        rc = eng._lib.tad_keydict_gather(eng._h, self._h, (ids.ptr if dev else (ids.ctypes.data if n else None)), n,
+                                         capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST, ptrs, side_ptr)
+        eng._check(rc)
+        columns = [outs[c][0] for c in want]
+        if dev:
+            side = side.view(0, n, np.uint8)
+            if out == "host":
+                columns = [c.to_host() for c in columns]
+                side = side.to_host()
+        return columns, side
+
     def load(self, cols, side=None):
         """Fill this EMPTY dictionary so that key i is tuple i (tad_keydict_import): what export() returned, after a restart.
         side None = every key on side 0."""
@@ -882,6 +923,42 @@ class StringDict:
         decoding result rows"""
         import pyarrow as pa
         offsets, data = self.export(first, n)
+        return pa.Array.from_buffers(pa.large_string(), offsets.size - 1, [None, pa.py_buffer(offsets), pa.py_buffer(data)])
+
+    def decode(self, codes, out="host"):
+        """The strings of arbitrary codes in Arrow's layout (tad_strdict_decode): codes a numpy array or a DeviceArray of int64 (what
+        KeyDict.gather returns for a string key column), in any order and with repeats.  Returns (offsets int64[n + 1], data uint8[...]):
+        the bytes of value codes[i] are data[offsets[i]:offsets[i + 1]] — numpy arrays (out="host") or DeviceArrays (out="device"),
+        wherever the codes live.  A code that is not in [0, num_values()) is refused: TAD_CODE_NONE decodes to nothing."""
+        eng = self._engine
+        _need_feature(eng._lib, "DICT_DECODE", "tad_strdict_decode")
+        if out not in ("host", "device"):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "StringDict.decode: out must be host or device")
+        dev_in = isinstance(codes, DeviceArray)
+        if not dev_in:
+            codes = np.ascontiguousarray(codes, dtype=np.int64).reshape(-1)
+        n = codes.n if dev_in else codes.size
+        cptr = codes.ptr if dev_in else (codes.ctypes.data if n else None)
+        cmem = capi.TAD_MEM_DEVICE if dev_in else capi.TAD_MEM_HOST
+        need = capi.u64()
+        eng._check(eng._lib.tad_strdict_decode(eng._h, self._h, cptr, n, cmem, None, None, 0, capi.TAD_MEM_HOST, C.byref(need)))
+        total = int(need.value)
+        if out == "device":
+            offsets = DeviceArray(eng, n + 1, np.int64)
+            room = DeviceArray(eng, max((total + 7) // 8, 1), np.uint64)
+            data, optr, dptr, omem = room.view(0, total, np.uint8), offsets.ptr, room.ptr, capi.TAD_MEM_DEVICE
+        else:
+            offsets = np.zeros(n + 1, dtype=np.int64)
+            data = np.zeros(total, dtype=np.uint8)
+            optr, dptr, omem = offsets.ctypes.data, (data.ctypes.data if total else None), capi.TAD_MEM_HOST
+        eng._check(eng._lib.tad_strdict_decode(eng._h, self._h, cptr, n, cmem, optr, dptr if total else None, total, omem, C.byref(need)))
+        return offsets, data
+
+    def take(self, codes):
+        """the values of arbitrary codes as a pyarrow large_string array (decode on the host side of the link): values() for the codes a
+        result names, not for the whole vocabulary"""
+        offsets, data = self.decode(codes, out="host")
+        import pyarrow as pa
         return pa.Array.from_buffers(pa.large_string(), offsets.size - 1, [None, pa.py_buffer(offsets), pa.py_buffer(data)])
 
     def load(self, values):

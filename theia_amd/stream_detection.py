@@ -3,8 +3,10 @@
 `anomaly_detection` (anomaly_detection.py) answers one job from the flow table: it reads the rows, applies the job's filters and runs
 the batch job.  A `StreamingAnomalyDetection` is fed the flow rows as they arrive — in any order — and answers the same jobs from what it
 keeps on the device: a key dictionary (KeyDict: the mode's key tuples -> stable ids), a series state (TadState with history and times,
-fed through TadEngine.merge_stream), one string dictionary per string key column (StringDict: strings -> stable codes, in HBM as well) and,
-on the host, the key table.
+fed through TadEngine.merge_stream) and one string dictionary per string key column (StringDict: strings -> stable codes, in HBM as
+well).  Nothing grows on the host: a job's result rows name key ids, and those ids alone are decoded — KeyDict.gather gives their code
+tuples, StringDict.decode the codes' strings (_KeyColumn) — so `snapshot()` / `restore()` of the three device structures is all a restart
+needs.
 
 The job's name filters (--pod-name, --pod-namespace, --pod-label, --external-ip, --svc-port-name) are predicates on KEY columns of the
 mode, so a job is a key selection: the filter is evaluated once per distinct string of the vocabulary, on the device (StringDict.match:
@@ -45,14 +47,74 @@ def _encode(vocab, flows, name):
     return vocab.encode(_arrow(c))[0]
 
 
-def _string_at(flows, name, row):
-    c = flows[name]
-    return str(c.values[c.codes[row]]) if isinstance(c, _ad.DictColumn) else str(np.asarray(c)[row])
-
-
 def _code_of(vocab, s):
     """the code the dictionary holds for s, or -1"""
     return int(vocab.lookup(_arrow([s]))[0])
+
+
+def _strings_of(offsets, data):
+    """a decoded column (Arrow's layout, UTF-8) -> an object array of str"""
+    n = offsets.size - 1
+    try:
+        import pyarrow as pa
+    except ImportError:      # the same strings, one slice at a time
+        raw, vals = data.tobytes(), np.empty(n, dtype=object)
+        vals[:] = [raw[a:b].decode("utf-8") for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist())]
+        return vals
+    return pa.Array.from_buffers(pa.large_string(), n, [None, pa.py_buffer(offsets), pa.py_buffer(data)]).to_numpy(zero_copy_only=False)
+
+
+class _KeyDecoder:
+    """What a job's key table shares: one KeyDict.gather of the unique ids the result rows name (the code tuples stay on the device) and
+    one StringDict.decode per string column, made when the first column is asked and kept for the others."""
+
+    def __init__(self, key_dict, vocab):
+        self.key_dict, self.vocab = key_dict, vocab
+        self._kid = self._cols = None
+
+    def columns(self, kid):
+        """kid: the rows' key ids -> [the strings of key column 0, of column 1, ..., the sides], one entry per row"""
+        kid = np.ascontiguousarray(np.asarray(kid).astype(np.uint64))
+        if self._kid is None or self._kid.shape != kid.shape or not np.array_equal(self._kid, kid):
+            if kid.size < 2 or bool((kid[1:] >= kid[:-1]).all()):      # every key once (a key has many result rows); rows in key order need no sort
+                first = np.ones(kid.size, dtype=bool)
+                first[1:] = kid[1:] != kid[:-1]
+                uniq, inv = kid[first], np.cumsum(first) - 1
+            else:
+                uniq, inv = np.unique(kid, return_inverse=True)
+            codes, side = self.key_dict.gather(uniq, out="device")
+            cols = []
+            for c, v in zip(codes, self.vocab):
+                cols.append(_strings_of(*v.decode(c, out="host"))[inv])
+                c.free()
+            cols.append(side.to_host()[inv])
+            side.free()
+            self._kid, self._cols = kid, cols
+        return self._cols
+
+
+class _KeyColumn:
+    """One column of a streaming job's key table, decoded ON DEMAND from the dictionaries on the device — what DeviceKeyColumn is to the
+    batch path's device ingest: `col[kid]` gives the column's values for the rows' key ids.  which: the index of a string key column, or
+    "direction" (from the key's side: side a = inbound)."""
+
+    def __init__(self, decoder, which):
+        self.decoder, self.which = decoder, which
+
+    def __len__(self):
+        return self.decoder.key_dict.num_keys()
+
+    def __getitem__(self, kid):
+        if np.asarray(kid).size == 0:
+            return np.zeros(0, dtype=object)
+        cols = self.decoder.columns(kid)
+        if self.which == "direction":
+            return np.where(cols[-1] == 1, "outbound", "inbound").astype(object)
+        return cols[self.which]
+
+    def __array__(self, dtype=None, copy=None):
+        a = self[np.arange(len(self), dtype=np.uint64)]
+        return a if dtype is None else a.astype(dtype)
 
 
 class StreamingAnomalyDetection:
@@ -80,7 +142,6 @@ class StreamingAnomalyDetection:
         self._vocab = [self._engine.string_dict() for _ in range(2 if agg_flow == "pod" else 1)]     # pod: namespaces, labels / names
         self._dict = self._engine.key_dict(len(self._vocab))
         self._state = None
-        self._keys = [[] for _ in _ad.KEY_COLUMNS[self.mode]]      # the host key table: key id -> the mode's key columns
 
     @property
     def state(self):
@@ -88,7 +149,7 @@ class StreamingAnomalyDetection:
 
     @property
     def num_keys(self):
-        return len(self._keys[0])
+        return self._dict.num_keys()
 
     def feed(self, flows):
         """One batch of flow rows (a column dict as anomaly_detection takes it), in any order; rows of a (key, flowEndSeconds) group may
@@ -109,14 +170,7 @@ class StreamingAnomalyDetection:
                 sides.append((codes, keep & (codes[1] != _code_of(self._vocab[1], ""))))
             if not (sides[0][1].any() or sides[1][1].any()):
                 return None
-            key, key2, first, _ = self._dict.encode(sides[0][0], sides[0][1], sides[1][0], sides[1][1])
-            for v in np.asarray(first).tolist():                   # the host key table: the new keys' strings, read at their first rows
-                b = v >= n
-                side = "source" if b else "destination"
-                row = v - n if b else v
-                self._keys[0].append(_string_at(flows, side + "PodNamespace", row))
-                self._keys[1].append(_string_at(flows, side + ident, row))
-                self._keys[2].append("outbound" if b else "inbound")
+            key, key2, _, _ = self._dict.encode(sides[0][0], sides[0][1], sides[1][0], sides[1][1], max_new=0)
         else:
             name = "destinationIP" if self.agg_flow == "external" else "destinationServicePortName"
             codes = _encode(self._vocab[0], flows, name)
@@ -126,12 +180,12 @@ class StreamingAnomalyDetection:
                 keep &= codes != _code_of(self._vocab[0], "")
             if not keep.any():
                 return None
-            key, key2, first, _ = self._dict.encode([codes], keep)
-            self._keys[0] += [_string_at(flows, name, v) for v in np.asarray(first).tolist()]
+            key, key2, _, _ = self._dict.encode([codes], keep, max_new=0)
+        num_keys = self.num_keys
         if self._state is None:
-            self._state = eng.state_create(self.num_keys, history=True, series=True, times=True)
-        elif self.num_keys > self._state.num_keys:
-            self._state.resize(self.num_keys)
+            self._state = eng.state_create(num_keys, history=True, series=True, times=True)
+        elif num_keys > self._state.num_keys:
+            self._state.resize(num_keys)
         return eng.merge_stream(self._state, key, flow_end, value, agg_flow=self.agg_flow, key_id2=key2)
 
     def _equal(self, col, s):
@@ -169,14 +223,57 @@ class StreamingAnomalyDetection:
         if algo_type not in _ad.VALID_ALGOS:
             raise ValueError("Algorithm should be in {}".format(" or ".join(_ad.VALID_ALGOS)))
         terms = self._terms(pod_label or "", pod_name or "", pod_namespace or "", external_ip or "", svc_port_name or "")
-        prep = _ad.PreparedColumns(self.mode, None, None, None, None, None,
-                                   {name: np.asarray(vals, dtype=object) for name, vals in zip(_ad.KEY_COLUMNS[self.mode], self._keys)}, 0, 0)
+        decoder = _KeyDecoder(self._dict, self._vocab)      # the key table: decoded on demand, for the keys with result rows
+        table = {name: _KeyColumn(decoder, "direction" if name == "direction" else i) for i, name in enumerate(_ad.KEY_COLUMNS[self.mode])}
+        prep = _ad.PreparedColumns(self.mode, None, None, None, None, None, table, 0, 0)
         if self._state is None:
             return {}, [_ad._sentinel_row(algo_type, self.agg_flow, tad_id)]
         keep, _ = self._dict.select(terms, out="device")
         to_t = _ad._epoch(end_time) if self.agg_flow != "pod" else 0
         res = self._engine.run_state_keys(self._state, keep, to_t=to_t, algo=algo_type, job_id=str(tad_id or ""))
         return res.stats, _ad.result_rows(prep, res, algo_type, self.agg_flow, tad_id)
+
+    def snapshot(self):
+        """Everything the instance holds, as a dict of numpy arrays (np.savez takes it as it is): the state's exports (moments, history,
+        series, times), the key dictionary's tuples and sides, and every string dictionary's values in Arrow's layout.  `restore` builds
+        an instance from it that continues as this one would."""
+        snap = {"mode": np.asarray([self.mode]), "num_keys": np.asarray([self.num_keys], dtype=np.uint64)}
+        cols, side = self._dict.export()
+        for c, col in enumerate(cols):
+            snap["key_col%d" % c] = col
+        snap["key_side"] = side
+        for i, v in enumerate(self._vocab):
+            snap["vocab%d_offsets" % i], snap["vocab%d_data" % i] = v.export()
+        if self._state is not None:
+            for name, a in self._state.export().items():
+                snap["state_" + name] = a
+            snap["state_history_len"], snap["state_history"] = self._state.export_history()
+            snap["state_series_len"], snap["state_series"] = self._state.export_series()
+            snap["state_times"] = self._state.export_times()
+        return snap
+
+    @classmethod
+    def restore(cls, engine, snapshot, agg_flow="svc", pod_ident="labels", ns_ignore_list=()):
+        """A new instance holding what `snapshot()` returned (after a restart: np.load of the saved dict).  agg_flow / pod_ident must be
+        the snapshot's; ns_ignore_list applies to the rows fed from here on."""
+        self = cls(engine, agg_flow, pod_ident, ns_ignore_list)
+        try:
+            if str(np.asarray(snapshot["mode"]).reshape(-1)[0]) != self.mode:
+                raise ValueError("the snapshot was taken in mode %r, not %r" % (str(np.asarray(snapshot["mode"]).reshape(-1)[0]), self.mode))
+            for i, v in enumerate(self._vocab):
+                v.load((np.asarray(snapshot["vocab%d_offsets" % i]), np.asarray(snapshot["vocab%d_data" % i])))
+            self._dict.load([snapshot["key_col%d" % c] for c in range(len(self._vocab))], snapshot["key_side"])
+            if "state_n" in snapshot:
+                st = self._engine.state_create(len(snapshot["state_n"]), history=True, series=True, times=True)
+                self._state = st
+                st.load({f: snapshot["state_" + f] for f in ("n", "avg", "m2", "ewma", "last_t")})
+                st.load_history(snapshot["state_history_len"], snapshot["state_history"])
+                st.load_series(snapshot["state_series_len"], snapshot["state_series"])
+                st.load_times(snapshot["state_times"])
+        except Exception:
+            self.close()
+            raise
+        return self
 
     def close(self):
         if self._state is not None:

@@ -170,7 +170,7 @@ def plan_settle(pl, T, narrow):
 
 
 def lattice_mode(step, nb):
-    """make_lattice (tad_engine.cpp:185)"""
+    """make_lattice (tad_rows.h)"""
     if step == 1:
         return 0
     return 1 if step < (1 << 32) and (nb == 0 or nb - 1 <= ((1 << 32) - 1) // step) else 2
@@ -544,7 +544,7 @@ def test_tile_plan_ends_at_65536_buckets(engine, T, dense):
 
 @pytest.mark.parametrize("step,mode", [(1, 0), (65538, 1), (65539, 2)])
 def test_lattice_modes_at_the_32_bit_edge(engine, step, mode):
-    """make_lattice / p_bucket / the fast path of pass B: mode 0 (step 1), mode 1 (multiply-high, exact for d < 2^32: the last bucket
+    """make_lattice / lattice_bucket / the fast path of pass B: mode 0 (step 1), mode 1 (multiply-high, exact for d < 2^32: the last bucket
     at d = 2^32 - 4), mode 2 (division, the GENERIC kernels) when (nb - 1) * step > 2^32 - 1.  Rows on buckets 0, 1, T - 2, T - 1, so
     the gcd is the step.  Derived, hinted, and hinted one bucket too short (a second attempt, the same rows)."""
     K, T = 2, 65535

@@ -20,10 +20,10 @@ struct Job {
   JobParams jp;
   tad_plan plan;               // the engine's plan when the job was admitted
   bool op_max, has2;
-  uint64_t n, K, slots_all;
+  uint64_t K, slots_all;
   RowFilter rf;
-  int cw;                      // narrow input columns (tad.h, tad_columns): read at their own width by the Stage-0 kernels, nothing is widened first
-  const void *d_key, *d_key2, *d_te, *d_ts, *d_val;
+  RowCols rows;                // the table on the device (stage_columns).  rows.cw: narrow input columns (tad.h, tad_columns) are read at their own
+                               // width by the Stage-0 kernels, nothing is widened first
   DevCounters *ctr;
   bool empty;                  // no live row: nothing to group
 };
@@ -129,25 +129,27 @@ int detect_and_count(JobCtx *e, Grid g, JobParams &jp, DevCounters *ctr, uint64_
 }
 
 // width: bytes per row of the column (8, or 4 for a narrow key / time column): a host column crosses PCIe at its own width
-int stage_column(JobCtx *e, DevBuf &buf, const void *src, uint64_t n, tad_mem mem, const void **dev, uint64_t width = 8) {
+template <typename T>
+int stage_column(JobCtx *e, DevBuf &buf, const T *src, uint64_t n, tad_mem mem, const T **dev, uint64_t width = 8) {
   if (!src) { *dev = nullptr; return TAD_OK; }
   if (mem == TAD_MEM_DEVICE) { *dev = src; return TAD_OK; }
   int rc = ensure(e, buf, n * width);
   if (rc != TAD_OK) return rc;
   HIP_TRY(e, hipMemcpyAsync(buf.p, src, n * width, hipMemcpyHostToDevice, e->stream));
-  *dev = buf.p;
+  *dev = static_cast<const T *>(buf.p);
   return TAD_OK;
 }
 
 int stage_columns(JobCtx *e, Job &j) {
   const tad_columns *cols = j.cols;
-  const uint64_t kw = (j.cw & kColKey32) ? 4 : 8, tw = (j.cw & kColTime32) ? 4 : 8;
+  RowCols &r = j.rows;
+  const uint64_t kw = (r.cw & kColKey32) ? 4 : 8, tw = (r.cw & kColTime32) ? 4 : 8;
   int rc;
-  if ((rc = stage_column(e, e->in_key, cols->key_id, j.n, cols->memory, &j.d_key, kw)) != TAD_OK) return rc;
-  if ((rc = stage_column(e, e->in_key2, cols->key_id2, j.n, cols->memory, &j.d_key2, kw)) != TAD_OK) return rc;
-  if ((rc = stage_column(e, e->in_te, cols->flow_end_s, j.n, cols->memory, &j.d_te, tw)) != TAD_OK) return rc;
-  if ((rc = stage_column(e, e->in_ts, cols->flow_start_s, j.n, cols->memory, &j.d_ts, tw)) != TAD_OK) return rc;
-  return stage_column(e, e->in_val, cols->value, j.n, cols->memory, &j.d_val);
+  if ((rc = stage_column(e, e->in_key, cols->key_id, r.n, cols->memory, &r.key, kw)) != TAD_OK) return rc;
+  if ((rc = stage_column(e, e->in_key2, cols->key_id2, r.n, cols->memory, &r.key2, kw)) != TAD_OK) return rc;
+  if ((rc = stage_column(e, e->in_te, cols->flow_end_s, r.n, cols->memory, &r.t_end, tw)) != TAD_OK) return rc;
+  if ((rc = stage_column(e, e->in_ts, cols->flow_start_s, r.n, cols->memory, &r.t_start, tw)) != TAD_OK) return rc;
+  return stage_column(e, e->in_val, cols->value, r.n, cols->memory, &r.value);
 }
 
 // ---- the time lattice ----
@@ -157,7 +159,7 @@ int stage_columns(JobCtx *e, Job &j) {
 int pass_a(JobCtx *e, const Job &j, const Stage0Retry &rs, Attempt &a, int *meta_blocks) {
   hipStream_t s = e->stream;
   int rc;
-  const uint64_t n = j.n, K = j.K;
+  const uint64_t n = j.rows.n, K = j.K;
   a.v2 = !j.empty && j.plan.stage0 != 1 && !rs.v1 && (j.plan.stage0 == 2 || n >= (1ull << 22)) && part_plan_bins(n, K, j.has2, &a.pl);
   if (a.v2 && e->hold) e->hold->acquire();   // pass B / pass C workgroups need whole CUs: ARIMA fits of other jobs in flight make room (PauseHold)
   if ((rc = ensure(e, e->meta, sizeof(MetaPartial) * kMetaBlocks)) != TAD_OK) return rc;
@@ -170,13 +172,12 @@ int pass_a(JobCtx *e, const Job &j, const Stage0Retry &rs, Attempt &a, int *meta
   const tad_key_hist *kh = j.cols->key_hist;
   a.use_kh = j.depth == 0 && !rs.kh_rejected && kh != nullptr && kh->bins != nullptr && rs.lat_mode != 2 && kh->n_rows == n && kh->num_keys == K &&
              kh->sides == (j.has2 ? 2u : 1u) && kh->workgroups == (uint32_t)pl.G && kh->nbins == pl.nbins && kh->shift == (uint32_t)pl.shift_bin &&
-             kh->chunk_rows == pl.chunk && j.rf.end_time == 0 && !(j.d_ts != nullptr && j.rf.start_time != 0);
+             kh->chunk_rows == pl.chunk && j.rf.end_time == 0 && !(j.rows.t_start != nullptr && j.rf.start_time != 0);
   if ((rc = ensure(e, e->binhist, (size_t)pl.G * pl.nbins * 4)) != TAD_OK) return rc;
   // pass A may histogram a SAMPLE of the rows (1/16 of the key column, plus the chunk ends, instead of all of it): pass B's regions are then
   // sized from the estimate with 6 sigma of slack; a region that still turns out too small (keys arriving in bursts the sample missed)
   // raises DEV_ERR_REGION_FULL and the job is redone with the exact histogram.  tad_plan.histogram = 1 disables it.
-  a.hist_sampled = launch_meta_hist(s, (const uint64_t *)j.d_key, (const uint64_t *)j.d_key2, (const int64_t *)j.d_te, (const int64_t *)j.d_ts, n, K, j.rf,
-                                    pl, static_cast<MetaPartial *>(e->meta.p), static_cast<uint32_t *>(e->binhist.p), j.ctr, j.cw,
+  a.hist_sampled = launch_meta_hist(s, j.rows, K, j.rf, pl, static_cast<MetaPartial *>(e->meta.p), static_cast<uint32_t *>(e->binhist.p), j.ctr,
                                     // small regions (many keys: C4 has ~50 records per workgroup and 128-key block) make pass C's walk
                                     // over the regions cost more than the sampled pass A saves: sample only when a region of a
                                     // 128-key block is expected to hold a few hundred records
@@ -201,10 +202,9 @@ int derive_lattice(JobCtx *e, Job &j, Stage0Retry &rs, Attempt &a) {
   a.L = make_lattice(j.cols->t0, a.hinted ? j.cols->step : 1, j.cols->n_buckets);
   if ((rc = pass_a(e, j, rs, a, &meta_blocks)) != TAD_OK) return rc;
   if (!a.hinted && !j.empty && (!a.v2 || rs.lat_mode == 2)) {
-    meta_blocks = (int)((j.n + 255) / 256);
+    meta_blocks = (int)((j.rows.n + 255) / 256);
     if (meta_blocks > kMetaBlocks) meta_blocks = kMetaBlocks;
-    launch_meta(s, (const uint64_t *)j.d_key, (const uint64_t *)j.d_key2, (const int64_t *)j.d_te, (const int64_t *)j.d_ts, j.n, j.rf,
-                static_cast<MetaPartial *>(e->meta.p), meta_blocks, j.cw);
+    launch_meta(s, j.rows, j.rf, static_cast<MetaPartial *>(e->meta.p), meta_blocks);
   }
   if (!a.hinted && !j.empty) {
     HIP_TRY(e, hipMemcpyAsync(e->meta_host, e->meta.p, sizeof(MetaPartial) * meta_blocks, hipMemcpyDeviceToHost, s));
@@ -290,7 +290,7 @@ void sparse_sorted_list(JobCtx *e, const Job &j, const Attempt &a, const SparseS
 int sparse_sort(JobCtx *e, const Job &j, Stage0Retry &rs, Attempt &a, SparseSort &ss) {
   hipStream_t s = e->stream;
   int rc;
-  const uint64_t n = j.n, K = j.K, slots_all = j.slots_all;
+  const uint64_t n = j.rows.n, K = j.K, slots_all = j.slots_all;
   const Lattice L = a.L;
   // Big sparse tables (pass A ran with its key-bin histogram): the dense path's partition pass brings every key block's rows together as
   // 8-byte records, a workgroup per key sub-range sorts them in LDS (tad_sparse.hip: launch_sparse_sort) — the columns are read once and
@@ -299,7 +299,7 @@ int sparse_sort(JobCtx *e, const Job &j, Stage0Retry &rs, Attempt &a, SparseSort
   spl = a.pl;
   a.sp_part = a.v2 && !rs.sparse_lsd && part_plan_sparse(K, L.nb, j.has2, &spl);
   if (a.sp_part) {
-    part_plan_wc(slots_all, columns_aligned16(j.d_key, j.d_key2, j.d_te, j.d_val), j.has2, 2, &spl);
+    part_plan_wc(slots_all, j.rows.aligned16(), j.has2, 2, &spl);
     if (spl.wc_cap == 0 || slots_all + spl.pad_slots >= (1ull << 32)) a.sp_part = false;
   }
   if ((rc = decide(e, j, rs, a, 0u)) != TAD_OK || a.retry) return rc;   // (the partition sort after a sampled pass A: the exact histogram first)
@@ -338,14 +338,13 @@ int sparse_sort(JobCtx *e, const Job &j, Stage0Retry &rs, Attempt &a, SparseSort
     launch_part_offsets(s, a.binhist, spl, offs32, static_cast<uint32_t *>(e->part_total.p), part_start, false,
                         static_cast<const MetaPartial *>(e->meta.p), n, slots, e->slices.p, Grid{});
     // (no overflow list: a value that does not fit the record raises DEV_ERR_OVERFLOW_LIST and the LSD sort redoes the job)
-    launch_partition(s, (const uint64_t *)j.d_key, (const uint64_t *)j.d_key2, (const int64_t *)j.d_te, (const int64_t *)j.d_ts, (const uint64_t *)j.d_val, n, K,
-                     j.rf, L, spl, offs32, part_start, e->recs.p, nullptr, dev_ovf_count(e), 0, j.ctr, nullptr, nullptr, j.cw);
+    launch_partition(s, j.rows, K, j.rf, L, spl, offs32, part_start, e->recs.p, nullptr, dev_ovf_count(e), 0, j.ctr);
     launch_sparse_sort(s, e->recs.p, part_start, a.binhist, spl, K, L.step, j.op_max,
                        ucomp, static_cast<unsigned long long *>(e->sp_comp_b.p), static_cast<unsigned long long *>(e->sp_val_b.p),
                        reinterpret_cast<uint32_t *>(uval), e->sp_temp.p, ss.d_runs, j.ctr);
-  } else if (launch_sparse_group(s, (const uint64_t *)j.d_key, (const uint64_t *)j.d_key2, (const int64_t *)j.d_te, (const int64_t *)j.d_ts, (const uint64_t *)j.d_val, n, K,
+  } else if (launch_sparse_group(s, j.rows, K,
                                  j.rf, L.t0, span, j.op_max, ucomp, uval, static_cast<unsigned long long *>(e->sp_comp_b.p),
-                                 static_cast<unsigned long long *>(e->sp_val_b.p), e->sp_temp.p, tb, ss.d_runs, j.ctr, j.cw) != 0)
+                                 static_cast<unsigned long long *>(e->sp_val_b.p), e->sp_temp.p, tb, ss.d_runs, j.ctr) != 0)
     return fail(e, TAD_ERR_HIP, "sparse Stage 0: sort / reduce failed");
   if (j.depth == 0) e->sp_by_partition = a.sp_part;
   // (the partition sort counted both numbers itself)
@@ -401,8 +400,8 @@ int sparse_rank_grid(JobCtx *e, const Job &j, Stage0Retry &rs, Attempt &a, const
     const DevCounters c0 = *e->ctr_host;
     if ((rc = decide(e, j, rs, a, c0.err & (DEV_ERR_KEY_RANGE | DEV_ERR_OFF_LATTICE))) != TAD_OK || a.retry) return rc;
     a.finished = true;
-    if (j.points_mode) return sparse_points_direct(e, j.n, c0.rows_used, a.L, P, j.ctr, j.out_memory, points_out);   // Stage 0 alone needs no grid
-    return run_sparse_classes(e, j.job, j.jp, j.op_max, j.n, c0.rows_used, K, a.L, P, tmax, j.out_memory, out);
+    if (j.points_mode) return sparse_points_direct(e, j.rows.n, c0.rows_used, a.L, P, j.ctr, j.out_memory, points_out);   // Stage 0 alone needs no grid
+    return run_sparse_classes(e, j.job, j.jp, j.op_max, j.rows.n, c0.rows_used, K, a.L, P, tmax, j.out_memory, out);
   }
   if (a.need > e->ws_limit)
     return fail(e, TAD_ERR_GRID_TOO_LARGE, "sparse point grid needs %llu bytes (%llu keys x longest series %u points) > workspace limit %llu",
@@ -473,10 +472,10 @@ int settle_setup(JobCtx *e, Job &j, const Stage0Retry &rs, Attempt &a, SettleArg
 // aggregates every tile in LDS and writes the grid.
 int stage0_tiles(JobCtx *e, Job &j, Stage0Retry &rs, Attempt &a) {
   hipStream_t s = e->stream;
-  const uint64_t n = j.n, K = j.K;
+  const uint64_t n = j.rows.n, K = j.K;
   PartPlan &pl = a.pl;
   int rc;
-  part_plan_wc(a.hist_sampled ? sampled_slots_bound(j.slots_all, pl) : j.slots_all, columns_aligned16(j.d_key, j.d_key2, j.d_te, j.d_val), j.has2, j.plan.partition_pass, &pl);
+  part_plan_wc(a.hist_sampled ? sampled_slots_bound(j.slots_all, pl) : j.slots_all, j.rows.aligned16(), j.has2, j.plan.partition_pass, &pl);
   // nparts is only known now: the bound is recomputed with the final plan (part_plan_bins' G, part_plan_tiles' nparts)
   const uint64_t slots = a.hist_sampled ? sampled_slots_bound(j.slots_all, pl) : j.slots_all + pl.pad_slots;
   {
@@ -509,8 +508,7 @@ int stage0_tiles(JobCtx *e, Job &j, Stage0Retry &rs, Attempt &a) {
   uint32_t *ovf_keys;
   if ((rc = settle_setup(e, j, rs, a, &settle, &ovf_keys)) != TAD_OK) return rc;
   HIP_TRY(e, hipEventRecord(e->ev[2], s));
-  launch_partition(s, (const uint64_t *)j.d_key, (const uint64_t *)j.d_key2, (const int64_t *)j.d_te, (const int64_t *)j.d_ts,
-                   (const uint64_t *)j.d_val, n, K, j.rf, a.L, pl, offs32, part_start, e->recs.p, ovf, ovf_count, kOverflowCap, j.ctr, fin, ovf_keys, j.cw);
+  launch_partition(s, j.rows, K, j.rf, a.L, pl, offs32, part_start, e->recs.p, ovf, ovf_count, kOverflowCap, j.ctr, fin, ovf_keys);
   HIP_TRY(e, hipEventRecord(e->ev[3], s));
   launch_tile_aggregate(s, e->recs.p, part_start, pl, slots, e->slices.p, a.g, j.op_max, ovf, ovf_count, kOverflowCap,
                         a.hist_sampled ? offs32 : nullptr, fin, settle);
@@ -540,8 +538,7 @@ int stage0_dense(JobCtx *e, Job &j, Stage0Retry &rs, Attempt &a) {
   }
   HIP_TRY(e, hipEventRecord(e->ev[2], s));
   if (!j.empty)
-    launch_scatter(s, (const uint64_t *)j.d_key, (const uint64_t *)j.d_key2, (const int64_t *)j.d_te, (const int64_t *)j.d_ts,
-                   (const uint64_t *)j.d_val, j.n, j.rf, a.L, a.g, j.op_max, j.ctr, j.cw);
+    launch_scatter(s, j.rows, j.rf, a.L, a.g, j.op_max, j.ctr);
   HIP_TRY(e, hipEventRecord(e->ev[3], s));
   return TAD_OK;
 }
@@ -624,7 +621,7 @@ int count_stream(JobCtx *e, const Job &j, const Attempt &a, StreamBatches *sb, u
 
 // the Stage-0 part of tad_stats that a points result and a rows result share
 void stage0_stats(JobCtx *e, const Job &j, const Attempt &a, const DevCounters &c, int attempts, tad_stats &st) {
-  st.rows_in = j.n;
+  st.rows_in = j.rows.n;
   st.rows_used = c.rows_used;
   st.n_keys = c.n_keys;
   st.n_points = c.n_points;
@@ -727,7 +724,7 @@ int job_merge(JobCtx *e, const Job &j, const Attempt &a, const DevCounters &c, i
   HIP_TRY(e, hipEventRecord(e->ev[4], e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   tad_merge_stats &ms = mc->stats;
-  ms.rows_in = j.n;
+  ms.rows_in = j.rows.n;
   ms.rows_used = c.rows_used;
   ms.stage0_path = a.stage0_path();
   ms.stage0_attempts = attempts;
@@ -794,12 +791,12 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
   j.plan = e->plan;
   j.op_max = job->value_op == TAD_OP_MAX || (job->value_op == TAD_OP_AUTO && job->agg_flow == TAD_AGG_NONE);
   j.has2 = cols->key_id2 != nullptr;
-  j.n = cols->n_rows;
+  j.rows.n = cols->n_rows;
   j.K = cols->num_keys;
-  j.slots_all = j.n * (j.has2 ? 2 : 1);
+  j.slots_all = j.rows.n * (j.has2 ? 2 : 1);
   j.rf = RowFilter{job->start_time, job->end_time};
-  j.cw = ((job->flags & TAD_FLAG_KEY_U32) ? kColKey32 : 0) | ((job->flags & TAD_FLAG_TIME_U32) ? kColTime32 : 0);
-  j.empty = (j.n == 0 || j.K == 0);
+  j.rows.cw = ((job->flags & TAD_FLAG_KEY_U32) ? kColKey32 : 0) | ((job->flags & TAD_FLAG_TIME_U32) ? kColTime32 : 0);
+  j.empty = (j.rows.n == 0 || j.K == 0);
   int rc;
   if ((rc = stage_columns(e, j)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->counters, kTailBytes)) != TAD_OK) return rc;
@@ -808,7 +805,7 @@ int run_job_locked(JobCtx *e, const tad_job *job, const tad_columns *cols, tad_m
   if (depth == 0) HIP_TRY(e, hipEventRecord(e->ev[6], s));   // (class jobs of a skewed sparse table re-record ev[0..5])
 
   // what the context's last job learnt about a table of this shape: skip the attempt that is known to fail
-  const Stage0Shape shape{j.n, j.K, j.has2, (int)job->algo, (int)j.op_max};
+  const Stage0Shape shape{j.rows.n, j.K, j.has2, (int)job->algo, (int)j.op_max};
   Stage0Retry rs = Stage0Retry::start(j.plan, cols->n_buckets > 0, depth == 0 ? &e->learnt : nullptr, shape);
   for (int attempt = 1; attempt <= kStage0MaxAttempts; ++attempt) {
     Attempt a;

@@ -188,26 +188,6 @@ void release_block(tad_engine *eng, void *p, size_t cap) {
   hipFree(p);
 }
 
-Lattice make_lattice(int64_t t0, int64_t step, uint64_t nb) {
-  Lattice L;
-  L.t0 = t0;
-  L.step = step < 1 ? 1 : step;
-  L.nb = nb;
-  L.magic = 0;
-  if (L.step == 1) {
-    L.mode = 0;
-  } else {
-    // ceil(2^64 / step) = floor((2^64 - 1) / step) + 1 (step >= 2 never divides 2^64 - 1 + 1 exactly
-    // unless it is a power of two, for which floor((2^64-1)/step) + 1 = 2^64/step as well)
-    L.magic = UINT64_MAX / (uint64_t)L.step + 1;
-    // the multiply-high quotient is exact for dividends < 2^32 and divisors < 2^32
-    const bool small = (uint64_t)L.step < (1ull << 32) &&
-                       (nb == 0 || (nb - 1) <= (UINT32_MAX / (uint64_t)L.step));
-    L.mode = small ? 1 : 2;
-  }
-  return L;
-}
-
 uint64_t host_gcd(uint64_t a, uint64_t b) {
   while (b) { uint64_t r = a % b; a = b; b = r; }
   return a;

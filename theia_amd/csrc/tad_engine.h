@@ -341,7 +341,6 @@ struct StateCall {
 void release_block(tad_engine *eng, void *p, size_t cap);
 inline void release_block(JobCtx *e, void *p, size_t cap) { release_block(e->eng, p, cap); }
 
-Lattice make_lattice(int64_t t0, int64_t step, uint64_t nb);
 uint64_t host_gcd(uint64_t a, uint64_t b);
 
 struct ResultBlock {

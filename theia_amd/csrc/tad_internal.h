@@ -3,22 +3,18 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include <type_traits>
 
 #include "tad.h"
 #include "tad_carve.h"     // the workspace blocks: their pointer structs (OutRows, StreamState, ArimaSlots, ...) and layouts
 #include "tad_dev_err.h"   // DEV_ERR_*: what a kernel raises in DevCounters::err
+#include "tad_rows.h"      // a row of the caller's table and its judges: Lattice, RowFilter, RowCols, the column widths
 
 namespace tad {
 
-// flowEndSeconds lattice: t = t0 + step * bucket, bucket < nb.
-struct Lattice {
-  int64_t t0;
-  int64_t step;
-  uint64_t nb;
-  uint64_t magic;  // ceil(2^64 / step): exact quotient for dividends < 2^32 (mode 1)
-  int mode;        // 0: step == 1, 1: multiply-high path ((tmax - t0) < 2^32), 2: 64-bit division
-};
+static_assert(kKeySkip == TAD_KEY_SKIP, "tad_rows.h restates tad.h's skip key");
 
 // The aggregated point grid, TIME-MAJOR: cell(bucket b, key k) = b * K + k.
 // Time-major so that "one lane = one key, walk the series sequentially" is a fully coalesced
@@ -42,28 +38,6 @@ struct MetaPartial {
   uint64_t seen;  // rows examined (k_meta_hist with a sampled histogram: the histogram's sampling ratio is seen / chunk rows)
 };
 
-// Device-side counters of one run (one 64-byte block, zeroed per run).
-struct DevCounters {
-  unsigned long long rows_used;
-  unsigned long long n_keys;
-  unsigned long long n_points;
-  unsigned long long keys_no_result;
-  unsigned long long kalman_steps;
-  unsigned long long arima_fits;
-  unsigned long long arima_nan_fits;   // fits whose prediction is not finite (the optimiser walked into a non-finite likelihood)
-  uint32_t err;
-  uint32_t pad;
-};
-
-// Widths of the input columns a Stage-0 launcher reads (tad.h, TAD_FLAG_KEY_U32 / TAD_FLAG_TIME_U32): 0 = every column 8 bytes.
-// The kernels take them as template parameters (K32, T32) and decode on load; everything after the loads is width-independent.
-enum : int { kColKey32 = 1, kColTime32 = 2 };
-
-struct RowFilter {
-  int64_t start_time;  // 0 = unset
-  int64_t end_time;    // 0 = unset
-};
-
 // Opt a kernel into more than 64 KB of dynamic LDS.  The attribute is per (function, device) in the HIP runtime and a
 // process may hold one engine per GPU (the Go controller does), so it is set — a cheap host call — before every
 // launch for the current device instead of being cached in a process-wide flag.
@@ -72,12 +46,9 @@ inline void allow_big_lds(const void *kernel, size_t bytes) {
 }
 
 // ---- launchers (tad_kernels.hip / tad_dbscan.hip / tad_arima.hip / tad_synth.hip) ----
-int launch_meta(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
-                const int64_t *t_start, uint64_t n, RowFilter f, MetaPartial *partials, int n_blocks, int cw = 0);
+int launch_meta(hipStream_t s, const RowCols &rows, RowFilter f, MetaPartial *partials, int n_blocks);
 
-void launch_scatter(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
-                    const int64_t *t_start, const uint64_t *value, uint64_t n, RowFilter f,
-                    Lattice lat, Grid g, bool op_max, DevCounters *ctr, int cw = 0);
+void launch_scatter(hipStream_t s, const RowCols &rows, RowFilter f, Lattice lat, Grid g, bool op_max, DevCounters *ctr);
 
 // a / b for an integer-valued b >= 1, given y = RN(1 / b): Markstein's correction steps on the FMA unit.
 // q0 = RN(a y); r = a - b q (exact in one FMA); q' = RN(q + r y) is the correctly rounded quotient once q is a
@@ -123,6 +94,15 @@ template <typename F> inline void with_widths(int cw, F &&f) {
     case kColTime32: f(std::false_type{}, std::true_type{}); break;
     default: f(std::true_type{}, std::true_type{}); break;
   }
+}
+// host: run-time booleans as template arguments: with_bools(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...).
+// f is instantiated for every combination: a launcher prunes the ones it never launches with `if constexpr` ... else dispatch_hole():
+// run-time booleans that reach a pruned combination stop the process instead of skipping the launch.
+[[noreturn]] inline void dispatch_hole(const char *kernel) { fprintf(stderr, "tad: no instantiation of %s for these launch parameters\n", kernel); abort(); }
+template <typename F> inline void with_bools(F &&f) { f(); }
+template <typename F, typename... Rest> inline void with_bools(F &&f, bool b, Rest... rest) {
+  if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 // (the per-key walks are HBM-latency bound: one lane = one key, 64 consecutive keys = one coalesced 512-byte access)
@@ -569,7 +549,6 @@ struct PartPlan {
 // decide whether pass B runs as the write-combining variant (sets wc_cap / pad_slots; needs 16-byte aligned columns)
 // partition_pass: tad_plan.partition_pass (0 = decide from the shape, 1 = sort-by-tile, 2 = write-combining whenever it fits)
 void part_plan_wc(uint64_t slots, bool aligned, bool has2, int partition_pass, PartPlan *pl);
-bool columns_aligned16(const void *key, const void *key2, const void *t_end, const void *value);
 bool part_plan_bins(uint64_t n, uint64_t K, bool has2, PartPlan *pl);
 bool part_plan_tiles(uint64_t K, uint64_t T, bool has2, PartPlan *pl);
 // sparse tables (tad_sparse.hip, launch_sparse_sort): key blocks for the partition pass alone — no LDS tile has to hold a block's buckets;
@@ -578,9 +557,8 @@ bool part_plan_sparse(uint64_t K, uint64_t T, bool has2, PartPlan *pl);
 // sample_hist: histogram only the rows whose time is sampled too (one iteration in eight + the chunk ends): pass A then
 // reads 1/8 of the key column; the regions of pass B are SIZED from the estimate (launch_part_offsets) instead of counted.
 // Returns whether the histogram is sampled (only without a time-window filter and with 16-byte aligned columns).
-bool launch_meta_hist(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
-                      const int64_t *t_start, uint64_t n, uint64_t K, RowFilter f, const PartPlan &pl,
-                      MetaPartial *partials, uint32_t *binhist, DevCounters *ctr, int cw, bool sample_hist);
+bool launch_meta_hist(hipStream_t s, const RowCols &rows, uint64_t K, RowFilter f, const PartPlan &pl,
+                      MetaPartial *partials, uint32_t *binhist, DevCounters *ctr, bool sample_hist);
 // offs32[G][nparts] (exclusive per-workgroup prefix inside each partition), total[nparts], part_start[nparts + 1]
 // sampled: the histogram is a sample -> region capacities (estimate + 6 sigma + margin); partials carry the sampling ratios
 // TWO launches (k_part_offsets, k_part_tail): also build the slice table of pass C in slice_mem (slice_table_bytes(slots, pl)) and zero
@@ -592,11 +570,10 @@ void launch_part_offsets(hipStream_t s, const uint32_t *binhist, const PartPlan 
 uint64_t sampled_slots_bound(uint64_t slots, const PartPlan &pl);
 // fin != NULL (sampled regions): no fillers; fin[(g * nparts + p) * 2 + {0, 1}] = end of the records written upwards /
 // start of the spilled records written downwards in region (g, p)
-void launch_partition(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
-                      const int64_t *t_start, const uint64_t *value, uint64_t n, uint64_t K, RowFilter f,
+void launch_partition(hipStream_t s, const RowCols &rows, uint64_t K, RowFilter f,
                       Lattice L, const PartPlan &pl, const uint32_t *offs32, const unsigned long long *part_start,
                       void *recs, OverflowRec *ovf, unsigned long long *ovf_count, uint32_t ovf_cap, DevCounters *ctr,
-                      uint32_t *fin = nullptr, uint32_t *ovf_keys = nullptr, int cw = 0);   // ovf_keys: bitmap (K bits, zeroed) of the keys with a value on the overflow list
+                      uint32_t *fin = nullptr, uint32_t *ovf_keys = nullptr);   // ovf_keys: bitmap (K bits, zeroed) of the keys with a value on the overflow list
 // slots = record slots of the run (rows x keys per row); slice_mem = slice_table_bytes(slots, pl) bytes of device scratch
 size_t slice_table_bytes(uint64_t slots, const PartPlan &pl);
 void launch_tile_aggregate(hipStream_t s, const void *recs, const unsigned long long *part_start, const PartPlan &pl,
@@ -621,10 +598,9 @@ void launch_sparse_place_staged(hipStream_t s, const PartPlan &pl, void *temp, c
                                 const uint32_t *stage_rank, int64_t t0, Grid g, long long *times);
 void launch_sparse_compact(hipStream_t s, const PartPlan &pl, void *temp, const unsigned long long *stage_comp, const unsigned long long *stage_val,
                            unsigned long long *comp_out, unsigned long long *val_out);
-int launch_sparse_group(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end, const int64_t *t_start,
-                        const uint64_t *value, uint64_t n, uint64_t K, RowFilter f, int64_t t0, uint64_t span, bool op_max, unsigned long long *comp_a,
+int launch_sparse_group(hipStream_t s, const RowCols &rows, uint64_t K, RowFilter f, int64_t t0, uint64_t span, bool op_max, unsigned long long *comp_a,
                         unsigned long long *val_a, unsigned long long *comp_b, unsigned long long *val_b, void *temp, size_t temp_bytes,
-                        unsigned long long *num_runs, DevCounters *ctr, int cw = 0);
+                        unsigned long long *num_runs, DevCounters *ctr);
 // slots: upper bound of the points (grid size); the point count itself is read on the device (*P_dev)
 void launch_sparse_tmax(hipStream_t s, const unsigned long long *ucomp, uint64_t slots, const unsigned long long *P_dev, uint32_t *first, unsigned int *tmax);
 void launch_sparse_place(hipStream_t s, const unsigned long long *ucomp, const unsigned long long *uval, uint64_t P, const uint32_t *first,

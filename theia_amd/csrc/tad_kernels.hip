@@ -17,57 +17,6 @@ namespace tad {
 static constexpr int kBlock = 256;
 
 // ------------------------------------------------------------------------------------------------
-// small device helpers
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t gcd_u64(uint64_t a, uint64_t b) {
-  if (a == 0) return b;
-  if (b == 0) return a;
-  if (((a | b) >> 32) == 0) {
-    uint32_t x = (uint32_t)a, y = (uint32_t)b;
-    while (y) { uint32_t r = x % y; x = y; y = r; }
-    return x;
-  }
-  while (b) { uint64_t r = a % b; a = b; b = r; }
-  return a;
-}
-
-__device__ __forceinline__ uint64_t absdiff_i64(int64_t a, int64_t b) {
-  return a >= b ? (uint64_t)a - (uint64_t)b : (uint64_t)b - (uint64_t)a;
-}
-
-struct MetaAcc {
-  int64_t tmin, tmax, tref;
-  uint64_t g, used;
-};
-
-__device__ __forceinline__ MetaAcc meta_merge(MetaAcc a, const MetaAcc &b) {
-  if (b.used == 0) return a;
-  if (a.used == 0) return b;
-  a.tmin = b.tmin < a.tmin ? b.tmin : a.tmin;
-  a.tmax = b.tmax > a.tmax ? b.tmax : a.tmax;
-  a.g = gcd_u64(gcd_u64(a.g, b.g), absdiff_i64(a.tref, b.tref));
-  a.used += b.used;
-  return a;
-}
-
-__device__ __forceinline__ MetaAcc meta_shfl_down(const MetaAcc &a, int d) {
-  MetaAcc r;
-  r.tmin = __shfl_down((long long)a.tmin, d);
-  r.tmax = __shfl_down((long long)a.tmax, d);
-  r.tref = __shfl_down((long long)a.tref, d);
-  r.g = __shfl_down((unsigned long long)a.g, d);
-  r.used = __shfl_down((unsigned long long)a.used, d);
-  return r;
-}
-
-template <bool T32 = false>
-__device__ __forceinline__ bool row_kept(int64_t te, const int64_t *t_start, uint64_t i, RowFilter f) {
-  if (f.end_time != 0 && !(te < f.end_time)) return false;          // :584-586
-  if (f.start_time != 0 && t_start != nullptr && !(ld_time<T32>(t_start, i) >= f.start_time)) return false;  // :581-583
-  return true;
-}
-
-// ------------------------------------------------------------------------------------------------
 // k_meta — derive the flowEndSeconds lattice (min, max, gcd of differences) of the rows that pass
 // the filters.  One read of the time column (+ key columns for TAD_KEY_SKIP).  K32 / T32: narrow key / time columns.
 // ------------------------------------------------------------------------------------------------
@@ -77,13 +26,14 @@ __global__ __launch_bounds__(kBlock) void k_meta(const uint64_t *__restrict__ ke
                                                  const int64_t *__restrict__ t_end,
                                                  const int64_t *__restrict__ t_start, uint64_t n,
                                                  RowFilter f, MetaPartial *__restrict__ partials) {
-  MetaAcc acc{0, 0, 0, 0, 0};
+  LatticeAcc acc{0, 0, 0, 0, 0};
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  const bool has_ts = t_start != nullptr && f.start_time != 0;
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
     const int64_t te = ld_time<T32>(t_end, i);
     bool live = ld_key<K32>(key, i) != TAD_KEY_SKIP;
     if (key2 != nullptr) live = live || ld_key<K32>(key2, i) != TAD_KEY_SKIP;
-    if (!live || !row_kept<T32>(te, t_start, i, f)) continue;
+    if (!live || !time_kept(te, has_ts ? ld_time<T32>(t_start, i) : 0, has_ts, f)) continue;
     if (acc.used == 0) {
       acc.tmin = acc.tmax = acc.tref = te;
       acc.g = 0;
@@ -95,24 +45,23 @@ __global__ __launch_bounds__(kBlock) void k_meta(const uint64_t *__restrict__ ke
     }
     acc.used++;
   }
-  for (int d = 32; d >= 1; d >>= 1) acc = meta_merge(acc, meta_shfl_down(acc, d));
-  __shared__ MetaAcc s_acc[kBlock / 64];
+  for (int d = 32; d >= 1; d >>= 1) acc = lattice_merge(acc, lattice_shfl_down(acc, d));
+  __shared__ LatticeAcc s_acc[kBlock / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) s_acc[wave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
-    MetaAcc a = s_acc[0];
-    for (int w = 1; w < kBlock / 64; ++w) a = meta_merge(a, s_acc[w]);
+    LatticeAcc a = s_acc[0];
+    for (int w = 1; w < kBlock / 64; ++w) a = lattice_merge(a, s_acc[w]);
     MetaPartial p;
     p.tmin = a.tmin; p.tmax = a.tmax; p.tref = a.tref; p.g = a.g; p.used = a.used;
     partials[blockIdx.x] = p;
   }
 }
 
-int launch_meta(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
-                const int64_t *t_start, uint64_t n, RowFilter f, MetaPartial *partials, int n_blocks, int cw) {
-  with_widths(cw, [&](auto k32, auto t32) {
-    hipLaunchKernelGGL((k_meta<k32(), t32()>), dim3(n_blocks), dim3(kBlock), 0, s, key, key2, t_end, t_start, n, f, partials);
+int launch_meta(hipStream_t s, const RowCols &rows, RowFilter f, MetaPartial *partials, int n_blocks) {
+  with_widths(rows.cw, [&](auto k32, auto t32) {
+    hipLaunchKernelGGL((k_meta<k32(), t32()>), dim3(n_blocks), dim3(kBlock), 0, s, rows.key, rows.key2, rows.t_end, rows.t_start, rows.n, f, partials);
   });
   return 0;
 }
@@ -124,22 +73,6 @@ int launch_meta(hipStream_t s, const uint64_t *key, const uint64_t *key2, const 
 // Measured on MI355X (tools/ubench_scatter.hip): the 24 B/row column stream alone runs at 5.6 TB/s;
 // the random 8-byte read-modify-write is bound at ~23.5e9 L2-miss line transactions/s.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool cell_index(const Lattice &L, int64_t te, uint64_t &bucket) {
-  const uint64_t d = (uint64_t)te - (uint64_t)L.t0;  // te < t0 wraps to a huge value -> rejected below
-  uint64_t b;
-  if (L.mode == 0) {
-    b = d;
-  } else if (L.mode == 1) {
-    if (d >> 32) return false;
-    b = __umul64hi(d, L.magic);
-  } else {
-    b = d / (uint64_t)L.step;
-  }
-  if (b >= L.nb || b * (uint64_t)L.step != d) return false;
-  bucket = b;
-  return true;
-}
-
 template <bool OPMAX>
 __device__ __forceinline__ void cell_update(const Grid &g, uint64_t bucket, uint64_t key, uint64_t v) {
   const uint64_t c = bucket * g.K + key;
@@ -154,17 +87,11 @@ template <bool OPMAX>
 __device__ __forceinline__ void scatter_row(uint64_t k1, uint64_t k2, bool has2, int64_t te, uint64_t v,
                                             const Lattice &L, const Grid &g, uint32_t &err, uint32_t &used) {
   uint64_t bucket;
-  const bool live1 = k1 != TAD_KEY_SKIP, live2 = has2 && k2 != TAD_KEY_SKIP;
+  const bool live1 = key_slot(true, k1, g.K, err) == kSlotLive, live2 = key_slot(has2, k2, g.K, err) == kSlotLive;
   if (!live1 && !live2) return;
-  if (!cell_index(L, te, bucket)) { err |= DEV_ERR_OFF_LATTICE; return; }
-  if (live1) {
-    if (k1 >= g.K) err |= DEV_ERR_KEY_RANGE;
-    else { cell_update<OPMAX>(g, bucket, k1, v); used++; }
-  }
-  if (live2) {
-    if (k2 >= g.K) err |= DEV_ERR_KEY_RANGE;
-    else { cell_update<OPMAX>(g, bucket, k2, v); used++; }
-  }
+  if (!lattice_bucket(L, te, bucket)) { err |= DEV_ERR_OFF_LATTICE; return; }
+  if (live1) { cell_update<OPMAX>(g, bucket, k1, v); used++; }
+  if (live2) { cell_update<OPMAX>(g, bucket, k2, v); used++; }
 }
 
 template <bool OPMAX, bool VEC2, bool K32 = false, bool T32 = false>
@@ -178,6 +105,8 @@ __global__ __launch_bounds__(kBlock) void k_scatter(const uint64_t *__restrict__
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   const uint64_t tid = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const bool has2 = key2 != nullptr;
+  const bool has_ts = t_start != nullptr && f.start_time != 0;
+  auto kept = [&](int64_t te, uint64_t i) { return time_kept(te, has_ts ? ld_time<T32>(t_start, i) : 0, has_ts, f); };
   if (VEC2) {
     // 16-byte loads: two rows per lane per column, 1 KiB per wave-instruction (8-byte loads of a narrow column).
     const uint64_t n2 = n >> 1;
@@ -188,17 +117,17 @@ __global__ __launch_bounds__(kBlock) void k_scatter(const uint64_t *__restrict__
       const ulonglong2 v = val_v[i];
       ulonglong2 k2 = make_ulonglong2(TAD_KEY_SKIP, TAD_KEY_SKIP);
       if (has2) k2 = ld_key2<K32>(key2, 0, i);
-      if (row_kept<T32>(te.x, t_start, 2 * i, f)) scatter_row<OPMAX>(k.x, k2.x, has2, te.x, v.x, L, g, err, used);
-      if (row_kept<T32>(te.y, t_start, 2 * i + 1, f)) scatter_row<OPMAX>(k.y, k2.y, has2, te.y, v.y, L, g, err, used);
+      if (kept(te.x, 2 * i)) scatter_row<OPMAX>(k.x, k2.x, has2, te.x, v.x, L, g, err, used);
+      if (kept(te.y, 2 * i + 1)) scatter_row<OPMAX>(k.y, k2.y, has2, te.y, v.y, L, g, err, used);
     }
     if ((n & 1) && tid == 0) {
       const uint64_t i = n - 1;
-      if (row_kept<T32>(ld_time<T32>(t_end, i), t_start, i, f))
+      if (kept(ld_time<T32>(t_end, i), i))
         scatter_row<OPMAX>(ld_key<K32>(key, i), has2 ? ld_key<K32>(key2, i) : TAD_KEY_SKIP, has2, ld_time<T32>(t_end, i), value[i], L, g, err, used);
     }
   } else {
     for (uint64_t i = tid; i < n; i += stride) {
-      if (row_kept<T32>(ld_time<T32>(t_end, i), t_start, i, f))
+      if (kept(ld_time<T32>(t_end, i), i))
         scatter_row<OPMAX>(ld_key<K32>(key, i), has2 ? ld_key<K32>(key2, i) : TAD_KEY_SKIP, has2, ld_time<T32>(t_end, i), value[i], L, g, err, used);
     }
   }
@@ -214,22 +143,20 @@ __global__ __launch_bounds__(kBlock) void k_scatter(const uint64_t *__restrict__
   }
 }
 
-void launch_scatter(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
-                    const int64_t *t_start, const uint64_t *value, uint64_t n, RowFilter f,
-                    Lattice lat, Grid g, bool op_max, DevCounters *ctr, int cw) {
+void launch_scatter(hipStream_t s, const RowCols &rows, RowFilter f, Lattice lat, Grid g, bool op_max, DevCounters *ctr) {
+  const uint64_t n = rows.n;
   if (n == 0) return;
-  auto aligned16 = [](const void *p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec = aligned16(key) && aligned16(key2) && aligned16(t_end) && aligned16(value) && n >= 2;
+  const bool vec = rows.aligned16() && n >= 2;
   const uint64_t work = vec ? (n >> 1) : n;
   int blocks = (int)((work + kBlock - 1) / kBlock);
   if (blocks > 256 * 16) blocks = 256 * 16;  // grid-stride the rest (guide: ~8-16 blocks per CU)
   if (blocks < 1) blocks = 1;
-  with_widths(cw, [&](auto k32, auto t32) {
-#define TAD_LAUNCH_SCATTER(OPMAX, VEC) \
-  hipLaunchKernelGGL((k_scatter<OPMAX, VEC, k32(), t32()>), dim3(blocks), dim3(kBlock), 0, s, key, key2, t_end, t_start, value, n, f, lat, g, ctr)
-    if (op_max) { if (vec) TAD_LAUNCH_SCATTER(true, true); else TAD_LAUNCH_SCATTER(true, false); }
-    else        { if (vec) TAD_LAUNCH_SCATTER(false, true); else TAD_LAUNCH_SCATTER(false, false); }
-#undef TAD_LAUNCH_SCATTER
+  with_widths(rows.cw, [&](auto k32, auto t32) {
+    constexpr bool K32 = decltype(k32)::value, T32 = decltype(t32)::value;
+    with_bools([&](auto opmax, auto vec2) {
+      hipLaunchKernelGGL((k_scatter<decltype(opmax)::value, decltype(vec2)::value, K32, T32>), dim3(blocks), dim3(kBlock), 0, s, rows.key, rows.key2, rows.t_end, rows.t_start,
+                         rows.value, n, f, lat, g, ctr);
+    }, op_max, vec);
   });
 }
 

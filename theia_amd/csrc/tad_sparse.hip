@@ -5,7 +5,7 @@
 // for the benchmarked tables (minute-resolution lattices, every key active most of the time), but the reference accepts
 // any flowEndSeconds and, in mode None, keys per connection (anomaly_detection.py:52-61, 109-116: the key contains
 // flowStartSeconds): second-resolution timestamps with gcd 1 over a day give T = 86 400 for a handful of points per
-// key.  Here the rows are sorted by (key, time) instead (rocPRIM radix sort on key << 32 | (t - t0)), equal (key, time)
+// key.  Here the rows are sorted by (key, time) instead (the project's own LSD radix sort, k_rs_* below, on key << 32 | (t - t0)), equal (key, time)
 // runs are reduced with the job's operator (wrapping u64 add / unsigned max — the same associative integer operators,
 // so the aggregates are bit-identical to the dense path's), and the points of every key are laid out by RANK in time
 // order: a K x Tmax grid, Tmax = the longest series, plus a parallel grid of the points' timestamps.  Every per-key
@@ -28,37 +28,26 @@ __global__ __launch_bounds__(kSpBlock) void k_sparse_keys(const uint64_t *__rest
   uint32_t err = 0;
   unsigned long long used = 0;
   const int nk = key2 != nullptr ? 2 : 1;
+  const bool has_ts = t_start != nullptr && f.start_time != 0;
   // grid-stride: the job counter gets ONE atomic per workgroup — one per wavefront of a 1e8-row table is 1.5e6 atomics on one address,
   // which serialise at ~12 ns each (the kernel took 18.8 ms for 4 GB of traffic, profiles/r4_v2_sparse_scale_kernel_stats.csv)
   for (uint64_t i = (uint64_t)blockIdx.x * kSpBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kSpBlock) {
     const int64_t te = ld_time<T32>(t_end, i);
-    bool kept = true;
-    if (f.end_time != 0 && !(te < f.end_time)) kept = false;                                       // anomaly_detection.py:584-586
-    if (f.start_time != 0 && t_start != nullptr && !(ld_time<T32>(t_start, i) >= f.start_time)) kept = false;    // :581-583
+    const bool kept = time_kept(te, has_ts ? ld_time<T32>(t_start, i) : 0, has_ts, f);
     const uint64_t dt = (uint64_t)te - (uint64_t)t0;
     const uint64_t v = value[i];
     for (int h = 0; h < nk; ++h) {
       const uint64_t k = h == 0 ? ld_key<K32>(key, i) : ld_key<K32>(key2, i);
       unsigned long long c = (unsigned long long)K << 32;
-      if (kept && k != TAD_KEY_SKIP) {
-        if (k >= K) err |= DEV_ERR_KEY_RANGE;
-        else if (dt > span) err |= DEV_ERR_OFF_LATTICE;     // te < t0 or beyond the lattice's last bucket (the sort covers bit_width(span) time bits): the lattice (hint / sample) was wrong
+      if (key_slot(kept, k, K, err) == kSlotLive) {
+        if (dt > span) err |= DEV_ERR_OFF_LATTICE;     // te < t0 or beyond the lattice's last bucket (the sort covers bit_width(span) time bits): the lattice (hint / sample) was wrong
         else { c = ((unsigned long long)k << 32) | dt; used++; }
       }
       comp[i * nk + h] = c;
       vals[i * nk + h] = v;
     }
   }
-  for (int d = 32; d >= 1; d >>= 1) { used += __shfl_down(used, d); err |= __shfl_down(err, d); }
-  __shared__ unsigned long long s_used[kSpBlock / 64];
-  __shared__ uint32_t s_err[kSpBlock / 64];
-  if ((threadIdx.x & 63) == 0) { s_used[threadIdx.x >> 6] = used; s_err[threadIdx.x >> 6] = err; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kSpBlock / 64; ++w) { used += s_used[w]; err |= s_err[w]; }
-    if (used) atomicAdd(&ctr->rows_used, used);
-    if (err) atomicOr(&ctr->err, err);
-  }
+  block_count_rows<kSpBlock>(used, err, ctr);
 }
 
 // first[k] = index of the key's first point in the sorted unique list
@@ -490,11 +479,10 @@ size_t sparse_sort_temp_bytes(uint64_t slots) { return rs_temp_layout(slots).tot
 
 // rows -> sorted unique (key, time) points with aggregated values in comp_a / val_a (device), their number in *num_runs (device).
 // span = the largest t - t0 the lattice allows ((n_buckets - 1) * step): rows beyond it raise DEV_ERR_OFF_LATTICE.
-int launch_sparse_group(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end, const int64_t *t_start,
-                        const uint64_t *value, uint64_t n, uint64_t K, RowFilter f, int64_t t0, uint64_t span, bool op_max, unsigned long long *comp_a,
+int launch_sparse_group(hipStream_t s, const RowCols &rows, uint64_t K, RowFilter f, int64_t t0, uint64_t span, bool op_max, unsigned long long *comp_a,
                         unsigned long long *val_a, unsigned long long *comp_b, unsigned long long *val_b, void *temp, size_t temp_bytes,
-                        unsigned long long *num_runs, DevCounters *ctr, int cw) {
-  const uint64_t slots = n * (key2 != nullptr ? 2 : 1);
+                        unsigned long long *num_runs, DevCounters *ctr) {
+  const uint64_t n = rows.n, slots = n * (rows.has2() ? 2 : 1);
   if (slots == 0 || slots >= (1ull << 32) || K > 0xFFFFFFFFull) return -1;
   if (span > 0xFFFFFFFFull) span = 0xFFFFFFFFull;
   const RsPlan pl = rs_plan(slots, K, span);
@@ -510,9 +498,9 @@ int launch_sparse_group(hipStream_t s, const uint64_t *key, const uint64_t *key2
   unsigned long long *ca = (pl.np & 1) ? comp_a : comp_b, *va = (pl.np & 1) ? val_a : val_b;
   unsigned long long *cb = (pl.np & 1) ? comp_b : comp_a, *vb = (pl.np & 1) ? val_b : val_a;
   const uint64_t kb = (n + kSpBlock - 1) / kSpBlock;
-  with_widths(cw, [&](auto k32, auto t32) {
-    hipLaunchKernelGGL((k_sparse_keys<k32(), t32()>), dim3((unsigned)(kb < 8192 ? kb : 8192)), dim3(kSpBlock), 0, s, key, key2, t_end, t_start,
-                       value, n, K, f, t0, span, ca, va, ctr);
+  with_widths(rows.cw, [&](auto k32, auto t32) {
+    hipLaunchKernelGGL((k_sparse_keys<k32(), t32()>), dim3((unsigned)(kb < 8192 ? kb : 8192)), dim3(kSpBlock), 0, s, rows.key, rows.key2, rows.t_end,
+                       rows.t_start, rows.value, n, K, f, t0, span, ca, va, ctr);
   });
   const size_t lds = (size_t)kRsTile * 16 + kRsRadix * 8 + (size_t)kRsWaves * kRsRadix * 4 + kRsRadix * 4 + 64;
   allow_big_lds(reinterpret_cast<const void *>(k_rs_scatter), lds);

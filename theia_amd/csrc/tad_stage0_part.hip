@@ -63,63 +63,12 @@ static constexpr int kGcdSamples = 4;
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ------------------------------------------------------------------------------------------------
-// shared helpers (duplicated from tad_kernels.hip on purpose: separate translation units)
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t p_gcd_u64(uint64_t a, uint64_t b) {
-  if (a == 0) return b;
-  if (b == 0) return a;
-  if (((a | b) >> 32) == 0) {
-    uint32_t x = (uint32_t)a, y = (uint32_t)b;
-    while (y) { uint32_t r = x % y; x = y; y = r; }
-    return x;
-  }
-  while (b) { uint64_t r = a % b; a = b; b = r; }
-  return a;
-}
-
-__device__ __forceinline__ uint64_t p_absdiff(int64_t a, int64_t b) {
-  return a >= b ? (uint64_t)a - (uint64_t)b : (uint64_t)b - (uint64_t)a;
-}
-
-struct PMeta {
-  int64_t tmin, tmax, tref;
-  uint64_t g, used;
-};
-
-__device__ __forceinline__ PMeta pmeta_merge(PMeta a, const PMeta &b) {
-  if (b.used == 0) return a;
-  if (a.used == 0) return b;
-  a.tmin = b.tmin < a.tmin ? b.tmin : a.tmin;
-  a.tmax = b.tmax > a.tmax ? b.tmax : a.tmax;
-  a.g = p_gcd_u64(p_gcd_u64(a.g, b.g), p_absdiff(a.tref, b.tref));
-  a.used += b.used;
-  return a;
-}
-
-__device__ __forceinline__ bool p_time_kept(int64_t te, int64_t ts, bool has_ts, RowFilter f) {
-  if (f.end_time != 0 && !(te < f.end_time)) return false;                  // anomaly_detection.py:584-586
-  if (f.start_time != 0 && has_ts && !(ts >= f.start_time)) return false;   // :581-583
-  return true;
-}
-
-__device__ __forceinline__ bool p_bucket(const Lattice &L, int64_t te, uint32_t &bucket) {
-  const uint64_t d = (uint64_t)te - (uint64_t)L.t0;
-  uint64_t b;
-  if (L.mode == 0) b = d;
-  else if (L.mode == 1) { if (d >> 32) return false; b = __umul64hi(d, L.magic); }
-  else b = d / (uint64_t)L.step;
-  if (b >= L.nb || b * (uint64_t)L.step != d) return false;
-  bucket = (uint32_t)b;
-  return true;
-}
-
-// ------------------------------------------------------------------------------------------------
 // pass A — lattice partial + per-workgroup key-bin histogram.  Workgroup b owns rows
 // [b * chunk, (b+1) * chunk): the SAME chunking as pass B, so the histogram row b is exactly what
 // workgroup b of pass B will emit.  chunk is even and the columns are 16-byte aligned when VEC.
 // ------------------------------------------------------------------------------------------------
 struct MetaAcc {
-  PMeta m;
+  LatticeAcc m;
   int nsample;
   uint32_t err;
 };
@@ -155,16 +104,9 @@ __device__ __forceinline__ void hist_add(uint32_t *hist, uint32_t bin, uint32_t 
 
 __device__ __forceinline__ void meta_row(MetaAcc &a, uint32_t *hist, uint64_t k1, uint64_t k2, int64_t te, bool kept,
                                          uint64_t K, int shift_bin, uint32_t weight = 1u) {
-  if (!kept) return;
   bool counted = false;
-  if (k1 != TAD_KEY_SKIP) {
-    if (k1 < K) { hist_add(hist, (uint32_t)(k1 >> shift_bin), weight); counted = true; }
-    else a.err |= DEV_ERR_KEY_RANGE;
-  }
-  if (k2 != TAD_KEY_SKIP) {
-    if (k2 < K) { hist_add(hist, (uint32_t)(k2 >> shift_bin), weight); counted = true; }
-    else a.err |= DEV_ERR_KEY_RANGE;
-  }
+  if (key_slot(kept, k1, K, a.err) == kSlotLive) { hist_add(hist, (uint32_t)(k1 >> shift_bin), weight); counted = true; }
+  if (key_slot(kept, k2, K, a.err) == kSlotLive) { hist_add(hist, (uint32_t)(k2 >> shift_bin), weight); counted = true; }
   if (!counted) return;
   if (a.m.used == 0) {
     a.m.tmin = a.m.tmax = a.m.tref = te;
@@ -173,8 +115,8 @@ __device__ __forceinline__ void meta_row(MetaAcc &a, uint32_t *hist, uint64_t k1
     a.m.tmin = te < a.m.tmin ? te : a.m.tmin;
     a.m.tmax = te > a.m.tmax ? te : a.m.tmax;
     if (a.nsample < kGcdSamples) {
-      const uint64_t d = p_absdiff(te, a.m.tref);
-      if (d != 0) { a.m.g = p_gcd_u64(a.m.g, d); a.nsample++; }
+      const uint64_t d = absdiff_i64(te, a.m.tref);
+      if (d != 0) { a.m.g = gcd_u64(a.m.g, d); a.nsample++; }
     }
   }
   a.m.used++;
@@ -182,14 +124,8 @@ __device__ __forceinline__ void meta_row(MetaAcc &a, uint32_t *hist, uint64_t k1
 
 // a row whose time is not sampled: histogram only
 __device__ __forceinline__ void hist_row(MetaAcc &a, uint32_t *hist, uint64_t k1, uint64_t k2, uint64_t K, int shift_bin) {
-  if (k1 != TAD_KEY_SKIP) {
-    if (k1 < K) hist_add(hist, (uint32_t)(k1 >> shift_bin), 1u);
-    else a.err |= DEV_ERR_KEY_RANGE;
-  }
-  if (k2 != TAD_KEY_SKIP) {
-    if (k2 < K) hist_add(hist, (uint32_t)(k2 >> shift_bin), 1u);
-    else a.err |= DEV_ERR_KEY_RANGE;
-  }
+  if (key_slot(true, k1, K, a.err) == kSlotLive) hist_add(hist, (uint32_t)(k1 >> shift_bin), 1u);
+  if (key_slot(true, k2, K, a.err) == kSlotLive) hist_add(hist, (uint32_t)(k2 >> shift_bin), 1u);
 }
 
 // Pass A reads one iteration (8192 rows of a workgroup's chunk) in kSampleMask + 1, plus both ends of the chunk.  One in eight until
@@ -275,8 +211,8 @@ __global__ __launch_bounds__(kPartThreads) void k_meta_hist(const uint64_t *__re
         for (int u = 0; u < U; ++u) {
           const uint64_t r = lo + 2 * (i + u * kPartThreads);
           const int64_t ts0 = has_ts ? ld_time<T32>(t_start, r) : 0, ts1 = has_ts ? ld_time<T32>(t_start, r + 1) : 0;
-          meta_row(acc, hist, k[u].x, k2[u].x, t[u].x, p_time_kept(t[u].x, ts0, has_ts, f), K, shift_bin, weight);
-          meta_row(acc, hist, k[u].y, k2[u].y, t[u].y, p_time_kept(t[u].y, ts1, has_ts, f), K, shift_bin, weight);
+          meta_row(acc, hist, k[u].x, k2[u].x, t[u].x, time_kept(t[u].x, ts0, has_ts, f), K, shift_bin, weight);
+          meta_row(acc, hist, k[u].y, k2[u].y, t[u].y, time_kept(t[u].y, ts1, has_ts, f), K, shift_bin, weight);
         }
       } else {
 #pragma unroll
@@ -293,47 +229,41 @@ __global__ __launch_bounds__(kPartThreads) void k_meta_hist(const uint64_t *__re
       const ulonglong2 k2 = HAS2 ? kpair(k2v, key2, i) : make_ulonglong2(TAD_KEY_SKIP, TAD_KEY_SKIP);
       const uint64_t r = lo + 2 * i;
       const int64_t ts0 = has_ts ? ld_time<T32>(t_start, r) : 0, ts1 = has_ts ? ld_time<T32>(t_start, r + 1) : 0;
-      meta_row(acc, hist, k.x, k2.x, t.x, p_time_kept(t.x, ts0, has_ts, f), K, shift_bin);
-      meta_row(acc, hist, k.y, k2.y, t.y, p_time_kept(t.y, ts1, has_ts, f), K, shift_bin);
+      meta_row(acc, hist, k.x, k2.x, t.x, time_kept(t.x, ts0, has_ts, f), K, shift_bin);
+      meta_row(acc, hist, k.y, k2.y, t.y, time_kept(t.y, ts1, has_ts, f), K, shift_bin);
     }
     if (((hi - lo) & 1) && threadIdx.x == 0 && hi > lo) {
       seen += 1;
       const uint64_t r = hi - 1;
       const int64_t te = ld_time<T32>(t_end, r);
-      meta_row(acc, hist, ld_key<K32>(key, r), HAS2 ? ld_key<K32>(key2, r) : TAD_KEY_SKIP, te, p_time_kept(te, has_ts ? ld_time<T32>(t_start, r) : 0, has_ts, f), K, shift_bin);
+      meta_row(acc, hist, ld_key<K32>(key, r), HAS2 ? ld_key<K32>(key2, r) : TAD_KEY_SKIP, te, time_kept(te, has_ts ? ld_time<T32>(t_start, r) : 0, has_ts, f), K, shift_bin);
     }
   } else {
     for (uint64_t r = lo + threadIdx.x; r < hi; r += kPartThreads) {
       seen += 1;
       const int64_t te = ld_time<T32>(t_end, r);
-      meta_row(acc, hist, ld_key<K32>(key, r), HAS2 ? ld_key<K32>(key2, r) : TAD_KEY_SKIP, te, p_time_kept(te, has_ts ? ld_time<T32>(t_start, r) : 0, has_ts, f), K, shift_bin);
+      meta_row(acc, hist, ld_key<K32>(key, r), HAS2 ? ld_key<K32>(key2, r) : TAD_KEY_SKIP, te, time_kept(te, has_ts ? ld_time<T32>(t_start, r) : 0, has_ts, f), K, shift_bin);
     }
   }
-  PMeta m = acc.m;
+  LatticeAcc m = acc.m;
   uint32_t err = acc.err;
   unsigned long long seen_w = seen;
   for (int d = 32; d >= 1; d >>= 1) seen_w += __shfl_down(seen_w, d);
   for (int d = 32; d >= 1; d >>= 1) {
-    PMeta o;
-    o.tmin = __shfl_down((long long)m.tmin, d);
-    o.tmax = __shfl_down((long long)m.tmax, d);
-    o.tref = __shfl_down((long long)m.tref, d);
-    o.g = __shfl_down((unsigned long long)m.g, d);
-    o.used = __shfl_down((unsigned long long)m.used, d);
-    m = pmeta_merge(m, o);
+    m = lattice_merge(m, lattice_shfl_down(m, d));
     err |= __shfl_down(err, d);
   }
-  __shared__ PMeta s_acc[kPartThreads / 64];
+  __shared__ LatticeAcc s_acc[kPartThreads / 64];
   __shared__ uint32_t s_err[kPartThreads / 64];
   __shared__ unsigned long long s_seen[kPartThreads / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) { s_acc[wave] = m; s_err[wave] = err; s_seen[wave] = seen_w; }
   __syncthreads();  // also: every histogram update of this workgroup is done
   if (threadIdx.x == 0) {
-    PMeta a = s_acc[0];
+    LatticeAcc a = s_acc[0];
     uint32_t e = s_err[0];
     unsigned long long sn = s_seen[0];
-    for (int w = 1; w < kPartThreads / 64; ++w) { a = pmeta_merge(a, s_acc[w]); e |= s_err[w]; sn += s_seen[w]; }
+    for (int w = 1; w < kPartThreads / 64; ++w) { a = lattice_merge(a, s_acc[w]); e |= s_err[w]; sn += s_seen[w]; }
     MetaPartial p;
     p.tmin = a.tmin; p.tmax = a.tmax; p.tref = a.tref; p.g = a.g; p.used = a.used; p.seen = sn;
     partials[blockIdx.x] = p;
@@ -516,22 +446,6 @@ __global__ __launch_bounds__(256) void k_part_tail(OffsetsArgs A) {
   if (threadIdx.x == 0) { A.part_start[F] = rtot; *A.st.n_slices = (A.ctr != nullptr && (A.ctr->err & DEV_ERR_REGION_FULL)) ? 0u : stot; }
 }
 
-// rows_used / error bits of a workgroup: ONE atomic per workgroup.  One per wavefront was 4096 atomics on one address at the very
-// end of pass B, when all workgroups finish together — contended atomics serialise at ~10 ns each.
-__device__ __forceinline__ void block_count_rows(uint32_t used, uint32_t err, DevCounters *ctr) {
-  __shared__ unsigned long long s_u[kPartThreads / 64];
-  __shared__ uint32_t s_e[kPartThreads / 64];
-  unsigned long long u = used;
-  for (int d = 32; d >= 1; d >>= 1) { u += __shfl_down(u, d); err |= __shfl_down(err, d); }
-  if ((threadIdx.x & 63) == 0) { s_u[threadIdx.x >> 6] = u; s_e[threadIdx.x >> 6] = err; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kPartThreads / 64; ++w) { u += s_u[w]; err |= s_e[w]; }
-    if (u) atomicAdd(&ctr->rows_used, u);
-    if (err) atomicOr(&ctr->err, err);
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // pass B — group records by partition through LDS.
 // LDS carve (dynamic): rec[S] u64 | part[S] u16 | off[F+1] u32 | gcur[F] u32 | delta[F] u32
@@ -616,29 +530,21 @@ __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs A) {
   uint32_t *gend = delta + F;      // end of the region: capacity, checked (exact counts of THIS batch never reach it; a caller's stale tad_key_hist can)
   __shared__ uint32_t s_wave[kPartThreads / 64];
   __shared__ uint32_t s_full;
+  __shared__ uint32_t s_shut;      // regions_open: this workgroup has nothing to do
 
   // no global load may sit inside the tile loop: vmcnt retires in order, so waiting for one fresh load would
   // also wait for every prefetched row behind it
-  if (A.fin != nullptr && (A.ctr->err & DEV_ERR_REGION_FULL)) return;   // k_part_offsets: this table is redone with the exact histogram
-  const uint32_t *my_offs = A.offs32 + (size_t)blockIdx.x * F;
-  {
-    const uint32_t *nx = A.offs32 + (size_t)(blockIdx.x + 1) * F;
-    const bool last = (int)blockIdx.x + 1 == A.G;
-    for (uint32_t p = threadIdx.x; p < F; p += kPartThreads) {
-      const uint32_t ps = (uint32_t)A.part_start[p];
-      gcur[p] = ps + my_offs[p];
-      gend[p] = last ? (uint32_t)A.part_start[p + 1] : ps + nx[p];
-      off[p] = 0;
-    }
-    if (threadIdx.x == 0) s_full = 0;
-  }
+  regions_open<kPartThreads>(A, A.G, F, gcur, gend, &s_shut);
+  for (uint32_t p = threadIdx.x; p < F; p += kPartThreads) off[p] = 0;
+  if (threadIdx.x == 0) s_full = 0;
+  lds_barrier();   // (the prologue's one barrier: it stood behind the first tile's loads; here the exit below can use it and those loads are not issued in vain)
+  // k_part_offsets sent this table to the exact histogram.  One thread read the flag before this barrier, every thread reads that one
+  // answer behind it: the workgroup leaves whole or not at all (regions_open says why a test per thread is not enough).
+  if (s_shut) return;
 
   const uint64_t lo = (uint64_t)blockIdx.x * A.chunk;
   const uint64_t hi = lo + A.chunk < A.n ? lo + A.chunk : A.n;
   const bool has_ts = GENERIC && A.t_start != nullptr && A.f.start_time != 0;
-  const uint32_t KP = A.kp_mask + 1u;
-  const uint32_t cell_none = (1u << A.cell_bits) - 1u;
-  const unsigned long long value_limit = A.value_limit;
   uint32_t err = 0, used = 0;
 
   uint64_t pk[RPT], pk2[HAS2 ? RPT : 1], pv[RPT];
@@ -699,7 +605,6 @@ __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs A) {
     if (nfull) { load_keys_full(lo); load_values_full(lo); }
     else { load_keys_tail(lo); load_values_tail(lo); }
   }
-  lds_barrier();
 
   for (uint64_t tile = 0; tile < ntiles; ++tile) {
     const uint64_t base = lo + tile * TILE;
@@ -714,46 +619,20 @@ __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs A) {
       if (GENERIC && (A.f.end_time != 0 || has_ts)) {
         const uint64_t i = row_index(base, j);
         const int64_t ts = (has_ts && i < hi) ? ld_time<T32>(A.t_start, i) : 0;
-        kept = p_time_kept(te, ts, has_ts, A.f);
+        kept = time_kept(te, ts, has_ts, A.f);
       }
-      uint32_t bucket = 0;
-      bool on_lattice;
-      if (GENERIC) {
-        on_lattice = p_bucket(A.L, te, bucket);
-      } else {  // mode 0 or 1: one multiply-high
-        const uint64_t d = (uint64_t)te - (uint64_t)A.L.t0;
-        const uint64_t bq = A.L.mode == 0 ? d : __umul64hi(d, A.L.magic);
-        on_lattice = (d >> 32) == 0 && bq < A.L.nb && bq * (uint64_t)A.L.step == d;
-        bucket = (uint32_t)bq;
-      }
+      uint64_t bucket = 0;   // (kept in 32 bits below: a lattice that reaches pass B has nb < 2^16 buckets, part_plan_tiles, or a cell field of at most 28 bits, part_plan_sparse)
+      const bool on_lattice = GENERIC ? lattice_bucket(A.L, te, bucket) : lattice_bucket_fast(A.L, te, bucket);
 #pragma unroll
       for (int h = 0; h < (HAS2 ? 2 : 1); ++h) {
         const int slot = j * (HAS2 ? 2 : 1) + h;
-        const uint64_t k = h == 0 ? pk[j] : pk2[HAS2 ? j : 0];
-        r_cell[slot] = cell_none;
+        r_cell[slot] = (1u << A.cell_bits) - 1u;
         r_pr[slot] = 0xFFFFFFFFu;
-        if (kept && k != TAD_KEY_SKIP && k < A.K) {  // same predicate as pass A: the slot is reserved
-          uint32_t cell = cell_none;
-          if (on_lattice) {
-            used++;
-            const bool big = pv[j] >= value_limit || (A.narrow_limit != 0 && pv[j] >= A.narrow_limit);
-            if (!big || A.narrow_limit != 0) cell = bucket * KP + ((uint32_t)k & A.kp_mask);
-            if (big) {  // rare: the value does not fit the record (or the 32-bit tile cell) -> overflow list
-              const unsigned long long o = atomicAdd(A.ovf_count, 1ull);
-              if (o < A.ovf_cap) { A.ovf[o].val = pv[j]; A.ovf[o].gcell = (unsigned long long)bucket * A.K + k; }
-              else err |= DEV_ERR_OVERFLOW_LIST;
-              if (A.ovf_keys != nullptr) atomicOr(A.ovf_keys + (k >> 5), 1u << (k & 31u));
-              if (A.narrow_limit != 0) r_big |= 1u << slot;      // the record stays, with the sentinel value
-            }
-          } else {
-            err |= DEV_ERR_OFF_LATTICE;  // wrong lattice hint, or the sampled gcd missed a residue: host re-derives
-          }
-          const uint32_t p = (uint32_t)(k >> A.shift_part);
-          r_cell[slot] = cell;
-          r_pr[slot] = (p << 16) | atomicAdd(&off[p], 1u);
-        } else if (kept && k != TAD_KEY_SKIP) {
-          err |= DEV_ERR_KEY_RANGE;   // pass A reports it too, but only for the rows it reads: with a sampled histogram that is one row in sixteen
-        }
+        part_slot(A, kept, on_lattice, (uint32_t)bucket, h == 0 ? pk[j] : pk2[HAS2 ? j : 0], pv[j], err, used, [&](const PartSlot &ps) {
+          if (ps.sentinel) r_big |= 1u << slot;
+          r_cell[slot] = ps.cell;
+          r_pr[slot] = (ps.part << 16) | atomicAdd(&off[ps.part], 1u);
+        });
       }
     }
     if (next_kind == 1) load_keys_full(base + TILE);  // lands during phases 2-4
@@ -766,7 +645,7 @@ __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs A) {
     for (int slot = 0; slot < NSLOT; ++slot) {
       if (r_pr[slot] != 0xFFFFFFFFu) {
         const uint32_t pos = off[r_pr[slot] >> 16] + (r_pr[slot] & 0xFFFFu);
-        rec[pos] = (((r_big >> slot) & 1u ? A.narrow_limit : pv[slot / (HAS2 ? 2 : 1)]) << A.cell_bits) | r_cell[slot];
+        rec[pos] = part_record(A, pv[slot / (HAS2 ? 2 : 1)], r_cell[slot], (r_big >> slot) & 1u);
         part[pos] = (uint16_t)(r_pr[slot] >> 16);
       }
     }
@@ -792,8 +671,7 @@ __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs A) {
     lds_barrier();
   }
   if (A.fin != nullptr) {
-    uint32_t *fo = A.fin + (size_t)blockIdx.x * F * 2;
-    for (uint32_t p = threadIdx.x; p < F; p += kPartThreads) { fo[2 * p] = gcur[p]; fo[2 * p + 1] = gend[p]; }
+    for (uint32_t p = threadIdx.x; p < F; p += kPartThreads) regions_fin(A, F, p, gcur[p], gend[p]);   // (nothing spills in this pass)
   } else {
     // exact regions are read whole by pass C: counts of this batch fill them to the last slot; counts that are not this batch's (a caller's
     // tad_key_hist) may leave slots over, which become `no cell` fillers like the line padding of the write-combining pass
@@ -803,7 +681,7 @@ __global__ __launch_bounds__(kPartThreads) void k_partition(PartArgs A) {
   // a region that was too small: sampled histogram — or exact counts that are not this batch's (a caller's tad_key_hist): the records were
   // left out, never written past the region; the host redoes the job with its own count
   if (s_full) err |= DEV_ERR_REGION_FULL;
-  block_count_rows(used, err, A.ctr);
+  block_count_rows<kPartThreads>(used, err, A.ctr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -860,20 +738,11 @@ __global__ __launch_bounds__(kPartThreads) void k_partition_wc(PartArgs A, uint3
   __shared__ unsigned long long s_spill_rec[kSpillSlots];
   __shared__ uint32_t s_spill_at[kSpillSlots];
   __shared__ uint32_t s_nspill2[2];
+  __shared__ uint32_t s_shut;      // regions_open: this workgroup has nothing to do
 
-  if (A.fin != nullptr && (A.ctr->err & DEV_ERR_REGION_FULL)) return;   // k_part_offsets: this table is redone with the exact histogram
-  {
-    const uint32_t *my = A.offs32 + (size_t)blockIdx.x * F;
-    const uint32_t *nx = A.offs32 + (size_t)(blockIdx.x + 1) * F;
-    const bool last = (int)blockIdx.x + 1 == G;
-    for (uint32_t p = threadIdx.x; p < F; p += kPartThreads) {
-      const uint32_t ps = (uint32_t)A.part_start[p];
-      nsp[p] = 0;
-      gcur[p] = ps + my[p];
-      gend[p] = last ? (uint32_t)A.part_start[p + 1] : ps + nx[p];
-    }
-    if (threadIdx.x == 0) { s_njobs2[0] = s_njobs2[1] = 0; s_nspill2[0] = s_nspill2[1] = 0; }
-  }
+  regions_open<kPartThreads>(A, G, F, gcur, gend, &s_shut);
+  for (uint32_t p = threadIdx.x; p < F; p += kPartThreads) nsp[p] = 0;
+  if (threadIdx.x == 0) { s_njobs2[0] = s_njobs2[1] = 0; s_nspill2[0] = s_nspill2[1] = 0; }
   // Queue depths follow the workgroup's histogram row.  A queue keeps SEC - 1 slots for its leftovers; behind them it needs room for a
   // tile's arrivals, ~Poisson(lambda_p) with lambda_p = the tile's record slots x the partition's share of this workgroup's records
   // (region size = pass A's count, or its capacity estimate).  The pool is shared out as lambda_p + z sqrt(lambda_p) with ONE z for all
@@ -892,6 +761,7 @@ __global__ __launch_bounds__(kPartThreads) void k_partition_wc(PartArgs A, uint3
     for (int d = 32; d >= 1; d >>= 1) { rsum += __shfl_down(rsum, d); ract += __shfl_down(ract, d); const uint32_t o = __shfl_down(rmax, d); rmax = o > rmax ? o : rmax; }
     if (lane == 0) { s_red[wave] = rsum; s_red[kPartThreads / 64 + wave] = ract; s_red[2 * (kPartThreads / 64) + wave] = rmax; }
     lds_barrier();
+    if (s_shut) return;   // as in k_partition: one thread's answer, read by all behind the barrier — the workgroup leaves whole or not at all
     rsum = 0; ract = 0; rmax = 0;
     for (int w = 0; w < kPartThreads / 64; ++w) {
       rsum += s_red[w]; ract += s_red[kPartThreads / 64 + w];
@@ -923,6 +793,8 @@ __global__ __launch_bounds__(kPartThreads) void k_partition_wc(PartArgs A, uint3
     const bool ok = skewed && tmp[F] <= pool;                          // (the sum fits by the arithmetic above: a safety net, not a code path)
     for (uint32_t p = threadIdx.x; p <= F; p += kPartThreads) cnt[p] = (ok ? tmp[p] : p * cap) << 16;   // (cnt lies behind the queues: no overlap with tmp)
 #else
+    lds_barrier();
+    if (s_shut) return;       // (as above: this build has no barrier of its own in the prologue)
     for (uint32_t p = threadIdx.x; p <= F; p += kPartThreads) cnt[p] = (p * cap) << 16;
 #endif
   }
@@ -930,9 +802,6 @@ __global__ __launch_bounds__(kPartThreads) void k_partition_wc(PartArgs A, uint3
   const uint64_t lo = (uint64_t)blockIdx.x * A.chunk;
   const uint64_t hi = lo + A.chunk < A.n ? lo + A.chunk : A.n;
   const bool has_ts = TS || (GENERIC && A.t_start != nullptr && A.f.start_time != 0);
-  const uint32_t KP = A.kp_mask + 1u;
-  const uint32_t cell_none = (1u << A.cell_bits) - 1u;
-  const unsigned long long value_limit = A.value_limit;
   uint32_t err = 0, used = 0;
   const uint64_t nfull = hi > lo ? (hi - lo) / TILE : 0;
   const uint64_t ntiles = hi > lo ? (hi - lo + TILE - 1) / TILE : 0;
@@ -977,40 +846,15 @@ __global__ __launch_bounds__(kPartThreads) void k_partition_wc(PartArgs A, uint3
       if (GENERIC && (A.f.end_time != 0 || has_ts)) {
         const uint64_t i = row_index(base, j);
         const int64_t ts = TS ? r.ts[TS ? j : 0] : ((has_ts && i < hi) ? ld_time<T32>(A.t_start, i) : 0);
-        kept = p_time_kept(te, ts, has_ts, A.f);
+        kept = time_kept(te, ts, has_ts, A.f);
       }
-      uint32_t bucket = 0;
-      bool on_lattice;
-      if (GENERIC) {
-        on_lattice = p_bucket(A.L, te, bucket);
-      } else {
-        const uint64_t d = (uint64_t)te - (uint64_t)A.L.t0;
-        const uint64_t bq = A.L.mode == 0 ? d : __umul64hi(d, A.L.magic);
-        on_lattice = (d >> 32) == 0 && bq < A.L.nb && bq * (uint64_t)A.L.step == d;
-        bucket = (uint32_t)bq;
-      }
+      uint64_t bucket = 0;   // (kept in 32 bits below: a lattice that reaches pass B has nb < 2^16 buckets, part_plan_tiles, or a cell field of at most 28 bits, part_plan_sparse)
+      const bool on_lattice = GENERIC ? lattice_bucket(A.L, te, bucket) : lattice_bucket_fast(A.L, te, bucket);
 #pragma unroll
       for (int h = 0; h < (HAS2 ? 2 : 1); ++h) {
-        const uint64_t k = h == 0 ? r.k[j] : r.k2[HAS2 ? j : 0];
-        if (kept && k != TAD_KEY_SKIP && k < A.K) {  // same predicate as pass A: the slot is reserved
-          uint32_t cell = cell_none;
-          unsigned long long vrec = r.v[j];
-          if (on_lattice) {
-            used++;
-            const bool big = r.v[j] >= value_limit || (A.narrow_limit != 0 && r.v[j] >= A.narrow_limit);
-            if (!big || A.narrow_limit != 0) cell = bucket * KP + ((uint32_t)k & A.kp_mask);
-            if (big) {
-              const unsigned long long o = atomicAdd(A.ovf_count, 1ull);
-              if (o < A.ovf_cap) { A.ovf[o].val = r.v[j]; A.ovf[o].gcell = (unsigned long long)bucket * A.K + k; }
-              else err |= DEV_ERR_OVERFLOW_LIST;
-              if (A.ovf_keys != nullptr) atomicOr(A.ovf_keys + (k >> 5), 1u << (k & 31u));
-              if (A.narrow_limit != 0) vrec = A.narrow_limit;   // the record stays, with the sentinel value: the tile cell becomes all ones
-            }
-          } else {
-            err |= DEV_ERR_OFF_LATTICE;
-          }
-          const uint32_t p = (uint32_t)(k >> A.shift_part);
-          const unsigned long long rec = (vrec << A.cell_bits) | cell;
+        part_slot(A, kept, on_lattice, (uint32_t)bucket, h == 0 ? r.k[j] : r.k2[HAS2 ? j : 0], r.v[j], err, used, [&](const PartSlot &ps) {
+          const uint32_t p = ps.part;
+          const unsigned long long rec = part_record(A, r.v[j], ps.cell, ps.sentinel);
 #if TAD_WAVE_AGG
           // Rows that arrive sorted (a GROUP BY result, a view ordered by its key; the first rows of any table whose ids were handed out in
           // order of first appearance) send most lanes of a wavefront to ONE partition: 64 atomics on one LDS word, a queue of ~20 slots
@@ -1030,7 +874,7 @@ __global__ __launch_bounds__(kPartThreads) void k_partition_wc(PartArgs A, uint3
               k0 = (uint32_t)__shfl((int)k0, (int)__builtin_ctzll(grp)) + rank;   // (from the group's OWN first lane: right whichever lanes execute this together)
               if (k0 < gend[p0] - gcur[p0]) A.recs[gend[p0] - 1u - k0] = rec;
               else err |= DEV_ERR_REGION_FULL;
-              continue;
+              return;
             }
           }
 #endif
@@ -1058,9 +902,7 @@ __global__ __launch_bounds__(kPartThreads) void k_partition_wc(PartArgs A, uint3
               else A.recs[at] = rec;                                       // a hot key: more spills in one tile than the buffer holds
             } else err |= DEV_ERR_REGION_FULL;                             // sampled regions only: the region is full
           }
-        } else if (kept && k != TAD_KEY_SKIP) {
-          err |= DEV_ERR_KEY_RANGE;   // pass A reports it too, but only for the rows it reads: with a sampled histogram that is one row in sixteen
-        }
+        });
       }
     }
     load_tile(r, tile + 2);  // this register set is free again: lands during the rest of this tile and the whole next one
@@ -1110,8 +952,7 @@ __global__ __launch_bounds__(kPartThreads) void k_partition_wc(PartArgs A, uint3
     if (A.fin != nullptr) {
       if (c <= e - g && g <= e) { for (uint32_t i = 0; i < c; ++i) A.recs[g + i] = q[qo + i]; g += c; }
       else err |= DEV_ERR_REGION_FULL;
-      uint32_t *fo = A.fin + ((size_t)blockIdx.x * F + p) * 2;
-      fo[0] = g; fo[1] = e;
+      regions_fin(A, F, p, g, e);
     } else if (c <= e - g && g <= e) {
       for (uint32_t i = 0; i < c; ++i) A.recs[g + i] = q[qo + i];
       for (g += c; g < e; ++g) A.recs[g] = ~0ull;
@@ -1119,7 +960,7 @@ __global__ __launch_bounds__(kPartThreads) void k_partition_wc(PartArgs A, uint3
       err |= DEV_ERR_REGION_FULL;   // exact counts that are not this batch's (a caller's tad_key_hist): nothing is written past the region
     }
   }
-  block_count_rows(used, err, A.ctr);
+  block_count_rows<kPartThreads>(used, err, A.ctr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1610,12 +1451,6 @@ bool part_plan_settle(uint64_t T, PartPlan *pl, bool narrow) {
   return true;
 }
 
-static bool aligned16(const void *p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-bool columns_aligned16(const void *key, const void *key2, const void *t_end, const void *value) {
-  return aligned16(key) && aligned16(key2) && aligned16(t_end) && aligned16(value);
-}
-
 // write-combining pass B: F * (8 * cap + 18) bytes of LDS.  With >= 18 slots per partition the queues emit whole
 // 128-byte lines (16 records), with 9..17 slots 64-byte sectors; below 9 slots (more than ~1800 partitions) and for
 // tables with so few partitions that the sort-by-tile pass already writes long runs, the old pass runs.
@@ -1655,25 +1490,21 @@ void part_plan_wc(uint64_t slots, bool aligned, bool has2, int partition_pass, P
   pl->pad_slots = pad;
 }
 
-bool launch_meta_hist(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
-                      const int64_t *t_start, uint64_t n, uint64_t K, RowFilter f, const PartPlan &pl,
-                      MetaPartial *partials, uint32_t *binhist, DevCounters *ctr, int cw, bool sample_hist) {
-  const bool vec = aligned16(key) && aligned16(key2) && aligned16(t_end);
-  const bool has2 = key2 != nullptr;
+bool launch_meta_hist(hipStream_t s, const RowCols &rows, uint64_t K, RowFilter f, const PartPlan &pl,
+                      MetaPartial *partials, uint32_t *binhist, DevCounters *ctr, bool sample_hist) {
+  const bool vec = rows.keys_aligned16();
   // the histogram is sampled with 16-byte loads only; a time-window filter (anomaly_detection.py:581-586) is applied to the sampled rows
-  const bool sh = sample_hist && vec && (t_start == nullptr || f.start_time == 0 || aligned16(t_start));
-  with_widths(cw, [&](auto k32, auto t32) {
-#define TAD_MH(V, H2, SH)                                                                                              \
-  do {                                                                                                                 \
-    allow_big_lds(reinterpret_cast<const void *>(k_meta_hist<V, H2, SH, k32(), t32()>), kLdsBudget);                   \
-    hipLaunchKernelGGL((k_meta_hist<V, H2, SH, k32(), t32()>), dim3(pl.G), dim3(kPartThreads), (size_t)pl.nbins * 4, s, key, key2, t_end, \
-                       t_start, n, pl.chunk, K, f, pl.shift_bin, pl.nbins, partials, binhist, ctr);                    \
-  } while (0)
-    if (vec) {
-      if (sh) { if (has2) TAD_MH(true, true, true); else TAD_MH(true, false, true); }
-      else { if (has2) TAD_MH(true, true, false); else TAD_MH(true, false, false); }
-    } else { if (has2) TAD_MH(false, true, false); else TAD_MH(false, false, false); }
-#undef TAD_MH
+  const bool sh = sample_hist && vec && (rows.t_start == nullptr || f.start_time == 0 || rows.start_aligned16());
+  with_widths(rows.cw, [&](auto k32, auto t32) {
+    constexpr bool K32 = decltype(k32)::value, T32 = decltype(t32)::value;
+    with_bools([&](auto v, auto h2, auto shc) {
+      constexpr bool V = decltype(v)::value, H2 = decltype(h2)::value, SH = decltype(shc)::value;
+      if constexpr (V || !SH) {   // a sampled histogram is read with 16-byte loads
+        allow_big_lds(reinterpret_cast<const void *>(k_meta_hist<V, H2, SH, K32, T32>), kLdsBudget);
+        hipLaunchKernelGGL((k_meta_hist<V, H2, SH, K32, T32>), dim3(pl.G), dim3(kPartThreads), (size_t)pl.nbins * 4, s, rows.key, rows.key2, rows.t_end,
+                           rows.t_start, rows.n, pl.chunk, K, f, pl.shift_bin, pl.nbins, partials, binhist, ctr);
+      } else dispatch_hole("k_meta_hist");
+    }, vec, rows.has2(), sh);
   });
   return sh;
 }
@@ -1725,43 +1556,43 @@ void launch_part_offsets(hipStream_t s, const uint32_t *binhist, const PartPlan 
   hipLaunchKernelGGL(k_part_tail, dim3(1), dim3(256), 0, s, A);
 }
 
-void launch_partition(hipStream_t s, const uint64_t *key, const uint64_t *key2, const int64_t *t_end,
-                      const int64_t *t_start, const uint64_t *value, uint64_t n, uint64_t K, RowFilter f, Lattice L,
+template <int N> using int_c = std::integral_constant<int, N>;
+
+void launch_partition(hipStream_t s, const RowCols &rows, uint64_t K, RowFilter f, Lattice L,
                       const PartPlan &pl, const uint32_t *offs32, const unsigned long long *part_start, void *recs,
-                      OverflowRec *ovf, unsigned long long *ovf_count, uint32_t ovf_cap, DevCounters *ctr, uint32_t *fin, uint32_t *ovf_keys, int cw) {
+                      OverflowRec *ovf, unsigned long long *ovf_count, uint32_t ovf_cap, DevCounters *ctr, uint32_t *fin, uint32_t *ovf_keys) {
   PartArgs A;
   A.fin = fin; A.G = pl.G;
   A.value_limit = 1ull << (64 - pl.cell_bits);
   A.narrow_limit = pl.narrow ? 0xFFFFFFFEull : 0ull;     // (value + 1 of every in-range value stays below the all-ones word)
   A.ovf_keys = ovf_keys;
-  A.key = key; A.key2 = key2; A.t_end = t_end; A.t_start = t_start; A.value = value;
-  A.n = n; A.chunk = pl.chunk; A.K = K; A.f = f; A.L = L;
+  A.key = rows.key; A.key2 = rows.key2; A.t_end = rows.t_end; A.t_start = rows.t_start; A.value = rows.value;
+  A.n = rows.n; A.chunk = pl.chunk; A.K = K; A.f = f; A.L = L;
   A.shift_part = pl.shift_part; A.kp_mask = pl.KP - 1; A.nparts = pl.nparts; A.cell_bits = pl.cell_bits;
   A.offs32 = offs32; A.part_start = part_start;
   A.recs = static_cast<unsigned long long *>(recs); A.ctr = ctr;
   A.ovf = ovf; A.ovf_count = ovf_count; A.ovf_cap = ovf_cap;
-  const bool has2 = key2 != nullptr;
-  const bool vec = aligned16(key) && aligned16(key2) && aligned16(t_end) && aligned16(value);
+  const bool has2 = rows.has2();
+  const bool vec = rows.aligned16();
   // fast path: 16-byte loads, no time-window filter, bucket by one multiply-high
-  const bool generic = !vec || L.mode == 2 || f.end_time != 0 || (f.start_time != 0 && t_start != nullptr);
-  with_widths(cw, [&](auto k32, auto t32) {
+  const bool generic = !vec || L.mode == 2 || f.end_time != 0 || (f.start_time != 0 && rows.t_start != nullptr);
+  with_widths(rows.cw, [&](auto k32, auto t32) {
     constexpr bool K32 = decltype(k32)::value, T32 = decltype(t32)::value;
     if (pl.wc_cap) {  // write-combining variant (the plan checked the alignment)
       const size_t wlds = ((size_t)pl.nparts * (8 * (size_t)pl.wc_cap + kWcFixedBytes) + 4 + 15) & ~(size_t)15;
-      const bool ts16 = generic && t_start != nullptr && f.start_time != 0 && aligned16(t_start);   // start times prefetched with the tile
-#define TAD_WC1(RPT, SEC, H2, GEN, TS)                                                                                  \
-  do {                                                                                                                \
-    allow_big_lds(reinterpret_cast<const void *>(k_partition_wc<RPT, SEC, H2, GEN, TS, K32, T32>), kLdsBudget);        \
-    hipLaunchKernelGGL((k_partition_wc<RPT, SEC, H2, GEN, TS, K32, T32>), dim3(pl.G), dim3(kPartThreads), wlds, s, A, pl.wc_cap, pl.G); \
-  } while (0)
-#define TAD_WC(RPT, SEC, H2, GEN) do { if (GEN && ts16) TAD_WC1(RPT, SEC, H2, GEN, GEN); else TAD_WC1(RPT, SEC, H2, GEN, false); } while (0)
-#define TAD_WC_SEC(RPT, H2, GEN) do { if (pl.wc_sec == 16) TAD_WC(RPT, 16, H2, GEN); else TAD_WC(RPT, 8, H2, GEN); } while (0)
-      if (pl.wc_rpt == 4 && !has2) { if (generic) TAD_WC_SEC(4, false, true); else TAD_WC_SEC(4, false, false); }
-      else if (has2) { if (generic) TAD_WC_SEC(2, true, true); else TAD_WC_SEC(2, true, false); }
-      else { if (generic) TAD_WC_SEC(2, false, true); else TAD_WC_SEC(2, false, false); }
-#undef TAD_WC_SEC
-#undef TAD_WC
-#undef TAD_WC1
+      const bool ts16 = generic && rows.t_start != nullptr && f.start_time != 0 && rows.start_aligned16();   // start times prefetched with the tile
+      auto wc = [&](auto rptc, auto secc) {
+        constexpr int RPT = decltype(rptc)::value, SEC = decltype(secc)::value;
+        with_bools([&](auto h2, auto gen, auto ts) {
+          constexpr bool H2 = decltype(h2)::value, GEN = decltype(gen)::value, TS = decltype(ts)::value;
+          if constexpr ((GEN || !TS) && (RPT == 2 || !H2)) {   // TS only with GENERIC; four rows per thread only with one key
+            allow_big_lds(reinterpret_cast<const void *>(k_partition_wc<RPT, SEC, H2, GEN, TS, K32, T32>), kLdsBudget);
+            hipLaunchKernelGGL((k_partition_wc<RPT, SEC, H2, GEN, TS, K32, T32>), dim3(pl.G), dim3(kPartThreads), wlds, s, A, pl.wc_cap, pl.G);
+          } else dispatch_hole("k_partition_wc");
+        }, has2, generic, ts16);
+      };
+      if (pl.wc_rpt == 4 && !has2) { if (pl.wc_sec == 16) wc(int_c<4>{}, int_c<16>{}); else wc(int_c<4>{}, int_c<8>{}); }
+      else { if (pl.wc_sec == 16) wc(int_c<2>{}, int_c<16>{}); else wc(int_c<2>{}, int_c<8>{}); }
       return;
     }
     int rpt = pl.rpt;
@@ -1769,26 +1600,26 @@ void launch_partition(hipStream_t s, const uint64_t *key, const uint64_t *key2, 
     if ((K32 || T32) && rpt > 4) rpt = 4;   // narrow columns: the sort-by-tile pass at 2 or 4 rows per thread (fewer instantiations)
     const size_t fixed = ((size_t)pl.nparts + 4) * 16 + 64;
     const size_t lds = ((size_t)rpt * kPartThreads * (has2 ? 2 : 1) * 10 + fixed + 15) & ~(size_t)15;
-#define TAD_PART(RPT, H2, V, GEN)                                                                                       \
-  do {                                                                                                                \
-    allow_big_lds(reinterpret_cast<const void *>(k_partition<RPT, H2, V, GEN, K32, T32>), kLdsBudget);                 \
-    hipLaunchKernelGGL((k_partition<RPT, H2, V, GEN, K32, T32>), dim3(pl.G), dim3(kPartThreads), lds, s, A);            \
-  } while (0)
+    auto part = [&](auto rptc) {
+      constexpr int RPT = decltype(rptc)::value;
+      with_bools([&](auto h2, auto v, auto gen) {
+        constexpr bool H2 = decltype(h2)::value, V = decltype(v)::value, GEN = decltype(gen)::value;
+        // the fast path reads 16 bytes; 8 and 10 rows per thread only on it and only for 8-byte columns; a second key takes 8 where one key takes 10
+        if constexpr ((GEN || V) && (RPT <= 4 || (!GEN && !K32 && !T32)) && (RPT != 10 || !H2)) {
+          allow_big_lds(reinterpret_cast<const void *>(k_partition<RPT, H2, V, GEN, K32, T32>), kLdsBudget);
+          hipLaunchKernelGGL((k_partition<RPT, H2, V, GEN, K32, T32>), dim3(pl.G), dim3(kPartThreads), lds, s, A);
+        } else dispatch_hole("k_partition");
+      }, has2, vec, generic);
+    };
     if (!generic) {
       switch (rpt) {
-        case 10: if constexpr (!K32 && !T32) { if (has2) TAD_PART(8, true, true, false); else TAD_PART(10, false, true, false); } break;
-        case 8: if constexpr (!K32 && !T32) { if (has2) TAD_PART(8, true, true, false); else TAD_PART(8, false, true, false); } break;
-        case 6: case 4: if (has2) TAD_PART(4, true, true, false); else TAD_PART(4, false, true, false); break;
-        default: if (has2) TAD_PART(2, true, true, false); else TAD_PART(2, false, true, false); break;
+        case 10: if (has2) part(int_c<8>{}); else part(int_c<10>{}); break;
+        case 8: part(int_c<8>{}); break;
+        case 6: case 4: part(int_c<4>{}); break;
+        default: part(int_c<2>{}); break;
       }
-    } else if (vec) {
-      if (rpt >= 4) { if (has2) TAD_PART(4, true, true, true); else TAD_PART(4, false, true, true); }
-      else { if (has2) TAD_PART(2, true, true, true); else TAD_PART(2, false, true, true); }
-    } else {
-      if (rpt >= 4) { if (has2) TAD_PART(4, true, false, true); else TAD_PART(4, false, false, true); }
-      else { if (has2) TAD_PART(2, true, false, true); else TAD_PART(2, false, false, true); }
-    }
-#undef TAD_PART
+    } else if (rpt >= 4) part(int_c<4>{});
+    else part(int_c<2>{});
   });
 }
 

@@ -71,9 +71,10 @@ def drop_stats(x):
 
 
 def drop_detection_series(x, n_sigma=N_SIGMA, min_samples=MIN_SAMPLES):
-    """-> None (too few samples) or (mean, std, verdict bool[n])."""
+    """-> None (no result) or (mean, std, verdict bool[n]).  A series has a result iff n >= min_samples and n >= 2 (include/tad.h): the
+    UDF's own rule at its min_samples of 3; below 2 points the sample standard deviation does not exist."""
     x = np.asarray(x, dtype=np.float64)
-    if x.size < min_samples:
+    if x.size < min_samples or x.size < 2:
         return None
     mean, std = drop_stats(x)
     upper, lower = mean + n_sigma * std, mean - n_sigma * std
@@ -82,11 +83,14 @@ def drop_detection_series(x, n_sigma=N_SIGMA, min_samples=MIN_SAMPLES):
     return mean, std, verdict
 
 
-def run_job(key_id, day_s, drop_number, n_sigma=N_SIGMA, min_samples=MIN_SAMPLES):
+def run_job(key_id, day_s, drop_number, n_sigma=N_SIGMA, min_samples=MIN_SAMPLES, value_op="sum", key_id2=None, flow_start_s=None,
+            start_time=0, end_time=0):
     """Columnar batch -> anomalous (key, day) rows, ordered by (key, day).  Stage 0 = SUM(dropNumber) GROUP BY
-    endpoint, direction, date (snowflake/cmd/dropDetection.go:151-162) through the TAD oracle's integer group-by."""
+    endpoint, direction, date (snowflake/cmd/dropDetection.go:151-162) through the TAD oracle's integer group-by; value_op, key_id2,
+    flow_start_s, start_time and end_time are tad_oracle.stage0's (tad_run takes them for every detector).  keys_no_result: the keys
+    with points and without a result (drop_detection_series)."""
     from . import tad_oracle as orc
-    pk, pt, pv = orc.stage0(key_id, day_s, drop_number, "sum")
+    pk, pt, pv = orc.stage0(key_id, day_s, drop_number, value_op, key_id2, flow_start_s, start_time, end_time)
     keys, ptr = orc.series_offsets(pk)
     xf = orc.u64_to_f64(pv)
     sel, means, stds = [], [], []

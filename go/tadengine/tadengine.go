@@ -2166,3 +2166,122 @@ func (d *StringDict) Decode(codes []int64) (offsets []int64, data []byte, err er
 	}
 	return offsets, data, nil
 }
+
+var stringRetireOnce sync.Once
+var stringRetireOK bool
+
+// hasStringRetire: the library retires strings (tad_features); an older one would not export the three calls.  Like the rest of this
+// binding the three methods below are never compiled in the project's checks (no Go toolchain runs there): they are written against
+// include/tad.h and read by tests/test_string_retire_abi.py as text.
+func hasStringRetire() bool {
+	stringRetireOnce.Do(func() { stringRetireOK = C.tad_features()&C.TAD_FEATURE_STRING_RETIRE != 0 })
+	return stringRetireOK
+}
+
+var errNoStringRetire = errors.New("tadengine: libtad_mi355x.so retires no strings (TAD_FEATURE_STRING_RETIRE)")
+
+// CodeNone is remap's entry for a retired value (TAD_CODE_NONE).
+const CodeNone = int64(-1)
+
+// StrdictCompactStats is what one StringDict.Compact retired (tad_strdict_compact_stats).
+type StrdictCompactStats struct {
+	ValuesBefore, ValuesAfter       uint64
+	BytesBefore, BytesAfter         uint64 // tad_strdict_bytes at entry and at exit
+	ArenaUsedBefore, ArenaUsedAfter uint64 // padded bytes of the values held
+	MsTotal                         float32
+}
+
+// UsedCodes says which codes of key column col the keys still hold (tad_keydict_mark_codes): used[c] = 1 iff some key, on either side,
+// holds value c there.  nValues = the NumValues of the column's StringDict.  into (nil, or nValues bytes of an earlier call) is ORed
+// into: columns that share one vocabulary.  The mask crosses in C memory.
+func (d *KeyDict) UsedCodes(col int32, nValues uint64, into []byte) (used []byte, nUsed uint64, err error) {
+	if !hasStringRetire() {
+		return nil, 0, errNoStringRetire
+	}
+	if into != nil && uint64(len(into)) != nValues {
+		return nil, 0, IllegalArgument{"tadengine: UsedCodes: into holds one byte per value"}
+	}
+	buf := (*C.uint8_t)(C.calloc(C.size_t(nValues)+1, 1))
+	if buf == nil {
+		return nil, 0, errors.New("tadengine: out of memory")
+	}
+	defer C.free(unsafe.Pointer(buf))
+	acc := C.int32_t(0)
+	if into != nil {
+		acc = 1
+		copy(unsafe.Slice((*byte)(unsafe.Pointer(buf)), nValues), into)
+	}
+	var n C.uint64_t
+	if rc := C.tad_keydict_mark_codes(d.e.h, d.h, C.int32_t(col), acc, buf, C.uint64_t(nValues), C.TAD_MEM_HOST, &n); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(d.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, 0, IllegalArgument{msg}
+		}
+		return nil, 0, fmt.Errorf("tad_keydict_mark_codes: %s (code %d)", msg, int(rc))
+	}
+	used = make([]byte, nValues)
+	copy(used, unsafe.Slice((*byte)(unsafe.Pointer(buf)), nValues))
+	return used, uint64(n), nil
+}
+
+// Compact drops the values whose keep byte is 0 and renumbers the survivors densely, order kept (tad_strdict_compact).  len(keep) must
+// be NumValues.  remap[c] = the new code of old value c, or CodeNone: pass it to KeyDict.Recode.  Any failure leaves the dictionary as
+// it was.  keep and remap cross in C memory.
+func (d *StringDict) Compact(keep []byte) (remap []int64, st StrdictCompactStats, err error) {
+	if !hasStringRetire() {
+		return nil, StrdictCompactStats{}, errNoStringRetire
+	}
+	n := len(keep)
+	kbuf := (*C.uint8_t)(C.calloc(C.size_t(n)+1, 1))
+	rbuf := (*C.int64_t)(C.calloc(C.size_t(n)+1, 8))
+	defer C.free(unsafe.Pointer(kbuf))
+	defer C.free(unsafe.Pointer(rbuf))
+	if kbuf == nil || rbuf == nil {
+		return nil, StrdictCompactStats{}, errors.New("tadengine: out of memory")
+	}
+	copy(unsafe.Slice((*byte)(unsafe.Pointer(kbuf)), n), keep)
+	var scs C.tad_strdict_compact_stats
+	if rc := C.tad_strdict_compact(d.e.h, d.h, kbuf, C.uint64_t(n), C.TAD_MEM_HOST, rbuf, C.TAD_MEM_HOST, &scs); rc != C.TAD_OK {
+		return nil, StrdictCompactStats{}, d.fail("tad_strdict_compact", rc)
+	}
+	remap = make([]int64, n)
+	copy(remap, unsafe.Slice((*int64)(unsafe.Pointer(rbuf)), n))
+	return remap, StrdictCompactStats{ValuesBefore: uint64(scs.values_before), ValuesAfter: uint64(scs.values_after), BytesBefore: uint64(scs.bytes_before),
+		BytesAfter: uint64(scs.bytes_after), ArenaUsedBefore: uint64(scs.arena_used_before), ArenaUsedAfter: uint64(scs.arena_used_after),
+		MsTotal: float32(scs.ms_total)}, nil
+}
+
+// Recode rewrites key columns through code remaps (tad_keydict_recode): every key's value v in column cols[t] becomes remaps[t][v] —
+// what StringDict.Compact returned for the column's vocabulary.  Key ids and sides stay.  A value outside its remap, a value mapped
+// to CodeNone, a column named twice or two keys that collide afterwards are an IllegalArgument and leave the dictionary unchanged.
+// The remaps and the three arrays that name them cross in C memory.  Returns the keys held.
+func (d *KeyDict) Recode(cols []int32, remaps [][]int64) (uint64, error) {
+	if !hasStringRetire() {
+		return 0, errNoStringRetire
+	}
+	nt := len(cols)
+	if nt != len(remaps) || nt > 8 {
+		return 0, IllegalArgument{"tadengine: Recode takes one remap per column, at most 8"}
+	}
+	colArr := (*[8]C.int32_t)(C.calloc(8, 4))
+	ptrArr := (*[8]*C.int64_t)(C.calloc(8, C.size_t(unsafe.Sizeof(unsafe.Pointer(nil)))))
+	lenArr := (*[8]C.uint64_t)(C.calloc(8, 8))
+	defer C.free(unsafe.Pointer(colArr))
+	defer C.free(unsafe.Pointer(ptrArr))
+	defer C.free(unsafe.Pointer(lenArr))
+	for t := 0; t < nt; t++ {
+		colArr[t] = C.int32_t(cols[t])
+		lenArr[t] = C.uint64_t(len(remaps[t]))
+		ptrArr[t] = (*C.int64_t)(cColumn(remaps[t]))
+		defer C.free(unsafe.Pointer(ptrArr[t]))
+	}
+	var n C.uint64_t
+	if rc := C.tad_keydict_recode(d.e.h, d.h, C.int32_t(nt), &colArr[0], &ptrArr[0], &lenArr[0], C.TAD_MEM_HOST, &n); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(d.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return 0, IllegalArgument{msg}
+		}
+		return 0, fmt.Errorf("tad_keydict_recode: %s (code %d)", msg, int(rc))
+	}
+	return uint64(n), nil
+}

@@ -674,7 +674,7 @@ int tad_window_history_by_sort(uint64_t window_points, uint64_t state_points);
  *   - *num_keys_before and *num_keys (either may be NULL) = the keys held before and after the call.
  * One-sided batches: after batches 1..b the ids of batch b's rows equal what tad_factorize returns for those rows when called once on the
  * concatenation of batches 1..b.  Two-sided batches are numbered in the sequential order b1.a, b1.b, b2.a, b2.b, ...  Ids are never
- * reused or moved, except by tad_keydict_compact (below), which the caller asks for.  Limits: n_rows * sides < 2^32 - 1 per batch, fewer than 2^32 - 1 keys per dictionary.  An empty batch is TAD_OK.
+ * reused or moved, except by tad_keydict_compact (below), which the caller asks for.  The values of a string column move only through tad_keydict_recode (further below), after its vocabulary was compacted.  Limits: n_rows * sides < 2^32 - 1 per batch, fewer than 2^32 - 1 keys per dictionary.  An empty batch is TAD_OK.
  * tad_keydict_lookup is tad_keydict_encode read-only: an unknown tuple gets TAD_KEY_SKIP and the dictionary is unchanged.
  * tad_keydict_export writes the tuples of the keys [first_key, first_key + n_keys) into n_cols HOST arrays of n_keys entries (cols[c][i] =
  * column c of key first_key + i) and their sides into side[n_keys] (HOST, may be NULL).  tad_keydict_import fills an EMPTY dictionary so
@@ -941,7 +941,8 @@ int tad_drop_state_keys(tad_engine *e, tad_state *s, const tad_job *job, int64_t
  * batch where value *num_before + j first appears — the host reads the new strings there, and only there.  A cap below the number of new
  * values caps the list, never the codes.  *num_before / *num_values (either may be NULL) = the values held before / after the call.
  * After batches 1..b the codes of batch b's rows equal what tad_encode_strings returns for those rows when called once on the
- * concatenation of batches 1..b (the one-sided tad_keydict contract, on strings).  Codes are never reused or moved.  An empty batch is
+ * concatenation of batches 1..b (the one-sided tad_keydict contract, on strings).  Codes are never reused or moved.  The one exception is
+ * tad_strdict_compact (further below), which the caller asks for: it drops values and renumbers the rest.  An empty batch is
  * TAD_OK.  Limits: n_rows < 2^32 - 1 per batch, fewer than 2^32 - 1 values per dictionary, one string shorter than 2^32 bytes; the arena
  * of bytes is addressed with 64 bits.
  * tad_strdict_lookup is encode read-only: an unknown string gets TAD_CODE_NONE and the dictionary is unchanged.
@@ -1030,6 +1031,74 @@ int tad_keydict_gather(tad_engine *e, const tad_keydict *d, const uint64_t *key_
                        uint8_t *side /* may be NULL */);
 int tad_strdict_decode(tad_engine *e, const tad_strdict *d, const int64_t *codes, uint64_t n, tad_mem codes_memory, int64_t *offsets,
                        uint8_t *data, uint64_t data_cap, tad_mem out_memory, uint64_t *data_bytes /* may be NULL */);
+
+/* ---- retiring dead strings: a string dictionary compacted, its key dictionary recoded (TAD_FEATURE_STRING_RETIRE; check tad_features()
+ * before calling these) ----
+ * A streaming host keeps a state, a key dictionary and one string dictionary per string key column on the device.  The state and the
+ * key dictionary shed their dead keys (the key-retire calls above); the string dictionaries kept a table slot, a record and padded
+ * arena bytes for every string ever met: pod names, label sets and external IPs churn, and the match masks, the key selections and
+ * every table growth walked all of them.  Three calls close that: which codes do the keys still use, drop the others from the
+ * vocabulary, rewrite the keys' columns through the renumbering.  Key ids are untouched throughout, so a state needs no call.
+ * The chain, after the state and the key dictionary were compacted: per vocabulary one mark call per column that shares it (accumulate
+ * from the second on), one compact with the mask as keep, and ONE recode with every column's remap at the end.  Masks and remaps may stay
+ * in device memory from call to call.  Between the first compact and the recode the key dictionary still holds OLD codes: no encode,
+ * lookup, select or gather may run in between, and a recode that fails leaves the pair inconsistent (the vocabularies cannot be
+ * uncompacted) — restore both from an export taken before the chain.
+ * tad_keydict_mark_codes, read-only: used[c] = 1 iff some key of the dictionary holds value c in column col, on either side, else 0;
+ * accumulate != 0 ORs into what used holds instead of writing it whole (columns that share one vocabulary).  *n_used (may be NULL) = the
+ * ones in used after the call.  `memory` says where used lives.  col outside [0, n_cols) is refused before anything runs.  A key whose
+ * value lies outside [0, used_len) is TAD_ERR_INVALID_ARGUMENT, raised from a device flag after the kernel ran, as the select call raises
+ * a value outside its mask; used is unspecified then.  An empty dictionary is TAD_OK with used all zero (untouched when accumulating).
+ * One lane per key loads the record in 16-byte loads and stores one byte; a second pass counts.  A host used is staged in job-context
+ * workspace (used_len bytes), checked against workspace_limit (TAD_ERR_GRID_TOO_LARGE) before anything runs.
+ * tad_strdict_compact: keep_len must equal num_values — a stale length is refused, never a short read.  Value c survives iff
+ * keep[c] != 0; its new code is the number of survivors below it, so the order of first appearance is kept.  remap (required, keep_len
+ * entries in remap_memory; keep lives in keep_memory, at any byte alignment): remap[c] = the new code, or TAD_CODE_NONE for a retired
+ * value.  Afterwards the dictionary is what a fresh one holds after an import of the m survivors in new-code order: export, decode,
+ * match, lookup and encode behave identically, a retired string looks up to TAD_CODE_NONE, and a retired string that returns in a later
+ * encode gets a new code at the end (m, m + 1, ... in order of first appearance).  Records, table and arena are rebuilt at the size a
+ * create with expected_values = 2 m and expected_bytes = twice the survivors' padded bytes picks, never below the minimum sizes of
+ * create and never larger than before, so tad_strdict_bytes never grows.  The new arena is packed: survivor j starts where the
+ * survivors 0 .. j - 1 end, every string 16-byte aligned and zero-padded to a multiple of 16.  Atomic: candidate arrays are filled
+ * first and swapped in last; an allocation that fails, workspace over workspace_limit (TAD_ERR_GRID_TOO_LARGE) or a HIP error leaves the
+ * dictionary exactly as it was (remap is unspecified then).  When nothing is retired the call is TAD_OK, remap is the identity and
+ * nothing is reallocated or moved.  m == 0 leaves an empty dictionary of minimum size that takes an import again.  stats may be NULL.
+ * How: survivor flags and padded lengths (in 16-byte units) are scanned into new codes and new arena offsets; one lane per old value
+ * writes remap and a survivor's new record; the bytes move in whole aligned 16-byte words — a workgroup takes 256 consecutive survivors,
+ * whose destination is contiguous, its lanes walk the destination's words in order and find their row by a search in LDS (whole lines
+ * out, a gather in), a survivor over 4 KiB is copied by the wavefronts in turn —; the fresh table is filled from the old table's slots
+ * and the remap, no string is read or hashed.  Workspace: 32 B a value before the call, the scan's scratch, 1 B a value for a host keep
+ * and 8 B a value for a host remap.  Two synchronisations.
+ * tad_keydict_recode: for every term t, every key's value v in column term_col[t] becomes remaps[t][v].  The pointer arrays term_col,
+ * remaps and remap_len are host memory with n_terms (0..8) entries; the remaps themselves live in `memory`.  Key ids, sides and the
+ * other columns stay as they are.  TAD_ERR_INVALID_ARGUMENT with the dictionary unchanged: a value outside [0, remap_len[t]); a value
+ * mapped to TAD_CODE_NONE — a key still uses a retired string —; a column named twice; two keys whose recoded tuples are equal (found
+ * while the fresh table is built).  Fresh records and a fresh table of the current sizes are filled and swapped in last.  With
+ * n_terms == 0, or identity remaps only, the dictionary is untouched.  Afterwards an encode or a lookup of a tuple written in NEW codes
+ * gives the key's old id, and export and gather return the new codes.  *num_keys (may be NULL) = the keys held.  A host call stages its
+ * remaps in job-context workspace (8 B an entry), checked against workspace_limit before anything runs.
+ * Every call on a NULL engine or dictionary is TAD_ERR_INVALID_ARGUMENT without a device and writes nothing.  The ABI version does not
+ * change and no struct grows.  Lock order: the dictionary, then a job context; calls on one dictionary are serial.  What it costs
+ * against the export / select / import round trip: DESIGN.md §5, tools/strdict_retire_bench.py. */
+#define TAD_FEATURE_STRING_RETIRE 16384u /* tad_keydict_mark_codes, tad_strdict_compact, tad_keydict_recode: dead strings dropped, codes renumbered */
+typedef struct {
+  uint64_t values_before;            /* num_values at entry */
+  uint64_t values_after;             /* surviving values m */
+  uint64_t bytes_before;             /* tad_strdict_bytes at entry ... */
+  uint64_t bytes_after;              /* ... and at exit */
+  uint64_t arena_used_before;        /* padded bytes of the values held at entry ... */
+  uint64_t arena_used_after;         /* ... and of the survivors */
+  int32_t job_context;
+  int32_t reserved;
+  float ms_total;                    /* HIP events */
+  float reserved1;
+} tad_strdict_compact_stats;
+int tad_keydict_mark_codes(tad_engine *e, const tad_keydict *d, int32_t col, int32_t accumulate, uint8_t *used, uint64_t used_len,
+                           tad_mem memory, uint64_t *n_used /* may be NULL */);
+int tad_strdict_compact(tad_engine *e, tad_strdict *d, const uint8_t *keep, uint64_t keep_len, tad_mem keep_memory, int64_t *remap,
+                        tad_mem remap_memory, tad_strdict_compact_stats *stats /* may be NULL */);
+int tad_keydict_recode(tad_engine *e, tad_keydict *d, int32_t n_terms, const int32_t *term_col, const int64_t *const *remaps,
+                       const uint64_t *remap_len, tad_mem memory, uint64_t *num_keys /* may be NULL */);
 
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).

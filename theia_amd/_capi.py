@@ -35,6 +35,7 @@ TAD_FEATURE_DROP_ROWS = 1024                 # tad_features() bit: tad_drop_sele
 TAD_FEATURE_KEY_SELECT = 2048                # tad_features() bit: tad_keydict_select, tad_run_state_keys, tad_drop_state_keys: jobs over selected keys of a state
 TAD_FEATURE_STRING_DICT = 4096               # tad_features() bit: tad_strdict, a persistent string -> code dictionary on the device, with match masks
 TAD_FEATURE_DICT_DECODE = 8192               # tad_features() bit: tad_keydict_gather, tad_strdict_decode: ids -> tuples and codes -> strings on the device
+TAD_FEATURE_STRING_RETIRE = 16384            # tad_features() bit: tad_keydict_mark_codes, tad_strdict_compact, tad_keydict_recode: dead strings dropped, codes renumbered
 TAD_CODE_NONE = -1                           # tad_strdict_lookup: the string is not in the dictionary
 TAD_STR_EQUAL, TAD_STR_CONTAINS_NOCASE = 0, 1   # tad_strdict_match: the value is the pattern / the pattern occurs in it, ASCII letters without case
 
@@ -131,6 +132,12 @@ class CompactStats(C.Structure):
                 ("job_context", i32), ("reserved", i32), ("ms_total", f32), ("reserved1", f32)]
 
 
+class StrdictCompactStats(C.Structure):
+    """tad_strdict_compact_stats: what one tad_strdict_compact call retired and what the dictionary holds before and after."""
+    _fields_ = [("values_before", u64), ("values_after", u64), ("bytes_before", u64), ("bytes_after", u64), ("arena_used_before", u64),
+                ("arena_used_after", u64), ("job_context", i32), ("reserved", i32), ("ms_total", f32), ("reserved1", f32)]
+
+
 class Points(C.Structure):
     _fields_ = [("n_points", u64), ("key_id", C.c_void_p), ("flow_end_s", C.c_void_p), ("value", C.c_void_p),
                 ("memory", C.c_int), ("stats", Stats)]
@@ -205,6 +212,9 @@ SYMBOLS = {
     "tad_strdict_match": (C.c_int, [C.c_void_p, C.c_void_p, i32, C.c_void_p, u64, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
     "tad_keydict_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "tad_strdict_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.c_void_p, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
+    "tad_keydict_mark_codes": (C.c_int, [C.c_void_p, C.c_void_p, i32, i32, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
+    "tad_strdict_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.c_void_p, C.c_int, C.POINTER(StrdictCompactStats)]),
+    "tad_keydict_recode": (C.c_int, [C.c_void_p, C.c_void_p, i32, C.POINTER(i32), C.POINTER(C.c_void_p), C.POINTER(u64), C.c_int, C.POINTER(u64)]),
     "tad_state_compact": (C.c_int, [C.c_void_p, C.c_void_p, i64, C.c_void_p, C.c_int, C.POINTER(CompactStats)]),
     "tad_keydict_compact": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
     "tad_drop_state": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_int, C.POINTER(C.POINTER(Result))]),

@@ -498,4 +498,138 @@ int tad_keydict_compact(tad_engine *eng, tad_keydict *d, const uint64_t *remap, 
   return TAD_OK;
 }
 
+// tad.h: which codes of a column do the keys still hold (kernels: k_kd_mark, k_kd_count_used).  The dictionary is only read.
+int tad_keydict_mark_codes(tad_engine *eng, const tad_keydict *d, int32_t col, int32_t accumulate, uint8_t *used, uint64_t used_len, tad_mem memory,
+                           uint64_t *n_used) {
+  const char *who = "tad_keydict_mark_codes";
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!d || (used_len && !used) || (memory != TAD_MEM_HOST && memory != TAD_MEM_DEVICE))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bad arguments (dictionary, used buffer in host or device memory)", who);
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  if (col < 0 || col >= d->n_cols)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: column %d, the dictionary holds tuples of %d", who, (int)col, d->n_cols);
+  const uint64_t K = d->K;
+  if (used_len == 0 && K == 0) {
+    if (n_used) *n_used = 0;
+    return TAD_OK;
+  }
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "%s: no job context available", who);
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  const bool host = memory == TAD_MEM_HOST;
+  // scratch: in_key = the count | the flag word | a host call's used bytes (kd_mark_layout)
+  Carve measure(nullptr);
+  kd_mark_layout(measure, used_len, host);
+  if (measure.bytes() > e->ws_limit) return over_limit(e, who, measure.bytes());
+  int rc;
+  if ((rc = ensure(e, e->in_key, measure.bytes())) != TAD_OK) return rc;
+  Carve place(e->in_key.p);
+  const KdMarkWs w = kd_mark_layout(place, used_len, host);
+  uint8_t *d_used = host ? w.used : used;
+  HIP_TRY(e, hipMemsetAsync(w.n_used, 0, 16, s));
+  if (used_len) {
+    if (!accumulate) HIP_TRY(e, hipMemsetAsync(d_used, 0, used_len, s));
+    else if (host) HIP_TRY(e, hipMemcpyAsync(d_used, used, used_len, hipMemcpyHostToDevice, s));
+  }
+  launch_kd_mark(s, d->keys, d->n_cols, K, col, d_used, used_len, w.flags);
+  launch_kd_count_used(s, d_used, used_len, w.n_used);
+  unsigned long long count = 0;
+  uint32_t flags = 0;
+  HIP_TRY(e, hipMemcpyAsync(&count, w.n_used, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(&flags, w.flags, 4, hipMemcpyDeviceToHost, s));
+  if (host && used_len) HIP_TRY(e, hipMemcpyAsync(used, d_used, used_len, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  if (flags & KD_FLAG_BAD_CODE)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: a key's value in column %d lies outside the %llu entries of used (used unspecified)", who, (int)col,
+                (unsigned long long)used_len);
+  if (n_used) *n_used = count;
+  return TAD_OK;
+}
+
+// tad.h: the keys' columns passed through code remaps (kernels: k_kd_recode, k_kd_rehash).  The check runs first and alone; then fresh
+// records and a fresh table are filled — two keys with one recoded tuple are found there — and swapped in.
+int tad_keydict_recode(tad_engine *eng, tad_keydict *d, int32_t n_terms, const int32_t *term_col, const int64_t *const *remaps, const uint64_t *remap_len,
+                       tad_mem memory, uint64_t *num_keys) {
+  const char *who = "tad_keydict_recode";
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!d || n_terms < 0 || n_terms > kKdMaxTerms || (n_terms && (!term_col || !remaps || !remap_len)) || (memory != TAD_MEM_HOST && memory != TAD_MEM_DEVICE))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bad arguments (dictionary, 0..%d terms, remaps in host or device memory); dictionary unchanged", who, kKdMaxTerms);
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  const uint64_t K = d->K;
+  for (int t = 0; t < n_terms; ++t) {
+    if (term_col[t] < 0 || term_col[t] >= d->n_cols)
+      return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: term %d names column %d, the dictionary holds tuples of %d (dictionary unchanged)", who, t, (int)term_col[t],
+                  d->n_cols);
+    for (int u = 0; u < t; ++u)
+      if (term_col[u] == term_col[t])
+        return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: terms %d and %d both name column %d (dictionary unchanged)", who, u, t, (int)term_col[t]);
+    if (remap_len[t] && !remaps[t]) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the remap of term %d is NULL (dictionary unchanged)", who, t);
+  }
+  auto done = [&]() {      // the output is written by a call that succeeds, and by no other
+    if (num_keys) *num_keys = K;
+    return TAD_OK;
+  };
+  if (K == 0 || n_terms == 0) return done();
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "%s: no job context available", who);
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  const bool host = memory == TAD_MEM_HOST;
+  // scratch: in_key = the flag word | a host call's remaps (kd_recode_layout)
+  Carve measure(nullptr);
+  kd_recode_layout(measure, n_terms, remap_len, host);
+  if (measure.bytes() > e->ws_limit) return over_limit(e, who, measure.bytes(), " (dictionary unchanged)");
+  int rc;
+  if ((rc = ensure(e, e->in_key, measure.bytes())) != TAD_OK) return rc;
+  Carve place(e->in_key.p);
+  const KdRecodeWs w = kd_recode_layout(place, n_terms, remap_len, host);
+  KdRecode q{};
+  q.n_terms = n_terms;
+  for (int t = 0; t < n_terms; ++t) {
+    q.col[t] = term_col[t];
+    q.len[t] = remap_len[t];
+    q.remap[t] = reinterpret_cast<const long long *>(remaps[t]);
+    if (host) {
+      if (remap_len[t]) HIP_TRY(e, hipMemcpyAsync(w.remap[t], remaps[t], remap_len[t] * 8, hipMemcpyHostToDevice, s));
+      q.remap[t] = w.remap[t];
+    }
+  }
+  // 1. the check: every value has a new code.  The dictionary is only read
+  HIP_TRY(e, hipMemsetAsync(w.flags, 0, 4, s));
+  launch_kd_recode(s, d->keys, d->n_cols, K, q, nullptr, w.flags);
+  uint32_t flags = 0;
+  HIP_TRY(e, hipMemcpyAsync(&flags, w.flags, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  if (flags & KD_FLAG_BAD_CODE)
+    return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: a key's value lies outside the remap of its column or maps to TAD_CODE_NONE — the key still uses a retired "
+                                             "value (dictionary unchanged)", who);
+  if (!(flags & KD_FLAG_CHANGED)) return done();      // the identity on every value held: nothing moves
+  // 2. fresh records and a fresh table of the current sizes
+  const size_t rec = (size_t)kd_stride(d->n_cols) * 8;
+  Candidate<unsigned long long> nkeys, ntable;
+  hipError_t r = nkeys.alloc(e, d->key_cap, d->key_cap * rec);
+  if (r == hipSuccess) r = ntable.alloc(e, d->slots, d->slots * 8);
+  if (r == hipSuccess) r = hipMemsetAsync(ntable.p, 0xFF, d->slots * 8, s);
+  if (r == hipSuccess) r = hipMemsetAsync(w.flags, 0, 4, s);
+  if (r == hipSuccess) {
+    launch_kd_recode(s, d->keys, d->n_cols, K, q, nkeys.p, w.flags);
+    launch_kd_rehash(s, nkeys.p, d->n_cols, K, ntable.p, d->slots, w.flags, true);
+    r = hipMemcpyAsync(&flags, w.flags, 4, hipMemcpyDeviceToHost, s);
+  }
+  r = finish_stream(e, r);
+  if (r != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(e, r == hipErrorOutOfMemory ? TAD_ERR_OUT_OF_MEMORY : TAD_ERR_HIP, "%s: %s (dictionary unchanged)", who, hipGetErrorString(r));
+  }
+  if (flags & KD_FLAG_DUPLICATE) return fail(e, TAD_ERR_INVALID_ARGUMENT, "%s: two keys hold the same tuple after recoding (dictionary unchanged)", who);
+  nkeys.commit_into(d->keys, d->key_cap);
+  ntable.commit_into(d->table, d->slots);
+  return done();
+}
+
 }  // extern "C"

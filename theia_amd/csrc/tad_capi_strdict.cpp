@@ -451,4 +451,113 @@ int tad_strdict_decode(tad_engine *eng, const tad_strdict *d, const int64_t *cod
   return TAD_OK;
 }
 
+// tad.h: values leave, the survivors are renumbered densely and the arena is packed (kernels: k_sd_compact_*, two scans).  Fresh records,
+// a fresh arena and a fresh table are filled beside the dictionary's and swapped in together once every launch has succeeded.
+int tad_strdict_compact(tad_engine *eng, tad_strdict *d, const uint8_t *keep, uint64_t keep_len, tad_mem keep_memory, int64_t *remap, tad_mem remap_memory,
+                        tad_strdict_compact_stats *stats) {
+  const char *who = "tad_strdict_compact";
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!d || (keep_len && (!keep || !remap)) || (keep_memory != TAD_MEM_HOST && keep_memory != TAD_MEM_DEVICE) ||
+      (remap_memory != TAD_MEM_HOST && remap_memory != TAD_MEM_DEVICE))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bad arguments (dictionary, keep and remap of num_values entries in host or device memory); dictionary unchanged", who);
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  const uint64_t K = d->K;
+  if (keep_len != K)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: keep has %llu entries, the dictionary holds %llu values (dictionary unchanged)", who, (unsigned long long)keep_len,
+                (unsigned long long)K);
+  tad_strdict_compact_stats cs{};
+  cs.values_before = cs.values_after = K;
+  cs.bytes_before = cs.bytes_after = d->slots * 8 + d->rec_cap * 16 + d->arena_cap;
+  cs.arena_used_before = cs.arena_used_after = d->arena_used;
+  cs.job_context = -1;
+  if (K == 0) {
+    if (stats) *stats = cs;
+    return TAD_OK;
+  }
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "%s: no job context available", who);
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  cs.job_context = e->index;
+  const bool host_keep = keep_memory == TAD_MEM_HOST, host_remap = remap_memory == TAD_MEM_HOST;
+  // scratch: sp_val_a = the block of sd_compact_layout, scan_scratch
+  Carve measure(nullptr);
+  sd_compact_layout(measure, K, host_keep, host_remap);
+  const size_t scan_bytes = scan_scratch_elems(K) * sizeof(unsigned long long);
+  if (measure.bytes() + scan_bytes > e->ws_limit) return over_limit(e, who, measure.bytes() + scan_bytes, " (dictionary unchanged)");
+  int rc;
+  if ((rc = ensure(e, e->sp_val_a, measure.bytes())) != TAD_OK || (rc = ensure(e, e->scan_scratch, scan_bytes)) != TAD_OK) return rc;
+  Carve place(e->sp_val_a.p);
+  const SdCompactWs w = sd_compact_layout(place, K, host_keep, host_remap);
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  const uint8_t *d_keep = keep;
+  long long *d_remap = host_remap ? w.remap : reinterpret_cast<long long *>(remap);
+  // 1. who survives, what it takes; the new codes and the new arena offsets; one round trip for the two totals
+  HIP_TRY(e, hipEventRecord(e->ev[0], s));
+  if (host_keep) {
+    HIP_TRY(e, hipMemcpyAsync(w.keep, keep, K, hipMemcpyHostToDevice, s));
+    d_keep = w.keep;
+  }
+  launch_sd_compact_flags(s, d_keep, d->recs, K, w.live, w.units);
+  launch_scan(s, w.live, w.newcode, K, scratch);
+  launch_scan(s, w.units, w.off16, K, scratch);
+  unsigned long long m = 0, units = 0;
+  HIP_TRY(e, hipMemcpyAsync(&m, w.newcode + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(&units, w.off16 + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  const uint64_t bytes = units * 16ull;
+  if (m > K || bytes > d->arena_used)
+    return fail(e, TAD_ERR_HIP, "%s: %llu survivors of %llu values, %llu of %llu bytes; dictionary unchanged", who, (unsigned long long)m, (unsigned long long)K,
+                (unsigned long long)bytes, (unsigned long long)d->arena_used);
+  auto remap_out = [&](hipError_t r) -> hipError_t {
+    if (r == hipSuccess && host_remap) r = hipMemcpyAsync(remap, d_remap, K * 8, hipMemcpyDeviceToHost, s);
+    if (r == hipSuccess) r = hipEventRecord(e->ev[1], s);
+    r = finish_stream(e, r);
+    if (r == hipSuccess) r = hipEventElapsedTime(&cs.ms_total, e->ev[0], e->ev[1]);
+    return r;
+  };
+  if (m == K) {      // nothing retired: the identity, the dictionary as it is
+    launch_sd_compact_recs(s, w.live, w.newcode, w.off16, d->recs, K, d_remap, nullptr, nullptr);
+    const hipError_t r = remap_out(hipSuccess);
+    if (r != hipSuccess) return fail(e, TAD_ERR_HIP, "%s: %s (dictionary unchanged)", who, hipGetErrorString(r));
+    if (stats) *stats = cs;
+    return TAD_OK;
+  }
+  // 2. fresh records, arena and table at the size tad_strdict_create(2 m, twice the survivors' bytes) picks — its minimum for m == 0 —
+  //    and never above the current one
+  uint64_t ncap = 2 * m > kSdMinValues ? 2 * m : kSdMinValues, nslots = pow2_at_least(4 * m), narena_cap = bytes ? 2 * bytes : 16;
+  if (ncap > d->rec_cap) ncap = d->rec_cap;
+  if (nslots > d->slots) nslots = d->slots;
+  if (narena_cap > d->arena_cap) narena_cap = d->arena_cap;
+  Candidate<void> nrecs;
+  Candidate<uint8_t> narena;
+  Candidate<unsigned long long> ntable;
+  hipError_t r = nrecs.alloc(e, ncap, ncap * 16);
+  if (r == hipSuccess) r = narena.alloc(e, narena_cap, narena_cap);
+  if (r == hipSuccess) r = ntable.alloc(e, nslots, nslots * 8);
+  if (r == hipSuccess) r = hipMemsetAsync(ntable.p, 0xFF, nslots * 8, s);
+  // 3. remap and the survivors' records; their bytes; their slots
+  if (r == hipSuccess) {
+    launch_sd_compact_recs(s, w.live, w.newcode, w.off16, d->recs, K, d_remap, nrecs.p, w.src16);
+    launch_sd_compact_copy(s, nrecs.p, w.src16, m, d->arena, narena.p);
+    if (m) launch_sd_compact_rehash(s, d->table, d->slots, d->recs, K, d_remap, ntable.p, nslots);
+  }
+  r = remap_out(r);
+  if (r != hipSuccess) (void)hipGetLastError();
+  if (r != hipSuccess)
+    return fail(e, r == hipErrorOutOfMemory ? TAD_ERR_OUT_OF_MEMORY : TAD_ERR_HIP, "%s: %s (dictionary unchanged)", who, hipGetErrorString(r));
+  nrecs.commit_into(d->recs, d->rec_cap);
+  narena.commit_into(d->arena, d->arena_cap);
+  ntable.commit_into(d->table, d->slots);
+  d->K = m;
+  d->arena_used = bytes;
+  cs.values_after = m;
+  cs.bytes_after = d->slots * 8 + d->rec_cap * 16 + d->arena_cap;
+  cs.arena_used_after = bytes;
+  if (stats) *stats = cs;
+  return TAD_OK;
+}
+
 }  // extern "C"

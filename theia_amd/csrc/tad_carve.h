@@ -504,6 +504,52 @@ inline SdDecodeWs sd_decode_layout(Carve &c, uint64_t n, bool host_codes) {
   w.off = c.take<unsigned long long>((size_t)n + 1, 256); c.pad_to(256);
   return w;
 }
+// tad_strdict_compact over K values: the survivor count's cell | a host call's keep | a host call's remap | live | units | new codes
+// (K + 1) | new arena offsets in 16-byte units (K + 1) | the survivors' old offsets in 16-byte units, by new code
+struct SdCompactWs {
+  uint32_t *flags;
+  uint8_t *keep;      // NULL when keep is device memory
+  long long *remap;   // NULL when remap is device memory
+  uint32_t *live, *units;
+  unsigned long long *newcode, *off16, *src16;
+};
+inline SdCompactWs sd_compact_layout(Carve &c, uint64_t K, bool host_keep, bool host_remap) {
+  SdCompactWs w{};
+  w.flags = c.take<uint32_t>(1, 256); c.pad_to(256);
+  if (host_keep) { w.keep = c.take<uint8_t>((size_t)K, 256); c.pad_to(256); }
+  if (host_remap) { w.remap = c.take<long long>((size_t)K, 256); c.pad_to(256); }
+  w.live = c.take<uint32_t>((size_t)K, 256); c.pad_to(256);
+  w.units = c.take<uint32_t>((size_t)K, 256); c.pad_to(256);
+  w.newcode = c.take<unsigned long long>((size_t)K + 1, 256); c.pad_to(256);
+  w.off16 = c.take<unsigned long long>((size_t)K + 1, 256); c.pad_to(256);
+  w.src16 = c.take<unsigned long long>((size_t)K, 256); c.pad_to(256);
+  return w;
+}
+// tad_keydict_mark_codes: the count | the flag word; a host call's used bytes behind them
+struct KdMarkWs {
+  unsigned long long *n_used;
+  uint32_t *flags;
+  uint8_t *used;      // NULL when used is device memory
+};
+inline KdMarkWs kd_mark_layout(Carve &c, uint64_t used_len, bool host) {
+  KdMarkWs w{};
+  w.n_used = c.take<unsigned long long>(1, 256);
+  w.flags = c.take<uint32_t>(1); c.pad_to(256);
+  if (host) { w.used = c.take<uint8_t>((size_t)used_len, 256); c.pad_to(256); }
+  return w;
+}
+// tad_keydict_recode: the flag word; a host call's remaps behind it, term by term
+struct KdRecodeWs {
+  uint32_t *flags;
+  long long *remap[8];   // NULL: the term's remap is device memory (or the term does not exist)
+};
+inline KdRecodeWs kd_recode_layout(Carve &c, int n_terms, const uint64_t *remap_len, bool host) {
+  KdRecodeWs w{};
+  w.flags = c.take<uint32_t>(1, 256); c.pad_to(256);
+  if (host)
+    for (int t = 0; t < n_terms && t < 8; ++t) { w.remap[t] = c.take<long long>((size_t)remap_len[t], 256); c.pad_to(256); }
+  return w;
+}
 
 }  // namespace tad
 

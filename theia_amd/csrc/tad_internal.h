@@ -651,7 +651,7 @@ struct TupleBatch {                 // the key tuples of one batch (device point
   uint32_t sides;                   // 1 or 2
 };
 static constexpr uint32_t kKdMaxProbe = 32;     // a claim that probed further asks the host for a larger table
-enum : uint32_t { KD_FLAG_CLUSTER = 1u, KD_FLAG_DUPLICATE = 2u, KD_FLAG_BAD_ROW = 4u, KD_FLAG_BAD_CODE = 8u, KD_FLAG_BAD_ID = 16u };
+enum : uint32_t { KD_FLAG_CLUSTER = 1u, KD_FLAG_DUPLICATE = 2u, KD_FLAG_BAD_ROW = 4u, KD_FLAG_BAD_CODE = 8u, KD_FLAG_BAD_ID = 16u, KD_FLAG_CHANGED = 32u };
 int kd_stride(int n_cols);          // 8-byte words of one key record: side + columns, padded to an even count
 // every kept virtual row looks its tuple up in table[slots] / keys (K records).  miss != NULL: hits write their id, misses raise miss[v] and
 // are counted in *n_miss (zeroed by the caller), rows that are not kept get TAD_KEY_SKIP; miss == NULL: a miss is TAD_KEY_SKIP too
@@ -686,6 +686,20 @@ struct KdGatherOut {
 // col[c][i] = column c of key key_id[i], side[i] = its side, for i < n; *flags |= KD_FLAG_BAD_ID for an id >= K (zeroed by the caller),
 // that row is not written
 void launch_kd_gather(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, const uint64_t *key_id, uint64_t n, const KdGatherOut &o, uint32_t *flags);
+// tad_keydict_mark_codes: used[v] = 1 for every key's value v in column col (plain byte stores; the other bytes are the caller's);
+// *flags |= KD_FLAG_BAD_CODE for a value outside [0, used_len).  *n_used += the ones among used[0 .. used_len) (both zeroed by the caller)
+void launch_kd_mark(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, int col, uint8_t *used, uint64_t used_len, uint32_t *flags);
+void launch_kd_count_used(hipStream_t s, const uint8_t *used, uint64_t used_len, unsigned long long *n_used);
+// tad_keydict_recode: the terms of a recoding (remap: device pointers; a term past n_terms is all zero)
+struct KdRecode {
+  const long long *remap[kKdMaxTerms];
+  unsigned long long len[kKdMaxTerms];
+  int32_t col[kKdMaxTerms];
+  int32_t n_terms;
+};
+// every key's value v in column q.col[t] -> q.remap[t][v]; *flags |= KD_FLAG_BAD_CODE for a value outside its remap or mapped below 0,
+// KD_FLAG_CHANGED when a value changes (zeroed by the caller).  keys_new == NULL: the check alone; else record k of keys_new is written
+void launch_kd_recode(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, const KdRecode &q, unsigned long long *keys_new, uint32_t *flags);
 
 // ---- ingest: a string dictionary that outlives the call — strings -> codes that stay the same from batch to batch (tad_strdict.hip) ----
 struct StrBatch {                   // one Arrow string column (device pointers): what tad_encode_strings' and the dictionary's kernels read
@@ -726,6 +740,16 @@ void launch_sd_export(hipStream_t s, const void *recs, const uint8_t *arena, uin
 static constexpr uint32_t kSdDecodeRows = 256, kSdDecodeStage = 16 * 1024, kSdDecodeMaxBlocks = 2048;
 void launch_sd_decode_lens(hipStream_t s, const void *recs, uint64_t K, const long long *codes, uint64_t n, uint32_t *cnt, uint32_t *flags);
 void launch_sd_decode(hipStream_t s, const void *recs, const uint8_t *arena, const long long *codes, uint64_t n, const unsigned long long *off, uint8_t *out);
+// tad_strdict_compact.  Flags: live[c] = keep[c] != 0, units[c] = a survivor's 16-byte units in the arena (0 for a retired value).  Records:
+// newcode / off16 = the scans of live / units; remap[c] = the new code or TAD_CODE_NONE; nrecs != NULL: survivor j's new record (offset
+// 16 off16) and src16[j] = its old arena offset in 16-byte units.  Copy: the survivors' padded bytes to their new records' offsets, a
+// workgroup per 256 consecutive survivors.  Rehash: the claimed slots of old_table, codes through remap, into an empty table of `slots` slots
+void launch_sd_compact_flags(hipStream_t s, const uint8_t *keep, const void *recs, uint64_t K, uint32_t *live, uint32_t *units);
+void launch_sd_compact_recs(hipStream_t s, const uint32_t *live, const unsigned long long *newcode, const unsigned long long *off16, const void *recs, uint64_t K,
+                            long long *remap, void *nrecs, unsigned long long *src16);
+void launch_sd_compact_copy(hipStream_t s, const void *nrecs, const unsigned long long *src16, uint64_t m, const uint8_t *arena, uint8_t *narena);
+void launch_sd_compact_rehash(hipStream_t s, const unsigned long long *old_table, uint64_t old_slots, const void *recs, uint64_t K, const long long *remap,
+                              unsigned long long *table, uint64_t slots);
 
 // ---- retiring dead keys: tad_state_compact / tad_keydict_compact (tad_compact.hip) ----
 // per key: live = it survives (n > 0 and, with retire_before != 0, last_t >= retire_before), slen / hlen = the series / history elements

@@ -22,6 +22,8 @@
 // The table never passes load 1/2 (the host grows it BEFORE step 3: k_kd_rehash fills a table of twice the size from the records, and
 // the new one is swapped in when that succeeded), so every probe sequence ends at an empty slot and step 3 cannot fail.
 // The other direction (tad_keydict_gather: arbitrary ids -> tuples) reads the records only: k_kd_gather.
+// Retiring strings (tad_keydict_mark_codes, tad_keydict_recode): k_kd_mark flags the codes a column's keys still hold, k_kd_recode writes
+// the records with their columns passed through code remaps; the fresh table is filled from them by k_kd_rehash.
 #include "tad_internal.h"
 #include "tad_slots.h"
 
@@ -184,6 +186,82 @@ __global__ __launch_bounds__(kKdBlock) void k_kd_gather(const unsigned long long
   }
 }
 
+// tad_keydict_mark_codes: one lane per key.  used[v] = 1 for the key's value v in column `col` — a plain byte store; lanes that hit the
+// same code store the same value.  The bytes of the codes no key holds are the caller's (zeroed, or kept when it accumulates).  A value
+// outside [0, used_len) raises KD_FLAG_BAD_CODE and stores nothing.
+__global__ __launch_bounds__(kKdBlock) void k_kd_mark(const unsigned long long *__restrict__ keys, int pairs, uint64_t K, int col, uint8_t *__restrict__ used,
+                                                      uint64_t used_len, uint32_t *__restrict__ flags) {
+  for (uint64_t k = (uint64_t)blockIdx.x * kKdBlock + threadIdx.x; k < K; k += (uint64_t)gridDim.x * kKdBlock) {
+    ulonglong2 w[kKdMaxPairs];
+    kd_load_record(keys, k, pairs, w);
+    uint64_t v = 0;
+#pragma unroll
+    for (int c = 0; c < kFzMaxCols; ++c)
+      if (col == c) v = kd_word(w, c + 1);
+    if (v < used_len) used[v] = 1;             // (a negative value is a huge unsigned one)
+    else atomicOr(flags, KD_FLAG_BAD_CODE);
+  }
+}
+
+// ... and the ones of used: the aligned body eight bytes a lane (the non-zero bytes of a word counted without a loop), the bytes in front
+// of and behind it singly; counted per wavefront, summed in LDS, one atomic per workgroup, as k_kd_select counts — from at most
+// kKdCountBlocks workgroups, because the atomics of a kernel all meet at one address
+static constexpr unsigned kKdCountBlocks = 1024;
+__global__ __launch_bounds__(kKdBlock) void k_kd_count_used(const uint8_t *__restrict__ used, uint64_t used_len, unsigned long long *__restrict__ n_used) {
+  __shared__ uint32_t s_cnt[kKdBlock / 64];
+  const uint64_t lead = (8u - (uint32_t)(reinterpret_cast<uintptr_t>(used) & 7u)) & 7u, head = lead < used_len ? lead : used_len;
+  const uint64_t words = (used_len - head) >> 3, tail = head + words * 8;
+  const unsigned long long *w = reinterpret_cast<const unsigned long long *>(used + head);
+  const uint64_t gid = (uint64_t)blockIdx.x * kKdBlock + threadIdx.x, stride = (uint64_t)gridDim.x * kKdBlock;
+  uint32_t mine = 0;
+  for (uint64_t i = gid; i < words; i += stride) {
+    const unsigned long long x = w[i], low7 = 0x7f7f7f7f7f7f7f7full;
+    mine += (uint32_t)__popcll((((x & low7) + low7) | x) & ~low7);      // bit 7 of a byte: the byte is not 0
+  }
+  if (gid < head) mine += used[gid] != 0 ? 1u : 0u;
+  if (gid < used_len - tail) mine += used[tail + gid] != 0 ? 1u : 0u;
+  block_count_add(s_cnt, n_used, mine);
+}
+
+// tad_keydict_recode: one lane per key.  For every term t the key's value v in column col[t] becomes remap[t][v]; the record is loaded
+// whole, the term's column is picked by compares (the record stays in registers) and the loop over the terms stays rolled, as in
+// k_kd_select.  A value outside [0, len[t]) or one mapped to TAD_CODE_NONE (the key still uses a retired string) raises KD_FLAG_BAD_CODE;
+// a value that changes raises KD_FLAG_CHANGED (one atomic per wavefront).  keys_new == NULL: the check alone; else record k of keys_new =
+// the recoded record.
+__global__ __launch_bounds__(kKdBlock) void k_kd_recode(const unsigned long long *__restrict__ keys, int pairs, uint64_t K, KdRecode q,
+                                                        unsigned long long *__restrict__ keys_new, uint32_t *__restrict__ flags) {
+  bool any_bad = false, any_changed = false;
+  for (uint64_t k = (uint64_t)blockIdx.x * kKdBlock + threadIdx.x; k < K; k += (uint64_t)gridDim.x * kKdBlock) {
+    ulonglong2 w[kKdMaxPairs];
+    kd_load_record(keys, k, pairs, w);
+    bool bad = false;
+#pragma unroll 1
+    for (int t = 0; t < q.n_terms; ++t) {      // (uniform: the terms are kernel arguments)
+      const int col = q.col[t];
+      uint64_t v = 0;
+#pragma unroll
+      for (int c = 0; c < kFzMaxCols; ++c)
+        if (col == c) v = kd_word(w, c + 1);
+      const bool in = v < q.len[t];
+      const long long nv = in ? q.remap[t][v] : (long long)TAD_CODE_NONE;
+      bad |= nv < 0;
+      any_changed |= (uint64_t)nv != v;
+#pragma unroll
+      for (int c = 0; c < kFzMaxCols; ++c)
+        if (col == c) (((c + 1) & 1) ? w[(c + 1) >> 1].y : w[(c + 1) >> 1].x) = (unsigned long long)nv;
+    }
+    any_bad |= bad;
+    if (keys_new != nullptr && !bad) {
+      ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(keys_new + k * (uint64_t)(2 * pairs));
+#pragma unroll
+      for (int p = 0; p < kKdMaxPairs; ++p)
+        if (p < pairs) dst[p] = w[p];
+    }
+  }
+  const unsigned long long wb = __ballot(any_bad), wc = __ballot(any_changed);      // one atomic per wavefront
+  if ((threadIdx.x & 63) == 0 && (wb | wc) != 0ull) atomicOr(flags, (wb ? KD_FLAG_BAD_CODE : 0u) | (wc ? KD_FLAG_CHANGED : 0u));
+}
+
 int kd_stride(int n_cols) { return (n_cols + 2) & ~1; }     // side + columns, padded to an even number of 8-byte words
 
 static dim3 kd_grid(uint64_t items) { const uint64_t b = (items + kKdBlock - 1) / kKdBlock; return dim3((unsigned)(b < 16384 ? (b ? b : 1) : 16384)); }
@@ -222,6 +300,22 @@ void launch_kd_select(hipStream_t s, const unsigned long long *keys, int n_cols,
 void launch_kd_gather(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, const uint64_t *key_id, uint64_t n, const KdGatherOut &o, uint32_t *flags) {
   if (n == 0) return;
   hipLaunchKernelGGL(k_kd_gather, kd_grid(n), dim3(kKdBlock), 0, s, keys, kd_stride(n_cols) / 2, n_cols, K, key_id, n, o, flags);
+}
+
+void launch_kd_mark(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, int col, uint8_t *used, uint64_t used_len, uint32_t *flags) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_kd_mark, kd_grid(K), dim3(kKdBlock), 0, s, keys, kd_stride(n_cols) / 2, K, col, used, used_len, flags);
+}
+
+void launch_kd_count_used(hipStream_t s, const uint8_t *used, uint64_t used_len, unsigned long long *n_used) {
+  if (used_len == 0) return;
+  const uint64_t b = (used_len / 8 + kKdBlock - 1) / kKdBlock;      // a lane per 8-byte word; at least one workgroup for the bytes at the two ends
+  hipLaunchKernelGGL(k_kd_count_used, dim3((unsigned)(b < kKdCountBlocks ? (b ? b : 1) : kKdCountBlocks)), dim3(kKdBlock), 0, s, used, used_len, n_used);
+}
+
+void launch_kd_recode(hipStream_t s, const unsigned long long *keys, int n_cols, uint64_t K, const KdRecode &q, unsigned long long *keys_new, uint32_t *flags) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_kd_recode, kd_grid(K), dim3(kKdBlock), 0, s, keys, kd_stride(n_cols) / 2, K, q, keys_new, flags);
 }
 
 // one kernel of this translation unit: tad_engine_create resolves it so that the unit's code object is loaded before the first batch

@@ -36,6 +36,9 @@
 // The other direction (tad_strdict_decode: arbitrary codes -> strings in Arrow's layout) reads records and arena only: k_sd_decode_lens,
 // launch_scan, k_sd_decode — the staging of step 1 run backwards, the arena's alignment and padding doing for the reads what they do for
 // the compare.
+// Retiring values (tad_strdict_compact): k_sd_compact_flags, two scans (new codes, new arena offsets), k_sd_compact_recs (remap and the new
+// records), k_sd_compact_copy (the survivors' bytes, packed, in whole 16-byte words) and k_sd_compact_rehash (the old table's slots with
+// their codes passed through remap) fill fresh records, a fresh arena and a fresh table; the host swaps them in last.
 #include "tad_internal.h"
 #include "tad_strbytes.h"
 
@@ -401,6 +404,104 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_decode(const ulonglong2 *__rest
 }
 #endif
 
+// ---- tad_strdict_compact: retired values leave, the survivors are renumbered densely, the arena is packed ----
+// Flags: live[c] = keep[c] != 0 and units[c] = the 16-byte units a survivor takes in the arena (0 for a retired value).  The scan of live
+// gives the new codes, the scan of units the new arena offsets — in 16-byte units, so that a count fits 32 bits, as in step 3 of the encode.
+__global__ __launch_bounds__(kSdBlock) void k_sd_compact_flags(const uint8_t *__restrict__ keep, const ulonglong2 *__restrict__ recs, uint64_t K, uint32_t *__restrict__ live,
+                                                               uint32_t *__restrict__ units) {
+  for (uint64_t c = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; c < K; c += (uint64_t)gridDim.x * kSdBlock) {
+    const bool alive = keep[c] != 0;
+    live[c] = alive ? 1u : 0u;
+    units[c] = alive ? (uint32_t)(((uint64_t)sd_rec_len(recs[c]) + 15) >> 4) : 0u;
+  }
+}
+
+// Records: one lane per OLD value writes remap[c] — the new code, TAD_CODE_NONE for a retired value.  kMove: a survivor also writes its new
+// record (the new offset; length and low hash copied) and, by new code, where its bytes lie in the old arena (src16, in 16-byte units).
+template <bool kMove>
+__global__ __launch_bounds__(kSdBlock) void k_sd_compact_recs(const uint32_t *__restrict__ live, const unsigned long long *__restrict__ newcode,
+                                                              const unsigned long long *__restrict__ off16, const ulonglong2 *__restrict__ recs, uint64_t K,
+                                                              long long *__restrict__ remap, ulonglong2 *__restrict__ nrecs, unsigned long long *__restrict__ src16) {
+  for (uint64_t c = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; c < K; c += (uint64_t)gridDim.x * kSdBlock) {
+    const bool alive = live[c] != 0u;
+    const unsigned long long j = newcode[c];
+    remap[c] = alive ? (long long)j : (long long)TAD_CODE_NONE;
+    if (kMove && alive) {
+      const ulonglong2 r = recs[c];
+      nrecs[j] = ulonglong2{off16[c] * 16ull, r.y};
+      src16[j] = r.x >> 4;
+    }
+  }
+}
+
+// Arena copy.  Source and destination strings are both 16-byte aligned and zero-padded to a multiple of 16, so whole 16-byte words move and
+// no byte is shifted.  A workgroup takes kSdBlock consecutive SURVIVORS: their destination range is contiguous (the new arena is packed), and
+// their first destination words — relative to the tile's — and source words lie in LDS.  The lanes walk the destination's words in order,
+// consecutive lanes on consecutive words; each finds its row by a search in the LDS offsets and loads the word from the old arena: aligned
+// 16-byte stores in whole lines out, a gather in.  A survivor of more than kSdCopyLaneMax words (one workgroup pass) is stepped over by the walk
+// and taken by the wavefronts in turn, 64 lanes on consecutive words, as k_sd_decode treats a tile over its stage.
+static constexpr uint32_t kSdCopyLaneMax = kSdBlock;
+__global__ __launch_bounds__(kSdBlock) void k_sd_compact_copy(const ulonglong2 *__restrict__ nrecs, const unsigned long long *__restrict__ src16, uint64_t m,
+                                                              const uint8_t *__restrict__ arena, uint8_t *__restrict__ narena) {
+  __shared__ unsigned long long s_dst[kSdBlock + 1];      // row r's first destination word; s_dst[rows] = the tile's words
+  __shared__ unsigned long long s_src[kSdBlock];
+  __shared__ uint16_t s_long[kSdBlock];
+  __shared__ uint32_t s_nlong;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  const uint4 *src = reinterpret_cast<const uint4 *>(arena);
+  uint4 *dst = reinterpret_cast<uint4 *>(narena);
+  for (uint64_t base = (uint64_t)blockIdx.x * kSdBlock; base < m; base += (uint64_t)gridDim.x * kSdBlock) {
+    const uint32_t rows = m - base < kSdBlock ? (uint32_t)(m - base) : kSdBlock;
+    const uint64_t tile0 = nrecs[base].x >> 4;            // block-uniform
+    if (tid == 0) s_nlong = 0;
+    __syncthreads();
+    if (tid < rows) {
+      const ulonglong2 r = nrecs[base + tid];
+      const uint64_t at = (r.x >> 4) - tile0, u = ((uint64_t)sd_rec_len(r) + 15) >> 4;
+      s_dst[tid] = at;
+      s_src[tid] = src16[base + tid];
+      if (tid == rows - 1) s_dst[rows] = at + u;
+      if (u > kSdCopyLaneMax) s_long[atomicAdd(&s_nlong, 1u)] = (uint16_t)tid;
+    }
+    __syncthreads();
+    const uint64_t total = s_dst[rows];
+    const uint32_t nlong = s_nlong;
+    for (uint64_t w = tid; w < total; w += kSdBlock) {
+      uint32_t lo = 0, hi = rows;                         // s_dst[lo] <= w < s_dst[hi]: rows of no bytes are passed over
+      while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (s_dst[mid] <= w) lo = mid; else hi = mid;
+      }
+      const uint64_t first = s_dst[lo], end = s_dst[lo + 1];
+      if (nlong != 0u && end - first > kSdCopyLaneMax) {      // a long row: on to this lane's first word behind it, without a search per word
+        w += (end - w - 1) / kSdBlock * kSdBlock;
+        continue;
+      }
+      dst[tile0 + w] = src[s_src[lo] + (w - first)];
+    }
+    for (uint32_t i = wave; i < nlong; i += kSdBlock / 64) {
+      const uint32_t t = s_long[i];
+      const uint64_t first = s_dst[t], n = s_dst[t + 1] - first, from = s_src[t];
+      for (uint64_t k = lane; k < n; k += 64) dst[tile0 + first + k] = src[from + k];
+    }
+    __syncthreads();                                      // (the next round rewrites the offsets and the list)
+  }
+}
+
+// Table: k_sd_rehash on the OLD table's claimed slots with the codes passed through remap.  The slot gives the high half of the hash and
+// the old code, the old record the low half; a survivor claims fingerprint << 32 | remap[code] in the fresh table.  No string is read.
+__global__ __launch_bounds__(kSdBlock) void k_sd_compact_rehash(const unsigned long long *__restrict__ old_table, uint64_t old_slots, const ulonglong2 *__restrict__ recs,
+                                                                uint64_t K, const long long *__restrict__ remap, unsigned long long *__restrict__ table, uint64_t mask) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; i < old_slots; i += (uint64_t)gridDim.x * kSdBlock) {
+    const unsigned long long w = old_table[i];
+    const uint64_t c = w & 0xffffffffull;
+    if (w == kSlotEmpty || c >= K) continue;
+    const long long j = remap[c];
+    if (j < 0) continue;
+    slot_claim(table, mask, ((w >> 32) << 32) | sd_rec_hash_lo(recs[c]), ((w >> 32) << 32) | (unsigned long long)j);
+  }
+}
+
 static dim3 sd_grid(uint64_t items) { const uint64_t b = (items + kSdBlock - 1) / kSdBlock; return dim3((unsigned)(b < 16384 ? (b ? b : 1) : 16384)); }
 
 void launch_sd_probe(hipStream_t s, const StrBatch &B, const unsigned long long *table, uint64_t slots, const void *recs, const uint8_t *arena, uint64_t K,
@@ -451,6 +552,29 @@ void launch_sd_decode(hipStream_t s, const void *recs, const uint8_t *arena, con
   const uint64_t tiles = (n + kSdDecodeRows - 1) / kSdDecodeRows;      // past kSdDecodeMaxBlocks workgroups the tiles are taken in a grid stride
   hipLaunchKernelGGL(k_sd_decode, dim3((unsigned)(tiles < kSdDecodeMaxBlocks ? (tiles ? tiles : 1) : kSdDecodeMaxBlocks)), dim3(kSdBlock), 0, s,
                      static_cast<const ulonglong2 *>(recs), arena, codes, n, off, out);
+}
+
+void launch_sd_compact_flags(hipStream_t s, const uint8_t *keep, const void *recs, uint64_t K, uint32_t *live, uint32_t *units) {
+  hipLaunchKernelGGL(k_sd_compact_flags, sd_grid(K), dim3(kSdBlock), 0, s, keep, static_cast<const ulonglong2 *>(recs), K, live, units);
+}
+
+void launch_sd_compact_recs(hipStream_t s, const uint32_t *live, const unsigned long long *newcode, const unsigned long long *off16, const void *recs, uint64_t K,
+                            long long *remap, void *nrecs, unsigned long long *src16) {
+  const ulonglong2 *r = static_cast<const ulonglong2 *>(recs);
+  if (nrecs != nullptr) hipLaunchKernelGGL(k_sd_compact_recs<true>, sd_grid(K), dim3(kSdBlock), 0, s, live, newcode, off16, r, K, remap, static_cast<ulonglong2 *>(nrecs), src16);
+  else hipLaunchKernelGGL(k_sd_compact_recs<false>, sd_grid(K), dim3(kSdBlock), 0, s, live, newcode, off16, r, K, remap, static_cast<ulonglong2 *>(nullptr), src16);
+}
+
+void launch_sd_compact_copy(hipStream_t s, const void *nrecs, const unsigned long long *src16, uint64_t m, const uint8_t *arena, uint8_t *narena) {
+  if (m == 0) return;
+  const uint64_t tiles = (m + kSdBlock - 1) / kSdBlock;      // past kSdDecodeMaxBlocks workgroups the tiles are taken in a grid stride
+  hipLaunchKernelGGL(k_sd_compact_copy, dim3((unsigned)(tiles < kSdDecodeMaxBlocks ? tiles : kSdDecodeMaxBlocks)), dim3(kSdBlock), 0, s,
+                     static_cast<const ulonglong2 *>(nrecs), src16, m, arena, narena);
+}
+
+void launch_sd_compact_rehash(hipStream_t s, const unsigned long long *old_table, uint64_t old_slots, const void *recs, uint64_t K, const long long *remap,
+                              unsigned long long *table, uint64_t slots) {
+  hipLaunchKernelGGL(k_sd_compact_rehash, sd_grid(old_slots), dim3(kSdBlock), 0, s, old_table, old_slots, static_cast<const ulonglong2 *>(recs), K, remap, table, slots - 1);
 }
 
 // one kernel of this translation unit: tad_engine_create resolves it so that the unit's code object is loaded before the first batch

@@ -760,6 +760,69 @@ class KeyDict:
         eng._check(rc)
         return int(n.value)
 
+    def used_codes(self, col, n_values, into=None, out="device"):
+        """Which codes of key column col the keys still hold (tad_keydict_mark_codes): used[c] = 1 iff some key, on either side, holds
+        value c in that column.  n_values: the entries of the mask — the num_values() of the column's StringDict; a key whose value
+        is not below it is refused.  into: a mask of an earlier call (a numpy uint8 array, or a DeviceArray of n_values bytes) to OR
+        into, for columns that share one vocabulary; None = a fresh mask.  Returns (used, n_used): used a DeviceArray of n_values
+        bytes (out="device": what StringDict.compact takes without a copy) or a numpy uint8 array (out="host"); with `into`, the memory
+        `into` lives in.  The dictionary is only read."""
+        eng = self._engine
+        _need_feature(eng._lib, "STRING_RETIRE", "tad_keydict_mark_codes")
+        if out not in ("device", "host"):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "KeyDict.used_codes: out must be device or host")
+        K = int(n_values)
+        if into is None:
+            dev = out == "device"
+            used, ptr = _out_mask(eng, dev, K)
+        elif isinstance(into, DeviceArray):
+            dev, used, ptr = True, into, (into.ptr if K else None)
+            if into.n * np.dtype(into.dtype).itemsize < K:
+                raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "KeyDict.used_codes: into holds fewer than %d bytes" % K)
+        else:
+            dev = False
+            used = np.ascontiguousarray(into, dtype=np.uint8).reshape(-1)
+            if used.size != K:
+                raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "KeyDict.used_codes: into holds %d entries, not %d" % (used.size, K))
+            ptr = used.ctypes.data if K else None
+        n = capi.u64()
+        rc = eng._lib.tad_keydict_mark_codes(eng._h, self._h, int(col), 0 if into is None else 1, ptr, K,
+                                             capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST, C.byref(n))
+        eng._check(rc)
+        if dev and into is None:
+            used = used.view(0, K, np.uint8)
+        return used, int(n.value)
+
+    def recode(self, remaps):
+        """Rewrite key columns through code remaps (tad_keydict_recode): remaps = {col: remap}; every key's value v in column col
+        becomes remap[v] — what StringDict.compact returned for the column's vocabulary.  The remaps are numpy int64 arrays, or all
+        DeviceArrays.  Key ids, sides and the other columns stay.  Refused with the dictionary unchanged: a value outside its remap,
+        a value mapped to TAD_CODE_NONE (a key still uses a retired string), two keys whose recoded tuples are equal.  Returns the
+        keys held."""
+        eng = self._engine
+        _need_feature(eng._lib, "STRING_RETIRE", "tad_keydict_recode")
+        items = list(remaps.items()) if hasattr(remaps, "items") else list(remaps)
+        dev = bool(items) and all(isinstance(r, DeviceArray) for _, r in items)
+        if not dev and any(isinstance(r, DeviceArray) for _, r in items):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "KeyDict.recode: the remaps are all numpy arrays or all DeviceArrays")
+        keepalive, ptrs, lens = [], [], []
+        for _, r in items:
+            if dev:
+                ptrs.append(r.ptr if r.n else None)
+                lens.append(r.n)
+            else:
+                a = np.ascontiguousarray(r, dtype=np.int64).reshape(-1)
+                keepalive.append(a)
+                ptrs.append(a.ctypes.data if a.size else None)
+                lens.append(a.size)
+        nt = len(items)
+        n = capi.u64()
+        rc = eng._lib.tad_keydict_recode(eng._h, self._h, nt, (capi.i32 * max(nt, 1))(*[int(c) for c, _ in items]), (C.c_void_p * max(nt, 1))(*ptrs),
+                                         (capi.u64 * max(nt, 1))(*lens), capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST, C.byref(n))
+        del keepalive
+        eng._check(rc)
+        return int(n.value)
+
     def export(self, first_key=0, n_keys=None):
         """(cols: list of n_cols int64 arrays, side uint8 array) of the keys [first_key, first_key + n_keys) (tad_keydict_export);
         n_keys None = up to the last key"""
@@ -903,6 +966,32 @@ class StringDict:
         n = capi.u64()
         self._engine._check(self._engine._lib.tad_strdict_bytes(self._engine._h, self._h, C.byref(n)))
         return int(n.value)
+
+    def compact(self, keep, out="host"):
+        """Drop values and renumber the survivors densely, order kept (tad_strdict_compact): value c survives iff keep[c] != 0.  keep: a
+        numpy array, or a DeviceArray of num_values() bytes (what KeyDict.used_codes returns).  Returns (remap, stats): remap[c] = the
+        new code of old value c or TAD_CODE_NONE (-1) — a numpy int64 array, or a DeviceArray with out="device" (what KeyDict.recode
+        takes without a copy) — and the fields of tad_strdict_compact_stats as a dict.  Afterwards the dictionary is what a fresh one
+        holds after load() of the survivors; any failure leaves it as it was."""
+        eng = self._engine
+        _need_feature(eng._lib, "STRING_RETIRE", "tad_strdict_compact")
+        if out not in ("host", "device"):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "StringDict.compact: out must be host or device")
+        if isinstance(keep, DeviceArray):
+            K = keep.n * np.dtype(keep.dtype).itemsize
+            kptr, kmem = (keep.ptr if K else None), capi.TAD_MEM_DEVICE
+        else:
+            keep = np.asarray(keep)
+            if keep.dtype != np.uint8:                 # survives iff keep[c] != 0, whatever the type: 256 and 0.5 keep their value
+                keep = keep != 0
+            keep = np.ascontiguousarray(keep.astype(np.uint8, copy=False)).reshape(-1)
+            K = keep.size
+            kptr, kmem = (keep.ctypes.data if K else None), capi.TAD_MEM_HOST
+        remap, rptr = _out_array(eng, out == "device", K, np.int64, room=max(K, 1))
+        cs = capi.StrdictCompactStats()
+        rc = eng._lib.tad_strdict_compact(eng._h, self._h, kptr, K, kmem, rptr, capi.TAD_MEM_DEVICE if out == "device" else capi.TAD_MEM_HOST, C.byref(cs))
+        eng._check(rc)
+        return remap, {name: getattr(cs, name) for name, _ in capi.StrdictCompactStats._fields_ if not name.startswith("reserved")}
 
     def export(self, first=0, n=None):
         """(offsets int64[n + 1], data uint8[...]) of the values [first, first + n) in Arrow's layout (tad_strdict_export); n None = up

@@ -6,7 +6,8 @@ keeps on the device: a key dictionary (KeyDict: the mode's key tuples -> stable 
 fed through TadEngine.merge_stream) and one string dictionary per string key column (StringDict: strings -> stable codes, in HBM as
 well).  Nothing grows on the host: a job's result rows name key ids, and those ids alone are decoded — KeyDict.gather gives their code
 tuples, StringDict.decode the codes' strings (_KeyColumn) — so `snapshot()` / `restore()` of the three device structures is all a restart
-needs.
+needs.  `retire(idle_before)` keeps all three bounded: it drops the idle keys from the state and the key dictionary and the strings no
+surviving key uses from the string dictionaries, on the device, so an instance can run indefinitely.
 
 The job's name filters (--pod-name, --pod-namespace, --pod-label, --external-ip, --svc-port-name) are predicates on KEY columns of the
 mode, so a job is a key selection: the filter is evaluated once per distinct string of the vocabulary, on the device (StringDict.match:
@@ -19,6 +20,7 @@ import numpy as np
 
 from . import _capi
 from . import anomaly_detection as _ad
+from .engine import TadError
 
 MODES = ("svc", "external", "pod")
 
@@ -62,6 +64,14 @@ def _strings_of(offsets, data):
         vals[:] = [raw[a:b].decode("utf-8") for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist())]
         return vals
     return pa.Array.from_buffers(pa.large_string(), n, [None, pa.py_buffer(offsets), pa.py_buffer(data)]).to_numpy(zero_copy_only=False)
+
+
+def _release(x):
+    """free a DeviceArray now — for a view, the array it is a slice of"""
+    base = x._base
+    x.free()
+    if base is not None:
+        base.free()
 
 
 class _KeyDecoder:
@@ -142,6 +152,7 @@ class StreamingAnomalyDetection:
         self._vocab = [self._engine.string_dict() for _ in range(2 if agg_flow == "pod" else 1)]     # pod: namespaces, labels / names
         self._dict = self._engine.key_dict(len(self._vocab))
         self._state = None
+        self._broken = None      # why the instance can no longer be used (retire)
 
     @property
     def state(self):
@@ -154,6 +165,7 @@ class StreamingAnomalyDetection:
     def feed(self, flows):
         """One batch of flow rows (a column dict as anomaly_detection takes it), in any order; rows of a (key, flowEndSeconds) group may
         be split over feeds.  Returns the merge's statistics (TadEngine.merge_stream), or None when no row passed the row predicates."""
+        self._usable()
         eng = self._engine
         n = len(flows["flowEndSeconds"])
         keep = np.ones(n, dtype=bool)
@@ -222,6 +234,7 @@ class StreamingAnomalyDetection:
         flowEndSeconds in svc and external mode; the pod query has no time filter."""
         if algo_type not in _ad.VALID_ALGOS:
             raise ValueError("Algorithm should be in {}".format(" or ".join(_ad.VALID_ALGOS)))
+        self._usable()
         terms = self._terms(pod_label or "", pod_name or "", pod_namespace or "", external_ip or "", svc_port_name or "")
         decoder = _KeyDecoder(self._dict, self._vocab)      # the key table: decoded on demand, for the keys with result rows
         table = {name: _KeyColumn(decoder, "direction" if name == "direction" else i) for i, name in enumerate(_ad.KEY_COLUMNS[self.mode])}
@@ -237,6 +250,7 @@ class StreamingAnomalyDetection:
         """Everything the instance holds, as a dict of numpy arrays (np.savez takes it as it is): the state's exports (moments, history,
         series, times), the key dictionary's tuples and sides, and every string dictionary's values in Arrow's layout.  `restore` builds
         an instance from it that continues as this one would."""
+        self._usable()
         snap = {"mode": np.asarray([self.mode]), "num_keys": np.asarray([self.num_keys], dtype=np.uint64)}
         cols, side = self._dict.export()
         for c, col in enumerate(cols):
@@ -274,6 +288,76 @@ class StreamingAnomalyDetection:
             self.close()
             raise
         return self
+
+    def _usable(self):
+        if self._broken:
+            raise RuntimeError("this instance is inconsistent (%s): restore one from a snapshot taken before the retire" % self._broken)
+
+    def device_bytes(self):
+        """the device bytes of everything the instance holds: the state, the key dictionary and every string dictionary"""
+        return (self._state.nbytes() if self._state is not None else 0) + self._dict.nbytes() + sum(v.nbytes() for v in self._vocab)
+
+    def retire(self, idle_before=0):
+        """Shed what is dead, on the device: the keys whose newest flowEndSeconds lies before idle_before (0 = no time rule; a key
+        without points always goes), and every string no surviving key uses.  The chain: TadState.compact -> KeyDict.compact with its
+        remap; per vocabulary KeyDict.used_codes; then per vocabulary StringDict.compact with that mask; then ONE KeyDict.recode with
+        every column's remap.  Masks and remaps stay on the device.  Jobs and feeds afterwards give what an instance gives that was
+        fed only the rows of the surviving keys; a retired name that returns is a new string and a new key.
+
+        Failure.  Each call of the chain is atomic; two PAIRS of calls are not, and a failure between the two halves of a pair leaves
+        an instance that is NOT consistent.  (1) The state is compacted first and the key dictionary takes its remap second: if
+        KeyDict.compact fails after a state compaction that retired keys, the state holds renumbered keys and the dictionary still
+        hands out the ids of before.  (2) The vocabularies are compacted before the keys are recoded: if the recode fails (it
+        allocates fresh records and a fresh table), or a StringDict.compact fails after an earlier vocabulary was compacted, the keys
+        hold codes of before, and a compacted vocabulary cannot be brought back.  In both cases the call raises, and the instance
+        refuses every later feed, job, snapshot and retire with a RuntimeError: it must be replaced by `restore` of a snapshot
+        taken before the call.  Every other failure raises with the instance consistent and usable — the state's own compaction,
+        a mask (every mask is computed before the first vocabulary is compacted), a StringDict.compact before any vocabulary moved:
+        the keys are then retired or not, the strings not yet, and the next retire finishes the work.  The masks and remaps of the
+        call are released on every path.
+
+        Returns a dict: keys_before / keys_after, values_before / values_after (a list, one entry per vocabulary), bytes_before /
+        bytes_after (device_bytes())."""
+        self._usable()
+        lib = self._engine._lib
+        if not (getattr(lib, "tad_features", None) and lib.tad_features() & _capi.TAD_FEATURE_STRING_RETIRE):
+            raise TadError(_capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_strdict_compact (TAD_FEATURE_STRING_RETIRE)")
+        out = {"keys_before": self.num_keys, "values_before": [v.num_values() for v in self._vocab], "bytes_before": self.device_bytes()}
+        if self._state is not None:
+            if self.num_keys > self._state.num_keys:      # (a remap has one entry per key of the dictionary)
+                self._state.resize(self.num_keys)
+            remap, cs = self._state.compact(int(idle_before), out="device")
+            try:
+                if cs["keys_after"] != cs["keys_before"]:
+                    self._dict.compact(remap)
+            except Exception as exc:                      # the state is renumbered, the dictionary is not
+                self._broken = "retire failed between the state and the key dictionary: %s" % exc
+                raise
+            finally:
+                _release(remap)
+            if cs["keys_after"] == 0:                     # nothing is left: as before the first feed
+                self._state.close()
+                self._state = None
+        held, compacted = [], False                       # the call's device masks and remaps
+        try:
+            masks, remaps = [], {}
+            for i, v in enumerate(self._vocab):
+                masks.append(self._dict.used_codes(i, v.num_values(), out="device")[0])
+                held.append(masks[i])
+            for i, v in enumerate(self._vocab):
+                remaps[i], st = v.compact(masks[i], out="device")
+                held.append(remaps[i])
+                compacted = compacted or st["values_after"] != st["values_before"]
+            self._dict.recode(remaps)
+        except Exception as exc:
+            if compacted:
+                self._broken = "retire failed between the vocabularies and the keys: %s" % exc
+            raise
+        finally:
+            for x in held:
+                _release(x)
+        out.update(keys_after=self.num_keys, values_after=[v.num_values() for v in self._vocab], bytes_after=self.device_bytes())
+        return out
 
     def close(self):
         if self._state is not None:

@@ -2093,6 +2093,49 @@ func (d *StringDict) Match(op int32, pattern []byte) (mask []byte, matched uint6
 	return mask, uint64(hit), nil
 }
 
+var stringLikeOnce sync.Once
+var stringLikeOK bool
+
+// hasStringLike: the library matches LIKE patterns on the device (tad_features); an older one would not export the call.  Like the rest
+// of this binding the method below is never compiled in the project's checks (no Go toolchain runs there): it is written against
+// include/tad.h and read by tests/test_string_like_abi.py as text.
+func hasStringLike() bool {
+	stringLikeOnce.Do(func() { stringLikeOK = C.tad_features()&C.TAD_FEATURE_STRING_LIKE != 0 })
+	return stringLikeOK
+}
+
+var errNoStringLike = errors.New("tadengine: libtad_mi355x.so matches no LIKE patterns (TAD_FEATURE_STRING_LIKE)")
+
+// Like evaluates a LIKE pattern on every value (tad_strdict_like): mask[c] = 1 iff the pattern (at most 1024 bytes) matches the WHOLE of
+// value c.  % matches any run of bytes, _ exactly one character, \ makes the next byte a literal; nocase folds 'A'..'Z' to 'a'..'z'
+// (ilike).  The job's label filter is Like([]byte("%"+label+"%"), true).  The mask is a term of KeyDict.Select.
+func (d *StringDict) Like(pattern []byte, nocase bool) (mask []byte, matched uint64, err error) {
+	if !hasStringLike() {
+		return nil, 0, errNoStringLike
+	}
+	n, err := d.NumValues()
+	if err != nil {
+		return nil, 0, err
+	}
+	mask = make([]byte, n)
+	var mp, pp *C.uint8_t
+	if n > 0 {
+		mp = (*C.uint8_t)(unsafe.Pointer(&mask[0]))
+	}
+	if len(pattern) > 0 {
+		pp = (*C.uint8_t)(unsafe.Pointer(&pattern[0]))
+	}
+	var flags C.uint32_t
+	if nocase {
+		flags = C.TAD_LIKE_NOCASE
+	}
+	var hit C.uint64_t
+	if rc := C.tad_strdict_like(d.e.h, d.h, pp, C.uint64_t(len(pattern)), flags, mp, C.uint64_t(n), C.TAD_MEM_HOST, &hit); rc != C.TAD_OK {
+		return nil, 0, d.fail("tad_strdict_like", rc)
+	}
+	return mask, uint64(hit), nil
+}
+
 var dictDecodeOnce sync.Once
 var dictDecodeOK bool
 

@@ -961,11 +961,12 @@ int tad_drop_state_keys(tad_engine *e, tad_state *s, const tad_job *job, int64_t
  * stale length is refused, never a short write.  `memory` says where mask lives; the pattern is host memory, pattern_len <= 1024;
  * *n_matched may be NULL.  TAD_STR_EQUAL: the value's bytes are the pattern's bytes (an empty pattern selects "" alone).
  * TAD_STR_CONTAINS_NOCASE: the pattern occurs in the value (an empty pattern selects everything), compared after folding 'A'..'Z' to
- * 'a'..'z' and nothing else: a byte >= 0x80 matches only itself, so no Unicode case folding and no % / _ wildcards.  That is enough
- * for the job's filters: Kubernetes restricts namespaces, pod names, label keys and values and service port names to ASCII, and
- * `ilike '%label%'` with a pattern free of %, _ and \ is exactly this operation on ASCII strings; equality (--pod-name,
- * --pod-namespace, --external-ip, --svc-port-name) is TAD_STR_EQUAL.  The mask is ready for tad_keydict_select (masks[t]) and
- * tad_mask_rows in device memory: no string is hashed, compared or matched on the host between the Arrow buffer and the state.
+ * 'a'..'z' and nothing else: a byte >= 0x80 matches only itself, so no Unicode case folding and no % / _ wildcards (those are
+ * tad_strdict_like's, further below).  That is enough for the job's filters: Kubernetes restricts namespaces, pod names, label keys
+ * and values and service port names to ASCII, and `ilike '%label%'` with a pattern free of %, _ and \ is exactly this operation on
+ * ASCII strings; equality (--pod-name, --pod-namespace, --external-ip, --svc-port-name) is TAD_STR_EQUAL.  The mask is ready for
+ * tad_keydict_select (masks[t]) and tad_mask_rows in device memory: no string is hashed, compared or matched on the host between the
+ * Arrow buffer and the state.
  * tad_strdict_bytes: the device bytes held — table, records and arena at their capacity.  tad_strdict_num_values: the values held.
  * Every call on a NULL engine is TAD_ERR_INVALID_ARGUMENT without a device and writes nothing; tad_strdict_destroy(NULL, NULL) is a no-op.
  * Cost.  A batch of known strings: one launch (the probe pass) and one host synchronisation; it reads the offsets (4 or 8 B a row) and the
@@ -1099,6 +1100,39 @@ int tad_strdict_compact(tad_engine *e, tad_strdict *d, const uint8_t *keep, uint
                         tad_mem remap_memory, tad_strdict_compact_stats *stats /* may be NULL */);
 int tad_keydict_recode(tad_engine *e, tad_keydict *d, int32_t n_terms, const int32_t *term_col, const int64_t *const *remaps,
                        const uint64_t *remap_len, tad_mem memory, uint64_t *num_keys /* may be NULL */);
+
+/* ---- LIKE patterns with % and _ on a string dictionary (TAD_FEATURE_STRING_LIKE; check tad_features() before calling this) ----
+ * The job's label filter is ilike(labels, '%label%') with the user's text in the middle, and the reference's own example label,
+ * "test_key":"test_value", holds a wildcard: _ is legal in Kubernetes label keys and values and matches any one character in a LIKE
+ * pattern.  The match call above knows no wildcard, so such a job exported every label string to the host and ran a regex over them.
+ * tad_strdict_like evaluates the whole pattern language on the device instead, one lane per value.
+ * The language (theia_amd/csrc/tad_like.h holds it, compile step and matcher, for host and device): \ followed by a byte makes that byte
+ * a literal, and \ as the last byte is a literal backslash; % matches any run of bytes, the empty run included, and %% is %; _ matches
+ * exactly one character; every other byte is a literal.  The pattern matches the WHOLE value — it is anchored at both ends, so a
+ * substring search is '%text%' — and % and _ also match a newline.  An empty pattern selects "" alone.  With TAD_LIKE_NOCASE the
+ * literals (escaped ones included) and the value's bytes are compared after folding 'A'..'Z' to 'a'..'z' and nothing else.  One
+ * character is the byte at the position, whatever it is, and every byte 0x80..0xBF that follows it: one code point on well-formed UTF-8.
+ * The place a % retries from advances by the same step.  This is what the batch job's regex (anomaly_detection.py: _like_regex) decides,
+ * with the two differences of the case-folded substring operation: no Unicode case folding, and Python's re.IGNORECASE lets k, s and i
+ * match U+212A, U+017F, U+0130 and U+0131, which no byte fold does.
+ * The call, read-only: mask[c] = 1 iff the pattern matches value c, else 0.  mask_len must equal num_values — a stale length is refused
+ * and the mask left untouched, never a short write.  `memory` says where mask lives; the pattern is host memory, pattern_len <= 1024;
+ * *n_matched may be NULL.  A flag bit other than TAD_LIKE_NOCASE is refused.  An empty dictionary is TAD_OK.  A NULL engine is
+ * TAD_ERR_INVALID_ARGUMENT without a device and writes nothing.  The mask is ready for the key selection and the row mask calls in device
+ * memory, as the match call's is.
+ * How: the host compiles the pattern into at most 1024 two-byte tokens and the least value length a match needs; the kernel holds the
+ * tokens in LDS, answers a shorter value from its record, and reads a value's bytes as aligned 16-byte words of the arena, the word under
+ * the cursor held in registers.  The matcher is iterative and keeps ONE backtrack point, the last % met.  Cost: one launch and one
+ * synchronisation; per value one 16-byte record and its bytes once per pass — worst case value length x pattern length steps per value
+ * ('%a%a%a%b' on a long run of a), against value length for a pattern whose literals rarely begin to match.  A wildcard-free
+ * substring search is cheaper through TAD_STR_CONTAINS_NOCASE, which compares eight bytes a step.  Job-context workspace, grow-only and
+ * bounded by workspace_limit: the staged program (2 KiB) and, for a host mask, num_values bytes.  The ABI stays 13 and no struct grows.
+ * Lock order: the dictionary, then a job context; calls on one dictionary are serial.  Measured once (DESIGN.md §5,
+ * tools/strdict_like_bench.py): 1e7 label sets of 87 bytes on average in 2.8 - 3.3 ms, 3.0 times the substring search on the same literal. */
+#define TAD_FEATURE_STRING_LIKE 32768u /* tad_strdict_like: LIKE / ilike patterns with % and _ matched on the device */
+#define TAD_LIKE_NOCASE 1u             /* flags: compare after folding 'A'..'Z' to 'a'..'z' (ilike) */
+int tad_strdict_like(tad_engine *e, const tad_strdict *d, const uint8_t *pattern, uint64_t pattern_len, uint32_t flags,
+                     uint8_t *mask, uint64_t mask_len, tad_mem memory, uint64_t *n_matched /* may be NULL */);
 
 /* Stage counter for Status.CompletedStages / TotalStages (controller.go:426-453); callable while
  * tad_run executes on another thread.  tad_progress: the sum over the jobs in flight (with none: the job that finished last).

@@ -36,6 +36,8 @@ TAD_FEATURE_KEY_SELECT = 2048                # tad_features() bit: tad_keydict_s
 TAD_FEATURE_STRING_DICT = 4096               # tad_features() bit: tad_strdict, a persistent string -> code dictionary on the device, with match masks
 TAD_FEATURE_DICT_DECODE = 8192               # tad_features() bit: tad_keydict_gather, tad_strdict_decode: ids -> tuples and codes -> strings on the device
 TAD_FEATURE_STRING_RETIRE = 16384            # tad_features() bit: tad_keydict_mark_codes, tad_strdict_compact, tad_keydict_recode: dead strings dropped, codes renumbered
+TAD_FEATURE_STRING_LIKE = 32768              # tad_features() bit: tad_strdict_like: LIKE / ilike patterns with % and _ matched on the device
+TAD_LIKE_NOCASE = 1                          # tad_strdict_like flags: compare after folding 'A'..'Z' to 'a'..'z' (ilike)
 TAD_CODE_NONE = -1                           # tad_strdict_lookup: the string is not in the dictionary
 TAD_STR_EQUAL, TAD_STR_CONTAINS_NOCASE = 0, 1   # tad_strdict_match: the value is the pattern / the pattern occurs in it, ASCII letters without case
 
@@ -210,6 +212,7 @@ SYMBOLS = {
     "tad_strdict_export": (C.c_int, [C.c_void_p, C.c_void_p, u64, u64, C.c_void_p, C.c_void_p, u64, C.POINTER(u64)]),
     "tad_strdict_import": (C.c_int, [C.c_void_p, C.c_void_p, u64, C.c_void_p, C.c_void_p]),
     "tad_strdict_match": (C.c_int, [C.c_void_p, C.c_void_p, i32, C.c_void_p, u64, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
+    "tad_strdict_like": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_uint32, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
     "tad_keydict_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "tad_strdict_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64, C.c_int, C.c_void_p, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
     "tad_keydict_mark_codes": (C.c_int, [C.c_void_p, C.c_void_p, i32, i32, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),

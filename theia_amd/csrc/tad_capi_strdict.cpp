@@ -378,6 +378,52 @@ int tad_strdict_match(tad_engine *eng, const tad_strdict *d, int32_t op, const u
   return TAD_OK;
 }
 
+// tad.h: a value mask from a LIKE pattern with % and _ (tad_like.h: the pattern is compiled here, on the host; kernel: k_sd_like).  The
+// dictionary is only read.
+int tad_strdict_like(tad_engine *eng, const tad_strdict *d, const uint8_t *pattern, uint64_t pattern_len, uint32_t flags, uint8_t *mask, uint64_t mask_len,
+                     tad_mem memory, uint64_t *n_matched) {
+  const char *who = "tad_strdict_like";
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!d || (flags & ~TAD_LIKE_NOCASE) != 0u || pattern_len > kSdMaxPattern || (pattern_len && !pattern) || (mask_len && !mask) ||
+      (memory != TAD_MEM_HOST && memory != TAD_MEM_DEVICE))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bad arguments (dictionary, flags TAD_LIKE_NOCASE or 0, a pattern of at most %u bytes, mask in host or device memory)", who,
+                kSdMaxPattern);
+  std::lock_guard<std::mutex> dict_lk(d->mu);
+  const uint64_t K = d->K;
+  if (mask_len != K)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: mask has %llu entries, the dictionary holds %llu values", who, (unsigned long long)mask_len, (unsigned long long)K);
+  if (n_matched) *n_matched = 0;
+  if (K == 0) return TAD_OK;
+  Lease lease(eng);
+  JobCtx *e = lease.c;
+  if (!e) return fail(eng, TAD_ERR_OUT_OF_MEMORY, "%s: no job context available", who);
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipStream_t s = e->stream;
+  const bool host = memory == TAD_MEM_HOST;
+  // scratch: sp_comp_a = the match count | the token program; a host mask in in_key2
+  const size_t prog_bytes = up256(kLikeMaxTokens * sizeof(uint16_t));
+  const size_t need = 256 + prog_bytes + (host ? up256(K) : 0);
+  if (need > e->ws_limit) return over_limit(e, who, need);
+  int rc;
+  if ((rc = ensure(e, e->sp_comp_a, 256 + prog_bytes)) != TAD_OK || (host && (rc = ensure(e, e->in_key2, up256(K))) != TAD_OK)) return rc;
+  unsigned long long *n_hit_dev = static_cast<unsigned long long *>(e->sp_comp_a.p);
+  uint16_t *prog_dev = reinterpret_cast<uint16_t *>(static_cast<uint8_t *>(e->sp_comp_a.p) + 256);
+  uint16_t prog[kLikeMaxTokens];
+  uint32_t min_len = 0;
+  const uint32_t n_tok = like_compile(pattern, (uint32_t)pattern_len, flags, prog, &min_len);
+  HIP_TRY(e, hipMemsetAsync(n_hit_dev, 0, 8, s));
+  if (n_tok) HIP_TRY(e, hipMemcpyAsync(prog_dev, prog, n_tok * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+  uint8_t *d_mask = host ? static_cast<uint8_t *>(e->in_key2.p) : mask;
+  launch_sd_like(s, d->recs, d->arena, K, prog_dev, n_tok, min_len, (flags & TAD_LIKE_NOCASE) != 0u, d_mask, n_hit_dev);
+  unsigned long long n_hit = 0;
+  HIP_TRY(e, hipMemcpyAsync(&n_hit, n_hit_dev, 8, hipMemcpyDeviceToHost, s));
+  if (host) HIP_TRY(e, hipMemcpyAsync(mask, d_mask, K, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  if (n_matched) *n_matched = n_hit;
+  return TAD_OK;
+}
+
 // tad.h: codes -> strings in Arrow's layout (kernels: k_sd_decode_lens, the scan, k_sd_decode).  The dictionary is only read.
 int tad_strdict_decode(tad_engine *eng, const tad_strdict *d, const int64_t *codes, uint64_t n, tad_mem codes_memory, int64_t *offsets, uint8_t *data,
                        uint64_t data_cap, tad_mem out_memory, uint64_t *data_bytes) {

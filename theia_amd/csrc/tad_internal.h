@@ -10,11 +10,13 @@
 #include "tad.h"
 #include "tad_carve.h"     // the workspace blocks: their pointer structs (OutRows, StreamState, ArimaSlots, ...) and layouts
 #include "tad_dev_err.h"   // DEV_ERR_*: what a kernel raises in DevCounters::err
+#include "tad_like.h"      // the LIKE pattern language: like_compile (host) and like_match (host and k_sd_like)
 #include "tad_rows.h"      // a row of the caller's table and its judges: Lattice, RowFilter, RowCols, the column widths
 
 namespace tad {
 
 static_assert(kKeySkip == TAD_KEY_SKIP, "tad_rows.h restates tad.h's skip key");
+static_assert(kLikeNocase == TAD_LIKE_NOCASE, "tad_like.h restates tad.h's flag");
 
 // The aggregated point grid, TIME-MAJOR: cell(bucket b, key k) = b * K + k.
 // Time-major so that "one lane = one key, walk the series sequentially" is a fully coalesced
@@ -731,6 +733,13 @@ void launch_sd_rehash(hipStream_t s, const unsigned long long *old_table, uint64
 // out[c] = 1 iff value c satisfies op (TAD_STR_*) with the pattern (device memory, folded for TAD_STR_CONTAINS_NOCASE), else 0; *n_hit += the matches
 void launch_sd_match(hipStream_t s, const void *recs, const uint8_t *arena, uint64_t K, int op, const uint8_t *pattern, uint32_t pattern_len, uint8_t *out,
                      unsigned long long *n_hit);
+// tad_strdict_like: out[c] = 1 iff the token program prog[n_tok] (device memory; tad_like.h: like_compile) matches the whole of value c, else
+// 0; *n_hit += the matches.  A value of fewer than min_len bytes is answered from its record alone.  At most kSdLikeMaxBlocks workgroups:
+// past kSdLikeMaxBlocks * 256 values the lanes take them in a grid stride
+static constexpr uint32_t kSdLikeMaxBlocks = 2048;
+static_assert(kLikeMaxTokens == kSdMaxPattern, "a pattern of the longest length compiles to a program that fits");
+void launch_sd_like(hipStream_t s, const void *recs, const uint8_t *arena, uint64_t K, const uint16_t *prog, uint32_t n_tok, uint32_t min_len, bool nocase,
+                    uint8_t *out, unsigned long long *n_hit);
 // cnt[i] = the length of value first + i; the values' bytes packed at out + off[i] (out 8-byte aligned)
 void launch_sd_export_lens(hipStream_t s, const void *recs, uint64_t first, uint64_t n, uint32_t *cnt);
 void launch_sd_export(hipStream_t s, const void *recs, const uint8_t *arena, uint64_t first, uint64_t n, const unsigned long long *off, uint8_t *out);

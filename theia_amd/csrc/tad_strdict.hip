@@ -36,6 +36,8 @@
 // The other direction (tad_strdict_decode: arbitrary codes -> strings in Arrow's layout) reads records and arena only: k_sd_decode_lens,
 // launch_scan, k_sd_decode — the staging of step 1 run backwards, the arena's alignment and padding doing for the reads what they do for
 // the compare.
+// Value masks read records and arena as well: k_sd_match (equality, the case-folded substring search) and k_sd_like (LIKE patterns with %
+// and _: tad_like.h's token program in LDS), one lane per value.
 // Retiring values (tad_strdict_compact): k_sd_compact_flags, two scans (new codes, new arena offsets), k_sd_compact_recs (remap and the new
 // records), k_sd_compact_copy (the survivors' bytes, packed, in whole 16-byte words) and k_sd_compact_rehash (the old table's slots with
 // their codes passed through remap) fill fresh records, a fresh arena and a fresh table; the host swaps them in last.
@@ -238,6 +240,44 @@ __global__ __launch_bounds__(kSdBlock) void k_sd_match(const ulonglong2 *__restr
         }
         hit = same;
       }
+    }
+    out[c] = hit ? 1 : 0;
+    mine += hit ? 1u : 0u;
+  }
+  block_count_add(s_cnt, n_hit, mine);
+}
+
+// tad_strdict_like: one lane per value, k_sd_match's shape.  The token program (tad_like.h: like_compile on the host) lies in LDS, two bytes a
+// token; like_match walks it against the value.  The value's bytes come from ALIGNED 16-byte loads of the arena — every value starts on a
+// 16-byte boundary and is padded to a multiple of 16, so the word that holds byte i < len lies inside the allocation — and the word under the
+// cursor stays in two registers: the matcher moves forward a byte at a time and falls back to the last % only, so a word is loaded once per
+// pass over it.  A value shorter than the program's least length is answered from its record.  No per-lane array: the byte is shifted out of
+// the held word.  The matches are counted with one atomic per workgroup.
+__global__ __launch_bounds__(kSdBlock) void k_sd_like(const ulonglong2 *__restrict__ recs, const uint8_t *__restrict__ arena, uint64_t K,
+                                                      const uint16_t *__restrict__ prog, uint32_t n_tok, uint32_t min_len, uint32_t nocase,
+                                                      uint8_t *__restrict__ out, unsigned long long *__restrict__ n_hit) {
+  __shared__ uint16_t s_tok[kLikeMaxTokens];
+  __shared__ uint32_t s_cnt[kSdBlock / 64];
+  for (uint32_t i = threadIdx.x; i < n_tok && i < kLikeMaxTokens; i += kSdBlock) s_tok[i] = prog[i];
+  __syncthreads();
+  uint32_t mine = 0;
+  for (uint64_t c = (uint64_t)blockIdx.x * kSdBlock + threadIdx.x; c < K; c += (uint64_t)gridDim.x * kSdBlock) {
+    const ulonglong2 r = recs[c];
+    const uint32_t len = sd_rec_len(r);
+    bool hit = false;
+    if (len >= min_len) {
+      const ulonglong2 *w = reinterpret_cast<const ulonglong2 *>(arena + r.x);      // 16-byte aligned, zero-padded to a multiple of 16
+      uint64_t lo = 0ull, hi = 0ull;                                                // the two halves of the 16-byte word held ...
+      uint32_t at = ~0u;                                                            // ... and which one it is (none yet)
+      auto byte = [&](uint32_t i) -> uint32_t {                                     // i < len
+        if ((i >> 4) != at) {
+          const ulonglong2 v = w[i >> 4];
+          at = i >> 4; lo = v.x; hi = v.y;
+        }
+        const uint64_t a = lo, b = hi;                                              // (both read as values: a choice between two addresses would put them in memory)
+        return (uint32_t)(((i & 8u) ? b : a) >> ((i & 7u) * 8u)) & 0xffu;
+      };
+      hit = like_match([&](uint32_t p) -> uint32_t { return s_tok[p]; }, n_tok, byte, len, nocase != 0u);
     }
     out[c] = hit ? 1 : 0;
     mine += hit ? 1u : 0u;
@@ -533,6 +573,14 @@ void launch_sd_match(hipStream_t s, const void *recs, const uint8_t *arena, uint
                      unsigned long long *n_hit) {
   if (K == 0) return;
   hipLaunchKernelGGL(k_sd_match, sd_grid(K), dim3(kSdBlock), 0, s, static_cast<const ulonglong2 *>(recs), arena, K, op, pattern, pattern_len, out, n_hit);
+}
+
+void launch_sd_like(hipStream_t s, const void *recs, const uint8_t *arena, uint64_t K, const uint16_t *prog, uint32_t n_tok, uint32_t min_len, bool nocase,
+                    uint8_t *out, unsigned long long *n_hit) {
+  if (K == 0) return;
+  const uint64_t b = (K + kSdBlock - 1) / kSdBlock;
+  hipLaunchKernelGGL(k_sd_like, dim3((unsigned)(b < kSdLikeMaxBlocks ? b : kSdLikeMaxBlocks)), dim3(kSdBlock), 0, s, static_cast<const ulonglong2 *>(recs), arena, K,
+                     prog, n_tok, min_len, nocase ? 1u : 0u, out, n_hit);
 }
 
 void launch_sd_export_lens(hipStream_t s, const void *recs, uint64_t first, uint64_t n, uint32_t *cnt) {

@@ -1088,6 +1088,28 @@ class StringDict:
             mask = mask.view(0, K, np.uint8)
         return mask, int(hit.value)
 
+    def like(self, pattern, nocase=False, out="host"):
+        """One byte per value (tad_strdict_like): mask[c] = 1 iff the LIKE pattern matches the WHOLE of value c.  % matches any run of
+        bytes, _ exactly one character, \\ makes the next byte a literal; a substring search is '%text%'.  nocase: ilike — 'A'..'Z'
+        fold to 'a'..'z', every other byte matches only itself.  pattern: str (UTF-8) or bytes, at most 1024 bytes.  Returns
+        (mask, n_matched) as match() does: a numpy uint8 array (out="host") or a DeviceArray of num_values bytes (out="device")."""
+        eng = self._engine
+        _need_feature(eng._lib, "STRING_LIKE", "tad_strdict_like")
+        if out not in ("host", "device"):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "StringDict.like: out must be host or device")
+        pat = pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern)
+        buf = (C.c_ubyte * max(len(pat), 1)).from_buffer_copy(pat or b"\0")
+        K = self.num_values()
+        dev = out == "device"
+        mask, ptr = _out_mask(eng, dev, K)
+        hit = capi.u64()
+        rc = eng._lib.tad_strdict_like(eng._h, self._h, C.cast(buf, C.c_void_p) if pat else None, len(pat), capi.TAD_LIKE_NOCASE if nocase else 0, ptr, K,
+                                       capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST, C.byref(hit))
+        eng._check(rc)
+        if dev:
+            mask = mask.view(0, K, np.uint8)
+        return mask, int(hit.value)
+
     def close(self):
         if self._h is not None and self._engine._h is not None:
             self._engine._lib.tad_strdict_destroy(self._engine._h, self._h)

@@ -11,7 +11,8 @@ surviving key uses from the string dictionaries, on the device, so an instance c
 
 The job's name filters (--pod-name, --pod-namespace, --pod-label, --external-ip, --svc-port-name) are predicates on KEY columns of the
 mode, so a job is a key selection: the filter is evaluated once per distinct string of the vocabulary, on the device (StringDict.match:
-equality, and ilike '%label%' as a case-folded substring search), KeyDict.select turns the vocabulary masks into a key mask there, and
+equality, and ilike '%label%' as a case-folded substring search; StringDict.like: a label with the LIKE wildcards % and _ or an
+escape), KeyDict.select turns the vocabulary masks into a key mask there, and
 TadEngine.run_state_keys judges the selected keys only.  The predicates that are NOT key predicates — the namespace ignore list (it tests
 both namespaces of a row), flowType = 3 in external mode, the `<> ''` rules — are applied to the rows in `feed`, before they reach the
 state.  Mode None (no aggregation) has no key filter to serve and is not offered.
@@ -136,8 +137,11 @@ class StreamingAnomalyDetection:
     job without a pod filter), while the batch query with a pod_label or pod_name filter applies only that filter — so a pattern that
     matches the empty string, such as pod_label='%', finds the '' keys in the batch job and not here.  The label filter runs on the
     device when pod_label is ASCII and free of %, _ and \\ (StringDict.match folds the bytes 'A'..'Z' to 'a'..'z' and nothing else: on
-    ASCII strings, which is what Kubernetes allows in labels, exactly ilike '%label%'); any other pattern is evaluated on the host over
-    the exported label strings, with the regex the batch job uses."""
+    ASCII strings, which is what Kubernetes allows in labels, exactly ilike '%label%').  Any other ASCII pod_label of at most 1022
+    bytes — one with the wildcards % and _ or an escape, such as the documented "test_key":"test_value" — runs on the device as well:
+    StringDict.like('%' + pod_label + '%', nocase=True) evaluates the LIKE pattern with the same byte fold.  Only a non-ASCII
+    pattern (Unicode case folding) or a longer one is evaluated on the host over the exported label strings, with the regex the
+    batch job uses."""
 
     def __init__(self, engine=None, agg_flow="svc", pod_ident="labels", ns_ignore_list=()):
         if agg_flow not in MODES:
@@ -216,7 +220,9 @@ class StreamingAnomalyDetection:
         if pod_label:
             if pod_label.isascii() and not any(c in pod_label for c in "%_\\") and len(pod_label) <= 1024:
                 terms = [(1, self._vocab[1].match(_capi.TAD_STR_CONTAINS_NOCASE, pod_label, out="device")[0])]
-            else:                                                  # wildcards or non-ASCII case folding: the batch job's regex over the exported labels
+            elif pod_label.isascii() and len(pod_label) <= 1022:     # %, _ or \ in ASCII text: the whole LIKE pattern on the device
+                terms = [(1, self._vocab[1].like("%" + pod_label + "%", nocase=True, out="device")[0])]
+            else:                                                  # non-ASCII case folding, or a pattern over the limit: the batch job's regex over the exported labels
                 rx = _ad._like_regex("%" + pod_label + "%")
                 labels = self._vocab[1].values().to_pylist()
                 terms = [(1, np.fromiter((1 if rx.match(s) is not None else 0 for s in labels), dtype=np.uint8, count=len(labels)))]

@@ -284,7 +284,8 @@ def hash8(words):
 
 def test_two_strings_with_one_fingerprint_are_two_values(engine):
     """Among 4e5 8-byte strings the expected number of pairs whose hashes share the high 32 bits — the slot's fingerprint — is
-    N (N - 1) / 2 / 2^32 = 18.6; the probability of none is e^-18.6.  Such a pair is told apart by the bytes alone."""
+    N (N - 1) / 2 / 2^32 = 18.6; the probability of none is e^-18.6.  Such a pair is told apart by the bytes alone.  Whether the two probe
+    sequences meet in the 64-slot table is left to chance here; the case where they do is built in tests/test_gpu_slot_table.py."""
     words = np.arange(400000, dtype=np.uint64) * np.uint64(0x0101010101010101) + np.uint64(0x2020202020202020)
     fp = hash8(words) >> np.uint64(32)
     order = np.argsort(fp, kind="stable")

@@ -1185,6 +1185,89 @@ func (s *State) Merge(job Job, cols Columns, keepFrom int64) (MergeStats, error)
 		MsTotal: float32(ms.ms_total)}, nil
 }
 
+var stateReplaceOnce sync.Once
+var stateReplaceOK bool
+
+// hasStateReplace: the library knows tad_state_replace (tad_features); an older one would not export the call.
+func hasStateReplace() bool {
+	stateReplaceOnce.Do(func() { stateReplaceOK = C.tad_features()&C.TAD_FEATURE_STATE_REPLACE != 0 })
+	return stateReplaceOK
+}
+
+// ReplaceStats is what one Replace did with the batch's points and with the points the state held (tad_replace_stats).
+type ReplaceStats struct {
+	RowsIn, RowsUsed uint64
+	BatchPoints      uint64 // distinct (key, flowEndSeconds) points of the batch
+	PointsTooOld     uint64 // older than keepFrom: dropped
+	PointsAppended   uint64 // newer than everything their key held
+	PointsInserted   uint64 // a new time before the key's last one
+	PointsReplaced   uint64 // a time the key already held: value = the batch's
+	PointsErased     uint64 // points the state held inside the range that the batch does not name
+	KeysEmptied      uint64 // keys that held points and hold none afterwards
+	KeysTouched      uint64
+	KeysReplayed     uint64 // keys whose moments were replayed from the zero state
+	MsTotal          float32
+}
+
+// Replace makes ONE batch the truth for the points it names (tad_state_replace): a point at a time its key already holds takes the
+// batch's value instead of being combined with it, so a re-read of the same rows leaves the same state under sum as under max.  With
+// ranged the batch is ALL rows with fromT <= flowEndSeconds < toT (0 = no bound on that side): every point of the state inside that
+// range that the batch does not name is erased, on every key, and an empty batch still erases the range.  A poller re-reads
+// [watermark - lag, now), calls Replace with that range and moves the watermark: the turn is idempotent.  The state must be made by
+// NewStateWithTimes.  No rows are returned.  The value op follows job.AggFlow as in RunStream and only aggregates rows inside the batch.
+func (s *State) Replace(job Job, cols Columns, ranged bool, fromT, toT, keepFrom int64) (ReplaceStats, error) {
+	if !hasStateReplace() {
+		return ReplaceStats{}, errors.New("tadengine: libtad_mi355x.so has no tad_state_replace (TAD_FEATURE_STATE_REPLACE)")
+	}
+	if !s.series || !s.times {
+		return ReplaceStats{}, IllegalArgument{"tadengine: Replace needs a state made by NewStateWithTimes"}
+	}
+	bufs, n, narrow, err := columnBuffers(cols)
+	if err != nil {
+		return ReplaceStats{}, err
+	}
+	defer freeBuffers(bufs)
+	var cj C.tad_job
+	cj.flags = narrow
+	cj.algo = C.TAD_ALGO_EWMA
+	cj.agg_flow = C.tad_agg_flow(job.AggFlow)
+	cj.value_op = C.TAD_OP_AUTO
+	cj.start_time = C.int64_t(job.StartTime)
+	cj.end_time = C.int64_t(job.EndTime)
+	id := []byte(job.ID)
+	if len(id) > 63 {
+		id = id[:63]
+	}
+	for i, b := range id {
+		cj.id[i] = C.char(b)
+	}
+	var cc C.tad_columns
+	cc.n_rows = C.uint64_t(n)
+	cc.num_keys = C.uint64_t(cols.NumKeys)
+	cc.memory = C.TAD_MEM_HOST
+	cc.key_id = (*C.uint64_t)(bufs[0])
+	cc.key_id2 = (*C.uint64_t)(bufs[1])
+	cc.flow_end_s = (*C.int64_t)(bufs[2])
+	cc.flow_start_s = (*C.int64_t)(bufs[3])
+	cc.value = (*C.uint64_t)(bufs[4])
+	var flags C.uint32_t
+	if ranged {
+		flags = C.TAD_REPLACE_RANGE
+	}
+	var rs C.tad_replace_stats
+	if rc := C.tad_state_replace(s.e.h, s.h, &cj, &cc, flags, C.int64_t(fromT), C.int64_t(toT), C.int64_t(keepFrom), &rs); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return ReplaceStats{}, IllegalArgument{msg}
+		}
+		return ReplaceStats{}, fmt.Errorf("tad_state_replace: %s (code %d)", msg, int(rc))
+	}
+	return ReplaceStats{RowsIn: uint64(rs.rows_in), RowsUsed: uint64(rs.rows_used), BatchPoints: uint64(rs.batch_points),
+		PointsTooOld: uint64(rs.points_too_old), PointsAppended: uint64(rs.points_appended), PointsInserted: uint64(rs.points_inserted),
+		PointsReplaced: uint64(rs.points_replaced), PointsErased: uint64(rs.points_erased), KeysEmptied: uint64(rs.keys_emptied),
+		KeysTouched: uint64(rs.keys_touched), KeysReplayed: uint64(rs.keys_replayed), MsTotal: float32(rs.ms_total)}, nil
+}
+
 var keyDictOnce sync.Once
 var keyDictOK bool
 

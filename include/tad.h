@@ -559,7 +559,8 @@ int tad_run_state(tad_engine *e, tad_state *s, const tad_job *job, tad_mem out_m
  *     (rows, order, bits) for EWMA, DBSCAN (history states) and ARIMA;
  *   - a point at a time the key already holds is combined with Stage 0's own operator, sum wrapping mod 2^64 or unsigned max.  The state
  *     does not remember which op built it: use the same value op for every batch of a state (there is nothing to check it against);
- *   - re-sending a batch is idempotent under max and doubles the values under sum: it is a merge, not a de-duplication;
+ *   - re-sending a batch is idempotent under max and doubles the values under sum: it is a merge, not a de-duplication (a re-read that
+ *     must not double goes through tad_state_replace, below);
  *   - tad_run_stream batches and merges mix freely on one state: the invariants (the moments are the series', the history is the series'
  *     values sorted, times ascend strictly, last_t is the newest time) hold after every merge, so a later DBSCAN / ARIMA stream batch
  *     emits what tad_run over the merged window plus the batch emits for the batch's points.  tad_run_stream itself still refuses late rows;
@@ -607,6 +608,73 @@ typedef struct {
 } tad_merge_stats;
 int tad_state_merge(tad_engine *e, tad_state *s, const tad_job *job, const tad_columns *cols, int64_t keep_from_t,
                     tad_merge_stats *stats /* may be NULL */);
+
+/* ---- a batch that replaces: re-read windows, retried polls, restarts (TAD_FEATURE_STATE_REPLACE; check tad_features() before calling
+ * this) ----
+ * A poller delivers at least once: it re-reads the last minutes because exporters lag by node, it re-reads after a restart, it retries
+ * after a timeout.  Through tad_state_merge every such re-read doubles, under sum, each point it saw twice.  tad_state_replace says "for
+ * these seconds, this batch is the truth": the poll loop becomes re-read [watermark - lag, now), replace, move the watermark, and is
+ * idempotent by construction under both value ops.
+ * Contract, a pure function of W.  Let W be the table with one row per series point the state holds, (key, flow_end_s, value) —
+ * tad_run_state's W.  Let B be Stage 0's points of the batch: the job's filters and value op, exactly as tad_state_merge aggregates a
+ * batch, without the points whose flow_end_s < keep_from_t when keep_from_t != 0.  Let R be empty without TAD_REPLACE_RANGE, and with it
+ * R = {t : (from_t == 0 || t >= from_t) && (to_t == 0 || t < to_t)} — the half-open rule of tad_run_state_window; from_t = to_t = 0 is
+ * every time.  Let W' = {w in W : time(w) not in R and (key, time)(w) not a point of B} ++ B.  After a successful call the state — n, avg,
+ * m2, ewma, last_t, series, times, and the history if it has one — is bit for bit the state a fresh state of the same flags and num_keys
+ * holds after ONE tad_run_stream EWMA batch over W' with ewma_alpha (0 -> 0.5).
+ * Consequences:
+ *   - the same call twice leaves the same bits: the second call replaces every point of B with itself and erases nothing;
+ *   - a point of B at a time its key already holds takes B's value; the old value is never combined with it;
+ *   - a key whose points all fall in R and that has none in B becomes an unseen key (all zeros, empty series);
+ *   - the erase acts on EVERY key of the state, not only on the keys of the batch: R says the batch holds all rows of those seconds;
+ *   - the value op only aggregates rows inside the batch (several rows of one (key, second)); it never meets a value of the state;
+ *   - without TAD_REPLACE_RANGE nothing is erased: the call is a merge whose combined points take the new value;
+ *   - replaces, merges, stream batches, trims and compacts mix freely on one state: the state's invariants hold after every replace, so
+ *     tad_run_state afterwards returns exactly tad_run over W', and a later DBSCAN / ARIMA stream batch emits what tad_run over W' plus
+ *     that batch emits for its points;
+ *   - the call emits no rows; job->algo and the detector parameters other than ewma_alpha are ignored;
+ *   - moments: a key with an inserted, replaced or erased point is replayed from the zero state over its new series in time order (an
+ *     emptied key is left at the zero state, the bits of an unseen key); a key that only had points appended continues from its stored
+ *     state; an untouched key is copied.
+ * Arguments and refusals (TAD_ERR_INVALID_ARGUMENT with a message, state unchanged): everything tad_state_merge refuses — a state
+ * without TAD_STATE_SERIES | TAD_STATE_TIMES, stale times, TAD_FLAG_EMIT_ALL_POINTS, ewma_alpha outside [0, 1], cols->num_keys other than
+ * the state's, the column checks — and: unknown bits in flags; a non-zero from_t or to_t without TAD_REPLACE_RANGE; from_t > to_t with
+ * both non-zero.  from_t == to_t non-zero is an empty R.  The honoured tad_job fields are tad_state_merge's.
+ * Atomic like a merge: only the candidate copies and job-context workspace are written, and the candidates become current together;
+ * any failure — a key out of range (TAD_ERR_KEY_RANGE), allocation, a HIP error — leaves the state as it was.
+ * Two differences from tad_state_merge: an empty batch (no row, or no row that passes the filters, or every point too old) with a
+ * non-empty R is not a no-op — it erases R; and the append path of a stream batch (keys_replayed == 0) needs a batch without a replaced,
+ * inserted, too-old or erased point.  Otherwise a replace costs what a merge costs — a rewrite of the series and times, the history
+ * rewritten once, twice when a point was replaced or erased, a serial replay per key with an inserted, replaced or erased point — plus,
+ * with a range, two binary searches per key of the state and a second host round trip for the erased total.  After a
+ * replace that erased, an arena left below a quarter of its capacity is allocated anew at twice its length, tad_state_trim's rule.
+ * Memory outside the state: tad_state_merge's, and the packed values the history loses (16 B per replaced or erased point).
+ * Lock order: the state, then a job context, as a merge. */
+#define TAD_FEATURE_STATE_REPLACE 65536u /* tad_state_replace: a batch that replaces the points it names and, ranged, erases the seconds it covers */
+#define TAD_REPLACE_RANGE 1u             /* erase every point of the state with from_t <= flow_end_s < to_t (0 = no bound) that the batch does not name */
+typedef struct {
+  uint64_t rows_in;                  /* as tad_stats */
+  uint64_t rows_used;
+  uint64_t batch_points;             /* distinct (key, flowEndSeconds) points Stage 0 made of the batch, before keep_from_t */
+  uint64_t points_too_old;           /* of those: flow_end_s < keep_from_t, dropped */
+  uint64_t points_appended;          /* newer than everything their key held before the call */
+  uint64_t points_inserted;          /* a new time before the key's last_t */
+  uint64_t points_replaced;          /* a time the key already held: value = the batch's */
+  uint64_t points_erased;            /* points the state held inside R that the batch does not name: removed */
+  uint64_t keys_emptied;             /* keys that held points before the call and hold none after it */
+  uint64_t keys_touched;             /* keys whose moments changed: >= 1 appended / inserted / replaced / erased point */
+  uint64_t keys_replayed;            /* of those: replayed from the zero state (>= 1 inserted, replaced or erased point) */
+  int32_t stage0_path;               /* as tad_stats */
+  int32_t stage0_attempts;
+  int32_t job_context;
+  int32_t reserved;
+  float ms_stage0;                   /* HIP events, as tad_stats */
+  float ms_replace;                  /* everything after Stage 0 */
+  float ms_total;
+  float reserved1;
+} tad_replace_stats;
+int tad_state_replace(tad_engine *e, tad_state *s, const tad_job *job, const tad_columns *cols, uint32_t flags, int64_t from_t, int64_t to_t,
+                      int64_t keep_from_t, tad_replace_stats *stats /* may be NULL */);
 
 /* ---- the batch verdicts over a time range of a state (TAD_FEATURE_STATE_WINDOW; check tad_features() before calling this) ----
  * tad_run_state judges everything the state holds, and tad_state_trim narrows a state for good and at its old end only.  A state that

@@ -27,6 +27,8 @@ TAD_FEATURE_STREAM_TRIM = 8                  # tad_features() bit: TAD_STATE_TIM
 TAD_STATE_TIMES = 8                          # tad_state_create_ex flag (with TAD_STATE_SERIES): keep every series point's flowEndSeconds
 TAD_FEATURE_STATE_RUN = 16                   # tad_features() bit: tad_run_state, the batch job's rows over everything a state holds
 TAD_FEATURE_STATE_MERGE = 32                 # tad_features() bit: tad_state_merge, a batch placed by time (late, re-sent and split rows)
+TAD_FEATURE_STATE_REPLACE = 65536            # tad_features() bit: tad_state_replace, a batch that replaces (re-read windows that must not double)
+TAD_REPLACE_RANGE = 1                        # tad_state_replace flag: erase every point of the state inside [from_t, to_t) that the batch does not name
 TAD_FEATURE_STATE_WINDOW = 64                # tad_features() bit: tad_run_state_window, tad_run_state over a time range of the state, read-only
 TAD_FEATURE_KEY_DICT = 128                   # tad_features() bit: tad_keydict, a persistent tuple -> key id dictionary on the device
 TAD_FEATURE_KEY_RETIRE = 256                 # tad_features() bit: tad_state_compact / tad_keydict_compact, dead keys dropped and the rest renumbered
@@ -127,6 +129,14 @@ class MergeStats(C.Structure):
                 ("ms_stage0", f32), ("ms_merge", f32), ("ms_total", f32), ("reserved1", f32)]
 
 
+class ReplaceStats(C.Structure):
+    """tad_replace_stats: what one tad_state_replace call did with the batch's points and with the points the state held."""
+    _fields_ = [("rows_in", u64), ("rows_used", u64), ("batch_points", u64), ("points_too_old", u64), ("points_appended", u64),
+                ("points_inserted", u64), ("points_replaced", u64), ("points_erased", u64), ("keys_emptied", u64), ("keys_touched", u64),
+                ("keys_replayed", u64), ("stage0_path", i32), ("stage0_attempts", i32), ("job_context", i32), ("reserved", i32),
+                ("ms_stage0", f32), ("ms_replace", f32), ("ms_total", f32), ("reserved1", f32)]
+
+
 class CompactStats(C.Structure):
     """tad_compact_stats: what one tad_state_compact call retired and moved."""
     _fields_ = [("keys_before", u64), ("keys_after", u64), ("num_keys", u64), ("keys_unseen", u64), ("keys_idle", u64), ("points_dropped", u64),
@@ -188,6 +198,7 @@ SYMBOLS = {
     "tad_run_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_run_state": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_state_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), i64, C.POINTER(MergeStats)]),
+    "tad_state_replace": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_uint32, i64, i64, i64, C.POINTER(ReplaceStats)]),
     "tad_run_state_window": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_window_history_by_sort": (C.c_int, [u64, u64]),
     "tad_aggregate": (C.c_int, [C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Points))]),

@@ -319,6 +319,49 @@ def rows_query(start_time, end_time, ns_ignore_list, agg_flow=None, pod_label=No
     return sql
 
 
+def stream_rows_query(agg_flow, pod_ident="labels", ns_ignore_list=(), from_t=0, to_t=0, dictionary=False):
+    """SELECT of the raw rows a StreamingAnomalyDetection(agg_flow, pod_ident, ns_ignore_list) reads in `feed`, for the seconds
+    from_t <= flowEndSeconds < to_t (epoch seconds; 0 = no bound on that side): the rows of a `poll`.  The WHERE clause is the instance's
+    ROW predicates — the namespace ignore list, flowType = 3 in external mode, the `<> ''` rule of the mode's key column (pod mode: a row
+    stays when either side passes, the feed tests each side again) — and the range.  No key filter (the jobs select keys on the
+    device) and no flowStartSeconds test (the state holds flowEndSeconds alone).  Only the columns `feed` reads are selected;
+    dictionary: the string columns as `toLowCardinality(c) AS c`, for a read with DICTIONARY_SETTINGS."""
+    if agg_flow not in ("pod", "external", "svc"):
+        raise ValueError("aggregated flow type should be 'pod' or 'external' or 'svc'")
+    if pod_ident not in ("labels", "name"):
+        raise ValueError("pod_ident should be 'labels' or 'name'")
+    from_t, to_t = int(from_t), int(to_t)
+    where = []
+    if ns_ignore_list:
+        quoted = ", ".join("'{}'".format(x) for x in ns_ignore_list)
+        where.append("sourcePodNamespace NOT IN ({0}) AND destinationPodNamespace NOT IN ({0})".format(quoted))
+    namespaces = ["sourcePodNamespace", "destinationPodNamespace"]
+    if agg_flow == "pod":
+        ident = "PodName" if pod_ident == "name" else "PodLabels"
+        where.append("(destination{0} <> '' OR source{0} <> '')".format(ident))
+        columns = namespaces + ["source" + ident, "destination" + ident]
+    elif agg_flow == "external":
+        where.append("flowType = 3")
+        columns = ["destinationIP", "flowType"] + (namespaces if ns_ignore_list else [])
+    else:
+        where.append("destinationServicePortName <> ''")
+        columns = ["destinationServicePortName"] + (namespaces if ns_ignore_list else [])
+    if from_t:
+        where.append("flowEndSeconds >= toDateTime({})".format(from_t))
+    if to_t:
+        where.append("flowEndSeconds < toDateTime({})".format(to_t))
+    columns += ["flowEndSeconds", "throughput"]
+    if dictionary:
+        columns = ["toLowCardinality({0}) AS {0}".format(c) if c in STRING_COLUMNS else c for c in columns]
+    return "SELECT {} FROM {} WHERE {}".format(", ".join(columns), FLOWS_TABLE, " AND ".join(where))
+
+
+def stream_rows_columns(agg_flow, pod_ident="labels", ns_ignore_list=()):
+    """the column names stream_rows_query selects, in its order (an empty read still needs them)"""
+    sql = stream_rows_query(agg_flow, pod_ident, ns_ignore_list)
+    return sql[len("SELECT "):sql.index(" FROM ")].split(", ")
+
+
 def fetch_flows(client, start_time="", end_time="", ns_ignore_list=(), agg_flow="", pod_label="", external_ip="",
                 svc_port_name="", pod_name="", pod_namespace="", engine=None):
     """Raw-rows read: the column dict theia_amd.anomaly_detection.prepare_columns expects.  With `engine` the string columns are

@@ -1,6 +1,6 @@
 // tad_capi.cpp — what the entry points of include/tad.h share (key buffers, the rows result and its epilogue, the moments' merge), the batches
-// on a streaming state that the job's count pass runs (history, series, merge, ARIMA, DROP), and the two calls that feed the job such a
-// batch: tad_drop_stream, tad_state_merge.  The batch job itself (run_job_locked: lattice, Stage 0, count, retries) is tad_capi_job.cpp;
+// on a streaming state that the job's count pass runs (history, series, merge, replace, ARIMA, DROP), and the calls that feed the job such a
+// batch: tad_drop_stream, tad_state_merge, tad_state_replace.  The batch job itself (run_job_locked: lattice, Stage 0, count, retries) is tad_capi_job.cpp;
 // the read-only jobs on a state (tad_run_state, tad_run_state_window, tad_drop_state, their *_keys forms) are tad_capi_view.cpp; the life
 // of a tad_state is tad_capi_state.cpp.
 #include "tad_engine.h"
@@ -281,6 +281,26 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
   return dbscan ? hist_verdicts(e, st->hist.off[cand], st->hist.val.p[cand], jp, hb) : TAD_OK;
 }
 
+// The append path of a merge or replace whose points are all newer than what their keys held: stream_history_batch's steps 2, 3, 3', 3''
+// into the candidate copies, then the moments continued from the stored state (no key replays).
+static void merge_append_path(JobCtx *e, tad_state *st, uint64_t K, const unsigned long long *poff, const long long *nt, const unsigned long long *nv,
+                              uint64_t P_cap, double alpha, const MergeKeys &mk, MergeCounters *mcnt) {
+  hipStream_t s = e->stream;
+  const int cur = st->cur, cand = cur ^ 1;
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  if (st->history) {
+    unsigned long long *ns = static_cast<unsigned long long *>(e->hs_sorted.p);
+    launch_hist_sort(s, nv, poff, K, ns, mk.long_list, mk.long_count);
+    launch_hist_merge(s, K, st->hist.off[cur], st->hist.val.p[cur], poff, ns, st->hist.off[cand], st->hist.val.p[cand], mk.chunks_h, mk.coff_h, scratch,
+                      hist_merge_chunks_bound(K, st->hist.len[cur] + P_cap));
+  }
+  launch_series_append(s, K, st->ser.off[cur], st->ser.val.p[cur], poff, nv, st->ser.off[cand], st->ser.val.p[cand]);
+  launch_series_append(s, K, st->ser.off[cur], reinterpret_cast<const unsigned long long *>(st->ser_times.p[cur]), poff,
+                       reinterpret_cast<const unsigned long long *>(nt), st->ser.off[cand], reinterpret_cast<unsigned long long *>(st->ser_times.p[cand]));
+  launch_merge_moments(s, K, nullptr, st->ser.off[cur], st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], alpha, state_view(st, cur),
+                       state_view(st, cand), mcnt);
+}
+
 // One tad_state_merge batch (tad.h; kernels in tad_merge.hip), in the place of a stream batch's count pass: the batch's points in (key, time)
 // order are classified against the current series, then either appended as a stream batch appends them (nothing inserted, combined or
 // too old) or merged by time into the candidate series, times, history and moments.  Writes candidate memory and context workspace only;
@@ -334,18 +354,8 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
   ms.keys_touched = ms.keys_replayed = 0;
   if (c.appended + c.inserted + c.combined == 0) return TAD_OK;   // nothing to merge: the state stays as it is
   if (c.inserted == 0 && c.combined == 0 && c.too_old == 0) {
-    // 6. every point is newer than what its key held: the append path of a stream batch (stream_history_batch's steps 2, 3, 3', 3'')
-    if (st->history) {
-      unsigned long long *ns = static_cast<unsigned long long *>(e->hs_sorted.p);
-      launch_hist_sort(s, nv, poff, K, ns, mk.long_list, mk.long_count);
-      launch_hist_merge(s, K, st->hist.off[cur], st->hist.val.p[cur], poff, ns, st->hist.off[cand], st->hist.val.p[cand], mk.chunks_h, mk.coff_h, scratch,
-                        hist_merge_chunks_bound(K, H + P_cap));
-    }
-    launch_series_append(s, K, st->ser.off[cur], st->ser.val.p[cur], poff, nv, st->ser.off[cand], st->ser.val.p[cand]);
-    launch_series_append(s, K, st->ser.off[cur], reinterpret_cast<const unsigned long long *>(st->ser_times.p[cur]), poff,
-                         reinterpret_cast<const unsigned long long *>(nt), st->ser.off[cand], reinterpret_cast<unsigned long long *>(st->ser_times.p[cand]));
-    launch_merge_moments(s, K, nullptr, st->ser.off[cur], st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], alpha, state_view(st, cur),
-                         state_view(st, cand), mcnt);
+    // 6. every point is newer than what its key held: the append path of a stream batch
+    merge_append_path(e, st, K, poff, nt, nv, P_cap, alpha, mk, mcnt);
   } else {
     if (st->history && c.combined && (rc = ensure(e, e->mg_hist, (H ? H : 1) * 8)) != TAD_OK) return rc;
     // 2. the scans; per key: candidate offsets, the history's packed gains / losses, chunk counts, who replays
@@ -385,6 +395,129 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
   ms.keys_replayed = c.keys_replayed;
   mc->changed = true;
   mc->added = c.inserted + c.appended;
+  return TAD_OK;
+}
+
+// One tad_state_replace batch (tad.h; kernels in tad_replace.hip), state_merge_batch's twin: the same classification, but a point at a
+// time its key holds takes the batch's value, and with mc->ranged every old point of every key inside [from_t, to_t) that the batch does
+// not name is erased.  K: the state's keys; g.K == 0 (a batch without a live row) or a batch without points still erases the range.  Two
+// host round trips when ranged: the classification's counters, then the erased total (the append path and the arena sizes hang on it).
+int state_replace_batch(JobCtx *e, tad_state *st, uint64_t K, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound,
+                        double alpha, MergeCall *mc) {
+  hipStream_t s = e->stream;
+  const int cur = st->cur, cand = cur ^ 1;
+  const bool no_batch = g.K == 0;
+  const uint64_t P_cap = no_batch ? 0 : (sparse_poff ? P : P_bound);
+  const uint64_t pc = P_cap ? P_cap : 1;
+  const uint64_t S = st->ser.len[cur], H = st->hist.len[cur];
+  BatchKeys bk;
+  MergePts mp;
+  MergeKeys mk;
+  ReplaceKeys rk;
+  int rc;
+  mc->changed = false;
+  mc->added = mc->erased = mc->emptied = 0;
+  // the candidate arenas first: an allocation failure leaves the state as it is
+  if ((rc = state_grow_candidates(e, st, P_cap)) != TAD_OK) return rc;
+  if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr, &bk)) != TAD_OK) return rc;
+  if ((rc = carve_buf(e, e->mg_pts, &mp, merge_pts_layout, pc)) != TAD_OK) return rc;
+  if ((rc = carve_buf(e, e->mg_keys, &mk, merge_keys_layout, K)) != TAD_OK) return rc;
+  if ((rc = carve_buf(e, e->rp_keys, &rk, replace_keys_layout, K)) != TAD_OK) return rc;
+  MergeCounters *mcnt = mk.mcnt;
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  const unsigned long long *nk = static_cast<const unsigned long long *>(e->hs_key.p);
+  const long long *nt = static_cast<const long long *>(e->hs_t.p);
+  const unsigned long long *poff = rk.pzero, *nv = nullptr;
+  {   // the erased runs and their scan are all zero until the range kernel says otherwise; pzero stays zero
+    Carve measure(nullptr);
+    replace_keys_layout(measure, K);
+    HIP_TRY(e, hipMemsetAsync(e->rp_keys.p, 0, measure.bytes(), s));
+  }
+  if (!no_batch) batch_points(e, bk, g, L, sparse_poff, P, &poff, &nv);
+  // 1. classify; the first round trip: Stage 0's error word, the point count, the classification's counters
+  HIP_TRY(e, hipMemsetAsync(mcnt, 0, sizeof(MergeCounters), s));
+  launch_merge_classify(s, nk, nt, poff + K, P_cap, K, st->ser.off[cur], st->ser_times.p[cur], (long long)mc->keep_from, mp.cls, mp.rank, mp.f_nh, mp.f_kept, mp.f_hit, mcnt);
+  unsigned char *hm = e->tail_host + kTailMoments;   // (the moment partials' place in the pinned tail: a replace has none)
+  HIP_TRY(e, hipMemcpyAsync(e->ctr_host, e->counters.p, sizeof(DevCounters), hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(hm + sizeof(MergeCounters), poff + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  if (e->ctr_host->err != 0) return TAD_OK;
+  MergeCounters c;
+  unsigned long long points = 0, erased = 0;
+  memcpy(&c, hm, sizeof c);
+  memcpy(&points, hm + sizeof c, 8);
+  tad_merge_stats &ms = mc->stats;
+  ms.batch_points = points;
+  ms.points_too_old = c.too_old;
+  ms.points_appended = c.appended;
+  ms.points_inserted = c.inserted;
+  ms.points_combined = c.combined;
+  ms.keys_touched = ms.keys_replayed = 0;
+  // 2. the scan of the replaced points, the erased runs (the poff the points came with is sound: Stage 0 raised no error), their scan;
+  //    the second round trip: the erased total
+  launch_scan(s, mp.f_hit, mp.roff, P_cap, scratch);
+  if (mc->ranged && S != 0) {
+    launch_replace_range(s, K, st->ser.off[cur], st->ser_times.p[cur], poff, nt, mp.roff, (long long)mc->from_t, (long long)mc->to_t, rk.ebeg, rk.eend, rk.ecnt);
+    launch_scan(s, rk.ecnt, rk.eoff, K, scratch);
+    HIP_TRY(e, hipMemcpyAsync(hm, rk.eoff + K, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    HIP_TRY(e, hipGetLastError());
+    memcpy(&erased, hm, 8);
+  }
+  if (c.appended + c.inserted + c.combined + erased == 0) return TAD_OK;   // nothing to place, nothing to erase: the state stays as it is
+  const uint64_t added = c.inserted + c.appended;
+  if (c.inserted == 0 && c.combined == 0 && c.too_old == 0 && erased == 0) {
+    // every point is newer than what its key held and nothing leaves: the append path of a stream batch, as a merge takes it
+    merge_append_path(e, st, K, poff, nt, nv, P_cap, alpha, mk, mcnt);
+  } else {
+    const uint64_t lost = c.combined + erased;
+    const uint64_t n_ser = S + added - erased, n_hist = H + added - erased;
+    ReplaceLoss rl{nullptr, nullptr};
+    if (erased && (rc = state_size_arenas(e, st, cand, n_ser, st->history ? n_hist : 0, true, "tad_state_replace")) != TAD_OK) return rc;
+    if (st->history && lost) {
+      if ((rc = ensure(e, e->mg_hist, (H ? H : 1) * 8)) != TAD_OK) return rc;
+      if ((rc = carve_buf(e, e->rp_loss, &rl, replace_loss_layout, lost)) != TAD_OK) return rc;
+    }
+    // the scans; per key: candidate offsets, the history's packed gains / losses, chunk counts, who replays, who is emptied
+    launch_scan(s, mp.f_nh, mp.nhoff, P_cap, scratch);
+    launch_scan(s, mp.f_kept, mp.aoff, P_cap, scratch);
+    launch_replace_keys(s, K, poff, mp.nhoff, mp.aoff, mp.roff, mp.cls, rk.ecnt, rk.eoff, st->ser.off[cur], st->history ? st->hist.off[cur] : nullptr,
+                        st->ser.off[cand], mk.akoff, mk.rkoff, mk.hoff_mid, mk.chunks_s, mk.chunks_h, mk.replay, mcnt);
+    launch_scan(s, mk.chunks_s, mk.coff_s, K, scratch);
+    // 3. series and times (and the history's gains and losses packed)
+    launch_replace_series(s, merge_chunks_bound(K, S + P_cap), mk.coff_s, K, st->ser.off[cur], st->ser.val.p[cur], st->ser_times.p[cur], poff, nt, nv, mp.cls,
+                          mp.rank, mp.nhoff, mp.aoff, mp.roff, rk.ebeg, rk.eend, rk.ecnt, mc->ranged ? (long long)mc->from_t : 0ll, mk.rkoff, st->ser.off[cand],
+                          st->ser.val.p[cand], st->ser_times.p[cand], st->history ? mp.hadd : nullptr, st->history ? (lost ? rl.hrem : mp.hrem) : nullptr);
+    if (st->history) {   // 4. the replaced and erased values leave the history (through the scratch arena), then the batch's values enter
+      const unsigned long long *hoff_from = st->hist.off[cur], *hval_from = st->hist.val.p[cur];
+      if (lost) {
+        unsigned long long *hmid = static_cast<unsigned long long *>(e->mg_hist.p);
+        launch_hist_sort(s, rl.hrem, mk.rkoff, K, rl.hrem_s, mk.long_list, mk.long_count);
+        launch_scan(s, mk.chunks_h, mk.coff_h, K, scratch);
+        launch_hist_subtract(s, trim_chunks_bound(K, H), mk.coff_h, K, st->hist.off[cur], st->hist.val.p[cur], mk.rkoff, rl.hrem_s, mk.hoff_mid, hmid, false);
+        hoff_from = mk.hoff_mid;
+        hval_from = hmid;
+      }
+      launch_hist_sort(s, mp.hadd, mk.akoff, K, mp.hadd_s, mk.long_list, mk.long_count);
+      launch_hist_merge(s, K, hoff_from, hval_from, mk.akoff, mp.hadd_s, st->hist.off[cand], st->hist.val.p[cand], mk.chunks_h, mk.coff_h, scratch,
+                        hist_merge_chunks_bound(K, H + P_cap));
+    }
+    // 5. the moments
+    launch_merge_moments(s, K, mk.replay, st->ser.off[cur], st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], alpha, state_view(st, cur),
+                         state_view(st, cand), mcnt);
+  }
+  HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  HIP_TRY(e, hipGetLastError());
+  memcpy(&c, hm, sizeof c);
+  ms.keys_touched = c.keys_touched;
+  ms.keys_replayed = c.keys_replayed;
+  mc->changed = true;
+  mc->added = added;
+  mc->erased = erased;
+  mc->emptied = c.keys_emptied;
   return TAD_OK;
 }
 
@@ -536,41 +669,78 @@ int tad_drop_stream(tad_engine *eng, tad_state *st, const tad_job *job, const ta
   return run_job_locked(call.e, job, cols, out_memory, out, nullptr, st, 0);
 }
 
-// tad.h: a batch placed by time.  The batch runs as a stream batch does up to the end of Stage 0 (run_job_locked with the context's merge
-// mode set), then state_merge_batch.
-int tad_state_merge(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, int64_t keep_from_t, tad_merge_stats *stats) {
-  if (stats) memset(stats, 0, sizeof *stats);
-  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: engine is NULL");
-  if (!st || !job || !cols) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: state, job and cols must not be NULL");
+// what tad_state_merge and tad_state_replace refuse alike (who: the call's name), then the batch run as a stream batch does up to the end
+// of Stage 0 (run_job_locked with the context's merge mode set) and state_merge_batch / state_replace_batch in the count pass's place
+static int run_merge_call(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, const char *who, MergeCall *mc) {
   if (!st->series || !st->times)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES): "
-                                               "without them it does not know where a late point belongs; state unchanged");
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES): "
+                                               "without them it does not know where a late point belongs; state unchanged", who);
   if (job->flags & TAD_FLAG_EMIT_ALL_POINTS)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: TAD_FLAG_EMIT_ALL_POINTS asks for rows; a merge emits none (tad_run_state judges the window)");
-  if (!(job->ewma_alpha >= 0.0 && job->ewma_alpha <= 1.0)) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: ewma_alpha out of range");
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: TAD_FLAG_EMIT_ALL_POINTS asks for rows; a merge emits none (tad_run_state judges the window)", who);
+  if (!(job->ewma_alpha >= 0.0 && job->ewma_alpha <= 1.0)) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: ewma_alpha out of range", who);
   if (cols->num_keys != st->K)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: batch declares %llu keys, the state holds %llu (they must be equal)",
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: batch declares %llu keys, the state holds %llu (they must be equal)", who,
                 (unsigned long long)cols->num_keys, (unsigned long long)st->K);
   {
-    const int vrc = validate_job_columns(eng, job, cols, "tad_state_merge");
+    const int vrc = validate_job_columns(eng, job, cols, who);
     if (vrc != TAD_OK) return vrc;
   }
   tad_job j = *job;   // the detector is not run: a stream batch of the EWMA kind up to the end of Stage 0
   j.algo = TAD_ALGO_EWMA;
   StateCall call(eng, st);
   if (st->times_stale)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: the series was imported without its times (tad_state_import_times); state unchanged");
-  int rc = call.enter("tad_state_merge", j.id);
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the series was imported without its times (tad_state_import_times); state unchanged", who);
+  int rc = call.enter(who, j.id);
   if (rc != TAD_OK) return rc;
   PauseHold hold(eng);     // (declared after the call's context: dropped before the context goes back to the pool)
   call.e->hold = &hold;
-  MergeCall mc;
-  mc.keep_from = keep_from_t;
-  call.e->merge = &mc;
+  call.e->merge = mc;
   tad_result *none = nullptr;
   rc = run_job_locked(call.e, &j, cols, TAD_MEM_DEVICE, &none, nullptr, st, 0);
   call.e->merge = nullptr;
+  return rc;
+}
+
+// tad.h: a batch placed by time.
+int tad_state_merge(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, int64_t keep_from_t, tad_merge_stats *stats) {
+  if (stats) memset(stats, 0, sizeof *stats);
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: engine is NULL");
+  if (!st || !job || !cols) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: state, job and cols must not be NULL");
+  MergeCall mc;
+  mc.keep_from = keep_from_t;
+  const int rc = run_merge_call(eng, st, job, cols, "tad_state_merge", &mc);
   if (rc == TAD_OK && stats) *stats = mc.stats;
+  return rc;
+}
+
+// tad.h: a batch that replaces what the state holds, with TAD_REPLACE_RANGE everything the state holds inside [from_t, to_t).
+int tad_state_replace(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, uint32_t flags, int64_t from_t, int64_t to_t,
+                      int64_t keep_from_t, tad_replace_stats *stats) {
+  if (stats) memset(stats, 0, sizeof *stats);
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_state_replace: engine is NULL");
+  if (!st || !job || !cols) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_replace: state, job and cols must not be NULL");
+  if (flags & ~TAD_REPLACE_RANGE) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_replace: unknown flag bits 0x%x", flags & ~TAD_REPLACE_RANGE);
+  const bool ranged = (flags & TAD_REPLACE_RANGE) != 0;
+  if (!ranged && (from_t != 0 || to_t != 0))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_replace: from_t / to_t need TAD_REPLACE_RANGE (without it nothing is erased); state unchanged");
+  if (from_t != 0 && to_t != 0 && from_t > to_t)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_replace: from_t %lld is after to_t %lld; state unchanged", (long long)from_t, (long long)to_t);
+  MergeCall mc;
+  mc.keep_from = keep_from_t;
+  mc.replace = true;
+  mc.ranged = ranged && !(from_t != 0 && from_t == to_t);   // (from_t == to_t non-zero: an empty range)
+  mc.from_t = from_t;
+  mc.to_t = to_t;
+  const int rc = run_merge_call(eng, st, job, cols, "tad_state_replace", &mc);
+  if (rc == TAD_OK && stats) {
+    const tad_merge_stats &m = mc.stats;
+    stats->rows_in = m.rows_in; stats->rows_used = m.rows_used; stats->batch_points = m.batch_points;
+    stats->points_too_old = m.points_too_old; stats->points_appended = m.points_appended; stats->points_inserted = m.points_inserted;
+    stats->points_replaced = m.points_combined; stats->points_erased = mc.erased; stats->keys_emptied = mc.emptied;
+    stats->keys_touched = m.keys_touched; stats->keys_replayed = m.keys_replayed;
+    stats->stage0_path = m.stage0_path; stats->stage0_attempts = m.stage0_attempts; stats->job_context = m.job_context;
+    stats->ms_stage0 = m.ms_stage0; stats->ms_replace = m.ms_merge; stats->ms_total = m.ms_total;
+  }
   return rc;
 }
 

@@ -586,7 +586,9 @@ int count_stream(JobCtx *e, const Job &j, const Attempt &a, StreamBatches *sb, u
   if ((rc = ensure_key_buffers(e, g.K)) != TAD_OK) return rc;
   if (e->merge) {
     e->merge->changed = false;
-    if (g.K && (rc = state_merge_batch(e, stream, g, a.L, a.stream_poff, a.stream_P, P_bound, j.op_max, jp.alpha, e->merge)) != TAD_OK) return rc;
+    if (e->merge->replace) {   // (a replace runs for a batch without a live row too: its range still erases)
+      if (stream->K && (rc = state_replace_batch(e, stream, stream->K, g, a.L, a.stream_poff, a.stream_P, P_bound, jp.alpha, e->merge)) != TAD_OK) return rc;
+    } else if (g.K && (rc = state_merge_batch(e, stream, g, a.L, a.stream_poff, a.stream_P, P_bound, j.op_max, jp.alpha, e->merge)) != TAD_OK) return rc;
   } else if (a.stream_poff)
     launch_stream_points(s, static_cast<const unsigned long long *>(e->sp_comp_a.p), static_cast<const unsigned long long *>(e->sp_val_a.p), a.stream_poff,
                          g.K, a.L.t0, jp.alpha, jp.all_points, false, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),
@@ -732,7 +734,13 @@ int job_merge(JobCtx *e, const Job &j, const Attempt &a, const DevCounters &c, i
   hipEventElapsedTime(&ms.ms_stage0, e->ev[1], e->ev[5]);
   hipEventElapsedTime(&ms.ms_merge, e->ev[5], e->ev[4]);
   hipEventElapsedTime(&ms.ms_total, e->ev[0], e->ev[4]);
-  if (mc->changed) state_commit(stream, stream->ser.len[stream->cur] + mc->added, stream->hist.len[stream->cur] + mc->added);
+  if (mc->changed) {
+    const int old_cur = stream->cur;
+    const uint64_t n_ser = stream->ser.len[old_cur] + mc->added - mc->erased, n_hist = stream->history ? stream->hist.len[old_cur] + mc->added - mc->erased : 0;
+    state_commit(stream, n_ser, n_hist);
+    // (a replace that erased: the old arenas, now the candidates, are given back when far too big for what is left, as after a trim)
+    if (mc->erased) (void)state_size_arenas(e, stream, old_cur, n_ser, n_hist, false, "tad_state_replace");
+  }
   if (j.depth == 0) e->done.store(4);
   return TAD_OK;
 }

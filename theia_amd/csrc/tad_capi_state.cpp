@@ -231,6 +231,10 @@ int state_grow_candidates(JobCtx *e, tad_state *st, uint64_t P_cap) {
   return each_arena(st, [&](auto &a, const Segments &seg, const char *what) { return grow_arena(e, a, cur ^ 1, seg.len[cur] + P_cap, what); });
 }
 
+int state_size_arenas(JobCtx *e, tad_state *st, int i, uint64_t n_ser, uint64_t n_hist, bool allocate, const char *who) {
+  return size_arenas(e, st, i, n_ser, n_hist, allocate, who);
+}
+
 // everything succeeded: the candidate copies, which now hold n_ser series points and n_hist history values, become current
 void state_commit(tad_state *st, uint64_t n_ser, uint64_t n_hist) {
   const int cand = st->cur ^ 1;

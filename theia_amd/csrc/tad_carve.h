@@ -216,7 +216,7 @@ inline WinPts win_pts_layout(Carve &c, uint64_t P, bool dbscan) {
 
 // ---- tad_state_merge (mg_pts, mg_keys) ----
 struct MergeCounters {   // one 64-byte block on the device, zeroed per attempt
-  unsigned long long too_old, appended, inserted, combined, keys_touched, keys_replayed, pad[2];
+  unsigned long long too_old, appended, inserted, combined, keys_touched, keys_replayed, keys_emptied, pad[1];   // keys_emptied: tad_state_replace only
 };
 struct MergePts {   // per batch point (pc = the batch's bound, at least 1)
   unsigned long long *nhoff, *aoff, *roff;            // the three scans (pc + 1 entries used, pc + 2 held)
@@ -262,6 +262,31 @@ inline MergeKeys merge_keys_layout(Carve &c, uint64_t K) {
   m.replay = take_counts(c, K);
   m.long_list = take_counts(c, K);
   return m;
+}
+
+// ---- tad_state_replace (rp_keys, rp_loss), beside a merge's mg_pts / mg_keys ----
+struct ReplaceKeys {   // per key: the erased run [ebeg, eend) of its old segment | the old points it loses without a batch point | their scan | zeros
+  uint32_t *ebeg, *eend, *ecnt;
+  unsigned long long *eoff;
+  unsigned long long *pzero;   // K + 1 zeros: the point offsets of a batch without points
+};
+inline ReplaceKeys replace_keys_layout(Carve &c, uint64_t K) {
+  ReplaceKeys r;
+  r.ebeg = take_counts(c, K);
+  r.eend = take_counts(c, K);
+  r.ecnt = take_counts(c, K);
+  r.eoff = take_offsets(c, K);
+  r.pzero = take_offsets(c, K);
+  return r;
+}
+struct ReplaceLoss {   // the values the history loses (replaced points' old values and erased points), packed per key | sorted per key
+  unsigned long long *hrem, *hrem_s;
+};
+inline ReplaceLoss replace_loss_layout(Carve &c, uint64_t n) {
+  ReplaceLoss l;
+  l.hrem = c.take<unsigned long long>(n);
+  l.hrem_s = c.take<unsigned long long>(n);
+  return l;
 }
 
 // ---- a stream ARIMA batch (as_key, as_pt, as_ser, as_pos, as_fit) ----

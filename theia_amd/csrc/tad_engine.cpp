@@ -114,7 +114,7 @@ int ensure(JobCtx *e, DevBuf &b, size_t bytes) {
 
 // Resolve one kernel of every translation unit: the lazy loader brings the unit's code object onto the device.
 void preload_code_objects() {
-  const void *anchors[] = {code_anchor_arima(), code_anchor_compact(), code_anchor_dbscan(), code_anchor_drop(), code_anchor_drop_select(), code_anchor_drop_state(), code_anchor_factorize(), code_anchor_history(), code_anchor_ingest(), code_anchor_kernels(), code_anchor_keydict(), code_anchor_merge(), code_anchor_shard(), code_anchor_sparse(), code_anchor_stage0_part(), code_anchor_strdict(), code_anchor_synth(), code_anchor_window()};
+  const void *anchors[] = {code_anchor_arima(), code_anchor_compact(), code_anchor_dbscan(), code_anchor_drop(), code_anchor_drop_select(), code_anchor_drop_state(), code_anchor_factorize(), code_anchor_history(), code_anchor_ingest(), code_anchor_kernels(), code_anchor_keydict(), code_anchor_merge(), code_anchor_replace(), code_anchor_shard(), code_anchor_sparse(), code_anchor_stage0_part(), code_anchor_strdict(), code_anchor_synth(), code_anchor_window()};
   for (const void *k : anchors) {
     hipFuncAttributes attr;
     (void)hipFuncGetAttributes(&attr, k);
@@ -219,7 +219,7 @@ int alloc_device_block(JobCtx *e, size_t bytes, ResultBlock *rb) {
 extern "C" {
 
 int tad_abi_version(void) { return TAD_ABI_VERSION; }
-int tad_features(void) { return (int)(TAD_FEATURE_NARROW_COLUMNS | TAD_FEATURE_STREAM_DBSCAN | TAD_FEATURE_STREAM_ARIMA | TAD_FEATURE_STREAM_TRIM | TAD_FEATURE_STATE_RUN | TAD_FEATURE_STATE_MERGE | TAD_FEATURE_STATE_WINDOW | TAD_FEATURE_KEY_DICT | TAD_FEATURE_KEY_RETIRE | TAD_FEATURE_STATE_DROP | TAD_FEATURE_DROP_ROWS | TAD_FEATURE_KEY_SELECT | TAD_FEATURE_STRING_DICT | TAD_FEATURE_DICT_DECODE | TAD_FEATURE_STRING_RETIRE | TAD_FEATURE_STRING_LIKE); }
+int tad_features(void) { return (int)(TAD_FEATURE_NARROW_COLUMNS | TAD_FEATURE_STREAM_DBSCAN | TAD_FEATURE_STREAM_ARIMA | TAD_FEATURE_STREAM_TRIM | TAD_FEATURE_STATE_RUN | TAD_FEATURE_STATE_MERGE | TAD_FEATURE_STATE_REPLACE | TAD_FEATURE_STATE_WINDOW | TAD_FEATURE_KEY_DICT | TAD_FEATURE_KEY_RETIRE | TAD_FEATURE_STATE_DROP | TAD_FEATURE_DROP_ROWS | TAD_FEATURE_KEY_SELECT | TAD_FEATURE_STRING_DICT | TAD_FEATURE_DICT_DECODE | TAD_FEATURE_STRING_RETIRE | TAD_FEATURE_STRING_LIKE); }
 
 const char *tad_last_error(tad_engine *e) {
   if (!e) return g_static_err.c_str();

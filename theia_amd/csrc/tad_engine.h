@@ -88,6 +88,7 @@ struct JobBufs {
   DevBuf hs_key, hs_t, hs_val, hs_sorted, hs_noise, hs_cnt, hs_row, hs_koff, hs_kcnt;   // a history batch: new points, sorted values, verdicts, rows, offsets
   DevBuf wv_key, wv_pts;   // tad_run_state_window's view: per key (bounds, offsets, moments) | per window point (values, times, sorted values)
   DevBuf mg_pts, mg_keys, mg_hist;   // tad_state_merge: per batch point | per key | the history between its subtract and its merge
+  DevBuf rp_keys, rp_loss;           // tad_state_replace, beside a merge's: per key (the erased runs) | the values the history loses, packed and sorted
   DevBuf as_key, as_pt, as_ser, as_fit, as_pos, as_ws;   // a stream ARIMA batch: per key | per new point | packed series | per fit | per position | fit workspace
   DevBuf ds_key, ds_pt;   // tad_drop_state / tad_drop_stream: per key (mean, std, m2, n, ok) | per judged point (verdict, rows, row offset)
   DevBuf dsel;            // tad_drop_select: row bitmask | tile counts | tile offsets | scan scratch | total | a host table's staged columns
@@ -126,12 +127,17 @@ struct JobCtx : JobBufs {
   tadh::Stage0Learnt learnt;   // what the last job of this context learnt about its table (tad_stage0_retry.h)
 };
 
-// one tad_state_merge call: what run_job_locked's merge mode needs beyond the job, and what it reports
+// one tad_state_merge or tad_state_replace call: what run_job_locked's merge mode needs beyond the job, and what it reports
 struct MergeCall {
   int64_t keep_from = 0;
-  tad_merge_stats stats{};
+  tad_merge_stats stats{};   // (a replace: points_combined = the replaced points)
   bool changed = false;    // the candidate copies hold the merged state (false: nothing to merge, the state stays as it is)
   uint64_t added = 0;      // series points gained (inserted + appended)
+  // tad_state_replace: the mode, its range (from_t / to_t 0 = no bound on that side) and what it reports beyond a merge
+  bool replace = false, ranged = false;
+  int64_t from_t = 0, to_t = 0;
+  uint64_t erased = 0;     // series points lost: old points inside the range that the batch does not name
+  uint64_t emptied = 0;    // keys that held points and hold none afterwards
 };
 
 // A double-buffered value arena of a streaming state: two device arrays of T and their capacities in values, indexed like
@@ -443,6 +449,10 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
                          const JobParams &jp, HistBatch *hb);
 int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound, bool op_max,
                       double alpha, MergeCall *mc);
+// the same place in the batch driver for tad_state_replace (mc->replace); K: the state's keys — g.K is 0 for a batch without a live row,
+// which still erases the range
+int state_replace_batch(JobCtx *e, tad_state *st, uint64_t K, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound,
+                        double alpha, MergeCall *mc);
 int stream_arima_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const JobParams &jp, DevCounters *ctr, ArimaBatch *ab);
 int state_drop_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const JobParams &jp, bool touched_only, unsigned long long coop_min,
                      uint32_t *list, unsigned int *lcount, DevCounters *ctr, DropBatch *db);
@@ -481,6 +491,9 @@ StreamState state_view(const tad_state *st, int which);
 StateView series_view(const tad_state *st, int which);       // copy `which` as the detectors of tad_run_state read it
 int state_grow_candidates(JobCtx *e, tad_state *st, uint64_t P_cap);   // room for a batch of at most P_cap new points
 void state_commit(tad_state *st, uint64_t n_ser, uint64_t n_hist); // the candidate copies become current
+// copy `i` of every arena sized for n_ser / n_hist values by tad_state_trim's rule: below a quarter of its capacity it is given back and,
+// with `allocate`, allocated anew at twice the length
+int state_size_arenas(JobCtx *e, tad_state *st, int i, uint64_t n_ser, uint64_t n_hist, bool allocate, const char *who);
 uint64_t state_device_bytes(const tad_state *st);            // tad_state_bytes with the state's lock held
 
 }  // namespace tadh

@@ -437,6 +437,20 @@ void launch_win_gather(hipStream_t s, uint64_t chunks_bound, const unsigned long
 // DBSCAN's window history: true = sort the window's values per key, false = sort the excluded values and subtract them from the state's
 // history.  A pure function of the two totals: 2 * window_points <= state_points
 bool win_hist_by_sort(uint64_t window_points, uint64_t state_points);
+// the classes of a batch point against its key's old times (k_merge_classify; tad_state_replace reads MG_COMBINED as "replaced")
+enum : uint8_t { MG_NONE = 0, MG_TOO_OLD = 1, MG_APPENDED = 2, MG_INSERTED = 3, MG_COMBINED = 4 };
+#if defined(__HIPCC__)
+// first index in the ascending a[lo, hi) whose time is >= t
+__device__ __forceinline__ unsigned long long lower_time(const long long *a, unsigned long long lo, unsigned long long hi, long long t) {
+  while (lo < hi) { const unsigned long long mid = lo + ((hi - lo) >> 1); if (a[mid] < t) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+
+__device__ __forceinline__ void count_wave(bool pred, unsigned lane, unsigned long long *dst) {
+  const unsigned long long m = __ballot(pred);
+  if (lane == 0 && m) atomicAdd(dst, (unsigned long long)__popcll(m));
+}
+#endif
 // ---- tad_state_merge (tad_merge.hip): a batch's points nk / nt / nv (key k's at [poff[k], poff[k + 1])) placed by time ----
 // per point: cls (too old / appended / inserted / combined), rank = the key's old points before it, and the flags of the three scans:
 // f_nh = adds an element (inserted or appended), f_kept = not too old, f_hit = combined; lanes in [*P_dev, P_cap) write zeros
@@ -463,6 +477,24 @@ void launch_merge_series(hipStream_t s, uint64_t chunks_bound, const unsigned lo
 // only gained newer points continued over them.  replay == NULL: no key replays.  Counts keys_touched / keys_replayed
 void launch_merge_moments(hipStream_t s, uint64_t K, const uint32_t *replay, const unsigned long long *soff_old, const unsigned long long *soff_new,
                           const unsigned long long *sval_new, const long long *st_new, double alpha, StreamState cur, StreamState next, MergeCounters *mc);
+// ---- tad_state_replace (tad_replace.hip): the same batch, but it replaces — classified by launch_merge_classify (combined = replaced) ----
+// per key: [ebeg, eend) = the old points with time in [from, to) (0 = no bound on that side), ecnt = those of them no batch point replaces
+void launch_replace_range(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, const unsigned long long *poff, const long long *nt,
+                          const unsigned long long *roff, long long from, long long to, uint32_t *ebeg, uint32_t *eend, uint32_t *ecnt);
+// launch_merge_keys with the erased points: eoff = the scan of ecnt; soff_new = soff_old + nhoff - eoff; rkoff counts the replaced and the
+// erased points; replay[k] = the key has an inserted, replaced or erased point; mc->keys_emptied counts the keys that lose every point
+void launch_replace_keys(hipStream_t s, uint64_t K, const unsigned long long *poff, const unsigned long long *nhoff, const unsigned long long *aoff,
+                         const unsigned long long *roff, const uint8_t *cls, const uint32_t *ecnt, const unsigned long long *eoff,
+                         const unsigned long long *soff_old, const unsigned long long *hoff_old, unsigned long long *soff_new, unsigned long long *akoff,
+                         unsigned long long *rkoff, unsigned long long *hoff_mid, uint32_t *chunks_s, uint32_t *chunks_h, uint32_t *replay, MergeCounters *mc);
+// launch_merge_series with the erased points dropped and a replaced point taking the batch's value.  hadd / hrem (NULL without a history):
+// the values the history gains at aoff[i] / loses, packed per key at rkoff[k] (replaced points first, then the erased ones)
+void launch_replace_series(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *soff_old,
+                           const unsigned long long *sval_old, const long long *st_old, const unsigned long long *poff, const long long *nt,
+                           const unsigned long long *nv, const uint8_t *cls, const uint32_t *rank, const unsigned long long *nhoff,
+                           const unsigned long long *aoff, const unsigned long long *roff, const uint32_t *ebeg, const uint32_t *eend, const uint32_t *ecnt,
+                           long long from, const unsigned long long *rkoff, const unsigned long long *soff_new, unsigned long long *sval_new,
+                           long long *st_new, unsigned long long *hadd, unsigned long long *hrem);
 // ---- streaming ARIMA (tad_arima.hip): a batch on a series state, per touched key (slot) and per new point ----
 struct FitListArgs {
   const uint32_t *wave_pos;          // [waves] position of each wavefront of k_arima_fit_list
@@ -820,6 +852,7 @@ const void *code_anchor_ingest();
 const void *code_anchor_kernels();
 const void *code_anchor_keydict();
 const void *code_anchor_merge();
+const void *code_anchor_replace();
 const void *code_anchor_shard();
 const void *code_anchor_sparse();
 const void *code_anchor_stage0_part();

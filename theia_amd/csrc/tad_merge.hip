@@ -26,18 +26,8 @@ namespace tad {
 
 static constexpr int kMBlock = 256;
 static constexpr uint32_t kMergeChunk = 2048;   // k_merge_series: elements per wavefront (32 per lane), as k_hist_merge
-enum : uint8_t { MG_NONE = 0, MG_TOO_OLD = 1, MG_APPENDED = 2, MG_INSERTED = 3, MG_COMBINED = 4 };
 
-// first index in the ascending a[lo, hi) whose time is >= t
-__device__ __forceinline__ unsigned long long lower_time(const long long *a, unsigned long long lo, unsigned long long hi, long long t) {
-  while (lo < hi) { const unsigned long long mid = lo + ((hi - lo) >> 1); if (a[mid] < t) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-
-__device__ __forceinline__ void count_wave(bool pred, unsigned lane, unsigned long long *dst) {
-  const unsigned long long m = __ballot(pred);
-  if (lane == 0 && m) atomicAdd(dst, (unsigned long long)__popcll(m));
-}
+// (the classes MG_*, lower_time and count_wave are in tad_internal.h: tad_replace.hip shares them)
 
 // ---- 1. classify ----
 // Lanes in [*P_dev, P_cap) write zero flags, so that the scans may run over the host's bound P_cap.

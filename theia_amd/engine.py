@@ -1322,6 +1322,24 @@ class TadEngine:
         self._check(rc)
         return {name: getattr(stats, name) for name, _ in capi.MergeStats._fields_ if not name.startswith("reserved")}
 
+    def replace_stream(self, state, key_id, flow_end_s, value, from_t=0, to_t=0, ranged=False, agg_flow="", value_op="auto", lattice=None,
+                       alpha=0.0, keep_from=0, job_id="", num_keys=None, key_id2=None):
+        """One batch that REPLACES what `state` holds (tad_state_replace): a point at a time its key already holds takes the batch's
+        value instead of being combined with it, so a re-read of the same rows leaves the same state under sum as under max.
+        ranged=True: the batch is ALL rows with from_t <= flowEndSeconds < to_t (0 = no bound on that side), and every point of the
+        state inside that range that the batch does not name is erased, on every key; an empty batch then still erases the range.
+        The other arguments are merge_stream's.  Returns the call's tad_replace_stats as a dict."""
+        self._need("STATE_REPLACE", "tad_state_replace")
+        cols, narrow, keep = self._stream_columns(state, key_id, flow_end_s, value, key_id2, num_keys, lattice)
+        job = capi.Job(algo=capi.TAD_ALGO["EWMA"], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
+                       flags=narrow, id=job_id.encode()[:63])
+        stats = capi.ReplaceStats()
+        rc = self._lib.tad_state_replace(self._h, state._h, C.byref(job), C.byref(cols), capi.TAD_REPLACE_RANGE if ranged else 0, int(from_t),
+                                         int(to_t), int(keep_from), C.byref(stats))
+        del keep
+        self._check(rc)
+        return {name: getattr(stats, name) for name, _ in capi.ReplaceStats._fields_ if not name.startswith("reserved")}
+
     def run_state(self, state, algo="EWMA", alpha=0.0, eps=0.0, min_samples=0, maxiter=0, emit_all=False, out="host", job_id=""):
         """The batch job's verdicts over everything `state` holds, from the state alone (tad_run_state): exactly the rows run() returns
         for the table of the state's series points with the same algo and parameters.  Needs a state with series=True and times=True

@@ -3,7 +3,7 @@
 `anomaly_detection` (anomaly_detection.py) answers one job from the flow table: it reads the rows, applies the job's filters and runs
 the batch job.  A `StreamingAnomalyDetection` is fed the flow rows as they arrive — in any order — and answers the same jobs from what it
 keeps on the device: a key dictionary (KeyDict: the mode's key tuples -> stable ids), a series state (TadState with history and times,
-fed through TadEngine.merge_stream) and one string dictionary per string key column (StringDict: strings -> stable codes, in HBM as
+fed through TadEngine.merge_stream, or TadEngine.replace_stream for a re-read: `feed(flows, replace=...)`, `poll`) and one string dictionary per string key column (StringDict: strings -> stable codes, in HBM as
 well).  Nothing grows on the host: a job's result rows name key ids, and those ids alone are decoded — KeyDict.gather gives their code
 tuples, StringDict.decode the codes' strings (_KeyColumn) — so `snapshot()` / `restore()` of the three device structures is all a restart
 needs.  `retire(idle_before)` keeps all three bounded: it drops the idle keys from the state and the key dictionary and the strings no
@@ -156,6 +156,7 @@ class StreamingAnomalyDetection:
         self._vocab = [self._engine.string_dict() for _ in range(2 if agg_flow == "pod" else 1)]     # pod: namespaces, labels / names
         self._dict = self._engine.key_dict(len(self._vocab))
         self._state = None
+        self.watermark = 0       # poll: the `now` of the last turn (0: no turn yet); carried by snapshot() / restore()
         self._broken = None      # why the instance can no longer be used (retire)
 
     @property
@@ -166,12 +167,20 @@ class StreamingAnomalyDetection:
     def num_keys(self):
         return self._dict.num_keys()
 
-    def feed(self, flows):
+    def feed(self, flows, replace=None):
         """One batch of flow rows (a column dict as anomaly_detection takes it), in any order; rows of a (key, flowEndSeconds) group may
-        be split over feeds.  Returns the merge's statistics (TadEngine.merge_stream), or None when no row passed the row predicates."""
+        be split over feeds.  Returns the merge's statistics (TadEngine.merge_stream), or None when no row passed the row predicates.
+
+        replace=(from_t, to_t): `flows` are ALL rows of this instance with from_t <= flowEndSeconds < to_t (0 = no bound on that
+        side) — a re-read.  They replace what the instance holds for those seconds instead of being added to it
+        (TadEngine.replace_stream with ranged=True): feeding the same range again, or an overlapping one, leaves every point once,
+        where the default feed would double it.  A re-read in which no row passes the row predicates still erases the range.
+        Returns the replace's statistics (None only when there is no state yet and nothing to erase)."""
         self._usable()
         eng = self._engine
         n = len(flows["flowEndSeconds"])
+        if n == 0 and replace is not None:
+            return self._erase(replace)
         keep = np.ones(n, dtype=bool)
         if self.ns_ignore_list:
             ign = np.asarray(list(self.ns_ignore_list), dtype=str)
@@ -185,7 +194,7 @@ class StreamingAnomalyDetection:
                 codes = [_encode(self._vocab[0], flows, side + "PodNamespace"), _encode(self._vocab[1], flows, side + ident)]
                 sides.append((codes, keep & (codes[1] != _code_of(self._vocab[1], ""))))
             if not (sides[0][1].any() or sides[1][1].any()):
-                return None
+                return self._erase(replace)
             key, key2, _, _ = self._dict.encode(sides[0][0], sides[0][1], sides[1][0], sides[1][1], max_new=0)
         else:
             name = "destinationIP" if self.agg_flow == "external" else "destinationServicePortName"
@@ -195,14 +204,48 @@ class StreamingAnomalyDetection:
             else:
                 keep &= codes != _code_of(self._vocab[0], "")
             if not keep.any():
-                return None
+                return self._erase(replace)
             key, key2, _, _ = self._dict.encode([codes], keep, max_new=0)
         num_keys = self.num_keys
         if self._state is None:
             self._state = eng.state_create(num_keys, history=True, series=True, times=True)
         elif num_keys > self._state.num_keys:
             self._state.resize(num_keys)
+        if replace is not None:
+            return eng.replace_stream(self._state, key, flow_end, value, from_t=int(replace[0]), to_t=int(replace[1]), ranged=True,
+                                      agg_flow=self.agg_flow, key_id2=key2)
         return eng.merge_stream(self._state, key, flow_end, value, agg_flow=self.agg_flow, key_id2=key2)
+
+    def _erase(self, replace):
+        """a feed without a live row: nothing to merge; a re-read of a range still says that the range holds nothing"""
+        if replace is None or self._state is None:
+            return None
+        none = np.zeros(0, dtype=np.uint64)
+        return self._engine.replace_stream(self._state, none, np.zeros(0, dtype=np.int64), none, from_t=int(replace[0]), to_t=int(replace[1]),
+                                           ranged=True, agg_flow=self.agg_flow)
+
+    def poll(self, client, now, lag_s):
+        """One turn of the poll loop against the flow table: read the instance's rows with watermark - lag_s <= flowEndSeconds < now
+        (clickhouse.stream_rows_query through `client`, a ClickHouseHTTP), feed them with replace, move the watermark to `now`.  The
+        exporters lag by node and the table is ordered by insertion time, so rows of the last lag_s seconds may still have been
+        missing at the previous turn: they are read again, and because the read REPLACES those seconds a row seen twice counts once.
+        The turn is idempotent: after a timeout or a restart (the watermark travels in snapshot() / restore()) it can simply be made
+        again.  The first turn reads everything before `now`.  Returns the replace's statistics (None: nothing held, nothing read)."""
+        from . import clickhouse as _ch
+        now, lag_s = int(now), int(lag_s)
+        if lag_s < 0:
+            raise ValueError("lag_s must not be negative")
+        from_t = max(self.watermark - lag_s, 0)
+        if from_t >= now:
+            raise ValueError("now (%d) must lie after the watermark less the lag (%d)" % (now, from_t))
+        flows = client.query_columns(_ch.stream_rows_query(self.agg_flow, self.pod_ident, list(self.ns_ignore_list), from_t, now), dict_strings=True)
+        if not flows:      # an empty result carries no batch
+            flows = {c: np.zeros(0, dtype=np.int64 if c.endswith("Seconds") or c in ("flowType", "throughput") else str)
+                     for c in _ch.stream_rows_columns(self.agg_flow, self.pod_ident, list(self.ns_ignore_list))}
+        flows["throughput"] = np.asarray(flows["throughput"]).astype(np.uint64)
+        stats = self.feed(flows, replace=(from_t, now))
+        self.watermark = now
+        return stats
 
     def _equal(self, col, s):
         return col, self._vocab[col].match(_capi.TAD_STR_EQUAL, s, out="device")[0]
@@ -257,7 +300,8 @@ class StreamingAnomalyDetection:
         series, times), the key dictionary's tuples and sides, and every string dictionary's values in Arrow's layout.  `restore` builds
         an instance from it that continues as this one would."""
         self._usable()
-        snap = {"mode": np.asarray([self.mode]), "num_keys": np.asarray([self.num_keys], dtype=np.uint64)}
+        snap = {"mode": np.asarray([self.mode]), "num_keys": np.asarray([self.num_keys], dtype=np.uint64),
+                "watermark": np.asarray([self.watermark], dtype=np.int64)}
         cols, side = self._dict.export()
         for c, col in enumerate(cols):
             snap["key_col%d" % c] = col
@@ -283,6 +327,8 @@ class StreamingAnomalyDetection:
             for i, v in enumerate(self._vocab):
                 v.load((np.asarray(snapshot["vocab%d_offsets" % i]), np.asarray(snapshot["vocab%d_data" % i])))
             self._dict.load([snapshot["key_col%d" % c] for c in range(len(self._vocab))], snapshot["key_side"])
+            if "watermark" in snapshot:      # (a snapshot of before the poll loop has none)
+                self.watermark = int(np.asarray(snapshot["watermark"]).reshape(-1)[0])
             if "state_n" in snapshot:
                 st = self._engine.state_create(len(snapshot["state_n"]), history=True, series=True, times=True)
                 self._state = st

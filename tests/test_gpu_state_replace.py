@@ -259,6 +259,37 @@ def test_chunks_of_2048_and_2049_elements_with_the_run_across_the_edge(engine, f
 
 
 @pytest.mark.parametrize("flags,op", FLAGS_OPS, ids=IDS)
+def test_the_unranged_replace_at_the_chunk_edges(engine, flags, op):
+    """without TAD_REPLACE_RANGE the series kernel runs with the replace rule and no range code: the batches of the ranged edge tests —
+    replaced, inserted and appended points on both sides of every 2048-element chunk edge of keys 3, 6 and 9 — with nothing erased"""
+    rng = np.random.default_rng(18)
+    st0, m0 = loaded(engine, LENS, flags, op, rng)
+    with_batch = [(3, LENS[3]), (6, LENS[6]), (9, LENS[9])]
+    for x, y in RUNS:
+        st, m = clone(engine, st0, m0, flags)
+        rows = edge_batch(rng, flags, op, x, y, with_batch)
+        rep = int(sum(1 for j, s in zip(rows[0].tolist(), rows[1].tolist()) if (s - T0) % 2 == 0 and (s - T0) // 2 < LENS[j]))
+        assert rep >= 1
+        got = replace(engine, st, m, rows, 0, 0, False, tag=(x, y),
+                      expect={"points_replaced": rep, "points_erased": 0, "keys_emptied": 0, "points_too_old": 0})
+        assert got["points_appended"] >= 3 and got["points_inserted"] + got["points_appended"] + rep == got["batch_points"], (x, y, got)
+        st.close()
+    st0.close()
+    # a + b = 2048 (one wavefront) and 2049 (a second one for the last batch point), as the ranged test has them
+    for b in (8, 9):
+        a = 2040
+        st, m = loaded(engine, [a, 7], flags, op, rng)
+        secs = [2 * 2030, 2 * 2039, 2 * 2031 + 1, 2 * 2033 + 1, 2 * 2038 + 1, 2 * a + 1, 2 * a + 3, 2 * a + 9][:8] + ([2 * a + 11] if b == 9 else [])
+        assert a + len(secs) == 2040 + b
+        rows = (np.zeros(len(secs), U64), T0 + np.array(secs, I64), new_values(rng, len(secs), flags, op))
+        o = rng.permutation(len(secs))
+        rows = tuple(c[o] for c in rows)
+        replace(engine, st, m, rows, 0, 0, False, tag=("a + b", a + b),
+                expect={"points_replaced": 2, "points_inserted": 3, "points_appended": b - 5, "points_erased": 0, "keys_emptied": 0})
+        st.close()
+
+
+@pytest.mark.parametrize("flags,op", FLAGS_OPS, ids=IDS)
 def test_keys_emptied_refilled_and_batches_outside_the_range(engine, flags, op):
     rng = np.random.default_rng(16)
     lens = [10, 10, 10, 10, 0, 3000]

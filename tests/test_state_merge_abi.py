@@ -97,3 +97,8 @@ def test_merge_kernels_are_part_of_the_build():
     assert "tad_merge.hip" in build.SOURCES
     src = open(os.path.join(ROOT, "theia_amd", "csrc", "tad_merge.hip")).read()
     assert "asm" not in src and "rocprim" not in src.lower()
+    # every kernel of the merge and of the replace is this unit's: one series kernel, the sum and the maximum among its rules
+    for name in ("k_merge_classify", "k_merge_range", "k_merge_keys", "k_merge_series", "k_merge_moments", "launch_series_as<MERGE_SUM, false>",
+                 "launch_series_as<MERGE_MAX, false>"):
+        assert name in src, name
+    assert not os.path.exists(os.path.join(ROOT, "theia_amd", "csrc", "tad_replace.hip"))

@@ -92,25 +92,34 @@ def test_library_exports_the_symbol_and_refuses_without_a_device():
 
 
 def test_the_kernels_are_hip_in_a_unit_of_their_own_beside_the_merge():
+    """(the name is of before the merge and the replace shared their kernels: the unit is the merge's, tad_merge.hip)"""
     csrc = os.path.join(ROOT, "theia_amd", "csrc")
-    src = open(os.path.join(csrc, "tad_replace.hip")).read()
-    for name in ("k_replace_range", "k_replace_keys", "k_replace_series", "launch_replace_range", "launch_replace_keys", "launch_replace_series",
-                 "code_anchor_replace", "kReplaceChunk = 2048"):
+    assert not os.path.exists(os.path.join(csrc, "tad_replace.hip"))
+    src = open(os.path.join(csrc, "tad_merge.hip")).read()
+    for name in ("k_merge_range", "k_merge_keys", "k_merge_series", "launch_merge_range", "launch_merge_keys", "launch_merge_series",
+                 "code_anchor_merge", "kMergeChunk = 2048", "static_assert(kMergeChunk == kHistChunk"):
         assert name in src, name
     assert "__shared__" not in src and not re.search(r"\basm\b|__asm", src) and "rocprim" not in src.lower() and "hipcub" not in src.lower()
     assert re.findall(r"#include\s+[<\"]([^>\"]+)[>\"]", src) == ["stdint.h", "tad_internal.h"]
     from theia_amd import build
-    assert "tad_replace.hip" in build.SOURCES
+    assert "tad_merge.hip" in build.SOURCES and "tad_replace.hip" not in build.SOURCES
     host = open(os.path.join(csrc, "tad_capi.cpp")).read()
-    body = host[host.index("int state_replace_batch("):host.index("constexpr uint64_t kStreamFitWaves")]
-    # the merge's own classification, scans, history kernels and moments; the erased total is read before anything is written
-    order = ["state_grow_candidates(", "launch_merge_classify(", "launch_replace_range(", "merge_append_path(", "state_size_arenas(", "launch_replace_keys(",
-             "launch_replace_series(", "launch_hist_sort(", "launch_hist_subtract(", "launch_hist_merge(", "launch_merge_moments("]
+    assert "state_replace_batch" not in host                                         # one driver
+    body = host[host.index("int state_merge_batch("):host.index("constexpr uint64_t kStreamFitWaves")]
+    # one classification, one set of scans, history kernels and moments; the erased total is read before anything is written
+    order = ["state_grow_candidates(", "launch_merge_classify(", "launch_merge_range(", "append_batch(", "state_size_arenas(", "launch_merge_keys(",
+             "launch_merge_series(", "launch_hist_sort(", "launch_hist_subtract(", "launch_hist_merge(", "launch_merge_moments("]
     at = [body.index(x) for x in order]
     assert at == sorted(at), list(zip(order, at))
     assert "int tad_state_replace(" in host and "replace_keys_layout" in open(os.path.join(csrc, "tad_carve.h")).read()
-    merge = open(os.path.join(csrc, "tad_merge.hip")).read()
-    assert "x = OP_MAX ? (x > y ? x : y) : x + y;" in merge            # the merge still combines
+    # the merge still combines, the replace assigns the batch's value; a range only comes with the replace rule
+    assert "if constexpr (RULE == MERGE_SUM) return x + y;" in src
+    assert "else if constexpr (RULE == MERGE_MAX) return x > y ? x : y;" in src
+    assert "else return y;" in src
+    assert "x = merge_value<RULE>(x, nv[j]);" in src and "hadd[aoff[j]] = merge_value<RULE>(x, y);" in src
+    assert "static_assert(!RANGED || RULE == MERGE_REPLACE" in src
+    for inst in ("<MERGE_SUM, false>", "<MERGE_MAX, false>", "<MERGE_REPLACE, false>", "<MERGE_REPLACE, true>"):
+        assert src.count("launch_series_as" + inst) == 1, inst
 
 
 class _OldLib:

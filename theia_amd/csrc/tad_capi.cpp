@@ -239,6 +239,28 @@ void emit_point_rows(hipStream_t s, const JobParams &jp, const HistBatch &hb, co
     launch_ds_emit(s, hb.nk, hb.nt, hb.nv, hb.P_dev, hb.P_cap, db.flag, db.cnt, db.row, db.keys, jp.all_points, out);
 }
 
+// A batch's points (key k's nt / nv at [poff[k], poff[k + 1]), at most P_cap) appended to what every key holds, current copies into
+// candidate copies: 2. a history state sorts every key's new values and 3. merges them with its history (tad_history.hip); 3'. a series
+// state appends them to its series, 3''. and their times beside them (the same offsets, written again).  long_list / long_count and
+// chunks / coff: the per-key scratch of the sort and of the merge, in the caller's block.
+static void append_batch(JobCtx *e, tad_state *st, const unsigned long long *poff, const long long *nt, const unsigned long long *nv, uint64_t P_cap,
+                         uint32_t *long_list, unsigned int *long_count, uint32_t *chunks, unsigned long long *coff) {
+  hipStream_t s = e->stream;
+  const uint64_t K = st->K;
+  const int cur = st->cur, cand = cur ^ 1;
+  if (st->history) {
+    unsigned long long *ns = static_cast<unsigned long long *>(e->hs_sorted.p);
+    launch_hist_sort(s, nv, poff, K, ns, long_list, long_count);
+    launch_hist_merge(s, K, st->hist.off[cur], st->hist.val.p[cur], poff, ns, st->hist.off[cand], st->hist.val.p[cand], chunks, coff,
+                      static_cast<unsigned long long *>(e->scan_scratch.p), hist_merge_chunks_bound(K, st->hist.len[cur] + P_cap));
+  }
+  if (st->series)
+    launch_series_append(s, K, st->ser.off[cur], st->ser.val.p[cur], poff, nv, st->ser.off[cand], st->ser.val.p[cand]);
+  if (st->times)
+    launch_series_append(s, K, st->ser.off[cur], reinterpret_cast<const unsigned long long *>(st->ser_times.p[cur]), poff,
+                         reinterpret_cast<const unsigned long long *>(nt), st->ser.off[cand], reinterpret_cast<unsigned long long *>(st->ser_times.p[cand]));
+}
+
 // One batch on a history and / or series state (tad.h, TAD_STATE_HISTORY / TAD_STATE_SERIES), after the stream count pass and before the
 // job's tail is read: the batch's new points in (key, time) order; a history state sorts them per key and merges them with the current
 // history into the candidate arena (tad_history.hip); a series state appends them to every key's series in the candidate arena; a DBSCAN
@@ -255,156 +277,41 @@ int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsi
   BatchKeys bk;
   int rc;
   // the candidate arenas first: an allocation failure leaves the state, its history and its series as they are
-  const uint64_t need = st->hist.len[cur] + P_cap;
   if ((rc = state_grow_candidates(e, st, P_cap)) != TAD_OK) return rc;
   if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr, &bk)) != TAD_OK) return rc;
   if (dbscan && (rc = ensure_hist_verdicts(e, P_cap)) != TAD_OK) return rc;   // (before the first launch: hist_verdicts then allocates nothing)
   unsigned long long *nk = static_cast<unsigned long long *>(e->hs_key.p);
   long long *nt = static_cast<long long *>(e->hs_t.p);
-  unsigned long long *ns = static_cast<unsigned long long *>(e->hs_sorted.p);
-  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
   const unsigned long long *poff, *nv;
   batch_points(e, bk, g, L, sparse_poff, P, &poff, &nv);   // 1.
-  if (st->history) {   // 2. every key's new values sorted; 3. merged with its history into the candidate arena
-    launch_hist_sort(s, nv, poff, K, ns, bk.kcnt, bk.long_count);
-    launch_hist_merge(s, K, st->hist.off[cur], st->hist.val.p[cur], poff, ns, st->hist.off[cand], st->hist.val.p[cand], bk.kcnt, bk.coff, scratch,
-                      hist_merge_chunks_bound(K, need));
-  }
-  if (st->series)      // 3'. appended to its series in the candidate arena
-    launch_series_append(s, K, st->ser.off[cur], st->ser.val.p[cur], poff, nv, st->ser.off[cand], st->ser.val.p[cand]);
-  if (st->times)       // 3''. and their times beside them (the same offsets, written again)
-    launch_series_append(s, K, st->ser.off[cur], reinterpret_cast<const unsigned long long *>(st->ser_times.p[cur]), poff,
-                         reinterpret_cast<const unsigned long long *>(nt), st->ser.off[cand], reinterpret_cast<unsigned long long *>(st->ser_times.p[cand]));
+  append_batch(e, st, poff, nt, nv, P_cap, bk.kcnt, bk.long_count, bk.kcnt, bk.coff);   // 2. to 3''. (the sort's long list, then the merge's chunk counts, in kcnt)
   HIP_TRY(e, hipMemcpyAsync(static_cast<unsigned char *>(e->counters.p) + kTailHistLen, poff + K, 8, hipMemcpyDeviceToDevice, s));
   hb->nk = nk; hb->nt = nt; hb->nv = nv; hb->poff = poff; hb->P_dev = poff + K; hb->P_cap = P_cap;
   // 4. verdicts of the new points against the merged history; 5. their rows
   return dbscan ? hist_verdicts(e, st->hist.off[cand], st->hist.val.p[cand], jp, hb) : TAD_OK;
 }
 
-// The append path of a merge or replace whose points are all newer than what their keys held: stream_history_batch's steps 2, 3, 3', 3''
-// into the candidate copies, then the moments continued from the stored state (no key replays).
-static void merge_append_path(JobCtx *e, tad_state *st, uint64_t K, const unsigned long long *poff, const long long *nt, const unsigned long long *nv,
-                              uint64_t P_cap, double alpha, const MergeKeys &mk, MergeCounters *mcnt) {
-  hipStream_t s = e->stream;
-  const int cur = st->cur, cand = cur ^ 1;
-  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
-  if (st->history) {
-    unsigned long long *ns = static_cast<unsigned long long *>(e->hs_sorted.p);
-    launch_hist_sort(s, nv, poff, K, ns, mk.long_list, mk.long_count);
-    launch_hist_merge(s, K, st->hist.off[cur], st->hist.val.p[cur], poff, ns, st->hist.off[cand], st->hist.val.p[cand], mk.chunks_h, mk.coff_h, scratch,
-                      hist_merge_chunks_bound(K, st->hist.len[cur] + P_cap));
-  }
-  launch_series_append(s, K, st->ser.off[cur], st->ser.val.p[cur], poff, nv, st->ser.off[cand], st->ser.val.p[cand]);
-  launch_series_append(s, K, st->ser.off[cur], reinterpret_cast<const unsigned long long *>(st->ser_times.p[cur]), poff,
-                       reinterpret_cast<const unsigned long long *>(nt), st->ser.off[cand], reinterpret_cast<unsigned long long *>(st->ser_times.p[cand]));
-  launch_merge_moments(s, K, nullptr, st->ser.off[cur], st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], alpha, state_view(st, cur),
-                       state_view(st, cand), mcnt);
+// the candidate copy of a series state's series and times, as a merge writes it
+static MergeInto candidate_series(const tad_state *st) {
+  const int cand = st->cur ^ 1;
+  MergeInto m;
+  m.soff = st->ser.off[cand]; m.sval = st->ser.val.p[cand]; m.st = st->ser_times.p[cand];
+  return m;
 }
 
-// One tad_state_merge batch (tad.h; kernels in tad_merge.hip), in the place of a stream batch's count pass: the batch's points in (key, time)
-// order are classified against the current series, then either appended as a stream batch appends them (nothing inserted, combined or
-// too old) or merged by time into the candidate series, times, history and moments.  Writes candidate memory and context workspace only;
-// mc->changed tells run_job_locked whether the candidates are to become current.  One host round trip: the Stage-0 error word and the
-// classification's counters; a Stage-0 error leaves the rest undone (run_job_locked retries or reports it).
+// One tad_state_merge or tad_state_replace batch (tad.h; kernels in tad_merge.hip), in the place of a stream batch's count pass: the batch's
+// points in (key, time) order are classified against the current series, then either appended as a stream batch appends them (nothing
+// inserted, combined, too old or erased) or merged by time into the candidate series, times, history and moments.  A point at a time its
+// key holds is combined with the held value (op_max: the maximum, else the sum) or, mc->replace, takes its place; with mc->ranged every
+// old point of every key inside [from_t, to_t) that the batch does not name is erased — by a batch without a live row (g.K == 0) or
+// without points too.  Writes candidate memory and context workspace only; mc->changed tells run_job_locked whether the candidates are to
+// become current.  One host round trip for the Stage-0 error word and the classification's counters — a Stage-0 error leaves the rest
+// undone (run_job_locked retries or reports it) — and, ranged, a second one for the erased total: the append path and the arena sizes hang
+// on it, and it is read before anything is written.
 int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound, bool op_max,
                       double alpha, MergeCall *mc) {
   hipStream_t s = e->stream;
-  const uint64_t K = g.K;
-  const int cur = st->cur, cand = cur ^ 1;
-  const uint64_t P_cap = sparse_poff ? P : P_bound;
-  const uint64_t pc = P_cap ? P_cap : 1;
-  const uint64_t S = st->ser.len[cur], H = st->hist.len[cur];
-  BatchKeys bk;
-  MergePts mp;
-  MergeKeys mk;
-  int rc;
-  mc->changed = false;
-  mc->added = 0;
-  // the candidate arenas first: an allocation failure leaves the state as it is
-  if ((rc = state_grow_candidates(e, st, P_cap)) != TAD_OK) return rc;
-  if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr, &bk)) != TAD_OK) return rc;
-  if ((rc = carve_buf(e, e->mg_pts, &mp, merge_pts_layout, pc)) != TAD_OK) return rc;
-  if ((rc = carve_buf(e, e->mg_keys, &mk, merge_keys_layout, K)) != TAD_OK) return rc;
-  MergeCounters *mcnt = mk.mcnt;
-  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
-  const unsigned long long *nk = static_cast<const unsigned long long *>(e->hs_key.p);
-  const long long *nt = static_cast<const long long *>(e->hs_t.p);
-  const unsigned long long *poff, *nv;
-  batch_points(e, bk, g, L, sparse_poff, P, &poff, &nv);
-  // 1. classify; the one round trip: Stage 0's error word, the point count, the classification's counters
-  HIP_TRY(e, hipMemsetAsync(mcnt, 0, sizeof(MergeCounters), s));
-  launch_merge_classify(s, nk, nt, poff + K, P_cap, K, st->ser.off[cur], st->ser_times.p[cur], (long long)mc->keep_from, mp.cls, mp.rank, mp.f_nh, mp.f_kept, mp.f_hit, mcnt);
-  unsigned char *hm = e->tail_host + kTailMoments;   // (the moment partials' place in the pinned tail: a merge has none)
-  HIP_TRY(e, hipMemcpyAsync(e->ctr_host, e->counters.p, sizeof(DevCounters), hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipMemcpyAsync(hm + sizeof(MergeCounters), poff + K, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipStreamSynchronize(s));
-  HIP_TRY(e, hipGetLastError());
-  if (e->ctr_host->err != 0) return TAD_OK;
-  MergeCounters c;
-  unsigned long long points = 0;
-  memcpy(&c, hm, sizeof c);
-  memcpy(&points, hm + sizeof c, 8);
-  tad_merge_stats &ms = mc->stats;
-  ms.batch_points = points;
-  ms.points_too_old = c.too_old;
-  ms.points_appended = c.appended;
-  ms.points_inserted = c.inserted;
-  ms.points_combined = c.combined;
-  ms.keys_touched = ms.keys_replayed = 0;
-  if (c.appended + c.inserted + c.combined == 0) return TAD_OK;   // nothing to merge: the state stays as it is
-  if (c.inserted == 0 && c.combined == 0 && c.too_old == 0) {
-    // 6. every point is newer than what its key held: the append path of a stream batch
-    merge_append_path(e, st, K, poff, nt, nv, P_cap, alpha, mk, mcnt);
-  } else {
-    if (st->history && c.combined && (rc = ensure(e, e->mg_hist, (H ? H : 1) * 8)) != TAD_OK) return rc;
-    // 2. the scans; per key: candidate offsets, the history's packed gains / losses, chunk counts, who replays
-    launch_scan(s, mp.f_nh, mp.nhoff, P_cap, scratch);
-    launch_scan(s, mp.f_kept, mp.aoff, P_cap, scratch);
-    launch_scan(s, mp.f_hit, mp.roff, P_cap, scratch);
-    launch_merge_keys(s, K, poff, mp.nhoff, mp.aoff, mp.roff, mp.cls, st->ser.off[cur], st->history ? st->hist.off[cur] : nullptr, st->ser.off[cand], mk.akoff, mk.rkoff,
-                      mk.hoff_mid, mk.chunks_s, mk.chunks_h, mk.replay);
-    launch_scan(s, mk.chunks_s, mk.coff_s, K, scratch);
-    // 3. series and times merged by time (and the history's gains and losses packed)
-    launch_merge_series(s, merge_chunks_bound(K, S + P_cap), mk.coff_s, K, op_max, st->ser.off[cur], st->ser.val.p[cur], st->ser_times.p[cur], poff, nt, nv, mp.cls, mp.rank,
-                        mp.nhoff, mp.aoff, mp.roff, st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], st->history ? mp.hadd : nullptr, st->history ? mp.hrem : nullptr);
-    if (st->history) {   // 4. the combined points' old values leave the history (through the scratch arena), then the batch's values enter
-      const unsigned long long *hoff_from = st->hist.off[cur], *hval_from = st->hist.val.p[cur];
-      if (c.combined) {
-        unsigned long long *hmid = static_cast<unsigned long long *>(e->mg_hist.p);
-        launch_hist_sort(s, mp.hrem, mk.rkoff, K, mp.hrem_s, mk.long_list, mk.long_count);
-        launch_scan(s, mk.chunks_h, mk.coff_h, K, scratch);
-        // (mk.chunks_h gives an empty key no chunk: not the one-chunk-at-least counts of a trim)
-        launch_hist_subtract(s, trim_chunks_bound(K, H), mk.coff_h, K, st->hist.off[cur], st->hist.val.p[cur], mk.rkoff, mp.hrem_s, mk.hoff_mid, hmid, false);
-        hoff_from = mk.hoff_mid;
-        hval_from = hmid;
-      }
-      launch_hist_sort(s, mp.hadd, mk.akoff, K, mp.hadd_s, mk.long_list, mk.long_count);
-      launch_hist_merge(s, K, hoff_from, hval_from, mk.akoff, mp.hadd_s, st->hist.off[cand], st->hist.val.p[cand], mk.chunks_h, mk.coff_h, scratch,
-                        hist_merge_chunks_bound(K, H + P_cap));
-    }
-    // 5. the moments
-    launch_merge_moments(s, K, mk.replay, st->ser.off[cur], st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], alpha, state_view(st, cur),
-                         state_view(st, cand), mcnt);
-  }
-  HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipStreamSynchronize(s));
-  HIP_TRY(e, hipGetLastError());
-  memcpy(&c, hm, sizeof c);
-  ms.keys_touched = c.keys_touched;
-  ms.keys_replayed = c.keys_replayed;
-  mc->changed = true;
-  mc->added = c.inserted + c.appended;
-  return TAD_OK;
-}
-
-// One tad_state_replace batch (tad.h; kernels in tad_replace.hip), state_merge_batch's twin: the same classification, but a point at a
-// time its key holds takes the batch's value, and with mc->ranged every old point of every key inside [from_t, to_t) that the batch does
-// not name is erased.  K: the state's keys; g.K == 0 (a batch without a live row) or a batch without points still erases the range.  Two
-// host round trips when ranged: the classification's counters, then the erased total (the append path and the arena sizes hang on it).
-int state_replace_batch(JobCtx *e, tad_state *st, uint64_t K, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound,
-                        double alpha, MergeCall *mc) {
-  hipStream_t s = e->stream;
+  const uint64_t K = st->K;   // (== g.K, the batch's keys, unless the batch has no live row)
   const int cur = st->cur, cand = cur ^ 1;
   const bool no_batch = g.K == 0;
   const uint64_t P_cap = no_batch ? 0 : (sparse_poff ? P : P_bound);
@@ -413,7 +320,7 @@ int state_replace_batch(JobCtx *e, tad_state *st, uint64_t K, Grid g, Lattice L,
   BatchKeys bk;
   MergePts mp;
   MergeKeys mk;
-  ReplaceKeys rk;
+  ReplaceKeys rk{};
   int rc;
   mc->changed = false;
   mc->added = mc->erased = mc->emptied = 0;
@@ -422,25 +329,31 @@ int state_replace_batch(JobCtx *e, tad_state *st, uint64_t K, Grid g, Lattice L,
   if ((rc = ensure_batch_points(e, K, P_cap, sparse_poff != nullptr, &bk)) != TAD_OK) return rc;
   if ((rc = carve_buf(e, e->mg_pts, &mp, merge_pts_layout, pc)) != TAD_OK) return rc;
   if ((rc = carve_buf(e, e->mg_keys, &mk, merge_keys_layout, K)) != TAD_OK) return rc;
-  if ((rc = carve_buf(e, e->rp_keys, &rk, replace_keys_layout, K)) != TAD_OK) return rc;
   MergeCounters *mcnt = mk.mcnt;
   unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
-  const unsigned long long *nk = static_cast<const unsigned long long *>(e->hs_key.p);
-  const long long *nt = static_cast<const long long *>(e->hs_t.p);
-  const unsigned long long *poff = rk.pzero, *nv = nullptr;
-  {   // the erased runs and their scan are all zero until the range kernel says otherwise; pzero stays zero
-    Carve measure(nullptr);
-    replace_keys_layout(measure, K);
-    HIP_TRY(e, hipMemsetAsync(e->rp_keys.p, 0, measure.bytes(), s));
+  HistBatch hb;
+  hb.nk = static_cast<const unsigned long long *>(e->hs_key.p);
+  hb.nt = static_cast<const long long *>(e->hs_t.p);
+  if (mc->replace) {   // the erased runs and their scan are all zero until the range kernel says otherwise; pzero stays zero
+    if ((rc = carve_buf(e, e->rp_keys, &rk, replace_keys_layout, K)) != TAD_OK) return rc;
+    HIP_TRY(e, hipMemsetAsync(e->rp_keys.p, 0, carved_bytes(replace_keys_layout, K), s));
+    hb.poff = rk.pzero;
   }
-  if (!no_batch) batch_points(e, bk, g, L, sparse_poff, P, &poff, &nv);
+  if (!no_batch) batch_points(e, bk, g, L, sparse_poff, P, &hb.poff, &hb.nv);
+  hb.P_dev = hb.poff + K;
+  hb.P_cap = P_cap;
+  const StateView old = series_view(st, cur);
+  MergeInto into = candidate_series(st);
+  MergeRule how;
+  how.replace = mc->replace; how.op_max = op_max;
+  if (mc->ranged) { how.range = &rk; how.from = (long long)mc->from_t; how.to = (long long)mc->to_t; }
   // 1. classify; the first round trip: Stage 0's error word, the point count, the classification's counters
   HIP_TRY(e, hipMemsetAsync(mcnt, 0, sizeof(MergeCounters), s));
-  launch_merge_classify(s, nk, nt, poff + K, P_cap, K, st->ser.off[cur], st->ser_times.p[cur], (long long)mc->keep_from, mp.cls, mp.rank, mp.f_nh, mp.f_kept, mp.f_hit, mcnt);
-  unsigned char *hm = e->tail_host + kTailMoments;   // (the moment partials' place in the pinned tail: a replace has none)
+  launch_merge_classify(s, hb, old, (long long)mc->keep_from, mp, mcnt);
+  unsigned char *hm = e->tail_host + kTailMoments;   // (the moment partials' place in the pinned tail: a merge has none)
   HIP_TRY(e, hipMemcpyAsync(e->ctr_host, e->counters.p, sizeof(DevCounters), hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
-  HIP_TRY(e, hipMemcpyAsync(hm + sizeof(MergeCounters), poff + K, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(hm + sizeof(MergeCounters), hb.P_dev, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipStreamSynchronize(s));
   HIP_TRY(e, hipGetLastError());
   if (e->ctr_host->err != 0) return TAD_OK;
@@ -455,11 +368,11 @@ int state_replace_batch(JobCtx *e, tad_state *st, uint64_t K, Grid g, Lattice L,
   ms.points_inserted = c.inserted;
   ms.points_combined = c.combined;
   ms.keys_touched = ms.keys_replayed = 0;
-  // 2. the scan of the replaced points, the erased runs (the poff the points came with is sound: Stage 0 raised no error), their scan;
-  //    the second round trip: the erased total
-  launch_scan(s, mp.f_hit, mp.roff, P_cap, scratch);
+  // 2. a replace scans its replaced points here (the poff the points came with is sound: Stage 0 raised no error): the erased runs of a
+  //    range on a state that holds points count them; then the runs' scan and the second round trip: the erased total
+  if (mc->replace) launch_scan(s, mp.f_hit, mp.roff, P_cap, scratch);
   if (mc->ranged && S != 0) {
-    launch_replace_range(s, K, st->ser.off[cur], st->ser_times.p[cur], poff, nt, mp.roff, (long long)mc->from_t, (long long)mc->to_t, rk.ebeg, rk.eend, rk.ecnt);
+    launch_merge_range(s, hb, old, mp, how);
     launch_scan(s, rk.ecnt, rk.eoff, K, scratch);
     HIP_TRY(e, hipMemcpyAsync(hm, rk.eoff + K, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(e, hipStreamSynchronize(s));
@@ -468,35 +381,44 @@ int state_replace_batch(JobCtx *e, tad_state *st, uint64_t K, Grid g, Lattice L,
   }
   if (c.appended + c.inserted + c.combined + erased == 0) return TAD_OK;   // nothing to place, nothing to erase: the state stays as it is
   const uint64_t added = c.inserted + c.appended;
-  if (c.inserted == 0 && c.combined == 0 && c.too_old == 0 && erased == 0) {
-    // every point is newer than what its key held and nothing leaves: the append path of a stream batch, as a merge takes it
-    merge_append_path(e, st, K, poff, nt, nv, P_cap, alpha, mk, mcnt);
+  // every point is newer than what its key held and nothing leaves: the append path of a stream batch, the moments continued from the
+  // stored state (no key replays)
+  const bool append = c.inserted == 0 && c.combined == 0 && c.too_old == 0 && erased == 0;
+  if (append) {
+    append_batch(e, st, hb.poff, hb.nt, hb.nv, P_cap, mk.long_list, mk.long_count, mk.chunks_h, mk.coff_h);
   } else {
-    const uint64_t lost = c.combined + erased;
-    const uint64_t n_ser = S + added - erased, n_hist = H + added - erased;
-    ReplaceLoss rl{nullptr, nullptr};
-    if (erased && (rc = state_size_arenas(e, st, cand, n_ser, st->history ? n_hist : 0, true, "tad_state_replace")) != TAD_OK) return rc;
-    if (st->history && lost) {
-      if ((rc = ensure(e, e->mg_hist, (H ? H : 1) * 8)) != TAD_OK) return rc;
-      if ((rc = carve_buf(e, e->rp_loss, &rl, replace_loss_layout, lost)) != TAD_OK) return rc;
+    const uint64_t lost = c.combined + erased;   // values that leave the history
+    unsigned long long *hrem_s = mp.hrem_s;
+    if (erased) {   // (a state that shrinks may give arenas back: the candidate copies anew)
+      if ((rc = state_size_arenas(e, st, cand, S + added - erased, st->history ? H + added - erased : 0, true, "tad_state_replace")) != TAD_OK) return rc;
+      into = candidate_series(st);
     }
-    // the scans; per key: candidate offsets, the history's packed gains / losses, chunk counts, who replays, who is emptied
+    if (st->history) {
+      into.hrem = mp.hrem;
+      if (lost && (rc = ensure(e, e->mg_hist, (H ? H : 1) * 8)) != TAD_OK) return rc;
+      if (lost && mc->replace) {   // (a replace's losses may outnumber the batch's points: a block of their own)
+        ReplaceLoss rl;
+        if ((rc = carve_buf(e, e->rp_loss, &rl, replace_loss_layout, lost)) != TAD_OK) return rc;
+        into.hrem = rl.hrem;
+        hrem_s = rl.hrem_s;
+      }
+    }
+    // 3. the remaining scans; per key: candidate offsets, the history's packed gains / losses, chunk counts, who replays, who is emptied
     launch_scan(s, mp.f_nh, mp.nhoff, P_cap, scratch);
     launch_scan(s, mp.f_kept, mp.aoff, P_cap, scratch);
-    launch_replace_keys(s, K, poff, mp.nhoff, mp.aoff, mp.roff, mp.cls, rk.ecnt, rk.eoff, st->ser.off[cur], st->history ? st->hist.off[cur] : nullptr,
-                        st->ser.off[cand], mk.akoff, mk.rkoff, mk.hoff_mid, mk.chunks_s, mk.chunks_h, mk.replay, mcnt);
+    if (!mc->replace) launch_scan(s, mp.f_hit, mp.roff, P_cap, scratch);
+    launch_merge_keys(s, hb, old, into, mp, mk, how);
     launch_scan(s, mk.chunks_s, mk.coff_s, K, scratch);
-    // 3. series and times (and the history's gains and losses packed)
-    launch_replace_series(s, merge_chunks_bound(K, S + P_cap), mk.coff_s, K, st->ser.off[cur], st->ser.val.p[cur], st->ser_times.p[cur], poff, nt, nv, mp.cls,
-                          mp.rank, mp.nhoff, mp.aoff, mp.roff, rk.ebeg, rk.eend, rk.ecnt, mc->ranged ? (long long)mc->from_t : 0ll, mk.rkoff, st->ser.off[cand],
-                          st->ser.val.p[cand], st->ser_times.p[cand], st->history ? mp.hadd : nullptr, st->history ? (lost ? rl.hrem : mp.hrem) : nullptr);
-    if (st->history) {   // 4. the replaced and erased values leave the history (through the scratch arena), then the batch's values enter
+    // 4. series and times merged by time (and the history's gains and losses packed)
+    launch_merge_series(s, hb, old, into, mp, mk, how);
+    if (st->history) {   // 5. the combined and erased values leave the history (through the scratch arena), then the batch's values enter
       const unsigned long long *hoff_from = st->hist.off[cur], *hval_from = st->hist.val.p[cur];
       if (lost) {
         unsigned long long *hmid = static_cast<unsigned long long *>(e->mg_hist.p);
-        launch_hist_sort(s, rl.hrem, mk.rkoff, K, rl.hrem_s, mk.long_list, mk.long_count);
+        launch_hist_sort(s, into.hrem, mk.rkoff, K, hrem_s, mk.long_list, mk.long_count);
         launch_scan(s, mk.chunks_h, mk.coff_h, K, scratch);
-        launch_hist_subtract(s, trim_chunks_bound(K, H), mk.coff_h, K, st->hist.off[cur], st->hist.val.p[cur], mk.rkoff, rl.hrem_s, mk.hoff_mid, hmid, false);
+        // (mk.chunks_h gives an empty key no chunk: not the one-chunk-at-least counts of a trim)
+        launch_hist_subtract(s, trim_chunks_bound(K, H), mk.coff_h, K, st->hist.off[cur], st->hist.val.p[cur], mk.rkoff, hrem_s, mk.hoff_mid, hmid, false);
         hoff_from = mk.hoff_mid;
         hval_from = hmid;
       }
@@ -504,10 +426,9 @@ int state_replace_batch(JobCtx *e, tad_state *st, uint64_t K, Grid g, Lattice L,
       launch_hist_merge(s, K, hoff_from, hval_from, mk.akoff, mp.hadd_s, st->hist.off[cand], st->hist.val.p[cand], mk.chunks_h, mk.coff_h, scratch,
                         hist_merge_chunks_bound(K, H + P_cap));
     }
-    // 5. the moments
-    launch_merge_moments(s, K, mk.replay, st->ser.off[cur], st->ser.off[cand], st->ser.val.p[cand], st->ser_times.p[cand], alpha, state_view(st, cur),
-                         state_view(st, cand), mcnt);
   }
+  // 6. the moments
+  launch_merge_moments(s, old, into, append ? nullptr : mk.replay, alpha, state_view(st, cand), mcnt);
   HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipStreamSynchronize(s));
   HIP_TRY(e, hipGetLastError());
@@ -670,7 +591,7 @@ int tad_drop_stream(tad_engine *eng, tad_state *st, const tad_job *job, const ta
 }
 
 // what tad_state_merge and tad_state_replace refuse alike (who: the call's name), then the batch run as a stream batch does up to the end
-// of Stage 0 (run_job_locked with the context's merge mode set) and state_merge_batch / state_replace_batch in the count pass's place
+// of Stage 0 (run_job_locked with the context's merge mode set) and state_merge_batch in the count pass's place
 static int run_merge_call(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, const char *who, MergeCall *mc) {
   if (!st->series || !st->times)
     return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the state must keep its series with times (TAD_STATE_SERIES | TAD_STATE_TIMES): "

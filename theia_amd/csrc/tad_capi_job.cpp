@@ -586,9 +586,10 @@ int count_stream(JobCtx *e, const Job &j, const Attempt &a, StreamBatches *sb, u
   if ((rc = ensure_key_buffers(e, g.K)) != TAD_OK) return rc;
   if (e->merge) {
     e->merge->changed = false;
-    if (e->merge->replace) {   // (a replace runs for a batch without a live row too: its range still erases)
-      if (stream->K && (rc = state_replace_batch(e, stream, stream->K, g, a.L, a.stream_poff, a.stream_P, P_bound, jp.alpha, e->merge)) != TAD_OK) return rc;
-    } else if (g.K && (rc = state_merge_batch(e, stream, g, a.L, a.stream_poff, a.stream_P, P_bound, j.op_max, jp.alpha, e->merge)) != TAD_OK) return rc;
+    // (a replace runs for a batch without a live row, a merge does not: a replace's range still erases)
+    if ((e->merge->replace ? stream->K : g.K) != 0 &&
+        (rc = state_merge_batch(e, stream, g, a.L, a.stream_poff, a.stream_P, P_bound, j.op_max, jp.alpha, e->merge)) != TAD_OK)
+      return rc;
   } else if (a.stream_poff)
     launch_stream_points(s, static_cast<const unsigned long long *>(e->sp_comp_a.p), static_cast<const unsigned long long *>(e->sp_val_a.p), a.stream_poff,
                          g.K, a.L.t0, jp.alpha, jp.all_points, false, state_view(stream, stream->cur), state_view(stream, stream->cur ^ 1),

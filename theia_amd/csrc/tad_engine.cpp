@@ -114,7 +114,7 @@ int ensure(JobCtx *e, DevBuf &b, size_t bytes) {
 
 // Resolve one kernel of every translation unit: the lazy loader brings the unit's code object onto the device.
 void preload_code_objects() {
-  const void *anchors[] = {code_anchor_arima(), code_anchor_compact(), code_anchor_dbscan(), code_anchor_drop(), code_anchor_drop_select(), code_anchor_drop_state(), code_anchor_factorize(), code_anchor_history(), code_anchor_ingest(), code_anchor_kernels(), code_anchor_keydict(), code_anchor_merge(), code_anchor_replace(), code_anchor_shard(), code_anchor_sparse(), code_anchor_stage0_part(), code_anchor_strdict(), code_anchor_synth(), code_anchor_window()};
+  const void *anchors[] = {code_anchor_arima(), code_anchor_compact(), code_anchor_dbscan(), code_anchor_drop(), code_anchor_drop_select(), code_anchor_drop_state(), code_anchor_factorize(), code_anchor_history(), code_anchor_ingest(), code_anchor_kernels(), code_anchor_keydict(), code_anchor_merge(), code_anchor_shard(), code_anchor_sparse(), code_anchor_stage0_part(), code_anchor_strdict(), code_anchor_synth(), code_anchor_window()};
   for (const void *k : anchors) {
     hipFuncAttributes attr;
     (void)hipFuncGetAttributes(&attr, k);

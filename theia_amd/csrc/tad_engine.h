@@ -412,17 +412,6 @@ int finish_result(JobCtx *e, ResultPriv *rp, uint64_t rows, bool with_anomaly, R
 // (any_points), n_anomalies (TAD_FLAG_EMIT_ALL_POINTS: the verdicts counted), the context, the id.
 int finish_rows(JobCtx *e, const tad_job *job, RowsOut *ro, uint64_t rows, bool with_anomaly, const DevCounters &c, bool any_points);
 
-// What a batch on a history or series state leaves for its emit: the new points in (key, time) order and, for DBSCAN, their verdicts and rows.
-struct HistBatch {
-  const unsigned long long *nk = nullptr, *nv = nullptr;
-  const long long *nt = nullptr;
-  const unsigned long long *poff = nullptr;    // key k's new points at [poff[k], poff[k + 1])
-  const unsigned long long *P_dev = nullptr;   // the number of new points (device)
-  uint64_t P_cap = 0;                          // its bound on the host (exact for a sparse batch)
-  const uint8_t *noise = nullptr;
-  const uint32_t *cnt = nullptr;
-  const unsigned long long *row = nullptr;
-};
 // What a stream ARIMA batch leaves for its emit (stream_arima_batch)
 struct ArimaBatch {
   uint64_t P = 0;
@@ -447,12 +436,10 @@ void emit_point_rows(hipStream_t s, const JobParams &jp, const HistBatch &hb, co
                      OutRows out);
 int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound,
                          const JobParams &jp, HistBatch *hb);
+// tad_state_merge and tad_state_replace (mc->replace) in the count pass's place; K = the state's keys: a replace runs for a batch
+// without a live row too (g.K == 0), which still erases the range
 int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound, bool op_max,
                       double alpha, MergeCall *mc);
-// the same place in the batch driver for tad_state_replace (mc->replace); K: the state's keys — g.K is 0 for a batch without a live row,
-// which still erases the range
-int state_replace_batch(JobCtx *e, tad_state *st, uint64_t K, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound,
-                        double alpha, MergeCall *mc);
 int stream_arima_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const JobParams &jp, DevCounters *ctr, ArimaBatch *ab);
 int state_drop_batch(JobCtx *e, const StateView &v, const HistBatch &hb, const JobParams &jp, bool touched_only, unsigned long long coop_min,
                      uint32_t *list, unsigned int *lcount, DevCounters *ctr, DropBatch *db);

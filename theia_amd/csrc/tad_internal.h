@@ -422,6 +422,18 @@ struct StateView {
                        // state's, not the window's newest time: the detectors of run_view_locked read neither, a stream-style kernel must not
   const unsigned long long *hoff = nullptr, *hval = nullptr;
 };
+// What a batch on a history or series state leaves for its emit, and what a merge places: the new points in (key, time) order and, for
+// DBSCAN, their verdicts and rows.
+struct HistBatch {
+  const unsigned long long *nk = nullptr, *nv = nullptr;
+  const long long *nt = nullptr;
+  const unsigned long long *poff = nullptr;    // key k's new points at [poff[k], poff[k + 1])
+  const unsigned long long *P_dev = nullptr;   // the number of new points (device)
+  uint64_t P_cap = 0;                          // its bound on the host (exact for a sparse batch)
+  const uint8_t *noise = nullptr;
+  const uint32_t *cnt = nullptr;
+  const unsigned long long *row = nullptr;
+};
 // ---- tad_run_state_window (tad_window.hip): the view of every key's points inside a window ----
 // per key: wbeg = the window's first point inside the key's segment, wlen = its points, ecnt = the key's points outside it (prefix +
 // suffix), chunks = the wavefronts of the key's old segment in launch_win_gather / launch_hist_subtract (at least 1).  from_t / to_t 0 = no bound on
@@ -437,64 +449,43 @@ void launch_win_gather(hipStream_t s, uint64_t chunks_bound, const unsigned long
 // DBSCAN's window history: true = sort the window's values per key, false = sort the excluded values and subtract them from the state's
 // history.  A pure function of the two totals: 2 * window_points <= state_points
 bool win_hist_by_sort(uint64_t window_points, uint64_t state_points);
-// the classes of a batch point against its key's old times (k_merge_classify; tad_state_replace reads MG_COMBINED as "replaced")
-enum : uint8_t { MG_NONE = 0, MG_TOO_OLD = 1, MG_APPENDED = 2, MG_INSERTED = 3, MG_COMBINED = 4 };
-#if defined(__HIPCC__)
-// first index in the ascending a[lo, hi) whose time is >= t
-__device__ __forceinline__ unsigned long long lower_time(const long long *a, unsigned long long lo, unsigned long long hi, long long t) {
-  while (lo < hi) { const unsigned long long mid = lo + ((hi - lo) >> 1); if (a[mid] < t) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-
-__device__ __forceinline__ void count_wave(bool pred, unsigned lane, unsigned long long *dst) {
-  const unsigned long long m = __ballot(pred);
-  if (lane == 0 && m) atomicAdd(dst, (unsigned long long)__popcll(m));
-}
-#endif
-// ---- tad_state_merge (tad_merge.hip): a batch's points nk / nt / nv (key k's at [poff[k], poff[k + 1])) placed by time ----
+// ---- tad_state_merge and tad_state_replace (tad_merge.hip): a batch's points (key k's at [poff[k], poff[k + 1])) placed by time ----
+// What a merge writes: the candidate series offsets (K + 1), values and times, and hrem = the packed values the history loses (NULL
+// without a history: then nothing is packed for it, mp.hadd neither)
+struct MergeInto {
+  unsigned long long *soff = nullptr, *sval = nullptr;
+  long long *st = nullptr;
+  unsigned long long *hrem = nullptr;
+};
+// What a batch point does to the value its key holds at that time — the sum, the maximum or (replace) the batch's value — and the range
+// [from, to) of a replace (0 = no bound on that side) with its per-key runs; range == NULL: nothing is erased
+struct MergeRule {
+  bool replace = false, op_max = false;
+  const ReplaceKeys *range = nullptr;
+  long long from = 0, to = 0;
+};
 // per point: cls (too old / appended / inserted / combined), rank = the key's old points before it, and the flags of the three scans:
 // f_nh = adds an element (inserted or appended), f_kept = not too old, f_hit = combined; lanes in [*P_dev, P_cap) write zeros
-void launch_merge_classify(hipStream_t s, const unsigned long long *nk, const long long *nt, const unsigned long long *P_dev, uint64_t P_cap, uint64_t K,
-                           const unsigned long long *soff, const long long *st, long long keep_from, uint8_t *cls, uint32_t *rank, uint32_t *f_nh,
-                           uint32_t *f_kept, uint32_t *f_hit, MergeCounters *mc);
-// nhoff / aoff / roff = the scans of f_nh / f_kept / f_hit.  soff_new (K + 1) = the candidate series offsets; chunks_s[k] = the key's
-// wavefronts in launch_merge_series; replay[k] = the key has an inserted or combined point.  hoff_old != NULL (history states): akoff /
-// rkoff (K + 1) = the packed per-key offsets of the values the history gains / loses, hoff_mid = hoff_old - rkoff, chunks_h[k] = the
-// wavefronts of the key's old history
-void launch_merge_keys(hipStream_t s, uint64_t K, const unsigned long long *poff, const unsigned long long *nhoff, const unsigned long long *aoff,
-                       const unsigned long long *roff, const uint8_t *cls, const unsigned long long *soff_old, const unsigned long long *hoff_old,
-                       unsigned long long *soff_new, unsigned long long *akoff, unsigned long long *rkoff, unsigned long long *hoff_mid, uint32_t *chunks_s,
-                       uint32_t *chunks_h, uint32_t *replay);
+void launch_merge_classify(hipStream_t s, const HistBatch &b, const StateView &old, long long keep_from, const MergePts &mp, MergeCounters *mc);
+// per key, after the scan roff: [ebeg, eend) = the old points with time in [from, to), ecnt = those of them no batch point replaces
+void launch_merge_range(hipStream_t s, const HistBatch &b, const StateView &old, const MergePts &mp, const MergeRule &how);
+// nhoff / aoff / roff = the scans of f_nh / f_kept / f_hit; with a range eoff = the scan of ecnt.  into.soff = soff_old + nhoff - eoff;
+// chunks_s[k] = the key's wavefronts in launch_merge_series; replay[k] = the key has an inserted, combined or erased point;
+// mk.mcnt->keys_emptied counts the keys that lose every point (with a range only).  old.hoff != NULL (history states): akoff / rkoff
+// (K + 1) = the packed per-key offsets of the values the history gains / loses (combined and erased), hoff_mid = hoff_old - rkoff,
+// chunks_h[k] = the wavefronts of the key's old history.  Empty keys have no chunk
+void launch_merge_keys(hipStream_t s, const HistBatch &b, const StateView &old, const MergeInto &into, const MergePts &mp, const MergeKeys &mk,
+                       const MergeRule &how);
 uint64_t merge_chunks_bound(uint64_t K, uint64_t total_len);   // total_len = old series points + batch points
-// every key's old points and batch points merged by time into sval_new / st_new; a combined point's value is op(old, new).  hadd / hrem
-// (NULL without a history): the values the history gains at aoff[i] / loses at roff[i]
-void launch_merge_series(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, bool op_max, const unsigned long long *soff_old,
-                         const unsigned long long *sval_old, const long long *st_old, const unsigned long long *poff, const long long *nt,
-                         const unsigned long long *nv, const uint8_t *cls, const uint32_t *rank, const unsigned long long *nhoff,
-                         const unsigned long long *aoff, const unsigned long long *roff, const unsigned long long *soff_new, unsigned long long *sval_new,
-                         long long *st_new, unsigned long long *hadd, unsigned long long *hrem);
-// next = cur for the untouched keys; a key with replay[k] replayed with stream_step over its merged series from the zero state; a key that
-// only gained newer points continued over them.  replay == NULL: no key replays.  Counts keys_touched / keys_replayed
-void launch_merge_moments(hipStream_t s, uint64_t K, const uint32_t *replay, const unsigned long long *soff_old, const unsigned long long *soff_new,
-                          const unsigned long long *sval_new, const long long *st_new, double alpha, StreamState cur, StreamState next, MergeCounters *mc);
-// ---- tad_state_replace (tad_replace.hip): the same batch, but it replaces — classified by launch_merge_classify (combined = replaced) ----
-// per key: [ebeg, eend) = the old points with time in [from, to) (0 = no bound on that side), ecnt = those of them no batch point replaces
-void launch_replace_range(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, const unsigned long long *poff, const long long *nt,
-                          const unsigned long long *roff, long long from, long long to, uint32_t *ebeg, uint32_t *eend, uint32_t *ecnt);
-// launch_merge_keys with the erased points: eoff = the scan of ecnt; soff_new = soff_old + nhoff - eoff; rkoff counts the replaced and the
-// erased points; replay[k] = the key has an inserted, replaced or erased point; mc->keys_emptied counts the keys that lose every point
-void launch_replace_keys(hipStream_t s, uint64_t K, const unsigned long long *poff, const unsigned long long *nhoff, const unsigned long long *aoff,
-                         const unsigned long long *roff, const uint8_t *cls, const uint32_t *ecnt, const unsigned long long *eoff,
-                         const unsigned long long *soff_old, const unsigned long long *hoff_old, unsigned long long *soff_new, unsigned long long *akoff,
-                         unsigned long long *rkoff, unsigned long long *hoff_mid, uint32_t *chunks_s, uint32_t *chunks_h, uint32_t *replay, MergeCounters *mc);
-// launch_merge_series with the erased points dropped and a replaced point taking the batch's value.  hadd / hrem (NULL without a history):
-// the values the history gains at aoff[i] / loses, packed per key at rkoff[k] (replaced points first, then the erased ones)
-void launch_replace_series(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *soff_old,
-                           const unsigned long long *sval_old, const long long *st_old, const unsigned long long *poff, const long long *nt,
-                           const unsigned long long *nv, const uint8_t *cls, const uint32_t *rank, const unsigned long long *nhoff,
-                           const unsigned long long *aoff, const unsigned long long *roff, const uint32_t *ebeg, const uint32_t *eend, const uint32_t *ecnt,
-                           long long from, const unsigned long long *rkoff, const unsigned long long *soff_new, unsigned long long *sval_new,
-                           long long *st_new, unsigned long long *hadd, unsigned long long *hrem);
+// every key's old points and batch points merged by time into the candidate series; a combined point's value is how's rule of (old, new),
+// the erased points are dropped.  History states: the values the history gains at mp.hadd[aoff[i]], the ones it loses packed per key at
+// rkoff[k] in into.hrem (combined points' old values first, then the erased points)
+void launch_merge_series(hipStream_t s, const HistBatch &b, const StateView &old, const MergeInto &into, const MergePts &mp, const MergeKeys &mk,
+                         const MergeRule &how);
+// next = old.mom for the untouched keys; a key with replay[k] replayed with stream_step over its merged series from the zero state; a key
+// that only gained newer points continued over them.  replay == NULL: no key replays.  Counts keys_touched / keys_replayed
+void launch_merge_moments(hipStream_t s, const StateView &old, const MergeInto &into, const uint32_t *replay, double alpha, StreamState next,
+                          MergeCounters *mc);
 // ---- streaming ARIMA (tad_arima.hip): a batch on a series state, per touched key (slot) and per new point ----
 struct FitListArgs {
   const uint32_t *wave_pos;          // [waves] position of each wavefront of k_arima_fit_list
@@ -852,7 +843,6 @@ const void *code_anchor_ingest();
 const void *code_anchor_kernels();
 const void *code_anchor_keydict();
 const void *code_anchor_merge();
-const void *code_anchor_replace();
 const void *code_anchor_shard();
 const void *code_anchor_sparse();
 const void *code_anchor_stage0_part();

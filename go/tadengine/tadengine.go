@@ -22,6 +22,7 @@ import "C"
 import (
 	"errors"
 	"fmt"
+	"math"
 	"runtime"
 	"sync"
 	"unsafe"
@@ -1143,34 +1144,11 @@ func (s *State) Merge(job Job, cols Columns, keepFrom int64) (MergeStats, error)
 	if !s.series || !s.times {
 		return MergeStats{}, IllegalArgument{"tadengine: Merge needs a state made by NewStateWithTimes"}
 	}
-	bufs, n, narrow, err := columnBuffers(cols)
+	cj, cc, free, err := batchCall(job, cols)
 	if err != nil {
 		return MergeStats{}, err
 	}
-	defer freeBuffers(bufs)
-	var cj C.tad_job
-	cj.flags = narrow
-	cj.algo = C.TAD_ALGO_EWMA
-	cj.agg_flow = C.tad_agg_flow(job.AggFlow)
-	cj.value_op = C.TAD_OP_AUTO
-	cj.start_time = C.int64_t(job.StartTime)
-	cj.end_time = C.int64_t(job.EndTime)
-	id := []byte(job.ID)
-	if len(id) > 63 {
-		id = id[:63]
-	}
-	for i, b := range id {
-		cj.id[i] = C.char(b)
-	}
-	var cc C.tad_columns
-	cc.n_rows = C.uint64_t(n)
-	cc.num_keys = C.uint64_t(cols.NumKeys)
-	cc.memory = C.TAD_MEM_HOST
-	cc.key_id = (*C.uint64_t)(bufs[0])
-	cc.key_id2 = (*C.uint64_t)(bufs[1])
-	cc.flow_end_s = (*C.int64_t)(bufs[2])
-	cc.flow_start_s = (*C.int64_t)(bufs[3])
-	cc.value = (*C.uint64_t)(bufs[4])
+	defer free()
 	var ms C.tad_merge_stats
 	if rc := C.tad_state_merge(s.e.h, s.h, &cj, &cc, C.int64_t(keepFrom), &ms); rc != C.TAD_OK {
 		msg := C.GoString(C.tad_last_error(s.e.h))
@@ -1222,34 +1200,11 @@ func (s *State) Replace(job Job, cols Columns, ranged bool, fromT, toT, keepFrom
 	if !s.series || !s.times {
 		return ReplaceStats{}, IllegalArgument{"tadengine: Replace needs a state made by NewStateWithTimes"}
 	}
-	bufs, n, narrow, err := columnBuffers(cols)
+	cj, cc, free, err := batchCall(job, cols)
 	if err != nil {
 		return ReplaceStats{}, err
 	}
-	defer freeBuffers(bufs)
-	var cj C.tad_job
-	cj.flags = narrow
-	cj.algo = C.TAD_ALGO_EWMA
-	cj.agg_flow = C.tad_agg_flow(job.AggFlow)
-	cj.value_op = C.TAD_OP_AUTO
-	cj.start_time = C.int64_t(job.StartTime)
-	cj.end_time = C.int64_t(job.EndTime)
-	id := []byte(job.ID)
-	if len(id) > 63 {
-		id = id[:63]
-	}
-	for i, b := range id {
-		cj.id[i] = C.char(b)
-	}
-	var cc C.tad_columns
-	cc.n_rows = C.uint64_t(n)
-	cc.num_keys = C.uint64_t(cols.NumKeys)
-	cc.memory = C.TAD_MEM_HOST
-	cc.key_id = (*C.uint64_t)(bufs[0])
-	cc.key_id2 = (*C.uint64_t)(bufs[1])
-	cc.flow_end_s = (*C.int64_t)(bufs[2])
-	cc.flow_start_s = (*C.int64_t)(bufs[3])
-	cc.value = (*C.uint64_t)(bufs[4])
+	defer free()
 	var flags C.uint32_t
 	if ranged {
 		flags = C.TAD_REPLACE_RANGE
@@ -1884,19 +1839,8 @@ func (d *KeyDict) Select(terms []SelectTerm, side int32, numKeys uint64) (keep [
 	return keep, uint64(n), nil
 }
 
-// RunKeys is RunWindow over the keys keyKeep selects, read-only (tad_run_state_keys): one byte per key of the state, any non-zero byte
-// selects; nil is RunWindow itself.  The rows are exactly those of RunWindow whose key is selected, with the state's own key ids; a key
-// that is not selected costs no fit.
-func (s *State) RunKeys(job Job, fromT, toT int64, keepPoints uint64, keyKeep []byte) ([]Row, error) {
-	if !hasKeySelect() {
-		return nil, errors.New("tadengine: libtad_mi355x.so has no tad_run_state_keys (TAD_FEATURE_KEY_SELECT)")
-	}
-	if !s.series || !s.times {
-		return nil, IllegalArgument{"tadengine: RunKeys needs a state made by NewStateWithTimes"}
-	}
-	if job.Algo == DBSCAN && !s.history {
-		return nil, IllegalArgument{"tadengine: RunKeys with DBSCAN needs a state made by NewStateWithTimes with history"}
-	}
+// keysJob: the tad_job of a detector over selected keys of a state (RunKeys, RunSince).
+func keysJob(job Job) C.tad_job {
 	var cj C.tad_job
 	cj.algo = C.tad_algo(job.Algo)
 	cj.start_time = C.int64_t(job.StartTime)
@@ -1910,6 +1854,23 @@ func (s *State) RunKeys(job Job, fromT, toT int64, keepPoints uint64, keyKeep []
 	for i, b := range id {
 		cj.id[i] = C.char(b)
 	}
+	return cj
+}
+
+// RunKeys is RunWindow over the keys keyKeep selects, read-only (tad_run_state_keys): one byte per key of the state, any non-zero byte
+// selects; nil is RunWindow itself.  The rows are exactly those of RunWindow whose key is selected, with the state's own key ids; a key
+// that is not selected costs no fit.
+func (s *State) RunKeys(job Job, fromT, toT int64, keepPoints uint64, keyKeep []byte) ([]Row, error) {
+	if !hasKeySelect() {
+		return nil, errors.New("tadengine: libtad_mi355x.so has no tad_run_state_keys (TAD_FEATURE_KEY_SELECT)")
+	}
+	if !s.series || !s.times {
+		return nil, IllegalArgument{"tadengine: RunKeys needs a state made by NewStateWithTimes"}
+	}
+	if job.Algo == DBSCAN && !s.history {
+		return nil, IllegalArgument{"tadengine: RunKeys with DBSCAN needs a state made by NewStateWithTimes with history"}
+	}
+	cj := keysJob(job)
 	var kp *C.uint8_t
 	if len(keyKeep) > 0 {
 		kp = (*C.uint8_t)(unsafe.Pointer(&keyKeep[0]))
@@ -1947,6 +1908,244 @@ func (s *State) DropKeys(job Job, nSigma float64, minSamples int32, fromT, toT i
 			return nil, IllegalArgument{msg}
 		}
 		return nil, fmt.Errorf("tad_drop_state_keys: %s (code %d)", msg, int(rc))
+	}
+	return s.resultRows(res), nil
+}
+
+var stateAlertsOnce sync.Once
+var stateAlertsOK bool
+
+// hasStateAlerts: the library knows the change report and the since calls (tad_features); an older one would not export them.
+func hasStateAlerts() bool {
+	stateAlertsOnce.Do(func() { stateAlertsOK = C.tad_features()&C.TAD_FEATURE_STATE_ALERTS != 0 })
+	return stateAlertsOK
+}
+
+var errNoStateAlerts = errors.New("tadengine: libtad_mi355x.so has no change report (TAD_FEATURE_STATE_ALERTS)")
+
+// NoChange marks a key of Changes.KeySince whose series did not change (TAD_NO_CHANGE).
+const NoChange = int64(math.MaxInt64)
+
+// Changes is what a MergeChanges or a ReplaceChanges changed (tad_changes): KeySince[k] is the smallest flowEndSeconds at which key k's
+// series changed — a point added, erased, or given another value — and NoChange where it did not.  A sum of 0, a maximum not above the
+// held value and a replace by the held value change nothing: the same Replace twice reports KeysChanged == 0 the second time.
+type Changes struct {
+	KeySince      []int64
+	KeysChanged   uint64
+	PointsChanged uint64
+	MinT, MaxT    int64 // 0, 0 when PointsChanged == 0
+}
+
+// batchCall: the tad_job and tad_columns of a merge or a replace — Merge, Replace and their *Changes forms; free releases the column buffers.
+func batchCall(job Job, cols Columns) (cj C.tad_job, cc C.tad_columns, free func(), err error) {
+	bufs, n, narrow, err := columnBuffers(cols)
+	if err != nil {
+		return cj, cc, func() {}, err
+	}
+	cj.flags = narrow
+	cj.algo = C.TAD_ALGO_EWMA
+	cj.agg_flow = C.tad_agg_flow(job.AggFlow)
+	cj.value_op = C.TAD_OP_AUTO
+	cj.start_time = C.int64_t(job.StartTime)
+	cj.end_time = C.int64_t(job.EndTime)
+	id := []byte(job.ID)
+	if len(id) > 63 {
+		id = id[:63]
+	}
+	for i, b := range id {
+		cj.id[i] = C.char(b)
+	}
+	cc.n_rows = C.uint64_t(n)
+	cc.num_keys = C.uint64_t(cols.NumKeys)
+	cc.memory = C.TAD_MEM_HOST
+	cc.key_id = (*C.uint64_t)(bufs[0])
+	cc.key_id2 = (*C.uint64_t)(bufs[1])
+	cc.flow_end_s = (*C.int64_t)(bufs[2])
+	cc.flow_start_s = (*C.int64_t)(bufs[3])
+	cc.value = (*C.uint64_t)(bufs[4])
+	return cj, cc, func() { freeBuffers(bufs) }, nil
+}
+
+// newChanges: a report with one entry per key of the batch's key space (which must be the state's), in C memory so that the library
+// may write it; done copies it out and frees it.
+func newChanges(numKeys uint64) (ch C.tad_changes, done func() Changes) {
+	var p unsafe.Pointer
+	if numKeys > 0 {
+		p = C.malloc(C.size_t(numKeys * 8))
+	}
+	ch.key_since = (*C.int64_t)(p)
+	ch.len = C.uint64_t(numKeys)
+	ch.memory = C.TAD_MEM_HOST
+	return ch, func() Changes {
+		out := Changes{KeySince: make([]int64, numKeys), KeysChanged: uint64(ch.keys_changed), PointsChanged: uint64(ch.points_changed),
+			MinT: int64(ch.min_t), MaxT: int64(ch.max_t)}
+		if numKeys > 0 {
+			copy(out.KeySince, unsafe.Slice((*int64)(p), numKeys))
+			C.free(p)
+		}
+		return out
+	}
+}
+
+// MergeChanges is Merge that also reports what it changed (tad_state_merge_changes).
+func (s *State) MergeChanges(job Job, cols Columns, keepFrom int64) (MergeStats, Changes, error) {
+	if !hasStateAlerts() {
+		return MergeStats{}, Changes{}, errNoStateAlerts
+	}
+	if !s.series || !s.times {
+		return MergeStats{}, Changes{}, IllegalArgument{"tadengine: MergeChanges needs a state made by NewStateWithTimes"}
+	}
+	cj, cc, free, err := batchCall(job, cols)
+	if err != nil {
+		return MergeStats{}, Changes{}, err
+	}
+	defer free()
+	ch, done := newChanges(cols.NumKeys)
+	var ms C.tad_merge_stats
+	rc := C.tad_state_merge_changes(s.e.h, s.h, &cj, &cc, C.int64_t(keepFrom), &ms, &ch)
+	changes := done()
+	if rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return MergeStats{}, Changes{}, IllegalArgument{msg}
+		}
+		return MergeStats{}, Changes{}, fmt.Errorf("tad_state_merge_changes: %s (code %d)", msg, int(rc))
+	}
+	return MergeStats{RowsIn: uint64(ms.rows_in), RowsUsed: uint64(ms.rows_used), BatchPoints: uint64(ms.batch_points),
+		PointsTooOld: uint64(ms.points_too_old), PointsAppended: uint64(ms.points_appended), PointsInserted: uint64(ms.points_inserted),
+		PointsCombined: uint64(ms.points_combined), KeysTouched: uint64(ms.keys_touched), KeysReplayed: uint64(ms.keys_replayed),
+		MsTotal: float32(ms.ms_total)}, changes, nil
+}
+
+// ReplaceChanges is Replace that also reports what it changed (tad_state_replace_changes): the poll loop's alerts come from RunSince
+// with the report's KeySince, and a turn made twice reports no changed key the second time.
+func (s *State) ReplaceChanges(job Job, cols Columns, ranged bool, fromT, toT, keepFrom int64) (ReplaceStats, Changes, error) {
+	if !hasStateAlerts() {
+		return ReplaceStats{}, Changes{}, errNoStateAlerts
+	}
+	if !s.series || !s.times {
+		return ReplaceStats{}, Changes{}, IllegalArgument{"tadengine: ReplaceChanges needs a state made by NewStateWithTimes"}
+	}
+	cj, cc, free, err := batchCall(job, cols)
+	if err != nil {
+		return ReplaceStats{}, Changes{}, err
+	}
+	defer free()
+	var flags C.uint32_t
+	if ranged {
+		flags = C.TAD_REPLACE_RANGE
+	}
+	ch, done := newChanges(cols.NumKeys)
+	var rs C.tad_replace_stats
+	rc := C.tad_state_replace_changes(s.e.h, s.h, &cj, &cc, flags, C.int64_t(fromT), C.int64_t(toT), C.int64_t(keepFrom), &rs, &ch)
+	changes := done()
+	if rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return ReplaceStats{}, Changes{}, IllegalArgument{msg}
+		}
+		return ReplaceStats{}, Changes{}, fmt.Errorf("tad_state_replace_changes: %s (code %d)", msg, int(rc))
+	}
+	return ReplaceStats{RowsIn: uint64(rs.rows_in), RowsUsed: uint64(rs.rows_used), BatchPoints: uint64(rs.batch_points),
+		PointsTooOld: uint64(rs.points_too_old), PointsAppended: uint64(rs.points_appended), PointsInserted: uint64(rs.points_inserted),
+		PointsReplaced: uint64(rs.points_replaced), PointsErased: uint64(rs.points_erased), KeysEmptied: uint64(rs.keys_emptied),
+		KeysTouched: uint64(rs.keys_touched), KeysReplayed: uint64(rs.keys_replayed), MsTotal: float32(rs.ms_total)}, changes, nil
+}
+
+// ReportWindow says which of the state's points a RunSince / DropSince judges and which of those it reports (tad_report_window):
+// the window and the key mask of RunKeys; KeySince (one entry per key, or nil) and SinceT (0 = none) name the reported points — those
+// with flowEndSeconds >= SinceT and >= KeySince[key].  A key whose KeySince is NoChange is not selected at all.
+type ReportWindow struct {
+	FromT, ToT int64
+	KeepPoints uint64
+	KeyKeep    []byte
+	KeySince   []int64
+	SinceT     int64
+}
+
+func (w ReportWindow) c() (C.tad_report_window, error) {
+	var cw C.tad_report_window
+	cw.from_t, cw.to_t, cw.keep_points, cw.since_t = C.int64_t(w.FromT), C.int64_t(w.ToT), C.uint64_t(w.KeepPoints), C.int64_t(w.SinceT)
+	cw.key_memory = C.TAD_MEM_HOST
+	if len(w.KeyKeep) > 0 && len(w.KeySince) > 0 && len(w.KeyKeep) != len(w.KeySince) {
+		return cw, IllegalArgument{"tadengine: KeyKeep and KeySince must have one entry per key of the state each"}
+	}
+	if len(w.KeyKeep) > 0 {
+		cw.key_keep = (*C.uint8_t)(unsafe.Pointer(&w.KeyKeep[0]))
+		cw.num_keys = C.uint64_t(len(w.KeyKeep))
+	}
+	if len(w.KeySince) > 0 {
+		cw.key_since = (*C.int64_t)(unsafe.Pointer(&w.KeySince[0]))
+		cw.num_keys = C.uint64_t(len(w.KeySince))
+	}
+	return cw, nil
+}
+
+// RunSince judges the window as RunKeys does and reports from a time on, read-only (tad_run_state_since): exactly the rows of RunKeys
+// with the same window and the effective mask, restricted to the reported points.  Points of a changed key before its first changed
+// time may have changed verdict and are not reported: RunKeys gives the whole answer.
+func (s *State) RunSince(job Job, w ReportWindow) ([]Row, error) {
+	if !hasStateAlerts() {
+		return nil, errNoStateAlerts
+	}
+	if !s.series || !s.times {
+		return nil, IllegalArgument{"tadengine: RunSince needs a state made by NewStateWithTimes"}
+	}
+	if job.Algo == DBSCAN && !s.history {
+		return nil, IllegalArgument{"tadengine: RunSince with DBSCAN needs a state made by NewStateWithTimes with history"}
+	}
+	cj := keysJob(job)
+	cw, err := w.c()
+	if err != nil {
+		return nil, err
+	}
+	var pin runtime.Pinner // (the struct points into Go memory: cgo passes &cw, the slices it names are pinned for the call)
+	defer pin.Unpin()
+	if len(w.KeyKeep) > 0 {
+		pin.Pin(&w.KeyKeep[0])
+	}
+	if len(w.KeySince) > 0 {
+		pin.Pin(&w.KeySince[0])
+	}
+	var res *C.tad_result
+	if rc := C.tad_run_state_since(s.e.h, s.h, &cj, &cw, C.TAD_MEM_HOST, &res); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, IllegalArgument{msg}
+		}
+		return nil, fmt.Errorf("tad_run_state_since: %s (code %d)", msg, int(rc))
+	}
+	return s.resultRows(res), nil
+}
+
+// DropSince is DropKeys that reports from a time on, read-only (tad_drop_state_since); w as for RunSince.
+func (s *State) DropSince(job Job, nSigma float64, minSamples int32, w ReportWindow) ([]Row, error) {
+	if !hasStateAlerts() {
+		return nil, errNoStateAlerts
+	}
+	if !s.series || !s.times {
+		return nil, IllegalArgument{"tadengine: DropSince needs a state made by NewStateWithTimes"}
+	}
+	cj := dropJob(job, nSigma, minSamples)
+	cw, err := w.c()
+	if err != nil {
+		return nil, err
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	if len(w.KeyKeep) > 0 {
+		pin.Pin(&w.KeyKeep[0])
+	}
+	if len(w.KeySince) > 0 {
+		pin.Pin(&w.KeySince[0])
+	}
+	var res *C.tad_result
+	if rc := C.tad_drop_state_since(s.e.h, s.h, &cj, &cw, C.TAD_MEM_HOST, &res); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, IllegalArgument{msg}
+		}
+		return nil, fmt.Errorf("tad_drop_state_since: %s (code %d)", msg, int(rc))
 	}
 	return s.resultRows(res), nil
 }

@@ -676,6 +676,86 @@ typedef struct {
 int tad_state_replace(tad_engine *e, tad_state *s, const tad_job *job, const tad_columns *cols, uint32_t flags, int64_t from_t, int64_t to_t,
                       int64_t keep_from_t, tad_replace_stats *stats /* may be NULL */);
 
+/* ---- what a merge or a replace changed: the change report (TAD_FEATURE_STATE_ALERTS; check tad_features() before calling these) ----
+ * tad_state_merge and tad_state_replace take rows in any order and any number of times, emit nothing and do not say which keys they
+ * changed.  The *_changes forms are the same calls — the same batch, contract, atomicity, stats, refusals, lock order and append path —
+ * and also fill a report.  A NULL report makes them tad_state_merge / tad_state_replace, which are these calls with a NULL report.
+ * Contract: let W be the state's table of points before the call and W' the table after it, as in the two contracts above.  A point of
+ * key k is CHANGED iff it is in exactly one of W and W', or in both with different values: appended and inserted points, the points a
+ * range erased, and combined / replaced points whose stored value differs.  key_since[k] = the smallest flow_end_s of key k's changed
+ * points, TAD_NO_CHANGE when it has none.  What does NOT change a key: a sum merge of value 0 at a held time, a max merge of a value not
+ * above the held one, a replace by the held value — so the same replace twice reports keys_changed == 0 the second time, and a poll
+ * loop that alerts on the report is idempotent, not only its state.  keys_changed <= stats.keys_touched always (a touched key may have
+ * been rewritten with the bits it held).  An empty or all-too-old batch without a range is TAD_OK with every entry TAD_NO_CHANGE and the
+ * counters 0.
+ * The report's memory: key_since is int64[len] in host or device memory (memory), 8-byte aligned, len == the state's num_keys; or NULL
+ * with len == 0 for the counters alone.  Refused (TAD_ERR_INVALID_ARGUMENT, state unchanged): len other than num_keys with an array, a
+ * NULL array with a non-zero len, a misaligned array, a memory that is neither TAD_MEM_HOST nor TAD_MEM_DEVICE.  On any failure the
+ * state is unchanged as without a report, the counters are 0 and the array's content is unspecified (a device array is written in
+ * place while the call runs; a host array is staged in job-context workspace, 8 B per key, and copied out only on success).
+ * Cost: one more lane-per-key fill before and one lane-per-key pass after the series kernel, which reduces the changed elements'
+ * smallest time per wavefront (one 64-bit atomic minimum per 2048-element chunk with a changed element) — and nothing at all, not
+ * even compiled into the kernels it runs, for a call with a NULL report.  No further host round trip: the counters ride on the
+ * call's last copy. */
+#define TAD_FEATURE_STATE_ALERTS 131072u /* tad_state_merge_changes / tad_state_replace_changes, tad_run_state_since / tad_drop_state_since */
+#define TAD_NO_CHANGE INT64_MAX
+typedef struct {
+  int64_t *key_since;                /* out, int64[len]: the smallest flow_end_s at which key k's series changed; TAD_NO_CHANGE = unchanged.
+                                        May be NULL with len == 0: counters only */
+  uint64_t len;                      /* must equal the state's num_keys when key_since != NULL */
+  tad_mem memory;                    /* host or device, any 8-byte aligned address */
+  uint64_t keys_changed;             /* out: keys with key_since != TAD_NO_CHANGE */
+  uint64_t points_changed;           /* out: points added + points removed + points whose value changed */
+  int64_t min_t;                     /* out: smallest changed flow_end_s; 0 when points_changed == 0 */
+  int64_t max_t;                     /* out: largest changed flow_end_s; 0 when points_changed == 0 */
+} tad_changes;
+int tad_state_merge_changes(tad_engine *e, tad_state *s, const tad_job *job, const tad_columns *cols, int64_t keep_from_t,
+                            tad_merge_stats *stats /* may be NULL */, tad_changes *ch /* NULL: tad_state_merge */);
+int tad_state_replace_changes(tad_engine *e, tad_state *s, const tad_job *job, const tad_columns *cols, uint32_t flags, int64_t from_t,
+                              int64_t to_t, int64_t keep_from_t, tad_replace_stats *stats /* may be NULL */,
+                              tad_changes *ch /* NULL: tad_state_replace */);
+
+/* Judge the window, report from a time on (TAD_FEATURE_STATE_ALERTS as well).  tad_run_state_keys / tad_drop_state_keys return every row of
+ * the window again at every call; after a merge or a replace only the points from each changed key's first changed time on are news.
+ * tad_run_state_since (EWMA, DBSCAN, ARIMA) and tad_drop_state_since (DROP) judge the window exactly as the *_keys calls do and REPORT a
+ * part of it.  The report window: from_t / to_t / keep_points are tad_run_state_window's window, key_keep tad_run_state_keys' mask (NULL:
+ * every key); key_since is one int64 per key or NULL — a change report's array as it stands — and since_t one time for all keys (0 =
+ * none); num_keys is the length of the arrays that are given and must equal the state's; key_memory is where both arrays live.
+ * Contract: a point is REPORTED iff it lies in the window, its key is selected, (since_t == 0 || flow_end_s >= since_t) and (key_since ==
+ * NULL || flow_end_s >= key_since[key]).  A key with key_since[k] == TAD_NO_CHANGE counts as NOT SELECTED: the effective mask is key_keep
+ * AND (key_since != TAD_NO_CHANGE), such a key gets an empty window and costs nothing after the bounds.  The call returns exactly the
+ * rows of tad_run_state_keys / tad_drop_state_keys with the same window and the effective mask, restricted to the reported points: the
+ * same order, bit for bit, TAD_FLAG_EMIT_ALL_POINTS included.  Every selected key is still judged over its WHOLE window — EWMA's
+ * recurrence and stddev, DBSCAN's neighbourhood, ARIMA's lambda and fits' histories, DROP's mean and std.  With no since at all (key_since
+ * NULL, since_t 0) the call IS the *_keys call.  Read-only: the state is bit for bit what it was.  A changed key's points BEFORE its
+ * first changed time may have changed verdict too (a late point moves the stddev of the whole key); they are not reported — the stream's
+ * rule, "each point once, when it arrives"; the *_keys calls give the whole answer.
+ * Refusals: the *_keys calls' (algorithm family, start_time / end_time, narrow-column flags, parameter ranges, what the state must
+ * keep, stale times, from_t > to_t, an array in neither memory) plus: a NULL report window, num_keys other than the state's with an
+ * array given, a key_since that is not 8-byte aligned.
+ * tad_stats: rows_in, rows_used, n_points, n_keys and t0 are over the JUDGED points, as the *_keys calls report them; n_anomalies,
+ * keys_no_result and the ARIMA counters cover the keys with at least one reported point, and arima_fits counts the fits actually run —
+ * those of the reported points.  For tad_drop_state_since with a since pts_mean / pts_m2 are 0 (only the keys with a reported point get
+ * their mean and std computed).  host_syncs: tad_run_state_window's — 2, and 3 when bounds, a key_keep or a key_since are set on a
+ * non-empty state — plus one with a since for DBSCAN, ARIMA and DROP (the number of reported points is read before their block is
+ * sized; not when the judged window is empty); EWMA needs none.
+ * How: times ascend per key, so a key's reported points are a suffix of its view segment.  One lane per key finds the suffix's first
+ * index by a lower bound over the view's times; EWMA walks every series as before and counts or emits from that index on; for the
+ * others the suffixes are packed (key, time, value; 24 B per reported point of context workspace, plus about 40 B per key) and go to
+ * the stream batches' detectors as the batch of new points. */
+typedef struct {
+  int64_t from_t;                    /* tad_run_state_window's window */
+  int64_t to_t;
+  uint64_t keep_points;
+  const uint8_t *key_keep;           /* tad_run_state_keys' mask or NULL */
+  const int64_t *key_since;          /* per key or NULL */
+  int64_t since_t;                   /* 0 = none */
+  uint64_t num_keys;                 /* length of the arrays that are given; must equal the state's */
+  tad_mem key_memory;                /* of both arrays */
+} tad_report_window;
+int tad_run_state_since(tad_engine *e, tad_state *s, const tad_job *job, const tad_report_window *w, tad_mem out_memory, tad_result **out);
+int tad_drop_state_since(tad_engine *e, tad_state *s, const tad_job *job, const tad_report_window *w, tad_mem out_memory, tad_result **out);
+
 /* ---- the batch verdicts over a time range of a state (TAD_FEATURE_STATE_WINDOW; check tad_features() before calling this) ----
  * tad_run_state judges everything the state holds, and tad_state_trim narrows a state for good and at its old end only.  A state that
  * keeps seven days can answer "the last 24 h" or "everything up to the last complete hour" with this call: read-only, any window the

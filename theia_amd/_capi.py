@@ -39,6 +39,8 @@ TAD_FEATURE_STRING_DICT = 4096               # tad_features() bit: tad_strdict, 
 TAD_FEATURE_DICT_DECODE = 8192               # tad_features() bit: tad_keydict_gather, tad_strdict_decode: ids -> tuples and codes -> strings on the device
 TAD_FEATURE_STRING_RETIRE = 16384            # tad_features() bit: tad_keydict_mark_codes, tad_strdict_compact, tad_keydict_recode: dead strings dropped, codes renumbered
 TAD_FEATURE_STRING_LIKE = 32768              # tad_features() bit: tad_strdict_like: LIKE / ilike patterns with % and _ matched on the device
+TAD_FEATURE_STATE_ALERTS = 131072            # tad_features() bit: tad_state_merge_changes / tad_state_replace_changes: what a merge or a replace changed; tad_run_state_since / tad_drop_state_since
+TAD_NO_CHANGE = (1 << 63) - 1                # tad_changes.key_since: the key's series did not change
 TAD_LIKE_NOCASE = 1                          # tad_strdict_like flags: compare after folding 'A'..'Z' to 'a'..'z' (ilike)
 TAD_CODE_NONE = -1                           # tad_strdict_lookup: the string is not in the dictionary
 TAD_STR_EQUAL, TAD_STR_CONTAINS_NOCASE = 0, 1   # tad_strdict_match: the value is the pattern / the pattern occurs in it, ASCII letters without case
@@ -137,6 +139,18 @@ class ReplaceStats(C.Structure):
                 ("ms_stage0", f32), ("ms_replace", f32), ("ms_total", f32), ("reserved1", f32)]
 
 
+class Changes(C.Structure):
+    """tad_changes: the change report of tad_state_merge_changes / tad_state_replace_changes."""
+    _fields_ = [("key_since", C.c_void_p), ("len", u64), ("memory", C.c_int), ("keys_changed", u64), ("points_changed", u64),
+                ("min_t", i64), ("max_t", i64)]
+
+
+class ReportWindow(C.Structure):
+    """tad_report_window: the window, the key mask and the since rules of tad_run_state_since / tad_drop_state_since."""
+    _fields_ = [("from_t", i64), ("to_t", i64), ("keep_points", u64), ("key_keep", C.c_void_p), ("key_since", C.c_void_p), ("since_t", i64),
+                ("num_keys", u64), ("key_memory", C.c_int)]
+
+
 class CompactStats(C.Structure):
     """tad_compact_stats: what one tad_state_compact call retired and moved."""
     _fields_ = [("keys_before", u64), ("keys_after", u64), ("num_keys", u64), ("keys_unseen", u64), ("keys_idle", u64), ("points_dropped", u64),
@@ -199,6 +213,9 @@ SYMBOLS = {
     "tad_run_state": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_state_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), i64, C.POINTER(MergeStats)]),
     "tad_state_replace": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_uint32, i64, i64, i64, C.POINTER(ReplaceStats)]),
+    "tad_state_merge_changes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), i64, C.POINTER(MergeStats), C.POINTER(Changes)]),
+    "tad_state_replace_changes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_uint32, i64, i64, i64, C.POINTER(ReplaceStats),
+                                            C.POINTER(Changes)]),
     "tad_run_state_window": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_window_history_by_sort": (C.c_int, [u64, u64]),
     "tad_aggregate": (C.c_int, [C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Points))]),
@@ -235,6 +252,8 @@ SYMBOLS = {
     "tad_keydict_select": (C.c_int, [C.c_void_p, C.c_void_p, i32, C.POINTER(i32), C.POINTER(C.c_void_p), C.POINTER(u64), i32, C.c_void_p, u64, C.c_int, C.POINTER(u64)]),
     "tad_run_state_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_void_p, u64, C.c_int, C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_drop_state_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_void_p, u64, C.c_int, C.c_int, C.POINTER(C.POINTER(Result))]),
+    "tad_run_state_since": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(ReportWindow), C.c_int, C.POINTER(C.POINTER(Result))]),
+    "tad_drop_state_since": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(ReportWindow), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_drop_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_drop_select": (C.c_int, [C.c_void_p, C.POINTER(DropFlowColumns), i64, i64, C.c_int, C.POINTER(C.POINTER(DropRows))]),
     "tad_drop_rows_free": (None, [C.c_void_p, C.POINTER(DropRows)]),

@@ -299,6 +299,20 @@ static MergeInto candidate_series(const tad_state *st) {
   return m;
 }
 
+// tad_state_merge_changes / tad_state_replace_changes: where the report of this attempt is written.  The counters, and the per-key array
+// when the caller's is in host memory (or absent: the changed keys are counted from it), live in context workspace; a device array of
+// the caller's is written in place (on a failure its content is unspecified).
+int merge_report_begin(JobCtx *e, const tad_state *st, MergeCall *mc) {
+  const tad_changes *ch = mc->ch;
+  int rc;
+  mc->report_staged = ch->key_since == nullptr || ch->memory == TAD_MEM_HOST;
+  if ((rc = carve_buf(e, e->mg_report, &mc->report, merge_report_layout, st->K, mc->report_staged)) != TAD_OK) return rc;
+  if (!mc->report_staged) mc->report.since = reinterpret_cast<long long *>(ch->key_since);
+  mc->counted = ChangeCounters{};
+  launch_merge_report_fill(e->stream, st->K, mc->report);
+  return TAD_OK;
+}
+
 // One tad_state_merge or tad_state_replace batch (tad.h; kernels in tad_merge.hip), in the place of a stream batch's count pass: the batch's
 // points in (key, time) order are classified against the current series, then either appended as a stream batch appends them (nothing
 // inserted, combined, too old or erased) or merged by time into the candidate series, times, history and moments.  A point at a time its
@@ -347,6 +361,7 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
   MergeRule how;
   how.replace = mc->replace; how.op_max = op_max;
   if (mc->ranged) { how.range = &rk; how.from = (long long)mc->from_t; how.to = (long long)mc->to_t; }
+  if (mc->ch) how.report = &mc->report;   // (merge_report_begin filled it for this attempt)
   // 1. classify; the first round trip: Stage 0's error word, the point count, the classification's counters
   HIP_TRY(e, hipMemsetAsync(mcnt, 0, sizeof(MergeCounters), s));
   launch_merge_classify(s, hb, old, (long long)mc->keep_from, mp, mcnt);
@@ -386,6 +401,7 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
   const bool append = c.inserted == 0 && c.combined == 0 && c.too_old == 0 && erased == 0;
   if (append) {
     append_batch(e, st, hb.poff, hb.nt, hb.nv, P_cap, mk.long_list, mk.long_count, mk.chunks_h, mk.coff_h);
+    if (how.report) launch_merge_report_keys(s, K, hb.poff, hb.nt, *how.report);   // a key's changed points: its batch segment
   } else {
     const uint64_t lost = c.combined + erased;   // values that leave the history
     unsigned long long *hrem_s = mp.hrem_s;
@@ -411,6 +427,7 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
     launch_scan(s, mk.chunks_s, mk.coff_s, K, scratch);
     // 4. series and times merged by time (and the history's gains and losses packed)
     launch_merge_series(s, hb, old, into, mp, mk, how);
+    if (how.report) launch_merge_report_keys(s, K, nullptr, nullptr, *how.report);
     if (st->history) {   // 5. the combined and erased values leave the history (through the scratch arena), then the batch's values enter
       const unsigned long long *hoff_from = st->hist.off[cur], *hval_from = st->hist.val.p[cur];
       if (lost) {
@@ -430,9 +447,14 @@ int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigne
   // 6. the moments
   launch_merge_moments(s, old, into, append ? nullptr : mk.replay, alpha, state_view(st, cand), mcnt);
   HIP_TRY(e, hipMemcpyAsync(hm, mcnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s));
+  if (how.report) HIP_TRY(e, hipMemcpyAsync(hm + sizeof(MergeCounters), how.report->cc, sizeof(ChangeCounters), hipMemcpyDeviceToHost, s));
   HIP_TRY(e, hipStreamSynchronize(s));
   HIP_TRY(e, hipGetLastError());
   memcpy(&c, hm, sizeof c);
+  if (how.report) {
+    memcpy(&mc->counted, hm + sizeof c, sizeof mc->counted);
+    if (append) mc->counted.points = c.appended;   // (the series kernel, which counts them, did not run)
+  }
   ms.keys_touched = c.keys_touched;
   ms.keys_replayed = c.keys_replayed;
   mc->changed = true;
@@ -622,37 +644,81 @@ static int run_merge_call(tad_engine *eng, tad_state *st, const tad_job *job, co
   return rc;
 }
 
+// what a call with a report refuses about it, before anything runs (the state's num_keys does not change under a call's feet: only
+// tad_state_grow / tad_state_compact change it, and the caller orders those)
+static int check_changes(tad_engine *eng, const tad_state *st, tad_changes *ch, const char *who) {
+  ch->keys_changed = ch->points_changed = 0;
+  ch->min_t = ch->max_t = 0;
+  if (ch->memory != TAD_MEM_HOST && ch->memory != TAD_MEM_DEVICE)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the report's memory must be TAD_MEM_HOST or TAD_MEM_DEVICE; state unchanged", who);
+  if (!ch->key_since && ch->len != 0)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the report's key_since is NULL with len %llu (NULL goes with len 0: counters only); state unchanged", who,
+                (unsigned long long)ch->len);
+  if (ch->key_since && ch->len != st->K)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the report's len is %llu, the state holds %llu keys (they must be equal); state unchanged", who,
+                (unsigned long long)ch->len, (unsigned long long)st->K);
+  if (reinterpret_cast<uintptr_t>(ch->key_since) % 8 != 0)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the report's key_since must be 8-byte aligned; state unchanged", who);
+  return TAD_OK;
+}
+
+// after a successful call: the counters (0, 0 for min_t / max_t without a changed point)
+static void report_counters(const MergeCall &mc, tad_changes *ch) {
+  ch->keys_changed = mc.counted.keys;
+  ch->points_changed = mc.counted.points;
+  if (mc.counted.points != 0) { ch->min_t = mc.counted.min_t; ch->max_t = mc.counted.max_t; }
+}
+
 // tad.h: a batch placed by time.
-int tad_state_merge(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, int64_t keep_from_t, tad_merge_stats *stats) {
+int tad_state_merge_changes(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, int64_t keep_from_t, tad_merge_stats *stats,
+                            tad_changes *ch) {
+  const char *who = ch ? "tad_state_merge_changes" : "tad_state_merge";
   if (stats) memset(stats, 0, sizeof *stats);
-  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: engine is NULL");
-  if (!st || !job || !cols) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_merge: state, job and cols must not be NULL");
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!st || !job || !cols) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: state, job and cols must not be NULL", who);
+  if (ch) {
+    const int crc = check_changes(eng, st, ch, who);
+    if (crc != TAD_OK) return crc;
+  }
   MergeCall mc;
   mc.keep_from = keep_from_t;
-  const int rc = run_merge_call(eng, st, job, cols, "tad_state_merge", &mc);
+  mc.ch = ch;
+  const int rc = run_merge_call(eng, st, job, cols, who, &mc);
   if (rc == TAD_OK && stats) *stats = mc.stats;
+  if (rc == TAD_OK && ch) report_counters(mc, ch);
   return rc;
 }
 
+int tad_state_merge(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, int64_t keep_from_t, tad_merge_stats *stats) {
+  return tad_state_merge_changes(eng, st, job, cols, keep_from_t, stats, nullptr);
+}
+
 // tad.h: a batch that replaces what the state holds, with TAD_REPLACE_RANGE everything the state holds inside [from_t, to_t).
-int tad_state_replace(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, uint32_t flags, int64_t from_t, int64_t to_t,
-                      int64_t keep_from_t, tad_replace_stats *stats) {
+int tad_state_replace_changes(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, uint32_t flags, int64_t from_t,
+                              int64_t to_t, int64_t keep_from_t, tad_replace_stats *stats, tad_changes *ch) {
+  const char *who = ch ? "tad_state_replace_changes" : "tad_state_replace";
   if (stats) memset(stats, 0, sizeof *stats);
-  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "tad_state_replace: engine is NULL");
-  if (!st || !job || !cols) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_replace: state, job and cols must not be NULL");
-  if (flags & ~TAD_REPLACE_RANGE) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_replace: unknown flag bits 0x%x", flags & ~TAD_REPLACE_RANGE);
+  if (!eng) return fail(nullptr, TAD_ERR_INVALID_ARGUMENT, "%s: engine is NULL", who);
+  if (!st || !job || !cols) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: state, job and cols must not be NULL", who);
+  if (ch) {
+    const int crc = check_changes(eng, st, ch, who);
+    if (crc != TAD_OK) return crc;
+  }
+  if (flags & ~TAD_REPLACE_RANGE) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~TAD_REPLACE_RANGE);
   const bool ranged = (flags & TAD_REPLACE_RANGE) != 0;
   if (!ranged && (from_t != 0 || to_t != 0))
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_replace: from_t / to_t need TAD_REPLACE_RANGE (without it nothing is erased); state unchanged");
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: from_t / to_t need TAD_REPLACE_RANGE (without it nothing is erased); state unchanged", who);
   if (from_t != 0 && to_t != 0 && from_t > to_t)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "tad_state_replace: from_t %lld is after to_t %lld; state unchanged", (long long)from_t, (long long)to_t);
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: from_t %lld is after to_t %lld; state unchanged", who, (long long)from_t, (long long)to_t);
   MergeCall mc;
+  mc.ch = ch;
   mc.keep_from = keep_from_t;
   mc.replace = true;
   mc.ranged = ranged && !(from_t != 0 && from_t == to_t);   // (from_t == to_t non-zero: an empty range)
   mc.from_t = from_t;
   mc.to_t = to_t;
-  const int rc = run_merge_call(eng, st, job, cols, "tad_state_replace", &mc);
+  const int rc = run_merge_call(eng, st, job, cols, who, &mc);
+  if (rc == TAD_OK && ch) report_counters(mc, ch);
   if (rc == TAD_OK && stats) {
     const tad_merge_stats &m = mc.stats;
     stats->rows_in = m.rows_in; stats->rows_used = m.rows_used; stats->batch_points = m.batch_points;
@@ -663,6 +729,11 @@ int tad_state_replace(tad_engine *eng, tad_state *st, const tad_job *job, const 
     stats->ms_stage0 = m.ms_stage0; stats->ms_replace = m.ms_merge; stats->ms_total = m.ms_total;
   }
   return rc;
+}
+
+int tad_state_replace(tad_engine *eng, tad_state *st, const tad_job *job, const tad_columns *cols, uint32_t flags, int64_t from_t, int64_t to_t,
+                      int64_t keep_from_t, tad_replace_stats *stats) {
+  return tad_state_replace_changes(eng, st, job, cols, flags, from_t, to_t, keep_from_t, stats, nullptr);
 }
 
 }  // extern "C"

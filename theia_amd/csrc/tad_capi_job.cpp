@@ -586,6 +586,7 @@ int count_stream(JobCtx *e, const Job &j, const Attempt &a, StreamBatches *sb, u
   if ((rc = ensure_key_buffers(e, g.K)) != TAD_OK) return rc;
   if (e->merge) {
     e->merge->changed = false;
+    if (e->merge->ch && (rc = merge_report_begin(e, stream, e->merge)) != TAD_OK) return rc;
     // (a replace runs for a batch without a live row, a merge does not: a replace's range still erases)
     if ((e->merge->replace ? stream->K : g.K) != 0 &&
         (rc = state_merge_batch(e, stream, g, a.L, a.stream_poff, a.stream_P, P_bound, j.op_max, jp.alpha, e->merge)) != TAD_OK)
@@ -735,6 +736,10 @@ int job_merge(JobCtx *e, const Job &j, const Attempt &a, const DevCounters &c, i
   hipEventElapsedTime(&ms.ms_stage0, e->ev[1], e->ev[5]);
   hipEventElapsedTime(&ms.ms_merge, e->ev[5], e->ev[4]);
   hipEventElapsedTime(&ms.ms_total, e->ev[0], e->ev[4]);
+  // a report's host array: staged in context workspace, copied out now that nothing can fail the call any more but this copy (it comes
+  // before the candidates become current, so that its failure leaves the state as it was)
+  if (mc->ch && mc->ch->key_since && mc->report_staged && stream->K != 0)
+    HIP_TRY(e, hipMemcpy(mc->ch->key_since, mc->report.since, (size_t)stream->K * 8, hipMemcpyDeviceToHost));
   if (mc->changed) {
     const int old_cur = stream->cur;
     const uint64_t n_ser = stream->ser.len[old_cur] + mc->added - mc->erased, n_hist = stream->history ? stream->hist.len[old_cur] + mc->added - mc->erased : 0;

@@ -2,7 +2,8 @@
 // their *_keys forms.  All five are one call (view_call): one checker for what they refuse, one window — time bounds, a point count, a key
 // mask, any of them absent — whose view is built in the context's workspace (window_bounds, window_gather; kernels: tad_window.hip), and
 // one job on that view (run_view_locked), which runs the stream batches' detectors (tad_capi.cpp) with every point of the view named as
-// new.  Nothing here writes the state.
+// new.  tad_run_state_since / tad_drop_state_since are the same call with a Since: the view is judged whole, and only every key's points
+// from a time on are named as new (the stream's own rule: a per-key suffix).  Nothing here writes the state.
 #include "tad_engine.h"
 
 using namespace tad;
@@ -31,11 +32,24 @@ struct ViewJob {
   uint32_t *list = nullptr;
   unsigned int *lcount = nullptr;
   const unsigned long long *off = nullptr;   // EWMA: the row offsets
+  const uint32_t *first = nullptr;           // EWMA with a Since: every key's first reported index
+  int syncs = 0;                             // host round trips view_detect itself spent (a Since of DBSCAN, ARIMA and DROP: the reported total)
+};
+
+// tad_run_state_since / tad_drop_state_since: what is reported of the judged view — of key k the points with flow_end_s >= since_t (0: no
+// such bound) and >= key_since[k] (device, K entries; NULL: no such bound).  keys: the call's per-key block in sn_key, carved by view_call
+struct Since {
+  const long long *key_since = nullptr;
+  long long since_t = 0;
+  SinceKeys keys{};
 };
 
 // Before the round trip: the routing, the moments, the detector and its row total.  EWMA walks the CSR series; DBSCAN, ARIMA and DROP
 // (its view carries no moments) run the stream's kernels with every series point named as new (poff = the series offsets).
-int view_detect(JobCtx *e, const StateView &v, const JobParams &jp, ViewJob *vj) {
+// since != NULL: the reported points are a suffix of every key's segment (launch_win_since).  EWMA walks every series and counts or emits
+// from first[k] on; the others get the suffixes packed as their batch of new points, after one more round trip for the packed total,
+// and DROP judges the keys with a reported point only (touched_only, as a stream batch).
+int view_detect(JobCtx *e, const StateView &v, const JobParams &jp, const Since *since, ViewJob *vj) {
   hipStream_t s = e->stream;
   const uint64_t K = v.K, P = v.P;
   DevCounters *ctr = static_cast<DevCounters *>(e->counters.p);
@@ -52,14 +66,41 @@ int view_detect(JobCtx *e, const StateView &v, const JobParams &jp, ViewJob *vj)
   vj->coop_min = win_coop_min(K, P);
   launch_win_route(s, K, v.soff, v.st, vj->coop_min, vj->list, vj->lcount, tmin_dev);
   if (jp.algo != TAD_ALGO_DROP) launch_moments(s, K, v.mom.n, v.mom.avg, v.mom.m2, dev_moments(e), ctr);   // (and n_keys / n_points)
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  if (since) {
+    const SinceKeys &sk = since->keys;
+    // EWMA's anomalous rows need first[k] alone: the walk counts them itself, so no suffix length is written and nothing is scanned
+    const bool first_only = jp.algo == TAD_ALGO_EWMA && !jp.all_points;
+    const bool ewma_all = jp.algo == TAD_ALGO_EWMA && jp.all_points;
+    launch_win_since(s, K, v.soff, v.st, since->key_since, since->since_t, sk, !first_only, jp.algo == TAD_ALGO_DROP ? &ctr->n_keys : nullptr);
+    if (!first_only) launch_scan(s, sk.cnt, sk.poff, K, scratch, ewma_all ? dev_total(e) : nullptr);   // (EWMA with every point: the row total)
+    vj->first = sk.first;
+    if (ewma_all) { vj->off = sk.poff; return TAD_OK; }
+  }
   if (jp.algo == TAD_ALGO_EWMA) {
     if (jp.all_points) return TAD_OK;
     launch_win_ewma(s, K, v.soff, v.sval, v.st, v.mom, jp.alpha, vj->coop_min, vj->list, vj->lcount, false, false, static_cast<uint32_t *>(e->n_anom.p), nullptr,
-                    OutRows{});
+                    OutRows{}, 0, 0, 0, vj->first);
     launch_scan(s, static_cast<const uint32_t *>(e->n_anom.p), static_cast<unsigned long long *>(e->off.p), K,
                 static_cast<unsigned long long *>(e->scan_scratch.p), dev_total(e));
     vj->off = static_cast<const unsigned long long *>(e->off.p);
     return TAD_OK;
+  }
+  if (since) {   // the reported suffixes packed: the batch of new points
+    const SinceKeys &sk = since->keys;
+    launch_scan(s, sk.chunks, sk.coff, K, scratch);
+    unsigned long long reported = 0;
+    HIP_TRY(e, hipMemcpyAsync(&reported, sk.poff + K, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    HIP_TRY(e, hipGetLastError());
+    vj->syncs = 1;
+    SincePts sp;
+    if ((rc = carve_buf(e, e->sn_pts, &sp, since_pts_layout, reported ? reported : 1)) != TAD_OK) return rc;
+    launch_win_suffix(s, K, reported, v.soff, v.sval, v.st, sk, sp);
+    hist.nk = sp.nk; hist.nv = sp.nv; hist.nt = sp.nt; hist.poff = sk.poff; hist.P_dev = sk.poff + K; hist.P_cap = reported;
+    if (jp.algo == TAD_ALGO_DBSCAN) return hist_verdicts(e, v.hoff, v.hval, jp, &hist);
+    if (jp.algo == TAD_ALGO_DROP) return state_drop_batch(e, v, hist, jp, true, vj->coop_min, vj->list, vj->lcount, ctr, &vj->db);
+    return stream_arima_batch(e, v, hist, jp, ctr, &vj->ab);
   }
   if ((rc = ensure(e, e->hs_key, P * 8)) != TAD_OK) return rc;
   unsigned long long *nk = static_cast<unsigned long long *>(e->hs_key.p);
@@ -81,7 +122,7 @@ int view_rows(JobCtx *e, const StateView &v, const tad_job *job, const JobParams
   if ((rc = make_result(e, rows, jp.all_points, out_memory, &ro.rp, &ro.dev_rows, &ro.dev_block)) != TAD_OK) return rc;
   if (rows && jp.algo == TAD_ALGO_EWMA)
     launch_win_ewma(s, v.K, v.soff, v.sval, v.st, v.mom, jp.alpha, vj.coop_min, vj.list, vj.lcount, true, jp.all_points, nullptr, vj.off, ro.dev_rows, rows,
-                    e->plan.ewma_emit, e->plan.ewma_emit_rows);
+                    e->plan.ewma_emit, e->plan.ewma_emit_rows, vj.first);
   else if (rows)
     emit_point_rows(s, jp, vj.hist, vj.ab, vj.db, v.mom, ro.dev_rows);
   if ((rc = finish_rows(e, job, &ro, rows, jp.all_points, c, P != 0)) != TAD_OK) return rc;
@@ -94,7 +135,7 @@ int view_rows(JobCtx *e, const StateView &v, const tad_job *job, const JobParams
   }
   hipEventElapsedTime(&rs.ms_total, e->ev[0], e->ev[4]);
   rs.ms_detect = rs.ms_total;   // no Stage 0 ran: the whole call is the detector and its emit
-  rs.host_syncs = 2 + view_syncs;
+  rs.host_syncs = 2 + view_syncs + vj.syncs;
   e->done.store(4);
   *out = &ro.rp->pub;
   return TAD_OK;
@@ -103,16 +144,17 @@ int view_rows(JobCtx *e, const StateView &v, const tad_job *job, const JobParams
 // The job on a view after run_view_begin (tad.h; kernels: tad_window.hip): the detector, the one host round trip of the job's tail, the
 // rows.  Reads the view only: the state's CURRENT copies, or a window's view in this context's workspace (wv_key / wv_pts, which nothing
 // below resizes).
-int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem out_memory, tad_result **out, int view_syncs) {
+int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem out_memory, tad_result **out, int view_syncs,
+                    const Since *since = nullptr) {
   const JobParams jp = job_params(job);
   ViewJob vj;
   int rc;
-  if ((rc = view_detect(e, v, jp, &vj)) != TAD_OK) return rc;
+  if ((rc = view_detect(e, v, jp, since, &vj)) != TAD_OK) return rc;
   e->done.store(2);
   HIP_TRY(e, hipMemcpyAsync(e->tail_host, e->counters.p, kTailBytes, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   HIP_TRY(e, hipGetLastError());
-  const uint64_t rows = (jp.algo == TAD_ALGO_EWMA && jp.all_points) ? v.P : (v.P ? *e->total_host : 0);
+  const uint64_t rows = (jp.algo == TAD_ALGO_EWMA && jp.all_points && !since) ? v.P : (v.P ? *e->total_host : 0);
   const DevCounters c = *e->ctr_host;
   e->done.store(3);
   return view_rows(e, v, job, jp, vj, c, rows, out_memory, out, view_syncs);
@@ -124,7 +166,9 @@ int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem o
 // view; run_view_locked resizes neither.
 // 1. every key's bounds; the view's offsets and the chunk offsets; *P = the window's point total.  keep (device, K bytes, or NULL): the
 // key selection of tad_run_state_keys / tad_drop_state_keys — a key that is not selected gets an empty window
-int window_bounds(JobCtx *e, const tad_state *st, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *keep, uint64_t *P) {
+// — and `since` (device, K entries, or NULL) that of tad_run_state_since: so does a key whose entry is kNoChange
+int window_bounds(JobCtx *e, const tad_state *st, int64_t from_t, int64_t to_t, uint64_t keep_points, const uint8_t *keep, const long long *since,
+                  uint64_t *P) {
   hipStream_t s = e->stream;
   const uint64_t K = st->K;
   const StateView whole = series_view(st, st->cur);
@@ -133,7 +177,7 @@ int window_bounds(JobCtx *e, const tad_state *st, int64_t from_t, int64_t to_t, 
   if ((rc = carve_buf(e, e->wv_key, &w, win_keys_layout, K)) != TAD_OK) return rc;
   if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(K) * sizeof(unsigned long long))) != TAD_OK) return rc;
   unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
-  launch_win_bounds(s, K, whole.soff, whole.st, (long long)from_t, (long long)to_t, keep_points, keep, w.wbeg, w.wlen, w.ecnt, w.chunks);
+  launch_win_bounds(s, K, whole.soff, whole.st, (long long)from_t, (long long)to_t, keep_points, keep, w.wbeg, w.wlen, w.ecnt, w.chunks, since);
   launch_scan(s, w.wlen, w.woff, K, scratch);
   launch_scan(s, w.chunks, w.coff, K, scratch);
   HIP_TRY(e, hipGetLastError());
@@ -227,6 +271,10 @@ struct Window {
   const uint8_t *key_keep = nullptr;
   uint64_t key_keep_len = 0;
   tad_mem key_memory = TAD_MEM_HOST;
+  // tad_run_state_since / tad_drop_state_since: of the judged points, the ones that are reported (key_since: key_keep_len entries, in
+  // key_memory; an entry of TAD_NO_CHANGE also takes the key out of the selection)
+  const int64_t *key_since = nullptr;
+  int64_t since_t = 0;
 };
 
 const char *const kNarrowWindow = "the window is from_t / to_t / keep_points";
@@ -237,15 +285,20 @@ const char *const kNarrowWindow = "the window is from_t / to_t / keep_points";
 // only, no moments, no history.
 int view_call(tad_engine *eng, tad_state *st, const tad_job *job, const char *who, const Window &w, tad_mem out_memory, tad_result **out) {
   if (w.from_t != 0 && w.to_t != 0 && w.from_t > w.to_t) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: from_t is later than to_t", who);
-  if (!w.key_keep && w.key_keep_len != 0)
+  if (!w.key_keep && !w.key_since && w.key_keep_len != 0)
     return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep is NULL with a length of %llu", who, (unsigned long long)w.key_keep_len);
-  if (w.key_keep && w.key_memory != TAD_MEM_HOST && w.key_memory != TAD_MEM_DEVICE)
-    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep must be in host or device memory", who);
+  if ((w.key_keep || w.key_since) && w.key_memory != TAD_MEM_HOST && w.key_memory != TAD_MEM_DEVICE)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: %s must be in host or device memory", who,
+                w.key_keep && w.key_since ? "key_keep and key_since" : (w.key_since ? "key_since" : "key_keep"));
+  if (reinterpret_cast<uintptr_t>(w.key_since) % 8 != 0) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_since must be 8-byte aligned", who);
   StateCall call(eng, st);
   if (st->times_stale)
     return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the series was imported without its times (tad_state_import_times)", who);
   if (w.key_keep && w.key_keep_len != st->K)
     return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_keep has %llu entries, the state holds %llu keys", who, (unsigned long long)w.key_keep_len,
+                (unsigned long long)st->K);
+  if (w.key_since && w.key_keep_len != st->K)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: key_since has %llu entries, the state holds %llu keys", who, (unsigned long long)w.key_keep_len,
                 (unsigned long long)st->K);
   int rc;
   if ((rc = call.enter(who, job->id, job->algo == TAD_ALGO_ARIMA)) != TAD_OK) return rc;
@@ -253,7 +306,23 @@ int view_call(tad_engine *eng, tad_state *st, const tad_job *job, const char *wh
   if ((rc = run_view_begin(e, st->K)) != TAD_OK) return rc;
   const StateView whole = series_view(st, st->cur);
   const uint64_t S = whole.P;
-  if (S == 0 || (!w.key_keep && w.from_t == 0 && w.to_t == 0 && w.keep_points == 0)) return run_view_locked(e, whole, job, out_memory, out, 0);
+  // with no since at all the call is the *_keys call: `since` stays NULL and nothing below differs
+  Since since_args;
+  const Since *since = nullptr;
+  if (w.key_since || w.since_t != 0) {
+    const bool staged = w.key_since && w.key_memory == TAD_MEM_HOST;
+    if ((rc = carve_buf(e, e->sn_key, &since_args.keys, since_keys_layout, st->K, staged)) != TAD_OK) return rc;
+    since_args.since_t = (long long)w.since_t;
+    since_args.key_since = reinterpret_cast<const long long *>(w.key_since);
+    if (staged && st->K != 0) {
+      HIP_TRY(e, hipMemcpyAsync(since_args.keys.since, w.key_since, (size_t)st->K * 8, hipMemcpyHostToDevice, e->stream));
+      since_args.key_since = since_args.keys.since;
+    }
+    since = &since_args;
+  }
+  const long long *d_since = since ? since->key_since : nullptr;
+  if (S == 0 || (!w.key_keep && !d_since && w.from_t == 0 && w.to_t == 0 && w.keep_points == 0))
+    return run_view_locked(e, whole, job, out_memory, out, 0, since);
   const uint8_t *d_keep = w.key_keep;
   if (w.key_keep && w.key_memory == TAD_MEM_HOST) {   // staged: only window_bounds reads it
     if ((rc = ensure(e, e->in_key, (size_t)st->K)) != TAD_OK) return rc;
@@ -261,12 +330,24 @@ int view_call(tad_engine *eng, tad_state *st, const tad_job *job, const char *wh
     d_keep = static_cast<const uint8_t *>(e->in_key.p);
   }
   uint64_t P = 0;
-  if ((rc = window_bounds(e, st, w.from_t, w.to_t, w.keep_points, d_keep, &P)) != TAD_OK) return rc;
-  if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1);   // every key is selected and whole: the state's own arrays, no view
+  if ((rc = window_bounds(e, st, w.from_t, w.to_t, w.keep_points, d_keep, d_since, &P)) != TAD_OK) return rc;
+  if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1, since);   // every key is selected and whole: the state's own arrays, no view
   const bool subtract = job->algo == TAD_ALGO_DBSCAN && P != 0 && !win_hist_by_sort(P, S);   // (P: the SELECTED window points)
   StateView v;
   if ((rc = window_gather(e, st, job, P, subtract, &v)) != TAD_OK) return rc;
-  return run_view_locked(e, v, job, out_memory, out, 1);
+  return run_view_locked(e, v, job, out_memory, out, 1, since);
+}
+
+// tad_run_state_since / tad_drop_state_since: the report window's own checks, then the call
+int since_call(tad_engine *eng, tad_state *st, const tad_job *job, const char *who, Family family, const tad_report_window *w, tad_mem out_memory,
+               tad_result **out) {
+  const int rc = check_view_job(eng, st, job, out, who, family, "the window is the report window's from_t / to_t / keep_points");
+  if (rc != TAD_OK) return rc;
+  if (!w) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the report window must not be NULL", who);
+  Window win{w->from_t, w->to_t, w->keep_points, w->key_keep, (w->key_keep || w->key_since) ? w->num_keys : 0, w->key_memory};
+  win.key_since = w->key_since;
+  win.since_t = w->since_t;
+  return view_call(eng, st, job, who, win, out_memory, out);
 }
 
 }  // namespace
@@ -303,6 +384,14 @@ int tad_drop_state_keys(tad_engine *eng, tad_state *st, const tad_job *job, int6
                         uint64_t key_keep_len, tad_mem key_memory, tad_mem out_memory, tad_result **out) {
   const int rc = check_view_job(eng, st, job, out, "tad_drop_state_keys", Family::Drop, kNarrowWindow);
   return rc != TAD_OK ? rc : view_call(eng, st, job, "tad_drop_state_keys", Window{from_t, to_t, keep_points, key_keep, key_keep_len, key_memory}, out_memory, out);
+}
+
+int tad_run_state_since(tad_engine *eng, tad_state *st, const tad_job *job, const tad_report_window *w, tad_mem out_memory, tad_result **out) {
+  return since_call(eng, st, job, "tad_run_state_since", Family::Run, w, out_memory, out);
+}
+
+int tad_drop_state_since(tad_engine *eng, tad_state *st, const tad_job *job, const tad_report_window *w, tad_mem out_memory, tad_result **out) {
+  return since_call(eng, st, job, "tad_drop_state_since", Family::Drop, w, out_memory, out);
 }
 
 }  // extern "C"

@@ -214,6 +214,34 @@ inline WinPts win_pts_layout(Carve &c, uint64_t P, bool dbscan) {
   return w;
 }
 
+// ---- tad_run_state_since / tad_drop_state_since (sn_key, sn_pts): the reported suffix of every key of the view ----
+struct SinceKeys {   // per key: the suffix's first index | its length | its chunks | the packed offsets | the chunk offsets | a host key_since staged
+  uint32_t *first, *cnt, *chunks;
+  unsigned long long *poff, *coff;
+  long long *since;   // NULL unless staged
+};
+inline SinceKeys since_keys_layout(Carve &c, uint64_t K, bool staged) {
+  SinceKeys k;
+  k.first = take_counts(c, K);
+  k.cnt = take_counts(c, K);
+  k.chunks = take_counts(c, K);
+  k.poff = take_offsets(c, K);
+  k.coff = take_offsets(c, K);
+  k.since = staged ? c.take<long long>(K ? K : 1) : nullptr;
+  return k;
+}
+struct SincePts {   // per reported point: key | value | time
+  unsigned long long *nk, *nv;
+  long long *nt;
+};
+inline SincePts since_pts_layout(Carve &c, uint64_t P) {
+  SincePts p;
+  p.nk = c.take<unsigned long long>(P);
+  p.nv = c.take<unsigned long long>(P);
+  p.nt = c.take<long long>(P);
+  return p;
+}
+
 // ---- tad_state_merge (mg_pts, mg_keys) ----
 struct MergeCounters {   // one 64-byte block on the device, zeroed per attempt
   unsigned long long too_old, appended, inserted, combined, keys_touched, keys_replayed, keys_emptied, pad[1];   // keys_emptied: tad_state_replace only
@@ -287,6 +315,23 @@ inline ReplaceLoss replace_loss_layout(Carve &c, uint64_t n) {
   l.hrem = c.take<unsigned long long>(n);
   l.hrem_s = c.take<unsigned long long>(n);
   return l;
+}
+
+// ---- the change report of a merge or a replace (mg_report; tad_state_merge_changes / tad_state_replace_changes) ----
+struct ChangeCounters {   // one 64-byte block on the device, set per attempt by the report's fill kernel
+  unsigned long long points, keys;   // changed points | keys with a changed point
+  long long min_t, max_t;            // smallest / largest changed time (INT64_MAX / INT64_MIN: none)
+  unsigned long long pad[4];
+};
+struct MergeReport {   // counters | per key: the smallest changed time (staged == false: the caller's own device array is written)
+  ChangeCounters *cc;
+  long long *since;
+};
+inline MergeReport merge_report_layout(Carve &c, uint64_t K, bool staged) {
+  MergeReport r;
+  r.cc = c.take<ChangeCounters>(1);
+  r.since = staged ? c.take<long long>(K ? K : 1) : nullptr;
+  return r;
 }
 
 // ---- a stream ARIMA batch (as_key, as_pt, as_ser, as_pos, as_fit) ----

@@ -87,8 +87,10 @@ struct JobBufs {
   DevBuf sp_cls;                                                                  // Stage 0 sparse, length classes: per-key class arrays
   DevBuf hs_key, hs_t, hs_val, hs_sorted, hs_noise, hs_cnt, hs_row, hs_koff, hs_kcnt;   // a history batch: new points, sorted values, verdicts, rows, offsets
   DevBuf wv_key, wv_pts;   // tad_run_state_window's view: per key (bounds, offsets, moments) | per window point (values, times, sorted values)
+  DevBuf sn_key, sn_pts;   // tad_run_state_since / tad_drop_state_since: per key (the reported suffix, a staged key_since) | per reported point (key, value, time)
   DevBuf mg_pts, mg_keys, mg_hist;   // tad_state_merge: per batch point | per key | the history between its subtract and its merge
   DevBuf rp_keys, rp_loss;           // tad_state_replace, beside a merge's: per key (the erased runs) | the values the history loses, packed and sorted
+  DevBuf mg_report;                  // tad_state_merge_changes / tad_state_replace_changes: the report's counters | a host array's staging
   DevBuf as_key, as_pt, as_ser, as_fit, as_pos, as_ws;   // a stream ARIMA batch: per key | per new point | packed series | per fit | per position | fit workspace
   DevBuf ds_key, ds_pt;   // tad_drop_state / tad_drop_stream: per key (mean, std, m2, n, ok) | per judged point (verdict, rows, row offset)
   DevBuf dsel;            // tad_drop_select: row bitmask | tile counts | tile offsets | scan scratch | total | a host table's staged columns
@@ -138,6 +140,12 @@ struct MergeCall {
   int64_t from_t = 0, to_t = 0;
   uint64_t erased = 0;     // series points lost: old points inside the range that the batch does not name
   uint64_t emptied = 0;    // keys that held points and hold none afterwards
+  // tad_state_merge_changes / tad_state_replace_changes: the caller's report (NULL: none is made) and, per attempt, where the kernels
+  // write it (merge_report_begin) and what they counted
+  tad_changes *ch = nullptr;
+  tad::MergeReport report{};
+  bool report_staged = false;   // report.since is context workspace: copied to ch->key_since when the call has succeeded
+  tad::ChangeCounters counted{};
 };
 
 // A double-buffered value arena of a streaming state: two device arrays of T and their capacities in values, indexed like
@@ -436,6 +444,9 @@ void emit_point_rows(hipStream_t s, const JobParams &jp, const HistBatch &hb, co
                      OutRows out);
 int stream_history_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound,
                          const JobParams &jp, HistBatch *hb);
+// a call with a report, before its batch is placed (every attempt, a batch without a live row too): the report's block, every entry
+// TAD_NO_CHANGE, the counters at their start
+int merge_report_begin(JobCtx *e, const tad_state *st, MergeCall *mc);
 // tad_state_merge and tad_state_replace (mc->replace) in the count pass's place; K = the state's keys: a replace runs for a batch
 // without a live row too (g.K == 0), which still erases the range
 int state_merge_batch(JobCtx *e, tad_state *st, Grid g, Lattice L, const unsigned long long *sparse_poff, uint64_t P, uint64_t P_bound, bool op_max,

@@ -408,7 +408,8 @@ void launch_win_route(hipStream_t s, uint64_t K, const unsigned long long *soff,
 void launch_win_ewma(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *sval, const long long *st, StreamState cur,
                      double alpha, unsigned long long coop_min, const uint32_t *list, const unsigned int *count, bool emit, bool all_points,
                      uint32_t *n_anom, const unsigned long long *off, OutRows out, uint64_t rows = 0,   // rows: off[K], for the emit
-                     int ewma_emit = 0, uint32_t ewma_emit_rows = 0);   // tad_plan: 1 = the lanes store their rows themselves; LDS rows per wavefront of the staged emit
+                     int ewma_emit = 0, uint32_t ewma_emit_rows = 0,   // tad_plan: 1 = the lanes store their rows themselves; LDS rows per wavefront of the staged emit
+                     const uint32_t *first = nullptr);   // tad_run_state_since: key k's points before index first[k] are walked, not counted or emitted (off: of the rest)
 // nk[i] = the key of series point i
 void launch_win_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, unsigned long long *nk);
 // What tad_run_state's kernels read: K keys holding P points, key k's values and times in time order at [soff[k], soff[k + 1]), the
@@ -438,9 +439,19 @@ struct HistBatch {
 // per key: wbeg = the window's first point inside the key's segment, wlen = its points, ecnt = the key's points outside it (prefix +
 // suffix), chunks = the wavefronts of the key's old segment in launch_win_gather / launch_hist_subtract (at least 1).  from_t / to_t 0 = no bound on
 // that side (flow_end_s >= from_t, < to_t); keep_points 0 = no count rule, else the newest keep_points of the rest.  keep != NULL (K bytes):
-// a key with keep[k] == 0 gets wlen = 0 and ecnt = its length
+// a key with keep[k] == 0 gets wlen = 0 and ecnt = its length; since != NULL (K entries): so does a key with since[k] == kNoChange
 void launch_win_bounds(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, long long from_t, long long to_t,
-                       uint64_t keep_points, const uint8_t *keep, uint32_t *wbeg, uint32_t *wlen, uint32_t *ecnt, uint32_t *chunks);
+                       uint64_t keep_points, const uint8_t *keep, uint32_t *wbeg, uint32_t *wlen, uint32_t *ecnt, uint32_t *chunks,
+                       const long long *since = nullptr);
+// ---- tad_run_state_since / tad_drop_state_since (tad_window.hip): the reported points of a view, a suffix of every key's segment ----
+// sk.first[k] = the first index of key k's segment [soff[k], soff[k + 1]) with a time >= since_t (0: no such bound) and >= key_since[k]
+// (NULL: no such bound; kNoChange: the suffix is empty), sk.cnt[k] = the points from there on, sk.chunks[k] = ceil(cnt / kHistChunk);
+// lengths == false: first alone is written; n_keys != NULL: += the keys with a point in the view
+void launch_win_since(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, const long long *key_since, long long since_t,
+                      const SinceKeys &sk, bool lengths, unsigned long long *n_keys);
+// key, time and value of every reported point packed at sk.poff (the scan of sk.cnt; sk.coff: the scan of sk.chunks); points = poff[K]
+void launch_win_suffix(hipStream_t s, uint64_t K, uint64_t points, const unsigned long long *soff, const unsigned long long *sval, const long long *st,
+                       const SinceKeys &sk, const SincePts &sp);
 // every key's window values and times to woff (the scan of wlen); ev != NULL: the excluded values, prefix then suffix, packed at eoff
 // (the scan of ecnt).  chunks_bound: trim_chunks_bound(K, the state's points)
 void launch_win_gather(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *soff,
@@ -458,11 +469,13 @@ struct MergeInto {
   unsigned long long *hrem = nullptr;
 };
 // What a batch point does to the value its key holds at that time — the sum, the maximum or (replace) the batch's value — and the range
-// [from, to) of a replace (0 = no bound on that side) with its per-key runs; range == NULL: nothing is erased
+// [from, to) of a replace (0 = no bound on that side) with its per-key runs; range == NULL: nothing is erased.  report != NULL: the
+// series kernel also says what it changed (launch_merge_report_*)
 struct MergeRule {
   bool replace = false, op_max = false;
   const ReplaceKeys *range = nullptr;
   long long from = 0, to = 0;
+  const MergeReport *report = nullptr;
 };
 // per point: cls (too old / appended / inserted / combined), rank = the key's old points before it, and the flags of the three scans:
 // f_nh = adds an element (inserted or appended), f_kept = not too old, f_hit = combined; lanes in [*P_dev, P_cap) write zeros
@@ -486,6 +499,15 @@ void launch_merge_series(hipStream_t s, const HistBatch &b, const StateView &old
 // that only gained newer points continued over them.  replay == NULL: no key replays.  Counts keys_touched / keys_replayed
 void launch_merge_moments(hipStream_t s, const StateView &old, const MergeInto &into, const uint32_t *replay, double alpha, StreamState next,
                           MergeCounters *mc);
+// The change report of a merge or a replace (tad.h: tad_changes): since[k] = the smallest time at which key k's series changed
+// (kNoChange: it did not).  launch_merge_series with how.report lowers since[k] to the smallest time of the points it adds, erases or
+// gives another value (one atomic per wavefront with such a point) and adds them to cc->points / cc->max_t.
+static constexpr long long kNoChange = 0x7fffffffffffffffll;   // TAD_NO_CHANGE
+// since[0, K) = kNoChange; cc: no point, no key, min_t / max_t at their neutral values
+void launch_merge_report_fill(hipStream_t s, uint64_t K, const MergeReport &r);
+// per key, after the series kernel (poff == NULL) or in its place on the append path (since[k] = the key's first batch time, cc->max_t
+// from its last): cc->keys and cc->min_t from since
+void launch_merge_report_keys(hipStream_t s, uint64_t K, const unsigned long long *poff, const long long *nt, const MergeReport &r);
 // ---- streaming ARIMA (tad_arima.hip): a batch on a series state, per touched key (slot) and per new point ----
 struct FitListArgs {
   const uint32_t *wave_pos;          // [waves] position of each wavefront of k_arima_fit_list

@@ -32,6 +32,10 @@
 //   6. k_merge_moments, one lane per key: a key with replay set is replayed from the zero state over its merged series (stream_step: the
 //      fresh state's bits — an emptied key holds an unseen key's), a key that only gained newer points continues from its stored state,
 //      the rest is copied.  A range adds nothing.
+// The change report (tad.h: tad_changes; the REPORT forms, run only by a call that asked for one): k_merge_series knows every element it
+// adds, erases or gives another value; the smallest such time of a chunk lowers the key's entry of `since` with one atomic per wavefront,
+// and the counters take one atomic per wavefront and counter, as count_wave's.  The append path writes no series here: a lane per key
+// takes the key's first batch time (k_merge_report_keys, which on either path counts the changed keys and reduces the smallest time).
 // No LDS, no scratch.  Times inside one key's batch segment ascend strictly (Stage 0 made the points unique), as the key's old times do.
 #include <stdint.h>
 
@@ -180,7 +184,10 @@ __device__ __forceinline__ unsigned long long merge_value(unsigned long long x, 
 
 // A key's losses in the packed list hrem start at rkoff[k]: the old values of its combined points first (point j's at its index among
 // them, roff[j] - roff[p0]), then (RANGED) its erased points in time order.
-template <int RULE, bool RANGED>
+// REPORT: since[k] = min(since[k], the smallest time of the chunk's changed elements) — an added batch point, an erased old point, an
+// old point whose value the rule changes (a sum of 0, a maximum not above and a replace by the held value change nothing) — and
+// cc->points / cc->max_t over them.
+template <int RULE, bool RANGED, bool REPORT>
 __global__ __launch_bounds__(kMBlock) void k_merge_series(const unsigned long long *__restrict__ coff, uint64_t K,
                                                          const unsigned long long *__restrict__ soff_old, const unsigned long long *__restrict__ sval_old,
                                                          const long long *__restrict__ st_old, const unsigned long long *__restrict__ poff,
@@ -191,7 +198,8 @@ __global__ __launch_bounds__(kMBlock) void k_merge_series(const unsigned long lo
                                                          unsigned long long *__restrict__ sval_new, long long *__restrict__ st_new,
                                                          unsigned long long *__restrict__ hadd, unsigned long long *__restrict__ hrem,
                                                          const unsigned long long *__restrict__ rkoff, const uint32_t *__restrict__ ebeg,
-                                                         const uint32_t *__restrict__ eend, const uint32_t *__restrict__ ecnt, long long from) {
+                                                         const uint32_t *__restrict__ eend, const uint32_t *__restrict__ ecnt, long long from,
+                                                         long long *__restrict__ since, ChangeCounters *__restrict__ cc) {
   static_assert(!RANGED || RULE == MERGE_REPLACE, "only a replace carries a range");
   const unsigned long long w = ((uint64_t)blockIdx.x * kMBlock + threadIdx.x) >> 6;
   if (w >= coff[K]) return;
@@ -213,6 +221,8 @@ __global__ __launch_bounds__(kMBlock) void k_merge_series(const unsigned long lo
   const unsigned long long c0 = (w - coff[k]) * kMergeChunk;
   unsigned long long c1 = c0 + kMergeChunk;
   if (c1 > a + b) c1 = a + b;
+  [[maybe_unused]] long long ch_min = kNoChange, ch_max = -kNoChange - 1;   // the lane's changed elements: smallest / largest time, how many
+  [[maybe_unused]] unsigned ch_n = 0;
   for (unsigned long long u = c0 + lane; u < c1; u += 64) {
     if (u < a) {
       unsigned long long x = sval_old[o0 + u];
@@ -225,7 +235,10 @@ __global__ __launch_bounds__(kMBlock) void k_merge_series(const unsigned long lo
         shift = nhoff[j] - nh0;
         if (j < p0 + b && nt[j] == t && cls[j] == MG_COMBINED) {
           hit = true;
+          [[maybe_unused]] const unsigned long long held = x;
           x = merge_value<RULE>(x, nv[j]);
+          if constexpr (REPORT)
+            if (x != held) { ch_min = t < ch_min ? t : ch_min; ch_max = t > ch_max ? t : ch_max; ++ch_n; }
         }
         if constexpr (RANGED)
           if (u > e0 && u < e1) rep = roff[j] - rf;   // combined points of the key in [e0, u)
@@ -234,6 +247,7 @@ __global__ __launch_bounds__(kMBlock) void k_merge_series(const unsigned long lo
       if constexpr (RANGED) {
         if (u >= e0 && u < e1 && !hit) {
           if (hrem) hrem[l0 + nrep + (u - e0) - rep] = x;
+          if constexpr (REPORT) { ch_min = t < ch_min ? t : ch_min; ch_max = t > ch_max ? t : ch_max; ++ch_n; }
           continue;
         }
         eb = u <= e0 ? 0ull : (u >= e1 ? ec : (u - e0) - rep);
@@ -249,9 +263,11 @@ __global__ __launch_bounds__(kMBlock) void k_merge_series(const unsigned long lo
         unsigned long long eb = 0;
         if constexpr (RANGED) eb = r <= e0 ? 0ull : (r >= e1 ? ec : (r - e0) - (roff[j] - rf));
         const unsigned long long d = d0 + r - eb + (nhoff[j] - nh0);
+        const long long t = nt[j];
         sval_new[d] = y;
-        st_new[d] = nt[j];
+        st_new[d] = t;
         if (hadd) hadd[aoff[j]] = y;
+        if constexpr (REPORT) { ch_min = t < ch_min ? t : ch_min; ch_max = t > ch_max ? t : ch_max; ++ch_n; }
       } else if (c == MG_COMBINED && hadd) {
         const unsigned long long x = sval_old[o0 + rank[j]];
         // its place among the key's losses, rkoff[k] + (roff[j] - roff[p0]); without a range rkoff[k] == roff[p0]
@@ -259,6 +275,55 @@ __global__ __launch_bounds__(kMBlock) void k_merge_series(const unsigned long lo
         hadd[aoff[j]] = merge_value<RULE>(x, y);
       }
     }
+  }
+  if constexpr (REPORT) {   // (every lane of the wavefront is here: the loop has no exit but its end)
+    for (int d = 32; d >= 1; d >>= 1) {
+      const long long omin = __shfl_xor(ch_min, d), omax = __shfl_xor(ch_max, d);
+      ch_n += __shfl_xor(ch_n, d);
+      ch_min = omin < ch_min ? omin : ch_min;
+      ch_max = omax > ch_max ? omax : ch_max;
+    }
+    if (lane == 0 && ch_n != 0) {
+      atomicMin(&since[k], ch_min);
+      atomicMax(&cc->max_t, ch_max);
+      atomicAdd(&cc->points, (unsigned long long)ch_n);
+    }
+  }
+}
+
+// ---- the change report's per-key passes ----
+__global__ __launch_bounds__(kMBlock) void k_merge_report_fill(uint64_t K, long long *__restrict__ since, ChangeCounters *__restrict__ cc) {
+  const uint64_t k = (uint64_t)blockIdx.x * kMBlock + threadIdx.x;
+  if (k < K) since[k] = kNoChange;
+  if (k == 0) { cc->points = 0; cc->keys = 0; cc->min_t = kNoChange; cc->max_t = -kNoChange - 1; }
+}
+
+// APPEND: every batch point is newer than what its key held and is kept, so key k's changed points are its batch segment.
+template <bool APPEND>
+__global__ __launch_bounds__(kMBlock) void k_merge_report_keys(uint64_t K, const unsigned long long *__restrict__ poff, const long long *__restrict__ nt,
+                                                              long long *__restrict__ since, ChangeCounters *__restrict__ cc) {
+  const uint64_t k = (uint64_t)blockIdx.x * kMBlock + threadIdx.x;
+  const unsigned lane = threadIdx.x & 63u;
+  long long t0 = kNoChange;
+  [[maybe_unused]] long long t1 = -kNoChange - 1;
+  if (k < K) {
+    if constexpr (APPEND) {
+      const unsigned long long p0 = poff[k], p1 = poff[k + 1];
+      if (p1 > p0) { t0 = nt[p0]; t1 = nt[p1 - 1]; }
+      since[k] = t0;
+    } else {
+      t0 = since[k];
+    }
+  }
+  count_wave(t0 != kNoChange, lane, &cc->keys);
+  for (int d = 32; d >= 1; d >>= 1) {
+    const long long omin = __shfl_xor(t0, d);
+    t0 = omin < t0 ? omin : t0;
+    if constexpr (APPEND) { const long long omax = __shfl_xor(t1, d); t1 = omax > t1 ? omax : t1; }
+  }
+  if (lane == 0 && t0 != kNoChange) {
+    atomicMin(&cc->min_t, t0);
+    if constexpr (APPEND) atomicMax(&cc->max_t, t1);
   }
 }
 
@@ -320,13 +385,21 @@ void launch_merge_keys(hipStream_t s, const HistBatch &b, const StateView &old, 
 
 uint64_t merge_chunks_bound(uint64_t K, uint64_t total_len) { return K + total_len / kMergeChunk + 1; }
 
+template <int RULE, bool RANGED, bool REPORT>
+static void launch_series_rule(hipStream_t s, const HistBatch &b, const StateView &old, const MergeInto &into, const MergePts &mp, const MergeKeys &mk,
+                             const MergeRule &how) {
+  const ReplaceKeys r = RANGED ? *how.range : ReplaceKeys{};   // (the unranged forms read no run)
+  const MergeReport rep = REPORT ? *how.report : MergeReport{};
+  hipLaunchKernelGGL((k_merge_series<RULE, RANGED, REPORT>), dim3(merge_blocks(merge_chunks_bound(old.K, old.P + b.P_cap) * 64)), dim3(kMBlock), 0, s, mk.coff_s,
+                     old.K, old.soff, old.sval, old.st, b.poff, b.nt, b.nv, mp.cls, mp.rank, mp.nhoff, mp.aoff, mp.roff, into.soff, into.sval, into.st,
+                     into.hrem ? mp.hadd : nullptr, into.hrem, mk.rkoff, r.ebeg, r.eend, r.ecnt, how.from, rep.since, rep.cc);
+}
+
 template <int RULE, bool RANGED>
 static void launch_series_as(hipStream_t s, const HistBatch &b, const StateView &old, const MergeInto &into, const MergePts &mp, const MergeKeys &mk,
                              const MergeRule &how) {
-  const ReplaceKeys r = RANGED ? *how.range : ReplaceKeys{};   // (the unranged forms read no run)
-  hipLaunchKernelGGL((k_merge_series<RULE, RANGED>), dim3(merge_blocks(merge_chunks_bound(old.K, old.P + b.P_cap) * 64)), dim3(kMBlock), 0, s, mk.coff_s,
-                     old.K, old.soff, old.sval, old.st, b.poff, b.nt, b.nv, mp.cls, mp.rank, mp.nhoff, mp.aoff, mp.roff, into.soff, into.sval, into.st,
-                     into.hrem ? mp.hadd : nullptr, into.hrem, mk.rkoff, r.ebeg, r.eend, r.ecnt, how.from);
+  if (how.report) launch_series_rule<RULE, RANGED, true>(s, b, old, into, mp, mk, how);
+  else launch_series_rule<RULE, RANGED, false>(s, b, old, into, mp, mk, how);
 }
 
 void launch_merge_series(hipStream_t s, const HistBatch &b, const StateView &old, const MergeInto &into, const MergePts &mp, const MergeKeys &mk,
@@ -343,6 +416,16 @@ void launch_merge_moments(hipStream_t s, const StateView &old, const MergeInto &
   if (old.K == 0) return;
   hipLaunchKernelGGL(k_merge_moments, dim3(merge_blocks(old.K)), dim3(kMBlock), 0, s, old.K, replay, old.soff, into.soff, into.sval, into.st, alpha, old.mom,
                      next, mc);
+}
+
+void launch_merge_report_fill(hipStream_t s, uint64_t K, const MergeReport &r) {
+  hipLaunchKernelGGL(k_merge_report_fill, dim3(merge_blocks(K ? K : 1)), dim3(kMBlock), 0, s, K, r.since, r.cc);
+}
+
+void launch_merge_report_keys(hipStream_t s, uint64_t K, const unsigned long long *poff, const long long *nt, const MergeReport &r) {
+  if (K == 0) return;
+  if (poff) hipLaunchKernelGGL(k_merge_report_keys<true>, dim3(merge_blocks(K)), dim3(kMBlock), 0, s, K, poff, nt, r.since, r.cc);
+  else hipLaunchKernelGGL(k_merge_report_keys<false>, dim3(merge_blocks(K)), dim3(kMBlock), 0, s, K, poff, nt, r.since, r.cc);
 }
 
 const void *code_anchor_merge() { return reinterpret_cast<const void *>(&k_merge_classify); }

@@ -75,7 +75,8 @@ __global__ __launch_bounds__(kWBlock) void k_win_route(uint64_t K, const unsigne
 template <bool EMIT, bool ALL>
 __global__ __launch_bounds__(kWBlock) void k_win_ewma(uint64_t K, const unsigned long long *__restrict__ soff, const unsigned long long *__restrict__ sval,
                                                      const long long *__restrict__ st, StreamState cur, double alpha, unsigned long long coop_min,
-                                                     uint32_t *__restrict__ n_anom, const unsigned long long *__restrict__ off, OutRows out) {
+                                                     uint32_t *__restrict__ n_anom, const unsigned long long *__restrict__ off, OutRows out,
+                                                     const uint32_t *__restrict__ first) {
   const uint64_t k = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
   if (k >= K) return;
   const unsigned long long p0 = soff[k], len = soff[k + 1] - p0;
@@ -90,6 +91,7 @@ __global__ __launch_bounds__(kWBlock) void k_win_ewma(uint64_t K, const unsigned
   double e = 0.0;
   uint32_t a = 0;
   unsigned long long pos = EMIT ? off[k] : 0ull;
+  const unsigned long long f = first ? first[k] : 0ull;   // tad_run_state_since: points before index f are walked, not counted or emitted
   const unsigned long long nch = (len + kWinChunk - 1) / kWinChunk;
   unsigned long long va[kWinChunk], vb[kWinChunk];
   long long ta[kWinChunk], tb[kWinChunk];
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(kWBlock) void k_win_ewma(uint64_t K, const unsigned
       const double x = (double)v[u];
       e = one_minus * e + alpha * x;
       const bool verdict = has_sigma && fabs(x - e) > sg;
-      if (ALL || verdict) {
+      if ((ALL || verdict) && c * kWinChunk + u >= f) {
         if (EMIT) win_row(out, pos++, k, t[u], x, e, sg, ALL, verdict);
         a++;
       }
@@ -132,7 +134,8 @@ __global__ __launch_bounds__(kWBlock) void k_win_ewma(uint64_t K, const unsigned
 static constexpr uint32_t kWinNoLane = 0xFFu;
 __global__ __launch_bounds__(64) void k_win_emit_staged(uint64_t K, const unsigned long long *__restrict__ soff, const unsigned long long *__restrict__ sval,
                                                         const long long *__restrict__ st, StreamState cur, double alpha, unsigned long long coop_min,
-                                                        const unsigned long long *__restrict__ off, OutRows out, uint32_t cap) {
+                                                        const unsigned long long *__restrict__ off, OutRows out, uint32_t cap,
+                                                        const uint32_t *__restrict__ first) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_win[];
   double *s_e = reinterpret_cast<double *>(smem_win);                  // [cap]
   double *s_sg = s_e + cap;                                            // [64]
@@ -162,6 +165,7 @@ __global__ __launch_bounds__(64) void k_win_emit_staged(uint64_t K, const unsign
   if (len != 0 && pos != end) {   // (rows imply a defined sigma: the count pass counts nothing otherwise)
     const double one_minus = 1.0 - alpha;
     double e = 0.0;
+    const unsigned long long f = first ? first[k] : 0ull;
     const unsigned long long nch = (len + kWinChunk - 1) / kWinChunk;
     unsigned long long va[kWinChunk], vb[kWinChunk];
     auto load = [&](unsigned long long c, unsigned long long *v) {
@@ -178,7 +182,7 @@ __global__ __launch_bounds__(64) void k_win_emit_staged(uint64_t K, const unsign
         if (i >= len) break;
         const double x = (double)v[u];
         e = one_minus * e + alpha * x;
-        if (has_sigma && fabs(x - e) > sg && pos < end) {
+        if (has_sigma && fabs(x - e) > sg && i >= f && pos < end) {
           if (pos < staged) {
             s_e[pos] = e;
             s_p[pos] = (uint32_t)(p0 + i - pbase);
@@ -217,7 +221,8 @@ template <bool EMIT, bool ALL>
 __global__ __launch_bounds__(kWBlock) void k_win_ewma_coop(const uint32_t *__restrict__ list, const unsigned int *__restrict__ count,
                                                           const unsigned long long *__restrict__ soff, const unsigned long long *__restrict__ sval,
                                                           const long long *__restrict__ st, StreamState cur, double alpha,
-                                                          uint32_t *__restrict__ n_anom, const unsigned long long *__restrict__ off, OutRows out) {
+                                                          uint32_t *__restrict__ n_anom, const unsigned long long *__restrict__ off, OutRows out,
+                                                          const uint32_t *__restrict__ first) {
   const unsigned lane = threadIdx.x & 63u;
   const unsigned wave = (blockIdx.x * kWBlock + threadIdx.x) >> 6, nwaves = gridDim.x * (kWBlock / 64);
   const unsigned total = *count;
@@ -231,6 +236,7 @@ __global__ __launch_bounds__(kWBlock) void k_win_ewma_coop(const uint32_t *__res
     double e = 0.0;
     uint32_t a = 0;
     unsigned long long pos = EMIT ? off[k] : 0ull;
+    const unsigned long long f = first ? first[k] : 0ull;
     auto load = [&](unsigned long long c, unsigned long long &v, long long &t) {
       const unsigned long long i = c * 64 + lane;
       const bool in = c < nblk && i < len;
@@ -254,7 +260,7 @@ __global__ __launch_bounds__(kWBlock) void k_win_ewma_coop(const uint32_t *__res
         const bool verdict = has_sigma && fabs(x - e) > sg;
         if ((int)lane == u) { my_e = e; my_verdict = verdict; }
       }
-      const unsigned long long m = __ballot(ALL ? (int)lane < cnt : my_verdict);
+      const unsigned long long m = __ballot((ALL ? (int)lane < cnt : my_verdict) && c * 64 + lane >= f);
       if (EMIT && ((m >> lane) & 1ull))
         win_row(out, pos + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull)), k, t0, x0, my_e, sg, ALL, my_verdict);
       pos += (unsigned long long)__popcll(m);
@@ -304,12 +310,14 @@ __device__ __forceinline__ unsigned long long win_lower_t(const long long *__res
 
 __global__ __launch_bounds__(kWBlock) void k_win_bounds(uint64_t K, const unsigned long long *__restrict__ soff, const long long *__restrict__ st,
                                                        long long from_t, long long to_t, uint64_t keep_points, const uint8_t *__restrict__ keep,
-                                                       uint32_t *__restrict__ wbeg, uint32_t *__restrict__ wlen, uint32_t *__restrict__ ecnt,
+                                                       const long long *__restrict__ since, uint32_t *__restrict__ wbeg, uint32_t *__restrict__ wlen, uint32_t *__restrict__ ecnt,
                                                        uint32_t *__restrict__ chunks) {
   const uint64_t k = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
   if (k >= K) return;
   const unsigned long long o0 = soff[k], o1 = soff[k + 1], len = o1 - o0;
-  if (keep != nullptr && keep[k] == 0) {   // a key that is not selected (tad_run_state_keys): no window point, every point excluded, no search
+  // a key that is not selected (tad_run_state_keys' mask; tad_run_state_since: a key without a change): no window point, every point
+  // excluded, no search
+  if ((keep != nullptr && keep[k] == 0) || (since != nullptr && since[k] == kNoChange)) {
     wbeg[k] = 0;
     wlen[k] = 0;
     ecnt[k] = (uint32_t)len;
@@ -355,6 +363,64 @@ __global__ __launch_bounds__(kWBlock) void k_win_gather(const unsigned long long
   }
 }
 
+// ---- tad_run_state_since / tad_drop_state_since: judge the view, report from a time on (include/tad.h) ----
+// Times ascend per key, so the reported points of a key — t >= since_t, t >= key_since[k] — are a SUFFIX of its view segment.
+//   k_win_since   one lane per key: first[k] = the suffix's first index (one lower bound over the view's times for the larger of the two
+//                 thresholds; the whole segment without one; len for a key whose key_since is kNoChange), cnt[k] = the suffix's length,
+//                 chunks[k] = its wavefronts in k_win_suffix (0 for an empty one); n_keys (DROP, whose judged keys nothing else counts)
+//                 += the keys with a view point, one atomic per wavefront.  The scan of cnt is poff.
+//   k_win_suffix  one wavefront per kHistChunk points of one key's suffix, lanes on consecutive points (coalesced 8-byte loads and
+//                 stores), k_win_gather's manner: key, time and value of every reported point packed at poff[k].  That is the HistBatch
+//                 of "new points" the stream detectors judge against the whole view (hist_verdicts, stream_arima_batch, state_drop_batch).
+// EWMA walks the series anyway: the three kernels above take first[k] and count or emit a point only at an index >= first[k].
+__global__ __launch_bounds__(kWBlock) void k_win_since(uint64_t K, const unsigned long long *__restrict__ soff, const long long *__restrict__ st,
+                                                      const long long *__restrict__ key_since, long long since_t, uint32_t *__restrict__ first,
+                                                      uint32_t *__restrict__ cnt, uint32_t *__restrict__ chunks, unsigned long long *__restrict__ n_keys) {
+  const uint64_t k = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
+  unsigned long long len = 0;
+  if (k < K) {
+    const unsigned long long o0 = soff[k];
+    len = soff[k + 1] - o0;
+    bool bounded = since_t != 0, selected = true;
+    long long thr = since_t;
+    if (key_since != nullptr) {
+      const long long ks = key_since[k];
+      if (ks == kNoChange) selected = false;
+      else if (!bounded || ks > thr) { thr = ks; bounded = true; }
+    }
+    const unsigned long long f = !selected ? len : (bounded ? win_lower_t(st, o0, o0 + len, thr) - o0 : 0ull);
+    first[k] = (uint32_t)f;
+    if (cnt != nullptr) {   // (NULL: the caller wants first[k] alone — EWMA's anomalous rows, counted by the walk)
+      cnt[k] = (uint32_t)(len - f);
+      chunks[k] = (uint32_t)((len - f + kHistChunk - 1) / kHistChunk);
+    }
+  }
+  if (n_keys != nullptr) {   // (uniform: every lane of the wavefront reaches the ballot)
+    const unsigned long long m = __ballot(len != 0);
+    if ((threadIdx.x & 63u) == 0 && m) atomicAdd(n_keys, (unsigned long long)__popcll(m));
+  }
+}
+
+__global__ __launch_bounds__(kWBlock) void k_win_suffix(const unsigned long long *__restrict__ coff, uint64_t K, const unsigned long long *__restrict__ soff,
+                                                       const unsigned long long *__restrict__ sval, const long long *__restrict__ st,
+                                                       const uint32_t *__restrict__ first, const unsigned long long *__restrict__ poff,
+                                                       unsigned long long *__restrict__ nk, long long *__restrict__ nt,
+                                                       unsigned long long *__restrict__ nv) {
+  const unsigned long long w = ((uint64_t)blockIdx.x * kWBlock + threadIdx.x) >> 6;
+  if (w >= coff[K]) return;
+  const unsigned lane = threadIdx.x & 63u;
+  const uint64_t k = chunk_key(coff, K, w);   // (wavefront-uniform; a key with an empty suffix has no chunk)
+  const unsigned long long src = soff[k] + first[k], d0 = poff[k], n = poff[k + 1] - d0;
+  const unsigned long long c0 = (w - coff[k]) * kHistChunk;
+  unsigned long long c1 = c0 + kHistChunk;
+  if (c1 > n) c1 = n;
+  for (unsigned long long u = c0 + lane; u < c1; u += 64) {
+    nk[d0 + u] = k;
+    nt[d0 + u] = st[src + u];
+    nv[d0 + u] = sval[src + u];
+  }
+}
+
 // ---- launchers ----
 static inline unsigned win_blocks(uint64_t lanes) { return (unsigned)((lanes + kWBlock - 1) / kWBlock); }
 
@@ -391,22 +457,23 @@ static uint32_t win_stage_rows(uint64_t K, uint64_t rows, int ewma_emit, uint32_
 
 void launch_win_ewma(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *sval, const long long *st, StreamState cur,
                      double alpha, unsigned long long coop_min, const uint32_t *list, const unsigned int *count, bool emit, bool all_points,
-                     uint32_t *n_anom, const unsigned long long *off, OutRows out, uint64_t rows, int ewma_emit, uint32_t ewma_emit_rows) {
+                     uint32_t *n_anom, const unsigned long long *off, OutRows out, uint64_t rows, int ewma_emit, uint32_t ewma_emit_rows,
+                     const uint32_t *first) {
   if (K == 0) return;
   const unsigned cwaves = (unsigned)(K < 8192 ? K : 8192);   // wavefronts that stride over the list of long keys
 #define TAD_WIN_COOP(E, A)                                                                                                                     \
   hipLaunchKernelGGL((k_win_ewma_coop<E, A>), dim3(win_blocks((uint64_t)cwaves * 64)), dim3(kWBlock), 0, s, list, count, soff, sval, st, cur, \
-                     alpha, n_anom, off, out)
+                     alpha, n_anom, off, out, first)
 #define TAD_WIN(E, A)                                                                                                                              \
   do {                                                                                                                                             \
-    hipLaunchKernelGGL((k_win_ewma<E, A>), dim3(win_blocks(K)), dim3(kWBlock), 0, s, K, soff, sval, st, cur, alpha, coop_min, n_anom, off, out);   \
+    hipLaunchKernelGGL((k_win_ewma<E, A>), dim3(win_blocks(K)), dim3(kWBlock), 0, s, K, soff, sval, st, cur, alpha, coop_min, n_anom, off, out, first); \
     TAD_WIN_COOP(E, A);                                                                                                                            \
   } while (0)
   if (!emit) TAD_WIN(false, false);
   else if (all_points) TAD_WIN(true, true);
   else if (const uint32_t cap = win_stage_rows(K, rows, ewma_emit, ewma_emit_rows)) {
     hipLaunchKernelGGL(k_win_emit_staged, dim3((unsigned)((K + 63) / 64)), dim3(64), (size_t)cap * 13 + 64 * 8, s, K, soff, sval, st, cur, alpha, coop_min,
-                       off, out, cap);
+                       off, out, cap, first);
     TAD_WIN_COOP(true, false);
   } else TAD_WIN(true, false);
 #undef TAD_WIN
@@ -429,9 +496,25 @@ bool win_hist_by_sort(uint64_t window_points, uint64_t state_points) {
 }
 
 void launch_win_bounds(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, long long from_t, long long to_t,
-                       uint64_t keep_points, const uint8_t *keep, uint32_t *wbeg, uint32_t *wlen, uint32_t *ecnt, uint32_t *chunks) {
+                       uint64_t keep_points, const uint8_t *keep, uint32_t *wbeg, uint32_t *wlen, uint32_t *ecnt, uint32_t *chunks, const long long *since) {
   if (K == 0) return;
-  hipLaunchKernelGGL(k_win_bounds, dim3(win_blocks(K)), dim3(kWBlock), 0, s, K, soff, st, from_t, to_t, keep_points, keep, wbeg, wlen, ecnt, chunks);
+  hipLaunchKernelGGL(k_win_bounds, dim3(win_blocks(K)), dim3(kWBlock), 0, s, K, soff, st, from_t, to_t, keep_points, keep, since, wbeg, wlen, ecnt, chunks);
+}
+
+void launch_win_since(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, const long long *key_since, long long since_t,
+                      const SinceKeys &sk, bool lengths, unsigned long long *n_keys) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_win_since, dim3(win_blocks(K)), dim3(kWBlock), 0, s, K, soff, st, key_since, since_t, sk.first, lengths ? sk.cnt : nullptr,
+                     lengths ? sk.chunks : nullptr, n_keys);
+}
+
+uint64_t win_suffix_chunks_bound(uint64_t K, uint64_t points) { return K + points / kHistChunk + 1; }
+
+void launch_win_suffix(hipStream_t s, uint64_t K, uint64_t points, const unsigned long long *soff, const unsigned long long *sval, const long long *st,
+                       const SinceKeys &sk, const SincePts &sp) {
+  if (K == 0 || points == 0) return;
+  hipLaunchKernelGGL(k_win_suffix, dim3(win_blocks(win_suffix_chunks_bound(K, points) * 64)), dim3(kWBlock), 0, s, sk.coff, K, soff, sval, st, sk.first,
+                     sk.poff, sp.nk, sp.nt, sp.nv);
 }
 
 void launch_win_gather(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *soff,

@@ -139,7 +139,9 @@ class PeriodicalDropDetection:
     job over the concatenation would compute them); `window` returns the verdicts of a range of days of what is kept.  Owns a series +
     times state on the engine (TadEngine.drop_stream / drop_state) and the (endpoint, direction) -> key id table, ids in order of first
     appearance; the state is resized as partitions appear.  A partition's days must arrive in order: a feed with a day that is not
-    newer than the partition's newest fails as a whole and changes nothing.  Nothing is computed on the host."""
+    newer than the partition's newest fails as a whole and changes nothing — unless the feed is made with partial=True, which adds the
+    counts to the days the state holds and judges the changed partitions again from their first changed day on (TadEngine
+    .merge_stream_changes + drop_state_since).  Nothing is computed on the host."""
 
     def __init__(self, engine=None):
         self._engine = engine or _ad.get_engine()
@@ -179,8 +181,30 @@ class PeriodicalDropDetection:
             rows.append((job_type, detection_id or str(uuid.uuid4()), now, ep, di, mean, std, dd, int(x)))
         return rows
 
-    def feed(self, endpoint, direction, date, drop_number, detection_id=None):
-        """One batch -> its anomalous days as RESULT_COLUMNS tuples with job_type "periodical", in (partition, date) order."""
+    def _judge(self, key, day, count, partial, detection_id):
+        """the batch into the state, and its rows.  Whole days (the default): drop_stream, which refuses a day that is not newer than its
+        partition's newest.  partial: the counts are ADDED to what the state holds for their days (merge_stream_changes with "sum"), and
+        drop_state_since judges every changed partition over everything kept and reports its days from the first changed one on — a
+        day whose count grew is judged again."""
+        eng = self._engine
+        if not partial:
+            return self._rows(eng.drop_stream(self._state, key, day, count, agg_flow="svc", value_op="sum"), "periodical", detection_id)
+        stats = eng.merge_stream_changes(self._state, key, day, count, "device", agg_flow="svc", value_op="sum")
+        since = stats["key_since"]
+        try:
+            if stats["keys_changed"] == 0:
+                return []
+            res = eng.drop_state_since(self._state, key_since=since)
+        finally:
+            since.free()
+        return self._rows(res, "periodical", detection_id)
+
+    def feed(self, endpoint, direction, date, drop_number, detection_id=None, partial=False):
+        """One batch -> its anomalous days as RESULT_COLUMNS tuples with job_type "periodical", in (partition, date) order.
+        partial=True: the batch may hold PART of a day's drops, and a day may be split over any number of feeds, in any order: the
+        counts add up, and the feed returns the anomalous days among each changed partition's days from its first changed day on,
+        judged over everything kept.  A partition's earlier days are not reported again (their verdicts may have moved with the
+        partition's mean and std: `window` gives the whole answer)."""
         if self._dict is not None:
             raise ValueError("this instance is fed flow rows (feed_flows): its key ids come from the device dictionary")
         endpoint, direction = np.asarray(endpoint).astype(str), np.asarray(direction).astype(str)
@@ -191,16 +215,16 @@ class PeriodicalDropDetection:
             self._state = self._engine.state_create(n_keys, series=True, times=True)
         elif n_keys > self._state.num_keys:
             self._state.resize(n_keys)
-        res = self._engine.drop_stream(self._state, key, day, np.asarray(drop_number, dtype=np.uint64), agg_flow="svc", value_op="sum")
-        return self._rows(res, "periodical", detection_id)
+        return self._judge(key, day, np.asarray(drop_number, dtype=np.uint64), partial, detection_id)
 
-    def feed_flows(self, columns, dictionaries, start_time=0, end_time=0, keep=None, detection_id=None):
+    def feed_flows(self, columns, dictionaries, start_time=0, end_time=0, keep=None, detection_id=None, partial=False):
         """One batch of FLOW ROWS -> its anomalous days, as `feed` returns them for the batch's aggregated counts: drop_select -> this
         instance's key dictionary (KeyDict over kind, ns, name, direction: ids stay the same from feed to feed) -> drop_stream with
         value_op="sum" over (key id, day, 1).  columns / dictionaries / start_time / end_time / keep: as drop_detection_from_flows; the
-        dictionaries must keep their codes from feed to feed (they may grow).  A feed must hold WHOLE DAYS: the stream judges a day when
-        it arrives, so a day split over two feeds is a late row in the second and that feed is refused as a whole, as `feed` refuses
-        it.  An instance is fed either counts (`feed`) or flow rows, not both; dates come back as YYYY-MM-DD."""
+        dictionaries must keep their codes from feed to feed (they may grow).  By default a feed must hold WHOLE DAYS: the stream judges
+        a day when it arrives, so a day split over two feeds is a late row in the second and that feed is refused as a whole, as `feed`
+        refuses it.  partial=True takes a day in any number of feeds, as `feed` with partial=True does.  An instance is fed either
+        counts (`feed`) or flow rows, not both; dates come back as YYYY-MM-DD."""
         if self._keys and self._dict is None:
             raise ValueError("this instance is fed daily counts (feed): its key ids come from the host table")
         eng = self._engine
@@ -218,8 +242,7 @@ class PeriodicalDropDetection:
             self._state = eng.state_create(n_keys, series=True, times=True)
         elif n_keys > self._state.num_keys:
             self._state.resize(n_keys)
-        res = eng.drop_stream(self._state, key, rows["day_s"], rows["count"], agg_flow="svc", value_op="sum")
-        return self._rows(res, "periodical", detection_id)
+        return self._judge(key, rows["day_s"], rows["count"], partial, detection_id)
 
     def window(self, from_date=None, to_date=None, detection_id=None, direction=None, namespace=None):
         """The anomalous days with from_date <= date < to_date (None = no bound) of everything kept, each partition judged over its days

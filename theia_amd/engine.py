@@ -1304,23 +1304,60 @@ class TadEngine:
         job.flags |= narrow
         return self._state_rows("tad_run_stream", state, job, out, C.byref(cols))
 
+    def _changes(self, state, changes):
+        """-> (tad_changes or None, its key_since array or None) for changes in (None, "host", "device", "counters")"""
+        if changes is None:
+            return None, None
+        if changes not in ("host", "device", "counters"):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "changes must be None, 'host', 'device' or 'counters'")
+        self._need("STATE_ALERTS", "tad_state_merge_changes / tad_state_replace_changes")
+        if changes == "counters":
+            return capi.Changes(key_since=None, len=0, memory=capi.TAD_MEM_HOST), None
+        arr, ptr = _out_array(self, changes == "device", state.num_keys, np.int64)
+        return capi.Changes(key_since=ptr, len=state.num_keys, memory=self._out_mem(changes)), arr
+
+    @staticmethod
+    def _with_changes(stats, ch, arr):
+        """the stats dict of a merge or a replace, carrying the change report when one was asked for"""
+        if ch is not None:
+            stats.update(key_since=arr, keys_changed=ch.keys_changed, points_changed=ch.points_changed, min_t=ch.min_t, max_t=ch.max_t)
+        return stats
+
     def merge_stream(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, alpha=0.0, keep_from=0, job_id="",
                      num_keys=None, key_id2=None):
         """One batch placed BY TIME into `state` (tad_state_merge): late rows, re-sent rows, rows of a (key, flowEndSeconds) group split
         over batches.  Afterwards the state is the one a fresh state holds after one run_stream EWMA batch over its window's points plus
         this batch (without the points older than keep_from, when that is not 0).  Needs a state with series=True and times=True; use
         the same value_op for every batch of a state.  No rows: ask run_state for the window's verdicts.  Returns the call's
-        tad_merge_stats as a dict."""
+        tad_merge_stats as a dict.  merge_stream_changes is this call with a report of what it changed."""
+        return self._merge(state, key_id, flow_end_s, value, agg_flow, value_op, lattice, alpha, keep_from, job_id, num_keys, key_id2, None)
+
+    def merge_stream_changes(self, state, key_id, flow_end_s, value, changes="host", **kw):
+        """merge_stream (whose other arguments go through **kw) with the change report (tad_state_merge_changes): the returned dict also
+        carries key_since — one int64 per key of the state, a numpy array (changes="host") or a DeviceArray ("device"): the smallest
+        flowEndSeconds at which the key's series changed, capi.TAD_NO_CHANGE where it did not — and keys_changed, points_changed, min_t,
+        max_t; changes="counters": those four alone (key_since None).  A point is changed when it was added, or combined into another
+        value: a sum of 0 and a maximum not above the held value change nothing."""
+        if changes is None:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "changes must be 'host', 'device' or 'counters'")
+        return self._merge(state, key_id, flow_end_s, value, changes=changes, **kw)
+
+    def _merge(self, state, key_id, flow_end_s, value, agg_flow="", value_op="auto", lattice=None, alpha=0.0, keep_from=0, job_id="",
+               num_keys=None, key_id2=None, changes=None):
         if not self._lib.tad_features() & capi.TAD_FEATURE_STATE_MERGE:
             raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "this build of the library has no tad_state_merge (TAD_FEATURE_STATE_MERGE)")
         cols, narrow, keep = self._stream_columns(state, key_id, flow_end_s, value, key_id2, num_keys, lattice)
         job = capi.Job(algo=capi.TAD_ALGO["EWMA"], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
                        flags=narrow, id=job_id.encode()[:63])
         stats = capi.MergeStats()
-        rc = self._lib.tad_state_merge(self._h, state._h, C.byref(job), C.byref(cols), int(keep_from), C.byref(stats))
+        ch, arr = self._changes(state, changes)
+        if ch is None:
+            rc = self._lib.tad_state_merge(self._h, state._h, C.byref(job), C.byref(cols), int(keep_from), C.byref(stats))
+        else:
+            rc = self._lib.tad_state_merge_changes(self._h, state._h, C.byref(job), C.byref(cols), int(keep_from), C.byref(stats), C.byref(ch))
         del keep
         self._check(rc)
-        return {name: getattr(stats, name) for name, _ in capi.MergeStats._fields_ if not name.startswith("reserved")}
+        return self._with_changes({name: getattr(stats, name) for name, _ in capi.MergeStats._fields_ if not name.startswith("reserved")}, ch, arr)
 
     def replace_stream(self, state, key_id, flow_end_s, value, from_t=0, to_t=0, ranged=False, agg_flow="", value_op="auto", lattice=None,
                        alpha=0.0, keep_from=0, job_id="", num_keys=None, key_id2=None):
@@ -1328,17 +1365,33 @@ class TadEngine:
         value instead of being combined with it, so a re-read of the same rows leaves the same state under sum as under max.
         ranged=True: the batch is ALL rows with from_t <= flowEndSeconds < to_t (0 = no bound on that side), and every point of the
         state inside that range that the batch does not name is erased, on every key; an empty batch then still erases the range.
-        The other arguments are merge_stream's.  Returns the call's tad_replace_stats as a dict."""
+        The other arguments are merge_stream's.  Returns the call's tad_replace_stats as a dict.  replace_stream_changes is this call
+        with a report of what it changed."""
+        return self._replace(state, key_id, flow_end_s, value, from_t, to_t, ranged, agg_flow, value_op, lattice, alpha, keep_from, job_id, num_keys,
+                             key_id2, None)
+
+    def replace_stream_changes(self, state, key_id, flow_end_s, value, changes="host", **kw):
+        """replace_stream (whose other arguments go through **kw) with the change report (tad_state_replace_changes), carried by the
+        returned dict as by merge_stream_changes'.  Changed points: added, erased by the range, or replaced by another value — a
+        replace by the held value changes nothing, so the same re-read twice reports keys_changed == 0 the second time."""
+        if changes is None:
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "changes must be 'host', 'device' or 'counters'")
+        return self._replace(state, key_id, flow_end_s, value, changes=changes, **kw)
+
+    def _replace(self, state, key_id, flow_end_s, value, from_t=0, to_t=0, ranged=False, agg_flow="", value_op="auto", lattice=None,
+                 alpha=0.0, keep_from=0, job_id="", num_keys=None, key_id2=None, changes=None):
         self._need("STATE_REPLACE", "tad_state_replace")
         cols, narrow, keep = self._stream_columns(state, key_id, flow_end_s, value, key_id2, num_keys, lattice)
         job = capi.Job(algo=capi.TAD_ALGO["EWMA"], agg_flow=capi.TAD_AGG[agg_flow], value_op=capi.TAD_OP[value_op], ewma_alpha=float(alpha),
                        flags=narrow, id=job_id.encode()[:63])
         stats = capi.ReplaceStats()
-        rc = self._lib.tad_state_replace(self._h, state._h, C.byref(job), C.byref(cols), capi.TAD_REPLACE_RANGE if ranged else 0, int(from_t),
-                                         int(to_t), int(keep_from), C.byref(stats))
+        ch, arr = self._changes(state, changes)
+        args = (self._h, state._h, C.byref(job), C.byref(cols), capi.TAD_REPLACE_RANGE if ranged else 0, int(from_t), int(to_t), int(keep_from),
+                C.byref(stats))
+        rc = self._lib.tad_state_replace(*args) if ch is None else self._lib.tad_state_replace_changes(*args, C.byref(ch))
         del keep
         self._check(rc)
-        return {name: getattr(stats, name) for name, _ in capi.ReplaceStats._fields_ if not name.startswith("reserved")}
+        return self._with_changes({name: getattr(stats, name) for name, _ in capi.ReplaceStats._fields_ if not name.startswith("reserved")}, ch, arr)
 
     def run_state(self, state, algo="EWMA", alpha=0.0, eps=0.0, min_samples=0, maxiter=0, emit_all=False, out="host", job_id=""):
         """The batch job's verdicts over everything `state` holds, from the state alone (tad_run_state): exactly the rows run() returns
@@ -1408,6 +1461,64 @@ class TadEngine:
         ptr, n, mem, alive = self._key_mask(key_keep)
         job = self._detector_job("DROP", nsigma=nsigma, min_samples=min_samples, emit_all=emit_all, job_id=job_id)
         return self._state_rows("tad_drop_state_keys", state, job, out, int(from_t), int(to_t), int(keep_points), ptr, n, mem)
+
+    # ---- judge the window, report from a time on (tad_run_state_since / tad_drop_state_since) ----
+    def _report_window(self, state, since_t, key_since, key_keep, from_t, to_t, keep_points):
+        """-> (tad_report_window, what must stay alive): both arrays in one memory — when one is a DeviceArray the other is copied there"""
+        alive = []
+        dev = isinstance(key_since, DeviceArray) or isinstance(key_keep, DeviceArray)
+
+        def place(x, dtype, what):
+            if x is None:
+                return None
+            if isinstance(x, DeviceArray):
+                n = x.n * x.dtype.itemsize // np.dtype(dtype).itemsize
+                if dtype == np.int64 and x.dtype.itemsize != 8:
+                    raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "%s on the device must hold 8-byte elements" % what)
+                if n < state.num_keys:
+                    raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "%s has room for %d entries, the state holds %d keys" % (what, n, state.num_keys))
+                alive.append(x)
+                return x.ptr
+            a = np.ascontiguousarray(np.asarray(x).astype(dtype, copy=False)).reshape(-1)
+            if a.size != state.num_keys:
+                raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "%s has %d entries, the state holds %d keys" % (what, a.size, state.num_keys))
+            if dev:   # (a byte mask travels in 8-byte elements, as KeyDict.select's does)
+                pad = np.zeros((a.nbytes + 7) // 8 * 8 if a.nbytes else 8, np.uint8)
+                pad[:a.nbytes] = a.view(np.uint8)
+                a = DeviceArray.from_host(self, pad.view(np.uint64))
+                alive.append(a)
+                return a.ptr
+            alive.append(a)
+            return a.ctypes.data if a.size else None
+        w = capi.ReportWindow(from_t=int(from_t), to_t=int(to_t), keep_points=int(keep_points), key_keep=place(key_keep, np.uint8, "key_keep"),
+                              key_since=place(key_since, np.int64, "key_since"), since_t=int(since_t), num_keys=state.num_keys,
+                              key_memory=capi.TAD_MEM_DEVICE if dev else capi.TAD_MEM_HOST)
+        return w, alive
+
+    def run_state_since(self, state, since_t=0, key_since=None, key_keep=None, from_t=0, to_t=0, keep_points=0, algo="EWMA", alpha=0.0, eps=0.0,
+                        min_samples=0, maxiter=0, emit_all=False, out="host", job_id=""):
+        """run_state_keys that reports from a time on, read-only (tad_run_state_since): the window (from_t, to_t, keep_points) and the
+        keys (key_keep) are judged exactly as run_state_keys judges them, and of its rows the call returns those with flow_end_s >=
+        since_t (0 = no such bound) and >= key_since[key] — one int64 per key, a numpy array or a DeviceArray such as
+        merge_stream_changes / replace_stream_changes return; a key whose entry is capi.TAD_NO_CHANGE is not selected at all.  Same
+        order, same bits.  A changed key's points before its first changed time may have changed verdict and are not reported: that is
+        the stream's rule, run_state_keys gives the whole answer."""
+        job = self._detector_job(algo, alpha, eps, min_samples, maxiter, emit_all=emit_all, job_id=job_id)
+        self._need("STATE_ALERTS", "tad_run_state_since")
+        w, alive = self._report_window(state, since_t, key_since, key_keep, from_t, to_t, keep_points)
+        res = self._state_rows("tad_run_state_since", state, job, out, C.byref(w))
+        del alive
+        return res
+
+    def drop_state_since(self, state, since_t=0, key_since=None, key_keep=None, from_t=0, to_t=0, keep_points=0, nsigma=0.0, min_samples=0,
+                         emit_all=False, out="host", job_id=""):
+        """drop_state_keys that reports from a time on, read-only (tad_drop_state_since); the arguments are run_state_since's"""
+        self._need("STATE_ALERTS", "tad_drop_state_since")
+        job = self._detector_job("DROP", nsigma=nsigma, min_samples=min_samples, emit_all=emit_all, job_id=job_id)
+        w, alive = self._report_window(state, since_t, key_since, key_keep, from_t, to_t, keep_points)
+        res = self._state_rows("tad_drop_state_since", state, job, out, C.byref(w))
+        del alive
+        return res
 
     # ---- the drop job's flow-row query (tad_drop_select) ----
     def drop_select(self, ingress_action, egress_action, flow_start_s, src_ip, src_pod_ns, src_pod_name, dst_ip, dst_pod_ns, dst_pod_name,

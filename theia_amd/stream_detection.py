@@ -176,11 +176,15 @@ class StreamingAnomalyDetection:
         (TadEngine.replace_stream with ranged=True): feeding the same range again, or an overlapping one, leaves every point once,
         where the default feed would double it.  A re-read in which no row passes the row predicates still erases the range.
         Returns the replace's statistics (None only when there is no state yet and nothing to erase)."""
+        return self._feed(flows, replace, None)
+
+    def _feed(self, flows, replace, changes):
+        """feed; changes: None, or where the change report of the merge / replace goes (TadEngine.merge_stream_changes)"""
         self._usable()
         eng = self._engine
         n = len(flows["flowEndSeconds"])
         if n == 0 and replace is not None:
-            return self._erase(replace)
+            return self._erase(replace, changes)
         keep = np.ones(n, dtype=bool)
         if self.ns_ignore_list:
             ign = np.asarray(list(self.ns_ignore_list), dtype=str)
@@ -194,7 +198,7 @@ class StreamingAnomalyDetection:
                 codes = [_encode(self._vocab[0], flows, side + "PodNamespace"), _encode(self._vocab[1], flows, side + ident)]
                 sides.append((codes, keep & (codes[1] != _code_of(self._vocab[1], ""))))
             if not (sides[0][1].any() or sides[1][1].any()):
-                return self._erase(replace)
+                return self._erase(replace, changes)
             key, key2, _, _ = self._dict.encode(sides[0][0], sides[0][1], sides[1][0], sides[1][1], max_new=0)
         else:
             name = "destinationIP" if self.agg_flow == "external" else "destinationServicePortName"
@@ -204,7 +208,7 @@ class StreamingAnomalyDetection:
             else:
                 keep &= codes != _code_of(self._vocab[0], "")
             if not keep.any():
-                return self._erase(replace)
+                return self._erase(replace, changes)
             key, key2, _, _ = self._dict.encode([codes], keep, max_new=0)
         num_keys = self.num_keys
         if self._state is None:
@@ -212,17 +216,61 @@ class StreamingAnomalyDetection:
         elif num_keys > self._state.num_keys:
             self._state.resize(num_keys)
         if replace is not None:
-            return eng.replace_stream(self._state, key, flow_end, value, from_t=int(replace[0]), to_t=int(replace[1]), ranged=True,
-                                      agg_flow=self.agg_flow, key_id2=key2)
+            kw = dict(from_t=int(replace[0]), to_t=int(replace[1]), ranged=True, agg_flow=self.agg_flow, key_id2=key2)
+            if changes:
+                return eng.replace_stream_changes(self._state, key, flow_end, value, changes, **kw)
+            return eng.replace_stream(self._state, key, flow_end, value, **kw)
+        if changes:
+            return eng.merge_stream_changes(self._state, key, flow_end, value, changes, agg_flow=self.agg_flow, key_id2=key2)
         return eng.merge_stream(self._state, key, flow_end, value, agg_flow=self.agg_flow, key_id2=key2)
 
-    def _erase(self, replace):
+    def _erase(self, replace, changes=None):
         """a feed without a live row: nothing to merge; a re-read of a range still says that the range holds nothing"""
         if replace is None or self._state is None:
             return None
         none = np.zeros(0, dtype=np.uint64)
-        return self._engine.replace_stream(self._state, none, np.zeros(0, dtype=np.int64), none, from_t=int(replace[0]), to_t=int(replace[1]),
-                                           ranged=True, agg_flow=self.agg_flow)
+        kw = dict(from_t=int(replace[0]), to_t=int(replace[1]), ranged=True, agg_flow=self.agg_flow)
+        if changes:
+            return self._engine.replace_stream_changes(self._state, none, np.zeros(0, dtype=np.int64), none, changes, **kw)
+        return self._engine.replace_stream(self._state, none, np.zeros(0, dtype=np.int64), none, **kw)
+
+    def feed_alerts(self, flows, algo_type, tad_id, replace=None, pod_label="", pod_name="", pod_namespace="", external_ip="", svc_port_name=""):
+        """feed, and what it made anomalous -> (the feed's statistics with the change report's counters, list of result rows).  The
+        feed runs with a change report on the device (TadEngine.merge_stream_changes / replace_stream_changes): per key, the smallest
+        flowEndSeconds at which the key's series changed.  Then TadEngine.run_state_since judges the keys that changed AND pass the
+        job's name filters (KeyDict.select, as `job`) over everything they hold, and reports every changed key's points from its
+        first changed time on.  The rows have `job`'s shape and are decoded on the device as `job`'s are; there is NO sentinel row: no
+        anomaly is an empty list.  The same re-read fed twice changes nothing the second time and returns no rows.
+
+        What is not reported: a changed key's points BEFORE its first changed time.  A late point moves the whole key's stddev (and
+        DBSCAN's neighbourhoods, ARIMA's lambda), so their verdicts may have changed as well; that is the stream's rule — each point
+        once, when it arrives or changes — and `job` gives the whole answer."""
+        if algo_type not in _ad.VALID_ALGOS:
+            raise ValueError("Algorithm should be in {}".format(" or ".join(_ad.VALID_ALGOS)))
+        filters = (pod_label or "", pod_name or "", pod_namespace or "", external_ip or "", svc_port_name or "")
+        self._terms(*filters)      # (a filter this instance does not serve is refused before the feed changes anything)
+        stats = self._feed(flows, replace, "device")
+        if stats is None:
+            return None, []
+        since = stats.pop("key_since")
+        try:
+            if stats["keys_changed"] == 0:
+                return stats, []
+            keep, _ = self._dict.select(self._terms(*filters), out="device")      # (the masks: over the vocabularies as the feed left them)
+            res = self._engine.run_state_since(self._state, key_since=since, key_keep=keep, algo=algo_type, job_id=str(tad_id or ""))
+        finally:
+            since.free()
+        if res.n_rows == 0:
+            return stats, []
+        decoder = _KeyDecoder(self._dict, self._vocab)
+        table = {name: _KeyColumn(decoder, "direction" if name == "direction" else i) for i, name in enumerate(_ad.KEY_COLUMNS[self.mode])}
+        prep = _ad.PreparedColumns(self.mode, None, None, None, None, None, table, 0, 0)
+        return stats, _ad.result_rows(prep, res, algo_type, self.agg_flow, tad_id)
+
+    def poll_alerts(self, client, now, lag_s, algo_type, tad_id, **filters):
+        """One turn of `poll` that also returns what the turn made anomalous -> (statistics, rows) as feed_alerts: the lagged range is
+        re-read and REPLACES those seconds, so a turn made twice (a timeout, a restart) returns no rows the second time."""
+        return self._poll(client, now, lag_s, lambda flows, replace: self.feed_alerts(flows, algo_type, tad_id, replace=replace, **filters))
 
     def poll(self, client, now, lag_s):
         """One turn of the poll loop against the flow table: read the instance's rows with watermark - lag_s <= flowEndSeconds < now
@@ -231,6 +279,9 @@ class StreamingAnomalyDetection:
         missing at the previous turn: they are read again, and because the read REPLACES those seconds a row seen twice counts once.
         The turn is idempotent: after a timeout or a restart (the watermark travels in snapshot() / restore()) it can simply be made
         again.  The first turn reads everything before `now`.  Returns the replace's statistics (None: nothing held, nothing read)."""
+        return self._poll(client, now, lag_s, lambda flows, replace: self.feed(flows, replace=replace))
+
+    def _poll(self, client, now, lag_s, feed):
         from . import clickhouse as _ch
         now, lag_s = int(now), int(lag_s)
         if lag_s < 0:
@@ -243,9 +294,9 @@ class StreamingAnomalyDetection:
             flows = {c: np.zeros(0, dtype=np.int64 if c.endswith("Seconds") or c in ("flowType", "throughput") else str)
                      for c in _ch.stream_rows_columns(self.agg_flow, self.pod_ident, list(self.ns_ignore_list))}
         flows["throughput"] = np.asarray(flows["throughput"]).astype(np.uint64)
-        stats = self.feed(flows, replace=(from_t, now))
+        out = feed(flows, (from_t, now))
         self.watermark = now
-        return stats
+        return out
 
     def _equal(self, col, s):
         return col, self._vocab[col].match(_capi.TAD_STR_EQUAL, s, out="device")[0]

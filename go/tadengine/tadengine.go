@@ -2150,6 +2150,80 @@ func (s *State) DropSince(job Job, nSigma float64, minSamples int32, w ReportWin
 	return s.resultRows(res), nil
 }
 
+var stateBucketsOnce sync.Once
+var stateBucketsOK bool
+
+// hasStateBuckets: the library knows tad_run_state_buckets (tad_features); an older one would not export it.
+func hasStateBuckets() bool {
+	stateBucketsOnce.Do(func() { stateBucketsOK = C.tad_features()&C.TAD_FEATURE_STATE_BUCKETS != 0 })
+	return stateBucketsOK
+}
+
+var errNoStateBuckets = errors.New("tadengine: libtad_mi355x.so has no bucketed state job (TAD_FEATURE_STATE_BUCKETS)")
+
+// ValueOp is how the points of one bucket are folded (tad_value_op): OpSum wraps mod 2^64, OpMax is the unsigned maximum.
+type ValueOp int
+
+const (
+	OpMax ValueOp = ValueOp(C.TAD_OP_MAX)
+	OpSum ValueOp = ValueOp(C.TAD_OP_SUM)
+)
+
+// BucketWindow is a ReportWindow whose judged points are folded into time buckets (tad_bucket_window): a point of second t lies in the
+// bucket that starts at Origin + BucketS*floor((t-Origin)/BucketS), the points of a bucket are summed (mod 2^64) or, with Op == OpMax,
+// reduced to their maximum, and the bucket's start stands in the rows' FlowEndS.  BucketS >= 1, 0 <= Origin < BucketS; Op is OpSum or
+// OpMax.  The window (FromT, ToT, KeepPoints, KeyKeep) acts on the raw points, first; a bucket is reported iff it starts at or after the
+// start of the bucket that holds the since threshold.
+type BucketWindow struct {
+	ReportWindow
+	BucketS int64
+	Origin  int64
+	Op      ValueOp
+}
+
+// RunBuckets judges the state's window in time buckets, read-only (tad_run_state_buckets): exactly the rows Engine.Run returns for the
+// window's rows with their times floored to the bucket starts and ValueOp = w.Op.  BucketS == 1 is RunKeys / RunSince.
+func (s *State) RunBuckets(job Job, w BucketWindow) ([]Row, error) {
+	if !hasStateBuckets() {
+		return nil, errNoStateBuckets
+	}
+	if !s.series || !s.times {
+		return nil, IllegalArgument{"tadengine: RunBuckets needs a state made by NewStateWithTimes"}
+	}
+	if job.Algo == DBSCAN && !s.history {
+		return nil, IllegalArgument{"tadengine: RunBuckets with DBSCAN needs a state made by NewStateWithTimes with history"}
+	}
+	if w.BucketS < 1 || w.Origin < 0 || w.Origin >= w.BucketS {
+		return nil, IllegalArgument{"tadengine: BucketS must be >= 1 and 0 <= Origin < BucketS"}
+	}
+	cj := keysJob(job)
+	rw, err := w.ReportWindow.c()
+	if err != nil {
+		return nil, err
+	}
+	var cw C.tad_bucket_window
+	cw.from_t, cw.to_t, cw.keep_points, cw.since_t = rw.from_t, rw.to_t, rw.keep_points, rw.since_t
+	cw.key_keep, cw.key_since, cw.num_keys, cw.key_memory = rw.key_keep, rw.key_since, rw.num_keys, rw.key_memory
+	cw.bucket_s, cw.bucket_origin, cw.bucket_op = C.int64_t(w.BucketS), C.int64_t(w.Origin), C.tad_value_op(w.Op)
+	var pin runtime.Pinner // (the struct points into Go memory: cgo passes &cw, the slices it names are pinned for the call)
+	defer pin.Unpin()
+	if len(w.KeyKeep) > 0 {
+		pin.Pin(&w.KeyKeep[0])
+	}
+	if len(w.KeySince) > 0 {
+		pin.Pin(&w.KeySince[0])
+	}
+	var res *C.tad_result
+	if rc := C.tad_run_state_buckets(s.e.h, s.h, &cj, &cw, C.TAD_MEM_HOST, &res); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return nil, IllegalArgument{msg}
+		}
+		return nil, fmt.Errorf("tad_run_state_buckets: %s (code %d)", msg, int(rc))
+	}
+	return s.resultRows(res), nil
+}
+
 var stringDictOnce sync.Once
 var stringDictOK bool
 

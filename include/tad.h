@@ -756,6 +756,55 @@ typedef struct {
 int tad_run_state_since(tad_engine *e, tad_state *s, const tad_job *job, const tad_report_window *w, tad_mem out_memory, tad_result **out);
 int tad_drop_state_since(tad_engine *e, tad_state *s, const tad_job *job, const tad_report_window *w, tad_mem out_memory, tad_result **out);
 
+/* ---- a state judged in time buckets (TAD_FEATURE_STATE_BUCKETS; check tad_features() before calling this) ----
+ * A state keeps every key's series at the resolution of flow_end_s, one second, and every read-only job above judges those per-second
+ * points.  Throughput is looked at per interval (the reference's dashboards group by $__timeInterval(flowEndSeconds)); this call judges
+ * the state at that resolution without the rows leaving the device: the report window of tad_run_state_since plus a bucket length, an
+ * origin and the operation that folds a bucket's points.
+ * Contract: let W' be the rows tad_run_state_keys judges for the same from_t / to_t / keep_points and key_keep — one row per point; the
+ * window is applied FIRST, on the raw points, and keep_points counts points, not buckets.  Let W'' be W' with flow_end_s replaced by
+ *     bucket_origin + bucket_s * floor((flow_end_s - bucket_origin) / bucket_s)
+ * (FLOOR division: a time below the origin, below zero too, rounds down).  The call returns exactly the rows tad_run returns for W''
+ * with value_op = bucket_op and the same algo, detector parameters and TAD_FLAG_EMIT_ALL_POINTS: the same (key, time) order, bit for bit.
+ * The bucket's start stands in flow_end_s; a bucket cut by from_t / to_t / keep_points holds only the window's points.  bucket_s = 1
+ * with bucket_origin = 0 therefore IS the *_keys call (through the bucket kernels).  Integer sums wrap mod 2^64 and maxima are unsigned,
+ * as in Stage 0, so the fold does not depend on any order.  Read-only: whether the call succeeds or not, the state is bit for bit what
+ * it was.  Domain of the time arithmetic: |flow_end_s| < 2^62 and bucket_s <= 2^40; outside it the bucket starts wrap (defined, and the
+ * same on host and device: csrc/tad_bucket.h), they are no longer the mathematical floor.
+ * The since rule (key_since / since_t as in tad_report_window): the threshold of key k is the larger of since_t and key_since[k]; a
+ * BUCKET is reported iff its start >= the start of the threshold's bucket — so every bucket that holds a point at or after the
+ * threshold is reported, whole.  TAD_NO_CHANGE deselects the key.  The rows are those of the same call without a since, restricted to
+ * the reported buckets, bit for bit; every selected key is still judged over all its buckets.
+ * Refusals: everything tad_run_state_since refuses, plus a NULL bucket window, bucket_s < 1, bucket_origin outside [0, bucket_s), a
+ * bucket_op other than TAD_OP_SUM / TAD_OP_MAX (TAD_OP_AUTO too: a state does not remember which of the two built it) and TAD_ALGO_DROP
+ * (the drop job buckets by day in tad_drop_select).
+ * tad_stats: rows_in = rows_used = the window's RAW points; n_points = the buckets; n_keys and t0 are over the buckets (t0: the smallest
+ * bucket start); the moments and the ARIMA counters as tad_run over W'' reports them.  host_syncs: 2 on an empty state, 3 when the
+ * window is empty, else 4 — tad_run_state_keys' 3 plus one, the bucket total being read before the view is sized — plus the since's one
+ * for DBSCAN and ARIMA.  Unlike the *_keys calls a window that leaves every key whole, or no window at all, still builds a view.
+ * How: times ascend per key, so a bucket is a contiguous run of a key's window range — a segmented fold and a compaction, no sort, no
+ * hash.  Two passes over the window's chunks of 2048 points (heads per chunk, then the fold: ballot ranks and a segmented scan by
+ * shuffles per 64 points; a run that crosses a chunk edge is combined by 64-bit integer atomics), straight from the state's arrays: no
+ * unbucketed copy of the window is written.  Moments: a key with a point cut or folded away is replayed over its buckets, as for a
+ * window.  DBSCAN's history: the buckets' values sorted per key.
+ * Memory outside the state (job-context workspace, as tad_run_state_window's): 16 B per bucket, 8 B more for DBSCAN, 12 B per chunk
+ * (one chunk per key and per 2048 points of the state) and about 100 B per key. */
+#define TAD_FEATURE_STATE_BUCKETS 262144u /* tad_run_state_buckets: a state's window judged in time buckets, read-only */
+typedef struct {
+  int64_t from_t;                    /* tad_run_state_window's window, on the RAW points, applied first */
+  int64_t to_t;
+  uint64_t keep_points;
+  const uint8_t *key_keep;           /* tad_run_state_keys' mask or NULL */
+  const int64_t *key_since;          /* tad_run_state_since's report rule, per key, or NULL */
+  int64_t since_t;                   /* 0 = none */
+  uint64_t num_keys;                 /* as tad_report_window */
+  tad_mem key_memory;
+  int64_t bucket_s;                  /* >= 1 */
+  int64_t bucket_origin;             /* 0 <= bucket_origin < bucket_s */
+  tad_value_op bucket_op;            /* TAD_OP_SUM or TAD_OP_MAX (TAD_OP_AUTO is refused) */
+} tad_bucket_window;
+int tad_run_state_buckets(tad_engine *e, tad_state *s, const tad_job *job, const tad_bucket_window *w, tad_mem out_memory, tad_result **out);
+
 /* ---- the batch verdicts over a time range of a state (TAD_FEATURE_STATE_WINDOW; check tad_features() before calling this) ----
  * tad_run_state judges everything the state holds, and tad_state_trim narrows a state for good and at its old end only.  A state that
  * keeps seven days can answer "the last 24 h" or "everything up to the last complete hour" with this call: read-only, any window the

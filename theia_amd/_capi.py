@@ -40,7 +40,8 @@ TAD_FEATURE_DICT_DECODE = 8192               # tad_features() bit: tad_keydict_g
 TAD_FEATURE_STRING_RETIRE = 16384            # tad_features() bit: tad_keydict_mark_codes, tad_strdict_compact, tad_keydict_recode: dead strings dropped, codes renumbered
 TAD_FEATURE_STRING_LIKE = 32768              # tad_features() bit: tad_strdict_like: LIKE / ilike patterns with % and _ matched on the device
 TAD_FEATURE_STATE_ALERTS = 131072            # tad_features() bit: tad_state_merge_changes / tad_state_replace_changes: what a merge or a replace changed; tad_run_state_since / tad_drop_state_since
-TAD_NO_CHANGE = (1 << 63) - 1                # tad_changes.key_since: the key's series did not change
+TAD_FEATURE_STATE_BUCKETS = 262144           # tad_features() bit: tad_run_state_buckets: a state's window judged in time buckets
+TAD_NO_CHANGE = (1 << 63) - 1               # tad_changes.key_since: the key's series did not change
 TAD_LIKE_NOCASE = 1                          # tad_strdict_like flags: compare after folding 'A'..'Z' to 'a'..'z' (ilike)
 TAD_CODE_NONE = -1                           # tad_strdict_lookup: the string is not in the dictionary
 TAD_STR_EQUAL, TAD_STR_CONTAINS_NOCASE = 0, 1   # tad_strdict_match: the value is the pattern / the pattern occurs in it, ASCII letters without case
@@ -151,6 +152,11 @@ class ReportWindow(C.Structure):
                 ("num_keys", u64), ("key_memory", C.c_int)]
 
 
+class BucketWindow(C.Structure):
+    """tad_bucket_window: tad_report_window plus the bucket length, origin and folding operation of tad_run_state_buckets."""
+    _fields_ = ReportWindow._fields_ + [("bucket_s", i64), ("bucket_origin", i64), ("bucket_op", C.c_int)]
+
+
 class CompactStats(C.Structure):
     """tad_compact_stats: what one tad_state_compact call retired and moved."""
     _fields_ = [("keys_before", u64), ("keys_after", u64), ("num_keys", u64), ("keys_unseen", u64), ("keys_idle", u64), ("points_dropped", u64),
@@ -254,6 +260,7 @@ SYMBOLS = {
     "tad_drop_state_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), i64, i64, u64, C.c_void_p, u64, C.c_int, C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_run_state_since": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(ReportWindow), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_drop_state_since": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(ReportWindow), C.c_int, C.POINTER(C.POINTER(Result))]),
+    "tad_run_state_buckets": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(BucketWindow), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_drop_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),
     "tad_drop_select": (C.c_int, [C.c_void_p, C.POINTER(DropFlowColumns), i64, i64, C.c_int, C.POINTER(C.POINTER(DropRows))]),
     "tad_drop_rows_free": (None, [C.c_void_p, C.POINTER(DropRows)]),

@@ -13,7 +13,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libtad_mi355x.so")
 SOURCES = ["tad_kernels.hip", "tad_stage0_part.hip", "tad_dbscan.hip", "tad_history.hip", "tad_window.hip", "tad_merge.hip", "tad_arima.hip", "tad_drop.hip", "tad_drop_state.hip", "tad_drop_select.hip", "tad_synth.hip", "tad_shard.hip", "tad_sparse.hip", "tad_factorize.hip", "tad_keydict.hip", "tad_strdict.hip", "tad_compact.hip", "tad_ingest.hip", "tad_engine.cpp", "tad_capi.cpp", "tad_capi_job.cpp", "tad_capi_view.cpp", "tad_capi_state.cpp", "tad_capi_ingest.cpp", "tad_capi_keydict.cpp", "tad_capi_strdict.cpp", "tad_capi_series.cpp"]
-HEADERS = [os.path.join(CSRC, "tad_internal.h"), os.path.join(CSRC, "tad_rows.h"), os.path.join(CSRC, "tad_engine.h"), os.path.join(CSRC, "tad_detmath.h"), os.path.join(CSRC, "tad_dev_err.h"), os.path.join(CSRC, "tad_stage0_retry.h"), os.path.join(CSRC, "tad_carve.h"), os.path.join(CSRC, "tad_strbytes.h"), os.path.join(CSRC, "tad_like.h"), os.path.join(CSRC, "tad_slots.h"), os.path.join(CSRC, "tad_capi_dict.h"), os.path.join(REPO_ROOT, "include", "tad.h")]
+HEADERS = [os.path.join(CSRC, "tad_internal.h"), os.path.join(CSRC, "tad_rows.h"), os.path.join(CSRC, "tad_engine.h"), os.path.join(CSRC, "tad_detmath.h"), os.path.join(CSRC, "tad_dev_err.h"), os.path.join(CSRC, "tad_stage0_retry.h"), os.path.join(CSRC, "tad_carve.h"), os.path.join(CSRC, "tad_strbytes.h"), os.path.join(CSRC, "tad_like.h"), os.path.join(CSRC, "tad_slots.h"), os.path.join(CSRC, "tad_capi_dict.h"), os.path.join(CSRC, "tad_bucket.h"), os.path.join(REPO_ROOT, "include", "tad.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
          "-Wno-unused-value", "-Wno-unused-result"]
 

@@ -3,7 +3,10 @@
 // mask, any of them absent — whose view is built in the context's workspace (window_bounds, window_gather; kernels: tad_window.hip), and
 // one job on that view (run_view_locked), which runs the stream batches' detectors (tad_capi.cpp) with every point of the view named as
 // new.  tad_run_state_since / tad_drop_state_since are the same call with a Since: the view is judged whole, and only every key's points
-// from a time on are named as new (the stream's own rule: a per-key suffix).  Nothing here writes the state.
+// from a time on are named as new (the stream's own rule: a per-key suffix).  tad_run_state_buckets is the same call with three more
+// fields of the window: the judged points are folded into time buckets (window_buckets in window_gather's place) and the view's points
+// are the buckets.  Nothing here writes the state.
+#include "tad_bucket.h"
 #include "tad_engine.h"
 
 using namespace tad;
@@ -42,6 +45,7 @@ struct Since {
   const long long *key_since = nullptr;
   long long since_t = 0;
   SinceKeys keys{};
+  long long bucket_s = 0, bucket_origin = 0;   // tad_run_state_buckets: the threshold is floored to its bucket's start (0: not bucketed)
 };
 
 // Before the round trip: the routing, the moments, the detector and its row total.  EWMA walks the CSR series; DBSCAN, ARIMA and DROP
@@ -72,7 +76,8 @@ int view_detect(JobCtx *e, const StateView &v, const JobParams &jp, const Since 
     // EWMA's anomalous rows need first[k] alone: the walk counts them itself, so no suffix length is written and nothing is scanned
     const bool first_only = jp.algo == TAD_ALGO_EWMA && !jp.all_points;
     const bool ewma_all = jp.algo == TAD_ALGO_EWMA && jp.all_points;
-    launch_win_since(s, K, v.soff, v.st, since->key_since, since->since_t, sk, !first_only, jp.algo == TAD_ALGO_DROP ? &ctr->n_keys : nullptr);
+    launch_win_since(s, K, v.soff, v.st, since->key_since, since->since_t, sk, !first_only, jp.algo == TAD_ALGO_DROP ? &ctr->n_keys : nullptr,
+                     since->bucket_s, since->bucket_origin);
     if (!first_only) launch_scan(s, sk.cnt, sk.poff, K, scratch, ewma_all ? dev_total(e) : nullptr);   // (EWMA with every point: the row total)
     vj->first = sk.first;
     if (ewma_all) { vj->off = sk.poff; return TAD_OK; }
@@ -112,9 +117,10 @@ int view_detect(JobCtx *e, const StateView &v, const JobParams &jp, const Since 
 }
 
 // After the round trip (c: the job's counters as the host read them): the result, the emit, the stats.  view_syncs: the host
-// synchronisations the caller spent on building the view (tad_stats.host_syncs).
+// synchronisations the caller spent on building the view (tad_stats.host_syncs).  raw_points: the state's points behind a bucketed view
+// (tad_stats.rows_in / rows_used); 0: the view's own
 int view_rows(JobCtx *e, const StateView &v, const tad_job *job, const JobParams &jp, const ViewJob &vj, const DevCounters &c, uint64_t rows,
-              tad_mem out_memory, tad_result **out, int view_syncs) {
+              tad_mem out_memory, tad_result **out, int view_syncs, uint64_t raw_points) {
   hipStream_t s = e->stream;
   const uint64_t P = v.P;
   RowsOut ro;
@@ -127,7 +133,8 @@ int view_rows(JobCtx *e, const StateView &v, const tad_job *job, const JobParams
     emit_point_rows(s, jp, vj.hist, vj.ab, vj.db, v.mom, ro.dev_rows);
   if ((rc = finish_rows(e, job, &ro, rows, jp.all_points, c, P != 0)) != TAD_OK) return rc;
   tad_stats &rs = ro.rp->pub.stats;
-  rs.rows_in = rs.rows_used = rs.n_points = P;
+  rs.n_points = P;
+  rs.rows_in = rs.rows_used = raw_points ? raw_points : P;
   {
     unsigned long long tmin = ~0ull;
     memcpy(&tmin, e->tail_host + kTailHistLen, 8);
@@ -145,7 +152,7 @@ int view_rows(JobCtx *e, const StateView &v, const tad_job *job, const JobParams
 // rows.  Reads the view only: the state's CURRENT copies, or a window's view in this context's workspace (wv_key / wv_pts, which nothing
 // below resizes).
 int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem out_memory, tad_result **out, int view_syncs,
-                    const Since *since = nullptr) {
+                    const Since *since = nullptr, uint64_t raw_points = 0) {
   const JobParams jp = job_params(job);
   ViewJob vj;
   int rc;
@@ -157,7 +164,7 @@ int run_view_locked(JobCtx *e, const StateView &v, const tad_job *job, tad_mem o
   const uint64_t rows = (jp.algo == TAD_ALGO_EWMA && jp.all_points && !since) ? v.P : (v.P ? *e->total_host : 0);
   const DevCounters c = *e->ctr_host;
   e->done.store(3);
-  return view_rows(e, v, job, jp, vj, c, rows, out_memory, out, view_syncs);
+  return view_rows(e, v, job, jp, vj, c, rows, out_memory, out, view_syncs, raw_points);
 }
 
 // The view of a window of the state in the context's workspace (kernels: tad_window.hip), after run_view_begin, in two steps:
@@ -233,6 +240,53 @@ int window_gather(JobCtx *e, const tad_state *st, const tad_job *job, uint64_t P
   return TAD_OK;
 }
 
+// tad_run_state_buckets, in window_gather's place: the view of the window's points FOLDED into time buckets, built straight from the
+// state's arrays through window_bounds' wbeg / wlen — no unbucketed copy of the window is written.  The heads per chunk and their scan
+// (bk_key), one more host round trip for the bucket total, the fold into wv_pts, then what a window's view gets: the moments by
+// launch_trim_moments (a key with a point cut or folded away is replayed over its buckets, a key left whole with every point in a bucket
+// of its own keeps the state's) and DBSCAN's history by sorting the buckets' values.  P: the window's points (0: an empty view)
+int window_buckets(JobCtx *e, const tad_state *st, const tad_job *job, int64_t bucket_s, int64_t origin, bool op_max, uint64_t P, StateView *v) {
+  hipStream_t s = e->stream;
+  const uint64_t K = st->K;
+  const StateView whole = series_view(st, st->cur);
+  const WinKeys w = carve_at(e->wv_key.p, win_keys_layout, K);   // (as window_bounds placed it)
+  int rc;
+  *v = StateView{};
+  v->K = K;
+  if (P != 0) {
+    const uint64_t bound = trim_chunks_bound(K, whole.P);
+    BucketKeys b;
+    if ((rc = carve_buf(e, e->bk_key, &b, bucket_keys_layout, K, bound)) != TAD_OK) return rc;
+    if ((rc = ensure(e, e->scan_scratch, scan_scratch_elems(bound > K ? bound : K) * sizeof(unsigned long long))) != TAD_OK) return rc;
+    unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+    const BucketSource src{whole.soff, whole.sval, whole.st, w.wbeg, w.wlen};
+    launch_win_bucket_heads(s, bound, w.coff, K, src, (long long)bucket_s, (long long)origin, b.hcnt);
+    launch_scan(s, b.hcnt, b.hoff, bound, scratch);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipMemcpyAsync(e->tail_host + kTailTotal, b.hoff + bound, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(e, hipStreamSynchronize(s));
+    const uint64_t B = *e->total_host;   // the buckets: at least one per key with a window point, at most P
+    const bool dbscan = job->algo == TAD_ALGO_DBSCAN;
+    const size_t need = carved_bytes(win_pts_layout, B, dbscan) + carved_bytes(bucket_keys_layout, K, bound) + carved_bytes(win_keys_layout, K);
+    if (need > e->ws_limit)   // (the state is only ever read: nothing to undo)
+      return fail(e, TAD_ERR_GRID_TOO_LARGE, "tad_run_state_buckets: the view of %llu buckets needs %llu bytes > workspace limit %llu (state unchanged)",
+                  (unsigned long long)B, (unsigned long long)need, (unsigned long long)e->ws_limit);
+    WinPts bp;
+    if ((rc = carve_buf(e, e->wv_pts, &bp, win_pts_layout, B, dbscan)) != TAD_OK) return rc;
+    launch_win_bucket_fold(s, bound, w.coff, K, src, (long long)bucket_s, (long long)origin, op_max, b.hoff, B, bp.wval, bp.wt);
+    launch_win_bucket_keys(s, K, whole.soff, w.coff, b.hoff, b.boff, b.bcnt, b.becnt);
+    const double alpha = job->ewma_alpha == 0.0 ? 0.5 : job->ewma_alpha;   // (for the view's ewma only, which no detector reads)
+    launch_trim_moments(s, K, b.bcnt, b.becnt, b.boff, bp.wval, alpha, whole.mom, w.wmom);
+    if (dbscan) launch_hist_sort(s, bp.wval, b.boff, K, bp.wh, w.chunks, w.long_count);   // (chunks: read for the last time by the scan to coff)
+    HIP_TRY(e, hipGetLastError());
+    v->P = B;
+    v->soff = b.boff; v->sval = bp.wval; v->st = bp.wt; v->mom = w.wmom;
+    if (dbscan) { v->hoff = b.boff; v->hval = bp.wh; }
+  }
+  e->done.store(1);
+  return TAD_OK;
+}
+
 // What the five calls refuse before they take the state's lock.  Both families check the same things in the same order; the family
 // supplies the algorithm test with its message, the parameter ranges and DBSCAN's history.  who: the call's name in the messages; narrow:
 // where the caller narrows the window instead of start_time / end_time.
@@ -275,6 +329,9 @@ struct Window {
   // key_memory; an entry of TAD_NO_CHANGE also takes the key out of the selection)
   const int64_t *key_since = nullptr;
   int64_t since_t = 0;
+  // tad_run_state_buckets: the judged points folded into time buckets of bucket_s seconds (0: judged as they are, the other calls)
+  int64_t bucket_s = 0, bucket_origin = 0;
+  bool bucket_max = false;
 };
 
 const char *const kNarrowWindow = "the window is from_t / to_t / keep_points";
@@ -318,10 +375,13 @@ int view_call(tad_engine *eng, tad_state *st, const tad_job *job, const char *wh
       HIP_TRY(e, hipMemcpyAsync(since_args.keys.since, w.key_since, (size_t)st->K * 8, hipMemcpyHostToDevice, e->stream));
       since_args.key_since = since_args.keys.since;
     }
+    since_args.bucket_s = (long long)w.bucket_s;
+    since_args.bucket_origin = (long long)w.bucket_origin;
     since = &since_args;
   }
   const long long *d_since = since ? since->key_since : nullptr;
-  if (S == 0 || (!w.key_keep && !d_since && w.from_t == 0 && w.to_t == 0 && w.keep_points == 0))
+  const bool bucketed = w.bucket_s != 0;   // (then neither shortcut below is taken: a whole key is still folded)
+  if (S == 0 || (!bucketed && !w.key_keep && !d_since && w.from_t == 0 && w.to_t == 0 && w.keep_points == 0))
     return run_view_locked(e, whole, job, out_memory, out, 0, since);
   const uint8_t *d_keep = w.key_keep;
   if (w.key_keep && w.key_memory == TAD_MEM_HOST) {   // staged: only window_bounds reads it
@@ -331,6 +391,11 @@ int view_call(tad_engine *eng, tad_state *st, const tad_job *job, const char *wh
   }
   uint64_t P = 0;
   if ((rc = window_bounds(e, st, w.from_t, w.to_t, w.keep_points, d_keep, d_since, &P)) != TAD_OK) return rc;
+  if (bucketed) {
+    StateView v;
+    if ((rc = window_buckets(e, st, job, w.bucket_s, w.bucket_origin, w.bucket_max, P, &v)) != TAD_OK) return rc;
+    return run_view_locked(e, v, job, out_memory, out, P ? 2 : 1, since, P);
+  }
   if (P == S) return run_view_locked(e, whole, job, out_memory, out, 1, since);   // every key is selected and whole: the state's own arrays, no view
   const bool subtract = job->algo == TAD_ALGO_DBSCAN && P != 0 && !win_hist_by_sort(P, S);   // (P: the SELECTED window points)
   StateView v;
@@ -392,6 +457,26 @@ int tad_run_state_since(tad_engine *eng, tad_state *st, const tad_job *job, cons
 
 int tad_drop_state_since(tad_engine *eng, tad_state *st, const tad_job *job, const tad_report_window *w, tad_mem out_memory, tad_result **out) {
   return since_call(eng, st, job, "tad_drop_state_since", Family::Drop, w, out_memory, out);
+}
+
+// the since call with three more fields of the one window: the bucket window's own checks, then the call
+int tad_run_state_buckets(tad_engine *eng, tad_state *st, const tad_job *job, const tad_bucket_window *w, tad_mem out_memory, tad_result **out) {
+  const char *who = "tad_run_state_buckets";
+  const int rc = check_view_job(eng, st, job, out, who, Family::Run, "the window is the bucket window's from_t / to_t / keep_points");
+  if (rc != TAD_OK) return rc;
+  if (!w) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the bucket window must not be NULL", who);
+  if (!bucket_args_ok(w->bucket_s, w->bucket_origin))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bucket_s must be >= 1 and 0 <= bucket_origin < bucket_s (got %lld, %lld)", who, (long long)w->bucket_s,
+                (long long)w->bucket_origin);
+  if (w->bucket_op != TAD_OP_SUM && w->bucket_op != TAD_OP_MAX)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bucket_op must be TAD_OP_SUM or TAD_OP_MAX", who);
+  Window win{w->from_t, w->to_t, w->keep_points, w->key_keep, (w->key_keep || w->key_since) ? w->num_keys : 0, w->key_memory};
+  win.key_since = w->key_since;
+  win.since_t = w->since_t;
+  win.bucket_s = w->bucket_s;
+  win.bucket_origin = w->bucket_origin;
+  win.bucket_max = w->bucket_op == TAD_OP_MAX;
+  return view_call(eng, st, job, who, win, out_memory, out);
 }
 
 }  // extern "C"

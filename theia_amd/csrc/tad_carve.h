@@ -242,6 +242,24 @@ inline SincePts since_pts_layout(Carve &c, uint64_t P) {
   return p;
 }
 
+// ---- tad_run_state_buckets (bk_key; the bucketed values, times and sorted values are a WinPts over the buckets in wv_pts) ----
+// (this layout's stand-alone check lives in tests/test_state_buckets_abi.py)
+struct BucketKeys {   // per key: buckets | points folded away or cut | bucket offsets; per chunk of k_win_bucket_fold: heads | their scan (chunks + 1)
+  uint32_t *bcnt, *becnt;
+  unsigned long long *boff;
+  uint32_t *hcnt;
+  unsigned long long *hoff;
+};
+inline BucketKeys bucket_keys_layout(Carve &c, uint64_t K, uint64_t chunks) {
+  BucketKeys b;
+  b.bcnt = take_counts(c, K);
+  b.becnt = take_counts(c, K);
+  b.boff = take_offsets(c, K);
+  b.hcnt = take_counts(c, chunks);
+  b.hoff = take_offsets(c, chunks);
+  return b;
+}
+
 // ---- tad_state_merge (mg_pts, mg_keys) ----
 struct MergeCounters {   // one 64-byte block on the device, zeroed per attempt
   unsigned long long too_old, appended, inserted, combined, keys_touched, keys_replayed, keys_emptied, pad[1];   // keys_emptied: tad_state_replace only

@@ -447,8 +447,9 @@ void launch_win_bounds(hipStream_t s, uint64_t K, const unsigned long long *soff
 // sk.first[k] = the first index of key k's segment [soff[k], soff[k + 1]) with a time >= since_t (0: no such bound) and >= key_since[k]
 // (NULL: no such bound; kNoChange: the suffix is empty), sk.cnt[k] = the points from there on, sk.chunks[k] = ceil(cnt / kHistChunk);
 // lengths == false: first alone is written; n_keys != NULL: += the keys with a point in the view
+// bucket_s != 0 (tad_run_state_buckets: the view's times are bucket starts): the threshold is floored to its bucket's start first; 0 is inert
 void launch_win_since(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, const long long *key_since, long long since_t,
-                      const SinceKeys &sk, bool lengths, unsigned long long *n_keys);
+                      const SinceKeys &sk, bool lengths, unsigned long long *n_keys, long long bucket_s = 0, long long bucket_origin = 0);
 // key, time and value of every reported point packed at sk.poff (the scan of sk.cnt; sk.coff: the scan of sk.chunks); points = poff[K]
 void launch_win_suffix(hipStream_t s, uint64_t K, uint64_t points, const unsigned long long *soff, const unsigned long long *sval, const long long *st,
                        const SinceKeys &sk, const SincePts &sp);
@@ -457,6 +458,23 @@ void launch_win_suffix(hipStream_t s, uint64_t K, uint64_t points, const unsigne
 void launch_win_gather(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const unsigned long long *soff,
                        const unsigned long long *sval, const long long *st, const uint32_t *wbeg, const unsigned long long *woff,
                        unsigned long long *wval, long long *wt, const unsigned long long *eoff, unsigned long long *ev);
+// ---- tad_run_state_buckets (tad_window.hip): every key's range [beg[k], beg[k] + len[k]) of its segment folded into time buckets ----
+// what is bucketed: CSR offsets, values and times, and per key the range of its segment (launch_win_bounds' wbeg / wlen)
+struct BucketSource {
+  const unsigned long long *soff, *sval;
+  const long long *st;
+  const uint32_t *beg, *len;
+};
+// hcnt[w] = the heads (first points of a bucket) of chunk w, for every w < chunks_bound (0 past the last chunk); coff: the scan of
+// launch_win_bounds' chunks; chunks_bound: trim_chunks_bound(K, the source's points).  The scan of hcnt is hoff
+void launch_win_bucket_heads(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const BucketSource &src, long long bucket_s,
+                             long long bucket_origin, uint32_t *hcnt);
+// bval[c] / bt[c] = the fold (wrapping sum, or unsigned maximum with op_max) and the start of bucket c, c < buckets = hoff[chunks_bound]
+void launch_win_bucket_fold(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const BucketSource &src, long long bucket_s,
+                            long long bucket_origin, bool op_max, const unsigned long long *hoff, uint64_t buckets, unsigned long long *bval, long long *bt);
+// boff[k] (K + 1) = the first bucket of key k, bcnt[k] = its buckets, becnt[k] = the points of its segment that are not a bucket of their own
+void launch_win_bucket_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *coff, const unsigned long long *hoff,
+                            unsigned long long *boff, uint32_t *bcnt, uint32_t *becnt);
 // DBSCAN's window history: true = sort the window's values per key, false = sort the excluded values and subtract them from the state's
 // history.  A pure function of the two totals: 2 * window_points <= state_points
 bool win_hist_by_sort(uint64_t window_points, uint64_t state_points);

@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "tad_internal.h"
+#include "tad_bucket.h"
 
 namespace tad {
 
@@ -374,8 +375,9 @@ __global__ __launch_bounds__(kWBlock) void k_win_gather(const unsigned long long
 //                 of "new points" the stream detectors judge against the whole view (hist_verdicts, stream_arima_batch, state_drop_batch).
 // EWMA walks the series anyway: the three kernels above take first[k] and count or emit a point only at an index >= first[k].
 __global__ __launch_bounds__(kWBlock) void k_win_since(uint64_t K, const unsigned long long *__restrict__ soff, const long long *__restrict__ st,
-                                                      const long long *__restrict__ key_since, long long since_t, uint32_t *__restrict__ first,
-                                                      uint32_t *__restrict__ cnt, uint32_t *__restrict__ chunks, unsigned long long *__restrict__ n_keys) {
+                                                      const long long *__restrict__ key_since, long long since_t, long long bucket_s,
+                                                      long long bucket_origin, uint32_t *__restrict__ first, uint32_t *__restrict__ cnt,
+                                                      uint32_t *__restrict__ chunks, unsigned long long *__restrict__ n_keys) {
   const uint64_t k = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
   unsigned long long len = 0;
   if (k < K) {
@@ -388,6 +390,8 @@ __global__ __launch_bounds__(kWBlock) void k_win_since(uint64_t K, const unsigne
       if (ks == kNoChange) selected = false;
       else if (!bounded || ks > thr) { thr = ks; bounded = true; }
     }
+    // tad_run_state_buckets (the view's times are bucket starts): the bucket that holds the threshold is reported whole
+    if (bucket_s != 0 && bounded) thr = bucket_start(thr, bucket_s, bucket_origin);
     const unsigned long long f = !selected ? len : (bounded ? win_lower_t(st, o0, o0 + len, thr) - o0 : 0ull);
     first[k] = (uint32_t)f;
     if (cnt != nullptr) {   // (NULL: the caller wants first[k] alone — EWMA's anomalous rows, counted by the walk)
@@ -419,6 +423,142 @@ __global__ __launch_bounds__(kWBlock) void k_win_suffix(const unsigned long long
     nt[d0 + u] = st[src + u];
     nv[d0 + u] = sval[src + u];
   }
+}
+
+// ---- tad_run_state_buckets: the window's points folded into time buckets, straight from the state's arrays (include/tad.h) ----
+// Times ascend per key, so a bucket — the points of one key with the same bucket_start (tad_bucket.h) — is a contiguous RUN of the key's
+// window range [beg, beg + len) of its segment: a segmented fold and a compaction, no sort, no hash, no K x T grid.  A HEAD is a point
+// whose bucket differs from its predecessor's in the key; the key's first window point always is one.  The chunks are k_win_gather's
+// (coff from k_win_bounds: kHistChunk consecutive points of one key's segment per wavefront, lanes on consecutive points), ordered by key
+// and then position, so the scan of the chunks' head counts is every chunk's first destination cell, and the cell before it is the one
+// of the run open at the chunk's first point.
+//   k_win_bucket_heads  per chunk: the heads inside the key's window range (ballot + popcount per 64-point slice);
+//   k_win_bucket_fold   the same chunks, per slice: bucket start, head flag (lane 0 against the element before the slice), rank by ballot
+//                       and popcount, a segmented inclusive scan of the values across the wavefront (six shuffle steps, unsigned 64-bit,
+//                       wrapping add or unsigned maximum), the run left open at lane 63 carried in registers into the next slice.  A run
+//                       whose head and end both lie in the chunk takes ONE plain store; a partial of a run that crosses a chunk edge (it
+//                       may span several chunks) is one 64-bit atomicAdd / atomicMax onto its cell, zeroed beforehand — an integer
+//                       operation, so the result does not depend on the order.  The head's owner writes the bucket start.  No LDS, no
+//                       scratch, no floating point;
+//   k_win_bucket_keys   one lane per key: the view's offsets boff[k] = the destination of the key's first chunk, the buckets per key and
+//                       the points folded away or cut (what launch_trim_moments takes as rcnt / ecnt).
+// The source is described by offsets and ranges and the destination by plain arrays (BucketSource), so a later in-place roll-up of a
+// state's old points can call the same launchers.  No kernel here reads a series slot outside the key's range or writes a cell >= buckets.
+__device__ __forceinline__ bool bucket_head(const long long *__restrict__ st_key, unsigned long long u, bool valid, unsigned long long beg, unsigned lane,
+                                            long long bucket_s, long long origin, long long *start) {
+  const long long s = valid ? bucket_start(st_key[u], bucket_s, origin) : 0ll;
+  long long prev = __shfl_up(s, 1);
+  if (lane == 0 && valid && u > beg) prev = bucket_start(st_key[u - 1], bucket_s, origin);   // the element before the slice
+  *start = s;
+  return valid && (u == beg || s != prev);
+}
+
+// the part [c0, c1) of chunk w's points that lies inside its key's range; false: none
+__device__ __forceinline__ bool bucket_chunk(const unsigned long long *__restrict__ coff, uint64_t K, const BucketSource &src, unsigned long long w, uint64_t *key,
+                                             unsigned long long *o0, unsigned long long *beg, unsigned long long *end, unsigned long long *c0,
+                                             unsigned long long *c1) {
+  const uint64_t k = chunk_key_min1(coff, K, w);
+  const unsigned long long len = src.soff[k + 1] - src.soff[k];
+  const unsigned long long b = src.beg[k], be = b + src.len[k];
+  unsigned long long a0 = (w - coff[k]) * kHistChunk, a1 = a0 + kHistChunk;
+  if (a1 > len) a1 = len;
+  if (a0 < b) a0 = b;
+  if (a1 > be) a1 = be;
+  *key = k; *o0 = src.soff[k]; *beg = b; *end = be; *c0 = a0; *c1 = a1;
+  return a0 < a1;
+}
+
+__global__ __launch_bounds__(kWBlock) void k_win_bucket_heads(const unsigned long long *__restrict__ coff, uint64_t K, uint64_t chunks_bound, BucketSource src,
+                                                             long long bucket_s, long long origin, uint32_t *__restrict__ hcnt) {
+  const unsigned long long w = ((uint64_t)blockIdx.x * kWBlock + threadIdx.x) >> 6;
+  if (w >= chunks_bound) return;
+  const unsigned lane = threadIdx.x & 63u;
+  uint32_t heads = 0;
+  if (w < coff[K]) {   // (wavefront-uniform; the entries past the last chunk are scanned too and must be 0)
+    uint64_t k;
+    unsigned long long o0, beg, end, c0, c1;
+    if (bucket_chunk(coff, K, src, w, &k, &o0, &beg, &end, &c0, &c1)) {
+      for (unsigned long long u0 = c0; u0 < c1; u0 += 64) {
+        const unsigned long long u = u0 + lane;
+        long long start;
+        const bool head = bucket_head(src.st + o0, u, u < c1, beg, lane, bucket_s, origin, &start);
+        heads += (uint32_t)__popcll(__ballot(head));
+      }
+    }
+  }
+  if (lane == 0) hcnt[w] = heads;
+}
+
+template <bool MAX> __device__ __forceinline__ unsigned long long bucket_op(unsigned long long a, unsigned long long b) {
+  return MAX ? (a > b ? a : b) : a + b;
+}
+
+template <bool MAX>
+__global__ __launch_bounds__(kWBlock) void k_win_bucket_fold(const unsigned long long *__restrict__ coff, uint64_t K, BucketSource src, long long bucket_s,
+                                                            long long origin, const unsigned long long *__restrict__ hoff, uint64_t buckets,
+                                                            unsigned long long *__restrict__ bval, long long *__restrict__ bt) {
+  const unsigned long long w = ((uint64_t)blockIdx.x * kWBlock + threadIdx.x) >> 6;
+  if (w >= coff[K]) return;
+  const unsigned lane = threadIdx.x & 63u;
+  uint64_t k;
+  unsigned long long o0, beg, end, c0, c1;
+  if (!bucket_chunk(coff, K, src, w, &k, &o0, &beg, &end, &c0, &c1)) return;
+  // the chunk's first head goes to cell hoff[w]; the run open at its first point (head in an earlier chunk of the key) is the cell before
+  unsigned long long cell_next = hoff[w];
+  // the run open at a slice's first point: what this chunk has folded of it so far, and whether its head lies in this chunk
+  unsigned long long carry = 0;
+  bool carry_head = false;
+  for (unsigned long long u0 = c0; u0 < c1; u0 += 64) {   // (wavefront-uniform)
+    const unsigned long long u = u0 + lane;
+    const bool valid = u < c1;
+    long long start;
+    const bool head = bucket_head(src.st + o0, u, valid, beg, lane, bucket_s, origin, &start);
+    unsigned long long x = valid ? src.sval[o0 + u] : 0ull;
+    const unsigned long long hm = __ballot(head);
+    // the run carried out of the previous slice ended at its lane 63: this slice opens with a head
+    if (lane == 0 && head && u0 != c0 && cell_next - 1 < buckets) {
+      if (carry_head) bval[cell_next - 1] = carry;
+      else if (MAX) atomicMax(bval + cell_next - 1, carry);
+      else atomicAdd(bval + cell_next - 1, carry);
+    }
+    // segmented inclusive scan: after it x folds the lane's run from its head (or from lane 0) up to the lane
+    bool seen = head;
+#pragma unroll
+    for (unsigned d = 1; d < 64; d <<= 1) {
+      const unsigned long long xo = __shfl_up(x, d);
+      const int so = __shfl_up((int)seen, d);
+      if (lane >= d && !seen) { x = bucket_op<MAX>(xo, x); seen = so != 0; }
+    }
+    const unsigned r = (unsigned)__popcll(hm & (~0ull >> (63u - lane)));   // heads at or before this lane
+    if (r == 0) x = bucket_op<MAX>(carry, x);
+    const bool head_here = r != 0 || carry_head;      // the run's head lies in this chunk
+    const unsigned long long cell = cell_next + r - 1;
+    const bool next_valid = u + 1 < c1;
+    const bool next_head = lane < 63u && ((hm >> (lane + 1u)) & 1ull) != 0;
+    if (head && cell < buckets) bt[cell] = start;
+    if (valid && (next_head || !next_valid) && cell < buckets) {   // the run ends here: at a head, at the range's end, or at the chunk's edge
+      if (head_here && (next_head || c1 == end)) bval[cell] = x;   // whole inside the chunk: nobody else writes the cell
+      else if (MAX) atomicMax(bval + cell, x);
+      else atomicAdd(bval + cell, x);
+    }
+    // (lane 63 with a valid successor: the run is still open — carried; whether it ends there the next slice's lane 0 finds out)
+    carry = __shfl(x, 63);
+    carry_head = __shfl((int)head_here, 63) != 0;
+    cell_next += (unsigned long long)__popcll(hm);
+  }
+}
+
+__global__ __launch_bounds__(kWBlock) void k_win_bucket_keys(uint64_t K, const unsigned long long *__restrict__ soff, const unsigned long long *__restrict__ coff,
+                                                            const unsigned long long *__restrict__ hoff, unsigned long long *__restrict__ boff,
+                                                            uint32_t *__restrict__ bcnt, uint32_t *__restrict__ becnt) {
+  const uint64_t k = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
+  if (k > K) return;
+  const unsigned long long b0 = hoff[coff[k]];
+  boff[k] = b0;
+  if (k == K) return;
+  const unsigned long long nb = hoff[coff[k + 1]] - b0;
+  bcnt[k] = (uint32_t)nb;
+  becnt[k] = (uint32_t)(soff[k + 1] - soff[k] - nb);
 }
 
 // ---- launchers ----
@@ -502,10 +642,31 @@ void launch_win_bounds(hipStream_t s, uint64_t K, const unsigned long long *soff
 }
 
 void launch_win_since(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, const long long *key_since, long long since_t,
-                      const SinceKeys &sk, bool lengths, unsigned long long *n_keys) {
+                      const SinceKeys &sk, bool lengths, unsigned long long *n_keys, long long bucket_s, long long bucket_origin) {
   if (K == 0) return;
-  hipLaunchKernelGGL(k_win_since, dim3(win_blocks(K)), dim3(kWBlock), 0, s, K, soff, st, key_since, since_t, sk.first, lengths ? sk.cnt : nullptr,
-                     lengths ? sk.chunks : nullptr, n_keys);
+  hipLaunchKernelGGL(k_win_since, dim3(win_blocks(K)), dim3(kWBlock), 0, s, K, soff, st, key_since, since_t, bucket_s, bucket_origin, sk.first,
+                     lengths ? sk.cnt : nullptr, lengths ? sk.chunks : nullptr, n_keys);
+}
+
+void launch_win_bucket_heads(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const BucketSource &src, long long bucket_s,
+                             long long bucket_origin, uint32_t *hcnt) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_win_bucket_heads, dim3(win_blocks(chunks_bound * 64)), dim3(kWBlock), 0, s, coff, K, chunks_bound, src, bucket_s, bucket_origin, hcnt);
+}
+
+void launch_win_bucket_fold(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const BucketSource &src, long long bucket_s,
+                            long long bucket_origin, bool op_max, const unsigned long long *hoff, uint64_t buckets, unsigned long long *bval, long long *bt) {
+  if (K == 0 || buckets == 0) return;
+  hipMemsetAsync(bval, 0, (size_t)buckets * 8, s);   // 0 is the identity of both operations: a chunk-edge partial is an atomic onto its cell
+  const dim3 grid(win_blocks(chunks_bound * 64)), block(kWBlock);
+  if (op_max) hipLaunchKernelGGL(k_win_bucket_fold<true>, grid, block, 0, s, coff, K, src, bucket_s, bucket_origin, hoff, buckets, bval, bt);
+  else hipLaunchKernelGGL(k_win_bucket_fold<false>, grid, block, 0, s, coff, K, src, bucket_s, bucket_origin, hoff, buckets, bval, bt);
+}
+
+void launch_win_bucket_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *coff, const unsigned long long *hoff,
+                            unsigned long long *boff, uint32_t *bcnt, uint32_t *becnt) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_win_bucket_keys, dim3(win_blocks(K + 1)), dim3(kWBlock), 0, s, K, soff, coff, hoff, boff, bcnt, becnt);
 }
 
 uint64_t win_suffix_chunks_bound(uint64_t K, uint64_t points) { return K + points / kHistChunk + 1; }

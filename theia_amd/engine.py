@@ -1520,6 +1520,26 @@ class TadEngine:
         del alive
         return res
 
+    # ---- a state judged in time buckets (tad_run_state_buckets) ----
+    def run_state_buckets(self, state, bucket_s, origin=0, op="sum", from_t=0, to_t=0, keep_points=0, key_keep=None, key_since=None, since_t=0,
+                          algo="EWMA", alpha=0.0, eps=0.0, min_samples=0, maxiter=0, emit_all=False, out="host", job_id=""):
+        """run_state_since over the window's points folded into time buckets, read-only (tad_run_state_buckets): exactly the rows run()
+        returns with value_op=op ("sum" or "max") for the window's rows — from_t / to_t / keep_points and key_keep act on the raw points,
+        first — with flow_end_s replaced by origin + bucket_s * floor((flow_end_s - origin) / bucket_s); the bucket's start stands in
+        flow_end_s.  key_since / since_t: a bucket is reported iff it starts at or after the start of the threshold's bucket, so the
+        bucket holding the first changed second is reported whole.  bucket_s=1 is run_state_keys."""
+        job = self._detector_job(algo, alpha, eps, min_samples, maxiter, emit_all=emit_all, job_id=job_id)
+        self._need("STATE_BUCKETS", "tad_run_state_buckets")
+        if op not in ("sum", "max"):
+            raise TadError(capi.TAD_ERR_INVALID_ARGUMENT, "op must be sum or max")
+        rw, alive = self._report_window(state, since_t, key_since, key_keep, from_t, to_t, keep_points)
+        w = capi.BucketWindow(bucket_s=int(bucket_s), bucket_origin=int(origin), bucket_op=capi.TAD_OP[op])
+        for name, _ in capi.ReportWindow._fields_:
+            setattr(w, name, getattr(rw, name))
+        res = self._state_rows("tad_run_state_buckets", state, job, out, C.byref(w))
+        del alive
+        return res
+
     # ---- the drop job's flow-row query (tad_drop_select) ----
     def drop_select(self, ingress_action, egress_action, flow_start_s, src_ip, src_pod_ns, src_pod_name, dst_ip, dst_pod_ns, dst_pod_name,
                     flow_end_s=None, src_pod_null=-1, dst_pod_null=-1, start_time=0, end_time=0, keep=None, out="device"):

@@ -234,7 +234,8 @@ class StreamingAnomalyDetection:
             return self._engine.replace_stream_changes(self._state, none, np.zeros(0, dtype=np.int64), none, changes, **kw)
         return self._engine.replace_stream(self._state, none, np.zeros(0, dtype=np.int64), none, **kw)
 
-    def feed_alerts(self, flows, algo_type, tad_id, replace=None, pod_label="", pod_name="", pod_namespace="", external_ip="", svc_port_name=""):
+    def feed_alerts(self, flows, algo_type, tad_id, replace=None, pod_label="", pod_name="", pod_namespace="", external_ip="", svc_port_name="",
+                    bucket_s=0, bucket_op="sum"):
         """feed, and what it made anomalous -> (the feed's statistics with the change report's counters, list of result rows).  The
         feed runs with a change report on the device (TadEngine.merge_stream_changes / replace_stream_changes): per key, the smallest
         flowEndSeconds at which the key's series changed.  Then TadEngine.run_state_since judges the keys that changed AND pass the
@@ -244,9 +245,13 @@ class StreamingAnomalyDetection:
 
         What is not reported: a changed key's points BEFORE its first changed time.  A late point moves the whole key's stddev (and
         DBSCAN's neighbourhoods, ARIMA's lambda), so their verdicts may have changed as well; that is the stream's rule — each point
-        once, when it arrives or changes — and `job` gives the whole answer."""
+        once, when it arrives or changes — and `job` gives the whole answer.
+
+        bucket_s > 0: the changed keys are judged per bucket as `job(bucket_s=...)` judges them (TadEngine.run_state_buckets), and
+        every changed key's buckets are reported from the one that holds its first changed second on, whole."""
         if algo_type not in _ad.VALID_ALGOS:
             raise ValueError("Algorithm should be in {}".format(" or ".join(_ad.VALID_ALGOS)))
+        bucket_s = self._bucket_args(bucket_s, bucket_op)
         filters = (pod_label or "", pod_name or "", pod_namespace or "", external_ip or "", svc_port_name or "")
         self._terms(*filters)      # (a filter this instance does not serve is refused before the feed changes anything)
         stats = self._feed(flows, replace, "device")
@@ -257,7 +262,11 @@ class StreamingAnomalyDetection:
             if stats["keys_changed"] == 0:
                 return stats, []
             keep, _ = self._dict.select(self._terms(*filters), out="device")      # (the masks: over the vocabularies as the feed left them)
-            res = self._engine.run_state_since(self._state, key_since=since, key_keep=keep, algo=algo_type, job_id=str(tad_id or ""))
+            if bucket_s:
+                res = self._engine.run_state_buckets(self._state, bucket_s, 0, bucket_op, key_keep=keep, key_since=since, algo=algo_type,
+                                                     job_id=str(tad_id or ""))
+            else:
+                res = self._engine.run_state_since(self._state, key_since=since, key_keep=keep, algo=algo_type, job_id=str(tad_id or ""))
         finally:
             since.free()
         if res.n_rows == 0:
@@ -267,10 +276,12 @@ class StreamingAnomalyDetection:
         prep = _ad.PreparedColumns(self.mode, None, None, None, None, None, table, 0, 0)
         return stats, _ad.result_rows(prep, res, algo_type, self.agg_flow, tad_id)
 
-    def poll_alerts(self, client, now, lag_s, algo_type, tad_id, **filters):
+    def poll_alerts(self, client, now, lag_s, algo_type, tad_id, bucket_s=0, bucket_op="sum", **filters):
         """One turn of `poll` that also returns what the turn made anomalous -> (statistics, rows) as feed_alerts: the lagged range is
-        re-read and REPLACES those seconds, so a turn made twice (a timeout, a restart) returns no rows the second time."""
-        return self._poll(client, now, lag_s, lambda flows, replace: self.feed_alerts(flows, algo_type, tad_id, replace=replace, **filters))
+        re-read and REPLACES those seconds, so a turn made twice (a timeout, a restart) returns no rows the second time.  bucket_s /
+        bucket_op: feed_alerts'."""
+        return self._poll(client, now, lag_s, lambda flows, replace: self.feed_alerts(flows, algo_type, tad_id, replace=replace, bucket_s=bucket_s,
+                                                                                      bucket_op=bucket_op, **filters))
 
     def poll(self, client, now, lag_s):
         """One turn of the poll loop against the flow table: read the instance's rows with watermark - lag_s <= flowEndSeconds < now
@@ -328,12 +339,32 @@ class StreamingAnomalyDetection:
             terms.append(self._equal(0, pod_namespace))
         return terms
 
-    def job(self, algo_type, tad_id, end_time="", pod_label="", pod_name="", pod_namespace="", external_ip="", svc_port_name=""):
+    @staticmethod
+    def _bucket_args(bucket_s, bucket_op):
+        bucket_s = int(bucket_s)
+        if bucket_s < 0:
+            raise ValueError("bucket_s must not be negative")
+        if bucket_s and bucket_op not in ("sum", "max"):
+            raise ValueError("bucket_op should be 'sum' or 'max'")
+        return bucket_s
+
+    def job(self, algo_type, tad_id, end_time="", pod_label="", pod_name="", pod_namespace="", external_ip="", svc_port_name="", bucket_s=0,
+            bucket_op="sum", complete_before=None):
         """One job over everything fed so far -> (stats dict, list of result rows): what anomaly_detection(algo_type, all rows fed, "",
         end_time, tad_id, ns_ignore_list, agg_flow, the same filters) returns, the sentinel row included.  end_time bounds
-        flowEndSeconds in svc and external mode; the pod query has no time filter."""
+        flowEndSeconds in svc and external mode; the pod query has no time filter.
+
+        bucket_s > 0: the job judges throughput per bucket of bucket_s seconds, not per second (TadEngine.run_state_buckets, on the
+        device): the rows are those of anomaly_detection over everything fed with flowEndSeconds floored to a multiple of bucket_s,
+        the points of a bucket folded by bucket_op ("sum", what the aggregated flow types do, or "max"); a row's flowEndSeconds is its
+        bucket's start.  end_time, if given, must then be a multiple of bucket_s (a bucket cut by it would hold a part of its rows).
+        complete_before=now: judge only the buckets that lie wholly before `now` — the window ends at the start of now's bucket, so
+        the half-filled newest bucket is not judged as a drop.  bucket_s=0 is the job as it always was."""
         if algo_type not in _ad.VALID_ALGOS:
             raise ValueError("Algorithm should be in {}".format(" or ".join(_ad.VALID_ALGOS)))
+        bucket_s = self._bucket_args(bucket_s, bucket_op)
+        if complete_before is not None and not bucket_s:
+            raise ValueError("complete_before needs bucket_s")
         self._usable()
         terms = self._terms(pod_label or "", pod_name or "", pod_namespace or "", external_ip or "", svc_port_name or "")
         decoder = _KeyDecoder(self._dict, self._vocab)      # the key table: decoded on demand, for the keys with result rows
@@ -343,7 +374,17 @@ class StreamingAnomalyDetection:
             return {}, [_ad._sentinel_row(algo_type, self.agg_flow, tad_id)]
         keep, _ = self._dict.select(terms, out="device")
         to_t = _ad._epoch(end_time) if self.agg_flow != "pod" else 0
-        res = self._engine.run_state_keys(self._state, keep, to_t=to_t, algo=algo_type, job_id=str(tad_id or ""))
+        if not bucket_s:
+            res = self._engine.run_state_keys(self._state, keep, to_t=to_t, algo=algo_type, job_id=str(tad_id or ""))
+            return res.stats, _ad.result_rows(prep, res, algo_type, self.agg_flow, tad_id)
+        if to_t % bucket_s:
+            raise ValueError("end_time must be a multiple of bucket_s (%d)" % bucket_s)
+        if complete_before is not None:
+            edge = (int(complete_before) // bucket_s) * bucket_s
+            to_t = min(to_t, edge) if to_t else edge
+            if to_t == 0:      # (0 means "no bound" to the engine; nothing fed lies before the epoch's first bucket)
+                return {}, [_ad._sentinel_row(algo_type, self.agg_flow, tad_id)]
+        res = self._engine.run_state_buckets(self._state, bucket_s, 0, bucket_op, to_t=to_t, key_keep=keep, algo=algo_type, job_id=str(tad_id or ""))
         return res.stats, _ad.result_rows(prep, res, algo_type, self.agg_flow, tad_id)
 
     def snapshot(self):

@@ -2224,6 +2224,57 @@ func (s *State) RunBuckets(job Job, w BucketWindow) ([]Row, error) {
 	return s.resultRows(res), nil
 }
 
+var stateRollupOnce sync.Once
+var stateRollupOK bool
+
+// hasStateRollup: the library knows tad_state_rollup (tad_features); an older one would not export it.
+func hasStateRollup() bool {
+	stateRollupOnce.Do(func() { stateRollupOK = C.tad_features()&C.TAD_FEATURE_STATE_ROLLUP != 0 })
+	return stateRollupOK
+}
+
+var errNoStateRollup = errors.New("tadengine: libtad_mi355x.so has no state roll-up (TAD_FEATURE_STATE_ROLLUP)")
+
+// RollupStats is what one Rollup call folded (tad_rollup_stats).
+type RollupStats struct {
+	PointsBefore uint64  // series points of the state before and
+	PointsAfter  uint64  // after the call
+	PointsRolled uint64  // raw points that lay below the bound
+	Buckets      uint64  // points the state holds below the bound afterwards
+	KeysChanged  uint64  // keys that lost at least one point
+	BeforeT      int64   // the bound that was applied: Before floored to a bucket start
+	MsTotal      float64 // HIP events
+	JobContext   int32
+}
+
+// Rollup folds every key's points older than before into time buckets, in place (tad_state_rollup): before is floored to a bucket start
+// b; below b the points of one key and bucket become one point at the bucket's start (op: OpSum, wrapping, or OpMax), at or after b
+// nothing changes.  The state becomes that of a fresh state streamed the folded points with EWMA parameter alpha (0 -> 0.5); a key whose
+// newest point lay below b gets that point's bucket start as its last time.  Idempotent; RunBuckets at a multiple of bucketS with a
+// congruent origin and the same op returns what it returned before the roll-up.  Needs a state made by NewStateWithTimes.
+func (s *State) Rollup(before, bucketS, origin int64, op ValueOp, alpha float64) (RollupStats, error) {
+	if !hasStateRollup() {
+		return RollupStats{}, errNoStateRollup
+	}
+	if !s.series || !s.times {
+		return RollupStats{}, IllegalArgument{"tadengine: Rollup needs a state made by NewStateWithTimes"}
+	}
+	if bucketS < 1 || origin < 0 || origin >= bucketS {
+		return RollupStats{}, IllegalArgument{"tadengine: bucketS must be >= 1 and 0 <= origin < bucketS"}
+	}
+	var ru C.tad_rollup_stats
+	if rc := C.tad_state_rollup(s.e.h, s.h, C.int64_t(before), C.int64_t(bucketS), C.int64_t(origin), C.tad_value_op(op), C.double(alpha), &ru); rc != C.TAD_OK {
+		msg := C.GoString(C.tad_last_error(s.e.h))
+		if rc == C.TAD_ERR_INVALID_ARGUMENT {
+			return RollupStats{}, IllegalArgument{msg}
+		}
+		return RollupStats{}, fmt.Errorf("tad_state_rollup: %s (code %d)", msg, int(rc))
+	}
+	return RollupStats{PointsBefore: uint64(ru.points_before), PointsAfter: uint64(ru.points_after), PointsRolled: uint64(ru.points_rolled),
+		Buckets: uint64(ru.buckets), KeysChanged: uint64(ru.keys_changed), BeforeT: int64(ru.before_t), MsTotal: float64(ru.ms_total),
+		JobContext: int32(ru.job_context)}, nil
+}
+
 var stringDictOnce sync.Once
 var stringDictOK bool
 

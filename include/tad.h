@@ -805,6 +805,69 @@ typedef struct {
 } tad_bucket_window;
 int tad_run_state_buckets(tad_engine *e, tad_state *s, const tad_job *job, const tad_bucket_window *w, tad_mem out_memory, tad_result **out);
 
+/* ---- a state's old points folded into time buckets, in place (TAD_FEATURE_STATE_ROLLUP; check tad_features() before calling this) ----
+ * A state keeps one point per key and second, and tad_state_trim can only delete old points.  tad_state_rollup coarsens them instead:
+ * "seven days of context, the newest day at full resolution" costs a day of seconds plus six days of minutes, not a week of seconds.
+ * The transformation.  Let W be the table of points the state holds (tad_run_state's W) and
+ *     b = bucket_origin + bucket_s * floor((before_t - bucket_origin) / bucket_s)
+ * the bound FLOORED to a bucket start (FLOOR division, csrc/tad_bucket.h), so that no bucket straddles it; b is reported in
+ * stats->before_t.  Let Wr be W with flow_end_s replaced by its bucket's start (tad_run_state_buckets' formula) for every point with
+ * flow_end_s < b; the points at or after b are untouched, those in [b, before_t) too.
+ * Contract.  After a successful call the state — n, avg, m2, ewma, last_t, series, times, and the history if it has one — is bit for
+ * bit what a fresh state of the same flags and num_keys holds after ONE tad_run_stream EWMA batch over Wr with value_op = bucket_op and
+ * ewma_alpha (0 -> 0.5): tad_state_trim's shape of contract.  In detail:
+ *   - series and times: Stage 0 of Wr per key — the points of one key and bucket fold into one point at the bucket's start, sums wrapping
+ *     mod 2^64, maxima unsigned; times still ascend strictly (bucket starts below b are distinct and below b);
+ *   - the history, if any: every key's new values sorted;
+ *   - a key that lost no point keeps n, avg, m2 and ewma as they are — also when the times of its old points moved to their bucket
+ *     starts — so, as for a trim, the contract holds for it when its batches used the same ewma_alpha; a key that lost a point is
+ *     replayed from the zero state over its new series with the very step of the stream batches;
+ *   - last_t becomes the key's newest time AFTERWARDS.  Unlike a trim this can change it: a key whose newest point lies below b gets
+ *     that point's bucket start.
+ * Consequences:
+ *   - idempotent: the same call twice leaves the same bits;
+ *   - composable: with bucket_s dividing bucket_s' and bucket_origin' congruent to bucket_origin mod bucket_s, a roll-up at bucket_s
+ *     followed by one at bucket_s' over the same bound b — both calls floor to it, so b is a bucket start of the coarser call — equals
+ *     the one at bucket_s' alone (sum and max buckets compose);
+ *   - tiers commute: "older than 7 d at 3600 s" and "older than 1 d at 60 s" may run in either order;
+ *   - tad_run_state_buckets at a multiple of bucket_s with a congruent origin and the same op returns, on the rolled state, the rows it
+ *     returns on the raw state, bit for bit — over the whole state and over any window whose from_t / to_t are bucket starts of that
+ *     call.  keep_points counts POINTS, which the roll-up made fewer: a window with keep_points differs;
+ *   - a stream batch after the roll-up is accepted iff it is newer than the NEW last_t: a point inside a key's last, rolled bucket is
+ *     taken (it sits beside the bucket's point), one at the bucket's start is late;
+ *   - late rows merged (tad_state_merge) into the rolled region sit beside the bucket's point and are still right at bucket
+ *     resolution; a later roll-up folds them;
+ *   - a ranged tad_state_replace whose from_t lies inside the rolled region and is not a bucket start erases the seconds from from_t
+ *     on but not the bucket's point before it, which already holds their old values: it double-counts.  This is the caller's duty
+ *     (the Python layer refuses it).
+ * Arguments and refusals (TAD_ERR_INVALID_ARGUMENT with a message, state unchanged): a NULL engine or state; a state without
+ * TAD_STATE_SERIES | TAD_STATE_TIMES; stale times; bucket_s < 1 or bucket_origin outside [0, bucket_s); a bucket_op other than
+ * TAD_OP_SUM / TAD_OP_MAX; ewma_alpha outside [0, 1]; |before_t| >= 2^62.  An empty state, or a state with no point below b, is
+ * TAD_OK with the state untouched (points_rolled == 0).
+ * Atomic like a trim: only the candidate copies (moments, offsets, arenas) and job-context workspace are written, and the candidates
+ * become current together; any failure — the workspace limit (TAD_ERR_GRID_TOO_LARGE), an allocation, a HIP error — leaves moments,
+ * history, series and times bit for bit as they were; the limit and the allocations are checked before any candidate is written.  The
+ * arenas shrink by tad_state_trim's rule (below a quarter of its capacity an arena is allocated anew at twice its length), so
+ * tad_state_bytes falls.
+ * How: tad_run_state_buckets' two passes over every key's whole segment with a piecewise bucket function (a point at or after b is a
+ * bucket of its own): heads per chunk of 2048 points, one scan, then the fold written straight into the candidate arenas — no packed
+ * copy of the state in between.  A chunk wholly at or after b is a plain coalesced copy.  The history is re-sorted per key.
+ * Memory outside the state: 12 B per chunk (one per key and per 2048 points) and about 30 B per key of job-context workspace.
+ * Lock order: the state, then a job context, as a trim. */
+#define TAD_FEATURE_STATE_ROLLUP 524288u /* tad_state_rollup: a state's points below a bound folded into time buckets, in place */
+typedef struct {
+  uint64_t points_before;                 /* series points of the state before the call */
+  uint64_t points_after;                  /* ... and after it */
+  uint64_t points_rolled;                 /* raw points that lay below the bound */
+  uint64_t buckets;                       /* points the state holds below the bound afterwards */
+  uint64_t keys_changed;                  /* keys that lost at least one point */
+  int64_t  before_t;                      /* the bound that was applied (floored, above) */
+  double   ms_total;                      /* HIP events; 0 when nothing ran */
+  int32_t  job_context;
+} tad_rollup_stats;
+int tad_state_rollup(tad_engine *e, tad_state *s, int64_t before_t, int64_t bucket_s, int64_t bucket_origin,
+                     tad_value_op bucket_op, double ewma_alpha, tad_rollup_stats *stats /* may be NULL */);
+
 /* ---- the batch verdicts over a time range of a state (TAD_FEATURE_STATE_WINDOW; check tad_features() before calling this) ----
  * tad_run_state judges everything the state holds, and tad_state_trim narrows a state for good and at its old end only.  A state that
  * keeps seven days can answer "the last 24 h" or "everything up to the last complete hour" with this call: read-only, any window the

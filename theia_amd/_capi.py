@@ -41,7 +41,8 @@ TAD_FEATURE_STRING_RETIRE = 16384            # tad_features() bit: tad_keydict_m
 TAD_FEATURE_STRING_LIKE = 32768              # tad_features() bit: tad_strdict_like: LIKE / ilike patterns with % and _ matched on the device
 TAD_FEATURE_STATE_ALERTS = 131072            # tad_features() bit: tad_state_merge_changes / tad_state_replace_changes: what a merge or a replace changed; tad_run_state_since / tad_drop_state_since
 TAD_FEATURE_STATE_BUCKETS = 262144           # tad_features() bit: tad_run_state_buckets: a state's window judged in time buckets
-TAD_NO_CHANGE = (1 << 63) - 1               # tad_changes.key_since: the key's series did not change
+TAD_FEATURE_STATE_ROLLUP = 524288            # tad_features() bit: tad_state_rollup: a state's old points folded into time buckets, in place
+TAD_NO_CHANGE = (1 << 63) - 1              # tad_changes.key_since: the key's series did not change
 TAD_LIKE_NOCASE = 1                          # tad_strdict_like flags: compare after folding 'A'..'Z' to 'a'..'z' (ilike)
 TAD_CODE_NONE = -1                           # tad_strdict_lookup: the string is not in the dictionary
 TAD_STR_EQUAL, TAD_STR_CONTAINS_NOCASE = 0, 1   # tad_strdict_match: the value is the pattern / the pattern occurs in it, ASCII letters without case
@@ -157,6 +158,12 @@ class BucketWindow(C.Structure):
     _fields_ = ReportWindow._fields_ + [("bucket_s", i64), ("bucket_origin", i64), ("bucket_op", C.c_int)]
 
 
+class RollupStats(C.Structure):
+    """tad_rollup_stats: what one tad_state_rollup call folded."""
+    _fields_ = [("points_before", u64), ("points_after", u64), ("points_rolled", u64), ("buckets", u64), ("keys_changed", u64), ("before_t", i64),
+                ("ms_total", f64), ("job_context", i32)]
+
+
 class CompactStats(C.Structure):
     """tad_compact_stats: what one tad_state_compact call retired and moved."""
     _fields_ = [("keys_before", u64), ("keys_after", u64), ("num_keys", u64), ("keys_unseen", u64), ("keys_idle", u64), ("points_dropped", u64),
@@ -213,6 +220,7 @@ SYMBOLS = {
     "tad_state_import_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_state_trim": (C.c_int, [C.c_void_p, C.c_void_p, u64, i64, f64, C.POINTER(u64)]),
     "tad_state_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(u64)]),
+    "tad_state_rollup": (C.c_int, [C.c_void_p, C.c_void_p, i64, i64, i64, C.c_int, f64, C.POINTER(RollupStats)]),
     "tad_state_export_times": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_state_import_times": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tad_run_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Job), C.POINTER(Columns), C.c_int, C.POINTER(C.POINTER(Result))]),

@@ -1,6 +1,6 @@
-// tad_bucket.h — the time arithmetic of tad_run_state_buckets (include/tad.h), in one place: the kernels of tad_window.hip, the host
-// checks of tad_capi_view.cpp and a stand-alone program (tests/test_bucket_host.py) all include this header and nothing else computes a
-// bucket.  Plain C++: no HIP, no engine types.
+// tad_bucket.h — the time arithmetic of tad_run_state_buckets and tad_state_rollup (include/tad.h), in one place: the kernels of
+// tad_window.hip, the host checks of tad_capi_view.cpp and tad_capi_state.cpp and two stand-alone programs (tests/test_bucket_host.py,
+// tests/test_rollup_host.py) all include this header and nothing else computes a bucket.  Plain C++: no HIP, no engine types.
 //
 // A bucket is [start, start + bucket_s) with start = origin + bucket_s * floor((t - origin) / bucket_s): FLOOR division, so a time below
 // the origin (below zero too) rounds down, never towards zero.  Documented domain: |t| < 2^62, 1 <= bucket_s <= 2^40, 0 <= origin <
@@ -35,6 +35,11 @@ TAD_BUCKET_FN int64_t bucket_start(int64_t t, int64_t bucket_s, int64_t origin) 
   const uint64_t back = below ? (r != 0 ? b - r : 0) : r;   // how far t lies above its bucket's start
   return (int64_t)((uint64_t)t - back);
 }
+
+// tad_state_rollup's piecewise bucket function: a time below the bound b moves to its bucket's start, a time at or after it stays.  b is
+// itself a bucket start (the caller floors it), so no bucket straddles it: every image of a time below b is below b, and a key's strictly
+// ascending times stay strictly ascending once equal images are folded into one point
+TAD_BUCKET_FN int64_t rollup_start(int64_t t, int64_t b, int64_t bucket_s, int64_t origin) { return t < b ? bucket_start(t, bucket_s, origin) : t; }
 
 }  // namespace tad
 

@@ -2,6 +2,7 @@
 // history, the series and the times, resize, trim, compact, and what the batches on a state (tad_capi.cpp) share with them.  Everything a
 // state holds is double-buffered and indexed by tad_state::cur (tad_engine.h); every step that applies to "each store the state keeps"
 // is written once here, over each_segments / each_arena.
+#include "tad_bucket.h"
 #include "tad_engine.h"
 
 using namespace tad;
@@ -533,6 +534,102 @@ int tad_state_trim(tad_engine *eng, tad_state *st, uint64_t keep_points, int64_t
   state_commit(st, kept, kept);
   (void)size_arenas(e, st, cur, kept, kept, false, "tad_state_trim");
   if (dropped) *dropped = evicted;
+  return TAD_OK;
+}
+
+// tad.h: every key's points below the bound fold into their time buckets, the rest stay (kernels in tad_window.hip: the bucket pair of
+// tad_run_state_buckets with rollup_start, over every key's whole segment).  A trim's shape: only the candidate copies of the moments,
+// offsets and arenas are written — the fold goes straight into the candidate arenas, no packed copy of the state in between — and they
+// become current together once every launch has succeeded.
+int tad_state_rollup(tad_engine *eng, tad_state *st, int64_t before_t, int64_t bucket_s, int64_t bucket_origin, tad_value_op bucket_op, double ewma_alpha,
+                     tad_rollup_stats *stats) {
+  const char *who = "tad_state_rollup";
+  if (stats) *stats = tad_rollup_stats{};
+  if (!eng || !st) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bad arguments", who);
+  if (!st->series || !st->times)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the state needs TAD_STATE_SERIES | TAD_STATE_TIMES; state unchanged", who);
+  if (!bucket_args_ok(bucket_s, bucket_origin))
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bucket_s must be >= 1 and 0 <= bucket_origin < bucket_s (got %lld, %lld); state unchanged", who,
+                (long long)bucket_s, (long long)bucket_origin);
+  if (bucket_op != TAD_OP_SUM && bucket_op != TAD_OP_MAX)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: bucket_op must be TAD_OP_SUM or TAD_OP_MAX; state unchanged", who);
+  if (!(ewma_alpha >= 0.0 && ewma_alpha <= 1.0)) return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: ewma_alpha out of range; state unchanged", who);
+  constexpr int64_t kLimit = (int64_t)1 << 62;
+  if (before_t >= kLimit || before_t <= -kLimit)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: |before_t| must be below 2^62; state unchanged", who);
+  StateCall call(eng, st);
+  if (st->times_stale)
+    return fail(eng, TAD_ERR_INVALID_ARGUMENT, "%s: the series was imported without its times (tad_state_import_times)", who);
+  const long long b = (long long)bucket_start(before_t, bucket_s, bucket_origin);   // no bucket straddles the bound
+  const uint64_t K = st->K;
+  const int cur = st->cur, cand = cur ^ 1;
+  const uint64_t S = st->ser.len[cur];
+  tad_rollup_stats rs{};
+  rs.points_before = rs.points_after = S;
+  rs.before_t = b;
+  if (S == 0) { if (stats) *stats = rs; return TAD_OK; }
+  int rc;
+  if ((rc = call.enter(who)) != TAD_OK) return rc;
+  JobCtx *e = call.e;
+  hipStream_t s = e->stream;
+  rs.job_context = e->index;
+  const double alpha = ewma_alpha == 0.0 ? 0.5 : ewma_alpha;
+  // workspace: the per-key and per-chunk arrays of RollupKeys (bk_key) and the scan scratch, held against the limit before anything is written
+  const uint64_t bound = trim_chunks_bound(K, S);
+  const size_t scan_bytes = scan_scratch_elems(bound > K ? bound : K) * sizeof(unsigned long long);
+  const size_t need = carved_bytes(rollup_keys_layout, K, bound) + scan_bytes;
+  if (need > e->ws_limit)
+    return fail(e, TAD_ERR_GRID_TOO_LARGE, "%s needs %llu bytes of scratch > workspace limit %llu; state unchanged", who, (unsigned long long)need,
+                (unsigned long long)e->ws_limit);
+  RollupKeys rk;
+  if ((rc = carve_buf(e, e->bk_key, &rk, rollup_keys_layout, K, bound)) != TAD_OK || (rc = ensure(e, e->scan_scratch, scan_bytes)) != TAD_OK) return rc;
+  unsigned long long *scratch = static_cast<unsigned long long *>(e->scan_scratch.p);
+  const Segments &ser = st->ser, &hist = st->hist;
+  const long long *t_cur = st->ser_times.p[cur];
+  // 1. every key's whole segment in chunks; the heads per chunk under rollup_start; 2. their scan = every chunk's first point afterwards;
+  // the candidate series offsets, what every key keeps and loses, the counters; one round trip for the totals
+  HIP_TRY(e, hipEventRecord(e->ev[0], s));
+  HIP_TRY(e, hipMemsetAsync(rk.rc, 0, sizeof(RollupCounters), s));
+  launch_win_bounds(s, K, ser.off[cur], t_cur, 0, 0, 0, nullptr, rk.beg, rk.len, rk.ecnt, rk.chunks);
+  launch_scan(s, rk.chunks, rk.coff, K, scratch);
+  const BucketSource src{ser.off[cur], ser.val.p[cur], t_cur, rk.beg, rk.len};
+  launch_rollup_heads(s, bound, rk.coff, K, src, b, (long long)bucket_s, (long long)bucket_origin, rk.hcnt);
+  launch_scan(s, rk.hcnt, rk.hoff, bound, scratch);
+  launch_rollup_keys(s, K, ser.off[cur], t_cur, rk.coff, rk.hoff, b, ser.off[cand], rk.rcnt, rk.ecnt, rk.rc);
+  HIP_TRY(e, hipGetLastError());
+  unsigned long long *tot = reinterpret_cast<unsigned long long *>(e->tail_host);
+  HIP_TRY(e, hipMemcpyAsync(tot, rk.hoff + bound, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipMemcpyAsync(tot + 1, rk.rc, 24, hipMemcpyDeviceToHost, s));
+  HIP_TRY(e, hipStreamSynchronize(s));
+  const uint64_t after = tot[0], rolled = tot[1], buckets = tot[2], changed = tot[3];
+  if (after > S || buckets > rolled || S - after != rolled - buckets)
+    return fail(e, TAD_ERR_HIP, "%s: %llu points of %llu afterwards, %llu of %llu below the bound; state unchanged", who, (unsigned long long)after,
+                (unsigned long long)S, (unsigned long long)buckets, (unsigned long long)rolled);
+  if (rolled == 0) { if (stats) *stats = rs; return TAD_OK; }   // nothing below the bound: the state stays as it is (the candidate offsets are scratch)
+  // 3. the candidate arenas at their new size (the trim's rule): an allocation failure leaves the state as it is
+  if ((rc = size_arenas(e, st, cand, after, after, true, who)) != TAD_OK) return rc;
+  // 4. the fold, straight into the candidate values and times; 5. the history: the new values sorted per key; 6. the moments and last_t
+  launch_rollup_fold(s, bound, rk.coff, K, src, b, (long long)bucket_s, (long long)bucket_origin, bucket_op == TAD_OP_MAX, rk.hoff, after, ser.val.p[cand],
+                     st->ser_times.p[cand]);
+  if (st->history) {
+    HIP_TRY(e, hipMemcpyAsync(hist.off[cand], ser.off[cand], (K + 1) * 8, hipMemcpyDeviceToDevice, s));
+    launch_hist_sort(s, ser.val.p[cand], ser.off[cand], K, hist.val.p[cand], rk.chunks, rk.long_count);   // (chunks: read for the last time by the scan to coff)
+  }
+  launch_rollup_moments(s, K, rk.rcnt, rk.ecnt, ser.off[cand], ser.val.p[cand], st->ser_times.p[cand], alpha, state_view(st, cur), state_view(st, cand));
+  HIP_TRY(e, hipEventRecord(e->ev[1], s));
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipStreamSynchronize(s));
+  float ms = 0.f;
+  HIP_TRY(e, hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
+  // everything succeeded: the candidate becomes current; the old arenas, now the candidates, are given back when far too big for it
+  state_commit(st, after, after);
+  (void)size_arenas(e, st, cur, after, after, false, who);
+  rs.points_after = after;
+  rs.points_rolled = rolled;
+  rs.buckets = buckets;
+  rs.keys_changed = changed;
+  rs.ms_total = ms;
+  if (stats) *stats = rs;
   return TAD_OK;
 }
 

@@ -260,6 +260,34 @@ inline BucketKeys bucket_keys_layout(Carve &c, uint64_t K, uint64_t chunks) {
   return b;
 }
 
+// ---- tad_state_rollup (bk_key; the folded values and times go straight into the state's candidate arenas) ----
+// (this layout's stand-alone check lives in tests/test_state_rollup_abi.py)
+struct RollupCounters {   // one 64-byte block on the device, zeroed per call
+  unsigned long long rolled, buckets, keys_changed, pad[5];   // raw points below the bound | points below it afterwards | keys that lost a point
+};
+struct RollupKeys {   // counters | per key: range begin (0) | range length | points afterwards | points folded away | chunks (later the long-sort list) | the list's length | chunk offsets; per chunk: heads | their scan (chunks + 1)
+  RollupCounters *rc;
+  uint32_t *beg, *len, *rcnt, *ecnt, *chunks;
+  unsigned int *long_count;
+  unsigned long long *coff;
+  uint32_t *hcnt;
+  unsigned long long *hoff;
+};
+inline RollupKeys rollup_keys_layout(Carve &c, uint64_t K, uint64_t chunks) {
+  RollupKeys r;
+  r.rc = c.take<RollupCounters>(1, 16);
+  r.beg = take_counts(c, K);
+  r.len = take_counts(c, K);
+  r.rcnt = take_counts(c, K);
+  r.ecnt = take_counts(c, K);
+  r.chunks = take_counts(c, K);
+  r.long_count = take_cell(c);
+  r.coff = take_offsets(c, K);
+  r.hcnt = take_counts(c, chunks);
+  r.hoff = take_offsets(c, chunks);
+  return r;
+}
+
 // ---- tad_state_merge (mg_pts, mg_keys) ----
 struct MergeCounters {   // one 64-byte block on the device, zeroed per attempt
   unsigned long long too_old, appended, inserted, combined, keys_touched, keys_replayed, keys_emptied, pad[1];   // keys_emptied: tad_state_replace only

@@ -219,7 +219,7 @@ int alloc_device_block(JobCtx *e, size_t bytes, ResultBlock *rb) {
 extern "C" {
 
 int tad_abi_version(void) { return TAD_ABI_VERSION; }
-int tad_features(void) { return (int)(TAD_FEATURE_NARROW_COLUMNS | TAD_FEATURE_STREAM_DBSCAN | TAD_FEATURE_STREAM_ARIMA | TAD_FEATURE_STREAM_TRIM | TAD_FEATURE_STATE_RUN | TAD_FEATURE_STATE_MERGE | TAD_FEATURE_STATE_REPLACE | TAD_FEATURE_STATE_WINDOW | TAD_FEATURE_KEY_DICT | TAD_FEATURE_KEY_RETIRE | TAD_FEATURE_STATE_DROP | TAD_FEATURE_DROP_ROWS | TAD_FEATURE_KEY_SELECT | TAD_FEATURE_STRING_DICT | TAD_FEATURE_DICT_DECODE | TAD_FEATURE_STRING_RETIRE | TAD_FEATURE_STRING_LIKE | TAD_FEATURE_STATE_ALERTS | TAD_FEATURE_STATE_BUCKETS); }
+int tad_features(void) { return (int)(TAD_FEATURE_NARROW_COLUMNS | TAD_FEATURE_STREAM_DBSCAN | TAD_FEATURE_STREAM_ARIMA | TAD_FEATURE_STREAM_TRIM | TAD_FEATURE_STATE_RUN | TAD_FEATURE_STATE_MERGE | TAD_FEATURE_STATE_REPLACE | TAD_FEATURE_STATE_WINDOW | TAD_FEATURE_KEY_DICT | TAD_FEATURE_KEY_RETIRE | TAD_FEATURE_STATE_DROP | TAD_FEATURE_DROP_ROWS | TAD_FEATURE_KEY_SELECT | TAD_FEATURE_STRING_DICT | TAD_FEATURE_DICT_DECODE | TAD_FEATURE_STRING_RETIRE | TAD_FEATURE_STRING_LIKE | TAD_FEATURE_STATE_ALERTS | TAD_FEATURE_STATE_BUCKETS | TAD_FEATURE_STATE_ROLLUP); }
 
 const char *tad_last_error(tad_engine *e) {
   if (!e) return g_static_err.c_str();

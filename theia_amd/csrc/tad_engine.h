@@ -88,7 +88,7 @@ struct JobBufs {
   DevBuf hs_key, hs_t, hs_val, hs_sorted, hs_noise, hs_cnt, hs_row, hs_koff, hs_kcnt;   // a history batch: new points, sorted values, verdicts, rows, offsets
   DevBuf wv_key, wv_pts;   // tad_run_state_window's view: per key (bounds, offsets, moments) | per window point (values, times, sorted values)
   DevBuf sn_key, sn_pts;   // tad_run_state_since / tad_drop_state_since: per key (the reported suffix, a staged key_since) | per reported point (key, value, time)
-  DevBuf bk_key;           // tad_run_state_buckets: per key (buckets, folded points, bucket offsets) | per chunk (heads, their scan); the buckets themselves: wv_pts
+  DevBuf bk_key;           // tad_run_state_buckets: per key (buckets, folded points, bucket offsets) | per chunk (heads, their scan); the buckets themselves: wv_pts; tad_state_rollup: its RollupKeys
   DevBuf mg_pts, mg_keys, mg_hist;   // tad_state_merge: per batch point | per key | the history between its subtract and its merge
   DevBuf rp_keys, rp_loss;           // tad_state_replace, beside a merge's: per key (the erased runs) | the values the history loses, packed and sorted
   DevBuf mg_report;                  // tad_state_merge_changes / tad_state_replace_changes: the report's counters | a host array's staging

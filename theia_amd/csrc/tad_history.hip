@@ -399,10 +399,12 @@ __global__ __launch_bounds__(kHBlock) void k_hist_subtract(const unsigned long l
 
 static constexpr int kTrimChunk = 8;   // points per prefetched register chunk of k_trim_moments (64 B of values)
 // One lane per key: the candidate moments.  The retained values are read from the candidate series (written by k_trim_copy);
-// last_t stays: a key that keeps a point keeps its newest one.
+// last_t stays: a key that keeps a point keeps its newest one.  NEW_T (tad_state_rollup, where a key's newest point can move to its
+// bucket's start): last_t of every key with a point is the candidate times' last entry of the key, whether the key lost a point or not.
+template <typename... NEW_T>   // (no argument: the trim's kernel with the trim's arguments; one: const long long *st_new)
 __global__ __launch_bounds__(kHBlock) void k_trim_moments(uint64_t K, const uint32_t *__restrict__ rcnt, const uint32_t *__restrict__ ecnt,
                                                          const unsigned long long *__restrict__ soff_new, const unsigned long long *__restrict__ sval_new,
-                                                         double alpha, StreamState cur, StreamState next) {
+                                                         double alpha, StreamState cur, StreamState next, NEW_T... st_new) {
   const uint64_t k = (uint64_t)blockIdx.x * kHBlock + threadIdx.x;
   if (k >= K) return;
   StreamAcc a = stream_load(cur, k);
@@ -440,6 +442,10 @@ __global__ __launch_bounds__(kHBlock) void k_trim_moments(uint64_t K, const uint
       }
     }
   }
+  if constexpr (sizeof...(NEW_T) != 0) {
+    const long long *const t_new[] = {st_new...};
+    if (r != 0) a.last_t = t_new[0][soff_new[k] + r - 1];
+  }
   stream_store(next, k, a);
 }
 
@@ -471,7 +477,13 @@ void launch_hist_subtract(hipStream_t s, uint64_t chunks_bound, const unsigned l
 void launch_trim_moments(hipStream_t s, uint64_t K, const uint32_t *rcnt, const uint32_t *ecnt, const unsigned long long *soff_new,
                          const unsigned long long *sval_new, double alpha, StreamState cur, StreamState next) {
   if (K == 0) return;
-  hipLaunchKernelGGL(k_trim_moments, dim3(hist_blocks(K)), dim3(kHBlock), 0, s, K, rcnt, ecnt, soff_new, sval_new, alpha, cur, next);
+  hipLaunchKernelGGL(k_trim_moments<>, dim3(hist_blocks(K)), dim3(kHBlock), 0, s, K, rcnt, ecnt, soff_new, sval_new, alpha, cur, next);
+}
+
+void launch_rollup_moments(hipStream_t s, uint64_t K, const uint32_t *rcnt, const uint32_t *ecnt, const unsigned long long *soff_new,
+                           const unsigned long long *sval_new, const long long *st_new, double alpha, StreamState cur, StreamState next) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_trim_moments<const long long *>, dim3(hist_blocks(K)), dim3(kHBlock), 0, s, K, rcnt, ecnt, soff_new, sval_new, alpha, cur, next, st_new);
 }
 
 const void *code_anchor_history() { return reinterpret_cast<const void *>(&k_hist_verdict); }

@@ -397,6 +397,9 @@ void launch_hist_subtract(hipStream_t s, uint64_t chunks_bound, const unsigned l
 // next = cur for the keys that lost nothing; the others replayed with stream_step over their retained values (unseen if none)
 void launch_trim_moments(hipStream_t s, uint64_t K, const uint32_t *rcnt, const uint32_t *ecnt, const unsigned long long *soff_new,
                          const unsigned long long *sval_new, double alpha, StreamState cur, StreamState next);
+// the same for tad_state_rollup, where a key's newest time can move: last_t of EVERY key with a point becomes st_new's last entry of the key
+void launch_rollup_moments(hipStream_t s, uint64_t K, const uint32_t *rcnt, const uint32_t *ecnt, const unsigned long long *soff_new,
+                           const unsigned long long *sval_new, const long long *st_new, double alpha, StreamState cur, StreamState next);
 // ---- tad_run_state (tad_window.hip): the batch verdicts of a state's whole window from its CSR series soff / sval / st ----
 // the shortest series that takes a wavefront of its own, for K keys holding `points` points
 unsigned long long win_coop_min(uint64_t K, uint64_t points);
@@ -475,6 +478,18 @@ void launch_win_bucket_fold(hipStream_t s, uint64_t chunks_bound, const unsigned
 // boff[k] (K + 1) = the first bucket of key k, bcnt[k] = its buckets, becnt[k] = the points of its segment that are not a bucket of their own
 void launch_win_bucket_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *coff, const unsigned long long *hoff,
                             unsigned long long *boff, uint32_t *bcnt, uint32_t *becnt);
+// ---- tad_state_rollup (tad_window.hip): the same two passes with rollup_start (tad_bucket.h) — a point at or after `bound` is a bucket
+// of its own — over every key's WHOLE segment (src.beg = 0, src.len = the segment), written straight into a state's candidate arenas ----
+void launch_rollup_heads(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const BucketSource &src, long long bound,
+                         long long bucket_s, long long bucket_origin, uint32_t *hcnt);
+// sval_new[c] / st_new[c] = value and time of point c afterwards, c < points = hoff[chunks_bound]; a chunk wholly at or after the bound is copied
+void launch_rollup_fold(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const BucketSource &src, long long bound,
+                        long long bucket_s, long long bucket_origin, bool op_max, const unsigned long long *hoff, uint64_t points,
+                        unsigned long long *sval_new, long long *st_new);
+// soff_new[k] (K + 1) = key k's first point afterwards, rcnt[k] = its points afterwards, ecnt[k] = its points folded away; rc (zeroed by the
+// caller) += the raw points below the bound, the points below it afterwards, the keys with ecnt != 0.  st: the OLD times
+void launch_rollup_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, const unsigned long long *coff,
+                        const unsigned long long *hoff, long long bound, unsigned long long *soff_new, uint32_t *rcnt, uint32_t *ecnt, RollupCounters *rc);
 // DBSCAN's window history: true = sort the window's values per key, false = sort the excluded values and subtract them from the state's
 // history.  A pure function of the two totals: 2 * window_points <= state_points
 bool win_hist_by_sort(uint64_t window_points, uint64_t state_points);

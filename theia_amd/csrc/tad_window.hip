@@ -442,13 +442,27 @@ __global__ __launch_bounds__(kWBlock) void k_win_suffix(const unsigned long long
 //                       scratch, no floating point;
 //   k_win_bucket_keys   one lane per key: the view's offsets boff[k] = the destination of the key's first chunk, the buckets per key and
 //                       the points folded away or cut (what launch_trim_moments takes as rcnt / ecnt).
-// The source is described by offsets and ranges and the destination by plain arrays (BucketSource), so a later in-place roll-up of a
-// state's old points can call the same launchers.  No kernel here reads a series slot outside the key's range or writes a cell >= buckets.
+// The source is described by offsets and ranges and the destination by plain arrays (BucketSource): tad_state_rollup (tad_capi_state.cpp)
+// runs the same two kernels with ROLLUP = true over every key's whole segment, its destination the state's candidate arenas.  No kernel here reads a series slot outside the key's range or writes a cell >= buckets.
+// The bucket function of a launch, passed by value: the two numbers of tad_run_state_buckets (two 8-byte kernel arguments, as before the
+// roll-up existed), and for tad_state_rollup the bound as well — rollup_start (tad_bucket.h): a point at or after the bound is a bucket of
+// its own.
+template <bool ROLLUP> struct BucketFn;
+template <> struct BucketFn<false> {
+  long long bucket_s, origin;
+  __device__ __forceinline__ long long operator()(long long t) const { return bucket_start(t, bucket_s, origin); }
+};
+template <> struct BucketFn<true> {
+  long long bucket_s, origin, bound;
+  __device__ __forceinline__ long long operator()(long long t) const { return rollup_start(t, bound, bucket_s, origin); }
+};
+
+template <bool ROLLUP>
 __device__ __forceinline__ bool bucket_head(const long long *__restrict__ st_key, unsigned long long u, bool valid, unsigned long long beg, unsigned lane,
-                                            long long bucket_s, long long origin, long long *start) {
-  const long long s = valid ? bucket_start(st_key[u], bucket_s, origin) : 0ll;
+                                            const BucketFn<ROLLUP> &fn, long long *start) {
+  const long long s = valid ? fn(st_key[u]) : 0ll;
   long long prev = __shfl_up(s, 1);
-  if (lane == 0 && valid && u > beg) prev = bucket_start(st_key[u - 1], bucket_s, origin);   // the element before the slice
+  if (lane == 0 && valid && u > beg) prev = fn(st_key[u - 1]);   // the element before the slice
   *start = s;
   return valid && (u == beg || s != prev);
 }
@@ -468,8 +482,11 @@ __device__ __forceinline__ bool bucket_chunk(const unsigned long long *__restric
   return a0 < a1;
 }
 
+// ROLLUP (tad_state_rollup): a chunk whose first point is at or after the bound holds only buckets of one point — times ascend, and its
+// first point is a head because its predecessor's image lies below the bound — so its heads are its points and it reads one time.
+template <bool ROLLUP>
 __global__ __launch_bounds__(kWBlock) void k_win_bucket_heads(const unsigned long long *__restrict__ coff, uint64_t K, uint64_t chunks_bound, BucketSource src,
-                                                             long long bucket_s, long long origin, uint32_t *__restrict__ hcnt) {
+                                                             BucketFn<ROLLUP> fn, uint32_t *__restrict__ hcnt) {
   const unsigned long long w = ((uint64_t)blockIdx.x * kWBlock + threadIdx.x) >> 6;
   if (w >= chunks_bound) return;
   const unsigned lane = threadIdx.x & 63u;
@@ -478,12 +495,16 @@ __global__ __launch_bounds__(kWBlock) void k_win_bucket_heads(const unsigned lon
     uint64_t k;
     unsigned long long o0, beg, end, c0, c1;
     if (bucket_chunk(coff, K, src, w, &k, &o0, &beg, &end, &c0, &c1)) {
-      for (unsigned long long u0 = c0; u0 < c1; u0 += 64) {
-        const unsigned long long u = u0 + lane;
-        long long start;
-        const bool head = bucket_head(src.st + o0, u, u < c1, beg, lane, bucket_s, origin, &start);
-        heads += (uint32_t)__popcll(__ballot(head));
-      }
+      bool tail = false;   // (wavefront-uniform: every lane reads the same time)
+      if constexpr (ROLLUP) tail = src.st[o0 + c0] >= fn.bound;
+      if (tail) heads = (uint32_t)(c1 - c0);
+      else
+        for (unsigned long long u0 = c0; u0 < c1; u0 += 64) {
+          const unsigned long long u = u0 + lane;
+          long long start;
+          const bool head = bucket_head(src.st + o0, u, u < c1, beg, lane, fn, &start);
+          heads += (uint32_t)__popcll(__ballot(head));
+        }
     }
   }
   if (lane == 0) hcnt[w] = heads;
@@ -493,9 +514,12 @@ template <bool MAX> __device__ __forceinline__ unsigned long long bucket_op(unsi
   return MAX ? (a > b ? a : b) : a + b;
 }
 
-template <bool MAX>
-__global__ __launch_bounds__(kWBlock) void k_win_bucket_fold(const unsigned long long *__restrict__ coff, uint64_t K, BucketSource src, long long bucket_s,
-                                                            long long origin, const unsigned long long *__restrict__ hoff, uint64_t buckets,
+// ROLLUP: a chunk wholly at or after the bound (k_win_bucket_heads' test) is a copy — coalesced loads and stores of values and times to
+// hoff[w] + (u - c0), no shuffle, no atomic.  The chunk that holds the split and the chunks below it take the fold; the points of the
+// split chunk at or after the bound are runs of one there.
+template <bool MAX, bool ROLLUP>
+__global__ __launch_bounds__(kWBlock) void k_win_bucket_fold(const unsigned long long *__restrict__ coff, uint64_t K, BucketSource src, BucketFn<ROLLUP> fn,
+                                                            const unsigned long long *__restrict__ hoff, uint64_t buckets,
                                                             unsigned long long *__restrict__ bval, long long *__restrict__ bt) {
   const unsigned long long w = ((uint64_t)blockIdx.x * kWBlock + threadIdx.x) >> 6;
   if (w >= coff[K]) return;
@@ -505,6 +529,15 @@ __global__ __launch_bounds__(kWBlock) void k_win_bucket_fold(const unsigned long
   if (!bucket_chunk(coff, K, src, w, &k, &o0, &beg, &end, &c0, &c1)) return;
   // the chunk's first head goes to cell hoff[w]; the run open at its first point (head in an earlier chunk of the key) is the cell before
   unsigned long long cell_next = hoff[w];
+  if constexpr (ROLLUP) {
+    if (src.st[o0 + c0] >= fn.bound) {   // (wavefront-uniform)
+      for (unsigned long long u = c0 + lane; u < c1; u += 64) {
+        const unsigned long long cell = cell_next + (u - c0);
+        if (cell < buckets) { bval[cell] = src.sval[o0 + u]; bt[cell] = src.st[o0 + u]; }
+      }
+      return;
+    }
+  }
   // the run open at a slice's first point: what this chunk has folded of it so far, and whether its head lies in this chunk
   unsigned long long carry = 0;
   bool carry_head = false;
@@ -512,7 +545,7 @@ __global__ __launch_bounds__(kWBlock) void k_win_bucket_fold(const unsigned long
     const unsigned long long u = u0 + lane;
     const bool valid = u < c1;
     long long start;
-    const bool head = bucket_head(src.st + o0, u, valid, beg, lane, bucket_s, origin, &start);
+    const bool head = bucket_head(src.st + o0, u, valid, beg, lane, fn, &start);
     unsigned long long x = valid ? src.sval[o0 + u] : 0ull;
     const unsigned long long hm = __ballot(head);
     // the run carried out of the previous slice ended at its lane 63: this slice opens with a head
@@ -559,6 +592,41 @@ __global__ __launch_bounds__(kWBlock) void k_win_bucket_keys(uint64_t K, const u
   const unsigned long long nb = hoff[coff[k + 1]] - b0;
   bcnt[k] = (uint32_t)nb;
   becnt[k] = (uint32_t)(soff[k + 1] - soff[k] - nb);
+}
+
+// tad_state_rollup, k_win_bucket_keys' place: the candidate series offsets, per key the points afterwards and the points folded away (what
+// launch_trim_moments takes as rcnt / ecnt), and the call's counters.  A key's points below the bound: one lower bound over its OLD times;
+// all of its folded points lie among them.  One atomic per wavefront and counter.
+__global__ __launch_bounds__(kWBlock) void k_rollup_keys(uint64_t K, const unsigned long long *__restrict__ soff, const long long *__restrict__ st,
+                                                        const unsigned long long *__restrict__ coff, const unsigned long long *__restrict__ hoff,
+                                                        long long bound, unsigned long long *__restrict__ boff, uint32_t *__restrict__ rcnt,
+                                                        uint32_t *__restrict__ ecnt, RollupCounters *__restrict__ rc) {
+  const uint64_t k = (uint64_t)blockIdx.x * kWBlock + threadIdx.x;
+  unsigned long long below = 0, folded = 0;
+  if (k <= K) {
+    const unsigned long long b0 = hoff[coff[k]];
+    boff[k] = b0;
+    if (k < K) {
+      const unsigned long long o0 = soff[k], o1 = soff[k + 1];
+      const unsigned long long nb = hoff[coff[k + 1]] - b0;
+      folded = o1 - o0 - nb;
+      rcnt[k] = (uint32_t)nb;
+      ecnt[k] = (uint32_t)folded;
+      below = win_lower_t(st, o0, o1, bound) - o0;
+    }
+  }
+  unsigned long long after = below - folded;   // the points the key holds below the bound afterwards
+  const unsigned long long changed = __ballot(folded != 0);
+#pragma unroll
+  for (unsigned d = 32; d >= 1; d >>= 1) {   // (every lane of the wavefront is here)
+    below += __shfl_down(below, d);
+    after += __shfl_down(after, d);
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    if (below) atomicAdd(&rc->rolled, below);
+    if (after) atomicAdd(&rc->buckets, after);
+    if (changed) atomicAdd(&rc->keys_changed, (unsigned long long)__popcll(changed));
+  }
 }
 
 // ---- launchers ----
@@ -651,7 +719,8 @@ void launch_win_since(hipStream_t s, uint64_t K, const unsigned long long *soff,
 void launch_win_bucket_heads(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const BucketSource &src, long long bucket_s,
                              long long bucket_origin, uint32_t *hcnt) {
   if (K == 0) return;
-  hipLaunchKernelGGL(k_win_bucket_heads, dim3(win_blocks(chunks_bound * 64)), dim3(kWBlock), 0, s, coff, K, chunks_bound, src, bucket_s, bucket_origin, hcnt);
+  hipLaunchKernelGGL(k_win_bucket_heads<false>, dim3(win_blocks(chunks_bound * 64)), dim3(kWBlock), 0, s, coff, K, chunks_bound, src,
+                     BucketFn<false>{bucket_s, bucket_origin}, hcnt);
 }
 
 void launch_win_bucket_fold(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const BucketSource &src, long long bucket_s,
@@ -659,8 +728,35 @@ void launch_win_bucket_fold(hipStream_t s, uint64_t chunks_bound, const unsigned
   if (K == 0 || buckets == 0) return;
   hipMemsetAsync(bval, 0, (size_t)buckets * 8, s);   // 0 is the identity of both operations: a chunk-edge partial is an atomic onto its cell
   const dim3 grid(win_blocks(chunks_bound * 64)), block(kWBlock);
-  if (op_max) hipLaunchKernelGGL(k_win_bucket_fold<true>, grid, block, 0, s, coff, K, src, bucket_s, bucket_origin, hoff, buckets, bval, bt);
-  else hipLaunchKernelGGL(k_win_bucket_fold<false>, grid, block, 0, s, coff, K, src, bucket_s, bucket_origin, hoff, buckets, bval, bt);
+  const BucketFn<false> fn{bucket_s, bucket_origin};
+  if (op_max) hipLaunchKernelGGL((k_win_bucket_fold<true, false>), grid, block, 0, s, coff, K, src, fn, hoff, buckets, bval, bt);
+  else hipLaunchKernelGGL((k_win_bucket_fold<false, false>), grid, block, 0, s, coff, K, src, fn, hoff, buckets, bval, bt);
+}
+
+void launch_rollup_heads(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const BucketSource &src, long long bound,
+                         long long bucket_s, long long bucket_origin, uint32_t *hcnt) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_win_bucket_heads<true>, dim3(win_blocks(chunks_bound * 64)), dim3(kWBlock), 0, s, coff, K, chunks_bound, src,
+                     BucketFn<true>{bucket_s, bucket_origin, bound}, hcnt);
+}
+
+void launch_rollup_fold(hipStream_t s, uint64_t chunks_bound, const unsigned long long *coff, uint64_t K, const BucketSource &src, long long bound,
+                        long long bucket_s, long long bucket_origin, bool op_max, const unsigned long long *hoff, uint64_t points,
+                        unsigned long long *sval_new, long long *st_new) {
+  if (K == 0 || points == 0) return;
+  // 0 is the identity of both operations.  Only the cells of runs that cross a chunk edge receive an atomic, but which those are is known
+  // to the fold alone: the whole candidate is zeroed (8 B per point afterwards; DESIGN.md §5 has the cost)
+  hipMemsetAsync(sval_new, 0, (size_t)points * 8, s);
+  const dim3 grid(win_blocks(chunks_bound * 64)), block(kWBlock);
+  const BucketFn<true> fn{bucket_s, bucket_origin, bound};
+  if (op_max) hipLaunchKernelGGL((k_win_bucket_fold<true, true>), grid, block, 0, s, coff, K, src, fn, hoff, points, sval_new, st_new);
+  else hipLaunchKernelGGL((k_win_bucket_fold<false, true>), grid, block, 0, s, coff, K, src, fn, hoff, points, sval_new, st_new);
+}
+
+void launch_rollup_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, const long long *st, const unsigned long long *coff,
+                        const unsigned long long *hoff, long long bound, unsigned long long *soff_new, uint32_t *rcnt, uint32_t *ecnt, RollupCounters *rc) {
+  if (K == 0) return;
+  hipLaunchKernelGGL(k_rollup_keys, dim3(win_blocks(K + 1)), dim3(kWBlock), 0, s, K, soff, st, coff, hoff, bound, soff_new, rcnt, ecnt, rc);
 }
 
 void launch_win_bucket_keys(hipStream_t s, uint64_t K, const unsigned long long *soff, const unsigned long long *coff, const unsigned long long *hoff,

@@ -460,6 +460,19 @@ class TadState:
                                                              C.byref(dropped)))
         return int(dropped.value)
 
+    def rollup(self, before, bucket_s, origin=0, op="sum", alpha=0.0):
+        """Fold every key's points older than `before` into time buckets of bucket_s seconds, in place (tad_state_rollup): `before` is
+        floored to a bucket start b, the points of one key and bucket below b become one point at the bucket's start (op: "sum" wrapping,
+        or "max"), the points at or after b stay.  The state becomes that of a fresh state streamed the folded points with EWMA parameter
+        alpha (0 -> 0.5); a key's last_t can move to its last bucket's start.  Returns the fields of tad_rollup_stats as a dict."""
+        eng = self._engine
+        _need_feature(eng._lib, "STATE_ROLLUP", "tad_state_rollup")
+        if op not in ("sum", "max"):
+            raise ValueError("op must be 'sum' or 'max'")
+        rs = capi.RollupStats()
+        eng._check(eng._lib.tad_state_rollup(eng._h, self._h, int(before), int(bucket_s), int(origin), capi.TAD_OP[op], float(alpha), C.byref(rs)))
+        return {name: getattr(rs, name) for name, _ in capi.RollupStats._fields_}
+
     def compact(self, retire_before=0, out="host"):
         """Drop the dead keys and renumber the survivors densely, order kept (tad_state_compact): a key survives iff it has points and,
         with retire_before != 0, its newest point is at or after retire_before.  What a survivor holds is unchanged.  Returns (remap,

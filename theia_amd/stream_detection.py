@@ -158,6 +158,7 @@ class StreamingAnomalyDetection:
         self._state = None
         self.watermark = 0       # poll: the `now` of the last turn (0: no turn yet); carried by snapshot() / restore()
         self._broken = None      # why the instance can no longer be used (retire)
+        self._tiers = []         # rollup: (the bound as applied, bucket_s, bucket_op) per tier; carried by snapshot() / restore()
 
     @property
     def state(self):
@@ -181,6 +182,8 @@ class StreamingAnomalyDetection:
     def _feed(self, flows, replace, changes):
         """feed; changes: None, or where the change report of the merge / replace goes (TadEngine.merge_stream_changes)"""
         self._usable()
+        if replace is not None:
+            self._check_replace(int(replace[0]))
         eng = self._engine
         n = len(flows["flowEndSeconds"])
         if n == 0 and replace is not None:
@@ -252,6 +255,7 @@ class StreamingAnomalyDetection:
         if algo_type not in _ad.VALID_ALGOS:
             raise ValueError("Algorithm should be in {}".format(" or ".join(_ad.VALID_ALGOS)))
         bucket_s = self._bucket_args(bucket_s, bucket_op)
+        self._check_job_buckets(0, bucket_s, bucket_op)      # (the changed keys are judged over everything they hold)
         filters = (pod_label or "", pod_name or "", pod_namespace or "", external_ip or "", svc_port_name or "")
         self._terms(*filters)      # (a filter this instance does not serve is refused before the feed changes anything)
         stats = self._feed(flows, replace, "device")
@@ -297,7 +301,7 @@ class StreamingAnomalyDetection:
         now, lag_s = int(now), int(lag_s)
         if lag_s < 0:
             raise ValueError("lag_s must not be negative")
-        from_t = max(self.watermark - lag_s, 0)
+        from_t = self._floor_to_tiers(max(self.watermark - lag_s, 0))
         if from_t >= now:
             raise ValueError("now (%d) must lie after the watermark less the lag (%d)" % (now, from_t))
         flows = client.query_columns(_ch.stream_rows_query(self.agg_flow, self.pod_ident, list(self.ns_ignore_list), from_t, now), dict_strings=True)
@@ -348,6 +352,63 @@ class StreamingAnomalyDetection:
             raise ValueError("bucket_op should be 'sum' or 'max'")
         return bucket_s
 
+    # ---- retention: old points folded into time buckets (TadState.rollup) ----
+    def rollup(self, before, bucket_s, bucket_op="sum"):
+        """Fold everything older than `before` into buckets of bucket_s seconds, on the device (TadState.rollup, origin 0): the instance
+        keeps its context at bucket resolution instead of per second, and device_bytes() falls.  `before` is floored to a multiple of
+        bucket_s.  Returns the roll-up's statistics (None: nothing held yet).  The instance remembers its tiers — (the bound as applied,
+        bucket_s, bucket_op), carried by snapshot() / restore() — and from then on guards what a rolled region cannot answer: `job` (and
+        feed_alerts / poll_alerts) over it needs a bucket_s that is a multiple of every tier's it reaches, with that tier's bucket_op;
+        feed(replace=(from_t, to_t)) with from_t inside a rolled region must start on that tier's bucket start (a re-read from the middle
+        of a bucket would count the bucket's older seconds twice) — `poll` / `poll_alerts` floor their re-read's start to it instead."""
+        bucket_s = self._bucket_args(bucket_s, bucket_op)
+        if bucket_s < 1:
+            raise ValueError("bucket_s must be at least 1")
+        self._usable()
+        if self._state is None:
+            return None
+        stats = self._state.rollup(int(before), bucket_s, 0, bucket_op)
+        tier = (int(stats["before_t"]), bucket_s, bucket_op)
+        same = [i for i, t in enumerate(self._tiers) if t[1:] == tier[1:]]
+        if same:      # the same resolution again, further on: one tier
+            self._tiers[same[0]] = max(self._tiers[same[0]], tier)
+        else:
+            self._tiers.append(tier)
+        return stats
+
+    @property
+    def tiers(self):
+        """the roll-ups made so far: [(the bound as applied, bucket_s, bucket_op)]"""
+        return list(self._tiers)
+
+    def _tiers_at(self, t):
+        """the tiers whose rolled region (everything before their bound) holds the time t (0: before everything)"""
+        return [tier for tier in getattr(self, "_tiers", ()) if t < tier[0]]
+
+    def _check_replace(self, from_t):
+        if from_t == 0:      # no lower bound: the re-read erases the rolled region with everything else
+            return
+        for bound, bucket_s, _ in self._tiers_at(from_t):
+            if from_t % bucket_s:
+                raise ValueError("replace from %d starts inside a bucket of the region rolled up to %d at %d s: a re-read must start on a "
+                                 "bucket start there (%d)" % (from_t, bound, bucket_s, from_t // bucket_s * bucket_s))
+
+    def _floor_to_tiers(self, from_t):
+        """from_t, moved down to a bucket start of every tier whose rolled region holds it"""
+        while from_t:
+            low = min([from_t // bucket_s * bucket_s for _, bucket_s, _ in self._tiers_at(from_t)], default=from_t)
+            if low == from_t:
+                break
+            from_t = low
+        return from_t
+
+    def _check_job_buckets(self, from_t, bucket_s, bucket_op):
+        """a job over a window from from_t (0: the beginning) on: every tier it reaches must divide bucket_s and share bucket_op"""
+        for bound, tier_s, tier_op in self._tiers_at(from_t):
+            if bucket_s == 0 or bucket_s % tier_s or bucket_op != tier_op:
+                raise ValueError("the points before %d are rolled up to %d s buckets by %s: a job that reaches them needs a bucket_s that is a "
+                                 "multiple of %d and bucket_op=%r" % (bound, tier_s, tier_op, tier_s, tier_op))
+
     def job(self, algo_type, tad_id, end_time="", pod_label="", pod_name="", pod_namespace="", external_ip="", svc_port_name="", bucket_s=0,
             bucket_op="sum", complete_before=None):
         """One job over everything fed so far -> (stats dict, list of result rows): what anomaly_detection(algo_type, all rows fed, "",
@@ -366,6 +427,7 @@ class StreamingAnomalyDetection:
         if complete_before is not None and not bucket_s:
             raise ValueError("complete_before needs bucket_s")
         self._usable()
+        self._check_job_buckets(0, bucket_s, bucket_op)
         terms = self._terms(pod_label or "", pod_name or "", pod_namespace or "", external_ip or "", svc_port_name or "")
         decoder = _KeyDecoder(self._dict, self._vocab)      # the key table: decoded on demand, for the keys with result rows
         table = {name: _KeyColumn(decoder, "direction" if name == "direction" else i) for i, name in enumerate(_ad.KEY_COLUMNS[self.mode])}
@@ -406,6 +468,8 @@ class StreamingAnomalyDetection:
             snap["state_history_len"], snap["state_history"] = self._state.export_history()
             snap["state_series_len"], snap["state_series"] = self._state.export_series()
             snap["state_times"] = self._state.export_times()
+        if getattr(self, "_tiers", None):      # (an instance that never rolled up snapshots exactly what it always did)
+            snap["rollup_tiers"] = np.asarray([(b, s, 1 if op == "max" else 0) for b, s, op in self._tiers], dtype=np.int64).reshape(-1, 3)
         return snap
 
     @classmethod
@@ -421,6 +485,8 @@ class StreamingAnomalyDetection:
             self._dict.load([snapshot["key_col%d" % c] for c in range(len(self._vocab))], snapshot["key_side"])
             if "watermark" in snapshot:      # (a snapshot of before the poll loop has none)
                 self.watermark = int(np.asarray(snapshot["watermark"]).reshape(-1)[0])
+            if "rollup_tiers" in snapshot:   # (a snapshot of an instance that never rolled up, or of before the roll-up, has none)
+                self._tiers = [(int(b), int(s), "max" if op else "sum") for b, s, op in np.asarray(snapshot["rollup_tiers"]).reshape(-1, 3).tolist()]
             if "state_n" in snapshot:
                 st = self._engine.state_create(len(snapshot["state_n"]), history=True, series=True, times=True)
                 self._state = st

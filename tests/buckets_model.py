@@ -2,9 +2,8 @@
 written independently of both the kernels and the oracle's Stage 0.  tests/test_buckets_model.py holds it against oracle.tad_oracle.stage0
 over the floored rows; the GPU tests use it for the host-side numbers every case asserts before the engine is asked."""
 import numpy as np
+from state_helpers import I64, U64
 
-U64 = np.uint64
-I64 = np.int64
 NO_CHANGE = (1 << 63) - 1
 
 

@@ -14,15 +14,13 @@ import numpy as np
 
 from oracle import drop_oracle as dro
 from oracle import tad_oracle as orc
-
-from test_gpu_state_drop import pairwise_rows as pairwise_rows_8_to_128
+from state_helpers import ROW_FIELDS, bits, pairwise_rows as pairwise_rows_8_to_128
 
 DAY = 86400
 T_BASE = 19000 * DAY
 SHORT_LENGTHS = list(range(1, 301))
 LONG_LENGTHS = list(range(511, 530)) + list(range(1023, 1042)) + [2049, 4100]
 ALL_LENGTHS = SHORT_LENGTHS + LONG_LENGTHS
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
 COUNTERS = ("n_keys", "n_points", "n_anomalies", "keys_no_result")
 
 
@@ -150,11 +148,6 @@ class DropTable:
             assert job["n_points"] == pk.size and job["n_keys"] == n.size and job["keys_no_result"] == int(((n < ms) | (n < 2)).sum())
             self._want[nsigma, ms] = (job, allp)
         return self._want[nsigma, ms]
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 def rows_table(series, K, seed, **stage0):

@@ -14,16 +14,9 @@ import numpy as np
 
 from oracle import stream_oracle as sorc
 from oracle import tad_oracle as orc
+from state_helpers import HIST, I64, SER, STATE_FIELDS, TIMES, U64, drop_oracle_rows, expected_counts
 
-from test_gpu_state_drop import oracle_rows as drop_oracle_rows
-from test_gpu_state_merge import expected_counts
-
-U64 = np.uint64
-I64 = np.int64
-HIST, SER, TIMES = 1, 2, 8     # TAD_STATE_HISTORY, TAD_STATE_SERIES, TAD_STATE_TIMES
 KEY_SKIP = U64(orc.MASK64)
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
-STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
 SEEDS = tuple(range(32))
 N_OPS = 12
 CEILING = 40000                # points held at any time

@@ -6,8 +6,8 @@ import re
 import subprocess
 
 import pytest
+from job_helpers import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "tad.h")
 
 

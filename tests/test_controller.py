@@ -166,7 +166,7 @@ def test_job_walks_the_states_on_the_gpu_engine(engine, algo, agg):
     from oracle import job_oracle as jo
     from theia_amd import anomaly_detection as ad
     from theia_amd import clickhouse as ch
-    from test_clickhouse_http import FakeClickHouse, arrow_table
+    from fake_clickhouse import FakeClickHouse, arrow_table
     server = FakeClickHouse()
     c = None
     try:

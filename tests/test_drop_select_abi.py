@@ -11,11 +11,10 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import drop_query_ref as dq  # noqa: E402
+from job_helpers import HEADER, ROOT
 
-HEADER = open(os.path.join(ROOT, "include", "tad.h")).read()
 GO = open(os.path.join(ROOT, "go", "tadengine", "tadengine.go")).read()
 CODE = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
 

@@ -7,44 +7,21 @@ the shared deterministic source tad_detmath.h — so the L-BFGS-B trajectories c
 at BASELINE.json's 1e-6 relative tolerance ON EVERY POINT, with zero verdict flips; in fact the results are bit-identical
 and that is asserted too.  Against the reference itself (statsmodels 0.14.0, absent) parity is pinned by its golden verdict
 list and the five leading characters of its golden predictions (anomaly_detection_test.py:261-283, 320-345)."""
-TOL = 1e-6   # BASELINE.json north_star: "EWMA/ARIMA scores within 1e-6 relative"
 import numpy as np
 import pytest
 
 import arima_gap
 from oracle import arima_oracle as ao
 from oracle import tad_oracle as orc
+from job_helpers import assert_predictions, rel_err
 
 pytestmark = pytest.mark.gpu
-
-
-def rel_err(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return np.abs(a - b) / np.abs(b)
-
-
-def assert_same(got, want, what):
-    """every finite prediction within 1e-6 (in fact bit-identical); a fit whose optimiser walks into a non-finite
-    likelihood yields NaN on both sides at the same index (Python: abs(x - nan) > sigma is False -> no anomaly row).
-    That happens where the reference algorithm itself is numerically void: Box-Cox with a strongly negative lambda
-    compresses the data to a variance of ~1e-18 next to the 1e6 diffuse prior, and P - K F K' cancels to a negative F
-    (the scipy-driven restatement oracle/arima_oracle.py:calculate_arima shows the same NaNs at a similar rate)."""
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape, what
-    nan = np.isnan(want)
-    assert (np.isnan(got) == nan).all(), (what, "NaN predictions at different indices")
-    inf = np.isinf(want)                  # inv_boxcox overflow (huge lambda): same infinity on both sides
-    assert (got[inf] == want[inf]).all(), (what, "infinite predictions differ")
-    fin = ~(nan | inf)
-    rel = rel_err(got[fin], want[fin])
-    assert (rel <= TOL).all(), (what, float(rel.max()), int((rel > TOL).sum()))
-    assert (got[fin].view(np.uint64) == want[fin].view(np.uint64)).all(), (what, "within 1e-6 but not bit-identical", float(rel.max()))
 
 
 def test_series_arima_golden_series(engine, golden):
     x, sd = golden["throughput_list"], golden["stddev"]
     got = engine.series_arima(x)
-    assert_same(got, ao.calculate_arima_exact(x), "golden series")
+    assert_predictions(got, ao.calculate_arima_exact(x), "golden series")
     # the reference's asserted goldens
     verdict = engine.series_arima_anomaly(x, sd)
     assert verdict.tolist() == golden["expected_anomaly_list_arima"]
@@ -72,7 +49,7 @@ def test_series_arima_reference_series(engine, ref_outputs):
         e = ref_outputs["series"][name]
         x, sd = e["x"], e["stddev_numpy_ddof1"]
         want = ao.calculate_arima_exact(x)
-        assert_same(engine.series_arima(x), want, name)
+        assert_predictions(engine.series_arima(x), want, name)
         verdict = engine.series_arima_anomaly(x, sd)
         assert verdict.tolist() == [abs(float(a) - p) > sd for a, p in zip(x, want)]      # identical verdicts
     assert engine.series_arima(ref_outputs["series"]["ramp"]["x"]) is None                   # contains 0 -> boxcox raises
@@ -92,7 +69,7 @@ def test_series_arima_random_shapes(engine):
         if want is None:
             assert got is None, i
         else:
-            assert_same(got, want, "random series %d" % i)
+            assert_predictions(got, want, "random series %d" % i)
 
 
 def test_series_arima_every_length(engine):
@@ -107,7 +84,7 @@ def test_series_arima_every_length(engine):
         want = ao.calculate_arima_exact(x)
         got = engine.series_arima(x)
         assert want is not None and got is not None, n
-        assert_same(got, want, "length %d" % n)
+        assert_predictions(got, want, "length %d" % n)
 
 
 def check_job(engine, k, t, v, K, maxiter=0):
@@ -120,11 +97,11 @@ def check_job(engine, k, t, v, K, maxiter=0):
     assert allp.n_rows == int(keep.sum()) and (allp["key_id"] == pk[keep]).all() and (allp["flow_end_s"] == pt[keep]).all()
     assert (allp["throughput"] == orc.u64_to_f64(pv)[keep]).all()
     assert (allp["stddev"] == np.repeat(want["sigma"], np.diff(want["ptr"]))[keep]).all()
-    assert_same(allp["algo_calc"], want["calc_all"][keep], "job predictions")
+    assert_predictions(allp["algo_calc"], want["calc_all"][keep], "job predictions")
     assert (allp["anomaly"].astype(bool) == want["anomaly_all"][keep]).all()       # zero verdict flips
     res = engine.run("ARIMA", k, t, v, K, agg_flow="svc", maxiter=maxiter)
     assert res.n_rows == want["n_anomalies"] and (res["key_id"] == want["key_id"]).all() and (res["flow_end_s"] == want["flow_end_s"]).all()
-    assert_same(res["algo_calc"], want["algo_calc"], "job anomaly rows")
+    assert_predictions(res["algo_calc"], want["algo_calc"], "job anomaly rows")
     assert res.stats["keys_no_result"] == want["keys_no_result"]
     return want, res
 

@@ -14,7 +14,7 @@ around them, where an off-by-one changes results or reads a neighbour's memory:
                        k_as_list's union of position ranges, (hcnt[p] + chunk - 1) / chunk wavefronts per position with chunk = 64
 
 Every case compares the engine's rows with orc.run_job — key, time, throughput and stddev equal, algo_calc bit for bit with non-finite
-values at the same indices (assert_same of tests/test_gpu_arima.py: 1e-6 relative AND bit identity), every verdict, keys_no_result,
+values at the same indices (assert_predictions of tests/job_helpers.py: 1e-6 relative AND bit identity), every verdict, keys_no_result,
 arima_fits against the sum of max(n_k - 3, 0) over the keys with a result, kalman_steps against the oracle's counter — for emit_all and
 for the anomaly rows.  The streaming cases take the oracle over the concatenated batches, restricted to the batch's points, never the GPU
 batch job (which shares arima_fit_body with the code under test).  The tables come from tests/arima_tables.py; tests/test_arima_tables.py
@@ -38,7 +38,7 @@ import pytest
 
 import arima_tables as at
 from oracle import tad_oracle as orc
-from test_gpu_arima import assert_same
+from job_helpers import assert_predictions
 
 pytestmark = pytest.mark.gpu
 
@@ -58,11 +58,11 @@ def want_rows(w, emit_all, keep=None):
             "algo_calc": w["calc_all"][sel], "anomaly": w["anomaly_all"][sel]}
 
 
-def assert_rows(res, want, emit_all, what):
+def assert_arima_rows(res, want, emit_all, what):
     assert res.n_rows == want["key_id"].size, (what, res.n_rows, want["key_id"].size)
     for f in ROW_FIELDS:
         assert np.array_equal(np.asarray(res[f]), want[f]), (what, f)
-    assert_same(res["algo_calc"], want["algo_calc"], what)
+    assert_predictions(res["algo_calc"], want["algo_calc"], what)
     if emit_all:
         assert np.array_equal(np.asarray(res["anomaly"]).astype(bool), want["anomaly"]), (what, "verdicts")      # zero verdict flips
 
@@ -78,7 +78,7 @@ def check_table(engine, tab, dense=True):
         st = res.stats
         if dense:
             assert st["stage0_path"] < 4 and st["n_buckets"] == tab.T, (what, st["stage0_path"], st["n_buckets"])
-        assert_rows(res, want_rows(w, emit_all), emit_all, what)
+        assert_arima_rows(res, want_rows(w, emit_all), emit_all, what)
         assert st["n_keys"] == w["n_keys"] and st["n_points"] == w["n_points"], what
         assert st["keys_no_result"] == w["keys_no_result"] == tab.expected_no_result(), what
         assert st["arima_fits"] == tab.expected_fits(), (what, st["arima_fits"], tab.expected_fits())
@@ -175,7 +175,7 @@ def check_stream(engine, case):
             what = (case.name, "batch %d" % b, "emit_all" if emit_all else "anomalies")
             res = engine.run_stream(st, bk, bt, bv, agg_flow="svc", algo="ARIMA", emit_all=emit_all)
             w = stream_want(case, b)
-            assert_rows(res, want_rows(w, emit_all, batch_mask(w, (bk, bt))), emit_all, what)
+            assert_arima_rows(res, want_rows(w, emit_all, batch_mask(w, (bk, bt))), emit_all, what)
             s = res.stats
             assert s["keys_no_result"] == case.expected_no_result(b), (what, s["keys_no_result"], case.expected_no_result(b))
             assert s["arima_fits"] == case.expected_fits(b), (what, s["arima_fits"], case.expected_fits(b))
@@ -203,7 +203,7 @@ def check_run_state(engine, st, case, b, window=(0, 0)):
             res = engine.run_state(st, algo="ARIMA", emit_all=emit_all)
         else:
             res = engine.run_state_window(st, window[0], window[1], algo="ARIMA", emit_all=emit_all)
-        assert_rows(res, want_rows(w, emit_all), emit_all, what)
+        assert_arima_rows(res, want_rows(w, emit_all), emit_all, what)
         s = res.stats
         n = np.diff(w["ptr"])
         has = np.array([r is not None for r in w["arima_results"]], bool)

@@ -38,8 +38,7 @@ import numpy as np
 import pytest
 
 from oracle import tad_oracle as orc
-
-from test_gpu_parity import check_job
+from job_helpers import check_job, lattice
 
 pytestmark = pytest.mark.gpu
 
@@ -196,14 +195,6 @@ def sort_tile_rows(pl, has2, generic):
     else:
         rpt = 4 if rpt >= 4 else 2
     return rpt * THREADS
-
-
-def lattice(t_live):
-    """(t0, step, n_buckets) as the engine derives them from the live rows: the gcd lattice through the first and the last time"""
-    t_live = np.asarray(t_live, dtype=np.int64)
-    t0 = int(t_live.min())
-    step = int(np.gcd.reduce(t_live - t0)) or 1
-    return t0, step, (int(t_live.max()) - t0) // step + 1
 
 
 def expected_path(pl, slots, has2, partition_pass):

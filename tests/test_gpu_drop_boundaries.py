@@ -11,7 +11,7 @@ from oracle import tad_oracle as orc
 
 import drop_tables as dt
 from drop_tables import DAY, T_BASE, DropTable, bits
-from test_gpu_sparse import class_boundary_table, day_table
+from job_helpers import class_boundary_table, day_table
 
 pytestmark = pytest.mark.gpu
 
@@ -25,7 +25,7 @@ CLASSES_PARTITION = dict(stage0="v2", sparse="always", sparse_sort="partition", 
 SPARSE_FORMS = {"lsd": (LSD, 4), "partition": (PARTITION, 8), "classes": (CLASSES, 6), "classes_partition": (CLASSES_PARTITION, 9)}
 
 
-def assert_rows(res, want, what):
+def assert_drop_rows(res, want, what):
     assert res.n_rows == want["key_id"].size, (what, res.n_rows, want["key_id"].size)
     for f, w in want.items():
         assert np.array_equal(bits(np.asarray(res[f])), bits(w)), (what, f)
@@ -43,8 +43,8 @@ def check(engine, tab, nsigma=0.0, ms=0, paths=None, what=""):
             assert r.stats[f] == job[f], (what, name, f, r.stats[f], job[f])
         if paths is not None:
             assert r.stats["stage0_path"] in paths, (what, name, r.stats["stage0_path"])
-    assert_rows(res, {f: job[f] for f in dt.ROW_FIELDS}, (what, "rows"))
-    assert_rows(allp, every, (what, "emit_all"))
+    assert_drop_rows(res, {f: job[f] for f in dt.ROW_FIELDS}, (what, "rows"))
+    assert_drop_rows(allp, every, (what, "emit_all"))
     return res, allp, job
 
 

@@ -14,31 +14,14 @@ import drop_query_ref as dq  # noqa: E402
 from oracle import drop_oracle as dro  # noqa: E402
 from theia_amd import TadError, _capi  # noqa: E402
 from theia_amd.engine import DeviceArray  # noqa: E402
+from stream_helpers import DAY0, N_DAYS, N_ENDPOINTS, PLANTED, SHORT, counts_of, flow_table, flows, keyed  # noqa: F401  (flows: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 LANE_ROWS = 16        # kDselLaneRows
 TILE_ROWS = 4096      # kDselTileRows
 WAVE_ROWS = 64 * LANE_ROWS
-T0 = 1660176000       # a midnight
 CODES = ("src_ip", "src_pod_ns", "src_pod_name", "dst_ip", "dst_pod_ns", "dst_pod_name")
-DROP_PAIRS = np.array([(2, 0), (3, 1), (0, 2), (4, 3), (2, 3), (3, 2), (255, 2), (2, 255), (3, 3)], dtype=np.uint8)
-PASS_PAIRS = np.array([(a, b) for a in (0, 1, 4, 255) for b in (0, 1, 4, 255)], dtype=np.uint8)
-
-
-def table(n, selected, seed=0):
-    """n flow rows whose ACTIONS select exactly the rows of `selected`; pod-name code 0 means "no pod" on about a third of the sides"""
-    rng = np.random.default_rng(1000 + seed)
-    selected = np.asarray(selected, dtype=bool)
-    pairs = np.where(selected[:, None], DROP_PAIRS[rng.integers(0, len(DROP_PAIRS), n)], PASS_PAIRS[rng.integers(0, len(PASS_PAIRS), n)])
-    c = {"ingress_action": np.ascontiguousarray(pairs[:, 0]), "egress_action": np.ascontiguousarray(pairs[:, 1])}
-    for side in ("src", "dst"):
-        c[side + "_ip"] = rng.integers(0, 50, n)
-        c[side + "_pod_ns"] = rng.integers(0, 5, n)
-        c[side + "_pod_name"] = np.where(rng.random(n) < 0.33, 0, rng.integers(1, 20, n))
-    c["flow_start_s"] = T0 + rng.integers(0, 20 * dq.DAY, n)
-    c["flow_end_s"] = c["flow_start_s"] + rng.integers(0, 3600, n)
-    return c
 
 
 def dev(engine, a, offset=0):
@@ -123,7 +106,7 @@ def test_every_size_and_selection_pattern(engine, n, name):
         assert s[0] and s.sum() == 1
     if name == "last" and n:
         assert s[n - 1] and s.sum() == 1
-    c = table(n, s, seed=n)
+    c = flow_table(n, s, seed=n)
     want = check(engine, c)
     assert np.array_equal(want["row"], np.flatnonzero(s).astype(np.uint64))
 
@@ -132,7 +115,7 @@ def test_every_size_and_selection_pattern(engine, n, name):
 @pytest.mark.parametrize("offs", [(1, 3, 8), (3, 8, 15), (8, 15, 1), (15, 1, 3), (1, 1, 1), (0, 15, 0)])
 def test_action_and_keep_columns_that_are_device_slices(engine, offs):
     n = 2 * TILE_ROWS + 37
-    c = table(n, pattern("r2", n), seed=7)
+    c = flow_table(n, pattern("r2", n), seed=7)
     keep = np.random.default_rng(5).random(n) < 0.7
     offsets = {"ingress_action": offs[0], "egress_action": offs[1], "keep": offs[2]}
     check(engine, c, offsets=offsets, keep=keep)
@@ -141,16 +124,16 @@ def test_action_and_keep_columns_that_are_device_slices(engine, offs):
 
 def test_eight_byte_columns_that_are_only_eight_byte_aligned(engine):
     n = TILE_ROWS + 19
-    c = table(n, pattern("r2", n), seed=8)
-    check(engine, c, offsets={k: 8 for k in CODES + ("flow_start_s", "flow_end_s")}, start_time=T0 + 3 * dq.DAY, end_time=T0 + 15 * dq.DAY)
+    c = flow_table(n, pattern("r2", n), seed=8)
+    check(engine, c, offsets={k: 8 for k in CODES + ("flow_start_s", "flow_end_s")}, start_time=DAY0 + 3 * dq.DAY, end_time=DAY0 + 15 * dq.DAY)
 
 
 def test_u32_time_columns_that_are_only_four_byte_aligned(engine):
     n = TILE_ROWS + 19
-    c = table(n, pattern("r2", n), seed=9)
+    c = flow_table(n, pattern("r2", n), seed=9)
     c["flow_start_s"], c["flow_end_s"] = c["flow_start_s"].astype(np.uint32), c["flow_end_s"].astype(np.uint32)
     for off in (4, 12):
-        check(engine, c, offsets={"flow_start_s": off, "flow_end_s": off}, start_time=T0 + 3 * dq.DAY, end_time=T0 + 15 * dq.DAY)
+        check(engine, c, offsets={"flow_start_s": off, "flow_end_s": off}, start_time=DAY0 + 3 * dq.DAY, end_time=DAY0 + 15 * dq.DAY)
 
 
 # ---- the row rule ----
@@ -158,7 +141,7 @@ def test_every_pair_of_actions(engine):
     acts = (0, 1, 2, 3, 4, 255)
     pairs = np.array([(a, b) for a in acts for b in acts] * 5, dtype=np.uint8)
     n = len(pairs)
-    c = table(n, np.zeros(n, bool), seed=11)
+    c = flow_table(n, np.zeros(n, bool), seed=11)
     c["ingress_action"], c["egress_action"] = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
     want = check(engine, c)
     ia, ea = pairs[:, 0].astype(int), pairs[:, 1].astype(int)
@@ -171,7 +154,7 @@ def test_every_pair_of_actions(engine):
 @pytest.mark.parametrize("null", [(0, 0), (-1, -1), (0, 7), (7, -1)], ids=["present", "none", "differ", "one-side"])
 def test_pod_null_codes(engine, null):
     n = 3000
-    c = table(n, pattern("r2", n), seed=12)
+    c = flow_table(n, pattern("r2", n), seed=12)
     want = check(engine, c, null=null)
     row, ing = want["row"].astype(int), want["direction"] == 0
     pod = np.where(ing, c["dst_pod_name"][row], c["src_pod_name"][row])
@@ -183,7 +166,7 @@ def test_pod_null_codes(engine, null):
 
 
 def test_an_endpoint_seen_as_pod_in_one_row_and_as_ip_in_another(engine):
-    c = table(4, np.ones(4, bool), seed=13)
+    c = flow_table(4, np.ones(4, bool), seed=13)
     c["ingress_action"][:], c["egress_action"][:] = 2, 0
     c["dst_ip"][:], c["dst_pod_ns"][:] = 9, 3
     c["dst_pod_name"][:] = [9, 0, 9, 0]            # the pod's name code equals the IP's code: only the kind column tells them apart
@@ -193,10 +176,10 @@ def test_an_endpoint_seen_as_pod_in_one_row_and_as_ip_in_another(engine):
 
 # ---- times ----
 def test_start_is_inclusive_and_end_exclusive_at_the_exact_second(engine):
-    S, E = T0 + 5000, T0 + 90000
+    S, E = DAY0 + 5000, DAY0 + 90000
     ts = np.array([S - 1, S, S + 1, S + 10, S + 10, S + 10, S - 1, S], dtype=np.int64)
     te = np.array([E - 5, E - 5, E - 5, E - 1, E, E + 1, E, E - 1], dtype=np.int64)
-    c = table(ts.size, np.ones(ts.size, bool), seed=14)
+    c = flow_table(ts.size, np.ones(ts.size, bool), seed=14)
     c["flow_start_s"], c["flow_end_s"] = ts, te
     want = check(engine, c, start_time=S, end_time=E)
     assert want["row"].tolist() == [1, 2, 3, 7]
@@ -209,10 +192,10 @@ def test_start_is_inclusive_and_end_exclusive_at_the_exact_second(engine):
 @pytest.mark.parametrize("which", ["start", "end", "keep"])
 def test_a_filter_removes_a_row_the_action_mask_kept_at_each_tile_edge(engine, which):
     n = 3 * TILE_ROWS + 5
-    c = table(n, np.ones(n, bool), seed=15)
+    c = flow_table(n, np.ones(n, bool), seed=15)
     edge = pattern("tile_edges", n)
     assert edge.sum() == 6 and all(edge[t * TILE_ROWS - 1] and edge[t * TILE_ROWS] for t in (1, 2, 3))
-    S, E = T0 + 2 * dq.DAY, T0 + 30 * dq.DAY
+    S, E = DAY0 + 2 * dq.DAY, DAY0 + 30 * dq.DAY
     c["flow_start_s"] = np.where(edge, S - 1, S + np.arange(n)) if which == "start" else S + np.arange(n)
     c["flow_end_s"] = np.where(edge, E, E - 1) if which == "end" else np.full(n, E - 1)
     kw = {"keep": ~edge} if which == "keep" else {"start_time": S, "end_time": E}
@@ -221,16 +204,16 @@ def test_a_filter_removes_a_row_the_action_mask_kept_at_each_tile_edge(engine, w
 
 
 def test_the_day_is_the_floor_of_the_start(engine):
-    ts = np.array([86399, 86400, 86401, -1, -86400, -86401, 0, T0 - 1, T0], dtype=np.int64)
-    c = table(ts.size, np.ones(ts.size, bool), seed=16)
+    ts = np.array([86399, 86400, 86401, -1, -86400, -86401, 0, DAY0 - 1, DAY0], dtype=np.int64)
+    c = flow_table(ts.size, np.ones(ts.size, bool), seed=16)
     c["flow_start_s"], c["flow_end_s"] = ts, ts + 5
     want = check(engine, c)
-    assert want["day_s"].tolist() == [0, 86400, 86400, -86400, -86400, -2 * 86400, 0, T0 - 86400, T0]
+    assert want["day_s"].tolist() == [0, 86400, 86400, -86400, -86400, -2 * 86400, 0, DAY0 - 86400, DAY0]
 
 
 def test_u32_times_are_zero_extended(engine):
     ts = np.array([2 ** 31, 4000000000, 2 ** 31 - 1, 2 ** 32 - 1], dtype=np.uint32)
-    c = table(ts.size, np.ones(ts.size, bool), seed=17)
+    c = flow_table(ts.size, np.ones(ts.size, bool), seed=17)
     c["flow_start_s"], c["flow_end_s"] = ts, ts
     want = check(engine, c, start_time=2 ** 31 - 1, end_time=2 ** 32)
     assert want["day_s"].tolist() == [int(t) // 86400 * 86400 for t in ts.tolist()] and want["day_s"].min() > 0
@@ -240,7 +223,7 @@ def test_u32_times_are_zero_extended(engine):
 # ---- the call ----
 def test_keep_combines_with_the_actions(engine):
     n = TILE_ROWS + 100
-    c = table(n, pattern("r2", n), seed=18)
+    c = flow_table(n, pattern("r2", n), seed=18)
     keep = (np.arange(n) % 3 != 0).astype(np.uint8) * np.uint8(255)           # any non-zero byte keeps
     want = check(engine, c, keep=keep)
     assert 0 < want["row"].size < pattern("r2", n).sum() and np.all(want["row"] % 3 != 0)
@@ -249,9 +232,9 @@ def test_keep_combines_with_the_actions(engine):
 
 def test_host_and_device_inputs_and_outputs_agree_and_a_call_repeats(engine):
     n = 2 * TILE_ROWS + 11
-    c = table(n, pattern("r64", n), seed=19)
+    c = flow_table(n, pattern("r64", n), seed=19)
     keep = np.random.default_rng(3).random(n) < 0.9
-    kw = dict(keep=keep, start_time=T0 + dq.DAY, end_time=T0 + 19 * dq.DAY)
+    kw = dict(keep=keep, start_time=DAY0 + dq.DAY, end_time=DAY0 + 19 * dq.DAY)
     want = reference(c, **kw)
     assert want["row"].size > 20
     for device in (True, False):
@@ -272,7 +255,7 @@ def test_host_and_device_inputs_and_outputs_agree_and_a_call_repeats(engine):
 
 def test_every_refusal_leaves_no_result_and_a_message(engine):
     lib, n = engine._lib, 64
-    c = table(n, np.ones(n, bool), seed=20)
+    c = flow_table(n, np.ones(n, bool), seed=20)
     keepalive = {k: np.ascontiguousarray(v) for k, v in c.items()}
     full = {k: v.ctypes.data for k, v in keepalive.items()}
 
@@ -290,7 +273,7 @@ def test_every_refusal_leaves_no_result_and_a_message(engine):
     for name in ("ingress_action", "egress_action", "flow_start_s") + CODES:
         rc, res, msg = call(**{name: None})
         assert rc == _capi.TAD_ERR_INVALID_ARGUMENT and not res and "tad_drop_select" in msg, name
-    rc, res, msg = call(end=T0, flow_end_s=None)
+    rc, res, msg = call(end=DAY0, flow_end_s=None)
     assert rc == _capi.TAD_ERR_INVALID_ARGUMENT and not res and "flow_end_s" in msg
     rc, res, _ = call(flow_end_s=None)         # without an end bound the column is optional
     assert rc == _capi.TAD_OK and res.contents.n_rows == n
@@ -311,61 +294,7 @@ def test_every_refusal_leaves_no_result_and_a_message(engine):
 
 
 # ---- end to end: flow rows -> result rows ----
-N_ENDPOINTS, N_DAYS, PLANTED, SHORT = 40, 20, (3, 11, 18, 26, 37), (5, 20, 33)
 # Why 20 days: with one outlier among n otherwise equal points, |x - mean| / std = (n - 1) / sqrt(n), which exceeds 3 only from n = 11 on
-
-
-@pytest.fixture(scope="module")
-def flows():
-    rng = np.random.default_rng(20260)
-    dictionaries = {"ip": ["10.1.%d.%d" % (i // 8, i % 8) for i in range(N_ENDPOINTS + 10)], "pod_ns": ["ns-a", "ns-b", "ns-c", "ns-d", "ns-e"],
-                    "pod_name": [""] + ["pod-%d" % i for i in range(N_ENDPOINTS)]}
-    ep, day = [], []
-    planted = {}
-    for e in range(N_ENDPOINTS):
-        days = [4, 13] if e in SHORT else list(range(N_DAYS))
-        counts = rng.integers(5, 10, len(days))
-        if e in PLANTED:
-            j = int(rng.integers(0, N_DAYS))
-            counts[j] = 60
-            planted[e] = j
-        for d, k in zip(days, counts):
-            ep += [e] * int(k)
-            day += [d] * int(k)
-    ep, day = np.array(ep), np.array(day)
-    m = ep.size
-    n = 31 * m                                   # unselected rows mixed in at 30 : 1
-    at = np.sort(rng.choice(n, m, replace=False))
-    order = rng.permutation(m)
-    ep, day = ep[order], day[order]
-    c = table(n, np.zeros(n, bool), seed=99)
-    pod, ingress = ep % 2 == 0, (ep // 2) % 2 == 0
-    also = rng.random(m) < 0.2                   # some rows drop on both sides: ingress wins
-    c["ingress_action"][at] = np.where(ingress, rng.choice([2, 3], m), rng.choice([0, 1, 4], m)).astype(np.uint8)
-    c["egress_action"][at] = np.where(ingress, np.where(also, 3, 0), rng.choice([2, 3], m)).astype(np.uint8)
-    for side, mine in (("dst", ingress), ("src", ~ingress)):
-        c[side + "_ip"][at] = np.where(mine, ep, c[side + "_ip"][at])
-        c[side + "_pod_ns"][at] = np.where(mine, ep % 3, c[side + "_pod_ns"][at])
-        c[side + "_pod_name"][at] = np.where(mine, np.where(pod, 1 + ep, 0), c[side + "_pod_name"][at])
-    c["flow_start_s"] = T0 + rng.integers(0, N_DAYS, n) * dq.DAY + rng.integers(0, dq.DAY, n)
-    c["flow_start_s"][at] = T0 + day * dq.DAY + rng.integers(0, dq.DAY, m)
-    c["flow_end_s"] = c["flow_start_s"] + 60
-    name = lambda e: ("ns-%s/pod-%d" % ("abc"[e % 3], e) if e % 2 == 0 else dictionaries["ip"][e], "ingress" if (e // 2) % 2 == 0 else "egress")
-    return {"cols": c, "dict": dictionaries, "planted": {name(e): str(np.datetime64(T0 + j * dq.DAY, "s").astype("datetime64[D]")) for e, j in planted.items()},
-            "short": [name(e) for e in SHORT], "m": m}
-
-
-def counts_of(flows, lo=0, hi=N_DAYS):
-    """the pandas query over the rows whose start lies in days [lo, hi)"""
-    c = flows["cols"]
-    rows = (c["flow_start_s"] >= T0 + lo * dq.DAY) & (c["flow_start_s"] < T0 + hi * dq.DAY)
-    part = {k: v[rows] for k, v in c.items()}
-    return part, dq.query_pandas(dq.strings_of(part, flows["dict"]), part["ingress_action"], part["egress_action"], part["flow_start_s"], part["flow_end_s"])
-
-
-def keyed(rows):
-    """result tuples -> comparable rows: endpoint, direction, mean and std as bit patterns, date, number"""
-    return sorted((r[3], r[4], float(r[5]).hex(), float(r[6]).hex(), str(r[7]), int(r[8])) for r in rows)
 
 
 def test_flow_rows_to_result_rows(engine, flows):

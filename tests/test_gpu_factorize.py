@@ -7,43 +7,11 @@ import pytest
 
 from oracle import job_oracle as jo
 from oracle import tad_oracle as orc
-from theia_amd import _capi as capi
 from theia_amd import anomaly_detection as ad
 from theia_amd.engine import DeviceArray
-from test_host_job import CASES
+from job_helpers import CASES, SKIP, pandas_ids
 
 pytestmark = pytest.mark.gpu
-SKIP = np.uint64(capi.TAD_KEY_SKIP)
-
-
-def pandas_ids(cols, keep, cols_b=None, keep_b=None):
-    """ids in order of first appearance over [kept rows of side a ++ kept rows of side b] (+ the first virtual rows)"""
-    import pandas as pd
-    n = len(cols[0])
-    sides = [(cols, np.ones(n, bool) if keep is None else np.asarray(keep, bool), 0)]
-    if cols_b is not None:
-        sides.append((cols_b, np.ones(n, bool) if keep_b is None else np.asarray(keep_b, bool), 1))
-    parts, vrows = [], []
-    for cs, kp, side in sides:
-        sel = np.flatnonzero(kp)
-        parts.append([np.asarray(c)[sel] for c in cs] + [np.full(sel.size, side)])
-        vrows.append(sel + side * n)
-    cat = [np.concatenate([p[i] for p in parts]) for i in range(len(cols) + 1)]
-    vrow = np.concatenate(vrows)
-    if vrow.size == 0:
-        return [np.full(n, SKIP) for _ in sides], np.zeros(0, np.uint64)
-    codes, _ = pd.MultiIndex.from_arrays(cat).factorize()
-    out, at = [], 0
-    for cs, kp, side in sides:
-        k = np.full(n, SKIP, dtype=np.uint64)
-        m = int(kp.sum())
-        k[np.flatnonzero(kp)] = codes[at:at + m].astype(np.uint64)
-        at += m
-        out.append(k)
-    first = np.full(codes.max() + 1, -1, dtype=np.int64)
-    for i in range(codes.size - 1, -1, -1):
-        first[codes[i]] = vrow[i]
-    return out, first.astype(np.uint64)
 
 
 @pytest.mark.parametrize("dict_encoded", [False, True], ids=["strings", "dictionaries"])

@@ -19,7 +19,7 @@ from theia_amd import TadError
 from theia_amd import anomaly_detection as ad
 from theia_amd import clickhouse as ch
 from theia_amd.engine import DeviceArray, HostBuffer
-from test_host_job import CASES, canon
+from job_helpers import CASES, canon
 
 pytestmark = pytest.mark.gpu
 KW = dict(start_time="", end_time="", ns_ignore_list=(), agg_flow="", pod_label="", external_ip="", svc_port_name="", pod_name="", pod_namespace="")

@@ -12,6 +12,7 @@ import pytest
 from theia_amd import TadEngine, TadError
 from theia_amd import _capi as capi
 from theia_amd.engine import DeviceArray
+from job_helpers import column, host
 
 pytestmark = pytest.mark.gpu
 
@@ -55,13 +56,6 @@ def refused(engine, code, call, *args, **kw):
     return last_error(engine)
 
 
-def column(strings):
-    """a list of bytes -> (offsets int32, data) in Arrow's layout"""
-    off = np.zeros(len(strings) + 1, dtype=np.int32)
-    np.cumsum([len(s) for s in strings], out=off[1:])
-    return off, np.frombuffer(b"".join(strings) + b"\0" * 16, dtype=np.uint8)[:off[-1]].copy()
-
-
 def device_column(engine, col):
     off, data = col
     room = DeviceArray.from_host(engine, np.concatenate([data, np.zeros(16, np.uint8)]))      # (the last aligned word a kernel loads)
@@ -70,10 +64,6 @@ def device_column(engine, col):
 
 def dev(engine, cols):
     return [DeviceArray.from_host(engine, np.ascontiguousarray(c)) for c in cols]
-
-
-def host(x):
-    return x.to_host() if isinstance(x, DeviceArray) else np.asarray(x)
 
 
 # ---- 1. the workspace-limit refusals: the text carries the scratch bytes of the staging layout ----

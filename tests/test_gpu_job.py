@@ -11,8 +11,7 @@ from oracle import arima_oracle as ao
 from oracle import job_oracle as jo
 from oracle import tad_oracle as orc
 from theia_amd import anomaly_detection as ad
-
-from test_host_job import CASES, canon
+from job_helpers import CASES, canon, e2e_flows
 
 pytestmark = pytest.mark.gpu
 
@@ -103,22 +102,6 @@ E2E_RESULT_MAP = {   # first five characters of the throughput of every emitted 
     "EWMA": {"4.004", "4.005", "4.006", "5.000", "2.002", "2.003", "2.500"},
     "DBSCAN": {"1.000", "1.005", "5.000", "3.260", "2.058", "5.002", "5.027", "2.500", "1.029", "1.630"},
 }
-
-
-def e2e_flows(golden):
-    """addFakeRecordforTAD (throughputanomalydetection_test.go:398-470): 90 rows of ONE connection, one per minute."""
-    x = np.array(golden["throughput_list"], dtype=np.uint64)
-    n = x.size
-    const = lambda v: np.full(n, v)
-    return {
-        "flowStartSeconds": const(1660199214).astype(np.int64), "flowEndSeconds": (1660202814 + 60 * np.arange(n)).astype(np.int64),
-        "sourceIP": const("10.10.1.25"), "destinationIP": const("10.10.1.33"), "sourceTransportPort": const(58076),
-        "destinationTransportPort": const(5201), "protocolIdentifier": const(6),
-        "sourcePodNamespace": const("test_namespace"), "sourcePodName": const("test_podName"),
-        "destinationPodName": const("test_podName"), "destinationPodNamespace": const("test_namespace"),
-        "sourcePodLabels": const("{test_key:test_value}"), "destinationPodLabels": const("{test_key:test_value}"),
-        "destinationServicePortName": const("test_serviceportname"), "flowType": const(3), "throughput": x,
-    }
 
 
 @pytest.mark.parametrize("algo", ["EWMA", "DBSCAN", "ARIMA"])

@@ -12,15 +12,12 @@ import pytest
 from oracle import tad_oracle as orc
 from theia_amd import TadEngine, TadError, _capi as capi
 from theia_amd.engine import DeviceArray
+from job_helpers import ROOT, host
+from state_helpers import HIST, SER, STATE_FIELDS, TIMES, U64, assert_rows, assert_same, bits, new_state, rows_of, snapshot
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SKIP = np.uint64(capi.TAD_KEY_SKIP)
-U64 = np.uint64
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
-STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
-HIST, SER, TIMES = 1, 2, 8
 CUT = 1_700_000_000          # the time rule of every case: a key whose newest point is older is idle
 
 
@@ -31,32 +28,6 @@ def scan_tile():
     items = int(re.search(r"static constexpr int kScanItems = (\d+);", src).group(1))
     assert re.search(r"kScanTile = kBlock \* kScanItems;", src)
     return block * items
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
-
-
-def new_state(engine, K, flags):
-    return engine.state_create(K, history=bool(flags & HIST), series=bool(flags & SER), times=bool(flags & TIMES))
-
-
-def snapshot(st):
-    return {"state": st.export(), "history": st.export_history() if st.history else None,
-            "series": st.export_series() if st.series else None, "times": st.export_times() if st.times else None}
-
-
-def assert_same(a, b, what=""):
-    for f in STATE_FIELDS:
-        assert np.array_equal(bits(a["state"][f]), bits(b["state"][f])), (what, f)
-    for part in ("history", "series"):
-        assert (a[part] is None) == (b[part] is None), (what, part)
-        if a[part] is not None:
-            assert np.array_equal(a[part][0], b[part][0]) and np.array_equal(a[part][1], b[part][1]), (what, part)
-    assert (a["times"] is None) == (b["times"] is None), what
-    if a["times"] is not None:
-        assert np.array_equal(a["times"], b["times"]), (what, "times")
 
 
 def build_state(engine, flags, n, last_t, seed):
@@ -92,7 +63,8 @@ def select(snap, live):
             ln, vals = snap[part]
             out[part] = (ln[live] if m else np.zeros(1, U64), vals[np.repeat(live, ln.astype(np.int64))])
     if snap["times"] is not None:
-        out["times"] = snap["times"][np.repeat(live, snap["series"][0].astype(np.int64))]
+        times = snap["times"][np.repeat(live, snap["series"][0].astype(np.int64))]
+        out["times"] = times if times.size else None      # (a state without points exports no times)
     return out
 
 
@@ -246,11 +218,6 @@ def test_segments_around_the_chunk_size_move_whole(engine, flags):
 
 
 # ---- 3. life goes on: the compacted state and an uncompacted twin take the same further batches ----
-def rows_of(res):
-    d = {f: np.asarray(res[f]) for f in ROW_FIELDS}
-    if "anomaly" in res.to_host():
-        d["anomaly"] = np.asarray(res["anomaly"])
-    return d
 
 
 def mapped(rows, remap_ext):
@@ -260,13 +227,6 @@ def mapped(rows, remap_ext):
     out = {f: a[keep] for f, a in rows.items()}
     out["key_id"] = new[keep].astype(rows["key_id"].dtype)
     return out, int((~keep).sum())
-
-
-def assert_rows(got, want, what):
-    assert set(got) == set(want), what
-    assert got["key_id"].size == want["key_id"].size, (what, got["key_id"].size, want["key_id"].size)
-    for f in want:
-        assert np.array_equal(bits(got[f]), bits(want[f])), (what, f)
 
 
 @pytest.mark.parametrize("flags", [11, 3])
@@ -325,8 +285,6 @@ def test_later_calls_equal_the_uncompacted_twin_through_remap(engine, flags):
 
 
 # ---- 4. the dictionary ----
-def host(x):
-    return x.to_host() if isinstance(x, DeviceArray) else np.asarray(x)
 
 
 def tuples(rng, n, salt):

@@ -11,12 +11,10 @@ import pytest
 from oracle import tad_oracle as orc
 from theia_amd import TadEngine, TadError, _capi as capi
 from theia_amd.engine import DeviceArray
-from test_gpu_factorize import pandas_ids
+from job_helpers import SKIP, assert_keydict_unchanged, host, keydict_snapshot, pandas_ids
+from state_helpers import ROW_FIELDS, U64, bits
 
 pytestmark = pytest.mark.gpu
-SKIP = np.uint64(capi.TAD_KEY_SKIP)
-U64 = np.uint64
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
 
 
 class DictOracle:
@@ -55,10 +53,6 @@ class DictOracle:
         return [np.array([t[c + 1] for t in ts], dtype=np.int64) for c in range(ncols)], np.array([t[0] for t in ts], dtype=np.uint8)
 
 
-def host(x):
-    return None if x is None else (x.to_host() if isinstance(x, DeviceArray) else np.asarray(x))
-
-
 def dev(engine, cols):
     return None if cols is None else [DeviceArray.from_host(engine, np.ascontiguousarray(c)) for c in cols]
 
@@ -70,17 +64,6 @@ def assert_batch(got, want, what=""):
     assert np.array_equal(host(k1), w1), what
     assert (k2 is None) == (w2 is None) and (w2 is None or np.array_equal(host(k2), w2)), what
     assert np.array_equal(host(fr), wfr), what
-
-
-def snapshot(d):
-    cols, side = d.export()
-    return d.num_keys(), [c.copy() for c in cols], side.copy()
-
-
-def assert_unchanged(d, snap, what=""):
-    n, cols, side = snapshot(d)
-    assert n == snap[0], what
-    assert all(np.array_equal(a, b) for a, b in zip(cols, snap[1])) and np.array_equal(side, snap[2]), what
 
 
 def random_columns(rng, ncols, n, card):
@@ -252,7 +235,7 @@ def test_lookup_is_read_only(engine):
     d, oracle = engine.key_dict(3, 1), DictOracle()
     cols = random_columns(rng, 3, 20_000, 900)
     assert_batch(d.encode(cols), oracle.run(cols))
-    snap = snapshot(d)
+    snap = keydict_snapshot(d)
     size = d.nbytes()
     probe = random_columns(rng, 3, 30_000, 2500)                                # about a third of these tuples are known
     keep = rng.random(30_000) < 0.7
@@ -263,7 +246,7 @@ def test_lookup_is_read_only(engine):
     assert np.array_equal(k1, want[0]) and np.array_equal(k2, want[1])
     k1, k2 = d.lookup(dev(engine, probe), keep)
     assert np.array_equal(k1.to_host(), want[0]) and k2 is None
-    assert_unchanged(d, snap)
+    assert_keydict_unchanged(d, snap)
     assert d.nbytes() == size
     d.close()
 
@@ -291,7 +274,7 @@ def test_export_in_slices_and_import_continues_with_the_same_ids(engine):
         want = oracle.run(ca, None, cb, None)
         assert_batch(d.encode(ca, None, cb, None), want)
         assert_batch(fresh.encode(dev(engine, ca), None, dev(engine, cb), None), want)
-    a, b = snapshot(d), snapshot(fresh)
+    a, b = keydict_snapshot(d), keydict_snapshot(fresh)
     assert a[0] == b[0] and np.array_equal(a[2], b[2]) and all(np.array_equal(x, y) for x, y in zip(a[1], b[1]))
     d.close(), fresh.close()
 
@@ -308,11 +291,11 @@ def test_import_refusals_leave_the_dictionary_unchanged(engine):
     side = (np.arange(5000) % 2).astype(np.uint8)
     d.load(dup, np.where(np.arange(5000) == 4321, 1, 0).astype(np.uint8))        # the same columns on the other side: another tuple
     assert d.num_keys() == 5000
-    snap = snapshot(d)
+    snap = keydict_snapshot(d)
     with pytest.raises(TadError) as ei:                                          # a dictionary that holds keys
         d.load(cols, side)
     assert ei.value.code == capi.TAD_ERR_INVALID_ARGUMENT
-    assert_unchanged(d, snap)
+    assert_keydict_unchanged(d, snap)
     k1, _, fr, before = d.encode([dup[0][:20], dup[1][:20]])                     # the imported keys are found
     assert before == 5000 and k1.tolist() == list(range(20)) and fr.size == 0
     d.close()
@@ -332,7 +315,7 @@ def test_bad_arguments_leave_the_dictionary_unchanged(engine):
     d = engine.key_dict(3, 1)
     c = [np.arange(100, dtype=np.int64) + 1000 * i for i in range(3)]
     d.encode(c)
-    snap = snapshot(d)
+    snap = keydict_snapshot(d)
     new = [x + 500 for x in c]
     assert raw_encode(engine, d, 2, new[:2], None, 100) == capi.TAD_ERR_INVALID_ARGUMENT        # n_cols is not the dictionary's
     assert raw_encode(engine, d, 4, new + [new[0]], None, 100) == capi.TAD_ERR_INVALID_ARGUMENT
@@ -344,7 +327,7 @@ def test_bad_arguments_leave_the_dictionary_unchanged(engine):
         assert ei.value.code == capi.TAD_ERR_INVALID_ARGUMENT
         with pytest.raises(TadError):
             d.lookup(*args)
-    assert_unchanged(d, snap)
+    assert_keydict_unchanged(d, snap)
     assert raw_encode(engine, d, 3, new, None, 100) == capi.TAD_OK and d.num_keys() == 200      # the same batch, passed properly
     d.close()
 
@@ -361,7 +344,7 @@ def test_workspace_limit_refuses_a_big_batch_and_leaves_the_dictionary_unchanged
         first = [np.arange(1000, dtype=np.int64), np.arange(1000, dtype=np.int64) * -7]
         k1, _, fr, before = d.encode(dev(small, first))
         assert before == 0 and np.array_equal(k1.to_host(), np.arange(1000, dtype=U64)) and d.num_keys() == 1000
-        snap = snapshot(d)
+        snap = keydict_snapshot(d)
         big = [np.arange(100_000, dtype=np.int64) + 5000, np.arange(100_000, dtype=np.int64)]
         with pytest.raises(TadError) as ei:
             d.encode(dev(small, big))
@@ -369,20 +352,17 @@ def test_workspace_limit_refuses_a_big_batch_and_leaves_the_dictionary_unchanged
         with pytest.raises(TadError) as ei:
             small.factorize(dev(small, big))                                     # the existing call refuses the same batch the same way
         assert ei.value.code == capi.TAD_ERR_GRID_TOO_LARGE
-        assert_unchanged(d, snap)
+        assert_keydict_unchanged(d, snap)
         known = [np.arange(100_000, dtype=np.int64) % 1000, (np.arange(100_000, dtype=np.int64) % 1000) * -7]
         k1, _, fr, before = d.encode(dev(small, known))
         assert before == 1000 and fr.n == 0 and np.array_equal(k1.to_host(), np.arange(100_000, dtype=U64) % U64(1000))
-        assert_unchanged(d, snap)
+        assert_keydict_unchanged(d, snap)
         d.close()
     finally:
         small.close()
 
 
 # ---- 7. end to end: stream the batches through the dictionary into a state, ask the state for the window's verdicts ----
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
 
 
 def test_streaming_ingest_through_the_dictionary_equals_the_batch_job(engine):

@@ -7,10 +7,10 @@ import pytest
 
 from theia_amd import TadEngine, TadError, _capi as capi
 from theia_amd.engine import DeviceArray
+from job_helpers import SKIP, column
 
 pytestmark = pytest.mark.gpu
 
-SKIP = np.uint64(capi.TAD_KEY_SKIP)
 KEYS = [1, 63, 64, 65, 256, 257, 2049]
 
 
@@ -35,7 +35,7 @@ def dev_bytes(engine, a):
     return base.view(0, a.size, np.uint8)
 
 
-def snapshot(d):
+def recode_snapshot(d):
     cols, side = d.export()
     return [c.tolist() for c in cols], side.tolist(), d.num_keys(), d.nbytes()
 
@@ -94,7 +94,7 @@ def test_a_code_at_the_masks_end_passes_and_one_beyond_is_refused(engine, memory
     used, n = d.used_codes(1, V + 7, out=memory)                             # used_len - 1
     got = used.to_host() if memory == "device" else used
     assert got[V + 6] == 1 and np.array_equal(got, np.isin(np.arange(V + 7), cols[1]))
-    snap = snapshot(d)
+    snap = recode_snapshot(d)
     with pytest.raises(TadError) as ei:
         d.used_codes(1, V + 6, out=memory)                                   # used_len: outside
     assert ei.value.code == capi.TAD_ERR_INVALID_ARGUMENT and "outside" in ei.value.message
@@ -104,7 +104,7 @@ def test_a_code_at_the_masks_end_passes_and_one_beyond_is_refused(engine, memory
         with pytest.raises(TadError) as ei:
             d.used_codes(bad_col, V + 7, out=memory)
         assert ei.value.code == capi.TAD_ERR_INVALID_ARGUMENT and "column" in ei.value.message
-    assert snapshot(d) == snap                                               # read-only throughout
+    assert recode_snapshot(d) == snap                                               # read-only throughout
     d.close()
 
 
@@ -195,7 +195,7 @@ def test_recode_one_and_two_terms_host_and_device_remaps(engine, n_cols, terms, 
 def test_the_identity_leaves_the_dictionary_untouched(engine, how):
     cols, side, V = tuples(300, 2, 31)
     d = loaded(engine, cols, side)
-    snap = snapshot(d)
+    snap = recode_snapshot(d)
     if how == "identity":
         assert d.recode({0: np.arange(V), 1: np.arange(V)}) == 300
     elif how == "no-terms":
@@ -204,7 +204,7 @@ def test_the_identity_leaves_the_dictionary_untouched(engine, how):
         r = np.arange(V, dtype=np.int64)
         r[~np.isin(np.arange(V), cols[1])] = -1
         assert d.recode({1: r}) == 300
-    assert snapshot(d) == snap
+    assert recode_snapshot(d) == snap
     assert np.array_equal(lookup_ids(d, cols, side), np.arange(300, dtype=np.uint64))
     d.close()
     e = engine.key_dict(2, 1)                              # an empty dictionary
@@ -229,7 +229,7 @@ def test_refusals_leave_the_dictionary_unchanged(engine, what, memory):
         cols[1][64], cols[1][3] = 9, 9                     # keys 3 and 64 differ in column 0 only ...
         remap[cols[0][64]] = remap[cols[0][3]]             # ... and no longer after it
     d = loaded(engine, cols, side)
-    snap = snapshot(d)
+    snap = recode_snapshot(d)
     terms = [(0, remap), (1, col1)]
     if what == "twice":
         terms = [(0, remap), (0, remap)]
@@ -240,7 +240,7 @@ def test_refusals_leave_the_dictionary_unchanged(engine, what, memory):
     with pytest.raises(TadError) as ei:
         d.recode(terms)
     assert ei.value.code == capi.TAD_ERR_INVALID_ARGUMENT and "unchanged" in ei.value.message
-    assert snapshot(d) == snap
+    assert recode_snapshot(d) == snap
     assert np.array_equal(lookup_ids(d, cols, side), np.arange(K, dtype=np.uint64))
     a, _, first, before = d.encode([np.array([cols[0][0], 10 ** 6]), np.array([cols[1][0], 1])])      # and it still takes keys
     assert before == K and np.array_equal(a, [0, K])
@@ -253,11 +253,11 @@ def test_a_remap_of_a_small_workspace_limit_engine_is_refused_whole():
     try:
         cols, side, V = tuples(500, 1, 3, V=200_000)
         d = loaded(small, cols, side)
-        snap = snapshot(d)
+        snap = recode_snapshot(d)
         remap = np.random.default_rng(8).permutation(V).astype(np.int64)
         with pytest.raises(TadError) as ei:
             d.recode({0: remap})
-        assert ei.value.code == capi.TAD_ERR_GRID_TOO_LARGE and snapshot(d) == snap
+        assert ei.value.code == capi.TAD_ERR_GRID_TOO_LARGE and recode_snapshot(d) == snap
         with pytest.raises(TadError) as ei:
             d.used_codes(0, 2_000_000, out="host")
         assert ei.value.code == capi.TAD_ERR_GRID_TOO_LARGE
@@ -269,11 +269,6 @@ def test_a_remap_of_a_small_workspace_limit_engine_is_refused_whole():
 
 
 # ---- the chain ----
-
-def column(strings):
-    off = np.zeros(len(strings) + 1, dtype=np.int64)
-    np.cumsum([len(s) for s in strings], out=off[1:])
-    return off, np.frombuffer(b"".join(strings), dtype=np.uint8).copy()
 
 
 def decoded(sd, codes):
@@ -289,7 +284,7 @@ def test_the_chain_mark_compact_recode_keeps_every_keys_strings(engine, memory):
     rng = np.random.default_rng(2024)
     names = [b"pod-%03d-%s" % (i, b"xyzxyzxyzxyzxyzxyzxyz"[:i % 20]) for i in range(500)]
     sd = engine.string_dict(1, 1)
-    assert np.array_equal(sd.encode(column(names))[0], np.arange(500))
+    assert np.array_equal(sd.encode(column(names, 64))[0], np.arange(500))
     live = np.sort(rng.choice(500, 37, replace=False))
     cols = [live[rng.integers(0, 37, 3000)].astype(np.int64), np.arange(3000, dtype=np.int64)]
     cols[0][:37] = live                                    # every one of the 37 is used
@@ -308,11 +303,11 @@ def test_the_chain_mark_compact_recode_keeps_every_keys_strings(engine, memory):
     assert sd.num_values() == 37 and decoded(sd, np.arange(37)) == [names[c] for c in live]
     assert g_cols[0].max() == 36 and np.array_equal(np.unique(g_cols[0]), np.arange(37))
     # a second round with nothing to retire is the identity everywhere
-    snap = snapshot(kd)
+    snap = recode_snapshot(kd)
     used, n_used = kd.used_codes(0, 37, out=memory)
     remap, st = sd.compact(used, out=memory)
     assert n_used == 37 and st["values_after"] == 37 and np.array_equal(remap.to_host() if memory == "device" else remap, np.arange(37))
     kd.recode({0: remap})
-    assert snapshot(kd) == snap
+    assert recode_snapshot(kd) == snap
     kd.close()
     sd.close()

@@ -10,6 +10,7 @@ import pytest
 
 from theia_amd import TadError, _capi as capi
 from theia_amd.engine import DeviceArray
+from job_helpers import assert_keydict_unchanged, keydict_snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -72,16 +73,6 @@ def reference(d, terms, side=None):
     return keep.astype(np.uint8)
 
 
-def snapshot(d):
-    cols, side = d.export()
-    return d.num_keys(), [c.copy() for c in cols], side.copy()
-
-
-def assert_unchanged(d, snap, what=""):
-    n, cols, side = snapshot(d)
-    assert n == snap[0] and all(np.array_equal(a, b) for a, b in zip(cols, snap[1])) and np.array_equal(side, snap[2]), what
-
-
 def host_of(keep):
     return keep.to_host() if isinstance(keep, DeviceArray) else np.asarray(keep)
 
@@ -106,7 +97,7 @@ def term_sets(ncols, K, rng):
 @pytest.mark.parametrize("ncols", WIDTHS)
 def test_select_equals_numpy_on_the_exported_tuples(engine, ncols, K):
     d = filled(engine, ncols, K)
-    snap = snapshot(d)
+    snap = keydict_snapshot(d)
     rng = np.random.default_rng(ncols * 7919 + K)
     some = 0
     for name, terms in term_sets(ncols, K, rng).items():
@@ -122,7 +113,7 @@ def test_select_equals_numpy_on_the_exported_tuples(engine, ncols, K):
             assert want.all()
     if K >= 255:
         assert some >= 4, some                               # mixed masks: the comparisons are not vacuous
-    assert_unchanged(d, snap)
+    assert_keydict_unchanged(d, snap)
     d.close()
 
 
@@ -230,7 +221,7 @@ def test_device_masks_and_output_at_odd_addresses(engine, shift):
 def test_refusals_leave_the_dictionary_unchanged(engine):
     K = 300
     d = filled(engine, 3, K)
-    snap = snapshot(d)
+    snap = keydict_snapshot(d)
     m = np.ones(card_of(3, K, 0), np.uint8)
     good = np.zeros(K, np.uint8)
     assert raw_select(engine, d, [(0, m)], good) == K
@@ -245,7 +236,7 @@ def test_refusals_leave_the_dictionary_unchanged(engine):
             raw_select(engine, d, terms, keep, **kw)
         assert ei.value.code == capi.TAD_ERR_INVALID_ARGUMENT, name
         assert "tad_keydict_select" in ei.value.message, (name, ei.value.message)
-        assert_unchanged(d, snap, name)
+        assert_keydict_unchanged(d, snap, name)
     # a tuple value equal to mask_len: the mask of column 0 one byte short of the largest code the dictionary holds
     cols, _ = d.export()
     top = int(cols[0].max())
@@ -254,17 +245,17 @@ def test_refusals_leave_the_dictionary_unchanged(engine):
         with pytest.raises(TadError) as ei:
             d.select([(0, np.ones(top, np.uint8))], out=out)
         assert ei.value.code == capi.TAD_ERR_INVALID_ARGUMENT and "outside the mask" in ei.value.message
-        assert_unchanged(d, snap, "value == mask_len")
+        assert_keydict_unchanged(d, snap, "value == mask_len")
     assert raw_select(engine, d, [(0, m)], good) == K and good.all()          # the next call is served
     d.close()
     # a negative tuple value
     d = engine.key_dict(2, expected_keys=1)
     d.encode([np.array([0, 1, -1, 2], np.int64), np.array([0, 0, 0, 0], np.int64)])
-    snap = snapshot(d)
+    snap = keydict_snapshot(d)
     with pytest.raises(TadError) as ei:
         d.select([(0, np.ones(8, np.uint8))], out="host")
     assert ei.value.code == capi.TAD_ERR_INVALID_ARGUMENT and "outside the mask" in ei.value.message
-    assert_unchanged(d, snap, "negative value")
+    assert_keydict_unchanged(d, snap, "negative value")
     keep, n_sel = d.select([(1, np.ones(1, np.uint8))], out="host")           # the other column is in range
     assert n_sel == 4 and keep.all()
     d.close()

@@ -6,10 +6,10 @@ chunks the total is K too, and the shortcut would leave most of the long key's h
 history is its series sorted, the series is the host model's, and the state equals a fresh one streamed over the final points."""
 import numpy as np
 import pytest
+from state_helpers import T_BASE, bits
 
 pytestmark = pytest.mark.gpu
 
-T_BASE = 1660202814
 MIN = 60
 CHUNK = 2048          # kHistChunk of theia_amd/csrc/tad_internal.h
 STATE_FIELDS = ("n", "avg", "m2", "last_t")
@@ -17,11 +17,6 @@ STATE_FIELDS = ("n", "avg", "m2", "last_t")
 # points per key -> the merge's history chunks ceil(len / 2048): the first and the last layout sum to K with a key of two chunks
 LAYOUTS = {"empty + long": (0, 3000), "short + long": (5, 3000), "long, two empty, long": (3000, 0, 0, 2500),
            "empty, three chunks, short": (0, 4500, 7)}
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
 
 
 def points(lens, seed):

@@ -7,11 +7,10 @@ import pytest
 from oracle import tad_oracle as orc
 from theia_amd import TadError
 from theia_amd import _capi as capi
+from job_helpers import PLANS, SKIP64, narrow_key, plan  # noqa: F401  (plan: the fixture)
 
 pytestmark = pytest.mark.gpu
 
-SKIP64 = np.uint64(orc.MASK64)
-SKIP32 = np.uint32(0xFFFFFFFF)
 FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev", "anomaly")
 WIDTHS = ((32, 64), (64, 32), (32, 32))      # (key bits, time bits)
 
@@ -28,10 +27,6 @@ def table(seed, n, K, T, t0=1_700_000_000, step=60, skip=0.01, pod=False):
         k2 = rng.integers(0, K, n, dtype=np.uint64)
         k2[rng.random(n) < 0.3] = SKIP64
     return dict(key_id=k, flow_end_s=t, value=v, key_id2=k2, flow_start_s=ts)
-
-
-def narrow_key(k):
-    return None if k is None else np.where(k == SKIP64, SKIP32, k).astype(np.uint32)
 
 
 def columns(tab, kb, tb, device=False, with_start=False):
@@ -69,29 +64,6 @@ def run_both(engine, tab, K, algo="EWMA", widths=WIDTHS, device=False, with_star
         got = engine.run(algo, num_keys=K, agg_flow=agg_flow, emit_all=True, **columns(tab, kb, tb, device, with_start), **kw)
         same_result(wide, got, (algo, kb, tb, device))
     return wide
-
-
-PLANS = [
-    dict(),
-    dict(stage0="v1"),
-    dict(stage0="v2", partition_pass="sort"),
-    dict(stage0="v2", partition_pass="wc"),
-    dict(stage0="v2", partition_pass="wc_sectors"),
-    dict(stage0="v2", histogram="exact"),
-    dict(stage0="v2", histogram="sampled"),
-    dict(sparse="never"),
-    dict(sparse="always", sparse_sort="lsd"),
-    dict(stage0="v2", sparse="always", sparse_sort="partition"),
-    dict(sparse="always", sparse_classes="always"),
-]
-
-
-@pytest.fixture
-def plan(engine):
-    def set_plan(**kw):
-        engine.set_plan(**kw)
-    yield set_plan
-    engine.set_plan()
 
 
 @pytest.mark.parametrize("p", PLANS, ids=lambda p: "-".join("%s=%s" % kv for kv in p.items()) or "auto")

@@ -15,9 +15,7 @@ import pytest
 
 from oracle import stream_oracle as so
 from oracle import tad_oracle as orc
-
-from test_gpu_parity import check_job
-from test_gpu_sparse import class_boundary_table, day_table
+from job_helpers import check_job, class_boundary_table, day_table
 
 pytestmark = pytest.mark.gpu
 

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import tad_oracle as orc
-
+from job_helpers import check_job
 
 pytestmark = pytest.mark.gpu
 
@@ -109,28 +109,6 @@ def test_series_dbscan_sorted_windows_adversarial(engine):
 
 
 # ------------------------------------------------------------------ (c) whole job vs oracle
-def check_job(engine, algo, key, t, v, num_keys, agg_flow="svc", **kw):
-    okw = {k: kw[k] for k in ("key_id2", "flow_start_s", "start_time", "end_time") if k in kw}
-    okw.update({k: kw[k] for k in ("alpha", "eps", "min_samples") if kw.get(k)})      # 0 = the detector's default on both sides
-    want = orc.run_job(algo, key, t, v, agg_flow=agg_flow, **okw)
-    # every point, with verdicts (plotDF before the filter)
-    allp = engine.run(algo, key, t, v, num_keys, agg_flow=agg_flow, emit_all=True, **kw)
-    pk, pt, pv = want["points"]
-    assert allp.n_rows == want["n_points"] == allp.stats["n_points"]
-    assert allp.stats["n_keys"] == want["n_keys"]
-    assert (allp["key_id"] == pk).all() and (allp["flow_end_s"] == pt).all()
-    assert (allp["throughput"] == orc.u64_to_f64(pv)).all()          # integer aggregates, bit-exact
-    n = np.diff(want["ptr"])
-    assert (allp["stddev"] == np.repeat(want["sigma"], n)).all()       # same recurrence -> same bits
-    assert (allp["algo_calc"] == want["calc_all"]).all()               # EWMA bit-exact / DBSCAN 0.0
-    assert (allp["anomaly"].astype(bool) == want["anomaly_all"]).all()
-    assert allp.stats["n_anomalies"] == want["n_anomalies"]
-    # the job's real output: anomalous points only
-    res = engine.run(algo, key, t, v, num_keys, agg_flow=agg_flow, **kw)
-    assert res.n_rows == want["n_anomalies"] == res.stats["n_anomalies"]
-    for f in ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev"):
-        assert (res[f] == want[f]).all(), f
-    return res, want
 
 
 @pytest.mark.parametrize("algo", ["EWMA", "DBSCAN"])

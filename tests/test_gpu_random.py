@@ -7,8 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import tad_oracle as orc
-
-from test_gpu_parity import check_job
+from job_helpers import check_job
 
 pytestmark = pytest.mark.gpu
 SKIP = np.uint64(orc.MASK64)

@@ -7,9 +7,8 @@ import numpy as np
 import pytest
 
 from rollup_model import HIST, SER, TIMES, I64, U64
-from test_gpu_state_keys import T_BASE, assert_rows, assert_same, key_values, rows_of, snapshot
-from test_gpu_state_rollup import build, roll
-from test_gpu_state_sequences import restart
+from state_drivers import build, restart, roll
+from state_helpers import T_BASE, assert_rows, assert_same, key_values, rows_of, snapshot
 
 pytestmark = pytest.mark.gpu
 

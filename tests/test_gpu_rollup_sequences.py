@@ -9,9 +9,8 @@ import pytest
 
 import rollup_model as R
 import state_model as sm
-from test_gpu_state_merge import assert_counts, new_state
-from test_gpu_state_run import assert_rows, assert_same, bits, rows_of, snapshot
-from test_gpu_state_sequences import COMPACT_FIELDS, execute, run_check
+from state_drivers import COMPACT_FIELDS, execute, run_check
+from state_helpers import assert_counts, assert_rows, assert_same, bits, new_state, rows_of, snapshot
 
 pytestmark = pytest.mark.gpu
 

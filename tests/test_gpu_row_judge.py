@@ -10,8 +10,7 @@ import pytest
 
 from theia_amd import TadError
 from theia_amd import _capi as capi
-
-from test_gpu_narrow_columns import PLANS, SKIP64, narrow_key, plan  # noqa: F401  (plan: the fixture)
+from job_helpers import PLANS, SKIP64, narrow_key, plan  # noqa: F401  (plan: the fixture)
 
 pytestmark = pytest.mark.gpu
 

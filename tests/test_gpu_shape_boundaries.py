@@ -21,8 +21,7 @@ import numpy as np
 import pytest
 
 from oracle import tad_oracle as orc
-
-from test_gpu_parity import check_job
+from job_helpers import check_job
 
 pytestmark = pytest.mark.gpu
 

@@ -25,9 +25,7 @@ import pytest
 import slot_model as sm
 from slot_model import Strings, Tuples
 from theia_amd import TadError, _capi as capi
-from test_gpu_factorize import SKIP
-from test_gpu_keydict import host
-from test_gpu_strdict import STAGE, column, device_column, exported
+from job_helpers import SKIP, STAGE, column, device_column, exported, host
 
 pytestmark = pytest.mark.gpu
 

@@ -8,55 +8,16 @@ import pytest
 
 from oracle import tad_oracle as orc
 from theia_amd import TadError
+from job_helpers import check_lsd, class_boundary_table, day_table, skewed_table
 
 pytestmark = pytest.mark.gpu
-
-
-def check(engine, algo, k, t, v, K, agg_flow, paths=(4,), **kw):
-    want = orc.run_job(algo, k, t, v, agg_flow=agg_flow, **kw)
-    allp = engine.run(algo, k, t, v, K, agg_flow=agg_flow, emit_all=True, **kw)
-    assert allp.stats["stage0_path"] in paths
-    pk, pt, pv = want["points"]
-    if algo == "ARIMA":
-        keep = np.repeat(np.array([r is not None for r in want["arima_results"]]), np.diff(want["ptr"]))
-    else:
-        keep = np.ones(pk.size, dtype=bool)
-    assert allp.n_rows == int(keep.sum())
-    assert (allp["key_id"] == pk[keep]).all() and (allp["flow_end_s"] == pt[keep]).all()
-    assert (allp["throughput"] == orc.u64_to_f64(pv)[keep]).all()
-    assert (allp["stddev"] == np.repeat(want["sigma"], np.diff(want["ptr"]))[keep]).all()
-    assert np.array_equal(allp["algo_calc"], want["calc_all"][keep], equal_nan=True)
-    assert (allp["anomaly"].astype(bool) == want["anomaly_all"][keep]).all()
-    res = engine.run(algo, k, t, v, K, agg_flow=agg_flow, **kw)
-    assert res.stats["stage0_path"] in paths and res.n_rows == want["n_anomalies"]
-    for f in ("key_id", "flow_end_s", "throughput", "stddev"):
-        assert (res[f] == want[f]).all(), f
-    assert np.array_equal(res["algo_calc"], want["algo_calc"], equal_nan=True)
-    assert res.stats["n_keys"] == want["n_keys"] and res.stats["n_points"] == want["n_points"]
-    return res, want
-
-
-def day_table(K, pts_per_key, rows_per_point, seed, span=86400):
-    """second-resolution timestamps anywhere in a day (gcd 1), a few rows per (key, second)"""
-    rng = np.random.default_rng(seed)
-    P = K * pts_per_key
-    pk = np.repeat(np.arange(K, dtype=np.uint64), pts_per_key)
-    pt = 1660202814 + rng.integers(0, span, size=P).astype(np.int64)
-    base = 1_000_000_000 + (orc.mix64(pk + np.uint64(3)) % np.uint64(3_000_000_000)).astype(np.int64)
-    k = np.repeat(pk, rows_per_point)
-    t = np.repeat(pt, rows_per_point)
-    v = (np.repeat(base, rows_per_point) + rng.integers(-1_000_000, 1_000_000, size=k.size)).astype(np.uint64)
-    spike = rng.random(k.size) < 2e-3
-    v = np.where(spike, v * np.uint64(7), v)
-    order = rng.permutation(k.size)
-    return k[order], t[order], v[order]
 
 
 @pytest.mark.parametrize("algo", ["EWMA", "DBSCAN"])
 def test_gcd1_timestamps_over_a_day(engine, algo):
     K = 20000
     k, t, v = day_table(K, 50, 3, seed=1)                       # 3e6 rows; dense grid would be 20000 x 86400 cells = 15.6 GB
-    res, want = check(engine, algo, k, t, v, K, "svc")
+    res, want = check_lsd(engine, algo, k, t, v, K, "svc")
     assert res.stats["step"] == 1 and res.stats["n_buckets"] > 86000
     print("%s: %d rows, %d points, sparse job %.2f ms" % (algo, k.size, want["n_points"], res.stats["ms_total"]))
     assert res.stats["ms_total"] < 60.0
@@ -67,7 +28,7 @@ def test_gcd1_arima(engine):
     k, t, v = day_table(K, 40, 2, seed=2)
     k, t, v = k[:], t[:], v[:]
     with engine.plan(sparse="always"):
-        check(engine, "ARIMA", k, t, v, K, "svc")
+        check_lsd(engine, "ARIMA", k, t, v, K, "svc")
 
 
 def test_a_million_short_lived_connections(engine):
@@ -85,9 +46,9 @@ def test_a_million_short_lived_connections(engine):
     vv = np.concatenate([v, (v[dup] // np.uint64(2))])
     order = rng.permutation(k.size)
     k, t, vv = k[order], t[order], vv[order]
-    res, want = check(engine, "DBSCAN", k, t, vv, K, "", paths=(8,))    # 5.8e6 rows: pass A ran, the key-block partition pass + LDS sorts (tests/test_gpu_sparse_partition.py)
+    res, want = check_lsd(engine, "DBSCAN", k, t, vv, K, "", paths=(8,))    # 5.8e6 rows: pass A ran, the key-block partition pass + LDS sorts (tests/test_gpu_sparse_partition.py)
     with engine.plan(sparse_sort="lsd"):
-        check(engine, "DBSCAN", k, t, vv, K, "")
+        check_lsd(engine, "DBSCAN", k, t, vv, K, "")
     # n_k < 4 = min_samples -> no core point -> every point of such a key is an anomaly
     assert want["n_anomalies"] > 1_000_000
     print("1e6 connections: %d rows, %d points, %d anomalies, sparse job %.2f ms" % (k.size, want["n_points"], want["n_anomalies"], res.stats["ms_total"]))
@@ -102,34 +63,16 @@ def test_sparse_with_second_key_time_window_and_aggregate(engine):
     k = np.where(k % np.uint64(7) == 0, orc.KEY_SKIP, k)
     ts = t - rng.integers(0, 600, size=t.size)
     with engine.plan(sparse="always"):
-        check(engine, "EWMA", k, t, v, 400, "pod", key_id2=k2, flow_start_s=ts, start_time=int(t.min()) + 100, end_time=int(t.max()) - 300)
+        check_lsd(engine, "EWMA", k, t, v, 400, "pod", key_id2=k2, flow_start_s=ts, start_time=int(t.min()) + 100, end_time=int(t.max()) - 300)
         pts = engine.aggregate(k, t, v, 400, agg_flow="pod", key_id2=k2)
         pk, pt, pv = orc.stage0(k, t, v, "sum", k2)
         assert pts.stats["stage0_path"] == 4 and pts.n_points == pk.size
         assert (pts["key_id"] == pk).all() and (pts["flow_end_s"] == pt).all() and (pts["value"] == pv).all()
         # wrap-around sums and values beyond 2^53 are exact here too (plain u64 arithmetic, no packed records)
         big = np.where(rng.random(v.size) < 0.05, rng.integers(2**62, 2**64 - 1, size=v.size, dtype=np.uint64), v)
-        check(engine, "EWMA", k, t, big, 400, "svc")
+        check_lsd(engine, "EWMA", k, t, big, 400, "svc")
         with pytest.raises(TadError):
             engine.run("EWMA", np.array([500], dtype=np.uint64), t[:1], v[:1], 400, agg_flow="svc")        # key id out of range
-
-
-def skewed_table(K, long_keys, long_len, seed, span=86400):
-    """a few keys with a point at (almost) every second of a day, the rest with 1..12 points: the rank grid of the sparse path
-    would be K x long_len cells for ~K * 6 points"""
-    rng = np.random.default_rng(seed)
-    n_k = rng.integers(1, 13, size=K)
-    n_k[rng.choice(K, size=long_keys, replace=False)] = long_len
-    n_k[rng.choice(K, size=K // 50, replace=False)] = 0          # keys without rows
-    pk = np.repeat(np.arange(K, dtype=np.uint64), n_k)
-    pt = np.concatenate([np.sort(rng.choice(span, size=n, replace=False)) for n in n_k]).astype(np.int64) + 1660202814
-    base = 1_000_000_000 + (orc.mix64(pk + np.uint64(3)) % np.uint64(3_000_000_000)).astype(np.int64)
-    v = (base + rng.integers(-1_000_000, 1_000_000, size=pk.size)).astype(np.uint64)
-    v = np.where(rng.random(pk.size) < 3e-3, v * np.uint64(9), v)
-    dup = rng.random(pk.size) < 0.2                                # some points have two rows
-    k = np.concatenate([pk, pk[dup]]); t = np.concatenate([pt, pt[dup]]); v = np.concatenate([v, v[dup] // np.uint64(3)])
-    order = rng.permutation(k.size)
-    return k[order], t[order], v[order]
 
 
 def check_classes(engine, algo, k, t, v, K, agg_flow):
@@ -179,19 +122,6 @@ def test_skewed_series_lengths_run_as_length_classes(algo, agg):
         assert abs(pts.stats["pts_mean"] - gm) <= 1e-12 * gm
     finally:
         eng.close()
-
-
-def class_boundary_table():
-    """18 keys with a series at every class boundary (16 / 64 / 256 points), keys without points among them -> (key, t, value, K)"""
-    rng = np.random.default_rng(3)
-    n_k = np.array([0, 1, 2, 3, 4, 15, 16, 17, 63, 64, 65, 255, 256, 257, 300, 0, 5, 40], dtype=np.int64)
-    K = n_k.size
-    pk = np.repeat(np.arange(K, dtype=np.uint64), n_k)
-    pt = np.concatenate([np.sort(rng.choice(5000, size=n, replace=False)) for n in n_k]).astype(np.int64) + 1660202814
-    v = (2_000_000_000 + rng.integers(-3_000_000, 3_000_000, size=pk.size)).astype(np.uint64)
-    v = np.where(rng.random(pk.size) < 0.02, v * np.uint64(5), v)
-    order = rng.permutation(pk.size)
-    return pk[order], pt[order], v[order], K
 
 
 def test_length_classes_forced_small_tables(engine):

@@ -30,9 +30,7 @@ import numpy as np
 import pytest
 
 from oracle import tad_oracle as orc
-
-from test_gpu_sparse import check as check_lsd, class_boundary_table
-from test_gpu_sparse_partition import PART, check as check_part
+from job_helpers import PART, check_lsd, check_part, class_boundary_table, lattice
 
 pytestmark = pytest.mark.gpu
 
@@ -74,14 +72,6 @@ def agg_check(engine, k, t, v, K, agg, paths, k2=None):
     assert pts.n_points == pk.size == pts.stats["n_points"]
     assert (pts["key_id"] == pk).all() and (pts["flow_end_s"] == pt).all() and (pts["value"] == pv).all()
     return pts
-
-
-def lattice(t_live):
-    """(t0, step, n_buckets) as the engine derives them from the live rows: the gcd lattice through the first and the last time"""
-    t_live = np.asarray(t_live, dtype=np.int64)
-    t0 = int(t_live.min())
-    step = int(np.gcd.reduce(t_live - t0)) or 1
-    return t0, step, (int(t_live.max()) - t0) // step + 1
 
 
 def sorted_slots(k, t, K, k2=None):

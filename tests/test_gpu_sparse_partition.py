@@ -9,31 +9,9 @@ import numpy as np
 import pytest
 
 from oracle import tad_oracle as orc
-from test_gpu_sparse import day_table, skewed_table
+from job_helpers import PART, check_part, day_table, skewed_table
 
 pytestmark = pytest.mark.gpu
-
-PART = dict(stage0="v2", sparse="always", sparse_sort="partition")
-
-
-def check(engine, algo, k, t, v, K, agg_flow, paths=(8,), **kw):
-    want = orc.run_job(algo, k, t, v, agg_flow=agg_flow, **kw)
-    allp = engine.run(algo, k, t, v, K, agg_flow=agg_flow, emit_all=True, **kw)
-    assert allp.stats["stage0_path"] in paths, allp.stats["stage0_path"]
-    pk, pt, pv = want["points"]
-    assert allp.n_rows == pk.size
-    assert (allp["key_id"] == pk).all() and (allp["flow_end_s"] == pt).all()
-    assert (allp["throughput"] == orc.u64_to_f64(pv)).all()
-    assert (allp["stddev"] == np.repeat(want["sigma"], np.diff(want["ptr"]))).all()
-    assert np.array_equal(allp["algo_calc"], want["calc_all"], equal_nan=True)
-    assert (allp["anomaly"].astype(bool) == want["anomaly_all"]).all()
-    res = engine.run(algo, k, t, v, K, agg_flow=agg_flow, **kw)
-    assert res.stats["stage0_path"] in paths and res.n_rows == want["n_anomalies"]
-    for f in ("key_id", "flow_end_s", "throughput", "stddev"):
-        assert (res[f] == want[f]).all(), f
-    assert np.array_equal(res["algo_calc"], want["algo_calc"], equal_nan=True)
-    assert res.stats["n_keys"] == want["n_keys"] and res.stats["n_points"] == want["n_points"]
-    return res, want
 
 
 @pytest.mark.parametrize("algo,agg", [("EWMA", "svc"), ("DBSCAN", "")])
@@ -41,7 +19,7 @@ def test_day_of_seconds_through_the_partition_pass(engine, algo, agg):
     K = 3000
     k, t, v = day_table(K, 20, 3, seed=21)                      # 1.8e5 rows, 86 400 buckets: 750 key blocks of 4 keys
     with engine.plan(**PART):
-        res, want = check(engine, algo, k, t, v, K, agg)
+        res, want = check_part(engine, algo, k, t, v, K, agg)
         assert res.stats["step"] == 1 and res.stats["n_buckets"] > 86000 and res.stats["stage0_attempts"] == 1
 
 
@@ -63,8 +41,8 @@ def test_key_blocks_of_several_rounds(engine):
     order = rng.permutation(k.size)
     k, t, v = k[order], t[order], v[order]
     with engine.plan(**PART):
-        check(engine, "EWMA", k, t, v, K, "svc")
-        check(engine, "DBSCAN", k, t, v, K, "")
+        check_part(engine, "EWMA", k, t, v, K, "svc")
+        check_part(engine, "DBSCAN", k, t, v, K, "")
         pts = engine.aggregate(k, t, v, K, agg_flow="svc")
         qk, qt, qv = orc.stage0(k, t, v, "sum")
         assert pts.stats["stage0_path"] in (8, 10) and pts.n_points == qk.size
@@ -80,7 +58,7 @@ def test_second_key_time_window_skipped_keys_and_a_coarse_lattice(engine):
     k = np.where(k % np.uint64(7) == 0, orc.KEY_SKIP, k)
     ts = t - rng.integers(0, 600, size=t.size)
     with engine.plan(**PART):
-        res, _ = check(engine, "EWMA", k, t, v, 2500, "pod", key_id2=k2, flow_start_s=ts, start_time=int(t.min()) + 700, end_time=int(t.max()) - 2100)
+        res, _ = check_part(engine, "EWMA", k, t, v, 2500, "pod", key_id2=k2, flow_start_s=ts, start_time=int(t.min()) + 700, end_time=int(t.max()) - 2100)
         assert res.stats["step"] == 7
         pts = engine.aggregate(k, t, v, 2500, agg_flow="pod", key_id2=k2)
         pk, pt, pv = orc.stage0(k, t, v, "sum", k2)
@@ -99,7 +77,7 @@ def test_lattice_of_exactly_a_power_of_two_buckets(engine):
     v = rng.integers(1, 3_000_000_000, size=pk.size).astype(np.uint64)
     t = 1660202814 + pt
     with engine.plan(**PART):
-        res, _ = check(engine, "DBSCAN", pk, t, v, K, "")
+        res, _ = check_part(engine, "DBSCAN", pk, t, v, K, "")
         assert res.stats["n_buckets"] == 4096
 
 
@@ -109,14 +87,14 @@ def test_what_the_records_cannot_hold_goes_to_the_lsd_sort(engine):
     K = 3000
     k, t, v = skewed_table(K, long_keys=1, long_len=20000, seed=26)
     with engine.plan(**PART):
-        res, _ = check(engine, "EWMA", k, t, v, K, "svc", paths=(4,))
+        res, _ = check_part(engine, "EWMA", k, t, v, K, "svc", paths=(4,))
         assert res.stats["stage0_attempts"] == 2
         k, t, v = day_table(K, 10, 2, seed=27)
         big = np.where(np.arange(v.size) % 1000 == 0, np.uint64(2**62) + v, v)
-        res, _ = check(engine, "EWMA", k, t, big, K, "svc", paths=(4,))
+        res, _ = check_part(engine, "EWMA", k, t, big, K, "svc", paths=(4,))
         assert res.stats["stage0_attempts"] == 2
         t_long = 1660202814 + (t - 1660202814) * 3001 + (np.arange(t.size) % 2)       # gcd 1 over 2.6e8 seconds: 28 time bits alone
-        check(engine, "EWMA", k, t_long, v, K, "svc", paths=(4,))
+        check_part(engine, "EWMA", k, t_long, v, K, "svc", paths=(4,))
 
 
 def test_length_classes_after_the_partition_sort():
@@ -142,5 +120,5 @@ def test_big_table_takes_the_partition_sort_by_itself(engine):
     """5e6 rows of per-connection keys on second-resolution timestamps: pass A runs (>= 2^22 rows), the table is sparse, no plan override"""
     K = 100_000
     k, t, v = day_table(K, 17, 3, seed=29)
-    res, want = check(engine, "DBSCAN", k, t, v, K, "")
+    res, want = check_part(engine, "DBSCAN", k, t, v, K, "")
     print("5.1e6 rows, %d points: job %.2f ms, stage 0 %.2f ms" % (want["n_points"], res.stats["ms_total"], res.stats["ms_stage0"]))

@@ -15,13 +15,11 @@ from oracle import arima_oracle as ao
 from oracle import tad_oracle as orc
 from theia_amd import TadEngine, TadError, _capi
 from theia_amd.engine import DeviceArray
-
-from test_gpu_state_keys import (COOP_MIN_T, COUNTERS, HIST_CHUNK, ROW_FIELDS, T_BASE, U64, assert_rows, assert_same, in_window, key_values,
-                                 new_state, rows_of, snapshot, window)
+from state_helpers import (ALL, COOP_MIN_T, COUNTERS, EDGE_RUNS, EDGE_S, EDGE_T0, HIST_CHUNK, I64, ROW_FIELDS, SER, TIMES, T_BASE, U64, assert_rows,
+                           assert_same, in_window, key_values, new_state, rows_of, run_times, snapshot, wide_values, window)
 
 pytestmark = pytest.mark.gpu
 
-I64 = np.int64
 NO_CHANGE = _capi.TAD_NO_CHANGE
 INV = _capi.TAD_ERR_INVALID_ARGUMENT
 
@@ -109,31 +107,10 @@ def state_of(engine, K, k, t, v, seed=1, history=True):
     """a state of K keys fed the points (k, t, v), one row each, in a seeded order -> (state, W)"""
     k, t, v = np.asarray(k).astype(U64), np.asarray(t, I64), np.asarray(v).astype(U64)
     o = np.random.default_rng(seed).permutation(k.size)
-    st = new_state(engine, K, history)
+    st = new_state(engine, K, ALL if history else SER | TIMES)
     if k.size:
         engine.run_stream(st, np.ascontiguousarray(k[o]), np.ascontiguousarray(t[o]), np.ascontiguousarray(v[o]), value_op="max")
     return st, (window(st) if k.size else (np.zeros(0, U64), np.zeros(0, I64), np.zeros(0, U64)))
-
-
-def run_times(runs, bucket_s, t0, skip=()):
-    """times of a key whose consecutive runs have the given lengths: run j fills the first runs[j] seconds of bucket j (after `skip`ped
-    bucket indices, which stay empty), buckets of bucket_s seconds from t0 (a bucket start) on"""
-    out, b = [], 0
-    for n in runs:
-        while b in skip:
-            b += 1
-        assert 1 <= n <= bucket_s
-        out.append(t0 + b * bucket_s + np.arange(n, dtype=I64))
-        b += 1
-    return np.concatenate(out) if out else np.zeros(0, I64)
-
-
-def wide_values(n, rng, top=0.0):
-    """values of 50 .. 62 significant bits (a few thousand of them wrap a 64-bit sum); a share `top` of them with bit 63 set too"""
-    bits_ = rng.integers(50, 63, size=n)
-    v = (rng.integers(1 << 49, 1 << 50, size=n).astype(U64) << (bits_ - 50).astype(U64)) | U64(1)
-    hi = rng.random(n) < top
-    return np.where(hi, v | U64(1 << 63), v)
 
 
 def assert_runs(W, key, bucket_s, origin, runs):
@@ -143,23 +120,6 @@ def assert_runs(W, key, bucket_s, origin, runs):
     first, lens = M.run_lengths(np.full(tk.size, key, U64), tk, bucket_s, origin)
     assert list(lens) == list(runs), (key, list(lens), list(runs))
     return [(int(f) // HIST_CHUNK, int(f + n - 1) // HIST_CHUNK) for f, n in zip(first, lens)]
-
-
-EDGE_S = 8192                 # the bucket of the edge state: runs of up to 6145 consecutive seconds fit one bucket
-EDGE_T0 = (T_BASE // EDGE_S) * EDGE_S
-EDGE_RUNS = [
-    [1, 63, 64, 65, 1, 2, 62, 66, 128, 129, 1],          # 0: runs around the 64-point slice, inside one chunk
-    [3, 2044, 5, 9],                                     # 1: a run ending on element 2046, the next starting on 2047
-    [3, 2045, 5, 9],                                     # 2: ending on 2047 (the chunk's last), the next starting on 2048 (a chunk's first)
-    [3, 2046, 5, 9],                                     # 3: ending on 2048, starting on 2049
-    [3, 2047, 5, 9],                                     # 4: ending on 2049, starting on 2050
-    [2048, 2048, 7],                                     # 5: runs of exactly one chunk, aligned
-    [5, 4097, 3],                                        # 6: one bucket over three chunks
-    [2047, 6145, 2],                                     # 7: one bucket over four chunks, its head the last point of chunk 0
-    [],                                                  # 8: empty
-    [4097],                                              # 9: all points of the key in one bucket
-    [1] * 70,                                            # 10: every point in a bucket of its own, over a slice edge
-]
 
 
 @pytest.fixture(scope="module")
@@ -477,7 +437,7 @@ def test_a_workspace_limit_too_small_for_the_view_fails_with_the_state_unchanged
     small = TadEngine(device=0, workspace_limit=1 << 20)
     try:
         K, n = 700, 200                                        # 140 000 points: a view of 16 B per bucket needs more than 1 MiB at one second
-        st = new_state(small, K, history=False)
+        st = new_state(small, K, SER | TIMES)
         rng = np.random.default_rng(2)
         for b in range(10):                                    # small batches: the feed itself stays under the limit
             k = np.repeat(np.arange(K, dtype=U64), n // 10)
@@ -523,7 +483,7 @@ def test_refusals(engine, small_state):
     plain = engine.state_create(K)
     assert call(ok(), state=plain) == INV
     plain.close()
-    nohist = new_state(engine, K, history=False)
+    nohist = new_state(engine, K, SER | TIMES)
     assert call(ok(), _capi.Job(algo=_capi.TAD_ALGO["DBSCAN"]), state=nohist) == INV
     nohist.close()
     with pytest.raises(TadError):

@@ -18,14 +18,12 @@ import alerts_model as am
 import replace_model as rm
 import state_model as sm
 from alerts_model import NO_CHANGE
-from test_gpu_state_merge import assert_counts, new_state
-from test_gpu_state_replace import FIVE, T0, big, clone, execute_any, table_of
-from test_gpu_state_run import assert_same, snapshot
+from state_drivers import FIVE, T0, big, clone, execute_any, table_of
+from state_helpers import HIST, SER, TIMES, assert_counts, assert_same, new_state, snapshot
 
 pytestmark = pytest.mark.gpu
 
 U64, I64 = np.uint64, np.int64
-HIST, SER, TIMES = 1, 2, 8
 MODES = ("host", "device", "counters")
 
 

@@ -11,24 +11,17 @@ import pytest
 
 from oracle import stream_oracle as sorc
 from oracle import tad_oracle as orc
+from state_helpers import SKIP, STATE_FIELDS, T_BASE, assert_same, bits, new_state, snapshot
 
 pytestmark = pytest.mark.gpu
 
-T_BASE = 1660202814
 ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev", "anomaly")
-STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
-SKIP = np.uint64((1 << 64) - 1)
 K = 6
 OP = "sum"
 
 
 def at(i):
     return T_BASE + 60 * i
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
 
 
 def table():
@@ -57,26 +50,10 @@ def cat(*rows):
     return tuple(np.concatenate([r[c] for r in rows]) for c in range(3))
 
 
-def new_state(engine, num_keys=K):
-    return engine.state_create(num_keys, history=True, series=True, times=True)
-
-
-def snapshot(st):
-    return {"state": st.export(), "history": st.export_history(), "series": st.export_series(), "times": st.export_times()}
-
-
-def assert_same(a, b, what):
-    for f in STATE_FIELDS:
-        assert np.array_equal(bits(a["state"][f]), bits(b["state"][f])), (what, f)
-    for part in ("history", "series"):
-        assert np.array_equal(a[part][0], b[part][0]) and np.array_equal(a[part][1], b[part][1]), (what, part)
-    assert np.array_equal(a["times"], b["times"]), (what, "times")
-
-
 def pair(engine):
     """A (two batches, cur == 0) and B (one batch, cur == 1) over the same rows"""
     first, second = table()
-    a, b = new_state(engine), new_state(engine)
+    a, b = new_state(engine, K), new_state(engine, K)
     engine.run_stream(a, *first, value_op=OP)
     engine.run_stream(a, *second, value_op=OP)
     engine.run_stream(b, *cat(first, second), value_op=OP)
@@ -127,7 +104,7 @@ def test_resize(engine):
 def test_export_and_import(engine):
     a, b, rows = pair(engine)
     sa, sb = snapshot(a), snapshot(b)
-    copies = [new_state(engine), new_state(engine)]       # fresh states from either export ...
+    copies = [new_state(engine, K), new_state(engine, K)]       # fresh states from either export ...
     for st, snap in zip([a, b] + copies, (sb, sa, sa, sb)):   # ... and each state takes the other's, into its own candidate copies
         st.load(snap["state"])
         st.load_history(*snap["history"])

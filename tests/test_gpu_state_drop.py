@@ -14,53 +14,14 @@ import pytest
 from oracle import drop_oracle as dro
 from oracle import tad_oracle as orc
 from theia_amd import TadError, _capi
+from state_helpers import (HIST, ROW_FIELDS, SER, TIMES, assert_rows, assert_same, bits, drop_oracle_rows, in_window, new_state, order_sensitive,
+                           pairwise_rows, rows_of, snapshot, window)
 
 pytestmark = pytest.mark.gpu
 
 T_BASE = 1660176000
 DAY = 86400
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
-STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
 COUNTERS = ("n_keys", "n_points", "n_anomalies", "keys_no_result")
-HIST, SER, TIMES = 1, 2, 8
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
-
-
-def rows_of(res):
-    d = {f: np.asarray(res[f]) for f in ROW_FIELDS}
-    if "anomaly" in res.to_host():
-        d["anomaly"] = np.asarray(res["anomaly"])
-    return d
-
-
-def assert_rows(got, want, what=""):
-    assert set(got) == set(want), (what, sorted(got), sorted(want))
-    assert got["key_id"].size == want["key_id"].size, (what, got["key_id"].size, want["key_id"].size)
-    for f in want:
-        assert np.array_equal(bits(got[f]), bits(want[f])), (what, f)
-
-
-def new_state(engine, K, flags=SER | TIMES):
-    return engine.state_create(K, history=bool(flags & HIST), series=bool(flags & SER), times=bool(flags & TIMES))
-
-
-def snapshot(st):
-    return {"state": st.export(), "history": st.export_history() if st.history else None,
-            "series": st.export_series() if st.series else None, "times": st.export_times() if st.times and st.series_points() else None}
-
-
-def assert_same(a, b, what=""):
-    for f in STATE_FIELDS:
-        assert np.array_equal(bits(a["state"][f]), bits(b["state"][f])), (what, f)
-    for part in ("history", "series"):
-        if a[part] is not None or b[part] is not None:
-            assert np.array_equal(a[part][0], b[part][0]) and np.array_equal(a[part][1], b[part][1]), (what, part)
-    if a["times"] is not None or b["times"] is not None:
-        assert np.array_equal(a["times"], b["times"]), (what, "times")
 
 
 def coop_min(K, P):
@@ -73,15 +34,6 @@ def draw(rng, n):
     nb = rng.integers(50, 63, size=n)
     lo = np.left_shift(np.uint64(1), (nb - 1).astype(np.uint64))
     return lo + (rng.integers(0, 1 << 62, size=n, dtype=np.uint64) & (lo - np.uint64(1)))
-
-
-def order_sensitive(v):
-    x = orc.u64_to_f64(v)
-    s = dro.pairwise_sum(x)
-    if s == np.cumsum(x)[-1]:
-        return False
-    sq = (s / x.size - x) ** 2
-    return dro.pairwise_sum(sq) != np.cumsum(sq)[-1]
 
 
 def draw_key(rng, n, tweak=None):
@@ -125,47 +77,13 @@ def fill(engine, st, W):
     engine.run_stream(st, W[0], W[1], W[2], agg_flow="svc", value_op="sum")
 
 
-def exported(st):
-    ln, vals = st.export_series()
-    return np.repeat(np.arange(st.num_keys, dtype=np.uint64), ln.astype(np.int64)), st.export_times(), vals
-
-
 # ---- the oracle ----
-def oracle_rows(W, nsigma=3.0, ms=3, emit_all=False, judged=None):
-    """the rows tad_run(DROP) emits over W (in (key, time) order, one row per point), restricted to the points of mask `judged`;
-    -> (rows, keys without a result among the keys with a judged point)"""
-    k, t, v = W
-    x = orc.u64_to_f64(v)
-    judged = np.ones(k.size, bool) if judged is None else judged
-    keys, first, cnt = np.unique(k, return_index=True, return_counts=True)
-    sel, mean, std, verd = [], [], [], []
-    no_result = 0
-    for a, n in zip(first, cnt):
-        j = judged[a:a + n]
-        if not j.any():
-            continue
-        r = dro.drop_detection_series(x[a:a + n], nsigma, ms) if n >= 2 else None     # k_drop_detect: n >= min_samples && n >= 2
-        if r is None:
-            no_result += 1
-            continue
-        m, s, z = r
-        idx = np.flatnonzero(j if emit_all else (j & z)) + a
-        sel.append(idx)
-        mean.append(np.full(idx.size, m))
-        std.append(np.full(idx.size, s))
-        verd.append(z[idx - a])
-    cat = lambda parts, dt: np.concatenate(parts).astype(dt) if parts else np.zeros(0, dt)
-    sel = cat(sel, np.int64)
-    rows = {"key_id": k[sel], "flow_end_s": t[sel], "throughput": x[sel], "algo_calc": cat(mean, np.float64), "stddev": cat(std, np.float64)}
-    if emit_all:
-        rows["anomaly"] = cat(verd, np.uint8)
-    return rows, no_result
 
 
 def check_state(engine, st, K, win=(0, 0, 0), W=None, m=None, what="", **kw):
     """drop_state over the window equals the oracle and the engine's own run("DROP") over W' = W[m], with and without emit_all, and
     leaves the state as it was; returns the emit_all result"""
-    W = W if W is not None else exported(st)
+    W = W if W is not None else window(st)
     m = np.ones(W[0].size, bool) if m is None else m
     Wm = (W[0][m], W[1][m], W[2][m])
     okw = {"nsigma": kw.get("nsigma") or 3.0, "ms": kw.get("min_samples") or 3}
@@ -174,7 +92,7 @@ def check_state(engine, st, K, win=(0, 0, 0), W=None, m=None, what="", **kw):
     for emit_all in (True, False):
         got = engine.drop_state(st, *win, emit_all=emit_all, **kw)
         assert_same(snapshot(st), snap, (what, win, "state changed"))
-        want, no_result = oracle_rows(Wm, emit_all=emit_all, **okw)
+        want, no_result = drop_oracle_rows(Wm, emit_all=emit_all, **okw)
         assert_rows(rows_of(got), want, (what, win, emit_all, kw, "oracle"))
         gs = got.stats
         assert gs["rows_in"] == gs["rows_used"] == gs["n_points"] == Wm[0].size, (what, win)
@@ -206,7 +124,7 @@ def test_series_length_edges_lane_and_wavefront(engine):
     cm = coop_min(K, sum(EDGES))
     assert cm == 512
     assert [n for n in EDGES if n >= cm] == [512, 513, 1023, 1024, 1025] and max(n for n in EDGES if n < cm) == 511     # wavefront | lane
-    st = new_state(engine, K)
+    st = new_state(engine, K, SER | TIMES)
     W = table(vals)
     fill(engine, st, W)
     got = check_state(engine, st, K, W=W, what="edges")
@@ -224,7 +142,7 @@ def test_series_length_edges_lane_and_wavefront(engine):
 def test_long_keys_take_several_rounds_of_leaves(engine):
     lengths = [8191, 8192, 8193, 16385, 100000]
     vals = draw_keys(lengths)
-    st = new_state(engine, 5)
+    st = new_state(engine, 5, SER | TIMES)
     W = table(vals)
     fill(engine, st, W)
     check_state(engine, st, 5, W=W, what="rounds")
@@ -232,21 +150,6 @@ def test_long_keys_take_several_rounds_of_leaves(engine):
 
 
 # ---- 3. the outlier rule above 8192 keys ----
-def pairwise_rows(A):
-    """dro.pairwise_sum over every row of A (8 <= columns <= 128), vectorised over the rows: the same additions in the same order"""
-    n = A.shape[1]
-    assert 8 <= n <= 128
-    r = [A[:, j].copy() for j in range(8)]
-    i = 8
-    while i < n - n % 8:
-        for j in range(8):
-            r[j] = r[j] + A[:, i + j]
-        i += 8
-    res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
-    while i < n:
-        res = res + A[:, i]
-        i += 1
-    return res
 
 
 def test_outlier_rule_above_8192_keys(engine):
@@ -271,7 +174,7 @@ def test_outlier_rule_above_8192_keys(engine):
     big = dict(zip(planted, draw_keys(list(planted.values()))))
     vals = [big[k] if k in big else A[k] for k in range(K)]
     W = table(vals)
-    st = new_state(engine, K)
+    st = new_state(engine, K, SER | TIMES)
     fill(engine, st, W)
     # the oracle, vectorised for the short keys
     X = orc.u64_to_f64(A.ravel()).reshape(K, short)
@@ -299,7 +202,7 @@ def test_parameters(engine):
     # one point far out in every key: its z-score is (n - 1) / sqrt(n), between 2.5 and 3 for n = 9, 10 and above 3 for n = 11, 12
     vals = draw_keys(lengths, tweaks={i: outlier_at(n // 2) for i, n in enumerate(lengths)})
     K = len(lengths)
-    st = new_state(engine, K)
+    st = new_state(engine, K, SER | TIMES)
     W = table(vals)
     fill(engine, st, W)
     default = rows_of(check_state(engine, st, K, W=W, what="defaults"))
@@ -317,18 +220,6 @@ def test_parameters(engine):
 
 
 # ---- 5. windows ----
-def in_window(k, t, from_t=0, to_t=0, keep_points=0):
-    m = np.ones(k.size, bool)
-    if from_t:
-        m &= t >= from_t
-    if to_t:
-        m &= t < to_t
-    if keep_points:
-        idx = np.flatnonzero(m)
-        kk = k[idx]
-        from_end = np.searchsorted(kk, kk, side="right") - np.arange(kk.size)
-        m[idx[from_end > keep_points]] = False
-    return m
 
 
 def test_windows(engine):
@@ -336,7 +227,7 @@ def test_windows(engine):
     vals = draw_keys([n for _, n in spans])
     K = len(spans)
     W = table(vals, [s for s, _ in spans])
-    st = new_state(engine, K)
+    st = new_state(engine, K, SER | TIMES)
     fill(engine, st, W)
     day = lambda d: T_BASE + DAY * d
     inside_seen = set()
@@ -407,7 +298,7 @@ def test_stream_batches(engine, flags):
             engine.run_stream(twin, *B, **kw)
         assert_same(snapshot(st), snapshot(twin), ("stream", b, "twin"))
         Wb = concat(bs[:b + 1])
-        want, no_result = oracle_rows(Wb, emit_all=True, judged=Wb[1] >= B[1].min())
+        want, no_result = drop_oracle_rows(Wb, emit_all=True, judged=Wb[1] >= B[1].min())
         assert_rows(rows_of(got), want, ("stream", b))
         assert got.stats["keys_no_result"] == no_result and got.stats["n_points"] == B[0].size, (b, got.stats)
         assert got.stats["rows_in"] == B[0].size and got.stats["n_keys"] == np.unique(B[0]).size
@@ -422,13 +313,13 @@ def test_stream_plain_rows_and_parameters(engine):
     """without emit_all a batch emits only its anomalous points, with parameters that change from batch to batch; and the window call
     on the state agrees with the batch about the batch's points"""
     bs, K = batches(tweaks={2: outlier_at(599, 604, 609, 669), 1: outlier_at(100, 128, 135, 143)})     # the last point of every batch
-    st = new_state(engine, K)
+    st = new_state(engine, K, SER | TIMES)
     params = [(0.0, 0), (2.0, 0), (0.0, 129), (1.5, 2)]
     for b, B in enumerate(bs):
         nsigma, ms = params[b]
         got = engine.drop_stream(st, *B, agg_flow="svc", value_op="sum", nsigma=nsigma, min_samples=ms)
         Wb = concat(bs[:b + 1])
-        want, no_result = oracle_rows(Wb, nsigma=nsigma or 3.0, ms=ms or 3, judged=Wb[1] >= B[1].min())
+        want, no_result = drop_oracle_rows(Wb, nsigma=nsigma or 3.0, ms=ms or 3, judged=Wb[1] >= B[1].min())
         assert_rows(rows_of(got), want, ("plain", b))
         assert got.stats["keys_no_result"] == no_result and got.stats["n_anomalies"] == got.n_rows
         assert 0 < got.n_rows < B[0].size, (b, got.n_rows)
@@ -448,7 +339,7 @@ def test_after_merge_trim_and_compact(engine):
     fill(engine, st, tuple(c[keep] for c in W))
     engine.merge_stream(st, *(c[~keep] for c in W), agg_flow="svc", value_op="sum")
     got = check_state(engine, st, K, what="merged")
-    assert np.array_equal(exported(st)[1], W[1]) and got.n_rows == sum(v.size for v in vals)
+    assert np.array_equal(window(st)[1], W[1]) and got.n_rows == sum(v.size for v in vals)
     assert st.trim(keep_points=520) == 180
     check_state(engine, st, K, what="trimmed")
     remap, cs = st.compact()
@@ -473,7 +364,7 @@ def test_refusals(engine):
         assert_same(snapshot(st), snap, what)
 
     import ctypes as C
-    full = new_state(engine, 2)
+    full = new_state(engine, 2, SER | TIMES)
     fill(engine, full, W)
     for flags in (0, HIST, SER):                             # drop_state: plain, history-only, series without times
         st = new_state(engine, 2, flags)
@@ -507,7 +398,7 @@ def test_refusals(engine):
     refused(lambda: engine.run_stream(full, *nxt, algo="DROP", **kw), full, "run_stream")
     # stale times: the series imported without its times
     ln, v = full.export_series()
-    stale = new_state(engine, 2)
+    stale = new_state(engine, 2, SER | TIMES)
     stale.load(full.export())
     stale.load_series(ln, v)
     with pytest.raises(TadError) as ei:

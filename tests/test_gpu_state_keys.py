@@ -10,125 +10,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from oracle import drop_oracle as dro
 from oracle import tad_oracle as orc
 from theia_amd import TadError, _capi
 from theia_amd.engine import DeviceArray
+from state_helpers import (COOP_MIN_T, COUNTERS, HIST_CHUNK, SER, TIMES, T_BASE, U64, assert_rows, assert_same, drop_oracle_rows, in_window,
+                           make_state, new_state, order_sensitive, rows_of, snapshot, window, window_oracle_rows)
 
 pytestmark = pytest.mark.gpu
 
-T_BASE = 1660202814
-U64 = np.uint64
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
-STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
-COUNTERS = ("n_keys", "n_points", "n_anomalies", "keys_no_result", "arima_fits", "arima_nan_fits", "kalman_steps")
-HIST_CHUNK = 2048             # tad_internal.h   kHistChunk
-COOP_MIN_T = 512              # tad_internal.h   kCoopMinT
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
-
-
-def rows_of(res):
-    d = {f: np.asarray(res[f]) for f in ROW_FIELDS}
-    if "anomaly" in res.to_host():
-        d["anomaly"] = np.asarray(res["anomaly"])
-    return d
-
-
-def assert_rows(got, want, what=""):
-    assert set(got) == set(want), (what, sorted(got), sorted(want))
-    assert got["key_id"].size == want["key_id"].size, (what, got["key_id"].size, want["key_id"].size)
-    for f in want:
-        assert np.array_equal(bits(got[f]), bits(want[f])), (what, f)
-
-
-def new_state(engine, K, history=True):
-    return engine.state_create(K, history=history, series=True, times=True)
-
-
-def snapshot(st):
-    return {"state": st.export(), "history": st.export_history() if st.history else None,
-            "series": st.export_series() if st.series else None, "times": st.export_times() if st.times and st.series_points() else None}
-
-
-def assert_same(a, b, what=""):
-    for f in STATE_FIELDS:
-        assert np.array_equal(bits(a["state"][f]), bits(b["state"][f])), (what, f)
-    for part in ("history", "series"):
-        if a[part] is not None or b[part] is not None:
-            assert np.array_equal(a[part][0], b[part][0]) and np.array_equal(a[part][1], b[part][1]), (what, part)
-    if a["times"] is not None or b["times"] is not None:
-        assert np.array_equal(a["times"], b["times"]), (what, "times")
-
-
-def window(st):
-    """W: one row per series point the state holds, (key, time, value) in (key, time) order"""
-    ln, vals = st.export_series()
-    keys = np.repeat(np.arange(st.num_keys, dtype=np.uint64), ln.astype(np.int64))
-    return keys, st.export_times(), vals
-
-
-def in_window(k, t, from_t=0, to_t=0, keep_points=0):
-    m = np.ones(k.size, bool)
-    if from_t:
-        m &= t >= from_t
-    if to_t:
-        m &= t < to_t
-    if keep_points:
-        idx = np.flatnonzero(m)
-        kk = k[idx]
-        from_end = np.searchsorted(kk, kk, side="right") - np.arange(kk.size)
-        m[idx[from_end > keep_points]] = False
-    return m
-
-
-def oracle_rows(W, m, algo, emit_all, **kw):
-    """orc.run_job on W'': the rows the engine must return (EWMA, DBSCAN)"""
-    k, t, v = W
-    want = orc.run_job(algo, k[m], t[m], v[m], op="sum", **kw)
-    if not emit_all:
-        return {f: want[f] for f in ROW_FIELDS}
-    pk, pt, pv = want["points"]
-    sig = np.repeat(want["sigma"], np.diff(want["ptr"]))
-    return {"key_id": pk, "flow_end_s": pt, "throughput": orc.u64_to_f64(pv), "algo_calc": want["calc_all"], "stddev": sig,
-            "anomaly": want["anomaly_all"].astype(np.uint8)}
-
 
 # ---- the states: key k holds lens[k] points at seconds starts[k] + 0, 1, 2 ... (or at seeded seconds), values around a per-key base ----
-def key_values(n, key, rng, ties=False):
-    base = 1_000_000_000 + int(orc.mix64(np.array([key + 5], dtype=U64))[0] % U64(3_000_000_000))
-    if ties:                                                  # two values only, the same for every key: ties across keys and inside them
-        v = np.where(rng.random(n) < 0.3, 1_000_000_000, 1_000_000_000 + (1 << 23)).astype(np.int64)
-    else:
-        v = base + rng.integers(-300_000_000, 300_000_000, size=n)
-    if n >= 6:                                                # two points far off: rows without the emit-all flag
-        v[n // 3] = v[n // 3] * 3
-        v[n - 2] = v[n - 2] // 4
-    return v
-
-
-def make_state(engine, lens, seed, starts=None, ties=(), history=True, spread=0):
-    """-> (state, W).  spread: the points of a key at seeded seconds inside [0, spread) instead of consecutive ones"""
-    rng = np.random.default_rng(seed)
-    K = len(lens)
-    ks, ts, vs = [], [], []
-    for key, n in enumerate(lens):
-        n = int(n)
-        if n == 0:
-            continue
-        off = np.sort(rng.choice(spread, size=n, replace=False)) if spread else np.arange(n)
-        ks.append(np.full(n, key, np.int64))
-        ts.append(T_BASE + (int(starts[key]) if starts is not None else 0) + off.astype(np.int64))
-        vs.append(key_values(n, key, rng, ties=key in ties))
-    k, t, v = np.concatenate(ks).astype(U64), np.concatenate(ts), np.concatenate(vs).astype(U64)
-    o = rng.permutation(k.size)
-    st = new_state(engine, K, history)
-    engine.run_stream(st, np.ascontiguousarray(k[o]), np.ascontiguousarray(t[o]), np.ascontiguousarray(v[o]), value_op="max")
-    assert np.array_equal(st.export_series()[0], np.asarray(lens).astype(U64))          # the segment lengths, from the state
-    return st, window(st)
 
 
 def check_keys(engine, st, W, keep, win=(0, 0, 0), algos=("EWMA", "DBSCAN"), what="", params=None, snap=None, key_arg=None, emits=(True, False)):
@@ -173,7 +64,7 @@ def check_keys(engine, st, W, keep, win=(0, 0, 0), algos=("EWMA", "DBSCAN"), wha
             if emit_all:
                 assert got.n_rows == P2 or algo == "ARIMA", tag
             if algo != "ARIMA":
-                assert_rows(rows_of(got), oracle_rows(W, m, algo, emit_all, **kw), (tag, "oracle"))
+                assert_rows(rows_of(got), window_oracle_rows(W, m, algo, emit_all, **kw), (tag, "oracle"))
     return out
 
 
@@ -370,41 +261,6 @@ def drop_values(rng, n):
     return lo + (rng.integers(0, 1 << 62, size=n, dtype=np.uint64) & (lo - np.uint64(1)))
 
 
-def order_sensitive(v):
-    x = orc.u64_to_f64(v)
-    s = dro.pairwise_sum(x)
-    if s == np.cumsum(x)[-1]:
-        return False
-    sq = (s / x.size - x) ** 2
-    return dro.pairwise_sum(sq) != np.cumsum(sq)[-1]
-
-
-def drop_oracle_rows(W, nsigma=3.0, ms=3, emit_all=False):
-    """the rows tad_run(DROP) emits over W (tests/test_gpu_state_drop.py's oracle) -> (rows, keys without a result)"""
-    k, t, v = W
-    x = orc.u64_to_f64(v)
-    _, first, cnt = np.unique(k, return_index=True, return_counts=True)
-    sel, mean, std, verd = [], [], [], []
-    no_result = 0
-    for a, n in zip(first, cnt):
-        r = dro.drop_detection_series(x[a:a + n], nsigma, ms) if n >= 2 else None
-        if r is None:
-            no_result += 1
-            continue
-        mu, s, z = r
-        idx = np.flatnonzero(np.ones(n, bool) if emit_all else z) + a
-        sel.append(idx)
-        mean.append(np.full(idx.size, mu))
-        std.append(np.full(idx.size, s))
-        verd.append(z[idx - a])
-    cat = lambda parts, dt: np.concatenate(parts).astype(dt) if parts else np.zeros(0, dt)
-    sel = cat(sel, np.int64)
-    rows = {"key_id": k[sel], "flow_end_s": t[sel], "throughput": x[sel], "algo_calc": cat(mean, np.float64), "stddev": cat(std, np.float64)}
-    if emit_all:
-        rows["anomaly"] = cat(verd, np.uint8)
-    return rows, no_result
-
-
 def test_drop_state_keys_on_the_day_count_state(engine):
     """40 endpoints x 20 days (tests/test_gpu_state_drop.py's shape), values whose pairwise and sequential sums differ; even keys are
     ingress endpoints, odd keys egress ones"""
@@ -424,7 +280,7 @@ def test_drop_state_keys_on_the_day_count_state(engine):
     k = np.repeat(np.arange(K, dtype=U64), days)
     t = np.tile(D_BASE + DAY * np.arange(days, dtype=np.int64), K)
     v = np.concatenate(vals)
-    st = new_state(engine, K, history=False)
+    st = new_state(engine, K, SER | TIMES)
     engine.run_stream(st, k, t, v, agg_flow="svc", value_op="sum")
     W = window(st)
     assert np.array_equal(W[0], k) and np.array_equal(W[1], t) and np.array_equal(W[2], v)
@@ -600,7 +456,7 @@ def test_refusals(engine):
     with pytest.raises(TadError):
         engine.run_state_keys(plain, keep)
     plain.close()
-    nohist = new_state(engine, K, history=False)
+    nohist = new_state(engine, K, SER | TIMES)
     with pytest.raises(TadError):
         engine.run_state_keys(nohist, keep, algo="DBSCAN")
     assert engine.run_state_keys(nohist, keep, emit_all=True).n_rows == 0            # an empty state: no rows, no error

@@ -14,53 +14,10 @@ from oracle import stream_oracle as sorc
 from oracle import tad_oracle as orc
 from theia_amd import TadError, _capi
 from theia_amd.engine import DeviceArray
+from state_helpers import (ALL, HIST, SER, STATE_FIELDS, TIMES, T_BASE, U64, assert_counts, assert_rows, assert_same, expected_counts, new_state,
+                           rows_of, snapshot)
 
 pytestmark = pytest.mark.gpu
-
-T_BASE = 1660202814
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
-STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
-HIST, SER, TIMES = 1, 2, 8     # TAD_STATE_HISTORY, TAD_STATE_SERIES, TAD_STATE_TIMES
-ALL = HIST | SER | TIMES       # 11
-U64 = np.uint64
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
-
-
-def rows_of(res):
-    d = {f: np.asarray(res[f]) for f in ROW_FIELDS}
-    if "anomaly" in res.to_host():
-        d["anomaly"] = np.asarray(res["anomaly"])
-    return d
-
-
-def assert_rows(got, want, what=""):
-    assert set(got) == set(want), (what, sorted(got), sorted(want))
-    assert got["key_id"].size == want["key_id"].size, (what, got["key_id"].size, want["key_id"].size)
-    for f in want:
-        assert np.array_equal(bits(got[f]), bits(want[f])), (what, f)
-
-
-def new_state(engine, K, flags=ALL):
-    return engine.state_create(K, history=bool(flags & HIST), series=bool(flags & SER), times=bool(flags & TIMES))
-
-
-def snapshot(st):
-    return {"state": st.export(), "history": st.export_history() if st.history else None,
-            "series": st.export_series() if st.series else None, "times": st.export_times() if st.times and st.series_points() else None}
-
-
-def assert_same(a, b, what=""):
-    for f in STATE_FIELDS:
-        assert np.array_equal(bits(a["state"][f]), bits(b["state"][f])), (what, f)
-    for part in ("history", "series"):
-        if a[part] is not None and b[part] is not None:
-            assert np.array_equal(a[part][0], b[part][0]) and np.array_equal(a[part][1], b[part][1]), (what, part)
-    if a["times"] is not None or b["times"] is not None:
-        assert np.array_equal(a["times"], b["times"]), (what, "times")
 
 
 def cat(batches):
@@ -87,38 +44,6 @@ def r2_snapshot(K, flags, rows, op, alpha=0.5):
     hv = pv[np.lexsort((pv, pk))]
     return {"state": {f: getattr(os_, f) for f in STATE_FIELDS}, "history": (ln, hv) if flags & HIST else None, "series": (ln, pv),
             "times": pt if pk.size else None}
-
-
-def expected_counts(prev_rows, batch, op, keep_from=0):
-    """what the call's counters must say, from sets of (key, time) on the host"""
-    pk, pt, _ = orc.stage0(*prev_rows, op) if prev_rows[0].size else (np.zeros(0, U64), np.zeros(0, np.int64), None)
-    bk, bt, _ = orc.stage0(*batch, op)
-    old = set(zip(pk.tolist(), pt.tolist()))
-    last = {}
-    for k, t in zip(pk.tolist(), pt.tolist()):
-        last[k] = t                    # (key, time) order: the last one wins
-    c = {"batch_points": int(bk.size), "points_too_old": 0, "points_appended": 0, "points_inserted": 0, "points_combined": 0}
-    touched, replayed = set(), set()
-    for k, t in zip(bk.tolist(), bt.tolist()):
-        if keep_from and t < keep_from:
-            c["points_too_old"] += 1
-            continue
-        touched.add(k)
-        if (k, t) in old:
-            c["points_combined"] += 1
-            replayed.add(k)
-        elif k not in last or t > last[k]:
-            c["points_appended"] += 1
-        else:
-            c["points_inserted"] += 1
-            replayed.add(k)
-    c["keys_touched"], c["keys_replayed"] = len(touched), len(replayed)
-    return c
-
-
-def assert_counts(stats, want, what=""):
-    for f, v in want.items():
-        assert stats[f] == v, (what, f, stats[f], v)
 
 
 def check_run_state(engine, st, rows, op, algos=("EWMA", "DBSCAN"), emit=(False, True), what="", k2=None):

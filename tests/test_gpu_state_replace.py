@@ -18,42 +18,20 @@ from theia_amd.engine import DeviceArray
 
 import replace_model as rm
 import state_model as sm
-from test_gpu_state_merge import assert_counts, new_state
-from test_gpu_state_run import assert_rows, assert_same, bits, rows_of, snapshot
-from test_gpu_state_sequences import execute, run_check
+from state_drivers import T0, big, clone, execute_any, old_values, run_check, table_of
+from state_helpers import HIST, SER, TIMES, assert_counts, assert_rows, assert_same, bits, new_state, rows_of, snapshot
 
 pytestmark = pytest.mark.gpu
 
 U64, I64 = np.uint64, np.int64
-HIST, SER, TIMES = 1, 2, 8
-T0 = 1_700_000_000
 LENS = (0, 1, 2, 63, 64, 65, 2047, 2048, 2049, 4097)
-FIVE = np.array([(1 << 61) + 12345, (1 << 55) + 7, (1 << 58) + 999, (1 << 50) + 1, (1 << 60) + 31], U64)
 FIVE_SMALL = np.array([3, 1 << 20, 77, (1 << 33) + 5, 12], U64)      # below every value of FIVE: what a max must not keep
-
-
-def big(rng, n):
-    """n values of 50 to 62 significant bits"""
-    b = rng.integers(49, 62, size=n).astype(U64)
-    return (U64(1) << b) | (rng.integers(0, 1 << 62, size=n, dtype=U64) & ((U64(1) << b) - U64(1)))
-
-
-def old_values(rng, n, flags):
-    return FIVE[rng.integers(0, 5, size=n)] if flags & HIST else big(rng, n)
 
 
 def new_values(rng, n, flags, op):
     if op == "max":
         return FIVE_SMALL[rng.integers(0, 5, size=n)] if flags & HIST else rng.integers(1, 1 << 40, size=n).astype(U64)
     return old_values(rng, n, flags)
-
-
-def table_of(lens, rng, flags):
-    """point i of key j at T0 + 2 i"""
-    lens = np.asarray(lens, I64)
-    k = np.repeat(np.arange(lens.size, dtype=U64), lens)
-    i = np.concatenate([np.arange(n, dtype=I64) for n in lens]) if lens.sum() else np.zeros(0, I64)
-    return k, T0 + 2 * i, old_values(rng, k.size, flags)
 
 
 def loaded(engine, lens, flags, op, rng, alpha=0.0):
@@ -66,20 +44,6 @@ def loaded(engine, lens, flags, op, rng, alpha=0.0):
         model.append(*rows)
     assert_same(snapshot(st), model.expected_snapshot(), "loaded")
     return st, model
-
-
-def clone(engine, st, model, flags):
-    """a fresh state and a fresh model holding what (st, model) hold: the edge loops start every case from the same table"""
-    snap = snapshot(st)
-    fresh = new_state(engine, st.num_keys, flags)
-    fresh.load(snap["state"])
-    if snap["history"] is not None:
-        fresh.load_history(*snap["history"])
-    fresh.load_series(*snap["series"])
-    fresh.load_times(snap["times"] if snap["times"] is not None else np.zeros(0, I64))
-    m = rm.ReplaceModel(model.num_keys, model.flags, model.op, model.alpha)
-    m._set(*model.points())
-    return fresh, m
 
 
 def replace(engine, st, model, rows, from_t=0, to_t=0, ranged=False, keep_from=0, expect=None, tag="", twice=True, device=False, narrow=False):
@@ -403,18 +367,6 @@ def test_overlapping_re_read_polls_leave_the_table_each_row_once(engine, flags):
 
 
 # ---- sequences ----
-def execute_any(engine, st, sc, op):
-    if op["kind"] != "replace":
-        return execute(engine, st, sc, op)
-    cols = op["cols"]
-    k, t, v = op["k"], op["t"], op["v"]
-    if cols == "host4":
-        k, t = k.astype(np.uint32), t.astype(np.uint32)
-    elif cols == "device":
-        k, t, v = (DeviceArray.from_host(engine, a) for a in (k, t, v))
-    with engine.plan(**op["plan"]):
-        return st, {"stats": engine.replace_stream(st, k, t, v, from_t=op["from_t"], to_t=op["to_t"], ranged=op["ranged"], value_op=sc["op"],
-                                                   alpha=sc["alpha"], keep_from=op["keep_from"])}
 
 
 @pytest.mark.parametrize("seed", rm.SEEDS)

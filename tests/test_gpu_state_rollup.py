@@ -10,10 +10,9 @@ import pytest
 
 from theia_amd import TadEngine, TadError, _capi
 
-import rollup_model as R
-from rollup_model import HIST, SER, TIMES, I64, U64, RollupModel
-from test_gpu_state_buckets import EDGE_RUNS, EDGE_S, EDGE_T0, run_times, wide_values
-from test_gpu_state_keys import HIST_CHUNK, T_BASE, assert_same, bits, key_values, new_state, snapshot, window
+from rollup_model import SER, TIMES, I64, U64, RollupModel
+from state_drivers import build, roll
+from state_helpers import EDGE_RUNS, EDGE_S, EDGE_T0, HIST_CHUNK, T_BASE, assert_same, bits, key_values, new_state, run_times, snapshot, wide_values
 
 pytestmark = pytest.mark.gpu
 
@@ -21,41 +20,6 @@ INV = _capi.TAD_ERR_INVALID_ARGUMENT
 
 
 # ---- helpers ----
-def build(engine, K, k, t, v, op="sum", alpha=0.0, history=True, seed=1):
-    """a state of K keys fed the points (k, t, v), one row each, in a seeded order -> (state, its model)"""
-    k, t, v = np.asarray(k).astype(U64), np.asarray(t, I64), np.asarray(v).astype(U64)
-    st = new_state(engine, K, history)
-    if k.size:
-        o = np.random.default_rng(seed).permutation(k.size)
-        engine.run_stream(st, np.ascontiguousarray(k[o]), np.ascontiguousarray(t[o]), np.ascontiguousarray(v[o]), value_op=op, alpha=alpha)
-    m = RollupModel(K, SER | TIMES | (HIST if history else 0), op, alpha)
-    if k.size:
-        m._set(*window(st))
-    assert_same(snapshot(st), m.expected_snapshot(), "the state as built")
-    return st, m
-
-
-def assert_stats(got, want, what):
-    for f in R.STATS:
-        assert got[f] == want[f], (what, f, got[f], want[f], got, want)
-
-
-def roll(st, m, before, bucket_s, origin=0, op=None, what="", alpha=None, expected=None):
-    """the call on state and model, everything compared; then the same call again, which must change no bit -> the first call's stats"""
-    op = op or m.op
-    alpha = m.alpha if alpha is None else alpha
-    want = m.rollup(before, bucket_s, origin, op)
-    got = st.rollup(before, bucket_s, origin, op, alpha)
-    assert_stats(got, want, what)
-    assert got["points_after"] == st.series_points() == m.key.size, what
-    exp = expected() if expected else m.expected_snapshot()
-    snap = snapshot(st)
-    assert_same(snap, exp, (what, "state"))
-    again = st.rollup(before, bucket_s, origin, op, alpha)
-    assert_same(snapshot(st), snap, (what, "the second call changed a bit"))
-    assert again["keys_changed"] == 0 and again["points_before"] == again["points_after"] == got["points_after"], (what, again)
-    assert again["points_rolled"] == again["buckets"] == got["buckets"] and again["before_t"] == got["before_t"], (what, again)
-    return got
 
 
 LENS = (0, 1, 2, 63, 64, 65, 2047, 2048, 2049, 4096, 4097)
@@ -333,7 +297,7 @@ def test_a_workspace_limit_too_small_refuses_and_leaves_the_export_unchanged(eng
     snap = snapshot(big)
     big.close()
     small = TadEngine(device=engine.device, workspace_limit=1 << 20)
-    st = new_state(small, K, False)
+    st = new_state(small, K, SER | TIMES)
     st.load(snap["state"]), st.load_series(*snap["series"]), st.load_times(snap["times"])
     with pytest.raises(TadError) as ei:
         st.rollup(T_BASE + 60, 60)

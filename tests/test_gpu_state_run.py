@@ -3,7 +3,6 @@ with one row per series point the state holds; tad_run_state returns exactly the
 parameters and emit flag — key, time, throughput, algo_calc, stddev (and the verdicts with emit_all) in the same order, bit for bit —
 and leaves the state as it was.  Two references: (R1) the engine's own tad_run on W, W taken from export_series / export_times;
 (R2) oracle.tad_oracle.run_job on W, which is independent of the engine.  Float columns are compared as uint64 bit patterns."""
-import ctypes as C
 import threading
 
 import numpy as np
@@ -11,59 +10,10 @@ import pytest
 
 from oracle import tad_oracle as orc
 from theia_amd import TadError, _capi
+from state_helpers import (ALL, HIST, ROW_FIELDS, SER, TIMES, T_BASE, assert_rows, assert_same, bits, minute_batches, new_state, raw_run_state,
+                           rows_of, second_batches, snapshot, window)
 
 pytestmark = pytest.mark.gpu
-
-T_BASE = 1660202814
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
-STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
-HIST, SER, TIMES = 1, 2, 8     # TAD_STATE_HISTORY, TAD_STATE_SERIES, TAD_STATE_TIMES
-ALL = HIST | SER | TIMES       # 11
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
-
-
-def rows_of(res):
-    d = {f: np.asarray(res[f]) for f in ROW_FIELDS}
-    if "anomaly" in res.to_host():
-        d["anomaly"] = np.asarray(res["anomaly"])
-    return d
-
-
-def assert_rows(got, want, what=""):
-    assert set(got) == set(want), (what, sorted(got), sorted(want))
-    assert got["key_id"].size == want["key_id"].size, (what, got["key_id"].size, want["key_id"].size)
-    for f in want:
-        assert np.array_equal(bits(got[f]), bits(want[f])), (what, f)
-
-
-def new_state(engine, K, flags=ALL):
-    return engine.state_create(K, history=bool(flags & HIST), series=bool(flags & SER), times=bool(flags & TIMES))
-
-
-def snapshot(st):
-    return {"state": st.export(), "history": st.export_history() if st.history else None,
-            "series": st.export_series() if st.series else None, "times": st.export_times() if st.times and st.series_points() else None}
-
-
-def assert_same(a, b, what=""):
-    for f in STATE_FIELDS:
-        assert np.array_equal(bits(a["state"][f]), bits(b["state"][f])), (what, f)
-    for part in ("history", "series"):
-        if a[part] is not None or b[part] is not None:
-            assert np.array_equal(a[part][0], b[part][0]) and np.array_equal(a[part][1], b[part][1]), (what, part)
-    if a["times"] is not None or b["times"] is not None:
-        assert np.array_equal(a["times"], b["times"]), (what, "times")
-
-
-def window(st):
-    """W: one row per series point the state holds, (key, time, value) in (key, time) order"""
-    ln, vals = st.export_series()
-    keys = np.repeat(np.arange(st.num_keys, dtype=np.uint64), ln.astype(np.int64))
-    return keys, st.export_times(), vals
 
 
 def r1(engine, st, algo, emit_all=False, **kw):
@@ -102,35 +52,6 @@ def check_oracle(engine, st, algo, what="", **kw):
     assert_rows(rows_of(got), {f: want[f] for f in ROW_FIELDS}, (what, algo, "oracle"))
     assert got.stats["n_anomalies"] == want["n_anomalies"] and got.stats["n_keys"] == want["n_keys"] and got.stats["n_points"] == want["n_points"]
     return got, want
-
-
-def minute_batches(n_rows, K, T, cuts):
-    k, t, v = orc.synth_rows(0, n_rows, K, T)
-    bucket = (t - orc.SYNTH_T_BASE) // orc.SYNTH_T_STEP
-    edges = (0,) + tuple(cuts) + (T,)
-    return [(k[(bucket >= lo) & (bucket < hi)], t[(bucket >= lo) & (bucket < hi)], v[(bucket >= lo) & (bucket < hi)])
-            for lo, hi in zip(edges[:-1], edges[1:])]
-
-
-def second_batches(K, n_batches, width, pts_per_batch, seed, lifetimes=False):
-    """second-resolution rows (two per point) in batches of `width` seconds; every key has exactly pts_per_batch points in every batch
-    it is alive in.  lifetimes: a third of the keys only in the first half, a third only in the last batches, the rest throughout."""
-    rng = np.random.default_rng(seed)
-    out = []
-    base = 1_000_000_000 + (orc.mix64(np.arange(K, dtype=np.uint64) + np.uint64(5)) % np.uint64(3_000_000_000)).astype(np.int64)
-    for b in range(n_batches):
-        alive = np.ones(K, bool)
-        if lifetimes:
-            g = np.arange(K) % 3
-            alive = (g == 2) | ((g == 0) & (b < n_batches // 2)) | ((g == 1) & (b >= n_batches - 2))
-        ks = np.nonzero(alive)[0].astype(np.uint64)
-        pk = np.repeat(ks, pts_per_batch)
-        pt = np.concatenate([np.sort(rng.choice(width, pts_per_batch, replace=False)) for _ in ks]).astype(np.int64) + T_BASE + b * width
-        k, t = np.repeat(pk, 2), np.repeat(pt, 2)
-        v = (np.repeat(base[pk.astype(np.int64)], 2) + rng.integers(-300_000_000, 300_000_000, size=k.size)).astype(np.uint64)
-        order = rng.permutation(k.size)
-        out.append((k[order], t[order], v[order]))
-    return out
 
 
 # ---- 1. minute lattice, sum ----
@@ -363,15 +284,6 @@ def test_restart(engine):
 
 
 # ---- 8. rejections leave the state unchanged ----
-def raw_run_state(engine, st, **job):
-    j = _capi.Job(**job)
-    res = C.POINTER(_capi.Result)()
-    rc = engine._lib.tad_run_state(engine._h, st._h, C.byref(j), _capi.TAD_MEM_HOST, C.byref(res))
-    if rc == _capi.TAD_OK:
-        engine._lib.tad_result_free(engine._h, res)
-    else:
-        assert not res
-    return rc
 
 
 def test_rejections(engine):

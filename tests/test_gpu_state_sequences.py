@@ -19,116 +19,11 @@ expected snapshot and every oracle job take at most 0.8 s of a seed (seeds 3, 28
 import numpy as np
 import pytest
 
-from theia_amd import TadError
-from theia_amd.engine import DeviceArray
-
 import state_model as sm
-from test_gpu_state_merge import assert_counts, new_state
-from test_gpu_state_run import assert_rows, assert_same, bits, raw_run_state, rows_of, snapshot
+from state_drivers import COMPACT_FIELDS, execute, run_check
+from state_helpers import assert_counts, assert_rows, assert_same, bits, new_state, rows_of, snapshot
 
 pytestmark = pytest.mark.gpu
-
-COMPACT_FIELDS = ("keys_before", "keys_after", "num_keys", "keys_unseen", "keys_idle", "points_dropped")
-
-
-def columns(engine, op):
-    """the batch's columns as the script drew them: 8-byte host arrays, 4-byte key and time columns, or device arrays"""
-    k, t, v = op["k"], op["t"], op["v"]
-    if op["cols"] == "host4":
-        return k.astype(np.uint32), t.astype(np.uint32), v
-    if op["cols"] == "device":
-        return tuple(DeviceArray.from_host(engine, a) for a in (k, t, v))
-    return k, t, v
-
-
-def engine_params(algo, params):
-    if algo == "DROP":
-        return {"nsigma": params["nsigma"], "min_samples": params["drop_min_samples"]}
-    return dict(params)
-
-
-def stream_batch(engine, st, sc, op, algo, **kw):
-    k, t, v = columns(engine, op)
-    with engine.plan(**op["plan"]):
-        if algo == "DROP":
-            return engine.drop_stream(st, k, t, v, value_op=sc["op"], alpha=sc["alpha"], emit_all=op["emit_all"], **kw)
-        return engine.run_stream(st, k, t, v, value_op=sc["op"], alpha=sc["alpha"], algo=algo, emit_all=op["emit_all"], **kw)
-
-
-def restart(engine, st, flags):
-    """export every part, a fresh state, import: the host restarted"""
-    snap = snapshot(st)
-    fresh = new_state(engine, st.num_keys, flags)
-    fresh.load(snap["state"])
-    if snap["history"] is not None:
-        fresh.load_history(*snap["history"])
-    fresh.load_series(*snap["series"])
-    fresh.load_times(snap["times"] if snap["times"] is not None else np.zeros(0, np.int64))      # (a state without points exports no times)
-    st.close()
-    return fresh
-
-
-def refused_call(engine, st, sc, op):
-    variant = op["variant"]
-    if variant == "dbscan_stream_without_history":
-        stream_batch(engine, st, sc, op, "DBSCAN")
-    elif variant == "num_keys_differs":
-        stream_batch(engine, st, sc, op, "EWMA", num_keys=op["num_keys"])
-    elif variant == "run_state_dbscan_without_history":
-        engine.run_state(st, algo="DBSCAN")
-    elif variant == "from_after_to":
-        (engine.run_state_window if op["call"] == "window" else engine.drop_state)(st, *op["win"])
-    elif variant == "start_time_in_run_state":
-        engine._check(raw_run_state(engine, st, algo=0, start_time=op["start_time"]))
-    else:
-        raise ValueError(variant)
-
-
-def execute(engine, st, sc, op):
-    """one operation of a script on the state -> (the state, the call's own outputs in the form state_model.apply gives them)"""
-    kind = op["kind"]
-    if kind == "append":
-        return st, {"rows": rows_of(stream_batch(engine, st, sc, op, op["algo"], **engine_params(op["algo"], op["params"])))}
-    if kind in ("late", "refused"):
-        try:
-            if kind == "late":
-                stream_batch(engine, st, sc, op, op["algo"], **engine_params(op["algo"], op["params"]))
-            else:
-                refused_call(engine, st, sc, op)
-        except TadError:
-            return st, {"raises": True}
-        return st, {"raises": False}
-    if kind == "merge":
-        k, t, v = columns(engine, op)
-        with engine.plan(**op["plan"]):
-            return st, {"stats": engine.merge_stream(st, k, t, v, value_op=sc["op"], alpha=sc["alpha"], keep_from=op["keep_from"])}
-    if kind == "trim":
-        return st, {"dropped": st.trim(op["keep_points"], op["keep_from"], alpha=sc["alpha"])}
-    if kind == "compact":
-        remap, stats = st.compact(op["retire_before"])
-        return st, {"remap": remap, "stats": stats}
-    if kind == "resize":
-        st.resize(op["n"])
-        return st, {}
-    if kind == "restart":
-        return restart(engine, st, sc["flags"]), {}
-    raise ValueError(kind)
-
-
-def run_check(engine, st, check):
-    p = engine_params(check["algo"], check["params"])
-    call, win, emit_all = check["call"], check.get("win"), check["emit_all"]
-    if call == "run_state":
-        return engine.run_state(st, algo=check["algo"], emit_all=emit_all, **p)
-    if call == "window":
-        return engine.run_state_window(st, *win, algo=check["algo"], emit_all=emit_all, **p)
-    if call == "keys":
-        return engine.run_state_keys(st, check["mask"], *win, algo=check["algo"], emit_all=emit_all, **p)
-    if call == "drop_state":
-        return engine.drop_state(st, *win, emit_all=emit_all, **p)
-    if call == "drop_state_keys":
-        return engine.drop_state_keys(st, check["mask"], *win, emit_all=emit_all, **p)
-    raise ValueError(call)
 
 
 def replay(engine, seed, upto):

@@ -20,6 +20,7 @@ import pytest
 
 from oracle import stream_oracle as so
 from oracle import tad_oracle as orc
+from state_helpers import COOP_MIN_T, HIST_CHUNK, STATE_FIELDS, T_BASE, U64, assert_rows, assert_same, bits, in_window, new_state, rows_of, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -27,55 +28,12 @@ pytestmark = pytest.mark.gpu
 SORT_WAVE = 64                # tad_history.hip:48   k_hist_sort_wave: `if (b > 64)` lists the key for k_hist_sort_long
 HIST_LDS = 4096               # tad_history.hip:25   kHistLdsPoints
 SORT_LONG_GRID = 2048         # tad_history.hip:251  launch_hist_sort: min(K, 2048) workgroups of k_hist_sort_long
-HIST_CHUNK = 2048             # tad_internal.h:324   kHistChunk
 WALK_CHUNK = 8                # tad_history.hip:400  kTrimChunk; tad_window.hip:32 kWinChunk
-COOP_MIN_T = 512              # tad_internal.h:184   kCoopMinT
 COOP_MAX_K = 8192             # tad_internal.h:184   kCoopMaxK
 SCAN_OWN_BASE = 4096 * 2048   # tad_kernels.hip:527  kScanOwnBaseBlocks x tad_kernels.hip:468 kScanTile
 
-T_BASE = 1660202814
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
-STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
-U64 = np.uint64
 EPS = 1 << 24                 # the DBSCAN eps of the crafted cases: an integer, every distance below 2^53 is exact
 ALPHA = 0.3                   # (the default 0.5 cannot see a wrong recurrence)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
-
-
-def rows_of(res):
-    d = {f: np.asarray(res[f]) for f in ROW_FIELDS}
-    if "anomaly" in res.to_host():
-        d["anomaly"] = np.asarray(res["anomaly"])
-    return d
-
-
-def assert_rows(got, want, what=""):
-    assert set(got) == set(want), (what, sorted(got), sorted(want))
-    assert got["key_id"].size == want["key_id"].size, (what, got["key_id"].size, want["key_id"].size)
-    for f in want:
-        assert np.array_equal(bits(got[f]), bits(want[f])), (what, f)
-
-
-def new_state(engine, K):
-    return engine.state_create(K, history=True, series=True, times=True)
-
-
-def snapshot(st):
-    return {"state": st.export(), "history": st.export_history(), "series": st.export_series(),
-            "times": st.export_times() if st.series_points() else None}
-
-
-def assert_same(a, b, what=""):
-    for f in STATE_FIELDS:
-        assert np.array_equal(bits(a["state"][f]), bits(b["state"][f])), (what, f)
-    for part in ("history", "series"):
-        assert np.array_equal(a[part][0], b[part][0]) and np.array_equal(a[part][1], b[part][1]), (what, part)
-    if a["times"] is not None or b["times"] is not None:
-        assert np.array_equal(a["times"], b["times"]), (what, "times")
 
 
 def clone(engine, K, snap):
@@ -471,17 +429,6 @@ WINDOWS = [("first to 2048th, exclusive", 0, 2047, 0), ("2048th and 2049th", 204
           [("last element of %d" % L, L - 1, L, 0) for L in CHUNK_LENS if L not in (2048, 2049)]
 
 
-def in_window(W, lo, hi, keep):
-    k, t, _ = W
-    m = (t >= T_BASE + lo) & (t < T_BASE + hi)
-    if keep:
-        idx = np.flatnonzero(m)
-        kk = k[idx]
-        from_end = np.searchsorted(kk, kk, side="right") - np.arange(kk.size)
-        m[idx[from_end > keep]] = False
-    return m
-
-
 def test_window_ranges_at_every_chunk_edge(engine):
     """k_win_bounds / k_win_gather / k_hist_subtract<true> / the window moments with the interior range beginning, ending and lying
     wholly inside any chunk.  The window's history is sorted from the window when 2 * window points <= state points and subtracted
@@ -497,7 +444,7 @@ def test_window_ranges_at_every_chunk_edge(engine):
         snap = snapshot(st)
         wins = WINDOWS + ([] if ballast else [("the whole state", None, None, 0)])
         for name, lo, hi, keep in wins:
-            m = np.ones(S, bool) if lo is None else in_window(W, lo, hi, keep)
+            m = np.ones(S, bool) if lo is None else in_window(W[0], W[1], T_BASE + lo, T_BASE + hi, keep)
             Pw = int(m.sum())
             args = (0, 0, 0) if lo is None else (T_BASE + lo, T_BASE + hi, keep)
             by_sort = 2 * Pw <= S

@@ -11,13 +11,11 @@ import pytest
 
 from theia_amd import TadError, _capi
 from theia_amd.engine import DeviceArray
-
-from test_gpu_state_drop import oracle_rows as drop_oracle_rows
-from test_gpu_state_keys import T_BASE, U64, assert_rows, assert_same, in_window, make_state, new_state, oracle_rows, rows_of, snapshot, window
+from state_helpers import (I64, SER, TIMES, T_BASE, U64, assert_rows, assert_same, drop_oracle_rows, in_window, make_state, new_state, rows_of,
+                           snapshot, window, window_oracle_rows)
 
 pytestmark = pytest.mark.gpu
 
-I64 = np.int64
 NO_CHANGE = _capi.TAD_NO_CHANGE
 ALGOS = ("EWMA", "DBSCAN", "DROP")
 
@@ -94,7 +92,7 @@ def check_since(engine, st, W, since_t=0, key_since=None, keep=None, win=(0, 0, 
                 assert_rows(rows_of(got), orows, (tag, "oracle"))
                 assert gs["keys_no_result"] == no_result, (tag, gs["keys_no_result"], no_result)
             elif algo in ("EWMA", "DBSCAN") and judged.any():
-                o = oracle_rows((jk, jt, jv), np.ones(jk.size, bool), algo, emit_all, **kw)
+                o = window_oracle_rows((jk, jt, jv), np.ones(jk.size, bool), algo, emit_all, **kw)
                 osel = reported_mask(o["key_id"], o["flow_end_s"], since_t, key_since)
                 assert_rows(rows_of(got), {f: a[osel] for f, a in o.items()}, (tag, "oracle"))
             out[(algo, emit_all)] = got
@@ -267,7 +265,7 @@ def test_arima_reports_the_suffix_and_runs_the_suffixes_fits_only(engine):
     rng = np.random.default_rng(11)
     lens, k, t, v, plain = arima_table(rng)
     K = len(lens)
-    st = new_state(engine, K, history=False)
+    st = new_state(engine, K, SER | TIMES)
     engine.run_stream(st, k, t, v, value_op="max")
     W = window(st)
     snap = snapshot(st)

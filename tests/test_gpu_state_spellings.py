@@ -10,12 +10,11 @@ import pytest
 
 from theia_amd import _capi
 from theia_amd.engine import DeviceArray
+from state_helpers import T_BASE, bits, rows_of
 
 pytestmark = pytest.mark.gpu
 
-T_BASE = 1660202814
 LENS = (20, 30, 25, 40, 600)
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
 ALGOS = ("EWMA", "DBSCAN", "ARIMA", "DROP")
 RUN_CALLS = ("tad_run_state", "tad_run_state_window", "tad_run_state_keys")
 DROP_CALLS = ("tad_drop_state", "tad_drop_state_keys")
@@ -39,18 +38,6 @@ REFUSALS = {
     ("tad_drop_state_keys", "family"): b"tad_drop_state_keys: the algorithm must be DROP (tad_run_state_keys judges EWMA, DBSCAN and ARIMA)",
     ("tad_drop_state_keys", "from_t"): b"tad_drop_state_keys: from_t is later than to_t",
 }
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
-
-
-def rows_of(res):
-    d = {f: np.asarray(res[f]) for f in ROW_FIELDS}
-    if "anomaly" in res.to_host():
-        d["anomaly"] = np.asarray(res["anomaly"])
-    return d
 
 
 def assert_same_answer(got, want, syncs, what):

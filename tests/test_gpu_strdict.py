@@ -10,31 +10,12 @@ import pytest
 
 from theia_amd import TadEngine, TadError, _capi as capi
 from theia_amd.engine import DeviceArray
+from job_helpers import STAGE, column, device_column, exported, hash8, host
 
 pytestmark = pytest.mark.gpu
 
 LENGTHS = (0, 1, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 255, 256, 257)
 ROWS = (1, 63, 64, 65, 255, 256, 257, 511, 513, 4097)
-STAGE = 24 * 1024          # kSeStage: a block of 256 rows whose bytes span more than this reads them lane by lane
-
-
-def column(strings, bits=32):
-    """a list of bytes -> (offsets, data) in Arrow's layout"""
-    off = np.zeros(len(strings) + 1, dtype=np.int32 if bits == 32 else np.int64)
-    np.cumsum([len(s) for s in strings], out=off[1:])
-    return off, np.frombuffer(b"".join(strings), dtype=np.uint8).copy()
-
-
-def device_column(engine, strings, bits=32, shift=0, validity=None, validity_offset=0):
-    """the column in device memory, its bytes a slice starting `shift` bytes into an allocation; validity: one bool per row"""
-    off, data = column(strings, bits)
-    big = DeviceArray.from_host(engine, np.concatenate([np.full(shift, 0xEE, np.uint8), data, np.full(16, 0xEE, np.uint8)]))
-    assert big.ptr % 16 == 0
-    col = [DeviceArray.from_host(engine, off), big.view(shift, data.size, np.uint8)]
-    if validity is not None:
-        bits_ = np.concatenate([np.ones(validity_offset, bool), np.asarray(validity, bool)])      # (the bits in front belong to other rows)
-        col += [DeviceArray.from_host(engine, np.packbits(bits_, bitorder="little")), validity_offset]
-    return tuple(col)
 
 
 class Oracle:
@@ -61,22 +42,11 @@ class Oracle:
         return sorted(self.ids, key=self.ids.get)
 
 
-def host(x):
-    return x.to_host() if isinstance(x, DeviceArray) else np.asarray(x)
-
-
-def exported(d, first=0, n=None):
-    off, data = d.export(first, n)
-    assert off[0] == 0 and off.size >= 1
-    raw = data.tobytes()
-    return [raw[off[i]:off[i + 1]] for i in range(off.size - 1)]
-
-
-def snapshot(d):
+def strdict_snapshot(d):
     return d.num_values(), exported(d)
 
 
-def assert_unchanged(d, snap):
+def assert_strdict_unchanged(d, snap):
     assert (d.num_values(), exported(d)) == snap
 
 
@@ -268,20 +238,6 @@ def test_many_rows_of_three_values(engine):
     d.close()
 
 
-def _mix(x):
-    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return x ^ (x >> np.uint64(31))
-
-
-def hash8(words):
-    """se_hash (tad_strbytes.h) of 8-byte strings given as little-endian uint64 words"""
-    with np.errstate(over="ignore"):
-        h = np.uint64(0x9E3779B97F4A7C15) ^ np.uint64(8)
-        h = _mix(h ^ words) + np.uint64(0x632BE59BD9B4E019)
-        return _mix(h)
-
-
 def test_two_strings_with_one_fingerprint_are_two_values(engine):
     """Among 4e5 8-byte strings the expected number of pairs whose hashes share the high 32 bits — the slot's fingerprint — is
     N (N - 1) / 2 / 2^32 = 18.6; the probability of none is e^-18.6.  Such a pair is told apart by the bytes alone.  Whether the two probe
@@ -314,12 +270,12 @@ def test_lookup_and_an_empty_batch_change_nothing(engine):
     assert d.encode(column([]))[2] == 0 and d.num_values() == 0
     assert np.array_equal(d.lookup(column([b"x", b""])), [-1, -1])
     d.encode(column([b"x", b"y"]))
-    snap = snapshot(d)
+    snap = strdict_snapshot(d)
     assert np.array_equal(d.lookup(column([b"y", b"z", b"x", b""])), [1, -1, 0, -1])
     assert np.array_equal(d.lookup(device_column(engine, [b"y", b"z", b"x"], 64, 3), out="device").to_host(), [1, -1, 0])
     codes, first, before = d.encode(column([]))
     assert codes.size == 0 and first.size == 0 and before == 2
-    assert_unchanged(d, snap)
+    assert_strdict_unchanged(d, snap)
     d.close()
 
 
@@ -348,21 +304,21 @@ def raw_encode(engine, d, off, data, data_bytes=None, bits=32):
 def test_malformed_offsets_are_refused_before_the_dictionary_is_touched(engine):
     d = engine.string_dict(1, 1)
     d.encode(column([b"held", b"too"]))
-    snap = snapshot(d)
+    snap = strdict_snapshot(d)
     strings = [b"new-%d" % i for i in range(600)]
     off, data = column(strings)
     bad = off.copy()
     bad[500] = bad[499] - 2                                                      # decreases, behind 499 rows of new strings
     assert raw_encode(engine, d, bad, data)[0] == capi.TAD_ERR_INVALID_ARGUMENT
-    assert_unchanged(d, snap)
+    assert_strdict_unchanged(d, snap)
     bad = off.copy()
     bad[-1] += 40                                                                # points beyond data_bytes
     assert raw_encode(engine, d, bad, data)[0] == capi.TAD_ERR_INVALID_ARGUMENT
-    assert_unchanged(d, snap)
+    assert_strdict_unchanged(d, snap)
     assert raw_encode(engine, d, off, data, data_bytes=data.size - 1)[0] == capi.TAD_ERR_INVALID_ARGUMENT
-    assert_unchanged(d, snap)
+    assert_strdict_unchanged(d, snap)
     assert raw_encode(engine, d, off.astype(np.int64), data, bits=16)[0] == capi.TAD_ERR_INVALID_ARGUMENT
-    assert_unchanged(d, snap)
+    assert_strdict_unchanged(d, snap)
     with pytest.raises(TadError) as ei:
         d.lookup((bad, data))
     assert ei.value.code == capi.TAD_ERR_INVALID_ARGUMENT
@@ -382,16 +338,16 @@ def test_workspace_limit_refuses_a_big_batch_and_leaves_the_dictionary_unchanged
         first = [b"k%d" % i for i in range(1000)]
         codes, _, before = d.encode(device_column(small, first), out="device")
         assert before == 0 and np.array_equal(codes.to_host(), np.arange(1000)) and d.num_values() == 1000
-        snap = snapshot(d)
+        snap = strdict_snapshot(d)
         big = device_column(small, [b"n%d" % i for i in range(100_000)])
         with pytest.raises(TadError) as ei:
             d.encode(big, out="device")
         assert ei.value.code == capi.TAD_ERR_GRID_TOO_LARGE
-        assert_unchanged(d, snap)
+        assert_strdict_unchanged(d, snap)
         known = device_column(small, [b"k%d" % (i % 1000) for i in range(100_000)])
         codes, fr, before = d.encode(known, out="device")
         assert before == 1000 and fr.n == 0 and np.array_equal(codes.to_host(), np.arange(100_000) % 1000)
-        assert_unchanged(d, snap)
+        assert_strdict_unchanged(d, snap)
         d.close()
     finally:
         small.close()
@@ -431,11 +387,11 @@ def test_import_restores_the_codes_and_refuses_what_it_must(engine):
     codes, first, before = r.encode(column(probe))
     want = np.array([vocab.index(s) for s in probe[:-1]] + [len(vocab)])
     assert before == len(vocab) and np.array_equal(codes, want) and np.array_equal(first, [len(probe) - 1])
-    snap = snapshot(r)
+    snap = strdict_snapshot(r)
     with pytest.raises(TadError) as ei:                                          # it already holds values
         r.load(saved)
     assert ei.value.code == capi.TAD_ERR_INVALID_ARGUMENT
-    assert_unchanged(r, snap)
+    assert_strdict_unchanged(r, snap)
     e = engine.string_dict(1, 1)
     for bad in ([b"a", b"b", b"a"], [b"", b"x", b""], [b"a\0", b"a", b"a\0"]):       # two strings are equal
         with pytest.raises(TadError) as ei:
@@ -491,7 +447,7 @@ def test_match_equal_and_contains_without_case(engine):
     assert n_sel == 40 and np.array_equal(keep.to_host(), match_oracle(vocab, 1, b"frontend")[::-1])
     kd.close()
     # refusals: a pattern over 1024 bytes, an unknown op, a stale mask length — nothing is written
-    snap = snapshot(d)
+    snap = strdict_snapshot(d)
     for op, pat in ((capi.TAD_STR_EQUAL, b"p" * 1025), (2, b"p"), (-1, b"p")):
         with pytest.raises(TadError) as ei:
             d.match(op, pat)
@@ -502,7 +458,7 @@ def test_match_equal_and_contains_without_case(engine):
     for n in (len(vocab) - 1, len(vocab) + 1, 0):
         rc = engine._lib.tad_strdict_match(engine._h, d._h, 0, C.cast(p, C.c_void_p), 1, stale.ctypes.data, n, capi.TAD_MEM_HOST, C.byref(hit))
         assert rc == capi.TAD_ERR_INVALID_ARGUMENT and (stale == 9).all() and hit.value == 77
-    assert_unchanged(d, snap)
+    assert_strdict_unchanged(d, snap)
     empty = engine.string_dict(1, 1)
     mask, hit = empty.match(capi.TAD_STR_CONTAINS_NOCASE, b"")
     assert mask.size == 0 and hit == 0

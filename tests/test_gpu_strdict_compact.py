@@ -14,10 +14,10 @@ import pytest
 
 from theia_amd import TadEngine, TadError, _capi as capi
 from theia_amd.engine import DeviceArray
+from job_helpers import ROOT, column, exported, hash8, host
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LENGTHS = (15, 16, 17, 31, 32, 33, 127, 128, 129)      # (0 and 1 are placed by hand: few strings are that short)
 
 
@@ -39,22 +39,6 @@ COUNTS = [1, 2, 63, 64, 65, BLOCK - 1, BLOCK, BLOCK + 1, SCAN_TILE - 1, SCAN_TIL
 def test_the_shapes_sit_on_the_kernels_edges():
     assert BLOCK == 256 and SCAN_TILE == 2048
     assert COUNTS == [1, 2, 63, 64, 65, 255, 256, 257, 2047, 2048, 2049, 4097]
-
-
-def column(strings):
-    off = np.zeros(len(strings) + 1, dtype=np.int64)
-    np.cumsum([len(s) for s in strings], out=off[1:])
-    return off, np.frombuffer(b"".join(strings), dtype=np.uint8).copy()
-
-
-def host(x):
-    return x.to_host() if isinstance(x, DeviceArray) else np.asarray(x)
-
-
-def exported(d):
-    off, data = d.export()
-    raw = data.tobytes()
-    return [raw[off[i]:off[i + 1]] for i in range(off.size - 1)]
 
 
 def up16(n):
@@ -104,7 +88,7 @@ def filled(engine, values, batch=None):
     d = engine.string_dict(1, 1)
     step = batch or max(len(values), 1)
     for i in range(0, len(values), step):
-        codes = d.encode(column(values[i:i + step]))[0]
+        codes = d.encode(column(values[i:i + step], 64))[0]
         assert np.array_equal(codes, np.arange(i, min(i + step, len(values))))
     return d
 
@@ -134,8 +118,8 @@ def check_compact(engine, d, values, keep, keep_arg=None, out="host", extra=None
         assert st["bytes_after"] == st["bytes_before"]                       # nothing retired: nothing reallocated
     # lookup of every old value: the new code, or TAD_CODE_NONE
     if values:
-        assert np.array_equal(d.lookup(column(values)), want_remap)
-        assert np.array_equal(fresh.lookup(column(values)), want_remap)
+        assert np.array_equal(d.lookup(column(values, 64)), want_remap)
+        assert np.array_equal(fresh.lookup(column(values, 64)), want_remap)
     # decode of a shuffled code list
     if m:
         codes = np.random.default_rng(m).integers(0, m, min(3 * m + 1, 3000)).astype(np.int64)
@@ -157,7 +141,7 @@ def check_compact(engine, d, values, keep, keep_arg=None, out="host", extra=None
     for v in batch:
         want_codes.append(seen.setdefault(v, len(seen)))
     if batch:
-        got, ref = d.encode(column(batch)), fresh.encode(column(batch))
+        got, ref = d.encode(column(batch, 64)), fresh.encode(column(batch, 64))
         assert np.array_equal(got[0], want_codes) and np.array_equal(ref[0], want_codes)
         assert np.array_equal(got[1], ref[1]) and got[2] == ref[2] == m
         assert exported(d) == sorted(seen, key=seen.get) == exported(fresh)
@@ -256,20 +240,6 @@ def test_a_tile_of_256_survivors_far_larger_than_any_stage(engine):
     d.close()
 
 
-def _mix(x):
-    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return x ^ (x >> np.uint64(31))
-
-
-def hash8(words):
-    """se_hash (tad_strbytes.h) of 8-byte strings given as little-endian uint64 words"""
-    with np.errstate(over="ignore"):
-        h = np.uint64(0x9E3779B97F4A7C15) ^ np.uint64(8)
-        h = _mix(h ^ words) + np.uint64(0x632BE59BD9B4E019)
-        return _mix(h)
-
-
 @pytest.fixture(scope="module")
 def fingerprint_pair():
     """two 8-byte strings whose hashes share the high 32 bits, the slot's fingerprint (among 4e5 strings 18.6 such pairs are expected)"""
@@ -314,7 +284,7 @@ def test_a_dictionary_that_grew_shrinks_and_grows_again(engine):
     d2.close()
     # later growth works again: records, arena and table all pass their new capacity
     more = [b"later-%d" % i for i in range(5000)]
-    codes, first, nb = d.encode(column(more + held[:50]))
+    codes, first, nb = d.encode(column(more + held[:50], 64))
     assert nb == len(held) and np.array_equal(codes, np.concatenate([len(held) + np.arange(5000), np.arange(50)]))
     assert exported(d) == held + more
     d.close()
@@ -407,6 +377,6 @@ def test_twice_in_a_row_then_an_import_into_the_emptied_dictionary(engine):
     assert remap.size == 0 and st["values_before"] == 0 and d.nbytes() == 64 * 8 + 32 * 16 + 16
     again = [b"imported-%d" % i for i in range(500)]
     d.load(again)
-    assert exported(d) == again and np.array_equal(d.lookup(column(again[::-1])), np.arange(500)[::-1])
+    assert exported(d) == again and np.array_equal(d.lookup(column(again[::-1], 64)), np.arange(500)[::-1])
     check_compact(engine, d, again, keep_pattern("one64th", 500))
     d.close()

@@ -13,25 +13,19 @@ import pytest
 
 import like_ref
 from theia_amd import TadError, _capi as capi
+from job_helpers import ROOT, column
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LENGTHS = (0, 1, 7, 8, 9, 15, 16, 17, 31, 32, 33, 255, 256, 257)
 COUNTS = (1, 63, 64, 65, 255, 256, 257)
-
-
-def column(strings):
-    off = np.zeros(len(strings) + 1, dtype=np.int64)
-    np.cumsum([len(s) for s in strings], out=off[1:])
-    return off, np.frombuffer(b"".join(strings), dtype=np.uint8).copy()
 
 
 def held(engine, values):
     """a dictionary whose value c is values[c] (distinct byte strings)"""
     assert len(set(values)) == len(values)
     d = engine.string_dict(1, 1)
-    codes = d.encode(column(values))[0]
+    codes = d.encode(column(values, 64))[0]
     assert np.array_equal(codes, np.arange(len(values)))
     return d
 
@@ -172,11 +166,11 @@ def test_after_growth_and_after_compact(engine):
     first, second = [label(i) for i in range(300)], [label(i) + b"x" * int(rng.integers(1, 200)) for i in range(300, 5000)]
     d = engine.string_dict(1, 1)
     patterns = ('%"test_key":"v3"%', "%test\\_key%", "%app%d_\"%", "{%}", '%"n":"4__"%')
-    d.encode(column(first))
+    d.encode(column(first, 64))
     before = d.nbytes()
     for p in patterns:
         check(d, first, p)
-    d.encode(column(second))
+    d.encode(column(second, 64))
     assert d.nbytes() > before and d.num_values() == 5000      # table, records and arena grew
     values = first + second
     for p in patterns:

@@ -16,53 +16,15 @@ from oracle import drop_oracle as dro
 from theia_amd import TadError
 from theia_amd import anomaly_detection as ad
 from theia_amd.drop_detection import PeriodicalDropDetection, drop_detection_table
-from theia_amd.stream_detection import StreamingAnomalyDetection, _KeyColumn, _KeyDecoder
+from theia_amd.stream_detection import StreamingAnomalyDetection
 
 import drop_query_ref as dq
-from test_gpu_drop_select import N_DAYS, counts_of, flows, keyed  # noqa: F401  (flows: the module's fixture, 40 endpoints x 20 days of flow rows)
-from test_gpu_drop_select import T0 as DAY0
-from test_gpu_stream_detection import IGNORE, STEP, T0, comparable
-from test_gpu_stream_replace import LAG, MODES, TableClient, table, turns  # noqa: F401  (table: the module's fixture)
+from stream_helpers import (DAY0, IGNORE, LAG, MODES, N_DAYS, STEP, T0, TableClient, changed_since, comparable, counts_of, flows, held, key_tuples,
+                            keyed, replace_table, turns)  # noqa: F401  (table: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
 FILTERS = {("svc", "labels"): dict(svc_port_name="shop/web:http"), ("pod", "labels"): dict(pod_label="web"), ("pod", "name"): dict(pod_name="web-0")}
-
-
-def held(s):
-    """-> {key id: {time: value}} of everything the instance's state holds"""
-    if s.state is None:
-        return {}
-    ln, vals = s.state.export_series()
-    times = s.state.export_times() if vals.size else np.zeros(0, np.int64)
-    out, at = {}, 0
-    for k, n in enumerate(ln.astype(np.int64).tolist()):
-        out[k] = dict(zip(times[at:at + n].tolist(), vals[at:at + n].tolist()))
-        at += n
-    return out
-
-
-def changed_since(before, after):
-    """{key id: the smallest time at which the key's points differ}"""
-    out = {}
-    for k, pts in after.items():
-        old = before.get(k, {})
-        ts = [t for t in set(pts) | set(old) if pts.get(t) != old.get(t)]
-        if ts:
-            out[k] = min(ts)
-    return out
-
-
-def key_tuples(s):
-    """key id -> the key's tuple in the mode's result columns"""
-    decoder = _KeyDecoder(s._dict, s._vocab)
-    cols = [np.asarray(_KeyColumn(decoder, "direction" if name == "direction" else i)) for i, name in enumerate(ad.KEY_COLUMNS[s.mode])]
-    for i, name in enumerate(ad.KEY_COLUMNS[s.mode]):
-        if name == "podLabels":      # (the result rows carry the canonical labels; the table's pods stay distinct under it)
-            cols[i] = np.asarray([ad.remove_meaningless_labels(v) for v in cols[i]], dtype=object)
-    tuples = [tuple(str(c[k]) for c in cols) for k in range(s.num_keys)]
-    assert len(set(tuples)) == len(tuples)
-    return tuples
 
 
 def expected_alerts(s, algo, filt, since):

@@ -11,46 +11,9 @@ import pytest
 from oracle import arima_oracle as ao
 from oracle import tad_oracle as orc
 from theia_amd import TadEngine, TadError
+from state_helpers import STATE_FIELDS, T_BASE, assert_rows, assert_same, bits, minute_batches, point_codes, restrict, rows_of, snapshot
 
 pytestmark = pytest.mark.gpu
-
-T_BASE = 1660202814
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
-STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
-SKIP = np.uint64((1 << 64) - 1)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
-
-
-def rows_of(res):
-    d = {f: np.asarray(res[f]) for f in ROW_FIELDS}
-    if "anomaly" in res.to_host():
-        d["anomaly"] = np.asarray(res["anomaly"])
-    return d
-
-
-def point_codes(k, t, k2=None):
-    """(key, time) of the batch's points as one uint64 code (key << 32 | t - T_BASE + 2^31)"""
-    ks = [np.asarray(k, np.uint64)] + ([np.asarray(k2, np.uint64)] if k2 is not None else [])
-    tt = (np.asarray(t, np.int64) - T_BASE + (1 << 31)).astype(np.uint64)
-    out = [(kk[kk != SKIP] << np.uint64(32)) | tt[kk != SKIP] for kk in ks]
-    return np.unique(np.concatenate(out))
-
-
-def restrict(rows, codes):
-    c = (rows["key_id"].astype(np.uint64) << np.uint64(32)) | (rows["flow_end_s"].astype(np.int64) - T_BASE + (1 << 31)).astype(np.uint64)
-    sel = np.isin(c, codes)
-    return {f: a[sel] for f, a in rows.items()}
-
-
-def assert_rows(got, want, what=""):
-    assert set(got) == set(want), (what, sorted(got), sorted(want))
-    assert got["key_id"].size == want["key_id"].size, (what, got["key_id"].size, want["key_id"].size)
-    for f in want:
-        assert np.array_equal(bits(got[f]), bits(want[f])), (what, f)
 
 
 def concat(batches, upto):
@@ -67,18 +30,6 @@ def job_rows(engine, K, batches, upto, op="auto", emit_all=False, pod=False, max
     return (rows, res.stats) if stats else rows
 
 
-def minute_batches(n_rows, K, T, cuts, pod=False):
-    k, t, v = orc.synth_rows(0, n_rows, K, T)
-    bucket = (t - orc.SYNTH_T_BASE) // orc.SYNTH_T_STEP
-    edges = (0,) + tuple(cuts) + (T,)
-    k2 = ((k + np.uint64(7)) % np.uint64(K)).astype(np.uint64)
-    out = []
-    for lo, hi in zip(edges[:-1], edges[1:]):
-        sel = (bucket >= lo) & (bucket < hi)
-        out.append((k[sel], t[sel], v[sel]) + ((k2[sel],) if pod else ()))
-    return out
-
-
 def second_batches(K, pts_per_key, rows_per_point, seed, span, width):
     rng = np.random.default_rng(seed)
     pts = np.broadcast_to(np.asarray(pts_per_key, dtype=np.int64), (K,))
@@ -91,19 +42,6 @@ def second_batches(K, pts_per_key, rows_per_point, seed, span, width):
     k, t, v = k[order], t[order], v[order]
     b = (t - T_BASE) // width
     return [(k[b == h], t[b == h], v[b == h]) for h in range(int(b.max()) + 1)]
-
-
-def snapshot(st):
-    return st.export(), st.export_history() if st.history else None, st.export_series() if st.series else None
-
-
-def assert_unchanged(st, snap):
-    s, h, r = snapshot(st)
-    for f in STATE_FIELDS:
-        assert np.array_equal(bits(s[f]), bits(snap[0][f])), f
-    for a, b in ((h, snap[1]), (r, snap[2])):
-        if a is not None:
-            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
 def assert_series(engine, st, K, batches, upto, op="auto", pod=False):
@@ -310,7 +248,7 @@ def test_restart_and_growth(engine):
     with pytest.raises(TadError) as ei:
         fresh.load_series(bad, vals[:-1])
     assert ei.value.code == -1
-    assert_unchanged(fresh, snap)
+    assert_same(snapshot(fresh), snap, "the state changed")
     hist_only = engine.state_create(K, history=True)
     hist_only.load(moments)
     with pytest.raises(TadError) as ei:
@@ -389,7 +327,7 @@ def test_rejections(engine):
         with pytest.raises(TadError) as ei:
             engine.run_stream(st, *batches[1], agg_flow="svc", algo="ARIMA")
         assert ei.value.code == -1
-        assert_unchanged(st, snap)
+        assert_same(snapshot(st), snap, "the state changed")
         with pytest.raises(TadError):
             st.export_series()
         assert st.series_points() == 0
@@ -401,11 +339,11 @@ def test_rejections(engine):
     with pytest.raises(TadError) as ei:
         engine.run_stream(st, *batches[1], agg_flow="svc", algo="DROP")
     assert ei.value.code == -1
-    assert_unchanged(st, snap)
+    assert_same(snapshot(st), snap, "the state changed")
     with pytest.raises(TadError) as ei:                                      # a late row (batch 0 again)
         engine.run_stream(st, *batches[0], agg_flow="svc", algo="ARIMA")
     assert ei.value.code == -1
-    assert_unchanged(st, snap)
+    assert_same(snapshot(st), snap, "the state changed")
     got = engine.run_stream(st, *batches[1], agg_flow="svc", algo="ARIMA", emit_all=True)   # the state goes on as if nothing had happened
     assert_rows(rows_of(got), job_rows(engine, K, batches, 1, "sum", emit_all=True))
     st.close()

@@ -11,44 +11,12 @@ import pytest
 
 from theia_amd import anomaly_detection as ad
 from theia_amd.stream_detection import StreamingAnomalyDetection
-
-from test_gpu_stream_alerts import changed_since, held, key_tuples
-from test_gpu_stream_detection import IGNORE, IPS, SVCS, T0, batches, comparable, pods
-from test_gpu_stream_replace import TableClient
+from stream_helpers import BUCKET, IGNORE, SPAN, T0, TableClient, batches, changed_since, comparable, held, key_tuples, seconds_table  # noqa: F401  (seconds_table: the fixture `table`)
 
 pytestmark = pytest.mark.gpu
 
-BUCKET = 60
-SPAN = 3600                  # an hour of seconds from T0 (which is not on a minute)
 MODES = [("svc", "labels"), ("pod", "labels")]
 FILTERS = {"svc": [dict(svc_port_name="shop/web:http"), dict()], "pod": [dict(pod_label="web"), dict()]}
-
-
-@pytest.fixture(scope="module")
-def table():
-    """test_gpu_stream_detection's table with flowEndSeconds at seconds, not minutes, and each row's arrival up to 150 s later"""
-    rng = np.random.default_rng(6000)
-    P = pods()
-    n = 6000
-    src, dst = rng.integers(0, 30, n), rng.integers(0, 30, n)
-    ext = rng.random(n) < 0.25
-    no_src = rng.random(n) < 0.05
-    sec = rng.integers(0, SPAN, n)
-    base = 100_000_000 * (1 + src % 7) + 30_000_000 * (dst % 5)
-    value = (base + rng.integers(0, 20_000_000, n)) * np.where((sec // 60) % 13 == 5, 9, 1)      # some minutes carry nine times the traffic
-    col = lambda idx, f, blank: np.where(blank, "", np.array([P[i][f] for i in idx]))
-    flows = {
-        "sourcePodNamespace": col(src, 0, no_src), "sourcePodName": col(src, 1, no_src), "sourcePodLabels": col(src, 2, no_src),
-        "destinationPodNamespace": col(dst, 0, ext), "destinationPodName": col(dst, 1, ext), "destinationPodLabels": col(dst, 2, ext),
-        "destinationIP": np.where(ext, np.array(IPS)[rng.integers(0, 5, n)], np.array(["10.0.0.%d" % i for i in dst])),
-        "destinationServicePortName": np.where(ext, "", np.array(SVCS)[rng.integers(0, 7, n)]),
-        "flowType": np.where(ext, 3, np.where(rng.random(n) < 0.5, 1, 2)).astype(np.int64),
-        "flowEndSeconds": (T0 + sec).astype(np.int64), "flowStartSeconds": (T0 + sec - 30).astype(np.int64),
-        "throughput": value.astype(np.uint64),
-    }
-    assert T0 % BUCKET != 0 and np.unique(flows["flowEndSeconds"] % BUCKET).size == BUCKET
-    arrival = flows["flowEndSeconds"] + rng.integers(0, 151, n)
-    return flows, arrival
 
 
 def floored(flows, before=None):

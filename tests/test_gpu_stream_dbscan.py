@@ -8,46 +8,9 @@ import pytest
 
 from oracle import tad_oracle as orc
 from theia_amd import TadEngine, TadError
+from state_helpers import SKIP, STATE_FIELDS, T_BASE, assert_rows, assert_same, bits, minute_batches, point_codes, restrict, rows_of, snapshot
 
 pytestmark = pytest.mark.gpu
-
-T_BASE = 1660202814
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
-STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
-SKIP = np.uint64((1 << 64) - 1)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
-
-
-def rows_of(res):
-    d = {f: res[f] for f in ROW_FIELDS}
-    if "anomaly" in res.to_host():
-        d["anomaly"] = res["anomaly"]
-    return d
-
-
-def point_codes(k, t, k2=None):
-    """(key, time) of the batch's points as one uint64 code (key << 32 | t - T_BASE + 2^31)"""
-    ks = [np.asarray(k, np.uint64)] + ([np.asarray(k2, np.uint64)] if k2 is not None else [])
-    tt = (np.asarray(t, np.int64) - T_BASE + (1 << 31)).astype(np.uint64)
-    out = [(kk[kk != SKIP] << np.uint64(32)) | tt[kk != SKIP] for kk in ks]
-    return np.unique(np.concatenate(out))
-
-
-def restrict(rows, codes):
-    c = (rows["key_id"].astype(np.uint64) << np.uint64(32)) | (rows["flow_end_s"] - T_BASE + (1 << 31)).astype(np.uint64)
-    sel = np.isin(c, codes)
-    return {f: a[sel] for f, a in rows.items()}
-
-
-def assert_rows(got, want, what=""):
-    assert set(got) == set(want), (what, sorted(got), sorted(want))
-    assert got["key_id"].size == want["key_id"].size, (what, got["key_id"].size, want["key_id"].size)
-    for f in want:
-        assert np.array_equal(bits(got[f]), bits(want[f])), (what, f)
 
 
 def batch_job_rows(engine, K, batches, upto, op, emit_all=False, eps=0.0, min_samples=0, pod=False):
@@ -82,14 +45,6 @@ def assert_history(st):
     off = np.concatenate([[0], np.cumsum(ln)]).astype(np.int64)
     for k in np.flatnonzero(ln > 1)[:2000]:
         assert (vals[off[k]:off[k + 1] - 1] <= vals[off[k] + 1:off[k + 1]]).all(), k
-
-
-def minute_batches(n_rows, K, T, cuts):
-    k, t, v = orc.synth_rows(0, n_rows, K, T)
-    bucket = (t - orc.SYNTH_T_BASE) // orc.SYNTH_T_STEP
-    edges = (0,) + tuple(cuts) + (T,)
-    return [(k[(bucket >= lo) & (bucket < hi)], t[(bucket >= lo) & (bucket < hi)], v[(bucket >= lo) & (bucket < hi)])
-            for lo, hi in zip(edges[:-1], edges[1:])]
 
 
 def second_batches(K, pts_per_key, rows_per_point, seed, span, width):
@@ -284,17 +239,6 @@ def test_ewma_batches_on_a_history_state(engine):
 
 
 # ---- 6. rejections leave everything untouched ----
-def snapshot(st):
-    s = st.export()
-    return s, st.export_history() if st.history else None
-
-
-def assert_unchanged(st, snap):
-    s, h = snapshot(st)
-    for f in STATE_FIELDS:
-        assert np.array_equal(bits(s[f]), bits(snap[0][f])), f
-    if h is not None:
-        assert np.array_equal(h[0], snap[1][0]) and np.array_equal(h[1], snap[1][1])
 
 
 def test_rejections(engine):
@@ -306,7 +250,7 @@ def test_rejections(engine):
     with pytest.raises(TadError) as ei:
         engine.run_stream(plain, *batches[1], agg_flow="svc", algo="DBSCAN")
     assert ei.value.code == -1
-    assert_unchanged(plain, snap)
+    assert_same(snapshot(plain), snap, "the state changed")
     with pytest.raises(TadError):
         plain.export_history()
     plain.close()
@@ -318,11 +262,11 @@ def test_rejections(engine):
         with pytest.raises(TadError) as ei:
             engine.run_stream(st, *batches[1], agg_flow="svc", algo=algo)
         assert ei.value.code == -1
-        assert_unchanged(st, snap)
+        assert_same(snapshot(st), snap, "the state changed")
     with pytest.raises(TadError) as ei:                                      # a late row (batch 0 again)
         engine.run_stream(st, *batches[0], agg_flow="svc", algo="DBSCAN")
     assert ei.value.code == -1
-    assert_unchanged(st, snap)
+    assert_same(snapshot(st), snap, "the state changed")
     got = engine.run_stream(st, *batches[1], agg_flow="svc", algo="DBSCAN")   # the state goes on as if nothing had happened
     assert_rows(rows_of(got), batch_job_rows(engine, K, batches, 1, "sum"))
     st.close()
@@ -346,7 +290,7 @@ def test_restart_and_growth(engine):
     with pytest.raises(TadError) as ei:
         fresh.load_history(bad_len, vals[:-1])
     assert ei.value.code == -1
-    assert_unchanged(fresh, snap)
+    assert_same(snapshot(fresh), snap, "the state changed")
     off = np.concatenate([[0], np.cumsum(ln)]).astype(np.int64)
     k = int(np.flatnonzero([vals[off[i]] != vals[off[i + 1] - 1] if ln[i] > 1 else False for i in range(K)])[0])
     unsorted = vals.copy()
@@ -354,7 +298,7 @@ def test_restart_and_growth(engine):
     with pytest.raises(TadError) as ei:
         fresh.load_history(ln, unsorted)
     assert ei.value.code == -1
-    assert_unchanged(fresh, snap)
+    assert_same(snapshot(fresh), snap, "the state changed")
     plain = engine.state_create(K)
     plain.load(moments)
     with pytest.raises(TadError) as ei:

@@ -4,7 +4,6 @@ fed in five shuffled batches to one StreamingAnomalyDetection per mode; every fi
 DBSCAN and ARIMA, is compared with anomaly_detection() over the concatenated table with the same arguments: rows sorted by the decoded key
 columns and time, every field equal, floats by their bits; the sentinel row without flowStartSeconds.  One drop case:
 PeriodicalDropDetection.window(direction=..., namespace=...) equals window() filtered on the host."""
-import struct
 import time
 
 import numpy as np
@@ -13,30 +12,12 @@ import pytest
 from theia_amd import anomaly_detection as ad
 from theia_amd import drop_detection as dd
 from theia_amd.stream_detection import StreamingAnomalyDetection
+from stream_helpers import IGNORE, IPS, N_STEPS, STEP, SVCS, T0, batches, comparable, keyed, pods
 
 pytestmark = pytest.mark.gpu
 
-T0 = 1660202800
-STEP = 60
-N_STEPS = 60
-NAMESPACES = ("shop", "blog", "infra", "kube-system")
-IGNORE = ("kube-system",)
-SVCS = ["", "shop/web:http", "shop/db:pg", "blog/web:http", "infra/dns:udp", "infra/log:tcp", "blog/cache:mc"]
-IPS = ["52.1.0.%d" % i for i in range(5)]
 ALGOS = ("EWMA", "DBSCAN", "ARIMA")
 END = time.strftime(ad.TIME_FORMAT, time.gmtime(T0 + 45 * STEP))
-
-
-def pods():
-    """30 pods: (namespace, name, labels).  web-0 exists in two namespaces; labels carry keys the result drops"""
-    out = []
-    for i in range(30):
-        ns = NAMESPACES[i % 4]
-        app = ("web", "db", "cache", "Web-Front", "dns")[i % 5]
-        name = "%s-%d" % (app.lower(), i // 20)
-        labels = '{"app":"%s","pod-template-hash":"h%d","tier":"t%d"}' % (app, i, i % 3)
-        out.append((ns, name, labels))
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -62,30 +43,6 @@ def table():
         "throughput": value.astype(np.uint64),
     }
     return flows
-
-
-def batches(flows, parts=5, seed=7):
-    n = len(flows["flowEndSeconds"])
-    part = np.random.default_rng(seed).integers(0, parts, n)
-    for p in np.random.default_rng(seed + 1).permutation(parts):
-        rows = np.random.default_rng(seed + 2 + p).permutation(np.flatnonzero(part == p))
-        yield {k: v[rows] for k, v in flows.items()}
-
-
-def f64_bits(x):
-    return struct.pack("<d", float(x)).hex()
-
-
-def comparable(rows, mode):
-    """result rows -> sorted tuples; floats as bit patterns; the sentinel row without its flowStartSeconds (the time it was made)"""
-    out = []
-    for r in rows:
-        r = dict(r)
-        if r.get("anomaly") == "NO ANOMALY DETECTED":
-            r.pop("flowStartSeconds")
-        out.append(tuple((k, f64_bits(v) if isinstance(v, float) else v) for k, v in sorted(r.items())))
-    key = lambda t: tuple(str(dict(t).get(c)) for c in ad.KEY_COLUMNS[mode]) + (dict(t)["flowEndSeconds"],)
-    return sorted(out, key=key)
 
 
 # mode, pod_ident -> the filters of the mode as keyword arguments of both calls
@@ -186,10 +143,6 @@ def drop_flows():
         c[side + "_pod_ns"] = np.where(mine & pod, ep % 3, zeros).astype(np.int64)
         c[side + "_pod_name"] = np.where(mine & pod, 1 + ep, zeros).astype(np.int64)
     return c, d
-
-
-def keyed(rows):
-    return sorted((r[3], r[4], float(r[5]).hex(), float(r[6]).hex(), str(r[7]), int(r[8])) for r in rows)
 
 
 def test_drop_window_by_direction_and_namespace(engine):

@@ -3,7 +3,6 @@ answers its jobs as anomaly_detection() does over the table with every row ONCE.
 to three steps late; eight polls each re-read everything that has arrived in [watermark - lag, now).  Every row is read two or three
 times; the default feed would double or triple its throughput under the modes' sum.  Half-way the instance is snapshotted, closed and
 restored, watermark included."""
-import re
 
 import numpy as np
 import pytest
@@ -11,64 +10,9 @@ import pytest
 from theia_amd import anomaly_detection as ad
 from theia_amd import clickhouse as ch
 from theia_amd.stream_detection import StreamingAnomalyDetection
-
-from test_gpu_stream_detection import IGNORE, IPS, N_STEPS, STEP, SVCS, T0, comparable, pods
+from stream_helpers import IGNORE, LAG, MODES, STEP, T0, TableClient, comparable, replace_table, turns  # noqa: F401  (replace_table: the fixture `table`)
 
 pytestmark = pytest.mark.gpu
-
-LAG = 4 * STEP
-MODES = [("svc", "labels"), ("pod", "labels"), ("pod", "name")]
-
-
-@pytest.fixture(scope="module")
-def table():
-    """test_gpu_stream_detection's table at 5000 rows, and each row's arrival time: up to three steps after its flowEndSeconds"""
-    rng = np.random.default_rng(5000)
-    P = pods()
-    n = 5000
-    src, dst = rng.integers(0, 30, n), rng.integers(0, 30, n)
-    ext = rng.random(n) < 0.25
-    no_src = rng.random(n) < 0.05
-    step = rng.integers(0, N_STEPS, n)
-    base = 1_000_000_000 * (1 + src % 7) + 300_000_000 * (dst % 5)
-    value = (base + rng.integers(0, 200_000_000, n)) * np.where(rng.random(n) < 0.04, 9, 1)
-    col = lambda idx, f, blank: np.where(blank, "", np.array([P[i][f] for i in idx]))
-    flows = {
-        "sourcePodNamespace": col(src, 0, no_src), "sourcePodName": col(src, 1, no_src), "sourcePodLabels": col(src, 2, no_src),
-        "destinationPodNamespace": col(dst, 0, ext), "destinationPodName": col(dst, 1, ext), "destinationPodLabels": col(dst, 2, ext),
-        "destinationIP": np.where(ext, np.array(IPS)[rng.integers(0, 5, n)], np.array(["10.0.0.%d" % i for i in dst])),
-        "destinationServicePortName": np.where(ext, "", np.array(SVCS)[rng.integers(0, 7, n)]),
-        "flowType": np.where(ext, 3, np.where(rng.random(n) < 0.5, 1, 2)).astype(np.int64),
-        "flowEndSeconds": (T0 + STEP * step).astype(np.int64), "flowStartSeconds": (T0 + STEP * step - 30).astype(np.int64),
-        "throughput": value.astype(np.uint64),
-    }
-    arrival = flows["flowEndSeconds"] + rng.integers(0, 3 * STEP + 1, n)
-    return flows, arrival
-
-
-class TableClient:
-    """what poll needs of a ClickHouseHTTP: query_columns(sql) answered from the table — the rows that have arrived by `self.now` inside
-    the range the SQL names (the row predicates are left to the feed, which applies them again)"""
-
-    def __init__(self, flows, arrival):
-        self.flows, self.arrival, self.now, self.queries = flows, arrival, 0, []
-
-    def query_columns(self, sql, dict_strings=False, **kw):
-        self.queries.append(sql)
-        lo = re.search(r"flowEndSeconds >= toDateTime\((\d+)\)", sql)
-        hi = re.search(r"flowEndSeconds < toDateTime\((\d+)\)", sql)
-        t = self.flows["flowEndSeconds"]
-        sel = (self.arrival <= self.now) & (t < int(hi.group(1)))
-        if lo:
-            sel &= t >= int(lo.group(1))
-        rows = np.random.default_rng(len(self.queries)).permutation(np.flatnonzero(sel))
-        names = sql[len("SELECT "):sql.index(" FROM ")].split(", ")
-        return {c: self.flows[c][rows] for c in names} if rows.size else {}
-
-
-def turns():
-    """the `now` of the eight polls: every 8 steps, the last one late enough for every row to have arrived"""
-    return [T0 + STEP * 8 * (p + 1) + (3 * STEP + 1 if p == 7 else 0) for p in range(8)]
 
 
 @pytest.mark.parametrize("mode,ident", MODES, ids=["svc", "pod-labels", "pod-name"])

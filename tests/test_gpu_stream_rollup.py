@@ -10,15 +10,11 @@ import numpy as np
 import pytest
 
 from theia_amd.stream_detection import StreamingAnomalyDetection
-
-from test_gpu_state_keys import assert_same, snapshot
-from test_gpu_stream_buckets import SPAN, table  # noqa: F401  (the fixture)
-from test_gpu_stream_detection import IGNORE, SVCS, T0, batches, comparable
-from test_gpu_stream_replace import TableClient
+from state_helpers import assert_same, snapshot
+from stream_helpers import BUCKET, IGNORE, SPAN, SVCS, T0, TableClient, batches, comparable, seconds_table  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-BUCKET = 60
 BOUND = ((T0 + 40 * 60) // BUCKET) * BUCKET
 
 

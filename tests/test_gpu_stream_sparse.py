@@ -9,12 +9,10 @@ import pytest
 from oracle import stream_oracle as so
 from oracle import tad_oracle as orc
 from theia_amd import TadEngine, TadError
+from state_helpers import ROW_FIELDS, STATE_FIELDS, T_BASE
 
 pytestmark = pytest.mark.gpu
 
-T_BASE = 1660202814
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
-STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
 PLANS = ({"sparse": "never"}, {"sparse": "always", "sparse_sort": "lsd"}, {"sparse": "always", "sparse_sort": "partition", "stage0": "v2"})
 
 
@@ -44,7 +42,7 @@ def oracle_batches(K, batches, op="sum"):
     return rows, ost
 
 
-def assert_rows(got, want, what=""):
+def assert_result_rows(got, want, what=""):
     assert got.n_rows == want["key_id"].size, (what, got.n_rows, want["key_id"].size)
     for f in ROW_FIELDS:
         assert (got[f] == want[f]).all(), (what, f)
@@ -98,7 +96,7 @@ def test_day_in_hourly_batches(engine, day):
         assert got.stats["stage0_path"] in (4, 8), (h, got.stats["stage0_path"])
         assert got.stats["step"] == 1 and got.stats["t0"] == bt.min() and got.stats["n_buckets"] == bt.max() - bt.min() + 1
         assert got.stats["n_points"] == np.unique(np.stack([bk.astype(np.int64), bt]), axis=1).shape[1]
-        assert_rows(got, w, h)
+        assert_result_rows(got, w, h)
     state = st.export()
     st.close()
     assert_state(state, ost)
@@ -115,7 +113,7 @@ def test_whole_day_batch_where_the_dense_grid_does_not_fit(day):
         st = eng.state_create(K)
         got = eng.run_stream(st, k, t, v, agg_flow="svc")
         assert got.stats["stage0_path"] in (4, 8)
-        assert_rows(got, want)
+        assert_result_rows(got, want)
         assert_state(st.export(), want_state)
         st.close()
     finally:
@@ -134,7 +132,7 @@ def test_forced_forms_agree_on_second_batches(engine):
             res, state = stream_all(engine, K, batches)
         for h, (r, w) in enumerate(zip(res, want)):
             assert r.stats["stage0_path"] in paths, (plan, h, r.stats["stage0_path"])
-            assert_rows(r, w, (plan, h))
+            assert_result_rows(r, w, (plan, h))
         assert_state(state, ost)
         outs.append(state)
     for f in STATE_FIELDS:
@@ -185,7 +183,7 @@ def test_skewed_lengths_take_no_length_classes():
         for (bk, bt, bv), w in zip([(k0, t0, v0), (k, t, v)], want):
             got = eng.run_stream(st, bk, bt, bv, agg_flow="svc")
             assert got.stats["stage0_path"] in (4, 8)
-            assert_rows(got, w)
+            assert_result_rows(got, w)
         assert_state(st.export(), ost)
         st.close()
     finally:
@@ -201,7 +199,7 @@ def test_big_batch_takes_the_partition_path_unforced(engine):
     st = engine.state_create(K)
     got = engine.run_stream(st, k, t, v, agg_flow="svc")
     assert got.stats["stage0_path"] == 8
-    assert_rows(got, want[0])
+    assert_result_rows(got, want[0])
     assert_state(st.export(), ost)
     st.close()
 
@@ -220,7 +218,7 @@ def test_pod_mode_two_keys_per_row(engine, plan):
         for s, w in zip(sel, want):
             got = engine.run_stream(st, k[s], t[s], v[s], agg_flow="pod", key_id2=k2[s])
             assert got.stats["stage0_path"] in (4, 8)
-            assert_rows(got, w)
+            assert_result_rows(got, w)
         assert_state(st.export(), ost)
         st.close()
 
@@ -264,7 +262,7 @@ def test_late_first_point_rejected_state_kept(engine, plan):
         assert got.stats["stage0_path"] in (4, 8)
         st.close()
     want, _ = oracle_batches(K, [(k[b == 0], t[b == 0], v[b == 0]), (bk, bt, bv)])
-    assert_rows(got, want[1])
+    assert_result_rows(got, want[1])
 
 
 def test_resize_as_keys_appear(engine):
@@ -287,7 +285,7 @@ def test_resize_as_keys_appear(engine):
                     engine.run_stream(st, bk[:0], bt[:0], bv[:0], agg_flow="svc", num_keys=old)
                 assert ei.value.code == -1 and "must be equal" in ei.value.message
             got = engine.run_stream(st, bk, bt, bv, agg_flow="svc")
-            assert_rows(got, w, h)
+            assert_result_rows(got, w, h)
         assert st.num_keys == K
         before = st.export()
         with pytest.raises(TadError) as ei:                                      # a state never shrinks
@@ -305,7 +303,7 @@ def test_export_import_round_trip(day):
     eng = TadEngine(device=0)
     st = eng.state_create(K)
     for (bk, bt, bv), w in zip(batches[:12], want[:12]):
-        assert_rows(eng.run_stream(st, bk, bt, bv, agg_flow="svc"), w)
+        assert_result_rows(eng.run_stream(st, bk, bt, bv, agg_flow="svc"), w)
     saved = st.export()
     st.close()
     eng.close()
@@ -315,7 +313,7 @@ def test_export_import_round_trip(day):
         st.load(saved)
         assert all((st.export()[f] == saved[f]).all() for f in STATE_FIELDS)
         for (bk, bt, bv), w in zip(batches[12:], want[12:]):
-            assert_rows(eng.run_stream(st, bk, bt, bv, agg_flow="svc"), w)
+            assert_result_rows(eng.run_stream(st, bk, bt, bv, agg_flow="svc"), w)
         assert_state(st.export(), ost)
         st.close()
     finally:
@@ -346,6 +344,6 @@ def test_imported_unseen_keys(engine):
         getattr(fresh, f)[~odd] = saved[f][~odd]
     fresh.seen[:] = fresh.n > 0
     w = so.run_stream(fresh, *batches[1], "sum")
-    assert_rows(engine.run_stream(st, *batches[1], agg_flow="svc"), w)
+    assert_result_rows(engine.run_stream(st, *batches[1], agg_flow="svc"), w)
     assert_state(st.export(), fresh)
     st.close()

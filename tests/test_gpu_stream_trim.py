@@ -9,69 +9,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from oracle import tad_oracle as orc
 from theia_amd import TadError, _capi
+from state_helpers import (ALL, HIST, SER, SKIP, TIMES, T_BASE, assert_rows, assert_same, minute_batches, new_state, point_codes, restrict, rows_of,
+                           second_batches, snapshot)
 
 pytestmark = pytest.mark.gpu
-
-T_BASE = 1660202814
-ROW_FIELDS = ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")
-STATE_FIELDS = ("n", "avg", "m2", "ewma", "last_t")
-SKIP = np.uint64((1 << 64) - 1)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype.itemsize == 8 else a
-
-
-def rows_of(res):
-    d = {f: np.asarray(res[f]) for f in ROW_FIELDS}
-    if "anomaly" in res.to_host():
-        d["anomaly"] = np.asarray(res["anomaly"])
-    return d
-
-
-def point_codes(k, t, k2=None):
-    ks = [np.asarray(k, np.uint64)] + ([np.asarray(k2, np.uint64)] if k2 is not None else [])
-    tt = (np.asarray(t, np.int64) - T_BASE + (1 << 31)).astype(np.uint64)
-    return np.unique(np.concatenate([(kk[kk != SKIP] << np.uint64(32)) | tt[kk != SKIP] for kk in ks]))
-
-
-def restrict(rows, codes):
-    c = (rows["key_id"].astype(np.uint64) << np.uint64(32)) | (rows["flow_end_s"].astype(np.int64) - T_BASE + (1 << 31)).astype(np.uint64)
-    sel = np.isin(c, codes)
-    return {f: a[sel] for f, a in rows.items()}
-
-
-def assert_rows(got, want, what=""):
-    assert set(got) == set(want), (what, sorted(got), sorted(want))
-    assert got["key_id"].size == want["key_id"].size, (what, got["key_id"].size, want["key_id"].size)
-    for f in want:
-        assert np.array_equal(bits(got[f]), bits(want[f])), (what, f)
-
-
-HIST, SER, TIMES = 1, 2, 8     # TAD_STATE_HISTORY, TAD_STATE_SERIES, TAD_STATE_TIMES
-ALL = HIST | SER | TIMES
-
-
-def new_state(engine, K, flags=ALL):
-    return engine.state_create(K, history=bool(flags & HIST), series=bool(flags & SER), times=bool(flags & TIMES))
-
-
-def snapshot(st):
-    return {"state": st.export(), "history": st.export_history() if st.history else None,
-            "series": st.export_series() if st.series else None, "times": st.export_times() if st.times else None}
-
-
-def assert_same(a, b, what=""):
-    for f in STATE_FIELDS:
-        assert np.array_equal(bits(a["state"][f]), bits(b["state"][f])), (what, f)
-    for part in ("history", "series"):
-        if a[part] is not None or b[part] is not None:
-            assert np.array_equal(a[part][0], b[part][0]) and np.array_equal(a[part][1], b[part][1]), (what, part)
-    if a["times"] is not None or b["times"] is not None:
-        assert np.array_equal(a["times"], b["times"]), (what, "times")
 
 
 def retained(st, keep_points=0, keep_from=0):
@@ -97,39 +39,6 @@ def fresh(engine, K, pts, op, flags=ALL, alpha=0.0):
     if pts[0].size:
         engine.run_stream(st, pts[0], pts[1], pts[2], agg_flow="svc", value_op=op, alpha=alpha)
     return st
-
-
-def minute_batches(n_rows, K, T, cuts, pod=False):
-    k, t, v = orc.synth_rows(0, n_rows, K, T)
-    bucket = (t - orc.SYNTH_T_BASE) // orc.SYNTH_T_STEP
-    edges = (0,) + tuple(cuts) + (T,)
-    k2 = ((k + np.uint64(7)) % np.uint64(K)).astype(np.uint64)
-    out = []
-    for lo, hi in zip(edges[:-1], edges[1:]):
-        sel = (bucket >= lo) & (bucket < hi)
-        out.append((k[sel], t[sel], v[sel]) + ((k2[sel],) if pod else ()))
-    return out
-
-
-def second_batches(K, n_batches, width, pts_per_batch, seed, lifetimes=False):
-    """second-resolution rows (two per point) in batches of `width` seconds; every key has exactly pts_per_batch points in every batch
-    it is alive in.  lifetimes: a third of the keys only in the first half, a third only in the last batches, the rest throughout."""
-    rng = np.random.default_rng(seed)
-    out = []
-    base = 1_000_000_000 + (orc.mix64(np.arange(K, dtype=np.uint64) + np.uint64(5)) % np.uint64(3_000_000_000)).astype(np.int64)
-    for b in range(n_batches):
-        alive = np.ones(K, bool)
-        if lifetimes:
-            g = np.arange(K) % 3
-            alive = (g == 2) | ((g == 0) & (b < n_batches // 2)) | ((g == 1) & (b >= n_batches - 2))
-        ks = np.nonzero(alive)[0].astype(np.uint64)
-        pk = np.repeat(ks, pts_per_batch)
-        pt = np.concatenate([np.sort(rng.choice(width, pts_per_batch, replace=False)) for _ in ks]).astype(np.int64) + T_BASE + b * width
-        k, t = np.repeat(pk, 2), np.repeat(pt, 2)
-        v = (np.repeat(base[pk.astype(np.int64)], 2) + rng.integers(-300_000_000, 300_000_000, size=k.size)).astype(np.uint64)
-        order = rng.permutation(k.size)
-        out.append((k[order], t[order], v[order]))
-    return out
 
 
 def check_trim(engine, st, K, op, keep_points=0, keep_from=0, alpha=0.0):

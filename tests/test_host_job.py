@@ -9,45 +9,8 @@ import numpy as np
 import pytest
 
 from oracle import job_oracle as jo
-from oracle import tad_oracle as orc
 from theia_amd import anomaly_detection as ad
-
-CASES = [
-    dict(agg_flow=""),
-    dict(agg_flow="", start_time="2022-08-11 07:30:00", end_time="2022-08-11 08:00:00"),
-    dict(agg_flow="", ns_ignore_list=["kube-system"]),
-    dict(agg_flow="svc"),
-    dict(agg_flow="svc", svc_port_name="svc-1:http", end_time="2022-08-11 08:00:00"),
-    dict(agg_flow="external"),
-    dict(agg_flow="external", external_ip="52.1.1.2"),
-    dict(agg_flow="pod"),
-    dict(agg_flow="pod", pod_label="APP1"),                       # ilike: case-insensitive
-    dict(agg_flow="pod", pod_label="app_", pod_namespace="default"),   # '_' is a LIKE wildcard
-    dict(agg_flow="pod", pod_name="pod-2"),
-    dict(agg_flow="pod", pod_name="pod-2", pod_namespace="flow-visibility", ns_ignore_list=["kube-system"]),
-    dict(agg_flow="pod", pod_name="pod-1", start_time="2022-08-11 07:50:00"),  # pod SQL ignores the time window
-]
-
-
-class FakeResult:
-    """Shaped like theia_amd.engine.TadResult, filled from the key-id oracle."""
-
-    def __init__(self, want):
-        self.n_rows = want["n_anomalies"]
-        self._h = {k: want[k] for k in ("key_id", "flow_end_s", "throughput", "algo_calc", "stddev")}
-        self.stats = {}
-
-    def to_host(self):
-        return self._h
-
-
-def canon(rows):
-    return sorted(json.dumps(r, sort_keys=True) for r in rows)
-
-
-def oracle_middle(prep, algo, agg_flow):
-    return orc.run_job(algo, prep.key_id, prep.flow_end_s, prep.value, agg_flow=agg_flow, key_id2=prep.key_id2,
-                       flow_start_s=prep.flow_start_s, start_time=prep.start_time, end_time=prep.end_time)
+from job_helpers import CASES, FakeResult, canon, oracle_middle
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join("%s=%s" % kv for kv in c.items()))

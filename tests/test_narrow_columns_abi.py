@@ -6,16 +6,9 @@ import re
 
 import numpy as np
 import pytest
+from job_helpers import HEADER, ROOT, header_define
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "tad.h")).read()
 GO = open(os.path.join(ROOT, "go", "tadengine", "tadengine.go")).read()
-
-
-def header_define(name):
-    m = re.search(r"#define %s\s+(\S+)" % name, HEADER)
-    assert m, name
-    return m.group(1)
 
 
 def test_header_defines_the_flags_the_sentinel_and_the_feature_query():

@@ -136,8 +136,8 @@ def test_e2e_result_map_on_the_engine(engine, golden, algo, agg_type):
     getTADetectorResult does, and check per row the field count of the aggregation type, the verdict and the throughput prefix — here through
     ClickHouse's HTTP interface (in-process), the controller, `tad_run` on the GPU, the INSERT, the handler's SELECT and Go's string forms."""
     from theia_amd import clickhouse as ch
-    from test_clickhouse_http import FakeClickHouse, arrow_table
-    from test_gpu_job import e2e_flows
+    from fake_clickhouse import FakeClickHouse, arrow_table
+    from job_helpers import e2e_flows
     spec = {"None": {}, "podName": dict(aggFlow="pod", podName="test_podName"), "podLabel": dict(aggFlow="pod", podLabel="test_key"),
             "external": dict(aggFlow="external"), "svc": dict(aggFlow="svc")}[agg_type]
     server = FakeClickHouse()

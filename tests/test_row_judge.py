@@ -7,8 +7,7 @@ import os
 import subprocess
 
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from job_helpers import ROOT
 
 PROGRAM = r"""
 #include <cstdio>

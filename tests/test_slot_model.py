@@ -5,7 +5,7 @@ import pytest
 
 import slot_model as sm
 from slot_model import Strings, Tuples
-from test_gpu_strdict import hash8
+from job_helpers import hash8
 
 U64 = np.uint64
 

@@ -8,9 +8,8 @@ import subprocess
 
 import numpy as np
 import pytest
+from job_helpers import HEADER, ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "tad.h")).read()
 CODE = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
 MERGE_ARGS = ["tad_engine *e", "tad_state *s", "const tad_job *job", "const tad_columns *cols", "int64_t keep_from_t", "tad_merge_stats *stats",
               "tad_changes *ch"]

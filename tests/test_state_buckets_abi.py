@@ -9,9 +9,8 @@ import re
 import subprocess
 
 import pytest
+from job_helpers import HEADER, ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "tad.h")).read()
 CODE = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
 ARGS = ["tad_engine *e", "tad_state *s", "const tad_job *job", "const tad_bucket_window *w", "tad_mem out_memory", "tad_result **out"]
 FIELDS = ["from_t", "to_t", "keep_points", "key_keep", "key_since", "since_t", "num_keys", "key_memory", "bucket_s", "bucket_origin", "bucket_op"]

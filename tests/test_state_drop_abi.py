@@ -7,9 +7,8 @@ import os
 import re
 
 import pytest
+from job_helpers import HEADER, ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "tad.h")).read()
 GO = open(os.path.join(ROOT, "go", "tadengine", "tadengine.go")).read()
 CODE = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
 

@@ -8,6 +8,7 @@ from oracle import stream_oracle as sorc
 from oracle import tad_oracle as orc
 
 import state_model as sm
+from state_helpers import ROW_FIELDS
 
 U64, I64 = np.uint64, np.int64
 
@@ -110,7 +111,7 @@ def test_the_emit_all_stream_rows_hold_the_stream_oracles_rows(scripts):
                 every = model.ewma_stream_rows(before, *pts, True)
                 some = model.ewma_stream_rows(before, *pts, False)
                 a = every["anomaly"].astype(bool)
-                for f in sm.ROW_FIELDS:
+                for f in ROW_FIELDS:
                     assert np.array_equal(every[f][a].view(U64), some[f].view(U64)), f
                 st = sorc.StreamState(model.num_keys)
                 for f in sm.STATE_FIELDS:

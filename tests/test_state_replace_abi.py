@@ -11,11 +11,9 @@ import numpy as np
 import pytest
 
 from theia_amd import clickhouse as ch
+from fake_clickhouse import arrow_table, server  # noqa: F401  (server: the fixture)
+from job_helpers import HEADER, ROOT
 
-from test_clickhouse_http import FakeClickHouse, arrow_table
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "tad.h")).read()
 CODE = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
 ARGS = ["tad_engine *e", "tad_state *s", "const tad_job *job", "const tad_columns *cols", "uint32_t flags", "int64_t from_t", "int64_t to_t",
         "int64_t keep_from_t", "tad_replace_stats *stats"]
@@ -175,11 +173,6 @@ def test_stream_rows_query_for_each_mode():
 
 
 # ---- the poll loop against the ClickHouse stand-in ----
-@pytest.fixture()
-def server():
-    s = FakeClickHouse()
-    yield s
-    s.close()
 
 
 def _instance(mode, ident="labels", ignore=()):

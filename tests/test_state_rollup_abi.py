@@ -9,9 +9,8 @@ import re
 import subprocess
 
 import pytest
+from job_helpers import HEADER, ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "tad.h")).read()
 CODE = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
 ARGS = ["tad_engine *e", "tad_state *s", "int64_t before_t", "int64_t bucket_s", "int64_t bucket_origin", "tad_value_op bucket_op", "double ewma_alpha",
         "tad_rollup_stats *stats"]

@@ -5,17 +5,10 @@ import ctypes
 import inspect
 import os
 import re
+from job_helpers import HEADER, ROOT, header_define
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "tad.h")).read()
 GO = open(os.path.join(ROOT, "go", "tadengine", "tadengine.go")).read()
 NEW = ("tad_state_series_points", "tad_state_export_series", "tad_state_import_series")
-
-
-def header_define(name):
-    m = re.search(r"#define %s\s+(\S+)" % name, HEADER)
-    assert m, name
-    return m.group(1)
 
 
 def test_header_defines_the_bits_and_declares_the_calls():

@@ -6,8 +6,8 @@ import re
 
 from theia_amd import _capi
 from theia_amd.engine import TadState
+from job_helpers import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("tad_state_resize", "tad_state_import")
 
 

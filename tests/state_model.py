@@ -8,7 +8,7 @@ make_script(seed) draws a list of operations with every argument fixed and every
 script can be built, inspected and replayed without a device.  tests/test_state_model.py checks the model and the seed set on the host,
 tests/test_gpu_state_sequences.py runs the scripts on a state and compares after every operation.
 
-Not covered, on purpose: the dictionaries (tad_keydict / tad_strdict: tests/test_gpu_key_retire.py runs them end to end), pod-mode
+Not covered here: the dictionaries (tad_keydict / tad_strdict: tests/dict_model.py holds their model and their scripts), pod-mode
 key_id2 batches, concurrent calls on one state, workspace-limit refusals."""
 import numpy as np
 
